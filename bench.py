@@ -15,6 +15,9 @@ Also printed on the same JSON line:
                  steps (ir_profile_begin/end), algorithmic FLOPs / time vs the dense bf16 MFMA peak (2.5 PFLOP/s);
   cpu_baseline : the oracle (CPU fp32 restatement of the reference, kind "port") timed on this box's host cores on a
                  bounded sample (one 512x512 network pass), extrapolated to the 2048x2048 workload by algorithmic FLOPs.
+
+--dump-outputs DIR writes what the last timed step returned (the uint8 images, as float32) to DIR/pred.npy, so that two builds can be
+compared output for output: inputs and weights are seeded, identical from run to run.
 """
 import argparse
 import json
@@ -277,6 +280,25 @@ def cli_files_leg(k, sds, value, log):
         shutil.rmtree(d, ignore_errors=True)
 
 
+DUMP_BUDGET_BYTES = 64_000_000
+
+
+def dump_outputs(d, arrays, log):
+    """--dump-outputs: every array as d/<name>.npy in float32, so that two builds can be compared output for output on the same seeded inputs.
+    Their total stays within DUMP_BUDGET_BYTES: above it, each array is replaced by the same fixed sample of its flattened elements (a sorted,
+    seed-0 choice of indices that depends on the array's size only) and written as d/<name>_sample.npy."""
+    os.makedirs(d, exist_ok=True)
+    total = sum(a.size for a in arrays.values()) * 4
+    for name, a in arrays.items():
+        if total > DUMP_BUDGET_BYTES:
+            k = int(a.size * (DUMP_BUDGET_BYTES - 4096 * len(arrays)) // total)
+            idx = np.sort(np.random.default_rng(0).choice(a.size, size=k, replace=False))
+            a, name = a.reshape(-1)[idx], name + "_sample"
+        a = np.ascontiguousarray(a, dtype=np.float32)
+        np.save(os.path.join(d, name + ".npy"), a)
+        log(f"dumped {name}.npy {tuple(a.shape)} float32 to {d}")
+
+
 def self_launch(n_ranks):
     """Run this script as n_ranks child processes under torch.distributed.run (one rank per GPU) and return the exit code."""
     import socket
@@ -312,7 +334,7 @@ def main():
                     "(COPIES copied blocks, 13 in the reference configs; c = the LQ latent). Not the headline workload: no such weights are released")
     ap.add_argument("--graph", action="store_true", help="diagnostic: replay the step as one hipGraph (IR_FLAG_GRAPH); implies --no_profile, "
                     "so the JSON line carries no roofline")
-    ap.add_argument("--profile_all", action="store_true", help="one pass: every launch of the timed loop bracketed by events (the form before round 4; costs about 1.4 %)")
+    ap.add_argument("--profile_all", action="store_true", help="one pass: every launch of the timed loop bracketed by events (the form before round 4; costs about 1.4 %%)")
     ap.add_argument("--no_profile", action="store_true", help="experiment: time the loop without the per-launch HIP events (no roofline)")
     ap.add_argument("--no_verify", action="store_true", help="skip the fast-vs-plain-kernel check of the last timed output")
     ap.add_argument("--no_host_rate", action="store_true", help="skip the host-buffer (PCIe-inclusive) rates")
@@ -323,7 +345,12 @@ def main():
     ap.add_argument("--cli_files", type=int, default=96, metavar="K", help="after the timed steps (N = 1, headline workload only): write K synthetic 512 x 512 PNGs and "
                     "the full-size artefacts, run `inference.py --sr_scale 4` on them as a fresh child process and report its files/s beside `value` (0 = skip)")
     ap.add_argument("--fp8", action="store_true", help="BASELINE configs[4]: fp8 (e4m3) MFMA operands in the parts ir_fp8_features() reports (the JSON line names them)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="after the timed steps: write what the last timed step returned to its caller (the "
+                    "uint8 images of ir_pipeline; with N > 1 the images gathered on rank 0) as DIR/pred.npy in float32, for output-for-output comparison "
+                    "of two builds (inputs and weights are seeded; above 64 MB a fixed seeded sample, DIR/pred_sample.npy)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     from instarevive_amd import parallel
     rank, world, local = parallel.env_rank_world()
@@ -481,6 +508,8 @@ def main():
         step()
     barrier()
     dt = time.perf_counter() - t0
+    if args.dump_outputs and rank == 0:   # outside the timed region, before any later pass reuses dout
+        dump_outputs(args.dump_outputs, {"pred": (gathered[0] if gathered[0] is not None else dout).cpu().numpy()}, log)
     power = None
     if sampler is not None:   # what the card's clock and socket power were DURING the timed loop (hwmon samples every 20 ms)
         from tools.power_sampler import summarise

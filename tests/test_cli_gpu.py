@@ -318,3 +318,24 @@ def test_bench_multi_gpu_branch_through_rccl_on_one_rank():
           f"RCCL {line.get('rccl_version')}")
     assert line["n_gpus"] == 1 and line["verified"] is True and line["gathered_images"] == 1 and line["world_size"] == 1
     assert line["rccl_version"] not in (None, "gloo") and 100.0 < line["ms_per_step"] < 200.0
+
+
+def test_bench_dump_outputs_and_steps(tmp_path):
+    """bench.py --dump-outputs DIR on a small workload (128 x 128 LQ, sr_scale 2): DIR/pred.npy holds the last timed step's uint8 images as float32,
+    --steps sets the number of timed steps the line reports, and two runs with different step counts dump identical outputs (seeded inputs and
+    weights, a deterministic path)."""
+    env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
+    preds = []
+    for k in (1, 3):
+        d = tmp_path / f"steps{k}"
+        cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--lq", "128", "--sr_scale", "2", "--steps", str(k), "--warmup", "1", "--no_cpu_baseline",
+               "--no_host_rate", "--no_verify", "--cli_files", "0", "--dump-outputs", str(d)]
+        r = subprocess.run(cmd, capture_output=True, text=True, timeout=900, cwd=ROOT, env=env)
+        assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-3000:]
+        line = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1])
+        assert line["steps"] == k and line["ms_per_step"] > 0
+        assert sorted(os.listdir(d)) == ["pred.npy"]
+        p = np.load(d / "pred.npy")
+        assert p.dtype == np.float32 and p.shape == (1, 256, 256, 3) and p.min() >= 0 and p.max() <= 255 and np.array_equal(p, np.round(p)) and p.std() > 1.0
+        preds.append(p)
+    assert np.array_equal(preds[0], preds[1])

@@ -738,3 +738,25 @@ def test_bench_helpers_of_round_5(tmp_path, monkeypatch):
     torch.testing.assert_close(out["vae"]["decoder.mid_block.attentions.0.to_q.weight"], vae["decoder.mid_block.attentions.0.to_q.weight"] * 3.0)
     assert torch.equal(out["vae"]["decoder.conv_out.weight"], vae["decoder.conv_out.weight"])
     assert int(((out["vae"]["decoder.up_blocks.0.resnets.0.conv1.bias"] / vae["decoder.up_blocks.0.resnets.0.conv1.bias"]) > 29).sum()) == 1
+
+
+def test_bench_dump_outputs_helper(tmp_path, monkeypatch):
+    """bench.py --dump-outputs without a GPU: an output within the budget is written whole as float32 with its values exact; above the budget
+    the same seeded sample of its flattened elements is written on every call, within the budget; --steps 0 is refused before any work."""
+    import importlib
+    sys.path.insert(0, ROOT)
+    bench = importlib.import_module("bench")
+    a = np.random.default_rng(3).integers(0, 256, (1, 64, 96, 3), dtype=np.uint8)
+    bench.dump_outputs(str(tmp_path / "whole"), {"pred": a}, lambda m: None)
+    got = np.load(tmp_path / "whole" / "pred.npy")
+    assert got.dtype == np.float32 and got.shape == a.shape and np.array_equal(got, a)
+    monkeypatch.setattr(bench, "DUMP_BUDGET_BYTES", 40_000)
+    for d in ("s1", "s2"):
+        bench.dump_outputs(str(tmp_path / d), {"pred": a}, lambda m: None)
+    s1, s2 = np.load(tmp_path / "s1" / "pred_sample.npy"), np.load(tmp_path / "s2" / "pred_sample.npy")
+    assert s1.dtype == np.float32 and s1.ndim == 1 and 0 < s1.size * 4 <= 40_000 and np.array_equal(s1, s2)
+    assert os.path.getsize(tmp_path / "s1" / "pred_sample.npy") <= 40_000 and not (tmp_path / "s1" / "pred.npy").exists()
+    assert np.isin(s1, a.reshape(-1).astype(np.float32)).all()
+    import subprocess
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "0"], capture_output=True, text=True, timeout=300, cwd=ROOT)
+    assert r.returncode != 0 and "--steps must be at least 1" in r.stderr

@@ -53,7 +53,7 @@ def _tile_worker8(rank, port, q):
     else:
         assert preds is None and stage1 is None
     q.put(("count", rank, mine))
-    dist.barrier()
+    dist.monitored_barrier()   # gloo-only; dist.barrier() first asks the HIP runtime for a device, which opens the GPU from a CPU rank
     dist.destroy_process_group()
 
 
@@ -108,7 +108,7 @@ def _encode_worker8(rank, port, T, bad_row, q):
     lat_h = T // 8
     _, init = P.sharded_encode(eng, [np.zeros((lat_h * 8, 8 * 8, 3), np.uint8)], rank, WORLD)   # lat_h x 8 latent = T tokens
     q.put((rank, init[:, 0].tolist(), eng.calls))
-    dist.barrier()
+    dist.monitored_barrier()   # gloo-only; dist.barrier() first asks the HIP runtime for a device, which opens the GPU from a CPU rank
     dist.destroy_process_group()
 
 

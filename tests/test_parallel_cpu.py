@@ -33,7 +33,7 @@ def _worker(rank, world, port, n_items, q):
         q.put((ids, tmax, out.shape[0]))
     else:
         assert out is None
-    dist.barrier()
+    dist.monitored_barrier()   # gloo-only; dist.barrier() first asks the HIP runtime for a device, which opens the GPU from a CPU rank
     dist.destroy_process_group()
 
 
@@ -90,7 +90,7 @@ def _tile_worker(rank, world, port, q):
         q.put((preds[0], stage1[0]))
     else:
         assert preds is None and stage1 is None
-    dist.barrier()
+    dist.monitored_barrier()   # gloo-only; dist.barrier() first asks the HIP runtime for a device, which opens the GPU from a CPU rank
     dist.destroy_process_group()
 
 
@@ -192,7 +192,7 @@ def _overflow_worker(rank, world, port, bad_row, forced, q):
         assert torch.equal(P._exchange_tiles(t, 3, 0, 1, to_all=True), t) and torch.equal(P._exchange_tiles(t, 3, 0, 1, to_all=False), t)
         plan = P.GatherPlan(torch.zeros(2, 4, 4, 3, dtype=torch.uint8))
         assert plan.on and torch.equal(plan.gather(torch.ones(2, 4, 4, 3, dtype=torch.uint8)), torch.ones(2, 4, 4, 3, dtype=torch.uint8))
-    dist.barrier()
+    dist.monitored_barrier()   # gloo-only; dist.barrier() first asks the HIP runtime for a device, which opens the GPU from a CPU rank
     dist.destroy_process_group()
 
 
