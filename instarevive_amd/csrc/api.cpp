@@ -431,8 +431,7 @@ void conv(Run& r, const Conv& cw, const bf16_t* in, int N, int H, int W, int in_
         q.wgt = cw.wup; q.wgt_rs = 4L * cw.cin; q.up2x2 = 1;
         if (ir_igemm_up2x2_takes(q)) p = q;
     }
-    static const bool no_gn_fuse = getenv("IR_NO_GN_FUSE") != nullptr;  // experiment knob
-    if (r.gn_want && r.gn_buf && !out_f32 && cw.cout % 32 == 0 && !no_gn_fuse) {
+    if (r.gn_want && r.gn_buf && !out_f32 && cw.cout % 32 == 0) {
         p.gn_cpg = cw.cout / 32;
         p.gn_chunks = ir_igemm_gn_chunks(p);
         if (p.gn_chunks > 0) {
@@ -466,11 +465,10 @@ void linear(Run& r, const Conv& cw, const bf16_t* in, int M, int in_cs, void* ou
 // ResnetBlock's norm -> SiLU -> 3x3 conv with the apply pass folded into the conv (conv_halo_s1_kernel<0, 9, NORM>): possible when the statistics of x
 // came out of the conv that wrote it (so that only the finalise is left of the GroupNorm) and the conv is one the NORM kernel takes. Worth it for ONE
 // 128-channel output tile only: the halo of a patch is normalised once per channel tile, measured +0.27 ms against a 0.42 ms pass at 128 -> 128 and
-// 2048 x 2048, +0.69 against 0.42 at 512 -> 512 and 1024 x 1024 (IR_S1_NORM_ALL lifts the limit for experiments). Leaves scale / shift in ws.
+// 2048 x 2048, +0.69 against 0.42 at 512 -> 512 and 1024 x 1024. Leaves scale / shift in ws.
 bool norm_conv_fused(Run& r, const Norm& n, const Conv& cw, const bf16_t* x, float* ws, int N, int H, int W, void* out, const void* res) {
     if (!r.live() || r.gn_x != x || r.gn_chunks <= 0 || r.c->plain || n.c != cw.cin) return false;
-    static const bool all = getenv("IR_S1_NORM_ALL") != nullptr;
-    if (cw.cout_pad != 128 && !all) return false;
+    if (cw.cout_pad != 128) return false;
     IGemmParams p;
     memset(&p, 0, sizeof p);
     p.in = x; p.NB = N; p.H = H; p.W = W; p.Cin = cw.cin; p.in_cs = cw.cin; p.taps = cw.taps; p.stride = 1; p.pad = 1;
@@ -606,8 +604,6 @@ void swinir_run(Run& r, const float* in, float* out, int n, int h, int w) {
         const float* cur = xa;
         bool have_ln1 = false;   // xn already holds norm1 of this block: written by the previous block's fused MLP kernel
         bool have_qkv = false;   // qkv already holds this block's q | k | v rows: the previous block's fused MLP kernel went on through norm1 and the projection
-        static const bool no_ln_fuse = getenv("IR_NO_SWIN_LN_FUSE") != nullptr;   // experiment knobs
-        static const bool no_qkv_fuse = getenv("IR_NO_SWIN_QKV_FUSE") != nullptr;
         for (size_t j = 0; j < L.blocks.size(); ++j) {
             const SwinBlock& b = L.blocks[j];
             const bool last = j + 1 == L.blocks.size();
@@ -616,10 +612,9 @@ void swinir_run(Run& r, const float* in, float* out, int n, int h, int w) {
                 linear(r, b.qkv, xn, (int)T, Cp, qkv, 3 * m.heads * 32, 0, ACT_NONE, nullptr, 0, 0);
             }
             have_ln1 = have_qkv = false;
-            static const bool no_block_fuse = getenv("IR_NO_SWIN_BLOCK_FUSE") != nullptr;   // experiment knob: attention + proj and the MLP as two launches
-            const bool fuse_ln = !last && !no_ln_fuse && (m.C & 3) == 0;      // not the last block of the RSTB: the MLP launch also makes norm1 of the NEXT block ...
+            const bool fuse_ln = !last && (m.C & 3) == 0;      // not the last block of the RSTB: the MLP launch also makes norm1 of the NEXT block ...
             const SwinBlock* nb = fuse_ln ? &L.blocks[j + 1] : nullptr;
-            const bool fuse_qkv = nb && nb->qkv_t && nb->qkv.b && !no_qkv_fuse;   // ... and, when the host packed that block's qkv weights as ring tiles, its qkv rows
+            const bool fuse_qkv = nb && nb->qkv_t && nb->qkv.b;   // ... and, when the host packed that block's qkv weights as ring tiles, its qkv rows
             const double f_attn = 4.0 * (double)T * 64 * m.C + 2.0 * (double)T * m.C * m.C;
             const double f_mlp = 4.0 * (double)T * m.C * m.hid + (fuse_qkv ? 6.0 * (double)T * m.C * m.C : 0.0);
             const double b_mlp = 4.0 * (double)T * m.C * 2 + (fuse_qkv ? 2.0 * (double)T * 3 * m.C : 0.0);
@@ -628,7 +623,7 @@ void swinir_run(Run& r, const float* in, float* out, int n, int h, int w) {
             const float* fbias = shift ? b.biasM : b.biasT;   // the fused attention kernels pick a masked table per window class in a shifted block
             // (the fused kernels address the [T][576] qkv tensor with 32-bit byte offsets: beyond 4 GB - 3.7 M tokens - the unfused path takes over)
             const bool fused_attn = b.proj_t && fbias && !g_ir_plain_kernels && (long)T * 576 * 2 < (1L << 32);
-            if (fused_attn && b.mlp_t && !no_block_fuse) {
+            if (fused_attn && b.mlp_t) {
                 // the whole block behind its qkv projection in ONE launch: the post-attention row stays in registers (swin_block_kernel)
                 LAUNCHK(r, PK_SWIN_BLOCK, f_attn + f_mlp, b_mlp + 2.0 * (double)T * 3 * m.C,
                        ir_launch_swin_block(qkv, cur, xb, mlp_out2, b.proj_t, b.proj.b, fbias, n, gh, gw, shift, scale, b.mlp_t, b.mlp_v, m.C, m.hid_p,
@@ -680,10 +675,9 @@ void swinir_run(Run& r, const float* in, float* out, int n, int h, int w) {
     conv(r, m.up3, u2, n, 4 * gh, 4 * gw, nf, u3, nf, 0, 1, 1, 1, ACT_LRELU, 0.2f, nullptr, 0, 0);
     conv(r, m.hr, u3, n, h, w, nf, u4, nf, 0, 1, 1, 0, ACT_LRELU, 0.2f, nullptr, 0, 0);
     // conv_last with x/img_range + mean folded into its weights (swinir.py:896,903)
-    static const bool no_to3 = getenv("IR_NO_SWIN_TO3") != nullptr;   // experiment knob: the generic implicit GEMM again
     // from 1024 x 1024 pixels up: below that the launch is 30 us either way, and the stress fixtures at 512 x 512 - whose PSNR against the oracle moves
     // by +- 0.7 dB with the summation ORDER of any one conv on the way (profiles/r06_stress_sensitivity.txt) - keep the numbers they were calibrated on
-    if (!r.c->plain && !no_to3 && nf == 64 && m.last.cin == 64 && m.last.cout_pad == 32 && m.last.taps == 9 && (long)h * w >= 1024L * 1024) {
+    if (!r.c->plain && nf == 64 && m.last.cin == 64 && m.last.cout_pad == 32 && m.last.taps == 9 && (long)h * w >= 1024L * 1024) {
         const double px = (double)n * h * w;
         LAUNCHK(r, PK_CONV_TO3, 2.0 * px * 3 * 9 * 64, px * (64 * 2 + 16), ir_launch_conv64_to3(u4, m.last.w, m.last.b, o4, n, h, w, r.s), "swin_conv_last");
     } else {
@@ -894,8 +888,7 @@ void vae_encode_run(Run& r, const float* in, float* lat, int n, int h, int w, fl
         ci = attnblock(r, m.attn, B, 0, gws, n, H, W, sh, IR_FP8_BIT_ENC_ATTN);
         goto after_attention;
     }
-    static const bool no_vae_io = getenv("IR_NO_VAE_IO") != nullptr;   // experiment knob: the generic kernels for conv_in / norm_out + conv_out
-    if (!r.c->plain && !no_vae_io && m.conv_in.cin == 32 && m.conv_in.cout == 128 && m.conv_in.cout_pad == 128) {
+    if (!r.c->plain && m.conv_in.cin == 32 && m.conv_in.cout == 128 && m.conv_in.cout_pad == 128) {
         // conv_in straight from the fp32 planes, with the statistics of norm1 of the first ResnetBlock (vae_io.hip)
         if (r.live()) {
             const double px = (double)n * h * w;
@@ -970,8 +963,7 @@ void vae_decode_run(Run& r, const float* lat, float in_scale, float* out_nhwc4, 
         }
     }
     const int t1 = (ci + 1) % 3;
-    static const bool no_vae_io = getenv("IR_NO_VAE_IO") != nullptr;
-    if (!r.c->plain && !no_vae_io && m.conv_out.cin == 128 && m.conv_out.cout_pad == 32 && r.gn_x == B[ci] && r.gn_chunks > 0) {
+    if (!r.c->plain && m.conv_out.cin == 128 && m.conv_out.cout_pad == 32 && r.gn_x == B[ci] && r.gn_chunks > 0) {
         // norm_out + SiLU + conv_out in one read of the tensor (vae_io.hip): the statistics come from the producing conv's epilogue, only the
         // finalise runs here
         if (r.live()) {
@@ -1453,9 +1445,8 @@ void cldm_pipeline_run(Run& r, const float* lq, const float* zT, float* samples,
                        float sf) {
     const size_t mk = r.a.mark();
     const int lh = h / 8, lw = w / 8;
-    static const int s1_min = getenv("IR_CLDM_S1_MIN_TILES") ? atoi(getenv("IR_CLDM_S1_MIN_TILES")) : 256;   // experiment knob (32: the DiT path's rule)
     const int s1_before = r.s1_min_tiles;
-    r.s1_min_tiles = s1_min;   // this path runs single 512 x 512 images: the big-tile persistent conv only where it has a tile per CU
+    r.s1_min_tiles = 256;   // this path runs single 512 x 512 images: the big-tile persistent conv only where it has a tile per CU (the DiT path's rule: 32)
     float* control = control_out ? control_out : r.a.alloc<float>((long)n * 3 * h * w);
     const float* cimg = lq;
     if (!(flags & IR_FLAG_NO_PREPROCESS)) {

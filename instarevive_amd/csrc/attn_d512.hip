@@ -31,8 +31,6 @@
 #include <type_traits>
 #include <utility>
 
-typedef __attribute__((address_space(3))) void* a5_lds_t;
-IR_DEVINL void a5_glds16(const void* g, a5_lds_t l) { __builtin_amdgcn_global_load_lds(g, l, 16, 0, 0); }
 IR_DEVINL int a5_swap23(int r) { return (r & ~12) | ((r & 4) << 1) | ((r & 8) >> 1); }
 
 namespace a5 {
@@ -47,14 +45,8 @@ constexpr float OVF_LIMIT = 80.0f;       // a later score may exceed the referen
 constexpr float RETRIG = 48.0f;          // flash_attn_d512_v2_kernel moves its reference in place once a score lies 2^48 above it (probabilities <= 2^48:
                                          // far inside fp32 / bf16 range, so nothing has overflowed when the check at the end of a tile sees it ...
                                          // unless ONE tile jumps by more than 2^128, which the in-place path handles by recomputing that tile)
-#ifndef IR_D512_LA
-#define IR_D512_LA 4
-#endif
-constexpr int LA = IR_D512_LA, NB = LA + 3;   // fragment reads in flight ahead of their MFMA; fragment register sets (see flash_attn_pp_kernel)
-#ifndef IR_D512_DMA_EVERY
-#define IR_D512_DMA_EVERY 2
-#endif
-constexpr int DMA_EVERY = IR_D512_DMA_EVERY;
+constexpr int LA = 4, NB = LA + 3;      // fragment reads in flight ahead of their MFMA; fragment register sets
+constexpr int DMA_EVERY = 2;
 constexpr int SM0 = 35;                  // first stream step that carries a softmax slice: three PV MFMAs behind the last QK^T MFMA
 }  // namespace a5
 
@@ -123,8 +115,6 @@ __global__ __launch_bounds__(256, 1) void flash_attn_d512_v2_kernel(const bf16_t
     asm volatile(".set ir_a5_i, 0\n\t.rept 256\n\tv_accvgpr_write_b32 a[ir_a5_i], 0\n\t.set ir_a5_i, ir_a5_i + 1\n\t.endr" ::: IR_AGPR256_CLOBBERS);
 
     // LDS-DMA pieces (1 KB per wave instruction): K rows wu + 4i and V^T pieces wu + 4i of a tile, i = 0..7
-    const bf16_t* k_lane = k + (long)wu * rs + lane * 8;
-    const bf16_t* v_lane = vt + wu * 512 + lane * 8;
     const long k_tile = 32L * rs, k_step = 4L * rs;
     // A piece = wave-uniform 64-bit base (scalar registers) + the lane's 32-bit byte offset (lane * 16, the same for every piece) in the
     // `global_load_lds_dwordx4 v_off, s[base]` form, written out: through the builtin hipcc keeps a 64-bit per-lane address and adds the
@@ -138,18 +128,10 @@ __global__ __launch_bounds__(256, 1) void flash_attn_d512_v2_kernel(const bf16_t
     const bf16_t* k_wave = k + (long)wu * rs;
     const bf16_t* v_wave = vt + wu * 512;
     auto k_piece = [&](int tile, int i, int slot) {
-#ifdef IR_D512_BUILTIN_DMA
-        a5_glds16(k_lane + tile * k_tile + i * k_step, (a5_lds_t)(smem + slot * KSLOT + (wu + 4 * i) * KROW));
-#else
         dma_piece(k_wave + tile * k_tile + i * k_step, (uint32_t)(slot * KSLOT + (wu + 4 * i) * KROW));
-#endif
     };
     auto v_piece = [&](int tile, int i, int slot) {
-#ifdef IR_D512_BUILTIN_DMA
-        a5_glds16(v_lane + (long)tile * (512 * 32) + i * 2048, (a5_lds_t)(smem + V_OFF + slot * VSLOT + (wu + 4 * i) * 1024));
-#else
         dma_piece(v_wave + (long)tile * (512 * 32) + i * 2048, (uint32_t)(V_OFF + slot * VSLOT + (wu + 4 * i) * 1024));
-#endif
     };
 #pragma unroll
     for (int i = 0; i < 8; ++i) {
@@ -369,9 +351,9 @@ int ir_launch_flash_attn_d512_v2_rows(const bf16_t* q, const bf16_t* k, const bf
 // =====================================================================================================================
 // flash_attn_pp2_kernel<72>: the DiT self-attention (16 heads x 72, T % 64 == 0, no key bias; reference PixArt_blocks.py:123-158) in the
 // structure of flash_attn_d512_v2_kernel above - ONE wave per SIMD with the whole register file, one pinned MFMA stream per tile,
-// everything else in the MFMA shadows - instead of the two-waves-per-SIMD ping-pong of flash_attn_pp_kernel (attention.hip), whose
-// matrix and vector segments are kept complementary by two workgroup barriers per tile (phase stamps: the waves wait at them for
-// about a third of a tile).
+// everything else in the MFMA shadows - instead of a two-waves-per-SIMD ping-pong (rounds 3-4, retired; in git history), whose matrix
+// and vector segments were kept complementary by two workgroup barriers per tile (phase stamps: the waves waited at them for about a
+// third of a tile).
 // A wave owns TWO groups of 32 queries: O^T (2 x 3 tiles) and the Q^T fragments (2 x 5 k-steps) live in AGPRs, addressed literally.
 // Per 64-key tile one stream of 44 MFMAs: S^T(t+1) of group 0, of group 1 (10 each: -m rides in as the C operand of the first),
 // then O^T += V^T(t) P^T(t) for both groups (24, the V^T fragments shared by the two groups). The exponentials of tile t+1 (no
@@ -381,19 +363,11 @@ int ir_launch_flash_attn_d512_v2_rows(const bf16_t* q, const bf16_t* k, const bf
 // rows, P^T registers as the B operand of the second product, reference fixed after the first tile (row maximum + 2^24 headroom).
 // Overflow is detected at the end: a denominator that is not a moderate finite number raises ovf_flag and the rescaling 4-wave
 // kernel, launched behind, recomputes everything.
-// Knock-out builds of flash_attn_pp2_kernel (diagnostic, -DIR_KO_PP2=n, results wrong by design): 1 no per-tile wait + barrier, 2 no LDS-DMA in the
-// stream, 3 no exponentials, 4 no fragment reads, 5 no MFMAs
-#ifndef IR_KO_PP2
-#define IR_KO_PP2 0
-#endif
-// Experiment knob (-DIR_PP2_TRUNC=1): the probabilities go to bf16 by truncation (one full-rate v_perm_b32 per pair instead of the quarter-rate
-// v_cvt_pk_bf16_f32: 128 issue cycles less per tile). Correct and as accurate as rounding (see pp2_pack), 6 % faster when the op runs alone
-// (1.349 -> 1.264 ms at 16384 tokens) - and NO faster inside the pipeline (30.15 against 30.16 ms for the 28 layers, A/B twice on one box): there
-// the kernel sits at the power-limited clock (about 1.8 GHz with the matrix pipe 75 % busy), where the time follows the energy of the MFMAs, not
-// the issue slots beside them. Default off: rounding is what every other kernel does.
-#ifndef IR_PP2_TRUNC
-#define IR_PP2_TRUNC 0
-#endif
+// Measured and not kept (the switch is retired; the code is in git history): the probabilities to bf16 by truncation (one full-rate v_perm_b32
+// per pair instead of the quarter-rate v_cvt_pk_bf16_f32: 128 issue cycles less per tile) ran 6 % faster when the op runs alone (1.349 -> 1.264 ms
+// at 16384 tokens) - and NO faster inside the pipeline (30.15 against 30.16 ms for the 28 layers, A/B twice on one box): there the kernel sits at
+// the power-limited clock (about 1.8 GHz with the matrix pipe 75 % busy), where the time follows the energy of the MFMAs, not the issue slots
+// beside them. Rounding is what every other kernel does.
 namespace pp2 {
 constexpr int D = 72, NKS = 5, NDT = 3, RCH = 9;
 constexpr int KROW = RCH * 16;              // 144-byte K rows, unpadded (9 chunks: conflict-free)
@@ -407,10 +381,7 @@ constexpr int LDS_O = 8 * 32 * OS * 2;           // 53 248 B
 constexpr int LDS_BYTES = LDS_MAIN > LDS_O ? LDS_MAIN : LDS_O;
 constexpr int NPC = (K_Q + V_Q + 3) / 4;         // pieces per wave and tile (at most)
 constexpr float MARGIN = 24.0f;
-#ifndef IR_PP2_DMA_EVERY
-#define IR_PP2_DMA_EVERY 2
-#endif
-constexpr int DMA_EVERY = IR_PP2_DMA_EVERY;      // one LDS-DMA piece behind every DMA_EVERY-th MFMA of the stream: 2 = behind the first score MFMAs, whose gaps
+constexpr int DMA_EVERY = 2;                     // one LDS-DMA piece behind every DMA_EVERY-th MFMA of the stream: 2 = behind the first score MFMAs, whose gaps
                                                  // carry no exponentials (6 / 8: 1.29 -> 1.30 / 1.32 ms per layer, measured in round 4)
 constexpr int LA = 6, NB = LA + 3;
 constexpr int NQK = 20, NPV = 24, NSTEP = NQK + NPV;
@@ -504,16 +475,11 @@ __global__ __launch_bounds__(256, 1) void flash_attn_pp2_kernel(AttnParams p) {
         constexpr int k = decltype(kc)::value;
         const bool isk = k < 2 || (k == 2 && k2_is_k);
         const unsigned char* base = isk ? kbase : vbase;
-#ifndef IR_PP2_BUILTIN_DMA
         // scalar base + 32-bit lane offset, written out: hipcc widens pc_off to a register pair and adds the base on the VALU
         const uint32_t m0v = (uint32_t)__builtin_amdgcn_readfirstlane((int)(lds0_early + (uint32_t)((isk ? kslot : vslot) + pc_dst[k])));
         const uint32_t off = pc_off[k];
         asm volatile("s_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, %1" ::"v"(off), "s"(base), "s"(m0v) : "memory");
-#else
-        a5_glds16(base + pc_off[k], (a5_lds_t)(smem + (isk ? kslot : vslot) + pc_dst[k]));
-#endif
     };
-#ifndef IR_PP2_NO_PADZERO
     // Rows 80..95 of the two V^T slots are never loaded (the 10 pieces of a tile end at row 79) but ARE multiplied: the third 32-row tile of O^T = V^T P^T
     // spans rows 64..95. Left as whatever the previous kernel had in LDS they cost the multiplier array as much as real data; as zeros they toggle
     // nothing - and this kernel runs at the power-limited clock (section 3, round 4). 2 x 2 KB, once per workgroup.
@@ -521,7 +487,6 @@ __global__ __launch_bounds__(256, 1) void flash_attn_pp2_kernel(AttnParams p) {
         const int slot = c >> 7, rem = c & 127;
         *reinterpret_cast<uint4*>(smem + V_OFF + slot * VSLOT + (80 + (rem >> 3)) * 128 + (rem & 7) * 16) = make_uint4(0, 0, 0, 0);
     }
-#endif
     // prologue: K(0) -> slot 0 and V^T(0) -> slot 0, then K(1) -> slot 1
     [&]<int... K>(std::integer_sequence<int, K...>) { ((issue(std::integral_constant<int, K>{})), ...); }(std::make_integer_sequence<int, NPC>{});
     if (NT > 1) {
@@ -557,25 +522,8 @@ __global__ __launch_bounds__(256, 1) void flash_attn_pp2_kernel(AttnParams p) {
     uint4 pbA[2][4], pbB[2][4];   // P^T fragments [group][kk] of the tile being multiplied / being exponentiated
     bf16x8 fr[NB];
     float p_hold2[2] = {0.f, 0.f}, pend0[2] = {0.f, 0.f}, pend1[2] = {0.f, 0.f};
-    // P -> bf16: 32 packs per tile in an issue-bound stream. Truncation is one full-rate v_perm_b32 instead of the quarter-rate v_cvt_pk; its mean
-    // bias (-0.27 %) is common to numerator and denominator (the ones row of V^T sums the SAME operand), what is left has round-to-nearest's variance
-    // (16384 tokens, random operands: rms error against fp32 3.88e-5 for 3.80e-5 rounded). Tile 0, computed in the open, keeps the rounding pack: its
-    // 64 keys weigh 0.27 % more than the others', 1e-5 of the result at 16384 tokens and 2e-4 at 1024.
-    const uint32_t psel = __builtin_amdgcn_readfirstlane(0x07060302u);
-    auto pp2_pack0 = [&](float lo, float hi) -> uint32_t { return pack2bf(lo, hi); };   // tile 0 (outside the pinned stream, compiler-scheduled): round to nearest
-    auto pp2_pack_last = [&](float lo, float hi) -> uint32_t {
-        if constexpr (IR_PP2_TRUNC) return pack2bf_trunc_trans(lo, hi, psel);
-        else return pack2bf_valu(lo, hi);
-    };
-    auto pp2_pack = [&](float lo, float hi) -> uint32_t {
-        if constexpr (IR_PP2_TRUNC) {
-            return pack2bf_trunc(lo, hi, psel);
-        } else return pack2bf_valu(lo, hi);
-    };
-    if (IR_KO_PP2 == 4) {
-#pragma unroll
-        for (int i = 0; i < NB; ++i) fr[i] = __builtin_bit_cast(bf16x8, make_uint4(lane, 0x3c003c00, 0x3c003c00, 0x3c003c00));
-    }
+    // P -> bf16, round to nearest: pack2bf for tile 0 (outside the pinned stream, compiler-scheduled), pack2bf_valu for the 32 packs per tile of the stream
+    auto pp2_pack0 = [&](float lo, float hi) -> uint32_t { return pack2bf(lo, hi); };
     uint32_t ka = k_addr, va[4] = {v_addr[0], v_addr[1], v_addr[2], v_addr[3]};
 #pragma unroll
     for (int g = 0; g < 2; ++g)
@@ -587,7 +535,6 @@ __global__ __launch_bounds__(256, 1) void flash_attn_pp2_kernel(AttnParams p) {
     // dt*4 + kk, group j & 1)
     auto frag_read = [&](auto jc) {
         constexpr int j = decltype(jc)::value;
-        if constexpr (IR_KO_PP2 == 4) return;
         if constexpr (j < NQK) fr[j % NB] = lds_read16<(((j % 10) / 5) * 32 * KROW + (j % 5) * 32)>(ka);
         else fr[(NQK + ((j - NQK) >> 1)) % NB] = lds_read16<(((j - NQK) >> 3) * 4096)>(va[((j - NQK) >> 1) & 3]);
     };
@@ -614,9 +561,7 @@ __global__ __launch_bounds__(256, 1) void flash_attn_pp2_kernel(AttnParams p) {
                 if constexpr (((sl - S0) & 1) == 0) wait_lds<(rem < LA ? (rem > 0 ? rem - 1 : 0) : LA - 1)>();
             }
             __builtin_amdgcn_sched_barrier(0);
-            if constexpr (IR_KO_PP2 == 5) {
-                asm volatile("" ::"v"(fr[sl % NB]));
-            } else if constexpr (j < NQK) {
+            if constexpr (j < NQK) {
                 constexpr int g = j / 10, kt = (j % 10) / 5, ks = j % 5;
                 if constexpr (ks == 0) pp2_mfma_qk_first<Q_BASE + 4 * (5 * g + ks)>(sacc[g][kt], fr[sl % NB], negm[g]);
                 else pp2_mfma_qk<Q_BASE + 4 * (5 * g + ks)>(sacc[g][kt], fr[sl % NB]);
@@ -626,12 +571,12 @@ __global__ __launch_bounds__(256, 1) void flash_attn_pp2_kernel(AttnParams p) {
             }
             if constexpr (sl - 2 >= S0) asm volatile("" ::"v"(fr[(sl - 2) % NB]));
             __builtin_amdgcn_sched_barrier(0);
-            if constexpr (DMA && IR_KO_PP2 != 2 && (j % DMA_EVERY) == 1 && j / DMA_EVERY < NPC) {   // K(t+2) / V^T(t+1) pieces, spread over the tile (see a5::DMA_EVERY)
+            if constexpr (DMA && (j % DMA_EVERY) == 1 && j / DMA_EVERY < NPC) {   // K(t+2) / V^T(t+1) pieces, spread over the tile (see a5::DMA_EVERY)
                 issue(std::integral_constant<int, (j / DMA_EVERY)>{});
                 __builtin_amdgcn_sched_barrier(0);
             }
-            if constexpr (SOFTMAX && IR_KO_PP2 != 3 && j >= 13) {   // two exponentials per MFMA shadow: group 0 from step 13 (three MFMAs behind its
-                                                                     // last score MFMA, step 9), group 1 from step 23
+            if constexpr (SOFTMAX && j >= 13) {   // two exponentials per MFMA shadow: group 0 from step 13 (three MFMAs behind its
+                                                   // last score MFMA, step 9), group 1 from step 23
                 constexpr int n0 = j < 23 ? 2 * (j - 13) : 20 + (j - 23) * 44 / 21, n1 = j < 23 ? n0 + 2 : 20 + (j - 22) * 44 / 21;
                 [&]<int... E>(std::integer_sequence<int, E...>) {
                     ([&] {
@@ -645,8 +590,8 @@ __global__ __launch_bounds__(256, 1) void flash_attn_pp2_kernel(AttnParams p) {
                                 if constexpr (((n >> 1) & 1) == 0) { pend0[0] = p_hold2[g]; pend0[1] = pv; } else { pend1[0] = p_hold2[g]; pend1[1] = pv; }
                                 if constexpr (n >= 3) {
                                     constexpr int gp = pp2_item_g(n - 2), ep = pp2_item_e(n - 2);
-                                    if constexpr (((n >> 1) & 1) == 0) a5_set_word<((ep & 7) >> 1)>(pn[gp][ep >> 3], pp2_pack(pend1[0], pend1[1]));
-                                    else a5_set_word<((ep & 7) >> 1)>(pn[gp][ep >> 3], pp2_pack(pend0[0], pend0[1]));
+                                    if constexpr (((n >> 1) & 1) == 0) a5_set_word<((ep & 7) >> 1)>(pn[gp][ep >> 3], pack2bf_valu(pend1[0], pend1[1]));
+                                    else a5_set_word<((ep & 7) >> 1)>(pn[gp][ep >> 3], pack2bf_valu(pend0[0], pend0[1]));
                                 }
                             } else {
                                 p_hold2[g] = pv;
@@ -656,7 +601,7 @@ __global__ __launch_bounds__(256, 1) void flash_attn_pp2_kernel(AttnParams p) {
                 }(std::make_integer_sequence<int, 4>{});
                 if constexpr (j == NSTEP - 1) {   // the last pair (item 63, pending slot 1)
                     constexpr int gp = pp2_item_g(63), ep = pp2_item_e(63);
-                    a5_set_word<((ep & 7) >> 1)>(pn[gp][ep >> 3], pp2_pack_last(pend1[0], pend1[1]));   // its exponentials are the two just issued
+                    a5_set_word<((ep & 7) >> 1)>(pn[gp][ep >> 3], pack2bf_valu(pend1[0], pend1[1]));   // its exponentials are the two just issued
                 }
                 __builtin_amdgcn_sched_barrier(0);
             }
@@ -708,10 +653,8 @@ __global__ __launch_bounds__(256, 1) void flash_attn_pp2_kernel(AttnParams p) {
     }
     // ---- main loop (two tiles per trip: the P^T buffers swap roles statically)
     auto tile_step = [&](int t, uint4 (&pc)[2][4], uint4 (&pn)[2][4]) {
-        if (IR_KO_PP2 != 1) {
-            wait_dma();
-            __syncthreads();
-        }
+        wait_dma();
+        __syncthreads();
         ka = k_addr + ((t + 1) & 1) * KSLOT;
 #pragma unroll
         for (int j = 0; j < 4; ++j) va[j] = v_addr[j] + (t & 1) * VSLOT;
@@ -760,9 +703,8 @@ __global__ __launch_bounds__(256, 1) void flash_attn_pp2_kernel(AttnParams p) {
 
 int ir_launch_flash_attn_pp2(const AttnParams& p, hipStream_t s) {
     if (p.D != 72 || p.Tq <= 0 || p.Tk < 64 || (p.Tk & 63) || !p.ovf_flag || p.key_bias) return -2;
-    static const bool no_xcd = getenv("IR_PP2_NO_XCD_MAP") != nullptr;   // experiment knob
     // (from 32 query tiles per head on - an XCD's 32 CUs then share one head; measured 1.253 -> 1.243 ms at 16384 tokens, 0.093 -> 0.094 at 4096)
-    if ((p.Hh & 7) == 0 && (p.Tq + 255) / 256 >= 32 && !no_xcd) hipLaunchKernelGGL(flash_attn_pp2_kernel, dim3(((p.Tq + 255) / 256) * p.Hh, 1, p.B), dim3(256), 0, s, p);
+    if ((p.Hh & 7) == 0 && (p.Tq + 255) / 256 >= 32) hipLaunchKernelGGL(flash_attn_pp2_kernel, dim3(((p.Tq + 255) / 256) * p.Hh, 1, p.B), dim3(256), 0, s, p);
     else hipLaunchKernelGGL(flash_attn_pp2_kernel, dim3((p.Tq + 255) / 256, p.Hh, p.B), dim3(256), 0, s, p);
     return hipGetLastError() == hipSuccess ? 0 : -1;
 }
@@ -1094,8 +1036,7 @@ __global__ __launch_bounds__(256, 1) void flash_attn_x72_kernel(AttnParams p, in
 }
 
 bool ir_flash_attn_x72_takes(const AttnParams& p) {
-    static const bool off = getenv("IR_NO_X72") != nullptr;   // experiment knob: the 4-wave kernel for the cross-attention again
-    return !off && !g_ir_plain_kernels && p.D == 72 && p.Tk > 0 && p.Tk <= 64 * x72::MAXT && p.Tk_pad >= ((p.Tk + 63) & ~63) && p.Tq >= 256 &&
+    return !g_ir_plain_kernels && p.D == 72 && p.Tk > 0 && p.Tk <= 64 * x72::MAXT && p.Tk_pad >= ((p.Tk + 63) & ~63) && p.Tq >= 256 &&
            (long)p.B * p.Hh * ((p.Tq + 255) / 256) >= 64;
 }
 int ir_launch_flash_attn_x72(const AttnParams& p, hipStream_t s) {

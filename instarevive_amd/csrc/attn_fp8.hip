@@ -150,29 +150,15 @@ struct AttnF8Params {
 // are covered by construction: an MFMA result is read by the VALU a phase (hundreds of cycles) later or behind explicit s_nops; VALU-written
 // operands (P8, exponent bytes) are a phase old; LDS fragments are behind counted lgkmcnt waits; the bf16 remainder MFMA, which reads the
 // e4m3 MFMA's result as its C operand, issues at least 18 wait states behind it (another MFMA plus softmax items sit in between).
-// diagnostic builds: wait states behind the MFMAs of one kind (-DIR_F8_NOP=1: e4m3 score MFMAs, 2: bf16 remainder MFMAs, 4: O^T MFMAs; sums combine)
-#ifndef IR_F8_NOP
-#define IR_F8_NOP 0
-#endif
-// knock-out builds (diagnostic, results wrong by design): -DIR_KO_F8=1 no MFMAs, 2 no softmax items, 4 no per-tile barrier + DMA wait, 8 no fragment reads
-#ifndef IR_KO_F8
-#define IR_KO_F8 0
-#endif
 IR_DEVINL void f8_mfma_s(f32x16& s, i32x8 a, i32x8 b, int sa, int sb) {   // s = A8 B8 (block scales sa / sb, byte 0), fresh destination
-    if constexpr (IR_KO_F8 & (1 | 32)) { asm volatile("" : "=v"(s) : "v"(a), "v"(b), "v"(sa), "v"(sb)); return; }
-    if constexpr (IR_F8_NOP & 1) asm volatile("v_mfma_scale_f32_32x32x64_f8f6f4 %0, %1, %2, 0, %3, %4 op_sel_hi:[0,0,0]\n\ts_nop 15" : "=&v"(s) : "v"(a), "v"(b), "v"(sa), "v"(sb));
-    else asm volatile("v_mfma_scale_f32_32x32x64_f8f6f4 %0, %1, %2, 0, %3, %4 op_sel_hi:[0,0,0]" : "=&v"(s) : "v"(a), "v"(b), "v"(sa), "v"(sb));
+    asm volatile("v_mfma_scale_f32_32x32x64_f8f6f4 %0, %1, %2, 0, %3, %4 op_sel_hi:[0,0,0]" : "=&v"(s) : "v"(a), "v"(b), "v"(sa), "v"(sb));
 }
 IR_DEVINL void bf_mfma_acc(f32x16& s, bf16x8 a, bf16x8 b) {
-    if constexpr (IR_KO_F8 & (1 | 16)) { asm volatile("" : "+v"(s) : "v"(a), "v"(b)); return; }
-    if constexpr (IR_F8_NOP & 2) asm volatile("v_mfma_f32_32x32x16_bf16 %0, %1, %2, %0\n\ts_nop 15" : "+v"(s) : "v"(a), "v"(b));
-    else asm volatile("v_mfma_f32_32x32x16_bf16 %0, %1, %2, %0" : "+v"(s) : "v"(a), "v"(b));
+    asm volatile("v_mfma_f32_32x32x16_bf16 %0, %1, %2, %0" : "+v"(s) : "v"(a), "v"(b));
 }
 template <int LO>
 IR_DEVINL void f8_mfma_o(i32x8 a, i32x8 b, int sa, int sb) {   // a[LO : LO + 15] += A8 B8
-    if constexpr (IR_KO_F8 & (1 | 64)) { asm volatile("" ::"v"(a), "v"(b), "v"(sa), "v"(sb)); return; }
-    if constexpr (IR_F8_NOP & 4) asm volatile("v_mfma_scale_f32_32x32x64_f8f6f4 a[%c4:%c5], %0, %1, a[%c4:%c5], %2, %3 op_sel_hi:[0,0,0]\n\ts_nop 15" ::"v"(a), "v"(b), "v"(sa), "v"(sb), "n"(LO), "n"(LO + 15));
-    else asm volatile("v_mfma_scale_f32_32x32x64_f8f6f4 a[%c4:%c5], %0, %1, a[%c4:%c5], %2, %3 op_sel_hi:[0,0,0]" ::"v"(a), "v"(b), "v"(sa), "v"(sb), "n"(LO), "n"(LO + 15));
+    asm volatile("v_mfma_scale_f32_32x32x64_f8f6f4 a[%c4:%c5], %0, %1, a[%c4:%c5], %2, %3 op_sel_hi:[0,0,0]" ::"v"(a), "v"(b), "v"(sa), "v"(sb), "n"(LO), "n"(LO + 15));
 }
 // (keep(): attn_fp8_common.h - pins an MFMA's operand registers past the softmax items that follow it: with the fragment registers handed
 // back to hipcc right behind the MFMA, an exponential landed in them and the product came out wrong - intermittently.)
@@ -270,14 +256,12 @@ __global__ __launch_bounds__(256, 1) void flash_attn_fp8_kernel(AttnF8Params p) 
     struct VF { bf16x8 a0, a1; };
     auto read_k = [&](KF& f, auto slot_c, auto ktc) {
         constexpr int base = decltype(slot_c)::value * TILE_BYTES, kt = decltype(ktc)::value;
-        if constexpr (IR_KO_F8 & 8) { asm volatile("" : "+v"(f.a0), "+v"(f.a1), "+v"(f.ar)); return; }
         f.a0 = lds_read16<base + kt * 32 * KROW>(k_lane);
         f.a1 = lds_read16<base + kt * 32 * KROW + 16>(k_lane);
         f.ar = lds_read16<base>(kr_lane[kt]);
     };
     auto read_v = [&](VF& f, auto slot_c, auto dtc) {
         constexpr int base = decltype(slot_c)::value * TILE_BYTES, dt = decltype(dtc)::value;
-        if constexpr (IR_KO_F8 & 8) { asm volatile("" : "+v"(f.a0), "+v"(f.a1)); return; }
         f.a0 = lds_read16<base>(v_lane[dt][0]);
         f.a1 = lds_read16<base>(v_lane[dt][1]);
     };
@@ -387,13 +371,11 @@ __global__ __launch_bounds__(256, 1) void flash_attn_fp8_kernel(AttnF8Params p) 
         using SF = std::integral_constant<int, (K + PF) % NSLOT>;  // free: tile t - 1 was its last user
         auto sm_a = [&](auto jc) {
             constexpr int J = decltype(jc)::value;
-            if constexpr (IR_KO_F8 & 2) { asm volatile("" : "+v"(S1old[0]), "+v"(S1old[1]), "+v"(P1), "+v"(e1)); return; }
             sm_range(std::integral_constant<int, A_LO[J]>{}, std::integral_constant<int, A_LO[J + 1]>{}, S1old, st1, P1, e1);
             __builtin_amdgcn_sched_barrier(0);
         };
         auto sm_b = [&](auto jc) {
             constexpr int J = decltype(jc)::value;
-            if constexpr (IR_KO_F8 & 2) { asm volatile("" : "+v"(S0[0]), "+v"(S0[1]), "+v"(P0next), "+v"(e0next)); return; }
             sm_range(std::integral_constant<int, B_LO[J]>{}, std::integral_constant<int, B_LO[J + 1]>{}, S0, st0, P0next, e0next);
             __builtin_amdgcn_sched_barrier(0);
         };
@@ -435,10 +417,8 @@ __global__ __launch_bounds__(256, 1) void flash_attn_fp8_kernel(AttnF8Params p) 
         F8_T(tb);
         // ---- mid
         wait_lds<0>();            // V(t) d-tile 0
-        if constexpr (!(IR_KO_F8 & 4)) {
         wait_vm<3 * (PF - 3)>();  // tile t + 2
         __builtin_amdgcn_s_barrier();   // bare: __syncthreads() makes hipcc drain vmcnt(0) in front of it, i.e. wait for the tiles still in flight
-        }
         issue_tile(t + PF, SF{});
         __builtin_amdgcn_sched_barrier(0);
         F8_T(tc);
@@ -518,7 +498,7 @@ __global__ __launch_bounds__(256, 1) void flash_attn_fp8_kernel(AttnF8Params p) 
             }
         }(), ...);
     }(std::make_integer_sequence<int, 6>{});
-    if (IR_KO_F8 == 0 && __any(bad) && lane == 0) atomicOr(p.ovf_flag, 1);   // (knock-out builds compute garbage: keep their timing free of the fallback)
+    if (__any(bad) && lane == 0) atomicOr(p.ovf_flag, 1);
     __syncthreads();
     bf16_t* op = p.o + (long)b * p.o_bs + (long)head * p.o_hs;
     for (int c = lane; c < 64 * 9; c += 64) {

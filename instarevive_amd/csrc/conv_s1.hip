@@ -59,10 +59,6 @@ constexpr int nh_first(int ntap, int t) { return ntap == 9 ? (t < 4 ? 2 * t : (t
 constexpr int hkey(int hx) { return ((hx >> 2) & 1) << 1; }
 }  // namespace cs1
 
-#ifndef IR_KO_S1
-#define IR_KO_S1 0   // knock-out builds for timing only (results wrong by design): 1 no epilogue, 2 no main loop, 3 neither,
-                     // 4 no halo DMA in the loop, 5 no weight DMA in the loop, 6 no fragment reads, 7 no per-step barrier
-#endif
 #ifdef IR_S1_STAMPS   // diagnostic build only (tools/conv_s1_stamp.hip): per-workgroup phase sums, never compiled into the library
 __device__ unsigned long long g_s1_stamps[1024 * 8];   // [wg][0..4] s_memrealtime sums (100 MHz): prologue, main, drain, passes, gn; [5] s_memtime over main; [6] tiles
 #define IR_S1_T(v) const unsigned long long v = __builtin_amdgcn_s_memrealtime()
@@ -237,7 +233,7 @@ __global__ __launch_bounds__(256, 1) void conv_halo_s1_kernel(IGemmParams p, int
         [&]<int... I>(std::integer_sequence<int, I...>) {
             ([&] {
                 constexpr int PT = I >> 3, CT = I & 7;
-                if constexpr ((I & 3) == 0 && IR_KO_S1 != 6) {   // one fragment of the next step per four MFMAs, into the other set
+                if constexpr ((I & 3) == 0) {   // one fragment of the next step per four MFMAs, into the other set
                     constexpr int R = I >> 2;
                     if constexpr (R < 8) fw[SET ^ 1][R] = lds_read16<R * 1024>(wa);
                     else fp[SET ^ 1][R - 8] = lds_read16<(((R - 8) >> 1) + KYN) * HWD * ROWB + ((R - 8) & 1) * 1024>(ha);
@@ -245,19 +241,19 @@ __global__ __launch_bounds__(256, 1) void conv_halo_s1_kernel(IGemmParams p, int
                 __builtin_amdgcn_sched_barrier(0);
                 cs1_mfma<4 * I>(fw[SET][CT], fp[SET][PT]);
                 __builtin_amdgcn_sched_barrier(0);
-                if constexpr (I == 1 && nh(NTAP, T) > 0 && IR_KO_S1 != 4) {
+                if constexpr (I == 1 && nh(NTAP, T) > 0) {
                     halo_piece(std::integral_constant<int, 0>{});
                     __builtin_amdgcn_sched_barrier(0);
                 }
-                if constexpr (I == 5 && nh(NTAP, T) > 1 && IR_KO_S1 != 4) {
+                if constexpr (I == 5 && nh(NTAP, T) > 1) {
                     halo_piece(std::integral_constant<int, 1>{});
                     __builtin_amdgcn_sched_barrier(0);
                 }
-                if constexpr (I == 17 && nh(NTAP, T) > 2 && IR_KO_S1 != 4) {
+                if constexpr (I == 17 && nh(NTAP, T) > 2) {
                     halo_piece(std::integral_constant<int, 2>{});
                     __builtin_amdgcn_sched_barrier(0);
                 }
-                if constexpr ((I == 10 || I == 13) && IR_KO_S1 != 5) {
+                if constexpr (I == 10 || I == 13) {
                     constexpr int K = I == 10 ? 0 : 1;
                     __builtin_amdgcn_raw_ptr_buffer_load_lds(w_rsrc, (cs1_lds_t)(smem + W_OFF + (s & 3) * WT_BYTES + (wu + 4 * K) * 1024), 16,
                                                              (int)(wmine ? w_ptr[K] : w_nxt[K]), wkoff, 0, 0);
@@ -268,9 +264,9 @@ __global__ __launch_bounds__(256, 1) void conv_halo_s1_kernel(IGemmParams p, int
         wait_lds<0>();
         // everything but the pieces of this step and the previous one has landed: the weight tile of step s + 2 (read during step s + 1)
         // and, before tap 8, the next chunk's halo (its last piece was issued a chunk ago)
-        wait_vm<(IR_KO_S1 == 5 ? 0 : 4) + (IR_KO_S1 == 4 ? 0 : nh(NTAP, (T + NTAP - 1) % NTAP) + nh(NTAP, T))>();
+        wait_vm<4 + nh(NTAP, (T + NTAP - 1) % NTAP) + nh(NTAP, T)>();
         __builtin_amdgcn_sched_barrier(0);
-        if (IR_KO_S1 != 7) __builtin_amdgcn_s_barrier();
+        __builtin_amdgcn_s_barrier();
         __builtin_amdgcn_sched_barrier(0);
     };
 
@@ -294,13 +290,12 @@ __global__ __launch_bounds__(256, 1) void conv_halo_s1_kernel(IGemmParams p, int
         }
     };
     // gn_apply_kernel's arithmetic, value for value (silu(a) = a * rcp(1 + __expf(-a)) with __expf(x) = v_exp_f32(x * log2 e), v_cvt_pk rounding), in six
-    // stages that ride in six MFMA gaps. The full-rate part runs as packed fp32 pairs (v_pk_fma_f32 / v_pk_mul_f32 / v_pk_add_f32: IEEE per lane, the
-    // same bits as the scalar forms, half the issue slots); the exponential and the reciprocal stay one instruction per value.
+    // stages that ride in six MFMA gaps. The full-rate part runs as scalar fp32 instructions (v_fma_f32 / v_mul_f32 / v_add_f32 through asm, which
+    // hipcc cannot re-pack): the packed pairs (v_pk_fma_f32 ...: the same bits, half the issue slots) were 0.5-1.2 % slower on every shape
+    // (profiles/r06_norm_scalar_ab.txt; one v_pk_fma_f32 beside MFMAs costs +22 cycles over two v_fma_f32). The exponential and the reciprocal are
+    // one instruction per value.
     typedef float nf32x2 __attribute__((ext_vector_type(2)));
     nf32x2 nfa[NORM ? 4 : 1], nfe[NORM ? 4 : 1];
-#ifndef IR_S1_NORM_SCALAR
-#define IR_S1_NORM_SCALAR 1   // 1 (default since round 6: 0.5-1.2 % faster on every shape, profiles/r06_norm_scalar_ab.txt): the full-rate part as scalar fp32 instructions (v_fma_f32 / v_mul_f32 / v_add_f32 through asm, which hipcc cannot re-pack) instead
-#endif                        // of the packed pairs: MI355X_MICROARCH.md prices one v_pk_fma_f32 beside MFMAs at +22 cycles over two v_fma_f32
     auto sfma = [](float a, float b, float c) { float r; asm("v_fma_f32 %0, %1, %2, %3" : "=v"(r) : "v"(a), "v"(b), "v"(c)); return r; };
     auto smul = [](float a, float b) { float r; asm("v_mul_f32 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b)); return r; };
     auto sadd1 = [](float a) { float r; asm("v_add_f32 %0, 1.0, %1" : "=v"(r) : "v"(a)); return r; };
@@ -316,32 +311,24 @@ __global__ __launch_bounds__(256, 1) void conv_halo_s1_kernel(IGemmParams p, int
             const uint32_t w[4] = {u.x, u.y, u.z, u.w};
 #pragma unroll
             for (int e = 0; e < 4; ++e) {
-                if constexpr (IR_S1_NORM_SCALAR) nfa[e] = nf32x2{sfma(bflo(w[e]), nsc[2 * e], nsh[2 * e]), sfma(bfhi(w[e]), nsc[2 * e + 1], nsh[2 * e + 1])};
-                else nfa[e] = nf32x2{bflo(w[e]), bfhi(w[e])} * nf32x2{nsc[2 * e], nsc[2 * e + 1]} + nf32x2{nsh[2 * e], nsh[2 * e + 1]};
+                nfa[e] = nf32x2{sfma(bflo(w[e]), nsc[2 * e], nsh[2 * e]), sfma(bfhi(w[e]), nsc[2 * e + 1], nsh[2 * e + 1])};
             }
         } else if constexpr (ST == 1 || ST == 2) {
 #pragma unroll
             for (int e = 2 * (ST - 1); e < 2 * ST; ++e) {
-                nf32x2 t;
-                if constexpr (IR_S1_NORM_SCALAR) t = nf32x2{smul(nfa[e][0], -1.44269504088896340736f), smul(nfa[e][1], -1.44269504088896340736f)};
-                else t = nfa[e] * -1.44269504088896340736f;   // __expf(-a)
+                const nf32x2 t = nf32x2{smul(nfa[e][0], -1.44269504088896340736f), smul(nfa[e][1], -1.44269504088896340736f)};   // __expf(-a)
                 nfe[e] = nf32x2{__builtin_amdgcn_exp2f(t[0]), __builtin_amdgcn_exp2f(t[1])};
             }
         } else if constexpr (ST == 3 || ST == 4) {
 #pragma unroll
             for (int e = 2 * (ST - 3); e < 2 * (ST - 2); ++e) {
-                nf32x2 d;
-                if constexpr (IR_S1_NORM_SCALAR) d = nf32x2{sadd1(nfe[e][0]), sadd1(nfe[e][1])};
-                else d = nfe[e] + 1.0f;
+                const nf32x2 d = nf32x2{sadd1(nfe[e][0]), sadd1(nfe[e][1])};
                 nfe[e] = nf32x2{fast_rcp(d[0]), fast_rcp(d[1])};
             }
         } else {
             nf32x2 y[4];
 #pragma unroll
-            for (int e = 0; e < 4; ++e) {
-                if constexpr (IR_S1_NORM_SCALAR) y[e] = nf32x2{smul(nfa[e][0], nfe[e][0]), smul(nfa[e][1], nfe[e][1])};
-                else y[e] = nfa[e] * nfe[e];
-            }
+            for (int e = 0; e < 4; ++e) y[e] = nf32x2{smul(nfa[e][0], nfe[e][0]), smul(nfa[e][1], nfe[e][1])};
             out = make_uint4(pack2bf_valu(y[0][0], y[0][1]), pack2bf_valu(y[1][0], y[1][1]), pack2bf_valu(y[2][0], y[2][1]), pack2bf_valu(y[3][0], y[3][1]));
         }
     };
@@ -373,11 +360,7 @@ __global__ __launch_bounds__(256, 1) void conv_halo_s1_kernel(IGemmParams p, int
         // one barrier before the first fragment of chunk c + 1 is read (during step 8)
         const bool nx = c + 1 >= chunks;                                         // chunk c + 1 belongs to the next tile
         const uint32_t nbuf = lds0 + (uint32_t)(hbuf == 2 ? 0 : hbuf + 1) * HALO_BYTES;
-#ifdef IR_S1_NORM_NOUNITS   // timing experiment: the streamed-fragment form alone (results wrong: nothing is normalised)
-        constexpr int NU = 0;
-#else
         constexpr int NU = T < 6 ? 1 : (T < 8 ? 2 : 0);
-#endif
         constexpr int UI[2] = {T < 8 ? T : 0, T == 6 ? 8 : 9};
         // gaps: one unit: read 22, arithmetic 30..45, write 48; two units: A read 6, arithmetic 14..29, write 31; B read 30, arithmetic 38..53, write 56
         constexpr int RD[2] = {NU == 2 ? 6 : 22, 30}, WR[2] = {NU == 2 ? 31 : 48, 56};
@@ -520,7 +503,6 @@ __global__ __launch_bounds__(256, 1) void conv_halo_s1_kernel(IGemmParams p, int
 #ifdef IR_S1_STAMPS
         const unsigned long long sc0 = __builtin_amdgcn_s_memtime();
 #endif
-        if (IR_KO_S1 != 2 && IR_KO_S1 != 3)
         for (int c = 0; c < chunks; c += 2) {
             const int hb3b = hb3 == 2 ? 0 : hb3 + 1;
             if constexpr (NORM) {
@@ -544,11 +526,11 @@ __global__ __launch_bounds__(256, 1) void conv_halo_s1_kernel(IGemmParams p, int
         unsigned char* ebuf = smem + (hb3 == 0 ? 2 : hb3 - 1) * HALO_BYTES;   // every wave passed the last barrier after its last read of it
 #ifdef IR_S1_STAMPS
         unsigned long long st4v = 0;
-        cs1_epilogue<false, EFULL>(p, ebuf, tid, lane, wid, c16, kq, cur.n0, cur.img, cur.oy0, cur.ox0, cur.trem, IR_KO_S1 != 1 && IR_KO_S1 != 3, IR_KO_S1 == 0, &st4v,
+        cs1_epilogue<false, EFULL>(p, ebuf, tid, lane, wid, c16, kq, cur.n0, cur.img, cur.oy0, cur.ox0, cur.trem, &st4v,
                             PH ? 2 : 1, cur.dy, cur.dx, PH ? p.H : p.Ho, PH ? p.W : p.Wo);
         const unsigned long long st4 = st4v;
 #else
-        cs1_epilogue<false, EFULL>(p, ebuf, tid, lane, wid, c16, kq, cur.n0, cur.img, cur.oy0, cur.ox0, cur.trem, IR_KO_S1 != 1 && IR_KO_S1 != 3, IR_KO_S1 == 0, nullptr,
+        cs1_epilogue<false, EFULL>(p, ebuf, tid, lane, wid, c16, kq, cur.n0, cur.img, cur.oy0, cur.ox0, cur.trem, nullptr,
                             PH ? 2 : 1, cur.dy, cur.dx, PH ? p.H : p.Ho, PH ? p.W : p.Wo);
 #endif
         IR_S1_T(st5);
@@ -573,8 +555,7 @@ __global__ __launch_bounds__(256, 1) void conv_halo_s1_kernel(IGemmParams p, int
 // NHWC in and out, 128-channel output tiles, no activation / gate / second output, a bf16 residual at most, and at least 32 patch
 // tiles per image.
 bool ir_conv_s1_takes(const IGemmParams& p) {
-    static const bool off = getenv("IR_NO_CONV_S1") != nullptr;   // experiment knob
-    if (off || g_ir_plain_kernels || p.fp8 || p.force_generic) return false;
+    if (g_ir_plain_kernels || p.fp8 || p.force_generic) return false;
     if (p.taps != 9 || p.stride != 1 || p.pad != 1 || (p.Cin & 127)) return false;   // chunks % 4 == 0: the weight ring runs through tile boundaries
     if (p.Cout != p.Cout_pad || p.Cout_pad % 128) return false;
     if (p.act != IR_ACT_NONE || p.gate || p.out2 || p.out_f32) return false;
@@ -601,7 +582,7 @@ static int cs1_cus() {
 }
 
 bool ir_conv_s1_norm_takes(const IGemmParams& p) {
-    static const bool off = getenv("IR_NO_S1_NORM") != nullptr;   // experiment knob: the stand-alone GroupNorm apply pass again
+    static const bool off = getenv("IR_NO_S1_NORM") != nullptr;   // the stand-alone GroupNorm apply pass again (bench.py's notes name this switch)
     return !off && p.nrm_scale && p.nrm_shift && !p.up && !p.up2x2 && p.Cin <= 512 && ir_conv_s1_takes(p);
 }
 
@@ -614,8 +595,7 @@ int ir_launch_conv_s1(const IGemmParams& p, hipStream_t s) {
     const long total = ((MT + 7) / 8) * 8 * NT;
     if (total > 0x7fffffffL) return -12;
     const long grid = total < cs1_cus() ? total : cs1_cus();
-    static const bool no_full = getenv("IR_S1_NO_EFULL") != nullptr;   // experiment knob: the general epilogue for every launch
-    const int full = (!no_full && p.Ho % 16 == 0 && p.Wo % 32 == 0 && p.out_scale == 1.f) ? (p.gn_part ? 1 : 2) : 0;
+    const int full = (p.Ho % 16 == 0 && p.Wo % 32 == 0 && p.out_scale == 1.f) ? (p.gn_part ? 1 : 2) : 0;
     const dim3 g((unsigned)grid), b(256);
     if (p.nrm_scale) {
         if (full == 1) hipLaunchKernelGGL((conv_halo_s1_kernel<0, 9, true, 1>), g, b, 0, s, p, tiles_y, tiles_x, (int)total);
@@ -632,7 +612,7 @@ int ir_launch_conv_s1(const IGemmParams& p, hipStream_t s) {
 // sees it (p.up = 1, p.H x p.W the LOW-resolution input, p.Ho = 2 H, p.Wo = 2 W, taps = 9), except that p.wgt holds the four phase matrices
 // [phase = 2 dy + dx][Cout][tap = 2 sy + sx][Cin] (weights.pack_conv_up2x2) with p.wgt_rs = 4 * Cin.
 bool ir_conv_s1_up2x2_takes(const IGemmParams& pin) {
-    static const bool off = getenv("IR_NO_UP2X2") != nullptr;   // experiment knob: the 9-tap form on the upsampled grid
+    static const bool off = getenv("IR_NO_UP2X2") != nullptr;   // the 9-tap form on the upsampled grid (bench.py reads this switch)
     if (off || !pin.up || pin.res) return false;
     IGemmParams p = pin;   // the low-resolution tile grid decides (4 phases per patch), everything else as for the 9-tap kernel
     p.up = 0; p.Ho = pin.H; p.Wo = pin.W;
@@ -650,8 +630,7 @@ int ir_launch_conv_s1_up2x2(const IGemmParams& p, hipStream_t s) {
     const long total = ((MT + 7) / 8) * 8 * NT;
     if (total > 0x7fffffffL) return -12;
     const long grid = total < cs1_cus() ? total : cs1_cus();
-    static const bool no_full = getenv("IR_S1_NO_EFULL") != nullptr;
-    if (!no_full && p.gn_part && p.H % 16 == 0 && p.W % 32 == 0 && p.out_scale == 1.f) hipLaunchKernelGGL((conv_halo_s1_kernel<0, 4, false, 1>), dim3((unsigned)grid), dim3(256), 0, s, p, tiles_y, tiles_x, (int)total);
+    if (p.gn_part && p.H % 16 == 0 && p.W % 32 == 0 && p.out_scale == 1.f) hipLaunchKernelGGL((conv_halo_s1_kernel<0, 4, false, 1>), dim3((unsigned)grid), dim3(256), 0, s, p, tiles_y, tiles_x, (int)total);
     else hipLaunchKernelGGL((conv_halo_s1_kernel<0, 4>), dim3((unsigned)grid), dim3(256), 0, s, p, tiles_y, tiles_x, (int)total);
     return hipGetLastError() == hipSuccess ? 0 : -1;
 }

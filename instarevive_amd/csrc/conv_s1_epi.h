@@ -23,7 +23,7 @@ IR_DEVINL float cs1_acc_read() {
 }
 
 // ebuf: an LDS buffer of cs1e::BYTES bytes that no wave reads any more; t_*: the tile (first channel, image, patch origin, patch index in
-// the image). do_passes / do_stats / mid_stamp: diagnostics of the callers' knock-out and stamp builds (true, true, nullptr in the product).
+// the image). mid_stamp: diagnostic of the callers' stamp builds (nullptr in the product).
 // Output map (the sub-pixel phase form of conv_s1.hip): tile pixel (y, x) is stored at output pixel (omul * y + oyoff, omul * x + oxoff); tile
 // pixels are valid below (hlim, wlim). Identity map: omul = 1, offsets 0, limits = p.Ho, p.Wo. The residual (if any) uses the same map.
 // FULL (round 6): the whole 16 x 32 patch lies inside the image - every tile of a 2048 x 2048 map and all but the last row / column of tiles
@@ -33,7 +33,7 @@ IR_DEVINL float cs1_acc_read() {
 // same order as the general form: results are bit-identical.
 template <bool GATE, bool FULL, bool FGN>
 IR_DEVINL void cs1_epilogue_impl(const IGemmParams& p, unsigned char* ebuf, int tid, int lane, int wid, int c16, int kq, int t_n0, int t_img, int t_oy0,
-                                 int t_ox0, int t_trem, bool do_passes, bool do_stats, unsigned long long* mid_stamp, int omul, int oyoff, int oxoff, int hlim,
+                                 int t_ox0, int t_trem, unsigned long long* mid_stamp, int omul, int oyoff, int oxoff, int hlim,
                                  int wlim) {
     using namespace cs1e;
     float* slab = reinterpret_cast<float*>(ebuf + wid * SLAB);
@@ -162,22 +162,20 @@ IR_DEVINL void cs1_epilogue_impl(const IGemmParams& p, unsigned char* ebuf, int 
             }(), ...);
         }(std::make_integer_sequence<int, 2>{});
     };
-    if (do_passes) {
-        if (p.res) {
-            res_fetch(0);
-            pass(std::integral_constant<int, 0>{}, std::true_type{});
-            pass(std::integral_constant<int, 1>{}, std::true_type{});
-            pass(std::integral_constant<int, 2>{}, std::true_type{});
-            pass(std::integral_constant<int, 3>{}, std::true_type{});
-        } else {
-            pass(std::integral_constant<int, 0>{}, std::false_type{});
-            pass(std::integral_constant<int, 1>{}, std::false_type{});
-            pass(std::integral_constant<int, 2>{}, std::false_type{});
-            pass(std::integral_constant<int, 3>{}, std::false_type{});
-        }
+    if (p.res) {
+        res_fetch(0);
+        pass(std::integral_constant<int, 0>{}, std::true_type{});
+        pass(std::integral_constant<int, 1>{}, std::true_type{});
+        pass(std::integral_constant<int, 2>{}, std::true_type{});
+        pass(std::integral_constant<int, 3>{}, std::true_type{});
+    } else {
+        pass(std::integral_constant<int, 0>{}, std::false_type{});
+        pass(std::integral_constant<int, 1>{}, std::false_type{});
+        pass(std::integral_constant<int, 2>{}, std::false_type{});
+        pass(std::integral_constant<int, 3>{}, std::false_type{});
     }
     if (mid_stamp) *mid_stamp = __builtin_amdgcn_s_memrealtime();
-    if (do_gn && do_stats) {
+    if (do_gn) {
         // Fixed-order workgroup reduction (no atomics, bit-identical run to run). Unit u = 4 channels; lane (L = lane & 15) holds units 2L and
         // 2L+1 over the pixel columns xq, xq + 4, ...: first the four column classes of a wave (lanes L, L+16, L+32, L+48), then the four
         // waves through LDS, then the units of a group.
@@ -216,7 +214,7 @@ IR_DEVINL void cs1_epilogue_impl(const IGemmParams& p, unsigned char* ebuf, int 
 // of the 512-register kernels fell apart: 145 spilled VGPRs and conv_halo_s1_kernel 40.6 -> 46.3 ms per image, profiles/r06_ab_s1_epi_pertile.txt.)
 template <bool GATE, int EMODE = 0>   // EMODE 0: general; 1: FULL with statistics; 2: FULL without (the launch has no gn_part)
 IR_DEVINL void cs1_epilogue(const IGemmParams& p, unsigned char* ebuf, int tid, int lane, int wid, int c16, int kq, int t_n0, int t_img, int t_oy0,
-                            int t_ox0, int t_trem, bool do_passes, bool do_stats, unsigned long long* mid_stamp, int omul, int oyoff, int oxoff, int hlim,
+                            int t_ox0, int t_trem, unsigned long long* mid_stamp, int omul, int oyoff, int oxoff, int hlim,
                             int wlim) {
-    cs1_epilogue_impl<GATE, EMODE != 0, EMODE == 1>(p, ebuf, tid, lane, wid, c16, kq, t_n0, t_img, t_oy0, t_ox0, t_trem, do_passes, do_stats, mid_stamp, omul, oyoff, oxoff, hlim, wlim);
+    cs1_epilogue_impl<GATE, EMODE != 0, EMODE == 1>(p, ebuf, tid, lane, wid, c16, kq, t_n0, t_img, t_oy0, t_ox0, t_trem, mid_stamp, omul, oyoff, oxoff, hlim, wlim);
 }

@@ -262,7 +262,7 @@ __global__ __launch_bounds__(256, 1) void conv_halo_s1_fp8_kernel(IGemmParams p,
         // ---- epilogue through slabs in halo buffer 1 (the last chunk's: every wave passed the last barrier after its last read of it;
         // the next tile's chunk 0 is landing in buffer 0, its chunk 1 is fetched during its own first steps)
         asm volatile("s_nop 15\n\ts_nop 15" ::: "memory");   // the last MFMA results -> v_accvgpr_read
-        cs1_epilogue<true, EFULL>(p, smem + HALO_BYTES, tid, lane, wid, c16, kq, cur.n0, cur.img, cur.oy0, cur.ox0, cur.trem, true, true, nullptr, 1, 0, 0, p.Ho, p.Wo);
+        cs1_epilogue<true, EFULL>(p, smem + HALO_BYTES, tid, lane, wid, c16, kq, cur.n0, cur.img, cur.oy0, cur.ox0, cur.trem, nullptr, 1, 0, 0, p.Ho, p.Wo);
         if (!more) break;
         bid = nbid;
         cur = nxt;
@@ -277,8 +277,7 @@ __global__ __launch_bounds__(256, 1) void conv_halo_s1_fp8_kernel(IGemmParams p,
 // residual at most, Cin a multiple of 128 channels - an even number of 64-channel chunks -, 128-channel output tiles, >= 32 patch tiles
 // per image). Everything else with fp8 operands stays with conv_halo_kernel<.., FP8> (igemm.hip), which is also the plain-kernel reference.
 bool ir_conv_s1_fp8_takes(const IGemmParams& p) {
-    static const bool off = getenv("IR_NO_CONV_S1_FP8") != nullptr;   // experiment knob
-    if (off || g_ir_plain_kernels || !p.fp8 || p.force_generic) return false;
+    if (g_ir_plain_kernels || !p.fp8 || p.force_generic) return false;
     if (p.taps != 9 || p.stride != 1 || p.pad != 1 || (p.Cin & 63)) return false;   // Cin counts pairs: 64 pairs = 128 channels
     if (p.Cout != p.Cout_pad || p.Cout_pad % 128) return false;
     if (p.act != IR_ACT_NONE || !p.gate || p.gate_stride != 0 || p.out2 || p.out_f32) return false;
@@ -302,9 +301,8 @@ int ir_launch_conv_s1_fp8(const IGemmParams& p, hipStream_t s) {
         return n & ~7;
     }();
     const long grid = total < cus ? total : cus;
-    static const bool no_full = getenv("IR_S1_NO_EFULL") != nullptr;   // experiment knob (shared with conv_s1.hip)
     if (p.up) hipLaunchKernelGGL(conv_halo_s1_fp8_kernel<1>, dim3((unsigned)grid), dim3(256), 0, s, p, tiles_y, tiles_x, (int)total);
-    else if (!no_full && p.gn_part && p.Ho % 16 == 0 && p.Wo % 32 == 0) hipLaunchKernelGGL((conv_halo_s1_fp8_kernel<0, 1>), dim3((unsigned)grid), dim3(256), 0, s, p, tiles_y, tiles_x, (int)total);
+    else if (p.gn_part && p.Ho % 16 == 0 && p.Wo % 32 == 0) hipLaunchKernelGGL((conv_halo_s1_fp8_kernel<0, 1>), dim3((unsigned)grid), dim3(256), 0, s, p, tiles_y, tiles_x, (int)total);
     else hipLaunchKernelGGL(conv_halo_s1_fp8_kernel<0>, dim3((unsigned)grid), dim3(256), 0, s, p, tiles_y, tiles_x, (int)total);
     return hipGetLastError() == hipSuccess ? 0 : -1;
 }

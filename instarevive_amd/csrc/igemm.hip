@@ -33,12 +33,8 @@ __device__ uint4 g_zero_page[4096];
 __device__ unsigned long long g_stamps[65536 * 8];  // [0..3] s_memrealtime (100 MHz) per phase edge, [4..7] s_memtime (core clock)
 #define IR_STAMP(k) do { if (threadIdx.x == 0 && blockIdx.x < 65536) { g_stamps[blockIdx.x * 8 + (k)] = __builtin_amdgcn_s_memrealtime(); \
                                                                         g_stamps[blockIdx.x * 8 + 4 + (k)] = __builtin_amdgcn_s_memtime(); } } while (0)
-#ifndef IR_KO
-#define IR_KO 0  // knock-out experiments of tools/conv_stamp.hip (results are wrong by design): 1 no per-step barrier, 2 no weight
-#endif           // re-staging, 3 no LDS fragment reads, 4 no MFMAs
 #else
 #define IR_STAMP(k) do { } while (0)
-#define IR_KO 0
 #endif
 
 // Epilogue shared by the igemm and halo-conv kernels: each wave transposes its accumulators through a private 32 x COLS fp32
@@ -844,21 +840,19 @@ __global__ __launch_bounds__(256, 2) void conv_halo_kernel(IGemmParams p, int ti
 #pragma unroll
         for (int ks = 0; ks < 4; ++ks) {
             __builtin_amdgcn_sched_barrier(0);
-            if (IR_KO != 4) mfmas(ks & 1, 0, 1);
+            mfmas(ks & 1, 0, 1);
             __builtin_amdgcn_sched_barrier(0);
             if (ks + 1 < 4) {
-                if (IR_KO != 3) load_frags(c & 1, s & 1, t, ks + 1, (ks + 1) & 1);
+                load_frags(c & 1, s & 1, t, ks + 1, (ks + 1) & 1);
             } else {
-                if (IR_KO != 1) {
-                    wait_dma();
-                    __syncthreads();  // step s+1's weights have landed; every wave has read the last fragments of step s
-                }
-                if (s + 2 < steps && IR_KO != 2) stage_b(s & 1, t2 * p.Cin + c2 * BK);
+                wait_dma();
+                __syncthreads();  // step s+1's weights have landed; every wave has read the last fragments of step s
+                if (s + 2 < steps) stage_b(s & 1, t2 * p.Cin + c2 * BK);
                 if (t == 0 && c + 1 < chunks) stage_halo((c + 1) & 1);  // whole next chunk's halo, eight steps ahead of its use
-                if (s + 1 < steps && IR_KO != 3) load_frags(cn & 1, (s + 1) & 1, tn, 0, 0);
+                if (s + 1 < steps) load_frags(cn & 1, (s + 1) & 1, tn, 0, 0);
             }
             __builtin_amdgcn_sched_barrier(0);
-            if (IR_KO != 4) mfmas(ks & 1, 1, TM * TN);
+            mfmas(ks & 1, 1, TM * TN);
         }
         t = tn; c = cn;
         if (++t2 == 9) { t2 = 0; ++c2; }
@@ -1191,8 +1185,6 @@ struct GemmPP {
     static constexpr int RING = B_BASE + NSB * B_BYTES;                   // 155648
     static constexpr int TM = 4, TN = 9;                                  // 16 x 16 tiles per wave
     static constexpr int SLAB = 32 * 144 * 4;                             // epilogue: two 16-row tiles of a wave at a time (fp32)
-    static constexpr int PF_OFF = RING;                                   // (-DIR_GPP_PF builds only) 1 KB nobody reads: landing area of the A operand's prefetch touches
-    static constexpr int LDS_PF = RING + 1024 > 8 * SLAB ? RING + 1024 : 8 * SLAB;
     static constexpr int LDS = RING > 8 * SLAB ? RING : 8 * SLAB;
 };
 
@@ -1204,22 +1196,16 @@ struct GemmPP {
 // add in the epilogue: started in the accumulators it saved one instruction per element, but bias + sum rounds differently from sum + bias, and the
 // 128 x 128 kernel that takes the same linear at smaller row counts adds it last - a tile-sharded frame then differed from the unsharded one by
 // up to 4 grey levels, tests/test_cli_gpu.py::test_tile_sharding_two_ranks_on_one_gpu.)
-// Experiment knob (-DIR_GPP_PF=d, d > 0; never set in the library): every A-issuing wave also touches, per k-tile, the rows of its four pieces d
+// Measured and not kept (the switch is retired; the code is in git history): every A-issuing wave also touching, per k-tile, the rows of its four pieces d
 // k-tiles AHEAD of the tile it stages (one LDS-DMA piece of 64 rows x 16 B into a landing area nobody reads), to turn the A fetch - a miss for all
 // four column-tile workgroups of a row tile, which run in lockstep on one XCD - into an L2 hit. Measured SLOWER whatever d (2, 4, 8): the kernel
 // 17.4 -> 19.6 ms per image, every shape -12 to -16 % (profiles/r06_ab_gemm_l2_prefetch.txt). One more piece per four is +12 % of the bytes this
 // loop moves through LDS-DMA and it costs +13 %: the loop's time follows the LDS-DMA volume (34 KB per k-tile and CU), not the A operand's latency.
-#ifndef IR_GPP_PF
-#define IR_GPP_PF 0
-#endif
-#ifndef IR_GPP_KO
-#define IR_GPP_KO 0   // knock-outs of the fp32-residual row phase, timing only (results wrong by design; never set in the library): 1 no residual
-#endif                // read, 2 no bf16 copy, 3 no fp32 store
 template <int ACT_T, int KIND_T, bool UNIT>
 __global__ __launch_bounds__(512, 1) void gemm_pp_kernel(IGemmParams p) {
     typedef GemmPP G;
     typedef __attribute__((ext_vector_type(4))) float f32x4_t;
-    __shared__ __attribute__((aligned(1024))) unsigned char smem[IR_GPP_PF > 0 ? G::LDS_PF : G::LDS];  // the ONLY LDS object of the kernel
+    __shared__ __attribute__((aligned(1024))) unsigned char smem[G::LDS];  // the ONLY LDS object of the kernel
     const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
     const int wu = __builtin_amdgcn_readfirstlane(wid);
     const int grp = wu >> 2, wq = wu & 3;   // half (column group) and row quarter of this wave
@@ -1253,8 +1239,6 @@ __global__ __launch_bounds__(512, 1) void gemm_pp_kernel(IGemmParams p) {
             dst[i] = G::B_BASE + q * 1024;
         }
     }
-    // L2 prefetch touch (IR_GPP_PF): lane l of A-issuing wave wq touches row 64 * wq + l (16 bytes of the k-tile's half line)
-    const bf16_t* pf_src = p.in + (long)min(m0 + wq * 64 + lane, p.M - 1) * p.in_cs;
     // prologue: A tiles 0..3 and B tiles 0..2 by all 8 waves (A piece q = wu + 8*i, i < 2; B piece q = wu + 8*i, i < 3, q < 18)
     auto issue_prologue = [&]() __attribute__((always_inline)) {
 #pragma unroll
@@ -1293,11 +1277,7 @@ __global__ __launch_bounds__(512, 1) void gemm_pp_kernel(IGemmParams p) {
         for (int j = 0; j < G::TN; ++j) acc[i][j] = f32x4_t{0.f, 0.f, 0.f, 0.f};
     // (Round 5 tried the GELU as packed fp32 pairs - v_pk_add / v_pk_mul / v_pk_fma - on the slab-write side: the fc1 launch alone 221 -> 210 us, but
     // at the kernel's 256-VGPR limit the pair form spilled 23 registers and every launch paid for the scratch set-up: profiles/r05_ab_gemm_pk_gelu.txt.)
-#ifndef IR_GKO
-#define IR_GKO 0  // knock-out builds for timing only (-DIR_GKO=n, results wrong by design; never set in the library): 1 no MFMAs, 2 no
-#endif            // LDS-DMA in the K loop, 3 no fragment reads - DESIGN.md section 7 quotes the three timings
     auto matrix = [&]() __attribute__((always_inline)) {
-        if (IR_GKO == 1) return;
         __builtin_amdgcn_s_setprio(1);
 #pragma unroll
         for (int j = 0; j < G::TN; ++j)
@@ -1323,9 +1303,9 @@ __global__ __launch_bounds__(512, 1) void gemm_pp_kernel(IGemmParams p) {
                 unsigned char* base = smem + ((kt + 3) & 3) * G::B_BYTES;
                 const int ko = (kt + 3) * G::BK;
 #pragma unroll
-                for (int i = 0; i < 5; ++i) if (IR_GKO != 2 && IR_GKO != 4) glds16(src[i] + ko, (lds_ptr_t)(base + dst[i]));   // (4: no B pieces only)
+                for (int i = 0; i < 5; ++i) glds16(src[i] + ko, (lds_ptr_t)(base + dst[i]));
             }
-            if (kt + 1 < KT && IR_GKO != 3) read_frags(sa1, (kt + 1) & 3);
+            if (kt + 1 < KT) read_frags(sa1, (kt + 1) & 3);
             sa1 = sa1 == G::NSA - 1 ? 0 : sa1 + 1;
             __builtin_amdgcn_sched_barrier(0);
             __builtin_amdgcn_s_barrier();
@@ -1338,13 +1318,12 @@ __global__ __launch_bounds__(512, 1) void gemm_pp_kernel(IGemmParams p) {
                 unsigned char* base = smem + sa4 * G::A_BYTES;
                 const int ko = (kt + 4) * G::BK;
 #pragma unroll
-                for (int i = 0; i < 4; ++i) if (IR_GKO != 2 && IR_GKO != 5) glds16(src[i] + ko, (lds_ptr_t)(base + dst[i]));   // (5: no A pieces only)
-                if (IR_GPP_PF > 0) glds16(pf_src + min(kt + 4 + IR_GPP_PF, KT - 1) * G::BK, (lds_ptr_t)(smem + G::PF_OFF));   // part of the batch: BATCH pieces
+                for (int i = 0; i < 4; ++i) glds16(src[i] + ko, (lds_ptr_t)(base + dst[i]));
             }
-            if (IR_GKO != 3 || kt == 0) read_frags(sa, kt & 3);
+            read_frags(sa, kt & 3);
             // A(kt+1) has landed; the batches of A(kt+2) .. A(kt+4) may be in flight (fewer at the end of the K loop)
             const int rem = KT - 2 - kt;
-            constexpr int BATCH = IR_GPP_PF > 0 ? 5 : 4;
+            constexpr int BATCH = 4;
             if (rem >= 3) wait_vm<3 * BATCH>(); else if (rem == 2) wait_vm<2 * BATCH>(); else if (rem == 1) wait_vm<BATCH>(); else wait_dma();
             sa = sa == G::NSA - 1 ? 0 : sa + 1;
             sa4 = sa4 == G::NSA - 1 ? 0 : sa4 + 1;
@@ -1472,8 +1451,7 @@ __global__ __launch_bounds__(512, 1) void gemm_pp_kernel(IGemmParams p) {
         for (int it = 0; it < n; ++it) {
             const int v = (it0 + it) * 64 + lane, row = v / 36, c4 = (v - row * 36) * 4;
             const int m = min(mw + hh * 32 + row, p.M - 1);
-            if (IR_GPP_KO == 1) rr[it] = f32x4_t{0.f, 0.f, 0.f, 0.f};
-            else rr[it] = *reinterpret_cast<const f32x4_t*>(resf + (unsigned)(m * p.res_cs + nw + c4));
+            rr[it] = *reinterpret_cast<const f32x4_t*>(resf + (unsigned)(m * p.res_cs + nw + c4));
         }
     };
     auto k1_rows = [&](auto hc, auto i0c, auto nc, const f32x4_t* rr) __attribute__((always_inline)) {
@@ -1485,36 +1463,22 @@ __global__ __launch_bounds__(512, 1) void gemm_pp_kernel(IGemmParams p) {
             const int m = mw + hh * 32 + row;
             const f32x4_t o = *reinterpret_cast<const f32x4_t*>(&slab[row * 144 + c4]) + rr[it];
             if (m < p.M) {
-                if (IR_GPP_KO != 3) *reinterpret_cast<f32x4_t*>(outf + (unsigned)(m * p.out_cs + nw + c4)) = o;
-                if (p.out2 && IR_GPP_KO != 2) *reinterpret_cast<uint2*>(p.out2 + (unsigned)(m * p.out2_cs + nw + c4)) = make_uint2(pack2bf(o[0], o[1]), pack2bf(o[2], o[3]));
+                *reinterpret_cast<f32x4_t*>(outf + (unsigned)(m * p.out_cs + nw + c4)) = o;
+                if (p.out2) *reinterpret_cast<uint2*>(p.out2 + (unsigned)(m * p.out2_cs + nw + c4)) = make_uint2(pack2bf(o[0], o[1]), pack2bf(o[2], o[3]));
             }
         }
     };
-#ifndef IR_GPP_K1
-#define IR_GPP_K1 0   // residual request schedule of the instantiated KIND 1 form: 0 = three batches of six per half, each after the previous one's stores;
-#endif                // 1 = IR_GPP_K1_NA vectors of a half requested BEFORE its slab is written, the rest behind it. Measured in round 6 (6 + 12, 9 + 9, 12 + 6
-#ifndef IR_GPP_K1_NA  // against 0, profiles/r06_gemm_k1_schedules.txt): 55 us per 1152 -> 1152 launch and 150 us per 4608 -> 1152 launch whatever the schedule -
-#define IR_GPP_K1_NA 9   // the row phase is bound by the memory system's burst (189 MB in and out per launch while every CU is in its epilogue), not by the
-#endif                   // latency of the requests. 0 stays.
+    // Residual request schedule: three batches of six per half, each after the previous one's stores. Measured in round 6 and not kept (the switch
+    // is retired; the code is in git history): 6, 9 or 12 vectors of a half requested BEFORE its slab is written, the rest behind it
+    // (profiles/r06_gemm_k1_schedules.txt) - 55 us per 1152 -> 1152 launch and 150 us per 4608 -> 1152 launch whatever the schedule: the row phase is
+    // bound by the memory system's burst (189 MB in and out per launch while every CU is in its epilogue), not by the latency of the requests.
     auto run_kind1 = [&](auto hc) __attribute__((always_inline)) {
-        constexpr int hh = decltype(hc)::value;
-        using I0 = std::integral_constant<int, 0>;
-        if constexpr (KIND_T == 1 && IR_GPP_K1 == 1) {
-            constexpr int NA = IR_GPP_K1_NA;
-            f32x4_t ra[NA], rb[18 - NA > 0 ? 18 - NA : 1];
-            k1_load(hc, I0{}, std::integral_constant<int, NA>{}, ra);
-            write_half(hc);   // this half's 72 accumulator registers die here
-            if constexpr (NA < 18) k1_load(hc, std::integral_constant<int, NA>{}, std::integral_constant<int, 18 - NA>{}, rb);
-            k1_rows(hc, I0{}, std::integral_constant<int, NA>{}, ra);
-            if constexpr (NA < 18) k1_rows(hc, std::integral_constant<int, NA>{}, std::integral_constant<int, 18 - NA>{}, rb);
-        } else {
-            write_half(hc);
-            f32x4_t rr[6];
-            [&]<int... BT>(std::integer_sequence<int, BT...>) {
-                ((k1_load(hc, std::integral_constant<int, 6 * BT>{}, std::integral_constant<int, 6>{}, rr),
-                  k1_rows(hc, std::integral_constant<int, 6 * BT>{}, std::integral_constant<int, 6>{}, rr)), ...);
-            }(std::make_integer_sequence<int, 3>{});
-        }
+        write_half(hc);
+        f32x4_t rr[6];
+        [&]<int... BT>(std::integer_sequence<int, BT...>) {
+            ((k1_load(hc, std::integral_constant<int, 6 * BT>{}, std::integral_constant<int, 6>{}, rr),
+              k1_rows(hc, std::integral_constant<int, 6 * BT>{}, std::integral_constant<int, 6>{}, rr)), ...);
+        }(std::make_integer_sequence<int, 3>{});
         done_half();
     };
     auto rows_kind2 = [&](auto hc) __attribute__((always_inline)) {
@@ -1551,23 +1515,15 @@ __global__ __launch_bounds__(512, 1) void gemm_pp_kernel(IGemmParams p) {
 
 int g_ir_plain_kernels = 0;
 
-// Grid of a tiled launch (see tile_of_block): one block per tile for small launches, the XCD-padded order otherwise. IR_NO_TILE_LIN: experiment knob.
-static long tile_grid(long MT, long NT) {
-    static const bool no_lin = getenv("IR_NO_TILE_LIN") != nullptr;
-    return ((MT & 7) && MT < 64 && !no_lin) ? MT * NT : ((MT + 7) / 8) * 8 * NT;
-}
+// Grid of a tiled launch (see tile_of_block): one block per tile for small launches, the XCD-padded order otherwise.
+static long tile_grid(long MT, long NT) { return ((MT & 7) && MT < 64) ? MT * NT : ((MT + 7) / 8) * 8 * NT; }
 
 // Shortest reduction gemm_pp_kernel takes: 8 k-tiles. (Its prologue needs 4; with the limit at 6 SwinIR's qkv projection - K = 192, N = 576 =
-// 2 x 288 - runs here: measured in round 4 at 36 us per launch, exactly what igemm_kernel<128, 64> needs for it: no gain, limit left at 8.
-// IR_GEMM_PP_MIN_K: experiment knob.)
-static int gemm_pp_min_k() {
-    static const int v = [] { const char* e = getenv("IR_GEMM_PP_MIN_K"); const int k = e ? atoi(e) : 8 * GemmPP::BK; return k < 4 * GemmPP::BK ? 4 * GemmPP::BK : k; }();
-    return v;
-}
+// 2 x 288 - runs here: measured in round 4 at 36 us per launch, exactly what igemm_kernel<128, 64> needs for it: no gain, limit left at 8.)
+constexpr int GEMM_PP_MIN_K = 8 * GemmPP::BK;
 static bool takes_gemm_pp(const IGemmParams& p) {
-    static const bool off = getenv("IR_NO_GEMM_PP") != nullptr;  // experiment knob
-    if (off || g_ir_plain_kernels || p.fp8 || p.taps != 1 || p.force_generic || !p.vec || p.gn_part) return false;
-    if (p.Cout != p.Cout_pad || p.Cout % GemmPP::BN || p.Cin % GemmPP::BK || p.Cin < gemm_pp_min_k()) return false;
+    if (g_ir_plain_kernels || p.fp8 || p.taps != 1 || p.force_generic || !p.vec || p.gn_part) return false;
+    if (p.Cout != p.Cout_pad || p.Cout % GemmPP::BN || p.Cin % GemmPP::BK || p.Cin < GEMM_PP_MIN_K) return false;
     const long span = (long)p.M * std::max(std::max(p.out_cs, p.res ? p.res_cs : 0), p.out2 ? p.out2_cs : 0);
     if (span >= (1L << 31)) return false;  // the epilogue's 32-bit element offsets
     const long blocks = (long)((p.M + GemmPP::BM - 1) / GemmPP::BM) * (p.Cout / GemmPP::BN);
@@ -1576,22 +1532,19 @@ static bool takes_gemm_pp(const IGemmParams& p) {
 // The transposed second output (IGemmParams::vt_out) is honoured by gemm_pp_kernel's bf16 / no-residual form on whole tiles only
 static bool igemm_vec(const IGemmParams& p);
 int ir_igemm_writes_vt(const IGemmParams& pin) {
-    static const bool off = getenv("IR_NO_VT_FUSE") != nullptr;   // experiment knob
     IGemmParams p = pin;
     p.vec = igemm_vec(p);
     if (p.ks_ws && ir_igemm_splitk(p) > 1) return 0;
-    return !off && p.vt_out && takes_gemm_pp(p) && !p.res && !p.out_f32 && !p.out2 && p.M % GemmPP::BM == 0 && p.vt_T > 0 && p.vt_T % 64 == 0 &&
+    return p.vt_out && takes_gemm_pp(p) && !p.res && !p.out_f32 && !p.out2 && p.M % GemmPP::BM == 0 && p.vt_T > 0 && p.vt_T % 64 == 0 &&
            p.vt_col0 % GemmPP::BN == 0 && p.vt_hd * 2 == 144 && (p.Cout - p.vt_col0) % 144 == 0 && (p.vt_ld & 7) == 0 && (p.vt_bs & 7) == 0 &&
            !(reinterpret_cast<uintptr_t>(p.vt_out) & 15);
 }
 static int launch_gemm_pp(const IGemmParams& p, hipStream_t s) {
     const int MT = (p.M + GemmPP::BM - 1) / GemmPP::BM, NT = p.Cout / GemmPP::BN;
     const dim3 grid(((MT + 7) / 8) * 8 * NT);
-    static const bool generic = getenv("IR_GEMM_PP_GENERIC") != nullptr;   // experiment knob: the run-time form for every launch
     const bool unit = !p.gate && p.out_scale == 1.f;
     const int kind = (!p.res && !p.out_f32 && !p.out2) ? 0 : (p.res && p.res_f32 && p.out_f32 && p.res_mod == 0) ? 1 : 2;
-    if (generic) hipLaunchKernelGGL((gemm_pp_kernel<-1, -1, false>), grid, dim3(512), 0, s, p);
-    else if (kind == 0 && unit && p.act == IR_ACT_NONE) hipLaunchKernelGGL((gemm_pp_kernel<IR_ACT_NONE, 0, true>), grid, dim3(512), 0, s, p);
+    if (kind == 0 && unit && p.act == IR_ACT_NONE) hipLaunchKernelGGL((gemm_pp_kernel<IR_ACT_NONE, 0, true>), grid, dim3(512), 0, s, p);
     else if (kind == 0 && unit && p.act == IR_ACT_GELU_TANH) hipLaunchKernelGGL((gemm_pp_kernel<IR_ACT_GELU_TANH, 0, true>), grid, dim3(512), 0, s, p);
     else if (kind == 1 && p.act == IR_ACT_NONE) hipLaunchKernelGGL((gemm_pp_kernel<IR_ACT_NONE, 1, false>), grid, dim3(512), 0, s, p);
     else hipLaunchKernelGGL((gemm_pp_kernel<-1, -1, false>), grid, dim3(512), 0, s, p);
@@ -1603,11 +1556,8 @@ static int launch_halo_pp(const IGemmParams& p, hipStream_t s) {
     const long MT = (long)p.NB * tiles_y * tiles_x, NT = p.Cout_pad / 128;
     const long grid = tile_grid(MT, NT);
     if (grid > 0x7fffffffL) return -12;
-    static const bool m16 = getenv("IR_NO_MFMA16") == nullptr;  // 16x16x32 MFMA form by default (knob: A/B against 32x32x16)
-    if (m16 && p.up) hipLaunchKernelGGL((conv_halo_pp_kernel<1, true>), dim3((unsigned)grid), dim3(512), 0, s, p, tiles_y, tiles_x);
-    else if (m16) hipLaunchKernelGGL((conv_halo_pp_kernel<0, true>), dim3((unsigned)grid), dim3(512), 0, s, p, tiles_y, tiles_x);
-    else if (p.up) hipLaunchKernelGGL((conv_halo_pp_kernel<1>), dim3((unsigned)grid), dim3(512), 0, s, p, tiles_y, tiles_x);
-    else hipLaunchKernelGGL((conv_halo_pp_kernel<0>), dim3((unsigned)grid), dim3(512), 0, s, p, tiles_y, tiles_x);
+    if (p.up) hipLaunchKernelGGL((conv_halo_pp_kernel<1, true>), dim3((unsigned)grid), dim3(512), 0, s, p, tiles_y, tiles_x);
+    else hipLaunchKernelGGL((conv_halo_pp_kernel<0, true>), dim3((unsigned)grid), dim3(512), 0, s, p, tiles_y, tiles_x);
     return hipGetLastError() == hipSuccess ? 0 : -1;
 }
 
@@ -1622,17 +1572,14 @@ static int launch_halo(const IGemmParams& p, hipStream_t s) {
         else hipLaunchKernelGGL((conv_halo_kernel<BN, 0, false, true>), dim3((unsigned)grid), dim3(256), 0, s, p, tiles_y, tiles_x);
         return hipGetLastError() == hipSuccess ? 0 : -1;
     }
-    static const bool m16 = getenv("IR_NO_MFMA16") == nullptr;  // 16x16x32 MFMA form by default (knob: A/B against 32x32x16)
-    if (m16 && p.up) hipLaunchKernelGGL((conv_halo_kernel<BN, 1, true>), dim3((unsigned)grid), dim3(256), 0, s, p, tiles_y, tiles_x);
-    else if (m16) hipLaunchKernelGGL((conv_halo_kernel<BN, 0, true>), dim3((unsigned)grid), dim3(256), 0, s, p, tiles_y, tiles_x);
-    else if (p.up) hipLaunchKernelGGL((conv_halo_kernel<BN, 1>), dim3((unsigned)grid), dim3(256), 0, s, p, tiles_y, tiles_x);
-    else hipLaunchKernelGGL((conv_halo_kernel<BN, 0>), dim3((unsigned)grid), dim3(256), 0, s, p, tiles_y, tiles_x);
+    if (p.up) hipLaunchKernelGGL((conv_halo_kernel<BN, 1, true>), dim3((unsigned)grid), dim3(256), 0, s, p, tiles_y, tiles_x);
+    else hipLaunchKernelGGL((conv_halo_kernel<BN, 0, true>), dim3((unsigned)grid), dim3(256), 0, s, p, tiles_y, tiles_x);
     return hipGetLastError() == hipSuccess ? 0 : -1;
 }
 
 // Sub-pixel phase form through the 4-wave halo kernel (64- or 128-channel tiles; what conv_halo_s1_kernel<0, 4> does not take)
 static bool takes_halo_up2x2(const IGemmParams& p) {
-    static const bool off = getenv("IR_NO_UP2X2") != nullptr;   // experiment knob (shared with conv_s1.hip)
+    static const bool off = getenv("IR_NO_UP2X2") != nullptr;   // (shared with conv_s1.hip: bench.py reads this switch)
     return !off && !g_ir_plain_kernels && p.up && p.taps == 9 && p.stride == 1 && !p.fp8 && !p.res && !p.gn_part && !p.gate && !p.out2 && !p.out_f32 &&
            p.Cin % 64 == 0 && p.Cout_pad % 64 == 0 && p.Ho == 2 * p.H && p.Wo == 2 * p.W && igemm_vec(p);
 }
@@ -1685,16 +1632,13 @@ __global__ __launch_bounds__(256) void splitk_finish_kernel(IGemmParams p, const
 // Split count ir_launch_igemm uses for p (0: no split): only launches whose caller allows it (p.allow_splitk) and provides the workspace
 // (p.ks_ws, ir_igemm_splitk(p) * p.M * p.Cout_pad floats), with at most 48 output tiles and at least 24 k-tiles.
 int ir_igemm_splitk(const IGemmParams& p) {
-    static const bool off = getenv("IR_NO_SPLITK") != nullptr;   // experiment knob
-    if (!p.allow_splitk || off || p.fp8 || p.gn_part || (p.Cin & 63) || (p.Cout_pad & 3)) return 0;
+    // most tiles a split launch may have, fewest k-tiles it must have, workgroups aimed at, fewest k-tiles per split
+    constexpr int max_tiles = 48, min_kt = 24, target = 256, per_min = 8;
+    if (!p.allow_splitk || p.fp8 || p.gn_part || (p.Cin & 63) || (p.Cout_pad & 3)) return 0;
     const int BN = p.Cout_pad % 128 == 0 ? 128 : (p.Cout_pad % 64 == 0 ? 64 : 32);
     const int tiles = ((p.M + 127) / 128) * (p.Cout_pad / BN), KT = p.taps * (p.Cin / 64);
-    // experiment knobs (defaults = the shipped heuristic): most tiles a split launch may have, fewest k-tiles it must have, workgroups aimed at,
-    // fewest k-tiles per split
-    static const int max_tiles = getenv("IR_SPLITK_TILES") ? atoi(getenv("IR_SPLITK_TILES")) : 48, min_kt = getenv("IR_SPLITK_KT") ? atoi(getenv("IR_SPLITK_KT")) : 24;
-    static const int target = getenv("IR_SPLITK_TARGET") ? atoi(getenv("IR_SPLITK_TARGET")) : 256, per_min = getenv("IR_SPLITK_PER") ? atoi(getenv("IR_SPLITK_PER")) : 8;
     if (tiles > max_tiles || KT < min_kt) return 0;
-    int ks = std::min(target / tiles, KT / std::max(per_min, 1));
+    const int ks = std::min(target / tiles, KT / per_min);
     if (ks < 2) return 0;
     const int per = (KT + ks - 1) / ks;
     return (KT + per - 1) / per;   // no empty split
@@ -1715,20 +1659,17 @@ static int launch_cfg(const IGemmParams& pin, hipStream_t s) {
     } else {
         p.ksplit = 0;
     }
-    static const bool force32 = getenv("IR_IGEMM_BK32") != nullptr;  // experiment knob
-    const bool k64 = (p.Cin & 63) == 0 && !force32;
+    const bool k64 = (p.Cin & 63) == 0;
     // the four-tile ring (igemm_kernel's NST): launches of at most one workgroup per CU with at least eight k-tiles per workgroup (with more
     // workgroups the two-tile form's second workgroup per CU covers the waits better: 16384 x 640 -> 5120 at M = 1024 ran 17 against 25 us)
-    static const int ring_max = getenv("IR_IGEMM_RING_MAX") ? atoi(getenv("IR_IGEMM_RING_MAX")) : 256;   // experiment knob (0: never)
-    static const bool m16r = getenv("IR_NO_MFMA16") == nullptr;
+    constexpr int ring_max = 256;
     const int kt_all = p.taps * (p.Cin / 64), kt_per = ks > 1 ? (kt_all + ks - 1) / ks : kt_all;
-    if (k64 && m16r && !g_ir_plain_kernels && (long)tiles * (ks > 1 ? ks : 1) <= ring_max && kt_per >= 8) {
+    if (k64 && !g_ir_plain_kernels && (long)tiles * (ks > 1 ? ks : 1) <= ring_max && kt_per >= 8) {
         // ... and with EIGHT waves (two per SIMD, each a 32-row slice of the tile) where the tile is 2 x 2 waves: alone on its SIMD a wave pays the
         // issue of its LDS-DMA pieces (about 64 cycles each, 8 per k-tile = as long as its 32 MFMAs) with the matrix pipe idle; the second wave's
         // MFMAs run under them. Not with fused GroupNorm statistics (their block reduction sums per wave row: another order).
-        static const bool no_w8 = getenv("IR_IGEMM_NO_W8") != nullptr;   // experiment knob
         if constexpr (WM == 2 && WN == 2) {
-            if (!no_w8 && !p.gn_part) {
+            if (!p.gn_part) {
                 if (p.taps == 9) hipLaunchKernelGGL((igemm_kernel<BM, BN, 4, 2, 9, 64, true, 4>), dim3(grid), dim3(512), 0, s, p);
                 else hipLaunchKernelGGL((igemm_kernel<BM, BN, 4, 2, 1, 64, true, 4>), dim3(grid), dim3(512), 0, s, p);
                 goto launched;
@@ -1737,14 +1678,10 @@ static int launch_cfg(const IGemmParams& pin, hipStream_t s) {
         if (p.taps == 9) hipLaunchKernelGGL((igemm_kernel<BM, BN, WM, WN, 9, 64, true, 4>), dim3(grid), dim3(256), 0, s, p);
         else hipLaunchKernelGGL((igemm_kernel<BM, BN, WM, WN, 1, 64, true, 4>), dim3(grid), dim3(256), 0, s, p);
     } else if (p.taps == 9) {
-        static const bool m16t = getenv("IR_NO_MFMA16") == nullptr;
-        if (k64 && m16t) hipLaunchKernelGGL((igemm_kernel<BM, BN, WM, WN, 9, 64, true>), dim3(grid), dim3(256), 0, s, p);
-        else if (k64) hipLaunchKernelGGL((igemm_kernel<BM, BN, WM, WN, 9, 64>), dim3(grid), dim3(256), 0, s, p);
+        if (k64) hipLaunchKernelGGL((igemm_kernel<BM, BN, WM, WN, 9, 64, true>), dim3(grid), dim3(256), 0, s, p);
         else hipLaunchKernelGGL((igemm_kernel<BM, BN, WM, WN, 9, 32>), dim3(grid), dim3(256), 0, s, p);
     } else {
-        static const bool m16 = getenv("IR_NO_MFMA16") == nullptr;  // 16x16x32 MFMA form of the 128x128 GEMM (knob: A/B against 32x32x16)
-        if (k64 && m16) hipLaunchKernelGGL((igemm_kernel<BM, BN, WM, WN, 1, 64, true>), dim3(grid), dim3(256), 0, s, p);
-        else if (k64) hipLaunchKernelGGL((igemm_kernel<BM, BN, WM, WN, 1, 64>), dim3(grid), dim3(256), 0, s, p);
+        if (k64) hipLaunchKernelGGL((igemm_kernel<BM, BN, WM, WN, 1, 64, true>), dim3(grid), dim3(256), 0, s, p);
         else hipLaunchKernelGGL((igemm_kernel<BM, BN, WM, WN, 1, 32>), dim3(grid), dim3(256), 0, s, p);
     }
 launched:
@@ -1758,12 +1695,10 @@ launched:
 
 // Fused GroupNorm statistics: which kernel would run and how many pixel tiles per image it has (0: cannot fuse).
 static bool takes_halo(const IGemmParams& p) {
-    static const bool no_halo = getenv("IR_NO_HALO") != nullptr;  // experiment knob
-    return p.taps == 9 && p.stride == 1 && p.pad == 1 && (p.Cin & 63) == 0 && !p.force_generic && !no_halo && p.Cout_pad % 64 == 0;
+    return p.taps == 9 && p.stride == 1 && p.pad == 1 && (p.Cin & 63) == 0 && !p.force_generic && p.Cout_pad % 64 == 0;
 }
 static bool takes_halo_pp(const IGemmParams& p) {  // the 8-wave ping-pong variant: 16 x 16 patches x 128 channels
-    static const bool no_pp = getenv("IR_NO_CONV_PP") != nullptr;  // experiment knob
-    return takes_halo(p) && !p.fp8 && p.Cout_pad % 128 == 0 && p.Cin >= 128 && !no_pp && !g_ir_plain_kernels;  // measured with the 16x16x32 MFMAs: +8 % at 512 channels,
+    return takes_halo(p) && !p.fp8 && p.Cout_pad % 128 == 0 && p.Cin >= 128 && !g_ir_plain_kernels;  // measured with the 16x16x32 MFMAs: +8 % at 512 channels,
                                                                                // +7 % at 256, +2 % at 128 over the 4-wave kernel
 }
 int ir_igemm_gn_chunks(const IGemmParams& p) {

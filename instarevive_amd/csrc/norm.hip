@@ -112,48 +112,6 @@ __global__ __launch_bounds__(256) void gn_finalize_kernel(const float* __restric
     }
 }
 
-// Finalise from per-GROUP partials written by the producing conv's epilogue (igemm.hip): part [N][chunks][2][G]. Same fixed-order
-// fp64 reduction as above (thread (g, slice) sums every spg-th chunk, then the slices are added in order). grid = N, block = 256.
-__global__ __launch_bounds__(256) void gn_finalize_groups_kernel(const float* __restrict__ part, const float* __restrict__ gamma,
-                                                                 const float* __restrict__ beta, float* __restrict__ scale,
-                                                                 float* __restrict__ shift, int HW, int C, int G, int chunks,
-                                                                 float eps) {
-    __shared__ double s_mean[64], s_rstd[64];
-    __shared__ double s_part[2][256];
-    const int n = blockIdx.x, tid = threadIdx.x;
-    const int cpg = C / G;
-    const int spg = 256 / G;
-    const int g = tid / spg, sl = tid % spg;
-    double s = 0.0, q = 0.0;
-    if (g < G) {
-        for (int ch = sl; ch < chunks; ch += spg) {
-            const float* pp = part + ((long)n * chunks + ch) * 2 * G;
-            s += (double)pp[g];
-            q += (double)pp[G + g];
-        }
-    }
-    s_part[0][tid] = s;
-    s_part[1][tid] = q;
-    __syncthreads();
-    if (tid < G) {
-        s = 0.0; q = 0.0;
-        for (int i = 0; i < spg; ++i) { s += s_part[0][tid * spg + i]; q += s_part[1][tid * spg + i]; }
-        const double cnt = (double)HW * cpg;
-        const double mean = s / cnt;
-        double var = q / cnt - mean * mean;
-        if (var < 0.0) var = 0.0;
-        s_mean[tid] = mean;
-        s_rstd[tid] = 1.0 / sqrt(var + (double)eps);
-    }
-    __syncthreads();
-    for (int c = tid; c < C; c += 256) {
-        const int gg = c / cpg;
-        const double a = s_rstd[gg] * (double)gamma[c];
-        scale[(long)n * C + c] = (float)a;
-        shift[(long)n * C + c] = (float)((double)beta[c] - s_mean[gg] * a);
-    }
-}
-
 // y = act(x*scale + shift); x,y: [N][HW][C] bf16. grid = (blocks, N): blockIdx.y is the image, the blocks of an image stride over
 // its 16-byte vectors. The stride (blocks * 256) is a multiple of the vectors per pixel, so a thread always meets the same 8
 // channels: its scale / shift live in registers and the loop has no index arithmetic beyond one add (the first version divided
@@ -240,23 +198,6 @@ int ir_launch_groupnorm(const bf16_t* x, bf16_t* y, const float* gamma, const fl
     return hipGetLastError() == hipSuccess ? 0 : -1;
 }
 
-// First reduction stage for many tiles: block (r, n) adds the per-group partials of a contiguous range of chunks in a fixed order
-// (4 interleaved slices per value, then the slices in order) -> part2 [N][R][2][G]. grid = (R, N), block = 256, 2*G <= 64.
-__global__ __launch_bounds__(256) void gn_reduce_groups_kernel(const float* __restrict__ part, float* __restrict__ part2, int G, int chunks,
-                                                               int R) {
-    __shared__ float s_red[4][64];
-    const int r = blockIdx.x, n = blockIdx.y, tid = threadIdx.x;
-    const int idx = tid & 63, sl = tid >> 6;
-    const int per = (chunks + R - 1) / R;
-    const int c0 = r * per, c1 = min(c0 + per, chunks);
-    float a = 0.f;
-    if (idx < 2 * G)
-        for (int ch = c0 + sl; ch < c1; ch += 4) a += part[((long)n * chunks + ch) * 2 * G + idx];
-    s_red[sl][idx] = a;
-    __syncthreads();
-    if (tid < 2 * G) part2[((long)n * R + r) * 2 * G + tid] = ((s_red[0][tid] + s_red[1][tid]) + s_red[2][tid]) + s_red[3][tid];
-}
-
 // One workgroup per (group, image): thread t adds the partials of chunks t, t + 256, ... in fp64, then a fixed-order tree over the 256
 // threads (bit-identical run to run), then the group's channels get their scale / shift. Replaces the single-block finalise (12-14 us of
 // dependent loads per call) and, for images with more than 512 tiles, the extra reduction launch in front of it. grid = (G, N).
@@ -298,20 +239,7 @@ int ir_launch_groupnorm_fused(const bf16_t* x, bf16_t* y, const float* gamma, co
     if (HW >= (1L << 31)) return -3;
     float* scale = ws;                 // [N][C]
     float* shift = ws + (long)N * C;   // [N][C]
-    static const bool old_finalize = getenv("IR_GN_FINALIZE_V1") != nullptr;   // experiment knob: round 2's single-block finalise
-    if (old_finalize) {
-        if (chunks > 512) {                // two-stage: a single finalise block per image would crawl through megabytes of partials
-            if (2 * G > 64) return -2;
-            const int R = 256;
-            float* part2 = shift + (long)N * C;  // [N][R][2][G]: fits the stand-alone path's partial area of ws (R*2*G <= chunks*2*C)
-            hipLaunchKernelGGL(gn_reduce_groups_kernel, dim3(R, N), dim3(256), 0, s, part, part2, G, chunks, R);
-            part = part2;
-            chunks = R;
-        }
-        hipLaunchKernelGGL(gn_finalize_groups_kernel, dim3(N), dim3(256), 0, s, part, gamma, beta, scale, shift, (int)HW, C, G, chunks, eps);
-    } else {
-        hipLaunchKernelGGL(gn_finalize_group_kernel, dim3(G, N), dim3(256), 0, s, part, gamma, beta, scale, shift, HW, C, G, chunks, eps);
-    }
+    hipLaunchKernelGGL(gn_finalize_group_kernel, dim3(G, N), dim3(256), 0, s, part, gamma, beta, scale, shift, HW, C, G, chunks, eps);
     if (y) launch_gn_apply(x, y, scale, shift, N, HW, C, do_silu, s, out_fp8, out_mul);   // y == nullptr: finalise only (scale = ws, shift = ws + N * C)
     return hipGetLastError() == hipSuccess ? 0 : -1;
 }

@@ -226,8 +226,7 @@ int ir_launch_groupnorm_any(const bf16_t* x, bf16_t* y, const float* gamma, cons
     float* shift = scale + (long)N * C;             // [N][C]
     hipLaunchKernelGGL(gn_any_partial_kernel, dim3(chunks, G, N), dim3(256), 0, s, x, part, HW, C, cpg, chunks, ppc);
     const long nv = (long)N * HW * (C / 8);
-    static const bool three = getenv("IR_GN_ANY_3") != nullptr;   // experiment knob: finalise as a launch of its own
-    if (!three && (long)N * G <= GN_ANY_MAX_GROUPS && !(reinterpret_cast<uintptr_t>(gamma) & 15) && !(reinterpret_cast<uintptr_t>(beta) & 15)) {
+    if ((long)N * G <= GN_ANY_MAX_GROUPS && !(reinterpret_cast<uintptr_t>(gamma) & 15) && !(reinterpret_cast<uintptr_t>(beta) & 15)) {
         hipLaunchKernelGGL(gn_any_finalize_apply_kernel, dim3(grid1d(nv)), dim3(256), 0, s, x, y, part, gamma, beta, HW, C, cpg, chunks, N * G, eps, do_silu, nv);
         return LAUNCH_OK();
     }

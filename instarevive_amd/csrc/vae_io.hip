@@ -301,15 +301,12 @@ int ir_launch_conv64_to3(const bf16_t* x, const bf16_t* wgt, const float* bias, 
 // two patch rows) with all 64 output channels (four 16-row weight tiles per k-step, the whole 72 KB weight image resident in LDS: one persistent
 // workgroup per CU) and vae_conv_in_kernel's store side (weight rows ordered so that a lane's accumulators of tiles 2j, 2j+1 are 8 consecutive
 // channels: 16-byte stores, 64 contiguous bytes per pixel and instruction). The halo travels through registers two tiles ahead.
-// 0.38 ms inside the pipeline, 0.45 alone (2.4 TB/s). Knock-outs (-DIR_C64_KO, alone): without MFMAs 0.23 ms, without stores 0.36, without the halo
+// 0.38 ms inside the pipeline, 0.45 alone (2.4 TB/s). Knock-out builds (alone; retired, in git history): without MFMAs 0.23 ms, without stores 0.36, without the halo
 // loads / staging 0.34 - the parts add up instead of overlapping: per k-step a wave reads 8 KB of fragments for 16 MFMAs, so the four waves keep
 // the LDS pipe as busy as the matrix pipe (576 KB per tile at 128 B per clock = the 4 600 cycles of its 288 MFMAs) and one wave per SIMD has
 // nothing to hide the rest behind. What did NOT matter (each built and timed): pinning the fragment reads a k-step ahead, the halo two tiles
 // instead of one ahead, precomputed per-lane offsets, inline-asm loads with hand-counted waits (hipcc's own waits did sit in front of every
 // tile's loads). The next step would be the weights in registers (half the LDS traffic) - not built.
-#ifndef IR_C64_KO
-#define IR_C64_KO 0   // knock-out builds, timing only (results wrong by design; never set in the library): 1 no MFMAs, 2 no stores, 3 halo fetched once, 4 no LDS staging
-#endif
 typedef unsigned int c64_u32x4 __attribute__((ext_vector_type(4)));
 namespace c64 {
 using namespace vco;                                   // TH, TW, HWD, HP, ROWB, HALO_BYTES, NV
@@ -417,7 +414,7 @@ __global__ __launch_bounds__(256) void conv64_kernel(const bf16_t* __restrict__ 
         const int ty = trem / tiles_x, tx = trem - ty * tiles_x;
         const int oy0 = ty * TH, ox0 = tx * TW;
         __syncthreads();
-        if (tt + 2 * G < total_tiles && IR_C64_KO != 3) fetch(vcur, okcur, tt + 2 * G);   // (its previous content is in LDS)
+        if (tt + 2 * G < total_tiles) fetch(vcur, okcur, tt + 2 * G);   // (its previous content is in LDS)
         f32x4_v acc[4][4];   // [weight tile f][pixel fragment fr = 2 * (row of the wave) + x half]
 #pragma unroll
         for (int f = 0; f < 4; ++f)
@@ -440,7 +437,7 @@ __global__ __launch_bounds__(256) void conv64_kernel(const bf16_t* __restrict__ 
         auto mfmas = [&](int set, int first, int last) __attribute__((always_inline)) {
 #pragma unroll
             for (int e = first; e < last; ++e)
-                if (IR_C64_KO != 1 || e == first) acc[e >> 2][e & 3] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a[set][e >> 2], b[set][e & 3], acc[e >> 2][e & 3], 0, 0, 0);
+                acc[e >> 2][e & 3] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a[set][e >> 2], b[set][e & 3], acc[e >> 2][e & 3], 0, 0, 0);
         };
         load(std::integral_constant<int, 0>{}, 0);
         [&]<int... KSI>(std::integer_sequence<int, KSI...>) {
@@ -455,12 +452,12 @@ __global__ __launch_bounds__(256) void conv64_kernel(const bf16_t* __restrict__ 
         }(std::make_integer_sequence<int, KS>{});
         __builtin_amdgcn_sched_barrier(0);
         __syncthreads();
-        if (tt + G < total_tiles && IR_C64_KO != 4) stage(vnxt, oknxt);
+        if (tt + G < total_tiles) stage(vnxt, oknxt);
         // ---- store: per pixel fragment and tile pair j the lane's 8 consecutive channels 32 j + 8 q .. + 7
 #pragma unroll
         for (int fr = 0; fr < 4; ++fr) {
             const int y = oy0 + 2 * wid + (fr >> 1), xx = ox0 + 16 * (fr & 1) + n16;
-            if (y < H && xx < W && (IR_C64_KO != 2 || acc[0][fr][0] == 1234.5f)) {
+            if (y < H && xx < W) {
                 bf16_t* dst = out + (((long)img * H + oy0) * W + ox0) * 64 + sto[fr];
 #pragma unroll
                 for (int j = 0; j < 2; ++j) {

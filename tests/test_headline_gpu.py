@@ -28,7 +28,7 @@ def _psnr(a, b):
 # ------------------------------------------------------------------------------------------------ attention at T = 16384 / 65536
 @pytest.mark.parametrize("heads,t,d,gain", [(16, 16384, 72, 3.0), (1, 65536, 512, 3.0)])
 def test_attention_at_headline_size(ctx, heads, t, d, gain):
-    """DiT self-attention of the 2048 x 2048 image (16 heads x 72, 16384 tokens: flash_attn_pp_kernel) and the VAE mid-block
+    """DiT self-attention of the 2048 x 2048 image (16 heads x 72, 16384 tokens: flash_attn_pp2_kernel) and the VAE mid-block
     attention (1 head x 512, 65536 tokens: the d = 512 kernel) against an fp64 softmax on 320 sampled query rows (block
     boundaries, first / last rows, random ones). Logits have a standard deviation of `gain`, so a handful of the keys carry each row."""
     g = torch.Generator(device="cuda").manual_seed(t + d)
@@ -317,7 +317,7 @@ def test_groupnorm_at_headline_size(ctx, n, c):
 
 def test_conv_groupnorm_fused_statistics_at_headline_size(ctx):
     """The 128 -> 128 ResnetBlock conv of the 2048 x 2048 level with its GroupNorm statistics produced by the conv epilogue
-    (conv_halo_s1_kernel: 128 x 64 = 8192 patch tiles -> gn_reduce_groups -> gn_finalize_groups -> gn_apply), residual included.
+    (conv_halo_s1_kernel: 128 x 64 = 8192 patch tiles -> gn_finalize_group -> gn_apply), residual included.
     The normalised output is checked against fp64 statistics of the kernel's OWN stored conv output (what GroupNorm is defined on),
     the conv output itself on row crops against F.conv2d."""
     import ctypes

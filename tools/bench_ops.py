@@ -68,7 +68,7 @@ def conv_norm(n, h, w, cin, cout):
 
 
 def conv8(n, h, w, cin, cout):
-    """3x3 conv on e4m3 operands (conv_halo_s1_fp8_kernel when it takes the shape; IR_NO_CONV_S1_FP8=1 forces conv_halo_kernel<.., FP8>)"""
+    """3x3 conv on e4m3 operands (conv_halo_s1_fp8_kernel when it takes the shape, conv_halo_kernel<.., FP8> otherwise)"""
     x = torch.randint(0, 120, (n, h, w, cin), device="cuda", dtype=torch.uint8)
     wt = torch.randint(0, 120, (cout, 9 * cin), device="cuda", dtype=torch.uint8)
     g, b = torch.full((cout,), 1e-3, device="cuda"), torch.zeros(cout, device="cuda")

@@ -1,7 +1,8 @@
 #!/usr/bin/env python3
 """Timing of the small-M convs / linears of the ControlLDM path (ir_op_conv_splitk: generic implicit GEMM, split-K when the heuristic says so) with COLD
 weights: every launch of a window uses another copy of the weight matrix (the copies together exceed the 256 MB Infinity Cache), as in the network,
-where 2.4 GB of weights pass once per step. Development aid for SURVEY.md section 8(f) N4; knobs: IR_SPLITK_*, IR_IGEMM_RING_MAX, IR_NO_SPLITK."""
+where 2.4 GB of weights pass once per step. Development aid for SURVEY.md section 8(f) N4. (The split-K / ring switches it was swept with are retired: A/B a change as a whole
+library build, tools/build_prev.sh + tools/ab_lib.sh.)"""
 import sys, os, math, ctypes
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch

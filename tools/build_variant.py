@@ -2,7 +2,6 @@
 """Build a diagnostic variant of the HIP library: one source recompiled with extra -D flags, everything else from the in-tree objects.
 
     python tools/build_variant.py attn_fp8.hip tools/libir_f8st.so -DIR_STAMPS_F8          # phase stamps (tools/dbg/attn8_stamps.py)
-    python tools/build_variant.py attn_fp8.hip tools/libir_f8ko48.so -DIR_KO_F8=48         # knock-out: no score MFMAs
     INSTAREVIVE_HIP_LIB=$PWD/tools/libir_f8st.so python tools/dbg/attn8_stamps.py
 
 Run `python -m instarevive_amd.build` first (the other objects must exist). Variant libraries are git-ignored."""

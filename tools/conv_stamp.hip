@@ -40,7 +40,7 @@ int main(int argc, char** argv) {
     CK(hipStreamSynchronize(st));
     float ms; CK(hipEventElapsedTime(&ms, e0, e1)); ms /= 10;
     printf("conv %dx%d %d->%d: %.3f ms  %.1f TFLOP/s\n", H, W, Cin, Cout, ms, 2.0 * H * W * Cout * 9 * Cin / ms / 1e9);
-    if (!getenv("IR_NO_CONV_PP") && Cout % 128 == 0) {  // ping-pong kernel: per-segment cycle sums of waves 0 and 4 of every workgroup
+    if (Cout % 128 == 0) {  // ping-pong kernel: per-segment cycle sums of waves 0 and 4 of every workgroup
         const long nb = std::min<long>(32768, (long)((H + 15) / 16) * ((W + 15) / 16) * (Cout / 128));
         std::vector<unsigned long long> st(nb * 16);
         CK(hipMemcpyFromSymbol(st.data(), HIP_SYMBOL(g_stamps), nb * 16 * 8));
@@ -62,7 +62,7 @@ int main(int argc, char** argv) {
         for (int k = 0; k < 4; ++k) st4[b * 4 + k] = st8[b * 8 + k];
         clk += (double)(st8[b * 8 + 6] - st8[b * 8 + 5]) / (double)(st8[b * 8 + 2] - st8[b * 8 + 1]) * 100.0;  // MHz over the main loop
     }
-    printf("in-kernel clock over the main loop: %.0f MHz (KO=%d)\n", clk / nblk, IR_KO);
+    printf("in-kernel clock over the main loop: %.0f MHz\n", clk / nblk);
     double d[3] = {0, 0, 0};
     unsigned long long tmin = ~0ull, tmax = 0;
     for (long b = 0; b < nblk; ++b) {
