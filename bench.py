@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Headline benchmark: 512 -> 2048 one-step super-resolution images/sec on MI355X (BASELINE.json metric).
 
-    python bench.py --gpus N --steps K --warmup W          (N > 1: launched by torch.distributed.run, one rank per GPU)
+    python bench.py --gpus N --steps K --warmup W [--full]   (N > 1: launched by torch.distributed.run, one rank per GPU)
 
 A step is ONE pass of the hot path — process() of test_scripts/inference.py:55-166: SwinIR -> VAE encode -> one
 PixArt-DiT step at t=400 (x0 from eps) -> VAE decode -> uint8 — over one batch of synthetic LQ images per rank, through
@@ -10,11 +10,15 @@ the fused C-ABI entry ir_pipeline with input and output resident in HBM. Workloa
 VAE 83.7 M, DiT 611 M parameters) with seeded random weights (no checkpoints exist offline; throughput is weight-
 independent). Images are independent, so ranks shard the batch with no data-path collective (weak scaling).
 
-Also printed on the same JSON line:
+A plain run sets up, warms up, times the K steps, dumps (--dump-outputs) and prints the headline line: metric, value, unit,
+ms_per_step, dtype, the workload. Everything else is measured by --full alone, after the timed steps, on the same JSON line:
   roofline     : the dominant kernel class (by GPU time) measured with HIP events on the launch stream during the timed
-                 steps (ir_profile_begin/end), algorithmic FLOPs / time vs the dense bf16 MFMA peak (2.5 PFLOP/s);
+                 steps (ir_profile_begin/end), algorithmic FLOPs / time vs the dense bf16 MFMA peak (2.5 PFLOP/s), and the
+                 per-kernel table from a second pass of the K steps with every launch bracketed;
   cpu_baseline : the oracle (CPU fp32 restatement of the reference, kind "port") timed on this box's host cores on a
-                 bounded sample (one 512x512 network pass), extrapolated to the 2048x2048 workload by algorithmic FLOPs.
+                 bounded sample (one 512x512 network pass), extrapolated to the 2048x2048 workload by algorithmic FLOPs;
+  and the fast-vs-plain-kernel check (verified), parity_2048, the host-buffer rates, the CLI leg (cli), the clock / power
+  trace of the timed loop, --logit_gain and, with --fp8, fp8_auto.
 
 --dump-outputs DIR writes what the last timed step returned (the uint8 images, as float32) to DIR/pred.npy, so that two builds can be
 compared output for output: inputs and weights are seeded, identical from run to run.
@@ -322,35 +326,40 @@ def main():
     ap.add_argument("--batch", type=int, default=1, help="images per GPU per step")
     ap.add_argument("--tiled", action="store_true")
     ap.add_argument("--net_hw", type=str, default="", help="HxW network input (overrides --lq/--sr_scale), e.g. 2176x3840 for the padded 4K case")
-    ap.add_argument("--no_cpu_baseline", action="store_true")
+    ap.add_argument("--no_cpu_baseline", action="store_true", help="--full: skip the CPU baseline")
     ap.add_argument("--fp8_parts", choices=["default", "qualified", "all", "attention", "no_encoder_convs", "convs"], default="default",
                     help="with --fp8: which parts take e4m3 operands. default = chosen ON THE LOADED WEIGHTS by instarevive_amd/fp8_select.py (one 512 x 512 calibration "
                          "image; north_star's 0.1 dB budget): on the bench's seeded weights the qualified set (the attention parts + the decoder's level-0 / level-2 "
                          "convs, >= 46.3 dB against the fp32 oracle at 2048 x 2048); the line also carries what the same rule chooses on the stress weights and "
                          "what that costs (fp8_auto). qualified = that set without calibration; all = every part BASELINE.json configs[4] names plus the VAE "
                          "mid-block attention: faster, but OUTSIDE the 0.1 dB tolerance above a 25.8 dB reference")
-    ap.add_argument("--cpu_small", action="store_true", help="CPU baseline from the 512x512 oracle pass only (skips the 1024x1024 pass, about 25 s)")
+    ap.add_argument("--cpu_small", action="store_true", help="--full: CPU baseline from the 512x512 oracle pass only (skips the 1024x1024 pass, about 25 s)")
     ap.add_argument("--control", type=int, default=0, metavar="COPIES", help="diagnostic: run the DiT step with the ControlNet-Half branch "
                     "(COPIES copied blocks, 13 in the reference configs; c = the LQ latent). Not the headline workload: no such weights are released")
     ap.add_argument("--graph", action="store_true", help="diagnostic: replay the step as one hipGraph (IR_FLAG_GRAPH); implies --no_profile, "
                     "so the JSON line carries no roofline")
     ap.add_argument("--profile_all", action="store_true", help="one pass: every launch of the timed loop bracketed by events (the form before round 4; costs about 1.4 %%)")
     ap.add_argument("--no_profile", action="store_true", help="experiment: time the loop without the per-launch HIP events (no roofline)")
-    ap.add_argument("--no_verify", action="store_true", help="skip the fast-vs-plain-kernel check of the last timed output")
-    ap.add_argument("--no_host_rate", action="store_true", help="skip the host-buffer (PCIe-inclusive) rates")
-    ap.add_argument("--logit_gain", type=float, nargs="*", default=[], metavar="G", help="diagnostic leg after the timed steps: every self-attention logit (DiT blocks, "
+    ap.add_argument("--no_verify", action="store_true", help="--full: skip the fast-vs-plain-kernel check of the last timed output")
+    ap.add_argument("--no_host_rate", action="store_true", help="--full: skip the host-buffer (PCIe-inclusive) rates")
+    ap.add_argument("--logit_gain", type=float, nargs="*", default=[], metavar="G", help="--full: diagnostic leg after the timed steps: every self-attention logit (DiT blocks, "
                     "VAE mid blocks) times G - q and k projections scaled by sqrt(G), tests/support/stress_weights.py - and the same steps timed again, with the "
                     "number of attention launches that raised the fixed-reference overflow flag and took the rescaling fallback (the seeded weights give "
                     "near-uniform softmax rows: logit spread about 8)")
-    ap.add_argument("--cli_files", type=int, default=96, metavar="K", help="after the timed steps (N = 1, headline workload only): write K synthetic 512 x 512 PNGs and "
+    ap.add_argument("--cli_files", type=int, default=96, metavar="K", help="--full: after the timed steps (N = 1, headline workload only): write K synthetic 512 x 512 PNGs and "
                     "the full-size artefacts, run `inference.py --sr_scale 4` on them as a fresh child process and report its files/s beside `value` (0 = skip)")
     ap.add_argument("--fp8", action="store_true", help="BASELINE configs[4]: fp8 (e4m3) MFMA operands in the parts ir_fp8_features() reports (the JSON line names them)")
     ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="after the timed steps: write what the last timed step returned to its caller (the "
                     "uint8 images of ir_pipeline; with N > 1 the images gathered on rank 0) as DIR/pred.npy in float32, for output-for-output comparison "
                     "of two builds (inputs and weights are seeded; above 64 MB a fixed seeded sample, DIR/pred_sample.npy)")
+    ap.add_argument("--full", action="store_true", help="after the timed steps, also measure and check everything besides the headline: the per-kernel "
+                    "roofline table, the CPU baseline, the fast-vs-plain-kernel check, parity_2048, the host-buffer rates, the CLI leg, the clock / power trace, "
+                    "--logit_gain and fp8_auto. The timed steps are the same with or without it")
     args = ap.parse_args()
     if args.steps < 1:
         ap.error("--steps must be at least 1")
+    if args.logit_gain and not args.full:
+        ap.error("--logit_gain is a leg of --full runs")
 
     from instarevive_amd import parallel
     rank, world, local = parallel.env_rank_world()
@@ -362,7 +371,7 @@ def main():
         raise SystemExit(f"--gpus {args.gpus} but WORLD_SIZE={world}: launch one rank per GPU")
     # clock / power trace of this rank's card over the whole run: a child that only reads sysfs, started BEFORE this process's first GPU call
     sampler, sampler_file = None, None
-    if rank == 0 and not os.environ.get("IR_NO_POWER_TRACE"):
+    if rank == 0 and args.full and not os.environ.get("IR_NO_POWER_TRACE"):
         import subprocess
         import tempfile
         sampler_file = os.path.join(tempfile.gettempdir(), f"ir_power_{os.getpid()}.txt")
@@ -482,6 +491,7 @@ def main():
     # An event between two launches is a barrier packet: ~700 of them per image cost 1.4 % (133.2 against 131.4 ms, A/B on one box). The timed
     # loop therefore brackets the launches of the DOMINANT kernel only - the live duration the roofline object needs - and the per-kernel
     # table comes from a second, untimed pass of the same K steps with every launch bracketed (--profile_all: one pass, as before round 4).
+    # A plain run keeps this warm-up and timed loop, events included, so that ms_per_step means the same with and without --full.
     dominant = None
     if not args.no_profile and not args.profile_all:
         ctx.profile_begin()
@@ -546,6 +556,32 @@ def main():
         return
     prof = ctx.profile_end()
     kprof = ctx.profile_end_kernels()
+    if dist is not None:
+        t = torch.tensor([dt], device=device if backend == "nccl" else "cpu", dtype=torch.float64)
+        dist.all_reduce(t, op=dist.ReduceOp.MAX)
+        dt = float(t[0])
+    ms_per_step = dt / args.steps * 1e3
+    value = world * n * args.steps / dt
+    fm = flops_model_tiled(h, w, tile_size, tile_stride, copies=args.control) if args.tiled else flops_model(h, w, copies=args.control)
+    src = f"{h}x{w} synthetic network input" if args.net_hw else f"{args.lq}x{args.lq} LQ, sr_scale {args.sr_scale:g} -> {h}x{w} network input"
+    head = {
+        "metric": "512->2048 one-step SR images/sec", "value": round(value, 4), "unit": "images/sec", "n_gpus": world, "steps": args.steps,
+        "warmup": args.warmup, "ms_per_step": round(ms_per_step, 2), "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
+        "dtype": "fp8" if args.fp8 else "bf16", "data": "synthetic",
+        "config": {"workload": f"{src}, {('tiled 512/448 + wavelet, %d tiles' % fm['tiles']) if args.tiled else 'untiled'}, batch {n} per GPU, "
+                               "full SwinIR->VAE-enc->DiT(t=400)->VAE-dec path"
+                               + (f" + ControlNet-Half ({args.control} copied blocks, c = LQ latent)" if args.control else "")
+                               + (fp8_words if args.fp8 else "")
+                               + (f", one {'RCCL' if backend == 'nccl' else backend} gather of the uint8 results on rank 0 per step" if world > 1 else ""),
+                   "global_batch": n * world, "parallelism": f"dp{world}", "weights": "seeded random, full-size architectures"},
+        "algorithmic_tflop_per_image": round(fm["total"] / 1e12, 2),
+        "path_tflops": round(fm["total"] * n * world / (ms_per_step / 1e3) / 1e12, 1)}
+    if not args.full:   # a plain run: the headline line and nothing after it
+        if rank == 0:
+            print(json.dumps(dict(head, roofline=None, cpu_baseline=None)), flush=True)
+        if dist is not None:
+            dist.destroy_process_group()
+        return
     table_ms_per_step = None
     if dominant is not None:   # the per-kernel table: the same K steps again with every launch bracketed, outside the timed region
         dom_live = kprof[dominant]
@@ -558,13 +594,7 @@ def main():
         prof = ctx.profile_end()
         kprof = ctx.profile_end_kernels()
         kprof[dominant] = dict(dom_live, ms_table_pass=kprof[dominant]["ms"])   # the dominant kernel's row stays the live measurement
-        log(f"timed loop {dt / args.steps * 1e3:.2f} ms/step with events around {dominant.split('/', 1)[1]} only; table pass (every launch bracketed) {table_ms_per_step:.2f} ms/step")
-    if dist is not None:
-        t = torch.tensor([dt], device=device if backend == "nccl" else "cpu", dtype=torch.float64)
-        dist.all_reduce(t, op=dist.ReduceOp.MAX)
-        dt = float(t[0])
-    ms_per_step = dt / args.steps * 1e3
-    value = world * n * args.steps / dt
+        log(f"timed loop {ms_per_step:.2f} ms/step with events around {dominant.split('/', 1)[1]} only; table pass (every launch bracketed) {table_ms_per_step:.2f} ms/step")
 
     # ---- outside the timed region: is what was timed correct? The last output of the timed loop against a second pass through the
     # older 4-wave kernels (an independent implementation of every large contraction; ir_set_plain_kernels)
@@ -756,7 +786,6 @@ def main():
             print(f"[bench] CLI LEG FAILED: {cli['error']} {cli.get('tail', '')[-400:]}", file=sys.stderr, flush=True)
 
     if rank == 0:
-        fm = flops_model_tiled(h, w, tile_size, tile_stride, copies=args.control) if args.tiled else flops_model(h, w, copies=args.control)
         total_ms = sum(v["ms"] for v in prof.values())
         for k, v in sorted(prof.items(), key=lambda kv: -kv[1]["ms"]):
             if v["launches"]:
@@ -864,20 +893,7 @@ def main():
                 return process(dit, [img], 1, "wavelet", False, False, 512, 448, preprocess_model=swin, vae=vae, y=y_dev, y_mask=mask_dev,
                                noise_scheduler=sched, fp8=bool(args.fp8))[0][0]
             cpu = cpu_baseline(sds, y, mask, h, w, log, hip_fn=hip_512, big_pass=not args.cpu_small)
-        src = f"{h}x{w} synthetic network input" if args.net_hw else f"{args.lq}x{args.lq} LQ, sr_scale {args.sr_scale:g} -> {h}x{w} network input"
-        line = {
-            "metric": "512->2048 one-step SR images/sec", "value": round(value, 4), "unit": "images/sec", "n_gpus": world, "steps": args.steps,
-            "warmup": args.warmup, "ms_per_step": round(ms_per_step, 2), "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
-            "dtype": "fp8" if args.fp8 else "bf16", "data": "synthetic",
-            "config": {"workload": f"{src}, {('tiled 512/448 + wavelet, %d tiles' % fm['tiles']) if args.tiled else 'untiled'}, batch {n} per GPU, "
-                                   "full SwinIR->VAE-enc->DiT(t=400)->VAE-dec path"
-                                   + (f" + ControlNet-Half ({args.control} copied blocks, c = LQ latent)" if args.control else "")
-                                   + (fp8_words if args.fp8 else "")
-                                   + (f", one {'RCCL' if backend == 'nccl' else backend} gather of the uint8 results on rank 0 per step" if world > 1 else ""),
-                       "global_batch": n * world, "parallelism": f"dp{world}", "weights": "seeded random, full-size architectures"},
-            "algorithmic_tflop_per_image": round(fm["total"] / 1e12, 2),
-            "path_tflops": round(fm["total"] * n * world / (ms_per_step / 1e3) / 1e12, 1),
-            "roofline": roof, "roofline_family": roof_family, "cpu_baseline": cpu}
+        line = dict(head, roofline=roof, roofline_family=roof_family, cpu_baseline=cpu)
         if verify is not None:
             line.update(verify)
         if host is not None:

@@ -183,7 +183,7 @@ def test_bench_self_launches_its_ranks():
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
     env["IR_BENCH_BACKEND"] = "gloo"
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--batch", "2", "--lq", "128", "--sr_scale", "2", "--steps", "2", "--warmup", "1",
-           "--no_cpu_baseline", "--no_host_rate"]
+           "--full", "--no_cpu_baseline", "--no_host_rate"]
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=900, cwd=ROOT, env=env)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-3000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
@@ -200,8 +200,8 @@ def test_bench_round5_legs_on_a_small_workload():
     the --logit_gain leg (weights re-uploaded with every self-attention logit x 4, the attention-fallback counter read through the C ABI, weights restored)
     and a `roofline.traffic_source` that is either a PMC file of THESE kernel sources or the reason why there is none."""
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--lq", "128", "--sr_scale", "2", "--steps", "2", "--warmup", "1", "--no_cpu_baseline", "--no_host_rate",
-           "--cli_files", "0", "--logit_gain", "4"]
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--lq", "128", "--sr_scale", "2", "--steps", "2", "--warmup", "1", "--full", "--no_cpu_baseline",
+           "--no_host_rate", "--cli_files", "0", "--logit_gain", "4"]
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=900, cwd=ROOT, env=env)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-3000:]
     line = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1])
@@ -310,7 +310,8 @@ def test_bench_multi_gpu_branch_through_rccl_on_one_rank():
     import json
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT", "IR_BENCH_BACKEND")}
     env.update(IR_FORCE_COLLECTIVES="1", HSA_ENABLE_IPC_MODE_LEGACY=env.get("HSA_ENABLE_IPC_MODE_LEGACY", "0"))
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1", "--no_cpu_baseline", "--no_host_rate"],
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1", "--full", "--no_cpu_baseline",
+                        "--no_host_rate"],
                        capture_output=True, text=True, timeout=900, cwd=ROOT, env=env)
     assert r.returncode == 0, r.stdout[-1500:] + r.stderr[-3000:]
     line = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
@@ -323,17 +324,23 @@ def test_bench_multi_gpu_branch_through_rccl_on_one_rank():
 def test_bench_dump_outputs_and_steps(tmp_path):
     """bench.py --dump-outputs DIR on a small workload (128 x 128 LQ, sr_scale 2): DIR/pred.npy holds the last timed step's uint8 images as float32,
     --steps sets the number of timed steps the line reports, and two runs with different step counts dump identical outputs (seeded inputs and
-    weights, a deterministic path)."""
+    weights, a deterministic path). The first run is a plain one - its line is the headline alone, with no roofline, check or power trace -, the
+    second a --full one, whose legs run after the dump."""
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
     preds = []
-    for k in (1, 3):
+    for k, extra in ((1, []), (3, ["--full", "--no_cpu_baseline", "--no_host_rate", "--cli_files", "0"])):
         d = tmp_path / f"steps{k}"
-        cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--lq", "128", "--sr_scale", "2", "--steps", str(k), "--warmup", "1", "--no_cpu_baseline",
-               "--no_host_rate", "--no_verify", "--cli_files", "0", "--dump-outputs", str(d)]
+        cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--lq", "128", "--sr_scale", "2", "--steps", str(k), "--warmup", "1", "--dump-outputs", str(d)] + extra
         r = subprocess.run(cmd, capture_output=True, text=True, timeout=900, cwd=ROOT, env=env)
         assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-3000:]
-        line = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1])
-        assert line["steps"] == k and line["ms_per_step"] > 0
+        lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
+        assert len(lines) == 1, r.stdout[-2000:]
+        line = json.loads(lines[0])
+        assert line["steps"] == k and line["ms_per_step"] > 0 and line["value"] > 0 and line["unit"] == "images/sec" and line["dtype"] == "bf16"
+        if extra:
+            assert line["roofline"]["per_kernel"] and line["verified"] is True and "power_trace" in line
+        else:
+            assert line["roofline"] is None and line["cpu_baseline"] is None and not {"verified", "parity_2048", "cli", "power_trace"} & set(line)
         assert sorted(os.listdir(d)) == ["pred.npy"]
         p = np.load(d / "pred.npy")
         assert p.dtype == np.float32 and p.shape == (1, 256, 256, 3) and p.min() >= 0 and p.max() <= 255 and np.array_equal(p, np.round(p)) and p.std() > 1.0

@@ -760,3 +760,11 @@ def test_bench_dump_outputs_helper(tmp_path, monkeypatch):
     import subprocess
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "0"], capture_output=True, text=True, timeout=300, cwd=ROOT)
     assert r.returncode != 0 and "--steps must be at least 1" in r.stderr
+
+
+def test_bench_logit_gain_is_a_full_leg():
+    """--logit_gain times extra steps after the timed ones, which only a --full run of bench.py does: a plain run that names it is refused before
+    any work, instead of printing a line without the leg asked for."""
+    import subprocess
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--logit_gain", "4"], capture_output=True, text=True, timeout=300, cwd=ROOT)
+    assert r.returncode != 0 and "--logit_gain is a leg of --full runs" in r.stderr

@@ -5,19 +5,19 @@ set -o pipefail
 cd "${GRAFT_REPO_ROOT:-.}"
 O=gpurun_out/r06; mkdir -p $O
 export TMPDIR=/tmp
-IR_KEEP_POWER_TRACE=$O/power_trace.txt python bench.py --cli_files 0 > $O/bench_final.json 2> $O/bench_final.err || exit 1
+IR_KEEP_POWER_TRACE=$O/power_trace.txt python bench.py --full --cli_files 0 > $O/bench_final.json 2> $O/bench_final.err || exit 1
 echo "[1] bench done: $(grep -o '"ms_per_step": [0-9.]*' $O/bench_final.json | head -1)"
-python bench.py --gpus 1 --steps 20 --warmup 5 --cpu_small > $O/bench_driver_form.json 2> $O/bench_driver_form.err || exit 1
+python bench.py --gpus 1 --steps 20 --warmup 5 --full --cpu_small > $O/bench_driver_form.json 2> $O/bench_driver_form.err || exit 1
 echo "[1b] driver form done: $(grep -o '"ms_per_step": [0-9.]*' $O/bench_driver_form.json | head -1)"
-python bench.py --fp8 --lq 1024 --sr_scale 2 --cpu_small > $O/bench_fp8.json 2> $O/bench_fp8.err || exit 1
-python bench.py --fp8 --fp8_parts all --lq 1024 --sr_scale 2 --cpu_small > $O/bench_fp8_all.json 2> $O/bench_fp8_all.err || exit 1
+python bench.py --full --fp8 --lq 1024 --sr_scale 2 --cpu_small > $O/bench_fp8.json 2> $O/bench_fp8.err || exit 1
+python bench.py --full --fp8 --fp8_parts all --lq 1024 --sr_scale 2 --cpu_small > $O/bench_fp8_all.json 2> $O/bench_fp8_all.err || exit 1
 echo "[2] fp8 done (calibrated set / every part)"
-python bench.py --tiled --net_hw 2176x3840 --no_cpu_baseline --no_host_rate > $O/bench_4k_tiled.json 2> $O/bench_4k_tiled.err || exit 1
-python bench.py --tiled --net_hw 2176x3840 --graph --steps 5 --warmup 2 > $O/bench_4k_tiled_graph.json 2> $O/bench_4k_tiled_graph.err || exit 1
+python bench.py --full --tiled --net_hw 2176x3840 --no_cpu_baseline --no_host_rate > $O/bench_4k_tiled.json 2> $O/bench_4k_tiled.err || exit 1
+python bench.py --full --tiled --net_hw 2176x3840 --graph --steps 5 --warmup 2 > $O/bench_4k_tiled_graph.json 2> $O/bench_4k_tiled_graph.err || exit 1
 echo "[3] 4k tiled done"
-python bench.py --batch 8 --steps 3 --warmup 1 --no_cpu_baseline --no_host_rate > $O/bench_b8.json 2> $O/bench_b8.err || exit 1
+python bench.py --full --batch 8 --steps 3 --warmup 1 --no_cpu_baseline --no_host_rate > $O/bench_b8.json 2> $O/bench_b8.err || exit 1
 echo "[4] batch 8 done"
-IR_NO_POWER_TRACE=1 rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof -o ks -- python3 bench.py --steps 2 --warmup 1 --no_cpu_baseline --no_verify --no_host_rate --cli_files 0 > $O/prof.log 2>&1 || exit 1
+IR_NO_POWER_TRACE=1 rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof -o ks -- python3 bench.py --full --steps 2 --warmup 1 --no_cpu_baseline --no_verify --no_host_rate --cli_files 0 > $O/prof.log 2>&1 || exit 1
 find $O/prof -name "*kernel_stats.csv" | head -1 | xargs -I{} cp {} $O/kernel_stats.csv
 rm -rf $O/prof
 echo "[5] kernel trace done"
