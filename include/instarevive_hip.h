@@ -330,6 +330,18 @@ int ir_op_attention_fp8(ir_ctx* ctx, void* stream, const uint16_t* q, const uint
                         float scale, void* ws, size_t ws_bytes);
 int ir_op_swin_attention(ir_ctx* ctx, void* stream, const uint16_t* qkv, uint16_t* out, const float* bias_t, int b, int h, int w,
                          int heads, int shift, float scale);
+/* The fused SwinIR block kernels (swin_fused.hip) for op-level tests, with the arguments of their launchers; weights in the layouts of
+ * weights.pack_swinir (proj_t, biasT / biasM, mlp_t + mlp_v, qkv_t). x / out / x_in / x_out: [t][192] fp32 residual rows (may alias);
+ * qkv: [b * h * w][576] bf16. swin_mlp: out = x + MLP(LN2(x)); swin_attn_proj: out = xres + proj(W-MSA(qkv)); swin_block: both halves.
+ * out2 (optional): bf16 copy of the new rows, or - with next_g / next_b - the next block's norm1 rows, or - with qkv_tiles too - its
+ * qkv rows [t][qkv_n]. Return codes of the launchers: -2 a shape the kernel does not take, -4 a tensor beyond 32-bit offsets. */
+int ir_op_swin_mlp(ir_ctx* ctx, void* stream, const float* x, float* out, uint16_t* out2, const void* w_tiles, const float* vec, long t, int c,
+                   int hid_p, float eps, const float* next_g, const float* next_b, const void* qkv_tiles, const float* qkv_b, int qkv_n);
+int ir_op_swin_attn_proj(ir_ctx* ctx, void* stream, const uint16_t* qkv, const float* xres, float* out, const void* proj_t, const float* proj_b,
+                         const float* bias_t, int b, int h, int w, int shift, float scale);
+int ir_op_swin_block(ir_ctx* ctx, void* stream, const uint16_t* qkv, const float* x_in, float* x_out, uint16_t* out2, const void* proj_t,
+                     const float* proj_b, const float* bias_t, int b, int h, int w, int shift, float scale, const void* w_tiles, const float* vec,
+                     int c, int hid_p, float eps, const float* next_g, const float* next_b, const void* qkv_tiles, const float* qkv_b, int qkv_n);
 int ir_op_softmax_rows(ir_ctx* ctx, void* stream, const float* x, uint16_t* y, int rows, int cols);
 /* layout kernels at the two ends of the VAE: fp32 NCHW [n][ch][hw] -> bf16 NHWC [n*hw][cpad] of v*scale+shift (zero padding channels),
  * and fp32 NHWC rows [n*hw][in_cs] -> fp32 NCHW [n][ch][hw] of v*scale+shift (optionally clamped to [0,1]) */

@@ -3182,6 +3182,26 @@ int ir_op_swin_attention(ir_ctx* c, void* stream, const uint16_t* qkv, uint16_t*
     int rc = ir_launch_swin_attn(qkv, out, bias_t, b, h, w, heads, 3 * heads * 32, heads * 32, shift, scale, (hipStream_t)stream);
     return rc ? fail(c, rc, "swin_attn failed (%d)", rc) : 0;
 }
+int ir_op_swin_mlp(ir_ctx* c, void* stream, const float* x, float* out, uint16_t* out2, const void* w_tiles, const float* vec, long t, int ch,
+                   int hid_p, float eps, const float* next_g, const float* next_b, const void* qkv_tiles, const float* qkv_b, int qkv_n) {
+    use_ctx(c);
+    int rc = ir_launch_swin_mlp(x, out, out2, w_tiles, vec, t, ch, hid_p, eps, (hipStream_t)stream, next_g, next_b, qkv_tiles, qkv_b, qkv_n);
+    return rc ? fail(c, rc, "swin_mlp failed (%d)", rc) : 0;
+}
+int ir_op_swin_attn_proj(ir_ctx* c, void* stream, const uint16_t* qkv, const float* xres, float* out, const void* proj_t, const float* proj_b,
+                         const float* bias_t, int b, int h, int w, int shift, float scale) {
+    use_ctx(c);
+    int rc = ir_launch_swin_attn_proj(qkv, xres, out, proj_t, proj_b, bias_t, b, h, w, shift, scale, (hipStream_t)stream);
+    return rc ? fail(c, rc, "swin_attn_proj failed (%d)", rc) : 0;
+}
+int ir_op_swin_block(ir_ctx* c, void* stream, const uint16_t* qkv, const float* x_in, float* x_out, uint16_t* out2, const void* proj_t,
+                     const float* proj_b, const float* bias_t, int b, int h, int w, int shift, float scale, const void* w_tiles, const float* vec,
+                     int ch, int hid_p, float eps, const float* next_g, const float* next_b, const void* qkv_tiles, const float* qkv_b, int qkv_n) {
+    use_ctx(c);
+    int rc = ir_launch_swin_block(qkv, x_in, x_out, out2, proj_t, proj_b, bias_t, b, h, w, shift, scale, w_tiles, vec, ch, hid_p, eps,
+                                  (hipStream_t)stream, next_g, next_b, qkv_tiles, qkv_b, qkv_n);
+    return rc ? fail(c, rc, "swin_block failed (%d)", rc) : 0;
+}
 int ir_op_nchw_to_nhwc(ir_ctx* c, void* stream, const float* in, uint16_t* out, int n, int ch, long hw, int cpad, float scale, float shift) {
     use_ctx(c);
     int rc = ir_launch_nchw_to_nhwc_bf16(in, out, n, ch, hw, cpad, scale, shift, (hipStream_t)stream);

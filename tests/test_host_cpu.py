@@ -118,6 +118,19 @@ def test_swin_qkv_ring_tiles():
     assert t[:, 26624:].abs().sum() == 0   # the slot's tail (the MLP's W2 area) is unused
 
 
+def test_swin_fused_launchers_refuse_empty_and_negative_grids():
+    """ir_op_swin_block / ir_op_swin_attn_proj return -2 for H or W <= 0 before anything touches a device (a negative size passes the
+    multiple-of-8 test on its own). Only sizes whose grid would be empty are tried, so a broken guard could not dispatch anything."""
+    from instarevive_amd import _lib
+    from instarevive_amd.build import build
+    build()
+    lib = _lib.load_library()
+    for h, w in ((0, 8), (8, 0), (-8, 8), (8, -8)):
+        assert lib.ir_op_swin_attn_proj(None, None, None, None, None, None, None, None, 1, h, w, 0, 0.18) == -2, (h, w)
+        assert lib.ir_op_swin_block(None, None, None, None, None, None, None, None, None, 1, h, w, 0, 0.18, None, None, 180, 384, 1e-5,
+                                    None, None, None, None, 0) == -2, (h, w)
+
+
 def test_sliding_windows_and_loaders():
     from instarevive_amd.pipeline import _sliding_windows
     from instarevive_amd import utils
