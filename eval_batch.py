@@ -39,6 +39,8 @@ def parse_args():
     ap.add_argument("--vae", default="stabilityai/sd-vae-ft-ema")
     ap.add_argument("--dit_config", default="PixArt-alpha/PixArt-Alpha-DMD-XL-2-512x512")
     ap.add_argument("--prompt_embeds", default=cli.DEFAULT_PROMPT)
+    ap.add_argument("--caption_dir", default=None, help="per-image prompts: DIR/<input-relative path without extension>.npz, else DIR/<file stem>.npz "
+                    "(caption_feature [1, T, 4096], optional attention_mask; the reference's caption files). Images without one get --prompt_embeds")
     ap.add_argument("--device", default="cuda")
     ap.add_argument("--workers", type=int, default=-1, help="host threads for decoding / PNG encoding (inference.py --workers)")
     return ap.parse_args()
@@ -53,6 +55,7 @@ def out_name(folder, src_root, path):
 def main():
     from instarevive_amd import parallel
     from instarevive_amd.pipeline import process_stream
+    from instarevive_amd.prompts import Captions
     from instarevive_amd.utils import center_crop_arr, list_image_files
     args = parse_args()
     cli.check_device(args.device)
@@ -69,11 +72,14 @@ def main():
     batches = [files[i:i + args.batch_size] for i in range(0, len(files), args.batch_size)]
     pools = cli.HostPools(cli.default_workers(int(os.environ.get("LOCAL_WORLD_SIZE", world))) if args.workers < 0 else args.workers)
 
+    caps = Captions(args.caption_dir, m.y, m.y_mask, args.input) if args.caption_dir else None
+
     def feed():
         # decode + centre crop run ahead of the GPU on the reader threads, in file order
         crops = pools.read_ahead(lambda f: center_crop_arr(Image.open(f).convert("RGB"), args.image_size), files)
         for group in batches:
-            yield [next(crops) for _ in group]
+            imgs = [next(crops) for _ in group]
+            yield (imgs, *caps.batch(group)) if caps else imgs
 
     def save(dst, img):
         os.makedirs(os.path.dirname(dst) or ".", exist_ok=True)

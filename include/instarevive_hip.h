@@ -76,6 +76,13 @@ int ir_dit_control_configure(ir_ctx* ctx, int copy_blocks_num);
 /* encoder_hidden_states / encoder_attention_mask of the fixed prompt (inference.py:256-259,273-277): host fp32
  * [n_tok][caption_dim] and [n_tok]; projects the caption and caches K/V of all layers on the device. */
 int ir_dit_set_prompt(ir_ctx* ctx, void* stream, const float* embeds_host, const float* mask_host, int n_tok);
+/* One prompt per image (the reference's per-image captions, dataset/codeformer.py:765-790): n_prompts prompts at once, DEVICE fp32
+ * embeds [n_prompts][n_tok][caption_dim] and additive key bias [n_prompts][n_tok] (as ir_dit_set_prompt takes it). Every DiT launch then
+ * gives batch item i prompt slot i % n_prompts: image i untiled, and the tiles of image i under tiling. The DiT entry points refuse a
+ * batch of n images unless n_prompts is 1 or n. Stream-ordered: no host wait, and no allocation while (n_prompts, 64-token bucket of n_tok)
+ * fits the caches; the caller keeps the inputs alive until the stream has passed the call. Recorded hipGraphs stay valid unless the
+ * caches moved or n_prompts / n_tok changed. Slot p holds the K / V ir_dit_set_prompt builds for prompt p alone, bit for bit. */
+int ir_dit_set_prompts(ir_ctx* ctx, void* stream, const float* embeds_dev, const float* bias_dev, int n_prompts, int n_tok);
 
 /* ---- ControlLDM one-step: Reflow_ControlLDM of diffusion/cldm.py:425-588, configs/cldm.yaml.
  * ir_unet_configure binds the SD-2.1 UNet (`which` 0: ControlledUnetModel, cldm.py:32-55 = UNetModel of openaimodel.py:411-786; tensors
@@ -202,6 +209,8 @@ int ir_set_plain_kernels(ir_ctx* ctx, int on);
  * right either way - the flag only costs time). op = 1: zero the counter and count from now on (one tiny launch behind each such attention);
  * op = 0: synchronise `stream` and return the number of attention launches that took the fallback since; op = -1: stop counting. */
 int ir_attn_fallback_count(ir_ctx* ctx, void* stream, int op);
+/* Diagnostic: how many hipGraphs this context has recorded (IR_FLAG_GRAPH) since it was created. */
+unsigned long ir_graph_records(ir_ctx* ctx);
 /* on != 0: the stage entry points (ir_vae_encode / ir_vae_decode / ir_dit_*) use the fp8 forms as IR_FLAG_FP8 does for ir_pipeline. */
 int ir_set_fp8(ir_ctx* ctx, int on);
 /* Which PARTS take fp8 operands while fp8 is on (default: IR_FP8_MASK_DEFAULT below). One bit per part, so that the error
@@ -309,6 +318,11 @@ int ir_op_layernorm(ir_ctx* ctx, void* stream, const float* x, uint16_t* y, cons
                     int ldy, float eps);
 int ir_op_attention(ir_ctx* ctx, void* stream, const uint16_t* q, const uint16_t* k, const uint16_t* v, uint16_t* o, int b, int heads,
                     int tq, int tk, int d, float scale, const float* key_bias, void* ws, size_t ws_bytes);
+/* ir_op_attention with K / V sets shared round-robin (the DiT cross-attention under ir_dit_set_prompts): q / o [b][tq][heads*d],
+ * k / v [groups][tk][heads*d], key_bias (optional) [groups][tk]; item i attends to set i % groups (b % groups == 0). Workspace as
+ * ir_op_attention's with b = groups. d = 512 is not offered. */
+int ir_op_attention_kv_groups(ir_ctx* ctx, void* stream, const uint16_t* q, const uint16_t* k, const uint16_t* v, uint16_t* o, int b, int heads,
+                              int tq, int tk, int d, float scale, const float* key_bias, int groups, void* ws, size_t ws_bytes);
 /* GroupNorm(groups) over NHWC bf16 rows for ANY channel count with ch % groups == 0, ch % 8 == 0 and an even group width (the UNet's
  * 320 ... 2560 channels; ir_op_groupnorm needs ch = 8 * 2^k <= 512). ws: (n * 32 * 64 * 2 + 2 * n * ch) floats at most. */
 int ir_op_groupnorm_any(ir_ctx* ctx, void* stream, const uint16_t* x, uint16_t* y, const float* gamma, const float* beta, int n, long hw, int ch,

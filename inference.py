@@ -66,6 +66,9 @@ def parse_args() -> Namespace:
     parser.add_argument("--vae", type=str, default="stabilityai/sd-vae-ft-ema")
     parser.add_argument("--dit_config", type=str, default="PixArt-alpha/PixArt-Alpha-DMD-XL-2-512x512")
     parser.add_argument("--prompt_embeds", type=str, default=DEFAULT_PROMPT)
+    parser.add_argument("--caption_dir", type=str, default=None, help="per-image prompts (no reference flag: the evaluation loop's captions, "
+                        "test_dmd_general.py:173-174): DIR/<input-relative path without extension>.npz, else DIR/<file stem>.npz (caption_feature "
+                        "[1, T, 4096], optional attention_mask). Images without one get --prompt_embeds; every prompt needs the same T")
     # extensions (defaults reproduce the reference's behaviour)
     parser.add_argument("--batch_size", type=int, default=1, help="consecutive files of equal network-input size per process() call")
     parser.add_argument("--shard_tiles", action="store_true", help="with --tiled under torchrun: spread the TILES of each image over the "
@@ -158,6 +161,7 @@ class Job:
     lq: Image.Image            # the (sr_scale-d) LQ image: target size of the saved result and left panel of --show_lq
     net_in: np.ndarray         # what process() receives: HWC uint8, edges multiples of 64 (or 512 x 512 under --use_center_crop)
     valid_hw: tuple            # un-padded extent of net_in, () under --use_center_crop (nothing to remove)
+    src: str = ""              # the input file (its caption under --caption_dir)
 
 
 def read_job(file_path: str, repeat: int, args: Namespace) -> Job:
@@ -173,7 +177,7 @@ def read_job(file_path: str, repeat: int, args: Namespace) -> Job:
     # --use_center_crop switches the un-padding / resize-back of the result off, also next to --tiled (inference.py:326-346)
     valid = () if args.use_center_crop else (fitted.height, fitted.width)
     folder, stem, _ = get_file_name_parts(os.path.join(args.output, os.path.relpath(file_path, args.input)))
-    return Job(os.path.join(folder, f"{stem}_{repeat}.png"), lq, net_in, valid)
+    return Job(os.path.join(folder, f"{stem}_{repeat}.png"), lq, net_in, valid, file_path)
 
 
 def write_job(job: Job, pred: np.ndarray, stage1_pred, args: Namespace) -> None:
@@ -336,11 +340,17 @@ def main() -> None:
     common = dict(color_fix_type=args.color_fix_type, disable_preprocess_model=args.disable_preprocess_model, tile_size=args.tile_size,
                   tile_stride=args.tile_stride, preprocess_model=m.preprocess_model, vae=m.vae, y=m.y, y_mask=m.y_mask,
                   noise_scheduler=m.noise_scheduler)
+    caps = None
+    if args.caption_dir:
+        from instarevive_amd.prompts import Captions
+        caps = Captions(args.caption_dir, m.y, m.y_mask, args.input)
     if args.shard_tiles and args.tiled and world > 1:
         # one large image at a time, its tiles spread over the GPUs; rank 0 re-assembles and writes
         engine = HipTileEngine(m.model, m.vae, m.preprocess_model, m.y, m.y_mask, args.color_fix_type, args.disable_preprocess_model,
                                args.tile_size, args.tile_stride, m.noise_scheduler)
         for job in pools.read_ahead(lambda pi: read_job(pi[0], pi[1], args), [(p, i) for p in files for i in range(args.repeat_times)]):
+            if caps:
+                engine.y, engine.y_mask = caps.batch([job.src])
             preds, stage1 = parallel.sharded_tiled_process(engine, [job.net_in], rank, world)
             if rank == 0:
                 pools.write_behind(write_job, job, preds[0], stage1[0], args)
@@ -354,7 +364,8 @@ def main() -> None:
     def feed():
         for group in batches_of(jobs, max(args.batch_size, 1)):
             todo.append(group)
-            yield [j.net_in for j in group]
+            imgs = [j.net_in for j in group]
+            yield (imgs, *caps.batch([j.src for j in group])) if caps else imgs
 
     first = None    # (time, files) when the first result left the GPU: what follows is the steady state (no library / workspace warm-up in it)
     for preds, stage1 in process_stream(m.model, feed(), tiled=args.tiled, return_stage1=args.show_lq and not args.disable_preprocess_model,

@@ -23,6 +23,7 @@ SYMBOLS = [
     "ir_op_swin_mlp", "ir_op_swin_attn_proj", "ir_op_swin_block", "ir_op_softmax_rows", "ir_op_nchw_to_nhwc", "ir_op_nhwc_to_nchw",
     "ir_tiled_count", "ir_tiled_encode", "ir_tiled_encode_part", "ir_tiled_encode_overflow", "ir_op_conv_up2x2", "ir_op_conv_norm", "ir_op_vae_conv_in", "ir_op_vae_norm_conv_out", "ir_op_conv64", "ir_op_conv64_to3", "ir_tiled_dit", "ir_tiled_blend_latent", "ir_tiled_decode", "ir_tiled_blend_pixels", "ir_set_plain_kernels", "ir_set_fp8", "ir_set_fp8_mask", "ir_attn_fallback_count", "ir_op_conv_fp8", "ir_op_conv_fp8_up", "ir_op_conv_fp8_route", "ir_fp8_features", "ir_op_attention_fp8", "ir_op_attention_d512_fp8",
     "ir_unet_configure", "ir_unet_set_context", "ir_cldm_sample", "ir_cldm_pipeline", "ir_clip_text_configure", "ir_clip_text_encode", "ir_op_groupnorm_any", "ir_op_geglu",
+    "ir_dit_set_prompts", "ir_op_attention_kv_groups", "ir_graph_records",
 ]
 
 STAGE_SWINIR, STAGE_VAE_ENCODE, STAGE_DIT, STAGE_VAE_DECODE, STAGE_PIPELINE, STAGE_COLORFIX, STAGE_T5, STAGE_CLDM, STAGE_CLDM_PIPELINE, STAGE_CLIP_TEXT = range(10)
@@ -135,6 +136,10 @@ def load_library():
     lib.ir_cldm_pipeline.argtypes = [vp, vp, vp, vp, vp, vp, i, i, i, i, f, f, vp, sz]
     lib.ir_op_groupnorm_any.argtypes = [vp, vp, vp, vp, vp, vp, i, C.c_long, i, i, f, i, vp, sz]
     lib.ir_op_geglu.argtypes = [vp, vp, vp, vp, C.c_long, i]
+    lib.ir_dit_set_prompts.argtypes = [vp, vp, vp, vp, i, i]
+    lib.ir_op_attention_kv_groups.argtypes = [vp, vp, vp, vp, vp, vp, i, i, i, i, i, f, vp, i, vp, sz]
+    lib.ir_graph_records.argtypes = [vp]
+    lib.ir_graph_records.restype = C.c_ulong
     for name in SYMBOLS:
         fn = getattr(lib, name)
         if fn.restype is C.c_int and name not in ("ir_abi_version",):
@@ -192,6 +197,11 @@ class Context:
 
     def stream(self):
         return C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+
+    @property
+    def graph_records(self):
+        """How many hipGraphs this context has recorded (process(graph=True) / process_stream(graph=True)) since it was created."""
+        return int(self.lib.ir_graph_records(self.h))
 
     def upload(self, name, t: torch.Tensor):
         """Copy a HOST tensor (any dtype, contiguous) into the named device buffer of the context."""

@@ -97,8 +97,8 @@ struct VaeModel {
 struct DitLayer {
     const float* sst = nullptr;
     Conv qkv, ao, cq, ckv, co, fc1, fc2;
-    bf16_t* kc = nullptr;   // [n_tok][2*hidden] cached K|V of the prompt
-    bf16_t* vtc = nullptr;  // [heads][DV][tok_pad]
+    bf16_t* kc = nullptr;   // [P][n_tok][2*hidden] cached K|V of the prompts (P = DitModel::n_prompts; rows for prompt_slots x tok_pad allocated)
+    bf16_t* vtc = nullptr;  // [P][heads][DV][tok_pad]
     // optional branches of the self-attention (AttentionKVCompress, PixArt_blocks.py:60-158; round 6): KV token compression by a depthwise r x r / stride r
     // convolution over the token grid (kvc_w [C][r*r], kvc_b; 'uniform' / 'ave' sampling arrive as a weight of 1 on the first tap) with an optional LayerNorm
     // (kvc_g / kvc_beta: the 'conv' sampler's `norm`), and LayerNorm on q and k (qk_norm)
@@ -118,7 +118,11 @@ struct DitModel {
     std::vector<Conv> after;
     Conv before;
     int n_tok = 0, tok_pad = 0;
-    float* key_bias = nullptr;
+    float* key_bias = nullptr;   // [P][n_tok]
+    // prompt slots (ir_dit_set_prompts): item b of every cross-attention launch attends to slot b % n_prompts; the slot strides of kc / vtc /
+    // key_bias (elements) are 0 while one prompt is set, so that launch is today's single-prompt one
+    int n_prompts = 1;
+    long kc_slot = 0, vt_slot = 0, kb_slot = 0;
     // timestep-dependent tables (recomputed when the timestep changes)
     float cached_t = -1e30f;
     float *tsin = nullptr, *th = nullptr, *emb = nullptr, *semb = nullptr, *t6 = nullptr, *modtab = nullptr, *fmod = nullptr;
@@ -261,6 +265,8 @@ struct ir_ctx {
     // branch's tables, the per-layer prompt K/V caches (+ key bias), the T5 flag
     std::vector<void*> dit_tabs, dit_ctrl_tabs, dit_prompt, t5_owned;
     int prompt_cap = 0;        // rows (tok_pad) the prompt caches in dit_prompt were sized for
+    int prompt_slots = 0;      // prompts they have room for
+    bf16_t *prompt_e16 = nullptr, *prompt_y1 = nullptr, *prompt_y2 = nullptr;   // ir_dit_set_prompts' caption-MLP operands (in dit_prompt; null until it runs)
     SwinModel swin;
     VaeModel vae;
     DitModel dit;
@@ -282,6 +288,7 @@ struct ir_ctx {
     struct GraphEntry { GraphKey key; hipGraphExec_t exec; };
     std::vector<GraphEntry> graphs;
     unsigned long generation = 0, graphs_generation = 0;
+    unsigned long graph_records = 0;   // graphs recorded so far (ir_graph_records)
     hipStream_t cap_stream = nullptr;  // recording happens on a private stream (the caller's may be the legacy default stream, which cannot capture)
     int* shard_flag = nullptr;         // device copy of the overflow flag of the last ir_tiled_encode_part(part 0 / 2) (in `owned`)
     int* attn_fb = nullptr;            // ir_attn_fallback_count: [0] attention launches whose fixed-reference kernel raised its overflow flag (in `owned`)
@@ -348,6 +355,8 @@ struct Run {
     bool vt_done = false;
     bool splitk = false;         // conv() / linear() may split K over extra workgroups (IGemmParams::allow_splitk): set by the UNet path
     int s1_min_tiles = 0;        // IGemmParams::s1_min_tiles of every conv this run launches: set by the ControlLDM pipeline (one small image per launch)
+    int route_rows = 0;          // > 0: linear() over M rows keeps the kernel it would pick for route_rows rows (M rows of independent route_rows-row
+                                 // problems: the batched prompt projection gives each prompt the bits of its own projection)
     bool live() const { return !a.dry && rc == 0 && !a.overflow; }
     void chk(int r, const char* w) {
         if (r != 0 && rc == 0) { rc = r; where = w; }
@@ -447,6 +456,11 @@ void conv(Run& r, const Conv& cw, const bf16_t* in, int N, int H, int W, int in_
         r.vt_out = nullptr;
         r.vt_done = ir_igemm_writes_vt(p) != 0;
         if (!r.vt_done) p.vt_out = nullptr;
+    }
+    if (r.route_rows > 0 && r.route_rows < p.M) {
+        IGemmParams q = p;
+        q.M = r.route_rows;
+        if (ir_igemm_kernel_id(q) != ir_igemm_kernel_id(p)) p.force_generic = 1;   // (only gemm_pp_kernel depends on M among the linear kernels)
     }
     static const int kid_of[6] = {PK_CONV_S1, PK_CONV_HALO_PP, PK_GEMM_PP, PK_CONV_HALO, -1, PK_CONV64};
     int kid = kid_of[ir_igemm_kernel_id(p)];
@@ -1105,10 +1119,11 @@ void dit_block(Run& r, const DitLayer& Lw, const float* mod, float* x, const Dit
         AttnParams p;
         memset(&p, 0, sizeof p);
         p.q = b.cq; p.k = Lw.kc; p.vt = Lw.vtc; p.o = b.att;
-        p.q_bs = T * C; p.k_bs = 0; p.o_bs = T * C; p.vt_bs = 0;
+        p.q_bs = T * C; p.k_bs = m.kc_slot; p.o_bs = T * C; p.vt_bs = m.vt_slot;
         p.q_rs = C; p.k_rs = 2 * C; p.o_rs = C; p.q_hs = p.k_hs = p.o_hs = hd;
         p.B = n; p.Hh = Hh; p.Tq = (int)T; p.Tk = m.n_tok; p.Tk_pad = m.tok_pad; p.D = hd; p.scale_log2 = sl2;
-        p.key_bias = m.key_bias; p.kb_bs = 0;
+        p.key_bias = m.key_bias; p.kb_bs = m.kb_slot;
+        p.kv_groups = m.n_prompts;   // item b (= tile * images + image) takes prompt slot b % P
         LAUNCHK(r, PK_ATTN_CROSS, 4.0 * n * Hh * (double)T * m.n_tok * hd, 0.0, ir_launch_flash_attn(p, r.s), "cross_attn");
     }
     linear(r, Lw.co, b.att, (int)BT, C, x, C, 1, ACT_NONE, x, 1, C);
@@ -1674,6 +1689,7 @@ int check_size(ir_ctx* c, int n, int h, int w, int mult) {
 extern "C" {
 
 int ir_abi_version(void) { return 3; }   // 2: ir_tiled_encode_part callers must read + MAX-reduce the overflow flag; 3: the context's default fp8 operand set (IR_FP8_MASK_DEFAULT) no longer contains the DiT self-attention (IR_FP8_MASK_QUALIFIED is round 5's set)
+unsigned long ir_graph_records(ir_ctx* c) { return c ? c->graph_records : 0; }
 
 int ir_init(int device, ir_ctx** out) {
     if (!out) return -1;
@@ -1922,6 +1938,12 @@ static void release_list(std::vector<void*>& list) {
     for (void* p : list) (void)hipFree(p);
     list.clear();
 }
+// the DiT's prompt caches and the temporaries of ir_dit_set_prompts (a re-bind, or a prompt of another 64-token bucket / more prompts than they hold)
+static void release_prompt_caches(ir_ctx* c) {
+    release_list(c->dit_prompt);
+    c->prompt_cap = c->prompt_slots = 0;
+    c->prompt_e16 = c->prompt_y1 = c->prompt_y2 = nullptr;
+}
 
 static DitLayer bind_dit_layer(Binder& b, const std::string& p, int C, int mlp_hidden) {
     DitLayer L;
@@ -1979,8 +2001,7 @@ int ir_dit_configure(ir_ctx* c, int n_layers, int heads, int head_dim, int mlp_h
     // a re-bind (load_state_dict / .to again) replaces the previous model's tables, control branch and prompt caches
     release_list(c->dit_tabs);
     release_list(c->dit_ctrl_tabs);
-    release_list(c->dit_prompt);
-    c->prompt_cap = 0;
+    release_prompt_caches(c);
     c->dit = DitModel();
     int rc = 0;
     rc |= dev_alloc(c, c->dit_tabs, (void**)&m.tsin, 256 * 4);
@@ -2017,8 +2038,8 @@ int ir_dit_control_configure(ir_ctx* c, int copy_blocks_num) {
     }
     if (!b.ok) return fail(c, -2, "ir_dit_control_configure: tensor %s", b.missing.c_str());
     release_list(c->dit_ctrl_tabs);   // a previous control binding's table
-    release_list(c->dit_prompt);      // prompt caches are rebuilt for base + control layers by the next ir_dit_set_prompt
-    c->prompt_cap = 0;
+    release_prompt_caches(c);         // prompt caches are rebuilt for base + control layers by the next ir_dit_set_prompt
+    m.n_prompts = 1; m.kc_slot = m.vt_slot = m.kb_slot = 0;
     for (DitLayer& L : m.layers) L.kc = L.vtc = nullptr;
     float* tab = nullptr;
     if (dev_alloc(c, c->dit_ctrl_tabs, (void**)&tab, (size_t)copy_blocks_num * 6 * m.C * 4)) return -100;
@@ -2052,8 +2073,7 @@ int ir_dit_set_prompt(ir_ctx* c, void* stream, const float* embeds_host, const f
     // control re-bind, which resets prompt_cap) frees the old buffers and allocates new ones. V^T rows have a tok_pad stride, so
     // a SHORTER bucket is re-allocated as well.
     if (!m.key_bias || c->prompt_cap != tok_pad) {
-        release_list(c->dit_prompt);
-        c->prompt_cap = 0;
+        release_prompt_caches(c);
         m.key_bias = nullptr;
         if (dev_alloc(c, c->dit_prompt, (void**)&m.key_bias, tok_pad * 4)) return -100;
         for (std::vector<DitLayer>* set : {&m.layers, &m.ctrl})
@@ -2062,6 +2082,7 @@ int ir_dit_set_prompt(ir_ctx* c, void* stream, const float* embeds_host, const f
                 if (dev_alloc(c, c->dit_prompt, (void**)&L.vtc, (size_t)m.heads * DV * tok_pad * 2)) return -100;
             }
         c->prompt_cap = tok_pad;
+        c->prompt_slots = 1;
     }
     HIPOK(c, hipMemsetAsync(m.key_bias, 0, tok_pad * 4, s));
     HIPOK(c, hipMemcpyAsync(m.key_bias, bias_host, (size_t)n_tok * 4, hipMemcpyHostToDevice, s));
@@ -2078,7 +2099,65 @@ int ir_dit_set_prompt(ir_ctx* c, void* stream, const float* embeds_host, const f
     HIPOK(c, hipStreamSynchronize(s));   // the temporaries are released when this function returns
     if (r.rc) return fail(c, r.rc, "ir_dit_set_prompt: %s failed", r.where);
     m.n_tok = n_tok; m.tok_pad = tok_pad; m.prompt_ok = true;
+    m.n_prompts = 1; m.kc_slot = m.vt_slot = m.kb_slot = 0;   // (slot 0 of caches ir_dit_set_prompts may have sized for more prompts)
     ++c->generation;
+    return 0;
+}
+
+// P prompts at once, stream-ordered (no host wait, no allocation while (P, 64-token bucket) fits the caches): slot p's K / V are those
+// ir_dit_set_prompt builds for prompt p alone, bit for bit (the projections keep the kernel of n_tok rows).
+int ir_dit_set_prompts(ir_ctx* c, void* stream, const float* embeds_dev, const float* bias_dev, int n_prompts, int n_tok) {
+    if (!c || !c->dit.ok || !embeds_dev || !bias_dev || n_tok <= 0 || n_prompts <= 0)
+        return fail(c, -1, "ir_dit_set_prompts: bad argument / DiT not configured");
+    DitModel& m = c->dit;
+    HIPOK(c, hipSetDevice(c->device));
+    hipStream_t s = (hipStream_t)stream;
+    const int C = m.C, DV = ir_attn_dv(m.hd), P = n_prompts;
+    const int tok_pad = ((n_tok + 63) & ~63) + 64;
+    const long rows = (long)P * n_tok;
+    if ((long)P * tok_pad * std::max(m.cap, 2 * C) >= (1L << 31)) return fail(c, -1, "ir_dit_set_prompts: %d prompts of %d tokens is too many", P, n_tok);
+    const bool realloc = !m.key_bias || c->prompt_cap != tok_pad || c->prompt_slots < P || !c->prompt_e16;
+    if (realloc) {
+        release_prompt_caches(c);
+        m.key_bias = nullptr;
+        const size_t slot_rows = (size_t)P * tok_pad;
+        if (dev_alloc(c, c->dit_prompt, (void**)&m.key_bias, slot_rows * 4)) return -100;
+        for (std::vector<DitLayer>* set : {&m.layers, &m.ctrl})
+            for (DitLayer& L : *set) {
+                if (dev_alloc(c, c->dit_prompt, (void**)&L.kc, slot_rows * 2 * C * 2)) return -100;
+                if (dev_alloc(c, c->dit_prompt, (void**)&L.vtc, (size_t)P * m.heads * DV * tok_pad * 2)) return -100;
+            }
+        if (dev_alloc(c, c->dit_prompt, (void**)&c->prompt_e16, slot_rows * m.cap * 2)) return -100;
+        if (dev_alloc(c, c->dit_prompt, (void**)&c->prompt_y1, slot_rows * C * 2)) return -100;
+        if (dev_alloc(c, c->dit_prompt, (void**)&c->prompt_y2, slot_rows * C * 2)) return -100;
+        c->prompt_cap = tok_pad;
+        c->prompt_slots = P;
+    }
+    HIPOK(c, hipMemcpyAsync(m.key_bias, bias_dev, (size_t)rows * 4, hipMemcpyDeviceToDevice, s));
+    Run r = make_run(c, stream, nullptr, 0, false);
+    r.route_rows = n_tok;
+    bf16_t *e16 = c->prompt_e16, *y1 = c->prompt_y1, *y2 = c->prompt_y2;
+    r.chk(ir_launch_f32_to_bf16(embeds_dev, e16, rows * m.cap, s), "f32_to_bf16");
+    linear(r, m.cap1, e16, (int)rows, m.cap, y1, C, 0, ACT_GELU_TANH, nullptr, 0, 0);
+    linear(r, m.cap2, y1, (int)rows, C, y2, C, 0, ACT_NONE, nullptr, 0, 0);
+    for (std::vector<DitLayer>* set : {&m.layers, &m.ctrl})
+        for (DitLayer& L : *set) {
+            linear(r, L.ckv, y2, (int)rows, C, L.kc, 2 * C, 0, ACT_NONE, nullptr, 0, 0);
+            LAUNCH(r, PC_TRANSPOSE, 0.0, 0.0, ir_launch_transpose_v(L.kc + C, L.vtc, (long)n_tok * 2 * C, 2 * C, m.hd, P, m.heads, n_tok, tok_pad, m.hd, DV, s),
+                   "transpose_v");
+        }
+    if (r.rc) {
+        m.prompt_ok = false;   // the caches may hold part of the new prompts
+        return fail(c, r.rc, "ir_dit_set_prompts: %s failed", r.where);
+    }
+    // recorded graphs carry the caches' addresses and the slot count / strides / n_tok by value: they stay valid unless one of those changed
+    const bool moved = realloc || !m.prompt_ok || m.n_prompts != P || m.n_tok != n_tok || m.tok_pad != tok_pad;
+    m.n_tok = n_tok; m.tok_pad = tok_pad; m.n_prompts = P;
+    m.kc_slot = P > 1 ? (long)n_tok * 2 * C : 0;
+    m.vt_slot = P > 1 ? (long)m.heads * DV * tok_pad : 0;
+    m.kb_slot = P > 1 ? n_tok : 0;
+    m.prompt_ok = true;
+    if (moved) ++c->generation;
     return 0;
 }
 
@@ -2266,6 +2345,12 @@ int ir_unet_set_context(ir_ctx* c, void* stream, const float* context_host, int 
 
 #define REQUIRE(cond, msg) \
     if (!(cond)) return fail(c, -11, msg)
+// the prompt slots set (ir_dit_set_prompts) against a DiT call over n images: one prompt for all, or one per image
+static int check_prompts(ir_ctx* c, int n, const char* who) {
+    const int P = c->dit.n_prompts;
+    if (P != 1 && P != n) return fail(c, -12, "%s: %d prompts are set for a batch of %d images (one prompt, or one per image)", who, P, n);
+    return 0;
+}
 
 static void t5_run(Run& r, const int* ids, const float* key_mask, const float* bias, float* out, int B, int T);
 static void clip_text_run(Run& r, const int* ids, float* out, int B);
@@ -2335,6 +2420,7 @@ int ir_vae_encode(ir_ctx* c, void* stream, const float* in, float* lat, int n, i
 
 int ir_dit_forward(ir_ctx* c, void* stream, const float* lat, float timestep, float* out, int n, int h, int w, void* ws, size_t ws_bytes) {
     REQUIRE(c && c->dit.ok && c->dit.prompt_ok, "DiT not configured or prompt not set");
+    if (int e = check_prompts(c, n, "ir_dit_forward")) return e;
     if (int e = check_size(c, n, h, w, 2)) return e;
     const float* pos = dit_pos(c, h / 2, w / 2, false);
     REQUIRE(pos, "dit.pos table for this latent size not uploaded");
@@ -2347,6 +2433,7 @@ int ir_dit_forward(ir_ctx* c, void* stream, const float* lat, float timestep, fl
 int ir_dit_step(ir_ctx* c, void* stream, const float* lat, float* x0, int n, int h, int w, float timestep, float acp, void* ws,
                 size_t ws_bytes) {
     REQUIRE(c && c->dit.ok && c->dit.prompt_ok, "DiT not configured or prompt not set");
+    if (int e = check_prompts(c, n, "ir_dit_step")) return e;
     if (int e = check_size(c, n, h, w, 2)) return e;
     REQUIRE(acp > 0.f && acp < 1.f, "alpha_cumprod must be in (0,1)");
     const float* pos = dit_pos(c, h / 2, w / 2, false);
@@ -2361,6 +2448,7 @@ int ir_dit_forward_control(ir_ctx* c, void* stream, const float* lat, const floa
                            void* ws, size_t ws_bytes) {
     REQUIRE(c && c->dit.ok && c->dit.prompt_ok, "DiT not configured or prompt not set");
     REQUIRE(c->dit.ncopy > 0 && cond, "control branch not configured (ir_dit_control_configure) or no condition latent");
+    if (int e = check_prompts(c, n, "ir_dit_forward_control")) return e;
     if (int e = check_size(c, n, h, w, 2)) return e;
     const float* pos = dit_pos(c, h / 2, w / 2, false);
     REQUIRE(pos, "dit.pos table for this latent size not uploaded");
@@ -2374,6 +2462,7 @@ int ir_dit_step_control(ir_ctx* c, void* stream, const float* lat, const float* 
                         float acp, void* ws, size_t ws_bytes) {
     REQUIRE(c && c->dit.ok && c->dit.prompt_ok, "DiT not configured or prompt not set");
     REQUIRE(c->dit.ncopy > 0 && cond, "control branch not configured (ir_dit_control_configure) or no condition latent");
+    if (int e = check_prompts(c, n, "ir_dit_step_control")) return e;
     if (int e = check_size(c, n, h, w, 2)) return e;
     REQUIRE(acp > 0.f && acp < 1.f, "alpha_cumprod must be in (0,1)");
     const float* pos = dit_pos(c, h / 2, w / 2, false);
@@ -2474,6 +2563,7 @@ int ir_cldm_pipeline(ir_ctx* c, void* stream, const float* lq, const float* zT, 
         c->graphs.erase(c->graphs.begin());
     }
     c->graphs.push_back({key, exec});
+    ++c->graph_records;
     HIPOK(c, hipGraphLaunch(exec, s));
     return 0;
 }
@@ -2492,6 +2582,7 @@ int ir_pipeline(ir_ctx* c, void* stream, const uint8_t* in, uint8_t* out, uint8_
     REQUIRE((flags & IR_FLAG_NO_PREPROCESS) || c->swin.ok, "pipeline: SwinIR not configured");
     REQUIRE(acp > 0.f && acp < 1.f && sf > 0.f, "pipeline: bad alpha_cumprod / scaling factor");
     REQUIRE(!(flags & IR_FLAG_CONTROL_LQ) || c->dit.ncopy > 0, "pipeline: IR_FLAG_CONTROL_LQ without ir_dit_control_configure");
+    if (int e = check_prompts(c, n, "ir_pipeline")) return e;
     if (int e = check_size(c, n, h, w, 64)) return e;
     struct Fp8Scope {  // IR_FLAG_FP8 holds for this call only (it is part of the graph key through `flags`)
         ir_ctx* c; bool old;
@@ -2551,6 +2642,7 @@ int ir_pipeline(ir_ctx* c, void* stream, const uint8_t* in, uint8_t* out, uint8_
         c->graphs.erase(c->graphs.begin());
     }
     c->graphs.push_back({key, exec});
+    ++c->graph_records;
     c->dit.cached_t = -1e30f;
     HIPOK(c, hipGraphLaunch(exec, s));
     return 0;
@@ -2623,6 +2715,7 @@ int ir_tiled_dit(ir_ctx* c, void* stream, const float* init, float* x0_tiles, in
     REQUIRE(c && c->dit.ok && c->dit.prompt_ok, "tiled dit: DiT not configured or prompt not set");
     REQUIRE(!(flags & IR_FLAG_CONTROL_LQ) || c->dit.ncopy > 0, "tiled dit: IR_FLAG_CONTROL_LQ without ir_dit_control_configure");
     REQUIRE(init && x0_tiles && first >= 0 && step >= 1 && acp > 0.f && acp < 1.f, "tiled dit: bad argument");
+    if (int e = check_prompts(c, n, "ir_tiled_dit")) return e;
     if (int e = check_size(c, n, h, w, 64)) return e;
     Run r = make_run(c, stream, ws, ws_bytes, false);
     TileGeom g;
@@ -3128,6 +3221,36 @@ int ir_op_attention(ir_ctx* c, void* stream, const uint16_t* q, const uint16_t* 
     p.B = b; p.Hh = heads; p.Tq = tq; p.Tk = tk; p.Tk_pad = tkp; p.D = d;
     p.scale_log2 = scale * 1.44269504088896340736f;
     p.key_bias = key_bias; p.kb_bs = tk;
+    rc = ir_launch_flash_attn(p, s);
+    return rc ? fail(c, rc, "flash_attn failed (%d)", rc) : 0;
+}
+// the DiT cross-attention with prompt slots: q / o [b][tq][heads*d], k / v [groups][tk][heads*d], key_bias (optional) [groups][tk]; item i attends to
+// K / V set i % groups. Workspace as ir_op_attention's for `groups` K / V sets (d = 512 has no grouped form).
+int ir_op_attention_kv_groups(ir_ctx* c, void* stream, const uint16_t* q, const uint16_t* k, const uint16_t* v, uint16_t* o, int b, int heads,
+                              int tq, int tk, int d, float scale, const float* key_bias, int groups, void* ws, size_t ws_bytes) {
+    use_ctx(c);
+    if (groups < 1 || b < 1 || b % groups) return fail(c, -2, "attention_kv_groups: %d items do not split into %d groups", b, groups);
+    if (d == 512) return fail(c, -5, "attention_kv_groups: no d = 512 form");
+    const int DV = ir_attn_dv(d), tkp = ((tk + 63) & ~63) + 64;
+    const size_t need = (size_t)groups * heads * DV * tkp * 2;
+    if (ws_bytes < need) return fail(c, -20, "attention workspace too small: need %zu", need);
+    hipStream_t s = (hipStream_t)stream;
+    int rc = ir_launch_transpose_v(v, (bf16_t*)ws, (long)tk * heads * d, heads * d, d, groups, heads, tk, tkp, d, DV, s);
+    if (rc) return fail(c, rc, "transpose_v failed (%d)", rc);
+    AttnParams p;
+    memset(&p, 0, sizeof p);
+    p.q = q; p.k = k; p.vt = (const bf16_t*)ws; p.o = o;
+    if (ws_bytes >= need + 64) {
+        const size_t off = (need + 15) & ~(size_t)15;
+        p.ovf_flag = (int*)((char*)ws + off);
+        p.ovf_map = (int)std::min<size_t>((ws_bytes - off) / 4 - 1, (size_t)1 << 24);
+    }
+    p.q_bs = (long)tq * heads * d; p.k_bs = (long)tk * heads * d; p.o_bs = p.q_bs; p.vt_bs = (long)heads * DV * tkp;
+    p.q_rs = p.k_rs = p.o_rs = heads * d; p.q_hs = p.k_hs = p.o_hs = d;
+    p.B = b; p.Hh = heads; p.Tq = tq; p.Tk = tk; p.Tk_pad = tkp; p.D = d;
+    p.scale_log2 = scale * 1.44269504088896340736f;
+    p.key_bias = key_bias; p.kb_bs = tk;
+    p.kv_groups = groups;
     rc = ir_launch_flash_attn(p, s);
     return rc ? fail(c, rc, "flash_attn failed (%d)", rc) : 0;
 }

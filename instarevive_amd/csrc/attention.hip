@@ -64,9 +64,10 @@ __global__ __launch_bounds__(256, 2) void flash_attn_kernel(AttnParams p) {
         reinterpret_cast<volatile const int*>(p.ovf_flag)[1 + ((long)b * p.Hh + head) * ((p.Tq + 255) >> 8) + (q0 >> 8)] == 0) return;
 
     const bf16_t* qp = p.q + (long)b * p.q_bs + (long)head * p.q_hs;
-    const bf16_t* kp = p.k + (long)b * p.k_bs + (long)head * p.k_hs;
-    const bf16_t* vtp = p.vt + (long)b * p.vt_bs + (long)head * DV * p.Tk_pad;
-    const float* kb = p.key_bias ? p.key_bias + (long)b * p.kb_bs : nullptr;
+    const int kvb = ir_attn_kv_item(p, b);
+    const bf16_t* kp = p.k + (long)kvb * p.k_bs + (long)head * p.k_hs;
+    const bf16_t* vtp = p.vt + (long)kvb * p.vt_bs + (long)head * DV * p.Tk_pad;
+    const float* kb = p.key_bias ? p.key_bias + (long)kvb * p.kb_bs : nullptr;
     constexpr bool general = GENERAL;  // additive key bias and/or ragged last tile -> bias path through LDS (separate instantiation)
 
     // Every global load below is UNCONDITIONAL on a clamped, always-valid address and never feeds a select: hipcc turns
@@ -303,7 +304,7 @@ int ir_launch_flash_attn_fallback(const AttnParams& p, hipStream_t s) {
 
 bool ir_flash_attn_is_pp2(const AttnParams& p) {
     const bool general = p.key_bias != nullptr || (p.Tk & 63);
-    return p.D == 72 && !general && p.Tq >= 256 && p.ovf_flag && !g_ir_plain_kernels;
+    return p.D == 72 && !general && p.Tq >= 256 && p.ovf_flag && !g_ir_plain_kernels && p.kv_groups <= 1;
 }
 
 int ir_launch_flash_attn(const AttnParams& p, hipStream_t s) {
@@ -313,6 +314,7 @@ int ir_launch_flash_attn(const AttnParams& p, hipStream_t s) {
         return -3;
     if ((p.Tk_pad & 63) || p.Tk_pad < ((p.Tk + 63) & ~63)) return -4;
     if (p.scale_log2 <= 0.f) return -6;
+    if (p.kv_groups < 0 || (p.kv_groups > 1 && p.B % p.kv_groups)) return -7;   // every slot serves the same number of items
     dim3 grid((p.Tq + 127) / 128, p.Hh, p.B);
     const bool general = p.key_bias != nullptr || (p.Tk & 63);
     if (ir_flash_attn_is_pp2(p)) {  // the DiT self-attention: flash_attn_pp2_kernel, 256 queries per workgroup

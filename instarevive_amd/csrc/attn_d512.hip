@@ -782,17 +782,18 @@ __global__ __launch_bounds__(256, 1) void flash_attn_x72_kernel(AttnParams p, in
 
     q_fetch(it0);
     wait_dma();   // (vmcnt(0): the first item's rows; later items' rows are waited for before the previous item's output stores)
-    int cur_b = -1, cur_head = -1;
+    int cur_kv = -1, cur_head = -1;
     for (int it = it0; it < it1; ++it) {
         int b, head, qt;
         item(it, b, head, qt);
         const int q0 = qt * 256 + wid * 64;
         // ---- K / V^T of the head -> LDS (when the head, or a batch with its own K / V, changes)
-        if (head != cur_head || (b != cur_b && (p.k_bs != 0 || p.vt_bs != 0 || p.kb_bs != 0))) {
+        const int kvb = ir_attn_kv_item(p, b);   // the prompt slot of the item (wave-uniform)
+        if (head != cur_head || (kvb != cur_kv && (p.k_bs != 0 || p.vt_bs != 0 || p.kb_bs != 0))) {
             __syncthreads();   // every wave is done with the previous head's tiles
-            const bf16_t* kp = p.k + (long)b * p.k_bs + (long)head * p.k_hs;
-            const bf16_t* vtp = p.vt + (long)b * p.vt_bs + (long)head * 96 * p.Tk_pad;
-            const float* kb = p.key_bias ? p.key_bias + (long)b * p.kb_bs : nullptr;
+            const bf16_t* kp = p.k + (long)kvb * p.k_bs + (long)head * p.k_hs;
+            const bf16_t* vtp = p.vt + (long)kvb * p.vt_bs + (long)head * 96 * p.Tk_pad;
+            const float* kb = p.key_bias ? p.key_bias + (long)kvb * p.kb_bs : nullptr;
             // every load of a thread is issued before its first LDS store (fixed trip counts, unrolled: 13 + 13 x 16 bytes in flight per thread):
             // a load -> store loop costs one memory latency per trip, 25 trips per head
             constexpr int KTRIP = (MAXT * 64 * 10 + 255) / 256, VTRIP = (MAXT * 80 * 8 + 255) / 256;
@@ -839,7 +840,7 @@ __global__ __launch_bounds__(256, 1) void flash_attn_x72_kernel(AttnParams p, in
             if (cur_head < 0)   // rows 80..95 of every tile: multiplied (third O^T tile) but never loaded - zeros toggle nothing (see flash_attn_pp2_kernel)
                 for (int c = tid_o; c < MAXT * 16 * 8; c += 256)
                     *reinterpret_cast<uint4*>(smem + V_OFF + (c >> 7) * VSLOT + (80 + ((c & 127) >> 3)) * 128 + (c & 7) * 16) = make_uint4(0, 0, 0, 0);
-            cur_b = b; cur_head = head;
+            cur_kv = kvb; cur_head = head;
             __syncthreads();
         }
 

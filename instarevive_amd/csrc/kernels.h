@@ -135,7 +135,11 @@ struct AttnParams {
     int ovf_map;               // ints available BEHIND ovf_flag[0] (0: none). With B * Hh * ceil(Tq / 256) of them (round 6) flash_attn_pp2_kernel marks the
                                // 256-query workgroups whose fixed reference was outgrown, and the rescaling kernel behind it recomputes only those
                                // instead of the whole launch (one peaky row among 16384 x 16 used to cost 28 x 1.7 ms per image)
+    int kv_groups;             // 0 / 1: K, V^T and key bias of item b sit at b * k_bs / vt_bs / kb_bs. G > 1: at (b % G) * ..., G prompt slots shared round-robin
+                               // by the B items (B % G == 0; the DiT cross-attention with one prompt per image, item = tile * n + image)
 };
+// the K / V^T / key-bias batch index of item b (wave-uniform)
+__host__ __device__ inline int ir_attn_kv_item(const AttnParams& p, int b) { return p.kv_groups > 1 ? b % p.kv_groups : b; }
 int ir_launch_flash_attn(const AttnParams& p, hipStream_t s);
 bool ir_flash_attn_is_pp2(const AttnParams& p);   // ir_launch_flash_attn routes p to flash_attn_pp2_kernel (profiler rows)
 // DiT self-attention (D = 72, Tk % 64 == 0, no key bias, ovf_flag set) as one wave per SIMD with two query groups (attn_d512.hip)

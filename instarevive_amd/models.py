@@ -365,6 +365,20 @@ class AutoencoderKL(_DeviceModule):
 
 
 # ====================================================================================================== DiT
+def prompt_bias(encoder_attention_mask, rows, n_tok):
+    """The additive key bias of each prompt row as host fp32 [rows, n_tok]: none -> zeros; a 2-D mask [B, L] -> (1 - m) * -10000 (diffusers
+    Transformer2DModel.forward); any other shape ([B, 1, L], what the reference's CLI passes) is the bias as is. One mask row serves every row."""
+    if encoder_attention_mask is None:
+        return torch.zeros(rows, n_tok)
+    m = encoder_attention_mask.detach().to("cpu", torch.float32)
+    bias = (1 - m) * -10000.0 if m.ndim == 2 else m.reshape(-1, m.shape[-1])
+    if bias.shape[0] != rows and all(torch.equal(bias[0], b) for b in bias[1:]):
+        bias = bias[:1].expand(rows, -1)
+    if bias.shape != (rows, n_tok):
+        raise ValueError(f"encoder_attention_mask of shape {tuple(m.shape)} does not fit {rows} prompts of {n_tok} tokens")
+    return bias.contiguous()
+
+
 class Transformer2DModel(_DeviceModule):
     FAMILY = "dit"
 
@@ -397,6 +411,7 @@ class Transformer2DModel(_DeviceModule):
                                       num_layers=num_layers, num_attention_heads=num_attention_heads, attention_head_dim=attention_head_dim,
                                       caption_channels=caption_channels)
         self._prompt_key = None
+        self._prompt_dev = None   # device copies of the prompts ir_dit_set_prompts was given (kept until the next prompt replaces them)
 
     @classmethod
     def from_pretrained(cls, name_or_path, subfolder=None, **kw):
@@ -440,7 +455,9 @@ class Transformer2DModel(_DeviceModule):
                                                      c["interpolation_scale"]))
 
     def set_prompt(self, encoder_hidden_states, encoder_attention_mask=None):
-        """Project the caption and cache all layers' cross-attention K/V (constant across images and tiles)."""
+        """Project the caption(s) and cache all layers' cross-attention K/V. Rows all equal: one prompt for the whole batch (ir_dit_set_prompt).
+        Rows that differ: one prompt per row (ir_dit_set_prompts), and batch item i of every later DiT call attends to prompt i (the tiles of
+        image i under tiling) - the per-image captions of the reference's evaluation loop (test_dmd_general.py:173-174)."""
         self._ready()
         y = encoder_hidden_states
         # Cache key: the tensor OBJECTS (held strongly, so their storage cannot be recycled for another prompt at the same
@@ -452,23 +469,29 @@ class Transformer2DModel(_DeviceModule):
         key = (y, y._version, encoder_attention_mask, None if encoder_attention_mask is None else encoder_attention_mask._version)
         y = y.detach().to("cpu", torch.float32)
         y = y.reshape(-1, y.shape[-2], y.shape[-1])
-        if y.shape[0] != 1:
-            if not all(torch.equal(y[0], y[i]) for i in range(1, y.shape[0])):
-                raise NotImplementedError("one shared prompt per batch (the CLI uses a single fixed prompt file, inference.py:256-259)")
-        y = y[0].contiguous()
-        n_tok = y.shape[0]
-        if encoder_attention_mask is None:
-            bias = torch.zeros(n_tok)
-        else:
-            m = encoder_attention_mask.detach().to("cpu", torch.float32)
-            if m.ndim == 2:  # diffusers Transformer2DModel.forward: 2-D masks become (1 - m) * -10000
-                bias = (1 - m[0]) * -10000.0
-            else:            # ndim == 3 ([B,1,L], what the CLI passes): used as an additive bias as is
-                bias = m.reshape(-1, m.shape[-1])[0]
-        bias = bias.contiguous()
-        self.ctx.check(self.ctx.lib.ir_dit_set_prompt(self.ctx.h, self.ctx.stream(), C.c_void_p(y.data_ptr()), C.c_void_p(bias.data_ptr()), n_tok),
-                       "ir_dit_set_prompt")
+        self._set_prompt_rows(y, prompt_bias(encoder_attention_mask, y.shape[0], y.shape[1]), stream_ordered=False)
         self._prompt_key = key
+
+    def _set_prompt_rows(self, y, bias, stream_ordered):
+        """y: host fp32 [B, T, caption_dim], bias: host fp32 [B, T] (additive, per key). stream_ordered: the prompts travel through pinned memory
+        and ir_dit_set_prompts even when they are all equal (P = 1), so that the call queues behind the stream's work without a host wait."""
+        same = all(torch.equal(y[0], y[i]) and torch.equal(bias[0], bias[i]) for i in range(1, y.shape[0]))
+        n_tok = y.shape[1]
+        if same and not stream_ordered:   # today's single-prompt path
+            y0, b0 = y[0].contiguous(), bias[0].contiguous()
+            self.ctx.check(self.ctx.lib.ir_dit_set_prompt(self.ctx.h, self.ctx.stream(), C.c_void_p(y0.data_ptr()), C.c_void_p(b0.data_ptr()), n_tok),
+                           "ir_dit_set_prompt")
+            self._prompt_dev = None
+            return
+        if same:
+            y, bias = y[:1], bias[:1]
+        if stream_ordered:
+            y, bias = y.contiguous().pin_memory(), bias.contiguous().pin_memory()
+        yd = y.to(self.device, torch.float32, non_blocking=stream_ordered).contiguous()
+        bd = bias.to(self.device, torch.float32, non_blocking=stream_ordered).contiguous()
+        self.ctx.check(self.ctx.lib.ir_dit_set_prompts(self.ctx.h, self.ctx.stream(), L.ptr(yd), L.ptr(bd), y.shape[0], n_tok), "ir_dit_set_prompts")
+        self._prompt_dev = (yd, bd)   # read by the queued projection: released (stream-ordered) when the next prompt replaces it
+        self._prompt_key = None
 
     def invalidate_prompt(self):
         """Forget the cached prompt: the next call projects encoder_hidden_states again even if it is the same tensor object."""

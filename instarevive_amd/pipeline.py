@@ -12,7 +12,7 @@ import numpy as np
 import torch
 
 from . import _lib as L
-from .models import AutoencoderKL, ControlTransformerHalf, DDPMScheduler, SwinIR, Transformer2DModel
+from .models import AutoencoderKL, ControlTransformerHalf, DDPMScheduler, SwinIR, Transformer2DModel, prompt_bias
 
 
 class _Staging:
@@ -161,12 +161,13 @@ def _pipeline_flags(model, color_fix_type, disable_preprocess_model, tiled):
     return flags
 
 
-def _prepare_fused(model, y, y_mask, h, w, tiled, tile_size, others=()):
+def _prepare_fused(model, y, y_mask, h, w, tiled, tile_size, others=(), set_prompt=True):
     for m in others:  # the context must hold THESE models' weights (another instance of the family may have been loaded since)
         if m is not None:
             m._ready()
     model._ready()    # a ControlTransformerHalf re-binds its control branch here (set_prompt below resolves to the base model only)
-    model.set_prompt(y, y_mask)
+    if set_prompt:
+        model.set_prompt(y, y_mask)
     if tiled:
         model.ensure_pos(tile_size // 16, tile_size // 16)
     else:
@@ -257,6 +258,13 @@ def process(model, control_imgs: List[np.ndarray], strength: float, color_fix_ty
     return [x_samples[i] for i in range(n)], [control[i] for i in range(n)]
 
 
+def _split_batch(b):
+    """A process_stream batch: a sequence of images, or an (images, y, y_mask) triple with the batch's own prompts (y a tensor)."""
+    if isinstance(b, tuple) and len(b) == 3 and isinstance(b[1], torch.Tensor):
+        return b[0], b[1], b[2]
+    return b, None, None
+
+
 @torch.no_grad()
 def process_stream(model, batches: Iterable[Sequence[np.ndarray]], color_fix_type: str, disable_preprocess_model: bool, tiled: bool,
                    tile_size: int, tile_stride: int, preprocess_model=None, vae=None, y=None, y_mask=None, noise_scheduler=None,
@@ -264,7 +272,10 @@ def process_stream(model, batches: Iterable[Sequence[np.ndarray]], color_fix_typ
     """process() over a sequence of image batches with the transfers hidden: while batch i computes on the current stream, batch
     i+1 is uploaded and batch i-1 downloaded on a copy stream (two staging slots per batch shape). Yields process()'s result for
     every batch, in order. Needs the fused form (all models instarevive_amd objects on one context). fp8 as in process() (cfg-5:
-    vae.enable_fp8() first; the operand set is the context's ir_set_fp8_mask, by default the tolerance-chosen one)."""
+    vae.enable_fp8() first; the operand set is the context's ir_set_fp8_mask, by default the tolerance-chosen one).
+    A batch may also be an (images, y, y_mask) triple: y [B, T, C] / y_mask (as set_prompt takes them) are that batch's prompts, one per image
+    or one for all. They are queued on the stream right before the batch's launch (pinned upload, ir_dit_set_prompts: no host wait), so a
+    recorded graph (graph=True) replays across batches whose prompts differ in content only. Batches without prompts take y / y_mask."""
     noise_scheduler = noise_scheduler or DDPMScheduler()
     if not _fused_ok(model, preprocess_model, vae, disable_preprocess_model):
         raise TypeError("process_stream needs instarevive_amd models sharing one context")
@@ -276,13 +287,14 @@ def process_stream(model, batches: Iterable[Sequence[np.ndarray]], color_fix_typ
     main, copy = torch.cuda.current_stream(device), ctx.__dict__.setdefault("_copy_stream", torch.cuda.Stream(device))
     it = iter(batches)
 
-    def upload(imgs, slot):
+    def upload(batch, slot):
+        imgs, by, bm = _split_batch(batch)
         n, h, w = _check_images(imgs)
         st = _Staging.get(ctx, n, h, w, slots=2, tag="stream")
         st.fill(slot, imgs)
         with torch.cuda.stream(copy):
             ev = st.upload(slot, copy)
-        return st, slot, (n, h, w), ev
+        return st, slot, (n, h, w), ev, (by, bm)
 
     def download(job):
         st, slot, (n, h, w), done = job
@@ -291,12 +303,33 @@ def process_stream(model, batches: Iterable[Sequence[np.ndarray]], color_fix_typ
         stage1 = st.h_st1[slot].clone().numpy() if return_stage1 else None
         return [preds[i] for i in range(n)], ([stage1[i] for i in range(n)] if return_stage1 else [])
 
+    last_prompt = None   # the host prompts of the last triple batch that were set (a batch with the same ones sets nothing)
+
+    def set_batch_prompt(by, bm, n):
+        nonlocal last_prompt
+        if by is None:
+            if last_prompt is not None:   # back to the run's own prompt after per-batch ones
+                model.invalidate_prompt()
+                last_prompt = None
+            model.set_prompt(y, y_mask)
+            return
+        hy = by.detach().to("cpu", torch.float32)
+        hy = hy.reshape(-1, hy.shape[-2], hy.shape[-1])
+        hb = prompt_bias(bm, hy.shape[0], hy.shape[1])
+        if hy.shape[0] not in (1, n):
+            raise ValueError(f"process_stream: a batch of {n} images came with {hy.shape[0]} prompts (one, or one per image)")
+        if last_prompt is not None and torch.equal(last_prompt[0], hy) and torch.equal(last_prompt[1], hb):
+            return
+        model._set_prompt_rows(hy, hb, stream_ordered=True)
+        last_prompt = (hy, hb)
+
     slot, pending = 0, None
     nxt = next(it, None)
     up = upload(nxt, slot) if nxt is not None else None
     while up is not None:
-        st, cur, (n, h, w), ready = up
-        _prepare_fused(model, y, y_mask, h, w, tiled, tile_size, (vae, None if disable_preprocess_model else preprocess_model))
+        st, cur, (n, h, w), ready, (by, bm) = up
+        _prepare_fused(model, y, y_mask, h, w, tiled, tile_size, (vae, None if disable_preprocess_model else preprocess_model), set_prompt=False)
+        set_batch_prompt(by, bm, n)
         main.wait_event(ready)
         _launch_pipeline(ctx, st, cur, n, h, w, base_flags, tile_size, tile_stride, acp, sf, return_stage1)
         computed = torch.cuda.Event()
