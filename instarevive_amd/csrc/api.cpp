@@ -1132,21 +1132,14 @@ void dit_block(Run& r, const DitLayer& Lw, const float* mod, float* x, const Dit
     linear(r, Lw.fc2, b.hid, (int)BT, m.mlp, x, C, 1, ACT_NONE, x, 1, C, out2, C, mod + 5 * C);
 }
 
-// returns fp32 tokens [n*T][32] of the final projection (column (p*2+q)*8 + c), allocated from the arena (not released).
-// ctrl_lat (optional, needs ir_dit_control_configure): the condition latent `c` of ControlTransformerHalf.forward
-// (transformer_controlnet.py:101-173), same shape as lat; the control copies then feed blocks 1..ncopy.
-float* dit_tokens_run(Run& r, const float* lat, int n, int h, int w, float timestep, const float* pos, const float* ctrl_lat = nullptr) {
-    DitModel& m = r.c->dit;
-    const int gh = h / 2, gw = w / 2, C = m.C, Hh = m.heads, hd = m.hd;
+// The block scratch of n items on a gh x gw token grid, from the arena, and the V^T padding that lets the qkv projection's epilogue write
+// V^T itself. Every caller of dit_block sizes its buffers here, so they all take the same kernel routes.
+void dit_bufs_init(Run& r, DitBufs& b, int n, int gh, int gw) {
+    const DitModel& m = r.c->dit;
+    const int C = m.C, Hh = m.heads, hd = m.hd;
     const long T = (long)gh * gw, BT = n * T;
-    DitBufs b;
     b.n = n; b.T = T;
     b.Tpad = (int)((T + 63) & ~63L) + 64; b.DV = ir_attn_dv(hd);  // +64: no power-of-two row stride (channel conflicts)
-    dit_update_timestep(r, timestep, h, w);
-    float* tok = r.a.alloc<float>(BT * 32);
-    const size_t mk = r.a.mark();
-    bf16_t* tokp = r.a.alloc<bf16_t>(BT * 32);
-    float* x = r.a.alloc<float>(BT * C);
     b.xb = r.a.alloc<bf16_t>(BT * C);
     b.xn = r.a.alloc<bf16_t>(BT * C);
     b.qkv = r.a.alloc<bf16_t>(BT * 3 * C);
@@ -1166,15 +1159,31 @@ float* dit_tokens_run(Run& r, const float* lat, int n, int h, int w, float times
     b.att = r.a.alloc<bf16_t>(BT * C);
     b.cq = r.a.alloc<bf16_t>(BT * C);
     b.hid = r.a.alloc<bf16_t>(BT * m.mlp);
+    if (hd == 72 && (T & 63) == 0 && T >= 256 && !r.c->plain) {   // (cheap: 50 MB at 16384 tokens, once per step)
+        LAUNCH(r, PC_TRANSPOSE, 0.0, 0.0, ir_launch_vt_pad_init(b.vt, n * Hh, hd, b.DV, (int)T, b.Tpad, r.s), "vt_pad_init");
+        b.vt_ready = r.live();
+    }
+}
+
+// returns fp32 tokens [n*T][32] of the final projection (column (p*2+q)*8 + c), allocated from the arena (not released).
+// ctrl_lat (optional, needs ir_dit_control_configure): the condition latent `c` of ControlTransformerHalf.forward
+// (transformer_controlnet.py:101-173), same shape as lat; the control copies then feed blocks 1..ncopy.
+float* dit_tokens_run(Run& r, const float* lat, int n, int h, int w, float timestep, const float* pos, const float* ctrl_lat = nullptr) {
+    DitModel& m = r.c->dit;
+    const int gh = h / 2, gw = w / 2, C = m.C;
+    const long T = (long)gh * gw, BT = n * T;
+    dit_update_timestep(r, timestep, h, w);
+    float* tok = r.a.alloc<float>(BT * 32);
+    const size_t mk = r.a.mark();
+    bf16_t* tokp = r.a.alloc<bf16_t>(BT * 32);
+    float* x = r.a.alloc<float>(BT * C);
+    DitBufs b;
+    dit_bufs_init(r, b, n, gh, gw);
     float* cs = nullptr;    // control stream (fp32) and its bf16 copy
     bf16_t* csb = nullptr;
     if (m.ncopy > 0) {      // sized whenever the branch is configured, so ir_workspace_bytes covers the conditioned call
         cs = r.a.alloc<float>(BT * C);
         csb = r.a.alloc<bf16_t>(BT * C);
-    }
-    if (hd == 72 && (T & 63) == 0 && T >= 256 && !r.c->plain) {   // (cheap: 50 MB at 16384 tokens, once per step)
-        LAUNCH(r, PC_TRANSPOSE, 0.0, 0.0, ir_launch_vt_pad_init(b.vt, n * Hh, hd, b.DV, (int)T, b.Tpad, r.s), "vt_pad_init");
-        b.vt_ready = r.live();
     }
     LAUNCH(r, PC_OTHER, 0.0, 0.0, ir_launch_patchify(lat, tokp, n, gh, gw, 32, r.s), "patchify");
     linear(r, m.patch, tokp, (int)BT, 32, x, C, 1, ACT_NONE, pos, 1, C, nullptr, 0, nullptr, (int)T);
@@ -2427,6 +2436,20 @@ int ir_dit_forward(ir_ctx* c, void* stream, const float* lat, float timestep, fl
     Run r = make_run(c, stream, ws, ws_bytes, false);
     float* tok = dit_tokens_run(r, lat, n, h, w, timestep, pos);
     LAUNCH(r, PC_OTHER, 0.0, 0.0, ir_launch_unpatchify(tok, out, n, h / 2, w / 2, r.s), "unpatchify");
+    return finish(r, c, ws_bytes);
+}
+
+int ir_op_dit_block(ir_ctx* c, void* stream, float* x, int layer, int n, int gh, int gw, float timestep, void* ws, size_t ws_bytes) {
+    REQUIRE(c && c->dit.ok && c->dit.prompt_ok, "DiT not configured or prompt not set");
+    if (layer < 0 || layer >= c->dit.L) return fail(c, -1, "ir_op_dit_block: layer %d outside 0..%d", layer, c->dit.L - 1);
+    if (int e = check_prompts(c, n, "ir_op_dit_block")) return e;
+    if (int e = check_size(c, n, gh, gw, 1)) return e;
+    REQUIRE(x, "ir_op_dit_block: no token stream");
+    Run r = make_run(c, stream, ws, ws_bytes, false);
+    dit_update_timestep(r, timestep, 2 * gh, 2 * gw);
+    DitBufs b;
+    dit_bufs_init(r, b, n, gh, gw);
+    dit_block(r, c->dit.layers[layer], c->dit.modtab + (long)layer * 6 * c->dit.C, x, b);
     return finish(r, c, ws_bytes);
 }
 

@@ -460,8 +460,9 @@ int ir_launch_gemv_f32(const float* w, const float* x, const float* b, float* ou
 //   * qk_norm (:136-137): r = 1, no weights, LayerNorm over all C channels of the token, in place on the q / k columns of the qkv rows.
 // in: [B][gh * gw] bf16 rows (row stride in_rs, batch stride in_bs); out: [B][(gh / r) * (gw / r)] rows (out_rs, out_bs); w: [C][r * r] fp32 or null
 // (weight 1 on tap 0), bias [C] or null, gamma / beta [C] or null (no LayerNorm); eps 1e-5 (nn.LayerNorm default). One 256-thread workgroup per
-// output token, a thread's channels (at most 8: C <= 2048) in registers between the two passes, so in == out is allowed for r == 1.
-__global__ __launch_bounds__(256) void dit_token_prep_kernel(const bf16_t* __restrict__ in, bf16_t* out, const float* __restrict__ w, const float* __restrict__ bias,
+// output token, a thread's channels (at most 8: C <= 2048) in registers between the two passes, so in == out is allowed for r == 1 (qk_norm
+// runs in place: neither pointer is __restrict__).
+__global__ __launch_bounds__(256) void dit_token_prep_kernel(const bf16_t* in, bf16_t* out, const float* __restrict__ w, const float* __restrict__ bias,
                                                              const float* __restrict__ gamma, const float* __restrict__ beta, int gh, int gw, int r, int C,
                                                              int in_rs, long in_bs, int out_rs, long out_bs, float eps) {
     __shared__ float red[2][4];

@@ -131,6 +131,15 @@ def test_swin_fused_launchers_refuse_empty_and_negative_grids():
                                     None, None, None, None, 0) == -2, (h, w)
 
 
+def test_dit_block_entry_refuses_a_missing_context():
+    """ir_op_dit_block returns -11 (no configured DiT) before anything touches a device."""
+    from instarevive_amd import _lib
+    from instarevive_amd.build import build
+    build()
+    lib = _lib.load_library()
+    assert lib.ir_op_dit_block(None, None, None, 0, 1, 4, 4, 400.0, None, 0) == -11
+
+
 def test_sliding_windows_and_loaders():
     from instarevive_amd.pipeline import _sliding_windows
     from instarevive_amd import utils
