@@ -299,6 +299,24 @@ int ir_op_vae_conv_in(ir_ctx* ctx, void* stream, const float* in, const uint16_t
                       int w, float in_scale, float in_shift, int* tiles);
 int ir_op_vae_norm_conv_out(ir_ctx* ctx, void* stream, const uint16_t* x, const float* scale, const float* shift, const uint16_t* wgt, const float* bias,
                             float* out, int n, int h, int w);
+/* A segment of the CONFIGURED VAE chain for op-level tests: steps first .. first + count - 1 of one half (0 encoder, 1 decoder; weights as
+ * uploaded for ir_vae_configure, fp8 and phase forms included) on x [n][h][w][cin of step first] bf16 NHWC -> y [n][oh][ow][cout of the last
+ * step] bf16 NHWC. The steps of a half are the interior of ir_vae_encode / ir_vae_decode in production order,
+ *   encoder: down0.res0, down0.res1, down0.ds, ... , down3.res1, mid.res0, mid.attn, mid.res1
+ *   decoder: mid.res0, mid.attn, mid.res1, up3.res0, up3.res1, up3.res2, up3.us, up2.res0, ... , up0.res2
+ * (conv_in, norm_out / conv_out and the quant convs stay outside), run by the very host code of the two stage functions: every step sees the
+ * state its production predecessor left (fused GroupNorm statistics, the fp8 bit of its level), and ir_set_plain_kernels, ir_set_fp8 /
+ * ir_set_fp8_mask and the profiler act as they do on the stages. The FIRST step of a segment has no pending statistics (its input came from
+ * the caller) and takes the stand-alone statistics pass; start one step earlier to see a step on its production route.
+ * ws: at least ir_op_vae_segment_ws(...) bytes (0: the arguments are refused). Returns -1 for a bad half, first or count or a null tensor,
+ * -10 for n, h or w < 1 or a size a step cannot take (odd in front of a Downsample), -11 when that half is not configured, -20 when ws is
+ * too small; nothing is launched then.
+ * ir_op_vae_segment_info: the number of steps of the half (or the error code); for step >= 0 also its name (up to name_cap bytes), channel
+ * counts and, for an h x w input, its output size (0 x 0 where the step cannot take h x w). step < 0: the count alone. */
+int ir_op_vae_segment(ir_ctx* ctx, void* stream, int half, int first, int count, const uint16_t* x, uint16_t* y, int n, int h, int w, void* ws,
+                      size_t ws_bytes);
+size_t ir_op_vae_segment_ws(ir_ctx* ctx, int half, int first, int count, int n, int h, int w);
+int ir_op_vae_segment_info(ir_ctx* ctx, int half, int step, int h, int w, char* name, int name_cap, int* cin, int* cout, int* oh, int* ow);
 /* Per-kernel test entry of conv64_kernel (vae_io.hip): 3x3 stride-1 conv 64 -> 64 on bf16 NHWC, bias, act = IR_ACT_NONE or IR_ACT_LRELU(slope) - the shape
  * of SwinIR's conv_hr (diffusion/model/swinir.py:895); h * w >= 65536. The pipeline takes this kernel only under IR_CONV64=1 (see vae_io.hip). */
 int ir_op_conv64(ir_ctx* ctx, void* stream, const uint16_t* in, const uint16_t* wgt, const float* bias, uint16_t* out, int n, int h, int w, int act,

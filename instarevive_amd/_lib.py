@@ -23,7 +23,7 @@ SYMBOLS = [
     "ir_op_swin_mlp", "ir_op_swin_attn_proj", "ir_op_swin_block", "ir_op_dit_block", "ir_op_softmax_rows", "ir_op_nchw_to_nhwc", "ir_op_nhwc_to_nchw",
     "ir_tiled_count", "ir_tiled_encode", "ir_tiled_encode_part", "ir_tiled_encode_overflow", "ir_op_conv_up2x2", "ir_op_conv_norm", "ir_op_vae_conv_in", "ir_op_vae_norm_conv_out", "ir_op_conv64", "ir_op_conv64_to3", "ir_tiled_dit", "ir_tiled_blend_latent", "ir_tiled_decode", "ir_tiled_blend_pixels", "ir_set_plain_kernels", "ir_set_fp8", "ir_set_fp8_mask", "ir_attn_fallback_count", "ir_op_conv_fp8", "ir_op_conv_fp8_up", "ir_op_conv_fp8_route", "ir_fp8_features", "ir_op_attention_fp8", "ir_op_attention_d512_fp8",
     "ir_unet_configure", "ir_unet_set_context", "ir_cldm_sample", "ir_cldm_pipeline", "ir_clip_text_configure", "ir_clip_text_encode", "ir_op_groupnorm_any", "ir_op_geglu",
-    "ir_dit_set_prompts", "ir_op_attention_kv_groups", "ir_graph_records",
+    "ir_dit_set_prompts", "ir_op_attention_kv_groups", "ir_graph_records", "ir_op_vae_segment", "ir_op_vae_segment_ws", "ir_op_vae_segment_info",
 ]
 
 STAGE_SWINIR, STAGE_VAE_ENCODE, STAGE_DIT, STAGE_VAE_DECODE, STAGE_PIPELINE, STAGE_COLORFIX, STAGE_T5, STAGE_CLDM, STAGE_CLDM_PIPELINE, STAGE_CLIP_TEXT = range(10)
@@ -141,6 +141,10 @@ def load_library():
     lib.ir_op_attention_kv_groups.argtypes = [vp, vp, vp, vp, vp, vp, i, i, i, i, i, f, vp, i, vp, sz]
     lib.ir_graph_records.argtypes = [vp]
     lib.ir_graph_records.restype = C.c_ulong
+    lib.ir_op_vae_segment.argtypes = [vp, vp, i, i, i, vp, vp, i, i, i, vp, sz]
+    lib.ir_op_vae_segment_ws.argtypes = [vp, i, i, i, i, i, i]
+    lib.ir_op_vae_segment_ws.restype = sz
+    lib.ir_op_vae_segment_info.argtypes = [vp, i, i, i, i, C.c_char_p, i, C.POINTER(i), C.POINTER(i), C.POINTER(i), C.POINTER(i)]
     for name in SYMBOLS:
         fn = getattr(lib, name)
         if fn.restype is C.c_int and name not in ("ir_abi_version",):

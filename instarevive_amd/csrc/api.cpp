@@ -341,7 +341,8 @@ struct Run {
     const char* where = "";
     // Fused GroupNorm statistics: a caller that knows a GroupNorm consumes the next conv's output sets gn_buf (and gn_want);
     // conv() then asks the epilogue for per-group partial sums and groupnorm() skips its own statistics pass when its input
-    // is the tensor the pending partials describe.
+    // is the tensor the pending partials describe. The hand-over rules (who sets gn_want, who consumes gn_x, what the first step of a
+    // segment does) stand above vae_steps(); tests/test_vae_segment_gpu.py pins them at the product's shapes.
     float* gn_buf = nullptr;
     bool gn_want = false;
     const void* gn_x = nullptr;
@@ -884,6 +885,91 @@ long gn_fused_floats(int h, int w) {
     return (halo > gemm ? halo : gemm) * 64;
 }
 
+// The interior of a VAE half as a list of steps in production order (everything between conv_in and norm_out):
+//   encoder  down0.res0, down0.res1, down0.ds, ... , down3.res1, mid.res0, mid.attn, mid.res1
+//   decoder  mid.res0, mid.attn, mid.res1, up3.res0, up3.res1, up3.res2, up3.us, up2.res0, ... , up0.res2
+// vae_encode_run, vae_decode_run and ir_op_vae_segment all walk this table through vae_step_run, so a step sees the same Run state
+// (gn_after, the fp8 bit of its level, gn_want in front of a resample conv) whoever runs it.
+//
+// Hand-over of fused GroupNorm statistics between steps (Run::gn_want / gn_x / gn_chunks / gn_buf):
+//  * gn_want is set by the CODE IN FRONT of a conv whose output a GroupNorm reads next: resblock() in front of conv1 (norm2 follows) and in
+//    front of conv2 when gn_after, vae_step_run in front of a resample conv, the stage functions in front of conv_in. conv() / conv_fp8()
+//    clear it with every launch, so the shortcut linear and the attention's projections never carry statistics.
+//  * a conv that was asked and whose kernel can (ir_igemm_gn_chunks > 0) writes per-tile partial sums of its STORED output (bias and residual
+//    included, rounded to bf16) to gn_buf and leaves gn_x = its output pointer, gn_chunks = tiles per image.
+//  * gn_x is consumed (and cleared) by the first groupnorm() / norm_conv_fused() after it - or norm_out's fused form in vae_decode_run - and only
+//    if that call's input IS gn_x; any other groupnorm() clears it and takes the stand-alone statistics pass. gn_chunks is never cleared:
+//    it is stale whenever gn_x is null.
+//  * the first step of a run has gn_x == nullptr unless the stage's conv_in produced statistics: the first step of an ir_op_vae_segment call
+//    therefore always takes the stand-alone pass (its input came from the caller).
+enum { VS_RES = 0, VS_ATTN = 1, VS_DOWN = 2, VS_UP = 3 };
+struct VaeStep {
+    int kind = VS_RES;
+    const ResW* res = nullptr;
+    const AttnW* attn = nullptr;
+    const Conv* rs = nullptr;
+    bool gn_after = false;
+    int f8bit = 31;
+    int level = -1, idx = 0;   // level -1: the mid block
+    int cin = 0, cout = 0;
+};
+std::vector<VaeStep> vae_steps(const VaeHalf& m, bool decoder) {
+    std::vector<VaeStep> v;
+    const int nl = (int)m.levels.size();
+    auto res = [&](const ResW& w, bool gn_after, int f8bit, int level, int idx) {
+        VaeStep s;
+        s.kind = VS_RES; s.res = &w; s.gn_after = gn_after; s.f8bit = f8bit; s.level = level; s.idx = idx; s.cin = w.c1.cin; s.cout = w.c1.cout;
+        v.push_back(s);
+    };
+    auto mid = [&]() {
+        res(m.mid1, true, decoder ? IR_FP8_BIT_DEC_MID : IR_FP8_BIT_ENC_MID, -1, 0);
+        VaeStep s;
+        s.kind = VS_ATTN; s.attn = &m.attn; s.f8bit = decoder ? IR_FP8_BIT_DEC_ATTN : IR_FP8_BIT_ENC_ATTN; s.cin = s.cout = m.attn.n.c;
+        v.push_back(s);
+        res(m.mid2, true, decoder ? IR_FP8_BIT_DEC_MID : IR_FP8_BIT_ENC_MID, -1, 1);
+    };
+    auto level = [&](int l) {
+        const VaeLevel& lv = m.levels[l];
+        const size_t nres = lv.res.size();
+        for (size_t i = 0; i < nres; ++i)
+            res(lv.res[i], i + 1 < nres || !lv.has_resample, (decoder ? IR_FP8_BIT_DEC_LEVEL0 : IR_FP8_BIT_ENC_LEVEL0) + (l < 4 ? l : 3), l, (int)i);
+        if (lv.has_resample) {
+            VaeStep s;
+            s.kind = decoder ? VS_UP : VS_DOWN; s.rs = &lv.resample; s.level = l; s.cin = lv.resample.cin; s.cout = lv.resample.cout;
+            v.push_back(s);
+        }
+    };
+    if (decoder) {
+        mid();
+        for (int l = nl - 1; l >= 0; --l) level(l);
+    } else {
+        for (int l = 0; l < nl; ++l) level(l);
+        mid();
+    }
+    return v;
+}
+void vae_step_name(const VaeStep& s, bool decoder, char* buf, size_t cap) {
+    if (s.kind == VS_ATTN) snprintf(buf, cap, "mid.attn");
+    else if (s.kind == VS_RES && s.level < 0) snprintf(buf, cap, "mid.res%d", s.idx);
+    else if (s.kind == VS_RES) snprintf(buf, cap, "%s%d.res%d", decoder ? "up" : "down", s.level, s.idx);
+    else snprintf(buf, cap, "%s%d.%s", decoder ? "up" : "down", s.level, decoder ? "us" : "ds");
+}
+// One step on the three rotating buffers: returns the index holding the result (-1: a sharded attention stopped behind part 0), updates H / W.
+int vae_step_run(Run& r, const VaeStep& s, bf16_t* B[3], int ci, float* gws, int n, int& H, int& W, const AttnShard* sh = nullptr) {
+    if (s.kind == VS_RES) return resblock(r, *s.res, B, ci, gws, n, H, W, s.gn_after, s.f8bit);
+    if (s.kind == VS_ATTN) return attnblock(r, *s.attn, B, ci, gws, n, H, W, sh, s.f8bit);
+    const int t1 = (ci + 1) % 3;
+    r.gn_want = true;
+    if (s.kind == VS_DOWN) {   // Downsample: pad (0,1,0,1) + stride-2 conv (model.py:82-86)
+        conv(r, *s.rs, B[ci], n, H, W, s.rs->cin, B[t1], s.rs->cout, 0, 2, 0, 0, ACT_NONE, 0.f, nullptr, 0, 0);
+        H /= 2; W /= 2;
+    } else {                   // Upsample: nearest x2 folded into the conv's addressing (model.py:63-67)
+        conv(r, *s.rs, B[ci], n, H, W, s.rs->cin, B[t1], s.rs->cout, 0, 1, 1, 1, ACT_NONE, 0.f, nullptr, 0, 0);
+        H *= 2; W *= 2;
+    }
+    return t1;
+}
+
 // Encoder.forward (model.py:521-546) + quant_conv + mode() (autoencoder.py:82-86). in: fp32 NCHW, v*in_scale+in_shift first.
 void vae_encode_run(Run& r, const float* in, float* lat, int n, int h, int w, float in_scale, float in_shift, float lat_scale, const AttnShard* sh = nullptr) {
     const VaeHalf& m = r.c->vae.enc;
@@ -897,12 +983,12 @@ void vae_encode_run(Run& r, const float* in, float* lat, int n, int h, int w, fl
     r.gn_buf = r.a.alloc<float>((long)n * gn_fused_floats(h, w));
     r.gn_x = nullptr;
     int ci = 0, H = h, W = w;
+    const std::vector<VaeStep> steps = vae_steps(m, false);
+    size_t first = 0;
     if (sh && sh->part == 1) {   // resume behind the exchanged attention rows: nothing in front of the block is needed again
         H = h >> (nl - 1); W = w >> (nl - 1);
-        ci = attnblock(r, m.attn, B, 0, gws, n, H, W, sh, IR_FP8_BIT_ENC_ATTN);
-        goto after_attention;
-    }
-    if (!r.c->plain && m.conv_in.cin == 32 && m.conv_in.cout == 128 && m.conv_in.cout_pad == 128) {
+        first = steps.size() - 2;   // mid.attn
+    } else if (!r.c->plain && m.conv_in.cin == 32 && m.conv_in.cout == 128 && m.conv_in.cout_pad == 128) {
         // conv_in straight from the fp32 planes, with the statistics of norm1 of the first ResnetBlock (vae_io.hip)
         if (r.live()) {
             const double px = (double)n * h * w;
@@ -916,26 +1002,14 @@ void vae_encode_run(Run& r, const float* in, float* lat, int n, int h, int w, fl
         r.gn_want = true;
         conv(r, m.conv_in, in32, n, h, w, 32, B[0], m.conv_in.cout, 0, 1, 1, 0, ACT_NONE, 0.f, nullptr, 0, 0);
     }
-    for (int l = 0; l < nl; ++l) {
-        const size_t nres = m.levels[l].res.size();
-        for (size_t i = 0; i < nres; ++i) ci = resblock(r, m.levels[l].res[i], B, ci, gws, n, H, W, i + 1 < nres || !m.levels[l].has_resample, IR_FP8_BIT_ENC_LEVEL0 + (l < 4 ? l : 3));
-        if (m.levels[l].has_resample) {  // Downsample: pad (0,1,0,1) + stride-2 conv (model.py:82-86)
-            const int t1 = (ci + 1) % 3;
-            r.gn_want = true;
-            conv(r, m.levels[l].resample, B[ci], n, H, W, m.levels[l].resample.cin, B[t1], m.levels[l].resample.cout, 0, 2, 0, 0,
-                 ACT_NONE, 0.f, nullptr, 0, 0);
-            ci = t1; H /= 2; W /= 2;
+    for (size_t i = first; i < steps.size(); ++i) {
+        ci = vae_step_run(r, steps[i], B, ci, gws, n, H, W, steps[i].kind == VS_ATTN ? sh : nullptr);
+        if (ci < 0) {   // part 0 of a sharded encode: stopped behind this rank's attention rows
+            r.gn_buf = nullptr;
+            r.a.release(mk);
+            return;
         }
     }
-    ci = resblock(r, m.mid1, B, ci, gws, n, H, W, true, IR_FP8_BIT_ENC_MID);
-    ci = attnblock(r, m.attn, B, ci, gws, n, H, W, sh, IR_FP8_BIT_ENC_ATTN);
-    if (ci < 0) {   // part 0 of a sharded encode: stopped behind this rank's attention rows
-        r.gn_buf = nullptr;
-        r.a.release(mk);
-        return;
-    }
-after_attention:
-    ci = resblock(r, m.mid2, B, ci, gws, n, H, W, true, IR_FP8_BIT_ENC_MID);
     const int t1 = (ci + 1) % 3;
     groupnorm(r, m.norm_out, B[ci], B[t1], gws, n, (long)H * W, 1);
     r.gn_buf = nullptr;
@@ -962,20 +1036,7 @@ void vae_decode_run(Run& r, const float* lat, float in_scale, float* out_nhwc4, 
     r.gn_want = true;
     conv(r, m.conv_in, z32, n, h, w, 32, B[0], m.conv_in.cout, 0, 1, 1, 0, ACT_NONE, 0.f, nullptr, 0, 0);
     int ci = 0, H = h, W = w;
-    ci = resblock(r, m.mid1, B, ci, gws, n, H, W, true, IR_FP8_BIT_DEC_MID);
-    ci = attnblock(r, m.attn, B, ci, gws, n, H, W, nullptr, IR_FP8_BIT_DEC_ATTN);
-    ci = resblock(r, m.mid2, B, ci, gws, n, H, W, true, IR_FP8_BIT_DEC_MID);
-    for (int l = nl - 1; l >= 0; --l) {
-        const size_t nres = m.levels[l].res.size();
-        for (size_t i = 0; i < nres; ++i) ci = resblock(r, m.levels[l].res[i], B, ci, gws, n, H, W, i + 1 < nres || !m.levels[l].has_resample, IR_FP8_BIT_DEC_LEVEL0 + (l < 4 ? l : 3));
-        if (m.levels[l].has_resample) {  // Upsample: nearest x2 folded into the conv's addressing (model.py:63-67)
-            const int t1 = (ci + 1) % 3;
-            r.gn_want = true;
-            conv(r, m.levels[l].resample, B[ci], n, H, W, m.levels[l].resample.cin, B[t1], m.levels[l].resample.cout, 0, 1, 1, 1,
-                 ACT_NONE, 0.f, nullptr, 0, 0);
-            ci = t1; H *= 2; W *= 2;
-        }
-    }
+    for (const VaeStep& st : vae_steps(m, true)) ci = vae_step_run(r, st, B, ci, gws, n, H, W);
     const int t1 = (ci + 1) % 3;
     if (!r.c->plain && m.conv_out.cin == 128 && m.conv_out.cout_pad == 32 && r.gn_x == B[ci] && r.gn_chunks > 0) {
         // norm_out + SiLU + conv_out in one read of the tensor (vae_io.hip): the statistics come from the producing conv's epilogue, only the
@@ -2503,6 +2564,96 @@ int ir_vae_decode(ir_ctx* c, void* stream, const float* lat, float* out, int n, 
     float* o4 = r.a.alloc<float>((long)n * h * 8 * w * 8 * 4);
     vae_decode_run(r, lat, 1.f, o4, n, h, w);
     LAUNCH(r, PC_OTHER, 0.0, 0.0, ir_launch_nhwc_to_nchw(o4, 4, out, n, 3, (long)h * 8 * w * 8, 1.f, 0.f, 0, r.s), "dec_out");
+    return finish(r, c, ws_bytes);
+}
+
+// ---- a segment of the VAE chain for op-level tests (see the header)
+static const VaeHalf* segment_half(ir_ctx* c, int half) {
+    if (!c || (half != 0 && half != 1)) return nullptr;
+    const VaeHalf& m = half ? c->vae.dec : c->vae.enc;
+    return m.ok ? &m : nullptr;
+}
+// walks steps first .. first + count - 1 from an h x w input: 0 and the sizes, or the number of the first step that cannot take its input
+static int segment_walk(const std::vector<VaeStep>& st, int first, int count, int h, int w, int* oh, int* ow, long* max_px, int* max_c, int* max_h, int* max_w) {
+    long px = (long)h * w;
+    int cm = 0, mh = h, mw = w;
+    for (int i = first; i < first + count; ++i) {
+        cm = std::max(cm, std::max(st[i].cin, st[i].cout));
+        if (st[i].kind == VS_DOWN) {
+            if ((h & 1) || (w & 1)) return i + 1;
+            h /= 2; w /= 2;
+        } else if (st[i].kind == VS_UP) {
+            if (h > (1 << 14) || w > (1 << 14)) return i + 1;
+            h *= 2; w *= 2;
+        }
+        px = std::max(px, (long)h * w);
+        mh = std::max(mh, h); mw = std::max(mw, w);
+    }
+    *oh = h; *ow = w;
+    if (max_px) *max_px = px;
+    if (max_c) *max_c = cm;
+    if (max_h) *max_h = mh;
+    if (max_w) *max_w = mw;
+    return 0;
+}
+static int segment_run(ir_ctx* c, Run& r, int half, int first, int count, const uint16_t* x, uint16_t* y, int n, int h, int w) {
+    const VaeHalf* m = segment_half(c, half);
+    if (half != 0 && half != 1) return fail(c, -1, "ir_op_vae_segment: half %d (0 encoder, 1 decoder)", half);
+    if (!m) return fail(c, -11, "ir_op_vae_segment: that half of the VAE is not configured");
+    const std::vector<VaeStep> st = vae_steps(*m, half == 1);
+    if (first < 0 || count < 1 || first >= (int)st.size() || count > (int)st.size() - first)
+        return fail(c, -1, "ir_op_vae_segment: steps %d .. %d outside 0 .. %d", first, first + count - 1, (int)st.size() - 1);
+    if (n < 1 || h < 1 || w < 1 || h > (1 << 14) || w > (1 << 14)) return fail(c, -10, "ir_op_vae_segment: bad size n=%d h=%d w=%d", n, h, w);
+    int oh, ow, max_c, max_h, max_w;
+    long max_px;
+    if (const int bad = segment_walk(st, first, count, h, w, &oh, &ow, &max_px, &max_c, &max_h, &max_w))
+        return fail(c, -10, "ir_op_vae_segment: step %d cannot take its input size (a Downsample needs even sizes)", bad - 1);
+    const size_t mk = r.a.mark();
+    bf16_t* B[3];
+    for (int i = 0; i < 3; ++i) B[i] = r.a.alloc<bf16_t>((long)n * max_px * max_c);
+    float* gws = r.a.alloc<float>(ir_gn_ws_floats(n, (long)max_h * max_w, 512));
+    r.gn_buf = r.a.alloc<float>((long)n * gn_fused_floats(max_h, max_w));
+    r.gn_x = nullptr;   // the input came from the caller: the first step takes the stand-alone statistics pass
+    if (r.live()) r.chk(hipMemcpyAsync(B[0], x, (size_t)n * h * w * st[first].cin * 2, hipMemcpyDeviceToDevice, r.s) == hipSuccess ? 0 : -1, "segment input");
+    int ci = 0, H = h, W = w;
+    for (int i = first; i < first + count; ++i) ci = vae_step_run(r, st[i], B, ci, gws, n, H, W);
+    if (r.live()) r.chk(hipMemcpyAsync(y, B[ci], (size_t)n * H * W * st[first + count - 1].cout * 2, hipMemcpyDeviceToDevice, r.s) == hipSuccess ? 0 : -1, "segment output");
+    r.chain = nullptr;
+    r.gn_buf = nullptr;
+    r.a.release(mk);
+    return 0;
+}
+
+int ir_op_vae_segment_info(ir_ctx* c, int half, int step, int h, int w, char* name, int name_cap, int* cin, int* cout, int* oh, int* ow) {
+    if (half != 0 && half != 1) return fail(c, -1, "ir_op_vae_segment_info: half %d (0 encoder, 1 decoder)", half);
+    const VaeHalf* m = segment_half(c, half);
+    if (!m) return fail(c, -11, "ir_op_vae_segment_info: that half of the VAE is not configured");
+    const std::vector<VaeStep> st = vae_steps(*m, half == 1);
+    if (step < 0) return (int)st.size();
+    if (step >= (int)st.size()) return fail(c, -1, "ir_op_vae_segment_info: step %d outside 0 .. %d", step, (int)st.size() - 1);
+    if (name && name_cap > 0) vae_step_name(st[step], half == 1, name, (size_t)name_cap);
+    if (cin) *cin = st[step].cin;
+    if (cout) *cout = st[step].cout;
+    int ho = 0, wo = 0;
+    if (h > 0 && w > 0 && h <= (1 << 14) && w <= (1 << 14) && segment_walk(st, step, 1, h, w, &ho, &wo, nullptr, nullptr, nullptr, nullptr)) ho = wo = 0;
+    if (oh) *oh = ho;
+    if (ow) *ow = wo;
+    return (int)st.size();
+}
+
+size_t ir_op_vae_segment_ws(ir_ctx* c, int half, int first, int count, int n, int h, int w) {
+    if (!c) return 0;
+    Run r = make_run(c, nullptr, nullptr, 0, true);
+    if (segment_run(c, r, half, first, count, nullptr, nullptr, n, h, w)) return 0;
+    return r.a.peak + 4096;
+}
+
+int ir_op_vae_segment(ir_ctx* c, void* stream, int half, int first, int count, const uint16_t* x, uint16_t* y, int n, int h, int w, void* ws,
+                      size_t ws_bytes) {
+    if (!c) return -11;
+    if (!x || !y) return fail(c, -1, "ir_op_vae_segment: no input or output tensor");
+    Run r = make_run(c, stream, ws, ws_bytes, false);
+    if (int e = segment_run(c, r, half, first, count, x, y, n, h, w)) return e;
     return finish(r, c, ws_bytes);
 }
 

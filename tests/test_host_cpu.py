@@ -140,6 +140,18 @@ def test_dit_block_entry_refuses_a_missing_context():
     assert lib.ir_op_dit_block(None, None, None, 0, 1, 4, 4, 400.0, None, 0) == -11
 
 
+def test_vae_segment_entries_refuse_a_missing_context():
+    """ir_op_vae_segment and its query forms return -11 / a zero size (no configured VAE) before anything touches a device; a bad half is -1."""
+    from instarevive_amd import _lib
+    from instarevive_amd.build import build
+    build()
+    lib = _lib.load_library()
+    assert lib.ir_op_vae_segment(None, None, 1, 0, 1, None, None, 1, 8, 8, None, 0) == -11
+    assert lib.ir_op_vae_segment_info(None, 1, -1, 0, 0, None, 0, None, None, None, None) == -11
+    assert lib.ir_op_vae_segment_info(None, 2, -1, 0, 0, None, 0, None, None, None, None) == -1
+    assert lib.ir_op_vae_segment_ws(None, 1, 0, 1, 1, 8, 8) == 0
+
+
 def test_sliding_windows_and_loaders():
     from instarevive_amd.pipeline import _sliding_windows
     from instarevive_amd import utils
