@@ -42,6 +42,8 @@ def parse_args():
     ap.add_argument("--caption_dir", default=None, help="per-image prompts: DIR/<input-relative path without extension>.npz, else DIR/<file stem>.npz "
                     "(caption_feature [1, T, 4096], optional attention_mask; the reference's caption files). Images without one get --prompt_embeds")
     ap.add_argument("--device", default="cuda")
+    ap.add_argument("--png_encoder", default="host", choices=["host", "gpu"], help="who compresses the PNGs of both output folders: the host (PIL, default) or "
+                    "the GPU behind the network (inference.py --png_encoder: lossless, meant for photographs; flat content comes out larger than PIL's)")
     ap.add_argument("--workers", type=int, default=-1, help="host threads for decoding / PNG encoding (inference.py --workers)")
     return ap.parse_args()
 
@@ -83,10 +85,18 @@ def main():
 
     def save(dst, img):
         os.makedirs(os.path.dirname(dst) or ".", exist_ok=True)
-        Image.fromarray(np.ascontiguousarray(img)).save(dst)
+        if isinstance(img, tuple):   # encoded on the GPU: (zlib stream, width, height), framed here on the writer thread
+            from instarevive_amd.png import wrap_png
+            with open(dst, "wb") as f:
+                f.write(wrap_png(*img))
+        else:
+            Image.fromarray(np.ascontiguousarray(img)).save(dst)
+
+    gpu_png = args.png_encoder == "gpu"   # every image is a whole image_size crop: nothing to un-pad, every file is eligible
 
     results = process_stream(m.model, feed(), "none", args.disable_preprocess_model, False, 512, 448, preprocess_model=m.preprocess_model, vae=m.vae,
-                             y=m.y, y_mask=m.y_mask, noise_scheduler=m.noise_scheduler, return_stage1=True)
+                             y=m.y, y_mask=m.y_mask, noise_scheduler=m.noise_scheduler, return_stage1=True,
+                             png=[[(args.image_size, args.image_size)] * len(group) for group in batches] if gpu_png else None, png_wrap=False)
     for group, (preds, stage1) in zip(batches, results):
         for f, pred, cond in zip(group, preds, stage1):
             for folder, img in ((args.output, pred), (cond_dir, cond)):
@@ -94,6 +104,8 @@ def main():
         print(f"[rank {rank}] queued {len(group)} images ({group[0]} ...)")
     pools.drain()
     print(f"[rank {rank}] saved {pools.written} files")
+    if gpu_png:
+        print(f"[rank {rank}] --png_encoder gpu: 0 of {pools.written} files took the host encoder")
 
 
 if __name__ == "__main__":

@@ -25,7 +25,8 @@ typedef struct ir_ctx ir_ctx;
 enum { IR_STAGE_SWINIR = 0, IR_STAGE_VAE_ENCODE = 1, IR_STAGE_DIT = 2, IR_STAGE_VAE_DECODE = 3, IR_STAGE_PIPELINE = 4,
        IR_STAGE_COLORFIX = 5, IR_STAGE_T5 = 6 /* ir_workspace_bytes(ctx, IR_STAGE_T5, batch, tokens, 0, ...) */,
        IR_STAGE_CLDM = 7 /* ir_cldm_sample: n, h, w = the LATENT size */, IR_STAGE_CLDM_PIPELINE = 8 /* ir_cldm_pipeline: image size */,
-       IR_STAGE_CLIP_TEXT = 9 /* ir_clip_text_encode: n = batch */ };
+       IR_STAGE_CLIP_TEXT = 9 /* ir_clip_text_encode: n = batch */,
+       IR_STAGE_PNG = 10 /* ir_png_encode: n images, h, w = the VALID rectangle vh, vw; depends on the sizes alone (ctx may be NULL) */ };
 /* ir_pipeline flags */
 enum { IR_FLAG_NO_PREPROCESS = 1, IR_FLAG_TILED = 2, IR_FLAG_FIX_WAVELET = 4, IR_FLAG_FIX_ADAIN = 8,
        /* ir_pipeline only, needs ir_dit_control_configure: run the DiT step with the ControlNet-Half branch, condition latent
@@ -259,6 +260,21 @@ int ir_profile_end_kernels(ir_ctx* ctx, void* stream, int n_kernels, double* ms,
 /* image <-> tensor helpers of process() (inference.py:92-93,159-161) */
 int ir_u8_to_nchw(ir_ctx* ctx, void* stream, const uint8_t* in, float* out, int n, int h, int w);
 int ir_nchw_to_u8(ir_ctx* ctx, void* stream, const float* in, uint8_t* out, int n, int h, int w);
+
+/* Lossless PNG encoding of results on the device (no reference counterpart: the reference saves through PIL, inference.py:346). Encodes the
+ * valid rectangle vh x vw (1 <= vh <= h, 1 <= vw <= w: the un-padding of the command line) of n RGB8 images img [n][h][pitch] (pitch >= 3 w bytes
+ * per row) into one complete zlib stream per image at out + i * out_stride: header, deflate blocks, Adler-32 - what a PNG's IDAT chunks carry;
+ * the host adds signature, IHDR, IDAT framing with its CRC and IEND (instarevive_amd.png.wrap_png). info[i] = the stream's byte count.
+ * Format: every row Paeth-filtered; the filtered bytes cut into chunks of whole rows, each ONE dynamic-Huffman block of literals and the
+ * end-of-block symbol (no matches, so a byte never costs less than one bit: meant for photographs, flat content grows), code lengths
+ * limited to 15; every chunk but the last closed by an empty stored block so that chunks start on byte boundaries.
+ * ir_png_bound(h, w): capacity that holds the stream of ANY h x w pixels (9 bits per filtered byte + the per-chunk overhead); out_stride must be
+ * at least ir_png_bound(vh, vw). Bytes of a slot behind the stream's end are not written. All pointers are device pointers; stream-ordered, no
+ * allocation, no host synchronisation (capturable). ws: 16-byte aligned, ir_workspace_bytes(ctx, IR_STAGE_PNG, n, vh, vw, 0, 0, 0) bytes.
+ * Returns -1 (nothing launched) for a null pointer, a rectangle outside 1..h / 1..w, an out_stride below the bound or a short workspace. */
+size_t ir_png_bound(int h, int w);
+int ir_png_encode(ir_ctx* ctx, void* stream, const uint8_t* img, int n, int h, int w, long pitch, int vh, int vw, uint8_t* out, size_t out_stride,
+                  uint32_t* info, void* ws, size_t ws_bytes);
 
 /* Single-kernel entry points, exported so tests/ can check every kernel against the oracle through the same ABI. */
 int ir_op_conv(ir_ctx* ctx, void* stream, const uint16_t* in, const uint16_t* wgt, const float* bias, void* out, int n, int h, int w,

@@ -83,6 +83,12 @@ def parse_args() -> Namespace:
     parser.add_argument("--png_compress_level", type=int, default=None, choices=range(0, 10), metavar="0..9", help="zlib level of the saved PNGs; default: PIL's own "
                         "(6, what the reference writes). The pixels are the same at every level; 1 costs about a third of the encoder time - for ranks whose CPU share "
                         "cannot keep up with the GPU (the CLI says so at start-up)")
+    parser.add_argument("--png_encoder", type=str, default="host", choices=["host", "gpu"], help="who compresses the saved PNGs. host (default): PIL / zlib on the "
+                        "writer threads, as the reference does. gpu: the device encodes the result behind the network (Paeth filter + Huffman coding of literals, no "
+                        "LZ77 matches; lossless, the same pixels) and only the compressed bytes cross PCIe - for restored PHOTOGRAPHS, where its files are 10 - 18 %% "
+                        "smaller than --png_compress_level 1 and within a few percent of the default level; flat or near-flat content (smooth sky, graphics) comes "
+                        "out several times larger than PIL's, since a byte never costs less than one bit. Files that are not a plain crop of the prediction "
+                        "(--show_lq, inputs that auto_resize enlarged) still take the host encoder; the run says how many")
     parser.add_argument("--workers", type=int, default=-1, help="host threads that decode / resize the inputs and resize / PNG-encode the results "
                         "around the GPU (PIL releases the GIL there); -1 = this process's CPU share, 0 = everything on the main thread like the reference")
     return parser.parse_args()
@@ -115,7 +121,9 @@ def default_workers(local_world: int = 1) -> int:
     """Host threads for this rank: its part of the CPU share, less the cores kept for the thread that feeds the GPU and the copy engine's callbacks
     (two; one when the rank's part is 8 cores or fewer - 8 ranks on a 64-core host - where the feeding thread, asleep in stream waits most of the time,
     shares a core with an encoder rather than take a quarter of the rank's budget), at most 16 (one MI355X produces ~8 results of 2048 x 2048 a second and
-    a PNG of that size costs 0.8 - 1.7 core-seconds; $IR_WORKERS overrides)."""
+    a PNG of that size costs 0.8 - 1.7 core-seconds on the host encoder, which is what this count is sized for; under --png_encoder gpu a file costs the host about
+    0.03 core-seconds, paid on the writer threads (the feeding thread only copies the compressed bytes out of the pinned buffer), and two or three threads would do - the count is not lowered for it, since files that are not plain crops still take the host encoder;
+    $IR_WORKERS overrides)."""
     if os.environ.get("IR_WORKERS"):
         return max(0, int(os.environ["IR_WORKERS"]))
     part = cpu_share() // max(local_world, 1)
@@ -123,22 +131,27 @@ def default_workers(local_world: int = 1) -> int:
 
 
 PNG_CORE_SECONDS_2048 = 1.25   # PIL's default encoder (compress_level 6) on one 2048 x 2048 RGB result: 0.8 - 1.7 core-seconds by content (profiles/r05_cli_rate_ab.txt)
+PNG_GPU_HOST_CORE_SECONDS_2048 = 0.03   # --png_encoder gpu: what is left to the host per 2048 x 2048 result - one CRC-32 over ~8 MB of compressed bytes (10 ms), the copies into the file's bytes and the write
 GPU_FILES_PER_SECOND_2048 = 8.4   # what one MI355X delivers at 2048 x 2048 (bench.py `value`)
 
 
-def host_keeps_up(workers: int, out_pixels: int, compress_level) -> str:
+def host_keeps_up(workers: int, out_pixels: int, compress_level, encoder: str = "host") -> str:
     """'' when `workers` encoder threads keep ahead of one GPU for results of out_pixels pixels, else the sentence the CLI prints: the rank is then
     host-bound (8 ranks on a 64-core host: 7 threads encode ~5.6 files/s of 2048 x 2048 at PIL's default level against ~8.4 from the GPU). The estimate
-    scales the measured level-6 cost by the pixel count; level 1 costs about a third of it (larger files, the same pixels)."""
+    scales the measured level-6 cost by the pixel count; level 1 costs about a third of it (larger files, the same pixels). encoder = "gpu" prices a
+    file at the host's share of the device encoder (PNG_GPU_HOST_CORE_SECONDS_2048), for runs whose files are plain crops of the prediction."""
     if workers <= 0 or out_pixels <= 0:
         return ""
     scale = out_pixels / float(2048 * 2048)
     cost = PNG_CORE_SECONDS_2048 * scale * (1.0 if compress_level is None or compress_level >= 6 else (0.35 if compress_level <= 1 else 0.6))
+    if encoder == "gpu":
+        cost = PNG_GPU_HOST_CORE_SECONDS_2048 * scale
     host_rate, gpu_rate = workers / cost, GPU_FILES_PER_SECOND_2048 / scale
     if host_rate >= gpu_rate:
         return ""
     return (f"host-bound: {workers} encoder threads write ~{host_rate:.1f} files/s of {out_pixels / 1e6:.1f} Mpixel against ~{gpu_rate:.1f} from the GPU - give the rank more "
-            f"cores (--workers / $IR_WORKERS), or trade file size for speed with --png_compress_level 1 (same pixels, lossless)")
+            f"cores (--workers / $IR_WORKERS), or trade file size for speed with --png_compress_level 1 (same pixels, lossless)"
+            + ("" if encoder == "gpu" else ", or encode photographs on the GPU with --png_encoder gpu"))
 
 
 def check_device(device: str) -> str:
@@ -178,6 +191,30 @@ def read_job(file_path: str, repeat: int, args: Namespace) -> Job:
     valid = () if args.use_center_crop else (fitted.height, fitted.width)
     folder, stem, _ = get_file_name_parts(os.path.join(args.output, os.path.relpath(file_path, args.input)))
     return Job(os.path.join(folder, f"{stem}_{repeat}.png"), lq, net_in, valid, file_path)
+
+
+def png_rect(job: Job, args: Namespace):
+    """The rectangle (vh, vw) of the prediction that write_job() would save unchanged, or None when the saved file is anything else. It is a plain
+    crop when there is no --show_lq strip and the resize back to the LQ size is the identity: nothing to un-pad (--use_center_crop), or an LQ image
+    that auto_resize left at its size (PIL's resize to the same size copies). Such jobs can be encoded on the GPU (--png_encoder gpu)."""
+    if getattr(args, "show_lq", False):
+        return None
+    if not job.valid_hw:
+        return tuple(job.net_in.shape[:2])
+    vh, vw = job.valid_hw
+    return (vh, vw) if job.lq.size == (vw, vh) else None
+
+
+def write_png_file(job: Job, blob) -> None:
+    """write_job() for a result the GPU has encoded already: a PNG file, or the (zlib stream, width, height) triple process_stream(png_wrap=False)
+    yields, framed here - on a writer thread - into one."""
+    if not isinstance(blob, bytes):
+        from instarevive_amd.png import wrap_png
+        blob = wrap_png(*blob)
+    os.makedirs(os.path.dirname(job.save_path) or ".", exist_ok=True)
+    with open(job.save_path, "wb") as f:
+        f.write(blob)
+    print(f"save to {job.save_path}")
 
 
 def write_job(job: Job, pred: np.ndarray, stage1_pred, args: Namespace) -> None:
@@ -261,11 +298,12 @@ class HostPools:
                 pool.shutdown(wait=True)
 
 
-def batches_of(jobs: Iterable[Job], limit: int) -> Iterator[List[Job]]:
-    """Consecutive jobs of equal network-input shape, at most `limit` per batch (limit 1 = the reference's one image per call)."""
+def batches_of(jobs: Iterable[Job], limit: int, key: Callable = None) -> Iterator[List[Job]]:
+    """Consecutive jobs of equal network-input shape, at most `limit` per batch (limit 1 = the reference's one image per call). With `key`, jobs
+    whose key(job) differs do not share a batch either (--png_encoder gpu: a batch is encoded on the GPU as a whole or not at all)."""
     group: List[Job] = []
     for job in jobs:
-        if group and (len(group) >= limit or job.net_in.shape != group[0].net_in.shape):
+        if group and (len(group) >= limit or job.net_in.shape != group[0].net_in.shape or (key is not None and key(job) != key(group[0]))):
             yield group
             group = []
         group.append(job)
@@ -326,7 +364,8 @@ def main() -> None:
         import sys
         sys.setswitchinterval(float(os.environ["IR_SWITCH_INTERVAL"]))
     pools = HostPools(default_workers(local_world) if args.workers < 0 else args.workers)
-    note = host_keeps_up(pools.workers, int(512 * 512 * max(args.sr_scale, 1.0) ** 2), args.png_compress_level)   # priced on a 512 x 512 LQ file at this --sr_scale
+    gpu_png = args.png_encoder == "gpu"
+    note = host_keeps_up(pools.workers, int(512 * 512 * max(args.sr_scale, 1.0) ** 2), args.png_compress_level, args.png_encoder)   # priced on a 512 x 512 LQ file at this --sr_scale
     if note:
         print(f"[rank {rank}] {note}")
     if not os.path.isdir(args.input):
@@ -344,6 +383,7 @@ def main() -> None:
     if args.caption_dir:
         from instarevive_amd.prompts import Captions
         caps = Captions(args.caption_dir, m.y, m.y_mask, args.input)
+    host_files = 0   # --png_encoder gpu: files that were not a plain crop of the prediction and went through PIL
     if args.shard_tiles and args.tiled and world > 1:
         # one large image at a time, its tiles spread over the GPUs; rank 0 re-assembles and writes
         engine = HipTileEngine(m.model, m.vae, m.preprocess_model, m.y, m.y_mask, args.color_fix_type, args.disable_preprocess_model,
@@ -351,33 +391,54 @@ def main() -> None:
         for job in pools.read_ahead(lambda pi: read_job(pi[0], pi[1], args), [(p, i) for p in files for i in range(args.repeat_times)]):
             if caps:
                 engine.y, engine.y_mask = caps.batch([job.src])
-            preds, stage1 = parallel.sharded_tiled_process(engine, [job.net_in], rank, world)
+            rect = png_rect(job, args) if gpu_png else None
+            preds, stage1 = parallel.sharded_tiled_process(engine, [job.net_in], rank, world, png=[rect] if rect else None)
             if rank == 0:
-                pools.write_behind(write_job, job, preds[0], stage1[0], args)
+                host_files += rect is None
+                if rect:   # rank 0 has encoded the assembled frame
+                    pools.write_behind(write_png_file, job, preds[0])
+                else:
+                    pools.write_behind(write_job, job, preds[0], stage1[0], args)
         pools.drain()
+        if gpu_png and rank == 0:
+            print(f"[rank {rank}] --png_encoder gpu: {host_files} of {pools.written} files took the host encoder (not a plain crop of the prediction)")
         return
     mine = parallel.shard(files, rank, world)       # images are independent: no collective on the data path
     t0 = time.perf_counter()
     jobs = pools.read_ahead(lambda pi: read_job(pi[0], pi[1], args), [(p, i) for p in mine for i in range(args.repeat_times)])
     todo: List[List[Job]] = []
+    rects = deque()   # --png_encoder gpu, per batch drawn by process_stream: its rectangles, or None for a batch of the host encoder
 
     def feed():
-        for group in batches_of(jobs, max(args.batch_size, 1)):
+        for group in batches_of(jobs, max(args.batch_size, 1), (lambda j: png_rect(j, args) is not None) if gpu_png else None):
             todo.append(group)
+            if gpu_png:
+                rr = [png_rect(j, args) for j in group]
+                rects.append(rr if all(rr) else None)
             imgs = [j.net_in for j in group]
             yield (imgs, *caps.batch([j.src for j in group])) if caps else imgs
 
+    def batch_rects():   # in step with feed(): process_stream advances it right after it has drawn a batch
+        while True:
+            yield rects.popleft()
+
     first = None    # (time, files) when the first result left the GPU: what follows is the steady state (no library / workspace warm-up in it)
     for preds, stage1 in process_stream(m.model, feed(), tiled=args.tiled, return_stage1=args.show_lq and not args.disable_preprocess_model,
-                                        fp8=args.fp8 != "off", **common):
+                                        fp8=args.fp8 != "off", png=batch_rects() if gpu_png else None, png_wrap=False, **common):
         group = todo.pop(0)
         last_result = time.perf_counter()
         if first is None:
             first = (last_result, len(group))
         for k, job in enumerate(group):
-            pools.write_behind(write_job, job, preds[k], stage1[k] if stage1 else None, args)
+            if isinstance(preds[k], tuple):   # encoded on the GPU; the writer thread frames it
+                pools.write_behind(write_png_file, job, preds[k])
+            else:
+                host_files += gpu_png
+                pools.write_behind(write_job, job, preds[k], stage1[k] if stage1 else None, args)
     pools.drain()
     t1 = time.perf_counter()
+    if gpu_png:
+        print(f"[rank {rank}] --png_encoder gpu: {host_files} of {pools.written} files took the host encoder (not a plain crop of the prediction)")
     if pools.written:
         # first read submitted -> last PNG closed, model loading excluded (bench.py --cli_files parses this line)
         rest, dt_rest = pools.written - first[1], t1 - first[0]

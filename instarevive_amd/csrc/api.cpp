@@ -2465,7 +2465,54 @@ static int stage_dispatch(ir_ctx* c, Run& r, int stage, int n, int h, int w, int
     return 0;
 }
 
+// ---------------------------------------------------------------- PNG encoding (png_encode.hip)
+// Bytes of one chunk of `rows` rows at most: the 1106-bit block header, at most 9 bits per filtered byte and for the end-of-block symbol (the
+// coder never exceeds the fixed 8 / 9-bit code, see png_codes_kernel), 3 bits of the empty stored block's header, the pad to the byte and its
+// four LEN / NLEN bytes.
+static size_t png_chunk_bound(size_t rows, size_t rowlen) { return (IR_PNG_HEADER_BITS + 9 * (rows * rowlen + 1) + 3 + 7) / 8 + 4; }
+struct PngLayout {
+    size_t chunks, slot_cap, hist, codes, header, sizes, slots, total;
+};
+static PngLayout png_layout(int n, int vh, int vw) {
+    PngLayout L;
+    L.chunks = ((size_t)vh + IR_PNG_ROWS - 1) / IR_PNG_ROWS;
+    // a slot is stored in whole 16-byte units and the compaction reads one dword beyond the chunk's last
+    L.slot_cap = ((png_chunk_bound(IR_PNG_ROWS, 3 * (size_t)vw + 1) + 15) & ~(size_t)15) + 16;
+    const size_t k = (size_t)n * L.chunks;
+    auto up = [](size_t b) { return (b + 255) & ~(size_t)255; };
+    L.hist = 0;
+    L.codes = L.hist + up(k * 260 * 4);
+    L.header = L.codes + up(k * 260 * 4);
+    L.sizes = L.header + up(k * 40 * 4);
+    L.slots = L.sizes + up(k * 4);
+    L.total = L.slots + up(k * L.slot_cap);
+    return L;
+}
+// 2 header bytes + the chunks + 4 bytes of Adler-32. With D = h * (3 w + 1) filtered bytes in ceil(h / IR_PNG_ROWS) chunks the chunk bounds sum
+// to at most ceil(9 D / 8) + chunks * (ceil((1106 + 9 + 3 + 7) / 8) + 4 + 1) (the + 1: each chunk's own rounding of 9 * bytes / 8).
+size_t ir_png_bound(int h, int w) {
+    if (h < 1 || w < 1) return 0;
+    const size_t rowlen = 3 * (size_t)w + 1, chunks = ((size_t)h + IR_PNG_ROWS - 1) / IR_PNG_ROWS;
+    return 2 + (9 * (size_t)h * rowlen + 7) / 8 + chunks * ((IR_PNG_HEADER_BITS + 9 + 3 + 7 + 7) / 8 + 4 + 1) + 4;
+}
+int ir_png_encode(ir_ctx* c, void* stream, const uint8_t* img, int n, int h, int w, long pitch, int vh, int vw, uint8_t* out, size_t out_stride,
+                  uint32_t* info, void* ws, size_t ws_bytes) {
+    if (!c || !img || !out || !info || !ws) return fail(c, -1, "ir_png_encode: null argument");
+    if (n < 1 || h < 1 || w < 1 || vh < 1 || vh > h || vw < 1 || vw > w || pitch < 3L * w)
+        return fail(c, -1, "ir_png_encode: bad size (n %d, %d x %d, pitch %ld, valid %d x %d)", n, h, w, pitch, vh, vw);
+    if (out_stride < ir_png_bound(vh, vw)) return fail(c, -1, "ir_png_encode: out_stride %zu below ir_png_bound(%d, %d) = %zu", out_stride, vh, vw, ir_png_bound(vh, vw));
+    const PngLayout L = png_layout(n, vh, vw);
+    if (ws_bytes < L.total || (reinterpret_cast<uintptr_t>(ws) & 15)) return fail(c, -1, "ir_png_encode: workspace too small or unaligned (%zu < %zu)", ws_bytes, L.total);
+    use_ctx(c);
+    char* b = static_cast<char*>(ws);
+    if (ir_launch_png_encode(img, n, h, pitch, vh, vw, out, out_stride, info, (uint32_t*)(b + L.hist), (uint32_t*)(b + L.codes), (uint32_t*)(b + L.header),
+                             (uint32_t*)(b + L.sizes), (uint8_t*)(b + L.slots), (long)L.slot_cap, (hipStream_t)stream))
+        return fail(c, -100, "ir_png_encode: launch failed");
+    return 0;
+}
+
 size_t ir_workspace_bytes(ir_ctx* c, int stage, int n, int h, int w, int flags, int tile_size, int tile_stride) {
+    if (stage == IR_STAGE_PNG) return (n < 1 || h < 1 || w < 1) ? 0 : png_layout(n, h, w).total;   // a function of the sizes alone: no context needed
     if (!c) return 0;
     Run r = make_run(c, nullptr, nullptr, 0, true);
     if (stage_dispatch(c, r, stage, n, h, w, flags, tile_size, tile_stride)) return 0;

@@ -63,6 +63,38 @@ class _Staging:
         return ev
 
 
+def _png_encoder(ctx, count, h, w, slot=0, tag="sync"):
+    """The PngEncoder (png.py) of a batch shape and staging slot, kept on the context like the staging buffers. Each entry holds count x ir_png_bound
+    bytes on the device and as much page-locked host memory (about 14 MB per 2048 x 2048 image; twice the images with stage-1 output, two slots
+    under process_stream). At most 8 entries: the oldest is dropped whatever its use, which is safe because a batch in flight keeps its own
+    reference (process_stream's `pending`), and costs a re-allocation when more than 8 shapes alternate."""
+    from .png import PngEncoder
+    pool = ctx.__dict__.setdefault("_png", {})
+    key = (tag, count, h, w, slot)
+    if key not in pool:
+        if len(pool) >= 8:
+            pool.pop(next(iter(pool)))
+        pool[key] = PngEncoder(ctx, count, h, w)
+    return pool[key]
+
+
+def _queue_png(ctx, st, slot, n, h, w, rects, with_stage1, tag):
+    """ir_png_encode behind the ir_pipeline of this slot, on the current stream: the predictions into slots 0 .. n - 1 of the encoder, the stage-1
+    images (when asked for) into n .. 2n - 1."""
+    if len(rects) != n:
+        raise ValueError(f"png: {len(rects)} rectangles for a batch of {n} images")
+    enc = _png_encoder(ctx, 2 * n if with_stage1 else n, h, w, slot, tag)
+    enc.queue(0, st.d_out[slot], rects)
+    if with_stage1:
+        enc.queue(n, st.d_st1[slot], rects)
+    return enc
+
+
+def _png_workspace(ctx, n, h, w):
+    """Grow the context's workspace for the encoder BEFORE the pipeline's launch takes its address (a recorded graph is keyed by it)."""
+    ctx.workspace(ctx.ws_bytes(L.STAGE_PNG, n, h, w))
+
+
 def _check_images(control_imgs):
     if len(control_imgs) == 0:
         raise ValueError("control_imgs is empty")
@@ -183,7 +215,7 @@ def _launch_pipeline(ctx, st, slot, n, h, w, flags, tile_size, tile_stride, acp,
 @torch.no_grad()
 def process(model, control_imgs: List[np.ndarray], strength: float, color_fix_type: str, disable_preprocess_model: bool, tiled: bool,
             tile_size: int, tile_stride: int, preprocess_model=None, vae=None, y=None, y_mask=None, noise_scheduler=None,
-            fused: bool = True, graph: bool = False, return_stage1: bool = True, fp8: bool = False) -> Tuple[List[np.ndarray], List[np.ndarray]]:
+            fused: bool = True, graph: bool = False, return_stage1: bool = True, fp8: bool = False, png=None) -> Tuple[List[np.ndarray], List[np.ndarray]]:
     """test_scripts/inference.py:55-166. control_imgs: list of HWC uint8 RGB arrays of equal size (multiples of 64).
     Returns (preds, stage1_preds) as lists of HWC uint8 arrays (stage1_preds is empty with return_stage1=False, which skips its
     conversion and download).
@@ -193,9 +225,14 @@ def process(model, control_imgs: List[np.ndarray], strength: float, color_fix_ty
     graph=True (fused form only): the launch sequence is recorded into a hipGraph per image size / flag set and replayed on later
     calls. Images travel through page-locked staging buffers kept per batch shape (which also gives a recorded graph stable
     device addresses). fp8=True (fused form, BASELINE.json configs[4]): fp8 MFMA operands in the VAE resnet convolutions
-    (vae.enable_fp8() must have uploaded the fp8 weight forms)."""
+    (vae.enable_fp8() must have uploaded the fp8 weight forms).
+    png (fused form only): a list of one valid rectangle (vh, vw) per image. The results are then encoded on the GPU (ir_png_encode queued behind
+    ir_pipeline - under graph=True behind the graph's replay, not inside the recording) and both lists hold PNG files as `bytes` of the
+    top-left vh x vw crops instead of arrays; only the compressed bytes are downloaded."""
     noise_scheduler = noise_scheduler or DDPMScheduler()
     n, h, w = _check_images(control_imgs)
+    if png is not None and not (fused and _fused_ok(model, preprocess_model, vae, disable_preprocess_model)):
+        raise ValueError("process(png=...) needs the fused form (instarevive_amd models sharing one context)")
     device = model.device
     acp = float(noise_scheduler.alphas_cumprod[400])
     sf = float(vae.config.scaling_factor)
@@ -210,7 +247,15 @@ def process(model, control_imgs: List[np.ndarray], strength: float, color_fix_ty
         st = _Staging.get(ctx, n, h, w)
         st.fill(0, control_imgs)
         st.upload(0)
+        if png is not None:
+            _png_workspace(ctx, n, h, w)
         _launch_pipeline(ctx, st, 0, n, h, w, flags, tile_size, tile_stride, acp, sf, return_stage1)
+        if png is not None:
+            enc = _queue_png(ctx, st, 0, n, h, w, png, return_stage1, "sync")
+            enc.fetch_sizes()
+            torch.cuda.current_stream(device).synchronize()
+            files = enc.fetch(2 * n if return_stage1 else n)
+            return files[:n], files[n:]
         st.h_out[0].copy_(st.d_out[0], non_blocking=True)
         if return_stage1:
             st.h_st1[0].copy_(st.d_st1[0], non_blocking=True)
@@ -268,14 +313,22 @@ def _split_batch(b):
 @torch.no_grad()
 def process_stream(model, batches: Iterable[Sequence[np.ndarray]], color_fix_type: str, disable_preprocess_model: bool, tiled: bool,
                    tile_size: int, tile_stride: int, preprocess_model=None, vae=None, y=None, y_mask=None, noise_scheduler=None,
-                   return_stage1: bool = True, graph: bool = False, fp8: bool = False) -> Iterator[Tuple[List[np.ndarray], List[np.ndarray]]]:
+                   return_stage1: bool = True, graph: bool = False, fp8: bool = False, png=None,
+                   png_wrap: bool = True) -> Iterator[Tuple[List[np.ndarray], List[np.ndarray]]]:
     """process() over a sequence of image batches with the transfers hidden: while batch i computes on the current stream, batch
     i+1 is uploaded and batch i-1 downloaded on a copy stream (two staging slots per batch shape). Yields process()'s result for
     every batch, in order. Needs the fused form (all models instarevive_amd objects on one context). fp8 as in process() (cfg-5:
     vae.enable_fp8() first; the operand set is the context's ir_set_fp8_mask, by default the tolerance-chosen one).
     A batch may also be an (images, y, y_mask) triple: y [B, T, C] / y_mask (as set_prompt takes them) are that batch's prompts, one per image
     or one for all. They are queued on the stream right before the batch's launch (pinned upload, ir_dit_set_prompts: no host wait), so a
-    recorded graph (graph=True) replays across batches whose prompts differ in content only. Batches without prompts take y / y_mask."""
+    recorded graph (graph=True) replays across batches whose prompts differ in content only. Batches without prompts take y / y_mask.
+    png: an iterable in step with `batches` (it is advanced right after the batch is drawn, so a generator fed by the batch generator works): per
+    batch None, or one valid rectangle (vh, vw) per image. For such a batch ir_png_encode is queued behind ir_pipeline on the compute stream for
+    the predictions and, with return_stage1, the stage-1 images; under graph=True it runs behind the graph's replay and is not part of the
+    recording. The copy stream then fetches the byte counts and only the produced bytes - the raw images are not downloaded - and the
+    batch's two lists hold PNG files (`bytes`, the top-left vh x vw crops) in place of arrays. The chunk framing (one CRC-32 over the compressed
+    bytes and their copy into the file, about 20 ms per 2048 x 2048 result) is done on the calling thread between launches; png_wrap=False yields
+    (zlib stream, width, height) triples instead, for png.wrap_png(*triple) on a thread of the caller's (what inference.py's writer pool does)."""
     noise_scheduler = noise_scheduler or DDPMScheduler()
     if not _fused_ok(model, preprocess_model, vae, disable_preprocess_model):
         raise TypeError("process_stream needs instarevive_amd models sharing one context")
@@ -286,19 +339,24 @@ def process_stream(model, batches: Iterable[Sequence[np.ndarray]], color_fix_typ
     base_flags = _pipeline_flags(model, color_fix_type, disable_preprocess_model, tiled) | (L.FLAG_GRAPH if graph else 0) | (L.FLAG_FP8 if fp8 else 0)
     main, copy = torch.cuda.current_stream(device), ctx.__dict__.setdefault("_copy_stream", torch.cuda.Stream(device))
     it = iter(batches)
+    png_it = iter(png) if png is not None else None
 
     def upload(batch, slot):
+        rects = next(png_it) if png_it is not None else None
         imgs, by, bm = _split_batch(batch)
         n, h, w = _check_images(imgs)
         st = _Staging.get(ctx, n, h, w, slots=2, tag="stream")
         st.fill(slot, imgs)
         with torch.cuda.stream(copy):
             ev = st.upload(slot, copy)
-        return st, slot, (n, h, w), ev, (by, bm)
+        return st, slot, (n, h, w), ev, (by, bm), rects
 
     def download(job):
-        st, slot, (n, h, w), done = job
+        st, slot, (n, h, w), done, enc = job
         done.synchronize()
+        if enc is not None:   # the byte counts are here: fetch that many bytes per image
+            files = enc.fetch(2 * n if return_stage1 else n, copy, png_wrap)
+            return files[:n], files[n:]
         preds = st.h_out[slot].clone().numpy()
         stage1 = st.h_st1[slot].clone().numpy() if return_stage1 else None
         return [preds[i] for i in range(n)], ([stage1[i] for i in range(n)] if return_stage1 else [])
@@ -327,11 +385,14 @@ def process_stream(model, batches: Iterable[Sequence[np.ndarray]], color_fix_typ
     nxt = next(it, None)
     up = upload(nxt, slot) if nxt is not None else None
     while up is not None:
-        st, cur, (n, h, w), ready, (by, bm) = up
+        st, cur, (n, h, w), ready, (by, bm), rects = up
         _prepare_fused(model, y, y_mask, h, w, tiled, tile_size, (vae, None if disable_preprocess_model else preprocess_model), set_prompt=False)
         set_batch_prompt(by, bm, n)
         main.wait_event(ready)
+        if rects is not None:
+            _png_workspace(ctx, n, h, w)
         _launch_pipeline(ctx, st, cur, n, h, w, base_flags, tile_size, tile_stride, acp, sf, return_stage1)
+        enc = _queue_png(ctx, st, cur, n, h, w, rects, return_stage1, "stream") if rects is not None else None
         computed = torch.cuda.Event()
         computed.record(main)
         # while this batch computes: fetch the previous result, stage the next input into the other slot. The other slot's device
@@ -342,12 +403,15 @@ def process_stream(model, batches: Iterable[Sequence[np.ndarray]], color_fix_typ
         up = upload(nxt, cur ^ 1) if nxt is not None else None
         with torch.cuda.stream(copy):
             copy.wait_event(computed)
-            st.h_out[cur].copy_(st.d_out[cur], non_blocking=True)
-            if return_stage1:
-                st.h_st1[cur].copy_(st.d_st1[cur], non_blocking=True)
+            if enc is not None:
+                enc.fetch_sizes()
+            else:
+                st.h_out[cur].copy_(st.d_out[cur], non_blocking=True)
+                if return_stage1:
+                    st.h_st1[cur].copy_(st.d_st1[cur], non_blocking=True)
             done = torch.cuda.Event()
             done.record(copy)
-        pending = (st, cur, (n, h, w), done)
+        pending = (st, cur, (n, h, w), done, enc)
     if pending is not None:
         yield download(pending)
 
@@ -471,11 +535,18 @@ class HipTileEngine:
                                       self.flags, self.sf, L.ptr(ws), ws.numel()), "ir_tiled_decode")
         return px[:k]
 
-    def blend_pixels(self, px_all):
+    def blend_pixels(self, px_all, png=None):
+        """The assembled uint8 frames; with png (one valid rectangle per image) their PNG files, encoded on this GPU, as bytes."""
         n, h, w = self.shape
         out = torch.empty((n, h, w, 3), dtype=torch.uint8, device=self.device)
         ws, c = self._ws(), self.ctx
         c.check(c.lib.ir_tiled_blend_pixels(c.h, c.stream(), L.ptr(px_all.contiguous()), L.ptr(out), n, h, w, self.tile_size, self.tile_stride,
                                             L.ptr(ws), ws.numel()), "ir_tiled_blend_pixels")
+        if png is not None:
+            enc = _png_encoder(c, n, h, w, 0, "tiles")
+            enc.queue(0, out, png)
+            enc.fetch_sizes()
+            torch.cuda.current_stream(self.device).synchronize()
+            return enc.fetch(n)
         a = out.cpu().numpy()
         return [a[i] for i in range(n)]
