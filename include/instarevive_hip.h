@@ -26,7 +26,8 @@ enum { IR_STAGE_SWINIR = 0, IR_STAGE_VAE_ENCODE = 1, IR_STAGE_DIT = 2, IR_STAGE_
        IR_STAGE_COLORFIX = 5, IR_STAGE_T5 = 6 /* ir_workspace_bytes(ctx, IR_STAGE_T5, batch, tokens, 0, ...) */,
        IR_STAGE_CLDM = 7 /* ir_cldm_sample: n, h, w = the LATENT size */, IR_STAGE_CLDM_PIPELINE = 8 /* ir_cldm_pipeline: image size */,
        IR_STAGE_CLIP_TEXT = 9 /* ir_clip_text_encode: n = batch */,
-       IR_STAGE_PNG = 10 /* ir_png_encode: n images, h, w = the VALID rectangle vh, vw; depends on the sizes alone (ctx may be NULL) */ };
+       IR_STAGE_PNG = 10 /* ir_png_encode: n images, h, w = the VALID rectangle vh, vw; depends on the sizes alone (ctx may be NULL) */,
+       IR_STAGE_RESAMPLE = 11 /* ir_resample_u8: n images, h = in_h, w = out_w; depends on the sizes alone (ctx may be NULL) */ };
 /* ir_pipeline flags */
 enum { IR_FLAG_NO_PREPROCESS = 1, IR_FLAG_TILED = 2, IR_FLAG_FIX_WAVELET = 4, IR_FLAG_FIX_ADAIN = 8,
        /* ir_pipeline only, needs ir_dit_control_configure: run the DiT step with the ControlNet-Half branch, condition latent
@@ -275,6 +276,28 @@ int ir_nchw_to_u8(ir_ctx* ctx, void* stream, const float* in, uint8_t* out, int 
 size_t ir_png_bound(int h, int w);
 int ir_png_encode(ir_ctx* ctx, void* stream, const uint8_t* img, int n, int h, int w, long pitch, int vh, int vw, uint8_t* out, size_t out_stride,
                   uint32_t* info, void* ws, size_t ws_bytes);
+
+/* Pillow's resampling of 8-bit RGB images on the device (PIL.Image.resize with BICUBIC / LANCZOS, Resample.c): what the command line does to
+ * every input (--sr_scale, auto_resize: inference.py:263-291) and to the results of enlarged inputs (LANCZOS back to the LQ size, :323-346).
+ * Integer arithmetic with Pillow's rounding, so the bytes are Pillow's: horizontal pass, then vertical pass, a uint8 image between them, a
+ * pass whose input and output length are equal skipped (equal sizes: a copy).
+ * ir_resample_plan (pure host code, no context, no GPU) writes the plan of one size pair into `bytes` >= ir_resample_plan_bytes(...) bytes of
+ * host memory: a header of 16 int32 - a tag, in_h, in_w, out_h, out_w, filter, ksize_h, ksize_v, the offsets (in int32 units) of the horizontal
+ * bounds, horizontal coefficients, vertical bounds, vertical coefficients, the length in int32 units - followed by the tables of
+ * precompute_coeffs + normalize_coeffs_8bpc: per output index (xmin, xmax) and ksize coefficients scaled by 2^22. Returns 0, or -1 for a
+ * size below 1, an unknown filter, a null pointer or too few bytes. ir_resample_plan_bytes returns 0 for arguments the plan refuses.
+ * ir_resample_u8: n images in [n][in_h][in_pitch] (valid in_w pixels per row) -> out [n][full_h][out_pitch]: the out_h x out_w result in the
+ * top-left corner, zeros in rows out_h .. full_h and columns out_w .. full_w (the pad to multiples of 64 of the network input), nothing behind
+ * column full_w. plan_dev: the plan of (in_h, in_w, out_h, out_w) in device memory after the caller's own (asynchronous) upload; a plan of other
+ * sizes makes the call write nothing. ws: 4-byte aligned, ir_workspace_bytes(ctx, IR_STAGE_RESAMPLE, n, in_h, out_w, 0, 0, 0) bytes; read only
+ * when both passes run (it may be NULL otherwise). Stream-ordered, no allocation, no host synchronisation (capturable). Returns -1 (nothing
+ * launched) for a null pointer, a size below 1, full_h < out_h, full_w < out_w, a pitch below three bytes per pixel, or a short or unaligned
+ * workspace. */
+enum { IR_RESAMPLE_BICUBIC = 0, IR_RESAMPLE_LANCZOS = 1 };
+size_t ir_resample_plan_bytes(int in_h, int in_w, int out_h, int out_w, int filter);
+int ir_resample_plan(int in_h, int in_w, int out_h, int out_w, int filter, void* host_plan, size_t bytes);
+int ir_resample_u8(ir_ctx* ctx, void* stream, const uint8_t* in, int n, int in_h, int in_w, long in_pitch, uint8_t* out, int out_h, int out_w,
+                   int full_h, int full_w, long out_pitch, const void* plan_dev, void* ws, size_t ws_bytes);
 
 /* Single-kernel entry points, exported so tests/ can check every kernel against the oracle through the same ABI. */
 int ir_op_conv(ir_ctx* ctx, void* stream, const uint16_t* in, const uint16_t* wgt, const float* bias, void* out, int n, int h, int w,

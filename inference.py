@@ -88,7 +88,12 @@ def parse_args() -> Namespace:
                         "LZ77 matches; lossless, the same pixels) and only the compressed bytes cross PCIe - for restored PHOTOGRAPHS, where its files are 10 - 18 %% "
                         "smaller than --png_compress_level 1 and within a few percent of the default level; flat or near-flat content (smooth sky, graphics) comes "
                         "out several times larger than PIL's, since a byte never costs less than one bit. Files that are not a plain crop of the prediction "
-                        "(--show_lq, inputs that auto_resize enlarged) still take the host encoder; the run says how many")
+                        "(--show_lq; inputs that auto_resize enlarged, unless --resize gpu resizes their results on the device) still take the host encoder; the run says how many")
+    parser.add_argument("--resize", type=str, default="host", choices=["host", "gpu"], help="who resizes the inputs (--sr_scale and the enlargement of short edges "
+                        "below 512 / the tile size, both bicubic) and the results of enlarged inputs (LANCZOS back to the input's size). host (default): PIL on the "
+                        "reader / writer threads, as the reference does. gpu: the decoded file is uploaded as it is and the device resamples it with Pillow's own "
+                        "integer arithmetic - the same pixels in the saved files - so the enlarged image neither costs a reader thread its bicubic nor crosses "
+                        "PCIe, and with --png_encoder gpu every file is encoded on the device. --show_lq, --use_center_crop and --shard_tiles keep the host path")
     parser.add_argument("--workers", type=int, default=-1, help="host threads that decode / resize the inputs and resize / PNG-encode the results "
                         "around the GPU (PIL releases the GIL there); -1 = this process's CPU share, 0 = everything on the main thread like the reference")
     return parser.parse_args()
@@ -122,7 +127,7 @@ def default_workers(local_world: int = 1) -> int:
     (two; one when the rank's part is 8 cores or fewer - 8 ranks on a 64-core host - where the feeding thread, asleep in stream waits most of the time,
     shares a core with an encoder rather than take a quarter of the rank's budget), at most 16 (one MI355X produces ~8 results of 2048 x 2048 a second and
     a PNG of that size costs 0.8 - 1.7 core-seconds on the host encoder, which is what this count is sized for; under --png_encoder gpu a file costs the host about
-    0.03 core-seconds, paid on the writer threads (the feeding thread only copies the compressed bytes out of the pinned buffer), and two or three threads would do - the count is not lowered for it, since files that are not plain crops still take the host encoder;
+    0.03 core-seconds, paid on the writer threads (the feeding thread only copies the compressed bytes out of the pinned buffer), and two or three threads would do - the count is not lowered for it, since files that are not plain crops still take the host encoder (without --resize gpu: every input that auto_resize enlarged);
     $IR_WORKERS overrides)."""
     if os.environ.get("IR_WORKERS"):
         return max(0, int(os.environ["IR_WORKERS"]))
@@ -139,7 +144,7 @@ def host_keeps_up(workers: int, out_pixels: int, compress_level, encoder: str = 
     """'' when `workers` encoder threads keep ahead of one GPU for results of out_pixels pixels, else the sentence the CLI prints: the rank is then
     host-bound (8 ranks on a 64-core host: 7 threads encode ~5.6 files/s of 2048 x 2048 at PIL's default level against ~8.4 from the GPU). The estimate
     scales the measured level-6 cost by the pixel count; level 1 costs about a third of it (larger files, the same pixels). encoder = "gpu" prices a
-    file at the host's share of the device encoder (PNG_GPU_HOST_CORE_SECONDS_2048), for runs whose files are plain crops of the prediction."""
+    file at the host's share of the device encoder (PNG_GPU_HOST_CORE_SECONDS_2048), for runs whose files are plain crops of the prediction or, under --resize gpu, resized on the device."""
     if workers <= 0 or out_pixels <= 0:
         return ""
     scale = out_pixels / float(2048 * 2048)
@@ -175,11 +180,24 @@ class Job:
     net_in: np.ndarray         # what process() receives: HWC uint8, edges multiples of 64 (or 512 x 512 under --use_center_crop)
     valid_hw: tuple            # un-padded extent of net_in, () under --use_center_crop (nothing to remove)
     src: str = ""              # the input file (its caption under --caption_dir)
+    # --resize gpu: lq is the DECODED file (nothing is resized on the host), net_in is None and valid_hw is geo.valid_hw
+    geo: object = None         # resample.job_geometry() of the file: resize chain, valid extent, network size, LANCZOS target
+    raw: np.ndarray = None     # the decoded file, HWC uint8: what is uploaded
+
+
+def net_shape(job: Job) -> tuple:
+    """Shape of the network input of a job, wherever it is made."""
+    return job.net_in.shape if job.geo is None else tuple(job.geo.net_hw) + (3,)
 
 
 def read_job(file_path: str, repeat: int, args: Namespace) -> Job:
     from instarevive_amd.utils import auto_resize, center_crop_arr, get_file_name_parts, pad
     lq = Image.open(file_path).convert("RGB")
+    if getattr(args, "resize_on_gpu", False):   # decode only: the sizes are worked out here, the pixels are resampled on the device
+        from instarevive_amd.resample import job_geometry
+        geo = job_geometry(lq.size, args.sr_scale, args.tiled, args.tile_size)
+        folder, stem, _ = get_file_name_parts(os.path.join(args.output, os.path.relpath(file_path, args.input)))
+        return Job(os.path.join(folder, f"{stem}_{repeat}.png"), lq, None, geo.valid_hw, file_path, geo, np.array(lq))
     if args.sr_scale != 1:
         lq = lq.resize(tuple(math.ceil(edge * args.sr_scale) for edge in lq.size), Image.BICUBIC)
     if args.use_center_crop and not args.tiled:
@@ -196,9 +214,13 @@ def read_job(file_path: str, repeat: int, args: Namespace) -> Job:
 def png_rect(job: Job, args: Namespace):
     """The rectangle (vh, vw) of the prediction that write_job() would save unchanged, or None when the saved file is anything else. It is a plain
     crop when there is no --show_lq strip and the resize back to the LQ size is the identity: nothing to un-pad (--use_center_crop), or an LQ image
-    that auto_resize left at its size (PIL's resize to the same size copies). Such jobs can be encoded on the GPU (--png_encoder gpu)."""
+    that auto_resize left at its size (PIL's resize to the same size copies). Such jobs can be encoded on the GPU (--png_encoder gpu).
+    A job that --resize gpu resizes on the device is saved as the device leaves it: the rectangle is its final size, the LANCZOS target of an
+    enlarged input included."""
     if getattr(args, "show_lq", False):
         return None
+    if job.geo is not None:
+        return tuple(job.geo.lanczos[::-1]) if job.geo.lanczos else tuple(job.geo.valid_hw)
     if not job.valid_hw:
         return tuple(job.net_in.shape[:2])
     vh, vw = job.valid_hw
@@ -219,7 +241,7 @@ def write_png_file(job: Job, blob) -> None:
 
 def write_job(job: Job, pred: np.ndarray, stage1_pred, args: Namespace) -> None:
     def back_to_lq(img):
-        if not job.valid_hw:
+        if not job.valid_hw or job.geo is not None:   # --resize gpu: the device has un-padded and resized it already
             return img
         img = img[:job.valid_hw[0], :job.valid_hw[1], :]
         return np.array(Image.fromarray(img).resize(job.lq.size, Image.LANCZOS))
@@ -303,7 +325,7 @@ def batches_of(jobs: Iterable[Job], limit: int, key: Callable = None) -> Iterato
     whose key(job) differs do not share a batch either (--png_encoder gpu: a batch is encoded on the GPU as a whole or not at all)."""
     group: List[Job] = []
     for job in jobs:
-        if group and (len(group) >= limit or job.net_in.shape != group[0].net_in.shape or (key is not None and key(job) != key(group[0]))):
+        if group and (len(group) >= limit or net_shape(job) != net_shape(group[0]) or (key is not None and key(job) != key(group[0]))):
             yield group
             group = []
         group.append(job)
@@ -365,6 +387,12 @@ def main() -> None:
         sys.setswitchinterval(float(os.environ["IR_SWITCH_INTERVAL"]))
     pools = HostPools(default_workers(local_world) if args.workers < 0 else args.workers)
     gpu_png = args.png_encoder == "gpu"
+    args.resize_on_gpu = args.resize == "gpu"
+    for flag, why in (("show_lq", "its strip needs the enlarged LQ panel on the host"), ("use_center_crop", "the centre crop halves with a BOX filter"),
+                      ("shard_tiles", "the tile-sharded path takes host-prepared images")):
+        if args.resize_on_gpu and getattr(args, flag):
+            print(f"[rank {rank}] --resize gpu: --{flag} keeps the resizes on the host ({why})")
+            args.resize_on_gpu = False
     note = host_keeps_up(pools.workers, int(512 * 512 * max(args.sr_scale, 1.0) ** 2), args.png_compress_level, args.png_encoder)   # priced on a 512 x 512 LQ file at this --sr_scale
     if note:
         print(f"[rank {rank}] {note}")
@@ -408,6 +436,7 @@ def main() -> None:
     jobs = pools.read_ahead(lambda pi: read_job(pi[0], pi[1], args), [(p, i) for p in mine for i in range(args.repeat_times)])
     todo: List[List[Job]] = []
     rects = deque()   # --png_encoder gpu, per batch drawn by process_stream: its rectangles, or None for a batch of the host encoder
+    records = deque()   # --resize gpu, per batch: the decoded files and their geometry
 
     def feed():
         for group in batches_of(jobs, max(args.batch_size, 1), (lambda j: png_rect(j, args) is not None) if gpu_png else None):
@@ -416,15 +445,23 @@ def main() -> None:
                 rr = [png_rect(j, args) for j in group]
                 rects.append(rr if all(rr) else None)
             imgs = [j.net_in for j in group]
+            if args.resize_on_gpu:
+                from instarevive_amd.resample import ResizeJob
+                records.append([ResizeJob(j.raw, j.geo) for j in group])
             yield (imgs, *caps.batch([j.src for j in group])) if caps else imgs
 
     def batch_rects():   # in step with feed(): process_stream advances it right after it has drawn a batch
         while True:
             yield rects.popleft()
 
+    def batch_records():
+        while True:
+            yield records.popleft()
+
     first = None    # (time, files) when the first result left the GPU: what follows is the steady state (no library / workspace warm-up in it)
     for preds, stage1 in process_stream(m.model, feed(), tiled=args.tiled, return_stage1=args.show_lq and not args.disable_preprocess_model,
-                                        fp8=args.fp8 != "off", png=batch_rects() if gpu_png else None, png_wrap=False, **common):
+                                        fp8=args.fp8 != "off", png=batch_rects() if gpu_png else None, png_wrap=False,
+                                        resize=batch_records() if args.resize_on_gpu else None, **common):
         group = todo.pop(0)
         last_result = time.perf_counter()
         if first is None:

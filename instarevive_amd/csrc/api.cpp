@@ -2511,8 +2511,120 @@ int ir_png_encode(ir_ctx* c, void* stream, const uint8_t* img, int n, int h, int
     return 0;
 }
 
+// ---------------------------------------------------------------- Pillow's 8-bit resampling (resample.hip)
+// The tables of Resample.c's precompute_coeffs + normalize_coeffs_8bpc. Plain double arithmetic in Pillow's order of operations (no contraction
+// into fused multiply-adds): the quantised coefficients have to be Pillow's to the last bit.
+#pragma clang fp contract(off)
+static double rs_bicubic(double x) {
+    const double a = -0.5;
+    if (x < 0.0) x = -x;
+    if (x < 1.0) return ((a + 2.0) * x - (a + 3.0)) * x * x + 1;
+    if (x < 2.0) return (((x - 5) * x + 8) * x - 4) * a;
+    return 0.0;
+}
+static double rs_sinc(double x) {
+    if (x == 0.0) return 1.0;
+    x = x * M_PI;
+    return sin(x) / x;
+}
+static double rs_lanczos(double x) { return (-3.0 <= x && x < 3.0) ? rs_sinc(x) * rs_sinc(x / 3) : 0.0; }
+struct RsAxis {
+    double scale, filterscale, support;
+    int ksize;
+};
+static RsAxis rs_axis(int in, int out, int filter) {
+    RsAxis a;
+    a.filterscale = a.scale = (double)(float)in / out;
+    if (a.filterscale < 1.0) a.filterscale = 1.0;
+    a.support = (filter == IR_RESAMPLE_LANCZOS ? 3.0 : 2.0) * a.filterscale;
+    a.ksize = (int)ceil(a.support) * 2 + 1;
+    return a;
+}
+static void rs_tables(int in, int out, int filter, int* bounds, int* kk) {
+    const RsAxis a = rs_axis(in, out, filter);
+    std::vector<double> w(a.ksize);
+    const double ss = 1.0 / a.filterscale;
+    for (int xx = 0; xx < out; ++xx) {
+        const double center = (xx + 0.5) * a.scale;
+        double ww = 0.0;
+        int xmin = (int)(center - a.support + 0.5);
+        if (xmin < 0) xmin = 0;
+        int xmax = (int)(center + a.support + 0.5);
+        if (xmax > in) xmax = in;
+        xmax -= xmin;
+        for (int x = 0; x < xmax; ++x) {
+            const double arg = (x + xmin - center + 0.5) * ss;
+            w[x] = filter == IR_RESAMPLE_LANCZOS ? rs_lanczos(arg) : rs_bicubic(arg);
+            ww += w[x];
+        }
+        int* k = kk + (size_t)xx * a.ksize;
+        for (int x = 0; x < a.ksize; ++x) {
+            double v = x < xmax ? w[x] : 0.0;
+            if (x < xmax && ww != 0.0) v /= ww;
+            k[x] = v < 0 ? (int)(-0.5 + v * (1 << 22)) : (int)(0.5 + v * (1 << 22));
+        }
+        bounds[2 * xx] = xmin;
+        bounds[2 * xx + 1] = xmax;
+    }
+}
+#pragma clang fp contract(fast)
+static bool rs_args_ok(int in_h, int in_w, int out_h, int out_w, int filter) {
+    return in_h >= 1 && in_w >= 1 && out_h >= 1 && out_w >= 1 && (filter == IR_RESAMPLE_BICUBIC || filter == IR_RESAMPLE_LANCZOS);
+}
+// ints of the plan: the header, then per pass that runs 2 bounds + ksize coefficients per output index
+static size_t rs_plan_ints(int in_h, int in_w, int out_h, int out_w, int filter, int* hd) {
+    size_t at = IR_RESAMPLE_HEADER;
+    int h[IR_RESAMPLE_HEADER] = {IR_RESAMPLE_MAGIC, in_h, in_w, out_h, out_w, filter};
+    if (in_w != out_w) {
+        h[6] = rs_axis(in_w, out_w, filter).ksize;
+        h[8] = (int)at; at += 2 * (size_t)out_w;
+        h[9] = (int)at; at += (size_t)out_w * h[6];
+    }
+    if (in_h != out_h) {
+        h[7] = rs_axis(in_h, out_h, filter).ksize;
+        h[10] = (int)at; at += 2 * (size_t)out_h;
+        h[11] = (int)at; at += (size_t)out_h * h[7];
+    }
+    h[12] = (int)at;
+    if (hd) memcpy(hd, h, sizeof h);
+    return at;
+}
+size_t ir_resample_plan_bytes(int in_h, int in_w, int out_h, int out_w, int filter) {
+    if (!rs_args_ok(in_h, in_w, out_h, out_w, filter)) return 0;
+    const size_t ints = rs_plan_ints(in_h, in_w, out_h, out_w, filter, nullptr);
+    return ints > 0x7fffffffu ? 0 : 4 * ints;   // the offsets are ints
+}
+int ir_resample_plan(int in_h, int in_w, int out_h, int out_w, int filter, void* host_plan, size_t bytes) {
+    const size_t need = ir_resample_plan_bytes(in_h, in_w, out_h, out_w, filter);
+    if (!host_plan || !need || bytes < need) return -1;
+    int* p = static_cast<int*>(host_plan);
+    rs_plan_ints(in_h, in_w, out_h, out_w, filter, p);
+    if (in_w != out_w) rs_tables(in_w, out_w, filter, p + p[8], p + p[9]);
+    if (in_h != out_h) rs_tables(in_h, out_h, filter, p + p[10], p + p[11]);
+    return 0;
+}
+static size_t rs_inter_pitch(int out_w) { return (3 * (size_t)out_w + 3) & ~(size_t)3; }
+static size_t rs_workspace(int n, int in_h, int out_w) { return ((size_t)n * in_h * rs_inter_pitch(out_w) + 255) & ~(size_t)255; }
+int ir_resample_u8(ir_ctx* c, void* stream, const uint8_t* in, int n, int in_h, int in_w, long in_pitch, uint8_t* out, int out_h, int out_w, int full_h,
+                   int full_w, long out_pitch, const void* plan_dev, void* ws, size_t ws_bytes) {
+    if (!c || !in || !out || !plan_dev) return fail(c, -1, "ir_resample_u8: null argument");
+    if (n < 1 || in_h < 1 || in_w < 1 || out_h < 1 || out_w < 1 || full_h < out_h || full_w < out_w || in_pitch < 3L * in_w || out_pitch < 3L * full_w)
+        return fail(c, -1, "ir_resample_u8: bad size (n %d, %d x %d pitch %ld -> %d x %d in %d x %d pitch %ld)", n, in_h, in_w, in_pitch, out_h, out_w, full_h,
+                    full_w, out_pitch);
+    const bool both = in_h != out_h && in_w != out_w;
+    if (both && (!ws || ws_bytes < rs_workspace(n, in_h, out_w) || (reinterpret_cast<uintptr_t>(ws) & 3)))
+        return fail(c, -1, "ir_resample_u8: workspace missing, too small or unaligned (%zu < %zu)", ws_bytes, rs_workspace(n, in_h, out_w));
+    if (reinterpret_cast<uintptr_t>(plan_dev) & 3) return fail(c, -1, "ir_resample_u8: plan not aligned to 4 bytes");
+    use_ctx(c);
+    if (ir_launch_resample_u8(in, n, in_h, in_w, in_pitch, out, out_h, out_w, full_h, full_w, out_pitch, static_cast<const int*>(plan_dev),
+                              static_cast<uint8_t*>(ws), (long)rs_inter_pitch(out_w), (hipStream_t)stream))
+        return fail(c, -100, "ir_resample_u8: launch failed (more than 65535 images or rows)");
+    return 0;
+}
+
 size_t ir_workspace_bytes(ir_ctx* c, int stage, int n, int h, int w, int flags, int tile_size, int tile_stride) {
     if (stage == IR_STAGE_PNG) return (n < 1 || h < 1 || w < 1) ? 0 : png_layout(n, h, w).total;   // a function of the sizes alone: no context needed
+    if (stage == IR_STAGE_RESAMPLE) return (n < 1 || h < 1 || w < 1) ? 0 : rs_workspace(n, h, w);    // n images, h = in_h, w = out_w: the uint8 image between the passes
     if (!c) return 0;
     Run r = make_run(c, nullptr, nullptr, 0, true);
     if (stage_dispatch(c, r, stage, n, h, w, flags, tile_size, tile_stride)) return 0;

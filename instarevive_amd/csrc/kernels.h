@@ -207,6 +207,16 @@ int ir_launch_t5_gated_gelu(const bf16_t* ab, bf16_t* out, long rows, int F, hip
 int ir_launch_png_encode(const uint8_t* img, int n, int h, long pitch, int vh, int vw, uint8_t* out, size_t out_stride, uint32_t* info,
                          uint32_t* hist, uint32_t* codes, uint32_t* header, uint32_t* chunk_bytes, uint8_t* slots, long slot_cap, hipStream_t s);
 
+// ---- Pillow's 8-bit resampling of uint8 images (resample.hip)
+// The plan (ir_resample_plan) is an int32 array: a header of IR_RESAMPLE_HEADER ints - [0] IR_RESAMPLE_MAGIC, [1..4] in_h, in_w, out_h, out_w, [5] the
+// filter, [6] ksize_h, [7] ksize_v, [8] / [9] the offsets (in ints, from the plan's start) of the horizontal bounds [out_w][2] and coefficients
+// [out_w][ksize_h], [10] / [11] the same of the vertical pass ([out_h] rows), [12] the plan's length in ints - and the tables. A skipped pass
+// (equal lengths) has ksize 0 and no tables. inter: [n][in_h][inter_pitch] bytes, inter_pitch a multiple of 4, used when both passes run.
+#define IR_RESAMPLE_MAGIC 0x52535038
+#define IR_RESAMPLE_HEADER 16
+int ir_launch_resample_u8(const uint8_t* in, int n, int in_h, int in_w, long in_pitch, uint8_t* out, int out_h, int out_w, int full_h, int full_w,
+                          long out_pitch, const int* plan, uint8_t* inter, long inter_pitch, hipStream_t s);
+
 // ---- layout / elementwise (elementwise.hip)
 int ir_launch_u8_to_nchw(const uint8_t* in, float* out, int N, int H, int W, hipStream_t s);
 int ir_launch_swin_prep(const float* x_nchw, bf16_t* out, int N, int H, int W, const float* mean3, float img_range, hipStream_t s);

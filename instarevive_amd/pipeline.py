@@ -95,6 +95,36 @@ def _png_workspace(ctx, n, h, w):
     ctx.workspace(ctx.ws_bytes(L.STAGE_PNG, n, h, w))
 
 
+def _resize_workspace(ctx, records):
+    """Grow the context's workspace for the resampling calls of a resize batch BEFORE the pipeline's launch takes its address, like _png_workspace."""
+    from .resample import chain_ws_bytes
+    ctx.workspace(chain_ws_bytes(records))
+
+
+def _resize_results(ctx, rs, records, st, slot, n, h, w, with_stage1, rects, tag):
+    """Behind the ir_pipeline of a resize batch, on the current stream: LANCZOS of the valid rectangles back to the LQ sizes (resample.ResizeSlot),
+    then - with rects - ir_png_encode of every image's final form: the resized result, or the valid rectangle of the network's output.
+    Returns (results, stage-1 results, encoder or None); a result is a device tensor [1][th][tw][3] or None for a plain crop."""
+    rs.reserve_results(n, h, w, with_stage1)
+    res = rs.back_to_lq(records, st.d_out[slot], 0)
+    res1 = rs.back_to_lq(records, st.d_st1[slot], n) if with_stage1 else []
+    if rects is None:
+        return res, res1, None
+    final = [tuple(rec.geo.lanczos[::-1]) if rec.geo.lanczos else tuple(rec.geo.valid_hw) for rec in records]
+    if [tuple(r) for r in rects] != final:
+        raise ValueError(f"png: the rectangles {list(rects)} of a resize batch are not its final sizes {final}")
+    enc = _png_encoder(ctx, 2 * n if with_stage1 else n, h, w, slot, tag)
+    for first, out, rr in ((0, st.d_out[slot], res), (n, st.d_st1[slot], res1)):
+        for i, r in enumerate(rr):
+            enc.queue(first + i, out[i:i + 1] if r is None else r, [final[i]])
+    return res, res1, enc
+
+
+def _resize_arrays(rs, records, res, host):
+    """The final arrays of a downloaded resize batch: the resized result, or the valid rectangle of the network's output `host` [n][h][w][3]."""
+    return [rs.host_result(r) if r is not None else host[i, :rec.geo.valid_hw[0], :rec.geo.valid_hw[1]].copy() for i, (rec, r) in enumerate(zip(records, res))]
+
+
 def _check_images(control_imgs):
     if len(control_imgs) == 0:
         raise ValueError("control_imgs is empty")
@@ -215,7 +245,8 @@ def _launch_pipeline(ctx, st, slot, n, h, w, flags, tile_size, tile_stride, acp,
 @torch.no_grad()
 def process(model, control_imgs: List[np.ndarray], strength: float, color_fix_type: str, disable_preprocess_model: bool, tiled: bool,
             tile_size: int, tile_stride: int, preprocess_model=None, vae=None, y=None, y_mask=None, noise_scheduler=None,
-            fused: bool = True, graph: bool = False, return_stage1: bool = True, fp8: bool = False, png=None) -> Tuple[List[np.ndarray], List[np.ndarray]]:
+            fused: bool = True, graph: bool = False, return_stage1: bool = True, fp8: bool = False, png=None,
+            resize=None) -> Tuple[List[np.ndarray], List[np.ndarray]]:
     """test_scripts/inference.py:55-166. control_imgs: list of HWC uint8 RGB arrays of equal size (multiples of 64).
     Returns (preds, stage1_preds) as lists of HWC uint8 arrays (stage1_preds is empty with return_stage1=False, which skips its
     conversion and download).
@@ -228,11 +259,20 @@ def process(model, control_imgs: List[np.ndarray], strength: float, color_fix_ty
     (vae.enable_fp8() must have uploaded the fp8 weight forms).
     png (fused form only): a list of one valid rectangle (vh, vw) per image. The results are then encoded on the GPU (ir_png_encode queued behind
     ir_pipeline - under graph=True behind the graph's replay, not inside the recording) and both lists hold PNG files as `bytes` of the
-    top-left vh x vw crops instead of arrays; only the compressed bytes are downloaded."""
+    top-left vh x vw crops instead of arrays; only the compressed bytes are downloaded.
+    resize (fused form only): a list of one resample.ResizeJob per image - the DECODED file and its job_geometry(). control_imgs is then not read:
+    the decoded bytes are uploaded, ir_resample_u8 makes the network input on the device (the bicubic chain of --sr_scale / auto_resize, the
+    zero pad), and behind ir_pipeline the valid rectangle of every image that auto_resize enlarged is resampled (LANCZOS) back to its LQ size.
+    Both lists then hold the FINAL images - what the command line saves: the resized result, else the valid rectangle - bit for bit what
+    PIL gives around a plain call; with png their files (the rectangles are then the final sizes)."""
     noise_scheduler = noise_scheduler or DDPMScheduler()
-    n, h, w = _check_images(control_imgs)
-    if png is not None and not (fused and _fused_ok(model, preprocess_model, vae, disable_preprocess_model)):
-        raise ValueError("process(png=...) needs the fused form (instarevive_amd models sharing one context)")
+    if resize is not None:
+        from .resample import ResizeSlot, check_records
+        n, h, w = check_records(resize)
+    else:
+        n, h, w = _check_images(control_imgs)
+    if (png is not None or resize is not None) and not (fused and _fused_ok(model, preprocess_model, vae, disable_preprocess_model)):
+        raise ValueError("process(png=... / resize=...) needs the fused form (instarevive_amd models sharing one context)")
     device = model.device
     acp = float(noise_scheduler.alphas_cumprod[400])
     sf = float(vae.config.scaling_factor)
@@ -245,13 +285,25 @@ def process(model, control_imgs: List[np.ndarray], strength: float, color_fix_ty
         _prepare_fused(model, y, y_mask, h, w, tiled, tile_size, (vae, None if disable_preprocess_model else preprocess_model))
         flags = _pipeline_flags(model, color_fix_type, disable_preprocess_model, tiled) | (L.FLAG_GRAPH if graph else 0) | (L.FLAG_FP8 if fp8 else 0)
         st = _Staging.get(ctx, n, h, w)
-        st.fill(0, control_imgs)
-        st.upload(0)
+        rs = None
+        if resize is None:
+            st.fill(0, control_imgs)
+            st.upload(0)
+        else:
+            rs = ResizeSlot.get(ctx, 0, "sync")
+            rs.fill(resize)
+            rs.upload()
+            _resize_workspace(ctx, resize)
         if png is not None:
             _png_workspace(ctx, n, h, w)
+        if rs is not None:
+            rs.to_network(resize, st.d_in[0])
         _launch_pipeline(ctx, st, 0, n, h, w, flags, tile_size, tile_stride, acp, sf, return_stage1)
+        if rs is not None:
+            res, res1, enc = _resize_results(ctx, rs, resize, st, 0, n, h, w, return_stage1, png, "sync")
         if png is not None:
-            enc = _queue_png(ctx, st, 0, n, h, w, png, return_stage1, "sync")
+            if rs is None:
+                enc = _queue_png(ctx, st, 0, n, h, w, png, return_stage1, "sync")
             enc.fetch_sizes()
             torch.cuda.current_stream(device).synchronize()
             files = enc.fetch(2 * n if return_stage1 else n)
@@ -259,6 +311,11 @@ def process(model, control_imgs: List[np.ndarray], strength: float, color_fix_ty
         st.h_out[0].copy_(st.d_out[0], non_blocking=True)
         if return_stage1:
             st.h_st1[0].copy_(st.d_st1[0], non_blocking=True)
+        if rs is not None:
+            rs.download(res + res1)
+            torch.cuda.current_stream(device).synchronize()
+            return (_resize_arrays(rs, resize, res, st.h_out[0].numpy()),
+                    _resize_arrays(rs, resize, res1, st.h_st1[0].numpy()) if return_stage1 else [])
         torch.cuda.current_stream(device).synchronize()
         preds = st.h_out[0].clone().numpy()   # the caller owns the result; the pinned buffer is reused by the next call
         stage1 = st.h_st1[0].clone().numpy() if return_stage1 else None
@@ -314,7 +371,7 @@ def _split_batch(b):
 def process_stream(model, batches: Iterable[Sequence[np.ndarray]], color_fix_type: str, disable_preprocess_model: bool, tiled: bool,
                    tile_size: int, tile_stride: int, preprocess_model=None, vae=None, y=None, y_mask=None, noise_scheduler=None,
                    return_stage1: bool = True, graph: bool = False, fp8: bool = False, png=None,
-                   png_wrap: bool = True) -> Iterator[Tuple[List[np.ndarray], List[np.ndarray]]]:
+                   png_wrap: bool = True, resize=None) -> Iterator[Tuple[List[np.ndarray], List[np.ndarray]]]:
     """process() over a sequence of image batches with the transfers hidden: while batch i computes on the current stream, batch
     i+1 is uploaded and batch i-1 downloaded on a copy stream (two staging slots per batch shape). Yields process()'s result for
     every batch, in order. Needs the fused form (all models instarevive_amd objects on one context). fp8 as in process() (cfg-5:
@@ -328,7 +385,12 @@ def process_stream(model, batches: Iterable[Sequence[np.ndarray]], color_fix_typ
     recording. The copy stream then fetches the byte counts and only the produced bytes - the raw images are not downloaded - and the
     batch's two lists hold PNG files (`bytes`, the top-left vh x vw crops) in place of arrays. The chunk framing (one CRC-32 over the compressed
     bytes and their copy into the file, about 20 ms per 2048 x 2048 result) is done on the calling thread between launches; png_wrap=False yields
-    (zlib stream, width, height) triples instead, for png.wrap_png(*triple) on a thread of the caller's (what inference.py's writer pool does)."""
+    (zlib stream, width, height) triples instead, for png.wrap_png(*triple) on a thread of the caller's (what inference.py's writer pool does).
+    resize: an iterable in step with `batches`, advanced like png: per batch None, or one resample.ResizeJob per image (the decoded file and its
+    job_geometry(); images that reach one network size share a batch whatever their own sizes). The batch's image list is then not read. The copy
+    stream uploads the decoded bytes, the compute stream runs ir_resample_u8 once or twice per image into the staging input ahead of ir_pipeline
+    and, behind it, LANCZOS of the valid rectangles back to the LQ sizes where auto_resize enlarged; the batch's lists hold the final images
+    as in process(resize=...), and with png (the rectangles are then the final sizes) every file of the batch comes from the device encoder."""
     noise_scheduler = noise_scheduler or DDPMScheduler()
     if not _fused_ok(model, preprocess_model, vae, disable_preprocess_model):
         raise TypeError("process_stream needs instarevive_amd models sharing one context")
@@ -340,23 +402,39 @@ def process_stream(model, batches: Iterable[Sequence[np.ndarray]], color_fix_typ
     main, copy = torch.cuda.current_stream(device), ctx.__dict__.setdefault("_copy_stream", torch.cuda.Stream(device))
     it = iter(batches)
     png_it = iter(png) if png is not None else None
+    resize_it = iter(resize) if resize is not None else None
+    if resize_it is not None:
+        from .resample import ResizeSlot, check_records
 
     def upload(batch, slot):
         rects = next(png_it) if png_it is not None else None
+        records = next(resize_it) if resize_it is not None else None
         imgs, by, bm = _split_batch(batch)
+        if records is not None:   # the decoded files travel; the network input is made on the device
+            n, h, w = check_records(records)
+            st = _Staging.get(ctx, n, h, w, slots=2, tag="stream")
+            rs = ResizeSlot.get(ctx, slot, "stream")
+            rs.fill(records)
+            with torch.cuda.stream(copy):
+                ev = rs.upload(copy, main)
+            return st, slot, (n, h, w), ev, (by, bm), rects, (rs, records)
         n, h, w = _check_images(imgs)
         st = _Staging.get(ctx, n, h, w, slots=2, tag="stream")
         st.fill(slot, imgs)
         with torch.cuda.stream(copy):
             ev = st.upload(slot, copy)
-        return st, slot, (n, h, w), ev, (by, bm), rects
+        return st, slot, (n, h, w), ev, (by, bm), rects, None
 
     def download(job):
-        st, slot, (n, h, w), done, enc = job
+        st, slot, (n, h, w), done, enc, rz = job
         done.synchronize()
         if enc is not None:   # the byte counts are here: fetch that many bytes per image
             files = enc.fetch(2 * n if return_stage1 else n, copy, png_wrap)
             return files[:n], files[n:]
+        if rz is not None:
+            rs, records, res, res1 = rz
+            return (_resize_arrays(rs, records, res, st.h_out[slot].numpy()),
+                    _resize_arrays(rs, records, res1, st.h_st1[slot].numpy()) if return_stage1 else [])
         preds = st.h_out[slot].clone().numpy()
         stage1 = st.h_st1[slot].clone().numpy() if return_stage1 else None
         return [preds[i] for i in range(n)], ([stage1[i] for i in range(n)] if return_stage1 else [])
@@ -385,14 +463,21 @@ def process_stream(model, batches: Iterable[Sequence[np.ndarray]], color_fix_typ
     nxt = next(it, None)
     up = upload(nxt, slot) if nxt is not None else None
     while up is not None:
-        st, cur, (n, h, w), ready, (by, bm), rects = up
+        st, cur, (n, h, w), ready, (by, bm), rects, rz = up
         _prepare_fused(model, y, y_mask, h, w, tiled, tile_size, (vae, None if disable_preprocess_model else preprocess_model), set_prompt=False)
         set_batch_prompt(by, bm, n)
         main.wait_event(ready)
         if rects is not None:
             _png_workspace(ctx, n, h, w)
+        if rz is not None:
+            _resize_workspace(ctx, rz[1])
+            rz[0].to_network(rz[1], st.d_in[cur])
         _launch_pipeline(ctx, st, cur, n, h, w, base_flags, tile_size, tile_stride, acp, sf, return_stage1)
-        enc = _queue_png(ctx, st, cur, n, h, w, rects, return_stage1, "stream") if rects is not None else None
+        if rz is not None:
+            res, res1, enc = _resize_results(ctx, rz[0], rz[1], st, cur, n, h, w, return_stage1, rects, "stream")
+            rz = rz + (res, res1)
+        else:
+            enc = _queue_png(ctx, st, cur, n, h, w, rects, return_stage1, "stream") if rects is not None else None
         computed = torch.cuda.Event()
         computed.record(main)
         # while this batch computes: fetch the previous result, stage the next input into the other slot. The other slot's device
@@ -406,12 +491,15 @@ def process_stream(model, batches: Iterable[Sequence[np.ndarray]], color_fix_typ
             if enc is not None:
                 enc.fetch_sizes()
             else:
-                st.h_out[cur].copy_(st.d_out[cur], non_blocking=True)
-                if return_stage1:
-                    st.h_st1[cur].copy_(st.d_st1[cur], non_blocking=True)
+                if rz is None or any(r is None for r in rz[2]):   # a batch whose results were all resized back downloads those alone
+                    st.h_out[cur].copy_(st.d_out[cur], non_blocking=True)
+                    if return_stage1:
+                        st.h_st1[cur].copy_(st.d_st1[cur], non_blocking=True)
+                if rz is not None:
+                    rz[0].download(rz[2] + rz[3])
             done = torch.cuda.Event()
             done.record(copy)
-        pending = (st, cur, (n, h, w), done, enc)
+        pending = (st, cur, (n, h, w), done, enc, rz)
     if pending is not None:
         yield download(pending)
 

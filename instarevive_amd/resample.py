@@ -1,0 +1,245 @@
+"""The command line's resizes on the device (ir_resample_u8, csrc/resample.hip): the bicubic enlargements ahead of the network (--sr_scale,
+auto_resize: test_scripts/inference.py:263-291) and the LANCZOS resize of the result back to the LQ size (:323-346). Both are Pillow's 8-bit
+separable resampling - integer arithmetic with fixed rounding - so the device's bytes are Pillow's and the saved files hold the same pixels.
+
+job_geometry() is the size arithmetic of a file without its pixels, Plans keeps the coefficient tables (made on the host: they need double
+sin()) per size pair, ResizeSlot the page-locked and device buffers of decoded files and resized results of one staging slot.
+"""
+import ctypes as C
+import math
+from typing import List, NamedTuple, Optional, Sequence, Tuple
+
+import numpy as np
+import torch
+
+from . import _lib as L
+
+BICUBIC, LANCZOS = L.RESAMPLE_BICUBIC, L.RESAMPLE_LANCZOS
+
+
+class Geometry(NamedTuple):
+    chain: tuple      # sizes (w, h) the decoded file is bicubic-resized to, in order: none, one (--sr_scale or auto_resize) or two (both)
+    valid_hw: tuple   # (h, w) of the image the network sees, before the pad
+    net_hw: tuple     # (h, w) of the network input: valid_hw padded to multiples of 64
+    lq_size: tuple    # (w, h) after --sr_scale: the size of the saved result
+    lanczos: Optional[tuple]   # lq_size when the result is resized back to it (auto_resize enlarged the file), else None
+
+
+def job_geometry(size: Tuple[int, int], sr_scale: float, tiled: bool, tile_size: int) -> Geometry:
+    """What inference.py's read_job() does to the sizes of a decoded file of `size` = (w, h), without --use_center_crop: the same expressions
+    in the same floating-point order (math.ceil(edge * sr_scale); utils.auto_resize's ceil(edge * (target / short)))."""
+    w, h = (int(v) for v in size)
+    chain = []
+    if sr_scale != 1:
+        w, h = (math.ceil(edge * sr_scale) for edge in (w, h))
+        chain.append((w, h))
+    lq = (w, h)
+    target = tile_size if tiled else 512
+    short = min(w, h)
+    if short < target:
+        w, h = (int(math.ceil(edge * (target / short))) for edge in (w, h))
+        chain.append((w, h))
+    return Geometry(tuple(chain), (h, w), (h + -h % 64, w + -w % 64), lq, lq if lq != (w, h) else None)
+
+
+class ResizeJob(NamedTuple):
+    """One image of a process(resize=...) batch: the decoded file (HWC uint8 RGB) and its job_geometry()."""
+    raw: np.ndarray
+    geo: Geometry
+
+
+def host_plan(in_h: int, in_w: int, out_h: int, out_w: int, flt: int) -> torch.Tensor:
+    """ir_resample_plan's tables as a page-locked int32 tensor (pure host code)."""
+    lib = L.load_library()
+    nbytes = int(lib.ir_resample_plan_bytes(in_h, in_w, out_h, out_w, flt))
+    if nbytes == 0:
+        raise ValueError(f"no resampling plan for {in_h} x {in_w} -> {out_h} x {out_w}, filter {flt}")
+    plan = torch.empty(nbytes // 4, dtype=torch.int32)
+    if torch.cuda.is_available():
+        plan = plan.pin_memory()
+    if lib.ir_resample_plan(in_h, in_w, out_h, out_w, flt, C.c_void_p(plan.data_ptr()), nbytes) != 0:
+        raise RuntimeError("ir_resample_plan refused a size it gave a byte count for")
+    return plan
+
+
+class Plans:
+    """Plan cache of a context, keyed by (in_h, in_w, out_h, out_w, filter) and bounded like the staging pool: each entry holds the plan in
+    page-locked memory and its device copy, uploaded asynchronously on the stream that is current at the first use - the stream of the
+    resampling calls themselves, so no wait is needed. A folder of equal-sized files plans once."""
+    LIMIT = 64
+
+    def __init__(self, ctx):
+        self.ctx, self.pool = ctx, {}
+
+    @staticmethod
+    def of(ctx) -> "Plans":
+        return ctx.__dict__.setdefault("_resample_plans", Plans(ctx))
+
+    def get(self, in_h, in_w, out_h, out_w, flt) -> torch.Tensor:
+        key = (in_h, in_w, out_h, out_w, flt, torch.cuda.current_stream(self.ctx.device).cuda_stream)
+        if key not in self.pool:
+            if len(self.pool) >= self.LIMIT:   # a copy still queued keeps its memory: torch frees both sides in stream order
+                self.pool.pop(next(iter(self.pool)))
+            host = host_plan(in_h, in_w, out_h, out_w, flt)
+            self.pool[key] = (host, host.to(self.ctx.device, non_blocking=True))
+        return self.pool[key][1]
+
+
+def ws_bytes(n: int, in_h: int, in_w: int, out_h: int, out_w: int) -> int:
+    """Workspace of one ir_resample_u8 call (the uint8 image between the passes; none when a pass is skipped)."""
+    if in_h == out_h or in_w == out_w:
+        return 0
+    return int(L.load_library().ir_workspace_bytes(None, L.STAGE_RESAMPLE, n, in_h, out_w, 0, 0, 0))
+
+
+def resample(ctx, src: int, in_h: int, in_w: int, in_pitch: int, dst: int, out_h: int, out_w: int, full_h: int, full_w: int, out_pitch: int,
+             flt: int, n: int = 1) -> None:
+    """ir_resample_u8 on the current stream; src / dst are device addresses. The scratch is the context's workspace (stream-ordered like
+    every other call that uses it; a caller that has handed its address to a later launch grows it first, see chain_ws_bytes)."""
+    plan = Plans.of(ctx).get(in_h, in_w, out_h, out_w, flt)
+    need = ws_bytes(n, in_h, in_w, out_h, out_w)
+    ws = ctx.workspace(need) if need else None
+    ctx.check(ctx.lib.ir_resample_u8(ctx.h, ctx.stream(), C.c_void_p(src), n, in_h, in_w, in_pitch, C.c_void_p(dst), out_h, out_w, full_h, full_w,
+                                     out_pitch, L.ptr(plan), L.ptr(ws), ws.numel() if need else 0), "ir_resample_u8")
+
+
+def _steps(rec: ResizeJob):
+    """[(in_h, in_w, out_h, out_w)] of the bicubic calls that take rec.raw to the network input (equal sizes: the padded copy)."""
+    h, w = rec.raw.shape[:2]
+    sizes = [(h, w)] + [(th, tw) for tw, th in rec.geo.chain]
+    if len(sizes) == 1:
+        sizes.append((h, w))
+    return [a + b for a, b in zip(sizes[:-1], sizes[1:])]
+
+
+def chain_ws_bytes(records: Sequence[ResizeJob]) -> int:
+    """The largest workspace any resampling call of this batch needs, ahead of and behind the network."""
+    need = 0
+    for rec in records:
+        for ih, iw, oh, ow in _steps(rec):
+            need = max(need, ws_bytes(1, ih, iw, oh, ow))
+        if rec.geo.lanczos:
+            need = max(need, ws_bytes(1, *rec.geo.valid_hw, rec.geo.lanczos[1], rec.geo.lanczos[0]))
+    return need
+
+
+def check_records(records: Sequence[ResizeJob]) -> Tuple[int, int, int]:
+    if len(records) == 0:
+        raise ValueError("resize: empty batch")
+    for rec in records:
+        a = rec.raw
+        if not isinstance(a, np.ndarray) or a.dtype != np.uint8 or a.ndim != 3 or a.shape[-1] != 3:
+            raise ValueError("resize: the decoded files must be HWC uint8 RGB arrays")
+        if rec.geo.net_hw != records[0].geo.net_hw:
+            raise ValueError("resize: the images of a batch must reach one network input size")
+        last = rec.geo.chain[-1] if rec.geo.chain else (a.shape[1], a.shape[0])
+        if (last[1], last[0]) != tuple(rec.geo.valid_hw):
+            raise ValueError("resize: the geometry does not belong to the decoded file")
+    return (len(records),) + tuple(records[0].geo.net_hw)
+
+
+def _grown(t: Optional[torch.Tensor], nbytes: int, device=None, pinned=False) -> torch.Tensor:
+    if t is not None and t.numel() >= nbytes:
+        return t
+    nbytes = max(int(nbytes * 1.25), 1 << 16)   # decoded files of one folder differ a little: do not re-allocate for every new maximum
+    return torch.empty(nbytes, dtype=torch.uint8).pin_memory() if pinned else torch.empty(nbytes, dtype=torch.uint8, device=device)
+
+
+class ResizeSlot:
+    """Buffers of one staging slot for batches whose images are resized on the device. Decoded files differ in size, so they get a flat
+    page-locked buffer and its device copy (each file at a 256-byte boundary) instead of _Staging's fixed shape; `mid` holds the image
+    between two chained bicubic calls; d_res / h_res hold the LANCZOS results (predictions, then stage-1 images) that are downloaded or
+    encoded in place of the network's output. All grow on demand and are reused by the next batch of the slot."""
+
+    def __init__(self, ctx):
+        self.ctx = ctx
+        self.h_raw = self.d_raw = self.mid = self.d_res = self.h_res = None
+        self.h2d_done = None
+        self.fresh = False
+        self.offsets: List[int] = []
+
+    @staticmethod
+    def get(ctx, slot=0, tag="sync") -> "ResizeSlot":
+        pool = ctx.__dict__.setdefault("_resize_slots", {})
+        if (tag, slot) not in pool:
+            pool[(tag, slot)] = ResizeSlot(ctx)
+        return pool[(tag, slot)]
+
+    def fill(self, records: Sequence[ResizeJob]) -> None:
+        """Copy the decoded files into the page-locked buffer (after the previous upload out of it has completed)."""
+        if self.h2d_done is not None:
+            self.h2d_done.synchronize()
+            self.h2d_done = None
+        self.offsets, at = [], 0
+        for rec in records:
+            self.offsets.append(at)
+            at += (rec.raw.size + 255) & ~255
+        self.h_raw = _grown(self.h_raw, at, pinned=True)
+        if self.d_raw is None or self.d_raw.numel() < self.h_raw.numel():
+            self.d_raw, self.fresh = _grown(None, self.h_raw.numel(), self.ctx.device), True
+        self.used = at
+        host = self.h_raw.numpy()
+        for rec, o in zip(records, self.offsets):
+            np.copyto(host[o:o + rec.raw.size].reshape(rec.raw.shape), rec.raw)
+
+    def upload(self, stream=None, owner=None):
+        """Asynchronous H2D copy of the decoded bytes on `stream` (default: the current one); the event behind it is what the next fill() waits for.
+        owner: the stream the buffers are allocated and read on, when it is another one - a device buffer that has just been (re-)allocated may be
+        memory that work queued on `owner` still uses, so the first copy into it waits for that stream."""
+        if self.fresh and owner is not None and stream is not None:
+            stream.wait_stream(owner)
+        self.fresh = False
+        self.d_raw[:self.used].copy_(self.h_raw[:self.used], non_blocking=True)
+        ev = torch.cuda.Event()
+        ev.record(stream if stream is not None else torch.cuda.current_stream(self.ctx.device))
+        self.h2d_done = ev
+        return ev
+
+    def to_network(self, records: Sequence[ResizeJob], d_in: torch.Tensor) -> None:
+        """Per image the bicubic chain from its decoded bytes into its slot of d_in [n][h][w][3], zero padding included, on the current stream."""
+        n, h, w, _ = d_in.shape
+        for i, rec in enumerate(records):
+            steps = _steps(rec)
+            src, pitch = self.d_raw.data_ptr() + self.offsets[i], 3 * rec.raw.shape[1]
+            for k, (ih, iw, oh, ow) in enumerate(steps):
+                if k + 1 < len(steps):   # the uint8 image between two resizes, as the reference has one
+                    self.mid = _grown(self.mid, oh * ow * 3, self.ctx.device)
+                    resample(self.ctx, src, ih, iw, pitch, self.mid.data_ptr(), oh, ow, oh, ow, 3 * ow, BICUBIC)
+                    src, pitch = self.mid.data_ptr(), 3 * ow
+                else:
+                    resample(self.ctx, src, ih, iw, pitch, d_in[i].data_ptr(), oh, ow, h, w, 3 * w, BICUBIC)
+
+    def reserve_results(self, n: int, h: int, w: int, with_stage1: bool) -> None:
+        """Room for every image's result at up to the network's size (a LANCZOS target never exceeds it), before anything is queued."""
+        need = (2 if with_stage1 else 1) * n * h * w * 3
+        self.d_res = _grown(self.d_res, need, self.ctx.device)
+        self.h_res = _grown(self.h_res, self.d_res.numel(), pinned=True)
+
+    def back_to_lq(self, records: Sequence[ResizeJob], d_out: torch.Tensor, first: int) -> List[Optional[torch.Tensor]]:
+        """Behind the network, on the current stream: the valid rectangle of every image of d_out [n][h][w][3] that names a LANCZOS target is
+        resampled into result slot first + i. Returns per image its result as a device tensor [1][th][tw][3], or None (a plain crop)."""
+        n, h, w, _ = d_out.shape
+        res = []
+        for i, rec in enumerate(records):
+            if not rec.geo.lanczos:
+                res.append(None)
+                continue
+            (tw, th), (vh, vw) = rec.geo.lanczos, rec.geo.valid_hw
+            o = (first + i) * h * w * 3
+            dst = self.d_res[o:o + th * tw * 3]
+            resample(self.ctx, d_out[i].data_ptr(), vh, vw, 3 * w, dst.data_ptr(), th, tw, th, tw, 3 * tw, LANCZOS)
+            res.append(dst.view(1, th, tw, 3))
+        return res
+
+    def download(self, results: Sequence[Optional[torch.Tensor]]) -> None:
+        """Asynchronous D2H copies of the given results (views of d_res) into the same places of h_res, on the current stream."""
+        base = self.d_res.data_ptr()
+        for r in results:
+            if r is not None:
+                o = r.data_ptr() - base
+                self.h_res[o:o + r.numel()].copy_(self.d_res[o:o + r.numel()], non_blocking=True)
+
+    def host_result(self, r: torch.Tensor) -> np.ndarray:
+        """The downloaded result (after the copy has completed) as an array the caller owns."""
+        o = r.data_ptr() - self.d_res.data_ptr()
+        return self.h_res[o:o + r.numel()].numpy().reshape(tuple(r.shape[1:])).copy()
