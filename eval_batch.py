@@ -44,6 +44,9 @@ def parse_args():
     ap.add_argument("--device", default="cuda")
     ap.add_argument("--png_encoder", default="host", choices=["host", "gpu"], help="who compresses the PNGs of both output folders: the host (PIL, default) or "
                     "the GPU behind the network (inference.py --png_encoder: lossless, meant for photographs; flat content comes out larger than PIL's)")
+    ap.add_argument("--gt", default=None, help="score both output folders against ground truth on the GPU (inference.py --gt: PSNR-Y / SSIM-Y, the same lookup "
+                    "rules); the ground truth is centre-cropped to --image_size like the input. Writes metrics.csv (metrics.rank<k>.csv with several ranks) into "
+                    "--output and --cond_output and prints both averages")
     ap.add_argument("--workers", type=int, default=-1, help="host threads for decoding / PNG encoding (inference.py --workers)")
     return ap.parse_args()
 
@@ -76,12 +79,29 @@ def main():
 
     caps = Captions(args.caption_dir, m.y, m.y_mask, args.input) if args.caption_dir else None
 
+    reports, truths = None, []
+    if args.gt:
+        from instarevive_amd.metrics import GroundTruth, Report
+        lookup = GroundTruth(args.gt, args.input)
+        name = "metrics.csv" if world == 1 else f"metrics.rank{rank}.csv"
+        reports = (Report(os.path.join(args.output, name)), Report(os.path.join(cond_dir, name)))
+
+    def read(f):
+        crop = center_crop_arr(Image.open(f).convert("RGB"), args.image_size)
+        return (crop, np.ascontiguousarray(center_crop_arr(lookup.load(f), args.image_size))) if reports else (crop, None)
+
     def feed():
         # decode + centre crop run ahead of the GPU on the reader threads, in file order
-        crops = pools.read_ahead(lambda f: center_crop_arr(Image.open(f).convert("RGB"), args.image_size), files)
+        crops = pools.read_ahead(read, files)
         for group in batches:
-            imgs = [next(crops) for _ in group]
+            pairs = [next(crops) for _ in group]
+            imgs = [p[0] for p in pairs]
+            truths.append([p[1] for p in pairs])
             yield (imgs, *caps.batch(group)) if caps else imgs
+
+    def batch_truths():   # in step with feed(): process_stream advances it right after it has drawn a batch
+        while True:
+            yield truths.pop(0)
 
     def save(dst, img):
         os.makedirs(os.path.dirname(dst) or ".", exist_ok=True)
@@ -96,8 +116,14 @@ def main():
 
     results = process_stream(m.model, feed(), "none", args.disable_preprocess_model, False, 512, 448, preprocess_model=m.preprocess_model, vae=m.vae,
                              y=m.y, y_mask=m.y_mask, noise_scheduler=m.noise_scheduler, return_stage1=True,
-                             png=[[(args.image_size, args.image_size)] * len(group) for group in batches] if gpu_png else None, png_wrap=False)
-    for group, (preds, stage1) in zip(batches, results):
+                             png=[[(args.image_size, args.image_size)] * len(group) for group in batches] if gpu_png else None, png_wrap=False,
+                             gt=batch_truths() if reports else None)
+    for group, out in zip(batches, results):
+        preds, stage1 = out[:2]
+        if reports:
+            for rep, folder, scores in zip(reports, (args.output, cond_dir), out[2]):
+                for f, (psnr, ssim) in zip(group, scores):
+                    rep.add(os.path.relpath(out_name(folder, args.input, f), folder), psnr, ssim)
         for f, pred, cond in zip(group, preds, stage1):
             for folder, img in ((args.output, pred), (cond_dir, cond)):
                 pools.write_behind(save, out_name(folder, args.input, f), img)
@@ -106,6 +132,12 @@ def main():
     print(f"[rank {rank}] saved {pools.written} files")
     if gpu_png:
         print(f"[rank {rank}] --png_encoder gpu: 0 of {pools.written} files took the host encoder")
+    if reports:
+        for rep, folder in zip(reports, (args.output, cond_dir)):
+            lines = rep.write()
+            print(f"[rank {rank}] --gt: scored {len(rep.rows)} files of {folder} against {args.gt} -> {rep.path}")
+            for ln in lines:
+                print(ln)
 
 
 if __name__ == "__main__":

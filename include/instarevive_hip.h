@@ -27,7 +27,8 @@ enum { IR_STAGE_SWINIR = 0, IR_STAGE_VAE_ENCODE = 1, IR_STAGE_DIT = 2, IR_STAGE_
        IR_STAGE_CLDM = 7 /* ir_cldm_sample: n, h, w = the LATENT size */, IR_STAGE_CLDM_PIPELINE = 8 /* ir_cldm_pipeline: image size */,
        IR_STAGE_CLIP_TEXT = 9 /* ir_clip_text_encode: n = batch */,
        IR_STAGE_PNG = 10 /* ir_png_encode: n images, h, w = the VALID rectangle vh, vw; depends on the sizes alone (ctx may be NULL) */,
-       IR_STAGE_RESAMPLE = 11 /* ir_resample_u8: n images, h = in_h, w = out_w; depends on the sizes alone (ctx may be NULL) */ };
+       IR_STAGE_RESAMPLE = 11 /* ir_resample_u8: n images, h = in_h, w = out_w; depends on the sizes alone (ctx may be NULL) */,
+       IR_STAGE_METRICS = 12 /* ir_metrics_y: n images, h, w = the compared rectangle; depends on the sizes alone (ctx may be NULL) */ };
 /* ir_pipeline flags */
 enum { IR_FLAG_NO_PREPROCESS = 1, IR_FLAG_TILED = 2, IR_FLAG_FIX_WAVELET = 4, IR_FLAG_FIX_ADAIN = 8,
        /* ir_pipeline only, needs ir_dit_control_configure: run the DiT step with the ControlNet-Half branch, condition latent
@@ -298,6 +299,22 @@ size_t ir_resample_plan_bytes(int in_h, int in_w, int out_h, int out_w, int filt
 int ir_resample_plan(int in_h, int in_w, int out_h, int out_w, int filter, void* host_plan, size_t bytes);
 int ir_resample_u8(ir_ctx* ctx, void* stream, const uint8_t* in, int n, int in_h, int in_w, long in_pitch, uint8_t* out, int out_h, int out_w,
                    int full_h, int full_w, long out_pitch, const void* plan_dev, void* ws, size_t ws_bytes);
+
+/* PSNR-Y and SSIM-Y of results against ground truth on the device (the reference scores saved files on the host: evaluate_img.py:30-57, pyiqa's
+ * `psnr` / `ssim` with test_y_channel=True; tools/evaluate_pairs.py restates them and is the model of this call). Compares the top-left h x w
+ * rectangle of every image of a [n][a_rows][a_pitch] with that of b [n][b_rows][b_pitch] (RGB8, three bytes per pixel) and writes
+ * out[i] = (mse_y, ssim_y) as doubles:
+ *   Y = 16 + 65.481 x_r + 128.553 x_g + 24.966 x_b, x = (double)((float)v / 255.0f) (the model divides in float32 first);
+ *   mse_y = mean((Ya / 255 - Yb / 255)^2) over the rectangle, not rounded; PSNR-Y = 10 log10(1 / (mse_y + 1e-8)) is left to the host;
+ *   ssim_y: Y rounded half-to-even to integers (16 .. 235), 11-tap Gaussian window (sigma 1.5, sum 1), separable, 'valid' extent
+ *   (h - 10) x (w - 10), the maps x, y, x^2, y^2, xy, C1 = 6.5025, C2 = 58.5225, the contrast-structure term clamped at 0, the mean of the map.
+ * Every statistic is fp64; per-workgroup partial sums go through ws and are folded in a fixed order (no floating-point atomics), so a pair
+ * gives the same bits on every call and at every position of a batch. All pointers are device pointers; stream-ordered, no allocation, no
+ * host synchronisation (capturable). ws: 8-byte aligned, ir_workspace_bytes(ctx, IR_STAGE_METRICS, n, h, w, 0, 0, 0) bytes.
+ * Returns -1 (nothing launched) for a null pointer, n < 1, h or w below 11 (the window), h above a_rows or b_rows, a pitch below 3 w, or a
+ * short or misaligned workspace. */
+int ir_metrics_y(ir_ctx* ctx, void* stream, const uint8_t* a, int a_rows, long a_pitch, const uint8_t* b, int b_rows, long b_pitch, int n, int h,
+                 int w, double* out, void* ws, size_t ws_bytes);
 
 /* Single-kernel entry points, exported so tests/ can check every kernel against the oracle through the same ABI. */
 int ir_op_conv(ir_ctx* ctx, void* stream, const uint16_t* in, const uint16_t* wgt, const float* bias, void* out, int n, int h, int w,

@@ -94,6 +94,12 @@ def parse_args() -> Namespace:
                         "reader / writer threads, as the reference does. gpu: the decoded file is uploaded as it is and the device resamples it with Pillow's own "
                         "integer arithmetic - the same pixels in the saved files - so the enlarged image neither costs a reader thread its bicubic nor crosses "
                         "PCIe, and with --png_encoder gpu every file is encoded on the device. --show_lq, --use_center_crop and --shard_tiles keep the host path")
+    parser.add_argument("--gt", type=str, default=None, help="score the results against ground truth on the GPU (PSNR-Y / SSIM-Y by the definitions of "
+                        "tools/evaluate_pairs.py, i.e. pyiqa's): DIR/<input-relative path> with any image extension, else DIR/<file stem>.*; a ground truth has the "
+                        "size of the saved result. A file is scored when its saved image is the device's image - a plain crop of the prediction, and every file "
+                        "under --resize gpu; the run says how many were not (inputs the host enlarged, --show_lq). Not offered with --shard_tiles")
+    parser.add_argument("--metrics_out", type=str, default=None, help="with --gt: the CSV of per-file scores (file,psnr_y,ssim_y); default <output>/metrics.csv, "
+                        "metrics.rank<k>.csv with several ranks. Each rank prints the averages of its own files")
     parser.add_argument("--workers", type=int, default=-1, help="host threads that decode / resize the inputs and resize / PNG-encode the results "
                         "around the GPU (PIL releases the GIL there); -1 = this process's CPU share, 0 = everything on the main thread like the reference")
     return parser.parse_args()
@@ -183,6 +189,7 @@ class Job:
     # --resize gpu: lq is the DECODED file (nothing is resized on the host), net_in is None and valid_hw is geo.valid_hw
     geo: object = None         # resample.job_geometry() of the file: resize chain, valid extent, network size, LANCZOS target
     raw: np.ndarray = None     # the decoded file, HWC uint8: what is uploaded
+    gt: np.ndarray = None      # --gt: the ground truth of a job that is scored on the device (png_rect() is not None), HWC uint8 of the saved size
 
 
 def net_shape(job: Job) -> tuple:
@@ -190,7 +197,25 @@ def net_shape(job: Job) -> tuple:
     return job.net_in.shape if job.geo is None else tuple(job.geo.net_hw) + (3,)
 
 
+def attach_gt(job: Job, args: Namespace) -> Job:
+    """--gt: decode the ground truth of a job whose saved image is the device's image (png_rect), next to the input on the reader thread."""
+    lookup = getattr(args, "gt_lookup", None)
+    rect = png_rect(job, args) if lookup is not None else None
+    if rect is not None:
+        from instarevive_amd.metrics import MetricsError
+        path = lookup.path(job.src)
+        gt = np.array(Image.open(path).convert("RGB"))
+        if gt.shape[:2] != tuple(rect):
+            raise MetricsError(f"--gt: {path} is {gt.shape[0]} x {gt.shape[1]}, the result of {job.src} is {rect[0]} x {rect[1]}")
+        job.gt = gt
+    return job
+
+
 def read_job(file_path: str, repeat: int, args: Namespace) -> Job:
+    return attach_gt(decode_job(file_path, repeat, args), args)
+
+
+def decode_job(file_path: str, repeat: int, args: Namespace) -> Job:
     from instarevive_amd.utils import auto_resize, center_crop_arr, get_file_name_parts, pad
     lq = Image.open(file_path).convert("RGB")
     if getattr(args, "resize_on_gpu", False):   # decode only: the sizes are worked out here, the pixels are resampled on the device
@@ -381,6 +406,13 @@ def main() -> None:
         ctx.check(ctx.lib.ir_set_fp8_mask(ctx.h, fmask), "ir_set_fp8_mask")
         if fmask == 0:
             print(f"[rank {rank}] fp8: no operand part holds the tolerance on these weights - running bf16 throughout")
+    report = None
+    if args.gt:
+        from instarevive_amd.metrics import GroundTruth, Report
+        if args.shard_tiles:
+            raise SystemExit("--gt is not offered together with --shard_tiles (the assembled frame of the tile-sharded path is not scored on the device)")
+        args.gt_lookup = GroundTruth(args.gt, args.input)
+        report = Report(args.metrics_out or os.path.join(args.output, "metrics.csv" if world == 1 else f"metrics.rank{rank}.csv"))
     local_world = int(os.environ.get("LOCAL_WORLD_SIZE", world))
     if os.environ.get("IR_SWITCH_INTERVAL"):   # experiment knob: how long a worker thread may keep the GIL while the thread that feeds the GPU waits for it
         import sys
@@ -437,10 +469,13 @@ def main() -> None:
     todo: List[List[Job]] = []
     rects = deque()   # --png_encoder gpu, per batch drawn by process_stream: its rectangles, or None for a batch of the host encoder
     records = deque()   # --resize gpu, per batch: the decoded files and their geometry
+    truths = deque()   # --gt, per batch: the ground-truth images, or None for a batch that is not scored
 
     def feed():
-        for group in batches_of(jobs, max(args.batch_size, 1), (lambda j: png_rect(j, args) is not None) if gpu_png else None):
+        for group in batches_of(jobs, max(args.batch_size, 1), (lambda j: png_rect(j, args) is not None) if gpu_png or report else None):
             todo.append(group)
+            if report:
+                truths.append([j.gt for j in group] if all(j.gt is not None for j in group) else None)
             if gpu_png:
                 rr = [png_rect(j, args) for j in group]
                 rects.append(rr if all(rr) else None)
@@ -458,11 +493,23 @@ def main() -> None:
         while True:
             yield records.popleft()
 
+    def batch_truths():
+        while True:
+            yield truths.popleft()
+
     first = None    # (time, files) when the first result left the GPU: what follows is the steady state (no library / workspace warm-up in it)
-    for preds, stage1 in process_stream(m.model, feed(), tiled=args.tiled, return_stage1=args.show_lq and not args.disable_preprocess_model,
-                                        fp8=args.fp8 != "off", png=batch_rects() if gpu_png else None, png_wrap=False,
-                                        resize=batch_records() if args.resize_on_gpu else None, **common):
+    unscored = 0    # --gt: files whose saved image is not the device's image
+    for out in process_stream(m.model, feed(), tiled=args.tiled, return_stage1=args.show_lq and not args.disable_preprocess_model,
+                              fp8=args.fp8 != "off", png=batch_rects() if gpu_png else None, png_wrap=False,
+                              resize=batch_records() if args.resize_on_gpu else None, gt=batch_truths() if report else None, **common):
+        preds, stage1 = out[:2]
         group = todo.pop(0)
+        if report:
+            if len(out) > 2:
+                for job, (psnr, ssim) in zip(group, out[2][0]):
+                    report.add(os.path.relpath(job.save_path, args.output), psnr, ssim)
+            else:
+                unscored += len(group)
         last_result = time.perf_counter()
         if first is None:
             first = (last_result, len(group))
@@ -476,6 +523,14 @@ def main() -> None:
     t1 = time.perf_counter()
     if gpu_png:
         print(f"[rank {rank}] --png_encoder gpu: {host_files} of {pools.written} files took the host encoder (not a plain crop of the prediction)")
+    if report:
+        lines = report.write()
+        print(f"[rank {rank}] --gt: scored {len(report.rows)} files against {args.gt} -> {report.path}")
+        for ln in lines:
+            print(ln)
+        if unscored:
+            print(f"[rank {rank}] --gt: {unscored} of {pools.written} files were not scored (their saved image is not the device's image: an input the host "
+                  f"enlarged, or --show_lq) - use --resize gpu")
     if pools.written:
         # first read submitted -> last PNG closed, model loading excluded (bench.py --cli_files parses this line)
         rest, dt_rest = pools.written - first[1], t1 - first[0]

@@ -24,10 +24,10 @@ SYMBOLS = [
     "ir_tiled_count", "ir_tiled_encode", "ir_tiled_encode_part", "ir_tiled_encode_overflow", "ir_op_conv_up2x2", "ir_op_conv_norm", "ir_op_vae_conv_in", "ir_op_vae_norm_conv_out", "ir_op_conv64", "ir_op_conv64_to3", "ir_tiled_dit", "ir_tiled_blend_latent", "ir_tiled_decode", "ir_tiled_blend_pixels", "ir_set_plain_kernels", "ir_set_fp8", "ir_set_fp8_mask", "ir_attn_fallback_count", "ir_op_conv_fp8", "ir_op_conv_fp8_up", "ir_op_conv_fp8_route", "ir_fp8_features", "ir_op_attention_fp8", "ir_op_attention_d512_fp8",
     "ir_unet_configure", "ir_unet_set_context", "ir_cldm_sample", "ir_cldm_pipeline", "ir_clip_text_configure", "ir_clip_text_encode", "ir_op_groupnorm_any", "ir_op_geglu",
     "ir_dit_set_prompts", "ir_op_attention_kv_groups", "ir_graph_records", "ir_op_vae_segment", "ir_op_vae_segment_ws", "ir_op_vae_segment_info",
-    "ir_png_bound", "ir_png_encode", "ir_resample_plan_bytes", "ir_resample_plan", "ir_resample_u8",
+    "ir_png_bound", "ir_png_encode", "ir_resample_plan_bytes", "ir_resample_plan", "ir_resample_u8", "ir_metrics_y",
 ]
 
-STAGE_SWINIR, STAGE_VAE_ENCODE, STAGE_DIT, STAGE_VAE_DECODE, STAGE_PIPELINE, STAGE_COLORFIX, STAGE_T5, STAGE_CLDM, STAGE_CLDM_PIPELINE, STAGE_CLIP_TEXT, STAGE_PNG, STAGE_RESAMPLE = range(12)
+STAGE_SWINIR, STAGE_VAE_ENCODE, STAGE_DIT, STAGE_VAE_DECODE, STAGE_PIPELINE, STAGE_COLORFIX, STAGE_T5, STAGE_CLDM, STAGE_CLDM_PIPELINE, STAGE_CLIP_TEXT, STAGE_PNG, STAGE_RESAMPLE, STAGE_METRICS = range(13)
 FLAG_NO_PREPROCESS, FLAG_TILED, FLAG_FIX_WAVELET, FLAG_FIX_ADAIN, FLAG_CONTROL_LQ, FLAG_GRAPH, FLAG_FP8 = 1, 2, 4, 8, 16, 32, 64
 # ir_set_fp8_mask (include/instarevive_hip.h): QUALIFIED = the set qualified against the fp32 oracle on flat-softmax weights (>= 46.3 dB at 2048 x
 # 2048: the three attention parts + decoder level-0 / level-2 ResnetBlock convs); DEFAULT (the context's, ABI v3) = the same without the DiT
@@ -154,6 +154,7 @@ def load_library():
     lib.ir_resample_plan_bytes.restype = sz
     lib.ir_resample_plan.argtypes = [i, i, i, i, i, vp, sz]
     lib.ir_resample_u8.argtypes = [vp, vp, vp, i, i, i, C.c_long, vp, i, i, i, i, C.c_long, vp, vp, sz]
+    lib.ir_metrics_y.argtypes = [vp, vp, vp, i, C.c_long, vp, i, C.c_long, i, i, i, vp, vp, sz]
     for name in SYMBOLS:
         fn = getattr(lib, name)
         if fn.restype is C.c_int and name not in ("ir_abi_version",):

@@ -293,6 +293,7 @@ struct ir_ctx {
     int* shard_flag = nullptr;         // device copy of the overflow flag of the last ir_tiled_encode_part(part 0 / 2) (in `owned`)
     int* attn_fb = nullptr;            // ir_attn_fallback_count: [0] attention launches whose fixed-reference kernel raised its overflow flag (in `owned`)
     bool count_fb = false;             // diagnostic: one counting launch behind every flagged attention (off in the product path)
+    double* luma_tab = nullptr;        // ir_metrics_y: the three 256-entry luma tables, filled by ir_init (in `owned`)
 };
 
 namespace {
@@ -1769,6 +1770,21 @@ int ir_init(int device, ir_ctx** out) {
     if (hipSetDevice(device) != hipSuccess) return -3;
     ir_ctx* c = new ir_ctx();
     c->device = device;
+    // ir_metrics_y's luma tables: c_k * (double)((float)v / 255.0f), the float32 division of the host model done once on the host
+    {
+        static const double coef[3] = {65.481, 128.553, 24.966};
+        double tab[3 * 256];
+        for (int k = 0; k < 3; ++k)
+            for (int v = 0; v < 256; ++v) {
+                volatile float x = (float)v / 255.0f;
+                tab[256 * k + v] = coef[k] * (double)x;
+            }
+        void* d = nullptr;
+        if (hipMalloc(&d, sizeof tab) != hipSuccess) { delete c; return -4; }
+        if (hipMemcpy(d, tab, sizeof tab, hipMemcpyHostToDevice) != hipSuccess) { (void)hipFree(d); delete c; return -4; }
+        c->owned.push_back(d);
+        c->luma_tab = static_cast<double*>(d);
+    }
     *out = c;
     return 0;
 }
@@ -2622,7 +2638,30 @@ int ir_resample_u8(ir_ctx* c, void* stream, const uint8_t* in, int n, int in_h, 
     return 0;
 }
 
+// ---------------------------------------------------------------- PSNR-Y / SSIM-Y (metrics.hip)
+// two doubles per tile of the 'valid' SSIM map (at least one tile, so that every size from 1 up has a positive answer)
+static size_t metrics_workspace(int n, int h, int w) {
+    const size_t tx = w > 10 ? ((size_t)w - 10 + IR_METRICS_TW - 1) / IR_METRICS_TW : 1, ty = h > 10 ? ((size_t)h - 10 + IR_METRICS_TH - 1) / IR_METRICS_TH : 1;
+    return ((size_t)n * tx * ty * 2 * sizeof(double) + 255) & ~(size_t)255;
+}
+int ir_metrics_y(ir_ctx* c, void* stream, const uint8_t* a, int a_rows, long a_pitch, const uint8_t* b, int b_rows, long b_pitch, int n, int h, int w,
+                 double* out, void* ws, size_t ws_bytes) {
+    if (!c || !a || !b || !out || !ws) return fail(c, -1, "ir_metrics_y: null argument");
+    if (n < 1 || h < 11 || w < 11 || h > a_rows || h > b_rows || a_pitch < 3L * w || b_pitch < 3L * w)
+        return fail(c, -1, "ir_metrics_y: bad size (n %d, %d x %d in %d rows pitch %ld and %d rows pitch %ld; the window needs 11 x 11)", n, h, w, a_rows, a_pitch,
+                    b_rows, b_pitch);
+    if (ws_bytes < metrics_workspace(n, h, w) || (reinterpret_cast<uintptr_t>(ws) & 7))
+        return fail(c, -1, "ir_metrics_y: workspace too small or unaligned (%zu < %zu)", ws_bytes, metrics_workspace(n, h, w));
+    if (reinterpret_cast<uintptr_t>(out) & 7) return fail(c, -1, "ir_metrics_y: out not aligned to 8 bytes");
+    if (!c->luma_tab) return fail(c, -1, "ir_metrics_y: the context has no luma tables");
+    use_ctx(c);
+    if (ir_launch_metrics_y(a, a_rows, a_pitch, b, b_rows, b_pitch, n, h, w, c->luma_tab, static_cast<double*>(ws), out, (hipStream_t)stream))
+        return fail(c, -100, "ir_metrics_y: launch failed (more than 65535 images or tile rows)");
+    return 0;
+}
+
 size_t ir_workspace_bytes(ir_ctx* c, int stage, int n, int h, int w, int flags, int tile_size, int tile_stride) {
+    if (stage == IR_STAGE_METRICS) return (n < 1 || h < 1 || w < 1) ? 0 : metrics_workspace(n, h, w);   // a function of the sizes alone: no context needed
     if (stage == IR_STAGE_PNG) return (n < 1 || h < 1 || w < 1) ? 0 : png_layout(n, h, w).total;   // a function of the sizes alone: no context needed
     if (stage == IR_STAGE_RESAMPLE) return (n < 1 || h < 1 || w < 1) ? 0 : rs_workspace(n, h, w);    // n images, h = in_h, w = out_w: the uint8 image between the passes
     if (!c) return 0;

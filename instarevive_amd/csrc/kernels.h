@@ -217,6 +217,14 @@ int ir_launch_png_encode(const uint8_t* img, int n, int h, long pitch, int vh, i
 int ir_launch_resample_u8(const uint8_t* in, int n, int in_h, int in_w, long in_pitch, uint8_t* out, int out_h, int out_w, int full_h, int full_w,
                           long out_pitch, const int* plan, uint8_t* inter, long inter_pitch, hipStream_t s);
 
+// ---- PSNR-Y / SSIM-Y of uint8 images (metrics.hip)
+// One workgroup per IR_METRICS_TH x IR_METRICS_TW tile of the 'valid' SSIM map; part: [n][tiles][2] doubles (the tile's squared-error sum and SSIM
+// sum), tab: the three 256-entry luma tables c_k * (double)((float)v / 255.0f) in device memory, out: [n][2] = (mse_y, ssim_y).
+#define IR_METRICS_TW 64
+#define IR_METRICS_TH 16
+int ir_launch_metrics_y(const uint8_t* a, int a_rows, long a_pitch, const uint8_t* b, int b_rows, long b_pitch, int n, int h, int w, const double* tab,
+                        double* part, double* out, hipStream_t s);
+
 // ---- layout / elementwise (elementwise.hip)
 int ir_launch_u8_to_nchw(const uint8_t* in, float* out, int N, int H, int W, hipStream_t s);
 int ir_launch_swin_prep(const float* x_nchw, bf16_t* out, int N, int H, int W, const float* mean3, float img_range, hipStream_t s);

@@ -1,0 +1,265 @@
+"""PSNR-Y and SSIM-Y of results against ground truth on the device (ir_metrics_y, csrc/metrics.hip): what the reference's evaluate_img.py takes
+from pyiqa (`psnr` / `ssim`, test_y_channel=True) and tools/evaluate_pairs.py restates in numpy fp64, computed behind the network from the
+uint8 result that is in device memory anyway, so that scoring a run does not mean decoding its own PNGs again.
+
+queue_scores() puts the call on the current stream, ScoreSlot holds the ground-truth images and the scores of one staging slot (page-locked and
+device side, like resample.ResizeSlot), GroundTruth finds the ground-truth file of an input and Report writes the per-file CSV and the averages
+in evaluate_pairs' format.
+"""
+import ctypes as C
+import math
+import os
+from typing import List, Optional, Sequence, Tuple
+
+import numpy as np
+import torch
+
+from . import _lib as L
+
+WINDOW = 11   # the Gaussian window: images below 11 x 11 have no SSIM (the host model raises, ir_metrics_y refuses)
+
+
+class MetricsError(ValueError):
+    pass
+
+
+def psnr_from_mse(mse: float) -> float:
+    """pyiqa's `psnr` at data_range 1 from the unit-scale MSE ir_metrics_y returns (tools/evaluate_pairs.py::psnr_y)."""
+    return float(10.0 * math.log10(1.0 / (float(mse) + 1e-8)))
+
+
+def ws_bytes(n: int, h: int, w: int) -> int:
+    return int(L.load_library().ir_workspace_bytes(None, L.STAGE_METRICS, n, h, w, 0, 0, 0))
+
+
+def queue_scores(ctx, a: int, a_rows: int, a_pitch: int, b: int, b_rows: int, b_pitch: int, n: int, h: int, w: int, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """ir_metrics_y on the current stream: the top-left h x w of the n images at device address a ([n][a_rows][a_pitch] bytes, RGB8) against
+    those at b. out: a contiguous float64 device tensor of n x 2 values (mse_y, ssim_y) - by default the context's own small buffer, whose
+    page-locked twin fetch_scores() fills. The scratch is the context's workspace (stream-ordered like every other call that uses it; a
+    caller that has handed its address to a later launch grows it first, see pipeline._metrics_workspace)."""
+    if out is None:
+        buf = ctx.__dict__.get("_scores")
+        if buf is None or buf[0].shape[0] < n:
+            cap = max(n, 16)
+            buf = ctx.__dict__["_scores"] = (torch.zeros((cap, 2), dtype=torch.float64, device=ctx.device), torch.zeros((cap, 2), dtype=torch.float64).pin_memory())
+        out = buf[0][:n]
+    if out.dtype != torch.float64 or out.numel() < 2 * n or not out.is_contiguous():
+        raise ValueError("queue_scores: out must be a contiguous float64 tensor of n x 2 values")
+    ws = ctx.workspace(ws_bytes(n, h, w))
+    ctx.check(ctx.lib.ir_metrics_y(ctx.h, ctx.stream(), C.c_void_p(a), a_rows, a_pitch, C.c_void_p(b), b_rows, b_pitch, n, h, w, C.c_void_p(out.data_ptr()),
+                                   L.ptr(ws), ws.numel()), "ir_metrics_y")
+    return out
+
+
+def fetch_scores(ctx, n: int) -> List[Tuple[float, float]]:
+    """The (psnr_y, ssim_y) of the last queue_scores(out=None) of n images: downloads through the page-locked twin and waits for the stream."""
+    dev, host = ctx.__dict__["_scores"]
+    host[:n].copy_(dev[:n], non_blocking=True)
+    torch.cuda.current_stream(ctx.device).synchronize()
+    return [(psnr_from_mse(m), float(s)) for m, s in host[:n].tolist()]
+
+
+def score_arrays(ctx, a: np.ndarray, b: np.ndarray) -> Tuple[float, float]:
+    """(psnr_y, ssim_y) of two HWC uint8 RGB arrays of equal size: upload, one call, wait. For tools and tests; the pipeline scores in place."""
+    a, b = (np.ascontiguousarray(x) for x in (a, b))
+    if a.dtype != np.uint8 or b.dtype != np.uint8 or a.ndim != 3 or a.shape[2] != 3 or a.shape != b.shape:
+        raise MetricsError(f"score_arrays: two HWC uint8 RGB arrays of equal size are needed, got {a.shape} and {b.shape}")
+    h, w = a.shape[:2]
+    if min(h, w) < WINDOW:
+        raise MetricsError("SSIM needs images of at least 11 x 11 pixels")
+    da, db = torch.from_numpy(a).to(ctx.device), torch.from_numpy(b).to(ctx.device)
+    queue_scores(ctx, da.data_ptr(), h, 3 * w, db.data_ptr(), h, 3 * w, 1, h, w)
+    return fetch_scores(ctx, 1)[0]
+
+
+def check_ground_truth(gts: Sequence[np.ndarray], finals: Sequence[Tuple[int, int]], what: str = "gt") -> None:
+    """Every ground-truth image an HWC uint8 RGB array of its image's final size (h, w); ValueError with both sizes otherwise."""
+    if len(gts) != len(finals):
+        raise ValueError(f"{what}: {len(gts)} ground-truth images for a batch of {len(finals)} images")
+    for i, (g, hw) in enumerate(zip(gts, finals)):
+        if not isinstance(g, np.ndarray) or g.dtype != np.uint8 or g.ndim != 3 or g.shape[2] != 3:
+            raise ValueError(f"{what}: ground truth {i} must be an HWC uint8 RGB array")
+        if tuple(g.shape[:2]) != tuple(hw):
+            raise ValueError(f"{what}: ground truth {i} is {g.shape[0]} x {g.shape[1]}, the image's final size is {hw[0]} x {hw[1]}")
+        if min(hw) < WINDOW:
+            raise ValueError(f"{what}: image {i} is {hw[0]} x {hw[1]}; SSIM needs at least 11 x 11 pixels")
+
+
+class ScoreSlot:
+    """Buffers of one staging slot for batches that are scored: the ground-truth images in a flat page-locked buffer and its device copy (images
+    differ in size; the kernel reads bytes, so they are packed without gaps and images of one size form an [n][h][3 w] block), and the scores
+    [count][2] (mse_y, ssim_y) with their page-locked twin. All grow on demand and are reused by the next batch of the slot."""
+
+    def __init__(self, ctx):
+        self.ctx = ctx
+        self.h_gt = self.d_gt = None
+        self.d_scores = self.h_scores = None
+        self.h2d_done = None
+        self.fresh = False
+        self.offsets: List[int] = []
+        self.shapes: List[Tuple[int, int]] = []
+        self.used = 0
+
+    @staticmethod
+    def get(ctx, slot=0, tag="sync") -> "ScoreSlot":
+        pool = ctx.__dict__.setdefault("_score_slots", {})
+        if (tag, slot) not in pool:
+            pool[(tag, slot)] = ScoreSlot(ctx)
+        return pool[(tag, slot)]
+
+    def fill(self, gts: Sequence[np.ndarray]) -> None:
+        """Copy the ground-truth images into the page-locked buffer (after the previous upload out of it has completed)."""
+        from .resample import _grown
+        if self.h2d_done is not None:
+            self.h2d_done.synchronize()
+            self.h2d_done = None
+        self.offsets, self.shapes, at = [], [], 0
+        for g in gts:
+            self.offsets.append(at)
+            self.shapes.append(tuple(g.shape[:2]))
+            at += g.size
+        self.h_gt = _grown(self.h_gt, at, pinned=True)
+        if self.d_gt is None or self.d_gt.numel() < self.h_gt.numel():
+            self.d_gt, self.fresh = _grown(None, self.h_gt.numel(), self.ctx.device), True
+        self.used = at
+        host = self.h_gt.numpy()
+        for g, o in zip(gts, self.offsets):
+            np.copyto(host[o:o + g.size].reshape(g.shape), g)
+        if self.d_scores is None or self.d_scores.shape[0] < 2 * len(gts):
+            cap = max(2 * len(gts), 16)
+            self.d_scores = torch.zeros((cap, 2), dtype=torch.float64, device=self.ctx.device)
+            self.h_scores = torch.zeros((cap, 2), dtype=torch.float64).pin_memory()
+
+    def upload(self, stream=None, owner=None):
+        """Asynchronous H2D copy of the ground truth on `stream` (default: the current one); stream / owner as in ResizeSlot.upload."""
+        if self.fresh and owner is not None and stream is not None:
+            stream.wait_stream(owner)
+        self.fresh = False
+        self.d_gt[:self.used].copy_(self.h_gt[:self.used], non_blocking=True)
+        ev = torch.cuda.Event()
+        ev.record(stream if stream is not None else torch.cuda.current_stream(self.ctx.device))
+        self.h2d_done = ev
+        return ev
+
+    def workspace_bytes(self) -> int:
+        """The largest workspace a call of this batch may need (all images of one size in one call)."""
+        n = len(self.shapes)
+        return max(ws_bytes(n, h, w) for h, w in self.shapes)
+
+    def queue(self, first: int, images: torch.Tensor, results: Optional[Sequence[Optional[torch.Tensor]]] = None) -> None:
+        """Score the images [n][h][w][3] (device uint8: the network's output) against the slot's ground truth into score rows first .. first + n - 1,
+        on the current stream. results[i], when not None, is image i's resized result [1][th][tw][3] and is scored in place of the crop.
+        Consecutive plain crops of one size share a call."""
+        n, h, w, _ = images.shape
+        base = self.d_gt.data_ptr()
+        i = 0
+        while i < n:
+            gh, gw = self.shapes[i]
+            r = results[i] if results is not None else None
+            if r is not None:
+                queue_scores(self.ctx, r.data_ptr(), gh, 3 * gw, base + self.offsets[i], gh, 3 * gw, 1, gh, gw, self.d_scores[first + i:first + i + 1])
+                i += 1
+                continue
+            k = i + 1
+            while k < n and self.shapes[k] == (gh, gw) and (results is None or results[k] is None):
+                k += 1
+            queue_scores(self.ctx, images[i].data_ptr(), h, 3 * w, base + self.offsets[i], gh, 3 * gw, k - i, gh, gw, self.d_scores[first + i:first + k])
+            i = k
+
+    def download(self, count: int) -> None:
+        """Asynchronous D2H copy of the first `count` score rows on the current stream."""
+        self.h_scores[:count].copy_(self.d_scores[:count], non_blocking=True)
+
+    def scores(self, first: int, count: int) -> List[Tuple[float, float]]:
+        """(psnr_y, ssim_y) of rows first .. first + count - 1 after the download has completed."""
+        return [(psnr_from_mse(m), float(s)) for m, s in self.h_scores[first:first + count].tolist()]
+
+
+class GroundTruth:
+    """The ground-truth file of an input, by the rules prompts.caption_file uses for captions: `gt_dir/<path relative to input_root>` with any
+    image extension list_image_files accepts first, then `gt_dir/<file stem>.*` (a flat folder). Unlike a caption, a ground truth is not
+    optional: a missing file and an ambiguous one (two extensions of one stem) raise MetricsError naming the input."""
+
+    def __init__(self, gt_dir: str, input_root: Optional[str] = None):
+        if not os.path.isdir(gt_dir):
+            raise MetricsError(f"--gt {gt_dir} is not a directory")
+        self.gt_dir, self.input_root = gt_dir, input_root
+
+    @staticmethod
+    def _matches(folder: str, stem: str) -> List[str]:
+        from .utils import IMAGE_EXTENSIONS
+        try:
+            names = sorted(os.listdir(folder))
+        except OSError:
+            return []
+        return [os.path.join(folder, nm) for nm in names
+                if os.path.splitext(nm)[0] == stem and os.path.splitext(nm)[1].lower() in IMAGE_EXTENSIONS and os.path.isfile(os.path.join(folder, nm))]
+
+    def path(self, image_path: str) -> str:
+        stem = os.path.splitext(os.path.basename(image_path))[0]
+        folders = []
+        if self.input_root is not None:
+            rel = os.path.relpath(image_path, self.input_root)
+            if not rel.startswith(".."):
+                folders.append(os.path.join(self.gt_dir, os.path.dirname(rel)))
+        if os.path.normpath(self.gt_dir) not in [os.path.normpath(f) for f in folders]:   # a top-level input: both rules name one folder
+            folders.append(self.gt_dir)
+        for folder in folders:
+            found = self._matches(folder, stem)
+            if len(found) > 1:
+                raise MetricsError(f"ground truth of {image_path} is ambiguous: {', '.join(found)}")
+            if found:
+                return found[0]
+        raise MetricsError(f"no ground truth for {image_path} under {self.gt_dir} (looked for {stem}.* with an image extension)")
+
+    def load(self, image_path: str):
+        """The ground truth of an input as a PIL RGB image."""
+        from PIL import Image
+        return Image.open(self.path(image_path)).convert("RGB")
+
+
+class Report:
+    """Per-file scores of a run: one CSV row per file (`file,psnr_y,ssim_y`, the values with every digit) and the averages in evaluate_pairs'
+    format (`psnr: %.5f`, `ssim: %.5f`)."""
+    HEADER = "file,psnr_y,ssim_y"
+
+    def __init__(self, path: Optional[str] = None):
+        self.path, self.rows = path, []
+
+    def add(self, name: str, psnr: float, ssim: float) -> None:
+        self.rows.append((str(name), float(psnr), float(ssim)))
+
+    def averages(self) -> dict:
+        if not self.rows:
+            return {}
+        return {"psnr": sum(r[1] for r in self.rows) / len(self.rows), "ssim": sum(r[2] for r in self.rows) / len(self.rows)}
+
+    def average_lines(self) -> List[str]:
+        return [f"{k}: {v:.5f}" for k, v in self.averages().items()]
+
+    def csv_lines(self) -> List[str]:
+        import csv
+        import io
+        buf = io.StringIO()
+        wr = csv.writer(buf, lineterminator="\n")
+        for name, p, s in sorted(self.rows):
+            wr.writerow([name, repr(p), repr(s)])
+        return [self.HEADER] + buf.getvalue().splitlines()
+
+    def write(self) -> List[str]:
+        """Write the CSV (when the report has a path) and return the average lines."""
+        if self.path:
+            os.makedirs(os.path.dirname(self.path) or ".", exist_ok=True)
+            with open(self.path, "w") as f:
+                f.write("\n".join(self.csv_lines()) + "\n")
+        return self.average_lines()
+
+
+def read_report(path: str) -> dict:
+    """{file: (psnr_y, ssim_y)} of a CSV that Report wrote."""
+    import csv
+    with open(path, newline="") as f:
+        rows = list(csv.reader(f))
+    if not rows or ",".join(rows[0]) != Report.HEADER:
+        raise MetricsError(f"{path}: not a metrics report")
+    return {r[0]: (float(r[1]), float(r[2])) for r in rows[1:]}

@@ -120,6 +120,40 @@ def _resize_results(ctx, rs, records, st, slot, n, h, w, with_stage1, rects, tag
     return res, res1, enc
 
 
+def _score_fill(ctx, slot, tag, gts, n, h, w, rects, records):
+    """The metrics.ScoreSlot of a batch with ground truth, filled on the host - after every ground-truth image has been checked against its image's
+    FINAL size (the LANCZOS target or valid rectangle of a resize batch, the png rectangle, else any size inside the network's output), so a
+    mismatch raises ValueError with both sizes before anything is launched for the batch."""
+    from .metrics import ScoreSlot, check_ground_truth
+    gts = list(gts)
+    if records is not None:
+        finals = [tuple(rec.geo.lanczos[::-1]) if rec.geo.lanczos else tuple(rec.geo.valid_hw) for rec in records]
+    elif rects is not None:
+        finals = [tuple(int(v) for v in r) for r in rects]
+    else:
+        finals = [tuple(np.shape(g)[:2]) for g in gts] if len(gts) == n else [(h, w)] * n
+    check_ground_truth(gts, finals)
+    for i, (gh, gw) in enumerate(finals):
+        if gh > h or gw > w:
+            raise ValueError(f"gt: ground truth {i} is {gh} x {gw}, the network's output is {h} x {w}")
+    sc = ScoreSlot.get(ctx, slot, tag)
+    sc.fill(gts)
+    return sc
+
+
+def _queue_scores(sc, st, slot, n, with_stage1, res=None, res1=None):
+    """ir_metrics_y behind the ir_pipeline (and the LANCZOS calls) of this slot, on the current stream: the predictions into score rows 0 .. n - 1,
+    the stage-1 images (when asked for) into n .. 2n - 1."""
+    sc.queue(0, st.d_out[slot], res)
+    if with_stage1:
+        sc.queue(n, st.d_st1[slot], res1)
+
+
+def _metrics_workspace(ctx, sc):
+    """Grow the context's workspace for the scoring calls BEFORE the pipeline's launch takes its address, like _png_workspace."""
+    ctx.workspace(sc.workspace_bytes())
+
+
 def _resize_arrays(rs, records, res, host):
     """The final arrays of a downloaded resize batch: the resized result, or the valid rectangle of the network's output `host` [n][h][w][3]."""
     return [rs.host_result(r) if r is not None else host[i, :rec.geo.valid_hw[0], :rec.geo.valid_hw[1]].copy() for i, (rec, r) in enumerate(zip(records, res))]
@@ -246,7 +280,7 @@ def _launch_pipeline(ctx, st, slot, n, h, w, flags, tile_size, tile_stride, acp,
 def process(model, control_imgs: List[np.ndarray], strength: float, color_fix_type: str, disable_preprocess_model: bool, tiled: bool,
             tile_size: int, tile_stride: int, preprocess_model=None, vae=None, y=None, y_mask=None, noise_scheduler=None,
             fused: bool = True, graph: bool = False, return_stage1: bool = True, fp8: bool = False, png=None,
-            resize=None) -> Tuple[List[np.ndarray], List[np.ndarray]]:
+            resize=None, gt=None) -> Tuple[List[np.ndarray], List[np.ndarray]]:
     """test_scripts/inference.py:55-166. control_imgs: list of HWC uint8 RGB arrays of equal size (multiples of 64).
     Returns (preds, stage1_preds) as lists of HWC uint8 arrays (stage1_preds is empty with return_stage1=False, which skips its
     conversion and download).
@@ -264,15 +298,20 @@ def process(model, control_imgs: List[np.ndarray], strength: float, color_fix_ty
     the decoded bytes are uploaded, ir_resample_u8 makes the network input on the device (the bicubic chain of --sr_scale / auto_resize, the
     zero pad), and behind ir_pipeline the valid rectangle of every image that auto_resize enlarged is resampled (LANCZOS) back to its LQ size.
     Both lists then hold the FINAL images - what the command line saves: the resized result, else the valid rectangle - bit for bit what
-    PIL gives around a plain call; with png their files (the rectangles are then the final sizes)."""
+    PIL gives around a plain call; with png their files (the rectangles are then the final sizes).
+    gt (fused form only): a list of one ground-truth image per image, HWC uint8 RGB of the image's FINAL size (the png rectangle, the final size
+    of a resize job, else any top-left rectangle of the network's output). ir_metrics_y is queued behind ir_pipeline (and the LANCZOS calls; under
+    graph=True behind the replay) and the call returns a triple (preds, stage1_preds, scores): scores is a pair of lists of (psnr_y, ssim_y), for
+    the predictions and - with return_stage1, else empty - the stage-1 images, by tools/evaluate_pairs.py's definitions. A ground truth of
+    another size raises ValueError before anything is launched."""
     noise_scheduler = noise_scheduler or DDPMScheduler()
     if resize is not None:
         from .resample import ResizeSlot, check_records
         n, h, w = check_records(resize)
     else:
         n, h, w = _check_images(control_imgs)
-    if (png is not None or resize is not None) and not (fused and _fused_ok(model, preprocess_model, vae, disable_preprocess_model)):
-        raise ValueError("process(png=... / resize=...) needs the fused form (instarevive_amd models sharing one context)")
+    if (png is not None or resize is not None or gt is not None) and not (fused and _fused_ok(model, preprocess_model, vae, disable_preprocess_model)):
+        raise ValueError("process(png=... / resize=... / gt=...) needs the fused form (instarevive_amd models sharing one context)")
     device = model.device
     acp = float(noise_scheduler.alphas_cumprod[400])
     sf = float(vae.config.scaling_factor)
@@ -282,6 +321,7 @@ def process(model, control_imgs: List[np.ndarray], strength: float, color_fix_ty
         if fp8 and not vae.__dict__.get("_fp8_uploaded"):
             raise RuntimeError("process(fp8=True): call vae.enable_fp8() first - without the fp8 weight forms every layer would silently run in bf16")
         ctx = model.ctx
+        sc = _score_fill(ctx, 0, "sync", gt, n, h, w, png, resize) if gt is not None else None
         _prepare_fused(model, y, y_mask, h, w, tiled, tile_size, (vae, None if disable_preprocess_model else preprocess_model))
         flags = _pipeline_flags(model, color_fix_type, disable_preprocess_model, tiled) | (L.FLAG_GRAPH if graph else 0) | (L.FLAG_FP8 if fp8 else 0)
         st = _Staging.get(ctx, n, h, w)
@@ -296,30 +336,43 @@ def process(model, control_imgs: List[np.ndarray], strength: float, color_fix_ty
             _resize_workspace(ctx, resize)
         if png is not None:
             _png_workspace(ctx, n, h, w)
+        if sc is not None:
+            sc.upload()
+            _metrics_workspace(ctx, sc)
         if rs is not None:
             rs.to_network(resize, st.d_in[0])
         _launch_pipeline(ctx, st, 0, n, h, w, flags, tile_size, tile_stride, acp, sf, return_stage1)
+        res = res1 = None
         if rs is not None:
             res, res1, enc = _resize_results(ctx, rs, resize, st, 0, n, h, w, return_stage1, png, "sync")
+
+        def scored(preds, stage1):   # after the stream has been waited for
+            if sc is None:
+                return preds, stage1
+            return preds, stage1, (sc.scores(0, n), sc.scores(n, n) if return_stage1 else [])
+
+        if sc is not None:
+            _queue_scores(sc, st, 0, n, return_stage1, res, res1)
+            sc.download(2 * n if return_stage1 else n)
         if png is not None:
             if rs is None:
                 enc = _queue_png(ctx, st, 0, n, h, w, png, return_stage1, "sync")
             enc.fetch_sizes()
             torch.cuda.current_stream(device).synchronize()
             files = enc.fetch(2 * n if return_stage1 else n)
-            return files[:n], files[n:]
+            return scored(files[:n], files[n:])
         st.h_out[0].copy_(st.d_out[0], non_blocking=True)
         if return_stage1:
             st.h_st1[0].copy_(st.d_st1[0], non_blocking=True)
         if rs is not None:
             rs.download(res + res1)
             torch.cuda.current_stream(device).synchronize()
-            return (_resize_arrays(rs, resize, res, st.h_out[0].numpy()),
-                    _resize_arrays(rs, resize, res1, st.h_st1[0].numpy()) if return_stage1 else [])
+            return scored(_resize_arrays(rs, resize, res, st.h_out[0].numpy()),
+                          _resize_arrays(rs, resize, res1, st.h_st1[0].numpy()) if return_stage1 else [])
         torch.cuda.current_stream(device).synchronize()
         preds = st.h_out[0].clone().numpy()   # the caller owns the result; the pinned buffer is reused by the next call
         stage1 = st.h_st1[0].clone().numpy() if return_stage1 else None
-        return [preds[i] for i in range(n)], ([stage1[i] for i in range(n)] if return_stage1 else [])
+        return scored([preds[i] for i in range(n)], ([stage1[i] for i in range(n)] if return_stage1 else []))
 
     imgs = np.ascontiguousarray(np.stack(control_imgs))
     # ---- stage-by-stage form: the reference's literal call sequence on NCHW fp32 tensors
@@ -371,7 +424,7 @@ def _split_batch(b):
 def process_stream(model, batches: Iterable[Sequence[np.ndarray]], color_fix_type: str, disable_preprocess_model: bool, tiled: bool,
                    tile_size: int, tile_stride: int, preprocess_model=None, vae=None, y=None, y_mask=None, noise_scheduler=None,
                    return_stage1: bool = True, graph: bool = False, fp8: bool = False, png=None,
-                   png_wrap: bool = True, resize=None) -> Iterator[Tuple[List[np.ndarray], List[np.ndarray]]]:
+                   png_wrap: bool = True, resize=None, gt=None) -> Iterator[Tuple[List[np.ndarray], List[np.ndarray]]]:
     """process() over a sequence of image batches with the transfers hidden: while batch i computes on the current stream, batch
     i+1 is uploaded and batch i-1 downloaded on a copy stream (two staging slots per batch shape). Yields process()'s result for
     every batch, in order. Needs the fused form (all models instarevive_amd objects on one context). fp8 as in process() (cfg-5:
@@ -390,7 +443,14 @@ def process_stream(model, batches: Iterable[Sequence[np.ndarray]], color_fix_typ
     job_geometry(); images that reach one network size share a batch whatever their own sizes). The batch's image list is then not read. The copy
     stream uploads the decoded bytes, the compute stream runs ir_resample_u8 once or twice per image into the staging input ahead of ir_pipeline
     and, behind it, LANCZOS of the valid rectangles back to the LQ sizes where auto_resize enlarged; the batch's lists hold the final images
-    as in process(resize=...), and with png (the rectangles are then the final sizes) every file of the batch comes from the device encoder."""
+    as in process(resize=...), and with png (the rectangles are then the final sizes) every file of the batch comes from the device encoder.
+    gt: an iterable in step with `batches`, advanced like png / resize: per batch None, or one ground-truth image per image - HWC uint8 RGB of the
+    image's FINAL size (the png rectangle, the final size of a resize job, else any top-left rectangle of the network's output). The copy stream
+    uploads them with the batch, ir_metrics_y is queued behind ir_pipeline and the LANCZOS calls on the compute stream (under graph=True behind the
+    replay, outside the recording) and the scores come back with the batch's download. Such a batch yields a triple (preds, stage1, scores): scores
+    is a pair of lists of (psnr_y, ssim_y), one for the predictions and - with return_stage1, else empty - one for the stage-1 images, by the
+    definitions of tools/evaluate_pairs.py. A batch without ground truth yields the pair. A ground truth of another size raises ValueError before
+    anything is launched for its batch. With png the raw result is still not downloaded."""
     noise_scheduler = noise_scheduler or DDPMScheduler()
     if not _fused_ok(model, preprocess_model, vae, disable_preprocess_model):
         raise TypeError("process_stream needs instarevive_amd models sharing one context")
@@ -403,41 +463,50 @@ def process_stream(model, batches: Iterable[Sequence[np.ndarray]], color_fix_typ
     it = iter(batches)
     png_it = iter(png) if png is not None else None
     resize_it = iter(resize) if resize is not None else None
+    gt_it = iter(gt) if gt is not None else None
     if resize_it is not None:
         from .resample import ResizeSlot, check_records
 
     def upload(batch, slot):
         rects = next(png_it) if png_it is not None else None
         records = next(resize_it) if resize_it is not None else None
+        gts = next(gt_it) if gt_it is not None else None
         imgs, by, bm = _split_batch(batch)
         if records is not None:   # the decoded files travel; the network input is made on the device
             n, h, w = check_records(records)
+            sc = _score_fill(ctx, slot, "stream", gts, n, h, w, rects, records) if gts is not None else None
             st = _Staging.get(ctx, n, h, w, slots=2, tag="stream")
             rs = ResizeSlot.get(ctx, slot, "stream")
             rs.fill(records)
             with torch.cuda.stream(copy):
                 ev = rs.upload(copy, main)
-            return st, slot, (n, h, w), ev, (by, bm), rects, (rs, records)
+                if sc is not None:
+                    ev = sc.upload(copy, main)   # the later event of the copy stream covers both uploads
+            return st, slot, (n, h, w), ev, (by, bm), rects, (rs, records), sc
         n, h, w = _check_images(imgs)
+        sc = _score_fill(ctx, slot, "stream", gts, n, h, w, rects, None) if gts is not None else None
         st = _Staging.get(ctx, n, h, w, slots=2, tag="stream")
         st.fill(slot, imgs)
         with torch.cuda.stream(copy):
             ev = st.upload(slot, copy)
-        return st, slot, (n, h, w), ev, (by, bm), rects, None
+            if sc is not None:
+                ev = sc.upload(copy, main)
+        return st, slot, (n, h, w), ev, (by, bm), rects, None, sc
 
     def download(job):
-        st, slot, (n, h, w), done, enc, rz = job
+        st, slot, (n, h, w), done, enc, rz, sc = job
         done.synchronize()
+        scores = ((sc.scores(0, n), sc.scores(n, n) if return_stage1 else []),) if sc is not None else ()
         if enc is not None:   # the byte counts are here: fetch that many bytes per image
             files = enc.fetch(2 * n if return_stage1 else n, copy, png_wrap)
-            return files[:n], files[n:]
+            return (files[:n], files[n:]) + scores
         if rz is not None:
             rs, records, res, res1 = rz
             return (_resize_arrays(rs, records, res, st.h_out[slot].numpy()),
-                    _resize_arrays(rs, records, res1, st.h_st1[slot].numpy()) if return_stage1 else [])
+                    _resize_arrays(rs, records, res1, st.h_st1[slot].numpy()) if return_stage1 else []) + scores
         preds = st.h_out[slot].clone().numpy()
         stage1 = st.h_st1[slot].clone().numpy() if return_stage1 else None
-        return [preds[i] for i in range(n)], ([stage1[i] for i in range(n)] if return_stage1 else [])
+        return ([preds[i] for i in range(n)], ([stage1[i] for i in range(n)] if return_stage1 else [])) + scores
 
     last_prompt = None   # the host prompts of the last triple batch that were set (a batch with the same ones sets nothing)
 
@@ -463,12 +532,14 @@ def process_stream(model, batches: Iterable[Sequence[np.ndarray]], color_fix_typ
     nxt = next(it, None)
     up = upload(nxt, slot) if nxt is not None else None
     while up is not None:
-        st, cur, (n, h, w), ready, (by, bm), rects, rz = up
+        st, cur, (n, h, w), ready, (by, bm), rects, rz, sc = up
         _prepare_fused(model, y, y_mask, h, w, tiled, tile_size, (vae, None if disable_preprocess_model else preprocess_model), set_prompt=False)
         set_batch_prompt(by, bm, n)
         main.wait_event(ready)
         if rects is not None:
             _png_workspace(ctx, n, h, w)
+        if sc is not None:
+            _metrics_workspace(ctx, sc)
         if rz is not None:
             _resize_workspace(ctx, rz[1])
             rz[0].to_network(rz[1], st.d_in[cur])
@@ -478,6 +549,8 @@ def process_stream(model, batches: Iterable[Sequence[np.ndarray]], color_fix_typ
             rz = rz + (res, res1)
         else:
             enc = _queue_png(ctx, st, cur, n, h, w, rects, return_stage1, "stream") if rects is not None else None
+        if sc is not None:
+            _queue_scores(sc, st, cur, n, return_stage1, rz[2] if rz is not None else None, rz[3] if rz is not None else None)
         computed = torch.cuda.Event()
         computed.record(main)
         # while this batch computes: fetch the previous result, stage the next input into the other slot. The other slot's device
@@ -497,9 +570,11 @@ def process_stream(model, batches: Iterable[Sequence[np.ndarray]], color_fix_typ
                         st.h_st1[cur].copy_(st.d_st1[cur], non_blocking=True)
                 if rz is not None:
                     rz[0].download(rz[2] + rz[3])
+            if sc is not None:
+                sc.download(2 * n if return_stage1 else n)
             done = torch.cuda.Event()
             done.record(copy)
-        pending = (st, cur, (n, h, w), done, enc, rz)
+        pending = (st, cur, (n, h, w), done, enc, rz, sc)
     if pending is not None:
         yield download(pending)
 

@@ -148,7 +148,18 @@ def list_images(folder):
     return sorted(Path(folder).glob("*.[jpJP][pnPN]*[gG]"))
 
 
-def evaluate(in_path, ref_path, ntest=None, log=print, lpips=None):
+def _gpu_scorer():
+    """--backend gpu: PSNR-Y / SSIM-Y of a pair from the device kernel (ir_metrics_y) that follows the definitions above."""
+    import os
+    sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+    import torch
+    from instarevive_amd.metrics import score_arrays
+    from instarevive_amd.models import get_context
+    ctx = get_context(torch.device("cuda", 0))
+    return lambda a8, b8: score_arrays(ctx, a8, b8)
+
+
+def evaluate(in_path, ref_path, ntest=None, log=print, lpips=None, backend="host"):
     from PIL import Image
     ins, refs = list_images(in_path), list_images(ref_path)
     if ntest is not None:
@@ -160,13 +171,20 @@ def evaluate(in_path, ref_path, ntest=None, log=print, lpips=None):
     if lpips is not None:
         import torch
         tot["lpips"] = 0.0
+    score = _gpu_scorer() if backend == "gpu" else None
     for fi, fr in zip(ins, refs):
-        a = np.asarray(Image.open(fi).convert("RGB"), np.float32) / 255.0
-        b = np.asarray(Image.open(fr).convert("RGB"), np.float32) / 255.0
+        a8, b8 = np.asarray(Image.open(fi).convert("RGB")), np.asarray(Image.open(fr).convert("RGB"))
+        a = np.asarray(a8, np.float32) / 255.0
+        b = np.asarray(b8, np.float32) / 255.0
         if a.shape != b.shape:
             raise SystemExit(f"{fi.name} {a.shape} and {fr.name} {b.shape} differ in size")
-        tot["psnr"] += psnr_y(a, b)
-        tot["ssim"] += ssim_y(a, b)
+        if score is not None:
+            p, s = score(a8, b8)
+            tot["psnr"] += p
+            tot["ssim"] += s
+        else:
+            tot["psnr"] += psnr_y(a, b)
+            tot["ssim"] += ssim_y(a, b)
         if lpips is not None:
             tot["lpips"] += float(lpips(torch.from_numpy(a).permute(2, 0, 1)[None], torch.from_numpy(b).permute(2, 0, 1)[None], normalize=True)[0])
     res = {k: v / len(ins) for k, v in tot.items()}
@@ -183,11 +201,13 @@ def main():
     ap.add_argument("--lpips_alexnet", type=str, default=None, help="torchvision AlexNet state dict (alexnet-owt-7be5be79.pth)")
     ap.add_argument("--lpips_lin", type=str, default=None, help="lpips v0.1 linear heads (lpips/weights/v0.1/alex.pth), or a full lpips.LPIPS() state dict")
     ap.add_argument("--device", type=str, default="cpu")
+    ap.add_argument("--backend", type=str, default="host", choices=["host", "gpu"], help="who computes PSNR-Y / SSIM-Y: host (default) = the numpy fp64 "
+                    "definitions of this file; gpu = ir_metrics_y on the MI355X (the same definitions, fp64 statistics; the printed lines are the same)")
     a = ap.parse_args()
     net = LPIPS(a.lpips_alexnet, a.lpips_lin, a.device) if a.lpips_lin else None
     if net is None:
         print("lpips: skipped (no weights given: --lpips_lin [--lpips_alexnet])")
-    evaluate(a.in_path, a.ref_path, a.ntest, lpips=net)
+    evaluate(a.in_path, a.ref_path, a.ntest, lpips=net, backend=a.backend)
 
 
 if __name__ == "__main__":
