@@ -182,7 +182,10 @@ int ir_pipeline(ir_ctx* ctx, void* stream, const uint8_t* in, uint8_t* out, uint
  *   (gather of the pixel tiles into loop order on one rank)
  *   ir_tiled_blend_pixels  that rank: sum in loop order / overlap count -> clamp -> uint8 HWC                                      (:150-161)
  * ir_pipeline with IR_FLAG_TILED is exactly this sequence with first = 0, step = 1, so a sharded run reproduces it bit for bit.
- * ws: at least ir_workspace_bytes(ctx, IR_STAGE_PIPELINE, n, h, w, flags | IR_FLAG_TILED, tile_size, tile_stride). */
+ * ws: at least ir_workspace_bytes(ctx, IR_STAGE_PIPELINE, n, h, w, flags | IR_FLAG_TILED, tile_size, tile_stride).
+ * Tile geometry (in latent pixels, tile_size / 8 and tile_stride / 8): the tile edge even and at most the frame's shorter edge, the stride at
+ * least 1 and at most the tile edge (a larger stride would leave pixels that no window covers, which the blends would divide 0 by 0).
+ * Anything else is refused: ir_tiled_count returns -31, every other entry point -31 with "bad tile geometry" in ir_last_error. */
 int ir_tiled_count(int h, int w, int tile_size, int tile_stride);
 int ir_tiled_encode(ir_ctx* ctx, void* stream, const uint8_t* in, uint8_t* stage1, float* control, float* init, int n, int h, int w, int flags,
                     float scaling_factor, void* ws, size_t ws_bytes);

@@ -1586,13 +1586,15 @@ void colorfix_run(Run& r, int kind, const float* content, const float* style, fl
 // points expose them one by one so that the tiles of ONE image can be sharded over several GPUs: the
 // per-tile results travel (all-gather of latent tiles, gather of pixel tiles) and are accumulated in the canonical tile order on
 // the receiving side, so the sharded result is the single-GPU result bit for bit.
+// Geometry every one of them accepts (tile_geom, ir_tiled_count): tile / 8 even and inside the latent frame, 1 <= stride / 8 <= tile / 8.
 struct TileGeom {
     int tl = 0, sl = 0, tp = 0;                  // tile edge / stride in latent pixels, tile edge in image pixels
     std::vector<std::pair<int, int>> tiles;      // (y, x) latent origin of every tile, in the reference's loop order
 };
 bool tile_geom(Run& r, int lh, int lw, int tile_size, int tile_stride, TileGeom& g) {
     g.tl = tile_size / 8; g.sl = tile_stride / 8; g.tp = g.tl * 8;
-    if (g.tl <= 0 || g.sl <= 0 || g.tl > lh || g.tl > lw || (g.tl & 1)) { r.chk(-31, "bad tile geometry"); return false; }
+    // a stride above the tile would leave pixels that no window covers (count 0: the blend would divide 0 by 0 and write black stripes)
+    if (g.tl <= 0 || g.sl <= 0 || g.sl > g.tl || g.tl > lh || g.tl > lw || (g.tl & 1)) { r.chk(-31, "bad tile geometry"); return false; }
     g.tiles.clear();
     for (int y : starts(lh, g.tl, g.sl))
         for (int x : starts(lw, g.tl, g.sl)) g.tiles.push_back({y, x});
@@ -3023,7 +3025,7 @@ int ir_pipeline(ir_ctx* c, void* stream, const uint8_t* in, uint8_t* out, uint8_
 // ---------------------------------------------------------------- tiled sampling, phase by phase (tile sharding over several GPUs)
 int ir_tiled_count(int h, int w, int tile_size, int tile_stride) {
     const int lh = h / 8, lw = w / 8, tl = tile_size / 8, sl = tile_stride / 8;
-    if (tl <= 0 || sl <= 0 || tl > lh || tl > lw || (tl & 1)) return -31;
+    if (tl <= 0 || sl <= 0 || sl > tl || tl > lh || tl > lw || (tl & 1)) return -31;
     return (int)(starts(lh, tl, sl).size() * starts(lw, tl, sl).size());
 }
 

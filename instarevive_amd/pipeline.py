@@ -374,8 +374,12 @@ def process(model, control_imgs: List[np.ndarray], strength: float, color_fix_ty
         stage1 = st.h_st1[0].clone().numpy() if return_stage1 else None
         return scored([preds[i] for i in range(n)], ([stage1[i] for i in range(n)] if return_stage1 else []))
 
-    imgs = np.ascontiguousarray(np.stack(control_imgs))
     # ---- stage-by-stage form: the reference's literal call sequence on NCHW fp32 tensors
+    if tiled:   # before any network runs: what ir_pipeline refuses with -31 (tile_geom in csrc/api.cpp)
+        tl, sl = tile_size // 8, tile_stride // 8
+        if tl <= 0 or sl <= 0 or sl > tl or tl > min(h, w) // 8 or tl % 2:
+            raise ValueError(f"bad tile geometry for a {h}x{w} image: tile {tile_size}, stride {tile_stride}")
+    imgs = np.ascontiguousarray(np.stack(control_imgs))
     control = torch.tensor(imgs / 255.0, dtype=torch.float32, device=device).clamp_(0, 1).permute(0, 3, 1, 2).contiguous()
     if not disable_preprocess_model:
         control = preprocess_model(control)
@@ -388,7 +392,7 @@ def process(model, control_imgs: List[np.ndarray], strength: float, color_fix_ty
         latents = generate_sample_1step(model, noise_scheduler, init_noise, 400, y, y_mask, c=init_noise if with_c else None)
         img_buffer = vae.decode(latents / sf).sample / 2 + 0.5
     else:
-        wins = _sliding_windows(lh, lw, tile_size // 8, tile_stride // 8)
+        wins = _sliding_windows(lh, lw, tl, sl)
         count = torch.zeros((n, 4, lh, lw), device=device)
         noise_buffer = torch.zeros_like(init_noise)
         for hi, he, wi, we in wins:
