@@ -47,6 +47,9 @@ def parse_args():
     ap.add_argument("--gt", default=None, help="score both output folders against ground truth on the GPU (inference.py --gt: PSNR-Y / SSIM-Y, the same lookup "
                     "rules); the ground truth is centre-cropped to --image_size like the input. Writes metrics.csv (metrics.rank<k>.csv with several ranks) into "
                     "--output and --cond_output and prints both averages")
+    ap.add_argument("--lpips_lin", default=None, help="with --gt: LPIPS (v0.1, alex) on the GPU as a fourth CSV column and a `lpips:` average line "
+                    "(inference.py --lpips_lin: the lpips linear heads, or a full lpips.LPIPS() state dict); --image_size must be at least 31")
+    ap.add_argument("--lpips_alexnet", default=None, help="with --lpips_lin holding the heads alone: torchvision's AlexNet state dict")
     ap.add_argument("--workers", type=int, default=-1, help="host threads for decoding / PNG encoding (inference.py --workers)")
     return ap.parse_args()
 
@@ -80,11 +83,19 @@ def main():
     caps = Captions(args.caption_dir, m.y, m.y_mask, args.input) if args.caption_dir else None
 
     reports, truths = None, []
+    if (args.lpips_lin or args.lpips_alexnet) and not args.gt:
+        raise SystemExit("--lpips_lin / --lpips_alexnet score against ground truth: give --gt as well")
+    if args.lpips_alexnet and not args.lpips_lin:
+        raise SystemExit("--lpips_alexnet needs --lpips_lin (the lpips linear heads)")
+    with_lpips = {"lpips": True} if args.lpips_lin else {}
     if args.gt:
         from instarevive_amd.metrics import GroundTruth, Report
         lookup = GroundTruth(args.gt, args.input)
         name = "metrics.csv" if world == 1 else f"metrics.rank{rank}.csv"
-        reports = (Report(os.path.join(args.output, name)), Report(os.path.join(cond_dir, name)))
+        reports = (Report(os.path.join(args.output, name), **with_lpips), Report(os.path.join(cond_dir, name), **with_lpips))
+        if args.lpips_lin:
+            from instarevive_amd import lpips
+            lpips.configure(m.model.ctx, args.lpips_lin, args.lpips_alexnet)
 
     def read(f):
         crop = center_crop_arr(Image.open(f).convert("RGB"), args.image_size)
@@ -117,13 +128,13 @@ def main():
     results = process_stream(m.model, feed(), "none", args.disable_preprocess_model, False, 512, 448, preprocess_model=m.preprocess_model, vae=m.vae,
                              y=m.y, y_mask=m.y_mask, noise_scheduler=m.noise_scheduler, return_stage1=True,
                              png=[[(args.image_size, args.image_size)] * len(group) for group in batches] if gpu_png else None, png_wrap=False,
-                             gt=batch_truths() if reports else None)
+                             gt=batch_truths() if reports else None, **with_lpips)
     for group, out in zip(batches, results):
         preds, stage1 = out[:2]
         if reports:
             for rep, folder, scores in zip(reports, (args.output, cond_dir), out[2]):
-                for f, (psnr, ssim) in zip(group, scores):
-                    rep.add(os.path.relpath(out_name(folder, args.input, f), folder), psnr, ssim)
+                for f, score in zip(group, scores):
+                    rep.add(os.path.relpath(out_name(folder, args.input, f), folder), *score)
         for f, pred, cond in zip(group, preds, stage1):
             for folder, img in ((args.output, pred), (cond_dir, cond)):
                 pools.write_behind(save, out_name(folder, args.input, f), img)

@@ -28,7 +28,8 @@ enum { IR_STAGE_SWINIR = 0, IR_STAGE_VAE_ENCODE = 1, IR_STAGE_DIT = 2, IR_STAGE_
        IR_STAGE_CLIP_TEXT = 9 /* ir_clip_text_encode: n = batch */,
        IR_STAGE_PNG = 10 /* ir_png_encode: n images, h, w = the VALID rectangle vh, vw; depends on the sizes alone (ctx may be NULL) */,
        IR_STAGE_RESAMPLE = 11 /* ir_resample_u8: n images, h = in_h, w = out_w; depends on the sizes alone (ctx may be NULL) */,
-       IR_STAGE_METRICS = 12 /* ir_metrics_y: n images, h, w = the compared rectangle; depends on the sizes alone (ctx may be NULL) */ };
+       IR_STAGE_METRICS = 12 /* ir_metrics_y: n images, h, w = the compared rectangle; depends on the sizes alone (ctx may be NULL) */,
+       IR_STAGE_LPIPS = 13 /* ir_lpips: n pairs, h, w = the compared rectangle; depends on the sizes alone (ctx may be NULL) */ };
 /* ir_pipeline flags */
 enum { IR_FLAG_NO_PREPROCESS = 1, IR_FLAG_TILED = 2, IR_FLAG_FIX_WAVELET = 4, IR_FLAG_FIX_ADAIN = 8,
        /* ir_pipeline only, needs ir_dit_control_configure: run the DiT step with the ControlNet-Half branch, condition latent
@@ -318,6 +319,32 @@ int ir_resample_u8(ir_ctx* ctx, void* stream, const uint8_t* in, int n, int in_h
  * short or misaligned workspace. */
 int ir_metrics_y(ir_ctx* ctx, void* stream, const uint8_t* a, int a_rows, long a_pitch, const uint8_t* b, int b_rows, long b_pitch, int n, int h,
                  int w, double* out, void* ws, size_t ws_bytes);
+
+/* LPIPS (v0.1, net alex, eval mode) of results against ground truth on the device: the third paired metric of the reference's evaluate_img.py
+ * (:32, pyiqa's copy of lpips.LPIPS(net="alex")); tools/evaluate_pairs.py::LPIPS restates it and is the model of this call. Exact fp32:
+ * the convolutions run on the fp32-input MFMA (a k-ordered fmaf chain per output), the channel norms and the spatial sums in fp64.
+ * ir_lpips_scale_table (host only, no context): tab[c * 256 + v] = the fp32 network input of byte v in channel c, rounded step by step as the
+ * model does: x = (float)v / 255.0f, 2 x - 1, (x - shift_c) / scale_c with shift (-.030, -.088, -.188) and scale (.458, .448, .450).
+ * ir_lpips_configure binds tensors uploaded with ir_upload: `lpips.c{1..5}.w` fp32 [cout][cin][k][k] and `lpips.c{1..5}.b` fp32 [cout]
+ * (torchvision AlexNet's features.0 / .3 / .6 / .8 / .10: 3 -> 64 11x11 s4 p2, 64 -> 192 5x5 p2, 192 -> 384, 384 -> 256, 256 -> 256 3x3 p1) and
+ * `lpips.lin{1..5}` fp32 [cout], and repacks them for the kernels. Returns -2 for a missing tensor or one of another size (ir_last_error
+ * names it).
+ * ir_lpips compares the top-left h x w rectangle of every image of a [n][a_rows][a_pitch] with that of b [n][b_rows][b_pitch] (RGB8, addressed
+ * as ir_metrics_y does) and writes out[i] = the distance of pair i as a double: five conv + ReLU stages (MaxPool2d(3, 2), floor mode, in
+ * front of conv2 and conv3; zero padding is zero in the scaled domain), per stage x / (sqrt(sum_c x^2) + 1e-10) over channels,
+ * sum_c lin_c (a_c - b_c)^2, the mean over that stage's own map; the five means added. Per-workgroup partial sums go through ws and are
+ * folded in a fixed order (no floating-point atomics): a pair gives the same bits on every call and at every position of a batch.
+ * All pointers are device pointers; stream-ordered, no allocation, no host synchronisation (capturable).
+ * ws: 256-byte aligned, ir_workspace_bytes(ctx, IR_STAGE_LPIPS, n, h, w, 0, 0, 0) bytes: the two largest fp32 feature maps of the 2 n images that
+ * are alive at once (conv1's 64 channels at ((h - 7) / 4 + 1) x ((w - 7) / 4 + 1) and the pooled map behind it; no strip-mining: 167 MB for one
+ * 2048 x 2048 pair, 8.3 MB for a 512 x 512 pair) plus one double per 64 output pixels of every stage and pair.
+ * Returns -1 (nothing launched, out untouched) for a null pointer, n < 1, h or w below 31 (the smallest edge at which every stage has a
+ * pixel: 31 -> 7 -> 3 -> 3 -> 1), h above a_rows or b_rows, a pitch below 3 w, or a short or misaligned workspace; -12 when
+ * ir_lpips_configure has not succeeded on this context. */
+int ir_lpips_scale_table(float* tab768);
+int ir_lpips_configure(ir_ctx* ctx);
+int ir_lpips(ir_ctx* ctx, void* stream, const uint8_t* a, int a_rows, long a_pitch, const uint8_t* b, int b_rows, long b_pitch, int n, int h,
+             int w, double* out, void* ws, size_t ws_bytes);
 
 /* Single-kernel entry points, exported so tests/ can check every kernel against the oracle through the same ABI. */
 int ir_op_conv(ir_ctx* ctx, void* stream, const uint16_t* in, const uint16_t* wgt, const float* bias, void* out, int n, int h, int w,

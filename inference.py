@@ -100,6 +100,11 @@ def parse_args() -> Namespace:
                         "under --resize gpu; the run says how many were not (inputs the host enlarged, --show_lq). Not offered with --shard_tiles")
     parser.add_argument("--metrics_out", type=str, default=None, help="with --gt: the CSV of per-file scores (file,psnr_y,ssim_y); default <output>/metrics.csv, "
                         "metrics.rank<k>.csv with several ranks. Each rank prints the averages of its own files")
+    parser.add_argument("--lpips_lin", type=str, default=None, help="with --gt: score LPIPS (v0.1, alex) on the GPU as well (ir_lpips, exact fp32). FILE holds the "
+                        "lpips linear heads (lpips/weights/v0.1/alex.pth) or a full lpips.LPIPS() state dict, as tools/evaluate_pairs.py takes them. The CSV "
+                        "becomes file,psnr_y,ssim_y,lpips and the averages gain `lpips: x.xxxxx`; every scored image needs 31 x 31 pixels")
+    parser.add_argument("--lpips_alexnet", type=str, default=None, help="with --lpips_lin holding the heads alone: torchvision's AlexNet state dict "
+                        "(alexnet-owt-7be5be79.pth)")
     parser.add_argument("--workers", type=int, default=-1, help="host threads that decode / resize the inputs and resize / PNG-encode the results "
                         "around the GPU (PIL releases the GIL there); -1 = this process's CPU share, 0 = everything on the main thread like the reference")
     return parser.parse_args()
@@ -407,12 +412,20 @@ def main() -> None:
         if fmask == 0:
             print(f"[rank {rank}] fp8: no operand part holds the tolerance on these weights - running bf16 throughout")
     report = None
+    if (args.lpips_lin or args.lpips_alexnet) and not args.gt:
+        raise SystemExit("--lpips_lin / --lpips_alexnet score against ground truth: give --gt as well")
+    if args.lpips_alexnet and not args.lpips_lin:
+        raise SystemExit("--lpips_alexnet needs --lpips_lin (the lpips linear heads)")
     if args.gt:
         from instarevive_amd.metrics import GroundTruth, Report
         if args.shard_tiles:
             raise SystemExit("--gt is not offered together with --shard_tiles (the assembled frame of the tile-sharded path is not scored on the device)")
         args.gt_lookup = GroundTruth(args.gt, args.input)
-        report = Report(args.metrics_out or os.path.join(args.output, "metrics.csv" if world == 1 else f"metrics.rank{rank}.csv"))
+        report = Report(args.metrics_out or os.path.join(args.output, "metrics.csv" if world == 1 else f"metrics.rank{rank}.csv"),
+                        **({"lpips": True} if args.lpips_lin else {}))
+        if args.lpips_lin:
+            from instarevive_amd import lpips
+            lpips.configure(m.model.ctx, args.lpips_lin, args.lpips_alexnet)
     local_world = int(os.environ.get("LOCAL_WORLD_SIZE", world))
     if os.environ.get("IR_SWITCH_INTERVAL"):   # experiment knob: how long a worker thread may keep the GIL while the thread that feeds the GPU waits for it
         import sys
@@ -501,13 +514,14 @@ def main() -> None:
     unscored = 0    # --gt: files whose saved image is not the device's image
     for out in process_stream(m.model, feed(), tiled=args.tiled, return_stage1=args.show_lq and not args.disable_preprocess_model,
                               fp8=args.fp8 != "off", png=batch_rects() if gpu_png else None, png_wrap=False,
-                              resize=batch_records() if args.resize_on_gpu else None, gt=batch_truths() if report else None, **common):
+                              resize=batch_records() if args.resize_on_gpu else None, gt=batch_truths() if report else None,
+                              **({"lpips": True} if report and report.lpips else {}), **common):
         preds, stage1 = out[:2]
         group = todo.pop(0)
         if report:
             if len(out) > 2:
-                for job, (psnr, ssim) in zip(group, out[2][0]):
-                    report.add(os.path.relpath(job.save_path, args.output), psnr, ssim)
+                for job, score in zip(group, out[2][0]):
+                    report.add(os.path.relpath(job.save_path, args.output), *score)
             else:
                 unscored += len(group)
         last_result = time.perf_counter()

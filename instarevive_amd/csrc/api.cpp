@@ -294,6 +294,12 @@ struct ir_ctx {
     int* attn_fb = nullptr;            // ir_attn_fallback_count: [0] attention launches whose fixed-reference kernel raised its overflow flag (in `owned`)
     bool count_fb = false;             // diagnostic: one counting launch behind every flagged attention (off in the product path)
     double* luma_tab = nullptr;        // ir_metrics_y: the three 256-entry luma tables, filled by ir_init (in `owned`)
+    // ir_lpips: the scaling table, the repacked conv weights [K padded to 32][cout] and copies of the biases / lin heads (in lpips_owned)
+    struct Lpips {
+        bool ok = false;
+        const float *tab = nullptr, *w[5] = {}, *b[5] = {}, *lin[5] = {};
+    } lpips;
+    std::vector<void*> lpips_owned;
 };
 
 namespace {
@@ -1795,7 +1801,7 @@ void ir_destroy(ir_ctx* c) {
     if (!c) return;
     (void)hipSetDevice(c->device);
     for (auto& kv : c->t) (void)hipFree(kv.second.p);
-    for (std::vector<void*>* l : {&c->owned, &c->dit_tabs, &c->dit_ctrl_tabs, &c->dit_prompt, &c->t5_owned})
+    for (std::vector<void*>* l : {&c->owned, &c->dit_tabs, &c->dit_ctrl_tabs, &c->dit_prompt, &c->t5_owned, &c->lpips_owned})
         for (void* p : *l) (void)hipFree(p);
     for (hipEvent_t e : c->prof.pool) (void)hipEventDestroy(e);
     for (auto& g : c->graphs) (void)hipGraphExecDestroy(g.exec);
@@ -2662,7 +2668,100 @@ int ir_metrics_y(ir_ctx* c, void* stream, const uint8_t* a, int a_rows, long a_p
     return 0;
 }
 
+// ---------------------------------------------------------------- LPIPS (lpips.hip)
+int ir_lpips_scale_table(float* tab) {
+    if (!tab) return -1;
+    static const float shift[3] = {-.030f, -.088f, -.188f}, scale[3] = {.458f, .448f, .450f};
+    for (int ch = 0; ch < 3; ++ch)
+        for (int v = 0; v < 256; ++v) {   // every step rounded to fp32, in the model's order
+            volatile float x = (float)v / 255.0f;
+            volatile float y = 2.0f * x;
+            volatile float z = y - 1.0f;
+            volatile float u = z - shift[ch];
+            tab[256 * ch + v] = u / scale[ch];
+        }
+    return 0;
+}
+
+int ir_lpips_configure(ir_ctx* c) {
+    if (!c) return -1;
+    static const int shape[5][3] = {{3, 64, 11}, {64, 192, 5}, {192, 384, 3}, {384, 256, 3}, {256, 256, 3}};   // cin, cout, k
+    HIPOK(c, hipSetDevice(c->device));
+    c->lpips.ok = false;
+    ir_ctx::Lpips m;
+    const void* src[5];
+    for (int k = 0; k < 5; ++k) {
+        const int cin = shape[k][0], cout = shape[k][1], ks = shape[k][2];
+        const std::string names[3] = {fmt("lpips.c%d.w", k + 1), fmt("lpips.c%d.b", k + 1), fmt("lpips.lin%d", k + 1)};
+        const size_t want[3] = {(size_t)cout * cin * ks * ks * 4, (size_t)cout * 4, (size_t)cout * 4};
+        const void* got[3];
+        for (int i = 0; i < 3; ++i) {
+            auto it = c->t.find(names[i]);
+            if (it == c->t.end()) return fail(c, -2, "ir_lpips_configure: tensor %s (missing)", names[i].c_str());
+            if (it->second.bytes != want[i])
+                return fail(c, -2, "ir_lpips_configure: tensor %s has %zu bytes, AlexNet's has %zu", names[i].c_str(), it->second.bytes, want[i]);
+            got[i] = it->second.p;
+        }
+        src[k] = got[0];
+        m.b[k] = static_cast<const float*>(got[1]);
+        m.lin[k] = static_cast<const float*>(got[2]);
+    }
+    release_list(c->lpips_owned);
+    HIPOK(c, hipDeviceSynchronize());
+    float tab[3 * 256];
+    ir_lpips_scale_table(tab);
+    void* d = nullptr;
+    if (dev_alloc(c, c->lpips_owned, &d, sizeof tab)) return -100;
+    HIPOK(c, hipMemcpy(d, tab, sizeof tab, hipMemcpyHostToDevice));
+    m.tab = static_cast<const float*>(d);
+    for (int k = 0; k < 5; ++k) {   // [cout][cin][ky][kx] -> [(ky, kx, c) padded to 32][cout], zero rows behind K
+        const int cin = shape[k][0], cout = shape[k][1], ks = shape[k][2];
+        const int K = ks * ks * cin, Kp = pad32(K);
+        std::vector<float> w((size_t)cout * K), t((size_t)Kp * cout, 0.f);
+        HIPOK(c, hipMemcpy(w.data(), src[k], w.size() * 4, hipMemcpyDeviceToHost));
+        for (int o = 0; o < cout; ++o)
+            for (int ci = 0; ci < cin; ++ci)
+                for (int ky = 0; ky < ks; ++ky)
+                    for (int kx = 0; kx < ks; ++kx)
+                        t[(size_t)((ky * ks + kx) * cin + ci) * cout + o] = w[(((size_t)o * cin + ci) * ks + ky) * ks + kx];
+        if (dev_alloc(c, c->lpips_owned, &d, t.size() * 4)) return -100;
+        HIPOK(c, hipMemcpy(d, t.data(), t.size() * 4, hipMemcpyHostToDevice));
+        m.w[k] = static_cast<const float*>(d);
+        // copies of the bias and the lin head: the binding does not depend on later uploads under these names
+        for (const float** q : {&m.b[k], &m.lin[k]}) {
+            if (dev_alloc(c, c->lpips_owned, &d, (size_t)cout * 4)) return -100;
+            HIPOK(c, hipMemcpy(d, *q, (size_t)cout * 4, hipMemcpyDeviceToDevice));
+            *q = static_cast<const float*>(d);
+        }
+    }
+    m.ok = true;
+    c->lpips = m;
+    ++c->generation;
+    return 0;
+}
+
+int ir_lpips(ir_ctx* c, void* stream, const uint8_t* a, int a_rows, long a_pitch, const uint8_t* b, int b_rows, long b_pitch, int n, int h, int w,
+             double* out, void* ws, size_t ws_bytes) {
+    if (!c || !a || !b || !out || !ws) return fail(c, -1, "ir_lpips: null argument");
+    if (n < 1 || h < 31 || w < 31 || h > a_rows || h > b_rows || a_pitch < 3L * w || b_pitch < 3L * w)
+        return fail(c, -1, "ir_lpips: bad size (n %d, %d x %d in %d rows pitch %ld and %d rows pitch %ld; AlexNet's five stages need 31 x 31)", n, h, w, a_rows,
+                    a_pitch, b_rows, b_pitch);
+    IrLpipsPlan pl;
+    if (ir_lpips_plan(n, h, w, &pl)) return fail(c, -1, "ir_lpips: n %d of %d x %d is more than one call takes (2^31 output pixels, 65535 pairs)", n, h, w);
+    if (ws_bytes < pl.total || (reinterpret_cast<uintptr_t>(ws) & 255)) return fail(c, -1, "ir_lpips: workspace too small or unaligned (%zu < %zu)", ws_bytes, pl.total);
+    if (reinterpret_cast<uintptr_t>(out) & 7) return fail(c, -1, "ir_lpips: out not aligned to 8 bytes");
+    if (!c->lpips.ok) return fail(c, -12, "ir_lpips: LPIPS not configured (ir_lpips_configure)");
+    use_ctx(c);
+    if (ir_launch_lpips(a, a_rows, a_pitch, b, b_rows, b_pitch, n, h, w, c->lpips.tab, c->lpips.w, c->lpips.b, c->lpips.lin, ws, out, (hipStream_t)stream))
+        return fail(c, -100, "ir_lpips: launch failed");
+    return 0;
+}
+
 size_t ir_workspace_bytes(ir_ctx* c, int stage, int n, int h, int w, int flags, int tile_size, int tile_stride) {
+    if (stage == IR_STAGE_LPIPS) {   // a function of the sizes alone: no context needed
+        IrLpipsPlan pl;
+        return ir_lpips_plan(n, h, w, &pl) ? 0 : pl.total;
+    }
     if (stage == IR_STAGE_METRICS) return (n < 1 || h < 1 || w < 1) ? 0 : metrics_workspace(n, h, w);   // a function of the sizes alone: no context needed
     if (stage == IR_STAGE_PNG) return (n < 1 || h < 1 || w < 1) ? 0 : png_layout(n, h, w).total;   // a function of the sizes alone: no context needed
     if (stage == IR_STAGE_RESAMPLE) return (n < 1 || h < 1 || w < 1) ? 0 : rs_workspace(n, h, w);    // n images, h = in_h, w = out_w: the uint8 image between the passes

@@ -225,6 +225,19 @@ int ir_launch_resample_u8(const uint8_t* in, int n, int in_h, int in_w, long in_
 int ir_launch_metrics_y(const uint8_t* a, int a_rows, long a_pitch, const uint8_t* b, int b_rows, long b_pitch, int n, int h, int w, const double* tab,
                         double* part, double* out, hipStream_t s);
 
+// ---- LPIPS v0.1 / alex of uint8 images (lpips.hip)
+// ir_lpips_plan: the map sizes of a call and its workspace. Conv outputs oh x ow per stage (pool outputs ph x pw in front of conv2 / conv3), two
+// ping-pong NHWC fp32 maps for the 2n images (X: conv1 / conv2 / conv3 / conv5, Y: pool1 / pool2 / conv4) and the distance kernel's partial
+// sums [n][chunks] doubles (stage k's are first[k] .. first[k] + count[k] - 1). -1 below 31 x 31 or when a row count leaves an int.
+struct IrLpipsPlan {
+    int oh[5], ow[5], ph[5], pw[5], first[5], count[5], chunks;
+    size_t x_bytes, y_bytes, part_bytes, total;
+};
+int ir_lpips_plan(int n, int h, int w, IrLpipsPlan* plan);
+// tab: [3][256] fp32 scaling table, wgt[k]: [K padded to 32][cout] fp32 with K in (ky, kx, c) order, bias[k] / lin[k]: [cout]; out: [n] doubles
+int ir_launch_lpips(const uint8_t* a, int a_rows, long a_pitch, const uint8_t* b, int b_rows, long b_pitch, int n, int h, int w, const float* tab,
+                    const float* const* wgt, const float* const* bias, const float* const* lin, void* ws, double* out, hipStream_t s);
+
 // ---- layout / elementwise (elementwise.hip)
 int ir_launch_u8_to_nchw(const uint8_t* in, float* out, int N, int H, int W, hipStream_t s);
 int ir_launch_swin_prep(const float* x_nchw, bf16_t* out, int N, int H, int W, const float* mean3, float img_range, hipStream_t s);

@@ -72,8 +72,9 @@ def score_arrays(ctx, a: np.ndarray, b: np.ndarray) -> Tuple[float, float]:
     return fetch_scores(ctx, 1)[0]
 
 
-def check_ground_truth(gts: Sequence[np.ndarray], finals: Sequence[Tuple[int, int]], what: str = "gt") -> None:
-    """Every ground-truth image an HWC uint8 RGB array of its image's final size (h, w); ValueError with both sizes otherwise."""
+def check_ground_truth(gts: Sequence[np.ndarray], finals: Sequence[Tuple[int, int]], what: str = "gt", min_edge: int = WINDOW) -> None:
+    """Every ground-truth image an HWC uint8 RGB array of its image's final size (h, w); ValueError with both sizes otherwise. min_edge: the
+    smallest edge the scorers take (11 for SSIM's window; 31 when LPIPS is scored as well)."""
     if len(gts) != len(finals):
         raise ValueError(f"{what}: {len(gts)} ground-truth images for a batch of {len(finals)} images")
     for i, (g, hw) in enumerate(zip(gts, finals)):
@@ -83,17 +84,23 @@ def check_ground_truth(gts: Sequence[np.ndarray], finals: Sequence[Tuple[int, in
             raise ValueError(f"{what}: ground truth {i} is {g.shape[0]} x {g.shape[1]}, the image's final size is {hw[0]} x {hw[1]}")
         if min(hw) < WINDOW:
             raise ValueError(f"{what}: image {i} is {hw[0]} x {hw[1]}; SSIM needs at least 11 x 11 pixels")
+        if min(hw) < min_edge:
+            raise ValueError(f"{what}: image {i} is {hw[0]} x {hw[1]}; LPIPS needs at least {min_edge} x {min_edge} pixels")
 
 
 class ScoreSlot:
     """Buffers of one staging slot for batches that are scored: the ground-truth images in a flat page-locked buffer and its device copy (images
     differ in size; the kernel reads bytes, so they are packed without gaps and images of one size form an [n][h][3 w] block), and the scores
-    [count][2] (mse_y, ssim_y) with their page-locked twin. All grow on demand and are reused by the next batch of the slot."""
+    [count][2] (mse_y, ssim_y) with their page-locked twin. All grow on demand and are reused by the next batch of the slot. A batch filled with
+    lpips=True is scored by ir_lpips as well (lpips.py; the context's LPIPS weights must be bound): one more double per row, and scores()
+    yields (psnr_y, ssim_y, lpips) in place of pairs."""
 
     def __init__(self, ctx):
         self.ctx = ctx
         self.h_gt = self.d_gt = None
         self.d_scores = self.h_scores = None
+        self.d_lpips = self.h_lpips = None
+        self.lpips = False
         self.h2d_done = None
         self.fresh = False
         self.offsets: List[int] = []
@@ -107,9 +114,10 @@ class ScoreSlot:
             pool[(tag, slot)] = ScoreSlot(ctx)
         return pool[(tag, slot)]
 
-    def fill(self, gts: Sequence[np.ndarray]) -> None:
+    def fill(self, gts: Sequence[np.ndarray], lpips: bool = False) -> None:
         """Copy the ground-truth images into the page-locked buffer (after the previous upload out of it has completed)."""
         from .resample import _grown
+        self.lpips = bool(lpips)
         if self.h2d_done is not None:
             self.h2d_done.synchronize()
             self.h2d_done = None
@@ -129,6 +137,10 @@ class ScoreSlot:
             cap = max(2 * len(gts), 16)
             self.d_scores = torch.zeros((cap, 2), dtype=torch.float64, device=self.ctx.device)
             self.h_scores = torch.zeros((cap, 2), dtype=torch.float64).pin_memory()
+        if self.lpips and (self.d_lpips is None or self.d_lpips.shape[0] < 2 * len(gts)):
+            cap = max(2 * len(gts), 16)
+            self.d_lpips = torch.zeros((cap,), dtype=torch.float64, device=self.ctx.device)
+            self.h_lpips = torch.zeros((cap,), dtype=torch.float64).pin_memory()
 
     def upload(self, stream=None, owner=None):
         """Asynchronous H2D copy of the ground truth on `stream` (default: the current one); stream / owner as in ResizeSlot.upload."""
@@ -146,6 +158,18 @@ class ScoreSlot:
         n = len(self.shapes)
         return max(ws_bytes(n, h, w) for h, w in self.shapes)
 
+    def lpips_workspace_bytes(self) -> int:
+        """The same for the ir_lpips calls of a batch filled with lpips=True (their scratch is a buffer of its own, lpips.workspace)."""
+        from .lpips import ws_bytes as lpips_ws_bytes
+        n = len(self.shapes)
+        return max(lpips_ws_bytes(n, h, w) for h, w in self.shapes)
+
+    def _score(self, a: int, a_rows: int, a_pitch: int, b: int, gh: int, gw: int, count: int, first: int) -> None:
+        queue_scores(self.ctx, a, a_rows, a_pitch, b, gh, 3 * gw, count, gh, gw, self.d_scores[first:first + count])
+        if self.lpips:
+            from .lpips import queue_lpips
+            queue_lpips(self.ctx, a, a_rows, a_pitch, b, gh, 3 * gw, count, gh, gw, self.d_lpips[first:first + count])
+
     def queue(self, first: int, images: torch.Tensor, results: Optional[Sequence[Optional[torch.Tensor]]] = None) -> None:
         """Score the images [n][h][w][3] (device uint8: the network's output) against the slot's ground truth into score rows first .. first + n - 1,
         on the current stream. results[i], when not None, is image i's resized result [1][th][tw][3] and is scored in place of the crop.
@@ -157,22 +181,28 @@ class ScoreSlot:
             gh, gw = self.shapes[i]
             r = results[i] if results is not None else None
             if r is not None:
-                queue_scores(self.ctx, r.data_ptr(), gh, 3 * gw, base + self.offsets[i], gh, 3 * gw, 1, gh, gw, self.d_scores[first + i:first + i + 1])
+                self._score(r.data_ptr(), gh, 3 * gw, base + self.offsets[i], gh, gw, 1, first + i)
                 i += 1
                 continue
             k = i + 1
             while k < n and self.shapes[k] == (gh, gw) and (results is None or results[k] is None):
                 k += 1
-            queue_scores(self.ctx, images[i].data_ptr(), h, 3 * w, base + self.offsets[i], gh, 3 * gw, k - i, gh, gw, self.d_scores[first + i:first + k])
+            self._score(images[i].data_ptr(), h, 3 * w, base + self.offsets[i], gh, gw, k - i, first + i)
             i = k
 
     def download(self, count: int) -> None:
         """Asynchronous D2H copy of the first `count` score rows on the current stream."""
         self.h_scores[:count].copy_(self.d_scores[:count], non_blocking=True)
+        if self.lpips:
+            self.h_lpips[:count].copy_(self.d_lpips[:count], non_blocking=True)
 
-    def scores(self, first: int, count: int) -> List[Tuple[float, float]]:
-        """(psnr_y, ssim_y) of rows first .. first + count - 1 after the download has completed."""
-        return [(psnr_from_mse(m), float(s)) for m, s in self.h_scores[first:first + count].tolist()]
+    def scores(self, first: int, count: int) -> List[Tuple[float, ...]]:
+        """(psnr_y, ssim_y) of rows first .. first + count - 1 after the download has completed; (psnr_y, ssim_y, lpips) for a batch filled with
+        lpips=True."""
+        pairs = [(psnr_from_mse(m), float(s)) for m, s in self.h_scores[first:first + count].tolist()]
+        if not self.lpips:
+            return pairs
+        return [p + (float(v),) for p, v in zip(pairs, self.h_lpips[first:first + count].tolist())]
 
 
 class GroundTruth:
@@ -220,19 +250,24 @@ class GroundTruth:
 
 class Report:
     """Per-file scores of a run: one CSV row per file (`file,psnr_y,ssim_y`, the values with every digit) and the averages in evaluate_pairs'
-    format (`psnr: %.5f`, `ssim: %.5f`)."""
+    format (`psnr: %.5f`, `ssim: %.5f`). A report made with lpips=True carries LPIPS as well: every add() then takes the third value, the header
+    is `file,psnr_y,ssim_y,lpips` and the averages gain `lpips: %.5f` after `ssim`."""
     HEADER = "file,psnr_y,ssim_y"
+    HEADER_LPIPS = HEADER + ",lpips"
 
-    def __init__(self, path: Optional[str] = None):
-        self.path, self.rows = path, []
+    def __init__(self, path: Optional[str] = None, lpips: bool = False):
+        self.path, self.rows, self.lpips = path, [], bool(lpips)
 
-    def add(self, name: str, psnr: float, ssim: float) -> None:
-        self.rows.append((str(name), float(psnr), float(ssim)))
+    def add(self, name: str, psnr: float, ssim: float, lpips: Optional[float] = None) -> None:
+        if (lpips is not None) != self.lpips:
+            raise MetricsError("Report.add: an LPIPS value is needed by a report made with lpips=True and by no other")
+        self.rows.append((str(name), float(psnr), float(ssim)) + ((float(lpips),) if self.lpips else ()))
 
     def averages(self) -> dict:
         if not self.rows:
             return {}
-        return {"psnr": sum(r[1] for r in self.rows) / len(self.rows), "ssim": sum(r[2] for r in self.rows) / len(self.rows)}
+        keys = ("psnr", "ssim", "lpips")[:3 if self.lpips else 2]
+        return {k: sum(r[i + 1] for r in self.rows) / len(self.rows) for i, k in enumerate(keys)}
 
     def average_lines(self) -> List[str]:
         return [f"{k}: {v:.5f}" for k, v in self.averages().items()]
@@ -242,9 +277,9 @@ class Report:
         import io
         buf = io.StringIO()
         wr = csv.writer(buf, lineterminator="\n")
-        for name, p, s in sorted(self.rows):
-            wr.writerow([name, repr(p), repr(s)])
-        return [self.HEADER] + buf.getvalue().splitlines()
+        for row in sorted(self.rows):
+            wr.writerow([row[0]] + [repr(v) for v in row[1:]])
+        return [self.HEADER_LPIPS if self.lpips else self.HEADER] + buf.getvalue().splitlines()
 
     def write(self) -> List[str]:
         """Write the CSV (when the report has a path) and return the average lines."""
@@ -256,10 +291,10 @@ class Report:
 
 
 def read_report(path: str) -> dict:
-    """{file: (psnr_y, ssim_y)} of a CSV that Report wrote."""
+    """{file: (psnr_y, ssim_y)} of a CSV that Report wrote; {file: (psnr_y, ssim_y, lpips)} of one with the LPIPS column."""
     import csv
     with open(path, newline="") as f:
         rows = list(csv.reader(f))
-    if not rows or ",".join(rows[0]) != Report.HEADER:
+    if not rows or ",".join(rows[0]) not in (Report.HEADER, Report.HEADER_LPIPS):
         raise MetricsError(f"{path}: not a metrics report")
-    return {r[0]: (float(r[1]), float(r[2])) for r in rows[1:]}
+    return {r[0]: tuple(float(v) for v in r[1:len(rows[0])]) for r in rows[1:]}

@@ -120,24 +120,29 @@ def _resize_results(ctx, rs, records, st, slot, n, h, w, with_stage1, rects, tag
     return res, res1, enc
 
 
-def _score_fill(ctx, slot, tag, gts, n, h, w, rects, records):
+def _score_fill(ctx, slot, tag, gts, n, h, w, rects, records, lpips=False):
     """The metrics.ScoreSlot of a batch with ground truth, filled on the host - after every ground-truth image has been checked against its image's
     FINAL size (the LANCZOS target or valid rectangle of a resize batch, the png rectangle, else any size inside the network's output), so a
-    mismatch raises ValueError with both sizes before anything is launched for the batch."""
+    mismatch raises ValueError with both sizes before anything is launched for the batch. lpips: score LPIPS as well (ir_lpips with the
+    weights lpips.configure() bound to the context; every image then needs 31 x 31 pixels)."""
     from .metrics import ScoreSlot, check_ground_truth
     gts = list(gts)
+    if lpips:
+        from .lpips import MIN_EDGE, configured
+        if not configured(ctx):
+            raise ValueError("lpips=True: no LPIPS weights are bound to the context (instarevive_amd.lpips.configure)")
     if records is not None:
         finals = [tuple(rec.geo.lanczos[::-1]) if rec.geo.lanczos else tuple(rec.geo.valid_hw) for rec in records]
     elif rects is not None:
         finals = [tuple(int(v) for v in r) for r in rects]
     else:
         finals = [tuple(np.shape(g)[:2]) for g in gts] if len(gts) == n else [(h, w)] * n
-    check_ground_truth(gts, finals)
+    check_ground_truth(gts, finals, **({"min_edge": MIN_EDGE} if lpips else {}))
     for i, (gh, gw) in enumerate(finals):
         if gh > h or gw > w:
             raise ValueError(f"gt: ground truth {i} is {gh} x {gw}, the network's output is {h} x {w}")
     sc = ScoreSlot.get(ctx, slot, tag)
-    sc.fill(gts)
+    sc.fill(gts, **({"lpips": True} if lpips else {}))
     return sc
 
 
@@ -152,6 +157,9 @@ def _queue_scores(sc, st, slot, n, with_stage1, res=None, res1=None):
 def _metrics_workspace(ctx, sc):
     """Grow the context's workspace for the scoring calls BEFORE the pipeline's launch takes its address, like _png_workspace."""
     ctx.workspace(sc.workspace_bytes())
+    if sc.lpips:
+        from .lpips import workspace as lpips_workspace
+        lpips_workspace(ctx, sc.lpips_workspace_bytes())
 
 
 def _resize_arrays(rs, records, res, host):
@@ -280,7 +288,7 @@ def _launch_pipeline(ctx, st, slot, n, h, w, flags, tile_size, tile_stride, acp,
 def process(model, control_imgs: List[np.ndarray], strength: float, color_fix_type: str, disable_preprocess_model: bool, tiled: bool,
             tile_size: int, tile_stride: int, preprocess_model=None, vae=None, y=None, y_mask=None, noise_scheduler=None,
             fused: bool = True, graph: bool = False, return_stage1: bool = True, fp8: bool = False, png=None,
-            resize=None, gt=None) -> Tuple[List[np.ndarray], List[np.ndarray]]:
+            resize=None, gt=None, lpips: bool = False) -> Tuple[List[np.ndarray], List[np.ndarray]]:
     """test_scripts/inference.py:55-166. control_imgs: list of HWC uint8 RGB arrays of equal size (multiples of 64).
     Returns (preds, stage1_preds) as lists of HWC uint8 arrays (stage1_preds is empty with return_stage1=False, which skips its
     conversion and download).
@@ -303,8 +311,12 @@ def process(model, control_imgs: List[np.ndarray], strength: float, color_fix_ty
     of a resize job, else any top-left rectangle of the network's output). ir_metrics_y is queued behind ir_pipeline (and the LANCZOS calls; under
     graph=True behind the replay) and the call returns a triple (preds, stage1_preds, scores): scores is a pair of lists of (psnr_y, ssim_y), for
     the predictions and - with return_stage1, else empty - the stage-1 images, by tools/evaluate_pairs.py's definitions. A ground truth of
-    another size raises ValueError before anything is launched."""
+    another size raises ValueError before anything is launched.
+    lpips (with gt only): score LPIPS as well - ir_lpips with the weights instarevive_amd.lpips.configure() bound to the models' context, queued
+    behind ir_metrics_y on the same images. Every score is then (psnr_y, ssim_y, lpips); every image needs at least 31 x 31 pixels."""
     noise_scheduler = noise_scheduler or DDPMScheduler()
+    if lpips and gt is None:
+        raise ValueError("process(lpips=True) needs gt=: LPIPS is scored against the ground truth")
     if resize is not None:
         from .resample import ResizeSlot, check_records
         n, h, w = check_records(resize)
@@ -321,7 +333,7 @@ def process(model, control_imgs: List[np.ndarray], strength: float, color_fix_ty
         if fp8 and not vae.__dict__.get("_fp8_uploaded"):
             raise RuntimeError("process(fp8=True): call vae.enable_fp8() first - without the fp8 weight forms every layer would silently run in bf16")
         ctx = model.ctx
-        sc = _score_fill(ctx, 0, "sync", gt, n, h, w, png, resize) if gt is not None else None
+        sc = _score_fill(ctx, 0, "sync", gt, n, h, w, png, resize, lpips) if gt is not None else None
         _prepare_fused(model, y, y_mask, h, w, tiled, tile_size, (vae, None if disable_preprocess_model else preprocess_model))
         flags = _pipeline_flags(model, color_fix_type, disable_preprocess_model, tiled) | (L.FLAG_GRAPH if graph else 0) | (L.FLAG_FP8 if fp8 else 0)
         st = _Staging.get(ctx, n, h, w)
@@ -428,7 +440,7 @@ def _split_batch(b):
 def process_stream(model, batches: Iterable[Sequence[np.ndarray]], color_fix_type: str, disable_preprocess_model: bool, tiled: bool,
                    tile_size: int, tile_stride: int, preprocess_model=None, vae=None, y=None, y_mask=None, noise_scheduler=None,
                    return_stage1: bool = True, graph: bool = False, fp8: bool = False, png=None,
-                   png_wrap: bool = True, resize=None, gt=None) -> Iterator[Tuple[List[np.ndarray], List[np.ndarray]]]:
+                   png_wrap: bool = True, resize=None, gt=None, lpips: bool = False) -> Iterator[Tuple[List[np.ndarray], List[np.ndarray]]]:
     """process() over a sequence of image batches with the transfers hidden: while batch i computes on the current stream, batch
     i+1 is uploaded and batch i-1 downloaded on a copy stream (two staging slots per batch shape). Yields process()'s result for
     every batch, in order. Needs the fused form (all models instarevive_amd objects on one context). fp8 as in process() (cfg-5:
@@ -454,8 +466,11 @@ def process_stream(model, batches: Iterable[Sequence[np.ndarray]], color_fix_typ
     replay, outside the recording) and the scores come back with the batch's download. Such a batch yields a triple (preds, stage1, scores): scores
     is a pair of lists of (psnr_y, ssim_y), one for the predictions and - with return_stage1, else empty - one for the stage-1 images, by the
     definitions of tools/evaluate_pairs.py. A batch without ground truth yields the pair. A ground truth of another size raises ValueError before
-    anything is launched for its batch. With png the raw result is still not downloaded."""
+    anything is launched for its batch. With png the raw result is still not downloaded.
+    lpips (with gt only): as in process() - the scored batches yield (psnr_y, ssim_y, lpips) triples."""
     noise_scheduler = noise_scheduler or DDPMScheduler()
+    if lpips and gt is None:
+        raise ValueError("process_stream(lpips=True) needs gt=: LPIPS is scored against the ground truth")
     if not _fused_ok(model, preprocess_model, vae, disable_preprocess_model):
         raise TypeError("process_stream needs instarevive_amd models sharing one context")
     ctx, device = model.ctx, model.device
@@ -478,7 +493,7 @@ def process_stream(model, batches: Iterable[Sequence[np.ndarray]], color_fix_typ
         imgs, by, bm = _split_batch(batch)
         if records is not None:   # the decoded files travel; the network input is made on the device
             n, h, w = check_records(records)
-            sc = _score_fill(ctx, slot, "stream", gts, n, h, w, rects, records) if gts is not None else None
+            sc = _score_fill(ctx, slot, "stream", gts, n, h, w, rects, records, lpips) if gts is not None else None
             st = _Staging.get(ctx, n, h, w, slots=2, tag="stream")
             rs = ResizeSlot.get(ctx, slot, "stream")
             rs.fill(records)
@@ -488,7 +503,7 @@ def process_stream(model, batches: Iterable[Sequence[np.ndarray]], color_fix_typ
                     ev = sc.upload(copy, main)   # the later event of the copy stream covers both uploads
             return st, slot, (n, h, w), ev, (by, bm), rects, (rs, records), sc
         n, h, w = _check_images(imgs)
-        sc = _score_fill(ctx, slot, "stream", gts, n, h, w, rects, None) if gts is not None else None
+        sc = _score_fill(ctx, slot, "stream", gts, n, h, w, rects, None, lpips) if gts is not None else None
         st = _Staging.get(ctx, n, h, w, slots=2, tag="stream")
         st.fill(slot, imgs)
         with torch.cuda.stream(copy):

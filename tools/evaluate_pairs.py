@@ -159,7 +159,20 @@ def _gpu_scorer():
     return lambda a8, b8: score_arrays(ctx, a8, b8)
 
 
-def evaluate(in_path, ref_path, ntest=None, log=print, lpips=None, backend="host"):
+def _gpu_lpips(alexnet, lin):
+    """--backend gpu with LPIPS weights: the distance of a pair from the device kernel (ir_lpips, exact fp32) in place of the torch model."""
+    import os
+    sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+    import torch
+    from instarevive_amd import lpips as device_lpips
+    from instarevive_amd.models import get_context
+    ctx = get_context(torch.device("cuda", 0))
+    device_lpips.configure(ctx, lin, alexnet)
+    return lambda a8, b8: device_lpips.lpips_arrays(ctx, a8, b8)
+
+
+def evaluate(in_path, ref_path, ntest=None, log=print, lpips=None, backend="host", lpips_u8=None):
+    """lpips: the torch model (img1, img2 in [0, 1]); lpips_u8: a scorer of two HWC uint8 arrays in its place (the device's)."""
     from PIL import Image
     ins, refs = list_images(in_path), list_images(ref_path)
     if ntest is not None:
@@ -168,7 +181,9 @@ def evaluate(in_path, ref_path, ntest=None, log=print, lpips=None, backend="host
         raise SystemExit(f"{len(ins)} images in {in_path}, {len(refs)} in {ref_path}: the folders must pair up (sorted order, as evaluate_img.py)")
     log(f"Find {len(ins)} images in {in_path}")
     tot = {"psnr": 0.0, "ssim": 0.0}
-    if lpips is not None:
+    if lpips_u8 is not None:
+        tot["lpips"] = 0.0
+    elif lpips is not None:
         import torch
         tot["lpips"] = 0.0
     score = _gpu_scorer() if backend == "gpu" else None
@@ -185,7 +200,9 @@ def evaluate(in_path, ref_path, ntest=None, log=print, lpips=None, backend="host
         else:
             tot["psnr"] += psnr_y(a, b)
             tot["ssim"] += ssim_y(a, b)
-        if lpips is not None:
+        if lpips_u8 is not None:
+            tot["lpips"] += float(lpips_u8(a8, b8))
+        elif lpips is not None:
             tot["lpips"] += float(lpips(torch.from_numpy(a).permute(2, 0, 1)[None], torch.from_numpy(b).permute(2, 0, 1)[None], normalize=True)[0])
     res = {k: v / len(ins) for k, v in tot.items()}
     for k, v in res.items():
@@ -202,8 +219,12 @@ def main():
     ap.add_argument("--lpips_lin", type=str, default=None, help="lpips v0.1 linear heads (lpips/weights/v0.1/alex.pth), or a full lpips.LPIPS() state dict")
     ap.add_argument("--device", type=str, default="cpu")
     ap.add_argument("--backend", type=str, default="host", choices=["host", "gpu"], help="who computes PSNR-Y / SSIM-Y: host (default) = the numpy fp64 "
-                    "definitions of this file; gpu = ir_metrics_y on the MI355X (the same definitions, fp64 statistics; the printed lines are the same)")
+                    "definitions of this file; gpu = ir_metrics_y on the MI355X (the same definitions, fp64 statistics; the printed lines are the same) and, with --lpips_lin, "
+                    "LPIPS from ir_lpips (exact fp32 convolutions, fp64 sums: within 1e-6 relative of the torch model, so a last printed digit may differ)")
     a = ap.parse_args()
+    if a.lpips_lin and a.backend == "gpu":
+        evaluate(a.in_path, a.ref_path, a.ntest, backend=a.backend, lpips_u8=_gpu_lpips(a.lpips_alexnet, a.lpips_lin))
+        return
     net = LPIPS(a.lpips_alexnet, a.lpips_lin, a.device) if a.lpips_lin else None
     if net is None:
         print("lpips: skipped (no weights given: --lpips_lin [--lpips_alexnet])")
