@@ -50,6 +50,9 @@ def parse_args():
     ap.add_argument("--lpips_lin", default=None, help="with --gt: LPIPS (v0.1, alex) on the GPU as a fourth CSV column and a `lpips:` average line "
                     "(inference.py --lpips_lin: the lpips linear heads, or a full lpips.LPIPS() state dict); --image_size must be at least 31")
     ap.add_argument("--lpips_alexnet", default=None, help="with --lpips_lin holding the heads alone: torchvision's AlexNet state dict")
+    ap.add_argument("--niqe_params", default=None, help="score NIQE (no reference needed) of both output folders on the GPU (inference.py --niqe_params: "
+                    "niqe_modelparameters.mat or an .npz). Works without --gt: the CSVs are then file,niqe; with --gt the column comes last. --image_size must "
+                    "be at least 192 for two blocks")
     ap.add_argument("--workers", type=int, default=-1, help="host threads for decoding / PNG encoding (inference.py --workers)")
     return ap.parse_args()
 
@@ -66,6 +69,7 @@ def main():
     from instarevive_amd.prompts import Captions
     from instarevive_amd.utils import center_crop_arr, list_image_files
     args = parse_args()
+    niqe_params = cli.load_niqe_params(args)
     cli.check_device(args.device)
     rank, world, local = parallel.init_distributed()
     torch.cuda.set_device(local)
@@ -88,18 +92,20 @@ def main():
     if args.lpips_alexnet and not args.lpips_lin:
         raise SystemExit("--lpips_alexnet needs --lpips_lin (the lpips linear heads)")
     with_lpips = {"lpips": True} if args.lpips_lin else {}
-    if args.gt:
+    with_niqe = {"niqe": True, "paired": bool(args.gt)} if niqe_params else {}
+    lookup = None
+    if args.gt or niqe_params:
         from instarevive_amd.metrics import GroundTruth, Report
-        lookup = GroundTruth(args.gt, args.input)
+        lookup = GroundTruth(args.gt, args.input) if args.gt else None
         name = "metrics.csv" if world == 1 else f"metrics.rank{rank}.csv"
-        reports = (Report(os.path.join(args.output, name), **with_lpips), Report(os.path.join(cond_dir, name), **with_lpips))
+        reports = (Report(os.path.join(args.output, name), **with_lpips, **with_niqe), Report(os.path.join(cond_dir, name), **with_lpips, **with_niqe))
         if args.lpips_lin:
             from instarevive_amd import lpips
             lpips.configure(m.model.ctx, args.lpips_lin, args.lpips_alexnet)
 
     def read(f):
         crop = center_crop_arr(Image.open(f).convert("RGB"), args.image_size)
-        return (crop, np.ascontiguousarray(center_crop_arr(lookup.load(f), args.image_size))) if reports else (crop, None)
+        return (crop, np.ascontiguousarray(center_crop_arr(lookup.load(f), args.image_size))) if lookup else (crop, None)
 
     def feed():
         # decode + centre crop run ahead of the GPU on the reader threads, in file order
@@ -128,13 +134,17 @@ def main():
     results = process_stream(m.model, feed(), "none", args.disable_preprocess_model, False, 512, 448, preprocess_model=m.preprocess_model, vae=m.vae,
                              y=m.y, y_mask=m.y_mask, noise_scheduler=m.noise_scheduler, return_stage1=True,
                              png=[[(args.image_size, args.image_size)] * len(group) for group in batches] if gpu_png else None, png_wrap=False,
-                             gt=batch_truths() if reports else None, **with_lpips)
+                             gt=batch_truths() if lookup else None, **with_lpips, **({"niqe": niqe_params} if niqe_params else {}))
+    no_niqe = 0
     for group, out in zip(batches, results):
         preds, stage1 = out[:2]
         if reports:
             for rep, folder, scores in zip(reports, (args.output, cond_dir), out[2]):
                 for f, score in zip(group, scores):
-                    rep.add(os.path.relpath(out_name(folder, args.input, f), folder), *score)
+                    if niqe_params and score[-1] != score[-1]:   # NaN: the image has no NIQE
+                        no_niqe += 1
+                    else:
+                        rep.add_scores(os.path.relpath(out_name(folder, args.input, f), folder), score)
         for f, pred, cond in zip(group, preds, stage1):
             for folder, img in ((args.output, pred), (cond_dir, cond)):
                 pools.write_behind(save, out_name(folder, args.input, f), img)
@@ -146,9 +156,12 @@ def main():
     if reports:
         for rep, folder in zip(reports, (args.output, cond_dir)):
             lines = rep.write()
-            print(f"[rank {rank}] --gt: scored {len(rep.rows)} files of {folder} against {args.gt} -> {rep.path}")
+            print(f"[rank {rank}] {'--gt' if args.gt else '--niqe_params'}: scored {len(rep.rows)} files of {folder}"
+                  + (f" against {args.gt}" if args.gt else "") + f" -> {rep.path}")
             for ln in lines:
                 print(ln)
+        if no_niqe:
+            print(f"[rank {rank}] --niqe_params: {no_niqe} files were not scored (NIQE needs 96 x 96 blocks and two complete feature rows)")
 
 
 if __name__ == "__main__":

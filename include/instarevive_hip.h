@@ -29,7 +29,8 @@ enum { IR_STAGE_SWINIR = 0, IR_STAGE_VAE_ENCODE = 1, IR_STAGE_DIT = 2, IR_STAGE_
        IR_STAGE_PNG = 10 /* ir_png_encode: n images, h, w = the VALID rectangle vh, vw; depends on the sizes alone (ctx may be NULL) */,
        IR_STAGE_RESAMPLE = 11 /* ir_resample_u8: n images, h = in_h, w = out_w; depends on the sizes alone (ctx may be NULL) */,
        IR_STAGE_METRICS = 12 /* ir_metrics_y: n images, h, w = the compared rectangle; depends on the sizes alone (ctx may be NULL) */,
-       IR_STAGE_LPIPS = 13 /* ir_lpips: n pairs, h, w = the compared rectangle; depends on the sizes alone (ctx may be NULL) */ };
+       IR_STAGE_LPIPS = 13 /* ir_lpips: n pairs, h, w = the compared rectangle; depends on the sizes alone (ctx may be NULL) */,
+       IR_STAGE_NIQE = 14 /* ir_niqe_stats: n images, h, w = the scored rectangle; depends on the sizes alone (ctx may be NULL) */ };
 /* ir_pipeline flags */
 enum { IR_FLAG_NO_PREPROCESS = 1, IR_FLAG_TILED = 2, IR_FLAG_FIX_WAVELET = 4, IR_FLAG_FIX_ADAIN = 8,
        /* ir_pipeline only, needs ir_dit_control_configure: run the DiT step with the ControlNet-Half branch, condition latent
@@ -345,6 +346,27 @@ int ir_lpips_scale_table(float* tab768);
 int ir_lpips_configure(ir_ctx* ctx);
 int ir_lpips(ir_ctx* ctx, void* stream, const uint8_t* a, int a_rows, long a_pitch, const uint8_t* b, int b_rows, long b_pitch, int n, int h,
              int w, double* out, void* ws, size_t ws_bytes);
+
+/* The pixel work of NIQE (the no-reference metric of the reference's evaluate_img.py that is no pretrained network; pyiqa's `niqe` defaults:
+ * Y of YIQ, no border crop, 96 x 96 blocks) on the device; tools/evaluate_niqe.py restates the definition in numpy fp64, down to the order of
+ * additions, and is the model of this call. All arithmetic is fp64 with separate multiplies and adds.
+ * ir_niqe_window (host only, no context): the 49 doubles of the 7 x 7 window exp(-(i^2 + j^2) / (2 (7/6)^2)), entries below eps * max zeroed,
+ * divided by its sum, row-major - the table the kernels use, and the one a host model should read.
+ * ir_niqe_stats scores the top-left (h / 96 * 96) x (w / 96 * 96) rectangle of every image of [n][rows][pitch] bytes (RGB8, addressed as
+ * ir_metrics_y addresses a); nothing outside that rectangle is read. Per image and scale s = 1, 2 (scale 2: MATLAB's antialiased bicubic
+ * imresize(., 0.5) of luma / 255 with symmetric padding, down the columns first, times 255) and per block of (96 / s)^2 pixels, row-major:
+ * mu and m2 as 49-tap sums over the replicate-padded plane from 0.0 in row-major tap order, m = (y - mu) / (sqrt(|m2 - mu mu|) + 1), the five
+ * fields m and m * m shifted by (0,1), (1,0), (1,1), (1,-1) circularly inside the block, and of each field the six numbers count(p < 0),
+ * count(p > 0), sum of p^2 over the negatives, over the positives, sum |p|, sum p^2: out is [n][2][(h / 96) (w / 96)][5][6] doubles. The
+ * asymmetric generalised Gaussian fit and the score are host work (instarevive_amd/niqe.py). A block is summed by one workgroup in a fixed
+ * order (no floating-point atomics): an image gives the same bits on every call and at every position of a batch.
+ * All pointers are device pointers; stream-ordered, no allocation, no host synchronisation (capturable). ws: 8-byte aligned,
+ * ir_workspace_bytes(ctx, IR_STAGE_NIQE, n, h, w, 0, 0, 0) bytes (the half-size fp64 luma planes: 8.4 MB for one 2048 x 2048 image).
+ * Returns -1 (nothing launched, out untouched) for a null pointer, n < 1, h or w below 96, h above rows, a pitch below 3 w, or a short or
+ * misaligned workspace. */
+int ir_niqe_window(double* k49);
+int ir_niqe_stats(ir_ctx* ctx, void* stream, const uint8_t* img, int rows, long pitch, int n, int h, int w, double* out, void* ws,
+                  size_t ws_bytes);
 
 /* Single-kernel entry points, exported so tests/ can check every kernel against the oracle through the same ABI. */
 int ir_op_conv(ir_ctx* ctx, void* stream, const uint16_t* in, const uint16_t* wgt, const float* bias, void* out, int n, int h, int w,

@@ -105,6 +105,11 @@ def parse_args() -> Namespace:
                         "becomes file,psnr_y,ssim_y,lpips and the averages gain `lpips: x.xxxxx`; every scored image needs 31 x 31 pixels")
     parser.add_argument("--lpips_alexnet", type=str, default=None, help="with --lpips_lin holding the heads alone: torchvision's AlexNet state dict "
                         "(alexnet-owt-7be5be79.pth)")
+    parser.add_argument("--niqe_params", type=str, default=None, help="score NIQE, the no-reference metric of the reference's evaluate_img.py that is no "
+                        "pretrained network, on the GPU (ir_niqe_stats; the definition of tools/evaluate_niqe.py, i.e. pyiqa's defaults). FILE holds the pristine "
+                        "parameters mu_prisparam [36] / cov_prisparam [36][36]: pyiqa's niqe_modelparameters.mat, or an .npz. Works without --gt: the CSV is then "
+                        "file,niqe and the average prints as `niqe: x.xxxxx`; with --gt the column and the line come last. Which files are scored follows --gt's "
+                        "rule (the saved image is the device's image); files below 96 pixels on an edge or without two complete feature rows are counted as not scored")
     parser.add_argument("--workers", type=int, default=-1, help="host threads that decode / resize the inputs and resize / PNG-encode the results "
                         "around the GPU (PIL releases the GIL there); -1 = this process's CPU share, 0 = everything on the main thread like the reference")
     return parser.parse_args()
@@ -168,6 +173,19 @@ def host_keeps_up(workers: int, out_pixels: int, compress_level, encoder: str = 
     return (f"host-bound: {workers} encoder threads write ~{host_rate:.1f} files/s of {out_pixels / 1e6:.1f} Mpixel against ~{gpu_rate:.1f} from the GPU - give the rank more "
             f"cores (--workers / $IR_WORKERS), or trade file size for speed with --png_compress_level 1 (same pixels, lossless)"
             + ("" if encoder == "gpu" else ", or encode photographs on the GPU with --png_encoder gpu"))
+
+
+def load_niqe_params(args: Namespace):
+    """--niqe_params: the pristine parameters, read before any model is touched; a file that is missing or holds anything else ends the run."""
+    if not getattr(args, "niqe_params", None):
+        return None
+    from instarevive_amd.niqe import NiqeError, load_params
+    if not os.path.isfile(args.niqe_params):
+        raise SystemExit(f"--niqe_params {args.niqe_params}: no such file")
+    try:
+        return load_params(args.niqe_params)
+    except NiqeError as e:
+        raise SystemExit(str(e))
 
 
 def check_device(device: str) -> str:
@@ -388,6 +406,7 @@ def main() -> None:
     from instarevive_amd.pipeline import HipTileEngine, process_stream
     from instarevive_amd.utils import list_image_files
     args = parse_args()
+    niqe_params = load_niqe_params(args)
     torch.manual_seed(args.seed)  # the path is deterministic; kept for surface compatibility (pl.seed_everything)
     args.device = check_device(args.device)
     rank, world, local = parallel.init_distributed()
@@ -416,13 +435,14 @@ def main() -> None:
         raise SystemExit("--lpips_lin / --lpips_alexnet score against ground truth: give --gt as well")
     if args.lpips_alexnet and not args.lpips_lin:
         raise SystemExit("--lpips_alexnet needs --lpips_lin (the lpips linear heads)")
-    if args.gt:
+    if args.gt or niqe_params:
         from instarevive_amd.metrics import GroundTruth, Report
         if args.shard_tiles:
-            raise SystemExit("--gt is not offered together with --shard_tiles (the assembled frame of the tile-sharded path is not scored on the device)")
-        args.gt_lookup = GroundTruth(args.gt, args.input)
+            raise SystemExit("--gt / --niqe_params are not offered together with --shard_tiles (the assembled frame of the tile-sharded path is not scored on the device)")
+        if args.gt:
+            args.gt_lookup = GroundTruth(args.gt, args.input)
         report = Report(args.metrics_out or os.path.join(args.output, "metrics.csv" if world == 1 else f"metrics.rank{rank}.csv"),
-                        **({"lpips": True} if args.lpips_lin else {}))
+                        **({"lpips": True} if args.lpips_lin else {}), **({"niqe": True, "paired": bool(args.gt)} if niqe_params else {}))
         if args.lpips_lin:
             from instarevive_amd import lpips
             lpips.configure(m.model.ctx, args.lpips_lin, args.lpips_alexnet)
@@ -483,12 +503,16 @@ def main() -> None:
     rects = deque()   # --png_encoder gpu, per batch drawn by process_stream: its rectangles, or None for a batch of the host encoder
     records = deque()   # --resize gpu, per batch: the decoded files and their geometry
     truths = deque()   # --gt, per batch: the ground-truth images, or None for a batch that is not scored
+    sizes = deque()    # --niqe_params, per batch: the saved sizes, or None for a batch that is not scored
 
     def feed():
         for group in batches_of(jobs, max(args.batch_size, 1), (lambda j: png_rect(j, args) is not None) if gpu_png or report else None):
             todo.append(group)
-            if report:
+            if args.gt:
                 truths.append([j.gt for j in group] if all(j.gt is not None for j in group) else None)
+            if niqe_params:
+                rr = [png_rect(j, args) for j in group]
+                sizes.append(rr if all(rr) else None)
             if gpu_png:
                 rr = [png_rect(j, args) for j in group]
                 rects.append(rr if all(rr) else None)
@@ -510,18 +534,27 @@ def main() -> None:
         while True:
             yield truths.popleft()
 
+    def batch_sizes():
+        while True:
+            yield sizes.popleft()
+
     first = None    # (time, files) when the first result left the GPU: what follows is the steady state (no library / workspace warm-up in it)
-    unscored = 0    # --gt: files whose saved image is not the device's image
+    unscored = 0    # --gt / --niqe_params: files whose saved image is not the device's image
+    no_niqe = 0     # --niqe_params: files below 96 pixels on an edge or without two complete feature rows
     for out in process_stream(m.model, feed(), tiled=args.tiled, return_stage1=args.show_lq and not args.disable_preprocess_model,
                               fp8=args.fp8 != "off", png=batch_rects() if gpu_png else None, png_wrap=False,
-                              resize=batch_records() if args.resize_on_gpu else None, gt=batch_truths() if report else None,
-                              **({"lpips": True} if report and report.lpips else {}), **common):
+                              resize=batch_records() if args.resize_on_gpu else None, gt=batch_truths() if args.gt else None,
+                              **({"lpips": True} if report and report.lpips else {}),
+                              **({"niqe": niqe_params, "niqe_rects": batch_sizes()} if niqe_params else {}), **common):
         preds, stage1 = out[:2]
         group = todo.pop(0)
         if report:
             if len(out) > 2:
                 for job, score in zip(group, out[2][0]):
-                    report.add(os.path.relpath(job.save_path, args.output), *score)
+                    if niqe_params and score[-1] != score[-1]:   # NaN: the image has no NIQE
+                        no_niqe += 1
+                    else:
+                        report.add_scores(os.path.relpath(job.save_path, args.output), score)
             else:
                 unscored += len(group)
         last_result = time.perf_counter()
@@ -539,11 +572,14 @@ def main() -> None:
         print(f"[rank {rank}] --png_encoder gpu: {host_files} of {pools.written} files took the host encoder (not a plain crop of the prediction)")
     if report:
         lines = report.write()
-        print(f"[rank {rank}] --gt: scored {len(report.rows)} files against {args.gt} -> {report.path}")
+        what = " / ".join(f for f, on in (("--gt", args.gt), ("--niqe_params", niqe_params)) if on)
+        print(f"[rank {rank}] {what}: scored {len(report.rows)} files" + (f" against {args.gt}" if args.gt else "") + f" -> {report.path}")
         for ln in lines:
             print(ln)
+        if no_niqe:
+            print(f"[rank {rank}] --niqe_params: {no_niqe} of {pools.written} files were not scored (NIQE needs 96 x 96 blocks and two complete feature rows)")
         if unscored:
-            print(f"[rank {rank}] --gt: {unscored} of {pools.written} files were not scored (their saved image is not the device's image: an input the host "
+            print(f"[rank {rank}] {what}: {unscored} of {pools.written} files were not scored (their saved image is not the device's image: an input the host "
                   f"enlarged, or --show_lq) - use --resize gpu")
     if pools.written:
         # first read submitted -> last PNG closed, model loading excluded (bench.py --cli_files parses this line)

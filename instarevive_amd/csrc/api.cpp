@@ -294,6 +294,7 @@ struct ir_ctx {
     int* attn_fb = nullptr;            // ir_attn_fallback_count: [0] attention launches whose fixed-reference kernel raised its overflow flag (in `owned`)
     bool count_fb = false;             // diagnostic: one counting launch behind every flagged attention (off in the product path)
     double* luma_tab = nullptr;        // ir_metrics_y: the three 256-entry luma tables, filled by ir_init (in `owned`)
+    double* niqe_tab = nullptr;        // ir_niqe_stats: three luma tables and v / 255.0, filled by ir_init (in `owned`)
     // ir_lpips: the scaling table, the repacked conv weights [K padded to 32][cout] and copies of the biases / lin heads (in lpips_owned)
     struct Lpips {
         bool ok = false;
@@ -1793,6 +1794,21 @@ int ir_init(int device, ir_ctx** out) {
         c->owned.push_back(d);
         c->luma_tab = static_cast<double*>(d);
     }
+    // ir_niqe_stats' tables: the YIQ luma terms coef_c * (double)((float)v / 255.0f), then v / 255.0 (the unit scale the half-size filter works on)
+    {
+        static const double coef[3] = {0.299, 0.587, 0.114};
+        double tab[4 * 256];
+        for (int v = 0; v < 256; ++v) {
+            volatile float x = (float)v / 255.0f;
+            for (int k = 0; k < 3; ++k) tab[256 * k + v] = coef[k] * (double)x;
+            tab[768 + v] = (double)v / 255.0;
+        }
+        void* d = nullptr;
+        if (hipMalloc(&d, sizeof tab) != hipSuccess) { ir_destroy(c); return -4; }
+        c->owned.push_back(d);
+        if (hipMemcpy(d, tab, sizeof tab, hipMemcpyHostToDevice) != hipSuccess) { ir_destroy(c); return -4; }
+        c->niqe_tab = static_cast<double*>(d);
+    }
     *out = c;
     return 0;
 }
@@ -2757,7 +2773,33 @@ int ir_lpips(ir_ctx* c, void* stream, const uint8_t* a, int a_rows, long a_pitch
     return 0;
 }
 
+// ---------------------------------------------------------------- NIQE's block statistics (niqe.hip)
+// the half-size fp64 luma plane of every image's scored rectangle
+static size_t niqe_workspace(int n, int h, int w) {
+    const size_t H2 = (size_t)(h / IR_NIQE_BLOCK) * (IR_NIQE_BLOCK / 2), W2 = (size_t)(w / IR_NIQE_BLOCK) * (IR_NIQE_BLOCK / 2);
+    return ((size_t)n * H2 * W2 * sizeof(double) + 255) & ~(size_t)255;
+}
+int ir_niqe_window(double* k49) {
+    if (!k49) return -1;
+    ir_niqe_window_host(k49);
+    return 0;
+}
+int ir_niqe_stats(ir_ctx* c, void* stream, const uint8_t* img, int rows, long pitch, int n, int h, int w, double* out, void* ws, size_t ws_bytes) {
+    if (!c || !img || !out || !ws) return fail(c, -1, "ir_niqe_stats: null argument");
+    if (n < 1 || h < IR_NIQE_BLOCK || w < IR_NIQE_BLOCK || h > rows || pitch < 3L * w)
+        return fail(c, -1, "ir_niqe_stats: bad size (n %d, %d x %d in %d rows pitch %ld; a block is 96 x 96)", n, h, w, rows, pitch);
+    if (ws_bytes < niqe_workspace(n, h, w) || (reinterpret_cast<uintptr_t>(ws) & 7))
+        return fail(c, -1, "ir_niqe_stats: workspace too small or unaligned (%zu < %zu)", ws_bytes, niqe_workspace(n, h, w));
+    if (reinterpret_cast<uintptr_t>(out) & 7) return fail(c, -1, "ir_niqe_stats: out not aligned to 8 bytes");
+    if (!c->niqe_tab) return fail(c, -1, "ir_niqe_stats: the context has no luma tables");
+    use_ctx(c);
+    if (ir_launch_niqe_stats(img, rows, pitch, n, h, w, c->niqe_tab, static_cast<double*>(ws), out, (hipStream_t)stream))
+        return fail(c, -100, "ir_niqe_stats: launch failed (more than 65535 images or block rows)");
+    return 0;
+}
+
 size_t ir_workspace_bytes(ir_ctx* c, int stage, int n, int h, int w, int flags, int tile_size, int tile_stride) {
+    if (stage == IR_STAGE_NIQE) return (n < 1 || h < IR_NIQE_BLOCK || w < IR_NIQE_BLOCK) ? 0 : niqe_workspace(n, h, w);   // a function of the sizes alone: no context needed
     if (stage == IR_STAGE_LPIPS) {   // a function of the sizes alone: no context needed
         IrLpipsPlan pl;
         return ir_lpips_plan(n, h, w, &pl) ? 0 : pl.total;

@@ -238,6 +238,14 @@ int ir_lpips_plan(int n, int h, int w, IrLpipsPlan* plan);
 int ir_launch_lpips(const uint8_t* a, int a_rows, long a_pitch, const uint8_t* b, int b_rows, long b_pitch, int n, int h, int w, const float* tab,
                     const float* const* wgt, const float* const* bias, const float* const* lin, void* ws, double* out, hipStream_t s);
 
+// ---- NIQE's block statistics of uint8 images (niqe.hip)
+// One workgroup per IR_NIQE_BLOCK x IR_NIQE_BLOCK block of the top-left (h / 96 * 96) x (w / 96 * 96) rectangle. tab: four 256-entry fp64 tables in
+// device memory - coef_c * (double)((float)v / 255.0f) for 0.299 / 0.587 / 0.114, then v / 255.0; half: [n][H / 2][W / 2] doubles (the half-size
+// luma plane); out: [n][2][blocks][5][6] doubles. ir_niqe_window_host: the 7 x 7 window the kernels use.
+#define IR_NIQE_BLOCK 96
+void ir_niqe_window_host(double* k49);
+int ir_launch_niqe_stats(const uint8_t* img, int rows, long pitch, int n, int h, int w, const double* tab, double* half, double* out, hipStream_t s);
+
 // ---- layout / elementwise (elementwise.hip)
 int ir_launch_u8_to_nchw(const uint8_t* in, float* out, int N, int H, int W, hipStream_t s);
 int ir_launch_swin_prep(const float* x_nchw, bf16_t* out, int N, int H, int W, const float* mean3, float img_range, hipStream_t s);

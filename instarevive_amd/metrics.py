@@ -251,23 +251,42 @@ class GroundTruth:
 class Report:
     """Per-file scores of a run: one CSV row per file (`file,psnr_y,ssim_y`, the values with every digit) and the averages in evaluate_pairs'
     format (`psnr: %.5f`, `ssim: %.5f`). A report made with lpips=True carries LPIPS as well: every add() then takes the third value, the header
-    is `file,psnr_y,ssim_y,lpips` and the averages gain `lpips: %.5f` after `ssim`."""
+    is `file,psnr_y,ssim_y,lpips` and the averages gain `lpips: %.5f` after `ssim`. niqe=True appends the no-reference NIQE (niqe.py) as the last
+    column and the last average line (`niqe: %.5f`); paired=False (a run without ground truth) leaves NIQE alone: `file,niqe`."""
     HEADER = "file,psnr_y,ssim_y"
     HEADER_LPIPS = HEADER + ",lpips"
+    HEADER_NIQE = "file,niqe"
+    HEADERS = (HEADER, HEADER_LPIPS, HEADER + ",niqe", HEADER_LPIPS + ",niqe", HEADER_NIQE)
 
-    def __init__(self, path: Optional[str] = None, lpips: bool = False):
-        self.path, self.rows, self.lpips = path, [], bool(lpips)
+    def __init__(self, path: Optional[str] = None, lpips: bool = False, niqe: bool = False, paired: bool = True):
+        self.path, self.rows, self.lpips, self.niqe, self.paired = path, [], bool(lpips), bool(niqe), bool(paired)
+        if not self.paired and (self.lpips or not self.niqe):
+            raise MetricsError("Report: a report without paired scores carries NIQE and nothing else")
+        self.keys = (("psnr", "ssim") + (("lpips",) if self.lpips else ()) if self.paired else ()) + (("niqe",) if self.niqe else ())
 
-    def add(self, name: str, psnr: float, ssim: float, lpips: Optional[float] = None) -> None:
+    def add(self, name: str, psnr: Optional[float] = None, ssim: Optional[float] = None, lpips: Optional[float] = None, niqe: Optional[float] = None) -> None:
         if (lpips is not None) != self.lpips:
             raise MetricsError("Report.add: an LPIPS value is needed by a report made with lpips=True and by no other")
-        self.rows.append((str(name), float(psnr), float(ssim)) + ((float(lpips),) if self.lpips else ()))
+        if (niqe is not None) != self.niqe:
+            raise MetricsError("Report.add: a NIQE value is needed by a report made with niqe=True and by no other")
+        if (psnr is not None) != self.paired or (ssim is not None) != self.paired:
+            raise MetricsError("Report.add: PSNR and SSIM are needed by a report with paired scores and by no other")
+        given = dict(psnr=psnr, ssim=ssim, lpips=lpips, niqe=niqe)
+        self.rows.append((str(name),) + tuple(float(given[k]) for k in self.keys))
+
+    def add_scores(self, name: str, scores: Sequence[float]) -> None:
+        """add() with the values in the report's own column order: a score tuple of process_stream()."""
+        if len(scores) != len(self.keys):
+            raise MetricsError(f"Report.add_scores: {len(scores)} values for the columns {', '.join(self.keys)}")
+        self.add(name, **dict(zip(self.keys, scores)))
+
+    def header(self) -> str:
+        return ",".join(("file",) + tuple({"psnr": "psnr_y", "ssim": "ssim_y"}.get(k, k) for k in self.keys))
 
     def averages(self) -> dict:
         if not self.rows:
             return {}
-        keys = ("psnr", "ssim", "lpips")[:3 if self.lpips else 2]
-        return {k: sum(r[i + 1] for r in self.rows) / len(self.rows) for i, k in enumerate(keys)}
+        return {k: sum(r[i + 1] for r in self.rows) / len(self.rows) for i, k in enumerate(self.keys)}
 
     def average_lines(self) -> List[str]:
         return [f"{k}: {v:.5f}" for k, v in self.averages().items()]
@@ -279,7 +298,7 @@ class Report:
         wr = csv.writer(buf, lineterminator="\n")
         for row in sorted(self.rows):
             wr.writerow([row[0]] + [repr(v) for v in row[1:]])
-        return [self.HEADER_LPIPS if self.lpips else self.HEADER] + buf.getvalue().splitlines()
+        return [self.header()] + buf.getvalue().splitlines()
 
     def write(self) -> List[str]:
         """Write the CSV (when the report has a path) and return the average lines."""
@@ -291,10 +310,11 @@ class Report:
 
 
 def read_report(path: str) -> dict:
-    """{file: (psnr_y, ssim_y)} of a CSV that Report wrote; {file: (psnr_y, ssim_y, lpips)} of one with the LPIPS column."""
+    """{file: (psnr_y, ssim_y)} of a CSV that Report wrote; {file: (psnr_y, ssim_y, lpips)} of one with the LPIPS column; with the NIQE column
+    that value comes last, and a `file,niqe` report gives {file: (niqe,)}."""
     import csv
     with open(path, newline="") as f:
         rows = list(csv.reader(f))
-    if not rows or ",".join(rows[0]) not in (Report.HEADER, Report.HEADER_LPIPS):
+    if not rows or ",".join(rows[0]) not in Report.HEADERS:
         raise MetricsError(f"{path}: not a metrics report")
     return {r[0]: tuple(float(v) for v in r[1:len(rows[0])]) for r in rows[1:]}

@@ -162,6 +162,48 @@ def _metrics_workspace(ctx, sc):
         lpips_workspace(ctx, sc.lpips_workspace_bytes())
 
 
+def _niqe_plan(ctx, slot, tag, params, n, h, w, rects, records, gts, sizes, with_stage1):
+    """The niqe.NiqeSlot of a batch that is scored without reference, planned on the host: every image's FINAL size - the LANCZOS target or valid
+    rectangle of a resize batch, the png rectangle, else `sizes` (niqe_rects), the ground truth's size, else the network's output."""
+    from .niqe import NiqeSlot
+    if records is not None:
+        finals = [tuple(rec.geo.lanczos[::-1]) if rec.geo.lanczos else tuple(rec.geo.valid_hw) for rec in records]
+    elif rects is not None:
+        finals = [tuple(int(v) for v in r) for r in rects]
+    elif sizes is not None:
+        finals = [tuple(int(v) for v in r) for r in sizes]
+    elif gts is not None:
+        finals = [tuple(np.shape(g)[:2]) for g in gts]
+    else:
+        finals = [(h, w)] * n
+    if len(finals) != n:
+        raise ValueError(f"niqe: {len(finals)} sizes for a batch of {n} images")
+    for i, (fh, fw) in enumerate(finals):
+        if fh < 1 or fw < 1 or (records is None and (fh > h or fw > w)):
+            raise ValueError(f"niqe: image {i} is scored at {fh} x {fw}, the network's output is {h} x {w}")
+    nq = NiqeSlot.get(ctx, slot, tag)
+    nq.plan(finals, params, 2 if with_stage1 else 1)
+    return nq
+
+
+def _queue_niqe(nq, st, slot, n, with_stage1, res=None, res1=None):
+    """ir_niqe_stats behind the ir_pipeline (and the LANCZOS / scoring calls) of this slot, on the current stream: rows as in _queue_scores."""
+    nq.queue(0, st.d_out[slot], res)
+    if with_stage1:
+        nq.queue(n, st.d_st1[slot], res1)
+
+
+def _merged_scores(sc, nq, n, with_stage1):
+    """The scores element of a scored batch: a pair of lists (predictions, stage-1 images or empty) of tuples - the paired scores of `sc`, then
+    (niqe,) of `nq`. The host part of NIQE (the fits and the score) runs here, where the scores are read."""
+    out = []
+    for first, count in ((0, n), (n, n if with_stage1 else 0)):
+        a = sc.scores(first, count) if sc is not None and count else None
+        b = nq.scores(first, count) if nq is not None and count else None
+        out.append([] if not count else (b if a is None else a if b is None else [x + y for x, y in zip(a, b)]))
+    return tuple(out)
+
+
 def _resize_arrays(rs, records, res, host):
     """The final arrays of a downloaded resize batch: the resized result, or the valid rectangle of the network's output `host` [n][h][w][3]."""
     return [rs.host_result(r) if r is not None else host[i, :rec.geo.valid_hw[0], :rec.geo.valid_hw[1]].copy() for i, (rec, r) in enumerate(zip(records, res))]
@@ -288,7 +330,7 @@ def _launch_pipeline(ctx, st, slot, n, h, w, flags, tile_size, tile_stride, acp,
 def process(model, control_imgs: List[np.ndarray], strength: float, color_fix_type: str, disable_preprocess_model: bool, tiled: bool,
             tile_size: int, tile_stride: int, preprocess_model=None, vae=None, y=None, y_mask=None, noise_scheduler=None,
             fused: bool = True, graph: bool = False, return_stage1: bool = True, fp8: bool = False, png=None,
-            resize=None, gt=None, lpips: bool = False) -> Tuple[List[np.ndarray], List[np.ndarray]]:
+            resize=None, gt=None, lpips: bool = False, niqe=None, niqe_rects=None) -> Tuple[List[np.ndarray], List[np.ndarray]]:
     """test_scripts/inference.py:55-166. control_imgs: list of HWC uint8 RGB arrays of equal size (multiples of 64).
     Returns (preds, stage1_preds) as lists of HWC uint8 arrays (stage1_preds is empty with return_stage1=False, which skips its
     conversion and download).
@@ -313,7 +355,12 @@ def process(model, control_imgs: List[np.ndarray], strength: float, color_fix_ty
     the predictions and - with return_stage1, else empty - the stage-1 images, by tools/evaluate_pairs.py's definitions. A ground truth of
     another size raises ValueError before anything is launched.
     lpips (with gt only): score LPIPS as well - ir_lpips with the weights instarevive_amd.lpips.configure() bound to the models' context, queued
-    behind ir_metrics_y on the same images. Every score is then (psnr_y, ssim_y, lpips); every image needs at least 31 x 31 pixels."""
+    behind ir_metrics_y on the same images. Every score is then (psnr_y, ssim_y, lpips); every image needs at least 31 x 31 pixels.
+    niqe (fused form only; with or without gt): the pristine parameters (mu_prisparam, cov_prisparam) of instarevive_amd.niqe.load_params().
+    ir_niqe_stats is queued behind the network (and the paired scores) on every image's FINAL form - the png rectangle, the final size of a resize
+    job, niqe_rects (one (h, w) per image), the ground truth's size, else the whole output - and the fits and the score are computed on the host
+    when the scores are read. Alone, the call returns the triple with scores a pair of lists of (niqe,); with gt the value is appended to each
+    tuple. An image without a score (an edge below 96 pixels, fewer than two complete feature rows) gets NaN."""
     noise_scheduler = noise_scheduler or DDPMScheduler()
     if lpips and gt is None:
         raise ValueError("process(lpips=True) needs gt=: LPIPS is scored against the ground truth")
@@ -322,8 +369,8 @@ def process(model, control_imgs: List[np.ndarray], strength: float, color_fix_ty
         n, h, w = check_records(resize)
     else:
         n, h, w = _check_images(control_imgs)
-    if (png is not None or resize is not None or gt is not None) and not (fused and _fused_ok(model, preprocess_model, vae, disable_preprocess_model)):
-        raise ValueError("process(png=... / resize=... / gt=...) needs the fused form (instarevive_amd models sharing one context)")
+    if (png is not None or resize is not None or gt is not None or niqe is not None) and not (fused and _fused_ok(model, preprocess_model, vae, disable_preprocess_model)):
+        raise ValueError("process(png=... / resize=... / gt=... / niqe=...) needs the fused form (instarevive_amd models sharing one context)")
     device = model.device
     acp = float(noise_scheduler.alphas_cumprod[400])
     sf = float(vae.config.scaling_factor)
@@ -334,6 +381,7 @@ def process(model, control_imgs: List[np.ndarray], strength: float, color_fix_ty
             raise RuntimeError("process(fp8=True): call vae.enable_fp8() first - without the fp8 weight forms every layer would silently run in bf16")
         ctx = model.ctx
         sc = _score_fill(ctx, 0, "sync", gt, n, h, w, png, resize, lpips) if gt is not None else None
+        nq = _niqe_plan(ctx, 0, "sync", niqe, n, h, w, png, resize, gt, niqe_rects, return_stage1) if niqe is not None else None
         _prepare_fused(model, y, y_mask, h, w, tiled, tile_size, (vae, None if disable_preprocess_model else preprocess_model))
         flags = _pipeline_flags(model, color_fix_type, disable_preprocess_model, tiled) | (L.FLAG_GRAPH if graph else 0) | (L.FLAG_FP8 if fp8 else 0)
         st = _Staging.get(ctx, n, h, w)
@@ -351,6 +399,8 @@ def process(model, control_imgs: List[np.ndarray], strength: float, color_fix_ty
         if sc is not None:
             sc.upload()
             _metrics_workspace(ctx, sc)
+        if nq is not None:
+            ctx.workspace(nq.workspace_bytes())
         if rs is not None:
             rs.to_network(resize, st.d_in[0])
         _launch_pipeline(ctx, st, 0, n, h, w, flags, tile_size, tile_stride, acp, sf, return_stage1)
@@ -359,13 +409,16 @@ def process(model, control_imgs: List[np.ndarray], strength: float, color_fix_ty
             res, res1, enc = _resize_results(ctx, rs, resize, st, 0, n, h, w, return_stage1, png, "sync")
 
         def scored(preds, stage1):   # after the stream has been waited for
-            if sc is None:
+            if sc is None and nq is None:
                 return preds, stage1
-            return preds, stage1, (sc.scores(0, n), sc.scores(n, n) if return_stage1 else [])
+            return preds, stage1, _merged_scores(sc, nq, n, return_stage1)
 
         if sc is not None:
             _queue_scores(sc, st, 0, n, return_stage1, res, res1)
             sc.download(2 * n if return_stage1 else n)
+        if nq is not None:
+            _queue_niqe(nq, st, 0, n, return_stage1, res, res1)
+            nq.download()
         if png is not None:
             if rs is None:
                 enc = _queue_png(ctx, st, 0, n, h, w, png, return_stage1, "sync")
@@ -440,7 +493,8 @@ def _split_batch(b):
 def process_stream(model, batches: Iterable[Sequence[np.ndarray]], color_fix_type: str, disable_preprocess_model: bool, tiled: bool,
                    tile_size: int, tile_stride: int, preprocess_model=None, vae=None, y=None, y_mask=None, noise_scheduler=None,
                    return_stage1: bool = True, graph: bool = False, fp8: bool = False, png=None,
-                   png_wrap: bool = True, resize=None, gt=None, lpips: bool = False) -> Iterator[Tuple[List[np.ndarray], List[np.ndarray]]]:
+                   png_wrap: bool = True, resize=None, gt=None, lpips: bool = False, niqe=None,
+                   niqe_rects=None) -> Iterator[Tuple[List[np.ndarray], List[np.ndarray]]]:
     """process() over a sequence of image batches with the transfers hidden: while batch i computes on the current stream, batch
     i+1 is uploaded and batch i-1 downloaded on a copy stream (two staging slots per batch shape). Yields process()'s result for
     every batch, in order. Needs the fused form (all models instarevive_amd objects on one context). fp8 as in process() (cfg-5:
@@ -467,7 +521,12 @@ def process_stream(model, batches: Iterable[Sequence[np.ndarray]], color_fix_typ
     is a pair of lists of (psnr_y, ssim_y), one for the predictions and - with return_stage1, else empty - one for the stage-1 images, by the
     definitions of tools/evaluate_pairs.py. A batch without ground truth yields the pair. A ground truth of another size raises ValueError before
     anything is launched for its batch. With png the raw result is still not downloaded.
-    lpips (with gt only): as in process() - the scored batches yield (psnr_y, ssim_y, lpips) triples."""
+    lpips (with gt only): as in process() - the scored batches yield (psnr_y, ssim_y, lpips) triples.
+    niqe (with or without gt): the pristine parameters, as in process(). niqe_rects: an iterable in step with `batches`, advanced like png: per
+    batch None - the batch is not scored - or one final size (h, w) per image; without it every batch is scored (with gt: every batch that has
+    ground truth) at its png rectangle / resize target / ground truth's size / whole output. ir_niqe_stats is queued behind the paired scores on
+    the compute stream, the statistics come back with the batch's download, and the fits and the score run when the batch is yielded. A scored
+    batch yields the triple; alone its tuples are (niqe,), with gt the value is appended."""
     noise_scheduler = noise_scheduler or DDPMScheduler()
     if lpips and gt is None:
         raise ValueError("process_stream(lpips=True) needs gt=: LPIPS is scored against the ground truth")
@@ -483,6 +542,7 @@ def process_stream(model, batches: Iterable[Sequence[np.ndarray]], color_fix_typ
     png_it = iter(png) if png is not None else None
     resize_it = iter(resize) if resize is not None else None
     gt_it = iter(gt) if gt is not None else None
+    nq_it = iter(niqe_rects) if niqe is not None and niqe_rects is not None else None
     if resize_it is not None:
         from .resample import ResizeSlot, check_records
 
@@ -490,10 +550,13 @@ def process_stream(model, batches: Iterable[Sequence[np.ndarray]], color_fix_typ
         rects = next(png_it) if png_it is not None else None
         records = next(resize_it) if resize_it is not None else None
         gts = next(gt_it) if gt_it is not None else None
+        sizes = next(nq_it) if nq_it is not None else None
+        with_nq = niqe is not None and (sizes is not None if nq_it is not None else (gts is not None or gt_it is None))
         imgs, by, bm = _split_batch(batch)
         if records is not None:   # the decoded files travel; the network input is made on the device
             n, h, w = check_records(records)
             sc = _score_fill(ctx, slot, "stream", gts, n, h, w, rects, records, lpips) if gts is not None else None
+            nq = _niqe_plan(ctx, slot, "stream", niqe, n, h, w, rects, records, gts, sizes, return_stage1) if with_nq else None
             st = _Staging.get(ctx, n, h, w, slots=2, tag="stream")
             rs = ResizeSlot.get(ctx, slot, "stream")
             rs.fill(records)
@@ -501,21 +564,22 @@ def process_stream(model, batches: Iterable[Sequence[np.ndarray]], color_fix_typ
                 ev = rs.upload(copy, main)
                 if sc is not None:
                     ev = sc.upload(copy, main)   # the later event of the copy stream covers both uploads
-            return st, slot, (n, h, w), ev, (by, bm), rects, (rs, records), sc
+            return st, slot, (n, h, w), ev, (by, bm), rects, (rs, records), sc, nq
         n, h, w = _check_images(imgs)
         sc = _score_fill(ctx, slot, "stream", gts, n, h, w, rects, None, lpips) if gts is not None else None
+        nq = _niqe_plan(ctx, slot, "stream", niqe, n, h, w, rects, None, gts, sizes, return_stage1) if with_nq else None
         st = _Staging.get(ctx, n, h, w, slots=2, tag="stream")
         st.fill(slot, imgs)
         with torch.cuda.stream(copy):
             ev = st.upload(slot, copy)
             if sc is not None:
                 ev = sc.upload(copy, main)
-        return st, slot, (n, h, w), ev, (by, bm), rects, None, sc
+        return st, slot, (n, h, w), ev, (by, bm), rects, None, sc, nq
 
     def download(job):
-        st, slot, (n, h, w), done, enc, rz, sc = job
+        st, slot, (n, h, w), done, enc, rz, sc, nq = job
         done.synchronize()
-        scores = ((sc.scores(0, n), sc.scores(n, n) if return_stage1 else []),) if sc is not None else ()
+        scores = (_merged_scores(sc, nq, n, return_stage1),) if sc is not None or nq is not None else ()
         if enc is not None:   # the byte counts are here: fetch that many bytes per image
             files = enc.fetch(2 * n if return_stage1 else n, copy, png_wrap)
             return (files[:n], files[n:]) + scores
@@ -551,7 +615,7 @@ def process_stream(model, batches: Iterable[Sequence[np.ndarray]], color_fix_typ
     nxt = next(it, None)
     up = upload(nxt, slot) if nxt is not None else None
     while up is not None:
-        st, cur, (n, h, w), ready, (by, bm), rects, rz, sc = up
+        st, cur, (n, h, w), ready, (by, bm), rects, rz, sc, nq = up
         _prepare_fused(model, y, y_mask, h, w, tiled, tile_size, (vae, None if disable_preprocess_model else preprocess_model), set_prompt=False)
         set_batch_prompt(by, bm, n)
         main.wait_event(ready)
@@ -559,6 +623,8 @@ def process_stream(model, batches: Iterable[Sequence[np.ndarray]], color_fix_typ
             _png_workspace(ctx, n, h, w)
         if sc is not None:
             _metrics_workspace(ctx, sc)
+        if nq is not None:
+            ctx.workspace(nq.workspace_bytes())
         if rz is not None:
             _resize_workspace(ctx, rz[1])
             rz[0].to_network(rz[1], st.d_in[cur])
@@ -570,6 +636,8 @@ def process_stream(model, batches: Iterable[Sequence[np.ndarray]], color_fix_typ
             enc = _queue_png(ctx, st, cur, n, h, w, rects, return_stage1, "stream") if rects is not None else None
         if sc is not None:
             _queue_scores(sc, st, cur, n, return_stage1, rz[2] if rz is not None else None, rz[3] if rz is not None else None)
+        if nq is not None:
+            _queue_niqe(nq, st, cur, n, return_stage1, rz[2] if rz is not None else None, rz[3] if rz is not None else None)
         computed = torch.cuda.Event()
         computed.record(main)
         # while this batch computes: fetch the previous result, stage the next input into the other slot. The other slot's device
@@ -591,9 +659,11 @@ def process_stream(model, batches: Iterable[Sequence[np.ndarray]], color_fix_typ
                     rz[0].download(rz[2] + rz[3])
             if sc is not None:
                 sc.download(2 * n if return_stage1 else n)
+            if nq is not None:
+                nq.download()
             done = torch.cuda.Event()
             done.record(copy)
-        pending = (st, cur, (n, h, w), done, enc, rz, sc)
+        pending = (st, cur, (n, h, w), done, enc, rz, sc, nq)
     if pending is not None:
         yield download(pending)
 

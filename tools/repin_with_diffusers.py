@@ -21,6 +21,9 @@ random-initialised models of reduced width pin it exactly as the 4 GB checkpoint
     open_clip package).
  5. pyiqa's PSNR-Y / SSIM-Y (evaluate_img.py:30-33) -> tools/evaluate_pairs.py.
  7. the `lpips` package's LPIPS(net="alex") (utils/metrics.py:41-66, evaluate_img.py:32) -> tools/evaluate_pairs.py::LPIPS on the package's own weights.
+ 8. pyiqa's NIQE (evaluate_img.py's `create_metric('niqe')`; defaults test_y_channel=True, color_space='yiq', crop_border=0) -> tools/evaluate_niqe.py on
+    pyiqa's own niqe_modelparameters.mat: an image without flat areas (where the order of additions cannot matter) to 1e-6 relative, and one with
+    a saturated patch, where pyiqa's convolution order decides the signs of y - mu; the deviation there is reported, not gated.
  6. ftfy.fix_text (diffusion/model/t5.py:118-124) -> instarevive_amd.captions.fix_text (deterministic steps + the restricted mojibake repair).
 
 The fixture holds inputs, state-dict checksums and the third party's outputs (data, not source); tests/test_oracle_golden.py picks
@@ -199,6 +202,39 @@ def pin_lpips(out):
     return bool(torch.allclose(got, want, rtol=1e-4, atol=1e-6))
 
 
+def pin_niqe(out):
+    """pyiqa's `niqe` against tools/evaluate_niqe.py on pyiqa's own pristine parameters. The model fixes the order of additions of the 7 x 7 filter;
+    pyiqa inherits its convolution's, so only the image without flat areas is gated."""
+    import importlib.util
+    import pyiqa
+    from pyiqa.archs.niqe_arch import NIQE   # noqa: F401  (its default weight file is what load_params must read)
+    spec = importlib.util.spec_from_file_location("evaluate_niqe", os.path.join(ROOT, "tools", "evaluate_niqe.py"))
+    en = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(en)
+    metric = pyiqa.create_metric("niqe", device="cpu")
+    path = None
+    for root, _, names in os.walk(os.path.expanduser(os.environ.get("PYIQA_CACHE", "~/.cache/pyiqa"))):
+        path = os.path.join(root, "niqe_modelparameters.mat") if "niqe_modelparameters.mat" in names else path
+    if path is None:
+        raise ImportError("pyiqa has not downloaded niqe_modelparameters.mat")
+    mu, cov = en.load_params(path)
+    rng = np.random.default_rng(10)
+    yy, xx = np.mgrid[0:288, 0:384].astype(np.float64)
+    base = np.stack([128 + 80 * np.sin(xx / 23) * np.cos(yy / 31), 128 + 70 * np.sin((xx + yy) / 41), 128 + 90 * np.cos(xx / 17 - yy / 29)], -1)
+    plain = np.clip(np.rint(base + rng.normal(0, 4.0, base.shape)), 0, 255).astype(np.uint8)
+    flat = plain.copy()
+    flat[20:120, 40:200] = 255
+    ok = True
+    for name, img in (("plain", plain), ("flat", flat)):
+        ref = float(metric(torch.from_numpy(img).permute(2, 0, 1)[None].float() / 255.0))
+        got = en.niqe(img, mu, cov)
+        print(f"  [8] pyiqa NIQE ({name}) {ref:.6f} vs evaluate_niqe {got:.6f} (relative {abs(got - ref) / ref:.2e})")
+        out[f"niqe_{name}"], out[f"niqe_{name}_ref"] = img, np.float64(ref)
+        if name == "plain":
+            ok = abs(got - ref) <= 1e-6 * ref
+    return ok
+
+
 def pin_ftfy(out):
     import ftfy
     from instarevive_amd.captions import fix_text
@@ -220,7 +256,8 @@ def main():
     a = ap.parse_args()
     out, verdict = {}, {}
     for name, fn, args in (("diffusers DiT (items 1, 2)", pin_dit, (None,)), ("diffusers VAE (item 3)", pin_vae, (None,)),
-                           ("open_clip (item 4)", pin_clip, ()), ("pyiqa (item 5)", pin_iqa, ()), ("ftfy (item 6)", pin_ftfy, ()), ("lpips (item 7)", pin_lpips, ())):
+                           ("open_clip (item 4)", pin_clip, ()), ("pyiqa (item 5)", pin_iqa, ()), ("ftfy (item 6)", pin_ftfy, ()), ("lpips (item 7)", pin_lpips, ()),
+                           ("pyiqa NIQE (item 8)", pin_niqe, ())):
         print(name)
         try:
             verdict[name] = fn(out, *args)
