@@ -53,6 +53,9 @@ def parse_args():
     ap.add_argument("--niqe_params", default=None, help="score NIQE (no reference needed) of both output folders on the GPU (inference.py --niqe_params: "
                     "niqe_modelparameters.mat or an .npz). Works without --gt: the CSVs are then file,niqe; with --gt the column comes last. --image_size must "
                     "be at least 192 for two blocks")
+    ap.add_argument("--clipiqa_model", default=None, help="score CLIP-IQA (no reference needed) of both output folders on the GPU (inference.py --clipiqa_model: "
+                    "OpenAI's RN50.pt or an .npz). Works with or without --gt and --niqe_params; its column comes last. --image_size must be at least 32")
+    ap.add_argument("--clip_bpe", default=None, help="with --clipiqa_model: the folder that holds CLIP's BPE table (inference.py --clip_bpe)")
     ap.add_argument("--workers", type=int, default=-1, help="host threads for decoding / PNG encoding (inference.py --workers)")
     return ap.parse_args()
 
@@ -70,6 +73,8 @@ def main():
     from instarevive_amd.utils import center_crop_arr, list_image_files
     args = parse_args()
     niqe_params = cli.load_niqe_params(args)
+    clipiqa_model = cli.load_clipiqa_model(args)
+    noref = bool(niqe_params) or clipiqa_model is not None
     cli.check_device(args.device)
     rank, world, local = parallel.init_distributed()
     torch.cuda.set_device(local)
@@ -92,9 +97,9 @@ def main():
     if args.lpips_alexnet and not args.lpips_lin:
         raise SystemExit("--lpips_alexnet needs --lpips_lin (the lpips linear heads)")
     with_lpips = {"lpips": True} if args.lpips_lin else {}
-    with_niqe = {"niqe": True, "paired": bool(args.gt)} if niqe_params else {}
+    with_niqe = {**({"niqe": True} if niqe_params else {}), **({"clipiqa": True} if clipiqa_model else {}), **({"paired": bool(args.gt)} if noref else {})}
     lookup = None
-    if args.gt or niqe_params:
+    if args.gt or noref:
         from instarevive_amd.metrics import GroundTruth, Report
         lookup = GroundTruth(args.gt, args.input) if args.gt else None
         name = "metrics.csv" if world == 1 else f"metrics.rank{rank}.csv"
@@ -102,6 +107,9 @@ def main():
         if args.lpips_lin:
             from instarevive_amd import lpips
             lpips.configure(m.model.ctx, args.lpips_lin, args.lpips_alexnet)
+        if clipiqa_model:
+            from instarevive_amd import clipiqa
+            clipiqa.configure(m.model.ctx, clipiqa_model)
 
     def read(f):
         crop = center_crop_arr(Image.open(f).convert("RGB"), args.image_size)
@@ -134,15 +142,18 @@ def main():
     results = process_stream(m.model, feed(), "none", args.disable_preprocess_model, False, 512, 448, preprocess_model=m.preprocess_model, vae=m.vae,
                              y=m.y, y_mask=m.y_mask, noise_scheduler=m.noise_scheduler, return_stage1=True,
                              png=[[(args.image_size, args.image_size)] * len(group) for group in batches] if gpu_png else None, png_wrap=False,
-                             gt=batch_truths() if lookup else None, **with_lpips, **({"niqe": niqe_params} if niqe_params else {}))
-    no_niqe = 0
+                             gt=batch_truths() if lookup else None, **with_lpips, **({"niqe": niqe_params} if niqe_params else {}),
+                             **({"clipiqa": True} if clipiqa_model else {}))
+    no_niqe = no_clipiqa = 0
     for group, out in zip(batches, results):
         preds, stage1 = out[:2]
         if reports:
             for rep, folder, scores in zip(reports, (args.output, cond_dir), out[2]):
                 for f, score in zip(group, scores):
-                    if niqe_params and score[-1] != score[-1]:   # NaN: the image has no NIQE
+                    if niqe_params and score[-2 if clipiqa_model else -1] != score[-2 if clipiqa_model else -1]:   # NaN: the image has no NIQE
                         no_niqe += 1
+                    elif clipiqa_model and score[-1] != score[-1]:
+                        no_clipiqa += 1
                     else:
                         rep.add_scores(os.path.relpath(out_name(folder, args.input, f), folder), score)
         for f, pred, cond in zip(group, preds, stage1):
@@ -156,10 +167,12 @@ def main():
     if reports:
         for rep, folder in zip(reports, (args.output, cond_dir)):
             lines = rep.write()
-            print(f"[rank {rank}] {'--gt' if args.gt else '--niqe_params'}: scored {len(rep.rows)} files of {folder}"
+            print(f"[rank {rank}] {' / '.join(f for f, on in (('--gt', args.gt), ('--niqe_params', niqe_params), ('--clipiqa_model', clipiqa_model)) if on)}: scored {len(rep.rows)} files of {folder}"
                   + (f" against {args.gt}" if args.gt else "") + f" -> {rep.path}")
             for ln in lines:
                 print(ln)
+        if no_clipiqa:
+            print(f"[rank {rank}] --clipiqa_model: {no_clipiqa} files were not scored (CLIP-IQA needs 32 x 32 pixels)")
         if no_niqe:
             print(f"[rank {rank}] --niqe_params: {no_niqe} files were not scored (NIQE needs 96 x 96 blocks and two complete feature rows)")
 

@@ -30,7 +30,9 @@ enum { IR_STAGE_SWINIR = 0, IR_STAGE_VAE_ENCODE = 1, IR_STAGE_DIT = 2, IR_STAGE_
        IR_STAGE_RESAMPLE = 11 /* ir_resample_u8: n images, h = in_h, w = out_w; depends on the sizes alone (ctx may be NULL) */,
        IR_STAGE_METRICS = 12 /* ir_metrics_y: n images, h, w = the compared rectangle; depends on the sizes alone (ctx may be NULL) */,
        IR_STAGE_LPIPS = 13 /* ir_lpips: n pairs, h, w = the compared rectangle; depends on the sizes alone (ctx may be NULL) */,
-       IR_STAGE_NIQE = 14 /* ir_niqe_stats: n images, h, w = the scored rectangle; depends on the sizes alone (ctx may be NULL) */ };
+       IR_STAGE_NIQE = 14 /* ir_niqe_stats: n images, h, w = the scored rectangle; depends on the sizes alone (ctx may be NULL) */,
+       IR_STAGE_CLIPIQA = 15 /* ir_clipiqa: n images, h, w = the scored rectangle; depends on the sizes and on the layer counts bound by
+                                ir_clipiqa_configure (0 for a context that is not configured) */ };
 /* ir_pipeline flags */
 enum { IR_FLAG_NO_PREPROCESS = 1, IR_FLAG_TILED = 2, IR_FLAG_FIX_WAVELET = 4, IR_FLAG_FIX_ADAIN = 8,
        /* ir_pipeline only, needs ir_dit_control_configure: run the DiT step with the ControlNet-Half branch, condition latent
@@ -367,6 +369,36 @@ int ir_lpips(ir_ctx* ctx, void* stream, const uint8_t* a, int a_rows, long a_pit
 int ir_niqe_window(double* k49);
 int ir_niqe_stats(ir_ctx* ctx, void* stream, const uint8_t* img, int rows, long pitch, int n, int h, int w, double* out, void* ws,
                   size_t ws_bytes);
+
+/* CLIP-IQA (the no-reference metric `clipiqa` of the reference's evaluate_img.py; pyiqa's default: OpenAI CLIP RN50, no positional embedding in
+ * the attention pool, five antonym prompt pairs) on the device; tools/evaluate_clipiqa.py states the definition as a torch model and is the
+ * model of this call. The image runs at its own size: x = (v / 255 - mean) / std in fp32 through a 3 x 256 table (ir_clipiqa_scale_table, host
+ * only, no context: the table the kernels use, every step rounded to fp32 in that order), zero padding in that domain, CLIP's
+ * ModifiedResNet(layers, width, heads, out_dim) with every convolution an exact-fp32 implicit GEMM (fp32-input MFMA: a k-ordered fmaf chain
+ * per output) and the eval-mode BatchNorm (eps 1e-5) folded to one scale and one shift per channel, 2 x 2 floor-mode average pools, and the
+ * attention pool over [mean token, HW tokens] for its one used query, the feature norm, logit_scale * text . f / |f| and the softmax of each
+ * (positive, negative) pair in fp64; the score is the mean of the pairs' first probabilities. Sums run in a fixed order without
+ * floating-point atomics: an image gives the same bits on every call and at every position of a batch.
+ * ir_clipiqa_configure binds fp32 tensors uploaded with ir_upload under OpenAI's names with `visual.` replaced by `clipiqa.`:
+ *   clipiqa.conv{1,2,3}.weight [cout][cin][3][3], clipiqa.bn{1,2,3}.{weight,bias,running_mean,running_var};
+ *   clipiqa.layer{L}.{i}.conv{1,2,3}.weight, .bn{1,2,3}.*, and for a block whose stride is 2 or whose channel counts differ
+ *   .downsample.0.weight / .downsample.1.*; clipiqa.attnpool.{q,k,v,c}_proj.{weight,bias};
+ *   clipiqa.text [2 * n_pairs][out_dim], the L2-normalised text features, each pair's positive prompt first.
+ * width must be a multiple of 64 (every convolution but the stem's first then has input and output channels that are multiples of 32), heads
+ * must divide 32 * width. logit_scale_exp is exp(logit_scale). BatchNorm is folded in fp64 (scale = g / sqrt(var + eps), shift = b - mean
+ * scale, each rounded to fp32 once) and the weights are repacked to [K padded to 32][cout]; the binding holds its own copies. Returns -2 with
+ * ir_last_error naming the tensor when one is missing or has another shape, -1 for an unsupported model.
+ * ir_clipiqa scores the top-left h x w of each of the n images of [n][rows][pitch] bytes (RGB8, addressed as ir_metrics_y addresses a):
+ * scores [n] doubles; feat, when not NULL, [n][out_dim] floats, the un-normalised image feature (the fp64 value rounded once). All pointers are
+ * device pointers; stream-ordered, no allocation, no host synchronisation (capturable). ws: 256-byte aligned,
+ * ir_workspace_bytes(ctx, IR_STAGE_CLIPIQA, n, h, w, 0, 0, 0) bytes: five NHWC fp32 map slots - a block's input and output, its two
+ * intermediates and its identity branch - plus the tail's fp64 arrays; 1 075 896 832 bytes for one 2048 x 2048 image with the RN50 layer counts.
+ * Returns -1 (nothing launched) for a null pointer, n < 1, h or w below 32 (the last map would be empty), h above rows, a pitch below 3 w, a
+ * short or misaligned workspace, and -13 for a context without ir_clipiqa_configure. */
+int ir_clipiqa_scale_table(float* tab768);
+int ir_clipiqa_configure(ir_ctx* ctx, const int layers[4], int width, int heads, int out_dim, int n_pairs, float logit_scale_exp);
+int ir_clipiqa(ir_ctx* ctx, void* stream, const uint8_t* img, int rows, long pitch, int n, int h, int w, double* scores, float* feat_or_null,
+               void* ws, size_t ws_bytes);
 
 /* Single-kernel entry points, exported so tests/ can check every kernel against the oracle through the same ABI. */
 int ir_op_conv(ir_ctx* ctx, void* stream, const uint16_t* in, const uint16_t* wgt, const float* bias, void* out, int n, int h, int w,

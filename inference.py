@@ -110,6 +110,13 @@ def parse_args() -> Namespace:
                         "parameters mu_prisparam [36] / cov_prisparam [36][36]: pyiqa's niqe_modelparameters.mat, or an .npz. Works without --gt: the CSV is then "
                         "file,niqe and the average prints as `niqe: x.xxxxx`; with --gt the column and the line come last. Which files are scored follows --gt's "
                         "rule (the saved image is the device's image); files below 96 pixels on an edge or without two complete feature rows are counted as not scored")
+    parser.add_argument("--clipiqa_model", type=str, default=None, help="score CLIP-IQA, the no-reference metric `clipiqa` of the reference's evaluate_img.py, on "
+                        "the GPU (ir_clipiqa; the definition of tools/evaluate_clipiqa.py, i.e. pyiqa's default over OpenAI CLIP RN50 at the image's own size). "
+                        "FILE is OpenAI's RN50.pt (TorchScript archive or state dict), or an .npz with the same names - which may carry the ten text rows as "
+                        "`text`, so that no vocabulary is needed. Works with or without --gt and --niqe_params: the column `clipiqa` and the line "
+                        "`clipiqa: x.xxxxx` come last. Which files are scored follows --gt's rule; files below 32 pixels on an edge are counted as not scored")
+    parser.add_argument("--clip_bpe", type=str, default=None, help="with --clipiqa_model: the folder that holds CLIP's BPE table (bpe_simple_vocab_16e6.txt.gz, or "
+                        "vocab.json + merges.txt), from which the ten prompts are tokenised")
     parser.add_argument("--workers", type=int, default=-1, help="host threads that decode / resize the inputs and resize / PNG-encode the results "
                         "around the GPU (PIL releases the GIL there); -1 = this process's CPU share, 0 = everything on the main thread like the reference")
     return parser.parse_args()
@@ -186,6 +193,22 @@ def load_niqe_params(args: Namespace):
         return load_params(args.niqe_params)
     except NiqeError as e:
         raise SystemExit(str(e))
+
+
+def load_clipiqa_model(args: Namespace):
+    """--clipiqa_model [--clip_bpe]: the CLIP-IQA model with its text rows, read before any other model is touched; a file that is missing or holds
+    anything else ends the run."""
+    if not getattr(args, "clipiqa_model", None):
+        if getattr(args, "clip_bpe", None):
+            raise SystemExit("--clip_bpe needs --clipiqa_model")
+        return None
+    from instarevive_amd import clipiqa
+    if not os.path.isfile(args.clipiqa_model):
+        raise SystemExit(f"--clipiqa_model {args.clipiqa_model}: no such file")
+    try:
+        return clipiqa.load_model(args.clipiqa_model, args.clip_bpe)
+    except (ValueError, FileNotFoundError) as e:   # ClipIqaError is a ValueError
+        raise SystemExit(f"--clipiqa_model {args.clipiqa_model}: {e}")
 
 
 def check_device(device: str) -> str:
@@ -407,6 +430,8 @@ def main() -> None:
     from instarevive_amd.utils import list_image_files
     args = parse_args()
     niqe_params = load_niqe_params(args)
+    clipiqa_model = load_clipiqa_model(args)
+    noref = bool(niqe_params) or clipiqa_model is not None
     torch.manual_seed(args.seed)  # the path is deterministic; kept for surface compatibility (pl.seed_everything)
     args.device = check_device(args.device)
     rank, world, local = parallel.init_distributed()
@@ -435,17 +460,21 @@ def main() -> None:
         raise SystemExit("--lpips_lin / --lpips_alexnet score against ground truth: give --gt as well")
     if args.lpips_alexnet and not args.lpips_lin:
         raise SystemExit("--lpips_alexnet needs --lpips_lin (the lpips linear heads)")
-    if args.gt or niqe_params:
+    if args.gt or noref:
         from instarevive_amd.metrics import GroundTruth, Report
         if args.shard_tiles:
-            raise SystemExit("--gt / --niqe_params are not offered together with --shard_tiles (the assembled frame of the tile-sharded path is not scored on the device)")
+            raise SystemExit("--gt / --niqe_params / --clipiqa_model are not offered together with --shard_tiles (the assembled frame of the tile-sharded path is not scored on the device)")
         if args.gt:
             args.gt_lookup = GroundTruth(args.gt, args.input)
         report = Report(args.metrics_out or os.path.join(args.output, "metrics.csv" if world == 1 else f"metrics.rank{rank}.csv"),
-                        **({"lpips": True} if args.lpips_lin else {}), **({"niqe": True, "paired": bool(args.gt)} if niqe_params else {}))
+                        **({"lpips": True} if args.lpips_lin else {}), **({"niqe": True} if niqe_params else {}), **({"clipiqa": True} if clipiqa_model else {}),
+                        **({"paired": bool(args.gt)} if noref else {}))
         if args.lpips_lin:
             from instarevive_amd import lpips
             lpips.configure(m.model.ctx, args.lpips_lin, args.lpips_alexnet)
+        if clipiqa_model:
+            from instarevive_amd import clipiqa
+            clipiqa.configure(m.model.ctx, clipiqa_model)
     local_world = int(os.environ.get("LOCAL_WORLD_SIZE", world))
     if os.environ.get("IR_SWITCH_INTERVAL"):   # experiment knob: how long a worker thread may keep the GIL while the thread that feeds the GPU waits for it
         import sys
@@ -503,14 +532,14 @@ def main() -> None:
     rects = deque()   # --png_encoder gpu, per batch drawn by process_stream: its rectangles, or None for a batch of the host encoder
     records = deque()   # --resize gpu, per batch: the decoded files and their geometry
     truths = deque()   # --gt, per batch: the ground-truth images, or None for a batch that is not scored
-    sizes = deque()    # --niqe_params, per batch: the saved sizes, or None for a batch that is not scored
+    sizes = deque()    # --niqe_params / --clipiqa_model, per batch: the saved sizes, or None for a batch that is not scored
 
     def feed():
         for group in batches_of(jobs, max(args.batch_size, 1), (lambda j: png_rect(j, args) is not None) if gpu_png or report else None):
             todo.append(group)
             if args.gt:
                 truths.append([j.gt for j in group] if all(j.gt is not None for j in group) else None)
-            if niqe_params:
+            if noref:
                 rr = [png_rect(j, args) for j in group]
                 sizes.append(rr if all(rr) else None)
             if gpu_png:
@@ -539,20 +568,24 @@ def main() -> None:
             yield sizes.popleft()
 
     first = None    # (time, files) when the first result left the GPU: what follows is the steady state (no library / workspace warm-up in it)
-    unscored = 0    # --gt / --niqe_params: files whose saved image is not the device's image
+    unscored = 0    # --gt / --niqe_params / --clipiqa_model: files whose saved image is not the device's image
     no_niqe = 0     # --niqe_params: files below 96 pixels on an edge or without two complete feature rows
+    no_clipiqa = 0  # --clipiqa_model: files below 32 pixels on an edge
     for out in process_stream(m.model, feed(), tiled=args.tiled, return_stage1=args.show_lq and not args.disable_preprocess_model,
                               fp8=args.fp8 != "off", png=batch_rects() if gpu_png else None, png_wrap=False,
                               resize=batch_records() if args.resize_on_gpu else None, gt=batch_truths() if args.gt else None,
                               **({"lpips": True} if report and report.lpips else {}),
-                              **({"niqe": niqe_params, "niqe_rects": batch_sizes()} if niqe_params else {}), **common):
+                              **({"niqe": niqe_params} if niqe_params else {}), **({"clipiqa": True} if clipiqa_model else {}),
+                              **({"niqe_rects": batch_sizes()} if noref else {}), **common):
         preds, stage1 = out[:2]
         group = todo.pop(0)
         if report:
             if len(out) > 2:
                 for job, score in zip(group, out[2][0]):
-                    if niqe_params and score[-1] != score[-1]:   # NaN: the image has no NIQE
+                    if niqe_params and score[-2 if clipiqa_model else -1] != score[-2 if clipiqa_model else -1]:   # NaN: the image has no NIQE
                         no_niqe += 1
+                    elif clipiqa_model and score[-1] != score[-1]:
+                        no_clipiqa += 1
                     else:
                         report.add_scores(os.path.relpath(job.save_path, args.output), score)
             else:
@@ -572,12 +605,14 @@ def main() -> None:
         print(f"[rank {rank}] --png_encoder gpu: {host_files} of {pools.written} files took the host encoder (not a plain crop of the prediction)")
     if report:
         lines = report.write()
-        what = " / ".join(f for f, on in (("--gt", args.gt), ("--niqe_params", niqe_params)) if on)
+        what = " / ".join(f for f, on in (("--gt", args.gt), ("--niqe_params", niqe_params), ("--clipiqa_model", clipiqa_model)) if on)
         print(f"[rank {rank}] {what}: scored {len(report.rows)} files" + (f" against {args.gt}" if args.gt else "") + f" -> {report.path}")
         for ln in lines:
             print(ln)
         if no_niqe:
             print(f"[rank {rank}] --niqe_params: {no_niqe} of {pools.written} files were not scored (NIQE needs 96 x 96 blocks and two complete feature rows)")
+        if no_clipiqa:
+            print(f"[rank {rank}] --clipiqa_model: {no_clipiqa} of {pools.written} files were not scored (CLIP-IQA needs 32 x 32 pixels)")
         if unscored:
             print(f"[rank {rank}] {what}: {unscored} of {pools.written} files were not scored (their saved image is not the device's image: an input the host "
                   f"enlarged, or --show_lq) - use --resize gpu")

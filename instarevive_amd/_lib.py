@@ -26,12 +26,15 @@ SYMBOLS = [
     "ir_dit_set_prompts", "ir_op_attention_kv_groups", "ir_graph_records", "ir_op_vae_segment", "ir_op_vae_segment_ws", "ir_op_vae_segment_info",
     "ir_png_bound", "ir_png_encode", "ir_resample_plan_bytes", "ir_resample_plan", "ir_resample_u8", "ir_metrics_y",
     "ir_lpips_scale_table", "ir_lpips_configure", "ir_lpips", "ir_niqe_window", "ir_niqe_stats",
+    "ir_clipiqa_scale_table", "ir_clipiqa_configure", "ir_clipiqa",
 ]
 
 STAGE_SWINIR, STAGE_VAE_ENCODE, STAGE_DIT, STAGE_VAE_DECODE, STAGE_PIPELINE, STAGE_COLORFIX, STAGE_T5, STAGE_CLDM, STAGE_CLDM_PIPELINE, STAGE_CLIP_TEXT, STAGE_PNG, STAGE_RESAMPLE, STAGE_METRICS = range(13)
 STAGE_LPIPS = 13
 STAGE_NIQE = 14
+STAGE_CLIPIQA = 15
 LPIPS_NOT_CONFIGURED = -12   # ir_lpips before ir_lpips_configure
+CLIPIQA_NOT_CONFIGURED = -13   # ir_clipiqa before ir_clipiqa_configure
 FLAG_NO_PREPROCESS, FLAG_TILED, FLAG_FIX_WAVELET, FLAG_FIX_ADAIN, FLAG_CONTROL_LQ, FLAG_GRAPH, FLAG_FP8 = 1, 2, 4, 8, 16, 32, 64
 # ir_set_fp8_mask (include/instarevive_hip.h): QUALIFIED = the set qualified against the fp32 oracle on flat-softmax weights (>= 46.3 dB at 2048 x
 # 2048: the three attention parts + decoder level-0 / level-2 ResnetBlock convs); DEFAULT (the context's, ABI v3) = the same without the DiT
@@ -164,6 +167,9 @@ def load_library():
     lib.ir_lpips.argtypes = [vp, vp, vp, i, C.c_long, vp, i, C.c_long, i, i, i, vp, vp, sz]
     lib.ir_niqe_window.argtypes = [vp]
     lib.ir_niqe_stats.argtypes = [vp, vp, vp, i, C.c_long, i, i, i, vp, vp, sz]
+    lib.ir_clipiqa_scale_table.argtypes = [vp]
+    lib.ir_clipiqa_configure.argtypes = [vp, C.POINTER(C.c_int), i, i, i, i, C.c_float]
+    lib.ir_clipiqa.argtypes = [vp, vp, vp, i, C.c_long, i, i, i, vp, vp, vp, sz]
     for name in SYMBOLS:
         fn = getattr(lib, name)
         if fn.restype is C.c_int and name not in ("ir_abi_version",):

@@ -8,6 +8,7 @@
 #include <string.h>
 
 #include <algorithm>
+#include <memory>
 #include <string>
 #include <unordered_map>
 #include <vector>
@@ -301,6 +302,9 @@ struct ir_ctx {
         const float *tab = nullptr, *w[5] = {}, *b[5] = {}, *lin[5] = {};
     } lpips;
     std::vector<void*> lpips_owned;
+    // ir_clipiqa: the input table, the repacked conv weights, the folded BatchNorm vectors and copies of the attention pool / text rows (in clipiqa_owned)
+    IrClipiqaModel clipiqa;
+    std::vector<void*> clipiqa_owned;
 };
 
 namespace {
@@ -1817,7 +1821,7 @@ void ir_destroy(ir_ctx* c) {
     if (!c) return;
     (void)hipSetDevice(c->device);
     for (auto& kv : c->t) (void)hipFree(kv.second.p);
-    for (std::vector<void*>* l : {&c->owned, &c->dit_tabs, &c->dit_ctrl_tabs, &c->dit_prompt, &c->t5_owned, &c->lpips_owned})
+    for (std::vector<void*>* l : {&c->owned, &c->dit_tabs, &c->dit_ctrl_tabs, &c->dit_prompt, &c->t5_owned, &c->lpips_owned, &c->clipiqa_owned})
         for (void* p : *l) (void)hipFree(p);
     for (hipEvent_t e : c->prof.pool) (void)hipEventDestroy(e);
     for (auto& g : c->graphs) (void)hipGraphExecDestroy(g.exec);
@@ -2773,6 +2777,155 @@ int ir_lpips(ir_ctx* c, void* stream, const uint8_t* a, int a_rows, long a_pitch
     return 0;
 }
 
+// ---------------------------------------------------------------- CLIP-IQA (clipiqa.hip)
+int ir_clipiqa_scale_table(float* tab) {
+    if (!tab) return -1;
+    static const float mean[3] = {0.48145466f, 0.4578275f, 0.40821073f}, std3[3] = {0.26862954f, 0.26130258f, 0.27577711f};
+    for (int ch = 0; ch < 3; ++ch)
+        for (int v = 0; v < 256; ++v) {   // every step rounded to fp32, in the model's order
+            volatile float x = (float)v / 255.0f;
+            volatile float y = x - mean[ch];
+            tab[256 * ch + v] = y / std3[ch];
+        }
+    return 0;
+}
+
+namespace {
+// the tensor `name` of the context with exactly `floats` fp32 values, or null with ir_last_error naming it
+const float* clipiqa_tensor(ir_ctx* c, const std::string& name, size_t floats) {
+    auto it = c->t.find(name);
+    if (it == c->t.end()) {
+        fail(c, -2, "ir_clipiqa_configure: tensor %s (missing)", name.c_str());
+        return nullptr;
+    }
+    if (it->second.bytes != floats * 4) {
+        fail(c, -2, "ir_clipiqa_configure: tensor %s has %zu bytes, the configured model's has %zu", name.c_str(), it->second.bytes, floats * 4);
+        return nullptr;
+    }
+    return static_cast<const float*>(it->second.p);
+}
+int clipiqa_to_device(ir_ctx* c, const void* host, size_t bytes, const float** out) {
+    void* d = nullptr;
+    if (dev_alloc(c, c->clipiqa_owned, &d, bytes)) return -100;
+    HIPOK(c, hipMemcpy(d, host, bytes, hipMemcpyHostToDevice));
+    *out = static_cast<const float*>(d);
+    return 0;
+}
+int clipiqa_copy(ir_ctx* c, const float* dev, size_t floats, const float** out) {
+    void* d = nullptr;
+    if (dev_alloc(c, c->clipiqa_owned, &d, floats * 4)) return -100;
+    HIPOK(c, hipMemcpy(d, dev, floats * 4, hipMemcpyDeviceToDevice));
+    *out = static_cast<const float*>(d);
+    return 0;
+}
+struct ClipConvSrc { std::string conv, bn; int cin, cout, ks; IrClipConv* dst; };
+}  // namespace
+
+int ir_clipiqa_configure(ir_ctx* c, const int* layers, int width, int heads, int out_dim, int n_pairs, float logit_scale_exp) {
+    if (!c || !layers) return fail(c, -1, "ir_clipiqa_configure: null argument");
+    int n_blocks = 0;
+    for (int l = 0; l < 4; ++l) {
+        if (layers[l] < 1) return fail(c, -1, "ir_clipiqa_configure: layer %d has %d blocks", l + 1, layers[l]);
+        n_blocks += layers[l];
+    }
+    if (n_blocks > IR_CLIPIQA_MAX_BLOCKS) return fail(c, -1, "ir_clipiqa_configure: %d blocks, at most %d", n_blocks, IR_CLIPIQA_MAX_BLOCKS);
+    if (width < 64 || width % 64 || heads < 1 || (width * 32) % heads || out_dim < 1 || n_pairs < 1 || n_pairs > 64 || !(logit_scale_exp > 0.f))
+        return fail(c, -1, "ir_clipiqa_configure: unsupported model (width %d must be a multiple of 64, heads %d must divide %d, out_dim %d, %d pairs)", width,
+                    heads, width * 32, out_dim, n_pairs);
+    HIPOK(c, hipSetDevice(c->device));
+    c->clipiqa.ok = false;
+    auto m = std::make_unique<IrClipiqaModel>();
+    for (int l = 0; l < 4; ++l) m->layers[l] = layers[l];
+    m->width = width; m->heads = heads; m->out_dim = out_dim; m->n_pairs = n_pairs; m->n_blocks = n_blocks; m->logit_scale = (double)logit_scale_exp;
+    std::vector<ClipConvSrc> convs;
+    convs.push_back({"clipiqa.conv1", "clipiqa.bn1", 3, width / 2, 3, &m->stem[0]});
+    convs.push_back({"clipiqa.conv2", "clipiqa.bn2", width / 2, width / 2, 3, &m->stem[1]});
+    convs.push_back({"clipiqa.conv3", "clipiqa.bn3", width / 2, width, 3, &m->stem[2]});
+    int inplanes = width, bi = 0;
+    for (int l = 0; l < 4; ++l) {
+        const int planes = width << l;
+        for (int i = 0; i < layers[l]; ++i, ++bi) {
+            IrClipBlock& b = m->blocks[bi];
+            b.stride = (i == 0 && l > 0) ? 2 : 1;
+            b.has_down = b.stride == 2 || inplanes != planes * 4;
+            const std::string base = fmt("clipiqa.layer%d.%d.", l + 1, i);
+            convs.push_back({base + "conv1", base + "bn1", inplanes, planes, 1, &b.c1});
+            convs.push_back({base + "conv2", base + "bn2", planes, planes, 3, &b.c2});
+            convs.push_back({base + "conv3", base + "bn3", planes, planes * 4, 1, &b.c3});
+            if (b.has_down) convs.push_back({base + "downsample.0", base + "downsample.1", inplanes, planes * 4, 1, &b.down});
+            inplanes = planes * 4;
+        }
+    }
+    const int C = width * 32;
+    // every tensor is looked up before anything is replaced
+    struct Lin { const char* name; int rows, cols; const float **w, **b; };
+    const Lin lins[4] = {{"q_proj", C, C, &m->qw, &m->qb}, {"k_proj", C, C, &m->kw, &m->kb}, {"v_proj", C, C, &m->vw, &m->vb}, {"c_proj", out_dim, C, &m->cw, &m->cb}};
+    for (const ClipConvSrc& s : convs) {
+        if (!clipiqa_tensor(c, s.conv + ".weight", (size_t)s.cout * s.cin * s.ks * s.ks)) return -2;
+        for (const char* v : {".weight", ".bias", ".running_mean", ".running_var"})
+            if (!clipiqa_tensor(c, s.bn + v, (size_t)s.cout)) return -2;
+    }
+    for (const Lin& l : lins)
+        if (!clipiqa_tensor(c, fmt("clipiqa.attnpool.%s.weight", l.name), (size_t)l.rows * l.cols) || !clipiqa_tensor(c, fmt("clipiqa.attnpool.%s.bias", l.name), (size_t)l.rows))
+            return -2;
+    if (!clipiqa_tensor(c, "clipiqa.text", (size_t)2 * n_pairs * out_dim)) return -2;
+
+    release_list(c->clipiqa_owned);
+    HIPOK(c, hipDeviceSynchronize());
+    float tab[3 * 256];
+    ir_clipiqa_scale_table(tab);
+    if (int e = clipiqa_to_device(c, tab, sizeof tab, &m->tab)) return e;
+    for (const ClipConvSrc& s : convs) {   // [cout][cin][ky][kx] -> [(ky, kx, c) padded to 32][cout], zero rows behind K; BatchNorm folded in fp64
+        const int K = s.ks * s.ks * s.cin, Kp = pad32(K);
+        std::vector<float> w((size_t)s.cout * K), t((size_t)Kp * s.cout, 0.f), bn[4], sc(s.cout), sh(s.cout);
+        HIPOK(c, hipMemcpy(w.data(), clipiqa_tensor(c, s.conv + ".weight", w.size()), w.size() * 4, hipMemcpyDeviceToHost));
+        for (int o = 0; o < s.cout; ++o)
+            for (int ci = 0; ci < s.cin; ++ci)
+                for (int ky = 0; ky < s.ks; ++ky)
+                    for (int kx = 0; kx < s.ks; ++kx)
+                        t[(size_t)((ky * s.ks + kx) * s.cin + ci) * s.cout + o] = w[(((size_t)o * s.cin + ci) * s.ks + ky) * s.ks + kx];
+        int k = 0;
+        for (const char* v : {".weight", ".bias", ".running_mean", ".running_var"}) {
+            bn[k].resize(s.cout);
+            HIPOK(c, hipMemcpy(bn[k].data(), clipiqa_tensor(c, s.bn + v, (size_t)s.cout), (size_t)s.cout * 4, hipMemcpyDeviceToHost));
+            ++k;
+        }
+        for (int o = 0; o < s.cout; ++o) {   // scale = g / sqrt(var + eps), shift = b - mean scale, each rounded to fp32 once
+            const double scale = (double)bn[0][o] / sqrt((double)bn[3][o] + 1e-5);
+            sc[o] = (float)scale;
+            sh[o] = (float)((double)bn[1][o] - (double)bn[2][o] * scale);
+        }
+        s.dst->cin = s.cin; s.dst->cout = s.cout; s.dst->ks = s.ks;
+        if (int e = clipiqa_to_device(c, t.data(), t.size() * 4, &s.dst->w)) return e;
+        if (int e = clipiqa_to_device(c, sc.data(), sc.size() * 4, &s.dst->scale)) return e;
+        if (int e = clipiqa_to_device(c, sh.data(), sh.size() * 4, &s.dst->shift)) return e;
+    }
+    // copies of the linears and the text rows: the binding does not depend on later uploads under these names
+    for (const Lin& l : lins) {
+        if (int e = clipiqa_copy(c, clipiqa_tensor(c, fmt("clipiqa.attnpool.%s.weight", l.name), (size_t)l.rows * l.cols), (size_t)l.rows * l.cols, l.w)) return e;
+        if (int e = clipiqa_copy(c, clipiqa_tensor(c, fmt("clipiqa.attnpool.%s.bias", l.name), (size_t)l.rows), (size_t)l.rows, l.b)) return e;
+    }
+    if (int e = clipiqa_copy(c, clipiqa_tensor(c, "clipiqa.text", (size_t)2 * n_pairs * out_dim), (size_t)2 * n_pairs * out_dim, &m->text)) return e;
+    m->ok = true;
+    c->clipiqa = *m;
+    ++c->generation;
+    return 0;
+}
+
+int ir_clipiqa(ir_ctx* c, void* stream, const uint8_t* img, int rows, long pitch, int n, int h, int w, double* scores, float* feat, void* ws, size_t ws_bytes) {
+    if (!c || !img || !scores || !ws) return fail(c, -1, "ir_clipiqa: null argument");
+    if (n < 1 || h < 32 || w < 32 || h > rows || pitch < 3L * w)
+        return fail(c, -1, "ir_clipiqa: bad size (n %d, %d x %d in %d rows pitch %ld; the tower's last map needs 32 x 32)", n, h, w, rows, pitch);
+    if (!c->clipiqa.ok) return fail(c, -13, "ir_clipiqa: CLIP-IQA not configured (ir_clipiqa_configure)");
+    IrClipiqaPlan pl;
+    if (ir_clipiqa_plan(c->clipiqa, n, h, w, &pl)) return fail(c, -1, "ir_clipiqa: n %d of %d x %d is more than one call takes (2^31 output pixels, 65535 images)", n, h, w);
+    if (ws_bytes < pl.total || (reinterpret_cast<uintptr_t>(ws) & 255)) return fail(c, -1, "ir_clipiqa: workspace too small or unaligned (%zu < %zu)", ws_bytes, pl.total);
+    if ((reinterpret_cast<uintptr_t>(scores) & 7) || (reinterpret_cast<uintptr_t>(feat) & 3)) return fail(c, -1, "ir_clipiqa: scores / feat not aligned");
+    use_ctx(c);
+    if (ir_launch_clipiqa(c->clipiqa, img, rows, pitch, n, h, w, scores, feat, ws, (hipStream_t)stream)) return fail(c, -100, "ir_clipiqa: launch failed");
+    return 0;
+}
+
 // ---------------------------------------------------------------- NIQE's block statistics (niqe.hip)
 // the half-size fp64 luma plane of every image's scored rectangle
 static size_t niqe_workspace(int n, int h, int w) {
@@ -2800,6 +2953,10 @@ int ir_niqe_stats(ir_ctx* c, void* stream, const uint8_t* img, int rows, long pi
 
 size_t ir_workspace_bytes(ir_ctx* c, int stage, int n, int h, int w, int flags, int tile_size, int tile_stride) {
     if (stage == IR_STAGE_NIQE) return (n < 1 || h < IR_NIQE_BLOCK || w < IR_NIQE_BLOCK) ? 0 : niqe_workspace(n, h, w);   // a function of the sizes alone: no context needed
+    if (stage == IR_STAGE_CLIPIQA) {   // a function of the sizes and of the configured layer counts
+        IrClipiqaPlan pl;
+        return (!c || !c->clipiqa.ok || ir_clipiqa_plan(c->clipiqa, n, h, w, &pl)) ? 0 : pl.total;
+    }
     if (stage == IR_STAGE_LPIPS) {   // a function of the sizes alone: no context needed
         IrLpipsPlan pl;
         return ir_lpips_plan(n, h, w, &pl) ? 0 : pl.total;

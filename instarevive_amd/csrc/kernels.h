@@ -246,6 +246,41 @@ int ir_launch_lpips(const uint8_t* a, int a_rows, long a_pitch, const uint8_t* b
 void ir_niqe_window_host(double* k49);
 int ir_launch_niqe_stats(const uint8_t* img, int rows, long pitch, int n, int h, int w, const double* tab, double* half, double* out, hipStream_t s);
 
+// ---- CLIP-IQA of uint8 images (clipiqa.hip)
+// The bound model: every convolution as w [K padded to 32][cout] fp32 with K in (ky, kx, c) order and the folded BatchNorm as scale / shift [cout];
+// the stem's three, then the bottleneck blocks in order (down: the identity branch's 1 x 1, present when the stride is 2 or the counts differ);
+// the attention pool's four linears as PyTorch holds them ([out][in] fp32, bias [out]); text: [2 * n_pairs][out_dim] fp32 unit rows.
+struct IrClipConv {
+    int cin = 0, cout = 0, ks = 0;
+    const float *w = nullptr, *scale = nullptr, *shift = nullptr;
+};
+struct IrClipBlock {
+    IrClipConv c1, c2, c3, down;
+    int stride = 1;
+    bool has_down = false;
+};
+#define IR_CLIPIQA_MAX_BLOCKS 64
+struct IrClipiqaModel {
+    bool ok = false;
+    int layers[4] = {}, width = 0, heads = 0, out_dim = 0, n_pairs = 0, n_blocks = 0;
+    double logit_scale = 0.0;
+    const float* tab = nullptr;   // [3][256] input table
+    IrClipConv stem[3];
+    IrClipBlock blocks[IR_CLIPIQA_MAX_BLOCKS];
+    const float *qw = nullptr, *qb = nullptr, *kw = nullptr, *kb = nullptr, *vw = nullptr, *vb = nullptr, *cw = nullptr, *cb = nullptr, *text = nullptr;
+};
+// ir_clipiqa_plan: the workspace of a call - five NHWC fp32 map slots for the n images (0 / 1: a block's input and output in turn, 2: conv1's
+// output, the pooled conv2 output and the pooled identity input, 3: conv2's output, 4: the identity branch) and the fp64 tail's eight arrays
+// (token mean, q, u, c0, the [T][heads] probabilities, y, the attention output, the feature). Byte offsets; fh x fw is the last map.
+// -1 below 32 x 32, for more than 65535 images or when a row count leaves an int.
+struct IrClipiqaPlan {
+    size_t slot[5], tail[8], total;
+    int fh, fw, final_slot;
+};
+int ir_clipiqa_plan(const IrClipiqaModel& m, int n, int h, int w, IrClipiqaPlan* plan);
+int ir_launch_clipiqa(const IrClipiqaModel& m, const uint8_t* img, int rows, long pitch, int n, int h, int w, double* scores, float* feat, void* ws,
+                      hipStream_t s);
+
 // ---- layout / elementwise (elementwise.hip)
 int ir_launch_u8_to_nchw(const uint8_t* in, float* out, int N, int H, int W, hipStream_t s);
 int ir_launch_swin_prep(const float* x_nchw, bf16_t* out, int N, int H, int W, const float* mean3, float img_range, hipStream_t s);

@@ -162,10 +162,41 @@ def _metrics_workspace(ctx, sc):
         lpips_workspace(ctx, sc.lpips_workspace_bytes())
 
 
-def _niqe_plan(ctx, slot, tag, params, n, h, w, rects, records, gts, sizes, with_stage1):
-    """The niqe.NiqeSlot of a batch that is scored without reference, planned on the host: every image's FINAL size - the LANCZOS target or valid
-    rectangle of a resize batch, the png rectangle, else `sizes` (niqe_rects), the ground truth's size, else the network's output."""
-    from .niqe import NiqeSlot
+class _NoReference:
+    """The no-reference scorers of one batch behind the interface of niqe.NiqeSlot: NIQE's slot, CLIP-IQA's slot (clipiqa.ClipIqaSlot) or both.
+    ir_niqe_stats is queued first, ir_clipiqa behind it; a score tuple is (niqe,), (clipiqa,) or (niqe, clipiqa)."""
+
+    def __init__(self, ctx, nq, cq):
+        self.ctx, self.nq, self.cq = ctx, nq, cq
+
+    def reserve(self):
+        """Grow the scratch of both scorers before anything of the batch is queued."""
+        if self.nq is not None:
+            self.ctx.workspace(self.nq.workspace_bytes())
+        if self.cq is not None:
+            self.cq.reserve()
+
+    def queue(self, first, images, results=None):
+        for s in (self.nq, self.cq):
+            if s is not None:
+                s.queue(first, images, results)
+
+    def download(self):
+        for s in (self.nq, self.cq):
+            if s is not None:
+                s.download()
+
+    def scores(self, first, count):
+        a = self.nq.scores(first, count) if self.nq is not None else None
+        b = self.cq.scores(first, count) if self.cq is not None else None
+        return b if a is None else a if b is None else [x + y for x, y in zip(a, b)]
+
+
+def _niqe_plan(ctx, slot, tag, params, n, h, w, rects, records, gts, sizes, with_stage1, clipiqa=False):
+    """The no-reference scorers of a batch (NIQE with `params`, CLIP-IQA with `clipiqa`), planned on the host: every image's FINAL size - the
+    LANCZOS target or valid rectangle of a resize batch, the png rectangle, else `sizes` (niqe_rects), the ground truth's size, else the
+    network's output."""
+    what = "niqe" if params is not None else "clipiqa"
     if records is not None:
         finals = [tuple(rec.geo.lanczos[::-1]) if rec.geo.lanczos else tuple(rec.geo.valid_hw) for rec in records]
     elif rects is not None:
@@ -177,17 +208,25 @@ def _niqe_plan(ctx, slot, tag, params, n, h, w, rects, records, gts, sizes, with
     else:
         finals = [(h, w)] * n
     if len(finals) != n:
-        raise ValueError(f"niqe: {len(finals)} sizes for a batch of {n} images")
+        raise ValueError(f"{what}: {len(finals)} sizes for a batch of {n} images")
     for i, (fh, fw) in enumerate(finals):
         if fh < 1 or fw < 1 or (records is None and (fh > h or fw > w)):
-            raise ValueError(f"niqe: image {i} is scored at {fh} x {fw}, the network's output is {h} x {w}")
-    nq = NiqeSlot.get(ctx, slot, tag)
-    nq.plan(finals, params, 2 if with_stage1 else 1)
-    return nq
+            raise ValueError(f"{what}: image {i} is scored at {fh} x {fw}, the network's output is {h} x {w}")
+    nq = cq = None
+    if params is not None:
+        from .niqe import NiqeSlot
+        nq = NiqeSlot.get(ctx, slot, tag)
+        nq.plan(finals, params, 2 if with_stage1 else 1)
+    if clipiqa:
+        from .clipiqa import ClipIqaSlot
+        cq = ClipIqaSlot.get(ctx, slot, tag)
+        cq.plan(finals, 2 if with_stage1 else 1)
+    return _NoReference(ctx, nq, cq)
 
 
 def _queue_niqe(nq, st, slot, n, with_stage1, res=None, res1=None):
-    """ir_niqe_stats behind the ir_pipeline (and the LANCZOS / scoring calls) of this slot, on the current stream: rows as in _queue_scores."""
+    """ir_niqe_stats / ir_clipiqa behind the ir_pipeline (and the LANCZOS / scoring calls) of this slot, on the current stream: rows as in
+    _queue_scores."""
     nq.queue(0, st.d_out[slot], res)
     if with_stage1:
         nq.queue(n, st.d_st1[slot], res1)
@@ -195,7 +234,8 @@ def _queue_niqe(nq, st, slot, n, with_stage1, res=None, res1=None):
 
 def _merged_scores(sc, nq, n, with_stage1):
     """The scores element of a scored batch: a pair of lists (predictions, stage-1 images or empty) of tuples - the paired scores of `sc`, then
-    (niqe,) of `nq`. The host part of NIQE (the fits and the score) runs here, where the scores are read."""
+    the no-reference scores of `nq` ((niqe,), (clipiqa,) or (niqe, clipiqa)). The host part of NIQE (the fits and the score) runs here, where the
+    scores are read."""
     out = []
     for first, count in ((0, n), (n, n if with_stage1 else 0)):
         a = sc.scores(first, count) if sc is not None and count else None
@@ -330,7 +370,7 @@ def _launch_pipeline(ctx, st, slot, n, h, w, flags, tile_size, tile_stride, acp,
 def process(model, control_imgs: List[np.ndarray], strength: float, color_fix_type: str, disable_preprocess_model: bool, tiled: bool,
             tile_size: int, tile_stride: int, preprocess_model=None, vae=None, y=None, y_mask=None, noise_scheduler=None,
             fused: bool = True, graph: bool = False, return_stage1: bool = True, fp8: bool = False, png=None,
-            resize=None, gt=None, lpips: bool = False, niqe=None, niqe_rects=None) -> Tuple[List[np.ndarray], List[np.ndarray]]:
+            resize=None, gt=None, lpips: bool = False, niqe=None, niqe_rects=None, clipiqa: bool = False) -> Tuple[List[np.ndarray], List[np.ndarray]]:
     """test_scripts/inference.py:55-166. control_imgs: list of HWC uint8 RGB arrays of equal size (multiples of 64).
     Returns (preds, stage1_preds) as lists of HWC uint8 arrays (stage1_preds is empty with return_stage1=False, which skips its
     conversion and download).
@@ -360,7 +400,10 @@ def process(model, control_imgs: List[np.ndarray], strength: float, color_fix_ty
     ir_niqe_stats is queued behind the network (and the paired scores) on every image's FINAL form - the png rectangle, the final size of a resize
     job, niqe_rects (one (h, w) per image), the ground truth's size, else the whole output - and the fits and the score are computed on the host
     when the scores are read. Alone, the call returns the triple with scores a pair of lists of (niqe,); with gt the value is appended to each
-    tuple. An image without a score (an edge below 96 pixels, fewer than two complete feature rows) gets NaN."""
+    tuple. An image without a score (an edge below 96 pixels, fewer than two complete feature rows) gets NaN.
+    clipiqa (fused form only; with or without gt and niqe): score CLIP-IQA as well - ir_clipiqa with the model instarevive_amd.clipiqa.configure()
+    bound to the models' context, queued behind ir_niqe_stats on the same final rectangles (niqe_rects serves both). Its value is the last of
+    every tuple: (clipiqa,), (niqe, clipiqa), (psnr_y, ssim_y[, lpips][, niqe], clipiqa). An image below 32 pixels on an edge gets NaN."""
     noise_scheduler = noise_scheduler or DDPMScheduler()
     if lpips and gt is None:
         raise ValueError("process(lpips=True) needs gt=: LPIPS is scored against the ground truth")
@@ -369,7 +412,7 @@ def process(model, control_imgs: List[np.ndarray], strength: float, color_fix_ty
         n, h, w = check_records(resize)
     else:
         n, h, w = _check_images(control_imgs)
-    if (png is not None or resize is not None or gt is not None or niqe is not None) and not (fused and _fused_ok(model, preprocess_model, vae, disable_preprocess_model)):
+    if (png is not None or resize is not None or gt is not None or niqe is not None or clipiqa) and not (fused and _fused_ok(model, preprocess_model, vae, disable_preprocess_model)):
         raise ValueError("process(png=... / resize=... / gt=... / niqe=...) needs the fused form (instarevive_amd models sharing one context)")
     device = model.device
     acp = float(noise_scheduler.alphas_cumprod[400])
@@ -381,7 +424,7 @@ def process(model, control_imgs: List[np.ndarray], strength: float, color_fix_ty
             raise RuntimeError("process(fp8=True): call vae.enable_fp8() first - without the fp8 weight forms every layer would silently run in bf16")
         ctx = model.ctx
         sc = _score_fill(ctx, 0, "sync", gt, n, h, w, png, resize, lpips) if gt is not None else None
-        nq = _niqe_plan(ctx, 0, "sync", niqe, n, h, w, png, resize, gt, niqe_rects, return_stage1) if niqe is not None else None
+        nq = _niqe_plan(ctx, 0, "sync", niqe, n, h, w, png, resize, gt, niqe_rects, return_stage1, clipiqa) if niqe is not None or clipiqa else None
         _prepare_fused(model, y, y_mask, h, w, tiled, tile_size, (vae, None if disable_preprocess_model else preprocess_model))
         flags = _pipeline_flags(model, color_fix_type, disable_preprocess_model, tiled) | (L.FLAG_GRAPH if graph else 0) | (L.FLAG_FP8 if fp8 else 0)
         st = _Staging.get(ctx, n, h, w)
@@ -400,7 +443,7 @@ def process(model, control_imgs: List[np.ndarray], strength: float, color_fix_ty
             sc.upload()
             _metrics_workspace(ctx, sc)
         if nq is not None:
-            ctx.workspace(nq.workspace_bytes())
+            nq.reserve()
         if rs is not None:
             rs.to_network(resize, st.d_in[0])
         _launch_pipeline(ctx, st, 0, n, h, w, flags, tile_size, tile_stride, acp, sf, return_stage1)
@@ -494,7 +537,7 @@ def process_stream(model, batches: Iterable[Sequence[np.ndarray]], color_fix_typ
                    tile_size: int, tile_stride: int, preprocess_model=None, vae=None, y=None, y_mask=None, noise_scheduler=None,
                    return_stage1: bool = True, graph: bool = False, fp8: bool = False, png=None,
                    png_wrap: bool = True, resize=None, gt=None, lpips: bool = False, niqe=None,
-                   niqe_rects=None) -> Iterator[Tuple[List[np.ndarray], List[np.ndarray]]]:
+                   niqe_rects=None, clipiqa: bool = False) -> Iterator[Tuple[List[np.ndarray], List[np.ndarray]]]:
     """process() over a sequence of image batches with the transfers hidden: while batch i computes on the current stream, batch
     i+1 is uploaded and batch i-1 downloaded on a copy stream (two staging slots per batch shape). Yields process()'s result for
     every batch, in order. Needs the fused form (all models instarevive_amd objects on one context). fp8 as in process() (cfg-5:
@@ -526,7 +569,9 @@ def process_stream(model, batches: Iterable[Sequence[np.ndarray]], color_fix_typ
     batch None - the batch is not scored - or one final size (h, w) per image; without it every batch is scored (with gt: every batch that has
     ground truth) at its png rectangle / resize target / ground truth's size / whole output. ir_niqe_stats is queued behind the paired scores on
     the compute stream, the statistics come back with the batch's download, and the fits and the score run when the batch is yielded. A scored
-    batch yields the triple; alone its tuples are (niqe,), with gt the value is appended."""
+    batch yields the triple; alone its tuples are (niqe,), with gt the value is appended.
+    clipiqa (with or without gt and niqe): as in process() - ir_clipiqa is queued behind ir_niqe_stats on the batches NIQE scores or would score
+    (niqe_rects serves both), and its value comes last in every tuple."""
     noise_scheduler = noise_scheduler or DDPMScheduler()
     if lpips and gt is None:
         raise ValueError("process_stream(lpips=True) needs gt=: LPIPS is scored against the ground truth")
@@ -542,7 +587,8 @@ def process_stream(model, batches: Iterable[Sequence[np.ndarray]], color_fix_typ
     png_it = iter(png) if png is not None else None
     resize_it = iter(resize) if resize is not None else None
     gt_it = iter(gt) if gt is not None else None
-    nq_it = iter(niqe_rects) if niqe is not None and niqe_rects is not None else None
+    noref = niqe is not None or bool(clipiqa)
+    nq_it = iter(niqe_rects) if noref and niqe_rects is not None else None
     if resize_it is not None:
         from .resample import ResizeSlot, check_records
 
@@ -551,12 +597,12 @@ def process_stream(model, batches: Iterable[Sequence[np.ndarray]], color_fix_typ
         records = next(resize_it) if resize_it is not None else None
         gts = next(gt_it) if gt_it is not None else None
         sizes = next(nq_it) if nq_it is not None else None
-        with_nq = niqe is not None and (sizes is not None if nq_it is not None else (gts is not None or gt_it is None))
+        with_nq = noref and (sizes is not None if nq_it is not None else (gts is not None or gt_it is None))
         imgs, by, bm = _split_batch(batch)
         if records is not None:   # the decoded files travel; the network input is made on the device
             n, h, w = check_records(records)
             sc = _score_fill(ctx, slot, "stream", gts, n, h, w, rects, records, lpips) if gts is not None else None
-            nq = _niqe_plan(ctx, slot, "stream", niqe, n, h, w, rects, records, gts, sizes, return_stage1) if with_nq else None
+            nq = _niqe_plan(ctx, slot, "stream", niqe, n, h, w, rects, records, gts, sizes, return_stage1, clipiqa) if with_nq else None
             st = _Staging.get(ctx, n, h, w, slots=2, tag="stream")
             rs = ResizeSlot.get(ctx, slot, "stream")
             rs.fill(records)
@@ -567,7 +613,7 @@ def process_stream(model, batches: Iterable[Sequence[np.ndarray]], color_fix_typ
             return st, slot, (n, h, w), ev, (by, bm), rects, (rs, records), sc, nq
         n, h, w = _check_images(imgs)
         sc = _score_fill(ctx, slot, "stream", gts, n, h, w, rects, None, lpips) if gts is not None else None
-        nq = _niqe_plan(ctx, slot, "stream", niqe, n, h, w, rects, None, gts, sizes, return_stage1) if with_nq else None
+        nq = _niqe_plan(ctx, slot, "stream", niqe, n, h, w, rects, None, gts, sizes, return_stage1, clipiqa) if with_nq else None
         st = _Staging.get(ctx, n, h, w, slots=2, tag="stream")
         st.fill(slot, imgs)
         with torch.cuda.stream(copy):
@@ -624,7 +670,7 @@ def process_stream(model, batches: Iterable[Sequence[np.ndarray]], color_fix_typ
         if sc is not None:
             _metrics_workspace(ctx, sc)
         if nq is not None:
-            ctx.workspace(nq.workspace_bytes())
+            nq.reserve()
         if rz is not None:
             _resize_workspace(ctx, rz[1])
             rz[0].to_network(rz[1], st.d_in[cur])

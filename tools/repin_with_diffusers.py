@@ -24,6 +24,9 @@ random-initialised models of reduced width pin it exactly as the 4 GB checkpoint
  8. pyiqa's NIQE (evaluate_img.py's `create_metric('niqe')`; defaults test_y_channel=True, color_space='yiq', crop_border=0) -> tools/evaluate_niqe.py on
     pyiqa's own niqe_modelparameters.mat: an image without flat areas (where the order of additions cannot matter) to 1e-6 relative, and one with
     a saturated patch, where pyiqa's convolution order decides the signs of y - mu; the deviation there is reported, not gated.
+ 9. pyiqa's CLIP-IQA (evaluate_img.py's `create_metric('clipiqa')`: OpenAI CLIP RN50 at the image's own size, no positional embedding in the
+    attention pool, five antonym prompt pairs) -> tools/evaluate_clipiqa.py on pyiqa's own RN50 weights and vocabulary (pass --clip_bpe, the
+    folder of the BPE table): the ten text rows and the score of two images to 1e-5.
  6. ftfy.fix_text (diffusion/model/t5.py:118-124) -> instarevive_amd.captions.fix_text (deterministic steps + the restricted mojibake repair).
 
 The fixture holds inputs, state-dict checksums and the third party's outputs (data, not source); tests/test_oracle_golden.py picks
@@ -235,6 +238,32 @@ def pin_niqe(out):
     return ok
 
 
+def pin_clipiqa(out, bpe=None):
+    """pyiqa's `clipiqa` against tools/evaluate_clipiqa.py on the RN50 weights pyiqa itself loads (its CLIP model's state dict)."""
+    import importlib.util
+    import pyiqa
+    spec = importlib.util.spec_from_file_location("evaluate_clipiqa", os.path.join(ROOT, "tools", "evaluate_clipiqa.py"))
+    ec = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(ec)
+    if bpe is None:
+        raise ImportError("--clip_bpe (the folder of CLIP's BPE table) is needed to tokenise the prompts")
+    metric = pyiqa.create_metric("clipiqa", device="cpu")
+    sd = {k: v for k, v in metric.net.clip_model[0].state_dict().items()}
+    model = ec.load_model(sd, bpe)
+    rng = np.random.default_rng(12)
+    yy, xx = np.mgrid[0:224, 0:288].astype(np.float64)
+    base = np.stack([128 + 80 * np.sin(xx / 23) * np.cos(yy / 31), 128 + 70 * np.sin((xx + yy) / 41), 128 + 90 * np.cos(xx / 17 - yy / 29)], -1)
+    ok = True
+    for name, sigma in (("smooth", 2.0), ("noisy", 25.0)):
+        img = np.clip(np.rint(base + rng.normal(0, sigma, base.shape)), 0, 255).astype(np.uint8)
+        ref = float(metric(torch.from_numpy(img).permute(2, 0, 1)[None].float() / 255.0))
+        got = ec.clipiqa(img, model)
+        print(f"  [9] pyiqa CLIP-IQA ({name}) {ref:.6f} vs evaluate_clipiqa {got:.6f} (absolute {abs(got - ref):.2e})")
+        out[f"clipiqa_{name}"], out[f"clipiqa_{name}_ref"] = img, np.float64(ref)
+        ok = ok and abs(got - ref) <= 1e-5
+    return ok
+
+
 def pin_ftfy(out):
     import ftfy
     from instarevive_amd.captions import fix_text
@@ -252,12 +281,13 @@ def main():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("--dit", default=None, help="folder of a diffusers Transformer2DModel (the converted PixArt / InstaRevive transformer): also compare at full size")
     ap.add_argument("--vae", default=None, help="folder of the diffusers AutoencoderKL (sd-vae-ft-ema): also compare at full size")
+    ap.add_argument("--clip_bpe", default=None, help="folder of CLIP's BPE table (bpe_simple_vocab_16e6.txt.gz): needed by item 9")
     ap.add_argument("--out", default=OUT)
     a = ap.parse_args()
     out, verdict = {}, {}
     for name, fn, args in (("diffusers DiT (items 1, 2)", pin_dit, (None,)), ("diffusers VAE (item 3)", pin_vae, (None,)),
                            ("open_clip (item 4)", pin_clip, ()), ("pyiqa (item 5)", pin_iqa, ()), ("ftfy (item 6)", pin_ftfy, ()), ("lpips (item 7)", pin_lpips, ()),
-                           ("pyiqa NIQE (item 8)", pin_niqe, ())):
+                           ("pyiqa NIQE (item 8)", pin_niqe, ()), ("pyiqa CLIP-IQA (item 9)", pin_clipiqa, (a.clip_bpe,))):
         print(name)
         try:
             verdict[name] = fn(out, *args)
