@@ -56,6 +56,12 @@ def parse_args():
     ap.add_argument("--clipiqa_model", default=None, help="score CLIP-IQA (no reference needed) of both output folders on the GPU (inference.py --clipiqa_model: "
                     "OpenAI's RN50.pt or an .npz). Works with or without --gt and --niqe_params; its column comes last. --image_size must be at least 32")
     ap.add_argument("--clip_bpe", default=None, help="with --clipiqa_model: the folder that holds CLIP's BPE table (inference.py --clip_bpe)")
+    ap.add_argument("--degrade", nargs="?", const="lq", default=None, metavar="lq|FILE.json", help="--input holds GROUND TRUTH: the centre crops are degraded on "
+                    "the GPU (inference.py --degrade: blur, bilinear downsample, noise, JPEG, bilinear resize back) and the LQ images restored; needs "
+                    "--image_size to be a multiple of 64 of at least 512 (the crop is then the network input as it is). Without --gt the input folder "
+                    "is the ground truth of --lpips_lin / --niqe_params / --clipiqa_model")
+    ap.add_argument("--degrade_seed", type=int, default=231, help="with --degrade: seeds every file's draws together with the crc32 of its input-relative path")
+    ap.add_argument("--save_lq", default=None, metavar="DIR", help="with --degrade: write the synthesised LQ crops to DIR")
     ap.add_argument("--workers", type=int, default=-1, help="host threads for decoding / PNG encoding (inference.py --workers)")
     return ap.parse_args()
 
@@ -75,6 +81,21 @@ def main():
     niqe_params = cli.load_niqe_params(args)
     clipiqa_model = cli.load_clipiqa_model(args)
     noref = bool(niqe_params) or clipiqa_model is not None
+    recipe = geo = None
+    if args.save_lq and not args.degrade:
+        raise SystemExit("--save_lq writes the images --degrade synthesises: give --degrade as well")
+    if args.degrade:
+        from instarevive_amd import degrade as D
+        from instarevive_amd.resample import ResizeJob, job_geometry
+        try:
+            recipe = D.load_recipe(args.degrade)
+        except (D.DegradeError, OSError, ValueError) as e:
+            raise SystemExit(f"--degrade: {e}")
+        geo = job_geometry((args.image_size, args.image_size), 1, False, 512)   # the device input route of inference.py --resize gpu
+        if geo.chain or geo.net_hw != (args.image_size, args.image_size):
+            raise SystemExit("--degrade needs --image_size to be a multiple of 64 of at least 512 (the crop is the network input as it is)")
+        if not args.gt and (args.lpips_lin or noref):
+            args.gt = args.input   # the files that are degraded are the ground truth of what is restored from them
     cli.check_device(args.device)
     rank, world, local = parallel.init_distributed()
     torch.cuda.set_device(local)
@@ -91,7 +112,7 @@ def main():
 
     caps = Captions(args.caption_dir, m.y, m.y_mask, args.input) if args.caption_dir else None
 
-    reports, truths = None, []
+    reports, truths, records, dparams, lq_images = None, [], [], [], []
     if (args.lpips_lin or args.lpips_alexnet) and not args.gt:
         raise SystemExit("--lpips_lin / --lpips_alexnet score against ground truth: give --gt as well")
     if args.lpips_alexnet and not args.lpips_lin:
@@ -113,7 +134,11 @@ def main():
 
     def read(f):
         crop = center_crop_arr(Image.open(f).convert("RGB"), args.image_size)
-        return (crop, np.ascontiguousarray(center_crop_arr(lookup.load(f), args.image_size))) if lookup else (crop, None)
+        gt = np.ascontiguousarray(center_crop_arr(lookup.load(f), args.image_size)) if lookup else None
+        if recipe is None:
+            return crop, gt
+        crop = np.ascontiguousarray(crop)   # the draws (and the noise field) are made here, on a reader thread
+        return crop, gt, D.draw(recipe, os.path.relpath(f, args.input), crop.shape[0], crop.shape[1], args.degrade_seed)
 
     def feed():
         # decode + centre crop run ahead of the GPU on the reader threads, in file order
@@ -122,11 +147,22 @@ def main():
             pairs = [next(crops) for _ in group]
             imgs = [p[0] for p in pairs]
             truths.append([p[1] for p in pairs])
+            if recipe is not None:
+                records.append([ResizeJob(p[0], geo) for p in pairs])
+                dparams.append([p[2] for p in pairs])
             yield (imgs, *caps.batch(group)) if caps else imgs
 
     def batch_truths():   # in step with feed(): process_stream advances it right after it has drawn a batch
         while True:
             yield truths.pop(0)
+
+    def batch_records():
+        while True:
+            yield records.pop(0)
+
+    def batch_dparams():
+        while True:
+            yield dparams.pop(0)
 
     def save(dst, img):
         os.makedirs(os.path.dirname(dst) or ".", exist_ok=True)
@@ -143,7 +179,8 @@ def main():
                              y=m.y, y_mask=m.y_mask, noise_scheduler=m.noise_scheduler, return_stage1=True,
                              png=[[(args.image_size, args.image_size)] * len(group) for group in batches] if gpu_png else None, png_wrap=False,
                              gt=batch_truths() if lookup else None, **with_lpips, **({"niqe": niqe_params} if niqe_params else {}),
-                             **({"clipiqa": True} if clipiqa_model else {}))
+                             **({"clipiqa": True} if clipiqa_model else {}),
+                             **({"resize": batch_records(), "degrade": batch_dparams(), "lq_sink": lq_images.append if args.save_lq else None} if recipe else {}))
     no_niqe = no_clipiqa = 0
     for group, out in zip(batches, results):
         preds, stage1 = out[:2]
@@ -159,6 +196,10 @@ def main():
         for f, pred, cond in zip(group, preds, stage1):
             for folder, img in ((args.output, pred), (cond_dir, cond)):
                 pools.write_behind(save, out_name(folder, args.input, f), img)
+        if args.save_lq:
+            for f, lq in zip(group, lq_images.pop(0)):
+                pools.write_behind(save, os.path.splitext(os.path.join(args.save_lq, os.path.relpath(f, args.input)))[0] + ".png", lq)
+                pools.written -= 1   # a file counts by its results
         print(f"[rank {rank}] queued {len(group)} images ({group[0]} ...)")
     pools.drain()
     print(f"[rank {rank}] saved {pools.written} files")

@@ -32,7 +32,9 @@ enum { IR_STAGE_SWINIR = 0, IR_STAGE_VAE_ENCODE = 1, IR_STAGE_DIT = 2, IR_STAGE_
        IR_STAGE_LPIPS = 13 /* ir_lpips: n pairs, h, w = the compared rectangle; depends on the sizes alone (ctx may be NULL) */,
        IR_STAGE_NIQE = 14 /* ir_niqe_stats: n images, h, w = the scored rectangle; depends on the sizes alone (ctx may be NULL) */,
        IR_STAGE_CLIPIQA = 15 /* ir_clipiqa: n images, h, w = the scored rectangle; depends on the sizes and on the layer counts bound by
-                                ir_clipiqa_configure (0 for a context that is not configured) */ };
+                                ir_clipiqa_configure (0 for a context that is not configured) */,
+       IR_STAGE_DEGRADE = 16 /* ir_degrade: h, w = the image size; the images of a batch share one workspace, so n only has to be >= 1; depends
+                                on the size alone (ctx may be NULL) */ };
 /* ir_pipeline flags */
 enum { IR_FLAG_NO_PREPROCESS = 1, IR_FLAG_TILED = 2, IR_FLAG_FIX_WAVELET = 4, IR_FLAG_FIX_ADAIN = 8,
        /* ir_pipeline only, needs ir_dit_control_configure: run the DiT step with the ControlNet-Half branch, condition latent
@@ -399,6 +401,39 @@ int ir_clipiqa_scale_table(float* tab768);
 int ir_clipiqa_configure(ir_ctx* ctx, const int layers[4], int width, int heads, int out_dim, int n_pairs, float logit_scale_exp);
 int ir_clipiqa(ir_ctx* ctx, void* stream, const uint8_t* img, int rows, long pitch, int n, int h, int w, double* scores, float* feat_or_null,
                void* ws, size_t ws_bytes);
+
+/* Low-quality inputs from ground truth on the device: the first-order degradation of the reference's dataset/codeformer.py:140-163 and
+ * tools/lq.py - a K x K blur, a bilinear downsample, Gaussian noise, a JPEG round trip, a bilinear resize back - without OpenCV and without
+ * files in between. tools/degrade_folder.py states the definition in numpy, down to the order of operations, and is the model of this call:
+ * the bytes are equal. Per image: x = float32(v / 255.0); correlation with kernel [ksize][ksize] (fp64, ksize odd, at most 41: the halo tile
+ * of a 32 x 32 patch lives in 64 KB of LDS), border BORDER_REFLECT_101, fp64 accumulation in row-major tap order with separate multiplies and
+ * adds, rounded once to float32; cv2.resize's INTER_LINEAR for floats to lh x lw; x += noise * sigma / 255 in float32 and the clip to [0, 1]
+ * (noise: [lh][lw][3] floats, NULL skips both); for q in 1 .. 100 libjpeg's round trip of the bytes rint(x * 255) - baseline, 4:2:0, ISLOW
+ * DCT, fancy upsampling, Pillow's and OpenCV's defaults, in integer arithmetic with 64-bit sums (entropy coding is lossless and left out) -
+ * and x = float32(byte) / 255 (q = 0 skips it); INTER_LINEAR back to h x w; then IR_DEGRADE_NORM_NONE: uint8(trunc(clip(x, 0, 1) * 255)),
+ * IR_DEGRADE_NORM_MAX: uint8(trunc(max(x, 0) / m * 255)) with m the image's maximum (tools/lq.py:45; m = 0 gives zeros), found through
+ * per-workgroup partial maxima folded in a fixed order, no floating-point atomics.
+ * ir_degrade_qtables (host only, no context): the two quantisation tables of quality q in 1 .. 100, natural order - the ones the kernels use.
+ * img and out are [n][rows][pitch] bytes (RGB8, the top-left h x w of each image is read and written; out must not overlap img); params is a
+ * HOST array of n records, read before the call returns, whose kernel and noise members are device pointers; jpeg_or_null, when not NULL, is
+ * [n][h * w * 3] bytes of which image i's first lh * lw * 3 receive the bytes behind the JPEG step (untouched for q = 0). Stream-ordered, no
+ * allocation, no host synchronisation (capturable); the images follow each other through one workspace. ws: 256-byte aligned,
+ * ir_workspace_bytes(ctx, IR_STAGE_DEGRADE, n, h, w, 0, 0, 0) bytes (two float images and the YCbCr planes: 107 MB for 2048 x 2048).
+ * Returns -1 (nothing launched, out untouched) for a null pointer (a record's kernel included), n < 1, h above rows, a pitch below 3 w, an
+ * even ksize or one above 41, min(h, w) < ksize / 2 + 1 (the reflection would leave the image), lh or lw below 8 or above h or w, q outside
+ * 0 .. 100, an unknown norm, or a short or misaligned workspace. The bound of 8 keeps clear of libjpeg's narrow-chroma rule: when the chroma
+ * plane is 2 or fewer samples wide (lw <= 4) it replicates chroma instead of interpolating it, and a block-sized image is the least a JPEG
+ * round trip is meant for. */
+enum { IR_DEGRADE_NORM_NONE = 0, IR_DEGRADE_NORM_MAX = 1 };
+typedef struct ir_degrade_params {
+    const double* kernel;   /* device, [ksize][ksize] */
+    const float* noise;     /* device, [lh][lw][3], or NULL */
+    int ksize, lh, lw, q, norm;
+    float sigma;
+} ir_degrade_params;
+int ir_degrade_qtables(int q, uint16_t* luma64, uint16_t* chroma64);
+int ir_degrade(ir_ctx* ctx, void* stream, const uint8_t* img, int rows, long pitch, int n, int h, int w, const ir_degrade_params* params,
+               uint8_t* out, uint8_t* jpeg_or_null, void* ws, size_t ws_bytes);
 
 /* Single-kernel entry points, exported so tests/ can check every kernel against the oracle through the same ABI. */
 int ir_op_conv(ir_ctx* ctx, void* stream, const uint16_t* in, const uint16_t* wgt, const float* bias, void* out, int n, int h, int w,

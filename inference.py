@@ -117,6 +117,17 @@ def parse_args() -> Namespace:
                         "`clipiqa: x.xxxxx` come last. Which files are scored follows --gt's rule; files below 32 pixels on an edge are counted as not scored")
     parser.add_argument("--clip_bpe", type=str, default=None, help="with --clipiqa_model: the folder that holds CLIP's BPE table (bpe_simple_vocab_16e6.txt.gz, or "
                         "vocab.json + merges.txt), from which the ten prompts are tokenised")
+    parser.add_argument("--degrade", type=str, nargs="?", const="lq", default=None, metavar="lq|FILE.json", help="--input holds GROUND TRUTH: synthesise every "
+                        "file's low-quality image on the GPU (ir_degrade; the definition of tools/degrade_folder.py) and restore that - the first-order "
+                        "degradation of the reference's dataset/codeformer.py and tools/lq.py: 41 x 41 iso / aniso Gaussian blur, bilinear downsample by "
+                        "U[2,4], Gaussian noise of sigma U[0,20], JPEG at quality int(U[60,100]), bilinear resize back. `lq` (default) holds tools/lq.py's "
+                        "constants; a JSON file may set blur_kernel_size, kernel_list (iso, aniso), kernel_prob, blur_sigma, downsample_range, noise_range, "
+                        "jpeg_range and norm (none, or max for tools/lq.py's division by the maximum). No OpenCV, no second folder: the LQ image never "
+                        "leaves the device. Switches --resize gpu on; not offered with --show_lq, --use_center_crop, --shard_tiles. Without --gt the input "
+                        "folder is the ground truth of --metrics_out / --lpips_lin / --niqe_params / --clipiqa_model")
+    parser.add_argument("--degrade_seed", type=int, default=231, help="with --degrade: a file's parameters are drawn from a generator seeded by this number "
+                        "and the crc32 of its input-relative path, whatever the batch size, worker count or rank")
+    parser.add_argument("--save_lq", type=str, default=None, metavar="DIR", help="with --degrade: write the synthesised LQ images to DIR/<input-relative path>.png")
     parser.add_argument("--workers", type=int, default=-1, help="host threads that decode / resize the inputs and resize / PNG-encode the results "
                         "around the GPU (PIL releases the GIL there); -1 = this process's CPU share, 0 = everything on the main thread like the reference")
     return parser.parse_args()
@@ -236,6 +247,7 @@ class Job:
     geo: object = None         # resample.job_geometry() of the file: resize chain, valid extent, network size, LANCZOS target
     raw: np.ndarray = None     # the decoded file, HWC uint8: what is uploaded
     gt: np.ndarray = None      # --gt: the ground truth of a job that is scored on the device (png_rect() is not None), HWC uint8 of the saved size
+    deg: object = None         # --degrade: the file's degrade.Params (raw is then ground truth; the device makes the LQ image)
 
 
 def net_shape(job: Job) -> tuple:
@@ -250,7 +262,8 @@ def attach_gt(job: Job, args: Namespace) -> Job:
     if rect is not None:
         from instarevive_amd.metrics import MetricsError
         path = lookup.path(job.src)
-        gt = np.array(Image.open(path).convert("RGB"))
+        same = job.deg is not None and os.path.abspath(path) == os.path.abspath(job.src)   # --degrade without --gt: the decoded file is the ground truth
+        gt = job.raw if same else np.array(Image.open(path).convert("RGB"))
         if gt.shape[:2] != tuple(rect):
             raise MetricsError(f"--gt: {path} is {gt.shape[0]} x {gt.shape[1]}, the result of {job.src} is {rect[0]} x {rect[1]}")
         job.gt = gt
@@ -268,7 +281,11 @@ def decode_job(file_path: str, repeat: int, args: Namespace) -> Job:
         from instarevive_amd.resample import job_geometry
         geo = job_geometry(lq.size, args.sr_scale, args.tiled, args.tile_size)
         folder, stem, _ = get_file_name_parts(os.path.join(args.output, os.path.relpath(file_path, args.input)))
-        return Job(os.path.join(folder, f"{stem}_{repeat}.png"), lq, None, geo.valid_hw, file_path, geo, np.array(lq))
+        job = Job(os.path.join(folder, f"{stem}_{repeat}.png"), lq, None, geo.valid_hw, file_path, geo, np.array(lq))
+        if getattr(args, "degrade_recipe", None):   # the draws (and the noise field) are made here, on a reader thread
+            from instarevive_amd.degrade import draw
+            job.deg = draw(args.degrade_recipe, os.path.relpath(file_path, args.input), lq.height, lq.width, args.degrade_seed)
+        return job
     if args.sr_scale != 1:
         lq = lq.resize(tuple(math.ceil(edge * args.sr_scale) for edge in lq.size), Image.BICUBIC)
     if args.use_center_crop and not args.tiled:
@@ -308,6 +325,14 @@ def write_png_file(job: Job, blob) -> None:
     with open(job.save_path, "wb") as f:
         f.write(blob)
     print(f"save to {job.save_path}")
+
+
+def write_lq(job: Job, lq: np.ndarray, args: Namespace) -> None:
+    """--save_lq: the LQ image the device synthesised, as DIR/<input-relative path>.png."""
+    path = os.path.splitext(os.path.join(args.save_lq, os.path.relpath(job.src, args.input)))[0] + ".png"
+    os.makedirs(os.path.dirname(path) or ".", exist_ok=True)
+    Image.fromarray(lq).save(path)
+    print(f"save lq to {path}")
 
 
 def write_job(job: Job, pred: np.ndarray, stage1_pred, args: Namespace) -> None:
@@ -432,6 +457,20 @@ def main() -> None:
     niqe_params = load_niqe_params(args)
     clipiqa_model = load_clipiqa_model(args)
     noref = bool(niqe_params) or clipiqa_model is not None
+    if args.save_lq and not args.degrade:
+        raise SystemExit("--save_lq writes the images --degrade synthesises: give --degrade as well")
+    if args.degrade:
+        from instarevive_amd import degrade as D
+        try:
+            D.check_flags(args)
+            args.degrade_recipe = D.load_recipe(args.degrade)
+        except (D.DegradeError, OSError, ValueError) as e:
+            raise SystemExit(f"--degrade: {e}")
+        if args.resize != "gpu":
+            print(f"--degrade: the LQ images are made on the device, switching --resize gpu on")
+            args.resize = "gpu"
+        if not args.gt and (args.metrics_out or args.lpips_lin or noref):
+            args.gt = args.input   # the files that are degraded are the ground truth of what is restored from them
     torch.manual_seed(args.seed)  # the path is deterministic; kept for surface compatibility (pl.seed_everything)
     args.device = check_device(args.device)
     rank, world, local = parallel.init_distributed()
@@ -533,6 +572,8 @@ def main() -> None:
     records = deque()   # --resize gpu, per batch: the decoded files and their geometry
     truths = deque()   # --gt, per batch: the ground-truth images, or None for a batch that is not scored
     sizes = deque()    # --niqe_params / --clipiqa_model, per batch: the saved sizes, or None for a batch that is not scored
+    dparams = deque()  # --degrade, per batch: the files' degrade.Params
+    lq_images = deque()   # --save_lq, per batch: the LQ images process_stream hands over right before the batch's results
 
     def feed():
         for group in batches_of(jobs, max(args.batch_size, 1), (lambda j: png_rect(j, args) is not None) if gpu_png or report else None):
@@ -549,6 +590,8 @@ def main() -> None:
             if args.resize_on_gpu:
                 from instarevive_amd.resample import ResizeJob
                 records.append([ResizeJob(j.raw, j.geo) for j in group])
+                if args.degrade:
+                    dparams.append([j.deg for j in group])
             yield (imgs, *caps.batch([j.src for j in group])) if caps else imgs
 
     def batch_rects():   # in step with feed(): process_stream advances it right after it has drawn a batch
@@ -563,6 +606,10 @@ def main() -> None:
         while True:
             yield truths.popleft()
 
+    def batch_dparams():
+        while True:
+            yield dparams.popleft()
+
     def batch_sizes():
         while True:
             yield sizes.popleft()
@@ -576,9 +623,14 @@ def main() -> None:
                               resize=batch_records() if args.resize_on_gpu else None, gt=batch_truths() if args.gt else None,
                               **({"lpips": True} if report and report.lpips else {}),
                               **({"niqe": niqe_params} if niqe_params else {}), **({"clipiqa": True} if clipiqa_model else {}),
-                              **({"niqe_rects": batch_sizes()} if noref else {}), **common):
+                              **({"niqe_rects": batch_sizes()} if noref else {}),
+                              **({"degrade": batch_dparams(), "lq_sink": lq_images.append if args.save_lq else None} if args.degrade else {}), **common):
         preds, stage1 = out[:2]
         group = todo.pop(0)
+        if args.save_lq:
+            for job, lq in zip(group, lq_images.popleft()):
+                pools.write_behind(write_lq, job, lq, args)
+                pools.written -= 1   # a file counts once, by its result
         if report:
             if len(out) > 2:
                 for job, score in zip(group, out[2][0]):

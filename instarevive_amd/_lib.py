@@ -26,13 +26,16 @@ SYMBOLS = [
     "ir_dit_set_prompts", "ir_op_attention_kv_groups", "ir_graph_records", "ir_op_vae_segment", "ir_op_vae_segment_ws", "ir_op_vae_segment_info",
     "ir_png_bound", "ir_png_encode", "ir_resample_plan_bytes", "ir_resample_plan", "ir_resample_u8", "ir_metrics_y",
     "ir_lpips_scale_table", "ir_lpips_configure", "ir_lpips", "ir_niqe_window", "ir_niqe_stats",
-    "ir_clipiqa_scale_table", "ir_clipiqa_configure", "ir_clipiqa",
+    "ir_clipiqa_scale_table", "ir_clipiqa_configure", "ir_clipiqa", "ir_degrade_qtables", "ir_degrade",
 ]
 
 STAGE_SWINIR, STAGE_VAE_ENCODE, STAGE_DIT, STAGE_VAE_DECODE, STAGE_PIPELINE, STAGE_COLORFIX, STAGE_T5, STAGE_CLDM, STAGE_CLDM_PIPELINE, STAGE_CLIP_TEXT, STAGE_PNG, STAGE_RESAMPLE, STAGE_METRICS = range(13)
 STAGE_LPIPS = 13
 STAGE_NIQE = 14
 STAGE_CLIPIQA = 15
+STAGE_DEGRADE = 16
+DEGRADE_NORM_NONE, DEGRADE_NORM_MAX = 0, 1
+DEGRADE_MAX_KSIZE, DEGRADE_MIN_LOW = 41, 8
 LPIPS_NOT_CONFIGURED = -12   # ir_lpips before ir_lpips_configure
 CLIPIQA_NOT_CONFIGURED = -13   # ir_clipiqa before ir_clipiqa_configure
 FLAG_NO_PREPROCESS, FLAG_TILED, FLAG_FIX_WAVELET, FLAG_FIX_ADAIN, FLAG_CONTROL_LQ, FLAG_GRAPH, FLAG_FP8 = 1, 2, 4, 8, 16, 32, 64
@@ -46,6 +49,12 @@ RESAMPLE_BICUBIC, RESAMPLE_LANCZOS = 0, 1
 ACT_NONE, ACT_GELU_ERF, ACT_GELU_TANH, ACT_LRELU, ACT_SILU = range(5)
 
 _lib = None
+
+
+class DegradeParams(C.Structure):
+    """ir_degrade_params (include/instarevive_hip.h): one image's record; kernel and noise are device addresses."""
+    _fields_ = [("kernel", C.c_void_p), ("noise", C.c_void_p), ("ksize", C.c_int), ("lh", C.c_int), ("lw", C.c_int), ("q", C.c_int),
+                ("norm", C.c_int), ("sigma", C.c_float)]
 
 
 class NativeLibraryError(RuntimeError):
@@ -170,6 +179,8 @@ def load_library():
     lib.ir_clipiqa_scale_table.argtypes = [vp]
     lib.ir_clipiqa_configure.argtypes = [vp, C.POINTER(C.c_int), i, i, i, i, C.c_float]
     lib.ir_clipiqa.argtypes = [vp, vp, vp, i, C.c_long, i, i, i, vp, vp, vp, sz]
+    lib.ir_degrade_qtables.argtypes = [i, vp, vp]
+    lib.ir_degrade.argtypes = [vp, vp, vp, i, C.c_long, i, i, i, C.POINTER(DegradeParams), vp, vp, vp, sz]
     for name in SYMBOLS:
         fn = getattr(lib, name)
         if fn.restype is C.c_int and name not in ("ir_abi_version",):

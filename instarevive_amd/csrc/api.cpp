@@ -2951,7 +2951,45 @@ int ir_niqe_stats(ir_ctx* c, void* stream, const uint8_t* img, int rows, long pi
     return 0;
 }
 
+// ---------------------------------------------------------------- low-quality inputs from ground truth (degrade.hip)
+int ir_degrade_qtables(int q, uint16_t* luma64, uint16_t* chroma64) {
+    if (!luma64 || !chroma64 || q < 1 || q > 100) return -1;
+    ir_degrade_qtables_host(q, luma64, chroma64);
+    return 0;
+}
+int ir_degrade(ir_ctx* c, void* stream, const uint8_t* img, int rows, long pitch, int n, int h, int w, const ir_degrade_params* params, uint8_t* out,
+               uint8_t* jpeg_or_null, void* ws, size_t ws_bytes) {
+    if (!c || !img || !params || !out || !ws) return fail(c, -1, "ir_degrade: null argument");
+    if (n < 1 || h < 1 || w < 1 || h > rows || pitch < 3L * w || (long)h * w > (1L << 28))
+        return fail(c, -1, "ir_degrade: bad size (n %d, %d x %d in %d rows pitch %ld)", n, h, w, rows, pitch);
+    for (int i = 0; i < n; ++i) {   // every image is checked before the first launch
+        const ir_degrade_params& p = params[i];
+        if (!p.kernel) return fail(c, -1, "ir_degrade: image %d has no blur kernel", i);
+        if (p.ksize < 1 || p.ksize > IR_DEGRADE_MAX_KSIZE || !(p.ksize & 1))
+            return fail(c, -1, "ir_degrade: image %d: the blur kernel size %d is not odd and within 1 .. %d", i, p.ksize, IR_DEGRADE_MAX_KSIZE);
+        if (h < p.ksize / 2 + 1 || w < p.ksize / 2 + 1)
+            return fail(c, -1, "ir_degrade: a %d x %d image is too small for a %d x %d blur (reflection needs %d pixels)", h, w, p.ksize, p.ksize, p.ksize / 2 + 1);
+        if (p.lh < IR_DEGRADE_MIN_LOW || p.lw < IR_DEGRADE_MIN_LOW || p.lh > h || p.lw > w)
+            return fail(c, -1, "ir_degrade: image %d: low-resolution size %d x %d outside %d .. %d x %d", i, p.lh, p.lw, IR_DEGRADE_MIN_LOW, h, w);
+        if (p.q < 0 || p.q > 100) return fail(c, -1, "ir_degrade: image %d: JPEG quality %d outside 0 .. 100", i, p.q);
+        if (p.norm != IR_DEGRADE_NORM_NONE && p.norm != IR_DEGRADE_NORM_MAX) return fail(c, -1, "ir_degrade: image %d: unknown norm %d", i, p.norm);
+        if ((reinterpret_cast<uintptr_t>(p.kernel) & 7) || (reinterpret_cast<uintptr_t>(p.noise) & 3))
+            return fail(c, -1, "ir_degrade: image %d: misaligned kernel or noise pointer", i);
+    }
+    if (ws_bytes < ir_degrade_workspace(h, w) || (reinterpret_cast<uintptr_t>(ws) & 255))
+        return fail(c, -1, "ir_degrade: workspace too small or unaligned (%zu < %zu)", ws_bytes, ir_degrade_workspace(h, w));
+    use_ctx(c);
+    for (int i = 0; i < n; ++i) {
+        const ir_degrade_params& p = params[i];
+        if (ir_launch_degrade(img + (long)i * rows * pitch, pitch, h, w, p.kernel, p.ksize, p.lh, p.lw, p.sigma, p.q, p.noise, p.norm,
+                              out + (long)i * rows * pitch, pitch, jpeg_or_null ? jpeg_or_null + (long)i * h * w * 3 : nullptr, ws, (hipStream_t)stream))
+            return fail(c, -100, "ir_degrade: launch failed (image %d)", i);
+    }
+    return 0;
+}
+
 size_t ir_workspace_bytes(ir_ctx* c, int stage, int n, int h, int w, int flags, int tile_size, int tile_stride) {
+    if (stage == IR_STAGE_DEGRADE) return n < 1 ? 0 : ir_degrade_workspace(h, w);   // a function of the image size alone (the images of a batch share it): no context needed
     if (stage == IR_STAGE_NIQE) return (n < 1 || h < IR_NIQE_BLOCK || w < IR_NIQE_BLOCK) ? 0 : niqe_workspace(n, h, w);   // a function of the sizes alone: no context needed
     if (stage == IR_STAGE_CLIPIQA) {   // a function of the sizes and of the configured layer counts
         IrClipiqaPlan pl;

@@ -281,6 +281,18 @@ int ir_clipiqa_plan(const IrClipiqaModel& m, int n, int h, int w, IrClipiqaPlan*
 int ir_launch_clipiqa(const IrClipiqaModel& m, const uint8_t* img, int rows, long pitch, int n, int h, int w, double* scores, float* feat, void* ws,
                       hipStream_t s);
 
+// ---- low-quality inputs from ground truth (degrade.hip)
+// One image: blur (K x K fp64 taps in device memory, K odd, at most IR_DEGRADE_MAX_KSIZE: the float halo tile of a 32 x 32 patch must fit in 64 KB
+// of LDS), bilinear to lh x lw, noise (or NULL), the JPEG round trip at q (0: none), bilinear back, bytes (norm: include/instarevive_hip.h's IR_DEGRADE_NORM_*). jpeg: NULL or lh x lw x 3 bytes behind
+// the JPEG step (written when q > 0). ws: ir_degrade_workspace(h, w) bytes, 256-byte aligned. Returns -1 with nothing launched for a size the
+// kernels do not take. ir_degrade_qtables_host: jpeg_set_quality's two tables (natural order) for q in 1 .. 100.
+#define IR_DEGRADE_MAX_KSIZE 41
+#define IR_DEGRADE_MIN_LOW 8
+void ir_degrade_qtables_host(int q, uint16_t* luma64, uint16_t* chroma64);
+size_t ir_degrade_workspace(int h, int w);
+int ir_launch_degrade(const uint8_t* img, long pitch, int h, int w, const double* k, int K, int lh, int lw, float sigma, int q, const float* noise,
+                      int norm, uint8_t* out, long out_pitch, uint8_t* jpeg, void* ws, hipStream_t s);
+
 // ---- layout / elementwise (elementwise.hip)
 int ir_launch_u8_to_nchw(const uint8_t* in, float* out, int N, int H, int W, hipStream_t s);
 int ir_launch_swin_prep(const float* x_nchw, bf16_t* out, int N, int H, int W, const float* mean3, float img_range, hipStream_t s);

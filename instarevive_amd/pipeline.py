@@ -370,7 +370,8 @@ def _launch_pipeline(ctx, st, slot, n, h, w, flags, tile_size, tile_stride, acp,
 def process(model, control_imgs: List[np.ndarray], strength: float, color_fix_type: str, disable_preprocess_model: bool, tiled: bool,
             tile_size: int, tile_stride: int, preprocess_model=None, vae=None, y=None, y_mask=None, noise_scheduler=None,
             fused: bool = True, graph: bool = False, return_stage1: bool = True, fp8: bool = False, png=None,
-            resize=None, gt=None, lpips: bool = False, niqe=None, niqe_rects=None, clipiqa: bool = False) -> Tuple[List[np.ndarray], List[np.ndarray]]:
+            resize=None, gt=None, lpips: bool = False, niqe=None, niqe_rects=None, clipiqa: bool = False, degrade=None,
+            lq_sink=None) -> Tuple[List[np.ndarray], List[np.ndarray]]:
     """test_scripts/inference.py:55-166. control_imgs: list of HWC uint8 RGB arrays of equal size (multiples of 64).
     Returns (preds, stage1_preds) as lists of HWC uint8 arrays (stage1_preds is empty with return_stage1=False, which skips its
     conversion and download).
@@ -403,10 +404,16 @@ def process(model, control_imgs: List[np.ndarray], strength: float, color_fix_ty
     tuple. An image without a score (an edge below 96 pixels, fewer than two complete feature rows) gets NaN.
     clipiqa (fused form only; with or without gt and niqe): score CLIP-IQA as well - ir_clipiqa with the model instarevive_amd.clipiqa.configure()
     bound to the models' context, queued behind ir_niqe_stats on the same final rectangles (niqe_rects serves both). Its value is the last of
-    every tuple: (clipiqa,), (niqe, clipiqa), (psnr_y, ssim_y[, lpips][, niqe], clipiqa). An image below 32 pixels on an edge gets NaN."""
+    every tuple: (clipiqa,), (niqe, clipiqa), (psnr_y, ssim_y[, lpips][, niqe], clipiqa). An image below 32 pixels on an edge gets NaN.
+    degrade (with resize): one instarevive_amd.degrade.Params per image - the decoded files are GROUND TRUTH, and between the upload and the
+    bicubic chain ir_degrade makes each one's LQ image on the device (blur, bilinear downsample, noise, JPEG round trip, bilinear resize back;
+    tools/degrade_folder.py is the definition), which the network then restores. lq_sink: called once with the list of those LQ images (HWC
+    uint8, the decoded files' sizes) after they have been downloaded, before process() returns."""
     noise_scheduler = noise_scheduler or DDPMScheduler()
     if lpips and gt is None:
         raise ValueError("process(lpips=True) needs gt=: LPIPS is scored against the ground truth")
+    if degrade is not None and resize is None:
+        raise ValueError("process(degrade=...) needs resize=: the ground truth is degraded on the device input route")
     if resize is not None:
         from .resample import ResizeSlot, check_records
         n, h, w = check_records(resize)
@@ -434,8 +441,10 @@ def process(model, control_imgs: List[np.ndarray], strength: float, color_fix_ty
             st.upload(0)
         else:
             rs = ResizeSlot.get(ctx, 0, "sync")
-            rs.fill(resize)
+            rs.fill(resize, degrade)
             rs.upload()
+            if degrade is not None:
+                rs.degrade(resize)
             _resize_workspace(ctx, resize)
         if png is not None:
             _png_workspace(ctx, n, h, w)
@@ -462,11 +471,16 @@ def process(model, control_imgs: List[np.ndarray], strength: float, color_fix_ty
         if nq is not None:
             _queue_niqe(nq, st, 0, n, return_stage1, res, res1)
             nq.download()
+        want_lq = degrade is not None and lq_sink is not None
+        if want_lq:
+            rs.download_lq()
         if png is not None:
             if rs is None:
                 enc = _queue_png(ctx, st, 0, n, h, w, png, return_stage1, "sync")
             enc.fetch_sizes()
             torch.cuda.current_stream(device).synchronize()
+            if want_lq:
+                lq_sink(rs.host_lq(resize))
             files = enc.fetch(2 * n if return_stage1 else n)
             return scored(files[:n], files[n:])
         st.h_out[0].copy_(st.d_out[0], non_blocking=True)
@@ -475,6 +489,8 @@ def process(model, control_imgs: List[np.ndarray], strength: float, color_fix_ty
         if rs is not None:
             rs.download(res + res1)
             torch.cuda.current_stream(device).synchronize()
+            if want_lq:
+                lq_sink(rs.host_lq(resize))
             return scored(_resize_arrays(rs, resize, res, st.h_out[0].numpy()),
                           _resize_arrays(rs, resize, res1, st.h_st1[0].numpy()) if return_stage1 else [])
         torch.cuda.current_stream(device).synchronize()
@@ -537,7 +553,7 @@ def process_stream(model, batches: Iterable[Sequence[np.ndarray]], color_fix_typ
                    tile_size: int, tile_stride: int, preprocess_model=None, vae=None, y=None, y_mask=None, noise_scheduler=None,
                    return_stage1: bool = True, graph: bool = False, fp8: bool = False, png=None,
                    png_wrap: bool = True, resize=None, gt=None, lpips: bool = False, niqe=None,
-                   niqe_rects=None, clipiqa: bool = False) -> Iterator[Tuple[List[np.ndarray], List[np.ndarray]]]:
+                   niqe_rects=None, clipiqa: bool = False, degrade=None, lq_sink=None) -> Iterator[Tuple[List[np.ndarray], List[np.ndarray]]]:
     """process() over a sequence of image batches with the transfers hidden: while batch i computes on the current stream, batch
     i+1 is uploaded and batch i-1 downloaded on a copy stream (two staging slots per batch shape). Yields process()'s result for
     every batch, in order. Needs the fused form (all models instarevive_amd objects on one context). fp8 as in process() (cfg-5:
@@ -557,6 +573,10 @@ def process_stream(model, batches: Iterable[Sequence[np.ndarray]], color_fix_typ
     stream uploads the decoded bytes, the compute stream runs ir_resample_u8 once or twice per image into the staging input ahead of ir_pipeline
     and, behind it, LANCZOS of the valid rectangles back to the LQ sizes where auto_resize enlarged; the batch's lists hold the final images
     as in process(resize=...), and with png (the rectangles are then the final sizes) every file of the batch comes from the device encoder.
+    degrade: an iterable in step with `resize`, advanced like it: per batch None, or one instarevive_amd.degrade.Params per image - the decoded
+    files are then ground truth and ir_degrade makes their LQ images on the device ahead of the bicubic chain, as in process(degrade=...); the
+    kernels and noise fields ride the copy stream with the images. lq_sink: called with the list of a batch's LQ images (downloaded on the
+    copy stream) right before that batch's results are yielded.
     gt: an iterable in step with `batches`, advanced like png / resize: per batch None, or one ground-truth image per image - HWC uint8 RGB of the
     image's FINAL size (the png rectangle, the final size of a resize job, else any top-left rectangle of the network's output). The copy stream
     uploads them with the batch, ir_metrics_y is queued behind ir_pipeline and the LANCZOS calls on the compute stream (under graph=True behind the
@@ -586,6 +606,9 @@ def process_stream(model, batches: Iterable[Sequence[np.ndarray]], color_fix_typ
     it = iter(batches)
     png_it = iter(png) if png is not None else None
     resize_it = iter(resize) if resize is not None else None
+    degrade_it = iter(degrade) if degrade is not None else None
+    if degrade_it is not None and resize_it is None:
+        raise ValueError("process_stream(degrade=...) needs resize=: the ground truth is degraded on the device input route")
     gt_it = iter(gt) if gt is not None else None
     noref = niqe is not None or bool(clipiqa)
     nq_it = iter(niqe_rects) if noref and niqe_rects is not None else None
@@ -595,6 +618,9 @@ def process_stream(model, batches: Iterable[Sequence[np.ndarray]], color_fix_typ
     def upload(batch, slot):
         rects = next(png_it) if png_it is not None else None
         records = next(resize_it) if resize_it is not None else None
+        dparams = next(degrade_it) if degrade_it is not None else None
+        if dparams is not None and records is None:
+            raise ValueError("process_stream: a batch with degrade records needs resize records")
         gts = next(gt_it) if gt_it is not None else None
         sizes = next(nq_it) if nq_it is not None else None
         with_nq = noref and (sizes is not None if nq_it is not None else (gts is not None or gt_it is None))
@@ -605,7 +631,7 @@ def process_stream(model, batches: Iterable[Sequence[np.ndarray]], color_fix_typ
             nq = _niqe_plan(ctx, slot, "stream", niqe, n, h, w, rects, records, gts, sizes, return_stage1, clipiqa) if with_nq else None
             st = _Staging.get(ctx, n, h, w, slots=2, tag="stream")
             rs = ResizeSlot.get(ctx, slot, "stream")
-            rs.fill(records)
+            rs.fill(records, dparams)
             with torch.cuda.stream(copy):
                 ev = rs.upload(copy, main)
                 if sc is not None:
@@ -626,6 +652,8 @@ def process_stream(model, batches: Iterable[Sequence[np.ndarray]], color_fix_typ
         st, slot, (n, h, w), done, enc, rz, sc, nq = job
         done.synchronize()
         scores = (_merged_scores(sc, nq, n, return_stage1),) if sc is not None or nq is not None else ()
+        if rz is not None and rz[0].dparams is not None and lq_sink is not None:
+            lq_sink(rz[0].host_lq(rz[1]))
         if enc is not None:   # the byte counts are here: fetch that many bytes per image
             files = enc.fetch(2 * n if return_stage1 else n, copy, png_wrap)
             return (files[:n], files[n:]) + scores
@@ -672,6 +700,8 @@ def process_stream(model, batches: Iterable[Sequence[np.ndarray]], color_fix_typ
         if nq is not None:
             nq.reserve()
         if rz is not None:
+            if rz[0].dparams is not None:
+                rz[0].degrade(rz[1])
             _resize_workspace(ctx, rz[1])
             rz[0].to_network(rz[1], st.d_in[cur])
         _launch_pipeline(ctx, st, cur, n, h, w, base_flags, tile_size, tile_stride, acp, sf, return_stage1)
@@ -703,6 +733,8 @@ def process_stream(model, batches: Iterable[Sequence[np.ndarray]], color_fix_typ
                         st.h_st1[cur].copy_(st.d_st1[cur], non_blocking=True)
                 if rz is not None:
                     rz[0].download(rz[2] + rz[3])
+            if rz is not None and rz[0].dparams is not None and lq_sink is not None:
+                rz[0].download_lq()
             if sc is not None:
                 sc.download(2 * n if return_stage1 else n)
             if nq is not None:

@@ -4,6 +4,10 @@ separable resampling - integer arithmetic with fixed rounding - so the device's 
 
 job_geometry() is the size arithmetic of a file without its pixels, Plans keeps the coefficient tables (made on the host: they need double
 sin()) per size pair, ResizeSlot the page-locked and device buffers of decoded files and resized results of one staging slot.
+
+With --degrade the decoded files are ground truth: ResizeSlot.fill() packs every file's blur kernel and noise field (degrade.Params) behind
+the images, ResizeSlot.degrade() turns them into LQ images on the device (ir_degrade) between the upload and to_network(), which then reads
+those.
 """
 import ctypes as C
 import math
@@ -153,10 +157,14 @@ class ResizeSlot:
 
     def __init__(self, ctx):
         self.ctx = ctx
-        self.h_raw = self.d_raw = self.mid = self.d_res = self.h_res = None
+        self.h_raw = self.d_raw = self.mid = self.d_res = self.h_res = self.d_lq = self.h_lq = None
         self.h2d_done = None
         self.fresh = False
         self.offsets: List[int] = []
+        self.dparams = None      # degrade.Params of the batch in the slot, one per image, or None
+        self.extras: List[tuple] = []   # per image the offsets of its blur kernel and noise field (or None) in h_raw / d_raw
+        self.img_bytes = 0       # where the images end in h_raw / d_raw (the kernels and noise fields follow)
+        self.lq_made = False
 
     @staticmethod
     def get(ctx, slot=0, tag="sync") -> "ResizeSlot":
@@ -165,8 +173,15 @@ class ResizeSlot:
             pool[(tag, slot)] = ResizeSlot(ctx)
         return pool[(tag, slot)]
 
-    def fill(self, records: Sequence[ResizeJob]) -> None:
-        """Copy the decoded files into the page-locked buffer (after the previous upload out of it has completed)."""
+    def fill(self, records: Sequence[ResizeJob], degrade=None) -> None:
+        """Copy the decoded files into the page-locked buffer (after the previous upload out of it has completed). degrade: one degrade.Params
+        per image, or None - their blur kernels and noise fields travel behind the images."""
+        if degrade is not None:
+            from . import degrade as D
+            if len(degrade) != len(records):
+                raise ValueError("degrade: one parameter record per image")
+            for rec, p in zip(records, degrade):
+                D.check_params(p, *rec.raw.shape[:2])
         if self.h2d_done is not None:
             self.h2d_done.synchronize()
             self.h2d_done = None
@@ -174,6 +189,9 @@ class ResizeSlot:
         for rec in records:
             self.offsets.append(at)
             at += (rec.raw.size + 255) & ~255
+        self.img_bytes, self.dparams, self.extras, self.lq_made = at, degrade, [], False
+        if degrade is not None:
+            at += sum(D.extra_bytes(p) for p in degrade)
         self.h_raw = _grown(self.h_raw, at, pinned=True)
         if self.d_raw is None or self.d_raw.numel() < self.h_raw.numel():
             self.d_raw, self.fresh = _grown(None, self.h_raw.numel(), self.ctx.device), True
@@ -181,6 +199,10 @@ class ResizeSlot:
         host = self.h_raw.numpy()
         for rec, o in zip(records, self.offsets):
             np.copyto(host[o:o + rec.raw.size].reshape(rec.raw.shape), rec.raw)
+        at = self.img_bytes
+        for p in degrade or ():
+            k_at, n_at, at = D.pack_extras(p, host, at)
+            self.extras.append((k_at, n_at))
 
     def upload(self, stream=None, owner=None):
         """Asynchronous H2D copy of the decoded bytes on `stream` (default: the current one); the event behind it is what the next fill() waits for.
@@ -195,12 +217,35 @@ class ResizeSlot:
         self.h2d_done = ev
         return ev
 
+    def degrade(self, records: Sequence[ResizeJob]) -> None:
+        """Between upload() and to_network(), on the current stream: every decoded file (ground truth) becomes its LQ image in d_lq, at the
+        file's offset, by ir_degrade with the parameters fill() staged. The files differ in size, so each is a call of its own."""
+        from . import degrade as D
+        self.d_lq = _grown(self.d_lq, self.img_bytes, self.ctx.device)
+        base = self.d_raw.data_ptr()
+        for rec, p, o, (k_at, n_at) in zip(records, self.dparams, self.offsets, self.extras):
+            h, w = rec.raw.shape[:2]
+            D.launch(self.ctx, base + o, self.d_lq.data_ptr() + o, h, 3 * w, h, w, [D.record(p, base + k_at, base + n_at if n_at is not None else None)])
+        self.lq_made = True
+
+    def download_lq(self) -> None:
+        """Asynchronous D2H copy of the LQ images degrade() made, on the current stream."""
+        self.h_lq = _grown(self.h_lq, self.img_bytes, pinned=True)
+        self.h_lq[:self.img_bytes].copy_(self.d_lq[:self.img_bytes], non_blocking=True)
+
+    def host_lq(self, records: Sequence[ResizeJob]) -> List[np.ndarray]:
+        """The downloaded LQ images (after the copy has completed) as arrays the caller owns."""
+        host = self.h_lq.numpy()
+        return [host[o:o + rec.raw.size].reshape(rec.raw.shape).copy() for rec, o in zip(records, self.offsets)]
+
     def to_network(self, records: Sequence[ResizeJob], d_in: torch.Tensor) -> None:
-        """Per image the bicubic chain from its decoded bytes into its slot of d_in [n][h][w][3], zero padding included, on the current stream."""
+        """Per image the bicubic chain from its decoded bytes (its LQ image after degrade()) into its slot of d_in [n][h][w][3], zero padding
+        included, on the current stream."""
         n, h, w, _ = d_in.shape
+        first = self.d_lq if self.lq_made else self.d_raw
         for i, rec in enumerate(records):
             steps = _steps(rec)
-            src, pitch = self.d_raw.data_ptr() + self.offsets[i], 3 * rec.raw.shape[1]
+            src, pitch = first.data_ptr() + self.offsets[i], 3 * rec.raw.shape[1]
             for k, (ih, iw, oh, ow) in enumerate(steps):
                 if k + 1 < len(steps):   # the uint8 image between two resizes, as the reference has one
                     self.mid = _grown(self.mid, oh * ow * 3, self.ctx.device)

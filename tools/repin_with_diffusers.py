@@ -27,6 +27,9 @@ random-initialised models of reduced width pin it exactly as the 4 GB checkpoint
  9. pyiqa's CLIP-IQA (evaluate_img.py's `create_metric('clipiqa')`: OpenAI CLIP RN50 at the image's own size, no positional embedding in the
     attention pool, five antonym prompt pairs) -> tools/evaluate_clipiqa.py on pyiqa's own RN50 weights and vocabulary (pass --clip_bpe, the
     folder of the BPE table): the ten text rows and the score of two images to 1e-5.
+10. OpenCV's side of the degradation chain (dataset/codeformer.py:151-163, utils/degradation.py:744-747) -> tools/degrade_folder.py: cv2.filter2D
+    with a 41 x 41 kernel (a DFT path: to 1e-5 absolute, rounding only), cv2.resize INTER_LINEAR on floats down and up (bit-equal) and
+    cv2.imencode / imdecode of a float image at three qualities (byte-equal).
  6. ftfy.fix_text (diffusion/model/t5.py:118-124) -> instarevive_amd.captions.fix_text (deterministic steps + the restricted mojibake repair).
 
 The fixture holds inputs, state-dict checksums and the third party's outputs (data, not source); tests/test_oracle_golden.py picks
@@ -264,6 +267,39 @@ def pin_clipiqa(out, bpe=None):
     return ok
 
 
+def pin_degrade(out):
+    """cv2 against the steps of tools/degrade_folder.py that restate it: the blur (steps 2), the two resizes (3, 6) and the JPEG round trip (5)."""
+    import cv2
+    import importlib.util
+    from instarevive_amd.degrade import bivariate_gaussian
+    spec = importlib.util.spec_from_file_location("degrade_folder", os.path.join(ROOT, "tools", "degrade_folder.py"))
+    dm = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(dm)
+    rng = np.random.default_rng(21)
+    yy, xx = np.mgrid[0:150, 0:203].astype(np.float64)
+    img = np.clip(128 + 90 * np.sin(xx / 9)[..., None] * np.cos(yy / 13)[..., None] * np.array([1, .7, -.8]) + rng.normal(0, 12, (150, 203, 3)), 0, 255).astype(np.uint8)
+    x = dm.to_float(img)
+    k = bivariate_gaussian(41, 3.1, 0.8, 0.7, False)
+    ref, got = cv2.filter2D(x, -1, k), dm.blur(x, k)
+    d_blur = float(np.abs(ref - got).max())
+    print(f"  [10] cv2.filter2D vs blur: largest difference {d_blur:.2e}")
+    ok = d_blur <= 1e-5
+    for (oh, ow) in ((61, 88), (150, 203), (75, 101)):
+        src = got if (oh, ow) != (150, 203) else dm.bilinear(got, 61, 88)
+        same = np.array_equal(cv2.resize(src, (ow, oh), interpolation=cv2.INTER_LINEAR), dm.bilinear(src, oh, ow))
+        print(f"  [10] cv2.resize INTER_LINEAR {src.shape[:2]} -> {(oh, ow)}: {'bit-equal' if same else 'DIFFERENT'}")
+        ok = ok and same
+    low = np.clip(dm.bilinear(got, 61, 88), 0, 1)
+    for q in (10, 60, 100):
+        _, enc = cv2.imencode(".jpg", low[..., ::-1] * 255., [int(cv2.IMWRITE_JPEG_QUALITY), q])   # BGR, as the reference holds it
+        ref8 = cv2.imdecode(enc, 1)[..., ::-1]
+        same = np.array_equal(ref8, dm.jpeg_step(low, q)[1])
+        print(f"  [10] cv2.imencode / imdecode at quality {q}: {'byte-equal' if same else 'DIFFERENT'}")
+        ok = ok and same
+    out["degrade_img"], out["degrade_kernel"], out["degrade_blur_ref"] = img, k, ref
+    return ok
+
+
 def pin_ftfy(out):
     import ftfy
     from instarevive_amd.captions import fix_text
@@ -287,7 +323,8 @@ def main():
     out, verdict = {}, {}
     for name, fn, args in (("diffusers DiT (items 1, 2)", pin_dit, (None,)), ("diffusers VAE (item 3)", pin_vae, (None,)),
                            ("open_clip (item 4)", pin_clip, ()), ("pyiqa (item 5)", pin_iqa, ()), ("ftfy (item 6)", pin_ftfy, ()), ("lpips (item 7)", pin_lpips, ()),
-                           ("pyiqa NIQE (item 8)", pin_niqe, ()), ("pyiqa CLIP-IQA (item 9)", pin_clipiqa, (a.clip_bpe,))):
+                           ("pyiqa NIQE (item 8)", pin_niqe, ()), ("pyiqa CLIP-IQA (item 9)", pin_clipiqa, (a.clip_bpe,)),
+                           ("OpenCV degradation steps (item 10)", pin_degrade, ())):
         print(name)
         try:
             verdict[name] = fn(out, *args)
