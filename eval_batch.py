@@ -17,6 +17,7 @@ With torchrun the file list is sharded over the ranks.
 """
 import os
 from argparse import ArgumentParser
+from collections import deque
 
 import numpy as np
 import torch
@@ -112,7 +113,7 @@ def main():
 
     caps = Captions(args.caption_dir, m.y, m.y_mask, args.input) if args.caption_dir else None
 
-    reports, truths, records, dparams, lq_images = None, [], [], [], []
+    reports, truths, records, dparams, lq_images = None, deque(), deque(), deque(), []
     if (args.lpips_lin or args.lpips_alexnet) and not args.gt:
         raise SystemExit("--lpips_lin / --lpips_alexnet score against ground truth: give --gt as well")
     if args.lpips_alexnet and not args.lpips_lin:
@@ -152,18 +153,6 @@ def main():
                 dparams.append([p[2] for p in pairs])
             yield (imgs, *caps.batch(group)) if caps else imgs
 
-    def batch_truths():   # in step with feed(): process_stream advances it right after it has drawn a batch
-        while True:
-            yield truths.pop(0)
-
-    def batch_records():
-        while True:
-            yield records.pop(0)
-
-    def batch_dparams():
-        while True:
-            yield dparams.pop(0)
-
     def save(dst, img):
         os.makedirs(os.path.dirname(dst) or ".", exist_ok=True)
         if isinstance(img, tuple):   # encoded on the GPU: (zlib stream, width, height), framed here on the writer thread
@@ -178,19 +167,18 @@ def main():
     results = process_stream(m.model, feed(), "none", args.disable_preprocess_model, False, 512, 448, preprocess_model=m.preprocess_model, vae=m.vae,
                              y=m.y, y_mask=m.y_mask, noise_scheduler=m.noise_scheduler, return_stage1=True,
                              png=[[(args.image_size, args.image_size)] * len(group) for group in batches] if gpu_png else None, png_wrap=False,
-                             gt=batch_truths() if lookup else None, **with_lpips, **({"niqe": niqe_params} if niqe_params else {}),
+                             gt=cli.in_step(truths) if lookup else None, **with_lpips, **({"niqe": niqe_params} if niqe_params else {}),
                              **({"clipiqa": True} if clipiqa_model else {}),
-                             **({"resize": batch_records(), "degrade": batch_dparams(), "lq_sink": lq_images.append if args.save_lq else None} if recipe else {}))
-    no_niqe = no_clipiqa = 0
+                             **({"resize": cli.in_step(records), "degrade": cli.in_step(dparams), "lq_sink": lq_images.append if args.save_lq else None} if recipe else {}))
+    no_score = {"niqe": 0, "clipiqa": 0}
     for group, out in zip(batches, results):
         preds, stage1 = out[:2]
         if reports:
             for rep, folder, scores in zip(reports, (args.output, cond_dir), out[2]):
                 for f, score in zip(group, scores):
-                    if niqe_params and score[-2 if clipiqa_model else -1] != score[-2 if clipiqa_model else -1]:   # NaN: the image has no NIQE
-                        no_niqe += 1
-                    elif clipiqa_model and score[-1] != score[-1]:
-                        no_clipiqa += 1
+                    missing = rep.unscored(score)   # NaN: the image has no NIQE, or no CLIP-IQA
+                    if missing:
+                        no_score[missing] += 1
                     else:
                         rep.add_scores(os.path.relpath(out_name(folder, args.input, f), folder), score)
         for f, pred, cond in zip(group, preds, stage1):
@@ -212,10 +200,10 @@ def main():
                   + (f" against {args.gt}" if args.gt else "") + f" -> {rep.path}")
             for ln in lines:
                 print(ln)
-        if no_clipiqa:
-            print(f"[rank {rank}] --clipiqa_model: {no_clipiqa} files were not scored (CLIP-IQA needs 32 x 32 pixels)")
-        if no_niqe:
-            print(f"[rank {rank}] --niqe_params: {no_niqe} files were not scored (NIQE needs 96 x 96 blocks and two complete feature rows)")
+        if no_score["clipiqa"]:
+            print(f"[rank {rank}] --clipiqa_model: {no_score['clipiqa']} files were not scored (CLIP-IQA needs 32 x 32 pixels)")
+        if no_score["niqe"]:
+            print(f"[rank {rank}] --niqe_params: {no_score['niqe']} files were not scored (NIQE needs 96 x 96 blocks and two complete feature rows)")
 
 
 if __name__ == "__main__":

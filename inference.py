@@ -416,6 +416,13 @@ class HostPools:
                 pool.shutdown(wait=True)
 
 
+def in_step(queue: deque) -> Iterator:
+    """An endless iterator over what a batch generator appends to `queue` per batch it yields - the form process_stream(png= / resize= / gt= /
+    niqe_rects= / degrade=) takes: it advances each right after it has drawn a batch."""
+    while True:
+        yield queue.popleft()
+
+
 def batches_of(jobs: Iterable[Job], limit: int, key: Callable = None) -> Iterator[List[Job]]:
     """Consecutive jobs of equal network-input shape, at most `limit` per batch (limit 1 = the reference's one image per call). With `key`, jobs
     whose key(job) differs do not share a batch either (--png_encoder gpu: a batch is encoded on the GPU as a whole or not at all)."""
@@ -594,37 +601,16 @@ def main() -> None:
                     dparams.append([j.deg for j in group])
             yield (imgs, *caps.batch([j.src for j in group])) if caps else imgs
 
-    def batch_rects():   # in step with feed(): process_stream advances it right after it has drawn a batch
-        while True:
-            yield rects.popleft()
-
-    def batch_records():
-        while True:
-            yield records.popleft()
-
-    def batch_truths():
-        while True:
-            yield truths.popleft()
-
-    def batch_dparams():
-        while True:
-            yield dparams.popleft()
-
-    def batch_sizes():
-        while True:
-            yield sizes.popleft()
-
     first = None    # (time, files) when the first result left the GPU: what follows is the steady state (no library / workspace warm-up in it)
     unscored = 0    # --gt / --niqe_params / --clipiqa_model: files whose saved image is not the device's image
-    no_niqe = 0     # --niqe_params: files below 96 pixels on an edge or without two complete feature rows
-    no_clipiqa = 0  # --clipiqa_model: files below 32 pixels on an edge
+    no_score = {"niqe": 0, "clipiqa": 0}   # files below 96 pixels on an edge or without two complete feature rows; files below 32 pixels on an edge
     for out in process_stream(m.model, feed(), tiled=args.tiled, return_stage1=args.show_lq and not args.disable_preprocess_model,
-                              fp8=args.fp8 != "off", png=batch_rects() if gpu_png else None, png_wrap=False,
-                              resize=batch_records() if args.resize_on_gpu else None, gt=batch_truths() if args.gt else None,
+                              fp8=args.fp8 != "off", png=in_step(rects) if gpu_png else None, png_wrap=False,
+                              resize=in_step(records) if args.resize_on_gpu else None, gt=in_step(truths) if args.gt else None,
                               **({"lpips": True} if report and report.lpips else {}),
                               **({"niqe": niqe_params} if niqe_params else {}), **({"clipiqa": True} if clipiqa_model else {}),
-                              **({"niqe_rects": batch_sizes()} if noref else {}),
-                              **({"degrade": batch_dparams(), "lq_sink": lq_images.append if args.save_lq else None} if args.degrade else {}), **common):
+                              **({"niqe_rects": in_step(sizes)} if noref else {}),
+                              **({"degrade": in_step(dparams), "lq_sink": lq_images.append if args.save_lq else None} if args.degrade else {}), **common):
         preds, stage1 = out[:2]
         group = todo.pop(0)
         if args.save_lq:
@@ -634,10 +620,9 @@ def main() -> None:
         if report:
             if len(out) > 2:
                 for job, score in zip(group, out[2][0]):
-                    if niqe_params and score[-2 if clipiqa_model else -1] != score[-2 if clipiqa_model else -1]:   # NaN: the image has no NIQE
-                        no_niqe += 1
-                    elif clipiqa_model and score[-1] != score[-1]:
-                        no_clipiqa += 1
+                    missing = report.unscored(score)   # NaN: the image has no NIQE, or no CLIP-IQA
+                    if missing:
+                        no_score[missing] += 1
                     else:
                         report.add_scores(os.path.relpath(job.save_path, args.output), score)
             else:
@@ -661,10 +646,10 @@ def main() -> None:
         print(f"[rank {rank}] {what}: scored {len(report.rows)} files" + (f" against {args.gt}" if args.gt else "") + f" -> {report.path}")
         for ln in lines:
             print(ln)
-        if no_niqe:
-            print(f"[rank {rank}] --niqe_params: {no_niqe} of {pools.written} files were not scored (NIQE needs 96 x 96 blocks and two complete feature rows)")
-        if no_clipiqa:
-            print(f"[rank {rank}] --clipiqa_model: {no_clipiqa} of {pools.written} files were not scored (CLIP-IQA needs 32 x 32 pixels)")
+        if no_score["niqe"]:
+            print(f"[rank {rank}] --niqe_params: {no_score['niqe']} of {pools.written} files were not scored (NIQE needs 96 x 96 blocks and two complete feature rows)")
+        if no_score["clipiqa"]:
+            print(f"[rank {rank}] --clipiqa_model: {no_score['clipiqa']} of {pools.written} files were not scored (CLIP-IQA needs 32 x 32 pixels)")
         if unscored:
             print(f"[rank {rank}] {what}: {unscored} of {pools.written} files were not scored (their saved image is not the device's image: an input the host "
                   f"enlarged, or --show_lq) - use --resize gpu")

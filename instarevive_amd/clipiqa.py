@@ -16,6 +16,7 @@ import numpy as np
 import torch
 
 from . import _lib as L
+from .slots import Pooled, spans
 
 MIN_EDGE = 32             # below it the tower's last map is empty
 WS_CAP = 3 << 29          # bytes: a batch is split into calls whose workspace stays under it (one image is always taken whole)
@@ -138,7 +139,7 @@ def score_arrays(ctx, img: np.ndarray) -> float:
     return fetch_clipiqa(ctx, 1)[0]
 
 
-class ClipIqaSlot:
+class ClipIqaSlot(Pooled):
     """The scores of one staging slot's batch: a float64 device buffer, one value per row, and its page-locked twin. A row is an image of the batch:
     the predictions first, then - when asked for - the stage-1 images. Images below 32 pixels on an edge are not launched and score NaN."""
 
@@ -146,13 +147,6 @@ class ClipIqaSlot:
         self.ctx = ctx
         self.d = self.h = None
         self.shapes: List[Tuple[int, int]] = []
-
-    @staticmethod
-    def get(ctx, slot=0, tag="sync") -> "ClipIqaSlot":
-        pool = ctx.__dict__.setdefault("_clipiqa_slots", {})
-        if (tag, slot) not in pool:
-            pool[(tag, slot)] = ClipIqaSlot(ctx)
-        return pool[(tag, slot)]
 
     def plan(self, finals: Sequence[Tuple[int, int]], copies: int = 1) -> None:
         """finals: the final size (h, w) of every image of the batch; copies: 2 when the stage-1 images are scored as well."""
@@ -176,26 +170,16 @@ class ClipIqaSlot:
 
     def queue(self, first: int, images: torch.Tensor, results: Optional[Sequence[Optional[torch.Tensor]]] = None) -> None:
         """ir_clipiqa of the images [n][h][w][3] (device uint8: the network's output) into rows first .. first + n - 1, on the current stream.
-        results[i], when not None, is image i's resized result [1][th][tw][3] and is scored in place of the crop. Consecutive plain crops of one
-        size share a call."""
+        results[i], when not None, is image i's resized result [1][th][tw][3] and is scored in place of the crop."""
         n, h, w, _ = images.shape
-        i = 0
-        while i < n:
+        for i, k, r in spans(self.shapes[first:first + n], results, n):
             gh, gw = self.shapes[first + i]
-            r = results[i] if results is not None else None
+            out = self.d[first + i:first + k]
             if min(gh, gw) < MIN_EDGE:
-                self.d[first + i] = float("nan")
-                i += 1
+                out.fill_(float("nan"))
                 continue
-            if r is not None:
-                queue_clipiqa(self.ctx, r.data_ptr(), gh, 3 * gw, 1, gh, gw, self.d[first + i:first + i + 1])
-                i += 1
-                continue
-            k = i + 1
-            while k < n and self.shapes[first + k] == (gh, gw) and (results is None or results[k] is None):
-                k += 1
-            queue_clipiqa(self.ctx, images[i].data_ptr(), h, 3 * w, k - i, gh, gw, self.d[first + i:first + k])
-            i = k
+            img, rows, pitch = (images[i].data_ptr(), h, 3 * w) if r is None else (r.data_ptr(), gh, 3 * gw)
+            queue_clipiqa(self.ctx, img, rows, pitch, k - i, gh, gw, out)
 
     def download(self) -> None:
         """Asynchronous D2H copy of the batch's scores on the current stream."""

@@ -15,6 +15,7 @@ import numpy as np
 import torch
 
 from . import _lib as L
+from .slots import Pooled, spans
 
 WINDOW = 11   # the Gaussian window: images below 11 x 11 have no SSIM (the host model raises, ir_metrics_y refuses)
 
@@ -36,7 +37,7 @@ def queue_scores(ctx, a: int, a_rows: int, a_pitch: int, b: int, b_rows: int, b_
     """ir_metrics_y on the current stream: the top-left h x w of the n images at device address a ([n][a_rows][a_pitch] bytes, RGB8) against
     those at b. out: a contiguous float64 device tensor of n x 2 values (mse_y, ssim_y) - by default the context's own small buffer, whose
     page-locked twin fetch_scores() fills. The scratch is the context's workspace (stream-ordered like every other call that uses it; a
-    caller that has handed its address to a later launch grows it first, see pipeline._metrics_workspace)."""
+    caller that has handed its address to a later launch grows it first, see ScoreSlot.reserve)."""
     if out is None:
         buf = ctx.__dict__.get("_scores")
         if buf is None or buf[0].shape[0] < n:
@@ -88,12 +89,13 @@ def check_ground_truth(gts: Sequence[np.ndarray], finals: Sequence[Tuple[int, in
             raise ValueError(f"{what}: image {i} is {hw[0]} x {hw[1]}; LPIPS needs at least {min_edge} x {min_edge} pixels")
 
 
-class ScoreSlot:
+class ScoreSlot(Pooled):
     """Buffers of one staging slot for batches that are scored: the ground-truth images in a flat page-locked buffer and its device copy (images
     differ in size; the kernel reads bytes, so they are packed without gaps and images of one size form an [n][h][3 w] block), and the scores
     [count][2] (mse_y, ssim_y) with their page-locked twin. All grow on demand and are reused by the next batch of the slot. A batch filled with
     lpips=True is scored by ir_lpips as well (lpips.py; the context's LPIPS weights must be bound): one more double per row, and scores()
-    yields (psnr_y, ssim_y, lpips) in place of pairs."""
+    yields (psnr_y, ssim_y, lpips) in place of pairs. A row is an image of the batch: the predictions first, then - filled with copies=2 - the
+    stage-1 images, scored against the same ground truth."""
 
     def __init__(self, ctx):
         self.ctx = ctx
@@ -105,19 +107,13 @@ class ScoreSlot:
         self.fresh = False
         self.offsets: List[int] = []
         self.shapes: List[Tuple[int, int]] = []
-        self.used = 0
+        self.used = self.rows = 0
 
-    @staticmethod
-    def get(ctx, slot=0, tag="sync") -> "ScoreSlot":
-        pool = ctx.__dict__.setdefault("_score_slots", {})
-        if (tag, slot) not in pool:
-            pool[(tag, slot)] = ScoreSlot(ctx)
-        return pool[(tag, slot)]
-
-    def fill(self, gts: Sequence[np.ndarray], lpips: bool = False) -> None:
-        """Copy the ground-truth images into the page-locked buffer (after the previous upload out of it has completed)."""
+    def fill(self, gts: Sequence[np.ndarray], lpips: bool = False, copies: int = 1) -> None:
+        """Copy the ground-truth images into the page-locked buffer (after the previous upload out of it has completed). copies: 2 when the
+        stage-1 images are scored as well."""
         from .resample import _grown
-        self.lpips = bool(lpips)
+        self.lpips, self.rows = bool(lpips), copies * len(gts)
         if self.h2d_done is not None:
             self.h2d_done.synchronize()
             self.h2d_done = None
@@ -153,48 +149,34 @@ class ScoreSlot:
         self.h2d_done = ev
         return ev
 
-    def workspace_bytes(self) -> int:
-        """The largest workspace a call of this batch may need (all images of one size in one call)."""
+    def reserve(self) -> None:
+        """Grow the context's workspace to what the largest call of this batch may need (all images of one size in one call), and the LPIPS scratch
+        (a buffer of its own, lpips.workspace) of a batch filled with lpips=True, before anything of the batch is queued."""
         n = len(self.shapes)
-        return max(ws_bytes(n, h, w) for h, w in self.shapes)
-
-    def lpips_workspace_bytes(self) -> int:
-        """The same for the ir_lpips calls of a batch filled with lpips=True (their scratch is a buffer of its own, lpips.workspace)."""
-        from .lpips import ws_bytes as lpips_ws_bytes
-        n = len(self.shapes)
-        return max(lpips_ws_bytes(n, h, w) for h, w in self.shapes)
-
-    def _score(self, a: int, a_rows: int, a_pitch: int, b: int, gh: int, gw: int, count: int, first: int) -> None:
-        queue_scores(self.ctx, a, a_rows, a_pitch, b, gh, 3 * gw, count, gh, gw, self.d_scores[first:first + count])
+        self.ctx.workspace(max(ws_bytes(n, h, w) for h, w in self.shapes))
         if self.lpips:
-            from .lpips import queue_lpips
-            queue_lpips(self.ctx, a, a_rows, a_pitch, b, gh, 3 * gw, count, gh, gw, self.d_lpips[first:first + count])
+            from . import lpips
+            lpips.workspace(self.ctx, max(lpips.ws_bytes(n, h, w) for h, w in self.shapes))
 
     def queue(self, first: int, images: torch.Tensor, results: Optional[Sequence[Optional[torch.Tensor]]] = None) -> None:
         """Score the images [n][h][w][3] (device uint8: the network's output) against the slot's ground truth into score rows first .. first + n - 1,
         on the current stream. results[i], when not None, is image i's resized result [1][th][tw][3] and is scored in place of the crop.
-        Consecutive plain crops of one size share a call."""
+        ir_lpips is queued behind ir_metrics_y for the same images."""
         n, h, w, _ = images.shape
-        base = self.d_gt.data_ptr()
-        i = 0
-        while i < n:
+        for i, k, r in spans(self.shapes, results, n):
             gh, gw = self.shapes[i]
-            r = results[i] if results is not None else None
-            if r is not None:
-                self._score(r.data_ptr(), gh, 3 * gw, base + self.offsets[i], gh, gw, 1, first + i)
-                i += 1
-                continue
-            k = i + 1
-            while k < n and self.shapes[k] == (gh, gw) and (results is None or results[k] is None):
-                k += 1
-            self._score(images[i].data_ptr(), h, 3 * w, base + self.offsets[i], gh, gw, k - i, first + i)
-            i = k
+            a, a_rows, a_pitch = (images[i].data_ptr(), h, 3 * w) if r is None else (r.data_ptr(), gh, 3 * gw)
+            b, out = self.d_gt.data_ptr() + self.offsets[i], slice(first + i, first + k)
+            queue_scores(self.ctx, a, a_rows, a_pitch, b, gh, 3 * gw, k - i, gh, gw, self.d_scores[out])
+            if self.lpips:
+                from .lpips import queue_lpips
+                queue_lpips(self.ctx, a, a_rows, a_pitch, b, gh, 3 * gw, k - i, gh, gw, self.d_lpips[out])
 
-    def download(self, count: int) -> None:
-        """Asynchronous D2H copy of the first `count` score rows on the current stream."""
-        self.h_scores[:count].copy_(self.d_scores[:count], non_blocking=True)
+    def download(self) -> None:
+        """Asynchronous D2H copy of the batch's score rows on the current stream."""
+        self.h_scores[:self.rows].copy_(self.d_scores[:self.rows], non_blocking=True)
         if self.lpips:
-            self.h_lpips[:count].copy_(self.d_lpips[:count], non_blocking=True)
+            self.h_lpips[:self.rows].copy_(self.d_lpips[:self.rows], non_blocking=True)
 
     def scores(self, first: int, count: int) -> List[Tuple[float, ...]]:
         """(psnr_y, ssim_y) of rows first .. first + count - 1 after the download has completed; (psnr_y, ssim_y, lpips) for a batch filled with
@@ -285,6 +267,14 @@ class Report:
         if len(scores) != len(self.keys):
             raise MetricsError(f"Report.add_scores: {len(scores)} values for the columns {', '.join(self.keys)}")
         self.add(name, **dict(zip(self.keys, scores)))
+
+    def unscored(self, scores: Sequence[float]) -> Optional[str]:
+        """For a score tuple in the report's own column order: the no-reference column whose value is NaN - the image has no such score -
+        "niqe" before "clipiqa"; None when the tuple can be added."""
+        for k in ("niqe", "clipiqa"):
+            if k in self.keys and scores[self.keys.index(k)] != scores[self.keys.index(k)]:
+                return k
+        return None
 
     def header(self) -> str:
         return ",".join(("file",) + tuple({"psnr": "psnr_y", "ssim": "ssim_y"}.get(k, k) for k in self.keys))

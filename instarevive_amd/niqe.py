@@ -15,6 +15,7 @@ import numpy as np
 import torch
 
 from . import _lib as L
+from .slots import Pooled, spans
 
 BLOCK = 96        # a block at scale 1; images below 96 x 96 have no NIQE
 FEATURES = 36
@@ -190,7 +191,7 @@ def score_arrays(ctx, img: np.ndarray, params) -> float:
     return score(features_from_stats(stats_arrays(ctx, img)), params)
 
 
-class NiqeSlot:
+class NiqeSlot(Pooled):
     """The block statistics of one staging slot's batch: a flat float64 device buffer and its page-locked twin, [row][2][blocks][5][6] packed without
     gaps (images differ in size, so rows differ in length); both grow on demand and are reused by the next batch of the slot. A row is an image of
     the batch: the predictions first, then - when asked for - the stage-1 images. Images below 96 pixels on an edge have no blocks: nothing is
@@ -203,13 +204,6 @@ class NiqeSlot:
         self.shapes: List[Tuple[int, int]] = []
         self.offsets: List[int] = []
         self.used = 0
-
-    @staticmethod
-    def get(ctx, slot=0, tag="sync") -> "NiqeSlot":
-        pool = ctx.__dict__.setdefault("_niqe_slots", {})
-        if (tag, slot) not in pool:
-            pool[(tag, slot)] = NiqeSlot(ctx)
-        return pool[(tag, slot)]
 
     def plan(self, finals: Sequence[Tuple[int, int]], params, copies: int = 1) -> None:
         """finals: the final size (h, w) of every image of the batch; copies: 2 when the stage-1 images are scored as well."""
@@ -225,33 +219,23 @@ class NiqeSlot:
             self.d_stats = torch.zeros((cap,), dtype=torch.float64, device=self.ctx.device)
             self.h_stats = torch.zeros((cap,), dtype=torch.float64).pin_memory()
 
-    def workspace_bytes(self) -> int:
-        """The largest workspace a call of this batch may need (all images of one size in one call)."""
+    def reserve(self) -> None:
+        """Grow the context's workspace to what the largest call of this batch may need (all images of one size in one call), before anything of
+        the batch is queued."""
         n = len(self.shapes)
-        return max([ws_bytes(n, h, w) for h, w in self.shapes if min(h, w) >= BLOCK] + [256])
+        self.ctx.workspace(max([ws_bytes(n, h, w) for h, w in self.shapes if min(h, w) >= BLOCK] + [256]))
 
     def queue(self, first: int, images: torch.Tensor, results: Optional[Sequence[Optional[torch.Tensor]]] = None) -> None:
         """ir_niqe_stats of the images [n][h][w][3] (device uint8: the network's output) into rows first .. first + n - 1, on the current stream.
-        results[i], when not None, is image i's resized result [1][th][tw][3] and is scored in place of the crop. Consecutive plain crops of one
-        size share a call."""
+        results[i], when not None, is image i's resized result [1][th][tw][3] and is scored in place of the crop."""
         n, h, w, _ = images.shape
-        i = 0
-        while i < n:
+        for i, k, r in spans(self.shapes[first:first + n], results, n):
             gh, gw = self.shapes[first + i]
-            r = results[i] if results is not None else None
             if min(gh, gw) < BLOCK:
-                i += 1
                 continue
+            img, rows, pitch = (images[i].data_ptr(), h, 3 * w) if r is None else (r.data_ptr(), gh, 3 * gw)
             at = self.offsets[first + i]
-            if r is not None:
-                queue_stats(self.ctx, r.data_ptr(), gh, 3 * gw, 1, gh, gw, self.d_stats[at:at + blocks_of(gh, gw) * STATS])
-                i += 1
-                continue
-            k = i + 1
-            while k < n and self.shapes[first + k] == (gh, gw) and (results is None or results[k] is None):
-                k += 1
-            queue_stats(self.ctx, images[i].data_ptr(), h, 3 * w, k - i, gh, gw, self.d_stats[at:at + (k - i) * blocks_of(gh, gw) * STATS])
-            i = k
+            queue_stats(self.ctx, img, rows, pitch, k - i, gh, gw, self.d_stats[at:at + (k - i) * blocks_of(gh, gw) * STATS])
 
     def download(self) -> None:
         """Asynchronous D2H copy of the batch's statistics on the current stream."""

@@ -67,7 +67,7 @@ def _png_encoder(ctx, count, h, w, slot=0, tag="sync"):
     """The PngEncoder (png.py) of a batch shape and staging slot, kept on the context like the staging buffers. Each entry holds count x ir_png_bound
     bytes on the device and as much page-locked host memory (about 14 MB per 2048 x 2048 image; twice the images with stage-1 output, two slots
     under process_stream). At most 8 entries: the oldest is dropped whatever its use, which is safe because a batch in flight keeps its own
-    reference (process_stream's `pending`), and costs a re-allocation when more than 8 shapes alternate."""
+    reference (_Batch.enc), and costs a re-allocation when more than 8 shapes alternate."""
     from .png import PngEncoder
     pool = ctx.__dict__.setdefault("_png", {})
     key = (tag, count, h, w, slot)
@@ -76,177 +76,6 @@ def _png_encoder(ctx, count, h, w, slot=0, tag="sync"):
             pool.pop(next(iter(pool)))
         pool[key] = PngEncoder(ctx, count, h, w)
     return pool[key]
-
-
-def _queue_png(ctx, st, slot, n, h, w, rects, with_stage1, tag):
-    """ir_png_encode behind the ir_pipeline of this slot, on the current stream: the predictions into slots 0 .. n - 1 of the encoder, the stage-1
-    images (when asked for) into n .. 2n - 1."""
-    if len(rects) != n:
-        raise ValueError(f"png: {len(rects)} rectangles for a batch of {n} images")
-    enc = _png_encoder(ctx, 2 * n if with_stage1 else n, h, w, slot, tag)
-    enc.queue(0, st.d_out[slot], rects)
-    if with_stage1:
-        enc.queue(n, st.d_st1[slot], rects)
-    return enc
-
-
-def _png_workspace(ctx, n, h, w):
-    """Grow the context's workspace for the encoder BEFORE the pipeline's launch takes its address (a recorded graph is keyed by it)."""
-    ctx.workspace(ctx.ws_bytes(L.STAGE_PNG, n, h, w))
-
-
-def _resize_workspace(ctx, records):
-    """Grow the context's workspace for the resampling calls of a resize batch BEFORE the pipeline's launch takes its address, like _png_workspace."""
-    from .resample import chain_ws_bytes
-    ctx.workspace(chain_ws_bytes(records))
-
-
-def _resize_results(ctx, rs, records, st, slot, n, h, w, with_stage1, rects, tag):
-    """Behind the ir_pipeline of a resize batch, on the current stream: LANCZOS of the valid rectangles back to the LQ sizes (resample.ResizeSlot),
-    then - with rects - ir_png_encode of every image's final form: the resized result, or the valid rectangle of the network's output.
-    Returns (results, stage-1 results, encoder or None); a result is a device tensor [1][th][tw][3] or None for a plain crop."""
-    rs.reserve_results(n, h, w, with_stage1)
-    res = rs.back_to_lq(records, st.d_out[slot], 0)
-    res1 = rs.back_to_lq(records, st.d_st1[slot], n) if with_stage1 else []
-    if rects is None:
-        return res, res1, None
-    final = [tuple(rec.geo.lanczos[::-1]) if rec.geo.lanczos else tuple(rec.geo.valid_hw) for rec in records]
-    if [tuple(r) for r in rects] != final:
-        raise ValueError(f"png: the rectangles {list(rects)} of a resize batch are not its final sizes {final}")
-    enc = _png_encoder(ctx, 2 * n if with_stage1 else n, h, w, slot, tag)
-    for first, out, rr in ((0, st.d_out[slot], res), (n, st.d_st1[slot], res1)):
-        for i, r in enumerate(rr):
-            enc.queue(first + i, out[i:i + 1] if r is None else r, [final[i]])
-    return res, res1, enc
-
-
-def _score_fill(ctx, slot, tag, gts, n, h, w, rects, records, lpips=False):
-    """The metrics.ScoreSlot of a batch with ground truth, filled on the host - after every ground-truth image has been checked against its image's
-    FINAL size (the LANCZOS target or valid rectangle of a resize batch, the png rectangle, else any size inside the network's output), so a
-    mismatch raises ValueError with both sizes before anything is launched for the batch. lpips: score LPIPS as well (ir_lpips with the
-    weights lpips.configure() bound to the context; every image then needs 31 x 31 pixels)."""
-    from .metrics import ScoreSlot, check_ground_truth
-    gts = list(gts)
-    if lpips:
-        from .lpips import MIN_EDGE, configured
-        if not configured(ctx):
-            raise ValueError("lpips=True: no LPIPS weights are bound to the context (instarevive_amd.lpips.configure)")
-    if records is not None:
-        finals = [tuple(rec.geo.lanczos[::-1]) if rec.geo.lanczos else tuple(rec.geo.valid_hw) for rec in records]
-    elif rects is not None:
-        finals = [tuple(int(v) for v in r) for r in rects]
-    else:
-        finals = [tuple(np.shape(g)[:2]) for g in gts] if len(gts) == n else [(h, w)] * n
-    check_ground_truth(gts, finals, **({"min_edge": MIN_EDGE} if lpips else {}))
-    for i, (gh, gw) in enumerate(finals):
-        if gh > h or gw > w:
-            raise ValueError(f"gt: ground truth {i} is {gh} x {gw}, the network's output is {h} x {w}")
-    sc = ScoreSlot.get(ctx, slot, tag)
-    sc.fill(gts, **({"lpips": True} if lpips else {}))
-    return sc
-
-
-def _queue_scores(sc, st, slot, n, with_stage1, res=None, res1=None):
-    """ir_metrics_y behind the ir_pipeline (and the LANCZOS calls) of this slot, on the current stream: the predictions into score rows 0 .. n - 1,
-    the stage-1 images (when asked for) into n .. 2n - 1."""
-    sc.queue(0, st.d_out[slot], res)
-    if with_stage1:
-        sc.queue(n, st.d_st1[slot], res1)
-
-
-def _metrics_workspace(ctx, sc):
-    """Grow the context's workspace for the scoring calls BEFORE the pipeline's launch takes its address, like _png_workspace."""
-    ctx.workspace(sc.workspace_bytes())
-    if sc.lpips:
-        from .lpips import workspace as lpips_workspace
-        lpips_workspace(ctx, sc.lpips_workspace_bytes())
-
-
-class _NoReference:
-    """The no-reference scorers of one batch behind the interface of niqe.NiqeSlot: NIQE's slot, CLIP-IQA's slot (clipiqa.ClipIqaSlot) or both.
-    ir_niqe_stats is queued first, ir_clipiqa behind it; a score tuple is (niqe,), (clipiqa,) or (niqe, clipiqa)."""
-
-    def __init__(self, ctx, nq, cq):
-        self.ctx, self.nq, self.cq = ctx, nq, cq
-
-    def reserve(self):
-        """Grow the scratch of both scorers before anything of the batch is queued."""
-        if self.nq is not None:
-            self.ctx.workspace(self.nq.workspace_bytes())
-        if self.cq is not None:
-            self.cq.reserve()
-
-    def queue(self, first, images, results=None):
-        for s in (self.nq, self.cq):
-            if s is not None:
-                s.queue(first, images, results)
-
-    def download(self):
-        for s in (self.nq, self.cq):
-            if s is not None:
-                s.download()
-
-    def scores(self, first, count):
-        a = self.nq.scores(first, count) if self.nq is not None else None
-        b = self.cq.scores(first, count) if self.cq is not None else None
-        return b if a is None else a if b is None else [x + y for x, y in zip(a, b)]
-
-
-def _niqe_plan(ctx, slot, tag, params, n, h, w, rects, records, gts, sizes, with_stage1, clipiqa=False):
-    """The no-reference scorers of a batch (NIQE with `params`, CLIP-IQA with `clipiqa`), planned on the host: every image's FINAL size - the
-    LANCZOS target or valid rectangle of a resize batch, the png rectangle, else `sizes` (niqe_rects), the ground truth's size, else the
-    network's output."""
-    what = "niqe" if params is not None else "clipiqa"
-    if records is not None:
-        finals = [tuple(rec.geo.lanczos[::-1]) if rec.geo.lanczos else tuple(rec.geo.valid_hw) for rec in records]
-    elif rects is not None:
-        finals = [tuple(int(v) for v in r) for r in rects]
-    elif sizes is not None:
-        finals = [tuple(int(v) for v in r) for r in sizes]
-    elif gts is not None:
-        finals = [tuple(np.shape(g)[:2]) for g in gts]
-    else:
-        finals = [(h, w)] * n
-    if len(finals) != n:
-        raise ValueError(f"{what}: {len(finals)} sizes for a batch of {n} images")
-    for i, (fh, fw) in enumerate(finals):
-        if fh < 1 or fw < 1 or (records is None and (fh > h or fw > w)):
-            raise ValueError(f"{what}: image {i} is scored at {fh} x {fw}, the network's output is {h} x {w}")
-    nq = cq = None
-    if params is not None:
-        from .niqe import NiqeSlot
-        nq = NiqeSlot.get(ctx, slot, tag)
-        nq.plan(finals, params, 2 if with_stage1 else 1)
-    if clipiqa:
-        from .clipiqa import ClipIqaSlot
-        cq = ClipIqaSlot.get(ctx, slot, tag)
-        cq.plan(finals, 2 if with_stage1 else 1)
-    return _NoReference(ctx, nq, cq)
-
-
-def _queue_niqe(nq, st, slot, n, with_stage1, res=None, res1=None):
-    """ir_niqe_stats / ir_clipiqa behind the ir_pipeline (and the LANCZOS / scoring calls) of this slot, on the current stream: rows as in
-    _queue_scores."""
-    nq.queue(0, st.d_out[slot], res)
-    if with_stage1:
-        nq.queue(n, st.d_st1[slot], res1)
-
-
-def _merged_scores(sc, nq, n, with_stage1):
-    """The scores element of a scored batch: a pair of lists (predictions, stage-1 images or empty) of tuples - the paired scores of `sc`, then
-    the no-reference scores of `nq` ((niqe,), (clipiqa,) or (niqe, clipiqa)). The host part of NIQE (the fits and the score) runs here, where the
-    scores are read."""
-    out = []
-    for first, count in ((0, n), (n, n if with_stage1 else 0)):
-        a = sc.scores(first, count) if sc is not None and count else None
-        b = nq.scores(first, count) if nq is not None and count else None
-        out.append([] if not count else (b if a is None else a if b is None else [x + y for x, y in zip(a, b)]))
-    return tuple(out)
-
-
-def _resize_arrays(rs, records, res, host):
-    """The final arrays of a downloaded resize batch: the resized result, or the valid rectangle of the network's output `host` [n][h][w][3]."""
-    return [rs.host_result(r) if r is not None else host[i, :rec.geo.valid_hw[0], :rec.geo.valid_hw[1]].copy() for i, (rec, r) in enumerate(zip(records, res))]
 
 
 def _check_images(control_imgs):
@@ -366,6 +195,170 @@ def _launch_pipeline(ctx, st, slot, n, h, w, flags, tile_size, tile_stride, acp,
                                   n, h, w, flags, tile_size, tile_stride, 400.0, acp, sf, L.ptr(ws), ws.numel()), "ir_pipeline")
 
 
+class _Batch:
+    """One batch in flight through the fused form: what it was given, the buffers it travels in (the staging set, the resample.ResizeSlot of a
+    resize batch, the scorer slots, the PNG encoder) and one method per phase, in this order - plan (the constructor), upload, reserve, launch,
+    download, collect. process() runs them on one stream with a wait in between; process_stream() overlaps the phases of neighbouring batches on
+    two streams and keeps the batch's events in `ready` (its uploads) and `done` (its downloads)."""
+
+    def __init__(self, ctx, slot, tag, slots, shape, imgs, with_stage1, rects=None, records=None, dparams=None, gts=None, lpips=False, niqe=None,
+                 clipiqa=False, sizes=None, want_lq=False, prompts=(None, None)):
+        """The plan phase, host work only: every size is checked and every ground truth compared with its image's FINAL size, so a batch that
+        does not fit raises ValueError before anything is launched for it; then the scorer slots are filled / planned - `scorers` holds them in
+        the order of a score tuple: paired (metrics.ScoreSlot; with lpips it scores LPIPS as well, ir_lpips with the weights lpips.configure()
+        bound to the context), NIQE with `niqe` its parameters, CLIP-IQA - and the images copied into page-locked memory: the staging input, or
+        the decoded files (with their degrade parameters) into the ResizeSlot, whose bicubic chain then makes the staging input on the device.
+        sizes: the batch's niqe_rects entry."""
+        from .slots import final_sizes, record_sizes
+        self.ctx, self.slot, self.tag, self.shape, self.with_stage1 = ctx, slot, tag, shape, with_stage1
+        self.rects, self.records, self.dparams, self.prompts = rects, records, dparams, prompts
+        self.want_lq = want_lq and dparams is not None
+        self.enc = self.ready = self.done = None
+        n, h, w = shape
+        copies = 2 if with_stage1 else 1
+        self.sc, self.scorers = None, []
+        if gts is not None:
+            from .metrics import ScoreSlot
+            gts, min_edge = list(gts), None   # every image needs 11 x 11 pixels for SSIM's window, 31 x 31 with LPIPS
+            if lpips:
+                from .lpips import MIN_EDGE, configured
+                if not configured(ctx):
+                    raise ValueError("lpips=True: no LPIPS weights are bound to the context (instarevive_amd.lpips.configure)")
+                min_edge = MIN_EDGE
+            final_sizes("gt", n, h, w, records, rects, gts=gts, min_edge=min_edge)
+            self.sc = ScoreSlot.get(ctx, slot, tag)
+            self.sc.fill(gts, lpips, copies)
+            self.scorers.append(self.sc)
+        if niqe is not None or clipiqa:
+            finals = final_sizes("niqe" if niqe is not None else "clipiqa", n, h, w, records, rects, sizes, gts)
+            if niqe is not None:
+                from .niqe import NiqeSlot
+                self.scorers.append(NiqeSlot.get(ctx, slot, tag))
+                self.scorers[-1].plan(finals, niqe, copies)
+            if clipiqa:
+                from .clipiqa import ClipIqaSlot
+                self.scorers.append(ClipIqaSlot.get(ctx, slot, tag))
+                self.scorers[-1].plan(finals, copies)
+        if rects is not None:
+            if records is None and len(rects) != n:
+                raise ValueError(f"png: {len(rects)} rectangles for a batch of {n} images")
+            if records is not None and [tuple(r) for r in rects] != record_sizes(records):
+                raise ValueError(f"png: the rectangles {list(rects)} of a resize batch are not its final sizes {record_sizes(records)}")
+        self.st = _Staging.get(ctx, n, h, w, slots=slots, tag=tag)
+        self.rs = None
+        if records is None:
+            self.st.fill(slot, imgs)
+        else:   # the decoded files travel; the network input is made on the device
+            from .resample import ResizeSlot
+            self.rs = ResizeSlot.get(ctx, slot, tag)
+            self.rs.fill(records, dparams)
+
+    def upload(self, stream=None, owner=None):
+        """Asynchronous H2D copies of what plan staged - the images, then the ground truth - on `stream` (default: the current one), which the
+        caller has made current; owner: the compute stream when it is another one (ResizeSlot.upload). Returns the event behind the last copy:
+        the later event of one stream covers both uploads."""
+        ev = self.st.upload(self.slot, stream) if self.rs is None else self.rs.upload(stream, owner)
+        return ev if self.sc is None else self.sc.upload(stream, owner)
+
+    def reserve(self):
+        """Every growth of the context's workspace (and the scorers' own scratch) that the calls around the network need - the PNG encoder, the
+        resampling calls ahead of and behind the network, the scorers - BEFORE the pipeline's launch takes the workspace's address: a recorded
+        graph is keyed by it."""
+        n, h, w = self.shape
+        if self.rects is not None:
+            self.ctx.workspace(self.ctx.ws_bytes(L.STAGE_PNG, n, h, w))
+        if self.records is not None:
+            from .resample import chain_ws_bytes
+            self.ctx.workspace(chain_ws_bytes(self.records))
+        for s in self.scorers:
+            s.reserve()
+
+    def launch(self, flags, tile_size, tile_stride, acp, sf):
+        """The batch's device work on the current stream: [ir_degrade of the decoded files] -> the bicubic chain into the staging input ->
+        ir_pipeline -> LANCZOS of the valid rectangles back to the LQ sizes -> ir_png_encode of every image's final form -> every scorer's calls.
+        What stands behind ir_pipeline runs behind the replay of a recorded graph, outside the recording. `outs` lists the outputs the later
+        phases walk: (first row, the network's output [n][h][w][3], per image its resized result [1][th][tw][3] or None for a plain crop - None
+        for all without resize records), the predictions at rows 0 .. n - 1 and - with stage-1 output - the stage-1 images at n .. 2n - 1."""
+        from .slots import record_sizes
+        ctx, st, slot, rs, (n, h, w) = self.ctx, self.st, self.slot, self.rs, self.shape
+        if rs is not None:
+            if self.dparams is not None:
+                rs.degrade(self.records)
+            rs.to_network(self.records, st.d_in[slot])
+        _launch_pipeline(ctx, st, slot, n, h, w, flags, tile_size, tile_stride, acp, sf, self.with_stage1)
+        outs = [(0, st.d_out[slot])] + ([(n, st.d_st1[slot])] if self.with_stage1 else [])
+        if rs is not None:
+            rs.reserve_results(n, h, w, self.with_stage1)
+        self.outs = [(first, out, rs.back_to_lq(self.records, out, first) if rs is not None else None) for first, out in outs]
+        if self.rects is not None:   # the batch keeps its own reference to the encoder: the pool evicts after 8 shapes
+            self.enc = _png_encoder(ctx, len(outs) * n, h, w, slot, self.tag)
+            for first, out, res in self.outs:
+                if res is None:
+                    self.enc.queue(first, out, self.rects)
+                else:   # the resized result, or the valid rectangle of the network's output
+                    for i, (r, final) in enumerate(zip(res, record_sizes(self.records))):
+                        self.enc.queue(first + i, out[i:i + 1] if r is None else r, [final])
+        for s in self.scorers:
+            for first, out, res in self.outs:
+                s.queue(first, out, res)
+
+    def download(self):
+        """The batch's D2H copies on the current stream, behind its device work: the byte counts of an encoded batch - the raw images are then
+        not downloaded - else the network's output and / or the resized results (a batch whose results were all resized back downloads those
+        alone); the LQ images of a degraded batch when a sink wants them; every scorer's rows."""
+        st, slot = self.st, self.slot
+        if self.enc is not None:
+            self.enc.fetch_sizes()
+        else:
+            if self.rs is None or any(r is None for r in self.outs[0][2]):
+                st.h_out[slot].copy_(st.d_out[slot], non_blocking=True)
+                if self.with_stage1:
+                    st.h_st1[slot].copy_(st.d_st1[slot], non_blocking=True)
+            if self.rs is not None:
+                self.rs.download([r for _, _, res in self.outs for r in res])
+        if self.want_lq:
+            self.rs.download_lq()
+        for s in self.scorers:
+            s.download()
+
+    def host_lq(self):
+        """The LQ images of a degraded batch (want_lq), after the downloads have completed."""
+        return self.rs.host_lq(self.records)
+
+    def collect(self, stream=None, png_wrap=True):
+        """After the downloads have completed: process()'s result - (preds, stage1_preds) as arrays the caller owns (the pinned buffers are
+        reused by the slot's next batch) or as PNG files, whose bytes are fetched here on `stream` now that their counts are known - and, for a
+        scored batch, the scores element: a pair of lists (predictions, stage-1 images or empty) of tuples, every scorer's values in the order of
+        `scorers`. The host part of NIQE (the fits and the score) runs here, where the scores are read."""
+        n = self.shape[0]
+        if self.enc is not None:
+            files = self.enc.fetch(len(self.outs) * n, stream, png_wrap)
+            lists = [files[:n], files[n:]]
+        else:
+            lists = []
+            for (_, _, res), host in zip(self.outs, (self.st.h_out[self.slot], self.st.h_st1[self.slot])):
+                if res is None:
+                    host = host.clone().numpy()
+                    lists.append([host[i] for i in range(n)])
+                else:   # the resized result, or the valid rectangle of the network's output
+                    host = host.numpy()
+                    lists.append([self.rs.host_result(r) if r is not None else host[i, :rec.geo.valid_hw[0], :rec.geo.valid_hw[1]].copy()
+                                  for i, (rec, r) in enumerate(zip(self.records, res))])
+            lists.append([])
+        if not self.scorers:
+            return lists[0], lists[1]
+        scores = [[sum(row, ()) for row in zip(*(s.scores(first, n) for s in self.scorers))] for first, _, _ in self.outs] + [[]]
+        return lists[0], lists[1], (scores[0], scores[1])
+
+
+def _batch_shape(imgs, records):
+    """(n, h, w) of a batch: of its resize records' network input when it has them (the image list is then not read), else of its images."""
+    if records is not None:
+        from .resample import check_records
+        return check_records(records)
+    return _check_images(imgs)
+
+
 @torch.no_grad()
 def process(model, control_imgs: List[np.ndarray], strength: float, color_fix_type: str, disable_preprocess_model: bool, tiled: bool,
             tile_size: int, tile_stride: int, preprocess_model=None, vae=None, y=None, y_mask=None, noise_scheduler=None,
@@ -414,11 +407,7 @@ def process(model, control_imgs: List[np.ndarray], strength: float, color_fix_ty
         raise ValueError("process(lpips=True) needs gt=: LPIPS is scored against the ground truth")
     if degrade is not None and resize is None:
         raise ValueError("process(degrade=...) needs resize=: the ground truth is degraded on the device input route")
-    if resize is not None:
-        from .resample import ResizeSlot, check_records
-        n, h, w = check_records(resize)
-    else:
-        n, h, w = _check_images(control_imgs)
+    n, h, w = _batch_shape(control_imgs, resize)
     if (png is not None or resize is not None or gt is not None or niqe is not None or clipiqa) and not (fused and _fused_ok(model, preprocess_model, vae, disable_preprocess_model)):
         raise ValueError("process(png=... / resize=... / gt=... / niqe=...) needs the fused form (instarevive_amd models sharing one context)")
     device = model.device
@@ -430,73 +419,18 @@ def process(model, control_imgs: List[np.ndarray], strength: float, color_fix_ty
         if fp8 and not vae.__dict__.get("_fp8_uploaded"):
             raise RuntimeError("process(fp8=True): call vae.enable_fp8() first - without the fp8 weight forms every layer would silently run in bf16")
         ctx = model.ctx
-        sc = _score_fill(ctx, 0, "sync", gt, n, h, w, png, resize, lpips) if gt is not None else None
-        nq = _niqe_plan(ctx, 0, "sync", niqe, n, h, w, png, resize, gt, niqe_rects, return_stage1, clipiqa) if niqe is not None or clipiqa else None
+        batch = _Batch(ctx, 0, "sync", 1, (n, h, w), control_imgs, return_stage1, png, resize, degrade, gt, lpips, niqe, clipiqa, niqe_rects,
+                       lq_sink is not None)
         _prepare_fused(model, y, y_mask, h, w, tiled, tile_size, (vae, None if disable_preprocess_model else preprocess_model))
         flags = _pipeline_flags(model, color_fix_type, disable_preprocess_model, tiled) | (L.FLAG_GRAPH if graph else 0) | (L.FLAG_FP8 if fp8 else 0)
-        st = _Staging.get(ctx, n, h, w)
-        rs = None
-        if resize is None:
-            st.fill(0, control_imgs)
-            st.upload(0)
-        else:
-            rs = ResizeSlot.get(ctx, 0, "sync")
-            rs.fill(resize, degrade)
-            rs.upload()
-            if degrade is not None:
-                rs.degrade(resize)
-            _resize_workspace(ctx, resize)
-        if png is not None:
-            _png_workspace(ctx, n, h, w)
-        if sc is not None:
-            sc.upload()
-            _metrics_workspace(ctx, sc)
-        if nq is not None:
-            nq.reserve()
-        if rs is not None:
-            rs.to_network(resize, st.d_in[0])
-        _launch_pipeline(ctx, st, 0, n, h, w, flags, tile_size, tile_stride, acp, sf, return_stage1)
-        res = res1 = None
-        if rs is not None:
-            res, res1, enc = _resize_results(ctx, rs, resize, st, 0, n, h, w, return_stage1, png, "sync")
-
-        def scored(preds, stage1):   # after the stream has been waited for
-            if sc is None and nq is None:
-                return preds, stage1
-            return preds, stage1, _merged_scores(sc, nq, n, return_stage1)
-
-        if sc is not None:
-            _queue_scores(sc, st, 0, n, return_stage1, res, res1)
-            sc.download(2 * n if return_stage1 else n)
-        if nq is not None:
-            _queue_niqe(nq, st, 0, n, return_stage1, res, res1)
-            nq.download()
-        want_lq = degrade is not None and lq_sink is not None
-        if want_lq:
-            rs.download_lq()
-        if png is not None:
-            if rs is None:
-                enc = _queue_png(ctx, st, 0, n, h, w, png, return_stage1, "sync")
-            enc.fetch_sizes()
-            torch.cuda.current_stream(device).synchronize()
-            if want_lq:
-                lq_sink(rs.host_lq(resize))
-            files = enc.fetch(2 * n if return_stage1 else n)
-            return scored(files[:n], files[n:])
-        st.h_out[0].copy_(st.d_out[0], non_blocking=True)
-        if return_stage1:
-            st.h_st1[0].copy_(st.d_st1[0], non_blocking=True)
-        if rs is not None:
-            rs.download(res + res1)
-            torch.cuda.current_stream(device).synchronize()
-            if want_lq:
-                lq_sink(rs.host_lq(resize))
-            return scored(_resize_arrays(rs, resize, res, st.h_out[0].numpy()),
-                          _resize_arrays(rs, resize, res1, st.h_st1[0].numpy()) if return_stage1 else [])
+        batch.upload()
+        batch.reserve()
+        batch.launch(flags, tile_size, tile_stride, acp, sf)
+        batch.download()
         torch.cuda.current_stream(device).synchronize()
-        preds = st.h_out[0].clone().numpy()   # the caller owns the result; the pinned buffer is reused by the next call
-        stage1 = st.h_st1[0].clone().numpy() if return_stage1 else None
-        return scored([preds[i] for i in range(n)], ([stage1[i] for i in range(n)] if return_stage1 else []))
+        if batch.want_lq:
+            lq_sink(batch.host_lq())
+        return batch.collect()
 
     # ---- stage-by-stage form: the reference's literal call sequence on NCHW fp32 tensors
     if tiled:   # before any network runs: what ir_pipeline refuses with -31 (tile_geom in csrc/api.cpp)
@@ -612,10 +546,10 @@ def process_stream(model, batches: Iterable[Sequence[np.ndarray]], color_fix_typ
     gt_it = iter(gt) if gt is not None else None
     noref = niqe is not None or bool(clipiqa)
     nq_it = iter(niqe_rects) if noref and niqe_rects is not None else None
-    if resize_it is not None:
-        from .resample import ResizeSlot, check_records
 
-    def upload(batch, slot):
+    def staged(batch, slot):
+        """The next batch, planned and with its uploads queued on the copy stream. Every per-batch iterable is advanced right after the batch
+        has been drawn."""
         rects = next(png_it) if png_it is not None else None
         records = next(resize_it) if resize_it is not None else None
         dparams = next(degrade_it) if degrade_it is not None else None
@@ -625,45 +559,17 @@ def process_stream(model, batches: Iterable[Sequence[np.ndarray]], color_fix_typ
         sizes = next(nq_it) if nq_it is not None else None
         with_nq = noref and (sizes is not None if nq_it is not None else (gts is not None or gt_it is None))
         imgs, by, bm = _split_batch(batch)
-        if records is not None:   # the decoded files travel; the network input is made on the device
-            n, h, w = check_records(records)
-            sc = _score_fill(ctx, slot, "stream", gts, n, h, w, rects, records, lpips) if gts is not None else None
-            nq = _niqe_plan(ctx, slot, "stream", niqe, n, h, w, rects, records, gts, sizes, return_stage1, clipiqa) if with_nq else None
-            st = _Staging.get(ctx, n, h, w, slots=2, tag="stream")
-            rs = ResizeSlot.get(ctx, slot, "stream")
-            rs.fill(records, dparams)
-            with torch.cuda.stream(copy):
-                ev = rs.upload(copy, main)
-                if sc is not None:
-                    ev = sc.upload(copy, main)   # the later event of the copy stream covers both uploads
-            return st, slot, (n, h, w), ev, (by, bm), rects, (rs, records), sc, nq
-        n, h, w = _check_images(imgs)
-        sc = _score_fill(ctx, slot, "stream", gts, n, h, w, rects, None, lpips) if gts is not None else None
-        nq = _niqe_plan(ctx, slot, "stream", niqe, n, h, w, rects, None, gts, sizes, return_stage1, clipiqa) if with_nq else None
-        st = _Staging.get(ctx, n, h, w, slots=2, tag="stream")
-        st.fill(slot, imgs)
+        b = _Batch(ctx, slot, "stream", 2, _batch_shape(imgs, records), imgs, return_stage1, rects, records, dparams, gts, lpips,
+                   niqe if with_nq else None, bool(clipiqa) and with_nq, sizes, lq_sink is not None, (by, bm))
         with torch.cuda.stream(copy):
-            ev = st.upload(slot, copy)
-            if sc is not None:
-                ev = sc.upload(copy, main)
-        return st, slot, (n, h, w), ev, (by, bm), rects, None, sc, nq
+            b.ready = b.upload(copy, main)
+        return b
 
-    def download(job):
-        st, slot, (n, h, w), done, enc, rz, sc, nq = job
-        done.synchronize()
-        scores = (_merged_scores(sc, nq, n, return_stage1),) if sc is not None or nq is not None else ()
-        if rz is not None and rz[0].dparams is not None and lq_sink is not None:
-            lq_sink(rz[0].host_lq(rz[1]))
-        if enc is not None:   # the byte counts are here: fetch that many bytes per image
-            files = enc.fetch(2 * n if return_stage1 else n, copy, png_wrap)
-            return (files[:n], files[n:]) + scores
-        if rz is not None:
-            rs, records, res, res1 = rz
-            return (_resize_arrays(rs, records, res, st.h_out[slot].numpy()),
-                    _resize_arrays(rs, records, res1, st.h_st1[slot].numpy()) if return_stage1 else []) + scores
-        preds = st.h_out[slot].clone().numpy()
-        stage1 = st.h_st1[slot].clone().numpy() if return_stage1 else None
-        return ([preds[i] for i in range(n)], ([stage1[i] for i in range(n)] if return_stage1 else [])) + scores
+    def finished(b):
+        b.done.synchronize()
+        if b.want_lq:
+            lq_sink(b.host_lq())
+        return b.collect(copy, png_wrap)
 
     last_prompt = None   # the host prompts of the last triple batch that were set (a batch with the same ones sets nothing)
 
@@ -685,65 +591,32 @@ def process_stream(model, batches: Iterable[Sequence[np.ndarray]], color_fix_typ
         model._set_prompt_rows(hy, hb, stream_ordered=True)
         last_prompt = (hy, hb)
 
-    slot, pending = 0, None
+    pending = None
     nxt = next(it, None)
-    up = upload(nxt, slot) if nxt is not None else None
-    while up is not None:
-        st, cur, (n, h, w), ready, (by, bm), rects, rz, sc, nq = up
+    cur = staged(nxt, 0) if nxt is not None else None
+    while cur is not None:
+        n, h, w = cur.shape
         _prepare_fused(model, y, y_mask, h, w, tiled, tile_size, (vae, None if disable_preprocess_model else preprocess_model), set_prompt=False)
-        set_batch_prompt(by, bm, n)
-        main.wait_event(ready)
-        if rects is not None:
-            _png_workspace(ctx, n, h, w)
-        if sc is not None:
-            _metrics_workspace(ctx, sc)
-        if nq is not None:
-            nq.reserve()
-        if rz is not None:
-            if rz[0].dparams is not None:
-                rz[0].degrade(rz[1])
-            _resize_workspace(ctx, rz[1])
-            rz[0].to_network(rz[1], st.d_in[cur])
-        _launch_pipeline(ctx, st, cur, n, h, w, base_flags, tile_size, tile_stride, acp, sf, return_stage1)
-        if rz is not None:
-            res, res1, enc = _resize_results(ctx, rz[0], rz[1], st, cur, n, h, w, return_stage1, rects, "stream")
-            rz = rz + (res, res1)
-        else:
-            enc = _queue_png(ctx, st, cur, n, h, w, rects, return_stage1, "stream") if rects is not None else None
-        if sc is not None:
-            _queue_scores(sc, st, cur, n, return_stage1, rz[2] if rz is not None else None, rz[3] if rz is not None else None)
-        if nq is not None:
-            _queue_niqe(nq, st, cur, n, return_stage1, rz[2] if rz is not None else None, rz[3] if rz is not None else None)
+        set_batch_prompt(*cur.prompts, n)
+        main.wait_event(cur.ready)
+        cur.reserve()
+        cur.launch(base_flags, tile_size, tile_stride, acp, sf)
         computed = torch.cuda.Event()
         computed.record(main)
         # while this batch computes: fetch the previous result, stage the next input into the other slot. The other slot's device
-        # buffers were last read by the previous batch's download, which download() has waited for by then.
+        # buffers were last read by the previous batch's download, which finished() has waited for by then.
         if pending is not None:
-            yield download(pending)
+            yield finished(pending)
         nxt = next(it, None)
-        up = upload(nxt, cur ^ 1) if nxt is not None else None
+        up = staged(nxt, cur.slot ^ 1) if nxt is not None else None
         with torch.cuda.stream(copy):
             copy.wait_event(computed)
-            if enc is not None:
-                enc.fetch_sizes()
-            else:
-                if rz is None or any(r is None for r in rz[2]):   # a batch whose results were all resized back downloads those alone
-                    st.h_out[cur].copy_(st.d_out[cur], non_blocking=True)
-                    if return_stage1:
-                        st.h_st1[cur].copy_(st.d_st1[cur], non_blocking=True)
-                if rz is not None:
-                    rz[0].download(rz[2] + rz[3])
-            if rz is not None and rz[0].dparams is not None and lq_sink is not None:
-                rz[0].download_lq()
-            if sc is not None:
-                sc.download(2 * n if return_stage1 else n)
-            if nq is not None:
-                nq.download()
-            done = torch.cuda.Event()
-            done.record(copy)
-        pending = (st, cur, (n, h, w), done, enc, rz, sc, nq)
+            cur.download()
+            cur.done = torch.cuda.Event()
+            cur.done.record(copy)
+        pending, cur = cur, up
     if pending is not None:
-        yield download(pending)
+        yield finished(pending)
 
 
 class HipTileEngine:

@@ -17,6 +17,7 @@ import numpy as np
 import torch
 
 from . import _lib as L
+from .slots import Pooled
 
 BICUBIC, LANCZOS = L.RESAMPLE_BICUBIC, L.RESAMPLE_LANCZOS
 
@@ -149,7 +150,7 @@ def _grown(t: Optional[torch.Tensor], nbytes: int, device=None, pinned=False) ->
     return torch.empty(nbytes, dtype=torch.uint8).pin_memory() if pinned else torch.empty(nbytes, dtype=torch.uint8, device=device)
 
 
-class ResizeSlot:
+class ResizeSlot(Pooled):
     """Buffers of one staging slot for batches whose images are resized on the device. Decoded files differ in size, so they get a flat
     page-locked buffer and its device copy (each file at a 256-byte boundary) instead of _Staging's fixed shape; `mid` holds the image
     between two chained bicubic calls; d_res / h_res hold the LANCZOS results (predictions, then stage-1 images) that are downloaded or
@@ -165,13 +166,6 @@ class ResizeSlot:
         self.extras: List[tuple] = []   # per image the offsets of its blur kernel and noise field (or None) in h_raw / d_raw
         self.img_bytes = 0       # where the images end in h_raw / d_raw (the kernels and noise fields follow)
         self.lq_made = False
-
-    @staticmethod
-    def get(ctx, slot=0, tag="sync") -> "ResizeSlot":
-        pool = ctx.__dict__.setdefault("_resize_slots", {})
-        if (tag, slot) not in pool:
-            pool[(tag, slot)] = ResizeSlot(ctx)
-        return pool[(tag, slot)]
 
     def fill(self, records: Sequence[ResizeJob], degrade=None) -> None:
         """Copy the decoded files into the page-locked buffer (after the previous upload out of it has completed). degrade: one degrade.Params

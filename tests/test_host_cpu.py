@@ -802,3 +802,69 @@ def test_bench_logit_gain_is_a_full_leg():
     import subprocess
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--logit_gain", "4"], capture_output=True, text=True, timeout=300, cwd=ROOT)
     assert r.returncode != 0 and "--logit_gain is a leg of --full runs" in r.stderr
+
+
+def test_final_sizes_precedence_and_checks():
+    """slots.final_sizes: one case per rung of both precedences, and every refusal with its message."""
+    from instarevive_amd.resample import ResizeJob, job_geometry
+    from instarevive_amd.slots import final_sizes
+    recs = [ResizeJob(np.zeros((h, w, 3), np.uint8), job_geometry((w, h), 1, True, 64)) for h, w in ((40, 56), (64, 90))]
+    assert [r.geo.lanczos for r in recs] == [(56, 40), None]
+    rec_sizes = [(40, 56), (64, 90)]          # the LANCZOS target as (h, w), the valid rectangle
+    gt = lambda *hw: [np.zeros(s + (3,), np.uint8) for s in hw]
+    rects, sizes = [(33, 100), (64, 77)], [(20, 30), (64, 128)]
+    # paired: resize records -> png rectangles -> the ground truths' own sizes when there is one per image -> (h, w)
+    assert final_sizes("gt", 2, 64, 128, recs, rects, sizes, gt(*rec_sizes)) == rec_sizes
+    assert final_sizes("gt", 2, 64, 128, None, rects, sizes, gt(*rects)) == rects
+    assert final_sizes("gt", 2, 64, 128, None, None, sizes, gt((50, 60), (64, 128))) == [(50, 60), (64, 128)]   # niqe_rects is no rung here
+    with pytest.raises(ValueError, match="gt: 1 ground-truth images for a batch of 2 images"):
+        final_sizes("gt", 2, 64, 128, gts=gt((64, 128)))     # not one per image: (h, w) for every image, and the count is refused
+    with pytest.raises(ValueError, match="ground truth 1 is 64 x 78, the image's final size is 64 x 77"):
+        final_sizes("gt", 2, 64, 128, None, rects, gts=gt((33, 100), (64, 78)))
+    with pytest.raises(ValueError, match="gt: ground truth 1 is 65 x 128, the network's output is 64 x 128"):
+        final_sizes("gt", 2, 64, 128, gts=gt((64, 128), (65, 128)))
+    with pytest.raises(ValueError, match="LPIPS needs at least 31 x 31"):
+        final_sizes("gt", 1, 64, 128, gts=gt((30, 100)), min_edge=31)
+    assert final_sizes("gt", 1, 64, 128, gts=gt((30, 100))) == [(30, 100)]
+    # no-reference: resize records -> png rectangles -> niqe_rects -> the ground truths' sizes -> (h, w)
+    for what in ("niqe", "clipiqa"):
+        assert final_sizes(what, 2, 64, 128, recs, rects, sizes, gt(*rects)) == rec_sizes
+        assert final_sizes(what, 2, 64, 128, None, rects, sizes, gt(*rects)) == rects
+        assert final_sizes(what, 2, 64, 128, None, None, sizes, gt(*rects)) == sizes
+        assert final_sizes(what, 2, 64, 128, gts=gt(*rects)) == rects
+        assert final_sizes(what, 2, 64, 128) == [(64, 128)] * 2
+        with pytest.raises(ValueError, match=f"{what}: 1 sizes for a batch of 2 images"):
+            final_sizes(what, 2, 64, 128, sizes=sizes[:1])
+        with pytest.raises(ValueError, match=f"{what}: image 1 is scored at 65 x 128, the network's output is 64 x 128"):
+            final_sizes(what, 2, 64, 128, sizes=[(64, 128), (65, 128)])
+        with pytest.raises(ValueError, match=f"{what}: image 0 is scored at 0 x 5, the network's output"):
+            final_sizes(what, 1, 64, 128, rects=[(0, 5)])
+    # only a resized result may be larger than the network's output: 20 x 150 -> 64 x 480 in a 64 x 512 input, LANCZOS back to 20 x 150
+    wide = [ResizeJob(np.zeros((20, 150, 3), np.uint8), job_geometry((150, 20), 1, True, 64))]
+    assert wide[0].geo.net_hw == (64, 512) and final_sizes("niqe", 1, 64, 128, wide) == [(20, 150)]
+    with pytest.raises(ValueError, match="niqe: image 0 is scored at 20 x 150, the network's output is 64 x 128"):
+        final_sizes("niqe", 1, 64, 128, rects=[(20, 150)])
+
+
+def test_spans_group_plain_crops_of_one_size():
+    """slots.spans: equal neighbours share a call, a resized result and a different size split, results=None, n = 1."""
+    from instarevive_amd.slots import spans
+    a, b, r = (64, 128), (40, 100), object()
+    assert list(spans([a, a, a], None, 3)) == [(0, 3, None)]
+    assert list(spans([a, a, b, b, a], None, 5)) == [(0, 2, None), (2, 4, None), (4, 5, None)]
+    assert list(spans([a, a, a, a], [None, r, None, None], 4)) == [(0, 1, None), (1, 2, r), (2, 4, None)]   # a resized result stands alone
+    assert list(spans([a, a], [r, r], 2)) == [(0, 1, r), (1, 2, r)]
+    assert list(spans([a, a, b], [None, None, None], 3)) == [(0, 2, None), (2, 3, None)]
+    assert list(spans([a], None, 1)) == [(0, 1, None)] and list(spans([a], [r], 1)) == [(0, 1, r)]
+    assert list(spans([a, a, a], None, 2)) == [(0, 2, None)] and list(spans([], None, 0)) == []   # only the first n shapes count
+
+
+def test_report_names_the_missing_no_reference_score():
+    from instarevive_amd.metrics import Report
+    nan = float("nan")
+    both = Report(None, lpips=True, niqe=True, clipiqa=True)
+    assert both.unscored((30.0, 0.9, 0.1, 4.0, 0.5)) is None
+    assert both.unscored((30.0, 0.9, 0.1, nan, 0.5)) == "niqe" and both.unscored((30.0, 0.9, 0.1, 4.0, nan)) == "clipiqa"
+    assert both.unscored((30.0, 0.9, 0.1, nan, nan)) == "niqe"      # NIQE is looked at first
+    assert Report(None, niqe=True, paired=False).unscored((nan,)) == "niqe" and Report(None, clipiqa=True, paired=False).unscored((nan,)) == "clipiqa"
+    assert Report(None).unscored((nan, 0.9)) is None                 # a paired value is not its business
