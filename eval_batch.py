@@ -57,8 +57,9 @@ def parse_args():
     ap.add_argument("--clipiqa_model", default=None, help="score CLIP-IQA (no reference needed) of both output folders on the GPU (inference.py --clipiqa_model: "
                     "OpenAI's RN50.pt or an .npz). Works with or without --gt and --niqe_params; its column comes last. --image_size must be at least 32")
     ap.add_argument("--clip_bpe", default=None, help="with --clipiqa_model: the folder that holds CLIP's BPE table (inference.py --clip_bpe)")
-    ap.add_argument("--degrade", nargs="?", const="lq", default=None, metavar="lq|FILE.json", help="--input holds GROUND TRUTH: the centre crops are degraded on "
-                    "the GPU (inference.py --degrade: blur, bilinear downsample, noise, JPEG, bilinear resize back) and the LQ images restored; needs "
+    ap.add_argument("--degrade", nargs="?", const="lq", default=None, metavar="lq|realesrgan|FILE.json", help="--input holds GROUND TRUTH: the centre crops are degraded on "
+                    "the GPU (inference.py --degrade: blur, bilinear downsample, noise, JPEG, bilinear resize back; `realesrgan`: the reference's second-order "
+                    "validation recipe) and the LQ images restored; needs "
                     "--image_size to be a multiple of 64 of at least 512 (the crop is then the network input as it is). Without --gt the input folder "
                     "is the ground truth of --lpips_lin / --niqe_params / --clipiqa_model")
     ap.add_argument("--degrade_seed", type=int, default=231, help="with --degrade: seeds every file's draws together with the crc32 of its input-relative path")

@@ -34,7 +34,9 @@ enum { IR_STAGE_SWINIR = 0, IR_STAGE_VAE_ENCODE = 1, IR_STAGE_DIT = 2, IR_STAGE_
        IR_STAGE_CLIPIQA = 15 /* ir_clipiqa: n images, h, w = the scored rectangle; depends on the sizes and on the layer counts bound by
                                 ir_clipiqa_configure (0 for a context that is not configured) */,
        IR_STAGE_DEGRADE = 16 /* ir_degrade: h, w = the image size; the images of a batch share one workspace, so n only has to be >= 1; depends
-                                on the size alone (ctx may be NULL) */ };
+                                on the size alone (ctx may be NULL) */,
+       IR_STAGE_DEGRADE_CHAIN = 17 /* ir_degrade_chain: h, w = the image size, and in place of flags and tile_size the largest height and the
+                                      largest width among the chains' intermediate images; n only has to be >= 1 (ctx may be NULL) */ };
 /* ir_pipeline flags */
 enum { IR_FLAG_NO_PREPROCESS = 1, IR_FLAG_TILED = 2, IR_FLAG_FIX_WAVELET = 4, IR_FLAG_FIX_ADAIN = 8,
        /* ir_pipeline only, needs ir_dit_control_configure: run the DiT step with the ControlNet-Half branch, condition latent
@@ -434,6 +436,65 @@ typedef struct ir_degrade_params {
 int ir_degrade_qtables(int q, uint16_t* luma64, uint16_t* chroma64);
 int ir_degrade(ir_ctx* ctx, void* stream, const uint8_t* img, int rows, long pitch, int n, int h, int w, const ir_degrade_params* params,
                uint8_t* out, uint8_t* jpeg_or_null, void* ws, size_t ws_bytes);
+
+/* Low-quality inputs by the SECOND-ORDER degradation the reference validates general super-resolution with (configs/
+ * general_deg_realesrgan_val.yaml, dataset/realesrgan.py, dataset/batch_transform.py:RealESRGANBatchTransform), on the device.
+ * tools/degrade_folder.py:degrade_chain_model states the definition in numpy, down to the order of operations: the bytes and every
+ * intermediate float image are equal. Per image a CHAIN of at most IR_CHAIN_MAX_OPS ops on a float32 [h][w][3] image that starts as
+ * float32(v / 255.0); behind the last op the image must be h x w again and out receives uint8(clip(rint(x * 255), 0, 255)), half to even.
+ *   IR_CHAIN_FILTER    a = K (odd, at most 21), data = kernel [K][K] doubles. utils/image/common.py:filter2D: correlation, reflect border,
+ *                      fp64 accumulation in row-major tap order with separate multiplies and adds, rounded once. The image must be at least
+ *                      K / 2 + 1 on both sides.
+ *   IR_CHAIN_RESIZE    a = IR_CHAIN_AREA | _BILINEAR | _BICUBIC, b x c = the output height x width, s = the scale factor, or 0 for a call
+ *                      that passed size=. F.interpolate without antialiasing, align_corners = False: the source coordinate is
+ *                      float32(r * (float32(d) + 0.5) - 0.5), product and difference in double as the fused operation of torch's CPU kernels,
+ *                      with r = float32(1 / s), or float32(in) / float32(out) for s = 0; with s > 0 the output must be floor(in * s). Bilinear
+ *                      clamps a negative coordinate to 0; bicubic has A = -0.75, float32 weights and indices clamped to the image; area is
+ *                      adaptive_avg_pool2d (window floor(o in / out) .. ceil((o + 1) in / out)). 4, 16 or the window's taps are summed in
+ *                      fp64 in row-major order, acc += (wy * wx) * x (area: acc += x, then acc / count), and rounded once.
+ *   IR_CHAIN_GAUSS     a = gray, s = sigma (a float32 value), data = a standard-normal field of floats, [h][w][3] or for gray [h][w]:
+ *                      x + n * sigma / 255 in float32, clip to [0, 1].
+ *   IR_CHAIN_POISSON   a = gray, s = scale (a float32 value), data = a uniform field of doubles in [0, 1), [h][w][3] or for gray [h][w].
+ *                      utils/degradation.py:generate_poisson_noise_pt: level = clip(rint(x * 255), 0, 255) (gray: of float32 (0.2989 R + 0.587 G)
+ *                      + 0.114 B), r = level / 255, vals = the power of two at or above the number of distinct levels of the image (found
+ *                      through a 256-entry presence array and plain stores), lambda = r * vals; P = the smallest k whose cumulative sum
+ *                      exceeds u, with p(0) = exp_table[log2(vals)][level], p(k + 1) = p(k) * lambda / (k + 1) in fp64 (at most 1024 steps);
+ *                      x + (P / vals - r) * scale in float32 on the unrounded x, clip to [0, 1].
+ *   IR_CHAIN_DIFFJPEG  s = the factor quality_to_factor gives (a float32 value, positive). The clamp to [0, 1] the reference puts in front, then
+ *                      utils/image/diffjpeg.py:DiffJPEG(differentiable=False): zero padding to multiples of 16, * 255, the float32 YCbCr matrix,
+ *                      the 2 x 2 chroma mean, per 8 x 8 block the DCT with the module's float32 basis and scale, / (table * factor) with the
+ *                      module's TRANSPOSED tables, rint, * (table * factor), * alpha, the inverse DCT, replicated chroma, the inverse
+ *                      matrix, the clamp to [0, 255], / 255, the crop. Every 64-term and 3-term sum is fp64 in a fixed order and rounded once.
+ * exp_table: device, doubles [9][256], exp(-(level / 255 * 2 ** j)) with the rate in float32 (needed by a Poisson op); dct_basis: device,
+ * doubles: [64][64] float32(cos((2x + 1) u pi / 16) cos((2y + 1) v pi / 16)) at [8 x + y][8 u + v], then the module's scale [64] and alpha
+ * [64] (needed by a DiffJPEG op). Both are computed by numpy once, so that no difference between two libms enters the bytes.
+ * img and out are [n][rows][pitch] bytes as for ir_degrade (out must not overlap img); chains is a HOST array of n records, read before the
+ * call returns, whose data, exp_table and dct_basis members are device pointers. tap_or_null, when not NULL, receives for every image with
+ * tap >= 0 the float32 image behind op `tap`, [ih][iw][3], the images of the batch packed behind each other. Stream-ordered, no allocation,
+ * no host synchronisation (capturable); the images follow each other through one workspace. ws: 256-byte aligned,
+ * ir_workspace_bytes(ctx, IR_STAGE_DEGRADE_CHAIN, n, h, w, max_ih, max_iw, 0) bytes with max_ih, max_iw the largest height and width among the
+ * intermediate images of all chains (two float images of max(h, max_ih) x max(w, max_iw), the DiffJPEG planes, the presence array).
+ * Returns -1 (nothing launched, out untouched, ir_last_error set) for a null pointer, n < 1, h above rows, a pitch below 3 w, a side above
+ * 8192, more than 16 ops, a tap that is no op's index, an unknown kind or mode, an even K or one above 21, an image too small for its
+ * filter, an op without its (aligned) array or table, a negative level, a factor that is not positive, a scale factor that does not give
+ * the op's output size, a chain that does not end at h x w, or a short or misaligned workspace. */
+enum { IR_CHAIN_FILTER = 1, IR_CHAIN_RESIZE = 2, IR_CHAIN_GAUSS = 3, IR_CHAIN_POISSON = 4, IR_CHAIN_DIFFJPEG = 5 };
+enum { IR_CHAIN_AREA = 0, IR_CHAIN_BILINEAR = 1, IR_CHAIN_BICUBIC = 2 };
+enum { IR_CHAIN_MAX_OPS = 16 };
+typedef struct ir_chain_op {
+    int kind;           /* IR_CHAIN_* */
+    int a, b, c;
+    double s;
+    const void* data;   /* device */
+} ir_chain_op;
+typedef struct ir_chain {
+    int n_ops, tap;             /* tap: -1, or the op whose output goes to tap_or_null */
+    const double* exp_table;    /* device */
+    const double* dct_basis;    /* device */
+    ir_chain_op ops[IR_CHAIN_MAX_OPS];
+} ir_chain;
+int ir_degrade_chain(ir_ctx* ctx, void* stream, const uint8_t* img, int rows, long pitch, int n, int h, int w, const ir_chain* chains,
+                     uint8_t* out, float* tap_or_null, void* ws, size_t ws_bytes);
 
 /* Single-kernel entry points, exported so tests/ can check every kernel against the oracle through the same ABI. */
 int ir_op_conv(ir_ctx* ctx, void* stream, const uint16_t* in, const uint16_t* wgt, const float* bias, void* out, int n, int h, int w,

@@ -117,12 +117,15 @@ def parse_args() -> Namespace:
                         "`clipiqa: x.xxxxx` come last. Which files are scored follows --gt's rule; files below 32 pixels on an edge are counted as not scored")
     parser.add_argument("--clip_bpe", type=str, default=None, help="with --clipiqa_model: the folder that holds CLIP's BPE table (bpe_simple_vocab_16e6.txt.gz, or "
                         "vocab.json + merges.txt), from which the ten prompts are tokenised")
-    parser.add_argument("--degrade", type=str, nargs="?", const="lq", default=None, metavar="lq|FILE.json", help="--input holds GROUND TRUTH: synthesise every "
+    parser.add_argument("--degrade", type=str, nargs="?", const="lq", default=None, metavar="lq|realesrgan|FILE.json", help="--input holds GROUND TRUTH: synthesise every "
                         "file's low-quality image on the GPU (ir_degrade; the definition of tools/degrade_folder.py) and restore that - the first-order "
                         "degradation of the reference's dataset/codeformer.py and tools/lq.py: 41 x 41 iso / aniso Gaussian blur, bilinear downsample by "
                         "U[2,4], Gaussian noise of sigma U[0,20], JPEG at quality int(U[60,100]), bilinear resize back. `lq` (default) holds tools/lq.py's "
                         "constants; a JSON file may set blur_kernel_size, kernel_list (iso, aniso), kernel_prob, blur_sigma, downsample_range, noise_range, "
-                        "jpeg_range and norm (none, or max for tools/lq.py's division by the maximum). No OpenCV, no second folder: the LQ image never "
+                        "jpeg_range and norm (none, or max for tools/lq.py's division by the maximum). `realesrgan` is the SECOND-ORDER recipe the reference "
+                        "validates general super-resolution with (configs/general_deg_realesrgan_val.yaml; ir_degrade_chain): two stages of blur, area / "
+                        "bilinear / bicubic resize, Gaussian or Poisson noise and DiffJPEG, a final sinc filter, bicubic back - files of at least 44 pixels "
+                        "on the short side; a JSON file with \"chain\": \"realesrgan\" may set that recipe's keys. No OpenCV, no second folder: the LQ image never "
                         "leaves the device. Switches --resize gpu on; not offered with --show_lq, --use_center_crop, --shard_tiles. Without --gt the input "
                         "folder is the ground truth of --metrics_out / --lpips_lin / --niqe_params / --clipiqa_model")
     parser.add_argument("--degrade_seed", type=int, default=231, help="with --degrade: a file's parameters are drawn from a generator seeded by this number "

@@ -26,7 +26,7 @@ SYMBOLS = [
     "ir_dit_set_prompts", "ir_op_attention_kv_groups", "ir_graph_records", "ir_op_vae_segment", "ir_op_vae_segment_ws", "ir_op_vae_segment_info",
     "ir_png_bound", "ir_png_encode", "ir_resample_plan_bytes", "ir_resample_plan", "ir_resample_u8", "ir_metrics_y",
     "ir_lpips_scale_table", "ir_lpips_configure", "ir_lpips", "ir_niqe_window", "ir_niqe_stats",
-    "ir_clipiqa_scale_table", "ir_clipiqa_configure", "ir_clipiqa", "ir_degrade_qtables", "ir_degrade",
+    "ir_clipiqa_scale_table", "ir_clipiqa_configure", "ir_clipiqa", "ir_degrade_qtables", "ir_degrade", "ir_degrade_chain",
 ]
 
 STAGE_SWINIR, STAGE_VAE_ENCODE, STAGE_DIT, STAGE_VAE_DECODE, STAGE_PIPELINE, STAGE_COLORFIX, STAGE_T5, STAGE_CLDM, STAGE_CLDM_PIPELINE, STAGE_CLIP_TEXT, STAGE_PNG, STAGE_RESAMPLE, STAGE_METRICS = range(13)
@@ -36,6 +36,10 @@ STAGE_CLIPIQA = 15
 STAGE_DEGRADE = 16
 DEGRADE_NORM_NONE, DEGRADE_NORM_MAX = 0, 1
 DEGRADE_MAX_KSIZE, DEGRADE_MIN_LOW = 41, 8
+STAGE_DEGRADE_CHAIN = 17
+CHAIN_FILTER, CHAIN_RESIZE, CHAIN_GAUSS, CHAIN_POISSON, CHAIN_DIFFJPEG = 1, 2, 3, 4, 5   # ir_chain_op.kind
+CHAIN_AREA, CHAIN_BILINEAR, CHAIN_BICUBIC = 0, 1, 2   # a resize op's mode
+CHAIN_MAX_OPS, CHAIN_MAX_KSIZE, CHAIN_MAX_SIDE = 16, 21, 8192
 LPIPS_NOT_CONFIGURED = -12   # ir_lpips before ir_lpips_configure
 CLIPIQA_NOT_CONFIGURED = -13   # ir_clipiqa before ir_clipiqa_configure
 FLAG_NO_PREPROCESS, FLAG_TILED, FLAG_FIX_WAVELET, FLAG_FIX_ADAIN, FLAG_CONTROL_LQ, FLAG_GRAPH, FLAG_FP8 = 1, 2, 4, 8, 16, 32, 64
@@ -55,6 +59,16 @@ class DegradeParams(C.Structure):
     """ir_degrade_params (include/instarevive_hip.h): one image's record; kernel and noise are device addresses."""
     _fields_ = [("kernel", C.c_void_p), ("noise", C.c_void_p), ("ksize", C.c_int), ("lh", C.c_int), ("lw", C.c_int), ("q", C.c_int),
                 ("norm", C.c_int), ("sigma", C.c_float)]
+
+
+class ChainOp(C.Structure):
+    """ir_chain_op (include/instarevive_hip.h): data is a device address."""
+    _fields_ = [("kind", C.c_int), ("a", C.c_int), ("b", C.c_int), ("c", C.c_int), ("s", C.c_double), ("data", C.c_void_p)]
+
+
+class Chain(C.Structure):
+    """ir_chain (include/instarevive_hip.h): one image's ops; exp_table and dct_basis are device addresses."""
+    _fields_ = [("n_ops", C.c_int), ("tap", C.c_int), ("exp_table", C.c_void_p), ("dct_basis", C.c_void_p), ("ops", ChainOp * 16)]
 
 
 class NativeLibraryError(RuntimeError):
@@ -181,6 +195,7 @@ def load_library():
     lib.ir_clipiqa.argtypes = [vp, vp, vp, i, C.c_long, i, i, i, vp, vp, vp, sz]
     lib.ir_degrade_qtables.argtypes = [i, vp, vp]
     lib.ir_degrade.argtypes = [vp, vp, vp, i, C.c_long, i, i, i, C.POINTER(DegradeParams), vp, vp, vp, sz]
+    lib.ir_degrade_chain.argtypes = [vp, vp, vp, i, C.c_long, i, i, i, C.POINTER(Chain), vp, vp, vp, sz]
     for name in SYMBOLS:
         fn = getattr(lib, name)
         if fn.restype is C.c_int and name not in ("ir_abi_version",):

@@ -2988,7 +2988,41 @@ int ir_degrade(ir_ctx* c, void* stream, const uint8_t* img, int rows, long pitch
     return 0;
 }
 
+// ---------------------------------------------------------------- the second-order degradation chain (degrade_chain.hip)
+static long chain_tap_floats(const ir_chain& ch, int h, int w) {   // the size of the image behind op `tap`
+    if (ch.tap < 0) return 0;
+    for (int i = 0; i <= ch.tap; ++i)
+        if (ch.ops[i].kind == IR_CHAIN_RESIZE) h = ch.ops[i].b, w = ch.ops[i].c;
+    return (long)h * w * 3;
+}
+int ir_degrade_chain(ir_ctx* c, void* stream, const uint8_t* img, int rows, long pitch, int n, int h, int w, const ir_chain* chains, uint8_t* out,
+                     float* tap_or_null, void* ws, size_t ws_bytes) {
+    if (!c || !img || !chains || !out || !ws) return fail(c, -1, "ir_degrade_chain: null argument");
+    if (n < 1 || h < 1 || w < 1 || h > rows || pitch < 3L * w || h > IR_CHAIN_MAX_SIDE || w > IR_CHAIN_MAX_SIDE)
+        return fail(c, -1, "ir_degrade_chain: bad size (n %d, %d x %d in %d rows pitch %ld)", n, h, w, rows, pitch);
+    int mh = h, mw = w;
+    for (int i = 0; i < n; ++i) {   // every chain is checked before the first launch
+        int ih, iw;
+        const char* why;
+        if (ir_degrade_chain_check(&chains[i], h, w, &ih, &iw, &why)) return fail(c, -1, "ir_degrade_chain: image %d (%d x %d): %s", i, h, w, why);
+        mh = std::max(mh, ih), mw = std::max(mw, iw);
+    }
+    const size_t need = ir_degrade_chain_workspace(h, w, mh, mw);
+    if (ws_bytes < need || (reinterpret_cast<uintptr_t>(ws) & 255))
+        return fail(c, -1, "ir_degrade_chain: workspace too small or unaligned (%zu < %zu)", ws_bytes, need);
+    if (tap_or_null && (reinterpret_cast<uintptr_t>(tap_or_null) & 3)) return fail(c, -1, "ir_degrade_chain: misaligned tap pointer");
+    use_ctx(c);
+    for (int i = 0; i < n; ++i) {
+        if (ir_launch_degrade_chain(img + (long)i * rows * pitch, pitch, h, w, &chains[i], mh, mw, out + (long)i * rows * pitch, pitch, tap_or_null, ws,
+                                    (hipStream_t)stream))
+            return fail(c, -100, "ir_degrade_chain: launch failed (image %d)", i);
+        if (tap_or_null) tap_or_null += chain_tap_floats(chains[i], h, w);
+    }
+    return 0;
+}
+
 size_t ir_workspace_bytes(ir_ctx* c, int stage, int n, int h, int w, int flags, int tile_size, int tile_stride) {
+    if (stage == IR_STAGE_DEGRADE_CHAIN) return n < 1 ? 0 : ir_degrade_chain_workspace(h, w, flags, tile_size);   // a function of the sizes alone: no context needed
     if (stage == IR_STAGE_DEGRADE) return n < 1 ? 0 : ir_degrade_workspace(h, w);   // a function of the image size alone (the images of a batch share it): no context needed
     if (stage == IR_STAGE_NIQE) return (n < 1 || h < IR_NIQE_BLOCK || w < IR_NIQE_BLOCK) ? 0 : niqe_workspace(n, h, w);   // a function of the sizes alone: no context needed
     if (stage == IR_STAGE_CLIPIQA) {   // a function of the sizes and of the configured layer counts

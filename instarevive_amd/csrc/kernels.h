@@ -293,6 +293,17 @@ size_t ir_degrade_workspace(int h, int w);
 int ir_launch_degrade(const uint8_t* img, long pitch, int h, int w, const double* k, int K, int lh, int lw, float sigma, int q, const float* noise,
                       int norm, uint8_t* out, long out_pitch, uint8_t* jpeg, void* ws, hipStream_t s);
 
+// ---- the second-order degradation chain (degrade_chain.hip); ir_chain: include/instarevive_hip.h
+// check: walks one image's ops (host) -> 0 and the largest height and width among its images, or -1 and the reason. workspace: two float images of the
+// largest size, the DiffJPEG planes and the presence array. launch: the chain of one image, ws 256-byte aligned; the chain has passed check.
+#define IR_CHAIN_MAX_KSIZE 21
+#define IR_CHAIN_MAX_SIDE 8192
+struct ir_chain;
+int ir_degrade_chain_check(const ir_chain* ch, int h, int w, int* max_ih, int* max_iw, const char** why);
+size_t ir_degrade_chain_workspace(int h, int w, int max_ih, int max_iw);
+int ir_launch_degrade_chain(const uint8_t* img, long pitch, int h, int w, const ir_chain* ch, int max_ih, int max_iw, uint8_t* out, long out_pitch,
+                            float* tap, void* ws, hipStream_t s);
+
 // ---- layout / elementwise (elementwise.hip)
 int ir_launch_u8_to_nchw(const uint8_t* in, float* out, int N, int H, int W, hipStream_t s);
 int ir_launch_swin_prep(const float* x_nchw, bf16_t* out, int N, int H, int W, const float* mean3, float img_range, hipStream_t s);

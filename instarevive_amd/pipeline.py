@@ -398,7 +398,8 @@ def process(model, control_imgs: List[np.ndarray], strength: float, color_fix_ty
     clipiqa (fused form only; with or without gt and niqe): score CLIP-IQA as well - ir_clipiqa with the model instarevive_amd.clipiqa.configure()
     bound to the models' context, queued behind ir_niqe_stats on the same final rectangles (niqe_rects serves both). Its value is the last of
     every tuple: (clipiqa,), (niqe, clipiqa), (psnr_y, ssim_y[, lpips][, niqe], clipiqa). An image below 32 pixels on an edge gets NaN.
-    degrade (with resize): one instarevive_amd.degrade.Params per image - the decoded files are GROUND TRUTH, and between the upload and the
+    degrade (with resize): one instarevive_amd.degrade.Params (or one degrade.ChainParams - the second-order chain, ir_degrade_chain; a batch
+    holds one kind) per image - the decoded files are GROUND TRUTH, and between the upload and the
     bicubic chain ir_degrade makes each one's LQ image on the device (blur, bilinear downsample, noise, JPEG round trip, bilinear resize back;
     tools/degrade_folder.py is the definition), which the network then restores. lq_sink: called once with the list of those LQ images (HWC
     uint8, the decoded files' sizes) after they have been downloaded, before process() returns."""
@@ -507,7 +508,7 @@ def process_stream(model, batches: Iterable[Sequence[np.ndarray]], color_fix_typ
     stream uploads the decoded bytes, the compute stream runs ir_resample_u8 once or twice per image into the staging input ahead of ir_pipeline
     and, behind it, LANCZOS of the valid rectangles back to the LQ sizes where auto_resize enlarged; the batch's lists hold the final images
     as in process(resize=...), and with png (the rectangles are then the final sizes) every file of the batch comes from the device encoder.
-    degrade: an iterable in step with `resize`, advanced like it: per batch None, or one instarevive_amd.degrade.Params per image - the decoded
+    degrade: an iterable in step with `resize`, advanced like it: per batch None, or one instarevive_amd.degrade.Params (or degrade.ChainParams) per image - the decoded
     files are then ground truth and ir_degrade makes their LQ images on the device ahead of the bicubic chain, as in process(degrade=...); the
     kernels and noise fields ride the copy stream with the images. lq_sink: called with the list of a batch's LQ images (downloaded on the
     copy stream) right before that batch's results are yielded.

@@ -169,11 +169,13 @@ class ResizeSlot(Pooled):
 
     def fill(self, records: Sequence[ResizeJob], degrade=None) -> None:
         """Copy the decoded files into the page-locked buffer (after the previous upload out of it has completed). degrade: one degrade.Params
-        per image, or None - their blur kernels and noise fields travel behind the images."""
+        (or one degrade.ChainParams: a batch holds one kind) per image, or None - their blur kernels and noise fields travel behind the images."""
         if degrade is not None:
             from . import degrade as D
             if len(degrade) != len(records):
                 raise ValueError("degrade: one parameter record per image")
+            if len({isinstance(p, D.ChainParams) for p in degrade}) > 1:
+                raise ValueError("degrade: a batch holds one kind of record (degrade.Params or degrade.ChainParams)")
             for rec, p in zip(records, degrade):
                 D.check_params(p, *rec.raw.shape[:2])
         if self.h2d_done is not None:
@@ -213,12 +215,15 @@ class ResizeSlot(Pooled):
 
     def degrade(self, records: Sequence[ResizeJob]) -> None:
         """Between upload() and to_network(), on the current stream: every decoded file (ground truth) becomes its LQ image in d_lq, at the
-        file's offset, by ir_degrade with the parameters fill() staged. The files differ in size, so each is a call of its own."""
+        file's offset, by ir_degrade (ir_degrade_chain for ChainParams) with the parameters fill() staged. The files differ in size, so each is a call of its own."""
         from . import degrade as D
         self.d_lq = _grown(self.d_lq, self.img_bytes, self.ctx.device)
         base = self.d_raw.data_ptr()
         for rec, p, o, (k_at, n_at) in zip(records, self.dparams, self.offsets, self.extras):
             h, w = rec.raw.shape[:2]
+            if isinstance(p, D.ChainParams):   # k_at: the offsets of the chain's kernels and fields
+                D.launch_chain_params(self.ctx, p, base + o, self.d_lq.data_ptr() + o, h, w, base, k_at)
+                continue
             D.launch(self.ctx, base + o, self.d_lq.data_ptr() + o, h, 3 * w, h, w, [D.record(p, base + k_at, base + n_at if n_at is not None else None)])
         self.lq_made = True
 
