@@ -196,10 +196,6 @@ def load_library():
     lib.ir_degrade_qtables.argtypes = [i, vp, vp]
     lib.ir_degrade.argtypes = [vp, vp, vp, i, C.c_long, i, i, i, C.POINTER(DegradeParams), vp, vp, vp, sz]
     lib.ir_degrade_chain.argtypes = [vp, vp, vp, i, C.c_long, i, i, i, C.POINTER(Chain), vp, vp, vp, sz]
-    for name in SYMBOLS:
-        fn = getattr(lib, name)
-        if fn.restype is C.c_int and name not in ("ir_abi_version",):
-            pass
     _lib = lib
     return lib
 

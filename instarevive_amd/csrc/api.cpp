@@ -1,213 +1,19 @@
 // C-ABI layer of the MI355X-native InstaRevive path: context, device weight store, workspace arena and the stage
 // orchestration (which kernel runs on which buffer, in which order). See include/instarevive_hip.h for the contract
 // and the reference file:line each entry point replaces. Host code only; every arithmetic step is a HIP kernel.
-#include <hip/hip_runtime.h>
 #include <math.h>
-#include <stdarg.h>
-#include <stdio.h>
 #include <string.h>
 
 #include <algorithm>
 #include <memory>
-#include <string>
-#include <unordered_map>
-#include <vector>
 
-#include "../../include/instarevive_hip.h"
-#include "kernels.h"
+#include "host.h"
+
+using namespace ir_host;
 
 enum { ACT_NONE = 0, ACT_GELU_ERF = 1, ACT_GELU_TANH = 2, ACT_LRELU = 3, ACT_SILU = 4 };
 
-namespace {
-
-struct Tensor {
-    void* p = nullptr;
-    size_t bytes = 0;
-};
-
-struct Conv {  // packed conv / linear weight: w [cout_pad][taps*cin] bf16, b [cout_pad] fp32
-    const bf16_t* w = nullptr;
-    const float* b = nullptr;
-    int cin = 0, cout = 0, cout_pad = 0, taps = 1;
-    int cin_r = 0, cout_r = 0;  // un-padded channel counts for the algorithmic FLOP count of the profiler (0: cin / cout)
-    long w_rs = 0;  // weight row stride in elements (0: taps*cin, densely packed)
-    // optional fp8 form (BASELINE.json configs[4]): OCP e4m3 weights [cout][9][cin] quantised per output channel, the dequantisation
-    // factor per channel (weight scale / activation scale) and the bias divided by it (see IGemmParams::fp8)
-    const uint8_t* w8 = nullptr;
-    const float *g8 = nullptr, *b8 = nullptr;
-    // optional sub-pixel phase matrices of a conv that follows a nearest-2x upsample: [4][cout][4][cin] bf16 (weights.pack_conv_up2x2)
-    const bf16_t* wup = nullptr;
-};
 constexpr float FP8_ACT_SCALE = 16.0f;  // GroupNorm+SiLU outputs are stored as e4m3(x * 16): |x| up to 28 without clamping, 3 mantissa bits down to 2^-10
-struct Norm {
-    const float *g = nullptr, *b = nullptr;
-    int c = 0;
-};
-
-struct SwinBlock {
-    Norm n1, n2;
-    Conv qkv, proj, fc1, fc2;
-    const float* biasT = nullptr;
-    const float* biasM = nullptr;  // shifted blocks: [4 window classes][heads][64][64] bias tables with the attention mask folded in (the fused kernels), optional
-    const void* mlp_t = nullptr;   // weight tiles + vectors of the fused LN2 -> fc1 -> GELU -> fc2 -> + x kernel (swin_fused.hip), optional
-    const float* mlp_v = nullptr;
-    const void* proj_t = nullptr;  // proj weights with columns in accumulator order for the fused window attention + projection kernel, optional
-    const void* qkv_t = nullptr;   // qkv weights as ring tiles of swin_mlp_kernel: the PREVIOUS block's fused MLP launch also makes this block's qkv rows, optional
-};
-struct SwinLayer {
-    std::vector<SwinBlock> blocks;
-    Conv conv;
-};
-struct SwinModel {
-    bool ok = false;
-    int C = 0, Cp = 0, heads = 0, hid = 0, hid_p = 0, nf = 0;
-    float range = 1.f, mean[3] = {0, 0, 0};
-    Conv conv_first, after_body, before_up, up1, up2, up3, hr, last;
-    Norm pe, norm;
-    std::vector<SwinLayer> layers;
-};
-
-struct ResW {
-    Norm n1, n2;
-    Conv c1, c2, sc;
-    bool has_sc = false;
-};
-struct AttnW {
-    Norm n;
-    Conv q, k, v, o;
-};
-struct VaeLevel {
-    std::vector<ResW> res;
-    bool has_resample = false;
-    Conv resample;
-};
-struct VaeHalf {
-    bool ok = false;
-    Conv conv_in, conv_out;
-    std::vector<VaeLevel> levels;  // index = i_level (ldm numbering)
-    ResW mid1, mid2;
-    AttnW attn;
-    Norm norm_out;
-    int cmax = 0;
-};
-struct VaeModel {
-    VaeHalf enc, dec;
-    const float *qw = nullptr, *qb = nullptr, *pqw = nullptr, *pqb = nullptr;
-};
-
-struct DitLayer {
-    const float* sst = nullptr;
-    Conv qkv, ao, cq, ckv, co, fc1, fc2;
-    bf16_t* kc = nullptr;   // [P][n_tok][2*hidden] cached K|V of the prompts (P = DitModel::n_prompts; rows for prompt_slots x tok_pad allocated)
-    bf16_t* vtc = nullptr;  // [P][heads][DV][tok_pad]
-    // optional branches of the self-attention (AttentionKVCompress, PixArt_blocks.py:60-158; round 6): KV token compression by a depthwise r x r / stride r
-    // convolution over the token grid (kvc_w [C][r*r], kvc_b; 'uniform' / 'ave' sampling arrive as a weight of 1 on the first tap) with an optional LayerNorm
-    // (kvc_g / kvc_beta: the 'conv' sampler's `norm`), and LayerNorm on q and k (qk_norm)
-    int kvc_r = 1;
-    const float *kvc_w = nullptr, *kvc_b = nullptr, *kvc_g = nullptr, *kvc_beta = nullptr, *qn_g = nullptr, *qn_b = nullptr, *kn_g = nullptr, *kn_b = nullptr;
-};
-struct DitModel {
-    bool ok = false, prompt_ok = false;
-    int L = 0, heads = 0, hd = 0, C = 0, mlp = 0, cap = 0, base = 0;
-    Conv patch, cap1, cap2, fin;
-    const float *t1w = nullptr, *t1b = nullptr, *t2w = nullptr, *t2b = nullptr, *tbw = nullptr, *tbb = nullptr, *fsst = nullptr;
-    std::vector<DitLayer> layers;
-    // ControlNet-Half branch (transformer_controlnet.py:58-76): copies of the first ncopy blocks, each followed by after_proj;
-    // before_proj in front of copy 0. Empty unless ir_dit_control_configure ran.
-    int ncopy = 0;
-    std::vector<DitLayer> ctrl;
-    std::vector<Conv> after;
-    Conv before;
-    int n_tok = 0, tok_pad = 0;
-    float* key_bias = nullptr;   // [P][n_tok]
-    // prompt slots (ir_dit_set_prompts): item b of every cross-attention launch attends to slot b % n_prompts; the slot strides of kc / vtc /
-    // key_bias (elements) are 0 while one prompt is set, so that launch is today's single-prompt one
-    int n_prompts = 1;
-    long kc_slot = 0, vt_slot = 0, kb_slot = 0;
-    // timestep-dependent tables (recomputed when the timestep changes)
-    float cached_t = -1e30f;
-    float *tsin = nullptr, *th = nullptr, *emb = nullptr, *semb = nullptr, *t6 = nullptr, *modtab = nullptr, *fmod = nullptr;
-    float* ctrl_modtab = nullptr;
-    // Micro-conditioning (round 6; scripts/DMD/transformer_train/generate.py:56-62 builds `resolution` / `aspect_ratio` when config.sample_size == 128;
-    // diffusers' PixArtAlphaCombinedTimestepSizeEmbeddings, whose in-tree twin is SizeEmbedder, PixArt_blocks.py:366-399, wired as in
-    // diffusion/model/nets/controlnet.py:189-191): S = C / 3 > 0 when the host uploaded the two embedders (dit.res1 / dit.res2 / dit.ar1 / dit.ar2). The
-    // conditioning vector is then emb(t) + [size_emb(h) | size_emb(w) | ar_emb(h / w)] of the LATENT's height and width, so the tables also depend on them.
-    int S = 0;
-    const float *rs1w = nullptr, *rs1b = nullptr, *rs2w = nullptr, *ar1w = nullptr, *ar1b = nullptr, *ar2w = nullptr;
-    float *tsin2 = nullptr, *th2 = nullptr;
-    int cached_h = -1, cached_w = -1;
-};
-
-// T5 v1.1 encoder (prompt producer, diffusion/model/t5.py:82-101)
-struct T5Layer {
-    const float *ln1 = nullptr, *ln2 = nullptr;
-    Conv qkv, o, wi, wo;   // q|k|v fused [3*H*dk][D]; wi_0|wi_1 fused [2F][D]
-};
-struct T5Model {
-    bool ok = false;
-    int L = 0, D = 0, H = 0, dk = 0, F = 0, vocab = 0;
-    const bf16_t* embed = nullptr;
-    const float* final_ln = nullptr;
-    std::vector<T5Layer> layers;
-    int* bad = nullptr;   // device flag: an input id was outside the vocabulary
-};
-
-
-// OpenCLIP text tower of the ControlLDM path's cond_stage_model (FrozenOpenCLIPEmbedder.encode_with_transformer, ldm/modules/encoders/modules.py:
-// 176-193: token + positional embedding, pre-LN transformer blocks with a causal mask, ln_final)
-struct ClipLayer {
-    Norm n1, n2;
-    Conv qkv, o, fc, proj;   // in_proj (q rows pre-scaled by d_head^-0.5), out_proj, mlp.c_fc, mlp.c_proj
-};
-struct ClipTextModel {
-    bool ok = false;
-    int L = 0, D = 0, H = 0, dk = 0, F = 0, vocab = 0, T = 0;
-    const bf16_t* embed = nullptr;
-    const float *pos = nullptr, *causal = nullptr;   // [T][D]; [H][T][T] additive mask (0 / -3e38)
-    Norm final_ln;
-    std::vector<ClipLayer> layers;
-    int* bad = nullptr;
-};
-
-// SD-2.1 UNet / ControlNet of the ControlLDM one-step path (ldm/modules/diffusionmodules/openaimodel.py:411-786,
-// diffusion/cldm.py:58-292)
-struct UResW {        // ResBlock (openaimodel.py:163-272, use_scale_shift_norm = False)
-    Norm n1, n2;
-    Conv c1, c2, sc;
-    bool has_sc = false;
-    const float *ew = nullptr, *eb = nullptr;  // emb_layers.1 [cout][temb] fp32; eb already holds in_layers.2's bias + emb_layers.1's bias
-    float* bias1 = nullptr;                    // device [cout_pad]: the bias conv1 runs with = eb + ew . silu(emb) for the cached timestep
-};
-struct UXfW {         // SpatialTransformer with one BasicTransformerBlock (attention.py:205-350, use_linear = True)
-    Norm gn, l1, l2, l3;
-    Conv pin, pout, qkv, ao, cq, ckv, co, ff1, ff2;
-    int heads = 0;
-    bf16_t* kc = nullptr;    // [tok_pad][2C]: K | V of the context (set by ir_unet_set_context)
-    bf16_t* vtc = nullptr;   // [heads][DV][tok_pad]
-};
-struct UBlock {
-    bool has_res = false, has_xf = false;
-    int resample = 0;   // 1: Downsample (stride-2 conv), 2: Upsample (nearest x2 + conv), 3: input_blocks.0 (the first conv)
-    UResW res;
-    UXfW xf;
-    Conv rs;
-    int cin = 0, cout = 0;   // channels entering / leaving the block (decoder: cin = h + skip)
-    int skip = 0;            // decoder: channels of the skip it pops
-};
-struct UNetW {
-    bool ok = false, ctx_ok = false, control = false;
-    int mc = 0, temb = 0, ctx_dim = 0, hd = 0, in_ch = 0, n_levels = 0;
-    std::vector<UBlock> in, mid, out;
-    std::vector<Conv> zero;   // ControlNet: zero_convs[i] per input block, then middle_block_out
-    Norm out_norm;
-    Conv out_conv;
-    const float *t1w = nullptr, *t1b = nullptr, *t2w = nullptr, *t2b = nullptr;
-    float *tsin = nullptr, *th = nullptr, *emb = nullptr, *semb = nullptr;
-    float cached_t = -1e30f;
-    int n_tok = 0, tok_pad = 0;
-};
-
-}  // namespace
 
 // optional per-launch timing with HIP events on the launch stream (bench.py's roofline numbers come from here)
 enum { PC_CONV3X3 = 0, PC_LINEAR, PC_FLASH_ATTN, PC_SWIN_ATTN, PC_GROUPNORM, PC_LAYERNORM, PC_SOFTMAX, PC_TRANSPOSE, PC_OTHER, PC_COUNT };
@@ -232,98 +38,8 @@ static const int KERNEL_CLASS[PK_COUNT] = {PC_CONV3X3, PC_CONV3X3, PC_CONV3X3, P
                                            PC_FLASH_ATTN, PC_FLASH_ATTN, PC_FLASH_ATTN, PC_FLASH_ATTN, PC_SWIN_ATTN, PC_SWIN_ATTN, PC_GROUPNORM, PC_GROUPNORM, PC_LAYERNORM,
                                            PC_SOFTMAX, PC_TRANSPOSE, PC_OTHER, PC_CONV3X3, PC_CONV3X3, PC_LINEAR, PC_CONV3X3, PC_CONV3X3};
 static const int CLASS_DEFAULT_KERNEL[PC_COUNT] = {PK_CONV_IGEMM, PK_LINEAR_IGEMM, PK_ATTN_OTHER, PK_SWIN_ATTN, PK_GN_FULL, PK_LAYERNORM, PK_SOFTMAX, PK_TRANSPOSE, PK_OTHER};
-struct ProfRec {
-    int cls, kid;
-    double flops, bytes;
-    hipEvent_t e0, e1;
-};
-struct Profiler {
-    bool on = false;
-    int only = -1;   // ir_profile_select: kernel id whose launches alone are bracketed (-1: every launch)
-    std::vector<ProfRec> recs;
-    std::vector<hipEvent_t> pool;
-    size_t used = 0;
-    hipEvent_t get() {
-        if (used == pool.size()) {
-            hipEvent_t e;
-            if (hipEventCreate(&e) != hipSuccess) return nullptr;
-            pool.push_back(e);
-        }
-        return pool[used++];
-    }
-};
-
-struct ir_ctx {
-    int device = 0;
-    Profiler prof;
-    bool fp8 = false;   // ir_set_fp8 / IR_FLAG_FP8: VAE resnet convs with fp8 operands where fp8 weights were uploaded
-    uint32_t fp8_mask = IR_FP8_MASK_DEFAULT;   // ir_set_fp8_mask: which parts take fp8 operands when fp8 is on (IR_FP8_BIT_*); default = the guard-chosen set
-    bool plain = false; // ir_set_plain_kernels: this context's launches take the older 4-wave kernels (make_run publishes it to the launchers)
-    std::string err;
-    std::unordered_map<std::string, Tensor> t;
-    std::vector<void*> owned;  // extra device allocations that live as long as the context
-    // allocations that belong to one binding and are released when it is replaced: the DiT's timestep tables, the control
-    // branch's tables, the per-layer prompt K/V caches (+ key bias), the T5 flag
-    std::vector<void*> dit_tabs, dit_ctrl_tabs, dit_prompt, t5_owned;
-    int prompt_cap = 0;        // rows (tok_pad) the prompt caches in dit_prompt were sized for
-    int prompt_slots = 0;      // prompts they have room for
-    bf16_t *prompt_e16 = nullptr, *prompt_y1 = nullptr, *prompt_y2 = nullptr;   // ir_dit_set_prompts' caption-MLP operands (in dit_prompt; null until it runs)
-    SwinModel swin;
-    VaeModel vae;
-    DitModel dit;
-    T5Model t5;
-    UNetW unet[2];                                  // [0] the diffusion UNet, [1] the ControlNet
-    ClipTextModel clip;
-    std::vector<void*> clip_owned;
-    std::vector<void*> unet_tabs[2], unet_ctx[2];   // their timestep tables / context K-V caches
-    // hipGraph cache of ir_pipeline (IR_FLAG_GRAPH): one instantiated graph per exact call signature. `generation` changes whenever
-    // device allocations or bindings may have moved (upload with a new size, *_configure, set_prompt), which drops every graph.
-    struct GraphKey {
-        const void *in, *out, *stage1, *ws, *extra;   // extra + kind: which entry point recorded it (0 ir_pipeline, 1 ir_cldm_pipeline)
-        int kind;
-        size_t ws_bytes;
-        int n, h, w, flags, tile_size, tile_stride;
-        float timestep, acp, sf;
-        bool operator==(const GraphKey& o) const { return memcmp(this, &o, sizeof *this) == 0; }
-    };
-    struct GraphEntry { GraphKey key; hipGraphExec_t exec; };
-    std::vector<GraphEntry> graphs;
-    unsigned long generation = 0, graphs_generation = 0;
-    unsigned long graph_records = 0;   // graphs recorded so far (ir_graph_records)
-    hipStream_t cap_stream = nullptr;  // recording happens on a private stream (the caller's may be the legacy default stream, which cannot capture)
-    int* shard_flag = nullptr;         // device copy of the overflow flag of the last ir_tiled_encode_part(part 0 / 2) (in `owned`)
-    int* attn_fb = nullptr;            // ir_attn_fallback_count: [0] attention launches whose fixed-reference kernel raised its overflow flag (in `owned`)
-    bool count_fb = false;             // diagnostic: one counting launch behind every flagged attention (off in the product path)
-    double* luma_tab = nullptr;        // ir_metrics_y: the three 256-entry luma tables, filled by ir_init (in `owned`)
-    double* niqe_tab = nullptr;        // ir_niqe_stats: three luma tables and v / 255.0, filled by ir_init (in `owned`)
-    // ir_lpips: the scaling table, the repacked conv weights [K padded to 32][cout] and copies of the biases / lin heads (in lpips_owned)
-    struct Lpips {
-        bool ok = false;
-        const float *tab = nullptr, *w[5] = {}, *b[5] = {}, *lin[5] = {};
-    } lpips;
-    std::vector<void*> lpips_owned;
-    // ir_clipiqa: the input table, the repacked conv weights, the folded BatchNorm vectors and copies of the attention pool / text rows (in clipiqa_owned)
-    IrClipiqaModel clipiqa;
-    std::vector<void*> clipiqa_owned;
-};
 
 namespace {
-
-int fail(ir_ctx* c, int code, const char* fmt, ...) {
-    char buf[512];
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(buf, sizeof buf, fmt, ap);
-    va_end(ap);
-    if (c) c->err = buf;
-    return code;
-}
-
-#define HIPOK(c, call)                                                                         \
-    do {                                                                                       \
-        hipError_t e_ = (call);                                                                \
-        if (e_ != hipSuccess) return fail(c, -100, "%s failed: %s", #call, hipGetErrorString(e_)); \
-    } while (0)
 
 // ---------------------------------------------------------------- workspace arena (stack discipline, dry-run capable)
 struct Arena {
@@ -597,15 +313,6 @@ struct Binder {
     }
     const float* f32(const std::string& name, size_t count) { return (const float*)get(name, count * 4); }
 };
-int pad32(int x) { return (x + 31) & ~31; }
-std::string fmt(const char* f, ...) {
-    char buf[256];
-    va_list ap;
-    va_start(ap, f);
-    vsnprintf(buf, sizeof buf, f, ap);
-    va_end(ap);
-    return buf;
-}
 
 // ================================================================ SwinIR  (diffusion/model/swinir.py:867-905)
 void swinir_run(Run& r, const float* in, float* out, int n, int h, int w) {
@@ -1756,12 +1463,6 @@ Run make_run(ir_ctx* c, void* stream, void* ws, size_t ws_bytes, bool dry) {
     if (c) g_ir_plain_kernels = c->plain ? 1 : 0;
     return r;
 }
-// entry points that launch without a Run: make the context's GPU current and publish its kernel choice
-void use_ctx(ir_ctx* c) {
-    if (!c) return;
-    (void)hipSetDevice(c->device);
-    g_ir_plain_kernels = c->plain ? 1 : 0;
-}
 int check_size(ir_ctx* c, int n, int h, int w, int mult) {
     if (n <= 0 || h <= 0 || w <= 0 || (h % mult) || (w % mult)) return fail(c, -10, "bad size n=%d h=%d w=%d (need multiples of %d)", n, h, w, mult);
     return 0;
@@ -1783,36 +1484,7 @@ int ir_init(int device, ir_ctx** out) {
     if (hipSetDevice(device) != hipSuccess) return -3;
     ir_ctx* c = new ir_ctx();
     c->device = device;
-    // ir_metrics_y's luma tables: c_k * (double)((float)v / 255.0f), the float32 division of the host model done once on the host
-    {
-        static const double coef[3] = {65.481, 128.553, 24.966};
-        double tab[3 * 256];
-        for (int k = 0; k < 3; ++k)
-            for (int v = 0; v < 256; ++v) {
-                volatile float x = (float)v / 255.0f;
-                tab[256 * k + v] = coef[k] * (double)x;
-            }
-        void* d = nullptr;
-        if (hipMalloc(&d, sizeof tab) != hipSuccess) { delete c; return -4; }
-        if (hipMemcpy(d, tab, sizeof tab, hipMemcpyHostToDevice) != hipSuccess) { (void)hipFree(d); delete c; return -4; }
-        c->owned.push_back(d);
-        c->luma_tab = static_cast<double*>(d);
-    }
-    // ir_niqe_stats' tables: the YIQ luma terms coef_c * (double)((float)v / 255.0f), then v / 255.0 (the unit scale the half-size filter works on)
-    {
-        static const double coef[3] = {0.299, 0.587, 0.114};
-        double tab[4 * 256];
-        for (int v = 0; v < 256; ++v) {
-            volatile float x = (float)v / 255.0f;
-            for (int k = 0; k < 3; ++k) tab[256 * k + v] = coef[k] * (double)x;
-            tab[768 + v] = (double)v / 255.0;
-        }
-        void* d = nullptr;
-        if (hipMalloc(&d, sizeof tab) != hipSuccess) { ir_destroy(c); return -4; }
-        c->owned.push_back(d);
-        if (hipMemcpy(d, tab, sizeof tab, hipMemcpyHostToDevice) != hipSuccess) { ir_destroy(c); return -4; }
-        c->niqe_tab = static_cast<double*>(d);
-    }
+    if (image_init(c)) { ir_destroy(c); return -4; }
     *out = c;
     return 0;
 }
@@ -1821,8 +1493,8 @@ void ir_destroy(ir_ctx* c) {
     if (!c) return;
     (void)hipSetDevice(c->device);
     for (auto& kv : c->t) (void)hipFree(kv.second.p);
-    for (std::vector<void*>* l : {&c->owned, &c->dit_tabs, &c->dit_ctrl_tabs, &c->dit_prompt, &c->t5_owned, &c->lpips_owned, &c->clipiqa_owned})
-        for (void* p : *l) (void)hipFree(p);
+    for (auto& list : c->own)
+        for (void* p : list) (void)hipFree(p);
     for (hipEvent_t e : c->prof.pool) (void)hipEventDestroy(e);
     for (auto& g : c->graphs) (void)hipGraphExecDestroy(g.exec);
     if (c->cap_stream) (void)hipStreamDestroy(c->cap_stream);
@@ -2039,22 +1711,9 @@ int ir_vae_configure(ir_ctx* c, int ch, int n_levels, const int* ch_mult, int nu
     return 0;
 }
 
-static int dev_alloc(ir_ctx* c, std::vector<void*>& list, void** p, size_t bytes) {
-    HIPOK(c, hipMalloc(p, (bytes + 255) & ~(size_t)255));
-    list.push_back(*p);
-    return 0;
-}
-// Release the buffers of a binding that is being replaced. Kernels that still read them may be in flight on any stream of the
-// caller, so the device is drained first (re-binding is a load-time operation, never on the hot path).
-static void release_list(std::vector<void*>& list) {
-    if (list.empty()) return;
-    (void)hipDeviceSynchronize();
-    for (void* p : list) (void)hipFree(p);
-    list.clear();
-}
 // the DiT's prompt caches and the temporaries of ir_dit_set_prompts (a re-bind, or a prompt of another 64-token bucket / more prompts than they hold)
 static void release_prompt_caches(ir_ctx* c) {
-    release_list(c->dit_prompt);
+    release_list(c->own[OWN_DIT_PROMPT]);
     c->prompt_cap = c->prompt_slots = 0;
     c->prompt_e16 = c->prompt_y1 = c->prompt_y2 = nullptr;
 }
@@ -2113,21 +1772,21 @@ int ir_dit_configure(ir_ctx* c, int n_layers, int heads, int head_dim, int mlp_h
     }
     if (!b.ok) return fail(c, -2, "ir_dit_configure: tensor %s", b.missing.c_str());
     // a re-bind (load_state_dict / .to again) replaces the previous model's tables, control branch and prompt caches
-    release_list(c->dit_tabs);
-    release_list(c->dit_ctrl_tabs);
+    release_list(c->own[OWN_DIT_TABS]);
+    release_list(c->own[OWN_DIT_CTRL_TABS]);
     release_prompt_caches(c);
     c->dit = DitModel();
     int rc = 0;
-    rc |= dev_alloc(c, c->dit_tabs, (void**)&m.tsin, 256 * 4);
-    rc |= dev_alloc(c, c->dit_tabs, (void**)&m.th, C * 4);
-    rc |= dev_alloc(c, c->dit_tabs, (void**)&m.emb, C * 4);
-    rc |= dev_alloc(c, c->dit_tabs, (void**)&m.semb, C * 4);
-    rc |= dev_alloc(c, c->dit_tabs, (void**)&m.t6, 6 * C * 4);
-    rc |= dev_alloc(c, c->dit_tabs, (void**)&m.modtab, (size_t)n_layers * 6 * C * 4);
-    rc |= dev_alloc(c, c->dit_tabs, (void**)&m.fmod, 2 * C * 4);
+    rc |= dev_alloc(c, c->own[OWN_DIT_TABS], (void**)&m.tsin, 256 * 4);
+    rc |= dev_alloc(c, c->own[OWN_DIT_TABS], (void**)&m.th, C * 4);
+    rc |= dev_alloc(c, c->own[OWN_DIT_TABS], (void**)&m.emb, C * 4);
+    rc |= dev_alloc(c, c->own[OWN_DIT_TABS], (void**)&m.semb, C * 4);
+    rc |= dev_alloc(c, c->own[OWN_DIT_TABS], (void**)&m.t6, 6 * C * 4);
+    rc |= dev_alloc(c, c->own[OWN_DIT_TABS], (void**)&m.modtab, (size_t)n_layers * 6 * C * 4);
+    rc |= dev_alloc(c, c->own[OWN_DIT_TABS], (void**)&m.fmod, 2 * C * 4);
     if (m.S > 0) {
-        rc |= dev_alloc(c, c->dit_tabs, (void**)&m.tsin2, 256 * 4);
-        rc |= dev_alloc(c, c->dit_tabs, (void**)&m.th2, m.S * 4);
+        rc |= dev_alloc(c, c->own[OWN_DIT_TABS], (void**)&m.tsin2, 256 * 4);
+        rc |= dev_alloc(c, c->own[OWN_DIT_TABS], (void**)&m.th2, m.S * 4);
     }
     if (rc) return rc;
     m.ok = true;
@@ -2151,12 +1810,12 @@ int ir_dit_control_configure(ir_ctx* c, int copy_blocks_num) {
         after.push_back(b.conv(fmt("dit.ctrl%d.after", i), m.C, m.C, m.C, 1));
     }
     if (!b.ok) return fail(c, -2, "ir_dit_control_configure: tensor %s", b.missing.c_str());
-    release_list(c->dit_ctrl_tabs);   // a previous control binding's table
+    release_list(c->own[OWN_DIT_CTRL_TABS]);   // a previous control binding's table
     release_prompt_caches(c);         // prompt caches are rebuilt for base + control layers by the next ir_dit_set_prompt
     m.n_prompts = 1; m.kc_slot = m.vt_slot = m.kb_slot = 0;
     for (DitLayer& L : m.layers) L.kc = L.vtc = nullptr;
     float* tab = nullptr;
-    if (dev_alloc(c, c->dit_ctrl_tabs, (void**)&tab, (size_t)copy_blocks_num * 6 * m.C * 4)) return -100;
+    if (dev_alloc(c, c->own[OWN_DIT_CTRL_TABS], (void**)&tab, (size_t)copy_blocks_num * 6 * m.C * 4)) return -100;
     m.ctrl = ctrl; m.after = after; m.before = before; m.ctrl_modtab = tab; m.ncopy = copy_blocks_num;
     ++c->generation;
     m.cached_t = -1e30f;   // the control blocks' modulation tables are built with the timestep tables
@@ -2189,11 +1848,11 @@ int ir_dit_set_prompt(ir_ctx* c, void* stream, const float* embeds_host, const f
     if (!m.key_bias || c->prompt_cap != tok_pad) {
         release_prompt_caches(c);
         m.key_bias = nullptr;
-        if (dev_alloc(c, c->dit_prompt, (void**)&m.key_bias, tok_pad * 4)) return -100;
+        if (dev_alloc(c, c->own[OWN_DIT_PROMPT], (void**)&m.key_bias, tok_pad * 4)) return -100;
         for (std::vector<DitLayer>* set : {&m.layers, &m.ctrl})
             for (DitLayer& L : *set) {
-                if (dev_alloc(c, c->dit_prompt, (void**)&L.kc, (size_t)tok_pad * 2 * C * 2)) return -100;
-                if (dev_alloc(c, c->dit_prompt, (void**)&L.vtc, (size_t)m.heads * DV * tok_pad * 2)) return -100;
+                if (dev_alloc(c, c->own[OWN_DIT_PROMPT], (void**)&L.kc, (size_t)tok_pad * 2 * C * 2)) return -100;
+                if (dev_alloc(c, c->own[OWN_DIT_PROMPT], (void**)&L.vtc, (size_t)m.heads * DV * tok_pad * 2)) return -100;
             }
         c->prompt_cap = tok_pad;
         c->prompt_slots = 1;
@@ -2235,15 +1894,15 @@ int ir_dit_set_prompts(ir_ctx* c, void* stream, const float* embeds_dev, const f
         release_prompt_caches(c);
         m.key_bias = nullptr;
         const size_t slot_rows = (size_t)P * tok_pad;
-        if (dev_alloc(c, c->dit_prompt, (void**)&m.key_bias, slot_rows * 4)) return -100;
+        if (dev_alloc(c, c->own[OWN_DIT_PROMPT], (void**)&m.key_bias, slot_rows * 4)) return -100;
         for (std::vector<DitLayer>* set : {&m.layers, &m.ctrl})
             for (DitLayer& L : *set) {
-                if (dev_alloc(c, c->dit_prompt, (void**)&L.kc, slot_rows * 2 * C * 2)) return -100;
-                if (dev_alloc(c, c->dit_prompt, (void**)&L.vtc, (size_t)P * m.heads * DV * tok_pad * 2)) return -100;
+                if (dev_alloc(c, c->own[OWN_DIT_PROMPT], (void**)&L.kc, slot_rows * 2 * C * 2)) return -100;
+                if (dev_alloc(c, c->own[OWN_DIT_PROMPT], (void**)&L.vtc, (size_t)P * m.heads * DV * tok_pad * 2)) return -100;
             }
-        if (dev_alloc(c, c->dit_prompt, (void**)&c->prompt_e16, slot_rows * m.cap * 2)) return -100;
-        if (dev_alloc(c, c->dit_prompt, (void**)&c->prompt_y1, slot_rows * C * 2)) return -100;
-        if (dev_alloc(c, c->dit_prompt, (void**)&c->prompt_y2, slot_rows * C * 2)) return -100;
+        if (dev_alloc(c, c->own[OWN_DIT_PROMPT], (void**)&c->prompt_e16, slot_rows * m.cap * 2)) return -100;
+        if (dev_alloc(c, c->own[OWN_DIT_PROMPT], (void**)&c->prompt_y1, slot_rows * C * 2)) return -100;
+        if (dev_alloc(c, c->own[OWN_DIT_PROMPT], (void**)&c->prompt_y2, slot_rows * C * 2)) return -100;
         c->prompt_cap = tok_pad;
         c->prompt_slots = P;
     }
@@ -2388,17 +2047,17 @@ int ir_unet_configure(ir_ctx* c, int which, int model_channels, int n_levels, co
         m.out_conv = b.conv(P + ".out.conv", mc, 4, 32, 9);
     }
     if (!b.ok) return fail(c, -2, "ir_unet_configure: tensor %s", b.missing.c_str());
-    release_list(c->unet_tabs[which]);
-    release_list(c->unet_ctx[which]);
+    release_list(c->own[OWN_UNET_TABS + which]);
+    release_list(c->own[OWN_UNET_CTX + which]);
     c->unet[which] = UNetW();
     int rc = 0;
-    rc |= dev_alloc(c, c->unet_tabs[which], (void**)&m.tsin, (size_t)mc * 4);
-    rc |= dev_alloc(c, c->unet_tabs[which], (void**)&m.th, (size_t)temb * 4);
-    rc |= dev_alloc(c, c->unet_tabs[which], (void**)&m.emb, (size_t)temb * 4);
-    rc |= dev_alloc(c, c->unet_tabs[which], (void**)&m.semb, (size_t)temb * 4);
+    rc |= dev_alloc(c, c->own[OWN_UNET_TABS + which], (void**)&m.tsin, (size_t)mc * 4);
+    rc |= dev_alloc(c, c->own[OWN_UNET_TABS + which], (void**)&m.th, (size_t)temb * 4);
+    rc |= dev_alloc(c, c->own[OWN_UNET_TABS + which], (void**)&m.emb, (size_t)temb * 4);
+    rc |= dev_alloc(c, c->own[OWN_UNET_TABS + which], (void**)&m.semb, (size_t)temb * 4);
     for (std::vector<UBlock>* set : {&m.in, &m.mid, &m.out})
         for (UBlock& blk : *set)
-            if (blk.has_res) rc |= dev_alloc(c, c->unet_tabs[which], (void**)&blk.res.bias1, (size_t)blk.res.c1.cout_pad * 4);
+            if (blk.has_res) rc |= dev_alloc(c, c->own[OWN_UNET_TABS + which], (void**)&blk.res.bias1, (size_t)blk.res.c1.cout_pad * 4);
     if (rc) return rc;
     m.ok = true;
     c->unet[which] = m;
@@ -2435,15 +2094,15 @@ int ir_unet_set_context(ir_ctx* c, void* stream, const float* context_host, int 
         for (std::vector<UBlock>* set : {&m.in, &m.mid, &m.out})
             for (UBlock& blk : *set)
                 if (blk.has_xf) blk.xf.kc = nullptr, blk.xf.vtc = nullptr;
-        release_list(c->unet_ctx[which]);
+        release_list(c->own[OWN_UNET_CTX + which]);
         const int DV = ir_attn_dv(m.hd);
         for (std::vector<UBlock>* set : {&m.in, &m.mid, &m.out})
             for (UBlock& blk : *set) {
                 if (!blk.has_xf) continue;
                 UXfW& w = blk.xf;
                 const int C = w.gn.c;
-                if (dev_alloc(c, c->unet_ctx[which], (void**)&w.kc, (size_t)tok_pad * 2 * C * 2)) return -100;
-                if (dev_alloc(c, c->unet_ctx[which], (void**)&w.vtc, (size_t)w.heads * DV * tok_pad * 2)) return -100;
+                if (dev_alloc(c, c->own[OWN_UNET_CTX + which], (void**)&w.kc, (size_t)tok_pad * 2 * C * 2)) return -100;
+                if (dev_alloc(c, c->own[OWN_UNET_CTX + which], (void**)&w.vtc, (size_t)w.heads * DV * tok_pad * 2)) return -100;
                 linear(r, w.ckv, e16, n_tok, ctx_dim, w.kc, 2 * C, 0, ACT_NONE, nullptr, 0, 0);
                 LAUNCH(r, PC_TRANSPOSE, 0.0, 0.0, ir_launch_transpose_v(w.kc + C, w.vtc, 0, 2 * C, m.hd, 1, w.heads, n_tok, tok_pad, m.hd, DV, s), "transpose_v");
             }
@@ -2509,533 +2168,9 @@ static int stage_dispatch(ir_ctx* c, Run& r, int stage, int n, int h, int w, int
     return 0;
 }
 
-// ---------------------------------------------------------------- PNG encoding (png_encode.hip)
-// Bytes of one chunk of `rows` rows at most: the 1106-bit block header, at most 9 bits per filtered byte and for the end-of-block symbol (the
-// coder never exceeds the fixed 8 / 9-bit code, see png_codes_kernel), 3 bits of the empty stored block's header, the pad to the byte and its
-// four LEN / NLEN bytes.
-static size_t png_chunk_bound(size_t rows, size_t rowlen) { return (IR_PNG_HEADER_BITS + 9 * (rows * rowlen + 1) + 3 + 7) / 8 + 4; }
-struct PngLayout {
-    size_t chunks, slot_cap, hist, codes, header, sizes, slots, total;
-};
-static PngLayout png_layout(int n, int vh, int vw) {
-    PngLayout L;
-    L.chunks = ((size_t)vh + IR_PNG_ROWS - 1) / IR_PNG_ROWS;
-    // a slot is stored in whole 16-byte units and the compaction reads one dword beyond the chunk's last
-    L.slot_cap = ((png_chunk_bound(IR_PNG_ROWS, 3 * (size_t)vw + 1) + 15) & ~(size_t)15) + 16;
-    const size_t k = (size_t)n * L.chunks;
-    auto up = [](size_t b) { return (b + 255) & ~(size_t)255; };
-    L.hist = 0;
-    L.codes = L.hist + up(k * 260 * 4);
-    L.header = L.codes + up(k * 260 * 4);
-    L.sizes = L.header + up(k * 40 * 4);
-    L.slots = L.sizes + up(k * 4);
-    L.total = L.slots + up(k * L.slot_cap);
-    return L;
-}
-// 2 header bytes + the chunks + 4 bytes of Adler-32. With D = h * (3 w + 1) filtered bytes in ceil(h / IR_PNG_ROWS) chunks the chunk bounds sum
-// to at most ceil(9 D / 8) + chunks * (ceil((1106 + 9 + 3 + 7) / 8) + 4 + 1) (the + 1: each chunk's own rounding of 9 * bytes / 8).
-size_t ir_png_bound(int h, int w) {
-    if (h < 1 || w < 1) return 0;
-    const size_t rowlen = 3 * (size_t)w + 1, chunks = ((size_t)h + IR_PNG_ROWS - 1) / IR_PNG_ROWS;
-    return 2 + (9 * (size_t)h * rowlen + 7) / 8 + chunks * ((IR_PNG_HEADER_BITS + 9 + 3 + 7 + 7) / 8 + 4 + 1) + 4;
-}
-int ir_png_encode(ir_ctx* c, void* stream, const uint8_t* img, int n, int h, int w, long pitch, int vh, int vw, uint8_t* out, size_t out_stride,
-                  uint32_t* info, void* ws, size_t ws_bytes) {
-    if (!c || !img || !out || !info || !ws) return fail(c, -1, "ir_png_encode: null argument");
-    if (n < 1 || h < 1 || w < 1 || vh < 1 || vh > h || vw < 1 || vw > w || pitch < 3L * w)
-        return fail(c, -1, "ir_png_encode: bad size (n %d, %d x %d, pitch %ld, valid %d x %d)", n, h, w, pitch, vh, vw);
-    if (out_stride < ir_png_bound(vh, vw)) return fail(c, -1, "ir_png_encode: out_stride %zu below ir_png_bound(%d, %d) = %zu", out_stride, vh, vw, ir_png_bound(vh, vw));
-    const PngLayout L = png_layout(n, vh, vw);
-    if (ws_bytes < L.total || (reinterpret_cast<uintptr_t>(ws) & 15)) return fail(c, -1, "ir_png_encode: workspace too small or unaligned (%zu < %zu)", ws_bytes, L.total);
-    use_ctx(c);
-    char* b = static_cast<char*>(ws);
-    if (ir_launch_png_encode(img, n, h, pitch, vh, vw, out, out_stride, info, (uint32_t*)(b + L.hist), (uint32_t*)(b + L.codes), (uint32_t*)(b + L.header),
-                             (uint32_t*)(b + L.sizes), (uint8_t*)(b + L.slots), (long)L.slot_cap, (hipStream_t)stream))
-        return fail(c, -100, "ir_png_encode: launch failed");
-    return 0;
-}
-
-// ---------------------------------------------------------------- Pillow's 8-bit resampling (resample.hip)
-// The tables of Resample.c's precompute_coeffs + normalize_coeffs_8bpc. Plain double arithmetic in Pillow's order of operations (no contraction
-// into fused multiply-adds): the quantised coefficients have to be Pillow's to the last bit.
-#pragma clang fp contract(off)
-static double rs_bicubic(double x) {
-    const double a = -0.5;
-    if (x < 0.0) x = -x;
-    if (x < 1.0) return ((a + 2.0) * x - (a + 3.0)) * x * x + 1;
-    if (x < 2.0) return (((x - 5) * x + 8) * x - 4) * a;
-    return 0.0;
-}
-static double rs_sinc(double x) {
-    if (x == 0.0) return 1.0;
-    x = x * M_PI;
-    return sin(x) / x;
-}
-static double rs_lanczos(double x) { return (-3.0 <= x && x < 3.0) ? rs_sinc(x) * rs_sinc(x / 3) : 0.0; }
-struct RsAxis {
-    double scale, filterscale, support;
-    int ksize;
-};
-static RsAxis rs_axis(int in, int out, int filter) {
-    RsAxis a;
-    a.filterscale = a.scale = (double)(float)in / out;
-    if (a.filterscale < 1.0) a.filterscale = 1.0;
-    a.support = (filter == IR_RESAMPLE_LANCZOS ? 3.0 : 2.0) * a.filterscale;
-    a.ksize = (int)ceil(a.support) * 2 + 1;
-    return a;
-}
-static void rs_tables(int in, int out, int filter, int* bounds, int* kk) {
-    const RsAxis a = rs_axis(in, out, filter);
-    std::vector<double> w(a.ksize);
-    const double ss = 1.0 / a.filterscale;
-    for (int xx = 0; xx < out; ++xx) {
-        const double center = (xx + 0.5) * a.scale;
-        double ww = 0.0;
-        int xmin = (int)(center - a.support + 0.5);
-        if (xmin < 0) xmin = 0;
-        int xmax = (int)(center + a.support + 0.5);
-        if (xmax > in) xmax = in;
-        xmax -= xmin;
-        for (int x = 0; x < xmax; ++x) {
-            const double arg = (x + xmin - center + 0.5) * ss;
-            w[x] = filter == IR_RESAMPLE_LANCZOS ? rs_lanczos(arg) : rs_bicubic(arg);
-            ww += w[x];
-        }
-        int* k = kk + (size_t)xx * a.ksize;
-        for (int x = 0; x < a.ksize; ++x) {
-            double v = x < xmax ? w[x] : 0.0;
-            if (x < xmax && ww != 0.0) v /= ww;
-            k[x] = v < 0 ? (int)(-0.5 + v * (1 << 22)) : (int)(0.5 + v * (1 << 22));
-        }
-        bounds[2 * xx] = xmin;
-        bounds[2 * xx + 1] = xmax;
-    }
-}
-#pragma clang fp contract(fast)
-static bool rs_args_ok(int in_h, int in_w, int out_h, int out_w, int filter) {
-    return in_h >= 1 && in_w >= 1 && out_h >= 1 && out_w >= 1 && (filter == IR_RESAMPLE_BICUBIC || filter == IR_RESAMPLE_LANCZOS);
-}
-// ints of the plan: the header, then per pass that runs 2 bounds + ksize coefficients per output index
-static size_t rs_plan_ints(int in_h, int in_w, int out_h, int out_w, int filter, int* hd) {
-    size_t at = IR_RESAMPLE_HEADER;
-    int h[IR_RESAMPLE_HEADER] = {IR_RESAMPLE_MAGIC, in_h, in_w, out_h, out_w, filter};
-    if (in_w != out_w) {
-        h[6] = rs_axis(in_w, out_w, filter).ksize;
-        h[8] = (int)at; at += 2 * (size_t)out_w;
-        h[9] = (int)at; at += (size_t)out_w * h[6];
-    }
-    if (in_h != out_h) {
-        h[7] = rs_axis(in_h, out_h, filter).ksize;
-        h[10] = (int)at; at += 2 * (size_t)out_h;
-        h[11] = (int)at; at += (size_t)out_h * h[7];
-    }
-    h[12] = (int)at;
-    if (hd) memcpy(hd, h, sizeof h);
-    return at;
-}
-size_t ir_resample_plan_bytes(int in_h, int in_w, int out_h, int out_w, int filter) {
-    if (!rs_args_ok(in_h, in_w, out_h, out_w, filter)) return 0;
-    const size_t ints = rs_plan_ints(in_h, in_w, out_h, out_w, filter, nullptr);
-    return ints > 0x7fffffffu ? 0 : 4 * ints;   // the offsets are ints
-}
-int ir_resample_plan(int in_h, int in_w, int out_h, int out_w, int filter, void* host_plan, size_t bytes) {
-    const size_t need = ir_resample_plan_bytes(in_h, in_w, out_h, out_w, filter);
-    if (!host_plan || !need || bytes < need) return -1;
-    int* p = static_cast<int*>(host_plan);
-    rs_plan_ints(in_h, in_w, out_h, out_w, filter, p);
-    if (in_w != out_w) rs_tables(in_w, out_w, filter, p + p[8], p + p[9]);
-    if (in_h != out_h) rs_tables(in_h, out_h, filter, p + p[10], p + p[11]);
-    return 0;
-}
-static size_t rs_inter_pitch(int out_w) { return (3 * (size_t)out_w + 3) & ~(size_t)3; }
-static size_t rs_workspace(int n, int in_h, int out_w) { return ((size_t)n * in_h * rs_inter_pitch(out_w) + 255) & ~(size_t)255; }
-int ir_resample_u8(ir_ctx* c, void* stream, const uint8_t* in, int n, int in_h, int in_w, long in_pitch, uint8_t* out, int out_h, int out_w, int full_h,
-                   int full_w, long out_pitch, const void* plan_dev, void* ws, size_t ws_bytes) {
-    if (!c || !in || !out || !plan_dev) return fail(c, -1, "ir_resample_u8: null argument");
-    if (n < 1 || in_h < 1 || in_w < 1 || out_h < 1 || out_w < 1 || full_h < out_h || full_w < out_w || in_pitch < 3L * in_w || out_pitch < 3L * full_w)
-        return fail(c, -1, "ir_resample_u8: bad size (n %d, %d x %d pitch %ld -> %d x %d in %d x %d pitch %ld)", n, in_h, in_w, in_pitch, out_h, out_w, full_h,
-                    full_w, out_pitch);
-    const bool both = in_h != out_h && in_w != out_w;
-    if (both && (!ws || ws_bytes < rs_workspace(n, in_h, out_w) || (reinterpret_cast<uintptr_t>(ws) & 3)))
-        return fail(c, -1, "ir_resample_u8: workspace missing, too small or unaligned (%zu < %zu)", ws_bytes, rs_workspace(n, in_h, out_w));
-    if (reinterpret_cast<uintptr_t>(plan_dev) & 3) return fail(c, -1, "ir_resample_u8: plan not aligned to 4 bytes");
-    use_ctx(c);
-    if (ir_launch_resample_u8(in, n, in_h, in_w, in_pitch, out, out_h, out_w, full_h, full_w, out_pitch, static_cast<const int*>(plan_dev),
-                              static_cast<uint8_t*>(ws), (long)rs_inter_pitch(out_w), (hipStream_t)stream))
-        return fail(c, -100, "ir_resample_u8: launch failed (more than 65535 images or rows)");
-    return 0;
-}
-
-// ---------------------------------------------------------------- PSNR-Y / SSIM-Y (metrics.hip)
-// two doubles per tile of the 'valid' SSIM map (at least one tile, so that every size from 1 up has a positive answer)
-static size_t metrics_workspace(int n, int h, int w) {
-    const size_t tx = w > 10 ? ((size_t)w - 10 + IR_METRICS_TW - 1) / IR_METRICS_TW : 1, ty = h > 10 ? ((size_t)h - 10 + IR_METRICS_TH - 1) / IR_METRICS_TH : 1;
-    return ((size_t)n * tx * ty * 2 * sizeof(double) + 255) & ~(size_t)255;
-}
-int ir_metrics_y(ir_ctx* c, void* stream, const uint8_t* a, int a_rows, long a_pitch, const uint8_t* b, int b_rows, long b_pitch, int n, int h, int w,
-                 double* out, void* ws, size_t ws_bytes) {
-    if (!c || !a || !b || !out || !ws) return fail(c, -1, "ir_metrics_y: null argument");
-    if (n < 1 || h < 11 || w < 11 || h > a_rows || h > b_rows || a_pitch < 3L * w || b_pitch < 3L * w)
-        return fail(c, -1, "ir_metrics_y: bad size (n %d, %d x %d in %d rows pitch %ld and %d rows pitch %ld; the window needs 11 x 11)", n, h, w, a_rows, a_pitch,
-                    b_rows, b_pitch);
-    if (ws_bytes < metrics_workspace(n, h, w) || (reinterpret_cast<uintptr_t>(ws) & 7))
-        return fail(c, -1, "ir_metrics_y: workspace too small or unaligned (%zu < %zu)", ws_bytes, metrics_workspace(n, h, w));
-    if (reinterpret_cast<uintptr_t>(out) & 7) return fail(c, -1, "ir_metrics_y: out not aligned to 8 bytes");
-    if (!c->luma_tab) return fail(c, -1, "ir_metrics_y: the context has no luma tables");
-    use_ctx(c);
-    if (ir_launch_metrics_y(a, a_rows, a_pitch, b, b_rows, b_pitch, n, h, w, c->luma_tab, static_cast<double*>(ws), out, (hipStream_t)stream))
-        return fail(c, -100, "ir_metrics_y: launch failed (more than 65535 images or tile rows)");
-    return 0;
-}
-
-// ---------------------------------------------------------------- LPIPS (lpips.hip)
-int ir_lpips_scale_table(float* tab) {
-    if (!tab) return -1;
-    static const float shift[3] = {-.030f, -.088f, -.188f}, scale[3] = {.458f, .448f, .450f};
-    for (int ch = 0; ch < 3; ++ch)
-        for (int v = 0; v < 256; ++v) {   // every step rounded to fp32, in the model's order
-            volatile float x = (float)v / 255.0f;
-            volatile float y = 2.0f * x;
-            volatile float z = y - 1.0f;
-            volatile float u = z - shift[ch];
-            tab[256 * ch + v] = u / scale[ch];
-        }
-    return 0;
-}
-
-int ir_lpips_configure(ir_ctx* c) {
-    if (!c) return -1;
-    static const int shape[5][3] = {{3, 64, 11}, {64, 192, 5}, {192, 384, 3}, {384, 256, 3}, {256, 256, 3}};   // cin, cout, k
-    HIPOK(c, hipSetDevice(c->device));
-    c->lpips.ok = false;
-    ir_ctx::Lpips m;
-    const void* src[5];
-    for (int k = 0; k < 5; ++k) {
-        const int cin = shape[k][0], cout = shape[k][1], ks = shape[k][2];
-        const std::string names[3] = {fmt("lpips.c%d.w", k + 1), fmt("lpips.c%d.b", k + 1), fmt("lpips.lin%d", k + 1)};
-        const size_t want[3] = {(size_t)cout * cin * ks * ks * 4, (size_t)cout * 4, (size_t)cout * 4};
-        const void* got[3];
-        for (int i = 0; i < 3; ++i) {
-            auto it = c->t.find(names[i]);
-            if (it == c->t.end()) return fail(c, -2, "ir_lpips_configure: tensor %s (missing)", names[i].c_str());
-            if (it->second.bytes != want[i])
-                return fail(c, -2, "ir_lpips_configure: tensor %s has %zu bytes, AlexNet's has %zu", names[i].c_str(), it->second.bytes, want[i]);
-            got[i] = it->second.p;
-        }
-        src[k] = got[0];
-        m.b[k] = static_cast<const float*>(got[1]);
-        m.lin[k] = static_cast<const float*>(got[2]);
-    }
-    release_list(c->lpips_owned);
-    HIPOK(c, hipDeviceSynchronize());
-    float tab[3 * 256];
-    ir_lpips_scale_table(tab);
-    void* d = nullptr;
-    if (dev_alloc(c, c->lpips_owned, &d, sizeof tab)) return -100;
-    HIPOK(c, hipMemcpy(d, tab, sizeof tab, hipMemcpyHostToDevice));
-    m.tab = static_cast<const float*>(d);
-    for (int k = 0; k < 5; ++k) {   // [cout][cin][ky][kx] -> [(ky, kx, c) padded to 32][cout], zero rows behind K
-        const int cin = shape[k][0], cout = shape[k][1], ks = shape[k][2];
-        const int K = ks * ks * cin, Kp = pad32(K);
-        std::vector<float> w((size_t)cout * K), t((size_t)Kp * cout, 0.f);
-        HIPOK(c, hipMemcpy(w.data(), src[k], w.size() * 4, hipMemcpyDeviceToHost));
-        for (int o = 0; o < cout; ++o)
-            for (int ci = 0; ci < cin; ++ci)
-                for (int ky = 0; ky < ks; ++ky)
-                    for (int kx = 0; kx < ks; ++kx)
-                        t[(size_t)((ky * ks + kx) * cin + ci) * cout + o] = w[(((size_t)o * cin + ci) * ks + ky) * ks + kx];
-        if (dev_alloc(c, c->lpips_owned, &d, t.size() * 4)) return -100;
-        HIPOK(c, hipMemcpy(d, t.data(), t.size() * 4, hipMemcpyHostToDevice));
-        m.w[k] = static_cast<const float*>(d);
-        // copies of the bias and the lin head: the binding does not depend on later uploads under these names
-        for (const float** q : {&m.b[k], &m.lin[k]}) {
-            if (dev_alloc(c, c->lpips_owned, &d, (size_t)cout * 4)) return -100;
-            HIPOK(c, hipMemcpy(d, *q, (size_t)cout * 4, hipMemcpyDeviceToDevice));
-            *q = static_cast<const float*>(d);
-        }
-    }
-    m.ok = true;
-    c->lpips = m;
-    ++c->generation;
-    return 0;
-}
-
-int ir_lpips(ir_ctx* c, void* stream, const uint8_t* a, int a_rows, long a_pitch, const uint8_t* b, int b_rows, long b_pitch, int n, int h, int w,
-             double* out, void* ws, size_t ws_bytes) {
-    if (!c || !a || !b || !out || !ws) return fail(c, -1, "ir_lpips: null argument");
-    if (n < 1 || h < 31 || w < 31 || h > a_rows || h > b_rows || a_pitch < 3L * w || b_pitch < 3L * w)
-        return fail(c, -1, "ir_lpips: bad size (n %d, %d x %d in %d rows pitch %ld and %d rows pitch %ld; AlexNet's five stages need 31 x 31)", n, h, w, a_rows,
-                    a_pitch, b_rows, b_pitch);
-    IrLpipsPlan pl;
-    if (ir_lpips_plan(n, h, w, &pl)) return fail(c, -1, "ir_lpips: n %d of %d x %d is more than one call takes (2^31 output pixels, 65535 pairs)", n, h, w);
-    if (ws_bytes < pl.total || (reinterpret_cast<uintptr_t>(ws) & 255)) return fail(c, -1, "ir_lpips: workspace too small or unaligned (%zu < %zu)", ws_bytes, pl.total);
-    if (reinterpret_cast<uintptr_t>(out) & 7) return fail(c, -1, "ir_lpips: out not aligned to 8 bytes");
-    if (!c->lpips.ok) return fail(c, -12, "ir_lpips: LPIPS not configured (ir_lpips_configure)");
-    use_ctx(c);
-    if (ir_launch_lpips(a, a_rows, a_pitch, b, b_rows, b_pitch, n, h, w, c->lpips.tab, c->lpips.w, c->lpips.b, c->lpips.lin, ws, out, (hipStream_t)stream))
-        return fail(c, -100, "ir_lpips: launch failed");
-    return 0;
-}
-
-// ---------------------------------------------------------------- CLIP-IQA (clipiqa.hip)
-int ir_clipiqa_scale_table(float* tab) {
-    if (!tab) return -1;
-    static const float mean[3] = {0.48145466f, 0.4578275f, 0.40821073f}, std3[3] = {0.26862954f, 0.26130258f, 0.27577711f};
-    for (int ch = 0; ch < 3; ++ch)
-        for (int v = 0; v < 256; ++v) {   // every step rounded to fp32, in the model's order
-            volatile float x = (float)v / 255.0f;
-            volatile float y = x - mean[ch];
-            tab[256 * ch + v] = y / std3[ch];
-        }
-    return 0;
-}
-
-namespace {
-// the tensor `name` of the context with exactly `floats` fp32 values, or null with ir_last_error naming it
-const float* clipiqa_tensor(ir_ctx* c, const std::string& name, size_t floats) {
-    auto it = c->t.find(name);
-    if (it == c->t.end()) {
-        fail(c, -2, "ir_clipiqa_configure: tensor %s (missing)", name.c_str());
-        return nullptr;
-    }
-    if (it->second.bytes != floats * 4) {
-        fail(c, -2, "ir_clipiqa_configure: tensor %s has %zu bytes, the configured model's has %zu", name.c_str(), it->second.bytes, floats * 4);
-        return nullptr;
-    }
-    return static_cast<const float*>(it->second.p);
-}
-int clipiqa_to_device(ir_ctx* c, const void* host, size_t bytes, const float** out) {
-    void* d = nullptr;
-    if (dev_alloc(c, c->clipiqa_owned, &d, bytes)) return -100;
-    HIPOK(c, hipMemcpy(d, host, bytes, hipMemcpyHostToDevice));
-    *out = static_cast<const float*>(d);
-    return 0;
-}
-int clipiqa_copy(ir_ctx* c, const float* dev, size_t floats, const float** out) {
-    void* d = nullptr;
-    if (dev_alloc(c, c->clipiqa_owned, &d, floats * 4)) return -100;
-    HIPOK(c, hipMemcpy(d, dev, floats * 4, hipMemcpyDeviceToDevice));
-    *out = static_cast<const float*>(d);
-    return 0;
-}
-struct ClipConvSrc { std::string conv, bn; int cin, cout, ks; IrClipConv* dst; };
-}  // namespace
-
-int ir_clipiqa_configure(ir_ctx* c, const int* layers, int width, int heads, int out_dim, int n_pairs, float logit_scale_exp) {
-    if (!c || !layers) return fail(c, -1, "ir_clipiqa_configure: null argument");
-    int n_blocks = 0;
-    for (int l = 0; l < 4; ++l) {
-        if (layers[l] < 1) return fail(c, -1, "ir_clipiqa_configure: layer %d has %d blocks", l + 1, layers[l]);
-        n_blocks += layers[l];
-    }
-    if (n_blocks > IR_CLIPIQA_MAX_BLOCKS) return fail(c, -1, "ir_clipiqa_configure: %d blocks, at most %d", n_blocks, IR_CLIPIQA_MAX_BLOCKS);
-    if (width < 64 || width % 64 || heads < 1 || (width * 32) % heads || out_dim < 1 || n_pairs < 1 || n_pairs > 64 || !(logit_scale_exp > 0.f))
-        return fail(c, -1, "ir_clipiqa_configure: unsupported model (width %d must be a multiple of 64, heads %d must divide %d, out_dim %d, %d pairs)", width,
-                    heads, width * 32, out_dim, n_pairs);
-    HIPOK(c, hipSetDevice(c->device));
-    c->clipiqa.ok = false;
-    auto m = std::make_unique<IrClipiqaModel>();
-    for (int l = 0; l < 4; ++l) m->layers[l] = layers[l];
-    m->width = width; m->heads = heads; m->out_dim = out_dim; m->n_pairs = n_pairs; m->n_blocks = n_blocks; m->logit_scale = (double)logit_scale_exp;
-    std::vector<ClipConvSrc> convs;
-    convs.push_back({"clipiqa.conv1", "clipiqa.bn1", 3, width / 2, 3, &m->stem[0]});
-    convs.push_back({"clipiqa.conv2", "clipiqa.bn2", width / 2, width / 2, 3, &m->stem[1]});
-    convs.push_back({"clipiqa.conv3", "clipiqa.bn3", width / 2, width, 3, &m->stem[2]});
-    int inplanes = width, bi = 0;
-    for (int l = 0; l < 4; ++l) {
-        const int planes = width << l;
-        for (int i = 0; i < layers[l]; ++i, ++bi) {
-            IrClipBlock& b = m->blocks[bi];
-            b.stride = (i == 0 && l > 0) ? 2 : 1;
-            b.has_down = b.stride == 2 || inplanes != planes * 4;
-            const std::string base = fmt("clipiqa.layer%d.%d.", l + 1, i);
-            convs.push_back({base + "conv1", base + "bn1", inplanes, planes, 1, &b.c1});
-            convs.push_back({base + "conv2", base + "bn2", planes, planes, 3, &b.c2});
-            convs.push_back({base + "conv3", base + "bn3", planes, planes * 4, 1, &b.c3});
-            if (b.has_down) convs.push_back({base + "downsample.0", base + "downsample.1", inplanes, planes * 4, 1, &b.down});
-            inplanes = planes * 4;
-        }
-    }
-    const int C = width * 32;
-    // every tensor is looked up before anything is replaced
-    struct Lin { const char* name; int rows, cols; const float **w, **b; };
-    const Lin lins[4] = {{"q_proj", C, C, &m->qw, &m->qb}, {"k_proj", C, C, &m->kw, &m->kb}, {"v_proj", C, C, &m->vw, &m->vb}, {"c_proj", out_dim, C, &m->cw, &m->cb}};
-    for (const ClipConvSrc& s : convs) {
-        if (!clipiqa_tensor(c, s.conv + ".weight", (size_t)s.cout * s.cin * s.ks * s.ks)) return -2;
-        for (const char* v : {".weight", ".bias", ".running_mean", ".running_var"})
-            if (!clipiqa_tensor(c, s.bn + v, (size_t)s.cout)) return -2;
-    }
-    for (const Lin& l : lins)
-        if (!clipiqa_tensor(c, fmt("clipiqa.attnpool.%s.weight", l.name), (size_t)l.rows * l.cols) || !clipiqa_tensor(c, fmt("clipiqa.attnpool.%s.bias", l.name), (size_t)l.rows))
-            return -2;
-    if (!clipiqa_tensor(c, "clipiqa.text", (size_t)2 * n_pairs * out_dim)) return -2;
-
-    release_list(c->clipiqa_owned);
-    HIPOK(c, hipDeviceSynchronize());
-    float tab[3 * 256];
-    ir_clipiqa_scale_table(tab);
-    if (int e = clipiqa_to_device(c, tab, sizeof tab, &m->tab)) return e;
-    for (const ClipConvSrc& s : convs) {   // [cout][cin][ky][kx] -> [(ky, kx, c) padded to 32][cout], zero rows behind K; BatchNorm folded in fp64
-        const int K = s.ks * s.ks * s.cin, Kp = pad32(K);
-        std::vector<float> w((size_t)s.cout * K), t((size_t)Kp * s.cout, 0.f), bn[4], sc(s.cout), sh(s.cout);
-        HIPOK(c, hipMemcpy(w.data(), clipiqa_tensor(c, s.conv + ".weight", w.size()), w.size() * 4, hipMemcpyDeviceToHost));
-        for (int o = 0; o < s.cout; ++o)
-            for (int ci = 0; ci < s.cin; ++ci)
-                for (int ky = 0; ky < s.ks; ++ky)
-                    for (int kx = 0; kx < s.ks; ++kx)
-                        t[(size_t)((ky * s.ks + kx) * s.cin + ci) * s.cout + o] = w[(((size_t)o * s.cin + ci) * s.ks + ky) * s.ks + kx];
-        int k = 0;
-        for (const char* v : {".weight", ".bias", ".running_mean", ".running_var"}) {
-            bn[k].resize(s.cout);
-            HIPOK(c, hipMemcpy(bn[k].data(), clipiqa_tensor(c, s.bn + v, (size_t)s.cout), (size_t)s.cout * 4, hipMemcpyDeviceToHost));
-            ++k;
-        }
-        for (int o = 0; o < s.cout; ++o) {   // scale = g / sqrt(var + eps), shift = b - mean scale, each rounded to fp32 once
-            const double scale = (double)bn[0][o] / sqrt((double)bn[3][o] + 1e-5);
-            sc[o] = (float)scale;
-            sh[o] = (float)((double)bn[1][o] - (double)bn[2][o] * scale);
-        }
-        s.dst->cin = s.cin; s.dst->cout = s.cout; s.dst->ks = s.ks;
-        if (int e = clipiqa_to_device(c, t.data(), t.size() * 4, &s.dst->w)) return e;
-        if (int e = clipiqa_to_device(c, sc.data(), sc.size() * 4, &s.dst->scale)) return e;
-        if (int e = clipiqa_to_device(c, sh.data(), sh.size() * 4, &s.dst->shift)) return e;
-    }
-    // copies of the linears and the text rows: the binding does not depend on later uploads under these names
-    for (const Lin& l : lins) {
-        if (int e = clipiqa_copy(c, clipiqa_tensor(c, fmt("clipiqa.attnpool.%s.weight", l.name), (size_t)l.rows * l.cols), (size_t)l.rows * l.cols, l.w)) return e;
-        if (int e = clipiqa_copy(c, clipiqa_tensor(c, fmt("clipiqa.attnpool.%s.bias", l.name), (size_t)l.rows), (size_t)l.rows, l.b)) return e;
-    }
-    if (int e = clipiqa_copy(c, clipiqa_tensor(c, "clipiqa.text", (size_t)2 * n_pairs * out_dim), (size_t)2 * n_pairs * out_dim, &m->text)) return e;
-    m->ok = true;
-    c->clipiqa = *m;
-    ++c->generation;
-    return 0;
-}
-
-int ir_clipiqa(ir_ctx* c, void* stream, const uint8_t* img, int rows, long pitch, int n, int h, int w, double* scores, float* feat, void* ws, size_t ws_bytes) {
-    if (!c || !img || !scores || !ws) return fail(c, -1, "ir_clipiqa: null argument");
-    if (n < 1 || h < 32 || w < 32 || h > rows || pitch < 3L * w)
-        return fail(c, -1, "ir_clipiqa: bad size (n %d, %d x %d in %d rows pitch %ld; the tower's last map needs 32 x 32)", n, h, w, rows, pitch);
-    if (!c->clipiqa.ok) return fail(c, -13, "ir_clipiqa: CLIP-IQA not configured (ir_clipiqa_configure)");
-    IrClipiqaPlan pl;
-    if (ir_clipiqa_plan(c->clipiqa, n, h, w, &pl)) return fail(c, -1, "ir_clipiqa: n %d of %d x %d is more than one call takes (2^31 output pixels, 65535 images)", n, h, w);
-    if (ws_bytes < pl.total || (reinterpret_cast<uintptr_t>(ws) & 255)) return fail(c, -1, "ir_clipiqa: workspace too small or unaligned (%zu < %zu)", ws_bytes, pl.total);
-    if ((reinterpret_cast<uintptr_t>(scores) & 7) || (reinterpret_cast<uintptr_t>(feat) & 3)) return fail(c, -1, "ir_clipiqa: scores / feat not aligned");
-    use_ctx(c);
-    if (ir_launch_clipiqa(c->clipiqa, img, rows, pitch, n, h, w, scores, feat, ws, (hipStream_t)stream)) return fail(c, -100, "ir_clipiqa: launch failed");
-    return 0;
-}
-
-// ---------------------------------------------------------------- NIQE's block statistics (niqe.hip)
-// the half-size fp64 luma plane of every image's scored rectangle
-static size_t niqe_workspace(int n, int h, int w) {
-    const size_t H2 = (size_t)(h / IR_NIQE_BLOCK) * (IR_NIQE_BLOCK / 2), W2 = (size_t)(w / IR_NIQE_BLOCK) * (IR_NIQE_BLOCK / 2);
-    return ((size_t)n * H2 * W2 * sizeof(double) + 255) & ~(size_t)255;
-}
-int ir_niqe_window(double* k49) {
-    if (!k49) return -1;
-    ir_niqe_window_host(k49);
-    return 0;
-}
-int ir_niqe_stats(ir_ctx* c, void* stream, const uint8_t* img, int rows, long pitch, int n, int h, int w, double* out, void* ws, size_t ws_bytes) {
-    if (!c || !img || !out || !ws) return fail(c, -1, "ir_niqe_stats: null argument");
-    if (n < 1 || h < IR_NIQE_BLOCK || w < IR_NIQE_BLOCK || h > rows || pitch < 3L * w)
-        return fail(c, -1, "ir_niqe_stats: bad size (n %d, %d x %d in %d rows pitch %ld; a block is 96 x 96)", n, h, w, rows, pitch);
-    if (ws_bytes < niqe_workspace(n, h, w) || (reinterpret_cast<uintptr_t>(ws) & 7))
-        return fail(c, -1, "ir_niqe_stats: workspace too small or unaligned (%zu < %zu)", ws_bytes, niqe_workspace(n, h, w));
-    if (reinterpret_cast<uintptr_t>(out) & 7) return fail(c, -1, "ir_niqe_stats: out not aligned to 8 bytes");
-    if (!c->niqe_tab) return fail(c, -1, "ir_niqe_stats: the context has no luma tables");
-    use_ctx(c);
-    if (ir_launch_niqe_stats(img, rows, pitch, n, h, w, c->niqe_tab, static_cast<double*>(ws), out, (hipStream_t)stream))
-        return fail(c, -100, "ir_niqe_stats: launch failed (more than 65535 images or block rows)");
-    return 0;
-}
-
-// ---------------------------------------------------------------- low-quality inputs from ground truth (degrade.hip)
-int ir_degrade_qtables(int q, uint16_t* luma64, uint16_t* chroma64) {
-    if (!luma64 || !chroma64 || q < 1 || q > 100) return -1;
-    ir_degrade_qtables_host(q, luma64, chroma64);
-    return 0;
-}
-int ir_degrade(ir_ctx* c, void* stream, const uint8_t* img, int rows, long pitch, int n, int h, int w, const ir_degrade_params* params, uint8_t* out,
-               uint8_t* jpeg_or_null, void* ws, size_t ws_bytes) {
-    if (!c || !img || !params || !out || !ws) return fail(c, -1, "ir_degrade: null argument");
-    if (n < 1 || h < 1 || w < 1 || h > rows || pitch < 3L * w || (long)h * w > (1L << 28))
-        return fail(c, -1, "ir_degrade: bad size (n %d, %d x %d in %d rows pitch %ld)", n, h, w, rows, pitch);
-    for (int i = 0; i < n; ++i) {   // every image is checked before the first launch
-        const ir_degrade_params& p = params[i];
-        if (!p.kernel) return fail(c, -1, "ir_degrade: image %d has no blur kernel", i);
-        if (p.ksize < 1 || p.ksize > IR_DEGRADE_MAX_KSIZE || !(p.ksize & 1))
-            return fail(c, -1, "ir_degrade: image %d: the blur kernel size %d is not odd and within 1 .. %d", i, p.ksize, IR_DEGRADE_MAX_KSIZE);
-        if (h < p.ksize / 2 + 1 || w < p.ksize / 2 + 1)
-            return fail(c, -1, "ir_degrade: a %d x %d image is too small for a %d x %d blur (reflection needs %d pixels)", h, w, p.ksize, p.ksize, p.ksize / 2 + 1);
-        if (p.lh < IR_DEGRADE_MIN_LOW || p.lw < IR_DEGRADE_MIN_LOW || p.lh > h || p.lw > w)
-            return fail(c, -1, "ir_degrade: image %d: low-resolution size %d x %d outside %d .. %d x %d", i, p.lh, p.lw, IR_DEGRADE_MIN_LOW, h, w);
-        if (p.q < 0 || p.q > 100) return fail(c, -1, "ir_degrade: image %d: JPEG quality %d outside 0 .. 100", i, p.q);
-        if (p.norm != IR_DEGRADE_NORM_NONE && p.norm != IR_DEGRADE_NORM_MAX) return fail(c, -1, "ir_degrade: image %d: unknown norm %d", i, p.norm);
-        if ((reinterpret_cast<uintptr_t>(p.kernel) & 7) || (reinterpret_cast<uintptr_t>(p.noise) & 3))
-            return fail(c, -1, "ir_degrade: image %d: misaligned kernel or noise pointer", i);
-    }
-    if (ws_bytes < ir_degrade_workspace(h, w) || (reinterpret_cast<uintptr_t>(ws) & 255))
-        return fail(c, -1, "ir_degrade: workspace too small or unaligned (%zu < %zu)", ws_bytes, ir_degrade_workspace(h, w));
-    use_ctx(c);
-    for (int i = 0; i < n; ++i) {
-        const ir_degrade_params& p = params[i];
-        if (ir_launch_degrade(img + (long)i * rows * pitch, pitch, h, w, p.kernel, p.ksize, p.lh, p.lw, p.sigma, p.q, p.noise, p.norm,
-                              out + (long)i * rows * pitch, pitch, jpeg_or_null ? jpeg_or_null + (long)i * h * w * 3 : nullptr, ws, (hipStream_t)stream))
-            return fail(c, -100, "ir_degrade: launch failed (image %d)", i);
-    }
-    return 0;
-}
-
-// ---------------------------------------------------------------- the second-order degradation chain (degrade_chain.hip)
-static long chain_tap_floats(const ir_chain& ch, int h, int w) {   // the size of the image behind op `tap`
-    if (ch.tap < 0) return 0;
-    for (int i = 0; i <= ch.tap; ++i)
-        if (ch.ops[i].kind == IR_CHAIN_RESIZE) h = ch.ops[i].b, w = ch.ops[i].c;
-    return (long)h * w * 3;
-}
-int ir_degrade_chain(ir_ctx* c, void* stream, const uint8_t* img, int rows, long pitch, int n, int h, int w, const ir_chain* chains, uint8_t* out,
-                     float* tap_or_null, void* ws, size_t ws_bytes) {
-    if (!c || !img || !chains || !out || !ws) return fail(c, -1, "ir_degrade_chain: null argument");
-    if (n < 1 || h < 1 || w < 1 || h > rows || pitch < 3L * w || h > IR_CHAIN_MAX_SIDE || w > IR_CHAIN_MAX_SIDE)
-        return fail(c, -1, "ir_degrade_chain: bad size (n %d, %d x %d in %d rows pitch %ld)", n, h, w, rows, pitch);
-    int mh = h, mw = w;
-    for (int i = 0; i < n; ++i) {   // every chain is checked before the first launch
-        int ih, iw;
-        const char* why;
-        if (ir_degrade_chain_check(&chains[i], h, w, &ih, &iw, &why)) return fail(c, -1, "ir_degrade_chain: image %d (%d x %d): %s", i, h, w, why);
-        mh = std::max(mh, ih), mw = std::max(mw, iw);
-    }
-    const size_t need = ir_degrade_chain_workspace(h, w, mh, mw);
-    if (ws_bytes < need || (reinterpret_cast<uintptr_t>(ws) & 255))
-        return fail(c, -1, "ir_degrade_chain: workspace too small or unaligned (%zu < %zu)", ws_bytes, need);
-    if (tap_or_null && (reinterpret_cast<uintptr_t>(tap_or_null) & 3)) return fail(c, -1, "ir_degrade_chain: misaligned tap pointer");
-    use_ctx(c);
-    for (int i = 0; i < n; ++i) {
-        if (ir_launch_degrade_chain(img + (long)i * rows * pitch, pitch, h, w, &chains[i], mh, mw, out + (long)i * rows * pitch, pitch, tap_or_null, ws,
-                                    (hipStream_t)stream))
-            return fail(c, -100, "ir_degrade_chain: launch failed (image %d)", i);
-        if (tap_or_null) tap_or_null += chain_tap_floats(chains[i], h, w);
-    }
-    return 0;
-}
-
 size_t ir_workspace_bytes(ir_ctx* c, int stage, int n, int h, int w, int flags, int tile_size, int tile_stride) {
-    if (stage == IR_STAGE_DEGRADE_CHAIN) return n < 1 ? 0 : ir_degrade_chain_workspace(h, w, flags, tile_size);   // a function of the sizes alone: no context needed
-    if (stage == IR_STAGE_DEGRADE) return n < 1 ? 0 : ir_degrade_workspace(h, w);   // a function of the image size alone (the images of a batch share it): no context needed
-    if (stage == IR_STAGE_NIQE) return (n < 1 || h < IR_NIQE_BLOCK || w < IR_NIQE_BLOCK) ? 0 : niqe_workspace(n, h, w);   // a function of the sizes alone: no context needed
-    if (stage == IR_STAGE_CLIPIQA) {   // a function of the sizes and of the configured layer counts
-        IrClipiqaPlan pl;
-        return (!c || !c->clipiqa.ok || ir_clipiqa_plan(c->clipiqa, n, h, w, &pl)) ? 0 : pl.total;
-    }
-    if (stage == IR_STAGE_LPIPS) {   // a function of the sizes alone: no context needed
-        IrLpipsPlan pl;
-        return ir_lpips_plan(n, h, w, &pl) ? 0 : pl.total;
-    }
-    if (stage == IR_STAGE_METRICS) return (n < 1 || h < 1 || w < 1) ? 0 : metrics_workspace(n, h, w);   // a function of the sizes alone: no context needed
-    if (stage == IR_STAGE_PNG) return (n < 1 || h < 1 || w < 1) ? 0 : png_layout(n, h, w).total;   // a function of the sizes alone: no context needed
-    if (stage == IR_STAGE_RESAMPLE) return (n < 1 || h < 1 || w < 1) ? 0 : rs_workspace(n, h, w);    // n images, h = in_h, w = out_w: the uint8 image between the passes
+    size_t image_bytes;
+    if (image_workspace(c, stage, n, h, w, flags, tile_size, &image_bytes)) return image_bytes;
     if (!c) return 0;
     Run r = make_run(c, nullptr, nullptr, 0, true);
     if (stage_dispatch(c, r, stage, n, h, w, flags, tile_size, tile_stride)) return 0;
@@ -3428,7 +2563,7 @@ int ir_tiled_encode_part(ir_ctx* c, void* stream, const uint8_t* in, uint8_t* st
         HIPOK(c, hipSetDevice(c->device));
         void* q = nullptr;
         HIPOK(c, hipMalloc(&q, 256));
-        c->owned.push_back(q);
+        c->own[OWN_CTX].push_back(q);
         c->shard_flag = (int*)q;
     }
     struct NoFp8 {   // the sharded form runs the bf16 attention (the fp8 kernel has no row-shard entry)
@@ -3527,7 +2662,7 @@ int ir_attn_fallback_count(ir_ctx* c, void* stream, int op) {
     HIPOK(c, hipSetDevice(c->device));
     hipStream_t s = (hipStream_t)stream;
     if (op == 1) {
-        if (!c->attn_fb && dev_alloc(c, c->owned, (void**)&c->attn_fb, 256)) return -100;
+        if (!c->attn_fb && dev_alloc(c, c->own[OWN_CTX], (void**)&c->attn_fb, 256)) return -100;
         HIPOK(c, hipMemsetAsync(c->attn_fb, 0, 256, s));
         if (!c->count_fb) ++c->generation;   // recorded hipGraphs do not hold the counting launches
         c->count_fb = true;
@@ -3603,8 +2738,8 @@ int ir_t5_configure(ir_ctx* c, int n_layers, int d_model, int heads, int d_kv, i
         m.layers.push_back(L);
     }
     if (!b.ok) return fail(c, -2, "ir_t5_configure: tensor %s", b.missing.c_str());
-    release_list(c->t5_owned);
-    if (dev_alloc(c, c->t5_owned, (void**)&m.bad, 256)) return -100;
+    release_list(c->own[OWN_T5]);
+    if (dev_alloc(c, c->own[OWN_T5], (void**)&m.bad, 256)) return -100;
     HIPOK(c, hipMemset(m.bad, 0, 4));
     m.ok = true;
     c->t5 = m;
@@ -3681,8 +2816,8 @@ int ir_clip_text_configure(ir_ctx* c, int n_layers, int width, int heads, int d_
         m.layers.push_back(L);
     }
     if (!b.ok) return fail(c, -2, "ir_clip_text_configure: tensor %s", b.missing.c_str());
-    release_list(c->clip_owned);
-    if (dev_alloc(c, c->clip_owned, (void**)&m.bad, 256)) return -100;
+    release_list(c->own[OWN_CLIP]);
+    if (dev_alloc(c, c->own[OWN_CLIP], (void**)&m.bad, 256)) return -100;
     HIPOK(c, hipMemset(m.bad, 0, 4));
     m.ok = true;
     c->clip = m;

@@ -1,0 +1,577 @@
+// The image tools of the C ABI: PNG encoding, Pillow's resampling, PSNR-Y / SSIM-Y, LPIPS, CLIP-IQA, NIQE and the two degradation paths. Each entry
+// point checks its arguments and launches the kernels of its own .hip file; none of them runs a model stage, takes the workspace arena or is
+// profiled, so nothing here knows api.cpp's Run. Host code only, except for the tables the kernels read, which are computed here once.
+#include <math.h>
+#include <string.h>
+
+#include <algorithm>
+#include <initializer_list>
+#include <memory>
+
+#include "host.h"
+
+using namespace ir_host;
+
+namespace {
+
+// ---------------------------------------------------------------- the argument checks the entry points share
+// Each returns 0, or -1 with ir_last_error in the words of the entry point `who`. An entry point calls them in its own order.
+struct Plane {   // an operand: the rows of each image's slot and the bytes from row to row
+    int rows;
+    long pitch;
+};
+// n images of h x w, no edge below min_edge, inside every operand. `tail` says what the minimum is for (null: nothing to say); `also_bad` is the
+// entry point's own limit on the same sizes.
+int check_rect(ir_ctx* c, const char* who, const char* tail, int n, int h, int w, int min_edge, std::initializer_list<Plane> planes, bool also_bad = false) {
+    bool bad = also_bad || n < 1 || h < min_edge || w < min_edge;
+    for (const Plane& p : planes) bad |= h > p.rows || p.pitch < 3L * w;
+    if (!bad) return 0;
+    std::string in;
+    for (const Plane& p : planes) in += fmt("%s%d rows pitch %ld", in.empty() ? "" : " and ", p.rows, p.pitch);
+    return fail(c, -1, "%s: bad size (n %d, %d x %d in %s%s%s)", who, n, h, w, in.c_str(), tail ? "; " : "", tail ? tail : "");
+}
+int check_ws(ir_ctx* c, const char* who, const void* ws, size_t ws_bytes, size_t need, uintptr_t align) {
+    if (!ws || ws_bytes < need || (reinterpret_cast<uintptr_t>(ws) & (align - 1)))
+        return fail(c, -1, "%s: workspace too small or unaligned (%zu < %zu)", who, ws_bytes, need);
+    return 0;
+}
+int check_out8(ir_ctx* c, const char* who, const void* out) {
+    if (reinterpret_cast<uintptr_t>(out) & 7) return fail(c, -1, "%s: out not aligned to 8 bytes", who);
+    return 0;
+}
+
+// ---------------------------------------------------------------- what the LPIPS and CLIP-IQA bindings share
+// the tensor `name` of the context with exactly `floats` fp32 values, or null (the caller returns -2) with ir_last_error naming it and `whose` size it misses
+const float* exact_f32(ir_ctx* c, const char* who, const char* whose, const std::string& name, size_t floats) {
+    auto it = c->t.find(name);
+    if (it == c->t.end()) {
+        fail(c, -2, "%s: tensor %s (missing)", who, name.c_str());
+        return nullptr;
+    }
+    if (it->second.bytes != floats * 4) {
+        fail(c, -2, "%s: tensor %s has %zu bytes, %s has %zu", who, name.c_str(), it->second.bytes, whose, floats * 4);
+        return nullptr;
+    }
+    return static_cast<const float*>(it->second.p);
+}
+// a conv's device weights [cout][cin][ky][kx] as the host array [(ky, kx, c) padded to 32][cout], zero rows behind K
+int repacked_conv(ir_ctx* c, const float* dev_w, int cin, int cout, int ks, std::vector<float>& t) {
+    const int K = ks * ks * cin;
+    std::vector<float> w((size_t)cout * K);
+    HIPOK(c, hipMemcpy(w.data(), dev_w, w.size() * 4, hipMemcpyDeviceToHost));
+    t.assign((size_t)pad32(K) * cout, 0.f);
+    for (int o = 0; o < cout; ++o)
+        for (int ci = 0; ci < cin; ++ci)
+            for (int ky = 0; ky < ks; ++ky)
+                for (int kx = 0; kx < ks; ++kx)
+                    t[(size_t)((ky * ks + kx) * cin + ci) * cout + o] = w[(((size_t)o * cin + ci) * ks + ky) * ks + kx];
+    return 0;
+}
+// *out = a copy of `bytes` host or device bytes that `list`, a binding's list of ir_ctx::own, owns
+int own_copy(ir_ctx* c, std::vector<void*>& list, const void* src, size_t bytes, hipMemcpyKind kind, const float** out) {
+    void* d = nullptr;
+    if (dev_alloc(c, list, &d, bytes)) return -100;
+    HIPOK(c, hipMemcpy(d, src, bytes, kind));
+    *out = static_cast<const float*>(d);
+    return 0;
+}
+
+}  // namespace
+
+extern "C" {
+
+// ---------------------------------------------------------------- PNG encoding (png_encode.hip)
+// Bytes of one chunk of `rows` rows at most: the 1106-bit block header, at most 9 bits per filtered byte and for the end-of-block symbol (the
+// coder never exceeds the fixed 8 / 9-bit code, see png_codes_kernel), 3 bits of the empty stored block's header, the pad to the byte and its
+// four LEN / NLEN bytes.
+static size_t png_chunk_bound(size_t rows, size_t rowlen) { return (IR_PNG_HEADER_BITS + 9 * (rows * rowlen + 1) + 3 + 7) / 8 + 4; }
+struct PngLayout {
+    size_t chunks, slot_cap, hist, codes, header, sizes, slots, total;
+};
+static PngLayout png_layout(int n, int vh, int vw) {
+    PngLayout L;
+    L.chunks = ((size_t)vh + IR_PNG_ROWS - 1) / IR_PNG_ROWS;
+    // a slot is stored in whole 16-byte units and the compaction reads one dword beyond the chunk's last
+    L.slot_cap = ((png_chunk_bound(IR_PNG_ROWS, 3 * (size_t)vw + 1) + 15) & ~(size_t)15) + 16;
+    const size_t k = (size_t)n * L.chunks;
+    auto up = [](size_t b) { return (b + 255) & ~(size_t)255; };
+    L.hist = 0;
+    L.codes = L.hist + up(k * 260 * 4);
+    L.header = L.codes + up(k * 260 * 4);
+    L.sizes = L.header + up(k * 40 * 4);
+    L.slots = L.sizes + up(k * 4);
+    L.total = L.slots + up(k * L.slot_cap);
+    return L;
+}
+// 2 header bytes + the chunks + 4 bytes of Adler-32. With D = h * (3 w + 1) filtered bytes in ceil(h / IR_PNG_ROWS) chunks the chunk bounds sum
+// to at most ceil(9 D / 8) + chunks * (ceil((1106 + 9 + 3 + 7) / 8) + 4 + 1) (the + 1: each chunk's own rounding of 9 * bytes / 8).
+size_t ir_png_bound(int h, int w) {
+    if (h < 1 || w < 1) return 0;
+    const size_t rowlen = 3 * (size_t)w + 1, chunks = ((size_t)h + IR_PNG_ROWS - 1) / IR_PNG_ROWS;
+    return 2 + (9 * (size_t)h * rowlen + 7) / 8 + chunks * ((IR_PNG_HEADER_BITS + 9 + 3 + 7 + 7) / 8 + 4 + 1) + 4;
+}
+int ir_png_encode(ir_ctx* c, void* stream, const uint8_t* img, int n, int h, int w, long pitch, int vh, int vw, uint8_t* out, size_t out_stride,
+                  uint32_t* info, void* ws, size_t ws_bytes) {
+    if (!c || !img || !out || !info || !ws) return fail(c, -1, "ir_png_encode: null argument");
+    if (n < 1 || h < 1 || w < 1 || vh < 1 || vh > h || vw < 1 || vw > w || pitch < 3L * w)
+        return fail(c, -1, "ir_png_encode: bad size (n %d, %d x %d, pitch %ld, valid %d x %d)", n, h, w, pitch, vh, vw);
+    if (out_stride < ir_png_bound(vh, vw)) return fail(c, -1, "ir_png_encode: out_stride %zu below ir_png_bound(%d, %d) = %zu", out_stride, vh, vw, ir_png_bound(vh, vw));
+    const PngLayout L = png_layout(n, vh, vw);
+    if (int e = check_ws(c, "ir_png_encode", ws, ws_bytes, L.total, 16)) return e;
+    use_ctx(c);
+    char* b = static_cast<char*>(ws);
+    if (ir_launch_png_encode(img, n, h, pitch, vh, vw, out, out_stride, info, (uint32_t*)(b + L.hist), (uint32_t*)(b + L.codes), (uint32_t*)(b + L.header),
+                             (uint32_t*)(b + L.sizes), (uint8_t*)(b + L.slots), (long)L.slot_cap, (hipStream_t)stream))
+        return fail(c, -100, "ir_png_encode: launch failed");
+    return 0;
+}
+
+// ---------------------------------------------------------------- Pillow's 8-bit resampling (resample.hip)
+// The tables of Resample.c's precompute_coeffs + normalize_coeffs_8bpc. Plain double arithmetic in Pillow's order of operations (no contraction
+// into fused multiply-adds): the quantised coefficients have to be Pillow's to the last bit.
+#pragma clang fp contract(off)
+static double rs_bicubic(double x) {
+    const double a = -0.5;
+    if (x < 0.0) x = -x;
+    if (x < 1.0) return ((a + 2.0) * x - (a + 3.0)) * x * x + 1;
+    if (x < 2.0) return (((x - 5) * x + 8) * x - 4) * a;
+    return 0.0;
+}
+static double rs_sinc(double x) {
+    if (x == 0.0) return 1.0;
+    x = x * M_PI;
+    return sin(x) / x;
+}
+static double rs_lanczos(double x) { return (-3.0 <= x && x < 3.0) ? rs_sinc(x) * rs_sinc(x / 3) : 0.0; }
+struct RsAxis {
+    double scale, filterscale, support;
+    int ksize;
+};
+static RsAxis rs_axis(int in, int out, int filter) {
+    RsAxis a;
+    a.filterscale = a.scale = (double)(float)in / out;
+    if (a.filterscale < 1.0) a.filterscale = 1.0;
+    a.support = (filter == IR_RESAMPLE_LANCZOS ? 3.0 : 2.0) * a.filterscale;
+    a.ksize = (int)ceil(a.support) * 2 + 1;
+    return a;
+}
+static void rs_tables(int in, int out, int filter, int* bounds, int* kk) {
+    const RsAxis a = rs_axis(in, out, filter);
+    std::vector<double> w(a.ksize);
+    const double ss = 1.0 / a.filterscale;
+    for (int xx = 0; xx < out; ++xx) {
+        const double center = (xx + 0.5) * a.scale;
+        double ww = 0.0;
+        int xmin = (int)(center - a.support + 0.5);
+        if (xmin < 0) xmin = 0;
+        int xmax = (int)(center + a.support + 0.5);
+        if (xmax > in) xmax = in;
+        xmax -= xmin;
+        for (int x = 0; x < xmax; ++x) {
+            const double arg = (x + xmin - center + 0.5) * ss;
+            w[x] = filter == IR_RESAMPLE_LANCZOS ? rs_lanczos(arg) : rs_bicubic(arg);
+            ww += w[x];
+        }
+        int* k = kk + (size_t)xx * a.ksize;
+        for (int x = 0; x < a.ksize; ++x) {
+            double v = x < xmax ? w[x] : 0.0;
+            if (x < xmax && ww != 0.0) v /= ww;
+            k[x] = v < 0 ? (int)(-0.5 + v * (1 << 22)) : (int)(0.5 + v * (1 << 22));
+        }
+        bounds[2 * xx] = xmin;
+        bounds[2 * xx + 1] = xmax;
+    }
+}
+#pragma clang fp contract(fast)
+static bool rs_args_ok(int in_h, int in_w, int out_h, int out_w, int filter) {
+    return in_h >= 1 && in_w >= 1 && out_h >= 1 && out_w >= 1 && (filter == IR_RESAMPLE_BICUBIC || filter == IR_RESAMPLE_LANCZOS);
+}
+// ints of the plan: the header, then per pass that runs 2 bounds + ksize coefficients per output index
+static size_t rs_plan_ints(int in_h, int in_w, int out_h, int out_w, int filter, int* hd) {
+    size_t at = IR_RESAMPLE_HEADER;
+    int h[IR_RESAMPLE_HEADER] = {IR_RESAMPLE_MAGIC, in_h, in_w, out_h, out_w, filter};
+    if (in_w != out_w) {
+        h[6] = rs_axis(in_w, out_w, filter).ksize;
+        h[8] = (int)at; at += 2 * (size_t)out_w;
+        h[9] = (int)at; at += (size_t)out_w * h[6];
+    }
+    if (in_h != out_h) {
+        h[7] = rs_axis(in_h, out_h, filter).ksize;
+        h[10] = (int)at; at += 2 * (size_t)out_h;
+        h[11] = (int)at; at += (size_t)out_h * h[7];
+    }
+    h[12] = (int)at;
+    if (hd) memcpy(hd, h, sizeof h);
+    return at;
+}
+size_t ir_resample_plan_bytes(int in_h, int in_w, int out_h, int out_w, int filter) {
+    if (!rs_args_ok(in_h, in_w, out_h, out_w, filter)) return 0;
+    const size_t ints = rs_plan_ints(in_h, in_w, out_h, out_w, filter, nullptr);
+    return ints > 0x7fffffffu ? 0 : 4 * ints;   // the offsets are ints
+}
+int ir_resample_plan(int in_h, int in_w, int out_h, int out_w, int filter, void* host_plan, size_t bytes) {
+    const size_t need = ir_resample_plan_bytes(in_h, in_w, out_h, out_w, filter);
+    if (!host_plan || !need || bytes < need) return -1;
+    int* p = static_cast<int*>(host_plan);
+    rs_plan_ints(in_h, in_w, out_h, out_w, filter, p);
+    if (in_w != out_w) rs_tables(in_w, out_w, filter, p + p[8], p + p[9]);
+    if (in_h != out_h) rs_tables(in_h, out_h, filter, p + p[10], p + p[11]);
+    return 0;
+}
+static size_t rs_inter_pitch(int out_w) { return (3 * (size_t)out_w + 3) & ~(size_t)3; }
+static size_t rs_workspace(int n, int in_h, int out_w) { return ((size_t)n * in_h * rs_inter_pitch(out_w) + 255) & ~(size_t)255; }
+int ir_resample_u8(ir_ctx* c, void* stream, const uint8_t* in, int n, int in_h, int in_w, long in_pitch, uint8_t* out, int out_h, int out_w, int full_h,
+                   int full_w, long out_pitch, const void* plan_dev, void* ws, size_t ws_bytes) {
+    if (!c || !in || !out || !plan_dev) return fail(c, -1, "ir_resample_u8: null argument");
+    if (n < 1 || in_h < 1 || in_w < 1 || out_h < 1 || out_w < 1 || full_h < out_h || full_w < out_w || in_pitch < 3L * in_w || out_pitch < 3L * full_w)
+        return fail(c, -1, "ir_resample_u8: bad size (n %d, %d x %d pitch %ld -> %d x %d in %d x %d pitch %ld)", n, in_h, in_w, in_pitch, out_h, out_w, full_h,
+                    full_w, out_pitch);
+    const bool both = in_h != out_h && in_w != out_w;
+    if (both && (!ws || ws_bytes < rs_workspace(n, in_h, out_w) || (reinterpret_cast<uintptr_t>(ws) & 3)))
+        return fail(c, -1, "ir_resample_u8: workspace missing, too small or unaligned (%zu < %zu)", ws_bytes, rs_workspace(n, in_h, out_w));
+    if (reinterpret_cast<uintptr_t>(plan_dev) & 3) return fail(c, -1, "ir_resample_u8: plan not aligned to 4 bytes");
+    use_ctx(c);
+    if (ir_launch_resample_u8(in, n, in_h, in_w, in_pitch, out, out_h, out_w, full_h, full_w, out_pitch, static_cast<const int*>(plan_dev),
+                              static_cast<uint8_t*>(ws), (long)rs_inter_pitch(out_w), (hipStream_t)stream))
+        return fail(c, -100, "ir_resample_u8: launch failed (more than 65535 images or rows)");
+    return 0;
+}
+
+// ---------------------------------------------------------------- PSNR-Y / SSIM-Y (metrics.hip)
+// two doubles per tile of the 'valid' SSIM map (at least one tile, so that every size from 1 up has a positive answer)
+static size_t metrics_workspace(int n, int h, int w) {
+    const size_t tx = w > 10 ? ((size_t)w - 10 + IR_METRICS_TW - 1) / IR_METRICS_TW : 1, ty = h > 10 ? ((size_t)h - 10 + IR_METRICS_TH - 1) / IR_METRICS_TH : 1;
+    return ((size_t)n * tx * ty * 2 * sizeof(double) + 255) & ~(size_t)255;
+}
+int ir_metrics_y(ir_ctx* c, void* stream, const uint8_t* a, int a_rows, long a_pitch, const uint8_t* b, int b_rows, long b_pitch, int n, int h, int w,
+                 double* out, void* ws, size_t ws_bytes) {
+    if (!c || !a || !b || !out || !ws) return fail(c, -1, "ir_metrics_y: null argument");
+    if (int e = check_rect(c, "ir_metrics_y", "the window needs 11 x 11", n, h, w, 11, {{a_rows, a_pitch}, {b_rows, b_pitch}})) return e;
+    if (int e = check_ws(c, "ir_metrics_y", ws, ws_bytes, metrics_workspace(n, h, w), 8)) return e;
+    if (int e = check_out8(c, "ir_metrics_y", out)) return e;
+    if (!c->luma_tab) return fail(c, -1, "ir_metrics_y: the context has no luma tables");
+    use_ctx(c);
+    if (ir_launch_metrics_y(a, a_rows, a_pitch, b, b_rows, b_pitch, n, h, w, c->luma_tab, static_cast<double*>(ws), out, (hipStream_t)stream))
+        return fail(c, -100, "ir_metrics_y: launch failed (more than 65535 images or tile rows)");
+    return 0;
+}
+
+// ---------------------------------------------------------------- LPIPS (lpips.hip)
+int ir_lpips_scale_table(float* tab) {
+    if (!tab) return -1;
+    static const float shift[3] = {-.030f, -.088f, -.188f}, scale[3] = {.458f, .448f, .450f};
+    for (int ch = 0; ch < 3; ++ch)
+        for (int v = 0; v < 256; ++v) {   // every step rounded to fp32, in the model's order
+            volatile float x = (float)v / 255.0f;
+            volatile float y = 2.0f * x;
+            volatile float z = y - 1.0f;
+            volatile float u = z - shift[ch];
+            tab[256 * ch + v] = u / scale[ch];
+        }
+    return 0;
+}
+
+int ir_lpips_configure(ir_ctx* c) {
+    if (!c) return -1;
+    static const int shape[5][3] = {{3, 64, 11}, {64, 192, 5}, {192, 384, 3}, {384, 256, 3}, {256, 256, 3}};   // cin, cout, k
+    HIPOK(c, hipSetDevice(c->device));
+    c->lpips.ok = false;
+    ir_ctx::Lpips m;
+    const char* const who = "ir_lpips_configure";
+    const float* src[5];
+    for (int k = 0; k < 5; ++k) {   // every tensor is looked up before anything is replaced
+        const int cin = shape[k][0], cout = shape[k][1], ks = shape[k][2];
+        if (!(src[k] = exact_f32(c, who, "AlexNet's", fmt("lpips.c%d.w", k + 1), (size_t)cout * cin * ks * ks)) ||
+            !(m.b[k] = exact_f32(c, who, "AlexNet's", fmt("lpips.c%d.b", k + 1), (size_t)cout)) ||
+            !(m.lin[k] = exact_f32(c, who, "AlexNet's", fmt("lpips.lin%d", k + 1), (size_t)cout)))
+            return -2;
+    }
+    std::vector<void*>& own = c->own[OWN_LPIPS];
+    release_list(own);
+    HIPOK(c, hipDeviceSynchronize());
+    float tab[3 * 256];
+    ir_lpips_scale_table(tab);
+    if (int e = own_copy(c, own, tab, sizeof tab, hipMemcpyHostToDevice, &m.tab)) return e;
+    for (int k = 0; k < 5; ++k) {
+        const int cout = shape[k][1];
+        std::vector<float> t;
+        if (int e = repacked_conv(c, src[k], shape[k][0], cout, shape[k][2], t)) return e;
+        if (int e = own_copy(c, own, t.data(), t.size() * 4, hipMemcpyHostToDevice, &m.w[k])) return e;
+        // copies of the bias and the lin head: the binding does not depend on later uploads under these names
+        for (const float** q : {&m.b[k], &m.lin[k]})
+            if (int e = own_copy(c, own, *q, (size_t)cout * 4, hipMemcpyDeviceToDevice, q)) return e;
+    }
+    m.ok = true;
+    c->lpips = m;
+    ++c->generation;
+    return 0;
+}
+
+int ir_lpips(ir_ctx* c, void* stream, const uint8_t* a, int a_rows, long a_pitch, const uint8_t* b, int b_rows, long b_pitch, int n, int h, int w,
+             double* out, void* ws, size_t ws_bytes) {
+    if (!c || !a || !b || !out || !ws) return fail(c, -1, "ir_lpips: null argument");
+    if (int e = check_rect(c, "ir_lpips", "AlexNet's five stages need 31 x 31", n, h, w, 31, {{a_rows, a_pitch}, {b_rows, b_pitch}})) return e;
+    IrLpipsPlan pl;
+    if (ir_lpips_plan(n, h, w, &pl)) return fail(c, -1, "ir_lpips: n %d of %d x %d is more than one call takes (2^31 output pixels, 65535 pairs)", n, h, w);
+    if (int e = check_ws(c, "ir_lpips", ws, ws_bytes, pl.total, 256)) return e;
+    if (int e = check_out8(c, "ir_lpips", out)) return e;
+    if (!c->lpips.ok) return fail(c, -12, "ir_lpips: LPIPS not configured (ir_lpips_configure)");
+    use_ctx(c);
+    if (ir_launch_lpips(a, a_rows, a_pitch, b, b_rows, b_pitch, n, h, w, c->lpips.tab, c->lpips.w, c->lpips.b, c->lpips.lin, ws, out, (hipStream_t)stream))
+        return fail(c, -100, "ir_lpips: launch failed");
+    return 0;
+}
+
+// ---------------------------------------------------------------- CLIP-IQA (clipiqa.hip)
+int ir_clipiqa_scale_table(float* tab) {
+    if (!tab) return -1;
+    static const float mean[3] = {0.48145466f, 0.4578275f, 0.40821073f}, std3[3] = {0.26862954f, 0.26130258f, 0.27577711f};
+    for (int ch = 0; ch < 3; ++ch)
+        for (int v = 0; v < 256; ++v) {   // every step rounded to fp32, in the model's order
+            volatile float x = (float)v / 255.0f;
+            volatile float y = x - mean[ch];
+            tab[256 * ch + v] = y / std3[ch];
+        }
+    return 0;
+}
+
+namespace {
+struct ClipConvSrc { std::string conv, bn; int cin, cout, ks; IrClipConv* dst; };
+}  // namespace
+
+int ir_clipiqa_configure(ir_ctx* c, const int* layers, int width, int heads, int out_dim, int n_pairs, float logit_scale_exp) {
+    if (!c || !layers) return fail(c, -1, "ir_clipiqa_configure: null argument");
+    int n_blocks = 0;
+    for (int l = 0; l < 4; ++l) {
+        if (layers[l] < 1) return fail(c, -1, "ir_clipiqa_configure: layer %d has %d blocks", l + 1, layers[l]);
+        n_blocks += layers[l];
+    }
+    if (n_blocks > IR_CLIPIQA_MAX_BLOCKS) return fail(c, -1, "ir_clipiqa_configure: %d blocks, at most %d", n_blocks, IR_CLIPIQA_MAX_BLOCKS);
+    if (width < 64 || width % 64 || heads < 1 || (width * 32) % heads || out_dim < 1 || n_pairs < 1 || n_pairs > 64 || !(logit_scale_exp > 0.f))
+        return fail(c, -1, "ir_clipiqa_configure: unsupported model (width %d must be a multiple of 64, heads %d must divide %d, out_dim %d, %d pairs)", width,
+                    heads, width * 32, out_dim, n_pairs);
+    HIPOK(c, hipSetDevice(c->device));
+    c->clipiqa.ok = false;
+    auto m = std::make_unique<IrClipiqaModel>();
+    for (int l = 0; l < 4; ++l) m->layers[l] = layers[l];
+    m->width = width; m->heads = heads; m->out_dim = out_dim; m->n_pairs = n_pairs; m->n_blocks = n_blocks; m->logit_scale = (double)logit_scale_exp;
+    std::vector<ClipConvSrc> convs;
+    convs.push_back({"clipiqa.conv1", "clipiqa.bn1", 3, width / 2, 3, &m->stem[0]});
+    convs.push_back({"clipiqa.conv2", "clipiqa.bn2", width / 2, width / 2, 3, &m->stem[1]});
+    convs.push_back({"clipiqa.conv3", "clipiqa.bn3", width / 2, width, 3, &m->stem[2]});
+    int inplanes = width, bi = 0;
+    for (int l = 0; l < 4; ++l) {
+        const int planes = width << l;
+        for (int i = 0; i < layers[l]; ++i, ++bi) {
+            IrClipBlock& b = m->blocks[bi];
+            b.stride = (i == 0 && l > 0) ? 2 : 1;
+            b.has_down = b.stride == 2 || inplanes != planes * 4;
+            const std::string base = fmt("clipiqa.layer%d.%d.", l + 1, i);
+            convs.push_back({base + "conv1", base + "bn1", inplanes, planes, 1, &b.c1});
+            convs.push_back({base + "conv2", base + "bn2", planes, planes, 3, &b.c2});
+            convs.push_back({base + "conv3", base + "bn3", planes, planes * 4, 1, &b.c3});
+            if (b.has_down) convs.push_back({base + "downsample.0", base + "downsample.1", inplanes, planes * 4, 1, &b.down});
+            inplanes = planes * 4;
+        }
+    }
+    const int C = width * 32;
+    auto tensor = [&](const std::string& name, size_t floats) { return exact_f32(c, "ir_clipiqa_configure", "the configured model's", name, floats); };
+    // every tensor is looked up before anything is replaced
+    struct Lin { const char* name; int rows, cols; const float **w, **b; };
+    const Lin lins[4] = {{"q_proj", C, C, &m->qw, &m->qb}, {"k_proj", C, C, &m->kw, &m->kb}, {"v_proj", C, C, &m->vw, &m->vb}, {"c_proj", out_dim, C, &m->cw, &m->cb}};
+    for (const ClipConvSrc& s : convs) {
+        if (!tensor(s.conv + ".weight", (size_t)s.cout * s.cin * s.ks * s.ks)) return -2;
+        for (const char* v : {".weight", ".bias", ".running_mean", ".running_var"})
+            if (!tensor(s.bn + v, (size_t)s.cout)) return -2;
+    }
+    for (const Lin& l : lins)
+        if (!tensor(fmt("clipiqa.attnpool.%s.weight", l.name), (size_t)l.rows * l.cols) || !tensor(fmt("clipiqa.attnpool.%s.bias", l.name), (size_t)l.rows))
+            return -2;
+    if (!tensor("clipiqa.text", (size_t)2 * n_pairs * out_dim)) return -2;
+
+    std::vector<void*>& own = c->own[OWN_CLIPIQA];
+    release_list(own);
+    HIPOK(c, hipDeviceSynchronize());
+    float tab[3 * 256];
+    ir_clipiqa_scale_table(tab);
+    if (int e = own_copy(c, own, tab, sizeof tab, hipMemcpyHostToDevice, &m->tab)) return e;
+    for (const ClipConvSrc& s : convs) {   // the repacked weights, and BatchNorm folded in fp64
+        std::vector<float> t, bn[4], sc(s.cout), sh(s.cout);
+        if (int e = repacked_conv(c, tensor(s.conv + ".weight", (size_t)s.cout * s.cin * s.ks * s.ks), s.cin, s.cout, s.ks, t)) return e;
+        int k = 0;
+        for (const char* v : {".weight", ".bias", ".running_mean", ".running_var"}) {
+            bn[k].resize(s.cout);
+            HIPOK(c, hipMemcpy(bn[k].data(), tensor(s.bn + v, (size_t)s.cout), (size_t)s.cout * 4, hipMemcpyDeviceToHost));
+            ++k;
+        }
+        for (int o = 0; o < s.cout; ++o) {   // scale = g / sqrt(var + eps), shift = b - mean scale, each rounded to fp32 once
+            const double scale = (double)bn[0][o] / sqrt((double)bn[3][o] + 1e-5);
+            sc[o] = (float)scale;
+            sh[o] = (float)((double)bn[1][o] - (double)bn[2][o] * scale);
+        }
+        s.dst->cin = s.cin; s.dst->cout = s.cout; s.dst->ks = s.ks;
+        if (int e = own_copy(c, own, t.data(), t.size() * 4, hipMemcpyHostToDevice, &s.dst->w)) return e;
+        if (int e = own_copy(c, own, sc.data(), sc.size() * 4, hipMemcpyHostToDevice, &s.dst->scale)) return e;
+        if (int e = own_copy(c, own, sh.data(), sh.size() * 4, hipMemcpyHostToDevice, &s.dst->shift)) return e;
+    }
+    // copies of the linears and the text rows: the binding does not depend on later uploads under these names
+    for (const Lin& l : lins) {
+        const size_t nw = (size_t)l.rows * l.cols, nb = (size_t)l.rows;
+        if (int e = own_copy(c, own, tensor(fmt("clipiqa.attnpool.%s.weight", l.name), nw), nw * 4, hipMemcpyDeviceToDevice, l.w)) return e;
+        if (int e = own_copy(c, own, tensor(fmt("clipiqa.attnpool.%s.bias", l.name), nb), nb * 4, hipMemcpyDeviceToDevice, l.b)) return e;
+    }
+    const size_t nt = (size_t)2 * n_pairs * out_dim;
+    if (int e = own_copy(c, own, tensor("clipiqa.text", nt), nt * 4, hipMemcpyDeviceToDevice, &m->text)) return e;
+    m->ok = true;
+    c->clipiqa = *m;
+    ++c->generation;
+    return 0;
+}
+
+int ir_clipiqa(ir_ctx* c, void* stream, const uint8_t* img, int rows, long pitch, int n, int h, int w, double* scores, float* feat, void* ws, size_t ws_bytes) {
+    if (!c || !img || !scores || !ws) return fail(c, -1, "ir_clipiqa: null argument");
+    if (int e = check_rect(c, "ir_clipiqa", "the tower's last map needs 32 x 32", n, h, w, 32, {{rows, pitch}})) return e;
+    if (!c->clipiqa.ok) return fail(c, -13, "ir_clipiqa: CLIP-IQA not configured (ir_clipiqa_configure)");
+    IrClipiqaPlan pl;
+    if (ir_clipiqa_plan(c->clipiqa, n, h, w, &pl)) return fail(c, -1, "ir_clipiqa: n %d of %d x %d is more than one call takes (2^31 output pixels, 65535 images)", n, h, w);
+    if (int e = check_ws(c, "ir_clipiqa", ws, ws_bytes, pl.total, 256)) return e;
+    if ((reinterpret_cast<uintptr_t>(scores) & 7) || (reinterpret_cast<uintptr_t>(feat) & 3)) return fail(c, -1, "ir_clipiqa: scores / feat not aligned");
+    use_ctx(c);
+    if (ir_launch_clipiqa(c->clipiqa, img, rows, pitch, n, h, w, scores, feat, ws, (hipStream_t)stream)) return fail(c, -100, "ir_clipiqa: launch failed");
+    return 0;
+}
+
+// ---------------------------------------------------------------- NIQE's block statistics (niqe.hip)
+// the half-size fp64 luma plane of every image's scored rectangle
+static size_t niqe_workspace(int n, int h, int w) {
+    const size_t H2 = (size_t)(h / IR_NIQE_BLOCK) * (IR_NIQE_BLOCK / 2), W2 = (size_t)(w / IR_NIQE_BLOCK) * (IR_NIQE_BLOCK / 2);
+    return ((size_t)n * H2 * W2 * sizeof(double) + 255) & ~(size_t)255;
+}
+int ir_niqe_window(double* k49) {
+    if (!k49) return -1;
+    ir_niqe_window_host(k49);
+    return 0;
+}
+int ir_niqe_stats(ir_ctx* c, void* stream, const uint8_t* img, int rows, long pitch, int n, int h, int w, double* out, void* ws, size_t ws_bytes) {
+    if (!c || !img || !out || !ws) return fail(c, -1, "ir_niqe_stats: null argument");
+    if (int e = check_rect(c, "ir_niqe_stats", "a block is 96 x 96", n, h, w, IR_NIQE_BLOCK, {{rows, pitch}})) return e;
+    if (int e = check_ws(c, "ir_niqe_stats", ws, ws_bytes, niqe_workspace(n, h, w), 8)) return e;
+    if (int e = check_out8(c, "ir_niqe_stats", out)) return e;
+    if (!c->niqe_tab) return fail(c, -1, "ir_niqe_stats: the context has no luma tables");
+    use_ctx(c);
+    if (ir_launch_niqe_stats(img, rows, pitch, n, h, w, c->niqe_tab, static_cast<double*>(ws), out, (hipStream_t)stream))
+        return fail(c, -100, "ir_niqe_stats: launch failed (more than 65535 images or block rows)");
+    return 0;
+}
+
+// ---------------------------------------------------------------- low-quality inputs from ground truth (degrade.hip)
+int ir_degrade_qtables(int q, uint16_t* luma64, uint16_t* chroma64) {
+    if (!luma64 || !chroma64 || q < 1 || q > 100) return -1;
+    ir_degrade_qtables_host(q, luma64, chroma64);
+    return 0;
+}
+int ir_degrade(ir_ctx* c, void* stream, const uint8_t* img, int rows, long pitch, int n, int h, int w, const ir_degrade_params* params, uint8_t* out,
+               uint8_t* jpeg_or_null, void* ws, size_t ws_bytes) {
+    if (!c || !img || !params || !out || !ws) return fail(c, -1, "ir_degrade: null argument");
+    if (int e = check_rect(c, "ir_degrade", nullptr, n, h, w, 1, {{rows, pitch}}, (long)h * w > (1L << 28))) return e;
+    for (int i = 0; i < n; ++i) {   // every image is checked before the first launch
+        const ir_degrade_params& p = params[i];
+        if (!p.kernel) return fail(c, -1, "ir_degrade: image %d has no blur kernel", i);
+        if (p.ksize < 1 || p.ksize > IR_DEGRADE_MAX_KSIZE || !(p.ksize & 1))
+            return fail(c, -1, "ir_degrade: image %d: the blur kernel size %d is not odd and within 1 .. %d", i, p.ksize, IR_DEGRADE_MAX_KSIZE);
+        if (h < p.ksize / 2 + 1 || w < p.ksize / 2 + 1)
+            return fail(c, -1, "ir_degrade: a %d x %d image is too small for a %d x %d blur (reflection needs %d pixels)", h, w, p.ksize, p.ksize, p.ksize / 2 + 1);
+        if (p.lh < IR_DEGRADE_MIN_LOW || p.lw < IR_DEGRADE_MIN_LOW || p.lh > h || p.lw > w)
+            return fail(c, -1, "ir_degrade: image %d: low-resolution size %d x %d outside %d .. %d x %d", i, p.lh, p.lw, IR_DEGRADE_MIN_LOW, h, w);
+        if (p.q < 0 || p.q > 100) return fail(c, -1, "ir_degrade: image %d: JPEG quality %d outside 0 .. 100", i, p.q);
+        if (p.norm != IR_DEGRADE_NORM_NONE && p.norm != IR_DEGRADE_NORM_MAX) return fail(c, -1, "ir_degrade: image %d: unknown norm %d", i, p.norm);
+        if ((reinterpret_cast<uintptr_t>(p.kernel) & 7) || (reinterpret_cast<uintptr_t>(p.noise) & 3))
+            return fail(c, -1, "ir_degrade: image %d: misaligned kernel or noise pointer", i);
+    }
+    if (int e = check_ws(c, "ir_degrade", ws, ws_bytes, ir_degrade_workspace(h, w), 256)) return e;
+    use_ctx(c);
+    for (int i = 0; i < n; ++i) {
+        const ir_degrade_params& p = params[i];
+        if (ir_launch_degrade(img + (long)i * rows * pitch, pitch, h, w, p.kernel, p.ksize, p.lh, p.lw, p.sigma, p.q, p.noise, p.norm,
+                              out + (long)i * rows * pitch, pitch, jpeg_or_null ? jpeg_or_null + (long)i * h * w * 3 : nullptr, ws, (hipStream_t)stream))
+            return fail(c, -100, "ir_degrade: launch failed (image %d)", i);
+    }
+    return 0;
+}
+
+// ---------------------------------------------------------------- the second-order degradation chain (degrade_chain.hip)
+static long chain_tap_floats(const ir_chain& ch, int h, int w) {   // the size of the image behind op `tap`
+    if (ch.tap < 0) return 0;
+    for (int i = 0; i <= ch.tap; ++i)
+        if (ch.ops[i].kind == IR_CHAIN_RESIZE) h = ch.ops[i].b, w = ch.ops[i].c;
+    return (long)h * w * 3;
+}
+int ir_degrade_chain(ir_ctx* c, void* stream, const uint8_t* img, int rows, long pitch, int n, int h, int w, const ir_chain* chains, uint8_t* out,
+                     float* tap_or_null, void* ws, size_t ws_bytes) {
+    if (!c || !img || !chains || !out || !ws) return fail(c, -1, "ir_degrade_chain: null argument");
+    if (int e = check_rect(c, "ir_degrade_chain", nullptr, n, h, w, 1, {{rows, pitch}}, h > IR_CHAIN_MAX_SIDE || w > IR_CHAIN_MAX_SIDE)) return e;
+    int mh = h, mw = w;
+    for (int i = 0; i < n; ++i) {   // every chain is checked before the first launch
+        int ih, iw;
+        const char* why;
+        if (ir_degrade_chain_check(&chains[i], h, w, &ih, &iw, &why)) return fail(c, -1, "ir_degrade_chain: image %d (%d x %d): %s", i, h, w, why);
+        mh = std::max(mh, ih), mw = std::max(mw, iw);
+    }
+    if (int e = check_ws(c, "ir_degrade_chain", ws, ws_bytes, ir_degrade_chain_workspace(h, w, mh, mw), 256)) return e;
+    if (tap_or_null && (reinterpret_cast<uintptr_t>(tap_or_null) & 3)) return fail(c, -1, "ir_degrade_chain: misaligned tap pointer");
+    use_ctx(c);
+    for (int i = 0; i < n; ++i) {
+        if (ir_launch_degrade_chain(img + (long)i * rows * pitch, pitch, h, w, &chains[i], mh, mw, out + (long)i * rows * pitch, pitch, tap_or_null, ws,
+                                    (hipStream_t)stream))
+            return fail(c, -100, "ir_degrade_chain: launch failed (image %d)", i);
+        if (tap_or_null) tap_or_null += chain_tap_floats(chains[i], h, w);
+    }
+    return 0;
+}
+}  // extern "C"
+
+// the tables ir_init gives every context (both in OWN_CTX)
+int ir_host::image_init(ir_ctx* c) {
+    auto upload = [c](const double* tab, size_t bytes, double** out) {
+        if (dev_alloc(c, c->own[OWN_CTX], reinterpret_cast<void**>(out), bytes)) return -100;
+        HIPOK(c, hipMemcpy(*out, tab, bytes, hipMemcpyHostToDevice));
+        return 0;
+    };
+    double tab[4 * 256];
+    // ir_metrics_y's luma tables: c_k * (double)((float)v / 255.0f), the float32 division of the host model done once on the host
+    static const double bt601[3] = {65.481, 128.553, 24.966};
+    for (int k = 0; k < 3; ++k)
+        for (int v = 0; v < 256; ++v) {
+            volatile float x = (float)v / 255.0f;
+            tab[256 * k + v] = bt601[k] * (double)x;
+        }
+    if (int e = upload(tab, 3 * 256 * sizeof(double), &c->luma_tab)) return e;
+    // ir_niqe_stats' tables: the YIQ luma terms coef_c * (double)((float)v / 255.0f), then v / 255.0 (the unit scale the half-size filter works on)
+    static const double yiq[3] = {0.299, 0.587, 0.114};
+    for (int v = 0; v < 256; ++v) {
+        volatile float x = (float)v / 255.0f;
+        for (int k = 0; k < 3; ++k) tab[256 * k + v] = yiq[k] * (double)x;
+        tab[768 + v] = (double)v / 255.0;
+    }
+    return upload(tab, sizeof tab, &c->niqe_tab);
+}
+
+// Sizes alone decide every answer except CLIP-IQA's, which also takes the configured layer counts: no context is needed for the others.
+bool ir_host::image_workspace(ir_ctx* c, int stage, int n, int h, int w, int flags, int tile_size, size_t* bytes) {
+    const bool some = n >= 1 && h >= 1 && w >= 1;
+    IrClipiqaPlan cp;
+    IrLpipsPlan lp;
+    *bytes = 0;
+    switch (stage) {
+        case IR_STAGE_DEGRADE_CHAIN: if (n >= 1) *bytes = ir_degrade_chain_workspace(h, w, flags, tile_size); break;   // flags, tile_size: the largest intermediate image
+        case IR_STAGE_DEGRADE: if (n >= 1) *bytes = ir_degrade_workspace(h, w); break;   // the images of a batch share it
+        case IR_STAGE_NIQE: if (n >= 1 && h >= IR_NIQE_BLOCK && w >= IR_NIQE_BLOCK) *bytes = niqe_workspace(n, h, w); break;
+        case IR_STAGE_CLIPIQA: if (c && c->clipiqa.ok && !ir_clipiqa_plan(c->clipiqa, n, h, w, &cp)) *bytes = cp.total; break;
+        case IR_STAGE_LPIPS: if (!ir_lpips_plan(n, h, w, &lp)) *bytes = lp.total; break;
+        case IR_STAGE_METRICS: if (some) *bytes = metrics_workspace(n, h, w); break;
+        case IR_STAGE_PNG: if (some) *bytes = png_layout(n, h, w).total; break;
+        case IR_STAGE_RESAMPLE: if (some) *bytes = rs_workspace(n, h, w); break;   // n images, h = in_h, w = out_w: the uint8 image between the passes
+        default: return false;
+    }
+    return true;
+}

@@ -1,4 +1,4 @@
-// Internal launcher interface between the C-ABI layer (api.cpp) and the HIP kernels. Not part of the public ABI.
+// Internal launcher interface between the C-ABI layer (api.cpp, api_image.cpp) and the HIP kernels. Not part of the public ABI.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>

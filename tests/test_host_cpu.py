@@ -868,3 +868,56 @@ def test_report_names_the_missing_no_reference_score():
     assert both.unscored((30.0, 0.9, 0.1, nan, nan)) == "niqe"      # NIQE is looked at first
     assert Report(None, niqe=True, paired=False).unscored((nan,)) == "niqe" and Report(None, clipiqa=True, paired=False).unscored((nan,)) == "clipiqa"
     assert Report(None).unscored((nan, 0.9)) is None                 # a paired value is not its business
+
+
+def _image_host_tables(lib):
+    """Everything the image tools' host code answers without a device: workspace sizes, PNG bounds, resampling plans and the tables."""
+    import ctypes as C
+    import hashlib
+    from instarevive_amd import _lib
+    sha = lambda buf: hashlib.sha256(bytes(buf)).hexdigest()
+    sizes = [(1, 1), (10, 10), (11, 11), (30, 31), (31, 31), (95, 96), (96, 96), (97, 200), (512, 768)]
+    stages = dict(png=_lib.STAGE_PNG, resample=_lib.STAGE_RESAMPLE, metrics=_lib.STAGE_METRICS, lpips=_lib.STAGE_LPIPS, niqe=_lib.STAGE_NIQE,
+                  degrade=_lib.STAGE_DEGRADE, degrade_chain=_lib.STAGE_DEGRADE_CHAIN, clipiqa=_lib.STAGE_CLIPIQA)
+    out = {"workspace": {}, "png_bound": {}, "resample": {}, "tables": {}}
+    for name, stage in stages.items():
+        for n in (0, 1, 3):
+            for h, w in sizes:
+                chain = name == "degrade_chain"   # its flags / tile_size carry the largest intermediate's height / width
+                out["workspace"][f"{name} n{n} {h}x{w}"] = int(lib.ir_workspace_bytes(None, stage, n, h, w, h + 5 if chain else 0, w + 7 if chain else 0, 0))
+    for h, w in sizes:
+        out["png_bound"][f"{h}x{w}"] = int(lib.ir_png_bound(h, w))
+    for ih, iw, oh, ow in ((8, 8, 4, 4), (7, 9, 7, 4), (5, 5, 5, 5), (12, 16, 25, 33)):   # both passes, one pass, no pass, upscale
+        for fname, filt in (("bicubic", _lib.RESAMPLE_BICUBIC), ("lanczos", _lib.RESAMPLE_LANCZOS)):
+            nbytes = int(lib.ir_resample_plan_bytes(ih, iw, oh, ow, filt))
+            plan = (C.c_ubyte * nbytes)()
+            assert lib.ir_resample_plan(ih, iw, oh, ow, filt, plan, nbytes) == 0
+            out["resample"][f"{ih}x{iw}->{oh}x{ow} {fname}"] = [nbytes, sha(plan)]
+    for name, fn, buf in (("lpips_scale", lib.ir_lpips_scale_table, (C.c_float * 768)()), ("clipiqa_scale", lib.ir_clipiqa_scale_table, (C.c_float * 768)()),
+                          ("niqe_window", lib.ir_niqe_window, (C.c_double * 49)())):
+        assert fn(buf) == 0
+        out["tables"][name] = sha(buf)
+    for q in (1, 50, 75, 100):
+        luma, chroma = (C.c_uint16 * 64)(), (C.c_uint16 * 64)()
+        assert lib.ir_degrade_qtables(q, luma, chroma) == 0
+        out["tables"][f"qtables q{q}"] = sha(bytes(luma) + bytes(chroma))
+    return out
+
+
+def test_image_host_tables_are_the_recorded_ones():
+    """The image tools' host answers (api_image.cpp) against tests/golden/image_host_tables.json, bit for bit: ir_workspace_bytes without a context for
+    the eight image stages (CLIP-IQA answers 0 there), ir_png_bound, the size and SHA-256 of four resampling plans per filter, and the SHA-256 of
+    the LPIPS / CLIP-IQA scale tables, the NIQE window and four JPEG quantisation table pairs. The file was recorded from the library of the commit
+    before the image tools got their own translation unit, built in a checkout of its own and named by INSTAREVIVE_HIP_LIB:
+        import json; from instarevive_amd import _lib; from tests.test_host_cpu import _image_host_tables
+        json.dump(_image_host_tables(_lib.load_library()), open("tests/golden/image_host_tables.json", "w"), indent=1, sort_keys=True)
+    Record it again only from a library whose tables are known to be right: the file is the yardstick, not the code under test."""
+    from instarevive_amd import _lib
+    from instarevive_amd.build import build
+    build()
+    want = json.load(open(os.path.join(ROOT, "tests", "golden", "image_host_tables.json")))
+    got = _image_host_tables(_lib.load_library())
+    assert set(got) == set(want)
+    for part in want:
+        assert got[part] == want[part], (part, {k: (got[part].get(k), v) for k, v in want[part].items() if got[part].get(k) != v})
+    assert len(want["workspace"]) == 8 * 3 * 9 and all(v == 0 for k, v in want["workspace"].items() if k.startswith("clipiqa "))

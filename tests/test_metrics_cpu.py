@@ -191,7 +191,7 @@ def test_near_tie_colours_separate_the_luma_variants():
 
 
 def test_luma_tables_round_like_the_model_on_every_colour():
-    """What api.cpp uploads: t_k[v] = c_k * (double)((float)v / 255.0f), summed as 16 + t_r + t_g + t_b. Over the near-tie colours and a sample
+    """What api_image.cpp uploads: t_k[v] = c_k * (double)((float)v / 255.0f), summed as 16 + t_r + t_g + t_b. Over the near-tie colours and a sample
     of all colours the rounded luma must be the model's (the closest the model comes to a tie is 2.2e-7)."""
     x = (np.arange(256, dtype=np.float32) / np.float32(255.0)).astype(np.float64)
     tab = [c * x for c in (65.481, 128.553, 24.966)]

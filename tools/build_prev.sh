@@ -10,7 +10,7 @@ git show "$REV:$C/$SRC" > "$TMP"
 EXTRA=""; case "$SRC" in *.cpp) EXTRA="-x hip";; esac
 /opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 -std=c++20 -fPIC -ffp-contract=fast $EXTRA -c "$TMP" -o tools/_prev.o
 OBJS=""
-for o in igemm conv_s1 conv_s1_fp8 norm attention attn_d512 attn_fp8 attn_d512_fp8 swin_fused elementwise vae_io t5 unet api; do
+for o in $(python3 -c 'from instarevive_amd.build import SOURCES; print(" ".join(s.rsplit(".", 1)[0] for s in SOURCES))'); do
   if [ "$o" = "${SRC%.*}" ]; then OBJS="$OBJS tools/_prev.o"; else OBJS="$OBJS $C/$o.o"; fi
 done
 /opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -fPIC -o tools/libir_prev.so $OBJS
