@@ -553,6 +553,22 @@ int ir_op_vae_segment(ir_ctx* ctx, void* stream, int half, int first, int count,
                       size_t ws_bytes);
 size_t ir_op_vae_segment_ws(ir_ctx* ctx, int half, int first, int count, int n, int h, int w);
 int ir_op_vae_segment_info(ir_ctx* ctx, int half, int step, int h, int w, char* name, int name_cap, int* cin, int* cout, int* oh, int* ow);
+/* One part of the CONFIGURED SwinIR's shell around its blocks for op-level tests: the host code ir_swinir_forward runs outside the block loop,
+ * called one part at a time (weights as uploaded for ir_swinir_configure, phase forms and the folded conv_last included). T = n * h/8 * w/8
+ * tokens, Cp = 32 * heads columns per token row (columns embed_dim .. Cp - 1 are zero), h and w in pixels.
+ *   IR_SWIN_SHELL_HEAD       in0 = image fp32 NCHW [n][3][h][w] -> out0 = x0 fp32 [T][Cp] (conv_first of the mean-shifted, range-scaled,
+ *                            PixelUnshuffle(8)ed image: the long skip), out1 = xa fp32 [T][Cp] (x0 behind the patch-embed LayerNorm)
+ *   IR_SWIN_SHELL_RSTB_TAIL  in0 = xc bf16 [T][Cp] (the bf16 copy the last block of RSTB `layer` leaves), out0 = xa fp32 [T][Cp] = the RSTB's
+ *                            input, read and replaced in place by conv(xc) + xa
+ *   IR_SWIN_SHELL_RECON      in0 = xa, in1 = x0, both fp32 [T][Cp] -> out0 = fp32 NCHW [n][3][h][w]: final LayerNorm, conv_after_body + x0,
+ *                            conv_before_upsample, the three nearest-2x convs, conv_hr, conv_last (img_range and mean folded in)
+ * in1 / out1 / layer are ignored where a part has none. ir_set_plain_kernels and the profiler act as they do on the stage.
+ * ws: at least ir_op_swin_shell_ws(...) bytes (0: the arguments are refused). Returns -1 for a bad part or layer or a missing tensor, -10 for
+ * a size that is no positive multiple of 64, -11 when SwinIR is not configured, -20 when ws is too small; nothing is launched then. */
+enum { IR_SWIN_SHELL_HEAD = 0, IR_SWIN_SHELL_RSTB_TAIL = 1, IR_SWIN_SHELL_RECON = 2 };
+int ir_op_swin_shell(ir_ctx* ctx, void* stream, int part, int layer, const void* in0, const void* in1, void* out0, void* out1, int n, int h, int w,
+                     void* ws, size_t ws_bytes);
+size_t ir_op_swin_shell_ws(ir_ctx* ctx, int part, int n, int h, int w);
 /* Per-kernel test entry of conv64_kernel (vae_io.hip): 3x3 stride-1 conv 64 -> 64 on bf16 NHWC, bias, act = IR_ACT_NONE or IR_ACT_LRELU(slope) - the shape
  * of SwinIR's conv_hr (diffusion/model/swinir.py:895); h * w >= 65536. The pipeline takes this kernel only under IR_CONV64=1 (see vae_io.hip). */
 int ir_op_conv64(ir_ctx* ctx, void* stream, const uint16_t* in, const uint16_t* wgt, const float* bias, uint16_t* out, int n, int h, int w, int act,

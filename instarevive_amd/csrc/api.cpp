@@ -315,6 +315,51 @@ struct Binder {
 };
 
 // ================================================================ SwinIR  (diffusion/model/swinir.py:867-905)
+// The shell around the blocks in three parts; swinir_run() runs them with the block loop in between, ir_op_swin_shell one at a time.
+// HEAD: mean / range / PixelUnshuffle(8) -> conv_first -> x0 (fp32, kept for the long skip); patch_embed LayerNorm -> residual stream xa
+void swin_head(Run& r, const float* in, bf16_t* f0, float* x0, float* xa, int n, int h, int w) {
+    const SwinModel& m = r.c->swin;
+    const int gh = h / 8, gw = w / 8, Cp = m.Cp;
+    LAUNCH(r, PC_OTHER, 0.0, 0.0, ir_launch_swin_prep(in, f0, n, h, w, m.mean, m.range, r.s), "swin_prep");
+    conv(r, m.conv_first, f0, n, gh, gw, 192, x0, Cp, 1, 1, 1, 0, ACT_NONE, 0.f, nullptr, 0, 0);
+    layernorm(r, x0, nullptr, xa, m.pe.g, m.pe.b, (long)n * gh * gw, m.C, Cp, Cp, 1e-5f);
+}
+// RSTB tail: conv(x) + input of the RSTB (swinir.py:493); xc = the last block's bf16 copy, xa = the RSTB's input, updated in place
+void swin_rstb_tail(Run& r, const SwinLayer& L, const bf16_t* xc, float* xa, int n, int gh, int gw) {
+    const int Cp = r.c->swin.Cp;
+    conv(r, L.conv, xc, n, gh, gw, Cp, xa, Cp, 1, 1, 1, 0, ACT_NONE, 0.f, xa, 1, Cp);
+}
+// RECON: final LayerNorm -> conv_after_body + x0 (swinir.py:888) -> bf16; reconstruction (swinir.py:889-896) -> out fp32 NCHW.
+// xn, att: [T][Cp] bf16 scratch; the up-sampling buffers come from the arena.
+void swin_recon(Run& r, const float* xa, const float* x0, bf16_t* xn, bf16_t* att, float* out, int n, int h, int w) {
+    const SwinModel& m = r.c->swin;
+    const int gh = h / 8, gw = w / 8, Cp = m.Cp;
+    const long T = (long)n * gh * gw;
+    layernorm(r, xa, xn, nullptr, m.norm.g, m.norm.b, T, m.C, Cp, Cp, 1e-5f);
+    conv(r, m.after_body, xn, n, gh, gw, Cp, att, Cp, 0, 1, 1, 0, ACT_NONE, 0.f, x0, 1, Cp);
+    const int nf = m.nf;
+    bf16_t* u0 = r.a.alloc<bf16_t>(T * nf);
+    bf16_t* u1 = r.a.alloc<bf16_t>(T * 4 * nf);
+    bf16_t* u2 = r.a.alloc<bf16_t>(T * 16 * nf);
+    bf16_t* u3 = r.a.alloc<bf16_t>(T * 64 * nf);
+    bf16_t* u4 = r.a.alloc<bf16_t>(T * 64 * nf);
+    float* o4 = r.a.alloc<float>(T * 64 * 4);
+    conv(r, m.before_up, att, n, gh, gw, Cp, u0, nf, 0, 1, 1, 0, ACT_LRELU, 0.01f, nullptr, 0, 0);
+    conv(r, m.up1, u0, n, gh, gw, nf, u1, nf, 0, 1, 1, 1, ACT_LRELU, 0.2f, nullptr, 0, 0);
+    conv(r, m.up2, u1, n, 2 * gh, 2 * gw, nf, u2, nf, 0, 1, 1, 1, ACT_LRELU, 0.2f, nullptr, 0, 0);
+    conv(r, m.up3, u2, n, 4 * gh, 4 * gw, nf, u3, nf, 0, 1, 1, 1, ACT_LRELU, 0.2f, nullptr, 0, 0);
+    conv(r, m.hr, u3, n, h, w, nf, u4, nf, 0, 1, 1, 0, ACT_LRELU, 0.2f, nullptr, 0, 0);
+    // conv_last with x/img_range + mean folded into its weights (swinir.py:896,903)
+    // from 1024 x 1024 pixels up: below that the launch is 30 us either way, and the stress fixtures at 512 x 512 - whose PSNR against the oracle moves
+    // by +- 0.7 dB with the summation ORDER of any one conv on the way (profiles/r06_stress_sensitivity.txt) - keep the numbers they were calibrated on
+    if (!r.c->plain && nf == 64 && m.last.cin == 64 && m.last.cout_pad == 32 && m.last.taps == 9 && (long)h * w >= 1024L * 1024) {
+        const double px = (double)n * h * w;
+        LAUNCHK(r, PK_CONV_TO3, 2.0 * px * 3 * 9 * 64, px * (64 * 2 + 16), ir_launch_conv64_to3(u4, m.last.w, m.last.b, o4, n, h, w, r.s), "swin_conv_last");
+    } else {
+        conv(r, m.last, u4, n, h, w, nf, o4, 4, 1, 1, 1, 0, ACT_NONE, 0.f, nullptr, 0, 0);
+    }
+    LAUNCH(r, PC_OTHER, 0.0, 0.0, ir_launch_nhwc_to_nchw(o4, 4, out, n, 3, (long)h * w, 1.f, 0.f, 0, r.s), "nhwc_to_nchw");
+}
 void swinir_run(Run& r, const float* in, float* out, int n, int h, int w) {
     const SwinModel& m = r.c->swin;
     const int gh = h / 8, gw = w / 8, Cp = m.Cp;
@@ -329,10 +374,7 @@ void swinir_run(Run& r, const float* in, float* out, int n, int h, int w) {
     bf16_t* att = r.a.alloc<bf16_t>(T * Cp);
     bf16_t* hid = r.a.alloc<bf16_t>(T * m.hid_p);
     bf16_t* xc = r.a.alloc<bf16_t>(T * Cp);
-    LAUNCH(r, PC_OTHER, 0.0, 0.0, ir_launch_swin_prep(in, f0, n, h, w, m.mean, m.range, r.s), "swin_prep");
-    // conv_first -> x0 (fp32, kept for the long skip); patch_embed LayerNorm -> residual stream xa
-    conv(r, m.conv_first, f0, n, gh, gw, 192, x0, Cp, 1, 1, 1, 0, ACT_NONE, 0.f, nullptr, 0, 0);
-    layernorm(r, x0, nullptr, xa, m.pe.g, m.pe.b, T, m.C, Cp, Cp, 1e-5f);
+    swin_head(r, in, f0, x0, xa, n, h, w);
     const float scale = 1.0f / sqrtf((float)m.C / (float)m.heads);
     for (const SwinLayer& L : m.layers) {
         const float* cur = xa;
@@ -390,34 +432,9 @@ void swinir_run(Run& r, const float* in, float* out, int n, int h, int w) {
             }
             cur = xb;
         }
-        // RSTB tail: conv(x) + input of the RSTB (swinir.py:493)
-        conv(r, L.conv, xc, n, gh, gw, Cp, xa, Cp, 1, 1, 1, 0, ACT_NONE, 0.f, xa, 1, Cp);
+        swin_rstb_tail(r, L, xc, xa, n, gh, gw);
     }
-    layernorm(r, xa, xn, nullptr, m.norm.g, m.norm.b, T, m.C, Cp, Cp, 1e-5f);
-    // conv_after_body + x0 (swinir.py:888) -> bf16; reconstruction (swinir.py:889-896)
-    conv(r, m.after_body, xn, n, gh, gw, Cp, att, Cp, 0, 1, 1, 0, ACT_NONE, 0.f, x0, 1, Cp);
-    const int nf = m.nf;
-    bf16_t* u0 = r.a.alloc<bf16_t>(T * nf);
-    bf16_t* u1 = r.a.alloc<bf16_t>(T * 4 * nf);
-    bf16_t* u2 = r.a.alloc<bf16_t>(T * 16 * nf);
-    bf16_t* u3 = r.a.alloc<bf16_t>(T * 64 * nf);
-    bf16_t* u4 = r.a.alloc<bf16_t>(T * 64 * nf);
-    float* o4 = r.a.alloc<float>(T * 64 * 4);
-    conv(r, m.before_up, att, n, gh, gw, Cp, u0, nf, 0, 1, 1, 0, ACT_LRELU, 0.01f, nullptr, 0, 0);
-    conv(r, m.up1, u0, n, gh, gw, nf, u1, nf, 0, 1, 1, 1, ACT_LRELU, 0.2f, nullptr, 0, 0);
-    conv(r, m.up2, u1, n, 2 * gh, 2 * gw, nf, u2, nf, 0, 1, 1, 1, ACT_LRELU, 0.2f, nullptr, 0, 0);
-    conv(r, m.up3, u2, n, 4 * gh, 4 * gw, nf, u3, nf, 0, 1, 1, 1, ACT_LRELU, 0.2f, nullptr, 0, 0);
-    conv(r, m.hr, u3, n, h, w, nf, u4, nf, 0, 1, 1, 0, ACT_LRELU, 0.2f, nullptr, 0, 0);
-    // conv_last with x/img_range + mean folded into its weights (swinir.py:896,903)
-    // from 1024 x 1024 pixels up: below that the launch is 30 us either way, and the stress fixtures at 512 x 512 - whose PSNR against the oracle moves
-    // by +- 0.7 dB with the summation ORDER of any one conv on the way (profiles/r06_stress_sensitivity.txt) - keep the numbers they were calibrated on
-    if (!r.c->plain && nf == 64 && m.last.cin == 64 && m.last.cout_pad == 32 && m.last.taps == 9 && (long)h * w >= 1024L * 1024) {
-        const double px = (double)n * h * w;
-        LAUNCHK(r, PK_CONV_TO3, 2.0 * px * 3 * 9 * 64, px * (64 * 2 + 16), ir_launch_conv64_to3(u4, m.last.w, m.last.b, o4, n, h, w, r.s), "swin_conv_last");
-    } else {
-        conv(r, m.last, u4, n, h, w, nf, o4, 4, 1, 1, 1, 0, ACT_NONE, 0.f, nullptr, 0, 0);
-    }
-    LAUNCH(r, PC_OTHER, 0.0, 0.0, ir_launch_nhwc_to_nchw(o4, 4, out, n, 3, (long)h * w, 1.f, 0.f, 0, r.s), "nhwc_to_nchw");
+    swin_recon(r, xa, x0, xn, att, out, n, h, w);
     r.a.release(mk);
 }
 
@@ -2359,6 +2376,51 @@ int ir_op_vae_segment(ir_ctx* c, void* stream, int half, int first, int count, c
     if (!x || !y) return fail(c, -1, "ir_op_vae_segment: no input or output tensor");
     Run r = make_run(c, stream, ws, ws_bytes, false);
     if (int e = segment_run(c, r, half, first, count, x, y, n, h, w)) return e;
+    return finish(r, c, ws_bytes);
+}
+
+// ---- one part of the SwinIR shell around the blocks for op-level tests (see the header): the caller's tensors ARE x0 / xa / xc, the rest is arena
+static void swin_shell_run(ir_ctx* c, Run& r, int part, int layer, const void* in0, const void* in1, void* out0, void* out1, int n, int h, int w) {
+    const SwinModel& m = c->swin;
+    const int gh = h / 8, gw = w / 8, Cp = m.Cp;
+    const long T = (long)n * gh * gw;
+    const size_t mk = r.a.mark();
+    if (part == IR_SWIN_SHELL_HEAD) {
+        bf16_t* f0 = r.a.alloc<bf16_t>(T * 192);
+        swin_head(r, (const float*)in0, f0, (float*)out0, (float*)out1, n, h, w);
+    } else if (part == IR_SWIN_SHELL_RSTB_TAIL) {
+        swin_rstb_tail(r, m.layers[layer], (const bf16_t*)in0, (float*)out0, n, gh, gw);
+    } else {
+        bf16_t* xn = r.a.alloc<bf16_t>(T * Cp);
+        bf16_t* att = r.a.alloc<bf16_t>(T * Cp);
+        swin_recon(r, (const float*)in0, (const float*)in1, xn, att, (float*)out0, n, h, w);
+    }
+    r.a.release(mk);
+}
+static int swin_shell_check(ir_ctx* c, int part, int layer, int n, int h, int w) {
+    if (!c) return -11;
+    if (part != IR_SWIN_SHELL_HEAD && part != IR_SWIN_SHELL_RSTB_TAIL && part != IR_SWIN_SHELL_RECON)
+        return fail(c, -1, "ir_op_swin_shell: part %d (0 head, 1 RSTB tail, 2 reconstruction)", part);
+    if (!c->swin.ok) return fail(c, -11, "ir_op_swin_shell: SwinIR not configured");
+    if (part == IR_SWIN_SHELL_RSTB_TAIL && (layer < 0 || layer >= (int)c->swin.layers.size()))
+        return fail(c, -1, "ir_op_swin_shell: layer %d outside 0 .. %d", layer, (int)c->swin.layers.size() - 1);
+    return check_size(c, n, h, w, 64);
+}
+size_t ir_op_swin_shell_ws(ir_ctx* c, int part, int n, int h, int w) {
+    if (swin_shell_check(c, part, 0, n, h, w)) return 0;
+    Run r = make_run(c, nullptr, nullptr, 0, true);
+    swin_shell_run(c, r, part, 0, nullptr, nullptr, nullptr, nullptr, n, h, w);
+    return r.a.peak + 4096;
+}
+int ir_op_swin_shell(ir_ctx* c, void* stream, int part, int layer, const void* in0, const void* in1, void* out0, void* out1, int n, int h, int w,
+                     void* ws, size_t ws_bytes) {
+    if (int e = swin_shell_check(c, part, layer, n, h, w)) return e;
+    if (!in0 || !out0 || (part == IR_SWIN_SHELL_HEAD && !out1) || (part == IR_SWIN_SHELL_RECON && !in1))
+        return fail(c, -1, "ir_op_swin_shell: a tensor of part %d is missing", part);
+    const size_t need = ir_op_swin_shell_ws(c, part, n, h, w);   // refused as a whole: a part must not stop half way through its launches
+    if (!ws || ws_bytes < need) return fail(c, -20, "workspace too small: need %zu bytes, got %zu", need, ws_bytes);
+    Run r = make_run(c, stream, ws, ws_bytes, false);
+    swin_shell_run(c, r, part, layer, in0, in1, out0, out1, n, h, w);
     return finish(r, c, ws_bytes);
 }
 

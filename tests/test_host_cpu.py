@@ -152,6 +152,17 @@ def test_vae_segment_entries_refuse_a_missing_context():
     assert lib.ir_op_vae_segment_ws(None, 1, 0, 1, 1, 8, 8) == 0
 
 
+def test_swin_shell_entries_refuse_a_missing_context():
+    """ir_op_swin_shell and its workspace query return -11 / a zero size without a context, before anything touches a device."""
+    from instarevive_amd import _lib
+    from instarevive_amd.build import build
+    build()
+    lib = _lib.load_library()
+    for part in (_lib.SWIN_SHELL_HEAD, _lib.SWIN_SHELL_RSTB_TAIL, _lib.SWIN_SHELL_RECON, 3):
+        assert lib.ir_op_swin_shell(None, None, part, 0, None, None, None, None, 1, 64, 64, None, 0) == -11
+        assert lib.ir_op_swin_shell_ws(None, part, 1, 64, 64) == 0
+
+
 def test_sliding_windows_and_loaders():
     from instarevive_amd.pipeline import _sliding_windows
     from instarevive_amd import utils
