@@ -45,6 +45,7 @@ def parse_args():
     ap.add_argument("--device", default="cuda")
     ap.add_argument("--png_encoder", default="host", choices=["host", "gpu"], help="who compresses the PNGs of both output folders: the host (PIL, default) or "
                     "the GPU behind the network (inference.py --png_encoder: lossless, meant for photographs; flat content comes out larger than PIL's)")
+    cli.add_jpeg_flags(ap)   # --save_format jpg, --jpeg_quality, --jpeg_subsampling, --jpeg_encoder: as in inference.py, for both output folders
     ap.add_argument("--gt", default=None, help="score both output folders against ground truth on the GPU (inference.py --gt: PSNR-Y / SSIM-Y, the same lookup "
                     "rules); the ground truth is centre-cropped to --image_size like the input. Writes metrics.csv (metrics.rank<k>.csv with several ranks) into "
                     "--output and --cond_output and prints both averages")
@@ -68,9 +69,11 @@ def parse_args():
     return ap.parse_args()
 
 
-def out_name(folder, src_root, path):
+def out_name(folder, src_root, path, ext_out=".png"):
     rel = os.path.relpath(path, src_root)
     stem, ext = os.path.splitext(rel)
+    if ext_out == ".jpg":   # --save_format jpg: every file is a JPEG
+        return os.path.join(folder, stem + ".jpg")
     return os.path.join(folder, stem + ".png" if ext.lower() in (".jpg", ".jpeg") else rel)
 
 
@@ -80,6 +83,8 @@ def main():
     from instarevive_amd.prompts import Captions
     from instarevive_amd.utils import center_crop_arr, list_image_files
     args = parse_args()
+    cli.check_save_format(args)
+    ext_out = cli.save_ext(args)
     niqe_params = cli.load_niqe_params(args)
     clipiqa_model = cli.load_clipiqa_model(args)
     noref = bool(niqe_params) or clipiqa_model is not None
@@ -156,18 +161,27 @@ def main():
 
     def save(dst, img):
         os.makedirs(os.path.dirname(dst) or ".", exist_ok=True)
-        if isinstance(img, tuple):   # encoded on the GPU: (zlib stream, width, height), framed here on the writer thread
+        if isinstance(img, tuple):   # encoded on the GPU: (zlib stream, width, height) or a JPEG's six pieces, framed here on the writer thread
+            from instarevive_amd.jpeg import wrap_jpeg
             from instarevive_amd.png import wrap_png
             with open(dst, "wb") as f:
-                f.write(wrap_png(*img))
+                f.write(wrap_png(*img) if len(img) == 3 else wrap_jpeg(*img))
+        elif dst.endswith(".jpg") and ext_out == ".jpg":
+            from instarevive_amd.jpeg import save_host, subsampling_of
+            save_host(Image.fromarray(np.ascontiguousarray(img)), dst, args.jpeg_quality, subsampling_of(args.jpeg_subsampling))
         else:
             Image.fromarray(np.ascontiguousarray(img)).save(dst)
 
+    gpu_jpg = ext_out == ".jpg" and args.jpeg_encoder == "gpu"
+    whole = [[(args.image_size, args.image_size)] * len(group) for group in batches]
+    if ext_out == ".jpg" and (args.gt or noref):
+        print(f"[rank {rank}] --save_format jpg: the scores are those of the device's image, the result BEFORE the JPEG loss")
     gpu_png = args.png_encoder == "gpu"   # every image is a whole image_size crop: nothing to un-pad, every file is eligible
 
     results = process_stream(m.model, feed(), "none", args.disable_preprocess_model, False, 512, 448, preprocess_model=m.preprocess_model, vae=m.vae,
                              y=m.y, y_mask=m.y_mask, noise_scheduler=m.noise_scheduler, return_stage1=True,
-                             png=[[(args.image_size, args.image_size)] * len(group) for group in batches] if gpu_png else None, png_wrap=False,
+                             png=whole if gpu_png else None, png_wrap=False,
+                             **({"jpeg": whole, "jpeg_quality": args.jpeg_quality, "jpeg_subsampling": args.jpeg_subsampling} if gpu_jpg else {}),
                              gt=cli.in_step(truths) if lookup else None, **with_lpips, **({"niqe": niqe_params} if niqe_params else {}),
                              **({"clipiqa": True} if clipiqa_model else {}),
                              **({"resize": cli.in_step(records), "degrade": cli.in_step(dparams), "lq_sink": lq_images.append if args.save_lq else None} if recipe else {}))
@@ -181,10 +195,10 @@ def main():
                     if missing:
                         no_score[missing] += 1
                     else:
-                        rep.add_scores(os.path.relpath(out_name(folder, args.input, f), folder), score)
+                        rep.add_scores(os.path.relpath(out_name(folder, args.input, f, ext_out), folder), score)
         for f, pred, cond in zip(group, preds, stage1):
             for folder, img in ((args.output, pred), (cond_dir, cond)):
-                pools.write_behind(save, out_name(folder, args.input, f), img)
+                pools.write_behind(save, out_name(folder, args.input, f, ext_out), img)
         if args.save_lq:
             for f, lq in zip(group, lq_images.pop(0)):
                 pools.write_behind(save, os.path.splitext(os.path.join(args.save_lq, os.path.relpath(f, args.input)))[0] + ".png", lq)
@@ -194,6 +208,8 @@ def main():
     print(f"[rank {rank}] saved {pools.written} files")
     if gpu_png:
         print(f"[rank {rank}] --png_encoder gpu: 0 of {pools.written} files took the host encoder")
+    if gpu_jpg:
+        print(f"[rank {rank}] --jpeg_encoder gpu: {pools.written} of {pools.written} files were coded on the device, 0 took the host encoder")
     if reports:
         for rep, folder in zip(reports, (args.output, cond_dir)):
             lines = rep.write()

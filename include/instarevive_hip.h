@@ -36,7 +36,9 @@ enum { IR_STAGE_SWINIR = 0, IR_STAGE_VAE_ENCODE = 1, IR_STAGE_DIT = 2, IR_STAGE_
        IR_STAGE_DEGRADE = 16 /* ir_degrade: h, w = the image size; the images of a batch share one workspace, so n only has to be >= 1; depends
                                 on the size alone (ctx may be NULL) */,
        IR_STAGE_DEGRADE_CHAIN = 17 /* ir_degrade_chain: h, w = the image size, and in place of flags and tile_size the largest height and the
-                                      largest width among the chains' intermediate images; n only has to be >= 1 (ctx may be NULL) */ };
+                                      largest width among the chains' intermediate images; n only has to be >= 1 (ctx may be NULL) */,
+       IR_STAGE_JPEG = 18   /* n images, h, w = the VALID rectangle; depends on the sizes alone (ctx may be NULL); flags = subsampling,
+                               tile_size = restart_mcus (one slot per restart interval) */ };
 /* ir_pipeline flags */
 enum { IR_FLAG_NO_PREPROCESS = 1, IR_FLAG_TILED = 2, IR_FLAG_FIX_WAVELET = 4, IR_FLAG_FIX_ADAIN = 8,
        /* ir_pipeline only, needs ir_dit_control_configure: run the DiT step with the ControlNet-Half branch, condition latent
@@ -288,6 +290,27 @@ int ir_nchw_to_u8(ir_ctx* ctx, void* stream, const float* in, uint8_t* out, int 
 size_t ir_png_bound(int h, int w);
 int ir_png_encode(ir_ctx* ctx, void* stream, const uint8_t* img, int n, int h, int w, long pitch, int vh, int vw, uint8_t* out, size_t out_stride,
                   uint32_t* info, void* ws, size_t ws_bytes);
+
+/* Baseline JPEG encoding of results on the device (no reference counterpart: the reference saves PNGs through PIL). Encodes the valid
+ * rectangle vh x vw (1 <= vh <= h, 1 <= vw <= w) of n RGB8 images img [n][h][pitch] - ir_png_encode's layout - into one entropy-coded segment
+ * per image at out + i * out_stride: what lies between the SOS header and EOI of a baseline JPEG with one interleaved scan, the standard (Annex K)
+ * Huffman tables and a restart interval of restart_mcus MCUs, restart markers included. The host adds SOI, APP0, DQT, SOF0, DHT, DRI, SOS and EOI
+ * (instarevive_amd.jpeg.wrap_jpeg). info[i] = the segment's byte count. The bytes are libjpeg's: the file equals PIL's Image.save(format="JPEG",
+ * quality, subsampling, restart_marker_blocks=restart_mcus) (definition: tools/jpeg_encode_model.py).
+ * quality 1 .. 100 (jpeg_set_quality's tables, baseline); subsampling in PIL's numbers, 0 = 4:4:4 (MCU 8 x 8) or 2 = 4:2:0 (MCU 16 x 16);
+ * restart_mcus 1 .. 65535, in raster order of the MCUs.
+ * ir_jpeg_bound(h, w, subsampling, restart_mcus): capacity that holds the segment of ANY h x w pixels at any quality - per 8 x 8 block 20 bits of
+ * DC and 63 x 26 bits of AC, doubled for byte stuffing, plus the markers; 0 for arguments the encoder refuses (sides above 65535 among them).
+ * out_stride must be at least ir_jpeg_bound(vh, vw, ...). Bytes of a slot behind the segment's end are not written. All pointers are device
+ * pointers; stream-ordered, no allocation, no host synchronisation (capturable). ws: 16-byte aligned,
+ * ir_workspace_bytes(ctx, IR_STAGE_JPEG, n, vh, vw, subsampling, restart_mcus, 0) bytes (the int16 coefficients and one slot per restart interval).
+ * Returns -1 (nothing launched) for a null pointer, a rectangle outside 1..h / 1..w, a pitch below 3 w, quality outside 1..100, a subsampling
+ * other than 0 or 2, restart_mcus outside 1..65535, more than 65535 images, a bound beyond 2^32 - 1, an out_stride below the bound or a short
+ * or misaligned workspace. */
+size_t ir_jpeg_bound(int h, int w, int subsampling, int restart_mcus);
+int ir_jpeg_encode(ir_ctx* ctx, void* stream, const uint8_t* img, int n, int h, int w, long pitch, int vh, int vw,
+                   int quality, int subsampling, int restart_mcus, uint8_t* out, size_t out_stride, uint32_t* info,
+                   void* ws, size_t ws_bytes);
 
 /* Pillow's resampling of 8-bit RGB images on the device (PIL.Image.resize with BICUBIC / LANCZOS, Resample.c): what the command line does to
  * every input (--sr_scale, auto_resize: inference.py:263-291) and to the results of enlarged inputs (LANCZOS back to the LQ size, :323-346).

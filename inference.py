@@ -4,7 +4,7 @@
     python inference.py --ckpt weights/InstaRevive_v1.ckpt --input DIR --output DIR [--sr_scale F] [--tiled
         --tile_size 512 --tile_stride 448] [--color_fix_type wavelet|adain|none] [--disable_preprocess_model] ...
 
-Same flags, defaults, file naming (`<stem>_<i>.png` under the input's relative path) and artefacts:
+Same flags, defaults, file naming (`<stem>_<i>.png` under the input's relative path; `.jpg` with --save_format jpg) and artefacts:
   * DiT:      flat state dict in diffusers Transformer2DModel key layout  (--ckpt; the reference parses --ckpt but
               hard-codes ./weights/InstaRevive_v1.ckpt, inference.py:239-240 — here --ckpt is honoured)
   * SwinIR:   ./weights/general_swinir_v1.ckpt with ./configs/swinir.yaml     (override: --swinir_ckpt / --swinir_config)
@@ -89,6 +89,7 @@ def parse_args() -> Namespace:
                         "smaller than --png_compress_level 1 and within a few percent of the default level; flat or near-flat content (smooth sky, graphics) comes "
                         "out several times larger than PIL's, since a byte never costs less than one bit. Files that are not a plain crop of the prediction "
                         "(--show_lq; inputs that auto_resize enlarged, unless --resize gpu resizes their results on the device) still take the host encoder; the run says how many")
+    add_jpeg_flags(parser)
     parser.add_argument("--resize", type=str, default="host", choices=["host", "gpu"], help="who resizes the inputs (--sr_scale and the enlargement of short edges "
                         "below 512 / the tile size, both bicubic) and the results of enlarged inputs (LANCZOS back to the input's size). host (default): PIL on the "
                         "reader / writer threads, as the reference does. gpu: the decoded file is uploaded as it is and the device resamples it with Pillow's own "
@@ -134,6 +135,43 @@ def parse_args() -> Namespace:
     parser.add_argument("--workers", type=int, default=-1, help="host threads that decode / resize the inputs and resize / PNG-encode the results "
                         "around the GPU (PIL releases the GIL there); -1 = this process's CPU share, 0 = everything on the main thread like the reference")
     return parser.parse_args()
+
+
+def add_jpeg_flags(parser) -> None:
+    """--save_format and the --jpeg_* flags (eval_batch.py takes the same ones). The --jpeg_* defaults are None until check_save_format() has
+    seen whether they were given."""
+    parser.add_argument("--save_format", type=str, default="png", choices=["png", "jpg"], help="the format of the saved results. png (default): lossless, what the "
+                        "reference writes. jpg: baseline JPEG (standard Huffman tables, JFIF, no other metadata), the save path then ends in .jpg - a 2048 x 2048 "
+                        "result takes 1 - 2 MB instead of 8 - 12. Scoring (--gt, --niqe_params, --clipiqa_model) still reads the device's image, the result "
+                        "BEFORE the JPEG loss")
+    parser.add_argument("--jpeg_quality", type=int, default=None, metavar="1..100", help="with --save_format jpg: libjpeg's quality (default 95)")
+    parser.add_argument("--jpeg_subsampling", type=str, default=None, choices=["420", "444"], help="with --save_format jpg: chroma subsampling, 420 (default) or 444")
+    parser.add_argument("--jpeg_encoder", type=str, default=None, choices=["host", "gpu"], help="with --save_format jpg: who codes the files. host (default): PIL / "
+                        "libjpeg on the writer threads. gpu: the device codes the result behind the network (ir_jpeg_encode) and only the coded bytes cross PCIe. "
+                        "The files are the same bytes either way. Files whose saved image is not the device's image (--show_lq; inputs that auto_resize "
+                        "enlarged, unless --resize gpu resizes their results on the device; --use_center_crop next to --tiled; --shard_tiles) take the host "
+                        "encoder; the run says how many")
+
+
+def check_save_format(args: Namespace) -> None:
+    """The refusals around --save_format, one line each, and the --jpeg_* defaults; before anything is loaded."""
+    given = [f"--{k}" for k in ("jpeg_quality", "jpeg_subsampling", "jpeg_encoder") if getattr(args, k, None) is not None]
+    if args.save_format != "jpg":
+        if given:
+            raise SystemExit(f"{' / '.join(given)} set how JPEGs are written: give --save_format jpg as well")
+        args.jpeg_encoder = "host"
+        return
+    if getattr(args, "png_encoder", "host") == "gpu" or getattr(args, "png_compress_level", None) is not None:
+        raise SystemExit("--png_encoder gpu / --png_compress_level set how PNGs are written: not offered together with --save_format jpg")
+    args.jpeg_quality = 95 if args.jpeg_quality is None else args.jpeg_quality
+    if not 1 <= args.jpeg_quality <= 100:
+        raise SystemExit(f"--jpeg_quality {args.jpeg_quality} is outside 1 .. 100")
+    args.jpeg_subsampling = args.jpeg_subsampling or "420"
+    args.jpeg_encoder = args.jpeg_encoder or "host"
+
+
+def save_ext(args: Namespace) -> str:
+    return ".jpg" if getattr(args, "save_format", "png") == "jpg" else ".png"
 
 
 def cpu_share() -> int:
@@ -284,7 +322,7 @@ def decode_job(file_path: str, repeat: int, args: Namespace) -> Job:
         from instarevive_amd.resample import job_geometry
         geo = job_geometry(lq.size, args.sr_scale, args.tiled, args.tile_size)
         folder, stem, _ = get_file_name_parts(os.path.join(args.output, os.path.relpath(file_path, args.input)))
-        job = Job(os.path.join(folder, f"{stem}_{repeat}.png"), lq, None, geo.valid_hw, file_path, geo, np.array(lq))
+        job = Job(os.path.join(folder, f"{stem}_{repeat}{save_ext(args)}"), lq, None, geo.valid_hw, file_path, geo, np.array(lq))
         if getattr(args, "degrade_recipe", None):   # the draws (and the noise field) are made here, on a reader thread
             from instarevive_amd.degrade import draw
             job.deg = draw(args.degrade_recipe, os.path.relpath(file_path, args.input), lq.height, lq.width, args.degrade_seed)
@@ -299,7 +337,7 @@ def decode_job(file_path: str, repeat: int, args: Namespace) -> Job:
     # --use_center_crop switches the un-padding / resize-back of the result off, also next to --tiled (inference.py:326-346)
     valid = () if args.use_center_crop else (fitted.height, fitted.width)
     folder, stem, _ = get_file_name_parts(os.path.join(args.output, os.path.relpath(file_path, args.input)))
-    return Job(os.path.join(folder, f"{stem}_{repeat}.png"), lq, net_in, valid, file_path)
+    return Job(os.path.join(folder, f"{stem}_{repeat}{save_ext(args)}"), lq, net_in, valid, file_path)
 
 
 def png_rect(job: Job, args: Namespace):
@@ -319,11 +357,14 @@ def png_rect(job: Job, args: Namespace):
 
 
 def write_png_file(job: Job, blob) -> None:
-    """write_job() for a result the GPU has encoded already: a PNG file, or the (zlib stream, width, height) triple process_stream(png_wrap=False)
-    yields, framed here - on a writer thread - into one."""
-    if not isinstance(blob, bytes):
+    """write_job() for a result the GPU has encoded already: a PNG or JPEG file, or what process_stream(png_wrap=False) yields - the (zlib stream,
+    width, height) triple of a PNG, the six pieces of a JPEG - framed here, on a writer thread, into one."""
+    if not isinstance(blob, bytes) and len(blob) == 3:
         from instarevive_amd.png import wrap_png
         blob = wrap_png(*blob)
+    elif not isinstance(blob, bytes):
+        from instarevive_amd.jpeg import wrap_jpeg
+        blob = wrap_jpeg(*blob)
     os.makedirs(os.path.dirname(job.save_path) or ".", exist_ok=True)
     with open(job.save_path, "wb") as f:
         f.write(blob)
@@ -353,7 +394,10 @@ def write_job(job: Job, pred: np.ndarray, stage1_pred, args: Namespace) -> None:
             panels.append(back_to_lq(stage1_pred))
         result = np.concatenate(panels + [result], axis=1)
     lvl = getattr(args, "png_compress_level", None)
-    if lvl is None:
+    if getattr(args, "save_format", "png") == "jpg":   # the parameters that make PIL's file the device encoder's
+        from instarevive_amd.jpeg import save_host, subsampling_of
+        save_host(Image.fromarray(result), job.save_path, args.jpeg_quality, subsampling_of(args.jpeg_subsampling))
+    elif lvl is None:
         Image.fromarray(result).save(job.save_path)
     else:
         Image.fromarray(result).save(job.save_path, compress_level=lvl)
@@ -464,6 +508,7 @@ def main() -> None:
     from instarevive_amd.pipeline import HipTileEngine, process_stream
     from instarevive_amd.utils import list_image_files
     args = parse_args()
+    check_save_format(args)
     niqe_params = load_niqe_params(args)
     clipiqa_model = load_clipiqa_model(args)
     noref = bool(niqe_params) or clipiqa_model is not None
@@ -530,13 +575,18 @@ def main() -> None:
         sys.setswitchinterval(float(os.environ["IR_SWITCH_INTERVAL"]))
     pools = HostPools(default_workers(local_world) if args.workers < 0 else args.workers)
     gpu_png = args.png_encoder == "gpu"
+    jpg = args.save_format == "jpg"
+    gpu_jpg = jpg and args.jpeg_encoder == "gpu"
+    on_gpu = gpu_png or gpu_jpg   # the files whose saved image is the device's image are coded there
+    if jpg and report:
+        print(f"[rank {rank}] --save_format jpg: the scores are those of the device's image, the result BEFORE the JPEG loss")
     args.resize_on_gpu = args.resize == "gpu"
     for flag, why in (("show_lq", "its strip needs the enlarged LQ panel on the host"), ("use_center_crop", "the centre crop halves with a BOX filter"),
                       ("shard_tiles", "the tile-sharded path takes host-prepared images")):
         if args.resize_on_gpu and getattr(args, flag):
             print(f"[rank {rank}] --resize gpu: --{flag} keeps the resizes on the host ({why})")
             args.resize_on_gpu = False
-    note = host_keeps_up(pools.workers, int(512 * 512 * max(args.sr_scale, 1.0) ** 2), args.png_compress_level, args.png_encoder)   # priced on a 512 x 512 LQ file at this --sr_scale
+    note = "" if jpg else host_keeps_up(pools.workers, int(512 * 512 * max(args.sr_scale, 1.0) ** 2), args.png_compress_level, args.png_encoder)   # priced on a 512 x 512 LQ file at this --sr_scale
     if note:
         print(f"[rank {rank}] {note}")
     if not os.path.isdir(args.input):
@@ -573,6 +623,8 @@ def main() -> None:
         pools.drain()
         if gpu_png and rank == 0:
             print(f"[rank {rank}] --png_encoder gpu: {host_files} of {pools.written} files took the host encoder (not a plain crop of the prediction)")
+        if gpu_jpg and rank == 0:
+            print(f"[rank {rank}] --jpeg_encoder gpu: 0 of {pools.written} files were coded on the device (--shard_tiles keeps the host encoder, the same bytes)")
         return
     mine = parallel.shard(files, rank, world)       # images are independent: no collective on the data path
     t0 = time.perf_counter()
@@ -586,14 +638,14 @@ def main() -> None:
     lq_images = deque()   # --save_lq, per batch: the LQ images process_stream hands over right before the batch's results
 
     def feed():
-        for group in batches_of(jobs, max(args.batch_size, 1), (lambda j: png_rect(j, args) is not None) if gpu_png or report else None):
+        for group in batches_of(jobs, max(args.batch_size, 1), (lambda j: png_rect(j, args) is not None) if on_gpu or report else None):
             todo.append(group)
             if args.gt:
                 truths.append([j.gt for j in group] if all(j.gt is not None for j in group) else None)
             if noref:
                 rr = [png_rect(j, args) for j in group]
                 sizes.append(rr if all(rr) else None)
-            if gpu_png:
+            if on_gpu:
                 rr = [png_rect(j, args) for j in group]
                 rects.append(rr if all(rr) else None)
             imgs = [j.net_in for j in group]
@@ -609,6 +661,7 @@ def main() -> None:
     no_score = {"niqe": 0, "clipiqa": 0}   # files below 96 pixels on an edge or without two complete feature rows; files below 32 pixels on an edge
     for out in process_stream(m.model, feed(), tiled=args.tiled, return_stage1=args.show_lq and not args.disable_preprocess_model,
                               fp8=args.fp8 != "off", png=in_step(rects) if gpu_png else None, png_wrap=False,
+                              **({"jpeg": in_step(rects), "jpeg_quality": args.jpeg_quality, "jpeg_subsampling": args.jpeg_subsampling} if gpu_jpg else {}),
                               resize=in_step(records) if args.resize_on_gpu else None, gt=in_step(truths) if args.gt else None,
                               **({"lpips": True} if report and report.lpips else {}),
                               **({"niqe": niqe_params} if niqe_params else {}), **({"clipiqa": True} if clipiqa_model else {}),
@@ -637,12 +690,15 @@ def main() -> None:
             if isinstance(preds[k], tuple):   # encoded on the GPU; the writer thread frames it
                 pools.write_behind(write_png_file, job, preds[k])
             else:
-                host_files += gpu_png
+                host_files += on_gpu
                 pools.write_behind(write_job, job, preds[k], stage1[k] if stage1 else None, args)
     pools.drain()
     t1 = time.perf_counter()
     if gpu_png:
         print(f"[rank {rank}] --png_encoder gpu: {host_files} of {pools.written} files took the host encoder (not a plain crop of the prediction)")
+    if gpu_jpg:
+        print(f"[rank {rank}] --jpeg_encoder gpu: {pools.written - host_files} of {pools.written} files were coded on the device, {host_files} took the host "
+              f"encoder (their saved image is not the device's image; the same bytes)")
     if report:
         lines = report.write()
         what = " / ".join(f for f, on in (("--gt", args.gt), ("--niqe_params", niqe_params), ("--clipiqa_model", clipiqa_model)) if on)

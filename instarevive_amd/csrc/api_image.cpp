@@ -1,4 +1,4 @@
-// The image tools of the C ABI: PNG encoding, Pillow's resampling, PSNR-Y / SSIM-Y, LPIPS, CLIP-IQA, NIQE and the two degradation paths. Each entry
+// The image tools of the C ABI: PNG and JPEG encoding, Pillow's resampling, PSNR-Y / SSIM-Y, LPIPS, CLIP-IQA, NIQE and the two degradation paths. Each entry
 // point checks its arguments and launches the kernels of its own .hip file; none of them runs a model stage, takes the workspace arena or is
 // profiled, so nothing here knows api.cpp's Run. Host code only, except for the tables the kernels read, which are computed here once.
 #include <math.h>
@@ -123,6 +123,27 @@ int ir_png_encode(ir_ctx* c, void* stream, const uint8_t* img, int n, int h, int
     if (ir_launch_png_encode(img, n, h, pitch, vh, vw, out, out_stride, info, (uint32_t*)(b + L.hist), (uint32_t*)(b + L.codes), (uint32_t*)(b + L.header),
                              (uint32_t*)(b + L.sizes), (uint8_t*)(b + L.slots), (long)L.slot_cap, (hipStream_t)stream))
         return fail(c, -100, "ir_png_encode: launch failed");
+    return 0;
+}
+
+// ---------------------------------------------------------------- JPEG encoding (jpeg_encode.hip)
+size_t ir_jpeg_bound(int h, int w, int subsampling, int restart_mcus) { return ir_jpeg_bound_host(h, w, subsampling, restart_mcus); }
+int ir_jpeg_encode(ir_ctx* c, void* stream, const uint8_t* img, int n, int h, int w, long pitch, int vh, int vw, int quality, int subsampling,
+                   int restart_mcus, uint8_t* out, size_t out_stride, uint32_t* info, void* ws, size_t ws_bytes) {
+    if (!c || !img || !out || !info || !ws) return fail(c, -1, "ir_jpeg_encode: null argument");
+    if (int e = check_rect(c, "ir_jpeg_encode", nullptr, n, vh, vw, 1, {{h, pitch}}, h < 1 || w < 1 || vw > w || pitch < 3L * w)) return e;
+    if (quality < 1 || quality > 100) return fail(c, -1, "ir_jpeg_encode: quality %d outside 1 .. 100", quality);
+    if (subsampling != 0 && subsampling != 2) return fail(c, -1, "ir_jpeg_encode: subsampling %d is neither 0 (4:4:4) nor 2 (4:2:0)", subsampling);
+    if (restart_mcus < 1 || restart_mcus > 65535) return fail(c, -1, "ir_jpeg_encode: restart interval %d outside 1 .. 65535 MCUs", restart_mcus);
+    IrJpegLayout L;
+    if (!ir_jpeg_layout(n, vh, vw, subsampling, restart_mcus, &L))
+        return fail(c, -1, "ir_jpeg_encode: n %d of %d x %d is more than one call takes (sides and images up to 65535, 2^32 - 1 bytes per image)", n, vh, vw);
+    const size_t bound = ir_jpeg_bound_host(vh, vw, subsampling, restart_mcus);
+    if (out_stride < bound) return fail(c, -1, "ir_jpeg_encode: out_stride %zu below ir_jpeg_bound(%d, %d, %d, %d) = %zu", out_stride, vh, vw, subsampling, restart_mcus, bound);
+    if (int e = check_ws(c, "ir_jpeg_encode", ws, ws_bytes, L.total, 16)) return e;
+    use_ctx(c);
+    if (ir_launch_jpeg_encode(img, n, h, pitch, vh, vw, quality, subsampling, restart_mcus, out, out_stride, info, ws, (hipStream_t)stream))
+        return fail(c, -100, "ir_jpeg_encode: launch failed");
     return 0;
 }
 
@@ -561,6 +582,7 @@ bool ir_host::image_workspace(ir_ctx* c, int stage, int n, int h, int w, int fla
     const bool some = n >= 1 && h >= 1 && w >= 1;
     IrClipiqaPlan cp;
     IrLpipsPlan lp;
+    IrJpegLayout jl;
     *bytes = 0;
     switch (stage) {
         case IR_STAGE_DEGRADE_CHAIN: if (n >= 1) *bytes = ir_degrade_chain_workspace(h, w, flags, tile_size); break;   // flags, tile_size: the largest intermediate image
@@ -569,6 +591,7 @@ bool ir_host::image_workspace(ir_ctx* c, int stage, int n, int h, int w, int fla
         case IR_STAGE_CLIPIQA: if (c && c->clipiqa.ok && !ir_clipiqa_plan(c->clipiqa, n, h, w, &cp)) *bytes = cp.total; break;
         case IR_STAGE_LPIPS: if (!ir_lpips_plan(n, h, w, &lp)) *bytes = lp.total; break;
         case IR_STAGE_METRICS: if (some) *bytes = metrics_workspace(n, h, w); break;
+        case IR_STAGE_JPEG: if (ir_jpeg_layout(n, h, w, flags, tile_size, &jl)) *bytes = jl.total; break;   // flags: the subsampling, tile_size: restart_mcus
         case IR_STAGE_PNG: if (some) *bytes = png_layout(n, h, w).total; break;
         case IR_STAGE_RESAMPLE: if (some) *bytes = rs_workspace(n, h, w); break;   // n images, h = in_h, w = out_w: the uint8 image between the passes
         default: return false;

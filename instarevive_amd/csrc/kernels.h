@@ -207,6 +207,22 @@ int ir_launch_t5_gated_gelu(const bf16_t* ab, bf16_t* out, long rows, int F, hip
 int ir_launch_png_encode(const uint8_t* img, int n, int h, long pitch, int vh, int vw, uint8_t* out, size_t out_stride, uint32_t* info,
                          uint32_t* hist, uint32_t* codes, uint32_t* header, uint32_t* chunk_bytes, uint8_t* slots, long slot_cap, hipStream_t s);
 
+// ---- JPEG encoding of uint8 results (jpeg_encode.hip)
+// jpeg_encode.hip: the entropy-coded segment of a baseline JPEG (standard Huffman tables, restart intervals of restart_mcus MCUs), libjpeg's bytes.
+// IR_JPEG_BLOCK_BITS: the most bits one 8 x 8 block can take, 20 for the DC difference (9-bit code + 11 value bits) and 26 for each of the 63 AC
+// coefficients (16-bit code + 10 value bits; a zero costs less than that through ZRL / EOB). ir_jpeg_bound_host: ir_jpeg_bound (0 for arguments
+// the encoder refuses). ir_jpeg_layout: the workspace of n images of vh x vw (byte offsets; false where the encoder refuses, also for a bound that
+// does not fit info's 32 bits): coef [n][MCUs][blocks per MCU][64] int16, raw / ffs / offsets [n * intervals] dwords, slots [n * intervals][slot_cap]
+// bytes. ir_launch_jpeg_encode takes that workspace, 16-byte aligned, and returns -1 with nothing launched for arguments it refuses.
+#define IR_JPEG_BLOCK_BITS (20 + 63 * 26)
+struct IrJpegLayout {
+    size_t intervals, slot_cap, coef, raw, ffs, offsets, slots, total;
+};
+size_t ir_jpeg_bound_host(int h, int w, int subsampling, int restart_mcus);
+bool ir_jpeg_layout(int n, int vh, int vw, int subsampling, int restart_mcus, IrJpegLayout* L);
+int ir_launch_jpeg_encode(const uint8_t* img, int n, int h, long pitch, int vh, int vw, int quality, int subsampling, int restart_mcus, uint8_t* out,
+                          size_t out_stride, uint32_t* info, void* ws, hipStream_t s);
+
 // ---- Pillow's 8-bit resampling of uint8 images (resample.hip)
 // The plan (ir_resample_plan) is an int32 array: a header of IR_RESAMPLE_HEADER ints - [0] IR_RESAMPLE_MAGIC, [1..4] in_h, in_w, out_h, out_w, [5] the
 // filter, [6] ksize_h, [7] ksize_v, [8] / [9] the offsets (in ints, from the plan's start) of the horizontal bounds [out_w][2] and coefficients

@@ -78,6 +78,32 @@ def _png_encoder(ctx, count, h, w, slot=0, tag="sync"):
     return pool[key]
 
 
+def _jpeg_encoder(ctx, codec, count, h, w, slot=0, tag="sync"):
+    """The JpegEncoder (jpeg.py) of a batch shape, (quality, subsampling) and staging slot, pooled on the context like the PNG encoders (a pool of
+    its own, at most 8 entries). Each entry holds count x ir_jpeg_bound bytes on the device and as much page-locked host memory: the bound is the
+    worst case of any pixels at any quality, about 41 MB per 2048 x 2048 image in 4:2:0, of which a photograph at quality 95 fills 1 - 2 MB."""
+    from .jpeg import JpegEncoder
+    pool = ctx.__dict__.setdefault("_jpeg", {})
+    key = (tag, count, h, w, slot) + tuple(codec)
+    if key not in pool:
+        if len(pool) >= 8:
+            pool.pop(next(iter(pool)))
+        pool[key] = JpegEncoder(ctx, count, h, w, codec[0], codec[1])
+    return pool[key]
+
+
+def _jpeg_codec(png, jpeg, quality, subsampling):
+    """(quality, subsampling in PIL's numbers) of a call with jpeg=, None of one without; jpeg= and png= exclude each other."""
+    if jpeg is None:
+        return None
+    if png is not None:
+        raise ValueError("jpeg= and png= exclude each other: a result is saved in one format")
+    from .jpeg import check_params, subsampling_of
+    codec = (int(quality), subsampling_of(subsampling))
+    check_params(*codec)
+    return codec
+
+
 def _check_images(control_imgs):
     if len(control_imgs) == 0:
         raise ValueError("control_imgs is empty")
@@ -202,17 +228,18 @@ class _Batch:
     two streams and keeps the batch's events in `ready` (its uploads) and `done` (its downloads)."""
 
     def __init__(self, ctx, slot, tag, slots, shape, imgs, with_stage1, rects=None, records=None, dparams=None, gts=None, lpips=False, niqe=None,
-                 clipiqa=False, sizes=None, want_lq=False, prompts=(None, None)):
+                 clipiqa=False, sizes=None, want_lq=False, prompts=(None, None), codec=None):
         """The plan phase, host work only: every size is checked and every ground truth compared with its image's FINAL size, so a batch that
         does not fit raises ValueError before anything is launched for it; then the scorer slots are filled / planned - `scorers` holds them in
         the order of a score tuple: paired (metrics.ScoreSlot; with lpips it scores LPIPS as well, ir_lpips with the weights lpips.configure()
         bound to the context), NIQE with `niqe` its parameters, CLIP-IQA - and the images copied into page-locked memory: the staging input, or
         the decoded files (with their degrade parameters) into the ResizeSlot, whose bicubic chain then makes the staging input on the device.
-        sizes: the batch's niqe_rects entry."""
+        sizes: the batch's niqe_rects entry. codec: None - rects are coded as PNG - or _jpeg_codec()'s pair."""
         from .slots import final_sizes, record_sizes
         self.ctx, self.slot, self.tag, self.shape, self.with_stage1 = ctx, slot, tag, shape, with_stage1
         self.rects, self.records, self.dparams, self.prompts = rects, records, dparams, prompts
         self.want_lq = want_lq and dparams is not None
+        self.codec = codec
         self.enc = self.ready = self.done = None
         n, h, w = shape
         copies = 2 if with_stage1 else 1
@@ -241,9 +268,9 @@ class _Batch:
                 self.scorers[-1].plan(finals, copies)
         if rects is not None:
             if records is None and len(rects) != n:
-                raise ValueError(f"png: {len(rects)} rectangles for a batch of {n} images")
+                raise ValueError(f"{'png' if codec is None else 'jpeg'}: {len(rects)} rectangles for a batch of {n} images")
             if records is not None and [tuple(r) for r in rects] != record_sizes(records):
-                raise ValueError(f"png: the rectangles {list(rects)} of a resize batch are not its final sizes {record_sizes(records)}")
+                raise ValueError(f"{'png' if codec is None else 'jpeg'}: the rectangles {list(rects)} of a resize batch are not its final sizes {record_sizes(records)}")
         self.st = _Staging.get(ctx, n, h, w, slots=slots, tag=tag)
         self.rs = None
         if records is None:
@@ -265,8 +292,11 @@ class _Batch:
         resampling calls ahead of and behind the network, the scorers - BEFORE the pipeline's launch takes the workspace's address: a recorded
         graph is keyed by it."""
         n, h, w = self.shape
-        if self.rects is not None:
+        if self.rects is not None and self.codec is None:
             self.ctx.workspace(self.ctx.ws_bytes(L.STAGE_PNG, n, h, w))
+        elif self.rects is not None:
+            from .jpeg import RESTART_MCUS
+            self.ctx.workspace(self.ctx.ws_bytes(L.STAGE_JPEG, n, h, w, self.codec[1], RESTART_MCUS))
         if self.records is not None:
             from .resample import chain_ws_bytes
             self.ctx.workspace(chain_ws_bytes(self.records))
@@ -275,7 +305,7 @@ class _Batch:
 
     def launch(self, flags, tile_size, tile_stride, acp, sf):
         """The batch's device work on the current stream: [ir_degrade of the decoded files] -> the bicubic chain into the staging input ->
-        ir_pipeline -> LANCZOS of the valid rectangles back to the LQ sizes -> ir_png_encode of every image's final form -> every scorer's calls.
+        ir_pipeline -> LANCZOS of the valid rectangles back to the LQ sizes -> ir_png_encode / ir_jpeg_encode of every image's final form -> every scorer's calls.
         What stands behind ir_pipeline runs behind the replay of a recorded graph, outside the recording. `outs` lists the outputs the later
         phases walk: (first row, the network's output [n][h][w][3], per image its resized result [1][th][tw][3] or None for a plain crop - None
         for all without resize records), the predictions at rows 0 .. n - 1 and - with stage-1 output - the stage-1 images at n .. 2n - 1."""
@@ -291,7 +321,10 @@ class _Batch:
             rs.reserve_results(n, h, w, self.with_stage1)
         self.outs = [(first, out, rs.back_to_lq(self.records, out, first) if rs is not None else None) for first, out in outs]
         if self.rects is not None:   # the batch keeps its own reference to the encoder: the pool evicts after 8 shapes
-            self.enc = _png_encoder(ctx, len(outs) * n, h, w, slot, self.tag)
+            if self.codec is None:
+                self.enc = _png_encoder(ctx, len(outs) * n, h, w, slot, self.tag)
+            else:
+                self.enc = _jpeg_encoder(ctx, self.codec, len(outs) * n, h, w, slot, self.tag)
             for first, out, res in self.outs:
                 if res is None:
                     self.enc.queue(first, out, self.rects)
@@ -364,7 +397,7 @@ def process(model, control_imgs: List[np.ndarray], strength: float, color_fix_ty
             tile_size: int, tile_stride: int, preprocess_model=None, vae=None, y=None, y_mask=None, noise_scheduler=None,
             fused: bool = True, graph: bool = False, return_stage1: bool = True, fp8: bool = False, png=None,
             resize=None, gt=None, lpips: bool = False, niqe=None, niqe_rects=None, clipiqa: bool = False, degrade=None,
-            lq_sink=None) -> Tuple[List[np.ndarray], List[np.ndarray]]:
+            lq_sink=None, jpeg=None, jpeg_quality: int = 95, jpeg_subsampling=2) -> Tuple[List[np.ndarray], List[np.ndarray]]:
     """test_scripts/inference.py:55-166. control_imgs: list of HWC uint8 RGB arrays of equal size (multiples of 64).
     Returns (preds, stage1_preds) as lists of HWC uint8 arrays (stage1_preds is empty with return_stage1=False, which skips its
     conversion and download).
@@ -378,6 +411,10 @@ def process(model, control_imgs: List[np.ndarray], strength: float, color_fix_ty
     png (fused form only): a list of one valid rectangle (vh, vw) per image. The results are then encoded on the GPU (ir_png_encode queued behind
     ir_pipeline - under graph=True behind the graph's replay, not inside the recording) and both lists hold PNG files as `bytes` of the
     top-left vh x vw crops instead of arrays; only the compressed bytes are downloaded.
+    jpeg (fused form only; exclusive with png): the same list of rectangles, and the lists hold baseline JPEG files instead - ir_jpeg_encode at
+    jpeg_quality (1 .. 100) and jpeg_subsampling (2 or 420: 4:2:0, 0 or 444: 4:4:4), byte for byte PIL's Image.save(format="JPEG", quality,
+    subsampling, restart_marker_blocks=jpeg.RESTART_MCUS) of the raw result. It combines with resize, degrade, gt, niqe and clipiqa as png does;
+    the scores are those of the device's image, the result BEFORE the JPEG loss.
     resize (fused form only): a list of one resample.ResizeJob per image - the DECODED file and its job_geometry(). control_imgs is then not read:
     the decoded bytes are uploaded, ir_resample_u8 makes the network input on the device (the bicubic chain of --sr_scale / auto_resize, the
     zero pad), and behind ir_pipeline the valid rectangle of every image that auto_resize enlarged is resampled (LANCZOS) back to its LQ size.
@@ -409,7 +446,8 @@ def process(model, control_imgs: List[np.ndarray], strength: float, color_fix_ty
     if degrade is not None and resize is None:
         raise ValueError("process(degrade=...) needs resize=: the ground truth is degraded on the device input route")
     n, h, w = _batch_shape(control_imgs, resize)
-    if (png is not None or resize is not None or gt is not None or niqe is not None or clipiqa) and not (fused and _fused_ok(model, preprocess_model, vae, disable_preprocess_model)):
+    codec = _jpeg_codec(png, jpeg, jpeg_quality, jpeg_subsampling)
+    if (png is not None or jpeg is not None or resize is not None or gt is not None or niqe is not None or clipiqa) and not (fused and _fused_ok(model, preprocess_model, vae, disable_preprocess_model)):
         raise ValueError("process(png=... / resize=... / gt=... / niqe=...) needs the fused form (instarevive_amd models sharing one context)")
     device = model.device
     acp = float(noise_scheduler.alphas_cumprod[400])
@@ -420,8 +458,8 @@ def process(model, control_imgs: List[np.ndarray], strength: float, color_fix_ty
         if fp8 and not vae.__dict__.get("_fp8_uploaded"):
             raise RuntimeError("process(fp8=True): call vae.enable_fp8() first - without the fp8 weight forms every layer would silently run in bf16")
         ctx = model.ctx
-        batch = _Batch(ctx, 0, "sync", 1, (n, h, w), control_imgs, return_stage1, png, resize, degrade, gt, lpips, niqe, clipiqa, niqe_rects,
-                       lq_sink is not None)
+        batch = _Batch(ctx, 0, "sync", 1, (n, h, w), control_imgs, return_stage1, png if codec is None else jpeg, resize, degrade, gt, lpips, niqe,
+                       clipiqa, niqe_rects, lq_sink is not None, codec=codec)
         _prepare_fused(model, y, y_mask, h, w, tiled, tile_size, (vae, None if disable_preprocess_model else preprocess_model))
         flags = _pipeline_flags(model, color_fix_type, disable_preprocess_model, tiled) | (L.FLAG_GRAPH if graph else 0) | (L.FLAG_FP8 if fp8 else 0)
         batch.upload()
@@ -488,7 +526,8 @@ def process_stream(model, batches: Iterable[Sequence[np.ndarray]], color_fix_typ
                    tile_size: int, tile_stride: int, preprocess_model=None, vae=None, y=None, y_mask=None, noise_scheduler=None,
                    return_stage1: bool = True, graph: bool = False, fp8: bool = False, png=None,
                    png_wrap: bool = True, resize=None, gt=None, lpips: bool = False, niqe=None,
-                   niqe_rects=None, clipiqa: bool = False, degrade=None, lq_sink=None) -> Iterator[Tuple[List[np.ndarray], List[np.ndarray]]]:
+                   niqe_rects=None, clipiqa: bool = False, degrade=None, lq_sink=None, jpeg=None, jpeg_quality: int = 95,
+                   jpeg_subsampling=2) -> Iterator[Tuple[List[np.ndarray], List[np.ndarray]]]:
     """process() over a sequence of image batches with the transfers hidden: while batch i computes on the current stream, batch
     i+1 is uploaded and batch i-1 downloaded on a copy stream (two staging slots per batch shape). Yields process()'s result for
     every batch, in order. Needs the fused form (all models instarevive_amd objects on one context). fp8 as in process() (cfg-5:
@@ -503,6 +542,8 @@ def process_stream(model, batches: Iterable[Sequence[np.ndarray]], color_fix_typ
     batch's two lists hold PNG files (`bytes`, the top-left vh x vw crops) in place of arrays. The chunk framing (one CRC-32 over the compressed
     bytes and their copy into the file, about 20 ms per 2048 x 2048 result) is done on the calling thread between launches; png_wrap=False yields
     (zlib stream, width, height) triples instead, for png.wrap_png(*triple) on a thread of the caller's (what inference.py's writer pool does).
+    jpeg (exclusive with png): an iterable like png, and the files are JPEGs - ir_jpeg_encode at jpeg_quality / jpeg_subsampling, as in process().
+    With png_wrap=False the lists hold (segment, width, height, quality, subsampling, restart_mcus) pieces for jpeg.wrap_jpeg(*pieces).
     resize: an iterable in step with `batches`, advanced like png: per batch None, or one resample.ResizeJob per image (the decoded file and its
     job_geometry(); images that reach one network size share a batch whatever their own sizes). The batch's image list is then not read. The copy
     stream uploads the decoded bytes, the compute stream runs ir_resample_u8 once or twice per image into the staging input ahead of ir_pipeline
@@ -539,7 +580,8 @@ def process_stream(model, batches: Iterable[Sequence[np.ndarray]], color_fix_typ
     base_flags = _pipeline_flags(model, color_fix_type, disable_preprocess_model, tiled) | (L.FLAG_GRAPH if graph else 0) | (L.FLAG_FP8 if fp8 else 0)
     main, copy = torch.cuda.current_stream(device), ctx.__dict__.setdefault("_copy_stream", torch.cuda.Stream(device))
     it = iter(batches)
-    png_it = iter(png) if png is not None else None
+    codec = _jpeg_codec(png, jpeg, jpeg_quality, jpeg_subsampling)
+    png_it = iter(png) if png is not None else (iter(jpeg) if jpeg is not None else None)
     resize_it = iter(resize) if resize is not None else None
     degrade_it = iter(degrade) if degrade is not None else None
     if degrade_it is not None and resize_it is None:
@@ -561,7 +603,7 @@ def process_stream(model, batches: Iterable[Sequence[np.ndarray]], color_fix_typ
         with_nq = noref and (sizes is not None if nq_it is not None else (gts is not None or gt_it is None))
         imgs, by, bm = _split_batch(batch)
         b = _Batch(ctx, slot, "stream", 2, _batch_shape(imgs, records), imgs, return_stage1, rects, records, dparams, gts, lpips,
-                   niqe if with_nq else None, bool(clipiqa) and with_nq, sizes, lq_sink is not None, (by, bm))
+                   niqe if with_nq else None, bool(clipiqa) and with_nq, sizes, lq_sink is not None, (by, bm), codec=codec)
         with torch.cuda.stream(copy):
             b.ready = b.upload(copy, main)
         return b
