@@ -65,6 +65,8 @@ def parse_args():
                     "is the ground truth of --lpips_lin / --niqe_params / --clipiqa_model")
     ap.add_argument("--degrade_seed", type=int, default=231, help="with --degrade: seeds every file's draws together with the crc32 of its input-relative path")
     ap.add_argument("--save_lq", default=None, metavar="DIR", help="with --degrade: write the synthesised LQ crops to DIR")
+    ap.add_argument("--jpeg_decoder", default="host", choices=["host", "gpu"], help="inference.py's flag; only `host` here: every input is centre-cropped on the "
+                    "host (a BOX filter halves large files), which inference.py --jpeg_decoder gpu refuses as --use_center_crop")
     ap.add_argument("--workers", type=int, default=-1, help="host threads for decoding / PNG encoding (inference.py --workers)")
     return ap.parse_args()
 
@@ -84,6 +86,9 @@ def main():
     from instarevive_amd.utils import center_crop_arr, list_image_files
     args = parse_args()
     cli.check_save_format(args)
+    if args.jpeg_decoder == "gpu":
+        raise SystemExit("--jpeg_decoder gpu decodes into the device's resize route, and this tool centre-crops every input on the host (as inference.py "
+                         "--use_center_crop, where the flag is refused too): not offered")
     ext_out = cli.save_ext(args)
     niqe_params = cli.load_niqe_params(args)
     clipiqa_model = cli.load_clipiqa_model(args)

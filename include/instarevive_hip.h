@@ -38,7 +38,10 @@ enum { IR_STAGE_SWINIR = 0, IR_STAGE_VAE_ENCODE = 1, IR_STAGE_DIT = 2, IR_STAGE_
        IR_STAGE_DEGRADE_CHAIN = 17 /* ir_degrade_chain: h, w = the image size, and in place of flags and tile_size the largest height and the
                                       largest width among the chains' intermediate images; n only has to be >= 1 (ctx may be NULL) */,
        IR_STAGE_JPEG = 18   /* n images, h, w = the VALID rectangle; depends on the sizes alone (ctx may be NULL); flags = subsampling,
-                               tile_size = restart_mcus (one slot per restart interval) */ };
+                               tile_size = restart_mcus (one slot per restart interval) */,
+       IR_STAGE_JPEG_DECODE = 19 /* ir_jpeg_decode: h, w = the largest height and width among the files, flags = the largest stream_bytes,
+                                    tile_size = subseq_bits; holds for any sampling and restart interval; the files of a batch share one
+                                    workspace, so n only has to be >= 1; depends on these numbers alone (ctx may be NULL) */ };
 /* ir_pipeline flags */
 enum { IR_FLAG_NO_PREPROCESS = 1, IR_FLAG_TILED = 2, IR_FLAG_FIX_WAVELET = 4, IR_FLAG_FIX_ADAIN = 8,
        /* ir_pipeline only, needs ir_dit_control_configure: run the DiT step with the ControlNet-Half branch, condition latent
@@ -311,6 +314,50 @@ size_t ir_jpeg_bound(int h, int w, int subsampling, int restart_mcus);
 int ir_jpeg_encode(ir_ctx* ctx, void* stream, const uint8_t* img, int n, int h, int w, long pitch, int vh, int vw,
                    int quality, int subsampling, int restart_mcus, uint8_t* out, size_t out_stride, uint32_t* info,
                    void* ws, size_t ws_bytes);
+
+/* Baseline JPEG decoding on the device (the reference reads its inputs through PIL: Image.open(path).convert("RGB")). Decodes n files of
+ * differing sizes and sampling into HWC RGB8 images; the pixels are Pillow's (libjpeg-turbo's: Huffman decode, ISLOW inverse DCT, fancy
+ * upsampling, YCbCr -> RGB; definition: tools/jpeg_decode_model.py). The host parses the markers and removes the byte stuffing
+ * (instarevive_amd.jpeg_decode.JpegSource); the device does the rest. `files` is a HOST array of n records, read before the call returns, whose
+ * pointer members are device pointers:
+ *   stream        the scan's entropy-coded bytes with stuffing and RSTn markers removed, every restart interval starting on a 4-byte boundary
+ *                 (zero bytes between); stream_bytes of them, 4-byte aligned
+ *   intervals     [n_intervals][2] uint32: an interval's byte offset into stream (a multiple of 4) and its bit count (8 x its bytes, the
+ *                 padding bits of its last byte included); n_intervals = ceil(MCUs / restart_mcus), 1 for restart_mcus = 0 (no DRI)
+ *   tables        IR_JPEG_DECODE_TABLE_BYTES bytes, 4-byte aligned: the Huffman and quantisation tables in the kernels' format (private between
+ *                 jpeg_decode.py and jpeg_decode.hip)
+ *   out, pitch    the image [h][pitch] bytes, pitch >= 3 w; only the first 3 w bytes of each of the h rows are written
+ *   h, w          8 .. 65535 each (below 8 libjpeg replicates chroma instead of interpolating it)
+ *   comps, hs, vs 1 component (hs = vs = 1: a single-component scan has 8 x 8 MCUs whatever the file's factors say; R = G = B = Y), or 3 (YCbCr) with
+ *                 luma sampling hs x vs of 1 x 1, 2 x 1 or 2 x 2 and chroma 1 x 1
+ *   tq, td, ta    per component the quantisation table (0 .. 3) and the DC and AC Huffman tables (0 .. 1)
+ * The entropy decode runs in parallel on the serial stream: every subsequence of subseq_bits bits (a multiple of 32 in 128 .. 4096) of a restart
+ * interval is decoded from a guessed state, each takes its left neighbour's exit state as its entry state until nothing changes (a fixed number
+ * of parallel rounds, then one workgroup per interval iterates to the fixed point, so the result never depends on how fast a stream
+ * synchronises: the worst case is a serial walk of one interval), an exclusive scan of the blocks finished per subsequence places them, a second
+ * decode writes the coefficients, a segmented prefix sum turns the DC differences into values. info[i] = 0, or the error class of the first
+ * restart interval of file i that has one: 1 invalid Huffman code, 2 coefficient index past 63, 3 a read past the interval's bit count, 4 wrong
+ * block count for the interval; the pixels of such a file are unspecified (inside its image). Every read of the stream is guarded by the
+ * interval's bit count and by stream_bytes and every write by the sizes above, whatever the bytes say. coef_or_null, when not NULL, receives the
+ * int16 coefficients [blocks][64] in natural order, DC summed, blocks in scan order, file after file (a file has MCUs x (hs vs + 2) blocks, or
+ * MCUs for one component). Stream-ordered, no allocation, no host synchronisation; the number of launches depends on n alone. ws: 256-byte
+ * aligned, ir_workspace_bytes(ctx, IR_STAGE_JPEG_DECODE, n, max h, max w, max stream_bytes, subseq_bits, 0) bytes.
+ * Returns -1 (nothing launched) for a null pointer, n < 1, subseq_bits outside the above, a record with a size, sampling, table number,
+ * n_intervals, alignment or pitch outside the above, or a short or misaligned workspace. */
+#define IR_JPEG_DECODE_TABLE_BYTES 6176
+typedef struct ir_jpeg_file {
+    const uint8_t* stream;
+    const uint32_t* intervals;
+    const void* tables;
+    uint8_t* out;
+    long pitch;
+    uint32_t stream_bytes;
+    int n_intervals;
+    int h, w, comps, hs, vs, restart_mcus;
+    uint8_t tq[4], td[4], ta[4];
+} ir_jpeg_file;
+int ir_jpeg_decode(ir_ctx* ctx, void* stream, const ir_jpeg_file* files, int n, int subseq_bits, uint32_t* info, int16_t* coef_or_null, void* ws,
+                   size_t ws_bytes);
 
 /* Pillow's resampling of 8-bit RGB images on the device (PIL.Image.resize with BICUBIC / LANCZOS, Resample.c): what the command line does to
  * every input (--sr_scale, auto_resize: inference.py:263-291) and to the results of enlarged inputs (LANCZOS back to the LQ size, :323-346).

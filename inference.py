@@ -132,6 +132,10 @@ def parse_args() -> Namespace:
     parser.add_argument("--degrade_seed", type=int, default=231, help="with --degrade: a file's parameters are drawn from a generator seeded by this number "
                         "and the crc32 of its input-relative path, whatever the batch size, worker count or rank")
     parser.add_argument("--save_lq", type=str, default=None, metavar="DIR", help="with --degrade: write the synthesised LQ images to DIR/<input-relative path>.png")
+    parser.add_argument("--jpeg_decoder", type=str, default="host", choices=["host", "gpu"], help="who decodes JPEG inputs. host (default): PIL, as the reference. gpu: "
+                        "a reader thread parses the headers and removes the byte stuffing, the compressed bytes are uploaded and ir_jpeg_decode makes PIL's "
+                        "pixels on the device (baseline files, grey or YCbCr 4:4:4 / 4:2:2 / 4:2:0; every other file, JPEG or not, takes PIL as today and the "
+                        "run says how many). Switches --resize gpu on; not offered with --show_lq, --use_center_crop, --shard_tiles")
     parser.add_argument("--workers", type=int, default=-1, help="host threads that decode / resize the inputs and resize / PNG-encode the results "
                         "around the GPU (PIL releases the GIL there); -1 = this process's CPU share, 0 = everything on the main thread like the reference")
     return parser.parse_args()
@@ -168,6 +172,29 @@ def check_save_format(args: Namespace) -> None:
         raise SystemExit(f"--jpeg_quality {args.jpeg_quality} is outside 1 .. 100")
     args.jpeg_subsampling = args.jpeg_subsampling or "420"
     args.jpeg_encoder = args.jpeg_encoder or "host"
+
+
+def check_jpeg_decoder(args: Namespace) -> None:
+    """--jpeg_decoder gpu decodes into the device's resize route: it switches --resize gpu on and is refused wherever that is."""
+    if getattr(args, "jpeg_decoder", "host") != "gpu":
+        return
+    for flag in ("show_lq", "use_center_crop", "shard_tiles"):
+        if getattr(args, flag, False):
+            raise SystemExit(f"--jpeg_decoder gpu decodes into the device's resize route (--resize gpu), which --{flag} keeps on the host: not offered together")
+    if args.resize != "gpu":
+        print("--jpeg_decoder gpu: the files are decoded on the device, switching --resize gpu on")
+        args.resize = "gpu"
+    args.jpeg_decode_log = []   # per file None (decoded on the device) or the reason it took the host decoder; list.append is atomic
+
+
+def jpeg_decoder_note(args: Namespace) -> str:
+    log = getattr(args, "jpeg_decode_log", None)
+    if log is None:
+        return ""
+    host = [r for r in log if r is not None]
+    reasons = ", ".join(f"{r}: {host.count(r)}" for r in sorted(set(host)))
+    return (f"--jpeg_decoder gpu: {len(log) - len(host)} of {len(log)} files were decoded on the device, {len(host)} took the host decoder"
+            + (f" (reasons: {reasons})" if host else ""))
 
 
 def save_ext(args: Namespace) -> str:
@@ -303,7 +330,8 @@ def attach_gt(job: Job, args: Namespace) -> Job:
     if rect is not None:
         from instarevive_amd.metrics import MetricsError
         path = lookup.path(job.src)
-        same = job.deg is not None and os.path.abspath(path) == os.path.abspath(job.src)   # --degrade without --gt: the decoded file is the ground truth
+        # --degrade without --gt: the decoded file is the ground truth (a file the device decodes has no pixels here: the scorer's copy is PIL's)
+        same = job.deg is not None and os.path.abspath(path) == os.path.abspath(job.src) and isinstance(job.raw, np.ndarray)
         gt = job.raw if same else np.array(Image.open(path).convert("RGB"))
         if gt.shape[:2] != tuple(rect):
             raise MetricsError(f"--gt: {path} is {gt.shape[0]} x {gt.shape[1]}, the result of {job.src} is {rect[0]} x {rect[1]}")
@@ -317,15 +345,24 @@ def read_job(file_path: str, repeat: int, args: Namespace) -> Job:
 
 def decode_job(file_path: str, repeat: int, args: Namespace) -> Job:
     from instarevive_amd.utils import auto_resize, center_crop_arr, get_file_name_parts, pad
-    lq = Image.open(file_path).convert("RGB")
+    source = None
+    if getattr(args, "resize_on_gpu", False) and getattr(args, "jpeg_decode_log", None) is not None:   # --jpeg_decoder gpu: the headers and one byte pass
+        from instarevive_amd.jpeg_decode import JpegSource
+        with open(file_path, "rb") as f:
+            source, why = JpegSource.open(f.read())
+        args.jpeg_decode_log.append(why)
+        if source is not None:
+            source.name = file_path
+    lq = Image.open(file_path).convert("RGB") if source is None else None
     if getattr(args, "resize_on_gpu", False):   # decode only: the sizes are worked out here, the pixels are resampled on the device
         from instarevive_amd.resample import job_geometry
-        geo = job_geometry(lq.size, args.sr_scale, args.tiled, args.tile_size)
+        width, height = lq.size if source is None else (source.shape[1], source.shape[0])
+        geo = job_geometry((width, height), args.sr_scale, args.tiled, args.tile_size)
         folder, stem, _ = get_file_name_parts(os.path.join(args.output, os.path.relpath(file_path, args.input)))
-        job = Job(os.path.join(folder, f"{stem}_{repeat}{save_ext(args)}"), lq, None, geo.valid_hw, file_path, geo, np.array(lq))
+        job = Job(os.path.join(folder, f"{stem}_{repeat}{save_ext(args)}"), lq, None, geo.valid_hw, file_path, geo, np.array(lq) if source is None else source)
         if getattr(args, "degrade_recipe", None):   # the draws (and the noise field) are made here, on a reader thread
             from instarevive_amd.degrade import draw
-            job.deg = draw(args.degrade_recipe, os.path.relpath(file_path, args.input), lq.height, lq.width, args.degrade_seed)
+            job.deg = draw(args.degrade_recipe, os.path.relpath(file_path, args.input), height, width, args.degrade_seed)
         return job
     if args.sr_scale != 1:
         lq = lq.resize(tuple(math.ceil(edge * args.sr_scale) for edge in lq.size), Image.BICUBIC)
@@ -509,6 +546,7 @@ def main() -> None:
     from instarevive_amd.utils import list_image_files
     args = parse_args()
     check_save_format(args)
+    check_jpeg_decoder(args)
     niqe_params = load_niqe_params(args)
     clipiqa_model = load_clipiqa_model(args)
     noref = bool(niqe_params) or clipiqa_model is not None
@@ -694,6 +732,8 @@ def main() -> None:
                 pools.write_behind(write_job, job, preds[k], stage1[k] if stage1 else None, args)
     pools.drain()
     t1 = time.perf_counter()
+    if jpeg_decoder_note(args):
+        print(f"[rank {rank}] {jpeg_decoder_note(args)}")
     if gpu_png:
         print(f"[rank {rank}] --png_encoder gpu: {host_files} of {pools.written} files took the host encoder (not a plain crop of the prediction)")
     if gpu_jpg:

@@ -25,7 +25,7 @@ SYMBOLS = [
     "ir_unet_configure", "ir_unet_set_context", "ir_cldm_sample", "ir_cldm_pipeline", "ir_clip_text_configure", "ir_clip_text_encode", "ir_op_groupnorm_any", "ir_op_geglu",
     "ir_dit_set_prompts", "ir_op_attention_kv_groups", "ir_graph_records", "ir_op_vae_segment", "ir_op_vae_segment_ws", "ir_op_vae_segment_info",
     "ir_op_swin_shell", "ir_op_swin_shell_ws",
-    "ir_png_bound", "ir_png_encode", "ir_jpeg_bound", "ir_jpeg_encode", "ir_resample_plan_bytes", "ir_resample_plan", "ir_resample_u8", "ir_metrics_y",
+    "ir_png_bound", "ir_png_encode", "ir_jpeg_bound", "ir_jpeg_encode", "ir_jpeg_decode", "ir_resample_plan_bytes", "ir_resample_plan", "ir_resample_u8", "ir_metrics_y",
     "ir_lpips_scale_table", "ir_lpips_configure", "ir_lpips", "ir_niqe_window", "ir_niqe_stats",
     "ir_clipiqa_scale_table", "ir_clipiqa_configure", "ir_clipiqa", "ir_degrade_qtables", "ir_degrade", "ir_degrade_chain",
 ]
@@ -40,6 +40,8 @@ DEGRADE_NORM_NONE, DEGRADE_NORM_MAX = 0, 1
 DEGRADE_MAX_KSIZE, DEGRADE_MIN_LOW = 41, 8
 STAGE_DEGRADE_CHAIN = 17
 STAGE_JPEG = 18   # flags = subsampling, tile_size = restart_mcus
+STAGE_JPEG_DECODE = 19   # h, w = the largest sides, flags = the largest stream_bytes, tile_size = subseq_bits
+JPEG_DECODE_TABLE_BYTES = 6176
 CHAIN_FILTER, CHAIN_RESIZE, CHAIN_GAUSS, CHAIN_POISSON, CHAIN_DIFFJPEG = 1, 2, 3, 4, 5   # ir_chain_op.kind
 CHAIN_AREA, CHAIN_BILINEAR, CHAIN_BICUBIC = 0, 1, 2   # a resize op's mode
 CHAIN_MAX_OPS, CHAIN_MAX_KSIZE, CHAIN_MAX_SIDE = 16, 21, 8192
@@ -72,6 +74,13 @@ class ChainOp(C.Structure):
 class Chain(C.Structure):
     """ir_chain (include/instarevive_hip.h): one image's ops; exp_table and dct_basis are device addresses."""
     _fields_ = [("n_ops", C.c_int), ("tap", C.c_int), ("exp_table", C.c_void_p), ("dct_basis", C.c_void_p), ("ops", ChainOp * 16)]
+
+
+class JpegFile(C.Structure):
+    """ir_jpeg_file (include/instarevive_hip.h): one file's record; stream, intervals, tables and out are device addresses."""
+    _fields_ = [("stream", C.c_void_p), ("intervals", C.c_void_p), ("tables", C.c_void_p), ("out", C.c_void_p), ("pitch", C.c_long),
+                ("stream_bytes", C.c_uint32), ("n_intervals", C.c_int), ("h", C.c_int), ("w", C.c_int), ("comps", C.c_int), ("hs", C.c_int),
+                ("vs", C.c_int), ("restart_mcus", C.c_int), ("tq", C.c_uint8 * 4), ("td", C.c_uint8 * 4), ("ta", C.c_uint8 * 4)]
 
 
 class NativeLibraryError(RuntimeError):
@@ -189,6 +198,7 @@ def load_library():
     lib.ir_jpeg_bound.argtypes = [i, i, i, i]
     lib.ir_jpeg_bound.restype = sz
     lib.ir_jpeg_encode.argtypes = [vp, vp, vp, i, i, i, C.c_long, i, i, i, i, i, vp, sz, vp, vp, sz]
+    lib.ir_jpeg_decode.argtypes = [vp, vp, C.POINTER(JpegFile), i, i, vp, vp, vp, sz]
     lib.ir_resample_plan_bytes.argtypes = [i, i, i, i, i]
     lib.ir_resample_plan_bytes.restype = sz
     lib.ir_resample_plan.argtypes = [i, i, i, i, i, vp, sz]

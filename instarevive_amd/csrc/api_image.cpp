@@ -147,6 +147,29 @@ int ir_jpeg_encode(ir_ctx* c, void* stream, const uint8_t* img, int n, int h, in
     return 0;
 }
 
+// ---------------------------------------------------------------- JPEG decoding (jpeg_decode.hip)
+int ir_jpeg_decode(ir_ctx* c, void* stream, const ir_jpeg_file* files, int n, int subseq_bits, uint32_t* info, int16_t* coef_or_null, void* ws,
+                   size_t ws_bytes) {
+    if (!c || !files || !info || !ws) return fail(c, -1, "ir_jpeg_decode: null argument");
+    if (n < 1) return fail(c, -1, "ir_jpeg_decode: n %d", n);
+    if (subseq_bits < 128 || subseq_bits > 4096 || subseq_bits % 32) return fail(c, -1, "ir_jpeg_decode: subseq_bits %d is no multiple of 32 in 128 .. 4096", subseq_bits);
+    if ((reinterpret_cast<uintptr_t>(info) & 3) || (reinterpret_cast<uintptr_t>(coef_or_null) & 1)) return fail(c, -1, "ir_jpeg_decode: misaligned info or coef pointer");
+    size_t need = 0;
+    for (int i = 0; i < n; ++i) {   // every file is checked before the first launch
+        const char* why;
+        if (ir_jpeg_decode_check(&files[i], &why)) return fail(c, -1, "ir_jpeg_decode: file %d (%d x %d): %s", i, files[i].h, files[i].w, why);
+        need = std::max(need, ir_jpeg_decode_workspace(files[i].h, files[i].w, files[i].stream_bytes, subseq_bits));
+    }
+    if (int e = check_ws(c, "ir_jpeg_decode", ws, ws_bytes, need, 256)) return e;
+    use_ctx(c);
+    for (int i = 0; i < n; ++i) {
+        if (ir_launch_jpeg_decode(&files[i], subseq_bits, info + i, coef_or_null, ws, (hipStream_t)stream))
+            return fail(c, -100, "ir_jpeg_decode: launch failed (file %d)", i);
+        if (coef_or_null) coef_or_null += ir_jpeg_decode_blocks(&files[i]) * 64;
+    }
+    return 0;
+}
+
 // ---------------------------------------------------------------- Pillow's 8-bit resampling (resample.hip)
 // The tables of Resample.c's precompute_coeffs + normalize_coeffs_8bpc. Plain double arithmetic in Pillow's order of operations (no contraction
 // into fused multiply-adds): the quantised coefficients have to be Pillow's to the last bit.
@@ -592,6 +615,7 @@ bool ir_host::image_workspace(ir_ctx* c, int stage, int n, int h, int w, int fla
         case IR_STAGE_LPIPS: if (!ir_lpips_plan(n, h, w, &lp)) *bytes = lp.total; break;
         case IR_STAGE_METRICS: if (some) *bytes = metrics_workspace(n, h, w); break;
         case IR_STAGE_JPEG: if (ir_jpeg_layout(n, h, w, flags, tile_size, &jl)) *bytes = jl.total; break;   // flags: the subsampling, tile_size: restart_mcus
+        case IR_STAGE_JPEG_DECODE: if (n >= 1) *bytes = ir_jpeg_decode_workspace(h, w, (uint32_t)flags, tile_size); break;   // flags: stream_bytes, tile_size: subseq_bits
         case IR_STAGE_PNG: if (some) *bytes = png_layout(n, h, w).total; break;
         case IR_STAGE_RESAMPLE: if (some) *bytes = rs_workspace(n, h, w); break;   // n images, h = in_h, w = out_w: the uint8 image between the passes
         default: return false;

@@ -19,17 +19,19 @@
 // The order of the floating-point operations is part of the definition (a byte is a truncation or a rounding of their result), so build.py
 // compiles this file with -ffp-contract=off, for the reason niqe.hip gives: the pragma alone does not hold under -ffp-contract=fast.
 #include "common.h"
+#include "jpeg_back.h"
 #include "kernels.h"
 
 #pragma clang fp contract(off)
 
 namespace {
 
+using namespace ir_jpeg_back;
+
 constexpr int TPB = 256;
 constexpr int NORM_MAX = 1;   // IR_DEGRADE_NORM_MAX of include/instarevive_hip.h
 constexpr int PATCH = 32;   // the blur's and the last resize's output patch of a workgroup: 32 columns x (8 threads x 4 rows)
 
-IR_DEVINL int clampi(int v, int lo, int hi) { return v < lo ? lo : (v > hi ? hi : v); }
 IR_DEVINL float unit(int v) { return (float)((double)v / 255.0); }   // float32(v / 255.0); equals float32(v) / float32(255) for all 256 bytes
 IR_DEVINL int reflect101(int i, int n) { return clampi(i < 0 ? -i : (i >= n ? 2 * (n - 1) - i : i), 0, n - 1); }
 
@@ -126,8 +128,6 @@ __global__ __launch_bounds__(TPB) void degrade_down_kernel(const float* __restri
 }
 
 // ---------------------------------------------------------------- JPEG: colour conversion and chroma downsample
-constexpr int FIX(double x) { return (int)(x * 65536.0 + 0.5); }
-
 struct Ycc {
     int y, cb, cr;
 };
@@ -168,11 +168,6 @@ struct QTables {
     uint16_t t[2][64];   // luminance, chrominance; natural order
 };
 
-typedef long long i64;
-constexpr i64 F_0_298 = 2446, F_0_390 = 3196, F_0_541 = 4433, F_0_765 = 6270, F_0_899 = 7373, F_1_175 = 9633, F_1_501 = 12299, F_1_847 = 15137,
-              F_1_961 = 16069, F_2_053 = 16819, F_2_562 = 20995, F_3_072 = 25172;
-IR_DEVINL i64 descale(i64 x, int n) { return (x + ((i64)1 << (n - 1))) >> n; }
-
 template <bool FIRST>
 IR_DEVINL void fdct8(i64 d[8]) {   // jfdctint.c, one row (FIRST) or one column
     constexpr int N = FIRST ? 13 - 2 : 13 + 2;
@@ -193,27 +188,6 @@ IR_DEVINL void fdct8(i64 d[8]) {   // jfdctint.c, one row (FIRST) or one column
     d[5] = descale(t5 + z2 + z4, N);
     d[3] = descale(t6 + z2 + z3, N);
     d[1] = descale(t7 + z1 + z4, N);
-}
-
-template <bool FIRST>
-IR_DEVINL void idct8(i64 d[8]) {   // jidctint.c, one column (FIRST) or one row
-    constexpr int N = FIRST ? 13 - 2 : 13 + 2 + 3;
-    i64 z1 = (d[2] + d[6]) * F_0_541;
-    i64 t2 = z1 + d[6] * (-F_1_847), t3 = z1 + d[2] * F_0_765;
-    i64 t0 = (d[0] + d[4]) * 8192, t1 = (d[0] - d[4]) * 8192;
-    const i64 t10 = t0 + t3, t13 = t0 - t3, t11 = t1 + t2, t12 = t1 - t2;
-    t0 = d[7], t1 = d[5], t2 = d[3], t3 = d[1];
-    z1 = t0 + t3;
-    i64 z2 = t1 + t2, z3 = t0 + t2, z4 = t1 + t3;
-    const i64 z5 = (z3 + z4) * F_1_175;
-    t0 *= F_0_298, t1 *= F_2_053, t2 *= F_3_072, t3 *= F_1_501;
-    z1 *= -F_0_899, z2 *= -F_2_562, z3 *= -F_1_961, z4 *= -F_0_390;
-    z3 += z5, z4 += z5;
-    t0 += z1 + z3, t1 += z2 + z4, t2 += z2 + z3, t3 += z1 + z4;
-    d[0] = descale(t10 + t3, N), d[7] = descale(t10 - t3, N);
-    d[1] = descale(t11 + t2, N), d[6] = descale(t11 - t2, N);
-    d[2] = descale(t12 + t1, N), d[5] = descale(t12 - t1, N);
-    d[3] = descale(t13 + t0, N), d[4] = descale(t13 - t0, N);
 }
 
 // planes [gridDim.y][H][W] bytes, H and W multiples of 8; lane l of a group of eight takes row l, column l, column l, row l of its block
@@ -258,18 +232,6 @@ __global__ __launch_bounds__(TPB) void degrade_dct_kernel(uint8_t* __restrict__ 
 }
 
 // ---------------------------------------------------------------- JPEG: fancy upsampling and back to RGB
-// 3 * near + far of chroma column cx for output row y (the row above the first and below the last is the edge row itself)
-IR_DEVINL int chroma_v(const uint8_t* __restrict__ C, int CW, int ch, int y, int cx) {
-    const int cy = y >> 1, far = (y & 1) ? (cy + 1 < ch ? cy + 1 : ch - 1) : (cy > 0 ? cy - 1 : 0);
-    return 3 * (int)C[cy * CW + cx] + (int)C[far * CW + cx];
-}
-
-IR_DEVINL int chroma_up(const uint8_t* __restrict__ C, int CW, int ch, int cw, int y, int x) {
-    const int cx = x >> 1, cs = chroma_v(C, CW, ch, y, cx);
-    if (x & 1) return (3 * cs + (cx + 1 < cw ? chroma_v(C, CW, ch, y, cx + 1) : cs) + 7) >> 4;
-    return (3 * cs + (cx > 0 ? chroma_v(C, CW, ch, y, cx - 1) : cs) + 8) >> 4;
-}
-
 __global__ __launch_bounds__(TPB) void degrade_rgb_kernel(const uint8_t* __restrict__ Y, const uint8_t* __restrict__ Cb, const uint8_t* __restrict__ Cr,
                                                           int lh, int lw, int PW, float* __restrict__ low, uint8_t* __restrict__ bytes) {
     const int i = blockIdx.x * TPB + threadIdx.x;

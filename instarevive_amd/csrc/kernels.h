@@ -223,6 +223,16 @@ bool ir_jpeg_layout(int n, int vh, int vw, int subsampling, int restart_mcus, Ir
 int ir_launch_jpeg_encode(const uint8_t* img, int n, int h, long pitch, int vh, int vw, int quality, int subsampling, int restart_mcus, uint8_t* out,
                           size_t out_stride, uint32_t* info, void* ws, hipStream_t s);
 
+// ---- JPEG decoding into uint8 images (jpeg_decode.hip); ir_jpeg_file: include/instarevive_hip.h
+// ir_jpeg_decode_check: 0, or -1 with *why for a record the kernels do not take. ir_jpeg_decode_workspace: the bytes one file of at most h x w
+// pixels (any sampling, any restart interval) and stream_bytes needs at subseq_bits, 0 for sizes outside the contract. ir_launch_jpeg_decode: one
+// file's chain of launches; coef: NULL (the workspace's) or where the file's coefficients go; ws: that many bytes, 256-byte aligned.
+struct ir_jpeg_file;
+int ir_jpeg_decode_check(const ir_jpeg_file* f, const char** why);
+size_t ir_jpeg_decode_workspace(int h, int w, uint32_t stream_bytes, int subseq_bits);
+long ir_jpeg_decode_blocks(const ir_jpeg_file* f);
+int ir_launch_jpeg_decode(const ir_jpeg_file* f, int subseq_bits, uint32_t* info, int16_t* coef, void* ws, hipStream_t s);
+
 // ---- Pillow's 8-bit resampling of uint8 images (resample.hip)
 // The plan (ir_resample_plan) is an int32 array: a header of IR_RESAMPLE_HEADER ints - [0] IR_RESAMPLE_MAGIC, [1..4] in_h, in_w, out_h, out_w, [5] the
 // filter, [6] ksize_h, [7] ksize_v, [8] / [9] the offsets (in ints, from the plan's start) of the horizontal bounds [out_w][2] and coefficients

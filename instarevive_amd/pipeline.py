@@ -298,8 +298,8 @@ class _Batch:
             from .jpeg import RESTART_MCUS
             self.ctx.workspace(self.ctx.ws_bytes(L.STAGE_JPEG, n, h, w, self.codec[1], RESTART_MCUS))
         if self.records is not None:
-            from .resample import chain_ws_bytes
-            self.ctx.workspace(chain_ws_bytes(self.records))
+            from .resample import chain_ws_bytes, decode_ws_bytes
+            self.ctx.workspace(max(chain_ws_bytes(self.records), decode_ws_bytes(self.records)))
         for s in self.scorers:
             s.reserve()
 
@@ -312,6 +312,7 @@ class _Batch:
         from .slots import record_sizes
         ctx, st, slot, rs, (n, h, w) = self.ctx, self.st, self.slot, self.rs, self.shape
         if rs is not None:
+            rs.decode(self.records)   # the batch's JPEG files (jpeg_decode.JpegSource records), into the places of their pixels
             if self.dparams is not None:
                 rs.degrade(self.records)
             rs.to_network(self.records, st.d_in[slot])
@@ -351,6 +352,8 @@ class _Batch:
                 self.rs.download([r for _, _, res in self.outs for r in res])
         if self.want_lq:
             self.rs.download_lq()
+        if self.rs is not None:
+            self.rs.download_info()
         for s in self.scorers:
             s.download()
 
@@ -364,6 +367,8 @@ class _Batch:
         scored batch, the scores element: a pair of lists (predictions, stage-1 images or empty) of tuples, every scorer's values in the order of
         `scorers`. The host part of NIQE (the fits and the score) runs here, where the scores are read."""
         n = self.shape[0]
+        if self.rs is not None:
+            self.rs.check_info(self.records)
         if self.enc is not None:
             files = self.enc.fetch(len(self.outs) * n, stream, png_wrap)
             lists = [files[:n], files[n:]]
@@ -415,7 +420,9 @@ def process(model, control_imgs: List[np.ndarray], strength: float, color_fix_ty
     jpeg_quality (1 .. 100) and jpeg_subsampling (2 or 420: 4:2:0, 0 or 444: 4:4:4), byte for byte PIL's Image.save(format="JPEG", quality,
     subsampling, restart_marker_blocks=jpeg.RESTART_MCUS) of the raw result. It combines with resize, degrade, gt, niqe and clipiqa as png does;
     the scores are those of the device's image, the result BEFORE the JPEG loss.
-    resize (fused form only): a list of one resample.ResizeJob per image - the DECODED file and its job_geometry(). control_imgs is then not read:
+    resize (fused form only): a list of one resample.ResizeJob per image - the DECODED file (or a jpeg_decode.JpegSource: the file's compressed bytes
+    are uploaded and ir_jpeg_decode makes the pixels on the device, Pillow's bytes; a stream the device cannot decode raises RuntimeError when the
+    batch is collected) and its job_geometry(). control_imgs is then not read:
     the decoded bytes are uploaded, ir_resample_u8 makes the network input on the device (the bicubic chain of --sr_scale / auto_resize, the
     zero pad), and behind ir_pipeline the valid rectangle of every image that auto_resize enlarged is resampled (LANCZOS) back to its LQ size.
     Both lists then hold the FINAL images - what the command line saves: the resized result, else the valid rectangle - bit for bit what

@@ -48,7 +48,8 @@ def job_geometry(size: Tuple[int, int], sr_scale: float, tiled: bool, tile_size:
 
 
 class ResizeJob(NamedTuple):
-    """One image of a process(resize=...) batch: the decoded file (HWC uint8 RGB) and its job_geometry()."""
+    """One image of a process(resize=...) batch: the decoded file (HWC uint8 RGB) - or a jpeg_decode.JpegSource, a JPEG file the device decodes
+    into the place the pixels would have been copied to - and its job_geometry()."""
     raw: np.ndarray
     geo: Geometry
 
@@ -128,13 +129,25 @@ def chain_ws_bytes(records: Sequence[ResizeJob]) -> int:
     return need
 
 
+def _is_jpeg(raw) -> bool:
+    from .jpeg_decode import JpegSource
+    return isinstance(raw, JpegSource)
+
+
+def decode_ws_bytes(records: Sequence[ResizeJob]) -> int:
+    """Workspace of the batch's ir_jpeg_decode call (0 without JPEG files)."""
+    from . import jpeg_decode as J
+    sources = [rec.raw for rec in records if _is_jpeg(rec.raw)]
+    return J.ws_bytes(sources) if sources else 0
+
+
 def check_records(records: Sequence[ResizeJob]) -> Tuple[int, int, int]:
     if len(records) == 0:
         raise ValueError("resize: empty batch")
     for rec in records:
         a = rec.raw
-        if not isinstance(a, np.ndarray) or a.dtype != np.uint8 or a.ndim != 3 or a.shape[-1] != 3:
-            raise ValueError("resize: the decoded files must be HWC uint8 RGB arrays")
+        if not _is_jpeg(a) and (not isinstance(a, np.ndarray) or a.dtype != np.uint8 or a.ndim != 3 or a.shape[-1] != 3):
+            raise ValueError("resize: the decoded files must be HWC uint8 RGB arrays (or jpeg_decode.JpegSource files)")
         if rec.geo.net_hw != records[0].geo.net_hw:
             raise ValueError("resize: the images of a batch must reach one network input size")
         last = rec.geo.chain[-1] if rec.geo.chain else (a.shape[1], a.shape[0])
@@ -166,10 +179,13 @@ class ResizeSlot(Pooled):
         self.extras: List[tuple] = []   # per image the offsets of its blur kernel and noise field (or None) in h_raw / d_raw
         self.img_bytes = 0       # where the images end in h_raw / d_raw (the kernels and noise fields follow)
         self.lq_made = False
+        self.jpeg: List[tuple] = []     # per JPEG file of the batch (a JpegSource record): its index and the offset of its compressed bytes
+        self.d_info = self.h_info = None   # ir_jpeg_decode's info words of the batch, device and page-locked
 
     def fill(self, records: Sequence[ResizeJob], degrade=None) -> None:
         """Copy the decoded files into the page-locked buffer (after the previous upload out of it has completed). degrade: one degrade.Params
-        (or one degrade.ChainParams: a batch holds one kind) per image, or None - their blur kernels and noise fields travel behind the images."""
+        (or one degrade.ChainParams: a batch holds one kind) per image, or None - their blur kernels and noise fields travel behind the images.
+        A JpegSource keeps its image's place free and travels as compressed bytes behind all of that; decode() fills the place on the device."""
         if degrade is not None:
             from . import degrade as D
             if len(degrade) != len(records):
@@ -188,17 +204,26 @@ class ResizeSlot(Pooled):
         self.img_bytes, self.dparams, self.extras, self.lq_made = at, degrade, [], False
         if degrade is not None:
             at += sum(D.extra_bytes(p) for p in degrade)
+        self.jpeg = []
+        for i, rec in enumerate(records):
+            if _is_jpeg(rec.raw):
+                at = (at + 255) & ~255
+                self.jpeg.append((i, at))
+                at += rec.raw.blob_bytes
         self.h_raw = _grown(self.h_raw, at, pinned=True)
         if self.d_raw is None or self.d_raw.numel() < self.h_raw.numel():
             self.d_raw, self.fresh = _grown(None, self.h_raw.numel(), self.ctx.device), True
         self.used = at
         host = self.h_raw.numpy()
         for rec, o in zip(records, self.offsets):
-            np.copyto(host[o:o + rec.raw.size].reshape(rec.raw.shape), rec.raw)
+            if not _is_jpeg(rec.raw):
+                np.copyto(host[o:o + rec.raw.size].reshape(rec.raw.shape), rec.raw)
         at = self.img_bytes
         for p in degrade or ():
             k_at, n_at, at = D.pack_extras(p, host, at)
             self.extras.append((k_at, n_at))
+        for i, b_at in self.jpeg:
+            records[i].raw.pack(host, b_at)
 
     def upload(self, stream=None, owner=None):
         """Asynchronous H2D copy of the decoded bytes on `stream` (default: the current one); the event behind it is what the next fill() waits for.
@@ -207,11 +232,39 @@ class ResizeSlot(Pooled):
         if self.fresh and owner is not None and stream is not None:
             stream.wait_stream(owner)
         self.fresh = False
-        self.d_raw[:self.used].copy_(self.h_raw[:self.used], non_blocking=True)
+        first = self.img_bytes if self.jpeg and len(self.jpeg) == len(self.offsets) else 0   # a batch of JPEG files alone uploads no pixels
+        self.d_raw[first:self.used].copy_(self.h_raw[first:self.used], non_blocking=True)
         ev = torch.cuda.Event()
         ev.record(stream if stream is not None else torch.cuda.current_stream(self.ctx.device))
         self.h2d_done = ev
         return ev
+
+    def decode(self, records: Sequence[ResizeJob]) -> None:
+        """Between upload() and degrade() / to_network(), on the current stream: every JPEG file of the batch is decoded (ir_jpeg_decode, one call)
+        into its image's place in d_raw. The info words follow with download_info() and are read by check_info()."""
+        from . import jpeg_decode as J
+        if not self.jpeg:
+            return
+        n = len(self.jpeg)
+        if self.d_info is None or self.d_info.numel() < n:
+            self.d_info = torch.zeros(max(n, 16), dtype=torch.int32, device=self.ctx.device)
+            self.h_info = torch.zeros(max(n, 16), dtype=torch.int32).pin_memory()
+        base = self.d_raw.data_ptr()
+        J.launch(self.ctx, [records[i].raw.record(base + b_at, base + self.offsets[i]) for i, b_at in self.jpeg], self.d_info.data_ptr())
+
+    def download_info(self) -> None:
+        """Asynchronous D2H copy of decode()'s info words, on the current stream."""
+        if self.jpeg:
+            self.h_info.copy_(self.d_info, non_blocking=True)
+
+    def check_info(self, records: Sequence[ResizeJob]) -> None:
+        """After the copy has completed: a file the device could not decode ends the batch with an error that names it."""
+        from . import jpeg_decode as J
+        for k, (i, _) in enumerate(self.jpeg):
+            cls = int(self.h_info[k])
+            if cls:
+                name = getattr(records[i].raw, "name", None) or f"image {i} of the batch"
+                raise RuntimeError(f"ir_jpeg_decode: {name} is not a valid baseline JPEG stream ({J.ERRORS.get(cls, cls)})")
 
     def degrade(self, records: Sequence[ResizeJob]) -> None:
         """Between upload() and to_network(), on the current stream: every decoded file (ground truth) becomes its LQ image in d_lq, at the
