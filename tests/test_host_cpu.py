@@ -163,6 +163,32 @@ def test_swin_shell_entries_refuse_a_missing_context():
         assert lib.ir_op_swin_shell_ws(None, part, 1, 64, 64) == 0
 
 
+NULL_CONTEXT = {
+    -11: ["ir_swinir_forward", "ir_vae_encode", "ir_vae_decode", "ir_dit_forward", "ir_dit_step", "ir_dit_forward_control", "ir_dit_step_control",
+          "ir_pipeline", "ir_cldm_sample", "ir_cldm_pipeline", "ir_color_fix", "ir_tiled_encode", "ir_tiled_encode_part", "ir_tiled_encode_overflow",
+          "ir_tiled_dit", "ir_tiled_blend_latent", "ir_tiled_decode", "ir_tiled_blend_pixels", "ir_t5_encode", "ir_clip_text_encode"],
+    -1: ["ir_dit_set_prompt", "ir_dit_set_prompts", "ir_unet_set_context", "ir_dit_control_configure", "ir_profile_begin", "ir_profile_select",
+         "ir_profile_end", "ir_profile_end_kernels",
+         "ir_op_conv", "ir_op_conv_groupnorm", "ir_op_linear"]}   # these three dereferenced the null context before they got their neighbours' refusal
+
+
+def test_stage_entries_refuse_a_missing_context():
+    """The stage entry points, the K / V cache setters and the profiler calls answer a null context with their recorded code (read from the
+    library before these entry points got their shared checks; the three ir_op_* entries crashed there) before anything touches a device.
+    Every other argument is null or zero, so only the context check can be what answers."""
+    import ctypes as C
+    from instarevive_amd import _lib
+    from instarevive_amd.build import build
+    build()
+    lib = _lib.load_library()
+    for code, names in NULL_CONTEXT.items():
+        for name in names:
+            fn = getattr(lib, name)
+            args = [0.0 if t is C.c_float else 0 if t in (C.c_int, C.c_uint, C.c_long, C.c_size_t) else None for t in fn.argtypes]
+            assert fn(*args) == code, name
+            assert lib.ir_last_error(None) == b"null context"
+
+
 def test_sliding_windows_and_loaders():
     from instarevive_amd.pipeline import _sliding_windows
     from instarevive_amd import utils
