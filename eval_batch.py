@@ -44,7 +44,10 @@ def parse_args():
                     "(caption_feature [1, T, 4096], optional attention_mask; the reference's caption files). Images without one get --prompt_embeds")
     ap.add_argument("--device", default="cuda")
     ap.add_argument("--png_encoder", default="host", choices=["host", "gpu"], help="who compresses the PNGs of both output folders: the host (PIL, default) or "
-                    "the GPU behind the network (inference.py --png_encoder: lossless, meant for photographs; flat content comes out larger than PIL's)")
+                    "the GPU behind the network (inference.py --png_encoder: lossless, meant for photographs; flat content comes out larger than PIL's unless "
+                    "--png_runs is given)")
+    ap.add_argument("--png_runs", action="store_true", help="with --png_encoder gpu: the device encoder's run mode (inference.py --png_runs: runs of equal "
+                    "filtered bytes coded as matches, the same pixels, no file larger, flat content several times smaller)")
     cli.add_jpeg_flags(ap)   # --save_format jpg, --jpeg_quality, --jpeg_subsampling, --jpeg_encoder: as in inference.py, for both output folders
     ap.add_argument("--gt", default=None, help="score both output folders against ground truth on the GPU (inference.py --gt: PSNR-Y / SSIM-Y, the same lookup "
                     "rules); the ground truth is centre-cropped to --image_size like the input. Writes metrics.csv (metrics.rank<k>.csv with several ranks) into "
@@ -185,7 +188,7 @@ def main():
 
     results = process_stream(m.model, feed(), "none", args.disable_preprocess_model, False, 512, 448, preprocess_model=m.preprocess_model, vae=m.vae,
                              y=m.y, y_mask=m.y_mask, noise_scheduler=m.noise_scheduler, return_stage1=True,
-                             png=whole if gpu_png else None, png_wrap=False,
+                             png=whole if gpu_png else None, png_wrap=False, png_runs=args.png_runs,
                              **({"jpeg": whole, "jpeg_quality": args.jpeg_quality, "jpeg_subsampling": args.jpeg_subsampling} if gpu_jpg else {}),
                              gt=cli.in_step(truths) if lookup else None, **with_lpips, **({"niqe": niqe_params} if niqe_params else {}),
                              **({"clipiqa": True} if clipiqa_model else {}),

@@ -41,7 +41,8 @@ enum { IR_STAGE_SWINIR = 0, IR_STAGE_VAE_ENCODE = 1, IR_STAGE_DIT = 2, IR_STAGE_
                                tile_size = restart_mcus (one slot per restart interval) */,
        IR_STAGE_JPEG_DECODE = 19 /* ir_jpeg_decode: h, w = the largest height and width among the files, flags = the largest stream_bytes,
                                     tile_size = subseq_bits; holds for any sampling and restart interval; the files of a batch share one
-                                    workspace, so n only has to be >= 1; depends on these numbers alone (ctx may be NULL) */ };
+                                    workspace, so n only has to be >= 1; depends on these numbers alone (ctx may be NULL) */,
+       IR_STAGE_PNG_RUNS = 20 /* ir_png_encode_runs: n images, h, w = the VALID rectangle vh, vw; depends on the sizes alone (ctx may be NULL) */ };
 /* ir_pipeline flags */
 enum { IR_FLAG_NO_PREPROCESS = 1, IR_FLAG_TILED = 2, IR_FLAG_FIX_WAVELET = 4, IR_FLAG_FIX_ADAIN = 8,
        /* ir_pipeline only, needs ir_dit_control_configure: run the DiT step with the ControlNet-Half branch, condition latent
@@ -293,6 +294,15 @@ int ir_nchw_to_u8(ir_ctx* ctx, void* stream, const float* in, uint8_t* out, int 
 size_t ir_png_bound(int h, int w);
 int ir_png_encode(ir_ctx* ctx, void* stream, const uint8_t* img, int n, int h, int w, long pitch, int vh, int vw, uint8_t* out, size_t out_stride,
                   uint32_t* info, void* ws, size_t ws_bytes);
+/* The run mode of the same encoder: the same arguments, refusals, return codes, filtered bytes, chunks and bound, and the same pixels in the
+ * file. Inside a chunk every maximal run of equal filtered bytes is coded as one literal and matches at distance 1 (pieces of 258 bytes, then
+ * the remainder as one match if it has at least 6 bytes, as literals otherwise). A chunk coded so is one dynamic-Huffman block over literals,
+ * lengths and one distance code of 1 bit, its code lengths sent with the zero-repeat symbols 17 and 18. Per chunk the bit cost of that block and
+ * of ir_png_encode's literal-only block are compared and the cheaper is written, the literal-only block on a tie: the stream is never longer than
+ * ir_png_encode's and flat content stops costing a bit per byte. A chunk of more than 262144 filtered bytes (images wider than 10922 pixels) is
+ * always coded literal-only. ws: 16-byte aligned, ir_workspace_bytes(ctx, IR_STAGE_PNG_RUNS, n, vh, vw, 0, 0, 0) bytes. */
+int ir_png_encode_runs(ir_ctx* ctx, void* stream, const uint8_t* img, int n, int h, int w, long pitch, int vh, int vw, uint8_t* out,
+                       size_t out_stride, uint32_t* info, void* ws, size_t ws_bytes);
 
 /* Baseline JPEG encoding of results on the device (no reference counterpart: the reference saves PNGs through PIL). Encodes the valid
  * rectangle vh x vw (1 <= vh <= h, 1 <= vw <= w) of n RGB8 images img [n][h][pitch] - ir_png_encode's layout - into one entropy-coded segment

@@ -87,8 +87,14 @@ def parse_args() -> Namespace:
                         "writer threads, as the reference does. gpu: the device encodes the result behind the network (Paeth filter + Huffman coding of literals, no "
                         "LZ77 matches; lossless, the same pixels) and only the compressed bytes cross PCIe - for restored PHOTOGRAPHS, where its files are 10 - 18 %% "
                         "smaller than --png_compress_level 1 and within a few percent of the default level; flat or near-flat content (smooth sky, graphics) comes "
-                        "out several times larger than PIL's, since a byte never costs less than one bit. Files that are not a plain crop of the prediction "
+                        "out several times larger than PIL's, since a byte never costs less than one bit (--png_runs lifts that). Files that are not a plain crop of the prediction "
                         "(--show_lq; inputs that auto_resize enlarged, unless --resize gpu resizes their results on the device) still take the host encoder; the run says how many")
+    parser.add_argument("--png_runs", action="store_true", help="with --png_encoder gpu: the device encoder's run mode (ir_png_encode_runs). Runs of equal "
+                        "filtered bytes are coded as matches at distance 1 and the block headers are compacted, chunk by chunk wherever that is shorter: the same "
+                        "pixels, no file larger than without the flag, flat content (sky, graphics) 6 - 35 times smaller (1.6 - 1.9 times PIL's default level, "
+                        "about PIL's level 1), sky over a photograph 1.29 times smaller and below PIL's default (sizes of the format's CPU model on 512 x 512 "
+                        "cases, docs/parity.md). Measured: the encode then takes 0.72 ms instead of 0.38 ms per 2048 x 2048 result, 0.61 %% of the step "
+                        "(profiles/png_runs.txt). The default mode is unchanged")
     add_jpeg_flags(parser)
     parser.add_argument("--resize", type=str, default="host", choices=["host", "gpu"], help="who resizes the inputs (--sr_scale and the enlargement of short edges "
                         "below 512 / the tile size, both bicubic) and the results of enlarged inputs (LANCZOS back to the input's size). host (default): PIL on the "
@@ -158,7 +164,9 @@ def add_jpeg_flags(parser) -> None:
 
 
 def check_save_format(args: Namespace) -> None:
-    """The refusals around --save_format, one line each, and the --jpeg_* defaults; before anything is loaded."""
+    """The refusals around --save_format and the PNG encoder's flags, one line each, and the --jpeg_* defaults; before anything is loaded."""
+    if getattr(args, "png_runs", False) and getattr(args, "png_encoder", "host") != "gpu":
+        raise SystemExit("--png_runs is the run mode of the device PNG encoder: give --png_encoder gpu as well")
     given = [f"--{k}" for k in ("jpeg_quality", "jpeg_subsampling", "jpeg_encoder") if getattr(args, k, None) is not None]
     if args.save_format != "jpg":
         if given:
@@ -651,7 +659,7 @@ def main() -> None:
             if caps:
                 engine.y, engine.y_mask = caps.batch([job.src])
             rect = png_rect(job, args) if gpu_png else None
-            preds, stage1 = parallel.sharded_tiled_process(engine, [job.net_in], rank, world, png=[rect] if rect else None)
+            preds, stage1 = parallel.sharded_tiled_process(engine, [job.net_in], rank, world, png=[rect] if rect else None, png_runs=args.png_runs)
             if rank == 0:
                 host_files += rect is None
                 if rect:   # rank 0 has encoded the assembled frame
@@ -698,7 +706,7 @@ def main() -> None:
     unscored = 0    # --gt / --niqe_params / --clipiqa_model: files whose saved image is not the device's image
     no_score = {"niqe": 0, "clipiqa": 0}   # files below 96 pixels on an edge or without two complete feature rows; files below 32 pixels on an edge
     for out in process_stream(m.model, feed(), tiled=args.tiled, return_stage1=args.show_lq and not args.disable_preprocess_model,
-                              fp8=args.fp8 != "off", png=in_step(rects) if gpu_png else None, png_wrap=False,
+                              fp8=args.fp8 != "off", png=in_step(rects) if gpu_png else None, png_wrap=False, png_runs=args.png_runs,
                               **({"jpeg": in_step(rects), "jpeg_quality": args.jpeg_quality, "jpeg_subsampling": args.jpeg_subsampling} if gpu_jpg else {}),
                               resize=in_step(records) if args.resize_on_gpu else None, gt=in_step(truths) if args.gt else None,
                               **({"lpips": True} if report and report.lpips else {}),

@@ -25,7 +25,7 @@ SYMBOLS = [
     "ir_unet_configure", "ir_unet_set_context", "ir_cldm_sample", "ir_cldm_pipeline", "ir_clip_text_configure", "ir_clip_text_encode", "ir_op_groupnorm_any", "ir_op_geglu",
     "ir_dit_set_prompts", "ir_op_attention_kv_groups", "ir_graph_records", "ir_op_vae_segment", "ir_op_vae_segment_ws", "ir_op_vae_segment_info",
     "ir_op_swin_shell", "ir_op_swin_shell_ws",
-    "ir_png_bound", "ir_png_encode", "ir_jpeg_bound", "ir_jpeg_encode", "ir_jpeg_decode", "ir_resample_plan_bytes", "ir_resample_plan", "ir_resample_u8", "ir_metrics_y",
+    "ir_png_bound", "ir_png_encode", "ir_png_encode_runs", "ir_jpeg_bound", "ir_jpeg_encode", "ir_jpeg_decode", "ir_resample_plan_bytes", "ir_resample_plan", "ir_resample_u8", "ir_metrics_y",
     "ir_lpips_scale_table", "ir_lpips_configure", "ir_lpips", "ir_niqe_window", "ir_niqe_stats",
     "ir_clipiqa_scale_table", "ir_clipiqa_configure", "ir_clipiqa", "ir_degrade_qtables", "ir_degrade", "ir_degrade_chain",
 ]
@@ -42,6 +42,7 @@ STAGE_DEGRADE_CHAIN = 17
 STAGE_JPEG = 18   # flags = subsampling, tile_size = restart_mcus
 STAGE_JPEG_DECODE = 19   # h, w = the largest sides, flags = the largest stream_bytes, tile_size = subseq_bits
 JPEG_DECODE_TABLE_BYTES = 6176
+STAGE_PNG_RUNS = 20   # ir_png_encode_runs: as STAGE_PNG
 CHAIN_FILTER, CHAIN_RESIZE, CHAIN_GAUSS, CHAIN_POISSON, CHAIN_DIFFJPEG = 1, 2, 3, 4, 5   # ir_chain_op.kind
 CHAIN_AREA, CHAIN_BILINEAR, CHAIN_BICUBIC = 0, 1, 2   # a resize op's mode
 CHAIN_MAX_OPS, CHAIN_MAX_KSIZE, CHAIN_MAX_SIDE = 16, 21, 8192
@@ -195,6 +196,7 @@ def load_library():
     lib.ir_png_bound.argtypes = [i, i]
     lib.ir_png_bound.restype = sz
     lib.ir_png_encode.argtypes = [vp, vp, vp, i, i, i, C.c_long, i, i, vp, sz, vp, vp, sz]
+    lib.ir_png_encode_runs.argtypes = lib.ir_png_encode.argtypes
     lib.ir_jpeg_bound.argtypes = [i, i, i, i]
     lib.ir_jpeg_bound.restype = sz
     lib.ir_jpeg_encode.argtypes = [vp, vp, vp, i, i, i, C.c_long, i, i, i, i, i, vp, sz, vp, vp, sz]

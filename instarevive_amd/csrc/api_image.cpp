@@ -125,6 +125,42 @@ int ir_png_encode(ir_ctx* c, void* stream, const uint8_t* img, int n, int h, int
         return fail(c, -100, "ir_png_encode: launch failed");
     return 0;
 }
+// The run mode: ir_png_encode's workspace, and behind it per chunk the second histogram, the second code, the second header and the run marks.
+struct PngRunsLayout {
+    PngLayout lit;
+    size_t flag_words, run_hist, run_codes, run_header, flags, total;
+};
+static PngRunsLayout png_runs_layout(int n, int vh, int vw) {
+    PngRunsLayout R;
+    R.lit = png_layout(n, vh, vw);
+    const size_t k = (size_t)n * R.lit.chunks;
+    auto up = [](size_t b) { return (b + 255) & ~(size_t)255; };
+    R.flag_words = ir_png_runs_flag_words(IR_PNG_ROWS * (3 * (size_t)vw + 1));
+    R.run_hist = R.lit.total;
+    R.run_codes = R.run_hist + up(k * IR_PNG_RUNS_SYMS * 4);
+    R.run_header = R.run_codes + up(k * IR_PNG_RUNS_SYMS * 4);
+    R.flags = R.run_header + up(k * IR_PNG_RUNS_HEADER_WORDS * 4);
+    R.total = R.flags + up(k * R.flag_words * 4);
+    return R;
+}
+int ir_png_encode_runs(ir_ctx* c, void* stream, const uint8_t* img, int n, int h, int w, long pitch, int vh, int vw, uint8_t* out, size_t out_stride,
+                       uint32_t* info, void* ws, size_t ws_bytes) {
+    if (!c || !img || !out || !info || !ws) return fail(c, -1, "ir_png_encode_runs: null argument");
+    if (n < 1 || h < 1 || w < 1 || vh < 1 || vh > h || vw < 1 || vw > w || pitch < 3L * w)
+        return fail(c, -1, "ir_png_encode_runs: bad size (n %d, %d x %d, pitch %ld, valid %d x %d)", n, h, w, pitch, vh, vw);
+    if (out_stride < ir_png_bound(vh, vw))
+        return fail(c, -1, "ir_png_encode_runs: out_stride %zu below ir_png_bound(%d, %d) = %zu", out_stride, vh, vw, ir_png_bound(vh, vw));
+    const PngRunsLayout R = png_runs_layout(n, vh, vw);
+    const PngLayout& L = R.lit;
+    if (int e = check_ws(c, "ir_png_encode_runs", ws, ws_bytes, R.total, 16)) return e;
+    use_ctx(c);
+    char* b = static_cast<char*>(ws);
+    if (ir_launch_png_encode_runs(img, n, h, pitch, vh, vw, out, out_stride, info, (uint32_t*)(b + L.hist), (uint32_t*)(b + L.codes), (uint32_t*)(b + L.header),
+                                  (uint32_t*)(b + L.sizes), (uint8_t*)(b + L.slots), (long)L.slot_cap, (uint32_t*)(b + R.run_hist), (uint32_t*)(b + R.run_codes),
+                                  (uint32_t*)(b + R.run_header), (uint32_t*)(b + R.flags), (long)R.flag_words, (hipStream_t)stream))
+        return fail(c, -100, "ir_png_encode_runs: launch failed");
+    return 0;
+}
 
 // ---------------------------------------------------------------- JPEG encoding (jpeg_encode.hip)
 size_t ir_jpeg_bound(int h, int w, int subsampling, int restart_mcus) { return ir_jpeg_bound_host(h, w, subsampling, restart_mcus); }
@@ -617,6 +653,7 @@ bool ir_host::image_workspace(ir_ctx* c, int stage, int n, int h, int w, int fla
         case IR_STAGE_JPEG: if (ir_jpeg_layout(n, h, w, flags, tile_size, &jl)) *bytes = jl.total; break;   // flags: the subsampling, tile_size: restart_mcus
         case IR_STAGE_JPEG_DECODE: if (n >= 1) *bytes = ir_jpeg_decode_workspace(h, w, (uint32_t)flags, tile_size); break;   // flags: stream_bytes, tile_size: subseq_bits
         case IR_STAGE_PNG: if (some) *bytes = png_layout(n, h, w).total; break;
+        case IR_STAGE_PNG_RUNS: if (some) *bytes = png_runs_layout(n, h, w).total; break;
         case IR_STAGE_RESAMPLE: if (some) *bytes = rs_workspace(n, h, w); break;   // n images, h = in_h, w = out_w: the uint8 image between the passes
         default: return false;
     }

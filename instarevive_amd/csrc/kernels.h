@@ -196,7 +196,8 @@ int ir_launch_t5_attn(const bf16_t* qkv, const float* bias, const float* key_mas
 int ir_launch_t5_gated_gelu(const bf16_t* ab, bf16_t* out, long rows, int F, hipStream_t s);
 
 // ---- PNG encoding of uint8 results (png_encode.hip)
-// png_encode.hip: zlib streams of Paeth-filtered rows, one dynamic-Huffman block of literals per chunk of IR_PNG_ROWS rows. IR_PNG_ROWS is a build
+// png_encode.hip: zlib streams of Paeth-filtered rows, one dynamic-Huffman block of literals per chunk of IR_PNG_ROWS rows (in the run mode, where shorter,
+// one block of literals and distance-1 matches). IR_PNG_ROWS is a build
 // constant (8 .. 64 are sensible; ir_png_bound and the workspace follow it). 8 by measured time at 2048 x 2048: 0.49 ms against 0.72 at 16 and 1.11 at 32
 // rows (256 / 128 / 64 workgroups on 256 CUs) for files 0.1 - 0.3 % larger (profiles/png_encoder.txt). hist / codes: [n * chunks][260] dwords, header: [n * chunks][40],
 // chunk_bytes: [n * chunks], slots: [n * chunks][slot_cap] bytes, 16-byte aligned.
@@ -206,6 +207,17 @@ int ir_launch_t5_gated_gelu(const bf16_t* ab, bf16_t* out, long rows, int F, hip
 #define IR_PNG_HEADER_BITS 1106   // 17 + 19 * 3 + 257 * 4 + 4
 int ir_launch_png_encode(const uint8_t* img, int n, int h, long pitch, int vh, int vw, uint8_t* out, size_t out_stride, uint32_t* info,
                          uint32_t* hist, uint32_t* codes, uint32_t* header, uint32_t* chunk_bytes, uint8_t* slots, long slot_cap, hipStream_t s);
+// The run mode (ir_png_encode_runs): the buffers above, which hold the literal-only side of every chunk, and next to them run_hist / run_codes:
+// [n * chunks][IR_PNG_RUNS_SYMS] dwords (run_codes: 286 codes, the header's bit count, the chunk's choice), run_header: [n * chunks]
+// [IR_PNG_RUNS_HEADER_WORDS], flags: [n * chunks][ir_png_runs_flag_words(IR_PNG_ROWS * rowlen)] dwords, one bit per filtered byte that starts a
+// run. A chunk beyond IR_PNG_RUNS_MAX_CHUNK bytes has no room for its flags in the LDS: such an image takes ir_launch_png_encode.
+#define IR_PNG_RUNS_SYMS 288
+#define IR_PNG_RUNS_HEADER_WORDS 48   // 17 + 19 * 3 + 287 * 5 = 1509 bits at most
+#define IR_PNG_RUNS_MAX_CHUNK (1 << 18)
+static inline size_t ir_png_runs_flag_words(size_t chunk_len) { return (chunk_len + 1 + 31) / 32 + 12; }   // + the end's flag, + the words a lookahead of 258 bits may read
+int ir_launch_png_encode_runs(const uint8_t* img, int n, int h, long pitch, int vh, int vw, uint8_t* out, size_t out_stride, uint32_t* info,
+                              uint32_t* hist, uint32_t* codes, uint32_t* header, uint32_t* chunk_bytes, uint8_t* slots, long slot_cap,
+                              uint32_t* run_hist, uint32_t* run_codes, uint32_t* run_header, uint32_t* flags, long flag_words, hipStream_t s);
 
 // ---- JPEG encoding of uint8 results (jpeg_encode.hip)
 // jpeg_encode.hip: the entropy-coded segment of a baseline JPEG (standard Huffman tables, restart intervals of restart_mcus MCUs), libjpeg's bytes.

@@ -214,14 +214,14 @@ def sharded_encode(engine, control_imgs, rank: int, world: int):
     return control, engine.encode_part1(control, attn_o, attn_res)
 
 
-def sharded_tiled_process(engine, control_imgs, rank: int = None, world: int = None, dst: int = 0, png=None):
+def sharded_tiled_process(engine, control_imgs, rank: int = None, world: int = None, dst: int = 0, png=None, png_runs: bool = False):
     """process(..., tiled=True) of ONE image batch with its tiles sharded over the ranks (test_scripts/inference.py:119-153; SURVEY.md
     section 8(e), "tile-level sharding of one large image"). `engine` supplies the five phases (pipeline.HipTileEngine on a GPU).
     Exchange steps: one all_gather of the encoder's mid-block attention rows (sharded_encode), one all_gather of the x0 latent tiles between the two loops (every rank needs the blended latent for its own
     decoder tiles) and one gather of the decoded pixel tiles on rank `dst`, which re-assembles the image. Both sums run over ALL
     tiles in the reference's loop order on the receiving side, so the result equals the single-rank result bit for bit.
     Returns (preds, stage1_preds) on rank `dst`, (None, None) elsewhere. png: one valid rectangle (vh, vw) per image - rank `dst` then encodes the
-    assembled frames on its GPU (ir_png_encode) and preds holds PNG files as bytes."""
+    assembled frames on its GPU (ir_png_encode; ir_png_encode_runs with png_runs) and preds holds PNG files as bytes."""
     import torch.distributed as dist
     if rank is None or world is None:
         on = dist.is_available() and dist.is_initialized()
@@ -234,4 +234,4 @@ def sharded_tiled_process(engine, control_imgs, rank: int = None, world: int = N
     px_all = _exchange_tiles(engine.decode_tiles(nb, control, rank, world), n_tiles, rank, world, to_all=False, dst=dst)
     if rank != dst:
         return None, None
-    return (engine.blend_pixels(px_all, png=png) if png is not None else engine.blend_pixels(px_all)), engine.stage1()
+    return (engine.blend_pixels(px_all, png=png, png_runs=png_runs) if png is not None else engine.blend_pixels(px_all)), engine.stage1()

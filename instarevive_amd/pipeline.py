@@ -63,18 +63,19 @@ class _Staging:
         return ev
 
 
-def _png_encoder(ctx, count, h, w, slot=0, tag="sync"):
+def _png_encoder(ctx, count, h, w, slot=0, tag="sync", runs=False):
     """The PngEncoder (png.py) of a batch shape and staging slot, kept on the context like the staging buffers. Each entry holds count x ir_png_bound
     bytes on the device and as much page-locked host memory (about 14 MB per 2048 x 2048 image; twice the images with stage-1 output, two slots
     under process_stream). At most 8 entries: the oldest is dropped whatever its use, which is safe because a batch in flight keeps its own
-    reference (_Batch.enc), and costs a re-allocation when more than 8 shapes alternate."""
+    reference (_Batch.enc), and costs a re-allocation when more than 8 shapes alternate. runs: the encoder's run mode (ir_png_encode_runs), part
+    of the key: the two modes never share an entry."""
     from .png import PngEncoder
     pool = ctx.__dict__.setdefault("_png", {})
-    key = (tag, count, h, w, slot)
+    key = (tag, count, h, w, slot, bool(runs))
     if key not in pool:
         if len(pool) >= 8:
             pool.pop(next(iter(pool)))
-        pool[key] = PngEncoder(ctx, count, h, w)
+        pool[key] = PngEncoder(ctx, count, h, w, runs)
     return pool[key]
 
 
@@ -228,18 +229,18 @@ class _Batch:
     two streams and keeps the batch's events in `ready` (its uploads) and `done` (its downloads)."""
 
     def __init__(self, ctx, slot, tag, slots, shape, imgs, with_stage1, rects=None, records=None, dparams=None, gts=None, lpips=False, niqe=None,
-                 clipiqa=False, sizes=None, want_lq=False, prompts=(None, None), codec=None):
+                 clipiqa=False, sizes=None, want_lq=False, prompts=(None, None), codec=None, png_runs=False):
         """The plan phase, host work only: every size is checked and every ground truth compared with its image's FINAL size, so a batch that
         does not fit raises ValueError before anything is launched for it; then the scorer slots are filled / planned - `scorers` holds them in
         the order of a score tuple: paired (metrics.ScoreSlot; with lpips it scores LPIPS as well, ir_lpips with the weights lpips.configure()
         bound to the context), NIQE with `niqe` its parameters, CLIP-IQA - and the images copied into page-locked memory: the staging input, or
         the decoded files (with their degrade parameters) into the ResizeSlot, whose bicubic chain then makes the staging input on the device.
-        sizes: the batch's niqe_rects entry. codec: None - rects are coded as PNG - or _jpeg_codec()'s pair."""
+        sizes: the batch's niqe_rects entry. codec: None - rects are coded as PNG, in the run mode with png_runs - or _jpeg_codec()'s pair."""
         from .slots import final_sizes, record_sizes
         self.ctx, self.slot, self.tag, self.shape, self.with_stage1 = ctx, slot, tag, shape, with_stage1
         self.rects, self.records, self.dparams, self.prompts = rects, records, dparams, prompts
         self.want_lq = want_lq and dparams is not None
-        self.codec = codec
+        self.codec, self.png_runs = codec, bool(png_runs)
         self.enc = self.ready = self.done = None
         n, h, w = shape
         copies = 2 if with_stage1 else 1
@@ -293,7 +294,7 @@ class _Batch:
         graph is keyed by it."""
         n, h, w = self.shape
         if self.rects is not None and self.codec is None:
-            self.ctx.workspace(self.ctx.ws_bytes(L.STAGE_PNG, n, h, w))
+            self.ctx.workspace(self.ctx.ws_bytes(L.STAGE_PNG_RUNS if self.png_runs else L.STAGE_PNG, n, h, w))
         elif self.rects is not None:
             from .jpeg import RESTART_MCUS
             self.ctx.workspace(self.ctx.ws_bytes(L.STAGE_JPEG, n, h, w, self.codec[1], RESTART_MCUS))
@@ -323,7 +324,7 @@ class _Batch:
         self.outs = [(first, out, rs.back_to_lq(self.records, out, first) if rs is not None else None) for first, out in outs]
         if self.rects is not None:   # the batch keeps its own reference to the encoder: the pool evicts after 8 shapes
             if self.codec is None:
-                self.enc = _png_encoder(ctx, len(outs) * n, h, w, slot, self.tag)
+                self.enc = _png_encoder(ctx, len(outs) * n, h, w, slot, self.tag, self.png_runs)
             else:
                 self.enc = _jpeg_encoder(ctx, self.codec, len(outs) * n, h, w, slot, self.tag)
             for first, out, res in self.outs:
@@ -402,7 +403,7 @@ def process(model, control_imgs: List[np.ndarray], strength: float, color_fix_ty
             tile_size: int, tile_stride: int, preprocess_model=None, vae=None, y=None, y_mask=None, noise_scheduler=None,
             fused: bool = True, graph: bool = False, return_stage1: bool = True, fp8: bool = False, png=None,
             resize=None, gt=None, lpips: bool = False, niqe=None, niqe_rects=None, clipiqa: bool = False, degrade=None,
-            lq_sink=None, jpeg=None, jpeg_quality: int = 95, jpeg_subsampling=2) -> Tuple[List[np.ndarray], List[np.ndarray]]:
+            lq_sink=None, jpeg=None, jpeg_quality: int = 95, jpeg_subsampling=2, png_runs: bool = False) -> Tuple[List[np.ndarray], List[np.ndarray]]:
     """test_scripts/inference.py:55-166. control_imgs: list of HWC uint8 RGB arrays of equal size (multiples of 64).
     Returns (preds, stage1_preds) as lists of HWC uint8 arrays (stage1_preds is empty with return_stage1=False, which skips its
     conversion and download).
@@ -415,7 +416,8 @@ def process(model, control_imgs: List[np.ndarray], strength: float, color_fix_ty
     (vae.enable_fp8() must have uploaded the fp8 weight forms).
     png (fused form only): a list of one valid rectangle (vh, vw) per image. The results are then encoded on the GPU (ir_png_encode queued behind
     ir_pipeline - under graph=True behind the graph's replay, not inside the recording) and both lists hold PNG files as `bytes` of the
-    top-left vh x vw crops instead of arrays; only the compressed bytes are downloaded.
+    top-left vh x vw crops instead of arrays; only the compressed bytes are downloaded. png_runs=True (with png): the encoder's run mode,
+    ir_png_encode_runs - the same pixels, runs of equal filtered bytes coded as matches, no file larger than without it.
     jpeg (fused form only; exclusive with png): the same list of rectangles, and the lists hold baseline JPEG files instead - ir_jpeg_encode at
     jpeg_quality (1 .. 100) and jpeg_subsampling (2 or 420: 4:2:0, 0 or 444: 4:4:4), byte for byte PIL's Image.save(format="JPEG", quality,
     subsampling, restart_marker_blocks=jpeg.RESTART_MCUS) of the raw result. It combines with resize, degrade, gt, niqe and clipiqa as png does;
@@ -466,7 +468,7 @@ def process(model, control_imgs: List[np.ndarray], strength: float, color_fix_ty
             raise RuntimeError("process(fp8=True): call vae.enable_fp8() first - without the fp8 weight forms every layer would silently run in bf16")
         ctx = model.ctx
         batch = _Batch(ctx, 0, "sync", 1, (n, h, w), control_imgs, return_stage1, png if codec is None else jpeg, resize, degrade, gt, lpips, niqe,
-                       clipiqa, niqe_rects, lq_sink is not None, codec=codec)
+                       clipiqa, niqe_rects, lq_sink is not None, codec=codec, png_runs=png_runs)
         _prepare_fused(model, y, y_mask, h, w, tiled, tile_size, (vae, None if disable_preprocess_model else preprocess_model))
         flags = _pipeline_flags(model, color_fix_type, disable_preprocess_model, tiled) | (L.FLAG_GRAPH if graph else 0) | (L.FLAG_FP8 if fp8 else 0)
         batch.upload()
@@ -534,7 +536,7 @@ def process_stream(model, batches: Iterable[Sequence[np.ndarray]], color_fix_typ
                    return_stage1: bool = True, graph: bool = False, fp8: bool = False, png=None,
                    png_wrap: bool = True, resize=None, gt=None, lpips: bool = False, niqe=None,
                    niqe_rects=None, clipiqa: bool = False, degrade=None, lq_sink=None, jpeg=None, jpeg_quality: int = 95,
-                   jpeg_subsampling=2) -> Iterator[Tuple[List[np.ndarray], List[np.ndarray]]]:
+                   jpeg_subsampling=2, png_runs: bool = False) -> Iterator[Tuple[List[np.ndarray], List[np.ndarray]]]:
     """process() over a sequence of image batches with the transfers hidden: while batch i computes on the current stream, batch
     i+1 is uploaded and batch i-1 downloaded on a copy stream (two staging slots per batch shape). Yields process()'s result for
     every batch, in order. Needs the fused form (all models instarevive_amd objects on one context). fp8 as in process() (cfg-5:
@@ -549,6 +551,7 @@ def process_stream(model, batches: Iterable[Sequence[np.ndarray]], color_fix_typ
     batch's two lists hold PNG files (`bytes`, the top-left vh x vw crops) in place of arrays. The chunk framing (one CRC-32 over the compressed
     bytes and their copy into the file, about 20 ms per 2048 x 2048 result) is done on the calling thread between launches; png_wrap=False yields
     (zlib stream, width, height) triples instead, for png.wrap_png(*triple) on a thread of the caller's (what inference.py's writer pool does).
+    png_runs=True: every batch with png rectangles takes the encoder's run mode (ir_png_encode_runs), as in process().
     jpeg (exclusive with png): an iterable like png, and the files are JPEGs - ir_jpeg_encode at jpeg_quality / jpeg_subsampling, as in process().
     With png_wrap=False the lists hold (segment, width, height, quality, subsampling, restart_mcus) pieces for jpeg.wrap_jpeg(*pieces).
     resize: an iterable in step with `batches`, advanced like png: per batch None, or one resample.ResizeJob per image (the decoded file and its
@@ -610,7 +613,7 @@ def process_stream(model, batches: Iterable[Sequence[np.ndarray]], color_fix_typ
         with_nq = noref and (sizes is not None if nq_it is not None else (gts is not None or gt_it is None))
         imgs, by, bm = _split_batch(batch)
         b = _Batch(ctx, slot, "stream", 2, _batch_shape(imgs, records), imgs, return_stage1, rects, records, dparams, gts, lpips,
-                   niqe if with_nq else None, bool(clipiqa) and with_nq, sizes, lq_sink is not None, (by, bm), codec=codec)
+                   niqe if with_nq else None, bool(clipiqa) and with_nq, sizes, lq_sink is not None, (by, bm), codec=codec, png_runs=png_runs)
         with torch.cuda.stream(copy):
             b.ready = b.upload(copy, main)
         return b
@@ -788,15 +791,15 @@ class HipTileEngine:
                                       self.flags, self.sf, L.ptr(ws), ws.numel()), "ir_tiled_decode")
         return px[:k]
 
-    def blend_pixels(self, px_all, png=None):
-        """The assembled uint8 frames; with png (one valid rectangle per image) their PNG files, encoded on this GPU, as bytes."""
+    def blend_pixels(self, px_all, png=None, png_runs=False):
+        """The assembled uint8 frames; with png (one valid rectangle per image) their PNG files, encoded on this GPU (png_runs: in the run mode), as bytes."""
         n, h, w = self.shape
         out = torch.empty((n, h, w, 3), dtype=torch.uint8, device=self.device)
         ws, c = self._ws(), self.ctx
         c.check(c.lib.ir_tiled_blend_pixels(c.h, c.stream(), L.ptr(px_all.contiguous()), L.ptr(out), n, h, w, self.tile_size, self.tile_stride,
                                             L.ptr(ws), ws.numel()), "ir_tiled_blend_pixels")
         if png is not None:
-            enc = _png_encoder(c, n, h, w, 0, "tiles")
+            enc = _png_encoder(c, n, h, w, 0, "tiles", png_runs)
             enc.queue(0, out, png)
             enc.fetch_sizes()
             torch.cuda.current_stream(self.device).synchronize()
