@@ -689,7 +689,10 @@ int ir_op_geglu(ir_ctx* ctx, void* stream, const uint16_t* ag, uint16_t* out, lo
 /* VAE mid-block attention (one head, d = 512; ldm/modules/diffusionmodules/model.py:181-205) with both products on fp8 (e4m3) MFMA operands
  * (IR_FP8_VAE_MID_ATTENTION; attn_d512_fp8.hip): q / k / v / o [b][t][512] bf16, t a multiple of 128 (>= 256). ws receives, at its start, the
  * quantised tile images [b][t / 64][66560 B] (K8 rows of 528 B - the first dword of row 0's padding (offset 512) holds the K | V E8M0
- * exponent bytes - then V8^T rows of 64 B in the kernel's key order), then the flag and the V^T of the bf16 fallback. */
+ * exponent bytes - then V8^T rows of 64 B in the kernel's key order), then 256 B of flags and the V^T [512][t + 64] of the 4-wave fallback,
+ * then the V^T tile image of the bf16 d = 512 kernel (b * t * 512 * 2 bytes; every part rounded up to 256 B). The call runs the VAE's own
+ * chain: flag[0] (the fp8 kernel met a query it cannot handle) has the bf16 d = 512 kernel recompute the launch, flag[1] (that kernel's own
+ * overflow) the 4-wave rescaling kernel. */
 int ir_op_attention_d512_fp8(ir_ctx* ctx, void* stream, const uint16_t* q, const uint16_t* k, const uint16_t* v, uint16_t* o, int b, int t, float scale,
                              void* ws, size_t ws_bytes);
 /* DiT self-attention with both products on fp8 (e4m3) MFMA operands (IR_FP8_DIT_SELF_ATTENTION; attn_fp8.hip): q / k / v / o

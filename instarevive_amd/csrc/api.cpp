@@ -273,6 +273,68 @@ void layernorm(Run& r, const float* x, bf16_t* y, float* yf, const float* a, con
            ir_launch_layernorm(x, y, yf, a, b, rows, C, ldx, ldy, eps, 1L << 40, 0, r.s), "layernorm");
 }
 
+// ---------------------------------------------------------------- attention routes: which kernels, in which order, behind which overflow flag
+// AttnParams of B items x Hh heads of width D, head h in columns [h * D, (h + 1) * D) of a token row. key_bias / kb_bs, kv_groups and
+// ovf_flag / ovf_map stay zero: the callers that have them set them.
+AttnParams attn_params(const bf16_t* q, const bf16_t* k, const bf16_t* vt, bf16_t* o, int q_rs, int k_rs, int o_rs, long q_bs, long k_bs, long o_bs,
+                       long vt_bs, int B, int Hh, int Tq, int Tk, int Tk_pad, int D, float scale_log2) {
+    AttnParams p;
+    memset(&p, 0, sizeof p);
+    p.q = q; p.k = k; p.vt = vt; p.o = o;
+    p.q_rs = q_rs; p.k_rs = k_rs; p.o_rs = o_rs; p.q_hs = p.k_hs = p.o_hs = D;
+    p.q_bs = q_bs; p.k_bs = k_bs; p.o_bs = o_bs; p.vt_bs = vt_bs;
+    p.B = B; p.Hh = Hh; p.Tq = Tq; p.Tk = Tk; p.Tk_pad = Tk_pad; p.D = D; p.scale_log2 = scale_log2;
+    return p;
+}
+// DiT self-attention on e4m3 operands (attn_fp8.hip; p.ovf_flag set, v: the V rows, strides of p.k): the bf16 V^T p.vt is only built, and the
+// rescaling bf16 kernel only runs, if the fp8 kernel's fixed softmax reference was outgrown (flag).
+void attn_self_fp8(Run& r, const AttnParams& p, const bf16_t* v, uint8_t* tiles) {
+    LAUNCHK(r, PK_ATTN_SELF_FP8, 4.0 * p.B * p.Hh * (double)p.Tq * p.Tk * p.D, 0.0, ir_launch_flash_attn_fp8(p, v, tiles, r.s), "self_attn_fp8");
+    LAUNCH(r, PC_TRANSPOSE, 0.0, 0.0,
+           ir_launch_transpose_v(v, const_cast<bf16_t*>(p.vt), p.k_bs, p.k_rs, p.k_hs, p.B, p.Hh, p.Tk, p.Tk_pad, p.D, ir_attn_dv(p.D), r.s, p.ovf_flag), "transpose_v");
+    LAUNCHK(r, PK_ATTN_OTHER, 0.0, 0.0, ir_launch_flash_attn_fallback(p, r.s), "self_attn_fallback");
+}
+// d = 512, one image of T tokens ([T][512] rows) on the 4-wave rescaling kernel: V^T [512][T + 64] into vt, then the attention. With only_if
+// both launches return at once unless the flag is raised: the fallback behind a fixed-reference kernel.
+void attn_d512_rescale(Run& r, const bf16_t* q, const bf16_t* k, const bf16_t* v, bf16_t* o, bf16_t* vt, int T, float sc, const int* only_if = nullptr) {
+    const int C = 512, ld = ir_attn_tk_pad(T);
+    LAUNCH(r, PC_TRANSPOSE, 0.0, only_if ? 0.0 : 4.0 * (double)T * C, ir_launch_transpose_v(v, vt, 0, C, 128, 1, 4, T, ld, 128, 128, r.s, only_if), "transpose_v");
+    LAUNCH(r, PC_FLASH_ATTN, only_if ? 0.0 : 4.0 * (double)T * T * C, 0.0, ir_launch_flash_attn_d512(q, k, vt, o, T, C, C, ld, sc, r.s, only_if),
+           only_if ? "vae_flash_attn_fallback" : "vae_flash_attn");
+}
+// scratch of attn_d512: vt [512][T + 64] always; tiles [N][T][512] and 16 ints of flags unless the plain kernels run; f8tiles
+// (ir_attn_d512_fp8_tile_bytes) for fp8 operands
+struct AttnD512Scratch {
+    bf16_t *vt = nullptr, *vtt = nullptr;
+    uint8_t* f8tiles = nullptr;
+    int* flag = nullptr;
+};
+// The VAE mid-block attention at d = 512: q / k / v / o [N][T][512], T a multiple of 64. Three routes:
+//  * fp8 (BASELINE.json configs[4]; fp8 asked for and T one the kernel takes): both products on e4m3 operands (attn_d512_fp8.hip). Round 5: its
+//    fallback is the bf16 one-wave-per-SIMD kernel (which moves its reference in place and costs 6.5 ms at 65536 tokens), not the 4-wave rescaling
+//    kernel (11.8 ms): flag[0] = "the fp8 kernel could not handle a query" starts transpose_v_tiles + the v2 kernel, flag[1] = the v2 kernel's own
+//    (never seen) overflow starts the 4-wave pair behind.
+//  * bf16 (attn_d512.hip): no redundant score product, the whole batch in one launch, V^T in 32-key tiles; the 4-wave pair behind flag[0].
+//  * plain kernels: the 4-wave pair image by image, scores never leave the chip.
+void attn_d512(Run& r, const bf16_t* q, const bf16_t* k, const bf16_t* v, bf16_t* o, const AttnD512Scratch& w, int N, int T, float sc, bool fp8) {
+    const int C = 512;
+    const long TC = (long)T * C;
+    const bool v2 = !g_ir_plain_kernels, f8 = v2 && fp8 && ir_attn_d512_fp8_takes(T);
+    int* const flag2 = f8 ? w.flag + 1 : w.flag;   // the bf16 kernel's own flag: what the 4-wave pair at the end of the chain waits for
+    if (v2) {
+        LAUNCH(r, PC_OTHER, 0.0, 0.0, ir_launch_zero_f32(reinterpret_cast<float*>(w.flag), f8 ? 2 : 1, r.s), "zero");
+        if (f8)
+            LAUNCHK(r, PK_ATTN_D512_FP8, 4.0 * (double)N * T * T * C, 0.0,
+                   ir_launch_flash_attn_d512_fp8(q, k, v, o, w.f8tiles, N, T, C, C, TC, TC, sc, w.flag, r.s), "vae_flash_attn_fp8");
+        const int* only_if = f8 ? w.flag : nullptr;   // behind the fp8 kernel the bf16 kernel and its tiles are the fallback
+        LAUNCH(r, PC_TRANSPOSE, 0.0, f8 ? 0.0 : 4.0 * (double)N * T * C, ir_launch_transpose_v_tiles(v, w.vtt, N, T, C, TC, TC, r.s, only_if), "transpose_v_tiles");
+        LAUNCHK(r, PK_ATTN_D512, f8 ? 0.0 : 4.0 * (double)N * T * T * C, 0.0,
+               ir_launch_flash_attn_d512_v2(q, k, w.vtt, o, N, T, C, C, TC, TC, TC, sc, flag2, r.s, only_if), f8 ? "vae_flash_attn_fallback_v2" : "vae_flash_attn");
+        if (r.c->count_fb) LAUNCH(r, PC_OTHER, 0.0, 0.0, ir_launch_count_flag(w.flag, r.c->attn_fb, r.s), "count_flag");
+    }
+    for (int b = 0; b < N; ++b) attn_d512_rescale(r, q + b * TC, k + b * TC, v + b * TC, o + b * TC, w.vt, T, sc, v2 ? flag2 : nullptr);
+}
+
 // ---------------------------------------------------------------- tensor lookup
 struct Binder {
     ir_ctx* c;
@@ -495,7 +557,8 @@ struct AttnShard {
     bool force_fallback = false;           // part 0 again after ANOTHER rank's rows overflowed: all rows by the rescaling kernel
     int* flag_out = nullptr;               // device int that receives the overflow flag of part 0
 };
-// AttnBlock (model.py:181-205), single head, scores materialised per image in HBM (fp32 S, bf16 P).
+// AttnBlock (model.py:181-205), single head: at width 512 through attn_d512(), at any other width with the scores materialised per image in
+// HBM (fp32 S, bf16 P).
 int attnblock(Run& r, const AttnW& w, bf16_t* B[3], int ci, float* gws, int N, int H, int W, const AttnShard* sh = nullptr, int f8bit = 31) {
     const int t1 = (ci + 1) % 3, t2 = (ci + 2) % 3;
     const int C = w.n.c;
@@ -512,22 +575,22 @@ int attnblock(Run& r, const AttnW& w, bf16_t* B[3], int ci, float* gws, int N, i
     const long ld = T + 64;  // padded leading dimension of S, P and V^T: a power-of-two row stride would put every row of a
                              // tile on the same memory channel
     bf16_t* vt = r.a.alloc<bf16_t>(ld * C);
-    const bool flash = (C == 512 && (T & 63) == 0);
-    // d = 512 without the redundant score product (attn_d512.hip): the whole batch in one launch, V^T in 32-key tiles
+    const bool flash = (C == 512 && (T & 63) == 0);   // attn_d512(): scores never leave the chip
     const bool v2 = flash && !g_ir_plain_kernels;
-    // BASELINE.json configs[4]: both products on e4m3 operands (attn_d512_fp8.hip); the bf16 rescaling kernel stays behind it as the fallback
-    const bool f8 = v2 && r.c->fp8 && ((r.c->fp8_mask >> f8bit) & 1u) && ir_attn_d512_fp8_takes((int)T);
-    // (sized whenever the shape allows it, so that ir_workspace_bytes - which does not know the per-call IR_FLAG_FP8 - covers the fp8 call)
-    uint8_t* f8tiles = (v2 && ir_attn_d512_fp8_takes((int)T)) ? r.a.alloc<uint8_t>(ir_attn_d512_fp8_tile_bytes(N, (int)T)) : nullptr;
-    bf16_t* vtt = v2 ? r.a.alloc<bf16_t>((long)N * T * C) : nullptr;
-    int* flag = v2 ? r.a.alloc<int>(16) : nullptr;
+    // (the fp8 tile images are sized whenever the shape allows it, so that ir_workspace_bytes - which does not know the per-call IR_FLAG_FP8 -
+    // covers the fp8 call)
+    AttnD512Scratch ws;
+    ws.vt = vt;
+    ws.f8tiles = (v2 && ir_attn_d512_fp8_takes((int)T)) ? r.a.alloc<uint8_t>(ir_attn_d512_fp8_tile_bytes(N, (int)T)) : nullptr;
+    ws.vtt = v2 ? r.a.alloc<bf16_t>((long)N * T * C) : nullptr;
+    ws.flag = v2 ? r.a.alloc<int>(16) : nullptr;
+    int* flag = ws.flag;
     float* S = flash ? nullptr : r.a.alloc<float>(T * ld);
     bf16_t* P = flash ? nullptr : r.a.alloc<bf16_t>(T * ld);
     groupnorm(r, w.n, B[ci], B[t1], gws, N, T, 0);
     linear(r, w.q, B[t1], (int)(N * T), C, q, C, 0, ACT_NONE, nullptr, 0, 0);
     linear(r, w.k, B[t1], (int)(N * T), C, k, C, 0, ACT_NONE, nullptr, 0, 0);
     linear(r, w.v, B[t1], (int)(N * T), C, v, C, 0, ACT_NONE, nullptr, 0, 0);
-    const int dsub = (C % 128 == 0) ? 128 : (C % 64 == 0 ? 64 : 32);
     const float sc = 1.0f / sqrtf((float)C);
     if (sh && sh->part == 0) {   // (shape checked by the caller: N == 1, the d = 512 flash path, rows in whole workgroups)
         const int rows = sh->row1 - sh->row0;
@@ -535,56 +598,27 @@ int attnblock(Run& r, const AttnW& w, bf16_t* B[3], int ci, float* gws, int N, i
             LAUNCH(r, PC_OTHER, 0.0, 0.0, ir_launch_fill_u32(reinterpret_cast<uint32_t*>(flag), 1, 1u, r.s), "fill");
         } else {
             LAUNCH(r, PC_OTHER, 0.0, 0.0, ir_launch_zero_f32(reinterpret_cast<float*>(flag), 1, r.s), "zero");
-            LAUNCH(r, PC_TRANSPOSE, 0.0, 4.0 * (double)T * C, ir_launch_transpose_v_tiles(v, vtt, 1, (int)T, C, T * C, T * C, r.s), "transpose_v_tiles");
+            LAUNCH(r, PC_TRANSPOSE, 0.0, 4.0 * (double)T * C, ir_launch_transpose_v_tiles(v, ws.vtt, 1, (int)T, C, T * C, T * C, r.s), "transpose_v_tiles");
             if (rows > 0)
                 LAUNCHK(r, PK_ATTN_D512, 4.0 * (double)rows * T * C, 0.0,
-                       ir_launch_flash_attn_d512_v2_rows(q + (long)sh->row0 * C, k, vtt, sh->o + (long)sh->row0 * C, (int)T, rows, C, C, sc, flag, r.s), "vae_flash_attn_rows");
+                       ir_launch_flash_attn_d512_v2_rows(q + (long)sh->row0 * C, k, ws.vtt, sh->o + (long)sh->row0 * C, (int)T, rows, C, C, sc, flag, r.s), "vae_flash_attn_rows");
         }
         // overflow fallback (rare): this rank recomputes ALL rows with the rescaling kernel. The unsharded launch takes the fallback for every
         // row as soon as ANY row overflows, so the ranks must agree: the flag is handed to the host (ir_tiled_encode_overflow), the caller
         // MAX-reduces it over the ranks and a rank whose own rows did not overflow repeats part 0 with IR_ENCODE_PART_FORCE_FALLBACK
         // (parallel.sharded_encode) - then every rank holds all rows from the rescaling kernel, as the unsharded run does.
-        LAUNCH(r, PC_TRANSPOSE, 0.0, 0.0, ir_launch_transpose_v(v, vt, 0, C, dsub, 1, C / dsub, (int)T, (int)ld, dsub, dsub, r.s, flag), "transpose_v");
-        LAUNCH(r, PC_FLASH_ATTN, 0.0, 0.0, ir_launch_flash_attn_d512(q, k, vt, sh->o, (int)T, C, C, ld, sc, r.s, flag), "vae_flash_attn_fallback");
+        attn_d512_rescale(r, q, k, v, sh->o, vt, (int)T, sc, flag);
         if (r.live()) r.chk(hipMemcpyAsync(sh->res, B[ci], (size_t)T * C * 2, hipMemcpyDeviceToDevice, r.s) == hipSuccess ? 0 : -1, "save the block input");
         if (r.live() && sh->flag_out) r.chk(hipMemcpyAsync(sh->flag_out, flag, sizeof(int), hipMemcpyDeviceToDevice, r.s) == hipSuccess ? 0 : -1, "save the overflow flag");
         r.chain = nullptr;
         r.a.release(mk);
         return -1;   // stop here: the caller exchanges the rows
     }
-    int* flag4 = flag;   // the flag the 4-wave rescaling kernel at the end of the chain waits for
-    if (f8) {
-        // Round 5: the fp8 kernel's fallback is the bf16 one-wave-per-SIMD kernel (which moves its reference in place and costs 6.5 ms at 65536 tokens),
-        // not the 4-wave rescaling kernel (11.8 ms): flag[0] = "the fp8 kernel could not handle a query" starts transpose_v_tiles + the v2 kernel,
-        // flag[1] = the v2 kernel's own (never seen) overflow starts the 4-wave pair behind.
-        LAUNCH(r, PC_OTHER, 0.0, 0.0, ir_launch_zero_f32(reinterpret_cast<float*>(flag), 2, r.s), "zero");
-        LAUNCHK(r, PK_ATTN_D512_FP8, 4.0 * (double)N * T * T * C, 0.0,
-               ir_launch_flash_attn_d512_fp8(q, k, v, o, f8tiles, N, (int)T, C, C, T * C, T * C, sc, flag, r.s), "vae_flash_attn_fp8");
-        LAUNCH(r, PC_TRANSPOSE, 0.0, 0.0, ir_launch_transpose_v_tiles(v, vtt, N, (int)T, C, T * C, T * C, r.s, flag), "transpose_v_tiles");
-        LAUNCHK(r, PK_ATTN_D512, 0.0, 0.0, ir_launch_flash_attn_d512_v2(q, k, vtt, o, N, (int)T, C, C, T * C, T * C, T * C, sc, flag + 1, r.s, flag), "vae_flash_attn_fallback_v2");
-        flag4 = flag + 1;
-    } else if (v2) {
-        LAUNCH(r, PC_OTHER, 0.0, 0.0, ir_launch_zero_f32(reinterpret_cast<float*>(flag), 1, r.s), "zero");
-        LAUNCH(r, PC_TRANSPOSE, 0.0, 4.0 * (double)N * T * C, ir_launch_transpose_v_tiles(v, vtt, N, (int)T, C, T * C, T * C, r.s), "transpose_v_tiles");
-        LAUNCHK(r, PK_ATTN_D512, 4.0 * (double)N * T * T * C, 0.0,
-               ir_launch_flash_attn_d512_v2(q, k, vtt, o, N, (int)T, C, C, T * C, T * C, T * C, sc, flag, r.s), "vae_flash_attn");
-    }
-    if (v2 && r.c->count_fb) LAUNCH(r, PC_OTHER, 0.0, 0.0, ir_launch_count_flag(flag, r.c->attn_fb, r.s), "count_flag");
-    for (int b = 0; b < N; ++b) {
-        if (v2) {  // fallback with the rescaling softmax: both launches return at once unless the kernel above raised the flag
-            LAUNCH(r, PC_TRANSPOSE, 0.0, 0.0, ir_launch_transpose_v(v + b * T * C, vt, 0, C, dsub, 1, C / dsub, (int)T, (int)ld, dsub, dsub, r.s, flag4), "transpose_v");
-            LAUNCH(r, PC_FLASH_ATTN, 0.0, 0.0, ir_launch_flash_attn_d512(q + b * T * C, k + b * T * C, vt, o + b * T * C, (int)T, C, C, ld, sc, r.s, flag4),
-                   "vae_flash_attn_fallback");
-            continue;
-        }
+    if (flash) attn_d512(r, q, k, v, o, ws, N, (int)T, sc, r.c->fp8 && ((r.c->fp8_mask >> f8bit) & 1u));
+    const int dsub = (C % 128 == 0) ? 128 : (C % 64 == 0 ? 64 : 32);
+    for (int b = 0; !flash && b < N; ++b) {   // generic width (reduced test configurations)
         LAUNCH(r, PC_TRANSPOSE, 0.0, 4.0 * (double)T * C, ir_launch_transpose_v(v + b * T * C, vt, 0, C, dsub, 1, C / dsub, (int)T, (int)ld, dsub, dsub, r.s),
                "transpose_v");
-        if (flash) {  // flash path: scores never leave the chip
-            LAUNCH(r, PC_FLASH_ATTN, 4.0 * (double)T * T * C, 0.0,
-                   ir_launch_flash_attn_d512(q + b * T * C, k + b * T * C, vt, o + b * T * C, (int)T, C, C, ld, sc, r.s), "vae_flash_attn");
-            continue;
-        }
-        // generic width (reduced test configurations): scores materialised per image in HBM (fp32 S, bf16 P)
         Conv kw;  // S = q k^T * C^-0.5 : the keys play the role of the weight matrix [T][C]
         kw.w = k + b * T * C; kw.b = nullptr; kw.cin = C; kw.cout = (int)T; kw.cout_pad = (int)T; kw.taps = 1;
         linear(r, kw, q + b * T * C, (int)T, C, S, (int)ld, 1, ACT_NONE, nullptr, 0, 0, nullptr, 0, nullptr, 0, sc);
@@ -850,75 +884,48 @@ void dit_block(Run& r, const DitLayer& Lw, const float* mod, float* x, const Dit
     const float sl2 = (1.0f / sqrtf((float)hd)) * 1.44269504088896340736f;
     layernorm(r, x, b.xn, nullptr, mod + C, mod, BT, C, C, C, 1e-6f);
     const bool kvc = Lw.kvc_r > 1;
-    const bool attn8_pre = !kvc && r.c->fp8 && (r.c->fp8_mask & (1u << IR_FP8_BIT_DIT_ATTN)) && b.f8tiles && hd == 72 && (T & 63) == 0 && T >= 256 && !g_ir_plain_kernels;
-    if (b.vt_ready && !attn8_pre && !r.c->plain && !kvc) {   // the projection's epilogue writes V^T itself (gemm_pp_kernel at >= 12 k tokens): no transpose launch
+    // BASELINE.json configs[4]: both attention products on e4m3 operands (attn_self_fp8)
+    const bool attn8 = !kvc && r.c->fp8 && (r.c->fp8_mask & (1u << IR_FP8_BIT_DIT_ATTN)) && b.f8tiles && hd == 72 && (T & 63) == 0 && T >= 256 && !g_ir_plain_kernels;
+    if (b.vt_ready && !attn8 && !r.c->plain && !kvc) {   // the projection's epilogue writes V^T itself (gemm_pp_kernel at >= 12 k tokens): no transpose launch
         r.vt_out = b.vt; r.vt_col0 = 2 * C; r.vt_hd = hd; r.vt_dv = DV; r.vt_ld = Tpad; r.vt_T = (int)T; r.vt_bs = (long)Hh * DV * Tpad;
     }
     linear(r, Lw.qkv, b.xn, (int)BT, C, b.qkv, 3 * C, 0, ACT_NONE, nullptr, 0, 0);
     const bool vt_fused = r.vt_done;
     r.vt_done = false;
-    // BASELINE.json configs[4]: both attention products on e4m3 operands (attn_fp8.hip). The bf16 V^T is only built if the kernel's
-    // fixed softmax reference was outgrown (flag), for the rescaling fallback behind it.
-    const bool attn8 = !kvc && r.c->fp8 && (r.c->fp8_mask & (1u << IR_FP8_BIT_DIT_ATTN)) && b.f8tiles && hd == 72 && (T & 63) == 0 && T >= 256 && !g_ir_plain_kernels;
     if (r.live() && Lw.qn_g) {   // qk_norm (PixArt_blocks.py:136-137): LayerNorm over all C channels of q and of k, in place on the qkv rows
         LAUNCH(r, PC_LAYERNORM, 0.0, 4.0 * BT * C, ir_launch_dit_token_prep(b.qkv, b.qkv, nullptr, nullptr, Lw.qn_g, Lw.qn_b, n, b.gh, b.gw, 1, C, 3 * C, T * 3 * C, 3 * C, T * 3 * C, r.s), "q_norm");
         LAUNCH(r, PC_LAYERNORM, 0.0, 4.0 * BT * C, ir_launch_dit_token_prep(b.qkv + C, b.qkv + C, nullptr, nullptr, Lw.kn_g, Lw.kn_b, n, b.gh, b.gw, 1, C, 3 * C, T * 3 * C, 3 * C, T * 3 * C, r.s), "k_norm");
     }
-    if (r.live() && kvc) {
-        // KV compression (:139-142): k and v through the same sampler, attention of all T queries over T / r^2 keys
-        const int rr = Lw.kvc_r;
-        const long Tc = T / ((long)rr * rr);
-        const int Tcpad = (int)((Tc + 63) & ~63L) + 64;
-        LAUNCH(r, PC_OTHER, 0.0, 2.0 * BT * C, ir_launch_dit_token_prep(b.qkv + C, b.kcmp, Lw.kvc_w, Lw.kvc_b, Lw.kvc_g, Lw.kvc_beta, n, b.gh, b.gw, rr, C, 3 * C, T * 3 * C, C, Tc * C, r.s), "kv_compress_k");
-        LAUNCH(r, PC_OTHER, 0.0, 2.0 * BT * C, ir_launch_dit_token_prep(b.qkv + 2 * C, b.vcmp, Lw.kvc_w, Lw.kvc_b, Lw.kvc_g, Lw.kvc_beta, n, b.gh, b.gw, rr, C, 3 * C, T * 3 * C, C, Tc * C, r.s), "kv_compress_v");
-        LAUNCH(r, PC_TRANSPOSE, 0.0, 0.0, ir_launch_transpose_v(b.vcmp, b.vtcmp, Tc * C, C, hd, n, Hh, (int)Tc, Tcpad, hd, DV, r.s), "transpose_v");
-        AttnParams p;
-        memset(&p, 0, sizeof p);
-        p.q = b.qkv; p.k = b.kcmp; p.vt = b.vtcmp; p.o = b.att;
-        p.q_bs = T * 3 * C; p.k_bs = Tc * C; p.o_bs = T * C; p.vt_bs = (long)Hh * DV * Tcpad;
-        p.q_rs = 3 * C; p.k_rs = C; p.o_rs = C; p.q_hs = p.k_hs = p.o_hs = hd;
-        p.B = n; p.Hh = Hh; p.Tq = (int)T; p.Tk = (int)Tc; p.Tk_pad = Tcpad; p.D = hd; p.scale_log2 = sl2;
+    if (r.live()) {
+        const bf16_t* v = b.qkv + 2 * C;
+        AttnParams p = attn_params(b.qkv, b.qkv + C, b.vt, b.att, 3 * C, 3 * C, C, T * 3 * C, T * 3 * C, T * C, (long)Hh * DV * Tpad, n, Hh, (int)T, (int)T, Tpad, hd, sl2);
         p.ovf_flag = b.attn_flag;
-        p.ovf_map = b.attn_map;
-        const bool pp2 = ir_flash_attn_is_pp2(p);
-        LAUNCHK(r, pp2 ? PK_ATTN_SELF : PK_ATTN_OTHER, 4.0 * n * Hh * (double)T * Tc * hd, 0.0, ir_launch_flash_attn(p, r.s), "self_attn_kvc");
-        if (pp2 && r.c->count_fb) LAUNCH(r, PC_OTHER, 0.0, 0.0, ir_launch_count_flag(b.attn_flag, r.c->attn_fb, r.s), "count_flag");
-    } else if (r.live() && attn8) {
-        AttnParams p;
-        memset(&p, 0, sizeof p);
-        p.q = b.qkv; p.k = b.qkv + C; p.vt = b.vt; p.o = b.att;
-        p.q_bs = p.k_bs = T * 3 * C; p.o_bs = T * C; p.vt_bs = (long)Hh * DV * Tpad;
-        p.q_rs = p.k_rs = 3 * C; p.o_rs = C; p.q_hs = p.k_hs = p.o_hs = hd;
-        p.B = n; p.Hh = Hh; p.Tq = (int)T; p.Tk = (int)T; p.Tk_pad = Tpad; p.D = hd; p.scale_log2 = sl2;
-        p.ovf_flag = b.attn_flag;
-        LAUNCHK(r, PK_ATTN_SELF_FP8, 4.0 * n * Hh * (double)T * T * hd, 0.0, ir_launch_flash_attn_fp8(p, b.qkv + 2 * C, b.f8tiles, r.s), "self_attn_fp8");
-        LAUNCH(r, PC_TRANSPOSE, 0.0, 0.0, ir_launch_transpose_v(b.qkv + 2 * C, b.vt, T * 3 * C, 3 * C, hd, n, Hh, (int)T, Tpad, hd, DV, r.s, b.attn_flag), "transpose_v");
-        LAUNCHK(r, PK_ATTN_OTHER, 0.0, 0.0, ir_launch_flash_attn_fallback(p, r.s), "self_attn_fallback");
-        if (r.c->count_fb) LAUNCH(r, PC_OTHER, 0.0, 0.0, ir_launch_count_flag(b.attn_flag, r.c->attn_fb, r.s), "count_flag");
-    } else if (r.live()) {
-        if (!vt_fused) LAUNCH(r, PC_TRANSPOSE, 0.0, 0.0, ir_launch_transpose_v(b.qkv + 2 * C, b.vt, T * 3 * C, 3 * C, hd, n, Hh, (int)T, Tpad, hd, DV, r.s), "transpose_v");
-        AttnParams p;
-        memset(&p, 0, sizeof p);
-        p.q = b.qkv; p.k = b.qkv + C; p.vt = b.vt; p.o = b.att;
-        p.q_bs = p.k_bs = T * 3 * C; p.o_bs = T * C; p.vt_bs = (long)Hh * DV * Tpad;
-        p.q_rs = p.k_rs = 3 * C; p.o_rs = C; p.q_hs = p.k_hs = p.o_hs = hd;
-        p.B = n; p.Hh = Hh; p.Tq = (int)T; p.Tk = (int)T; p.Tk_pad = Tpad; p.D = hd; p.scale_log2 = sl2;
-        p.ovf_flag = b.attn_flag;
-        p.ovf_map = b.attn_map;
-        const bool pp2 = ir_flash_attn_is_pp2(p);
-        LAUNCHK(r, pp2 ? PK_ATTN_SELF : PK_ATTN_OTHER, 4.0 * n * Hh * (double)T * T * hd, 0.0, ir_launch_flash_attn(p, r.s), "self_attn");
-        if (pp2 && r.c->count_fb) LAUNCH(r, PC_OTHER, 0.0, 0.0, ir_launch_count_flag(b.attn_flag, r.c->attn_fb, r.s), "count_flag");
+        p.ovf_map = attn8 ? 0 : b.attn_map;   // (the fp8 kernel's fallback recomputes the whole launch)
+        if (kvc) {
+            // KV compression (:139-142): k and v through the same sampler, attention of all T queries over T / r^2 keys
+            const int rr = Lw.kvc_r;
+            const long Tc = T / ((long)rr * rr);
+            LAUNCH(r, PC_OTHER, 0.0, 2.0 * BT * C, ir_launch_dit_token_prep(b.qkv + C, b.kcmp, Lw.kvc_w, Lw.kvc_b, Lw.kvc_g, Lw.kvc_beta, n, b.gh, b.gw, rr, C, 3 * C, T * 3 * C, C, Tc * C, r.s), "kv_compress_k");
+            LAUNCH(r, PC_OTHER, 0.0, 2.0 * BT * C, ir_launch_dit_token_prep(v, b.vcmp, Lw.kvc_w, Lw.kvc_b, Lw.kvc_g, Lw.kvc_beta, n, b.gh, b.gw, rr, C, 3 * C, T * 3 * C, C, Tc * C, r.s), "kv_compress_v");
+            p.k = b.kcmp; p.vt = b.vtcmp; p.k_bs = Tc * C; p.k_rs = C; p.Tk = (int)Tc; p.Tk_pad = ir_attn_tk_pad((int)Tc); p.vt_bs = (long)Hh * DV * p.Tk_pad;
+            LAUNCH(r, PC_TRANSPOSE, 0.0, 0.0, ir_launch_transpose_v(b.vcmp, b.vtcmp, p.k_bs, C, hd, n, Hh, p.Tk, p.Tk_pad, hd, DV, r.s), "transpose_v");
+        } else if (!attn8 && !vt_fused) {
+            LAUNCH(r, PC_TRANSPOSE, 0.0, 0.0, ir_launch_transpose_v(v, b.vt, T * 3 * C, 3 * C, hd, n, Hh, (int)T, Tpad, hd, DV, r.s), "transpose_v");
+        }
+        bool fixed_ref = attn8;   // a kernel with a fixed softmax reference runs, and raises b.attn_flag when it was outgrown
+        if (attn8) {
+            attn_self_fp8(r, p, v, b.f8tiles);
+        } else {
+            fixed_ref = ir_flash_attn_is_pp2(p);
+            LAUNCHK(r, fixed_ref ? PK_ATTN_SELF : PK_ATTN_OTHER, 4.0 * n * Hh * (double)T * p.Tk * hd, 0.0, ir_launch_flash_attn(p, r.s), kvc ? "self_attn_kvc" : "self_attn");
+        }
+        if (fixed_ref && r.c->count_fb) LAUNCH(r, PC_OTHER, 0.0, 0.0, ir_launch_count_flag(b.attn_flag, r.c->attn_fb, r.s), "count_flag");
     }
     linear(r, Lw.ao, b.att, (int)BT, C, x, C, 1, ACT_NONE, x, 1, C, b.xb, C, mod + 2 * C);
     // cross attention on the un-normalised stream (PixArtMS.py:76); K/V of the prompt are cached per layer
     linear(r, Lw.cq, b.xb, (int)BT, C, b.cq, C, 0, ACT_NONE, nullptr, 0, 0);
     if (r.live()) {
-        AttnParams p;
-        memset(&p, 0, sizeof p);
-        p.q = b.cq; p.k = Lw.kc; p.vt = Lw.vtc; p.o = b.att;
-        p.q_bs = T * C; p.k_bs = m.kc_slot; p.o_bs = T * C; p.vt_bs = m.vt_slot;
-        p.q_rs = C; p.k_rs = 2 * C; p.o_rs = C; p.q_hs = p.k_hs = p.o_hs = hd;
-        p.B = n; p.Hh = Hh; p.Tq = (int)T; p.Tk = m.n_tok; p.Tk_pad = m.tok_pad; p.D = hd; p.scale_log2 = sl2;
+        AttnParams p = attn_params(b.cq, Lw.kc, Lw.vtc, b.att, C, 2 * C, C, T * C, m.kc_slot, T * C, m.vt_slot, n, Hh, (int)T, m.n_tok, m.tok_pad, hd, sl2);
         p.key_bias = m.key_bias; p.kb_bs = m.kb_slot;
         p.kv_groups = m.n_prompts;   // item b (= tile * images + image) takes prompt slot b % P
         LAUNCHK(r, PK_ATTN_CROSS, 4.0 * n * Hh * (double)T * m.n_tok * hd, 0.0, ir_launch_flash_attn(p, r.s), "cross_attn");
@@ -936,7 +943,7 @@ void dit_bufs_init(Run& r, DitBufs& b, int n, int gh, int gw) {
     const int C = m.C, Hh = m.heads, hd = m.hd;
     const long T = (long)gh * gw, BT = n * T;
     b.n = n; b.T = T;
-    b.Tpad = (int)((T + 63) & ~63L) + 64; b.DV = ir_attn_dv(hd);  // +64: no power-of-two row stride (channel conflicts)
+    b.Tpad = ir_attn_tk_pad((int)T); b.DV = ir_attn_dv(hd);
     b.xb = r.a.alloc<bf16_t>(BT * C);
     b.xn = r.a.alloc<bf16_t>(BT * C);
     b.qkv = r.a.alloc<bf16_t>(BT * 3 * C);
@@ -948,7 +955,7 @@ void dit_bufs_init(Run& r, DitBufs& b, int n, int gh, int gw) {
         const long Tc = T / ((long)b.rmin * b.rmin);
         b.kcmp = r.a.alloc<bf16_t>(n * Tc * C);
         b.vcmp = r.a.alloc<bf16_t>(n * Tc * C);
-        b.vtcmp = r.a.alloc<bf16_t>((long)n * Hh * b.DV * ((int)((Tc + 63) & ~63L) + 64));
+        b.vtcmp = r.a.alloc<bf16_t>((long)n * Hh * b.DV * ir_attn_tk_pad((int)Tc));
     }
     b.attn_map = (int)((long)n * Hh * ((T + 255) / 256));   // one int per 256-query workgroup of the self-attention behind the flag itself
     b.attn_flag = r.a.alloc<int>(16 + b.attn_map);  // [0]: overflow flag of the fixed-reference self-attention kernel; [1 ..]: which of its workgroups overflowed
@@ -1057,7 +1064,7 @@ void ures(Run& r, const UResW& w, const bf16_t* x, int N, int H, int W, bf16_t* 
 void uxf(Run& r, const UNetW& m, const UXfW& w, const bf16_t* h, int N, long HW, bf16_t* out, int out_cs, const UBufs& b) {
     const int C = w.gn.c, Hh = w.heads, hd = m.hd, DV = ir_attn_dv(hd);
     const long BT = N * HW;
-    const int Tpad = (int)((HW + 63) & ~63L) + 64;
+    const int Tpad = ir_attn_tk_pad((int)HW);
     const float sl2 = (1.0f / sqrtf((float)hd)) * 1.44269504088896340736f;
     gn_any(r, w.gn, h, b.t1, b.gws, N, HW, 0, 1e-6f);
     linear(r, w.pin, b.t1, (int)BT, C, b.x, C, 1, ACT_NONE, nullptr, 0, 0);
@@ -1066,25 +1073,15 @@ void uxf(Run& r, const UNetW& m, const UXfW& w, const bf16_t* h, int N, long HW,
     linear(r, w.qkv, b.xn, (int)BT, C, b.qkv, 3 * C, 0, ACT_NONE, nullptr, 0, 0);
     LAUNCH(r, PC_TRANSPOSE, 0.0, 0.0, ir_launch_transpose_v(b.qkv + 2 * C, b.vt, HW * 3 * C, 3 * C, hd, N, Hh, (int)HW, Tpad, hd, DV, r.s), "transpose_v");
     if (r.live()) {
-        AttnParams p;
-        memset(&p, 0, sizeof p);
-        p.q = b.qkv; p.k = b.qkv + C; p.vt = b.vt; p.o = b.att;
-        p.q_bs = p.k_bs = HW * 3 * C; p.o_bs = HW * C; p.vt_bs = (long)Hh * DV * Tpad;
-        p.q_rs = p.k_rs = 3 * C; p.o_rs = C; p.q_hs = p.k_hs = p.o_hs = hd;
-        p.B = N; p.Hh = Hh; p.Tq = (int)HW; p.Tk = (int)HW; p.Tk_pad = Tpad; p.D = hd; p.scale_log2 = sl2;
+        const AttnParams p = attn_params(b.qkv, b.qkv + C, b.vt, b.att, 3 * C, 3 * C, C, HW * 3 * C, HW * 3 * C, HW * C, (long)Hh * DV * Tpad, N, Hh, (int)HW, (int)HW, Tpad, hd, sl2);
         LAUNCHK(r, PK_ATTN_OTHER, 4.0 * N * Hh * (double)HW * HW * hd, 0.0, ir_launch_flash_attn(p, r.s), "unet_self_attn");
     }
     linear(r, w.ao, b.att, (int)BT, C, b.x, C, 1, ACT_NONE, b.x, 1, C);
     // attn2: cross-attention to the context (K / V cached per layer)
     layernorm(r, b.x, b.xn, nullptr, w.l2.g, w.l2.b, BT, C, C, C, 1e-5f);
     linear(r, w.cq, b.xn, (int)BT, C, b.cq, C, 0, ACT_NONE, nullptr, 0, 0);
-    if (r.live()) {
-        AttnParams p;
-        memset(&p, 0, sizeof p);
-        p.q = b.cq; p.k = w.kc; p.vt = w.vtc; p.o = b.att;
-        p.q_bs = HW * C; p.k_bs = 0; p.o_bs = HW * C; p.vt_bs = 0;
-        p.q_rs = C; p.k_rs = 2 * C; p.o_rs = C; p.q_hs = p.k_hs = p.o_hs = hd;
-        p.B = N; p.Hh = Hh; p.Tq = (int)HW; p.Tk = m.n_tok; p.Tk_pad = m.tok_pad; p.D = hd; p.scale_log2 = sl2;
+    if (r.live()) {   // (one context for the whole batch: no batch stride on K / V^T)
+        const AttnParams p = attn_params(b.cq, w.kc, w.vtc, b.att, C, 2 * C, C, HW * C, 0, HW * C, 0, N, Hh, (int)HW, m.n_tok, m.tok_pad, hd, sl2);
         LAUNCHK(r, PK_ATTN_OTHER, 4.0 * N * Hh * (double)HW * m.n_tok * hd, 0.0, ir_launch_flash_attn(p, r.s), "unet_cross_attn");
     }
     linear(r, w.co, b.att, (int)BT, C, b.x, C, 1, ACT_NONE, b.x, 1, C);
@@ -1132,7 +1129,7 @@ void usizes_block(const UNetW& m, const UBlock& blk, int N, int H, int W, USizes
     z.cmax = std::max(z.cmax, c);
     if (blk.has_xf) {
         z.xc = std::max(z.xc, T * blk.cout);
-        const int Tpad = (int)(((long)H * W + 63) & ~63L) + 64;
+        const int Tpad = ir_attn_tk_pad(H * W);
         z.vt = std::max(z.vt, (long)N * blk.xf.heads * ir_attn_dv(m.hd) * Tpad);
     }
 }
@@ -1941,7 +1938,7 @@ int ir_dit_set_prompt(ir_ctx* c, void* stream, const float* embeds_host, const f
     HIPOK(c, hipSetDevice(c->device));
     hipStream_t s = (hipStream_t)stream;
     const int C = m.C;
-    const int tok_pad = ((n_tok + 63) & ~63) + 64;
+    const int tok_pad = ir_attn_tk_pad(n_tok);
     struct Temps {   // freed on every exit path (the HIPOK early returns included)
         void* p[4] = {nullptr, nullptr, nullptr, nullptr};
         ~Temps() { for (void* q : p) if (q) (void)hipFree(q); }
@@ -1978,7 +1975,7 @@ int ir_dit_set_prompts(ir_ctx* c, void* stream, const float* embeds_dev, const f
     HIPOK(c, hipSetDevice(c->device));
     hipStream_t s = (hipStream_t)stream;
     const int C = m.C, DV = ir_attn_dv(m.hd), P = n_prompts;
-    const int tok_pad = ((n_tok + 63) & ~63) + 64;
+    const int tok_pad = ir_attn_tk_pad(n_tok);
     const long rows = (long)P * n_tok;
     if ((long)P * tok_pad * std::max(m.cap, 2 * C) >= (1L << 31)) return fail(c, -1, "ir_dit_set_prompts: %d prompts of %d tokens is too many", P, n_tok);
     const bool realloc = !m.key_bias || c->prompt_cap != tok_pad || c->prompt_slots < P || !c->prompt_e16;
@@ -2140,7 +2137,7 @@ int ir_unet_set_context(ir_ctx* c, void* stream, const float* context_host, int 
     if (!c || !context_host || n_tok <= 0 || (!c->unet[0].ok && !c->unet[1].ok)) return fail(c, -1, "ir_unet_set_context: bad argument / no UNet configured");
     HIPOK(c, hipSetDevice(c->device));
     hipStream_t s = (hipStream_t)stream;
-    const int tok_pad = ((n_tok + 63) & ~63) + 64;
+    const int tok_pad = ir_attn_tk_pad(n_tok);
     const int ctx_dim = c->unet[0].ok ? c->unet[0].ctx_dim : c->unet[1].ctx_dim;
     struct Temps {
         void* p[2] = {nullptr, nullptr};
@@ -3074,112 +3071,83 @@ int ir_op_layernorm(ir_ctx* c, void* stream, const float* x, uint16_t* y, const 
 // kv_groups 0: item i has its own set (sets = b); > 0: item i attends to set i % kv_groups (the launcher routes on it).
 static int attention_generic(ir_ctx* c, void* stream, const uint16_t* q, const uint16_t* k, const uint16_t* v, uint16_t* o, int b, int heads, int tq, int tk,
                              int d, float scale, const float* key_bias, int sets, int kv_groups, void* ws, size_t ws_bytes) {
-    const int DV = ir_attn_dv(d), tkp = ((tk + 63) & ~63) + 64;
+    const int DV = ir_attn_dv(d), tkp = ir_attn_tk_pad(tk);
     const size_t need = (size_t)sets * heads * DV * tkp * 2;
     if (ws_bytes < need) return fail(c, -20, "attention workspace too small: need %zu", need);
-    hipStream_t s = (hipStream_t)stream;
-    int rc = ir_launch_transpose_v(v, (bf16_t*)ws, (long)tk * heads * d, heads * d, d, sets, heads, tk, tkp, d, DV, s);
-    if (rc) return fail(c, rc, "transpose_v failed (%d)", rc);
-    AttnParams p;
-    memset(&p, 0, sizeof p);
-    p.q = q; p.k = k; p.vt = (const bf16_t*)ws; p.o = o;
+    if (!c) return fail(c, -1, "attention: null context");
+    Run r = make_run(c, stream, nullptr, 0, false);
+    const long hd = (long)heads * d;
+    LAUNCH(r, PC_TRANSPOSE, 0.0, 0.0, ir_launch_transpose_v(v, (bf16_t*)ws, tk * hd, (int)hd, d, sets, heads, tk, tkp, d, DV, r.s), "transpose_v");
+    AttnParams p = attn_params(q, k, (const bf16_t*)ws, o, (int)hd, (int)hd, (int)hd, tq * hd, tk * hd, tq * hd, (long)heads * DV * tkp, b, heads, tq, tk, tkp, d,
+                               scale * 1.44269504088896340736f);
     if (ws_bytes >= need + 64) {
         const size_t off = (need + 15) & ~(size_t)15;
         p.ovf_flag = (int*)((char*)ws + off);
         p.ovf_map = (int)std::min<size_t>((ws_bytes - off) / 4 - 1, (size_t)1 << 24);   // what is left behind the flag word: the per-workgroup overflow map if it fits
     }
-    p.q_bs = (long)tq * heads * d; p.k_bs = (long)tk * heads * d; p.o_bs = p.q_bs; p.vt_bs = (long)heads * DV * tkp;
-    p.q_rs = p.k_rs = p.o_rs = heads * d; p.q_hs = p.k_hs = p.o_hs = d;
-    p.B = b; p.Hh = heads; p.Tq = tq; p.Tk = tk; p.Tk_pad = tkp; p.D = d;
-    p.scale_log2 = scale * 1.44269504088896340736f;
     p.key_bias = key_bias; p.kb_bs = tk;
     p.kv_groups = kv_groups;
-    rc = ir_launch_flash_attn(p, s);
-    return rc ? fail(c, rc, "flash_attn failed (%d)", rc) : 0;
+    LAUNCHK(r, ir_flash_attn_is_pp2(p) ? PK_ATTN_SELF : PK_ATTN_OTHER, 4.0 * b * heads * (double)tq * tk * d, 0.0, ir_launch_flash_attn(p, r.s), "flash_attn");
+    return finish(r, c, ws_bytes);
 }
 int ir_op_attention(ir_ctx* c, void* stream, const uint16_t* q, const uint16_t* k, const uint16_t* v, uint16_t* o, int b, int heads,
                     int tq, int tk, int d, float scale, const float* key_bias, void* ws, size_t ws_bytes) {
     // q/o: [b][tq][heads*d], k/v: [b][tk][heads*d]
-    use_ctx(c);
-    const int tkp = ((tk + 63) & ~63) + 64;
-    if (heads == 1 && d == 512 && tq == tk && key_bias == nullptr) {  // VAE mid-block form
-        const size_t old_vt = ((size_t)512 * tkp * 2 + 255) & ~(size_t)255, tiles = ((size_t)b * tk * 512 * 2 + 255) & ~(size_t)255;
-        const bool v2 = !g_ir_plain_kernels && (tk & 31) == 0;
-        const size_t need512 = old_vt + (v2 ? tiles + 256 : 0);
-        if (ws_bytes < need512) return fail(c, -20, "attention workspace too small: need %zu", need512);
-        hipStream_t s = (hipStream_t)stream;
-        int* flag = nullptr;
-        if (v2) {
-            bf16_t* vtt = reinterpret_cast<bf16_t*>((char*)ws + old_vt);
-            flag = reinterpret_cast<int*>((char*)ws + old_vt + tiles);
-            int rc = ir_launch_zero_f32(reinterpret_cast<float*>(flag), 1, s);
-            if (!rc) rc = ir_launch_transpose_v_tiles(v, vtt, b, tk, 512, (long)tk * 512, (long)tk * 512, s);
-            if (!rc) rc = ir_launch_flash_attn_d512_v2(q, k, vtt, o, b, tq, 512, 512, (long)tq * 512, (long)tk * 512, (long)tq * 512, scale, flag, s);
-            if (rc) return fail(c, rc, "flash_attn_d512_v2 failed (%d)", rc);
-        }
-        for (int i = 0; i < b; ++i) {  // v2: the fallback, which returns at once unless the flag was raised
-            int rc = ir_launch_transpose_v(v + (long)i * tk * 512, (bf16_t*)ws, 0, 512, 128, 1, 4, tk, tkp, 128, 128, s, flag);
-            if (!rc) rc = ir_launch_flash_attn_d512(q + (long)i * tq * 512, k + (long)i * tk * 512, (const bf16_t*)ws, o + (long)i * tq * 512, tq, 512, 512,
-                                                    tkp, scale, s, flag);
-            if (rc) return fail(c, rc, "flash_attn_d512 failed (%d)", rc);
-        }
-        return 0;
+    if (!(heads == 1 && d == 512 && tq == tk && key_bias == nullptr))
+        return attention_generic(c, stream, q, k, v, o, b, heads, tq, tk, d, scale, key_bias, b, 0, ws, ws_bytes);
+    // VAE mid-block form: attnblock()'s chain on bf16 operands. ws: old V^T | V^T tiles | flag
+    if (tk & 63) return fail(c, -2, "ir_op_attention: the d = 512 form takes token counts that are multiples of 64 (got %d)", tk);
+    if (!c) return fail(c, -1, "attention: null context");
+    Run r = make_run(c, stream, ws, ws_bytes, false);
+    AttnD512Scratch w;
+    w.vt = r.a.alloc<bf16_t>(512L * ir_attn_tk_pad(tk));
+    if (!g_ir_plain_kernels) {
+        w.vtt = r.a.alloc<bf16_t>((long)b * tk * 512);
+        w.flag = r.a.alloc<int>(16);
     }
-    return attention_generic(c, stream, q, k, v, o, b, heads, tq, tk, d, scale, key_bias, b, 0, ws, ws_bytes);
+    if (r.a.overflow) return fail(c, -20, "attention workspace too small: need %zu", r.a.peak);
+    attn_d512(r, q, k, v, o, w, b, tk, scale, false);
+    return finish(r, c, ws_bytes);
 }
 // the DiT cross-attention with prompt slots: q / o [b][tq][heads*d], k / v [groups][tk][heads*d], key_bias (optional) [groups][tk]; item i attends to
 // K / V set i % groups. Workspace as ir_op_attention's for `groups` K / V sets (d = 512 has no grouped form).
 int ir_op_attention_kv_groups(ir_ctx* c, void* stream, const uint16_t* q, const uint16_t* k, const uint16_t* v, uint16_t* o, int b, int heads,
                               int tq, int tk, int d, float scale, const float* key_bias, int groups, void* ws, size_t ws_bytes) {
-    use_ctx(c);
     if (groups < 1 || b < 1 || b % groups) return fail(c, -2, "attention_kv_groups: %d items do not split into %d groups", b, groups);
     if (d == 512) return fail(c, -5, "attention_kv_groups: no d = 512 form");
     return attention_generic(c, stream, q, k, v, o, b, heads, tq, tk, d, scale, key_bias, groups, groups, ws, ws_bytes);
 }
 int ir_op_attention_fp8(ir_ctx* c, void* stream, const uint16_t* q, const uint16_t* k, const uint16_t* v, uint16_t* o, int b, int heads, int t,
                         float scale, void* ws, size_t ws_bytes) {
-    // q / k / v / o: [b][t][heads * 72]; ws: tile images | bf16 V^T of the fallback | flag
-    use_ctx(c);
-    if (t < 256 || (t & 63)) return fail(c, -1, "ir_op_attention_fp8: tokens must be a multiple of 64, >= 256");
-    const int d = 72, DV = ir_attn_dv(d), tkp = ((t + 63) & ~63) + 64;
-    const size_t tiles = (ir_attn_fp8_tile_bytes(b, heads, t) + 255) & ~(size_t)255, vt = ((size_t)b * heads * DV * tkp * 2 + 255) & ~(size_t)255;
-    if (ws_bytes < tiles + vt + 256) return fail(c, -20, "attention workspace too small: need %zu", tiles + vt + 256);
-    hipStream_t s = (hipStream_t)stream;
-    AttnParams p;
-    memset(&p, 0, sizeof p);
-    p.q = q; p.k = k; p.vt = reinterpret_cast<bf16_t*>((char*)ws + tiles); p.o = o;
-    p.ovf_flag = reinterpret_cast<int*>((char*)ws + tiles + vt);
-    p.q_bs = p.k_bs = p.o_bs = (long)t * heads * d; p.vt_bs = (long)heads * DV * tkp;
-    p.q_rs = p.k_rs = p.o_rs = heads * d; p.q_hs = p.k_hs = p.o_hs = d;
-    p.B = b; p.Hh = heads; p.Tq = t; p.Tk = t; p.Tk_pad = tkp; p.D = d;
-    p.scale_log2 = scale * 1.44269504088896340736f;
-    int rc = ir_launch_flash_attn_fp8(p, v, (uint8_t*)ws, s);
-    if (!rc) rc = ir_launch_transpose_v(v, const_cast<bf16_t*>(p.vt), (long)t * heads * d, heads * d, d, b, heads, t, tkp, d, DV, s, p.ovf_flag);
-    if (!rc) rc = ir_launch_flash_attn_fallback(p, s);
-    return rc ? fail(c, rc, "flash_attn_fp8 failed (%d)", rc) : 0;
+    // q / k / v / o: [b][t][heads * 72]: dit_block()'s fp8 chain. ws: tile images | bf16 V^T of the fallback | flag
+    if (!c || t < 256 || (t & 63)) return fail(c, -1, "ir_op_attention_fp8: tokens must be a multiple of 64, >= 256");
+    const int d = 72, DV = ir_attn_dv(d), tkp = ir_attn_tk_pad(t);
+    const long hd = (long)heads * d;
+    Run r = make_run(c, stream, ws, ws_bytes, false);
+    uint8_t* tiles = r.a.alloc<uint8_t>(ir_attn_fp8_tile_bytes(b, heads, t));
+    bf16_t* vt = r.a.alloc<bf16_t>((long)b * heads * DV * tkp);
+    int* flag = r.a.alloc<int>(16);
+    if (r.a.overflow) return fail(c, -20, "attention workspace too small: need %zu", r.a.peak);
+    AttnParams p = attn_params(q, k, vt, o, (int)hd, (int)hd, (int)hd, t * hd, t * hd, t * hd, (long)heads * DV * tkp, b, heads, t, t, tkp, d, scale * 1.44269504088896340736f);
+    p.ovf_flag = flag;
+    attn_self_fp8(r, p, v, tiles);
+    return finish(r, c, ws_bytes);
 }
-// q, k, v, o: [b][t][512] bf16 contiguous; single head, softmax scale `scale`. ws: tile images | flag | V^T of the bf16 fallback.
+// q, k, v, o: [b][t][512] bf16 contiguous; single head, softmax scale `scale`: attnblock()'s chain with fp8 operands on.
+// ws: tile images | flags | V^T of the 4-wave fallback | V^T tiles of the bf16 fallback.
 int ir_op_attention_d512_fp8(ir_ctx* c, void* stream, const uint16_t* q, const uint16_t* k, const uint16_t* v, uint16_t* o, int b, int t, float scale,
                              void* ws, size_t ws_bytes) {
     if (!c || !q || !k || !v || !o || !ws) return fail(c, -1, "ir_op_attention_d512_fp8: null argument");
     if (b < 1 || !ir_attn_d512_fp8_takes(t)) return fail(c, -1, "ir_op_attention_d512_fp8: t must be a multiple of 128, >= 256");
-    use_ctx(c);
-    hipStream_t s = (hipStream_t)stream;
-    const long ld = t + 64;
-    const size_t tb = (ir_attn_d512_fp8_tile_bytes(b, t) + 255) & ~(size_t)255;
-    if (ws_bytes < tb + 256 + (size_t)ld * 512 * 2) return fail(c, -20, "ir_op_attention_d512_fp8: workspace too small");
-    uint8_t* tiles = (uint8_t*)ws;
-    int* flag = (int*)((char*)ws + tb);
-    bf16_t* vt = (bf16_t*)((char*)ws + tb + 256);
-    if (ir_launch_zero_f32((float*)flag, 1, s)) return fail(c, -1, "zero failed");
-    int rc = ir_launch_flash_attn_d512_fp8(q, k, v, o, tiles, b, t, 512, 512, (long)t * 512, (long)t * 512, scale, flag, s);
-    if (rc) return fail(c, rc, "ir_launch_flash_attn_d512_fp8 failed (code %d)", rc);
-    for (int i = 0; i < b; ++i) {   // rescaling fallback: both launches return at once unless the kernel above raised the flag
-        rc = ir_launch_transpose_v(v + (long)i * t * 512, vt, 0, 512, 128, 1, 4, t, (int)ld, 128, 128, s, flag);
-        if (!rc) rc = ir_launch_flash_attn_d512(q + (long)i * t * 512, k + (long)i * t * 512, vt, o + (long)i * t * 512, t, 512, 512, ld, scale, s, flag);
-        if (rc) return fail(c, rc, "fallback launch failed (code %d)", rc);
-    }
-    return 0;
+    Run r = make_run(c, stream, ws, ws_bytes, false);
+    AttnD512Scratch w;
+    w.f8tiles = r.a.alloc<uint8_t>(ir_attn_d512_fp8_tile_bytes(b, t));
+    w.flag = r.a.alloc<int>(16);
+    w.vt = r.a.alloc<bf16_t>(512L * ir_attn_tk_pad(t));
+    w.vtt = r.a.alloc<bf16_t>((long)b * t * 512);
+    if (r.a.overflow) return fail(c, -20, "ir_op_attention_d512_fp8: workspace too small: need %zu", r.a.peak);
+    attn_d512(r, q, k, v, o, w, b, t, scale, true);
+    return finish(r, c, ws_bytes);
 }
 int ir_op_swin_attention(ir_ctx* c, void* stream, const uint16_t* qkv, uint16_t* out, const float* bias_t, int b, int h, int w,
                          int heads, int shift, float scale) {

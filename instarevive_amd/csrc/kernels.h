@@ -171,6 +171,8 @@ int ir_launch_swin_attn(const bf16_t* qkv, bf16_t* out, const float* biasT, int 
                         int shift, float scale, hipStream_t s);
 int ir_launch_softmax_rows(const float* x, bf16_t* y, long rows, int cols, long ldx, long ldy, hipStream_t s);
 static inline int ir_attn_dv(int D) { return (D + 31) & ~31; }
+// keys per row of a V^T buffer for T keys (AttnParams::Tk_pad): whole 64-key tiles, + 64 so that the row stride is no power of two (channel conflicts)
+static inline int ir_attn_tk_pad(int T) { return ((T + 63) & ~63) + 64; }
 
 // ---- fused SwinIR block halves (swin_fused.hip)
 // out = x + fc2(gelu(fc1(LayerNorm(x)))) on the fp32 residual stream [T][192] (in place allowed); out2: optional bf16 copy

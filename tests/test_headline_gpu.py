@@ -124,7 +124,7 @@ def test_attention_d512_fp8(ctx, b, t, gain):
     k = torch.randn(b, t, d, generator=g, device="cuda").to(torch.bfloat16)
     v = torch.randn(b, t, d, generator=g, device="cuda").to(torch.bfloat16)
     o = torch.empty(b, t, d, dtype=torch.int16, device="cuda")
-    ws = torch.zeros(b * (t // 64) * D512_TILE_BYTES + 4096 + (t + 64) * 512 * 2, dtype=torch.uint8, device="cuda")
+    ws = torch.zeros(b * (t // 64) * D512_TILE_BYTES + 4096 + (t + 64) * 512 * 2 + b * t * 512 * 2, dtype=torch.uint8, device="cuda")
     scale = d ** -0.5
     ctx.check(ctx.lib.ir_op_attention_d512_fp8(ctx.h, ctx.stream(), L.ptr(q.view(torch.int16)), L.ptr(k.view(torch.int16)), L.ptr(v.view(torch.int16)),
                                                L.ptr(o), b, t, scale, L.ptr(ws), ws.numel()), "attention_d512_fp8")

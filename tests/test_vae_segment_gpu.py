@@ -75,7 +75,8 @@ def rows(s1=0, pp=0, halo=0, igemm9=0, s1_fp8=0, gn_fused=0, gn_own=0, attn=0, a
 # The peaky case runs with fp8 ATTENTION operands: the bf16 d = 512 kernel moves its softmax reference in place and cannot be made to raise its
 # overflow flag by any scores, so the way into attnblock()'s fallback chain is the fp8 kernel's flag ("a query I cannot handle"), behind which
 # the bf16 d = 512 kernel recomputes the whole launch: the case asserts that the result then has the bits of the bf16 route. The 4-wave
-# rescaling pair at the END of the chain (behind the bf16 kernel's own flag) is NOT reached by this or any other case.
+# rescaling pair at the END of the chain (behind the bf16 kernel's own flag) is NOT reached by this or any other case. The chain is attn_d512() of
+# csrc/api.cpp; ir_op_attention and ir_op_attention_d512_fp8 run the same function (tests/test_attn_routes_gpu.py holds both to the same bits).
 CASES = {
     "dec_l0": ("dec_l0", 1, 1024, 1024, "base", False, rows(s1=7, gn_fused=6, lin=1)),
     "dec_l0_fp8": ("dec_l0", 1, 1024, 1024, "base", True, rows(s1=1, s1_fp8=6, gn_fused=6, lin=1)),

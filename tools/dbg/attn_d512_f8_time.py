@@ -9,7 +9,7 @@ t, d = 65536, 512
 g = torch.Generator(device="cuda").manual_seed(1)
 q, k, v = (torch.randn(1, t, d, generator=g, device="cuda").to(torch.bfloat16) for _ in range(3))
 o = torch.empty(1, t, d, dtype=torch.int16, device="cuda")
-ws = torch.zeros((t // 64) * 66560 + 4096 + (t + 64) * 512 * 2, dtype=torch.uint8, device="cuda")
+ws = torch.zeros((t // 64) * 66560 + 4096 + (t + 64) * 512 * 2 + t * 512 * 2, dtype=torch.uint8, device="cuda")
 fn = lambda: ctx.check(ctx.lib.ir_op_attention_d512_fp8(ctx.h, ctx.stream(), L.ptr(q.view(torch.int16)), L.ptr(k.view(torch.int16)), L.ptr(v.view(torch.int16)), L.ptr(o), 1, t, d ** -0.5, L.ptr(ws), ws.numel()), "x")
 for _ in range(3): fn()
 torch.cuda.synchronize()
