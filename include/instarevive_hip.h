@@ -649,6 +649,20 @@ enum { IR_SWIN_SHELL_HEAD = 0, IR_SWIN_SHELL_RSTB_TAIL = 1, IR_SWIN_SHELL_RECON 
 int ir_op_swin_shell(ir_ctx* ctx, void* stream, int part, int layer, const void* in0, const void* in1, void* out0, void* out1, int n, int h, int w,
                      void* ws, size_t ws_bytes);
 size_t ir_op_swin_shell_ws(ir_ctx* ctx, int part, int n, int h, int w);
+/* One input / middle / output block of a CONFIGURED UNet (`which` 0) or ControlNet (1) for op-level tests: the timestep tables and the block
+ * code ir_cldm_sample runs (ResBlock, SpatialTransformer, Downsample / Upsample, input_blocks.0), with its scratch sizing and its split-K scope,
+ * on the caller's tensors. `set` 0: input_blocks, 1: middle_block (its three layers are blocks 0 .. 2), 2: output_blocks; `index` counts within
+ * the set. x: bf16 [n * h * w][cin] contiguous, cin the block's input channels (input_blocks.0: 32 columns, the latent in 0 .. 3 - with the
+ * ControlNet's hint in 4 .. 7 - and zeros behind; output blocks: [h | skip] as the decoder concatenates them); h, w: the resolution entering
+ * the block. out: bf16 rows of out_cs elements (a multiple of 8), of which the block writes columns 0 .. cout - 1 of n * h * w rows (a
+ * Downsample: n * h/2 * w/2; a block that ends in an Upsample: n * 2h * 2w) and no other byte. ir_set_plain_kernels and the profiler act as they
+ * do on the stage. ws: at least ir_op_unet_block_ws(...) bytes (0: the arguments are refused). Returns -11 for a null context, -1 for a UNet
+ * that is not configured or a set / index it does not have, -10 for a non-positive n, h or w, -11 when the block has a transformer and
+ * ir_unet_set_context has not run, -1 for an odd h or w on a Downsample block, a missing tensor or out_cs < cout, -20 when ws is too small;
+ * nothing is launched then. */
+int ir_op_unet_block(ir_ctx* ctx, void* stream, int which, int set, int index, const void* x, void* out, int out_cs, int n, int h, int w, float timestep,
+                     void* ws, size_t ws_bytes);
+size_t ir_op_unet_block_ws(ir_ctx* ctx, int which, int set, int index, int n, int h, int w);
 /* Per-kernel test entry of conv64_kernel (vae_io.hip): 3x3 stride-1 conv 64 -> 64 on bf16 NHWC, bias, act = IR_ACT_NONE or IR_ACT_LRELU(slope) - the shape
  * of SwinIR's conv_hr (diffusion/model/swinir.py:895); h * w >= 65536. The pipeline takes this kernel only under IR_CONV64=1 (see vae_io.hip). */
 int ir_op_conv64(ir_ctx* ctx, void* stream, const uint16_t* in, const uint16_t* wgt, const float* bias, uint16_t* out, int n, int h, int w, int act,

@@ -83,6 +83,7 @@ struct Run {
     long vt_bs = 0;
     bool vt_done = false;
     bool splitk = false;         // conv() / linear() may split K over extra workgroups (IGemmParams::allow_splitk): set by the UNet path
+    int item_rows = 0;           // rows of one batch item in the linear() calls that follow (IGemmParams::item_rows; a conv knows its own): set by ublock
     int s1_min_tiles = 0;        // IGemmParams::s1_min_tiles of every conv this run launches: set by the ControlLDM pipeline (one small image per launch)
     int route_rows = 0;          // > 0: linear() over M rows keeps the kernel it would pick for route_rows rows (M rows of independent route_rows-row
                                  // problems: the batched prompt projection gives each prompt the bits of its own projection)
@@ -152,6 +153,7 @@ void conv(Run& r, const Conv& cw, const bf16_t* in, int N, int H, int W, int in_
     p.out = out; p.out_f32 = out_f32; p.out_cs = out_cs; p.out2 = out2; p.out2_cs = out2_cs;
     size_t ks_mark = 0;
     p.s1_min_tiles = r.s1_min_tiles;
+    p.item_rows = cw.taps == 9 ? p.Ho * p.Wo : ((long)H * W > 1 ? H * W : r.item_rows);
     if (r.splitk) {   // small-M launches of the UNet path: K split over extra workgroups, partial sums in arena scratch (sized in dry runs too)
         p.allow_splitk = 1;
         if (const int ks = ir_igemm_splitk(p); ks > 1) {
@@ -1095,6 +1097,7 @@ void uxf(Run& r, const UNetW& m, const UXfW& w, const bf16_t* h, int N, long HW,
 
 // one input / middle / output block: x contiguous [N*H*W][blk.cin] -> out (row stride out_cs); H, W updated by a resample
 void ublock(Run& r, const UNetW& m, const UBlock& blk, const bf16_t* x, int N, int& H, int& W, bf16_t* out, int out_cs, const UBufs& b) {
+    r.item_rows = H * W;   // of every linear of the block (the shortcut, the transformer); cldm_run's zero-convs follow at the block's output size
     if (blk.resample == 3) {   // input_blocks.0
         conv(r, blk.rs, x, N, H, W, 32, out, out_cs, 0, 1, 1, 0, ACT_NONE, 0.f, nullptr, 0, 0);
         return;
@@ -1102,6 +1105,7 @@ void ublock(Run& r, const UNetW& m, const UBlock& blk, const bf16_t* x, int N, i
     if (blk.resample == 1 && !blk.has_res) {   // Downsample (openaimodel.py:137-160): 3x3, stride 2, padding 1
         conv(r, blk.rs, x, N, H, W, blk.cin, out, out_cs, 0, 2, 1, 0, ACT_NONE, 0.f, nullptr, 0, 0);
         H /= 2; W /= 2;
+        r.item_rows = H * W;
         return;
     }
     const bool up = blk.resample == 2;
@@ -1134,13 +1138,43 @@ void usizes_block(const UNetW& m, const UBlock& blk, int N, int H, int W, USizes
     }
 }
 
+// The scratch of every ublock() whose sizes usizes_block() collected in z (hw: the largest pixel count a GroupNorm sees), from the arena, and
+// the split-K scope of the latent-resolution launches (64 ... 4096 pixels). cldm_run and ir_op_unet_block both run their blocks inside one
+// of these, so that they take the same kernel routes.
+struct UScope {
+    Run& r;
+    const bool splitk_before;
+    UBufs b;
+    UScope(Run& r_, const USizes& z, int n, long hw) : r(r_), splitk_before(r_.splitk) {
+        r.splitk = true;
+        b.t1 = r.a.alloc<bf16_t>(z.tc); b.t2 = r.a.alloc<bf16_t>(z.tc); b.ta = r.a.alloc<bf16_t>(z.tc); b.tb = r.a.alloc<bf16_t>(z.tc);
+        b.gws = r.a.alloc<float>(ir_gn_any_ws_floats(n, hw, z.cmax));
+        b.x = r.a.alloc<float>(z.xc); b.xn = r.a.alloc<bf16_t>(z.xc); b.xb = r.a.alloc<bf16_t>(z.xc); b.att = r.a.alloc<bf16_t>(z.xc);
+        b.cq = r.a.alloc<bf16_t>(z.xc); b.qkv = r.a.alloc<bf16_t>(3 * z.xc); b.ff = r.a.alloc<bf16_t>(8 * z.xc); b.hid = r.a.alloc<bf16_t>(4 * z.xc);
+        b.vt = r.a.alloc<bf16_t>(z.vt);
+    }
+    ~UScope() { r.splitk = splitk_before; r.item_rows = 0; }
+    UScope(const UScope&) = delete;
+    UScope& operator=(const UScope&) = delete;
+};
+
+// One block of a configured UNet on the caller's tensors (ir_op_unet_block): the timestep tables and the ublock() that cldm_run runs.
+void unet_block_run(Run& r, UNetW& m, const UBlock& blk, const bf16_t* x, bf16_t* out, int out_cs, int n, int h, int w, float timestep) {
+    unet_update_timestep(r, m, timestep);
+    const size_t mk = r.a.mark();
+    USizes z;
+    usizes_block(m, blk, n, h, w, z);
+    UScope scope(r, z, n, (long)h * w);
+    int H = h, W = w;
+    ublock(r, m, blk, x, n, H, W, out, out_cs, scope.b);
+    r.a.release(mk);
+}
+
 // zT, c_latent (null: the UNet alone, control = None), out: fp32 NCHW [n][4][h][w]
 void cldm_run(Run& r, const float* zT, const float* c_latent, float* out, int n, int h, int w, float timestep, bool add_zT = true) {
     UNetW& U = r.c->unet[0];
     UNetW& Cn = r.c->unet[1];
     const bool ctl = c_latent != nullptr;
-    const bool splitk_before = r.splitk;
-    r.splitk = true;   // latent-resolution launches: 64 ... 4096 pixels
     unet_update_timestep(r, U, timestep);
     if (ctl) unet_update_timestep(r, Cn, timestep);
     const size_t mk = r.a.mark();
@@ -1163,12 +1197,8 @@ void cldm_run(Run& r, const float* zT, const float* c_latent, float* out, int n,
         }
     }
     const long T0 = (long)n * h * w;
-    UBufs b;
-    b.t1 = r.a.alloc<bf16_t>(z.tc); b.t2 = r.a.alloc<bf16_t>(z.tc); b.ta = r.a.alloc<bf16_t>(z.tc); b.tb = r.a.alloc<bf16_t>(z.tc);
-    b.gws = r.a.alloc<float>(ir_gn_any_ws_floats(n, (long)h * w, z.cmax));
-    b.x = r.a.alloc<float>(z.xc); b.xn = r.a.alloc<bf16_t>(z.xc); b.xb = r.a.alloc<bf16_t>(z.xc); b.att = r.a.alloc<bf16_t>(z.xc);
-    b.cq = r.a.alloc<bf16_t>(z.xc); b.qkv = r.a.alloc<bf16_t>(3 * z.xc); b.ff = r.a.alloc<bf16_t>(8 * z.xc); b.hid = r.a.alloc<bf16_t>(4 * z.xc);
-    b.vt = r.a.alloc<bf16_t>(z.vt);
+    UScope scope(r, z, n, (long)h * w);
+    const UBufs& b = scope.b;
     bf16_t* in32 = r.a.alloc<bf16_t>(T0 * 32);
     // encoder of the UNet: hs[i] kept for the decoder
     std::vector<bf16_t*> hs(nin);
@@ -1253,7 +1283,6 @@ void cldm_run(Run& r, const float* zT, const float* c_latent, float* out, int n,
     conv(r, U.out_conv, b.t1, n, h, w, U.out_conv.cin, v4, 4, 1, 1, 1, 0, ACT_NONE, 0.f, nullptr, 0, 0);
     LAUNCH(r, PC_OTHER, 0.0, 0.0, ir_launch_cldm_out(add_zT ? zT : nullptr, v4, 4, out, n, (long)h * w, r.s), "cldm_out");
     r.a.release(mk);
-    r.splitk = splitk_before;
 }
 
 // The whole ControlLDM restoration of one batch, as Reflow_ControlLDM.get_input + sample_log + decode_first_stage chain it (cldm.py:494-509,
@@ -2467,6 +2496,40 @@ int ir_op_swin_shell(ir_ctx* c, void* stream, int part, int layer, const void* i
     return finish(r, c, ws_bytes);
 }
 
+// ---- one input / middle / output block of a configured UNet for op-level tests (see the header)
+static int unet_block_check(ir_ctx* c, int which, int set, int index, int n, int h, int w, const UBlock** blk) {
+    if (!c) return fail(c, -11, "null context");
+    if ((which != 0 && which != 1) || !c->unet[which].ok) return fail(c, -1, "ir_op_unet_block: UNet %d not configured (0 UNet, 1 ControlNet)", which);
+    const UNetW& m = c->unet[which];
+    const std::vector<UBlock>* sets[3] = {&m.in, &m.mid, &m.out};
+    if (set < 0 || set > 2) return fail(c, -1, "ir_op_unet_block: set %d (0 input, 1 middle, 2 output)", set);
+    if (index < 0 || index >= (int)sets[set]->size()) return fail(c, -1, "ir_op_unet_block: index %d outside 0 .. %d", index, (int)sets[set]->size() - 1);
+    *blk = &(*sets[set])[index];
+    if (int e = check_size(c, n, h, w, 1)) return e;
+    if ((*blk)->has_xf && !m.ctx_ok) return fail(c, -11, "ir_unet_set_context has not run since the UNet was configured");
+    if ((*blk)->resample == 1 && ((h | w) & 1)) return fail(c, -1, "ir_op_unet_block: a Downsample block needs an even grid, got %d x %d", h, w);
+    return 0;
+}
+size_t ir_op_unet_block_ws(ir_ctx* c, int which, int set, int index, int n, int h, int w) {
+    const UBlock* blk = nullptr;
+    if (unet_block_check(c, which, set, index, n, h, w, &blk)) return 0;
+    Run r = make_run(c, nullptr, nullptr, 0, true);
+    unet_block_run(r, c->unet[which], *blk, nullptr, nullptr, blk->cout, n, h, w, 0.f);
+    return r.a.peak + 4096;
+}
+int ir_op_unet_block(ir_ctx* c, void* stream, int which, int set, int index, const void* x, void* out, int out_cs, int n, int h, int w, float timestep,
+                     void* ws, size_t ws_bytes) {
+    const UBlock* blk = nullptr;
+    if (int e = unet_block_check(c, which, set, index, n, h, w, &blk)) return e;
+    if (!x || !out) return fail(c, -1, "ir_op_unet_block: a tensor is missing");
+    if (out_cs < blk->cout || (out_cs & 7)) return fail(c, -1, "ir_op_unet_block: out_cs %d (a multiple of 8, at least the block's %d channels)", out_cs, blk->cout);
+    const size_t need = ir_op_unet_block_ws(c, which, set, index, n, h, w);   // refused as a whole: a block must not stop half way through its launches
+    if (!ws || ws_bytes < need) return fail(c, -20, "workspace too small: need %zu bytes, got %zu", need, ws_bytes);
+    Run r = make_run(c, stream, ws, ws_bytes, false);
+    unet_block_run(r, c->unet[which], *blk, (const bf16_t*)x, (bf16_t*)out, out_cs, n, h, w, timestep);
+    return finish(r, c, ws_bytes);
+}
+
 // Reflow_ControlLDM.sample_log (diffusion/cldm.py:568-588): out = zT + UNet(zT, t, context, control = ControlNet(zT, c_latent, t, context)).
 // zT, c_latent, out: fp32 NCHW [n][4][h][w] (latent resolution); c_latent null: the UNet alone (cond['c_latent'] is None, cldm.py:577-578).
 int ir_cldm_sample(ir_ctx* c, void* stream, const float* zT, const float* c_latent, float* out, int n, int h, int w, float timestep, int return_v,
@@ -2926,7 +2989,7 @@ int ir_op_conv_splitk(ir_ctx* c, void* stream, const uint16_t* in, const uint16_
     if (splits) {
         IGemmParams p;
         memset(&p, 0, sizeof p);
-        p.Cin = cin; p.taps = taps; p.Cout = p.Cout_pad = cout; p.M = n * h * w; p.allow_splitk = 1;
+        p.Cin = cin; p.taps = taps; p.Cout = p.Cout_pad = cout; p.M = n * h * w; p.allow_splitk = 1; p.item_rows = h * w;
         *splits = ir_igemm_splitk(p);
     }
     conv(r, cw, in, n, h, w, cin, out, cout, out_f32, 1, 1, 0, act, 0.f, res, res_f32, cout);

@@ -1630,7 +1630,8 @@ __global__ __launch_bounds__(256) void splitk_finish_kernel(IGemmParams p, const
 }
 
 // Split count ir_launch_igemm uses for p (0: no split): only launches whose caller allows it (p.allow_splitk) and provides the workspace
-// (p.ks_ws, ir_igemm_splitk(p) * p.M * p.Cout_pad floats), with at most 48 output tiles and at least 24 k-tiles.
+// (p.ks_ws, ir_igemm_splitk(p) * p.M * p.Cout_pad floats), with at most 48 output tiles and at least 24 k-tiles. The count itself is that
+// of ONE batch item's tiles (p.item_rows): the k-ranges, and with them the order of the fp32 sums, are the same for an item in a batch and alone.
 int ir_igemm_splitk(const IGemmParams& p) {
     // most tiles a split launch may have, fewest k-tiles it must have, workgroups aimed at, fewest k-tiles per split
     constexpr int max_tiles = 48, min_kt = 24, target = 256, per_min = 8;
@@ -1638,7 +1639,8 @@ int ir_igemm_splitk(const IGemmParams& p) {
     const int BN = p.Cout_pad % 128 == 0 ? 128 : (p.Cout_pad % 64 == 0 ? 64 : 32);
     const int tiles = ((p.M + 127) / 128) * (p.Cout_pad / BN), KT = p.taps * (p.Cin / 64);
     if (tiles > max_tiles || KT < min_kt) return 0;
-    const int ks = std::min(target / tiles, KT / per_min);
+    const int rows = p.item_rows > 0 && p.item_rows < p.M ? p.item_rows : p.M;
+    const int ks = std::min(target / (((rows + 127) / 128) * (p.Cout_pad / BN)), KT / per_min);
     if (ks < 2) return 0;
     const int per = (KT + ks - 1) / ks;
     return (KT + per - 1) / per;   // no empty split

@@ -48,8 +48,10 @@ struct IGemmParams {
     int gn_cpg, gn_chunks;
     // Split-K for small-M launches: the caller sets allow_splitk and, when ir_igemm_splitk(p) > 1, ks_ws (that many slices of p.M * Cout_pad
     // floats of scratch); ksplit is set by the launcher. Each split stores its partial tile in its own slice; a second kernel adds the
-    // slices in order and applies the epilogue (deterministic).
-    int allow_splitk, ksplit;
+    // slices in order and applies the epilogue (deterministic). item_rows (0: M): the output rows of ONE batch item; the split count comes
+    // from one item's tiles, so that an item sums in the same order in a batch as alone (whether a launch splits at all is still a matter of
+    // the whole launch's tile count).
+    int allow_splitk, ksplit, item_rows;
     int s1_min_tiles;   // > 32: conv_halo_s1_kernel only takes images with at least that many patch tiles (callers that never batch small images)
     float* ks_ws;
     // Optional second, TRANSPOSED copy of the output columns >= vt_col0 (gemm_pp_kernel's bf16 form only; M % 256 == 0, vt_T % 64 == 0): column

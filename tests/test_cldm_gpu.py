@@ -4,7 +4,9 @@ reference's own ControlledUnetModel / ControlNet / Reflow_ControlLDM produced (t
 
 Tolerances: activations are bf16 between kernels (2^-9 relative) through ~25 ResBlocks and 16 transformer blocks per network; measured
 rel-L2 is printed, the gates are UNet / ControlNet + UNet <= 1.8 % relative L2 [measured 0.5-1.3 %] and worst element <= 2 % of the output range; the memory-bound
-kernels (GroupNorm, GEGLU) are compared with PyTorch fp32 on the same bf16-rounded data to bf16 output rounding (<= 1 bf16 ulp + 1e-3)."""
+kernels (GroupNorm, GEGLU) are compared with PyTorch fp32 on the same bf16-rounded data to bf16 output rounding (<= 1 bf16 ulp + 1e-3).
+Below the whole network: test_each_control_residual_alone here (one of the 13 control residuals at a time, gated on the difference it makes)
+and tests/test_unet_block_gpu.py (one full-width block at a time)."""
 import ctypes as C
 import os
 
@@ -239,6 +241,39 @@ def test_full_width_unet_vs_oracle():
     sd = {**{"model.diffusion_model." + k: v for k, v in sd_u.items()}, **{"control_model." + k: v for k, v in sd_c.items()}}
     ref = ocldm.reflow_sample(sd, zT, c_latent, ctxt, cfg)
     check(got, ref, "full-width ControlNet + UNet vs oracle")
+
+
+def test_each_control_residual_alone(small):
+    """Each of the 13 control residuals (zero_conv_i(g_i) + hs_i written into its slice of a decoder input, middle_block_out into the first
+    decoder block's h) one at a time: with a ControlNet whose zero-convs are all zero except number i, sample_log with control minus sample_log
+    without control against the same difference through oracle/cldm.py - rel-L2 ON THE DIFFERENCE, so a residual that is lost, scaled or lands
+    in another slice gives 1.0 or more where the whole-output gate sees 1.0 - 9.7 x its 1.8 % (residuals 11 and 12: 1.01 and 1.03 x). Gates:
+    unet_block_ref.RESIDUAL_GATES = 2 x the bf16 emulation of that difference, derived on the CPU by tests/test_unet_block_ref_cpu.py
+    (0.038 for residual 0 ... 0.32 for number 12: the rounding noise of two runs against an effect of 17 % ... 3.5 % of the output). No zero-conv
+    needed scaling. Measured on the MI355X: see docs/parity.md, "ControlLDM blocks"."""
+    from tests.support import unet_block_ref as R
+    m, sds = small
+    assert R.CLDM_SMALL == CLDM_SMALL and R.RESIDUAL_SEEDS["unet"] == 707 and R.RESIDUAL_SEEDS["cnet"] == 708   # the weights the gates were derived on
+    zT, c_latent, ctxt = R.residual_inputs()
+    t = torch.full((1,), 999.0)
+    cond = lambda cl: {"c_concat": [torch.zeros(1, 3, 128, 128)], "c_crossattn": [ctxt], "c_latent": cl}
+    bare_ref = zT + ocldm.unet_forward(sds["unet"], zT, t, ctxt, None, CLDM_SMALL)
+    bare = m.sample_log(cond(None), zT=zT).float().cpu()
+    failed = []
+    try:
+        for i in range(R.N_RESIDUALS):
+            sd_i = R.only_residual(sds["cnet"], i)
+            m.control_model.load_state_dict(sd_i)
+            got = m.sample_log(cond([c_latent]), zT=zT).float().cpu() - bare
+            ref = zT + ocldm.unet_forward(sds["unet"], zT, t, ctxt, ocldm.controlnet_forward(sd_i, zT, c_latent, t, ctxt, CLDM_SMALL), CLDM_SMALL) - bare_ref
+            assert torch.isfinite(got).all(), i
+            e = float((got - ref).norm() / ref.norm())
+            print(f"control residual {i:2d} alone: rel-L2 on the difference {e:.4f} (gate {R.RESIDUAL_GATES[i]:.3f}; |difference| / |output| {float(ref.norm() / bare_ref.norm()):.3f})")
+            if not e <= R.RESIDUAL_GATES[i]:
+                failed.append((i, e, R.RESIDUAL_GATES[i]))
+    finally:
+        m.control_model.load_state_dict(sds["cnet"])
+    assert not failed, f"(residual, rel-L2 on the difference, gate): {failed}"
 
 
 def test_errors_are_loud(small):

@@ -748,11 +748,14 @@ def test_conv3x3_fp8_up(ctx, n, h, w, cin, cout):
 
 
 @pytest.mark.parametrize("n,h,w,cin,cout,taps,res", [(1, 8, 8, 1280, 1280, 9, True), (1, 16, 16, 2560, 1280, 9, False), (2, 16, 16, 640, 640, 9, True),
-                                                    (1, 16, 16, 5120, 1280, 1, True), (1, 32, 32, 1280, 640, 9, False), (1, 64, 64, 320, 320, 9, False)])
+                                                    (1, 16, 16, 5120, 1280, 1, True), (1, 32, 32, 1280, 640, 9, False), (1, 64, 64, 320, 320, 9, False),
+                                                    (2, 16, 16, 1280, 1280, 9, True)])
 def test_conv_splitk(ctx, n, h, w, cin, cout, taps, res):
     """The split-K form of the generic implicit GEMM (igemm.hip: ir_igemm_splitk + splitk_finish_kernel), which the ControlLDM path's small-M
     convs / linears take: against F.conv2d in fp32 on the same bf16 operands, with bias, SiLU and an fp32 residual in the finishing kernel;
-    bit-identical run to run (fixed summation order). The last shape has too many tiles and too few k-tiles to split."""
+    bit-identical run to run (fixed summation order). The 64 x 64 shape has too many tiles and too few k-tiles to split. Item 1 of a batch equals
+    that item run alone bit for bit: the split count is that of one item's tiles (the last shape has 40 tiles as a batch and 20 alone, which gave
+    6 and 12 splits while the count came from the whole launch - the Upsample conv of output_blocks.5 on a 8 x 8 latent)."""
     import ctypes
     g = torch.Generator().manual_seed(cin + cout + h)
     x = rb(torch.randn(n, cin, h, w, generator=g))
@@ -787,6 +790,13 @@ def test_conv_splitk(ctx, n, h, w, cin, cout, taps, res):
         ctx.check(ctx.lib.ir_set_plain_kernels(ctx.h, 0), "plain off")
     assert torch.equal(outs[0], out2), "ring form and two-tile form must agree bit for bit"
     close(L.from_bf16_bits(outs[0]).cpu().permute(0, 3, 1, 2), ref, 2 ** -7, 4e-3, f"conv split-K x{splits.value}")
+    if n > 1:
+        solo, s1 = torch.empty(1, h, w, cout, dtype=torch.int16, device="cuda"), ctypes.c_int(-1)
+        ctx.check(ctx.lib.ir_op_conv_splitk(ctx.h, ctx.stream(), P(xin[1:].contiguous()), P(wp), P(b.cuda()), P(solo), 1, h, w, cin, cout, taps, L.ACT_SILU,
+                                            P(rd[1:].contiguous()) if res else None, 1, 0, P(ws), ws.numel(), ctypes.byref(s1)), "conv_splitk item 1 alone")
+        torch.cuda.synchronize()
+        assert s1.value == splits.value, f"split count {splits.value} in the batch, {s1.value} alone"
+        assert torch.equal(outs[0][1:], solo), "item 1 of the batch differs from item 1 run alone"
 
 
 # ---------------------------------------------------------------------------------------------------------------------
