@@ -649,6 +649,30 @@ enum { IR_SWIN_SHELL_HEAD = 0, IR_SWIN_SHELL_RSTB_TAIL = 1, IR_SWIN_SHELL_RECON 
 int ir_op_swin_shell(ir_ctx* ctx, void* stream, int part, int layer, const void* in0, const void* in1, void* out0, void* out1, int n, int h, int w,
                      void* ws, size_t ws_bytes);
 size_t ir_op_swin_shell_ws(ir_ctx* ctx, int part, int n, int h, int w);
+/* One part of the CONFIGURED DiT's shell around its blocks for op-level tests: the host code ir_dit_forward / ir_dit_step and their control forms
+ * run outside the block loop, called one part at a time. h and w are those of the LATENT (even), T = h/2 * w/2 tokens per item, C = heads *
+ * head_dim, L layers, ncopy control copies (0 without ir_dit_control_configure); token rows are item-major [n * T][C].
+ *   IR_DIT_SHELL_TABLES   the conditioning tables of (timestep, h, w), rebuilt when that key differs from the cached one, copied to out0 = emb
+ *                         fp32 [C] (timestep embedding plus, under micro-conditioning, the size embeddings), out1 = modtab fp32 [L][6][C] (rows
+ *                         shift_msa, 1 + scale_msa, gate_msa, shift_mlp, 1 + scale_mlp, gate_mlp), out2 = ctrl_modtab fp32 [ncopy][6][C] (may be
+ *                         null when ncopy is 0), out3 = fmod fp32 [2][C] (rows shift, 1 + scale of the final layer). n is ignored (pass 1).
+ *   IR_DIT_SHELL_EMBED    in0 = latent fp32 NCHW [n][4][h][w] -> out0 = x fp32 [n * T][C]: patch embedding plus the position table dit.pos.<h/2>x<w/2>
+ *                         (uploaded by the caller), which every item re-reads; out1 (optional) = the bf16 copy of x that the control form writes
+ *   IR_DIT_SHELL_CONTROL  ControlTransformerHalf's loop at `timestep`: out0 = x fp32 [n * T][C], read and replaced in place by the stream behind base
+ *                         block ncopy (base blocks 0 .. ncopy and every copy ran); out1 = cs fp32 and out2 = csb bf16, both [n * T][C]: the control
+ *                         stream pos_embed(c) and its bf16 copy as IR_DIT_SHELL_EMBED leaves them, both overwritten (they end as the last copy's
+ *                         output). Needs ir_dit_control_configure and a prompt (one, or one per item: -12 otherwise).
+ *   IR_DIT_SHELL_FINAL    in0 = x fp32 [n * T][C] -> final LayerNorm on fmod of `timestep`, the C -> 32 projection and out0 = the 8-channel output fp32
+ *                         NCHW [n][8][h][w]; with in1 = latent fp32 [n][4][h][w] and 0 < acp < 1 (-1 otherwise): out0 = x0 fp32 [n][4][h][w], as
+ *                         ir_dit_step ends
+ * Arguments a part has no use for are ignored. ir_set_plain_kernels and the profiler act as they do on the stage (the launches that build the
+ * tables are not profiled there either). ws: at least ir_op_dit_shell_ws(...) bytes (0: the arguments are refused). Returns -1 for a bad part or
+ * a missing tensor, -10 for a size that is not positive and even, -11 when the DiT (for CONTROL: the control branch, the prompt; for EMBED: the
+ * position table) is not configured, -20 when ws is too small; nothing is launched then. */
+enum { IR_DIT_SHELL_TABLES = 0, IR_DIT_SHELL_EMBED = 1, IR_DIT_SHELL_CONTROL = 2, IR_DIT_SHELL_FINAL = 3 };
+int ir_op_dit_shell(ir_ctx* ctx, void* stream, int part, const void* in0, const void* in1, void* out0, void* out1, void* out2, void* out3, int n, int h,
+                    int w, float timestep, float acp, void* ws, size_t ws_bytes);
+size_t ir_op_dit_shell_ws(ir_ctx* ctx, int part, int n, int h, int w);
 /* One input / middle / output block of a CONFIGURED UNet (`which` 0) or ControlNet (1) for op-level tests: the timestep tables and the block
  * code ir_cldm_sample runs (ResBlock, SpatialTransformer, Downsample / Upsample, input_blocks.0), with its scratch sizing and its split-K scope,
  * on the caller's tensors. `set` 0: input_blocks, 1: middle_block (its three layers are blocks 0 .. 2), 2: output_blocks; `index` counts within

@@ -125,6 +125,8 @@ def block(W, x, mod, kv, bias, n, gh, gw, emulate=False, mutation=None, chunk=10
     assert mutation is None or mutation in MUTATIONS, mutation
     r = rb if emulate else (lambda t: t)
     T = gh * gw
+    C = x.shape[1]          # the width of the rows given (the module's C at full width; tests/support/dit_shell_ref.py also runs toy widths)
+    HEADS = C // HD
     sh1, sc1, g1, sh2, sc2, g2 = mod
     if mutation == "msa_mlp_rows_swapped":
         sh1, sc1, g1, sh2, sc2, g2 = sh2, sc2, g2, sh1, sc1, g1

@@ -163,6 +163,17 @@ def test_swin_shell_entries_refuse_a_missing_context():
         assert lib.ir_op_swin_shell_ws(None, part, 1, 64, 64) == 0
 
 
+def test_dit_shell_entries_refuse_a_missing_context():
+    """ir_op_dit_shell and its workspace query return -11 / a zero size without a context, before anything touches a device."""
+    from instarevive_amd import _lib
+    from instarevive_amd.build import build
+    build()
+    lib = _lib.load_library()
+    for part in (_lib.DIT_SHELL_TABLES, _lib.DIT_SHELL_EMBED, _lib.DIT_SHELL_CONTROL, _lib.DIT_SHELL_FINAL, 4):
+        assert lib.ir_op_dit_shell(None, None, part, None, None, None, None, None, None, 1, 16, 16, 400.0, 0.5, None, 0) == -11
+        assert lib.ir_op_dit_shell_ws(None, part, 1, 16, 16) == 0
+
+
 def test_unet_block_entries_refuse_a_missing_context():
     """ir_op_unet_block and its workspace query return -11 / a zero size without a context, before anything touches a device."""
     from instarevive_amd import _lib
