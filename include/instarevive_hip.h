@@ -146,7 +146,9 @@ int ir_cldm_pipeline(ir_ctx* ctx, void* stream, const float* lq, const float* zT
  * sequence length is the tensor `t5.bias.{tokens}` [heads][tokens][tokens] fp32 (uploaded by the host mirror on first use). */
 int ir_t5_configure(ir_ctx* ctx, int n_layers, int d_model, int heads, int d_kv, int d_ff, int vocab);
 /* self.model(input_ids=, attention_mask=)['last_hidden_state'] — t5.py:95-100. ids: device int32 [b][tokens]; key_mask: device fp32
- * [b][tokens], 1 = token, 0 = padding (NULL: none); out: device fp32 [b][tokens][d_model]. tokens <= 512. The ONE exception to the
+ * [b][tokens], 1 = token, 0 = padding (NULL: none); out: device fp32 [b][tokens][d_model]. tokens <= 512. A masked key has weight exactly 0;
+ * an item whose keys are ALL masked attends uniformly to its `tokens` keys, as transformers does there (finfo.min absorbs score and bias), so
+ * its rows are finite. The ONE exception to the
  * "never synchronises" convention above: it waits for the stream so that it can fail on an id outside the vocabulary, as the
  * reference's embedding lookup does (the producer runs once per prompt, off the image path). */
 int ir_t5_encode(ir_ctx* ctx, void* stream, const int32_t* ids, const float* key_mask, float* out, int b, int tokens, void* ws, size_t ws_bytes);
@@ -673,6 +675,24 @@ enum { IR_DIT_SHELL_TABLES = 0, IR_DIT_SHELL_EMBED = 1, IR_DIT_SHELL_CONTROL = 2
 int ir_op_dit_shell(ir_ctx* ctx, void* stream, int part, const void* in0, const void* in1, void* out0, void* out1, void* out2, void* out3, int n, int h,
                     int w, float timestep, float acp, void* ws, size_t ws_bytes);
 size_t ir_op_dit_shell_ws(ir_ctx* ctx, int part, int n, int h, int w);
+/* One part of a CONFIGURED text encoder for op-level tests: the host code ir_t5_encode (`which` IR_TEXT_T5) / ir_clip_text_encode (IR_TEXT_CLIP)
+ * chain, called one part at a time. D = d_model / width, H heads of dk; token rows are item-major [b * t][D]; x is the fp32 residual stream.
+ *   IR_TEXT_EMBED  ids int32 [b][t] -> x [b * t][D]: the embedding rows; CLIP adds its position rows (period t). Like the stage it waits for the
+ *                  stream: an id outside the vocabulary gives -32 and clears the flag.
+ *   IR_TEXT_ATTN   x, read and replaced in place by the stream behind the attention residual of `layer` (norm, q|k|v, attention, o-projection).
+ *                  T5: key_mask fp32 [b][t] (may be null) and the uploaded table t5.bias.<t>; CLIP: its causal table. Optional outputs: qkv_out =
+ *                  the bf16 q|k|v [b * t][3 * H * dk] the attention kernel read, att_out = its bf16 output [b * t][H * dk] before the o-projection.
+ *   IR_TEXT_FFN    x, read and replaced in place by the stream behind the feed-forward residual of `layer`
+ *   IR_TEXT_FINAL  x -> out fp32 [b * t][D]: the final RMSNorm (T5) / ln_final (CLIP)
+ * Arguments a part has no use for are ignored. ir_set_plain_kernels and the profiler act as they do on the stage. ws: at least
+ * ir_op_text_block_ws(...) bytes (0: the arguments are refused). Returns -11 without a context or when the encoder is not configured, -1 for a bad
+ * encoder, part or layer, a missing tensor or a missing t5.bias table, -10 for a bad size (1 <= t <= 512; CLIP: t = its configured length), -20
+ * when ws is too small; nothing is launched then. */
+enum { IR_TEXT_T5 = 0, IR_TEXT_CLIP = 1 };
+enum { IR_TEXT_EMBED = 0, IR_TEXT_ATTN = 1, IR_TEXT_FFN = 2, IR_TEXT_FINAL = 3 };
+int ir_op_text_block(ir_ctx* ctx, void* stream, int which, int part, int layer, const int32_t* ids, const float* key_mask, float* x, void* qkv_out,
+                     void* att_out, float* out, int b, int t, void* ws, size_t ws_bytes);
+size_t ir_op_text_block_ws(ir_ctx* ctx, int which, int part, int b, int t);
 /* One input / middle / output block of a CONFIGURED UNet (`which` 0) or ControlNet (1) for op-level tests: the timestep tables and the block
  * code ir_cldm_sample runs (ResBlock, SpatialTransformer, Downsample / Upsample, input_blocks.0), with its scratch sizing and its split-K scope,
  * on the caller's tensors. `set` 0: input_blocks, 1: middle_block (its three layers are blocks 0 .. 2), 2: output_blocks; `index` counts within

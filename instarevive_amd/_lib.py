@@ -24,7 +24,7 @@ SYMBOLS = [
     "ir_tiled_count", "ir_tiled_encode", "ir_tiled_encode_part", "ir_tiled_encode_overflow", "ir_op_conv_up2x2", "ir_op_conv_norm", "ir_op_vae_conv_in", "ir_op_vae_norm_conv_out", "ir_op_conv64", "ir_op_conv64_to3", "ir_tiled_dit", "ir_tiled_blend_latent", "ir_tiled_decode", "ir_tiled_blend_pixels", "ir_set_plain_kernels", "ir_set_fp8", "ir_set_fp8_mask", "ir_attn_fallback_count", "ir_op_conv_fp8", "ir_op_conv_fp8_up", "ir_op_conv_fp8_route", "ir_fp8_features", "ir_op_attention_fp8", "ir_op_attention_d512_fp8",
     "ir_unet_configure", "ir_unet_set_context", "ir_cldm_sample", "ir_cldm_pipeline", "ir_clip_text_configure", "ir_clip_text_encode", "ir_op_groupnorm_any", "ir_op_geglu",
     "ir_dit_set_prompts", "ir_op_attention_kv_groups", "ir_graph_records", "ir_op_vae_segment", "ir_op_vae_segment_ws", "ir_op_vae_segment_info",
-    "ir_op_swin_shell", "ir_op_swin_shell_ws", "ir_op_dit_shell", "ir_op_dit_shell_ws", "ir_op_unet_block", "ir_op_unet_block_ws",
+    "ir_op_swin_shell", "ir_op_swin_shell_ws", "ir_op_dit_shell", "ir_op_dit_shell_ws", "ir_op_unet_block", "ir_op_unet_block_ws", "ir_op_text_block", "ir_op_text_block_ws",
     "ir_png_bound", "ir_png_encode", "ir_png_encode_runs", "ir_jpeg_bound", "ir_jpeg_encode", "ir_jpeg_decode", "ir_resample_plan_bytes", "ir_resample_plan", "ir_resample_u8", "ir_metrics_y",
     "ir_lpips_scale_table", "ir_lpips_configure", "ir_lpips", "ir_niqe_window", "ir_niqe_stats",
     "ir_clipiqa_scale_table", "ir_clipiqa_configure", "ir_clipiqa", "ir_degrade_qtables", "ir_degrade", "ir_degrade_chain",
@@ -32,6 +32,8 @@ SYMBOLS = [
 
 SWIN_SHELL_HEAD, SWIN_SHELL_RSTB_TAIL, SWIN_SHELL_RECON = range(3)   # ir_op_swin_shell parts
 DIT_SHELL_TABLES, DIT_SHELL_EMBED, DIT_SHELL_CONTROL, DIT_SHELL_FINAL = range(4)   # ir_op_dit_shell parts
+TEXT_T5, TEXT_CLIP = range(2)   # ir_op_text_block encoders
+TEXT_EMBED, TEXT_ATTN, TEXT_FFN, TEXT_FINAL = range(4)   # ir_op_text_block parts
 STAGE_SWINIR, STAGE_VAE_ENCODE, STAGE_DIT, STAGE_VAE_DECODE, STAGE_PIPELINE, STAGE_COLORFIX, STAGE_T5, STAGE_CLDM, STAGE_CLDM_PIPELINE, STAGE_CLIP_TEXT, STAGE_PNG, STAGE_RESAMPLE, STAGE_METRICS = range(13)
 STAGE_LPIPS = 13
 STAGE_NIQE = 14
@@ -200,6 +202,9 @@ def load_library():
     lib.ir_op_unet_block.argtypes = [vp, vp, i, i, i, vp, vp, i, i, i, i, f, vp, sz]
     lib.ir_op_unet_block_ws.argtypes = [vp, i, i, i, i, i, i]
     lib.ir_op_unet_block_ws.restype = sz
+    lib.ir_op_text_block.argtypes = [vp, vp, i, i, i, vp, vp, vp, vp, vp, vp, i, i, vp, sz]
+    lib.ir_op_text_block_ws.argtypes = [vp, i, i, i, i]
+    lib.ir_op_text_block_ws.restype = sz
     lib.ir_png_bound.argtypes = [i, i]
     lib.ir_png_bound.restype = sz
     lib.ir_png_encode.argtypes = [vp, vp, vp, i, i, i, C.c_long, i, i, vp, sz, vp, vp, sz]

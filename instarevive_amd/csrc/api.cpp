@@ -2861,29 +2861,61 @@ int ir_set_plain_kernels(ir_ctx* c, int on) {
 }
 
 // ================================================================ T5 encoder (transformers T5Stack as the reference calls it, t5.py:95-100)
-static void t5_run(Run& r, const int* ids, const float* key_mask, const float* bias, float* out, int B, int T) {
+// Scratch of the text encoders' parts; t5_run() / clip_text_run() allocate all of it once, ir_op_text_block what its part reads (the rest stays null).
+struct TextBufs {
+    bf16_t *xn = nullptr, *qkv = nullptr, *att = nullptr, *ab = nullptr, *hid = nullptr;
+};
+enum { TEXT_BUFS_ATTN = 1, TEXT_BUFS_FFN = 2 };
+static TextBufs text_bufs(Run& r, long BT, int D, int HD, int F, int gated, int parts) {
+    TextBufs b;
+    b.xn = r.a.alloc<bf16_t>(BT * D);
+    if (parts & TEXT_BUFS_ATTN) {
+        b.qkv = r.a.alloc<bf16_t>(BT * 3 * HD);
+        b.att = r.a.alloc<bf16_t>(BT * HD);
+    }
+    if (parts & TEXT_BUFS_FFN) {
+        if (gated) b.ab = r.a.alloc<bf16_t>(BT * 2 * F);
+        b.hid = r.a.alloc<bf16_t>(BT * F);
+    }
+    return b;
+}
+// The encoder in parts; t5_run() chains them, ir_op_text_block runs one at a time.
+static void t5_embed(Run& r, const int* ids, float* x, long BT) {
+    T5Model& m = r.c->t5;
+    LAUNCH(r, PC_OTHER, 0.0, 0.0, ir_launch_t5_embed(ids, m.embed, x, BT, m.D, m.vocab, m.bad, r.s), "t5_embed");
+}
+static void t5_attn(Run& r, const T5Layer& Lw, float* x, const float* bias, const float* key_mask, const TextBufs& b, int B, int T) {
     T5Model& m = r.c->t5;
     const long BT = (long)B * T;
     const int HD = m.H * m.dk;
+    LAUNCH(r, PC_LAYERNORM, 0.0, 6.0 * BT * m.D, ir_launch_t5_rmsnorm(x, Lw.ln1, b.xn, nullptr, BT, m.D, 1e-6f, r.s), "t5_rmsnorm");
+    linear(r, Lw.qkv, b.xn, (int)BT, m.D, b.qkv, 3 * HD, 0, ACT_NONE, nullptr, 0, 0);
+    LAUNCH(r, PC_OTHER, 4.0 * B * m.H * (double)T * T * m.dk, 0.0, ir_launch_t5_attn(b.qkv, bias, key_mask, b.att, B, T, m.H, m.dk, r.s), "t5_attn");
+    linear(r, Lw.o, b.att, (int)BT, HD, x, m.D, 1, ACT_NONE, x, 1, m.D);
+}
+static void t5_ffn(Run& r, const T5Layer& Lw, float* x, const TextBufs& b, long BT) {
+    T5Model& m = r.c->t5;
+    LAUNCH(r, PC_LAYERNORM, 0.0, 6.0 * BT * m.D, ir_launch_t5_rmsnorm(x, Lw.ln2, b.xn, nullptr, BT, m.D, 1e-6f, r.s), "t5_rmsnorm");
+    linear(r, Lw.wi, b.xn, (int)BT, m.D, b.ab, 2 * m.F, 0, ACT_NONE, nullptr, 0, 0);
+    LAUNCH(r, PC_OTHER, 0.0, 6.0 * BT * m.F, ir_launch_t5_gated_gelu(b.ab, b.hid, BT, m.F, r.s), "t5_gated_gelu");
+    linear(r, Lw.wo, b.hid, (int)BT, m.F, x, m.D, 1, ACT_NONE, x, 1, m.D);
+}
+static void t5_final(Run& r, const float* x, float* out, long BT) {
+    T5Model& m = r.c->t5;
+    LAUNCH(r, PC_LAYERNORM, 0.0, 8.0 * BT * m.D, ir_launch_t5_rmsnorm(x, m.final_ln, nullptr, out, BT, m.D, 1e-6f, r.s), "t5_final_norm");
+}
+static void t5_run(Run& r, const int* ids, const float* key_mask, const float* bias, float* out, int B, int T) {
+    T5Model& m = r.c->t5;
+    const long BT = (long)B * T;
     const size_t mk = r.a.mark();
     float* x = r.a.alloc<float>(BT * m.D);
-    bf16_t* xn = r.a.alloc<bf16_t>(BT * m.D);
-    bf16_t* qkv = r.a.alloc<bf16_t>(BT * 3 * HD);
-    bf16_t* att = r.a.alloc<bf16_t>(BT * HD);
-    bf16_t* ab = r.a.alloc<bf16_t>(BT * 2 * m.F);
-    bf16_t* hid = r.a.alloc<bf16_t>(BT * m.F);
-    LAUNCH(r, PC_OTHER, 0.0, 0.0, ir_launch_t5_embed(ids, m.embed, x, BT, m.D, m.vocab, m.bad, r.s), "t5_embed");
+    const TextBufs b = text_bufs(r, BT, m.D, m.H * m.dk, m.F, 1, TEXT_BUFS_ATTN | TEXT_BUFS_FFN);
+    t5_embed(r, ids, x, BT);
     for (const T5Layer& Lw : m.layers) {
-        LAUNCH(r, PC_LAYERNORM, 0.0, 6.0 * BT * m.D, ir_launch_t5_rmsnorm(x, Lw.ln1, xn, nullptr, BT, m.D, 1e-6f, r.s), "t5_rmsnorm");
-        linear(r, Lw.qkv, xn, (int)BT, m.D, qkv, 3 * HD, 0, ACT_NONE, nullptr, 0, 0);
-        LAUNCH(r, PC_OTHER, 4.0 * B * m.H * (double)T * T * m.dk, 0.0, ir_launch_t5_attn(qkv, bias, key_mask, att, B, T, m.H, m.dk, r.s), "t5_attn");
-        linear(r, Lw.o, att, (int)BT, HD, x, m.D, 1, ACT_NONE, x, 1, m.D);
-        LAUNCH(r, PC_LAYERNORM, 0.0, 6.0 * BT * m.D, ir_launch_t5_rmsnorm(x, Lw.ln2, xn, nullptr, BT, m.D, 1e-6f, r.s), "t5_rmsnorm");
-        linear(r, Lw.wi, xn, (int)BT, m.D, ab, 2 * m.F, 0, ACT_NONE, nullptr, 0, 0);
-        LAUNCH(r, PC_OTHER, 0.0, 6.0 * BT * m.F, ir_launch_t5_gated_gelu(ab, hid, BT, m.F, r.s), "t5_gated_gelu");
-        linear(r, Lw.wo, hid, (int)BT, m.F, x, m.D, 1, ACT_NONE, x, 1, m.D);
+        t5_attn(r, Lw, x, bias, key_mask, b, B, T);
+        t5_ffn(r, Lw, x, b, BT);
     }
-    LAUNCH(r, PC_LAYERNORM, 0.0, 8.0 * BT * m.D, ir_launch_t5_rmsnorm(x, m.final_ln, nullptr, out, BT, m.D, 1e-6f, r.s), "t5_final_norm");
+    t5_final(r, x, out, BT);
     r.a.release(mk);
 }
 
@@ -2944,28 +2976,43 @@ int ir_t5_encode(ir_ctx* c, void* stream, const int32_t* ids, const float* key_m
 }
 
 // ---------------------------------------------------------------- OpenCLIP text tower (ControlLDM's cond_stage_model)
-static void clip_text_run(Run& r, const int* ids, float* out, int B) {
+static void clip_embed(Run& r, const int* ids, float* x, long BT) {
+    ClipTextModel& m = r.c->clip;
+    LAUNCH(r, PC_OTHER, 0.0, 0.0, ir_launch_t5_embed(ids, m.embed, x, BT, m.D, m.vocab, m.bad, r.s), "clip_embed");        // token_embedding
+    LAUNCH(r, PC_OTHER, 0.0, 0.0, ir_launch_add_bias_rows(x, m.pos, BT * m.D, m.T * m.D, r.s), "clip_pos");                // + positional_embedding
+}
+// open_clip ResidualAttentionBlock: x + attn(ln_1(x), causal mask); x + mlp(ln_2(x))
+static void clip_attn(Run& r, const ClipLayer& Lw, float* x, const TextBufs& b, int B) {
     ClipTextModel& m = r.c->clip;
     const int T = m.T, HD = m.H * m.dk;
     const long BT = (long)B * T;
+    layernorm(r, x, b.xn, nullptr, Lw.n1.g, Lw.n1.b, BT, m.D, m.D, m.D, 1e-5f);
+    linear(r, Lw.qkv, b.xn, (int)BT, m.D, b.qkv, 3 * HD, 0, ACT_NONE, nullptr, 0, 0);
+    LAUNCH(r, PC_OTHER, 4.0 * B * m.H * (double)T * T * m.dk, 0.0, ir_launch_t5_attn(b.qkv, m.causal, nullptr, b.att, B, T, m.H, m.dk, r.s), "clip_attn");
+    linear(r, Lw.o, b.att, (int)BT, HD, x, m.D, 1, ACT_NONE, x, 1, m.D);
+}
+static void clip_ffn(Run& r, const ClipLayer& Lw, float* x, const TextBufs& b, long BT) {
+    ClipTextModel& m = r.c->clip;
+    layernorm(r, x, b.xn, nullptr, Lw.n2.g, Lw.n2.b, BT, m.D, m.D, m.D, 1e-5f);
+    linear(r, Lw.fc, b.xn, (int)BT, m.D, b.hid, m.F, 0, ACT_GELU_ERF, nullptr, 0, 0);
+    linear(r, Lw.proj, b.hid, (int)BT, m.F, x, m.D, 1, ACT_NONE, x, 1, m.D);
+}
+static void clip_final(Run& r, const float* x, float* out, long BT) {
+    ClipTextModel& m = r.c->clip;
+    layernorm(r, x, nullptr, out, m.final_ln.g, m.final_ln.b, BT, m.D, m.D, m.D, 1e-5f);   // ln_final
+}
+static void clip_text_run(Run& r, const int* ids, float* out, int B) {
+    ClipTextModel& m = r.c->clip;
+    const long BT = (long)B * m.T;
     const size_t mk = r.a.mark();
     float* x = r.a.alloc<float>(BT * m.D);
-    bf16_t* xn = r.a.alloc<bf16_t>(BT * m.D);
-    bf16_t* qkv = r.a.alloc<bf16_t>(BT * 3 * HD);
-    bf16_t* att = r.a.alloc<bf16_t>(BT * HD);
-    bf16_t* hid = r.a.alloc<bf16_t>(BT * m.F);
-    LAUNCH(r, PC_OTHER, 0.0, 0.0, ir_launch_t5_embed(ids, m.embed, x, BT, m.D, m.vocab, m.bad, r.s), "clip_embed");        // token_embedding
-    LAUNCH(r, PC_OTHER, 0.0, 0.0, ir_launch_add_bias_rows(x, m.pos, BT * m.D, T * m.D, r.s), "clip_pos");                  // + positional_embedding
-    for (const ClipLayer& Lw : m.layers) {   // open_clip ResidualAttentionBlock: x + attn(ln_1(x), causal mask); x + mlp(ln_2(x))
-        layernorm(r, x, xn, nullptr, Lw.n1.g, Lw.n1.b, BT, m.D, m.D, m.D, 1e-5f);
-        linear(r, Lw.qkv, xn, (int)BT, m.D, qkv, 3 * HD, 0, ACT_NONE, nullptr, 0, 0);
-        LAUNCH(r, PC_OTHER, 4.0 * B * m.H * (double)T * T * m.dk, 0.0, ir_launch_t5_attn(qkv, m.causal, nullptr, att, B, T, m.H, m.dk, r.s), "clip_attn");
-        linear(r, Lw.o, att, (int)BT, HD, x, m.D, 1, ACT_NONE, x, 1, m.D);
-        layernorm(r, x, xn, nullptr, Lw.n2.g, Lw.n2.b, BT, m.D, m.D, m.D, 1e-5f);
-        linear(r, Lw.fc, xn, (int)BT, m.D, hid, m.F, 0, ACT_GELU_ERF, nullptr, 0, 0);
-        linear(r, Lw.proj, hid, (int)BT, m.F, x, m.D, 1, ACT_NONE, x, 1, m.D);
+    const TextBufs b = text_bufs(r, BT, m.D, m.H * m.dk, m.F, 0, TEXT_BUFS_ATTN | TEXT_BUFS_FFN);
+    clip_embed(r, ids, x, BT);
+    for (const ClipLayer& Lw : m.layers) {
+        clip_attn(r, Lw, x, b, B);
+        clip_ffn(r, Lw, x, b, BT);
     }
-    layernorm(r, x, nullptr, out, m.final_ln.g, m.final_ln.b, BT, m.D, m.D, m.D, 1e-5f);   // ln_final
+    clip_final(r, x, out, BT);
     r.a.release(mk);
 }
 
@@ -3010,6 +3057,68 @@ int ir_clip_text_encode(ir_ctx* c, void* stream, const int32_t* ids, float* out,
     clip_text_run(r, ids, out, b);
     if (int rc = finish(r, c, ws_bytes)) return rc;
     return check_bad_ids(c, stream, c->clip.bad, "ir_clip_text_encode", c->clip.vocab);
+}
+
+// ---- one part of a configured text encoder for op-level tests (see the header): the caller's x IS the residual stream, the rest is arena
+static void text_block_run(ir_ctx* c, Run& r, int which, int part, int layer, const int* ids, const float* key_mask, const float* bias, float* x,
+                           void* qkv_out, void* att_out, float* out, int B, int T) {
+    const bool t5 = which == IR_TEXT_T5;
+    const long BT = (long)B * T;
+    const int D = t5 ? c->t5.D : c->clip.D, HD = t5 ? c->t5.H * c->t5.dk : c->clip.H * c->clip.dk, F = t5 ? c->t5.F : c->clip.F;
+    const size_t mk = r.a.mark();
+    if (part == IR_TEXT_EMBED) {
+        t5 ? t5_embed(r, ids, x, BT) : clip_embed(r, ids, x, BT);
+    } else if (part == IR_TEXT_ATTN) {
+        const TextBufs b = text_bufs(r, BT, D, HD, F, t5, TEXT_BUFS_ATTN);
+        if (t5) t5_attn(r, c->t5.layers[layer], x, bias, key_mask, b, B, T);
+        else clip_attn(r, c->clip.layers[layer], x, b, B);
+        if (r.live() && qkv_out) r.chk(hipMemcpyAsync(qkv_out, b.qkv, (size_t)BT * 3 * HD * 2, hipMemcpyDeviceToDevice, r.s) == hipSuccess ? 0 : -1, "copy of q|k|v");
+        if (r.live() && att_out) r.chk(hipMemcpyAsync(att_out, b.att, (size_t)BT * HD * 2, hipMemcpyDeviceToDevice, r.s) == hipSuccess ? 0 : -1, "copy of the attention output");
+    } else if (part == IR_TEXT_FFN) {
+        const TextBufs b = text_bufs(r, BT, D, HD, F, t5, TEXT_BUFS_FFN);
+        if (t5) t5_ffn(r, c->t5.layers[layer], x, b, BT);
+        else clip_ffn(r, c->clip.layers[layer], x, b, BT);
+    } else {
+        t5 ? t5_final(r, x, out, BT) : clip_final(r, x, out, BT);
+    }
+    r.a.release(mk);
+}
+static int text_block_check(ir_ctx* c, int which, int part, int layer, int b, int t, const float** bias) {
+    if (!c) return -11;
+    if (which != IR_TEXT_T5 && which != IR_TEXT_CLIP) return fail(c, -1, "ir_op_text_block: encoder %d (0 T5, 1 CLIP text tower)", which);
+    if (part < IR_TEXT_EMBED || part > IR_TEXT_FINAL) return fail(c, -1, "ir_op_text_block: part %d (0 embedding, 1 attention, 2 feed-forward, 3 final norm)", part);
+    const bool t5 = which == IR_TEXT_T5;
+    if (!(t5 ? c->t5.ok : c->clip.ok)) return fail(c, -11, "ir_op_text_block: %s not configured", t5 ? "T5 encoder" : "CLIP text encoder");
+    const int L = (int)(t5 ? c->t5.layers.size() : c->clip.layers.size());
+    if ((part == IR_TEXT_ATTN || part == IR_TEXT_FFN) && (layer < 0 || layer >= L)) return fail(c, -1, "ir_op_text_block: layer %d outside 0 .. %d", layer, L - 1);
+    if (b <= 0 || t <= 0 || t > 512 || (long)b * t > (1 << 24)) return fail(c, -10, "ir_op_text_block: bad size (batch %d, tokens %d; 1 <= tokens <= 512)", b, t);
+    if (!t5 && t != c->clip.T) return fail(c, -10, "ir_op_text_block: the CLIP text tower runs %d tokens, not %d", c->clip.T, t);
+    if (t5 && part == IR_TEXT_ATTN) {
+        auto it = c->t.find(fmt("t5.bias.%d", t));
+        if (it == c->t.end() || it->second.bytes < (size_t)c->t5.H * t * t * 4) return fail(c, -1, "ir_op_text_block: t5.bias table for %d tokens not uploaded", t);
+        if (bias) *bias = (const float*)it->second.p;
+    }
+    return 0;
+}
+size_t ir_op_text_block_ws(ir_ctx* c, int which, int part, int b, int t) {
+    if (text_block_check(c, which, part, 0, b, t, nullptr)) return 0;
+    Run r = make_run(c, nullptr, nullptr, 0, true);
+    text_block_run(c, r, which, part, 0, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, b, t);
+    return r.a.peak + 4096;
+}
+int ir_op_text_block(ir_ctx* c, void* stream, int which, int part, int layer, const int32_t* ids, const float* key_mask, float* x, void* qkv_out,
+                     void* att_out, float* out, int b, int t, void* ws, size_t ws_bytes) {
+    const float* bias = nullptr;
+    if (int e = text_block_check(c, which, part, layer, b, t, &bias)) return e;
+    if (!x || (part == IR_TEXT_EMBED && !ids) || (part == IR_TEXT_FINAL && !out)) return fail(c, -1, "ir_op_text_block: a tensor of part %d is missing", part);
+    const size_t need = ir_op_text_block_ws(c, which, part, b, t);   // refused as a whole: a part must not stop half way through its launches
+    if (!ws || ws_bytes < need) return fail(c, -20, "workspace too small: need %zu bytes, got %zu", need, ws_bytes);
+    Run r = make_run(c, stream, ws, ws_bytes, false);
+    text_block_run(c, r, which, part, layer, ids, key_mask, bias, x, qkv_out, att_out, out, b, t);
+    if (int rc = finish(r, c, ws_bytes)) return rc;
+    if (part != IR_TEXT_EMBED) return 0;
+    const bool t5 = which == IR_TEXT_T5;
+    return check_bad_ids(c, stream, t5 ? c->t5.bad : c->clip.bad, "ir_op_text_block", t5 ? c->t5.vocab : c->clip.vocab);
 }
 
 int ir_profile_select(ir_ctx* c, int kernel_id) {

@@ -48,7 +48,8 @@ __global__ __launch_bounds__(256) void t5_rmsnorm_kernel(const float* __restrict
 // Self-attention of one (batch, head, 64-query tile): scores = q.k + bias[h][q][k] (+ mask), softmax over keys, out = P v.
 // qkv: [B][T][3*H*dk] bf16 (q | k | v column blocks); bias: [H][T][T] fp32; key_mask: [B][T] fp32, 1 = token (null: no padding);
 // out: [B][T][H*dk] bf16. K (rows padded by 2 elements: conflict-free column walks) and V of the head live in LDS as bf16; a wave
-// takes one query at a time: lane j owns keys j, j+64, ... for the scores, lane d owns output dim d for P v.
+// takes one query at a time: lane j owns keys j, j+64, ... for the scores, lane d owns output dim d for P v. An item whose keys are
+// ALL masked attends uniformly to its T keys, as transformers does.
 __global__ __launch_bounds__(256) void t5_attn_kernel(const bf16_t* __restrict__ qkv, const float* __restrict__ bias,
                                                       const float* __restrict__ key_mask, bf16_t* __restrict__ out, int T, int H, int dk) {
     extern __shared__ __attribute__((aligned(16))) unsigned char t5_smem[];
@@ -91,10 +92,12 @@ __global__ __launch_bounds__(256) void t5_attn_kernel(const bf16_t* __restrict__
             mx = fmaxf(mx, a);
         }
         mx = wave_max(mx);
+        // every key masked: transformers' finfo.min absorbs score and bias alike, so its softmax is uniform over ALL T keys (not 0 / 0)
+        const bool none = mx < -1.0e38f;
         float sum = 0.f;
         for (int t = 0; t < nkeys; ++t) {
             const int j = t * 64 + lane;
-            const float e = (j < T && s[t] > -1.0e38f) ? __expf(s[t] - mx) : 0.f;
+            const float e = j >= T ? 0.f : none ? 1.f : s[t] > -1.0e38f ? __expf(s[t] - mx) : 0.f;
             if (j < T) P[j] = e;
             sum += e;
         }

@@ -5,10 +5,12 @@ In-tree part, followed literally: FrozenOpenCLIPEmbedder.encode_with_transformer
 len(resblocks) - layer_idx (layer "penultimate": the last block is skipped, configs/cldm.yaml:86-90), ln_final.
 
 Third-party part: the blocks themselves are open_clip's (`open_clip_torch`, not pinned in requirements.txt, neither in the tree nor installed
-here), so **parity is UNPINNED** for them; they are restated from the published open_clip implementation (src/open_clip/transformer.py:
+here); they are restated from the published open_clip implementation (src/open_clip/transformer.py:
 ResidualAttentionBlock = x + attn(ln_1(x), attn_mask) ; x + mlp(ln_2(x)) with nn.MultiheadAttention (packed in_proj_weight / in_proj_bias,
 out_proj), mlp = c_fc -> nn.GELU -> c_proj; model.py: build_attention_mask = -inf above the diagonal) and anchored on the reference's
-call site above. Parameter names are open_clip's (`transformer.resblocks.{i}.attn.in_proj_weight`, ...).
+call site above. Parameter names are open_clip's (`transformer.resblocks.{i}.attn.in_proj_weight`, ...). The tower is PINNED against an
+independent port of it, transformers.CLIPTextModel (hidden_act "gelu", layer_norm_eps 1e-5) on seeded weights mapped from these names
+(tests/golden/make_text_pins.py -> text_pins.npz, layers "last" and "penultimate"); it is still not pinned against open_clip itself.
 """
 import torch
 import torch.nn.functional as F

@@ -48,15 +48,18 @@ def gelu_new(x):
 
 @torch.no_grad()
 def t5_encode(sd, input_ids, attention_mask=None, cfg=None):
-    """sd: HF T5EncoderModel state dict (fp32). input_ids [B,T] long, attention_mask [B,T] (1 = token). Returns [B,T,d_model]."""
+    """sd: HF T5EncoderModel state dict (fp32; a float64 one is evaluated in float64). input_ids [B,T] long, attention_mask [B,T] (1 = token).
+    Returns [B,T,d_model]. A masked key gets finfo(float32).min added, which absorbs score and bias: an item whose keys are all masked attends
+    uniformly to all T keys, as in transformers."""
     cfg = dict(DEFAULT_CFG, **(cfg or {}))
     H, dk, eps = cfg["num_heads"], cfg["d_kv"], cfg["layer_norm_epsilon"]
     B, T = input_ids.shape
-    x = sd["shared.weight"][input_ids].float()
-    bias = position_bias(sd["encoder.block.0.layer.0.SelfAttention.relative_attention_bias.weight"].float(), T,
+    dt = torch.float64 if sd["shared.weight"].dtype == torch.float64 else torch.float32
+    x = sd["shared.weight"][input_ids].to(dt)
+    bias = position_bias(sd["encoder.block.0.layer.0.SelfAttention.relative_attention_bias.weight"].to(dt), T,
                          cfg["relative_attention_num_buckets"], cfg["relative_attention_max_distance"])[None]   # [1,H,T,T]
     if attention_mask is not None:
-        bias = bias + (1.0 - attention_mask.float())[:, None, None, :] * torch.finfo(torch.float32).min
+        bias = bias + (1.0 - attention_mask.to(dt))[:, None, None, :] * torch.finfo(torch.float32).min
     for i in range(cfg["num_layers"]):
         p = f"encoder.block.{i}.layer."
         h = rmsnorm(x, sd[p + "0.layer_norm.weight"], eps)

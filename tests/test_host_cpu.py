@@ -185,6 +185,18 @@ def test_unet_block_entries_refuse_a_missing_context():
         assert lib.ir_op_unet_block_ws(None, which, set_, 0, 1, 8, 8) == 0
 
 
+def test_text_block_entries_refuse_a_missing_context():
+    """ir_op_text_block and its workspace query return -11 / a zero size without a context, before anything touches a device."""
+    from instarevive_amd import _lib
+    from instarevive_amd.build import build
+    build()
+    lib = _lib.load_library()
+    for which in (_lib.TEXT_T5, _lib.TEXT_CLIP, 2):
+        for part in (_lib.TEXT_EMBED, _lib.TEXT_ATTN, _lib.TEXT_FFN, _lib.TEXT_FINAL, 4):
+            assert lib.ir_op_text_block(None, None, which, part, 0, None, None, None, None, None, None, 1, 77, None, 0) == -11
+            assert lib.ir_op_text_block_ws(None, which, part, 1, 77) == 0
+
+
 NULL_CONTEXT = {
     -11: ["ir_swinir_forward", "ir_vae_encode", "ir_vae_decode", "ir_dit_forward", "ir_dit_step", "ir_dit_forward_control", "ir_dit_step_control",
           "ir_pipeline", "ir_cldm_sample", "ir_cldm_pipeline", "ir_color_fix", "ir_tiled_encode", "ir_tiled_encode_part", "ir_tiled_encode_overflow",

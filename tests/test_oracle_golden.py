@@ -209,6 +209,53 @@ def test_t5_encoder_matches_transformers():
     assert b.tolist() == [0, 17, 1, 23, 7, 24, 31, 31, 31, 15]
 
 
+def test_t5_buckets_match_transformers_at_every_distance():
+    """text_pins.npz (a): transformers' bucket for rel = -511 .. 511 (the 40 tokens of t5_small.npz stop at distance 39: buckets 13 - 15 / 29 - 31
+    and the saturation at >= 128 never met transformers). Both copies of the rule - the oracle's and the one the production host code uploads
+    (weights.t5_position_bias) - reproduce it through their bias tables at lengths around every threshold."""
+    from instarevive_amd import weights as W
+    from oracle import t5 as ot5
+    pin = torch.from_numpy(load("text_pins.npz")["bucket"].astype(np.int64))
+    assert pin.shape == (1023,) and sorted(set(pin.tolist())) == [b for b in range(32) if b != 16]   # (16 = "0 to the right" cannot occur)
+    assert torch.equal(ot5.relative_position_bucket(torch.arange(-511, 512)), pin)
+    table = torch.arange(32, dtype=torch.float32)[:, None] * torch.tensor([1.0, -2.0])   # two heads: bias = the bucket index, and -2 x it
+    for T in (1, 8, 9, 128, 129, 300, 512):
+        pos = torch.arange(T)
+        want = table[pin[(pos[None, :] - pos[:, None]) + 511]].permute(2, 0, 1)
+        assert torch.equal(W.t5_position_bias(table, T), want), T
+        assert torch.equal(ot5.position_bias(table, T), want), T
+
+
+def test_t5_long_and_fully_masked_match_transformers():
+    """text_pins.npz (b), (c): T5EncoderModel at 300 tokens with valid lengths (300, 170) - the far buckets act on valid keys - and at b = 3 with
+    item 1 fully masked, whose rows are finite in transformers (uniform attention over all keys) and in the oracle."""
+    from oracle import t5 as ot5
+    fx = load("text_pins.npz")
+    sd = _t5_small()
+    assert abs(checksum(sd) - float(fx["t5_wsum"])) < 1e-6 * float(fx["t5_wsum"])
+    for tag in ("long", "full"):
+        ids, mask = torch.from_numpy(fx[f"t5_{tag}_ids"].astype(np.int64)), torch.from_numpy(fx[f"t5_{tag}_mask"].astype(np.int64))
+        out = ot5.t5_encode(sd, ids, mask, T5_SMALL)
+        assert torch.isfinite(out).all()
+        torch.testing.assert_close(out, fx[f"t5_{tag}_out"], rtol=2e-4, atol=2e-5)
+    assert int(mask[1].sum()) == 0
+
+
+def test_clip_text_tower_matches_transformers_port():
+    """text_pins.npz (d): transformers.CLIPTextModel (hidden_act "gelu", layer_norm_eps 1e-5), an independent port of open_clip's text tower, on
+    seeded weights mapped from open_clip's names (tests/golden/make_text_pins.py): layers "last" and "penultimate"."""
+    from oracle import clip_text as oclip
+    from tests.golden.make_text_pins import CLIP_SMALL, clip_small_sd
+    fx = load("text_pins.npz")
+    sd = clip_small_sd()
+    assert abs(checksum(sd) - float(fx["clip_wsum"])) < 1e-6 * float(fx["clip_wsum"])
+    ids = torch.from_numpy(fx["clip_ids"].astype(np.int64))
+    assert int(ids[0].argmax()) == 9 and int(ids[1].argmax()) == 76   # the end-of-text positions
+    for layer in ("last", "penultimate"):
+        out = oclip.encode_with_transformer(sd, ids, dict(CLIP_SMALL, layer=layer))
+        torch.testing.assert_close(out, fx["clip_" + layer], rtol=2e-4, atol=2e-5)
+
+
 def test_glue_matches_reference():
     fx = load("glue.npz")
     acp = oglue.alphas_cumprod()
