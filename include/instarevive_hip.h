@@ -726,6 +726,44 @@ int ir_op_conv_fp8_up(ir_ctx* ctx, void* stream, const uint8_t* in8, const uint8
 int ir_op_conv_fp8_route(ir_ctx* ctx, int n, int h, int w, int cin, int cout, int has_res);
 int ir_op_linear(ir_ctx* ctx, void* stream, const uint16_t* in, const uint16_t* wgt, const float* bias, void* out, int m, int k, int n,
                  int n_pad, int act, const float* gate, const void* res, int res_f32, int out_f32, float out_scale);
+/* ir_op_linear / ir_op_conv with the parameters those two hide: everything the host layer's conv() / linear() pass to the implicit-GEMM launcher
+ * for the product. A zero stride means the dense one of the short entries (in_cs = cin, out_cs = res_cs = out2_cs = cout).
+ *   res_mod > 0: the residual row of output row m is m % res_mod (the DiT position table); out2: a second, bf16 copy of the result;
+ *   splitk != 0: split-K allowed as in ir_op_conv_splitk, partial slices in ws (ws_bytes); item_rows: the rows of one batch item of a linear
+ *   (a conv knows its own); route_rows > 0: keep the kernel the launch would get with that many rows; wup: the phase weights of an up = 1 conv
+ *   (weights.pack_conv_up2x2), used where a phase kernel takes the shape; vt_*: the transposed copy of the columns >= vt_col0 (the V^T operand of
+ *   the DiT self-attention), written by the launch only where ir_op_igemm_route reports it.
+ * Both go through the host code of the product's launches: the profiler rows and ir_set_plain_kernels act as they do on the stages, and the
+ * launcher's refusal codes (-2 .. -16) come back unchanged. A linear is a conv with taps = 1 over n = m rows, h = w = 1, stride 1, pad 0, up 0. */
+typedef struct ir_igemm_ex {
+    int in_cs, out_cs, res_cs, res_mod;
+    uint16_t* out2;
+    int out2_cs;
+    int splitk, item_rows, route_rows;
+    const uint16_t* wup;
+    uint16_t* vt_out;
+    int vt_col0, vt_hd, vt_dv, vt_ld, vt_T;
+    long long vt_bs;
+    void* ws;
+    size_t ws_bytes;
+} ir_igemm_ex;
+int ir_op_linear_ex(ir_ctx* ctx, void* stream, const uint16_t* in, const uint16_t* wgt, const float* bias, void* out, int m, int k, int n, int n_pad,
+                    int act, const float* gate, const void* res, int res_f32, int out_f32, float out_scale, const ir_igemm_ex* ex);
+int ir_op_conv_ex(ir_ctx* ctx, void* stream, const uint16_t* in, const uint16_t* wgt, const float* bias, void* out, int n, int h, int w, int cin,
+                  int cout, int cout_pad, int taps, int stride, int pad, int up, int act, float slope, const void* res, int res_f32, int out_f32,
+                  const float* gate, float out_scale, const ir_igemm_ex* ex);
+/* What ir_op_conv_ex (ir_op_linear_ex: taps = 1, see above) would launch for exactly these arguments, from the function the launcher itself
+ * dispatches on; nothing is launched. Negative: an error code. Otherwise bits 0-3 the kernel (0 conv_halo_s1, 1 conv_halo_pp, 2 gemm_pp, 3
+ * conv_halo, 4 igemm_kernel, 5 conv64), 4-6 the form (gemm_pp: 0 none / 1 GELU-tanh bf16 forms, 2 fp32 gate + residual, 3 general; convs: 0
+ * plain, 1 nearest-2x folded in, 2 phase weights, 3 input normalisation), 7 the launch writes vt_out, 8-15 tile columns / 4, 16-19 BK / 16,
+ * 20-23 k-tile ring stages, 24-27 waves, 28-31 taps, 32-39 split-K slices, 40 XCD-padded tile order, 41 ... with idle blocks, 42 fp8. */
+long long ir_op_igemm_route(ir_ctx* ctx, void* stream, const uint16_t* in, const uint16_t* wgt, const float* bias, void* out, int n, int h, int w,
+                            int cin, int cout, int cout_pad, int taps, int stride, int pad, int up, int act, float slope, const void* res, int res_f32,
+                            int out_f32, const float* gate, float out_scale, const ir_igemm_ex* ex);
+/* Every route ir_op_igemm_route can report for bf16 operands, with bits 7 and 32-41 (vt, split-K slices, tile order) cleared: the library asks its
+ * own rule over a grid of launches that crosses every threshold the rule reads, on the fast and the plain kernels; no context, no device.
+ * Returns their number and writes the first min(number, cap) to out (out may be null with cap 0). For tests that must reach every route. */
+int ir_op_igemm_route_range(long long* out, int cap);
 int ir_op_groupnorm(ir_ctx* ctx, void* stream, const uint16_t* x, uint16_t* y, const float* gamma, const float* beta, int n, int hw,
                     int c, int groups, float eps, int silu, void* ws, size_t ws_bytes);
 int ir_op_layernorm(ir_ctx* ctx, void* stream, const float* x, uint16_t* y, const float* a, const float* b, int rows, int c, int ldx,

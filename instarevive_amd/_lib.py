@@ -28,6 +28,7 @@ SYMBOLS = [
     "ir_png_bound", "ir_png_encode", "ir_png_encode_runs", "ir_jpeg_bound", "ir_jpeg_encode", "ir_jpeg_decode", "ir_resample_plan_bytes", "ir_resample_plan", "ir_resample_u8", "ir_metrics_y",
     "ir_lpips_scale_table", "ir_lpips_configure", "ir_lpips", "ir_niqe_window", "ir_niqe_stats",
     "ir_clipiqa_scale_table", "ir_clipiqa_configure", "ir_clipiqa", "ir_degrade_qtables", "ir_degrade", "ir_degrade_chain",
+    "ir_op_linear_ex", "ir_op_conv_ex", "ir_op_igemm_route", "ir_op_igemm_route_range",
 ]
 
 SWIN_SHELL_HEAD, SWIN_SHELL_RSTB_TAIL, SWIN_SHELL_RECON = range(3)   # ir_op_swin_shell parts
@@ -68,6 +69,22 @@ class DegradeParams(C.Structure):
     """ir_degrade_params (include/instarevive_hip.h): one image's record; kernel and noise are device addresses."""
     _fields_ = [("kernel", C.c_void_p), ("noise", C.c_void_p), ("ksize", C.c_int), ("lh", C.c_int), ("lw", C.c_int), ("q", C.c_int),
                 ("norm", C.c_int), ("sigma", C.c_float)]
+
+
+class IGemmEx(C.Structure):
+    """ir_igemm_ex (include/instarevive_hip.h): what ir_op_linear_ex / ir_op_conv_ex / ir_op_igemm_route take beyond the short entries; out2, wup,
+    vt_out and ws are device addresses."""
+    _fields_ = [("in_cs", C.c_int), ("out_cs", C.c_int), ("res_cs", C.c_int), ("res_mod", C.c_int), ("out2", C.c_void_p), ("out2_cs", C.c_int),
+                ("splitk", C.c_int), ("item_rows", C.c_int), ("route_rows", C.c_int), ("wup", C.c_void_p), ("vt_out", C.c_void_p),
+                ("vt_col0", C.c_int), ("vt_hd", C.c_int), ("vt_dv", C.c_int), ("vt_ld", C.c_int), ("vt_T", C.c_int), ("vt_bs", C.c_longlong),
+                ("ws", C.c_void_p), ("ws_bytes", C.c_size_t)]
+
+
+def igemm_route_fields(packed: int) -> dict:
+    """The packed value of ir_op_igemm_route (include/instarevive_hip.h) as a dict."""
+    b = lambda lo, n: (packed >> lo) & ((1 << n) - 1)
+    return dict(kernel=b(0, 4), form=b(4, 3), vt=b(7, 1), bn=4 * b(8, 8), bk=16 * b(16, 4), stages=b(20, 4), waves=b(24, 4), taps=b(28, 4),
+                splits=b(32, 8), padded=b(40, 1), idle=b(41, 1), fp8=b(42, 1))
 
 
 class ChainOp(C.Structure):
@@ -142,6 +159,11 @@ def load_library():
     lib.ir_op_conv_splitk.argtypes = [vp, vp, vp, vp, vp, vp, i, i, i, i, i, i, i, vp, i, i, vp, sz, C.POINTER(C.c_int)]
     lib.ir_op_conv_groupnorm.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, vp, i, i, i, i, i, i, i, vp, i, vp, sz, C.POINTER(C.c_int)]
     lib.ir_op_linear.argtypes = [vp, vp, vp, vp, vp, vp, i, i, i, i, i, vp, vp, i, i, f]
+    lib.ir_op_linear_ex.argtypes = [vp, vp, vp, vp, vp, vp, i, i, i, i, i, vp, vp, i, i, f, C.POINTER(IGemmEx)]
+    lib.ir_op_conv_ex.argtypes = [vp, vp, vp, vp, vp, vp, i, i, i, i, i, i, i, i, i, i, i, f, vp, i, i, vp, f, C.POINTER(IGemmEx)]
+    lib.ir_op_igemm_route.argtypes = lib.ir_op_conv_ex.argtypes
+    lib.ir_op_igemm_route.restype = C.c_longlong
+    lib.ir_op_igemm_route_range.argtypes = [C.POINTER(C.c_longlong), i]
     lib.ir_op_groupnorm.argtypes = [vp, vp, vp, vp, vp, vp, i, i, i, i, f, i, vp, sz]
     lib.ir_op_layernorm.argtypes = [vp, vp, vp, vp, vp, vp, i, i, i, i, f]
     lib.ir_op_attention.argtypes = [vp, vp, vp, vp, vp, vp, i, i, i, i, i, f, vp, vp, sz]

@@ -87,6 +87,7 @@ struct Run {
     int s1_min_tiles = 0;        // IGemmParams::s1_min_tiles of every conv this run launches: set by the ControlLDM pipeline (one small image per launch)
     int route_rows = 0;          // > 0: linear() over M rows keeps the kernel it would pick for route_rows rows (M rows of independent route_rows-row
                                  // problems: the batched prompt projection gives each prompt the bits of its own projection)
+    IGemmRoute* route_out = nullptr;   // set (ir_op_igemm_route): conv() stores what ir_launch_igemm would run for its launch and launches nothing
     bool live() const { return !a.dry && rc == 0 && !a.overflow; }
     void chk(int r, const char* w) {
         if (r != 0 && rc == 0) { rc = r; where = w; }
@@ -193,13 +194,19 @@ void conv(Run& r, const Conv& cw, const bf16_t* in, int N, int H, int W, int in_
         q.M = r.route_rows;
         if (ir_igemm_kernel_id(q) != ir_igemm_kernel_id(p)) p.force_generic = 1;   // (only gemm_pp_kernel depends on M among the linear kernels)
     }
+    const IGemmRoute rt = ir_igemm_route(p);   // once: the profiler's row here, the dispatch in the launcher
+    r.vt_done = rt.vt != 0;                    // (route_rows above may have taken the launch away from gemm_pp_kernel)
+    if (r.route_out) {
+        *r.route_out = rt;
+        return;
+    }
     static const int kid_of[6] = {PK_CONV_S1, PK_CONV_HALO_PP, PK_GEMM_PP, PK_CONV_HALO, -1, PK_CONV64};
-    int kid = kid_of[ir_igemm_kernel_id(p)];
+    int kid = kid_of[rt.kernel];
     if (kid < 0) kid = cw.taps == 9 ? PK_CONV_IGEMM : PK_LINEAR_IGEMM;
     const double cin_r = cw.cin_r ? cw.cin_r : cw.cin, cout_r = cw.cout_r ? cw.cout_r : cw.cout;
     LAUNCHK(r, kid, 2.0 * p.M * cout_r * cw.taps * cin_r,
             2.0 * ((double)p.M * cin_r + (double)p.M * cout_r + cout_r * cw.taps * cin_r) + (res ? (res_f32 ? 4.0 : 2.0) * p.M * cout_r : 0.0),
-            ir_launch_igemm(p, r.s), "igemm");
+            ir_launch_igemm(p, r.s, &rt), "igemm");
 }
 // linear over rows: in [M][in_cs] -> out [M][out_cs]
 void linear(Run& r, const Conv& cw, const bf16_t* in, int M, int in_cs, void* out, int out_cs, int out_f32, int act, const void* res,
@@ -3318,6 +3325,47 @@ int ir_op_linear(ir_ctx* c, void* stream, const uint16_t* in, const uint16_t* wg
     linear(r, cw, in, m, k, out, n, out_f32, act, res, res_f32, n, nullptr, 0, gate, 0, out_scale);
     return finish(r, c, 0);
 }
+// ir_op_conv / ir_op_linear with everything conv() takes (ir_igemm_ex) - one body for the two entries and the route query, which runs the same
+// host code up to the launch (route != null: nothing is launched)
+static int op_igemm_ex(ir_ctx* c, void* stream, const char* who, const uint16_t* in, const uint16_t* wgt, const float* bias, void* out, int n, int h, int w,
+                       int cin, int cout, int cout_pad, int taps, int stride, int pad, int up, int act, float slope, const void* res, int res_f32,
+                       int out_f32, const float* gate, float out_scale, const ir_igemm_ex* ex, IGemmRoute* route) {
+    if (!c || !ex) return fail(c, -1, "%s: null context or ir_igemm_ex", who);
+    Run r = make_run(c, stream, ex->ws, ex->ws_bytes, false);
+    r.splitk = ex->splitk != 0;
+    r.item_rows = ex->item_rows;
+    r.route_rows = ex->route_rows;
+    r.route_out = route;
+    if (ex->vt_out) {
+        r.vt_out = ex->vt_out; r.vt_col0 = ex->vt_col0; r.vt_hd = ex->vt_hd; r.vt_dv = ex->vt_dv; r.vt_ld = ex->vt_ld; r.vt_T = ex->vt_T; r.vt_bs = (long)ex->vt_bs;
+    }
+    Conv cw;
+    cw.w = wgt; cw.b = bias; cw.cin = cin; cw.cout = cout; cw.cout_pad = cout_pad; cw.taps = taps; cw.wup = ex->wup;
+    const int out_cs = ex->out_cs ? ex->out_cs : cout;
+    conv(r, cw, in, n, h, w, ex->in_cs ? ex->in_cs : cin, out, out_cs, out_f32, stride, pad, up, act, slope, res, res_f32, ex->res_cs ? ex->res_cs : cout,
+         ex->out2, ex->out2 ? (ex->out2_cs ? ex->out2_cs : cout) : 0, gate, ex->res_mod, out_scale);
+    return finish(r, c, ex->ws_bytes);
+}
+int ir_op_linear_ex(ir_ctx* c, void* stream, const uint16_t* in, const uint16_t* wgt, const float* bias, void* out, int m, int k, int n, int n_pad, int act,
+                    const float* gate, const void* res, int res_f32, int out_f32, float out_scale, const ir_igemm_ex* ex) {
+    return op_igemm_ex(c, stream, "ir_op_linear_ex", in, wgt, bias, out, m, 1, 1, k, n, n_pad, 1, 1, 0, 0, act, 0.f, res, res_f32, out_f32, gate, out_scale, ex, nullptr);
+}
+int ir_op_conv_ex(ir_ctx* c, void* stream, const uint16_t* in, const uint16_t* wgt, const float* bias, void* out, int n, int h, int w, int cin, int cout,
+                  int cout_pad, int taps, int stride, int pad, int up, int act, float slope, const void* res, int res_f32, int out_f32, const float* gate,
+                  float out_scale, const ir_igemm_ex* ex) {
+    return op_igemm_ex(c, stream, "ir_op_conv_ex", in, wgt, bias, out, n, h, w, cin, cout, cout_pad, taps, stride, pad, up, act, slope, res, res_f32, out_f32, gate,
+                       out_scale, ex, nullptr);
+}
+long long ir_op_igemm_route(ir_ctx* c, void* stream, const uint16_t* in, const uint16_t* wgt, const float* bias, void* out, int n, int h, int w, int cin, int cout,
+                            int cout_pad, int taps, int stride, int pad, int up, int act, float slope, const void* res, int res_f32, int out_f32,
+                            const float* gate, float out_scale, const ir_igemm_ex* ex) {
+    IGemmRoute rt;
+    memset(&rt, 0, sizeof rt);
+    const int rc = op_igemm_ex(c, stream, "ir_op_igemm_route", in, wgt, bias, out, n, h, w, cin, cout, cout_pad, taps, stride, pad, up, act, slope, res, res_f32,
+                               out_f32, gate, out_scale, ex, &rt);
+    return rc ? (long long)rc : ir_igemm_route_pack(rt);
+}
+int ir_op_igemm_route_range(long long* out, int cap) { return (out || cap <= 0) ? ir_igemm_route_range(out, cap > 0 ? cap : 0) : -1; }
 int ir_op_groupnorm(ir_ctx* c, void* stream, const uint16_t* x, uint16_t* y, const float* gamma, const float* beta, int n, int hw, int ch,
                     int groups, float eps, int silu, void* ws, size_t ws_bytes) {
     use_ctx(c);

@@ -15,9 +15,11 @@
 // one barrier per k-tile. The epilogue transposes each wave's accumulators through LDS so that all
 // global traffic (bias, residual, gate, stores) is row-contiguous 8/16-byte vectors.
 #include <stdlib.h>
+#include <string.h>
 #include <algorithm>
 #include <type_traits>
 #include <utility>
+#include <vector>
 #include "common.h"
 #include "kernels.h"
 
@@ -1516,7 +1518,8 @@ __global__ __launch_bounds__(512, 1) void gemm_pp_kernel(IGemmParams p) {
 int g_ir_plain_kernels = 0;
 
 // Grid of a tiled launch (see tile_of_block): one block per tile for small launches, the XCD-padded order otherwise.
-static long tile_grid(long MT, long NT) { return ((MT & 7) && MT < 64) ? MT * NT : ((MT + 7) / 8) * 8 * NT; }
+static bool tile_order_padded(long MT) { return !((MT & 7) && MT < 64); }
+static long tile_grid(long MT, long NT) { return tile_order_padded(MT) ? ((MT + 7) / 8) * 8 * NT : MT * NT; }
 
 // Shortest reduction gemm_pp_kernel takes: 8 k-tiles. (Its prologue needs 4; with the limit at 6 SwinIR's qkv projection - K = 192, N = 576 =
 // 2 x 288 - runs here: measured in round 4 at 36 us per launch, exactly what igemm_kernel<128, 64> needs for it: no gain, limit left at 8.)
@@ -1539,14 +1542,21 @@ int ir_igemm_writes_vt(const IGemmParams& pin) {
            p.vt_col0 % GemmPP::BN == 0 && p.vt_hd * 2 == 144 && (p.Cout - p.vt_col0) % 144 == 0 && (p.vt_ld & 7) == 0 && (p.vt_bs & 7) == 0 &&
            !(reinterpret_cast<uintptr_t>(p.vt_out) & 15);
 }
-static int launch_gemm_pp(const IGemmParams& p, hipStream_t s) {
-    const int MT = (p.M + GemmPP::BM - 1) / GemmPP::BM, NT = p.Cout / GemmPP::BN;
-    const dim3 grid(((MT + 7) / 8) * 8 * NT);
+// Which gemm_pp_kernel instantiation runs p (IGemmRoute::form)
+static int gemm_pp_form(const IGemmParams& p) {
     const bool unit = !p.gate && p.out_scale == 1.f;
     const int kind = (!p.res && !p.out_f32 && !p.out2) ? 0 : (p.res && p.res_f32 && p.out_f32 && p.res_mod == 0) ? 1 : 2;
-    if (kind == 0 && unit && p.act == IR_ACT_NONE) hipLaunchKernelGGL((gemm_pp_kernel<IR_ACT_NONE, 0, true>), grid, dim3(512), 0, s, p);
-    else if (kind == 0 && unit && p.act == IR_ACT_GELU_TANH) hipLaunchKernelGGL((gemm_pp_kernel<IR_ACT_GELU_TANH, 0, true>), grid, dim3(512), 0, s, p);
-    else if (kind == 1 && p.act == IR_ACT_NONE) hipLaunchKernelGGL((gemm_pp_kernel<IR_ACT_NONE, 1, false>), grid, dim3(512), 0, s, p);
+    if (kind == 0 && unit && p.act == IR_ACT_NONE) return 0;
+    if (kind == 0 && unit && p.act == IR_ACT_GELU_TANH) return 1;
+    if (kind == 1 && p.act == IR_ACT_NONE) return 2;
+    return 3;
+}
+static int launch_gemm_pp(const IGemmParams& p, hipStream_t s, int form) {
+    const int MT = (p.M + GemmPP::BM - 1) / GemmPP::BM, NT = p.Cout / GemmPP::BN;
+    const dim3 grid(((MT + 7) / 8) * 8 * NT);   // always the XCD-padded order
+    if (form == 0) hipLaunchKernelGGL((gemm_pp_kernel<IR_ACT_NONE, 0, true>), grid, dim3(512), 0, s, p);
+    else if (form == 1) hipLaunchKernelGGL((gemm_pp_kernel<IR_ACT_GELU_TANH, 0, true>), grid, dim3(512), 0, s, p);
+    else if (form == 2) hipLaunchKernelGGL((gemm_pp_kernel<IR_ACT_NONE, 1, false>), grid, dim3(512), 0, s, p);
     else hipLaunchKernelGGL((gemm_pp_kernel<-1, -1, false>), grid, dim3(512), 0, s, p);
     return hipGetLastError() == hipSuccess ? 0 : -1;
 }
@@ -1646,12 +1656,32 @@ int ir_igemm_splitk(const IGemmParams& p) {
     return (KT + per - 1) / per;   // no empty split
 }
 
+// The igemm_kernel instantiation of a launch with BN-column tiles (WM x WN waves in the 4-wave form) and ks split-K slices -> rt.bn, bk, stages, waves
 template <int BM, int BN, int WM, int WN>
-static int launch_cfg(const IGemmParams& pin, hipStream_t s) {
+static void igemm_variant(const IGemmParams& p, int ks, IGemmRoute& rt) {
+    const int MT = (p.M + BM - 1) / BM, NT = p.Cout_pad / BN;
+    const int tiles = (int)tile_grid(MT, NT);
+    const bool k64 = (p.Cin & 63) == 0;
+    // the four-tile ring (igemm_kernel's NST): launches of at most one workgroup per CU with at least eight k-tiles per workgroup (with more
+    // workgroups the two-tile form's second workgroup per CU covers the waits better: 16384 x 640 -> 5120 at M = 1024 ran 17 against 25 us)
+    constexpr int ring_max = 256;
+    const int kt_all = p.taps * (p.Cin / 64), kt_per = ks > 1 ? (kt_all + ks - 1) / ks : kt_all;
+    const bool ring = k64 && !g_ir_plain_kernels && (long)tiles * (ks > 1 ? ks : 1) <= ring_max && kt_per >= 8;
+    // ... and with EIGHT waves (two per SIMD, each a 32-row slice of the tile) where the tile is 2 x 2 waves: alone on its SIMD a wave pays the
+    // issue of its LDS-DMA pieces (about 64 cycles each, 8 per k-tile = as long as its 32 MFMAs) with the matrix pipe idle; the second wave's
+    // MFMAs run under them. Not with fused GroupNorm statistics (their block reduction sums per wave row: another order). A split launch
+    // writes partial tiles and has no statistics.
+    rt.bn = BN; rt.bk = k64 ? 64 : 32; rt.stages = ring ? 4 : 2;
+    rt.waves = (ring && WM == 2 && WN == 2 && (ks > 1 || !p.gn_part)) ? 8 : 4;
+    rt.padded = tile_order_padded(MT); rt.idle = rt.padded && (MT & 7);
+}
+
+template <int BM, int BN, int WM, int WN>
+static int launch_cfg(const IGemmParams& pin, hipStream_t s, const IGemmRoute& rt) {
     IGemmParams p = pin;
     const int MT = (p.M + BM - 1) / BM, NT = p.Cout_pad / BN;
     const int tiles = (int)tile_grid(MT, NT);
-    const int ks = p.ks_ws ? ir_igemm_splitk(pin) : 0;
+    const int ks = rt.splits;
     const dim3 grid(tiles, ks > 1 ? ks : 1);
     if (ks > 1) {   // partial tiles into the workspace; bias / activation / residual in splitk_finish_kernel
         p.ksplit = ks;
@@ -1661,17 +1691,10 @@ static int launch_cfg(const IGemmParams& pin, hipStream_t s) {
     } else {
         p.ksplit = 0;
     }
-    const bool k64 = (p.Cin & 63) == 0;
-    // the four-tile ring (igemm_kernel's NST): launches of at most one workgroup per CU with at least eight k-tiles per workgroup (with more
-    // workgroups the two-tile form's second workgroup per CU covers the waits better: 16384 x 640 -> 5120 at M = 1024 ran 17 against 25 us)
-    constexpr int ring_max = 256;
-    const int kt_all = p.taps * (p.Cin / 64), kt_per = ks > 1 ? (kt_all + ks - 1) / ks : kt_all;
-    if (k64 && !g_ir_plain_kernels && (long)tiles * (ks > 1 ? ks : 1) <= ring_max && kt_per >= 8) {
-        // ... and with EIGHT waves (two per SIMD, each a 32-row slice of the tile) where the tile is 2 x 2 waves: alone on its SIMD a wave pays the
-        // issue of its LDS-DMA pieces (about 64 cycles each, 8 per k-tile = as long as its 32 MFMAs) with the matrix pipe idle; the second wave's
-        // MFMAs run under them. Not with fused GroupNorm statistics (their block reduction sums per wave row: another order).
+    const bool k64 = rt.bk == 64;
+    if (rt.stages == 4) {
         if constexpr (WM == 2 && WN == 2) {
-            if (!p.gn_part) {
+            if (rt.waves == 8) {
                 if (p.taps == 9) hipLaunchKernelGGL((igemm_kernel<BM, BN, 4, 2, 9, 64, true, 4>), dim3(grid), dim3(512), 0, s, p);
                 else hipLaunchKernelGGL((igemm_kernel<BM, BN, 4, 2, 1, 64, true, 4>), dim3(grid), dim3(512), 0, s, p);
                 goto launched;
@@ -1720,26 +1743,117 @@ static bool igemm_vec(const IGemmParams& p) {
     return !((p.out_cs & 3) || (p.res && (p.res_cs & 3)) || (p.out2 && (p.out2_cs & 3)) || (reinterpret_cast<uintptr_t>(p.res) & 15) ||
              (reinterpret_cast<uintptr_t>(p.out2) & 7) || (p.gate && (p.gate_stride & 3)));
 }
-int ir_igemm_kernel_id(const IGemmParams& pin) {
+// The one place that decides what runs a launch: kernel, instantiation, split count and tile order (kernels.h: IGemmRoute), in the order of
+// precedence ir_launch_igemm used to spell out. p.vec is computed here; a launch ir_launch_igemm refuses has a route all the same.
+IGemmRoute ir_igemm_route(const IGemmParams& pin) {
     IGemmParams p = pin;
     p.vec = igemm_vec(p);
-    if (p.up2x2) return ir_conv_s1_up2x2_takes(p) ? 0 : 3;
-    if (p.ks_ws && ir_igemm_splitk(p) > 1) return 4;
-    if (ir_conv64_takes(p)) return 5;
-    if (ir_conv_s1_takes(p) || ir_conv_s1_fp8_takes(p)) return 0;
-    if (takes_halo_pp(p)) return 1;
-    if (takes_gemm_pp(p)) return 2;
-    if (takes_halo(p)) return 3;
-    return 4;
+    IGemmRoute rt = {};
+    rt.taps = p.taps; rt.fp8 = p.fp8;
+    auto halo_tiles = [&](int ph, int pw, int h, int w, int mul) {   // conv_halo*: patches of ph x pw output pixels are the row tiles
+        const long MT = (long)p.NB * mul * ((h + ph - 1) / ph) * ((w + pw - 1) / pw);
+        rt.padded = tile_order_padded(MT); rt.idle = rt.padded && (MT & 7);
+    };
+    if (p.up2x2) {   // phase weights are no 9-tap weights: only the two phase kernels may run them
+        rt.form = 2;
+        if (ir_conv_s1_up2x2_takes(p)) { rt.kernel = 0; return rt; }
+        rt.kernel = 3; rt.bn = p.Cout_pad % 128 == 0 ? 128 : 64;
+        halo_tiles(8, 16, p.H, p.W, 4);
+        return rt;
+    }
+    rt.form = p.up ? 1 : 0;
+    const int ks = p.ks_ws ? ir_igemm_splitk(p) : 0;
+    if (ks > 1) rt.splits = ks;   // small-M launch of a caller that allows split-K: generic kernel, K split over blockIdx.y
+    else if (ir_conv64_takes(p)) { rt.kernel = 5; return rt; }
+    else if (ir_conv_s1_takes(p) || ir_conv_s1_fp8_takes(p)) { rt.kernel = 0; if (p.nrm_scale || p.nrm_shift) rt.form = 3; return rt; }
+    else if (takes_halo_pp(p)) { rt.kernel = 1; rt.bn = 128; halo_tiles(16, 16, p.Ho, p.Wo, 1); return rt; }
+    else if (takes_gemm_pp(p)) {
+        rt.kernel = 2; rt.form = gemm_pp_form(p); rt.bn = GemmPP::BN; rt.padded = 1;
+        rt.vt = ir_igemm_writes_vt(p) != 0;
+        rt.idle = (((p.M + GemmPP::BM - 1) / GemmPP::BM) & 7) != 0;
+        return rt;
+    } else if (takes_halo(p)) { rt.kernel = 3; rt.bn = p.Cout_pad % 128 == 0 ? 128 : 64; halo_tiles(8, 16, p.Ho, p.Wo, 1); return rt; }
+    rt.kernel = 4; rt.form = 0;
+    if (p.Cout_pad % 128 == 0) igemm_variant<128, 128, 2, 2>(p, ks, rt);
+    else if (p.Cout_pad % 64 == 0) igemm_variant<128, 64, 2, 2>(p, ks, rt);
+    else igemm_variant<128, 32, 4, 1>(p, ks, rt);
+    return rt;
+}
+long long ir_igemm_route_pack(const IGemmRoute& r) {
+    return (long long)r.kernel | (long long)(r.form & 7) << 4 | (long long)(r.vt != 0) << 7 | (long long)(r.bn / 4) << 8 | (long long)(r.bk / 16) << 16 | (long long)r.stages << 20 |
+           (long long)r.waves << 24 | (long long)r.taps << 28 | (long long)r.splits << 32 | (long long)r.padded << 40 | (long long)r.idle << 41 |
+           (long long)r.fp8 << 42;
+}
+int ir_igemm_kernel_id(const IGemmParams& p) { return ir_igemm_route(p).kernel; }
+
+// The range of ir_igemm_route (kernels.h), by asking it: launches filled in as the host layer's conv() fills them, over a grid that has a value
+// on either side of every threshold the rule and its takes_*() predicates read. Addresses are only tested for null and alignment.
+int ir_igemm_route_range(long long* out, int cap) {
+    alignas(16) static unsigned char some[16];
+    std::vector<long long> seen;
+    const int plain_was = g_ir_plain_kernels;
+    static const int cins[] = {32, 64, 96, 128, 224, 256, 512, 1536}, couts[] = {32, 64, 96, 128, 192, 1152};
+    static const int rows[] = {1, 260, 1024, 8315, 12032, 12288, 16384, 16385};              // linear: M
+    static const int maps[][2] = {{8, 8}, {16, 32}, {32, 128}, {64, 224}, {64, 256}};        // conv: H x W of the input
+    // epilogue forms: bf16 / fp32 output, bf16 / fp32 residual, gate, second output, periodic residual, activation
+    struct Epi { int out_f32, res, res_f32, gate, out2, res_mod, act; };
+    static const Epi epis[] = {{0, 0, 0, 0, 0, 0, IR_ACT_NONE}, {0, 0, 0, 0, 0, 0, IR_ACT_GELU_TANH}, {1, 1, 1, 1, 0, 0, IR_ACT_NONE}, {1, 1, 1, 0, 0, 64, IR_ACT_NONE},
+                               {0, 1, 0, 0, 1, 0, IR_ACT_NONE}, {1, 0, 0, 0, 0, 0, IR_ACT_NONE}, {0, 1, 0, 0, 0, 0, IR_ACT_NONE}};
+    for (int plain = 0; plain < 2; ++plain)
+        for (int taps : {1, 9})
+            for (int cin : cins)
+                for (int cout : couts)
+                    for (int shape = 0; shape < (taps == 9 ? 5 * 4 : 8); ++shape)        // conv: map x (stride 1, stride 2, up, up with phase weights)
+                        for (const Epi& e : epis)
+                            for (int splitk = 0; splitk < 2; ++splitk) {
+                                IGemmParams p;
+                                memset(&p, 0, sizeof p);
+                                g_ir_plain_kernels = plain;
+                                p.in = reinterpret_cast<const bf16_t*>(some); p.wgt = p.in; p.out = some;
+                                p.taps = taps; p.Cin = cin; p.in_cs = cin; p.wgt_rs = (long)taps * cin; p.Cout = p.Cout_pad = cout;
+                                p.NB = 1; p.stride = 1; p.Ho = p.Wo = p.H = p.W = 1;
+                                p.act = e.act; p.out_scale = 1.f; p.out_f32 = e.out_f32; p.out_cs = cout; p.rows_per_batch = 1 << 30;
+                                if (e.res) { p.res = some; p.res_f32 = e.res_f32; p.res_cs = cout; p.res_mod = e.res_mod; }
+                                if (e.gate) p.gate = reinterpret_cast<const float*>(some);
+                                if (e.out2) { p.out2 = reinterpret_cast<bf16_t*>(some); p.out2_cs = cout; }
+                                if (taps == 9) {
+                                    const int form = shape & 3;
+                                    p.H = maps[shape >> 2][0]; p.W = maps[shape >> 2][1]; p.pad = form == 1 ? 0 : 1;
+                                    p.stride = form == 1 ? 2 : 1; p.up = form >= 2;
+                                    p.Ho = form == 1 ? p.H / 2 : (p.up ? 2 * p.H : p.H);
+                                    p.Wo = form == 1 ? p.W / 2 : (p.up ? 2 * p.W : p.W);
+                                    p.M = p.Ho * p.Wo;
+                                    p.item_rows = p.M;
+                                    if (form == 3) {
+                                        if (plain) continue;
+                                        p.wgt_rs = 4L * cin; p.up2x2 = 1;
+                                        if (!ir_igemm_up2x2_takes(p)) continue;   // (conv() asks first)
+                                    }
+                                } else {
+                                    p.M = rows[shape];
+                                }
+                                if (splitk) {
+                                    p.allow_splitk = 1;
+                                    if (ir_igemm_splitk(p) <= 1) continue;
+                                    p.ks_ws = reinterpret_cast<float*>(some);
+                                }
+                                IGemmRoute rt = ir_igemm_route(p);
+                                rt.splits = rt.padded = rt.idle = rt.vt = 0;
+                                const long long key = ir_igemm_route_pack(rt);
+                                if (std::find(seen.begin(), seen.end(), key) == seen.end()) seen.push_back(key);
+                            }
+    g_ir_plain_kernels = plain_was;
+    for (int i = 0; i < (int)seen.size() && i < cap; ++i) out[i] = seen[i];
+    return (int)seen.size();
 }
 
 // Host launcher. Returns 0 or a negative error code; validates every shape assumption the kernel makes.
-int ir_launch_igemm(const IGemmParams& pin, hipStream_t s) {
+int ir_launch_igemm(const IGemmParams& pin, hipStream_t s, const IGemmRoute* route) {
     IGemmParams p = pin;
     if (p.M <= 0) return 0;
     if (p.up2x2) {   // phase weights are no 9-tap weights: only the two phase kernels may run them
         if ((reinterpret_cast<uintptr_t>(p.in) & 15) || (reinterpret_cast<uintptr_t>(p.wgt) & 15) || (reinterpret_cast<uintptr_t>(p.out) & 15) || !p.out) return -7;
-        if (ir_conv_s1_up2x2_takes(p)) return ir_launch_conv_s1_up2x2(p, s);
+        if ((route ? *route : ir_igemm_route(p)).kernel == 0) return ir_launch_conv_s1_up2x2(p, s);
         return takes_halo_up2x2(p) ? launch_halo_up2x2(p, s) : -15;
     }
     if ((p.nrm_scale || p.nrm_shift) && !ir_conv_s1_norm_takes(p)) return -16;   // only conv_halo_s1_kernel<0, 9, NORM> normalises its input: the caller asks first
@@ -1761,22 +1875,19 @@ int ir_launch_igemm(const IGemmParams& pin, hipStream_t s) {
     }
     if (p.gn_part && (!p.vec || p.gn_chunks <= 0 || p.gn_chunks != ir_igemm_gn_chunks(p))) return -13;
     if (p.fp8 && (!takes_halo(p) || !p.gate || p.act != IR_ACT_NONE)) return -14;  // fp8 operands: stride-1 3x3 halo kernel only
-    if (p.ks_ws && ir_igemm_splitk(p) > 1) {   // small-M launch of a caller that allows split-K: generic kernel, K split over blockIdx.y
-        if (p.Cout_pad % 128 == 0) return launch_cfg<128, 128, 2, 2>(p, s);
-        if (p.Cout_pad % 64 == 0) return launch_cfg<128, 64, 2, 2>(p, s);
-        return launch_cfg<128, 32, 4, 1>(p, s);
+    const IGemmRoute rt = route ? *route : ir_igemm_route(p);
+    // only the launch that writes the transposed copy (gemm_pp_kernel's bf16 form: the caller asked first) gets its address; no other kernel reads
+    // the field, so clearing it for all of them changes nothing they compute
+    if (!rt.vt) p.vt_out = nullptr;
+    switch (rt.kernel) {
+        case 5: return ir_launch_conv64(p, s);
+        case 0: return p.fp8 ? ir_launch_conv_s1_fp8(p, s) : ir_launch_conv_s1(p, s);
+        case 1: return launch_halo_pp(p, s);
+        case 2: return launch_gemm_pp(p, s, rt.form);
+        case 3: return rt.bn == 128 ? launch_halo<128>(p, s) : launch_halo<64>(p, s);
+        default: break;
     }
-    if (ir_conv64_takes(p)) return ir_launch_conv64(p, s);
-    if (ir_conv_s1_takes(p)) return ir_launch_conv_s1(p, s);
-    if (ir_conv_s1_fp8_takes(p)) return ir_launch_conv_s1_fp8(p, s);
-    if (takes_halo_pp(p)) return launch_halo_pp(p, s);
-    if (p.vt_out && !ir_igemm_writes_vt(p)) p.vt_out = nullptr;   // only gemm_pp_kernel's bf16 form writes the transposed copy: the caller asked first
-    if (takes_gemm_pp(p)) return launch_gemm_pp(p, s);
-    if (takes_halo(p)) {
-        if (p.Cout_pad % 128 == 0) return launch_halo<128>(p, s);
-        return launch_halo<64>(p, s);
-    }
-    if (p.Cout_pad % 128 == 0) return launch_cfg<128, 128, 2, 2>(p, s);
-    if (p.Cout_pad % 64 == 0) return launch_cfg<128, 64, 2, 2>(p, s);
-    return launch_cfg<128, 32, 4, 1>(p, s);
+    if (rt.bn == 128) return launch_cfg<128, 128, 2, 2>(p, s, rt);
+    if (rt.bn == 64) return launch_cfg<128, 64, 2, 2>(p, s, rt);
+    return launch_cfg<128, 32, 4, 1>(p, s, rt);
 }

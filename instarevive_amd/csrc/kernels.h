@@ -72,9 +72,34 @@ struct IGemmParams {
 bool ir_conv_s1_norm_takes(const IGemmParams& p);
 int ir_igemm_writes_vt(const IGemmParams& p);
 int ir_launch_vt_pad_init(bf16_t* vt, int heads_total, int D, int DV, int T, int Tpad, hipStream_t s);
-int ir_launch_igemm(const IGemmParams& p, hipStream_t s);
+struct IGemmRoute;
+// route: what ir_igemm_route(p) returned for this very p (a caller that asked for its profiler row passes it on), or null
+int ir_launch_igemm(const IGemmParams& p, hipStream_t s, const IGemmRoute* route = nullptr);
 // which kernel ir_launch_igemm picks for p: 0 conv_halo_s1, 1 conv_halo_pp, 2 gemm_pp, 3 conv_halo, 4 igemm_kernel (profiler rows)
 int ir_igemm_kernel_id(const IGemmParams& p);
+// The whole choice ir_launch_igemm makes for p, made in ONE place (ir_igemm_route): the launcher dispatches on it, ir_igemm_kernel_id is its
+// `kernel` field and ir_op_igemm_route reports it to the tests.
+struct IGemmRoute {
+    int kernel;   // ir_igemm_kernel_id's value (5: conv64_kernel)
+    int form;     // gemm_pp_kernel: 0 <NONE, 0, unit>, 1 <GELU_TANH, 0, unit>, 2 <NONE, 1>, 3 the general <-1, -1>; the conv kernels: 0 plain,
+                  // 1 nearest-2x folded in, 2 sub-pixel phase weights, 3 (conv_halo_s1 only) the NORM form; igemm_kernel: 0
+    int bn;       // output columns per tile (conv_halo_s1 / conv64: 0, their own files decide)
+    int bk, stages, waves;   // igemm_kernel: BK (64 / 32), ring of 2 / 4 k-tiles (NST), 4 / 8 waves; 0 for the other kernels
+    int taps;
+    int splits;   // split-K slices (0: none); > 1 only with kernel 4, followed by splitk_finish_kernel
+    int padded;   // tile order of tile_of_block: 1 XCD-padded (grid = row tiles rounded up to 8, times column tiles), 0 one block per tile
+    int idle;     // 1: a padded grid that has blocks without a tile
+    int fp8;
+    int vt;       // 1: the launch writes IGemmParams::vt_out itself (ir_igemm_writes_vt: gemm_pp_kernel's bf16 form on whole tiles); the launcher
+                  // hands vt_out to no other kernel
+};
+IGemmRoute ir_igemm_route(const IGemmParams& p);
+// bits 0-3 kernel, 4-6 form, 7 vt, 8-15 bn / 4, 16-19 bk / 16, 20-23 stages, 24-27 waves, 28-31 taps, 32-39 splits, 40 padded, 41 idle, 42 fp8
+long long ir_igemm_route_pack(const IGemmRoute& r);
+// The range of ir_igemm_route for bf16 operands, taken from the rule itself: the distinct packed routes - splits, padded, idle and vt cleared -
+// it returns over a grid of launches that crosses every threshold it reads (taps, Cin, Cout_pad, rows / map size, stride, upsample forms,
+// epilogue forms, split-K, plain kernels). -> their number; the first min(number, cap) in out. No device is touched.
+int ir_igemm_route_range(long long* out, int cap);
 // Pixel tiles per image the kernel ir_launch_igemm would pick for p writes statistics for, or 0 if this launch cannot fuse them.
 int ir_igemm_gn_chunks(const IGemmParams& p);
 // Split count ir_launch_igemm would use for p given a workspace (0: none); see IGemmParams::allow_splitk.
