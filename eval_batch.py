@@ -60,12 +60,14 @@ def parse_args():
                     "be at least 192 for two blocks")
     ap.add_argument("--clipiqa_model", default=None, help="score CLIP-IQA (no reference needed) of both output folders on the GPU (inference.py --clipiqa_model: "
                     "OpenAI's RN50.pt or an .npz). Works with or without --gt and --niqe_params; its column comes last. --image_size must be at least 32")
+    ap.add_argument("--musiq_model", default=None, help="score MUSIQ (no reference needed) of both output folders on the GPU (inference.py --musiq_model: an .npz "
+                    "in tools/evaluate_musiq.py's names or pyiqa's .pth). Works with or without --gt, --niqe_params and --clipiqa_model; its column comes last")
     ap.add_argument("--clip_bpe", default=None, help="with --clipiqa_model: the folder that holds CLIP's BPE table (inference.py --clip_bpe)")
     ap.add_argument("--degrade", nargs="?", const="lq", default=None, metavar="lq|realesrgan|FILE.json", help="--input holds GROUND TRUTH: the centre crops are degraded on "
                     "the GPU (inference.py --degrade: blur, bilinear downsample, noise, JPEG, bilinear resize back; `realesrgan`: the reference's second-order "
                     "validation recipe) and the LQ images restored; needs "
                     "--image_size to be a multiple of 64 of at least 512 (the crop is then the network input as it is). Without --gt the input folder "
-                    "is the ground truth of --lpips_lin / --niqe_params / --clipiqa_model")
+                    "is the ground truth of --lpips_lin / --niqe_params / --clipiqa_model / --musiq_model")
     ap.add_argument("--degrade_seed", type=int, default=231, help="with --degrade: seeds every file's draws together with the crc32 of its input-relative path")
     ap.add_argument("--save_lq", default=None, metavar="DIR", help="with --degrade: write the synthesised LQ crops to DIR")
     ap.add_argument("--jpeg_decoder", default="host", choices=["host", "gpu"], help="inference.py's flag; only `host` here: every input is centre-cropped on the "
@@ -95,7 +97,8 @@ def main():
     ext_out = cli.save_ext(args)
     niqe_params = cli.load_niqe_params(args)
     clipiqa_model = cli.load_clipiqa_model(args)
-    noref = bool(niqe_params) or clipiqa_model is not None
+    musiq_model = cli.load_musiq_model(args)
+    noref = bool(niqe_params) or clipiqa_model is not None or musiq_model is not None
     recipe = geo = None
     if args.save_lq and not args.degrade:
         raise SystemExit("--save_lq writes the images --degrade synthesises: give --degrade as well")
@@ -133,7 +136,8 @@ def main():
     if args.lpips_alexnet and not args.lpips_lin:
         raise SystemExit("--lpips_alexnet needs --lpips_lin (the lpips linear heads)")
     with_lpips = {"lpips": True} if args.lpips_lin else {}
-    with_niqe = {**({"niqe": True} if niqe_params else {}), **({"clipiqa": True} if clipiqa_model else {}), **({"paired": bool(args.gt)} if noref else {})}
+    with_niqe = {**({"niqe": True} if niqe_params else {}), **({"clipiqa": True} if clipiqa_model else {}), **({"musiq": True} if musiq_model else {}),
+                 **({"paired": bool(args.gt)} if noref else {})}
     lookup = None
     if args.gt or noref:
         from instarevive_amd.metrics import GroundTruth, Report
@@ -146,6 +150,9 @@ def main():
         if clipiqa_model:
             from instarevive_amd import clipiqa
             clipiqa.configure(m.model.ctx, clipiqa_model)
+        if musiq_model:
+            from instarevive_amd import musiq
+            musiq.configure(m.model.ctx, musiq_model)
 
     def read(f):
         crop = center_crop_arr(Image.open(f).convert("RGB"), args.image_size)
@@ -191,15 +198,15 @@ def main():
                              png=whole if gpu_png else None, png_wrap=False, png_runs=args.png_runs,
                              **({"jpeg": whole, "jpeg_quality": args.jpeg_quality, "jpeg_subsampling": args.jpeg_subsampling} if gpu_jpg else {}),
                              gt=cli.in_step(truths) if lookup else None, **with_lpips, **({"niqe": niqe_params} if niqe_params else {}),
-                             **({"clipiqa": True} if clipiqa_model else {}),
+                             **({"clipiqa": True} if clipiqa_model else {}), **({"musiq": True} if musiq_model else {}),
                              **({"resize": cli.in_step(records), "degrade": cli.in_step(dparams), "lq_sink": lq_images.append if args.save_lq else None} if recipe else {}))
-    no_score = {"niqe": 0, "clipiqa": 0}
+    no_score = {"niqe": 0, "clipiqa": 0, "musiq": 0}
     for group, out in zip(batches, results):
         preds, stage1 = out[:2]
         if reports:
             for rep, folder, scores in zip(reports, (args.output, cond_dir), out[2]):
                 for f, score in zip(group, scores):
-                    missing = rep.unscored(score)   # NaN: the image has no NIQE, or no CLIP-IQA
+                    missing = rep.unscored(score)   # NaN: the image has no NIQE, no CLIP-IQA or no MUSIQ
                     if missing:
                         no_score[missing] += 1
                     else:
@@ -221,12 +228,14 @@ def main():
     if reports:
         for rep, folder in zip(reports, (args.output, cond_dir)):
             lines = rep.write()
-            print(f"[rank {rank}] {' / '.join(f for f, on in (('--gt', args.gt), ('--niqe_params', niqe_params), ('--clipiqa_model', clipiqa_model)) if on)}: scored {len(rep.rows)} files of {folder}"
+            print(f"[rank {rank}] {' / '.join(f for f, on in (('--gt', args.gt), ('--niqe_params', niqe_params), ('--clipiqa_model', clipiqa_model), ('--musiq_model', musiq_model)) if on)}: scored {len(rep.rows)} files of {folder}"
                   + (f" against {args.gt}" if args.gt else "") + f" -> {rep.path}")
             for ln in lines:
                 print(ln)
         if no_score["clipiqa"]:
             print(f"[rank {rank}] --clipiqa_model: {no_score['clipiqa']} files were not scored (CLIP-IQA needs 32 x 32 pixels)")
+        if no_score["musiq"]:
+            print(f"[rank {rank}] --musiq_model: {no_score['musiq']} files were not scored (a resized side rounds to 0)")
         if no_score["niqe"]:
             print(f"[rank {rank}] --niqe_params: {no_score['niqe']} files were not scored (NIQE needs 96 x 96 blocks and two complete feature rows)")
 

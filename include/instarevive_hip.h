@@ -42,7 +42,9 @@ enum { IR_STAGE_SWINIR = 0, IR_STAGE_VAE_ENCODE = 1, IR_STAGE_DIT = 2, IR_STAGE_
        IR_STAGE_JPEG_DECODE = 19 /* ir_jpeg_decode: h, w = the largest height and width among the files, flags = the largest stream_bytes,
                                     tile_size = subseq_bits; holds for any sampling and restart interval; the files of a batch share one
                                     workspace, so n only has to be >= 1; depends on these numbers alone (ctx may be NULL) */,
-       IR_STAGE_PNG_RUNS = 20 /* ir_png_encode_runs: n images, h, w = the VALID rectangle vh, vw; depends on the sizes alone (ctx may be NULL) */ };
+       IR_STAGE_PNG_RUNS = 20 /* ir_png_encode_runs: n images, h, w = the VALID rectangle vh, vw; depends on the sizes alone (ctx may be NULL) */,
+       IR_STAGE_MUSIQ = 21 /* ir_musiq: n images, h, w = the scored rectangle; depends on the sizes and on the shape bound by ir_musiq_configure
+                              (0 for a context that is not configured and for a size ir_musiq refuses) */ };
 /* ir_pipeline flags */
 enum { IR_FLAG_NO_PREPROCESS = 1, IR_FLAG_TILED = 2, IR_FLAG_FIX_WAVELET = 4, IR_FLAG_FIX_ADAIN = 8,
        /* ir_pipeline only, needs ir_dit_control_configure: run the DiT step with the ControlNet-Half branch, condition latent
@@ -485,6 +487,47 @@ int ir_clipiqa_scale_table(float* tab768);
 int ir_clipiqa_configure(ir_ctx* ctx, const int layers[4], int width, int heads, int out_dim, int n_pairs, float logit_scale_exp);
 int ir_clipiqa(ir_ctx* ctx, void* stream, const uint8_t* img, int rows, long pitch, int n, int h, int w, double* scores, float* feat_or_null,
                void* ws, size_t ws_bytes);
+
+/* MUSIQ (the no-reference metric `musiq` of the reference's evaluate_img.py; pyiqa's default koniq10k configuration) on the device;
+ * tools/evaluate_musiq.py states the definition as a torch model and is the model of this call. The input is x = (v / 255 - 0.5) * 2 in fp32
+ * through a 256-entry table. Scale s of an image is the image resized so that its longer side is longer[s] (torch's bicubic, A = -0.75,
+ * align_corners = False, clamped taps, no antialias, computed in fp64 from the table values and rounded once; the sides are
+ * round-half-even(side * longer / max(h, w)) of the double product), or the image itself where longer[s] is 0. Every scale is cut into
+ * patch x patch patches at stride patch with TensorFlow's 'SAME' padding (0 in the table's domain); patch (i, j) of a count_h x count_w grid
+ * has the hashed spatial index floor(i * ((float)grid / count_h)) * grid + floor(j * ((float)grid / count_w)). Each patch runs through the
+ * weight-standardised ResNet stem (conv 7 x 7 / 2, GroupNorm(32, 1e-6), ReLU, max-pool 3 x 3 / 2, one bottleneck with GroupNorm(32, 1e-4))
+ * and a linear to `hidden`; position_emb[index] and scale_emb[s] are added, the class token goes in front, `layers` pre-LN transformer blocks
+ * (LayerNorm 1e-6, heads of 64, exact GELU) run over all T tokens of the image, and the score is head(final LayerNorm(class token)). Every
+ * contraction is an exact-fp32 GEMM on the fp32-input MFMA (a k-ordered fmaf chain per output, whatever the tile, T or the batch place);
+ * GroupNorm, LayerNorm and softmax sums run in fp64 in a fixed order without floating-point atomics: an image gives the same bits on every
+ * call and at every position of a batch.
+ * ir_musiq_layout (host only, no context, no device): T of an h x w image, or -1 when a resized side rounds to 0 (e.g. 1 x 1000), for
+ * n_scales outside 1 .. 4 or when spatial_index is given and cap < T - 1. out_per_scale, when not NULL, gets per scale the six ints
+ * rh, rw, count_h, count_w, pad_top, pad_left; spatial_index, when not NULL, the hashed index of every patch token in token order (scale by
+ * scale, row by row). ir_musiq uses the same function.
+ * ir_musiq_configure binds fp32 tensors uploaded with ir_upload under these names (L = 0 .. layers - 1):
+ *   musiq.stem.conv.weight [64][3][7][7], musiq.block.conv1.weight [64][64][1][1], musiq.block.conv2.weight [64][64][3][3],
+ *   musiq.block.conv3.weight [256][64][1][1], musiq.block.proj.weight [256][64][1][1] - the STANDARDISED weights ((w - mean) / sqrt(var + 1e-5)
+ *   per output channel, biased variance, computed in fp64 and rounded once: tools/evaluate_musiq.py's standardize());
+ *   musiq.stem.gn.{weight,bias} [64], musiq.block.gn1 / gn2 [64], musiq.block.gn3 / gn_proj [256];
+ *   musiq.embedding.{weight,bias} [hidden][16384] over the (y, x, c) flattened 8 x 8 x 256 map; musiq.position_emb [grid * grid][hidden],
+ *   musiq.scale_emb [n_scales][hidden], musiq.cls_token [hidden];
+ *   musiq.layers.L.ln1 / ln2.{weight,bias}, musiq.layers.L.attn.{q,k,v,out}.{weight,bias} [hidden][hidden],
+ *   musiq.layers.L.mlp.fc1.{weight,bias} [mlp][hidden], musiq.layers.L.mlp.fc2.{weight,bias} [hidden][mlp];
+ *   musiq.final_ln.{weight,bias}, musiq.head.weight [1][hidden], musiq.head.bias [1].
+ * Supported: patch 32, hidden = 64 heads, hidden and mlp multiples of 32, 1 .. 64 layers, 1 .. 4 scales. The binding holds its own repacked
+ * copies. Returns -2 with ir_last_error naming the tensor when one is missing or has another shape, -1 for an unsupported shape.
+ * ir_musiq scores the top-left h x w of each of the n images of [n][rows][pitch] bytes (RGB8, addressed as ir_clipiqa addresses them):
+ * scores [n] doubles; feat, when not NULL, [n][hidden] floats, the final LayerNorm of the class token. All pointers are device pointers;
+ * stream-ordered, no allocation, no host synchronisation (capturable). ws: 256-byte aligned,
+ * ir_workspace_bytes(ctx, IR_STAGE_MUSIQ, n, h, w, 0, 0, 0) bytes. Returns -1 (nothing launched, nothing written) for a null pointer,
+ * n < 1, a size whose resized side rounds to 0 (ir_last_error names the size), h above rows, a pitch below 3 w, a short or misaligned
+ * workspace, and -13 for a context without ir_musiq_configure. */
+int ir_musiq_layout(int h, int w, int patch, int grid, int n_scales, const int* longer, int* out_per_scale, int* spatial_index_or_null, int cap);
+int ir_musiq_input_table(float* tab256);
+int ir_musiq_configure(ir_ctx* ctx, int patch, int hidden, int mlp, int heads, int layers, int grid, int n_scales, const int* longer);
+int ir_musiq(ir_ctx* ctx, void* stream, const uint8_t* img, int rows, long pitch, int n, int h, int w, double* scores, float* feat_or_null,
+             void* ws, size_t ws_bytes);
 
 /* Low-quality inputs from ground truth on the device: the first-order degradation of the reference's dataset/codeformer.py:140-163 and
  * tools/lq.py - a K x K blur, a bilinear downsample, Gaussian noise, a JPEG round trip, a bilinear resize back - without OpenCV and without

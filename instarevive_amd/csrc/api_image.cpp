@@ -1,4 +1,4 @@
-// The image tools of the C ABI: PNG and JPEG encoding, Pillow's resampling, PSNR-Y / SSIM-Y, LPIPS, CLIP-IQA, NIQE and the two degradation paths. Each entry
+// The image tools of the C ABI: PNG and JPEG encoding, Pillow's resampling, PSNR-Y / SSIM-Y, LPIPS, CLIP-IQA, MUSIQ, NIQE and the two degradation paths. Each entry
 // point checks its arguments and launches the kernels of its own .hip file; none of them runs a model stage, takes the workspace arena or is
 // profiled, so nothing here knows api.cpp's Run. Host code only, except for the tables the kernels read, which are computed here once.
 #include <math.h>
@@ -521,6 +521,161 @@ int ir_clipiqa(ir_ctx* c, void* stream, const uint8_t* img, int rows, long pitch
     return 0;
 }
 
+// ---------------------------------------------------------------- MUSIQ (musiq.hip)
+int ir_musiq_input_table(float* tab) {
+    if (!tab) return -1;
+    ir_musiq_input_table_host(tab);
+    return 0;
+}
+
+int ir_musiq_layout(int h, int w, int patch, int grid, int n_scales, const int* longer, int* out_per_scale, int* spatial_index, int cap) {
+    IrMusiqLayout lay;
+    if (ir_musiq_layout_host(h, w, patch, grid, n_scales, longer, &lay)) return -1;
+    if (spatial_index && cap < lay.patches) return -1;
+    for (int k = 0; k < lay.n_scales; ++k) {
+        const IrMusiqScale& g = lay.s[k];
+        if (out_per_scale) {
+            const int v[6] = {g.rh, g.rw, g.count_h, g.count_w, g.pad_top, g.pad_left};
+            memcpy(out_per_scale + 6 * k, v, sizeof v);
+        }
+        if (spatial_index)
+            for (int i = 0; i < g.count_h; ++i)
+                for (int j = 0; j < g.count_w; ++j) {   // the kernel's expression: torch's nearest interpolation of arange(grid)
+                    volatile float fi = (float)i * g.fh, fj = (float)j * g.fw;
+                    spatial_index[g.first + i * g.count_w + j] = std::min((int)floorf(fi), grid - 1) * grid + std::min((int)floorf(fj), grid - 1);
+                }
+    }
+    return lay.T;
+}
+
+namespace {
+// the device tensor [rows][cols] as the host array [cols][ld] at column col0 (a linear's weight as the GEMM's B operand)
+int transposed_into(ir_ctx* c, const float* dev_w, int rows, int cols, std::vector<float>& t, int ld, int col0) {
+    std::vector<float> w((size_t)rows * cols);
+    HIPOK(c, hipMemcpy(w.data(), dev_w, w.size() * 4, hipMemcpyDeviceToHost));
+    for (int r = 0; r < rows; ++r)
+        for (int k = 0; k < cols; ++k) t[(size_t)k * ld + col0 + r] = w[(size_t)r * cols + k];
+    return 0;
+}
+}  // namespace
+
+int ir_musiq_configure(ir_ctx* c, int patch, int hidden, int mlp, int heads, int layers, int grid, int n_scales, const int* longer) {
+    if (!c || !longer) return fail(c, -1, "ir_musiq_configure: null argument");
+    if (patch != 32 || heads < 1 || hidden != 64 * heads || mlp < 32 || mlp % 32 || layers < 1 || layers > IR_MUSIQ_MAX_LAYERS || grid < 1 || grid > 1024 ||
+        n_scales < 1 || n_scales > IR_MUSIQ_MAX_SCALES)
+        return fail(c, -1, "ir_musiq_configure: unsupported model (patch %d must be 32, hidden %d must be 64 x heads %d, mlp %d a multiple of 32, layers %d within 1 .. %d, "
+                    "grid %d, %d scales within 1 .. %d)", patch, hidden, heads, mlp, layers, IR_MUSIQ_MAX_LAYERS, grid, n_scales, IR_MUSIQ_MAX_SCALES);
+    for (int k = 0; k < n_scales; ++k)
+        if (longer[k] < 0) return fail(c, -1, "ir_musiq_configure: scale %d has the longer side %d", k, longer[k]);
+    HIPOK(c, hipSetDevice(c->device));
+    c->musiq.ok = false;
+    auto m = std::make_unique<IrMusiqModel>();
+    m->patch = patch; m->hidden = hidden; m->mlp = mlp; m->heads = heads; m->layers = layers; m->grid = grid; m->n_scales = n_scales;
+    for (int k = 0; k < n_scales; ++k) m->longer[k] = longer[k];
+    const size_t C = hidden, F = mlp, EK = (size_t)8 * 8 * 256;
+    struct Conv { const char* name; int cin, cout, ks; const float** dst; };
+    const Conv convs[5] = {{"stem.conv", 3, 64, 7, &m->stem_w}, {"block.conv1", 64, 64, 1, &m->cw[0]}, {"block.conv2", 64, 64, 3, &m->cw[1]},
+                           {"block.conv3", 64, 256, 1, &m->cw[2]}, {"block.proj", 64, 256, 1, &m->cw[3]}};
+    struct Vec { std::string name; size_t floats; const float** dst; };   // tensors that are copied as they are
+    std::vector<Vec> vecs;
+    auto norm = [&](const std::string& base, size_t nfl, const float** g, const float** b) {
+        vecs.push_back({base + ".weight", nfl, g});
+        vecs.push_back({base + ".bias", nfl, b});
+    };
+    norm("musiq.stem.gn", 64, &m->stem_g, &m->stem_b);
+    norm("musiq.block.gn1", 64, &m->cg[0], &m->cb[0]);
+    norm("musiq.block.gn2", 64, &m->cg[1], &m->cb[1]);
+    norm("musiq.block.gn3", 256, &m->cg[2], &m->cb[2]);
+    norm("musiq.block.gn_proj", 256, &m->cg[3], &m->cb[3]);
+    vecs.push_back({"musiq.embedding.bias", C, &m->emb_b});
+    vecs.push_back({"musiq.position_emb", (size_t)grid * grid * C, &m->pos});
+    vecs.push_back({"musiq.scale_emb", (size_t)n_scales * C, &m->semb});
+    vecs.push_back({"musiq.cls_token", C, &m->cls});
+    norm("musiq.final_ln", C, &m->fin_g, &m->fin_b);
+    vecs.push_back({"musiq.head.weight", C, &m->head_w});
+    vecs.push_back({"musiq.head.bias", 1, &m->head_b});
+    for (int l = 0; l < layers; ++l) {
+        IrMusiqBlock& b = m->blk[l];
+        const std::string base = fmt("musiq.layers.%d.", l);
+        norm(base + "ln1", C, &b.ln1g, &b.ln1b);
+        norm(base + "ln2", C, &b.ln2g, &b.ln2b);
+        vecs.push_back({base + "attn.out.bias", C, &b.ob});
+        vecs.push_back({base + "mlp.fc1.bias", F, &b.f1b});
+        vecs.push_back({base + "mlp.fc2.bias", C, &b.f2b});
+    }
+    auto tensor = [&](const std::string& name, size_t floats) { return exact_f32(c, "ir_musiq_configure", "the configured model's", name, floats); };
+    // every tensor is looked up before anything is replaced
+    for (const Conv& s : convs)
+        if (!tensor(fmt("musiq.%s.weight", s.name), (size_t)s.cout * s.cin * s.ks * s.ks)) return -2;
+    if (!tensor("musiq.embedding.weight", C * EK)) return -2;
+    for (const Vec& v : vecs)
+        if (!tensor(v.name, v.floats)) return -2;
+    static const char* const qkv[3] = {"q", "k", "v"};
+    for (int l = 0; l < layers; ++l) {
+        const std::string base = fmt("musiq.layers.%d.", l);
+        for (const char* a : {"q", "k", "v", "out"})
+            if (!tensor(base + "attn." + a + ".weight", C * C)) return -2;
+        for (const char* a : qkv)
+            if (!tensor(base + "attn." + a + ".bias", C)) return -2;
+        if (!tensor(base + "mlp.fc1.weight", F * C) || !tensor(base + "mlp.fc2.weight", C * F)) return -2;
+    }
+
+    std::vector<void*>& own = c->own[OWN_MUSIQ];
+    release_list(own);
+    HIPOK(c, hipDeviceSynchronize());
+    float tab[256];
+    ir_musiq_input_table_host(tab);
+    if (int e = own_copy(c, own, tab, sizeof tab, hipMemcpyHostToDevice, &m->tab)) return e;
+    std::vector<float> t;
+    for (const Conv& s : convs) {
+        if (int e = repacked_conv(c, tensor(fmt("musiq.%s.weight", s.name), (size_t)s.cout * s.cin * s.ks * s.ks), s.cin, s.cout, s.ks, t)) return e;
+        if (int e = own_copy(c, own, t.data(), t.size() * 4, hipMemcpyHostToDevice, s.dst)) return e;
+    }
+    auto linear = [&](const std::string& name, int rows, int cols, const float** dst) {   // [rows][cols] -> [cols][rows]
+        t.assign((size_t)rows * cols, 0.f);
+        if (int e = transposed_into(c, tensor(name, (size_t)rows * cols), rows, cols, t, rows, 0)) return e;
+        return own_copy(c, own, t.data(), t.size() * 4, hipMemcpyHostToDevice, dst);
+    };
+    if (int e = linear("musiq.embedding.weight", hidden, (int)EK, &m->emb_w)) return e;
+    for (const Vec& v : vecs)
+        if (int e = own_copy(c, own, tensor(v.name, v.floats), v.floats * 4, hipMemcpyDeviceToDevice, v.dst)) return e;
+    for (int l = 0; l < layers; ++l) {
+        IrMusiqBlock& b = m->blk[l];
+        const std::string base = fmt("musiq.layers.%d.", l);
+        t.assign(C * 3 * C, 0.f);   // q | k | v side by side: one GEMM, the same chain per output
+        std::vector<float> bias(3 * C);
+        for (int k = 0; k < 3; ++k) {
+            if (int e = transposed_into(c, tensor(base + "attn." + qkv[k] + ".weight", C * C), hidden, hidden, t, 3 * hidden, k * hidden)) return e;
+            HIPOK(c, hipMemcpy(bias.data() + k * C, tensor(base + "attn." + qkv[k] + ".bias", C), C * 4, hipMemcpyDeviceToHost));
+        }
+        if (int e = own_copy(c, own, t.data(), t.size() * 4, hipMemcpyHostToDevice, &b.qkvw)) return e;
+        if (int e = own_copy(c, own, bias.data(), bias.size() * 4, hipMemcpyHostToDevice, &b.qkvb)) return e;
+        if (int e = linear(base + "attn.out.weight", hidden, hidden, &b.ow)) return e;
+        if (int e = linear(base + "mlp.fc1.weight", mlp, hidden, &b.f1w)) return e;
+        if (int e = linear(base + "mlp.fc2.weight", hidden, mlp, &b.f2w)) return e;
+    }
+    m->ok = true;
+    c->musiq = *m;
+    ++c->generation;
+    return 0;
+}
+
+int ir_musiq(ir_ctx* c, void* stream, const uint8_t* img, int rows, long pitch, int n, int h, int w, double* scores, float* feat, void* ws, size_t ws_bytes) {
+    if (!c || !img || !scores || !ws) return fail(c, -1, "ir_musiq: null argument");
+    if (int e = check_rect(c, "ir_musiq", nullptr, n, h, w, 1, {{rows, pitch}})) return e;
+    if (!c->musiq.ok) return fail(c, -13, "ir_musiq: MUSIQ not configured (ir_musiq_configure)");
+    IrMusiqLayout lay;
+    if (ir_musiq_layout_host(h, w, c->musiq.patch, c->musiq.grid, c->musiq.n_scales, c->musiq.longer, &lay))
+        return fail(c, -1, "ir_musiq: a resized side of a %d x %d image rounds to 0", h, w);
+    IrMusiqPlan pl;
+    if (ir_musiq_plan(c->musiq, n, h, w, &pl)) return fail(c, -1, "ir_musiq: n %d of %d x %d is more than one call takes (4096 images, 2^31 rows)", n, h, w);
+    if (int e = check_ws(c, "ir_musiq", ws, ws_bytes, pl.total, 256)) return e;
+    if ((reinterpret_cast<uintptr_t>(scores) & 7) || (reinterpret_cast<uintptr_t>(feat) & 3)) return fail(c, -1, "ir_musiq: scores / feat not aligned");
+    use_ctx(c);
+    if (ir_launch_musiq(c->musiq, img, rows, pitch, n, h, w, scores, feat, ws, (hipStream_t)stream)) return fail(c, -100, "ir_musiq: launch failed");
+    return 0;
+}
+
 // ---------------------------------------------------------------- NIQE's block statistics (niqe.hip)
 // the half-size fp64 luma plane of every image's scored rectangle
 static size_t niqe_workspace(int n, int h, int w) {
@@ -636,10 +791,11 @@ int ir_host::image_init(ir_ctx* c) {
     return upload(tab, sizeof tab, &c->niqe_tab);
 }
 
-// Sizes alone decide every answer except CLIP-IQA's, which also takes the configured layer counts: no context is needed for the others.
+// Sizes alone decide every answer except CLIP-IQA's and MUSIQ's, which also take the configured model's shape: no context is needed for the others.
 bool ir_host::image_workspace(ir_ctx* c, int stage, int n, int h, int w, int flags, int tile_size, size_t* bytes) {
     const bool some = n >= 1 && h >= 1 && w >= 1;
     IrClipiqaPlan cp;
+    IrMusiqPlan mp;
     IrLpipsPlan lp;
     IrJpegLayout jl;
     *bytes = 0;
@@ -648,6 +804,7 @@ bool ir_host::image_workspace(ir_ctx* c, int stage, int n, int h, int w, int fla
         case IR_STAGE_DEGRADE: if (n >= 1) *bytes = ir_degrade_workspace(h, w); break;   // the images of a batch share it
         case IR_STAGE_NIQE: if (n >= 1 && h >= IR_NIQE_BLOCK && w >= IR_NIQE_BLOCK) *bytes = niqe_workspace(n, h, w); break;
         case IR_STAGE_CLIPIQA: if (c && c->clipiqa.ok && !ir_clipiqa_plan(c->clipiqa, n, h, w, &cp)) *bytes = cp.total; break;
+        case IR_STAGE_MUSIQ: if (c && c->musiq.ok && !ir_musiq_plan(c->musiq, n, h, w, &mp)) *bytes = mp.total; break;
         case IR_STAGE_LPIPS: if (!ir_lpips_plan(n, h, w, &lp)) *bytes = lp.total; break;
         case IR_STAGE_METRICS: if (some) *bytes = metrics_workspace(n, h, w); break;
         case IR_STAGE_JPEG: if (ir_jpeg_layout(n, h, w, flags, tile_size, &jl)) *bytes = jl.total; break;   // flags: the subsampling, tile_size: restart_mcus

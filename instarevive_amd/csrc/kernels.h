@@ -348,6 +348,50 @@ int ir_clipiqa_plan(const IrClipiqaModel& m, int n, int h, int w, IrClipiqaPlan*
 int ir_launch_clipiqa(const IrClipiqaModel& m, const uint8_t* img, int rows, long pitch, int n, int h, int w, double* scores, float* feat, void* ws,
                       hipStream_t s);
 
+// ---- MUSIQ of uint8 images (musiq.hip)
+// ir_musiq_layout_host (host only): the scales of an h x w image - scale s is the image resized so that its longer side is longer[s], or the image
+// itself where longer[s] is 0 - with their 'SAME' patch grids, the first patch of each scale in the image's patch list, and the factors
+// (float)grid / count of the hashed spatial index. -1 when a resized side rounds to 0 or the token count leaves an int.
+#define IR_MUSIQ_MAX_SCALES 4
+#define IR_MUSIQ_MAX_LAYERS 64
+struct IrMusiqScale {
+    int rh, rw, count_h, count_w, pad_top, pad_left, first, resized;
+    float fh, fw;
+};
+struct IrMusiqLayout {
+    int n_scales, patches, T;   // T = 1 + patches
+    IrMusiqScale s[IR_MUSIQ_MAX_SCALES];
+};
+int ir_musiq_layout_host(int h, int w, int patch, int grid, int n_scales, const int* longer, IrMusiqLayout* lay);
+void ir_musiq_input_table_host(float* tab256);
+// The bound model: the standardised conv weights as [K padded to 32][cout] with K in (ky, kx, c) order, every linear as [in][out] (q | k | v side by
+// side), the GroupNorm / LayerNorm vectors and the embeddings as they were uploaded.
+struct IrMusiqBlock {
+    const float *ln1g, *ln1b, *qkvw, *qkvb, *ow, *ob, *ln2g, *ln2b, *f1w, *f1b, *f2w, *f2b;
+};
+struct IrMusiqModel {
+    bool ok = false;
+    int patch = 0, hidden = 0, mlp = 0, heads = 0, layers = 0, grid = 0, n_scales = 0, longer[IR_MUSIQ_MAX_SCALES] = {};
+    const float* tab = nullptr;   // [256] input table
+    const float *stem_w = nullptr, *stem_g = nullptr, *stem_b = nullptr;
+    const float *cw[4] = {}, *cg[4] = {}, *cb[4] = {};   // the bottleneck's conv1, conv2, conv3 and its projection branch
+    const float *emb_w = nullptr, *emb_b = nullptr, *pos = nullptr, *semb = nullptr, *cls = nullptr;
+    const float *fin_g = nullptr, *fin_b = nullptr, *head_w = nullptr, *head_b = nullptr;
+    IrMusiqBlock blk[IR_MUSIQ_MAX_LAYERS] = {};
+};
+// ir_musiq_plan: the workspace of a call, byte offsets. Per patch of the n images: two slots of 16384 floats (A: the stem conv's map, later the
+// bottleneck's output; B: the patch's input pixels, later the projection branch) and three of 4096 (the pooled map, conv1's and conv2's output);
+// behind them the patch embeddings. The transformer's arrays (x, the LayerNorm output, q | k | v, the attention output, the MLP's hidden rows and
+// the scores of zc (image, head) pairs at a time, rows padded to Tpad) lie over the patch slots, which are dead by then.
+struct IrMusiqPlan {
+    IrMusiqLayout lay;
+    size_t slot[5], emb, x, hn, qkv, o, f, s, total;
+    int zc, Tpad;
+};
+int ir_musiq_plan(const IrMusiqModel& m, int n, int h, int w, IrMusiqPlan* plan);
+int ir_launch_musiq(const IrMusiqModel& m, const uint8_t* img, int rows, long pitch, int n, int h, int w, double* scores, float* feat, void* ws,
+                    hipStream_t s);
+
 // ---- low-quality inputs from ground truth (degrade.hip)
 // One image: blur (K x K fp64 taps in device memory, K odd, at most IR_DEGRADE_MAX_KSIZE: the float halo tile of a 32 x 32 patch must fit in 64 KB
 // of LDS), bilinear to lh x lw, noise (or NULL), the JPEG round trip at q (0: none), bilinear back, bytes (norm: include/instarevive_hip.h's IR_DEGRADE_NORM_*). jpeg: NULL or lh x lw x 3 bytes behind

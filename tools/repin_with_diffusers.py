@@ -30,6 +30,9 @@ random-initialised models of reduced width pin it exactly as the 4 GB checkpoint
 10. OpenCV's side of the degradation chain (dataset/codeformer.py:151-163, utils/degradation.py:744-747) -> tools/degrade_folder.py: cv2.filter2D
     with a 41 x 41 kernel (a DFT path: to 1e-5 absolute, rounding only), cv2.resize INTER_LINEAR on floats down and up (bit-equal) and
     cv2.imencode / imdecode of a float image at three qualities (byte-equal).
+11. pyiqa's MUSIQ (evaluate_img.py's `create_metric('musiq')`, the koniq10k checkpoint) -> tools/evaluate_musiq.py on pyiqa's own weights, read
+    through PYIQA_KEYS: the score of two images to 1e-4 (the score is roughly 0 - 100; pyiqa runs fp32). A mismatch points at one of the three
+    recollections that file names: the key table, standardize() or resize().
  6. ftfy.fix_text (diffusion/model/t5.py:118-124) -> instarevive_amd.captions.fix_text (deterministic steps + the restricted mojibake repair).
 
 The fixture holds inputs, state-dict checksums and the third party's outputs (data, not source); tests/test_oracle_golden.py picks
@@ -267,6 +270,39 @@ def pin_clipiqa(out, bpe=None):
     return ok
 
 
+def pin_musiq(out):
+    """pyiqa's `musiq` against tools/evaluate_musiq.py on the koniq10k weights pyiqa itself loads (its network's state dict)."""
+    import importlib.util
+    import pyiqa
+    spec = importlib.util.spec_from_file_location("evaluate_musiq", os.path.join(ROOT, "tools", "evaluate_musiq.py"))
+    em = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(em)
+    metric = pyiqa.create_metric("musiq", device="cpu")
+    sd = {k: v.detach().float() for k, v in metric.net.state_dict().items()}
+    layers = 0
+    while em.PYIQA_KEYS(layers + 1)[f"layers.{layers}.ln1.weight"] in sd:
+        layers += 1
+    keys = em.PYIQA_KEYS(layers)
+    missing = [theirs for theirs in keys.values() if theirs not in sd]
+    if missing:
+        print(f"  [11] PYIQA_KEYS names {len(missing)} tensors pyiqa's checkpoint does not have, e.g. {missing[:3]}; it has e.g. {sorted(sd)[:5]}")
+        return False
+    model = em.load_model({ours: (sd[theirs].reshape(sd[theirs].shape[-2:]) if ours in ("position_emb", "scale_emb") else sd[theirs].reshape(-1)
+                                  if ours == "cls_token" else sd[theirs]) for ours, theirs in keys.items()})
+    rng = np.random.default_rng(13)
+    yy, xx = np.mgrid[0:224, 0:288].astype(np.float64)
+    base = np.stack([128 + 80 * np.sin(xx / 23) * np.cos(yy / 31), 128 + 70 * np.sin((xx + yy) / 41), 128 + 90 * np.cos(xx / 17 - yy / 29)], -1)
+    ok = True
+    for name, sigma in (("smooth", 2.0), ("noisy", 25.0)):
+        img = np.clip(np.rint(base + rng.normal(0, sigma, base.shape)), 0, 255).astype(np.uint8)
+        ref = float(metric(torch.from_numpy(img).permute(2, 0, 1)[None].float() / 255.0))
+        got = em.musiq(img, model)
+        print(f"  [11] pyiqa MUSIQ ({name}) {ref:.6f} vs evaluate_musiq {got:.6f} (absolute {abs(got - ref):.2e})")
+        out[f"musiq_{name}"], out[f"musiq_{name}_ref"] = img, np.float64(ref)
+        ok = ok and abs(got - ref) <= 1e-4
+    return ok
+
+
 def pin_degrade(out):
     """cv2 against the steps of tools/degrade_folder.py that restate it: the blur (steps 2), the two resizes (3, 6) and the JPEG round trip (5)."""
     import cv2
@@ -324,7 +360,7 @@ def main():
     for name, fn, args in (("diffusers DiT (items 1, 2)", pin_dit, (None,)), ("diffusers VAE (item 3)", pin_vae, (None,)),
                            ("open_clip (item 4)", pin_clip, ()), ("pyiqa (item 5)", pin_iqa, ()), ("ftfy (item 6)", pin_ftfy, ()), ("lpips (item 7)", pin_lpips, ()),
                            ("pyiqa NIQE (item 8)", pin_niqe, ()), ("pyiqa CLIP-IQA (item 9)", pin_clipiqa, (a.clip_bpe,)),
-                           ("OpenCV degradation steps (item 10)", pin_degrade, ())):
+                           ("OpenCV degradation steps (item 10)", pin_degrade, ()), ("pyiqa MUSIQ (item 11)", pin_musiq, ())):
         print(name)
         try:
             verdict[name] = fn(out, *args)
