@@ -62,12 +62,17 @@ def parse_args():
                     "OpenAI's RN50.pt or an .npz). Works with or without --gt and --niqe_params; its column comes last. --image_size must be at least 32")
     ap.add_argument("--musiq_model", default=None, help="score MUSIQ (no reference needed) of both output folders on the GPU (inference.py --musiq_model: an .npz "
                     "in tools/evaluate_musiq.py's names or pyiqa's .pth). Works with or without --gt, --niqe_params and --clipiqa_model; its column comes last")
+    ap.add_argument("--maniqa_model", default=None, help="score MANIQA (no reference needed) of both output folders on the GPU (inference.py --maniqa_model: an .npz "
+                    "in tools/evaluate_maniqa.py's names or pyiqa's .pth). Works with or without --gt and the other scorers; its column comes last. --image_size "
+                    "must be above 224")
+    ap.add_argument("--maniqa_crops", default="uniform", choices=["uniform", "random"], help="inference.py's flag: pyiqa's grid, or draws from --maniqa_seed and the saved file's name")
+    ap.add_argument("--maniqa_seed", type=int, default=None, help="with --maniqa_crops random: the seed (default 231)")
     ap.add_argument("--clip_bpe", default=None, help="with --clipiqa_model: the folder that holds CLIP's BPE table (inference.py --clip_bpe)")
     ap.add_argument("--degrade", nargs="?", const="lq", default=None, metavar="lq|realesrgan|FILE.json", help="--input holds GROUND TRUTH: the centre crops are degraded on "
                     "the GPU (inference.py --degrade: blur, bilinear downsample, noise, JPEG, bilinear resize back; `realesrgan`: the reference's second-order "
                     "validation recipe) and the LQ images restored; needs "
                     "--image_size to be a multiple of 64 of at least 512 (the crop is then the network input as it is). Without --gt the input folder "
-                    "is the ground truth of --lpips_lin / --niqe_params / --clipiqa_model / --musiq_model")
+                    "is the ground truth of --lpips_lin / --niqe_params / --clipiqa_model / --musiq_model / --maniqa_model")
     ap.add_argument("--degrade_seed", type=int, default=231, help="with --degrade: seeds every file's draws together with the crc32 of its input-relative path")
     ap.add_argument("--save_lq", default=None, metavar="DIR", help="with --degrade: write the synthesised LQ crops to DIR")
     ap.add_argument("--jpeg_decoder", default="host", choices=["host", "gpu"], help="inference.py's flag; only `host` here: every input is centre-cropped on the "
@@ -98,7 +103,8 @@ def main():
     niqe_params = cli.load_niqe_params(args)
     clipiqa_model = cli.load_clipiqa_model(args)
     musiq_model = cli.load_musiq_model(args)
-    noref = bool(niqe_params) or clipiqa_model is not None or musiq_model is not None
+    maniqa_model = cli.load_maniqa_model(args)
+    noref = bool(niqe_params) or clipiqa_model is not None or musiq_model is not None or maniqa_model is not None
     recipe = geo = None
     if args.save_lq and not args.degrade:
         raise SystemExit("--save_lq writes the images --degrade synthesises: give --degrade as well")
@@ -137,7 +143,7 @@ def main():
         raise SystemExit("--lpips_alexnet needs --lpips_lin (the lpips linear heads)")
     with_lpips = {"lpips": True} if args.lpips_lin else {}
     with_niqe = {**({"niqe": True} if niqe_params else {}), **({"clipiqa": True} if clipiqa_model else {}), **({"musiq": True} if musiq_model else {}),
-                 **({"paired": bool(args.gt)} if noref else {})}
+                 **({"maniqa": True} if maniqa_model else {}), **({"paired": bool(args.gt)} if noref else {})}
     lookup = None
     if args.gt or noref:
         from instarevive_amd.metrics import GroundTruth, Report
@@ -153,6 +159,9 @@ def main():
         if musiq_model:
             from instarevive_amd import musiq
             musiq.configure(m.model.ctx, musiq_model)
+        if maniqa_model:
+            from instarevive_amd import maniqa
+            maniqa.configure(m.model.ctx, maniqa_model, args.maniqa_crops, args.maniqa_seed)
 
     def read(f):
         crop = center_crop_arr(Image.open(f).convert("RGB"), args.image_size)
@@ -199,14 +208,15 @@ def main():
                              **({"jpeg": whole, "jpeg_quality": args.jpeg_quality, "jpeg_subsampling": args.jpeg_subsampling} if gpu_jpg else {}),
                              gt=cli.in_step(truths) if lookup else None, **with_lpips, **({"niqe": niqe_params} if niqe_params else {}),
                              **({"clipiqa": True} if clipiqa_model else {}), **({"musiq": True} if musiq_model else {}),
+                             **({"maniqa": [[os.path.basename(out_name(args.output, args.input, f, ext_out)) for f in group] for group in batches]} if maniqa_model else {}),
                              **({"resize": cli.in_step(records), "degrade": cli.in_step(dparams), "lq_sink": lq_images.append if args.save_lq else None} if recipe else {}))
-    no_score = {"niqe": 0, "clipiqa": 0, "musiq": 0}
+    no_score = {"niqe": 0, "clipiqa": 0, "musiq": 0, "maniqa": 0}
     for group, out in zip(batches, results):
         preds, stage1 = out[:2]
         if reports:
             for rep, folder, scores in zip(reports, (args.output, cond_dir), out[2]):
                 for f, score in zip(group, scores):
-                    missing = rep.unscored(score)   # NaN: the image has no NIQE, no CLIP-IQA or no MUSIQ
+                    missing = rep.unscored(score)   # NaN: the image has no NIQE, no CLIP-IQA, no MUSIQ or no MANIQA
                     if missing:
                         no_score[missing] += 1
                     else:
@@ -228,7 +238,7 @@ def main():
     if reports:
         for rep, folder in zip(reports, (args.output, cond_dir)):
             lines = rep.write()
-            print(f"[rank {rank}] {' / '.join(f for f, on in (('--gt', args.gt), ('--niqe_params', niqe_params), ('--clipiqa_model', clipiqa_model), ('--musiq_model', musiq_model)) if on)}: scored {len(rep.rows)} files of {folder}"
+            print(f"[rank {rank}] {' / '.join(f for f, on in (('--gt', args.gt), ('--niqe_params', niqe_params), ('--clipiqa_model', clipiqa_model), ('--musiq_model', musiq_model), ('--maniqa_model', maniqa_model)) if on)}: scored {len(rep.rows)} files of {folder}"
                   + (f" against {args.gt}" if args.gt else "") + f" -> {rep.path}")
             for ln in lines:
                 print(ln)
@@ -236,6 +246,8 @@ def main():
             print(f"[rank {rank}] --clipiqa_model: {no_score['clipiqa']} files were not scored (CLIP-IQA needs 32 x 32 pixels)")
         if no_score["musiq"]:
             print(f"[rank {rank}] --musiq_model: {no_score['musiq']} files were not scored (a resized side rounds to 0)")
+        if no_score["maniqa"]:
+            print(f"[rank {rank}] --maniqa_model: {no_score['maniqa']} files were not scored (MANIQA needs a short side above 224 pixels)")
         if no_score["niqe"]:
             print(f"[rank {rank}] --niqe_params: {no_score['niqe']} files were not scored (NIQE needs 96 x 96 blocks and two complete feature rows)")
 

@@ -44,7 +44,10 @@ enum { IR_STAGE_SWINIR = 0, IR_STAGE_VAE_ENCODE = 1, IR_STAGE_DIT = 2, IR_STAGE_
                                     workspace, so n only has to be >= 1; depends on these numbers alone (ctx may be NULL) */,
        IR_STAGE_PNG_RUNS = 20 /* ir_png_encode_runs: n images, h, w = the VALID rectangle vh, vw; depends on the sizes alone (ctx may be NULL) */,
        IR_STAGE_MUSIQ = 21 /* ir_musiq: n images, h, w = the scored rectangle; depends on the sizes and on the shape bound by ir_musiq_configure
-                              (0 for a context that is not configured and for a size ir_musiq refuses) */ };
+                              (0 for a context that is not configured and for a size ir_musiq refuses) */,
+       IR_STAGE_MANIQA = 22 /* ir_maniqa: n images, flags = the crops per image, tile_size = the crops one pass takes (0: one - the least
+                               ir_maniqa accepts; n * crops: everything at once); depends on these and on the shape bound by
+                               ir_maniqa_configure, not on h x w (0 for a context that is not configured) */ };
 /* ir_pipeline flags */
 enum { IR_FLAG_NO_PREPROCESS = 1, IR_FLAG_TILED = 2, IR_FLAG_FIX_WAVELET = 4, IR_FLAG_FIX_ADAIN = 8,
        /* ir_pipeline only, needs ir_dit_control_configure: run the DiT step with the ControlNet-Half branch, condition latent
@@ -528,6 +531,52 @@ int ir_musiq_input_table(float* tab256);
 int ir_musiq_configure(ir_ctx* ctx, int patch, int hidden, int mlp, int heads, int layers, int grid, int n_scales, const int* longer);
 int ir_musiq(ir_ctx* ctx, void* stream, const uint8_t* img, int rows, long pitch, int n, int h, int w, double* scores, float* feat_or_null,
              void* ws, size_t ws_bytes);
+
+/* MANIQA (the no-reference metric `maniqa` of the reference's evaluate_img.py; pyiqa's koniq configuration) on the device;
+ * tools/evaluate_maniqa.py states the definition as a torch model and is the model of this call. The input is x = (v / 255 - 0.5) / 0.5 in
+ * fp32 through a 256-entry table. Of every image `crops` windows of crop x crop pixels are scored, at the origins (y, x) the caller gives:
+ * the device computes a pure function of (image, origins, weights). Each crop runs through a ViT (a patch x patch stride-patch conv read
+ * straight from the bytes, class token, learned positions, vit_layers pre-LN blocks with LayerNorm 1e-6 and the exact GELU), of which the
+ * outputs of the four blocks `taps` are concatenated, without the class token, to a map [4 embed][N]; two transposed-attention blocks
+ * (q, k, v = Linear(N, N) along N, softmax((q k^T) N^-0.5) of C x C, the product stored through the published reinterpretation - element
+ * [c][n] at flat offset n * C + c - plus the input), a 1 x 1 conv to embed and a Swin stage (2 layers of swin_depth blocks, window x window
+ * windows, odd blocks shifted by window / 2 with the -100 mask, relative-position bias, LayerNorm 1e-5, MLP width dim_mlp, each layer
+ * entering as scale * layer(x) + x); the same again at embed -> embed / 2 with MLP width dim_mlp / 2; two heads per patch token
+ * (s = relu(fc2(relu(fc1 t))), w = sigmoid(fc2(relu(fc1 t)))), and score = sum(w s) / (sum(w) + 1e-8) over the patches of ALL crops of the
+ * image. Every contraction is an exact-fp32 chain on the fp32-input MFMA in k order; LayerNorm, softmax, the heads' last linear and the
+ * pooled sum run in fp64 in a fixed order without floating-point atomics: an image gives the same bits on every call, at every position of
+ * a batch and with every workspace size.
+ * ir_maniqa_crops (host only, no context, no device): pyiqa's uniform grid of origins - ceil(sqrt(crops)) positions per axis at the step
+ * (side - crop) / floor(sqrt(crops)), y outer, the first `crops`; -1 for min(h, w) <= crop or crops < 1.
+ * ir_maniqa_configure binds fp32 tensors uploaded with ir_upload under these names (L = 0 .. vit_layers - 1; S = 1, 2; K = 0, 1;
+ * l = 0, 1; B = 0 .. swin_depth - 1; N = (crop / patch)^2; D = embed for S = 1, embed / 2 for S = 2):
+ *   maniqa.vit.patch.{weight [embed][3][patch][patch], bias}, maniqa.vit.cls_token [embed], maniqa.vit.pos_embed [1 + N][embed],
+ *   maniqa.vit.blocks.L.{ln1,ln2}.{weight,bias}, maniqa.vit.blocks.L.attn.qkv.{weight [3 embed][embed], bias},
+ *   maniqa.vit.blocks.L.attn.proj.{weight,bias}, maniqa.vit.blocks.L.mlp.fc1.{weight [vit_mlp][embed], bias}, maniqa.vit.blocks.L.mlp.fc2.*;
+ *   maniqa.tabS.K.{q,k,v}.{weight [N][N], bias}; maniqa.convS.{weight [D][4 embed or embed], bias};
+ *   maniqa.swinS.l.B.{ln1,ln2}.*, maniqa.swinS.l.B.attn.rpb [(2 window - 1)^2][swin_heads], maniqa.swinS.l.B.attn.qkv.* [3 D][D],
+ *   maniqa.swinS.l.B.attn.proj.*, maniqa.swinS.l.B.mlp.fc1.* [dim_mlp or dim_mlp / 2][D], maniqa.swinS.l.B.mlp.fc2.*;
+ *   maniqa.score.fc1.* [embed / 2][embed / 2], maniqa.score.fc2.{weight [1][embed / 2], bias [1]}, maniqa.weight.fc1.*, maniqa.weight.fc2.*.
+ * Supported: crop a multiple of patch x window, window 2 .. 5, embed a multiple of 64, ViT heads of a multiple of 32, vit_mlp a multiple of
+ * 32, 1 .. 32 ViT layers, taps ascending and below vit_layers, 1 .. 4 swin heads dividing embed / 2 into even widths, swin_depth 1 .. 4,
+ * dim_mlp a multiple of 64. The binding holds its own repacked copies. Returns -2 with ir_last_error naming the tensor when one is missing
+ * or has another shape, -1 for an unsupported shape.
+ * ir_maniqa scores the top-left h x w of each of the n images of [n][rows][pitch] bytes (RGB8, addressed as ir_clipiqa addresses them).
+ * origins_yx: DEVICE ints [n][crops][2]; an origin outside 0 .. h - crop / 0 .. w - crop is clamped into that range on the device, since the
+ * device cannot refuse after the fact - the Python layer validates the origins before the upload. scores [n] doubles; feat, when not NULL,
+ * [n][crops][N][embed / 2] floats, the tokens the two heads read. All pointers are device pointers; stream-ordered, no allocation, no host
+ * synchronisation (capturable). ws: 256-byte aligned, at least ir_workspace_bytes(ctx, IR_STAGE_MANIQA, n, 0, 0, crops, 0, 0) bytes; the
+ * crops are processed in passes of as many as ws_bytes holds, and the results do not depend on that. Returns -1 (nothing launched, nothing
+ * written, ir_last_error saying which) for a null pointer, n < 1, crops < 1, h above rows, a pitch below 3 w, min(h, w) <= crop, a short
+ * or misaligned workspace, and -13 for a context without ir_maniqa_configure. */
+int ir_maniqa_input_table(float* tab256);
+int ir_maniqa_crops(int h, int w, int crop, int crops, int* out_yx /* [crops][2] */);
+int ir_maniqa_configure(ir_ctx* ctx, int crop, int patch, int embed, int vit_heads, int vit_mlp, int vit_layers, const int* taps /* [4] */,
+                        int window, int swin_heads, int swin_depth, int dim_mlp, float scale);
+int ir_maniqa(ir_ctx* ctx, void* stream, const uint8_t* img, int rows, long pitch, int n, int h, int w,
+              const int* origins_yx /* device, [n][crops][2] */, int crops,
+              double* scores /* [n] */, float* feat_or_null /* [n][crops][tokens][embed / 2], the tokens the two heads read */,
+              void* ws, size_t ws_bytes);
 
 /* Low-quality inputs from ground truth on the device: the first-order degradation of the reference's dataset/codeformer.py:140-163 and
  * tools/lq.py - a K x K blur, a bilinear downsample, Gaussian noise, a JPEG round trip, a bilinear resize back - without OpenCV and without

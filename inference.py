@@ -127,6 +127,15 @@ def parse_args() -> Namespace:
                         ".npz in that file's names, or pyiqa's .pth state dict. Works with or without --gt, --niqe_params and --clipiqa_model: the column "
                         "`musiq` and the line `musiq: x.xxxxx` come last. Which files are scored follows --gt's rule; files of which a resized side rounds "
                         "to 0 (1 x 1000) are counted as not scored")
+    parser.add_argument("--maniqa_model", type=str, default=None, help="score MANIQA, the no-reference metric `maniqa` of the reference's evaluate_img.py, on the "
+                        "GPU (ir_maniqa; the definition of tools/evaluate_maniqa.py, i.e. pyiqa's koniq configuration, in exact fp32). FILE is an "
+                        ".npz in that file's names, or pyiqa's .pth state dict. Works with or without --gt and the other scorers: the column "
+                        "`maniqa` and the line `maniqa: x.xxxxx` come last. Which files are scored follows --gt's rule; files with a short side of "
+                        "224 or less are counted as not scored. Costs about as much as the network's own step (20 crops through a ViT-B/8)")
+    parser.add_argument("--maniqa_crops", type=str, default="uniform", choices=["uniform", "random"], help="with --maniqa_model: where the 20 crops lie. uniform "
+                        "(default): pyiqa's grid. random: drawn from --maniqa_seed and the saved file's name (as tools/evaluate_maniqa.py draws them for that file), whatever the batch size, worker "
+                        "count or rank")
+    parser.add_argument("--maniqa_seed", type=int, default=None, help="with --maniqa_crops random: the seed (default 231)")
     parser.add_argument("--clip_bpe", type=str, default=None, help="with --clipiqa_model: the folder that holds CLIP's BPE table (bpe_simple_vocab_16e6.txt.gz, or "
                         "vocab.json + merges.txt), from which the ten prompts are tokenised")
     parser.add_argument("--degrade", type=str, nargs="?", const="lq", default=None, metavar="lq|realesrgan|FILE.json", help="--input holds GROUND TRUTH: synthesise every "
@@ -139,7 +148,7 @@ def parse_args() -> Namespace:
                         "bilinear / bicubic resize, Gaussian or Poisson noise and DiffJPEG, a final sinc filter, bicubic back - files of at least 44 pixels "
                         "on the short side; a JSON file with \"chain\": \"realesrgan\" may set that recipe's keys. No OpenCV, no second folder: the LQ image never "
                         "leaves the device. Switches --resize gpu on; not offered with --show_lq, --use_center_crop, --shard_tiles. Without --gt the input "
-                        "folder is the ground truth of --metrics_out / --lpips_lin / --niqe_params / --clipiqa_model / --musiq_model")
+                        "folder is the ground truth of --metrics_out / --lpips_lin / --niqe_params / --clipiqa_model / --musiq_model / --maniqa_model")
     parser.add_argument("--degrade_seed", type=int, default=231, help="with --degrade: a file's parameters are drawn from a generator seeded by this number "
                         "and the crc32 of its input-relative path, whatever the batch size, worker count or rank")
     parser.add_argument("--save_lq", type=str, default=None, metavar="DIR", help="with --degrade: write the synthesised LQ images to DIR/<input-relative path>.png")
@@ -157,7 +166,7 @@ def add_jpeg_flags(parser) -> None:
     seen whether they were given."""
     parser.add_argument("--save_format", type=str, default="png", choices=["png", "jpg"], help="the format of the saved results. png (default): lossless, what the "
                         "reference writes. jpg: baseline JPEG (standard Huffman tables, JFIF, no other metadata), the save path then ends in .jpg - a 2048 x 2048 "
-                        "result takes 1 - 2 MB instead of 8 - 12. Scoring (--gt, --niqe_params, --clipiqa_model, --musiq_model) still reads the device's image, the result "
+                        "result takes 1 - 2 MB instead of 8 - 12. Scoring (--gt, --niqe_params, --clipiqa_model, --musiq_model, --maniqa_model) still reads the device's image, the result "
                         "BEFORE the JPEG loss")
     parser.add_argument("--jpeg_quality", type=int, default=None, metavar="1..100", help="with --save_format jpg: libjpeg's quality (default 95)")
     parser.add_argument("--jpeg_subsampling", type=str, default=None, choices=["420", "444"], help="with --save_format jpg: chroma subsampling, 420 (default) or 444")
@@ -314,6 +323,26 @@ def load_musiq_model(args: Namespace):
         return musiq.load_model(args.musiq_model)
     except Exception as e:   # MusiqError is a ValueError; a file torch cannot unpickle raises its own kinds
         raise SystemExit(f"--musiq_model {args.musiq_model}: {e}")
+
+
+def load_maniqa_model(args: Namespace):
+    """--maniqa_model: the MANIQA model, read before any other model is touched; a file that is missing or holds anything else ends the run.
+    --maniqa_crops random without --maniqa_seed takes the stated default seed."""
+    if not getattr(args, "maniqa_model", None):
+        if getattr(args, "maniqa_seed", None) is not None or getattr(args, "maniqa_crops", "uniform") != "uniform":
+            raise SystemExit("--maniqa_crops / --maniqa_seed need --maniqa_model")
+        return None
+    from instarevive_amd import maniqa
+    if args.maniqa_crops != "random" and args.maniqa_seed is not None:
+        raise SystemExit("--maniqa_seed seeds --maniqa_crops random: give that as well")
+    if args.maniqa_crops == "random" and args.maniqa_seed is None:
+        args.maniqa_seed = maniqa.DEFAULT_SEED
+    if not os.path.isfile(args.maniqa_model):
+        raise SystemExit(f"--maniqa_model {args.maniqa_model}: no such file")
+    try:
+        return maniqa.load_model(args.maniqa_model)
+    except Exception as e:   # ManiqaError is a ValueError; a file torch cannot unpickle raises its own kinds
+        raise SystemExit(f"--maniqa_model {args.maniqa_model}: {e}")
 
 
 def check_device(device: str) -> str:
@@ -576,7 +605,8 @@ def main() -> None:
     niqe_params = load_niqe_params(args)
     clipiqa_model = load_clipiqa_model(args)
     musiq_model = load_musiq_model(args)
-    noref = bool(niqe_params) or clipiqa_model is not None or musiq_model is not None
+    maniqa_model = load_maniqa_model(args)
+    noref = bool(niqe_params) or clipiqa_model is not None or musiq_model is not None or maniqa_model is not None
     if args.save_lq and not args.degrade:
         raise SystemExit("--save_lq writes the images --degrade synthesises: give --degrade as well")
     if args.degrade:
@@ -622,12 +652,12 @@ def main() -> None:
     if args.gt or noref:
         from instarevive_amd.metrics import GroundTruth, Report
         if args.shard_tiles:
-            raise SystemExit("--gt / --niqe_params / --clipiqa_model / --musiq_model are not offered together with --shard_tiles (the assembled frame of the tile-sharded path is not scored on the device)")
+            raise SystemExit("--gt / --niqe_params / --clipiqa_model / --musiq_model are not offered together with --shard_tiles, nor is --maniqa_model (the assembled frame of the tile-sharded path is not scored on the device)")
         if args.gt:
             args.gt_lookup = GroundTruth(args.gt, args.input)
         report = Report(args.metrics_out or os.path.join(args.output, "metrics.csv" if world == 1 else f"metrics.rank{rank}.csv"),
                         **({"lpips": True} if args.lpips_lin else {}), **({"niqe": True} if niqe_params else {}), **({"clipiqa": True} if clipiqa_model else {}),
-                        **({"musiq": True} if musiq_model else {}), **({"paired": bool(args.gt)} if noref else {}))
+                        **({"musiq": True} if musiq_model else {}), **({"maniqa": True} if maniqa_model else {}), **({"paired": bool(args.gt)} if noref else {}))
         if args.lpips_lin:
             from instarevive_amd import lpips
             lpips.configure(m.model.ctx, args.lpips_lin, args.lpips_alexnet)
@@ -637,6 +667,9 @@ def main() -> None:
         if musiq_model:
             from instarevive_amd import musiq
             musiq.configure(m.model.ctx, musiq_model)
+        if maniqa_model:
+            from instarevive_amd import maniqa
+            maniqa.configure(m.model.ctx, maniqa_model, args.maniqa_crops, args.maniqa_seed)
     local_world = int(os.environ.get("LOCAL_WORLD_SIZE", world))
     if os.environ.get("IR_SWITCH_INTERVAL"):   # experiment knob: how long a worker thread may keep the GIL while the thread that feeds the GPU waits for it
         import sys
@@ -701,7 +734,8 @@ def main() -> None:
     rects = deque()   # --png_encoder gpu, per batch drawn by process_stream: its rectangles, or None for a batch of the host encoder
     records = deque()   # --resize gpu, per batch: the decoded files and their geometry
     truths = deque()   # --gt, per batch: the ground-truth images, or None for a batch that is not scored
-    sizes = deque()    # --niqe_params / --clipiqa_model / --musiq_model, per batch: the saved sizes, or None for a batch that is not scored
+    names = deque()    # --maniqa_model, per batch: the saved files' names, which key random crops
+    sizes = deque()    # --niqe_params / --clipiqa_model / --musiq_model / --maniqa_model, per batch: the saved sizes, or None for a batch that is not scored
     dparams = deque()  # --degrade, per batch: the files' degrade.Params
     lq_images = deque()   # --save_lq, per batch: the LQ images process_stream hands over right before the batch's results
 
@@ -713,6 +747,8 @@ def main() -> None:
             if noref:
                 rr = [png_rect(j, args) for j in group]
                 sizes.append(rr if all(rr) else None)
+                if maniqa_model:
+                    names.append([os.path.basename(j.save_path) for j in group])
             if on_gpu:
                 rr = [png_rect(j, args) for j in group]
                 rects.append(rr if all(rr) else None)
@@ -725,16 +761,17 @@ def main() -> None:
             yield (imgs, *caps.batch([j.src for j in group])) if caps else imgs
 
     first = None    # (time, files) when the first result left the GPU: what follows is the steady state (no library / workspace warm-up in it)
-    unscored = 0    # --gt / --niqe_params / --clipiqa_model / --musiq_model: files whose saved image is not the device's image
+    unscored = 0    # --gt / --niqe_params / --clipiqa_model / --musiq_model / --maniqa_model: files whose saved image is not the device's image
     # files below 96 pixels on an edge or without two complete feature rows; files below 32 pixels on an edge; files of which a resized side rounds to 0
-    no_score = {"niqe": 0, "clipiqa": 0, "musiq": 0}
+    no_score = {"niqe": 0, "clipiqa": 0, "musiq": 0, "maniqa": 0}   # maniqa: files with a short side of 224 or less
     for out in process_stream(m.model, feed(), tiled=args.tiled, return_stage1=args.show_lq and not args.disable_preprocess_model,
                               fp8=args.fp8 != "off", png=in_step(rects) if gpu_png else None, png_wrap=False, png_runs=args.png_runs,
                               **({"jpeg": in_step(rects), "jpeg_quality": args.jpeg_quality, "jpeg_subsampling": args.jpeg_subsampling} if gpu_jpg else {}),
                               resize=in_step(records) if args.resize_on_gpu else None, gt=in_step(truths) if args.gt else None,
                               **({"lpips": True} if report and report.lpips else {}),
                               **({"niqe": niqe_params} if niqe_params else {}), **({"clipiqa": True} if clipiqa_model else {}),
-                              **({"musiq": True} if musiq_model else {}), **({"niqe_rects": in_step(sizes)} if noref else {}),
+                              **({"musiq": True} if musiq_model else {}), **({"maniqa": in_step(names)} if maniqa_model else {}),
+                              **({"niqe_rects": in_step(sizes)} if noref else {}),
                               **({"degrade": in_step(dparams), "lq_sink": lq_images.append if args.save_lq else None} if args.degrade else {}), **common):
         preds, stage1 = out[:2]
         group = todo.pop(0)
@@ -745,7 +782,7 @@ def main() -> None:
         if report:
             if len(out) > 2:
                 for job, score in zip(group, out[2][0]):
-                    missing = report.unscored(score)   # NaN: the image has no NIQE, no CLIP-IQA or no MUSIQ
+                    missing = report.unscored(score)   # NaN: the image has no NIQE, no CLIP-IQA, no MUSIQ or no MANIQA
                     if missing:
                         no_score[missing] += 1
                     else:
@@ -772,7 +809,7 @@ def main() -> None:
               f"encoder (their saved image is not the device's image; the same bytes)")
     if report:
         lines = report.write()
-        what = " / ".join(f for f, on in (("--gt", args.gt), ("--niqe_params", niqe_params), ("--clipiqa_model", clipiqa_model), ("--musiq_model", musiq_model)) if on)
+        what = " / ".join(f for f, on in (("--gt", args.gt), ("--niqe_params", niqe_params), ("--clipiqa_model", clipiqa_model), ("--musiq_model", musiq_model), ("--maniqa_model", maniqa_model)) if on)
         print(f"[rank {rank}] {what}: scored {len(report.rows)} files" + (f" against {args.gt}" if args.gt else "") + f" -> {report.path}")
         for ln in lines:
             print(ln)
@@ -782,6 +819,8 @@ def main() -> None:
             print(f"[rank {rank}] --clipiqa_model: {no_score['clipiqa']} of {pools.written} files were not scored (CLIP-IQA needs 32 x 32 pixels)")
         if no_score["musiq"]:
             print(f"[rank {rank}] --musiq_model: {no_score['musiq']} of {pools.written} files were not scored (a resized side rounds to 0)")
+        if no_score["maniqa"]:
+            print(f"[rank {rank}] --maniqa_model: {no_score['maniqa']} of {pools.written} files were not scored (MANIQA needs a short side above 224 pixels)")
         if unscored:
             print(f"[rank {rank}] {what}: {unscored} of {pools.written} files were not scored (their saved image is not the device's image: an input the host "
                   f"enlarged, or --show_lq) - use --resize gpu")

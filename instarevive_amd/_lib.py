@@ -28,6 +28,7 @@ SYMBOLS = [
     "ir_png_bound", "ir_png_encode", "ir_png_encode_runs", "ir_jpeg_bound", "ir_jpeg_encode", "ir_jpeg_decode", "ir_resample_plan_bytes", "ir_resample_plan", "ir_resample_u8", "ir_metrics_y",
     "ir_lpips_scale_table", "ir_lpips_configure", "ir_lpips", "ir_niqe_window", "ir_niqe_stats",
     "ir_clipiqa_scale_table", "ir_clipiqa_configure", "ir_clipiqa", "ir_musiq_layout", "ir_musiq_input_table", "ir_musiq_configure", "ir_musiq",
+    "ir_maniqa_input_table", "ir_maniqa_crops", "ir_maniqa_configure", "ir_maniqa",
     "ir_degrade_qtables", "ir_degrade", "ir_degrade_chain",
     "ir_op_linear_ex", "ir_op_conv_ex", "ir_op_igemm_route", "ir_op_igemm_route_range",
 ]
@@ -42,6 +43,7 @@ STAGE_NIQE = 14
 STAGE_CLIPIQA = 15
 STAGE_DEGRADE = 16
 STAGE_MUSIQ = 21
+STAGE_MANIQA = 22
 DEGRADE_NORM_NONE, DEGRADE_NORM_MAX = 0, 1
 DEGRADE_MAX_KSIZE, DEGRADE_MIN_LOW = 41, 8
 STAGE_DEGRADE_CHAIN = 17
@@ -55,6 +57,7 @@ CHAIN_MAX_OPS, CHAIN_MAX_KSIZE, CHAIN_MAX_SIDE = 16, 21, 8192
 LPIPS_NOT_CONFIGURED = -12   # ir_lpips before ir_lpips_configure
 CLIPIQA_NOT_CONFIGURED = -13   # ir_clipiqa before ir_clipiqa_configure
 MUSIQ_NOT_CONFIGURED = -13     # ir_musiq before ir_musiq_configure
+MANIQA_NOT_CONFIGURED = -13    # ir_maniqa before ir_maniqa_configure
 MUSIQ_LONGER = (224, 384, 0)   # the longer side of each scale; 0: the image at its own size
 FLAG_NO_PREPROCESS, FLAG_TILED, FLAG_FIX_WAVELET, FLAG_FIX_ADAIN, FLAG_CONTROL_LQ, FLAG_GRAPH, FLAG_FP8 = 1, 2, 4, 8, 16, 32, 64
 # ir_set_fp8_mask (include/instarevive_hip.h): QUALIFIED = the set qualified against the fp32 oracle on flat-softmax weights (>= 46.3 dB at 2048 x
@@ -256,6 +259,10 @@ def load_library():
     lib.ir_musiq_input_table.argtypes = [vp]
     lib.ir_musiq_configure.argtypes = [vp, i, i, i, i, i, i, i, C.POINTER(C.c_int)]
     lib.ir_musiq.argtypes = [vp, vp, vp, i, C.c_long, i, i, i, vp, vp, vp, sz]
+    lib.ir_maniqa_input_table.argtypes = [vp]
+    lib.ir_maniqa_crops.argtypes = [i, i, i, i, vp]
+    lib.ir_maniqa_configure.argtypes = [vp, i, i, i, i, i, i, C.POINTER(C.c_int), i, i, i, i, C.c_float]
+    lib.ir_maniqa.argtypes = [vp, vp, vp, i, C.c_long, i, i, i, vp, i, vp, vp, vp, sz]
     lib.ir_degrade_qtables.argtypes = [i, vp, vp]
     lib.ir_degrade.argtypes = [vp, vp, vp, i, C.c_long, i, i, i, C.POINTER(DegradeParams), vp, vp, vp, sz]
     lib.ir_degrade_chain.argtypes = [vp, vp, vp, i, C.c_long, i, i, i, C.POINTER(Chain), vp, vp, vp, sz]

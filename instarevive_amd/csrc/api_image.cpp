@@ -1,4 +1,4 @@
-// The image tools of the C ABI: PNG and JPEG encoding, Pillow's resampling, PSNR-Y / SSIM-Y, LPIPS, CLIP-IQA, MUSIQ, NIQE and the two degradation paths. Each entry
+// The image tools of the C ABI: PNG and JPEG encoding, Pillow's resampling, PSNR-Y / SSIM-Y, LPIPS, CLIP-IQA, MUSIQ, MANIQA, NIQE and the two degradation paths. Each entry
 // point checks its arguments and launches the kernels of its own .hip file; none of them runs a model stage, takes the workspace arena or is
 // profiled, so nothing here knows api.cpp's Run. Host code only, except for the tables the kernels read, which are computed here once.
 #include <math.h>
@@ -676,6 +676,151 @@ int ir_musiq(ir_ctx* c, void* stream, const uint8_t* img, int rows, long pitch, 
     return 0;
 }
 
+// ---------------------------------------------------------------- MANIQA (maniqa.hip)
+int ir_maniqa_input_table(float* tab) {
+    if (!tab) return -1;
+    ir_maniqa_input_table_host(tab);
+    return 0;
+}
+
+int ir_maniqa_crops(int h, int w, int crop, int crops, int* out_yx) { return ir_maniqa_crops_host(h, w, crop, crops, out_yx); }
+
+int ir_maniqa_configure(ir_ctx* c, int crop, int patch, int embed, int vit_heads, int vit_mlp, int vit_layers, const int* taps, int window, int swin_heads,
+                        int swin_depth, int dim_mlp, float scale) {
+    if (!c || !taps) return fail(c, -1, "ir_maniqa_configure: null argument");
+    bool bad = patch < 1 || patch > 64 || window < 2 || window > 5 || crop < 1 || crop > 4096 || crop % (patch * window) || embed < 64 || embed % 64 || embed > 4096 ||
+               vit_heads < 1 || embed % vit_heads || (embed / vit_heads) % 32 || vit_mlp < 32 || vit_mlp % 32 || vit_layers < 1 || vit_layers > IR_MANIQA_MAX_LAYERS ||
+               swin_heads < 1 || swin_heads > 4 || (embed / 2) % swin_heads || (embed / 2 / swin_heads) % 2 || swin_depth < 1 || swin_depth > IR_MANIQA_MAX_DEPTH ||
+               dim_mlp < 64 || dim_mlp % 64 || !(scale == scale);
+    for (int k = 0; k < 4 && !bad; ++k) bad = taps[k] < 0 || taps[k] >= vit_layers || (k && taps[k] <= taps[k - 1]);
+    if (bad)
+        return fail(c, -1, "ir_maniqa_configure: unsupported model (crop %d must be a multiple of patch %d x window %d (2 .. 5), embed %d of 64 with %d heads of a multiple of 32, "
+                    "vit_mlp %d of 32, layers %d within 1 .. %d, taps ascending below them, 1 .. 4 swin heads (%d) dividing embed / 2, depth %d within 1 .. %d, dim_mlp %d of 64)",
+                    crop, patch, window, embed, vit_heads, vit_mlp, vit_layers, IR_MANIQA_MAX_LAYERS, swin_heads, swin_depth, IR_MANIQA_MAX_DEPTH, dim_mlp);
+    HIPOK(c, hipSetDevice(c->device));
+    c->maniqa.ok = false;
+    auto m = std::make_unique<IrManiqaModel>();
+    m->crop = crop; m->patch = patch; m->embed = embed; m->vit_heads = vit_heads; m->vit_mlp = vit_mlp; m->vit_layers = vit_layers; m->window = window;
+    m->swin_heads = swin_heads; m->swin_depth = swin_depth; m->dim_mlp = dim_mlp; m->scale = scale;
+    for (int k = 0; k < 4; ++k) m->taps[k] = taps[k];
+    const int G = crop / patch, N = G * G, E = embed, Eh = embed / 2, PK = 3 * patch * patch, RP = (2 * window - 1) * (2 * window - 1);
+    struct Vec { std::string name; size_t floats; const float** dst; };   // tensors that are copied as they are
+    struct Lin { std::string name; int rows, cols; const float** dst; };  // [rows][cols] -> [cols][rows]
+    std::vector<Vec> vecs;
+    std::vector<Lin> lins;
+    auto block = [&](const std::string& b, int D, int mlp, IrManiqaBlock& k, bool rpb) {
+        vecs.push_back({b + "ln1.weight", (size_t)D, &k.ln1g});
+        vecs.push_back({b + "ln1.bias", (size_t)D, &k.ln1b});
+        vecs.push_back({b + "ln2.weight", (size_t)D, &k.ln2g});
+        vecs.push_back({b + "ln2.bias", (size_t)D, &k.ln2b});
+        vecs.push_back({b + "attn.qkv.bias", (size_t)3 * D, &k.qkvb});
+        vecs.push_back({b + "attn.proj.bias", (size_t)D, &k.pb});
+        vecs.push_back({b + "mlp.fc1.bias", (size_t)mlp, &k.f1b});
+        vecs.push_back({b + "mlp.fc2.bias", (size_t)D, &k.f2b});
+        if (rpb) vecs.push_back({b + "attn.rpb", (size_t)RP * swin_heads, &k.rpb});
+        lins.push_back({b + "attn.qkv.weight", 3 * D, D, &k.qkvw});
+        lins.push_back({b + "attn.proj.weight", D, D, &k.pw});
+        lins.push_back({b + "mlp.fc1.weight", mlp, D, &k.f1w});
+        lins.push_back({b + "mlp.fc2.weight", D, mlp, &k.f2w});
+    };
+    vecs.push_back({"maniqa.vit.patch.bias", (size_t)E, &m->patch_b});
+    vecs.push_back({"maniqa.vit.cls_token", (size_t)E, &m->cls});
+    vecs.push_back({"maniqa.vit.pos_embed", (size_t)(N + 1) * E, &m->pos});
+    lins.push_back({"maniqa.vit.patch.weight", E, PK, &m->patch_w});
+    for (int l = 0; l < vit_layers; ++l) block(fmt("maniqa.vit.blocks.%d.", l), E, vit_mlp, m->vit[l], false);
+    for (int s = 0; s < 2; ++s) {
+        const int cin = s == 0 ? 4 * E : E, D = s == 0 ? E : Eh;
+        vecs.push_back({fmt("maniqa.conv%d.bias", s + 1), (size_t)D, &m->convb[s]});
+        lins.push_back({fmt("maniqa.conv%d.weight", s + 1), D, cin, &m->convw[s]});
+        for (int l = 0; l < IR_MANIQA_SWIN_LAYERS; ++l)
+            for (int k = 0; k < swin_depth; ++k) block(fmt("maniqa.swin%d.%d.%d.", s + 1, l, k), D, s == 0 ? dim_mlp : dim_mlp / 2, m->swin[s][l][k], true);
+    }
+    auto tensor = [&](const std::string& name, size_t floats) { return exact_f32(c, "ir_maniqa_configure", "the configured model's", name, floats); };
+    static const char* const qkv[3] = {"q", "k", "v"};
+    static const char* const hn[2] = {"score", "weight"};
+    // every tensor is looked up before anything is replaced
+    for (const Vec& v : vecs)
+        if (!tensor(v.name, v.floats)) return -2;
+    for (const Lin& l : lins)
+        if (!tensor(l.name, (size_t)l.rows * l.cols)) return -2;
+    for (int s = 0; s < 2; ++s)
+        for (int t = 0; t < 2; ++t)
+            for (const char* a : qkv)
+                if (!tensor(fmt("maniqa.tab%d.%d.%s.weight", s + 1, t, a), (size_t)N * N) || !tensor(fmt("maniqa.tab%d.%d.%s.bias", s + 1, t, a), N)) return -2;
+    for (const char* a : hn)
+        if (!tensor(fmt("maniqa.%s.fc1.weight", a), (size_t)Eh * Eh) || !tensor(fmt("maniqa.%s.fc1.bias", a), Eh) || !tensor(fmt("maniqa.%s.fc2.weight", a), Eh) ||
+            !tensor(fmt("maniqa.%s.fc2.bias", a), 1))
+            return -2;
+
+    std::vector<void*>& own = c->own[OWN_MANIQA];
+    release_list(own);
+    HIPOK(c, hipDeviceSynchronize());
+    float tab[256];
+    ir_maniqa_input_table_host(tab);
+    if (int e = own_copy(c, own, tab, sizeof tab, hipMemcpyHostToDevice, &m->tab)) return e;
+    std::vector<float> t;
+    for (const Vec& v : vecs)
+        if (int e = own_copy(c, own, tensor(v.name, v.floats), v.floats * 4, hipMemcpyDeviceToDevice, v.dst)) return e;
+    for (const Lin& l : lins) {
+        t.assign((size_t)l.rows * l.cols, 0.f);
+        if (int e = transposed_into(c, tensor(l.name, (size_t)l.rows * l.cols), l.rows, l.cols, t, l.rows, 0)) return e;
+        if (int e = own_copy(c, own, t.data(), t.size() * 4, hipMemcpyHostToDevice, l.dst)) return e;
+    }
+    // side by side: q | k | v of a TAB, fc1 of the two heads - one GEMM each, the same chain per output
+    auto side_by_side = [&](const std::string& pre, const char* const* names, int count, const std::string& post, int rows, int cols, const float** w, const float** b) {
+        t.assign((size_t)cols * count * rows, 0.f);
+        std::vector<float> bias((size_t)count * rows);
+        for (int k = 0; k < count; ++k) {
+            const std::string base = pre + names[k] + post;
+            if (int e = transposed_into(c, tensor(base + ".weight", (size_t)rows * cols), rows, cols, t, count * rows, k * rows)) return e;
+            HIPOK(c, hipMemcpy(bias.data() + (size_t)k * rows, tensor(base + ".bias", rows), (size_t)rows * 4, hipMemcpyDeviceToHost));
+        }
+        if (int e = own_copy(c, own, t.data(), t.size() * 4, hipMemcpyHostToDevice, w)) return e;
+        return own_copy(c, own, bias.data(), bias.size() * 4, hipMemcpyHostToDevice, b);
+    };
+    for (int s = 0; s < 2; ++s)
+        for (int k = 0; k < 2; ++k)
+            if (int e = side_by_side(fmt("maniqa.tab%d.%d.", s + 1, k), qkv, 3, "", N, N, &m->tabw[s][k], &m->tabb[s][k])) return e;
+    if (int e = side_by_side("maniqa.", hn, 2, ".fc1", Eh, Eh, &m->head_w1, &m->head_b1)) return e;
+    std::vector<float> w2((size_t)2 * Eh), b2(2);
+    for (int k = 0; k < 2; ++k) {
+        HIPOK(c, hipMemcpy(w2.data() + (size_t)k * Eh, tensor(fmt("maniqa.%s.fc2.weight", hn[k]), Eh), (size_t)Eh * 4, hipMemcpyDeviceToHost));
+        HIPOK(c, hipMemcpy(&b2[k], tensor(fmt("maniqa.%s.fc2.bias", hn[k]), 1), 4, hipMemcpyDeviceToHost));
+    }
+    if (int e = own_copy(c, own, w2.data(), w2.size() * 4, hipMemcpyHostToDevice, &m->head_w2)) return e;
+    if (int e = own_copy(c, own, b2.data(), b2.size() * 4, hipMemcpyHostToDevice, &m->head_b2)) return e;
+    m->ok = true;
+    c->maniqa = *m;
+    ++c->generation;
+    return 0;
+}
+
+int ir_maniqa(ir_ctx* c, void* stream, const uint8_t* img, int rows, long pitch, int n, int h, int w, const int* origins_yx, int crops, double* scores,
+              float* feat, void* ws, size_t ws_bytes) {
+    if (!c || !img || !scores || !ws || !origins_yx) return fail(c, -1, "ir_maniqa: null argument");
+    if (crops < 1 || crops > IR_MANIQA_MAX_CROPS) return fail(c, -1, "ir_maniqa: %d crops (1 .. %d)", crops, IR_MANIQA_MAX_CROPS);
+    if (int e = check_rect(c, "ir_maniqa", nullptr, n, h, w, 1, {{rows, pitch}})) return e;
+    if (!c->maniqa.ok) return fail(c, -13, "ir_maniqa: MANIQA not configured (ir_maniqa_configure)");
+    if (std::min(h, w) <= c->maniqa.crop) return fail(c, -1, "ir_maniqa: a %d x %d image has no %d x %d crops (the short side must be above it)", h, w, c->maniqa.crop, c->maniqa.crop);
+    IrManiqaPlan pl;
+    if (ir_maniqa_plan(c->maniqa, n, crops, 1, &pl)) return fail(c, -1, "ir_maniqa: n %d with %d crops is more than one call takes (4096 images)", n, crops);
+    if (int e = check_ws(c, "ir_maniqa", ws, ws_bytes, pl.total, 256)) return e;
+    if ((reinterpret_cast<uintptr_t>(scores) & 7) || (reinterpret_cast<uintptr_t>(feat) & 3) || (reinterpret_cast<uintptr_t>(origins_yx) & 3))
+        return fail(c, -1, "ir_maniqa: scores / feat / origins not aligned");
+    // as many crops per pass as the workspace holds: the plan's size grows with the pass, so the largest that fits is found by bisection
+    int lo = 1, hi = (int)std::min<long>((long)n * crops, 32768);
+    while (lo < hi) {
+        const int mid = (lo + hi + 1) / 2;
+        IrManiqaPlan q;
+        if (!ir_maniqa_plan(c->maniqa, n, crops, mid, &q) && q.total <= ws_bytes) lo = mid;
+        else hi = mid - 1;
+    }
+    if (ir_maniqa_plan(c->maniqa, n, crops, lo, &pl) || pl.total > ws_bytes) return fail(c, -1, "ir_maniqa: no plan for %d crops per pass", lo);
+    use_ctx(c);
+    if (ir_launch_maniqa(c->maniqa, img, rows, pitch, n, h, w, origins_yx, crops, scores, feat, ws, pl, (hipStream_t)stream)) return fail(c, -100, "ir_maniqa: launch failed");
+    return 0;
+}
+
 // ---------------------------------------------------------------- NIQE's block statistics (niqe.hip)
 // the half-size fp64 luma plane of every image's scored rectangle
 static size_t niqe_workspace(int n, int h, int w) {
@@ -791,11 +936,12 @@ int ir_host::image_init(ir_ctx* c) {
     return upload(tab, sizeof tab, &c->niqe_tab);
 }
 
-// Sizes alone decide every answer except CLIP-IQA's and MUSIQ's, which also take the configured model's shape: no context is needed for the others.
+// Sizes alone decide every answer except CLIP-IQA's, MUSIQ's and MANIQA's, which also take the configured model's shape: no context is needed for the others.
 bool ir_host::image_workspace(ir_ctx* c, int stage, int n, int h, int w, int flags, int tile_size, size_t* bytes) {
     const bool some = n >= 1 && h >= 1 && w >= 1;
     IrClipiqaPlan cp;
     IrMusiqPlan mp;
+    IrManiqaPlan qp;
     IrLpipsPlan lp;
     IrJpegLayout jl;
     *bytes = 0;
@@ -805,6 +951,9 @@ bool ir_host::image_workspace(ir_ctx* c, int stage, int n, int h, int w, int fla
         case IR_STAGE_NIQE: if (n >= 1 && h >= IR_NIQE_BLOCK && w >= IR_NIQE_BLOCK) *bytes = niqe_workspace(n, h, w); break;
         case IR_STAGE_CLIPIQA: if (c && c->clipiqa.ok && !ir_clipiqa_plan(c->clipiqa, n, h, w, &cp)) *bytes = cp.total; break;
         case IR_STAGE_MUSIQ: if (c && c->musiq.ok && !ir_musiq_plan(c->musiq, n, h, w, &mp)) *bytes = mp.total; break;
+        case IR_STAGE_MANIQA:   // flags: the crops per image, tile_size: the crops per pass (0: one, the least a call takes); h and w do not matter
+            if (c && c->maniqa.ok && !ir_maniqa_plan(c->maniqa, n, flags, std::max(tile_size, 1), &qp)) *bytes = qp.total;
+            break;
         case IR_STAGE_LPIPS: if (!ir_lpips_plan(n, h, w, &lp)) *bytes = lp.total; break;
         case IR_STAGE_METRICS: if (some) *bytes = metrics_workspace(n, h, w); break;
         case IR_STAGE_JPEG: if (ir_jpeg_layout(n, h, w, flags, tile_size, &jl)) *bytes = jl.total; break;   // flags: the subsampling, tile_size: restart_mcus

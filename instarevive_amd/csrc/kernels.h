@@ -392,6 +392,44 @@ int ir_musiq_plan(const IrMusiqModel& m, int n, int h, int w, IrMusiqPlan* plan)
 int ir_launch_musiq(const IrMusiqModel& m, const uint8_t* img, int rows, long pitch, int n, int h, int w, double* scores, float* feat, void* ws,
                     hipStream_t s);
 
+// ---- MANIQA of uint8 images (maniqa.hip)
+#define IR_MANIQA_MAX_LAYERS 32
+#define IR_MANIQA_MAX_DEPTH 4
+#define IR_MANIQA_SWIN_LAYERS 2
+#define IR_MANIQA_MAX_CROPS 1024
+void ir_maniqa_input_table_host(float* tab256);
+// host only: the uniform grid of crop origins (y, x) - step (side - crop) / floor(sqrt(crops)) per axis, ceil(sqrt(crops)) positions per axis, y
+// outer, the first `crops` of them. -1 for min(h, w) <= crop, crops outside 1 .. IR_MANIQA_MAX_CROPS.
+int ir_maniqa_crops_host(int h, int w, int crop, int crops, int* out_yx);
+// The bound model: every linear as [in][out] (q | k | v as they are stored, side by side), the patch conv as [(c, ky, kx)][embed], the norm
+// vectors, embeddings and relative-position tables as they were uploaded. A block of the ViT has no rpb.
+struct IrManiqaBlock {
+    const float *ln1g, *ln1b, *qkvw, *qkvb, *pw, *pb, *ln2g, *ln2b, *f1w, *f1b, *f2w, *f2b, *rpb;
+};
+struct IrManiqaModel {
+    bool ok = false;
+    int crop = 0, patch = 0, embed = 0, vit_heads = 0, vit_mlp = 0, vit_layers = 0, taps[4] = {}, window = 0, swin_heads = 0, swin_depth = 0, dim_mlp = 0;
+    float scale = 0.f;
+    const float* tab = nullptr;   // [256] input table
+    const float *patch_w = nullptr, *patch_b = nullptr, *cls = nullptr, *pos = nullptr;
+    IrManiqaBlock vit[IR_MANIQA_MAX_LAYERS] = {};
+    const float *tabw[2][2] = {}, *tabb[2][2] = {};   // [stage][k]: [N][3 N] and [3 N]
+    const float *convw[2] = {}, *convb[2] = {};       // [in][out]
+    IrManiqaBlock swin[2][IR_MANIQA_SWIN_LAYERS][IR_MANIQA_MAX_DEPTH] = {};
+    const float *head_w1 = nullptr, *head_b1 = nullptr, *head_w2 = nullptr, *head_b2 = nullptr;   // fc1 of score | weight [Eh][2 Eh], [2 Eh]; fc2 [2][Eh], [2]
+};
+// ir_maniqa_plan: the workspace of a call that processes its n * crops crops in passes of per_pass (cut to n * crops), byte offsets. In front the
+// per-patch (s, w) doubles of ALL crops and the two maps [4 embed][N] per crop of a pass that the TABs alternate between; behind them, over one
+// another, the trunk's arrays (x, the LayerNorm output, q | k | v, the attention output, the MLP's hidden rows, the scores of zc (crop, head)
+// pairs with rows padded to Tpad, the patch embeddings), a TAB's (q | k | v of every crop, one crop's C x C matrix) and a Swin stage's.
+struct IrManiqaPlan {
+    size_t sw, tap[2], x, hn, qkv, o, f, s, emb, tqkv, ts, y0, y, yn, sqkv, so, sf, total;
+    int cp, zc, Tpad;
+};
+int ir_maniqa_plan(const IrManiqaModel& m, int n, int crops, int per_pass, IrManiqaPlan* plan);
+int ir_launch_maniqa(const IrManiqaModel& m, const uint8_t* img, int rows, long pitch, int n, int h, int w, const int* origins, int crops, double* scores,
+                     float* feat, void* ws, const IrManiqaPlan& plan, hipStream_t s);
+
 // ---- low-quality inputs from ground truth (degrade.hip)
 // One image: blur (K x K fp64 taps in device memory, K odd, at most IR_DEGRADE_MAX_KSIZE: the float halo tile of a 32 x 32 patch must fit in 64 KB
 // of LDS), bilinear to lh x lw, noise (or NULL), the JPEG round trip at q (0: none), bilinear back, bytes (norm: include/instarevive_hip.h's IR_DEGRADE_NORM_*). jpeg: NULL or lh x lw x 3 bytes behind

@@ -235,26 +235,28 @@ class Report:
     format (`psnr: %.5f`, `ssim: %.5f`). A report made with lpips=True carries LPIPS as well: every add() then takes the third value, the header
     is `file,psnr_y,ssim_y,lpips` and the averages gain `lpips: %.5f` after `ssim`. niqe=True appends the no-reference NIQE (niqe.py) as the last
     column and the last average line (`niqe: %.5f`); clipiqa=True appends CLIP-IQA (clipiqa.py) behind it (`clipiqa: %.5f`, evaluate_img.py's
-    key), musiq=True appends MUSIQ (musiq.py) behind that (`musiq: %.5f`). The full column order is
-    `file,psnr_y,ssim_y,lpips,niqe,clipiqa,musiq`; absent metrics are left out. paired=False (a run without ground truth) carries the
-    no-reference columns alone: `file,niqe`, `file,clipiqa`, `file,musiq`, `file,niqe,clipiqa` and so on."""
+    key), musiq=True appends MUSIQ (musiq.py) behind that (`musiq: %.5f`), maniqa=True MANIQA (maniqa.py) behind that (`maniqa: %.5f`). The
+    full column order is `file,psnr_y,ssim_y,lpips,niqe,clipiqa,musiq,maniqa`; absent metrics are left out. paired=False (a run without ground truth) carries the
+    no-reference columns alone: `file,niqe`, `file,clipiqa`, `file,musiq`, `file,maniqa`, `file,niqe,clipiqa` and so on. HEADERS lists
+    the headers without the MANIQA column, HEADERS_MANIQA those with it."""
     HEADER = "file,psnr_y,ssim_y"
     HEADER_LPIPS = HEADER + ",lpips"
     HEADER_NIQE = "file,niqe"
     HEADERS = tuple(p + n + c + m for p in (HEADER, HEADER_LPIPS, "file") for n in ("", ",niqe") for c in ("", ",clipiqa") for m in ("", ",musiq")
                     if p != "file" or n or c or m)
+    HEADERS_MANIQA = tuple(h + ",maniqa" for h in HEADERS + ("file",))
 
     def __init__(self, path: Optional[str] = None, lpips: bool = False, niqe: bool = False, paired: bool = True, clipiqa: bool = False,
-                 musiq: bool = False):
+                 musiq: bool = False, maniqa: bool = False):
         self.path, self.rows, self.lpips, self.niqe, self.paired, self.clipiqa = path, [], bool(lpips), bool(niqe), bool(paired), bool(clipiqa)
-        self.musiq = bool(musiq)
-        if not self.paired and (self.lpips or not (self.niqe or self.clipiqa or self.musiq)):
-            raise MetricsError("Report: a report without paired scores carries NIQE, CLIP-IQA and / or MUSIQ and nothing else")
+        self.musiq, self.maniqa = bool(musiq), bool(maniqa)
+        if not self.paired and (self.lpips or not (self.niqe or self.clipiqa or self.musiq or self.maniqa)):
+            raise MetricsError("Report: a report without paired scores carries NIQE, CLIP-IQA, MUSIQ and / or MANIQA and nothing else")
         self.keys = ((("psnr", "ssim") + (("lpips",) if self.lpips else ()) if self.paired else ()) + (("niqe",) if self.niqe else ())
-                     + (("clipiqa",) if self.clipiqa else ()) + (("musiq",) if self.musiq else ()))
+                     + (("clipiqa",) if self.clipiqa else ()) + (("musiq",) if self.musiq else ()) + (("maniqa",) if self.maniqa else ()))
 
     def add(self, name: str, psnr: Optional[float] = None, ssim: Optional[float] = None, lpips: Optional[float] = None, niqe: Optional[float] = None,
-            clipiqa: Optional[float] = None, musiq: Optional[float] = None) -> None:
+            clipiqa: Optional[float] = None, musiq: Optional[float] = None, maniqa: Optional[float] = None) -> None:
         if (lpips is not None) != self.lpips:
             raise MetricsError("Report.add: an LPIPS value is needed by a report made with lpips=True and by no other")
         if (niqe is not None) != self.niqe:
@@ -263,9 +265,11 @@ class Report:
             raise MetricsError("Report.add: a CLIP-IQA value is needed by a report made with clipiqa=True and by no other")
         if (musiq is not None) != self.musiq:
             raise MetricsError("Report.add: a MUSIQ value is needed by a report made with musiq=True and by no other")
+        if (maniqa is not None) != self.maniqa:
+            raise MetricsError("Report.add: a MANIQA value is needed by a report made with maniqa=True and by no other")
         if (psnr is not None) != self.paired or (ssim is not None) != self.paired:
             raise MetricsError("Report.add: PSNR and SSIM are needed by a report with paired scores and by no other")
-        given = dict(psnr=psnr, ssim=ssim, lpips=lpips, niqe=niqe, clipiqa=clipiqa, musiq=musiq)
+        given = dict(psnr=psnr, ssim=ssim, lpips=lpips, niqe=niqe, clipiqa=clipiqa, musiq=musiq, maniqa=maniqa)
         self.rows.append((str(name),) + tuple(float(given[k]) for k in self.keys))
 
     def add_scores(self, name: str, scores: Sequence[float]) -> None:
@@ -276,8 +280,8 @@ class Report:
 
     def unscored(self, scores: Sequence[float]) -> Optional[str]:
         """For a score tuple in the report's own column order: the no-reference column whose value is NaN - the image has no such score -
-        "niqe" before "clipiqa" before "musiq"; None when the tuple can be added."""
-        for k in ("niqe", "clipiqa", "musiq"):
+        "niqe" before "clipiqa" before "musiq" before "maniqa"; None when the tuple can be added."""
+        for k in ("niqe", "clipiqa", "musiq", "maniqa"):
             if k in self.keys and scores[self.keys.index(k)] != scores[self.keys.index(k)]:
                 return k
         return None
@@ -313,10 +317,10 @@ class Report:
 
 def read_report(path: str) -> dict:
     """{file: (psnr_y, ssim_y)} of a CSV that Report wrote; {file: (psnr_y, ssim_y, lpips)} of one with the LPIPS column; with the NIQE column
-    that value follows, with the CLIP-IQA and MUSIQ columns those values come last; a `file,niqe` report gives {file: (niqe,)}."""
+    that value follows, with the CLIP-IQA, MUSIQ and MANIQA columns those values come last; a `file,niqe` report gives {file: (niqe,)}."""
     import csv
     with open(path, newline="") as f:
         rows = list(csv.reader(f))
-    if not rows or ",".join(rows[0]) not in Report.HEADERS:
+    if not rows or ",".join(rows[0]) not in Report.HEADERS + Report.HEADERS_MANIQA:
         raise MetricsError(f"{path}: not a metrics report")
     return {r[0]: tuple(float(v) for v in r[1:len(rows[0])]) for r in rows[1:]}

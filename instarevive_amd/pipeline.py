@@ -229,11 +229,11 @@ class _Batch:
     two streams and keeps the batch's events in `ready` (its uploads) and `done` (its downloads)."""
 
     def __init__(self, ctx, slot, tag, slots, shape, imgs, with_stage1, rects=None, records=None, dparams=None, gts=None, lpips=False, niqe=None,
-                 clipiqa=False, sizes=None, want_lq=False, prompts=(None, None), codec=None, png_runs=False, musiq=False):
+                 clipiqa=False, sizes=None, want_lq=False, prompts=(None, None), codec=None, png_runs=False, musiq=False, maniqa=False):
         """The plan phase, host work only: every size is checked and every ground truth compared with its image's FINAL size, so a batch that
         does not fit raises ValueError before anything is launched for it; then the scorer slots are filled / planned - `scorers` holds them in
         the order of a score tuple: paired (metrics.ScoreSlot; with lpips it scores LPIPS as well, ir_lpips with the weights lpips.configure()
-        bound to the context), NIQE with `niqe` its parameters, CLIP-IQA, MUSIQ - and the images copied into page-locked memory: the staging input, or
+        bound to the context), NIQE with `niqe` its parameters, CLIP-IQA, MUSIQ, MANIQA (maniqa: True, or the images' names, which key random crops) - and the images copied into page-locked memory: the staging input, or
         the decoded files (with their degrade parameters) into the ResizeSlot, whose bicubic chain then makes the staging input on the device.
         sizes: the batch's niqe_rects entry. codec: None - rects are coded as PNG, in the run mode with png_runs - or _jpeg_codec()'s pair."""
         from .slots import final_sizes, record_sizes
@@ -257,8 +257,8 @@ class _Batch:
             self.sc = ScoreSlot.get(ctx, slot, tag)
             self.sc.fill(gts, lpips, copies)
             self.scorers.append(self.sc)
-        if niqe is not None or clipiqa or musiq:
-            finals = final_sizes("niqe" if niqe is not None else "clipiqa" if clipiqa else "musiq", n, h, w, records, rects, sizes, gts)
+        if niqe is not None or clipiqa or musiq or maniqa:
+            finals = final_sizes("niqe" if niqe is not None else "clipiqa" if clipiqa else "musiq" if musiq else "maniqa", n, h, w, records, rects, sizes, gts)
             if niqe is not None:
                 from .niqe import NiqeSlot
                 self.scorers.append(NiqeSlot.get(ctx, slot, tag))
@@ -271,6 +271,10 @@ class _Batch:
                 from .musiq import MusiqSlot
                 self.scorers.append(MusiqSlot.get(ctx, slot, tag))
                 self.scorers[-1].plan(finals, copies)
+            if maniqa:
+                from .maniqa import ManiqaSlot
+                self.scorers.append(ManiqaSlot.get(ctx, slot, tag))
+                self.scorers[-1].plan(finals, copies, None if maniqa is True else list(maniqa))
         if rects is not None:
             if records is None and len(rects) != n:
                 raise ValueError(f"{'png' if codec is None else 'jpeg'}: {len(rects)} rectangles for a batch of {n} images")
@@ -407,7 +411,7 @@ def process(model, control_imgs: List[np.ndarray], strength: float, color_fix_ty
             tile_size: int, tile_stride: int, preprocess_model=None, vae=None, y=None, y_mask=None, noise_scheduler=None,
             fused: bool = True, graph: bool = False, return_stage1: bool = True, fp8: bool = False, png=None,
             resize=None, gt=None, lpips: bool = False, niqe=None, niqe_rects=None, clipiqa: bool = False, degrade=None,
-            lq_sink=None, jpeg=None, jpeg_quality: int = 95, jpeg_subsampling=2, png_runs: bool = False, musiq: bool = False) -> Tuple[List[np.ndarray], List[np.ndarray]]:
+            lq_sink=None, jpeg=None, jpeg_quality: int = 95, jpeg_subsampling=2, png_runs: bool = False, musiq: bool = False, maniqa=False) -> Tuple[List[np.ndarray], List[np.ndarray]]:
     """test_scripts/inference.py:55-166. control_imgs: list of HWC uint8 RGB arrays of equal size (multiples of 64).
     Returns (preds, stage1_preds) as lists of HWC uint8 arrays (stage1_preds is empty with return_stage1=False, which skips its
     conversion and download).
@@ -451,6 +455,10 @@ def process(model, control_imgs: List[np.ndarray], strength: float, color_fix_ty
     musiq (fused form only; alone or with gt, lpips, niqe and clipiqa): score MUSIQ as well - ir_musiq with the model instarevive_amd.musiq.configure()
     bound to the models' context, queued behind ir_clipiqa on the same final rectangles (niqe_rects serves it too). Its value comes behind
     clipiqa's, the last of every tuple. An image of which a resized side rounds to 0 (1 x 1000) gets NaN.
+    maniqa (fused form only; alone or with the others): score MANIQA as well - ir_maniqa with the model instarevive_amd.maniqa.configure() bound to
+    the models' context, queued behind ir_musiq on the same final rectangles. True, or one name per image: with maniqa.configure(mode="random")
+    an image's crop origins are drawn from the seed and its name (its row in the batch without names). Its value is the last of every tuple.
+    An image whose short side is not above the crop (224) gets NaN.
     degrade (with resize): one instarevive_amd.degrade.Params (or one degrade.ChainParams - the second-order chain, ir_degrade_chain; a batch
     holds one kind) per image - the decoded files are GROUND TRUTH, and between the upload and the
     bicubic chain ir_degrade makes each one's LQ image on the device (blur, bilinear downsample, noise, JPEG round trip, bilinear resize back;
@@ -463,7 +471,7 @@ def process(model, control_imgs: List[np.ndarray], strength: float, color_fix_ty
         raise ValueError("process(degrade=...) needs resize=: the ground truth is degraded on the device input route")
     n, h, w = _batch_shape(control_imgs, resize)
     codec = _jpeg_codec(png, jpeg, jpeg_quality, jpeg_subsampling)
-    if (png is not None or jpeg is not None or resize is not None or gt is not None or niqe is not None or clipiqa or musiq) and not (fused and _fused_ok(model, preprocess_model, vae, disable_preprocess_model)):
+    if (png is not None or jpeg is not None or resize is not None or gt is not None or niqe is not None or clipiqa or musiq or maniqa) and not (fused and _fused_ok(model, preprocess_model, vae, disable_preprocess_model)):
         raise ValueError("process(png=... / resize=... / gt=... / niqe=...) needs the fused form (instarevive_amd models sharing one context)")
     device = model.device
     acp = float(noise_scheduler.alphas_cumprod[400])
@@ -475,7 +483,7 @@ def process(model, control_imgs: List[np.ndarray], strength: float, color_fix_ty
             raise RuntimeError("process(fp8=True): call vae.enable_fp8() first - without the fp8 weight forms every layer would silently run in bf16")
         ctx = model.ctx
         batch = _Batch(ctx, 0, "sync", 1, (n, h, w), control_imgs, return_stage1, png if codec is None else jpeg, resize, degrade, gt, lpips, niqe,
-                       clipiqa, niqe_rects, lq_sink is not None, codec=codec, png_runs=png_runs, musiq=musiq)
+                       clipiqa, niqe_rects, lq_sink is not None, codec=codec, png_runs=png_runs, musiq=musiq, maniqa=maniqa)
         _prepare_fused(model, y, y_mask, h, w, tiled, tile_size, (vae, None if disable_preprocess_model else preprocess_model))
         flags = _pipeline_flags(model, color_fix_type, disable_preprocess_model, tiled) | (L.FLAG_GRAPH if graph else 0) | (L.FLAG_FP8 if fp8 else 0)
         batch.upload()
@@ -543,7 +551,7 @@ def process_stream(model, batches: Iterable[Sequence[np.ndarray]], color_fix_typ
                    return_stage1: bool = True, graph: bool = False, fp8: bool = False, png=None,
                    png_wrap: bool = True, resize=None, gt=None, lpips: bool = False, niqe=None,
                    niqe_rects=None, clipiqa: bool = False, degrade=None, lq_sink=None, jpeg=None, jpeg_quality: int = 95,
-                   jpeg_subsampling=2, png_runs: bool = False, musiq: bool = False) -> Iterator[Tuple[List[np.ndarray], List[np.ndarray]]]:
+                   jpeg_subsampling=2, png_runs: bool = False, musiq: bool = False, maniqa=False) -> Iterator[Tuple[List[np.ndarray], List[np.ndarray]]]:
     """process() over a sequence of image batches with the transfers hidden: while batch i computes on the current stream, batch
     i+1 is uploaded and batch i-1 downloaded on a copy stream (two staging slots per batch shape). Yields process()'s result for
     every batch, in order. Needs the fused form (all models instarevive_amd objects on one context). fp8 as in process() (cfg-5:
@@ -586,7 +594,9 @@ def process_stream(model, batches: Iterable[Sequence[np.ndarray]], color_fix_typ
     clipiqa (with or without gt and niqe): as in process() - ir_clipiqa is queued behind ir_niqe_stats on the batches NIQE scores or would score
     (niqe_rects serves both), and its value comes last in every tuple.
     musiq (alone or with gt, lpips, niqe and clipiqa): as in process() - ir_musiq is queued behind ir_clipiqa on the same batches and rectangles, and
-    its value comes behind clipiqa's."""
+    its value comes behind clipiqa's.
+    maniqa (alone or with the others): as in process() - ir_maniqa is queued behind ir_musiq on the same batches and rectangles, and its value comes
+    last. True, or an iterable in step with the batches that gives each batch's list of names."""
     noise_scheduler = noise_scheduler or DDPMScheduler()
     if lpips and gt is None:
         raise ValueError("process_stream(lpips=True) needs gt=: LPIPS is scored against the ground truth")
@@ -606,7 +616,8 @@ def process_stream(model, batches: Iterable[Sequence[np.ndarray]], color_fix_typ
     if degrade_it is not None and resize_it is None:
         raise ValueError("process_stream(degrade=...) needs resize=: the ground truth is degraded on the device input route")
     gt_it = iter(gt) if gt is not None else None
-    noref = niqe is not None or bool(clipiqa) or bool(musiq)
+    noref = niqe is not None or bool(clipiqa) or bool(musiq) or bool(maniqa)
+    mq_it = iter(maniqa) if maniqa and maniqa is not True else None
     nq_it = iter(niqe_rects) if noref and niqe_rects is not None else None
 
     def staged(batch, slot):
@@ -620,9 +631,11 @@ def process_stream(model, batches: Iterable[Sequence[np.ndarray]], color_fix_typ
         gts = next(gt_it) if gt_it is not None else None
         sizes = next(nq_it) if nq_it is not None else None
         with_nq = noref and (sizes is not None if nq_it is not None else (gts is not None or gt_it is None))
+        names = next(mq_it) if mq_it is not None else None
         imgs, by, bm = _split_batch(batch)
         b = _Batch(ctx, slot, "stream", 2, _batch_shape(imgs, records), imgs, return_stage1, rects, records, dparams, gts, lpips,
-                   niqe if with_nq else None, bool(clipiqa) and with_nq, sizes, lq_sink is not None, (by, bm), codec=codec, png_runs=png_runs, musiq=bool(musiq) and with_nq)
+                   niqe if with_nq else None, bool(clipiqa) and with_nq, sizes, lq_sink is not None, (by, bm), codec=codec, png_runs=png_runs, musiq=bool(musiq) and with_nq,
+                   maniqa=(names if names is not None else True) if maniqa and with_nq else False)
         with torch.cuda.stream(copy):
             b.ready = b.upload(copy, main)
         return b

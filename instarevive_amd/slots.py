@@ -1,5 +1,5 @@
 """What the per-slot buffers of a batch in flight share (resample.ResizeSlot, metrics.ScoreSlot, niqe.NiqeSlot, clipiqa.ClipIqaSlot,
-musiq.MusiqSlot): the pool
+musiq.MusiqSlot, maniqa.ManiqaSlot): the pool
 they are kept in, the final size of every image of a batch, and the grouping of a batch's images into device calls. Host code only.
 
 The scorer slots have one life cycle, which pipeline._Batch drives without knowing which is which: fill() / plan() on the host says what
@@ -35,7 +35,7 @@ def final_sizes(what: str, n: int, h: int, w: int, records=None, rects=None, siz
     what="gt", the paired scores: the final sizes of the resize records, else the png rectangles `rects`, else the ground truths' own sizes when
     there is one per image, else the whole output. Every ground truth is then checked against its size (metrics.check_ground_truth; min_edge is
     the smallest edge the scorers take), so a mismatch raises ValueError with both sizes before anything is launched for the batch.
-    what="niqe" / "clipiqa" / "musiq", the no-reference scores: the resize records, the png rectangles, `sizes` (niqe_rects), the ground truths' sizes, the
+    what="niqe" / "clipiqa" / "musiq" / "maniqa", the no-reference scores: the resize records, the png rectangles, `sizes` (niqe_rects), the ground truths' sizes, the
     whole output. Only a resized result may be larger than the network's output."""
     def ints(rr):
         return [tuple(int(v) for v in r) for r in rr]

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """NIQE of an output folder: the one no-reference metric of the reference's evaluate_img.py that is no pretrained network (`create_metric('niqe')`
-next to MANIQA / MUSIQ / CLIPIQA, which are; tools/evaluate_clipiqa.py and tools/evaluate_musiq.py score the latter two).
+next to MANIQA / MUSIQ / CLIPIQA, which are; tools/evaluate_maniqa.py, tools/evaluate_musiq.py and tools/evaluate_clipiqa.py score those).
 
     python tools/evaluate_niqe.py -i results/ --niqe_params niqe_modelparameters.mat [--ntest N] [--backend gpu]
 

@@ -20,8 +20,9 @@ runs tools/repin_with_diffusers.py-style checks:
     The pretrained weights (torchvision's alexnet-owt-7be5be79.pth, 233 MB, and lpips/weights/v0.1/alex.pth, 6 KB) do not exist offline:
     LPIPS is computed only when the user passes them (--lpips_alexnet / --lpips_lin, or one full `lpips.LPIPS().state_dict()` file through
     --lpips_lin alone); the arithmetic is tested against an independent torch.nn construction on random weights (tests/test_host_cpu.py).
-Of the no-reference metrics of the same script, MANIQA, MUSIQ and CLIPIQA are pretrained networks: CLIPIQA and MUSIQ have
-their own tools, tools/evaluate_clipiqa.py and tools/evaluate_musiq.py, which take the user's weights; MANIQA (20 random crops) is out of scope. NIQE
+Of the no-reference metrics of the same script, MANIQA, MUSIQ and CLIPIQA are pretrained networks: each has its own tool,
+tools/evaluate_clipiqa.py, tools/evaluate_musiq.py and tools/evaluate_maniqa.py (its 20 crops lie on pyiqa's uniform grid, or are drawn from a
+seed and the file's name), which take the user's weights. NIQE
 is classical image statistics plus a few KB of pristine parameters and has its own tool, tools/evaluate_niqe.py.
 Files are paired by sorted order exactly as the reference does (glob "*.[jpJP][pnPN]*[gG]")."""
 import argparse

@@ -33,6 +33,9 @@ random-initialised models of reduced width pin it exactly as the 4 GB checkpoint
 11. pyiqa's MUSIQ (evaluate_img.py's `create_metric('musiq')`, the koniq10k checkpoint) -> tools/evaluate_musiq.py on pyiqa's own weights, read
     through PYIQA_KEYS: the score of two images to 1e-4 (the score is roughly 0 - 100; pyiqa runs fp32). A mismatch points at one of the three
     recollections that file names: the key table, standardize() or resize().
+12. pyiqa's MANIQA (evaluate_img.py's `create_metric('maniqa')`, the koniq checkpoint) -> tools/evaluate_maniqa.py on pyiqa's own weights, read
+    through PYIQA_KEYS, at pyiqa's uniform crop grid: the score of two images to 1e-5 (the score is roughly 0 - 1; pyiqa runs fp32). A mismatch
+    points at one of that file's recollections: the key table, uniform_origins(), DEFAULTS (scale, crops, taps), or a step docs/parity.md lists.
  6. ftfy.fix_text (diffusion/model/t5.py:118-124) -> instarevive_amd.captions.fix_text (deterministic steps + the restricted mojibake repair).
 
 The fixture holds inputs, state-dict checksums and the third party's outputs (data, not source); tests/test_oracle_golden.py picks
@@ -270,6 +273,41 @@ def pin_clipiqa(out, bpe=None):
     return ok
 
 
+def pin_maniqa(out):
+    """pyiqa's `maniqa` against tools/evaluate_maniqa.py on the koniq weights pyiqa itself loads (its network's state dict, the ViT under `vit.`)."""
+    import importlib.util
+    import pyiqa
+    spec = importlib.util.spec_from_file_location("evaluate_maniqa", os.path.join(ROOT, "tools", "evaluate_maniqa.py"))
+    em = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(em)
+    metric = pyiqa.create_metric("maniqa", device="cpu")
+    sd = {k: v.detach().float() for k, v in metric.net.state_dict().items()}
+    keys = em.PYIQA_KEYS(dict(vit_layers=em.DEFAULTS["taps"][-1] + 1, swin_depth=2))
+    missing = [theirs for theirs in keys.values() if theirs not in sd]
+    if missing:
+        print(f"  [12] PYIQA_KEYS names {len(missing)} tensors pyiqa's checkpoint does not have, e.g. {missing[:3]}; it has e.g. {sorted(sd)[:5]}")
+        return False
+    import tempfile
+    with tempfile.TemporaryDirectory() as tmp:   # through the .pth reader, as a user's file goes
+        torch.save(sd, os.path.join(tmp, "maniqa.pth"))
+        model = em.load_model(os.path.join(tmp, "maniqa.pth"))
+    net = metric.net
+    print(f"  [12] pyiqa: scale {getattr(net.swintransformer1, 'scale', None)}, test_sample {getattr(net, 'test_sample', None)}; evaluate_maniqa: scale "
+          f"{model['cfg']['scale']}, crops {model['cfg']['crops']}, taps {model['cfg']['taps']}")
+    rng = np.random.default_rng(17)
+    yy, xx = np.mgrid[0:288, 0:352].astype(np.float64)
+    base = np.stack([128 + 80 * np.sin(xx / 23) * np.cos(yy / 31), 128 + 70 * np.sin((xx + yy) / 41), 128 + 90 * np.cos(xx / 17 - yy / 29)], -1)
+    ok = True
+    for name, sigma in (("smooth", 2.0), ("noisy", 25.0)):
+        img = np.clip(np.rint(base + rng.normal(0, sigma, base.shape)), 0, 255).astype(np.uint8)
+        ref = float(metric(torch.from_numpy(img).permute(2, 0, 1)[None].float() / 255.0))
+        got = em.maniqa(img, model)   # the uniform grid: current pyiqa's uniform_crop
+        print(f"  [12] pyiqa MANIQA ({name}) {ref:.6f} vs evaluate_maniqa {got:.6f} (absolute {abs(got - ref):.2e})")
+        out[f"maniqa_{name}"], out[f"maniqa_{name}_ref"] = img, np.float64(ref)
+        ok = ok and abs(got - ref) <= 1e-5
+    return ok
+
+
 def pin_musiq(out):
     """pyiqa's `musiq` against tools/evaluate_musiq.py on the koniq10k weights pyiqa itself loads (its network's state dict)."""
     import importlib.util
@@ -360,7 +398,8 @@ def main():
     for name, fn, args in (("diffusers DiT (items 1, 2)", pin_dit, (None,)), ("diffusers VAE (item 3)", pin_vae, (None,)),
                            ("open_clip (item 4)", pin_clip, ()), ("pyiqa (item 5)", pin_iqa, ()), ("ftfy (item 6)", pin_ftfy, ()), ("lpips (item 7)", pin_lpips, ()),
                            ("pyiqa NIQE (item 8)", pin_niqe, ()), ("pyiqa CLIP-IQA (item 9)", pin_clipiqa, (a.clip_bpe,)),
-                           ("OpenCV degradation steps (item 10)", pin_degrade, ()), ("pyiqa MUSIQ (item 11)", pin_musiq, ())):
+                           ("OpenCV degradation steps (item 10)", pin_degrade, ()), ("pyiqa MUSIQ (item 11)", pin_musiq, ()),
+                           ("pyiqa MANIQA (item 12)", pin_maniqa, ())):
         print(name)
         try:
             verdict[name] = fn(out, *args)
