@@ -70,13 +70,17 @@ def parse_args():
     ap.add_argument("--clip_bpe", default=None, help="with --clipiqa_model: the folder that holds CLIP's BPE table (inference.py --clip_bpe)")
     ap.add_argument("--degrade", nargs="?", const="lq", default=None, metavar="lq|realesrgan|FILE.json", help="--input holds GROUND TRUTH: the centre crops are degraded on "
                     "the GPU (inference.py --degrade: blur, bilinear downsample, noise, JPEG, bilinear resize back; `realesrgan`: the reference's second-order "
-                    "validation recipe) and the LQ images restored; needs "
+                    "validation recipe) and the LQ images restored (with --center_crop gpu the crops are made on the device as well); needs "
                     "--image_size to be a multiple of 64 of at least 512 (the crop is then the network input as it is). Without --gt the input folder "
                     "is the ground truth of --lpips_lin / --niqe_params / --clipiqa_model / --musiq_model / --maniqa_model")
     ap.add_argument("--degrade_seed", type=int, default=231, help="with --degrade: seeds every file's draws together with the crc32 of its input-relative path")
     ap.add_argument("--save_lq", default=None, metavar="DIR", help="with --degrade: write the synthesised LQ crops to DIR")
-    ap.add_argument("--jpeg_decoder", default="host", choices=["host", "gpu"], help="inference.py's flag; only `host` here: every input is centre-cropped on the "
-                    "host (a BOX filter halves large files), which inference.py --jpeg_decoder gpu refuses as --use_center_crop")
+    ap.add_argument("--jpeg_decoder", default="host", choices=["host", "gpu"], help="inference.py's flag; `gpu` only together with --center_crop gpu: without it "
+                    "every input is centre-cropped on the host (a BOX filter halves large files), which inference.py --jpeg_decoder gpu refuses as --use_center_crop")
+    ap.add_argument("--center_crop", default="host", choices=["host", "gpu"], help="who centre-crops the inputs to --image_size. host (default): PIL on the reader "
+                    "threads (center_crop_arr). gpu: the decoded file - with --jpeg_decoder gpu the compressed bytes of a baseline JPEG - is uploaded and the "
+                    "device makes the same pixels (inference.py --center_crop gpu: BOX halvings, the bicubic resize, the central window); with --degrade the crop "
+                    "is then degraded on the device as well. The ground-truth files of --gt stay decoded and cropped on the host")
     ap.add_argument("--workers", type=int, default=-1, help="host threads for decoding / PNG encoding (inference.py --workers)")
     return ap.parse_args()
 
@@ -93,12 +97,16 @@ def main():
     from instarevive_amd import parallel
     from instarevive_amd.pipeline import process_stream
     from instarevive_amd.prompts import Captions
+    from instarevive_amd.resample import ResizeJob, crop_geometry
     from instarevive_amd.utils import center_crop_arr, list_image_files
     args = parse_args()
     cli.check_save_format(args)
-    if args.jpeg_decoder == "gpu":
+    crop_gpu = args.center_crop == "gpu"
+    if args.jpeg_decoder == "gpu" and crop_gpu:
+        args.jpeg_decode_log = []   # per file None (decoded on the device) or the reason it took the host decoder
+    elif args.jpeg_decoder == "gpu":
         raise SystemExit("--jpeg_decoder gpu decodes into the device's resize route, and this tool centre-crops every input on the host (as inference.py "
-                         "--use_center_crop, where the flag is refused too): not offered")
+                         "--use_center_crop, where the flag is refused too): not offered (or give --center_crop gpu)")
     ext_out = cli.save_ext(args)
     niqe_params = cli.load_niqe_params(args)
     clipiqa_model = cli.load_clipiqa_model(args)
@@ -110,7 +118,7 @@ def main():
         raise SystemExit("--save_lq writes the images --degrade synthesises: give --degrade as well")
     if args.degrade:
         from instarevive_amd import degrade as D
-        from instarevive_amd.resample import ResizeJob, job_geometry
+        from instarevive_amd.resample import job_geometry
         try:
             recipe = D.load_recipe(args.degrade)
         except (D.DegradeError, OSError, ValueError) as e:
@@ -164,8 +172,22 @@ def main():
             maniqa.configure(m.model.ctx, maniqa_model, args.maniqa_crops, args.maniqa_seed)
 
     def read(f):
-        crop = center_crop_arr(Image.open(f).convert("RGB"), args.image_size)
         gt = np.ascontiguousarray(center_crop_arr(lookup.load(f), args.image_size)) if lookup else None
+        if crop_gpu:   # decode only (--jpeg_decoder gpu: the headers and one byte pass); the device crops, and degrades the crop
+            source = None
+            if args.jpeg_decoder == "gpu":
+                from instarevive_amd.jpeg_decode import JpegSource
+                with open(f, "rb") as fh:
+                    source, why = JpegSource.open(fh.read())
+                args.jpeg_decode_log.append(why)
+                if source is not None:
+                    source.name = f
+            raw = np.array(Image.open(f).convert("RGB")) if source is None else source
+            job = ResizeJob(raw, crop_geometry((raw.shape[1], raw.shape[0]), 1, args.image_size))
+            if recipe is None:
+                return job, gt
+            return job, gt, D.draw(recipe, os.path.relpath(f, args.input), args.image_size, args.image_size, args.degrade_seed)
+        crop = center_crop_arr(Image.open(f).convert("RGB"), args.image_size)
         if recipe is None:
             return crop, gt
         crop = np.ascontiguousarray(crop)   # the draws (and the noise field) are made here, on a reader thread
@@ -176,10 +198,13 @@ def main():
         crops = pools.read_ahead(read, files)
         for group in batches:
             pairs = [next(crops) for _ in group]
-            imgs = [p[0] for p in pairs]
+            imgs = [None if crop_gpu else p[0] for p in pairs]
             truths.append([p[1] for p in pairs])
-            if recipe is not None:
+            if crop_gpu:
+                records.append([p[0] for p in pairs])
+            elif recipe is not None:
                 records.append([ResizeJob(p[0], geo) for p in pairs])
+            if recipe is not None:
                 dparams.append([p[2] for p in pairs])
             yield (imgs, *caps.batch(group)) if caps else imgs
 
@@ -209,7 +234,8 @@ def main():
                              gt=cli.in_step(truths) if lookup else None, **with_lpips, **({"niqe": niqe_params} if niqe_params else {}),
                              **({"clipiqa": True} if clipiqa_model else {}), **({"musiq": True} if musiq_model else {}),
                              **({"maniqa": [[os.path.basename(out_name(args.output, args.input, f, ext_out)) for f in group] for group in batches]} if maniqa_model else {}),
-                             **({"resize": cli.in_step(records), "degrade": cli.in_step(dparams), "lq_sink": lq_images.append if args.save_lq else None} if recipe else {}))
+                             **({"resize": cli.in_step(records)} if recipe or crop_gpu else {}),
+                             **({"degrade": cli.in_step(dparams), "lq_sink": lq_images.append if args.save_lq else None} if recipe else {}))
     no_score = {"niqe": 0, "clipiqa": 0, "musiq": 0, "maniqa": 0}
     for group, out in zip(batches, results):
         preds, stage1 = out[:2]
@@ -231,6 +257,8 @@ def main():
         print(f"[rank {rank}] queued {len(group)} images ({group[0]} ...)")
     pools.drain()
     print(f"[rank {rank}] saved {pools.written} files")
+    if cli.jpeg_decoder_note(args):
+        print(f"[rank {rank}] {cli.jpeg_decoder_note(args)}")
     if gpu_png:
         print(f"[rank {rank}] --png_encoder gpu: 0 of {pools.written} files took the host encoder")
     if gpu_jpg:

@@ -391,12 +391,24 @@ int ir_jpeg_decode(ir_ctx* ctx, void* stream, const ir_jpeg_file* files, int n, 
  * sizes makes the call write nothing. ws: 4-byte aligned, ir_workspace_bytes(ctx, IR_STAGE_RESAMPLE, n, in_h, out_w, 0, 0, 0) bytes; read only
  * when both passes run (it may be NULL otherwise). Stream-ordered, no allocation, no host synchronisation (capturable). Returns -1 (nothing
  * launched) for a null pointer, a size below 1, full_h < out_h, full_w < out_w, a pitch below three bytes per pixel, or a short or unaligned
- * workspace. */
-enum { IR_RESAMPLE_BICUBIC = 0, IR_RESAMPLE_LANCZOS = 1 };
+ * workspace.
+ * IR_RESAMPLE_BOX is Pillow's BOX filter (support 0.5, 1.0 for -0.5 < x <= 0.5) under Pillow's own number: what center_crop_arr halves large
+ * files with. Filters 2 and 3 have no plan.
+ * ir_resample_u8_window writes only the window [y0, y0 + win_h) x [x0, x0 + win_w) of the virtual out_h x out_w result of ir_resample_u8 - the
+ * same bytes - into the top-left corner of out [n][full_h][out_pitch]: zeros in rows win_h .. full_h and columns win_w .. full_w, nothing behind
+ * column full_w. The centre crop's last step: the cut lands in the network input without a full-size image. The horizontal pass produces
+ * columns x0 .. x0 + win_w only, and only of the source rows the window's vertical taps reach (read from the plan's vertical bounds on the
+ * device); a skipped pass copies the window. plan_dev: the plan of (in_h, in_w, out_h, out_w), as for the full call. ws: 4-byte aligned,
+ * ir_workspace_bytes(NULL, IR_STAGE_RESAMPLE, n, in_h, win_w, 0, 0, 0) bytes, read only when both passes run. Stream-ordered, no allocation,
+ * capturable. Returns -1 (nothing launched) for what ir_resample_u8 refuses, a window outside out_h x out_w (or an empty one), full_h < win_h,
+ * full_w < win_w, or out_pitch < 3 * full_w. */
+enum { IR_RESAMPLE_BICUBIC = 0, IR_RESAMPLE_LANCZOS = 1, IR_RESAMPLE_BOX = 4 };
 size_t ir_resample_plan_bytes(int in_h, int in_w, int out_h, int out_w, int filter);
 int ir_resample_plan(int in_h, int in_w, int out_h, int out_w, int filter, void* host_plan, size_t bytes);
 int ir_resample_u8(ir_ctx* ctx, void* stream, const uint8_t* in, int n, int in_h, int in_w, long in_pitch, uint8_t* out, int out_h, int out_w,
                    int full_h, int full_w, long out_pitch, const void* plan_dev, void* ws, size_t ws_bytes);
+int ir_resample_u8_window(ir_ctx* ctx, void* stream, const uint8_t* in, int n, int in_h, int in_w, long in_pitch, uint8_t* out, int out_h, int out_w,
+                          int y0, int x0, int win_h, int win_w, int full_h, int full_w, long out_pitch, const void* plan_dev, void* ws, size_t ws_bytes);
 
 /* PSNR-Y and SSIM-Y of results against ground truth on the device (the reference scores saved files on the host: evaluate_img.py:30-57, pyiqa's
  * `psnr` / `ssim` with test_y_channel=True; tools/evaluate_pairs.py restates them and is the model of this call). Compares the top-left h x w

@@ -100,7 +100,8 @@ def parse_args() -> Namespace:
                         "below 512 / the tile size, both bicubic) and the results of enlarged inputs (LANCZOS back to the input's size). host (default): PIL on the "
                         "reader / writer threads, as the reference does. gpu: the decoded file is uploaded as it is and the device resamples it with Pillow's own "
                         "integer arithmetic - the same pixels in the saved files - so the enlarged image neither costs a reader thread its bicubic nor crosses "
-                        "PCIe, and with --png_encoder gpu every file is encoded on the device. --show_lq, --use_center_crop and --shard_tiles keep the host path")
+                        "PCIe, and with --png_encoder gpu every file is encoded on the device. --show_lq, --use_center_crop (unless --center_crop gpu makes the crop on the device too) and --shard_tiles keep "
+                        "the host path")
     parser.add_argument("--gt", type=str, default=None, help="score the results against ground truth on the GPU (PSNR-Y / SSIM-Y by the definitions of "
                         "tools/evaluate_pairs.py, i.e. pyiqa's): DIR/<input-relative path> with any image extension, else DIR/<file stem>.*; a ground truth has the "
                         "size of the saved result. A file is scored when its saved image is the device's image - a plain crop of the prediction, and every file "
@@ -147,7 +148,7 @@ def parse_args() -> Namespace:
                         "validates general super-resolution with (configs/general_deg_realesrgan_val.yaml; ir_degrade_chain): two stages of blur, area / "
                         "bilinear / bicubic resize, Gaussian or Poisson noise and DiffJPEG, a final sinc filter, bicubic back - files of at least 44 pixels "
                         "on the short side; a JSON file with \"chain\": \"realesrgan\" may set that recipe's keys. No OpenCV, no second folder: the LQ image never "
-                        "leaves the device. Switches --resize gpu on; not offered with --show_lq, --use_center_crop, --shard_tiles. Without --gt the input "
+                        "leaves the device. Switches --resize gpu on; not offered with --show_lq, --use_center_crop (unless --center_crop gpu), --shard_tiles. Without --gt the input "
                         "folder is the ground truth of --metrics_out / --lpips_lin / --niqe_params / --clipiqa_model / --musiq_model / --maniqa_model")
     parser.add_argument("--degrade_seed", type=int, default=231, help="with --degrade: a file's parameters are drawn from a generator seeded by this number "
                         "and the crc32 of its input-relative path, whatever the batch size, worker count or rank")
@@ -155,7 +156,13 @@ def parse_args() -> Namespace:
     parser.add_argument("--jpeg_decoder", type=str, default="host", choices=["host", "gpu"], help="who decodes JPEG inputs. host (default): PIL, as the reference. gpu: "
                         "a reader thread parses the headers and removes the byte stuffing, the compressed bytes are uploaded and ir_jpeg_decode makes PIL's "
                         "pixels on the device (baseline files, grey or YCbCr 4:4:4 / 4:2:2 / 4:2:0; every other file, JPEG or not, takes PIL as today and the "
-                        "run says how many). Switches --resize gpu on; not offered with --show_lq, --use_center_crop, --shard_tiles")
+                        "run says how many). Switches --resize gpu on; not offered with --show_lq, --use_center_crop (unless --center_crop gpu), --shard_tiles")
+    parser.add_argument("--center_crop", type=str, default="host", choices=["host", "gpu"], help="who makes the centre crop of --use_center_crop. host (default): PIL on a "
+                        "reader thread, as the reference does (center_crop_arr: BOX halvings, a bicubic resize of the short edge to 512, the central window). gpu: "
+                        "the decoded file - or, with --jpeg_decoder gpu, its compressed bytes - is uploaded and the device runs the same chain with Pillow's own "
+                        "integer arithmetic (ir_resample_u8 with BOX plans, ir_resample_u8_window for the last step): the same pixels in the network input. Needs "
+                        "--use_center_crop and switches --resize gpu on; with it --use_center_crop is accepted next to --jpeg_decoder gpu and --degrade (the crop "
+                        "is then what is degraded). Not offered with --tiled, --show_lq, --shard_tiles")
     parser.add_argument("--workers", type=int, default=-1, help="host threads that decode / resize the inputs and resize / PNG-encode the results "
                         "around the GPU (PIL releases the GIL there); -1 = this process's CPU share, 0 = everything on the main thread like the reference")
     return parser.parse_args()
@@ -196,13 +203,34 @@ def check_save_format(args: Namespace) -> None:
     args.jpeg_encoder = args.jpeg_encoder or "host"
 
 
+def crop_on_gpu(args: Namespace) -> bool:
+    """--center_crop gpu (a Namespace without the attribute is the host crop of before the flag)."""
+    return getattr(args, "center_crop", "host") == "gpu"
+
+
+def check_center_crop(args: Namespace) -> None:
+    """--center_crop gpu makes --use_center_crop's crop on the device's resize route: it switches --resize gpu on and is refused where that route
+    is not offered. One line each, before anything is loaded."""
+    if not crop_on_gpu(args):
+        return
+    if not getattr(args, "use_center_crop", False):
+        raise SystemExit("--center_crop gpu says who makes the crop of --use_center_crop: give --use_center_crop as well")
+    for flag in ("tiled", "show_lq", "shard_tiles"):
+        if getattr(args, flag, False):
+            raise SystemExit(f"--center_crop gpu crops on the device's resize route (--resize gpu), which is not offered with --{flag}: not offered together")
+    if args.resize != "gpu":
+        print("--center_crop gpu: the crops are made on the device, switching --resize gpu on")
+        args.resize = "gpu"
+
+
 def check_jpeg_decoder(args: Namespace) -> None:
     """--jpeg_decoder gpu decodes into the device's resize route: it switches --resize gpu on and is refused wherever that is."""
     if getattr(args, "jpeg_decoder", "host") != "gpu":
         return
     for flag in ("show_lq", "use_center_crop", "shard_tiles"):
-        if getattr(args, flag, False):
-            raise SystemExit(f"--jpeg_decoder gpu decodes into the device's resize route (--resize gpu), which --{flag} keeps on the host: not offered together")
+        if getattr(args, flag, False) and not (flag == "use_center_crop" and crop_on_gpu(args)):
+            raise SystemExit(f"--jpeg_decoder gpu decodes into the device's resize route (--resize gpu), which --{flag} keeps on the host: not offered together"
+                             + (" (or give --center_crop gpu)" if flag == "use_center_crop" else ""))
     if args.resize != "gpu":
         print("--jpeg_decoder gpu: the files are decoded on the device, switching --resize gpu on")
         args.resize = "gpu"
@@ -388,6 +416,13 @@ def attach_gt(job: Job, args: Namespace) -> Job:
         # --degrade without --gt: the decoded file is the ground truth (a file the device decodes has no pixels here: the scorer's copy is PIL's)
         same = job.deg is not None and os.path.abspath(path) == os.path.abspath(job.src) and isinstance(job.raw, np.ndarray)
         gt = job.raw if same else np.array(Image.open(path).convert("RGB"))
+        if job.deg is not None and job.geo.crop is not None and gt.shape[:2] != tuple(rect):
+            # --center_crop gpu under --degrade: what is degraded is the crop, so the ground truth is cropped as well - on the host, by the same rule
+            from instarevive_amd.utils import center_crop_arr
+            full = Image.fromarray(gt)
+            if args.sr_scale != 1:
+                full = full.resize(tuple(math.ceil(edge * args.sr_scale) for edge in full.size), Image.BICUBIC)
+            gt = np.ascontiguousarray(center_crop_arr(full, rect[0]))
         if gt.shape[:2] != tuple(rect):
             raise MetricsError(f"--gt: {path} is {gt.shape[0]} x {gt.shape[1]}, the result of {job.src} is {rect[0]} x {rect[1]}")
         job.gt = gt
@@ -410,14 +445,17 @@ def decode_job(file_path: str, repeat: int, args: Namespace) -> Job:
             source.name = file_path
     lq = Image.open(file_path).convert("RGB") if source is None else None
     if getattr(args, "resize_on_gpu", False):   # decode only: the sizes are worked out here, the pixels are resampled on the device
-        from instarevive_amd.resample import job_geometry
+        from instarevive_amd.resample import crop_geometry, job_geometry
         width, height = lq.size if source is None else (source.shape[1], source.shape[0])
-        geo = job_geometry((width, height), args.sr_scale, args.tiled, args.tile_size)
+        if args.use_center_crop and crop_on_gpu(args):   # the device crops: the parameters of --degrade are drawn for the crop
+            geo = crop_geometry((width, height), args.sr_scale, 512)
+        else:
+            geo = job_geometry((width, height), args.sr_scale, args.tiled, args.tile_size)
         folder, stem, _ = get_file_name_parts(os.path.join(args.output, os.path.relpath(file_path, args.input)))
         job = Job(os.path.join(folder, f"{stem}_{repeat}{save_ext(args)}"), lq, None, geo.valid_hw, file_path, geo, np.array(lq) if source is None else source)
         if getattr(args, "degrade_recipe", None):   # the draws (and the noise field) are made here, on a reader thread
             from instarevive_amd.degrade import draw
-            job.deg = draw(args.degrade_recipe, os.path.relpath(file_path, args.input), height, width, args.degrade_seed)
+            job.deg = draw(args.degrade_recipe, os.path.relpath(file_path, args.input), *(geo.valid_hw if geo.crop is not None else (height, width)), args.degrade_seed)
         return job
     if args.sr_scale != 1:
         lq = lq.resize(tuple(math.ceil(edge * args.sr_scale) for edge in lq.size), Image.BICUBIC)
@@ -601,6 +639,7 @@ def main() -> None:
     from instarevive_amd.utils import list_image_files
     args = parse_args()
     check_save_format(args)
+    check_center_crop(args)
     check_jpeg_decoder(args)
     niqe_params = load_niqe_params(args)
     clipiqa_model = load_clipiqa_model(args)
@@ -684,7 +723,7 @@ def main() -> None:
     args.resize_on_gpu = args.resize == "gpu"
     for flag, why in (("show_lq", "its strip needs the enlarged LQ panel on the host"), ("use_center_crop", "the centre crop halves with a BOX filter"),
                       ("shard_tiles", "the tile-sharded path takes host-prepared images")):
-        if args.resize_on_gpu and getattr(args, flag):
+        if args.resize_on_gpu and getattr(args, flag) and not (flag == "use_center_crop" and crop_on_gpu(args)):
             print(f"[rank {rank}] --resize gpu: --{flag} keeps the resizes on the host ({why})")
             args.resize_on_gpu = False
     note = "" if jpg else host_keeps_up(pools.workers, int(512 * 512 * max(args.sr_scale, 1.0) ** 2), args.png_compress_level, args.png_encoder)   # priced on a 512 x 512 LQ file at this --sr_scale

@@ -25,7 +25,7 @@ SYMBOLS = [
     "ir_unet_configure", "ir_unet_set_context", "ir_cldm_sample", "ir_cldm_pipeline", "ir_clip_text_configure", "ir_clip_text_encode", "ir_op_groupnorm_any", "ir_op_geglu",
     "ir_dit_set_prompts", "ir_op_attention_kv_groups", "ir_graph_records", "ir_op_vae_segment", "ir_op_vae_segment_ws", "ir_op_vae_segment_info",
     "ir_op_swin_shell", "ir_op_swin_shell_ws", "ir_op_dit_shell", "ir_op_dit_shell_ws", "ir_op_unet_block", "ir_op_unet_block_ws", "ir_op_text_block", "ir_op_text_block_ws",
-    "ir_png_bound", "ir_png_encode", "ir_png_encode_runs", "ir_jpeg_bound", "ir_jpeg_encode", "ir_jpeg_decode", "ir_resample_plan_bytes", "ir_resample_plan", "ir_resample_u8", "ir_metrics_y",
+    "ir_png_bound", "ir_png_encode", "ir_png_encode_runs", "ir_jpeg_bound", "ir_jpeg_encode", "ir_jpeg_decode", "ir_resample_plan_bytes", "ir_resample_plan", "ir_resample_u8", "ir_resample_u8_window", "ir_metrics_y",
     "ir_lpips_scale_table", "ir_lpips_configure", "ir_lpips", "ir_niqe_window", "ir_niqe_stats",
     "ir_clipiqa_scale_table", "ir_clipiqa_configure", "ir_clipiqa", "ir_musiq_layout", "ir_musiq_input_table", "ir_musiq_configure", "ir_musiq",
     "ir_maniqa_input_table", "ir_maniqa_crops", "ir_maniqa_configure", "ir_maniqa",
@@ -67,6 +67,7 @@ FLAG_NO_PREPROCESS, FLAG_TILED, FLAG_FIX_WAVELET, FLAG_FIX_ADAIN, FLAG_CONTROL_L
 FP8_MASK_DEFAULT, FP8_MASK_QUALIFIED, FP8_MASK_ALL, FP8_MASK_ATTENTION = 0x5006, 0x5007, 0xffffffff, 0b111
 FP8_CONV_BITS = sum(1 << b for b in (4, 5, 6, 7, 8, 12, 13, 14, 15, 16))
 RESAMPLE_BICUBIC, RESAMPLE_LANCZOS = 0, 1
+RESAMPLE_BOX = 4   # Pillow's own number for BOX
 ACT_NONE, ACT_GELU_ERF, ACT_GELU_TANH, ACT_LRELU, ACT_SILU = range(5)
 
 _lib = None
@@ -246,6 +247,7 @@ def load_library():
     lib.ir_resample_plan_bytes.restype = sz
     lib.ir_resample_plan.argtypes = [i, i, i, i, i, vp, sz]
     lib.ir_resample_u8.argtypes = [vp, vp, vp, i, i, i, C.c_long, vp, i, i, i, i, C.c_long, vp, vp, sz]
+    lib.ir_resample_u8_window.argtypes = [vp, vp, vp, i, i, i, C.c_long, vp, i, i, i, i, i, i, i, i, C.c_long, vp, vp, sz]
     lib.ir_metrics_y.argtypes = [vp, vp, vp, i, C.c_long, vp, i, C.c_long, i, i, i, vp, vp, sz]
     lib.ir_lpips_scale_table.argtypes = [vp]
     lib.ir_lpips_configure.argtypes = [vp]

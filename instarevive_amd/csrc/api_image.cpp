@@ -223,6 +223,8 @@ static double rs_sinc(double x) {
     return sin(x) / x;
 }
 static double rs_lanczos(double x) { return (-3.0 <= x && x < 3.0) ? rs_sinc(x) * rs_sinc(x / 3) : 0.0; }
+static double rs_box(double x) { return (x > -0.5 && x <= 0.5) ? 1.0 : 0.0; }
+static double rs_support(int filter) { return filter == IR_RESAMPLE_LANCZOS ? 3.0 : filter == IR_RESAMPLE_BOX ? 0.5 : 2.0; }
 struct RsAxis {
     double scale, filterscale, support;
     int ksize;
@@ -231,7 +233,7 @@ static RsAxis rs_axis(int in, int out, int filter) {
     RsAxis a;
     a.filterscale = a.scale = (double)(float)in / out;
     if (a.filterscale < 1.0) a.filterscale = 1.0;
-    a.support = (filter == IR_RESAMPLE_LANCZOS ? 3.0 : 2.0) * a.filterscale;
+    a.support = rs_support(filter) * a.filterscale;
     a.ksize = (int)ceil(a.support) * 2 + 1;
     return a;
 }
@@ -249,7 +251,7 @@ static void rs_tables(int in, int out, int filter, int* bounds, int* kk) {
         xmax -= xmin;
         for (int x = 0; x < xmax; ++x) {
             const double arg = (x + xmin - center + 0.5) * ss;
-            w[x] = filter == IR_RESAMPLE_LANCZOS ? rs_lanczos(arg) : rs_bicubic(arg);
+            w[x] = filter == IR_RESAMPLE_LANCZOS ? rs_lanczos(arg) : filter == IR_RESAMPLE_BOX ? rs_box(arg) : rs_bicubic(arg);
             ww += w[x];
         }
         int* k = kk + (size_t)xx * a.ksize;
@@ -264,7 +266,7 @@ static void rs_tables(int in, int out, int filter, int* bounds, int* kk) {
 }
 #pragma clang fp contract(fast)
 static bool rs_args_ok(int in_h, int in_w, int out_h, int out_w, int filter) {
-    return in_h >= 1 && in_w >= 1 && out_h >= 1 && out_w >= 1 && (filter == IR_RESAMPLE_BICUBIC || filter == IR_RESAMPLE_LANCZOS);
+    return in_h >= 1 && in_w >= 1 && out_h >= 1 && out_w >= 1 && (filter == IR_RESAMPLE_BICUBIC || filter == IR_RESAMPLE_LANCZOS || filter == IR_RESAMPLE_BOX);
 }
 // ints of the plan: the header, then per pass that runs 2 bounds + ksize coefficients per output index
 static size_t rs_plan_ints(int in_h, int in_w, int out_h, int out_w, int filter, int* hd) {
@@ -314,6 +316,25 @@ int ir_resample_u8(ir_ctx* c, void* stream, const uint8_t* in, int n, int in_h, 
     if (ir_launch_resample_u8(in, n, in_h, in_w, in_pitch, out, out_h, out_w, full_h, full_w, out_pitch, static_cast<const int*>(plan_dev),
                               static_cast<uint8_t*>(ws), (long)rs_inter_pitch(out_w), (hipStream_t)stream))
         return fail(c, -100, "ir_resample_u8: launch failed (more than 65535 images or rows)");
+    return 0;
+}
+int ir_resample_u8_window(ir_ctx* c, void* stream, const uint8_t* in, int n, int in_h, int in_w, long in_pitch, uint8_t* out, int out_h, int out_w, int y0,
+                          int x0, int win_h, int win_w, int full_h, int full_w, long out_pitch, const void* plan_dev, void* ws, size_t ws_bytes) {
+    if (!c || !in || !out || !plan_dev) return fail(c, -1, "ir_resample_u8_window: null argument");
+    if (n < 1 || in_h < 1 || in_w < 1 || out_h < 1 || out_w < 1 || in_pitch < 3L * in_w)
+        return fail(c, -1, "ir_resample_u8_window: bad size (n %d, %d x %d pitch %ld -> %d x %d)", n, in_h, in_w, in_pitch, out_h, out_w);
+    if (y0 < 0 || x0 < 0 || win_h < 1 || win_w < 1 || y0 > out_h - win_h || x0 > out_w - win_w)
+        return fail(c, -1, "ir_resample_u8_window: the window %d x %d at (%d, %d) lies outside the %d x %d result", win_h, win_w, y0, x0, out_h, out_w);
+    if (full_h < win_h || full_w < win_w || out_pitch < 3L * full_w)
+        return fail(c, -1, "ir_resample_u8_window: bad destination (window %d x %d in %d x %d pitch %ld)", win_h, win_w, full_h, full_w, out_pitch);
+    const bool both = in_h != out_h && in_w != out_w;
+    if (both && (!ws || ws_bytes < rs_workspace(n, in_h, win_w) || (reinterpret_cast<uintptr_t>(ws) & 3)))
+        return fail(c, -1, "ir_resample_u8_window: workspace missing, too small or unaligned (%zu < %zu)", ws_bytes, rs_workspace(n, in_h, win_w));
+    if (reinterpret_cast<uintptr_t>(plan_dev) & 3) return fail(c, -1, "ir_resample_u8_window: plan not aligned to 4 bytes");
+    use_ctx(c);
+    if (ir_launch_resample_u8_window(in, n, in_h, in_w, in_pitch, out, out_h, out_w, y0, x0, win_h, win_w, full_h, full_w, out_pitch,
+                                     static_cast<const int*>(plan_dev), static_cast<uint8_t*>(ws), (long)rs_inter_pitch(win_w), (hipStream_t)stream))
+        return fail(c, -100, "ir_resample_u8_window: launch failed (more than 65535 images or rows)");
     return 0;
 }
 

@@ -283,6 +283,9 @@ int ir_launch_jpeg_decode(const ir_jpeg_file* f, int subseq_bits, uint32_t* info
 #define IR_RESAMPLE_HEADER 16
 int ir_launch_resample_u8(const uint8_t* in, int n, int in_h, int in_w, long in_pitch, uint8_t* out, int out_h, int out_w, int full_h, int full_w,
                           long out_pitch, const int* plan, uint8_t* inter, long inter_pitch, hipStream_t s);
+// rows y0 .. y0 + win_h, columns x0 .. x0 + win_w of that result alone; inter: [n][in_h][inter_pitch], win_w samples per row
+int ir_launch_resample_u8_window(const uint8_t* in, int n, int in_h, int in_w, long in_pitch, uint8_t* out, int out_h, int out_w, int y0, int x0, int win_h,
+                                 int win_w, int full_h, int full_w, long out_pitch, const int* plan, uint8_t* inter, long inter_pitch, hipStream_t s);
 
 // ---- PSNR-Y / SSIM-Y of uint8 images (metrics.hip)
 // One workgroup per IR_METRICS_TH x IR_METRICS_TW tile of the 'valid' SSIM map; part: [n][tiles][2] doubles (the tile's squared-error sum and SSIM

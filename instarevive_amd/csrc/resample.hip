@@ -10,6 +10,10 @@
 // was removed. A lane produces four consecutive bytes of an output row - the dword it stores - so a vertical lane shares one bounds
 // entry and coefficient row over its four sums and loads whole dwords of the intermediate. The second launch also zero-fills the
 // destination's padding (rows out_h .. full_h, columns out_w .. full_w): the pad to multiples of 64 of the network input.
+// ir_resample_u8_window runs the same passes for a window of the result alone (the centre crop's last step): the horizontal pass makes the
+// window's columns of the source rows the window's vertical taps reach - it reads that span from the plan's vertical bounds - and the
+// vertical pass the window's rows; a skipped pass copies from the window's first row / byte, which is on a dword boundary only by chance,
+// so the dword loads fall back to bytes there.
 // Every launch first compares the plan's header with the call's sizes and writes nothing when they differ; the table entries are clipped to
 // the source extent before they index it, so a damaged plan cannot make a lane read or write outside the buffers.
 #include "common.h"
@@ -33,6 +37,9 @@ struct Pass {
     int rows, row_bytes;        // rows / bytes per row that are written (the rest, beyond the samples: zeros)
     const int* plan;
     int in_h, in_w, out_h, out_w;   // of the whole call: what the plan's header must say
+    // the window form alone (ir_resample_u8_window; zeros otherwise): the pass produces columns x_org .. / rows y_org .. of its virtual result
+    int x_org, y_org;
+    int span_rows;        // horizontal pass ahead of a vertical one: rows y_org .. y_org + span_rows of the result decide which source rows it covers
 };
 
 IR_DEVINL uint32_t clip8(int ss) {
@@ -40,14 +47,28 @@ IR_DEVINL uint32_t clip8(int ss) {
     return (uint32_t)min(max(v, 0), 255);
 }
 
-// MODE 0: horizontal pass, 1: vertical pass, 2: copy (both passes skipped)
-template <int MODE>
+// MODE 0: horizontal pass, 1: vertical pass, 2: copy (both passes skipped). WIN: the window form - the table index of an output sample is its
+// place in the window plus the pass's origin (without WIN the origins are the constant 0 and the code is the whole-image one); the caller
+// has moved the source pointer to the window's first row / byte where the pass copies that axis.
+template <int MODE, bool WIN>
 __global__ __launch_bounds__(TPB) void resample_pass_kernel(Pass p) {
     const int* hd = p.plan;
     if (hd[0] != IR_RESAMPLE_MAGIC || hd[1] != p.in_h || hd[2] != p.in_w || hd[3] != p.out_h || hd[4] != p.out_w) return;
     const int yy = blockIdx.y, image = blockIdx.z;
     const int j0 = 4 * (blockIdx.x * TPB + threadIdx.x);
     if (j0 >= p.row_bytes || yy >= p.rows) return;
+    const int x_org = WIN ? p.x_org : 0, y_org = WIN ? p.y_org : 0;
+    if (WIN && MODE == 0 && p.span_rows > 0) {
+        // only the source rows the window's vertical taps reach (the bounds ascend with the row): first row's start .. last row's end,
+        // clipped like every table entry; the vertical pass reads no other row of the intermediate
+        const int ksv = hd[7];
+        const int* vb = hd + hd[10];
+        const int last = y_org + p.span_rows - 1;
+        const int lo = min(max(vb[2 * y_org], 0), p.in_h);
+        const int lmin = min(max(vb[2 * last], 0), p.in_h);
+        const int hi = lmin + min(min(vb[2 * last + 1], ksv), p.in_h - lmin);
+        if (yy < lo || yy >= hi) return;
+    }
     uint32_t v = 0;
     if (yy < p.valid_h && j0 < p.valid_bytes) {
         const uint8_t* simg = p.src + (long)image * p.src_img;
@@ -60,7 +81,7 @@ __global__ __launch_bounds__(TPB) void resample_pass_kernel(Pass p) {
             for (int b = 0; b < 4; ++b) {
                 const int j = j0 + b;
                 if (j < p.valid_bytes) {
-                    const int xx = j / 3, c = j - 3 * xx;
+                    const int xw = j / 3, c = j - 3 * xw, xx = xw + x_org;
                     const int xmin = min(max(bounds[2 * xx], 0), p.src_len);
                     const int xmax = min(min(bounds[2 * xx + 1], ks), p.src_len - xmin);
                     const int* k = kk + (long)xx * ks;
@@ -76,9 +97,10 @@ __global__ __launch_bounds__(TPB) void resample_pass_kernel(Pass p) {
             if (MODE == 1) {
                 ks = hd[7];
                 const int* bounds = hd + hd[10];
-                ymin = min(max(bounds[2 * yy], 0), p.src_len);
-                ymax = min(min(bounds[2 * yy + 1], ks), p.src_len - ymin);
-                k = hd + hd[11] + (long)yy * ks;
+                const int yt = yy + y_org;
+                ymin = min(max(bounds[2 * yt], 0), p.src_len);
+                ymax = min(min(bounds[2 * yt + 1], ks), p.src_len - ymin);
+                k = hd + hd[11] + (long)yt * ks;
             }
             const int half = MODE == 1 ? 1 << (PRECISION_BITS - 1) : 0;
             int s0 = half, s1 = half, s2 = half, s3 = half;
@@ -120,10 +142,10 @@ __global__ __launch_bounds__(TPB) void resample_pass_kernel(Pass p) {
     }
 }
 
-template <int MODE>
+template <int MODE, bool WIN = false>
 void launch_pass(const Pass& p, int n, hipStream_t s) {
     const dim3 grid(((p.row_bytes + 3) / 4 + TPB - 1) / TPB, p.rows, n);
-    hipLaunchKernelGGL(resample_pass_kernel<MODE>, grid, dim3(TPB), 0, s, p);
+    hipLaunchKernelGGL((resample_pass_kernel<MODE, WIN>), grid, dim3(TPB), 0, s, p);
 }
 
 inline int dword_aligned(const void* ptr, long pitch, long img) { return ((reinterpret_cast<uintptr_t>(ptr) | (uintptr_t)pitch | (uintptr_t)img) & 3) == 0; }
@@ -158,6 +180,42 @@ int ir_launch_resample_u8(const uint8_t* in, int n, int in_h, int in_w, long in_
         if (need_h) launch_pass<0>(last, n, s);
         else if (need_v) launch_pass<1>(last, n, s);
         else launch_pass<2>(last, n, s);
+    }
+    return hipGetLastError() == hipSuccess ? 0 : -1;
+}
+
+// The window form: rows y0 .. y0 + win_h, columns x0 .. x0 + win_w of the virtual out_h x out_w result, into the top-left corner of out.
+// The intermediate is [n][in_h][inter_pitch] with win_w samples per row; the horizontal pass fills only the rows the vertical taps of the window reach.
+int ir_launch_resample_u8_window(const uint8_t* in, int n, int in_h, int in_w, long in_pitch, uint8_t* out, int out_h, int out_w, int y0, int x0, int win_h,
+                                 int win_w, int full_h, int full_w, long out_pitch, const int* plan, uint8_t* inter, long inter_pitch, hipStream_t s) {
+    if (n > 65535 || in_h > 65535 || full_h > 65535) return -1;   // grid.y / grid.z
+    const bool need_h = in_w != out_w, need_v = in_h != out_h;
+    Pass p{};
+    p.plan = plan;
+    p.in_h = in_h; p.in_w = in_w; p.out_h = out_h; p.out_w = out_w;
+    Pass first = p, last = p;
+    const long in_img = (long)in_h * in_pitch;
+    last.dst = out; last.dst_pitch = out_pitch; last.dst_img = (long)full_h * out_pitch;
+    last.dst_dwords = dword_aligned(out, out_pitch, last.dst_img);
+    last.valid_h = win_h; last.valid_bytes = 3 * win_w; last.rows = full_h; last.row_bytes = 3 * full_w;
+    if (need_h && need_v) {
+        first.src = in; first.src_pitch = in_pitch; first.src_img = in_img; first.src_len = in_w;
+        first.dst = inter; first.dst_pitch = inter_pitch; first.dst_img = (long)in_h * inter_pitch; first.dst_dwords = 1;
+        first.valid_h = in_h; first.valid_bytes = 3 * win_w; first.rows = in_h; first.row_bytes = (int)inter_pitch;
+        first.x_org = x0; first.y_org = y0; first.span_rows = win_h;
+        last.src = inter; last.src_pitch = inter_pitch; last.src_img = first.dst_img; last.src_dwords = 1; last.src_cap = (int)inter_pitch;
+        last.src_len = in_h; last.y_org = y0;
+        launch_pass<0, true>(first, n, s);
+        launch_pass<1, true>(last, n, s);
+    } else if (need_h) {   // the rows are copied: the source starts at the window's first row
+        last.src = in + (long)y0 * in_pitch; last.src_pitch = in_pitch; last.src_img = in_img; last.src_len = in_w; last.x_org = x0;
+        launch_pass<0, true>(last, n, s);
+    } else {   // the columns are copied: the source starts at the window's first byte, which is on a dword boundary only by chance
+        last.src = in + 3L * x0 + (need_v ? 0 : (long)y0 * in_pitch); last.src_pitch = in_pitch; last.src_img = in_img;
+        last.src_dwords = dword_aligned(last.src, in_pitch, in_img); last.src_cap = 3 * (in_w - x0);
+        last.src_len = in_h; last.y_org = y0;
+        if (need_v) launch_pass<1, true>(last, n, s);
+        else launch_pass<2, true>(last, n, s);
     }
     return hipGetLastError() == hipSuccess ? 0 : -1;
 }

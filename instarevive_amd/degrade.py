@@ -88,9 +88,11 @@ def load_recipe(spec) -> dict:
 
 def check_flags(args) -> None:
     """--degrade runs on the device input route of --resize gpu; refuse the flags that switch that route off, by name."""
+    crop_on_gpu = getattr(args, "center_crop", "host") == "gpu"   # --center_crop gpu: the crop is made on that route too, and is what is degraded
     for flag in CONFLICTS:
-        if getattr(args, flag, None):
-            raise DegradeError(f"--degrade makes the LQ images on the device and cannot be combined with --{flag}")
+        if getattr(args, flag, None) and not (flag == "use_center_crop" and crop_on_gpu):
+            raise DegradeError(f"--degrade makes the LQ images on the device and cannot be combined with --{flag}"
+                               + (" (or give --center_crop gpu)" if flag == "use_center_crop" else ""))
 
 
 def bivariate_gaussian(K: int, sig_x: float, sig_y: float, theta: float, isotropic: bool) -> np.ndarray:

@@ -437,6 +437,9 @@ def process(model, control_imgs: List[np.ndarray], strength: float, color_fix_ty
     zero pad), and behind ir_pipeline the valid rectangle of every image that auto_resize enlarged is resampled (LANCZOS) back to its LQ size.
     Both lists then hold the FINAL images - what the command line saves: the resized result, else the valid rectangle - bit for bit what
     PIL gives around a plain call; with png their files (the rectangles are then the final sizes).
+    A job whose geometry is resample.crop_geometry() is centre-cropped on the device instead (utils.center_crop_arr's BOX halvings and bicubic
+    resize, the last step ir_resample_u8_window straight into the network input): its final image is the image_size x image_size prediction;
+    the jobs of a batch may come from files of different sizes. With degrade the crop is made first and is what is degraded.
     gt (fused form only): a list of one ground-truth image per image, HWC uint8 RGB of the image's FINAL size (the png rectangle, the final size
     of a resize job, else any top-left rectangle of the network's output). ir_metrics_y is queued behind ir_pipeline (and the LANCZOS calls; under
     graph=True behind the replay) and the call returns a triple (preds, stage1_preds, scores): scores is a pair of lists of (psnr_y, ssim_y), for

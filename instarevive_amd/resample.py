@@ -8,6 +8,10 @@ sin()) per size pair, ResizeSlot the page-locked and device buffers of decoded f
 With --degrade the decoded files are ground truth: ResizeSlot.fill() packs every file's blur kernel and noise field (degrade.Params) behind
 the images, ResizeSlot.degrade() turns them into LQ images on the device (ir_degrade) between the upload and to_network(), which then reads
 those.
+
+--center_crop gpu: crop_geometry() is the size arithmetic of utils.center_crop_arr (BOX halvings, the bicubic resize of the short edge, the
+central window). ResizeSlot runs such a geometry as a chain of ir_resample_u8 calls whose last step is ir_resample_u8_window - the window alone,
+straight into the network input; with --degrade the crop is made first and is what is degraded.
 """
 import ctypes as C
 import math
@@ -19,7 +23,7 @@ import torch
 from . import _lib as L
 from .slots import Pooled
 
-BICUBIC, LANCZOS = L.RESAMPLE_BICUBIC, L.RESAMPLE_LANCZOS
+BICUBIC, LANCZOS, BOX = L.RESAMPLE_BICUBIC, L.RESAMPLE_LANCZOS, L.RESAMPLE_BOX
 
 
 class Geometry(NamedTuple):
@@ -28,6 +32,32 @@ class Geometry(NamedTuple):
     net_hw: tuple     # (h, w) of the network input: valid_hw padded to multiples of 64
     lq_size: tuple    # (w, h) after --sr_scale: the size of the saved result
     lanczos: Optional[tuple]   # lq_size when the result is resized back to it (auto_resize enlarged the file), else None
+    # a centre crop (crop_geometry) alone sets the rest: the chain may then be longer than two, a step of equal size is skipped, and the network
+    # sees the window of valid_hw at `crop` of the last size
+    filters: tuple = ()            # the filter of every chain step (BICUBIC / BOX); empty: all BICUBIC
+    crop: Optional[tuple] = None   # (top, left) of the window in the chain's last size
+
+
+def crop_geometry(size: Tuple[int, int], sr_scale: float, image_size: int) -> Geometry:
+    """What inference.py's decode_job() with --use_center_crop (and eval_batch.py) does to the sizes of a decoded file of `size` = (w, h): the
+    --sr_scale bicubic, then utils.center_crop_arr - the same expressions in the same floating-point order (math.ceil(edge * sr_scale);
+    floor(edge * 0.5) while the short edge is at least twice the target; round(edge * (image_size / short)); the central window)."""
+    w, h = (int(v) for v in size)
+    s = int(image_size)
+    chain, filters = [], []
+    if sr_scale != 1:
+        w, h = (math.ceil(edge * sr_scale) for edge in (w, h))
+        chain.append((w, h))
+        filters.append(BICUBIC)
+    while min(w, h) >= 2 * s:
+        w, h = (int(math.floor(edge * 0.5)) for edge in (w, h))
+        chain.append((w, h))
+        filters.append(BOX)
+    scale = s / min(w, h)
+    w, h = (int(round(edge * scale)) for edge in (w, h))
+    chain.append((w, h))
+    filters.append(BICUBIC)
+    return Geometry(tuple(chain), (s, s), (s, s), (s, s), None, tuple(filters), ((h - s) // 2, (w - s) // 2))
 
 
 def job_geometry(size: Tuple[int, int], sr_scale: float, tiled: bool, tile_size: int) -> Geometry:
@@ -109,8 +139,41 @@ def resample(ctx, src: int, in_h: int, in_w: int, in_pitch: int, dst: int, out_h
                                      out_pitch, L.ptr(plan), L.ptr(ws), ws.numel() if need else 0), "ir_resample_u8")
 
 
+def window_ws_bytes(n: int, in_h: int, in_w: int, out_h: int, out_w: int, win_w: int) -> int:
+    """Workspace of one ir_resample_u8_window call: the intermediate holds win_w columns."""
+    if in_h == out_h or in_w == out_w:
+        return 0
+    return int(L.load_library().ir_workspace_bytes(None, L.STAGE_RESAMPLE, n, in_h, win_w, 0, 0, 0))
+
+
+def resample_window(ctx, src: int, in_h: int, in_w: int, in_pitch: int, dst: int, out_h: int, out_w: int, y0: int, x0: int, win_h: int, win_w: int,
+                    full_h: int, full_w: int, out_pitch: int, flt: int, n: int = 1) -> None:
+    """ir_resample_u8_window on the current stream: the window of the virtual out_h x out_w result into the top-left corner of dst."""
+    plan = Plans.of(ctx).get(in_h, in_w, out_h, out_w, flt)
+    need = window_ws_bytes(n, in_h, in_w, out_h, out_w, win_w)
+    ws = ctx.workspace(need) if need else None
+    ctx.check(ctx.lib.ir_resample_u8_window(ctx.h, ctx.stream(), C.c_void_p(src), n, in_h, in_w, in_pitch, C.c_void_p(dst), out_h, out_w, y0, x0, win_h,
+                                            win_w, full_h, full_w, out_pitch, L.ptr(plan), L.ptr(ws), ws.numel() if need else 0), "ir_resample_u8_window")
+
+
+def _crop_steps(rec: ResizeJob):
+    """[(in_h, in_w, out_h, out_w, filter)] of the calls that take rec.raw to the size the centre crop's window is cut from. A step of equal
+    size is left out (Pillow's resize to the same size copies) - but for the last one, which is the window call whatever its sizes."""
+    sizes = [tuple(rec.raw.shape[:2])] + [(th, tw) for tw, th in rec.geo.chain]
+    flts = rec.geo.filters or (BICUBIC,) * len(rec.geo.chain)
+    steps, at = [], sizes[0]
+    for k, (to, flt) in enumerate(zip(sizes[1:], flts)):
+        if to != at or k + 2 == len(sizes):
+            steps.append(at + to + (flt,))
+        at = to
+    return steps
+
+
 def _steps(rec: ResizeJob):
-    """[(in_h, in_w, out_h, out_w)] of the bicubic calls that take rec.raw to the network input (equal sizes: the padded copy)."""
+    """[(in_h, in_w, out_h, out_w)] of the bicubic calls that take rec.raw to the network input (equal sizes: the padded copy); of a centre
+    crop, the calls of _crop_steps()."""
+    if rec.geo.crop is not None:
+        return [s[:4] for s in _crop_steps(rec)]
     h, w = rec.raw.shape[:2]
     sizes = [(h, w)] + [(th, tw) for tw, th in rec.geo.chain]
     if len(sizes) == 1:
@@ -122,7 +185,11 @@ def chain_ws_bytes(records: Sequence[ResizeJob]) -> int:
     """The largest workspace any resampling call of this batch needs, ahead of and behind the network."""
     need = 0
     for rec in records:
-        for ih, iw, oh, ow in _steps(rec):
+        steps = _steps(rec)
+        if rec.geo.crop is not None:   # the last call makes the window's columns alone
+            need = max(need, window_ws_bytes(1, *steps[-1], rec.geo.valid_hw[1]))
+            steps = steps[:-1]
+        for ih, iw, oh, ow in steps:
             need = max(need, ws_bytes(1, ih, iw, oh, ow))
         if rec.geo.lanczos:
             need = max(need, ws_bytes(1, *rec.geo.valid_hw, rec.geo.lanczos[1], rec.geo.lanczos[0]))
@@ -151,9 +218,20 @@ def check_records(records: Sequence[ResizeJob]) -> Tuple[int, int, int]:
         if rec.geo.net_hw != records[0].geo.net_hw:
             raise ValueError("resize: the images of a batch must reach one network input size")
         last = rec.geo.chain[-1] if rec.geo.chain else (a.shape[1], a.shape[0])
+        if rec.geo.crop is not None:   # a centre crop: the window lies in the chain's last size and is the network input as it is
+            (top, left), (vh, vw) = rec.geo.crop, rec.geo.valid_hw
+            if (not rec.geo.chain or len(rec.geo.filters or rec.geo.chain) != len(rec.geo.chain) or rec.geo.lanczos or tuple(rec.geo.net_hw) != (vh, vw)
+                    or top < 0 or left < 0 or top + vh > last[1] or left + vw > last[0]):
+                raise ValueError("resize: the crop geometry does not hold its window")
+            continue
         if (last[1], last[0]) != tuple(rec.geo.valid_hw):
             raise ValueError("resize: the geometry does not belong to the decoded file")
     return (len(records),) + tuple(records[0].geo.net_hw)
+
+
+def _lq_shape(rec: ResizeJob) -> tuple:
+    """The shape of what ir_degrade reads and writes for a record: the decoded file, or the centre crop made of it."""
+    return tuple(rec.geo.valid_hw) + (3,) if rec.geo.crop is not None else tuple(rec.raw.shape)
 
 
 def _grown(t: Optional[torch.Tensor], nbytes: int, device=None, pinned=False) -> torch.Tensor:
@@ -166,12 +244,14 @@ def _grown(t: Optional[torch.Tensor], nbytes: int, device=None, pinned=False) ->
 class ResizeSlot(Pooled):
     """Buffers of one staging slot for batches whose images are resized on the device. Decoded files differ in size, so they get a flat
     page-locked buffer and its device copy (each file at a 256-byte boundary) instead of _Staging's fixed shape; `mid` holds the image
-    between two chained bicubic calls; d_res / h_res hold the LANCZOS results (predictions, then stage-1 images) that are downloaded or
+    between two chained calls (a pair used alternately: a centre crop's chain may be longer than two); d_crop holds the centre crops that
+    ir_degrade reads; d_res / h_res hold the LANCZOS results (predictions, then stage-1 images) that are downloaded or
     encoded in place of the network's output. All grow on demand and are reused by the next batch of the slot."""
 
     def __init__(self, ctx):
         self.ctx = ctx
-        self.h_raw = self.d_raw = self.mid = self.d_res = self.h_res = self.d_lq = self.h_lq = None
+        self.h_raw = self.d_raw = self.d_res = self.h_res = self.d_lq = self.h_lq = self.d_crop = None
+        self.mid = [None, None]
         self.h2d_done = None
         self.fresh = False
         self.offsets: List[int] = []
@@ -179,6 +259,8 @@ class ResizeSlot(Pooled):
         self.extras: List[tuple] = []   # per image the offsets of its blur kernel and noise field (or None) in h_raw / d_raw
         self.img_bytes = 0       # where the images end in h_raw / d_raw (the kernels and noise fields follow)
         self.lq_made = False
+        self.lq_offsets: List[int] = []   # where every image's LQ image (and the centre crop it is made from) lies in d_lq / d_crop
+        self.lq_bytes = 0
         self.jpeg: List[tuple] = []     # per JPEG file of the batch (a JpegSource record): its index and the offset of its compressed bytes
         self.d_info = self.h_info = None   # ir_jpeg_decode's info words of the batch, device and page-locked
 
@@ -193,7 +275,7 @@ class ResizeSlot(Pooled):
             if len({isinstance(p, D.ChainParams) for p in degrade}) > 1:
                 raise ValueError("degrade: a batch holds one kind of record (degrade.Params or degrade.ChainParams)")
             for rec, p in zip(records, degrade):
-                D.check_params(p, *rec.raw.shape[:2])
+                D.check_params(p, *_lq_shape(rec)[:2])
         if self.h2d_done is not None:
             self.h2d_done.synchronize()
             self.h2d_done = None
@@ -202,6 +284,10 @@ class ResizeSlot(Pooled):
             self.offsets.append(at)
             at += (rec.raw.size + 255) & ~255
         self.img_bytes, self.dparams, self.extras, self.lq_made = at, degrade, [], False
+        self.lq_offsets, self.lq_bytes = [], 0
+        for rec in records:   # the files' own offsets, but for centre crops: a crop may be larger than its file
+            self.lq_offsets.append(self.lq_bytes)
+            self.lq_bytes += (int(np.prod(_lq_shape(rec))) + 255) & ~255
         if degrade is not None:
             at += sum(D.extra_bytes(p) for p in degrade)
         self.jpeg = []
@@ -268,43 +354,71 @@ class ResizeSlot(Pooled):
 
     def degrade(self, records: Sequence[ResizeJob]) -> None:
         """Between upload() and to_network(), on the current stream: every decoded file (ground truth) becomes its LQ image in d_lq, at the
-        file's offset, by ir_degrade (ir_degrade_chain for ChainParams) with the parameters fill() staged. The files differ in size, so each is a call of its own."""
+        file's offset, by ir_degrade (ir_degrade_chain for ChainParams) with the parameters fill() staged. The files differ in size, so each is a call of its own.
+        A centre crop is cut first, into d_crop, and the crop is what is degraded."""
         from . import degrade as D
-        self.d_lq = _grown(self.d_lq, self.img_bytes, self.ctx.device)
+        self.d_lq = _grown(self.d_lq, self.lq_bytes, self.ctx.device)
+        if any(rec.geo.crop is not None for rec in records):
+            self.d_crop = _grown(self.d_crop, self.lq_bytes, self.ctx.device)
         base = self.d_raw.data_ptr()
-        for rec, p, o, (k_at, n_at) in zip(records, self.dparams, self.offsets, self.extras):
-            h, w = rec.raw.shape[:2]
+        for rec, p, o, lo, (k_at, n_at) in zip(records, self.dparams, self.offsets, self.lq_offsets, self.extras):
+            h, w = _lq_shape(rec)[:2]
+            src = base + o
+            if rec.geo.crop is not None:
+                src = self.d_crop.data_ptr() + lo
+                self._crop(rec, base + o, src, h, w)
             if isinstance(p, D.ChainParams):   # k_at: the offsets of the chain's kernels and fields
-                D.launch_chain_params(self.ctx, p, base + o, self.d_lq.data_ptr() + o, h, w, base, k_at)
+                D.launch_chain_params(self.ctx, p, src, self.d_lq.data_ptr() + lo, h, w, base, k_at)
                 continue
-            D.launch(self.ctx, base + o, self.d_lq.data_ptr() + o, h, 3 * w, h, w, [D.record(p, base + k_at, base + n_at if n_at is not None else None)])
+            D.launch(self.ctx, src, self.d_lq.data_ptr() + lo, h, 3 * w, h, w, [D.record(p, base + k_at, base + n_at if n_at is not None else None)])
         self.lq_made = True
 
     def download_lq(self) -> None:
         """Asynchronous D2H copy of the LQ images degrade() made, on the current stream."""
-        self.h_lq = _grown(self.h_lq, self.img_bytes, pinned=True)
-        self.h_lq[:self.img_bytes].copy_(self.d_lq[:self.img_bytes], non_blocking=True)
+        self.h_lq = _grown(self.h_lq, self.lq_bytes, pinned=True)
+        self.h_lq[:self.lq_bytes].copy_(self.d_lq[:self.lq_bytes], non_blocking=True)
 
     def host_lq(self, records: Sequence[ResizeJob]) -> List[np.ndarray]:
         """The downloaded LQ images (after the copy has completed) as arrays the caller owns."""
         host = self.h_lq.numpy()
-        return [host[o:o + rec.raw.size].reshape(rec.raw.shape).copy() for rec, o in zip(records, self.offsets)]
+        return [host[o:o + int(np.prod(_lq_shape(rec)))].reshape(_lq_shape(rec)).copy() for rec, o in zip(records, self.lq_offsets)]
 
     def to_network(self, records: Sequence[ResizeJob], d_in: torch.Tensor) -> None:
         """Per image the bicubic chain from its decoded bytes (its LQ image after degrade()) into its slot of d_in [n][h][w][3], zero padding
-        included, on the current stream."""
+        included, on the current stream. A centre crop runs its chain (_crop): the last call writes the window alone, straight into d_in."""
         n, h, w, _ = d_in.shape
-        first = self.d_lq if self.lq_made else self.d_raw
         for i, rec in enumerate(records):
+            if rec.geo.crop is not None:
+                if self.lq_made:   # the degraded crop is the network input as it is
+                    vh, vw = rec.geo.valid_hw
+                    resample(self.ctx, self.d_lq.data_ptr() + self.lq_offsets[i], vh, vw, 3 * vw, d_in[i].data_ptr(), vh, vw, h, w, 3 * w, BICUBIC)
+                else:
+                    self._crop(rec, self.d_raw.data_ptr() + self.offsets[i], d_in[i].data_ptr(), h, w)
+                continue
             steps = _steps(rec)
-            src, pitch = first.data_ptr() + self.offsets[i], 3 * rec.raw.shape[1]
+            # the LQ images have offsets of their own: they differ from the files' as soon as a centre crop shares the batch
+            src = self.d_lq.data_ptr() + self.lq_offsets[i] if self.lq_made else self.d_raw.data_ptr() + self.offsets[i]
+            pitch = 3 * rec.raw.shape[1]
             for k, (ih, iw, oh, ow) in enumerate(steps):
                 if k + 1 < len(steps):   # the uint8 image between two resizes, as the reference has one
-                    self.mid = _grown(self.mid, oh * ow * 3, self.ctx.device)
-                    resample(self.ctx, src, ih, iw, pitch, self.mid.data_ptr(), oh, ow, oh, ow, 3 * ow, BICUBIC)
-                    src, pitch = self.mid.data_ptr(), 3 * ow
+                    self.mid[0] = _grown(self.mid[0], oh * ow * 3, self.ctx.device)
+                    resample(self.ctx, src, ih, iw, pitch, self.mid[0].data_ptr(), oh, ow, oh, ow, 3 * ow, BICUBIC)
+                    src, pitch = self.mid[0].data_ptr(), 3 * ow
                 else:
                     resample(self.ctx, src, ih, iw, pitch, d_in[i].data_ptr(), oh, ow, h, w, 3 * w, BICUBIC)
+
+    def _crop(self, rec: ResizeJob, src: int, dst: int, full_h: int, full_w: int) -> None:
+        """The chain of a centre crop from the decoded file at src: the optional --sr_scale bicubic, the BOX halvings and the final bicubic,
+        uint8 images between them as Pillow has them; the last call cuts the window into the top-left corner of dst [full_h][full_w][3]."""
+        steps = _crop_steps(rec)
+        (top, left), (vh, vw), pitch = rec.geo.crop, rec.geo.valid_hw, 3 * rec.raw.shape[1]
+        for k, (ih, iw, oh, ow, flt) in enumerate(steps):
+            if k + 1 < len(steps):
+                mid = self.mid[k & 1] = _grown(self.mid[k & 1], oh * ow * 3, self.ctx.device)
+                resample(self.ctx, src, ih, iw, pitch, mid.data_ptr(), oh, ow, oh, ow, 3 * ow, flt)
+                src, pitch = mid.data_ptr(), 3 * ow
+            else:
+                resample_window(self.ctx, src, ih, iw, pitch, dst, oh, ow, top, left, vh, vw, full_h, full_w, 3 * full_w, flt)
 
     def reserve_results(self, n: int, h: int, w: int, with_stage1: bool) -> None:
         """Room for every image's result at up to the network's size (a LANCZOS target never exceeds it), before anything is queued."""
