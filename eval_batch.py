@@ -55,6 +55,9 @@ def parse_args():
     ap.add_argument("--lpips_lin", default=None, help="with --gt: LPIPS (v0.1, alex) on the GPU as a fourth CSV column and a `lpips:` average line "
                     "(inference.py --lpips_lin: the lpips linear heads, or a full lpips.LPIPS() state dict); --image_size must be at least 31")
     ap.add_argument("--lpips_alexnet", default=None, help="with --lpips_lin holding the heads alone: torchvision's AlexNet state dict")
+    ap.add_argument("--dists_model", default=None, metavar="FILE", help="with --gt (or --degrade): DISTS on the GPU as the last CSV column and a `dists:` average line "
+                    "(inference.py --dists_model: a DISTS state dict, alpha / beta with --dists_vgg, or an .npz); --image_size must be at least 16")
+    ap.add_argument("--dists_vgg", default=None, metavar="FILE", help="with --dists_model holding alpha / beta alone: torchvision's VGG-16 state dict")
     ap.add_argument("--niqe_params", default=None, help="score NIQE (no reference needed) of both output folders on the GPU (inference.py --niqe_params: "
                     "niqe_modelparameters.mat or an .npz). Works without --gt: the CSVs are then file,niqe; with --gt the column comes last. --image_size must "
                     "be at least 192 for two blocks")
@@ -112,6 +115,7 @@ def main():
     clipiqa_model = cli.load_clipiqa_model(args)
     musiq_model = cli.load_musiq_model(args)
     maniqa_model = cli.load_maniqa_model(args)
+    dists_weights = cli.load_dists_weights(args)
     noref = bool(niqe_params) or clipiqa_model is not None or musiq_model is not None or maniqa_model is not None
     recipe = geo = None
     if args.save_lq and not args.degrade:
@@ -126,7 +130,7 @@ def main():
         geo = job_geometry((args.image_size, args.image_size), 1, False, 512)   # the device input route of inference.py --resize gpu
         if geo.chain or geo.net_hw != (args.image_size, args.image_size):
             raise SystemExit("--degrade needs --image_size to be a multiple of 64 of at least 512 (the crop is the network input as it is)")
-        if not args.gt and (args.lpips_lin or noref):
+        if not args.gt and (args.lpips_lin or noref or dists_weights):
             args.gt = args.input   # the files that are degraded are the ground truth of what is restored from them
     cli.check_device(args.device)
     rank, world, local = parallel.init_distributed()
@@ -151,7 +155,7 @@ def main():
         raise SystemExit("--lpips_alexnet needs --lpips_lin (the lpips linear heads)")
     with_lpips = {"lpips": True} if args.lpips_lin else {}
     with_niqe = {**({"niqe": True} if niqe_params else {}), **({"clipiqa": True} if clipiqa_model else {}), **({"musiq": True} if musiq_model else {}),
-                 **({"maniqa": True} if maniqa_model else {}), **({"paired": bool(args.gt)} if noref else {})}
+                 **({"maniqa": True} if maniqa_model else {}), **({"paired": bool(args.gt)} if noref else {}), **({"dists": True} if dists_weights else {})}
     lookup = None
     if args.gt or noref:
         from instarevive_amd.metrics import GroundTruth, Report
@@ -161,6 +165,9 @@ def main():
         if args.lpips_lin:
             from instarevive_amd import lpips
             lpips.configure(m.model.ctx, args.lpips_lin, args.lpips_alexnet)
+        if dists_weights:
+            from instarevive_amd import dists
+            dists.configure(m.model.ctx, dists_weights)
         if clipiqa_model:
             from instarevive_amd import clipiqa
             clipiqa.configure(m.model.ctx, clipiqa_model)
@@ -232,11 +239,11 @@ def main():
                              png=whole if gpu_png else None, png_wrap=False, png_runs=args.png_runs,
                              **({"jpeg": whole, "jpeg_quality": args.jpeg_quality, "jpeg_subsampling": args.jpeg_subsampling} if gpu_jpg else {}),
                              gt=cli.in_step(truths) if lookup else None, **with_lpips, **({"niqe": niqe_params} if niqe_params else {}),
-                             **({"clipiqa": True} if clipiqa_model else {}), **({"musiq": True} if musiq_model else {}),
+                             **({"clipiqa": True} if clipiqa_model else {}), **({"musiq": True} if musiq_model else {}), **({"dists": True} if dists_weights else {}),
                              **({"maniqa": [[os.path.basename(out_name(args.output, args.input, f, ext_out)) for f in group] for group in batches]} if maniqa_model else {}),
                              **({"resize": cli.in_step(records)} if recipe or crop_gpu else {}),
                              **({"degrade": cli.in_step(dparams), "lq_sink": lq_images.append if args.save_lq else None} if recipe else {}))
-    no_score = {"niqe": 0, "clipiqa": 0, "musiq": 0, "maniqa": 0}
+    no_score = {"niqe": 0, "clipiqa": 0, "musiq": 0, "maniqa": 0, "dists": 0}
     for group, out in zip(batches, results):
         preds, stage1 = out[:2]
         if reports:
@@ -278,6 +285,8 @@ def main():
             print(f"[rank {rank}] --maniqa_model: {no_score['maniqa']} files were not scored (MANIQA needs a short side above 224 pixels)")
         if no_score["niqe"]:
             print(f"[rank {rank}] --niqe_params: {no_score['niqe']} files were not scored (NIQE needs 96 x 96 blocks and two complete feature rows)")
+        if no_score["dists"]:
+            print(f"[rank {rank}] --dists_model: {no_score['dists']} files were not scored (DISTS is scored from 16 x 16 pixels)")
 
 
 if __name__ == "__main__":

@@ -47,7 +47,8 @@ enum { IR_STAGE_SWINIR = 0, IR_STAGE_VAE_ENCODE = 1, IR_STAGE_DIT = 2, IR_STAGE_
                               (0 for a context that is not configured and for a size ir_musiq refuses) */,
        IR_STAGE_MANIQA = 22 /* ir_maniqa: n images, flags = the crops per image, tile_size = the crops one pass takes (0: one - the least
                                ir_maniqa accepts; n * crops: everything at once); depends on these and on the shape bound by
-                               ir_maniqa_configure, not on h x w (0 for a context that is not configured) */ };
+                               ir_maniqa_configure, not on h x w (0 for a context that is not configured) */,
+       IR_STAGE_DISTS = 23 /* ir_dists: n pairs, h, w = the compared rectangle; depends on the sizes alone (ctx may be NULL) */ };
 /* ir_pipeline flags */
 enum { IR_FLAG_NO_PREPROCESS = 1, IR_FLAG_TILED = 2, IR_FLAG_FIX_WAVELET = 4, IR_FLAG_FIX_ADAIN = 8,
        /* ir_pipeline only, needs ir_dit_control_configure: run the DiT step with the ControlNet-Half branch, condition latent
@@ -451,6 +452,37 @@ int ir_lpips_scale_table(float* tab768);
 int ir_lpips_configure(ir_ctx* ctx);
 int ir_lpips(ir_ctx* ctx, void* stream, const uint8_t* a, int a_rows, long a_pitch, const uint8_t* b, int b_rows, long b_pitch, int n, int h,
              int w, double* out, void* ws, size_t ws_bytes);
+
+/* DISTS (the published model and pyiqa's `dists` defaults: no resize, the image's own size, eval mode) of results against ground truth on the
+ * device; tools/evaluate_pairs.py::DISTS restates it and is the model of this call. Exact fp32 convolutions on the fp32-input MFMA (a k-ordered
+ * fmaf chain per output), fp32 L2 pooling, fp64 moments and score.
+ * ir_dists_scale_table (host only, no context): tab[c * 256 + v] = the fp32 network input of byte v in channel c, rounded step by step as the
+ * model does: x = (float)v / 255.0f, (x - mean_c) / std_c with mean (0.485, 0.456, 0.406) and std (0.229, 0.224, 0.225).
+ * ir_dists_configure binds tensors uploaded with ir_upload: `dists.c{1..13}.w` fp32 [cout][cin][3][3] and `dists.c{1..13}.b` fp32 [cout]
+ * (torchvision VGG-16's features.0 / .2 | .5 / .7 | .10 / .12 / .14 | .17 / .19 / .21 | .24 / .26 / .28: 3 -> 64 -> 64 | 128, 128 | 256 x 3 |
+ * 512 x 3 | 512 x 3, every conv 3x3 stride 1 padding 1) and `dists.alpha`, `dists.beta` fp32 [1475], and repacks them for the kernels. Returns
+ * -2 for a missing tensor or one of another size (ir_last_error names it).
+ * ir_dists compares the top-left h x w rectangle of every image of a [n][a_rows][a_pitch] with that of b [n][b_rows][b_pitch] (RGB8, addressed
+ * as ir_lpips does) and writes out[i] = the score of pair i as a double. Five stages of conv + bias + ReLU (zero padding is zero in the
+ * normalised domain); in front of stages 2 .. 5 the L2 pool sqrt(sum_taps g x^2 + 1e-12) per channel, g = (1, 2, 1) x (1, 2, 1) / 16, stride 2,
+ * zero padding 1, taps added row by row from the top-left in fp32, output ceil(H / 2) x ceil(W / 2). Six maps are compared: the raw x = v / 255
+ * (3 channels) and the ReLU output that ends each stage (64, 128, 256, 512, 512 channels), 1475 channels in this order. Per channel over the
+ * map's own pixels, in fp64 from the fp32 maps: mx, my the means, vx, vy the biased variances, cxy = mean(fx fy) - mx my,
+ * S1 = (2 mx my + 1e-6) / (mx^2 + my^2 + 1e-6), S2 = (2 cxy + 1e-6) / (vx + vy + 1e-6); the score is
+ * 1 - sum_c (alpha_c S1_c + beta_c S2_c) / (sum(alpha) + sum(beta)). Per-workgroup partial sums go through ws and are folded in a fixed order
+ * (no floating-point atomics): a pair gives the same bits on every call and at every position of a batch.
+ * moments_or_null: [n][1475][5] doubles (mx, my, vx, vy, cxy; channels in map order), or NULL.
+ * All pointers are device pointers; stream-ordered, no allocation, no host synchronisation (capturable).
+ * ws: 256-byte aligned, ir_workspace_bytes(ctx, IR_STAGE_DISTS, n, h, w, 0, 0, 0) bytes: four stage-1-sized fp32 maps per pair (two ping-pong
+ * maps of 64 x h x w floats for each of the 2 n images; every later map is smaller; no strip-mining: 4.3 GB for one 2048 x 2048 pair, 268 MB
+ * for a 512 x 512 pair) plus the moment sums (five doubles per channel and 1024 pixels of the largest map, and the 1475 x 5 moments per pair).
+ * Returns -1 (nothing launched, nothing written) for a null pointer, n < 1, h or w below 16 (a limit of this library; the definition has none),
+ * h above a_rows or b_rows, a pitch below 3 w, or a short or misaligned workspace; -14 when ir_dists_configure has not succeeded on this
+ * context. */
+int ir_dists_scale_table(float* tab768);
+int ir_dists_configure(ir_ctx* ctx);
+int ir_dists(ir_ctx* ctx, void* stream, const uint8_t* a, int a_rows, long a_pitch, const uint8_t* b, int b_rows, long b_pitch, int n, int h,
+             int w, double* out, double* moments_or_null, void* ws, size_t ws_bytes);
 
 /* The pixel work of NIQE (the no-reference metric of the reference's evaluate_img.py that is no pretrained network; pyiqa's `niqe` defaults:
  * Y of YIQ, no border crop, 96 x 96 blocks) on the device; tools/evaluate_niqe.py restates the definition in numpy fp64, down to the order of

@@ -113,6 +113,14 @@ def parse_args() -> Namespace:
                         "becomes file,psnr_y,ssim_y,lpips and the averages gain `lpips: x.xxxxx`; every scored image needs 31 x 31 pixels")
     parser.add_argument("--lpips_alexnet", type=str, default=None, help="with --lpips_lin holding the heads alone: torchvision's AlexNet state dict "
                         "(alexnet-owt-7be5be79.pth)")
+    parser.add_argument("--dists_model", type=str, default=None, metavar="FILE", help="with --gt (or --degrade): score DISTS on the GPU as well (ir_dists: VGG-16 at the "
+                        "image's own size in exact fp32, fp64 statistics; the definition of tools/evaluate_pairs.py::DISTS, i.e. pyiqa's `dists` defaults). FILE is "
+                        "one state dict in the DISTS module's names, or alpha / beta alone (DISTS_weights.pt) together with --dists_vgg, or an .npz in "
+                        "ir_dists_configure's names. The CSV gains the column `dists` and the averages `dists: x.xxxxx`, both last. Which files are scored follows "
+                        "--gt's rule; files below 16 x 16 pixels are counted as not scored. Opt-in: the thirteen convolutions at full size cost about as much as "
+                        "the network itself. Not offered with --shard_tiles")
+    parser.add_argument("--dists_vgg", type=str, default=None, metavar="FILE", help="with --dists_model holding alpha / beta alone: torchvision's VGG-16 state dict "
+                        "(vgg16-397923af.pth)")
     parser.add_argument("--niqe_params", type=str, default=None, help="score NIQE, the no-reference metric of the reference's evaluate_img.py that is no "
                         "pretrained network, on the GPU (ir_niqe_stats; the definition of tools/evaluate_niqe.py, i.e. pyiqa's defaults). FILE holds the pristine "
                         "parameters mu_prisparam [36] / cov_prisparam [36][36]: pyiqa's niqe_modelparameters.mat, or an .npz. Works without --gt: the CSV is then "
@@ -371,6 +379,27 @@ def load_maniqa_model(args: Namespace):
         return maniqa.load_model(args.maniqa_model)
     except Exception as e:   # ManiqaError is a ValueError; a file torch cannot unpickle raises its own kinds
         raise SystemExit(f"--maniqa_model {args.maniqa_model}: {e}")
+
+
+def load_dists_weights(args: Namespace):
+    """--dists_model [--dists_vgg]: the tensors ir_dists_configure binds, read before any other model is touched. The flag alone (no --gt, no
+    --degrade), with --shard_tiles, or with a file that is missing or holds anything else ends the run in one line."""
+    if not getattr(args, "dists_model", None):
+        if getattr(args, "dists_vgg", None):
+            raise SystemExit("--dists_vgg needs --dists_model (DISTS' alpha / beta)")
+        return None
+    if not (getattr(args, "gt", None) or getattr(args, "degrade", None)):
+        raise SystemExit("--dists_model scores against ground truth: give --gt (or --degrade) as well")
+    if getattr(args, "shard_tiles", False):
+        raise SystemExit("--dists_model is not offered together with --shard_tiles (the assembled frame of the tile-sharded path is not scored on the device)")
+    for flag in ("dists_model", "dists_vgg"):
+        if getattr(args, flag, None) and not os.path.isfile(getattr(args, flag)):
+            raise SystemExit(f"--{flag} {getattr(args, flag)}: no such file")
+    from instarevive_amd import dists
+    try:
+        return dists.load_weights(args.dists_model, args.dists_vgg)
+    except Exception as e:   # KeyError / ValueError of the loader; a file torch cannot unpickle raises its own kinds
+        raise SystemExit(f"--dists_model {args.dists_model}: {e}")
 
 
 def check_device(device: str) -> str:
@@ -645,6 +674,7 @@ def main() -> None:
     clipiqa_model = load_clipiqa_model(args)
     musiq_model = load_musiq_model(args)
     maniqa_model = load_maniqa_model(args)
+    dists_weights = load_dists_weights(args)
     noref = bool(niqe_params) or clipiqa_model is not None or musiq_model is not None or maniqa_model is not None
     if args.save_lq and not args.degrade:
         raise SystemExit("--save_lq writes the images --degrade synthesises: give --degrade as well")
@@ -658,7 +688,7 @@ def main() -> None:
         if args.resize != "gpu":
             print(f"--degrade: the LQ images are made on the device, switching --resize gpu on")
             args.resize = "gpu"
-        if not args.gt and (args.metrics_out or args.lpips_lin or noref):
+        if not args.gt and (args.metrics_out or args.lpips_lin or noref or dists_weights):
             args.gt = args.input   # the files that are degraded are the ground truth of what is restored from them
     torch.manual_seed(args.seed)  # the path is deterministic; kept for surface compatibility (pl.seed_everything)
     args.device = check_device(args.device)
@@ -696,7 +726,11 @@ def main() -> None:
             args.gt_lookup = GroundTruth(args.gt, args.input)
         report = Report(args.metrics_out or os.path.join(args.output, "metrics.csv" if world == 1 else f"metrics.rank{rank}.csv"),
                         **({"lpips": True} if args.lpips_lin else {}), **({"niqe": True} if niqe_params else {}), **({"clipiqa": True} if clipiqa_model else {}),
-                        **({"musiq": True} if musiq_model else {}), **({"maniqa": True} if maniqa_model else {}), **({"paired": bool(args.gt)} if noref else {}))
+                        **({"musiq": True} if musiq_model else {}), **({"maniqa": True} if maniqa_model else {}), **({"paired": bool(args.gt)} if noref else {}),
+                        **({"dists": True} if dists_weights else {}))
+        if dists_weights:
+            from instarevive_amd import dists
+            dists.configure(m.model.ctx, dists_weights)
         if args.lpips_lin:
             from instarevive_amd import lpips
             lpips.configure(m.model.ctx, args.lpips_lin, args.lpips_alexnet)
@@ -802,7 +836,7 @@ def main() -> None:
     first = None    # (time, files) when the first result left the GPU: what follows is the steady state (no library / workspace warm-up in it)
     unscored = 0    # --gt / --niqe_params / --clipiqa_model / --musiq_model / --maniqa_model: files whose saved image is not the device's image
     # files below 96 pixels on an edge or without two complete feature rows; files below 32 pixels on an edge; files of which a resized side rounds to 0
-    no_score = {"niqe": 0, "clipiqa": 0, "musiq": 0, "maniqa": 0}   # maniqa: files with a short side of 224 or less
+    no_score = {"niqe": 0, "clipiqa": 0, "musiq": 0, "maniqa": 0, "dists": 0}   # maniqa: files with a short side of 224 or less; dists: files below 16 x 16
     for out in process_stream(m.model, feed(), tiled=args.tiled, return_stage1=args.show_lq and not args.disable_preprocess_model,
                               fp8=args.fp8 != "off", png=in_step(rects) if gpu_png else None, png_wrap=False, png_runs=args.png_runs,
                               **({"jpeg": in_step(rects), "jpeg_quality": args.jpeg_quality, "jpeg_subsampling": args.jpeg_subsampling} if gpu_jpg else {}),
@@ -810,6 +844,7 @@ def main() -> None:
                               **({"lpips": True} if report and report.lpips else {}),
                               **({"niqe": niqe_params} if niqe_params else {}), **({"clipiqa": True} if clipiqa_model else {}),
                               **({"musiq": True} if musiq_model else {}), **({"maniqa": in_step(names)} if maniqa_model else {}),
+                              **({"dists": True} if dists_weights else {}),
                               **({"niqe_rects": in_step(sizes)} if noref else {}),
                               **({"degrade": in_step(dparams), "lq_sink": lq_images.append if args.save_lq else None} if args.degrade else {}), **common):
         preds, stage1 = out[:2]
@@ -860,6 +895,8 @@ def main() -> None:
             print(f"[rank {rank}] --musiq_model: {no_score['musiq']} of {pools.written} files were not scored (a resized side rounds to 0)")
         if no_score["maniqa"]:
             print(f"[rank {rank}] --maniqa_model: {no_score['maniqa']} of {pools.written} files were not scored (MANIQA needs a short side above 224 pixels)")
+        if no_score["dists"]:
+            print(f"[rank {rank}] --dists_model: {no_score['dists']} of {pools.written} files were not scored (DISTS is scored from 16 x 16 pixels)")
         if unscored:
             print(f"[rank {rank}] {what}: {unscored} of {pools.written} files were not scored (their saved image is not the device's image: an input the host "
                   f"enlarged, or --show_lq) - use --resize gpu")

@@ -1,4 +1,4 @@
-// The image tools of the C ABI: PNG and JPEG encoding, Pillow's resampling, PSNR-Y / SSIM-Y, LPIPS, CLIP-IQA, MUSIQ, MANIQA, NIQE and the two degradation paths. Each entry
+// The image tools of the C ABI: PNG and JPEG encoding, Pillow's resampling, PSNR-Y / SSIM-Y, LPIPS, DISTS, CLIP-IQA, MUSIQ, MANIQA, NIQE and the two degradation paths. Each entry
 // point checks its arguments and launches the kernels of its own .hip file; none of them runs a model stage, takes the workspace arena or is
 // profiled, so nothing here knows api.cpp's Run. Host code only, except for the tables the kernels read, which are computed here once.
 #include <math.h>
@@ -420,6 +420,78 @@ int ir_lpips(ir_ctx* c, void* stream, const uint8_t* a, int a_rows, long a_pitch
     use_ctx(c);
     if (ir_launch_lpips(a, a_rows, a_pitch, b, b_rows, b_pitch, n, h, w, c->lpips.tab, c->lpips.w, c->lpips.b, c->lpips.lin, ws, out, (hipStream_t)stream))
         return fail(c, -100, "ir_lpips: launch failed");
+    return 0;
+}
+
+// ---------------------------------------------------------------- DISTS (dists.hip)
+int ir_dists_scale_table(float* tab) {
+    if (!tab) return -1;
+    static const float mean[3] = {0.485f, 0.456f, 0.406f}, std3[3] = {0.229f, 0.224f, 0.225f};
+    for (int ch = 0; ch < 3; ++ch)
+        for (int v = 0; v < 256; ++v) {   // every step rounded to fp32, in the model's order
+            volatile float x = (float)v / 255.0f;
+            volatile float u = x - mean[ch];
+            tab[256 * ch + v] = u / std3[ch];
+        }
+    return 0;
+}
+
+int ir_dists_configure(ir_ctx* c) {
+    if (!c) return -1;
+    static const int width[IR_DISTS_CONVS + 1] = {3, 64, 64, 128, 128, 256, 256, 256, 512, 512, 512, 512, 512, 512};   // conv k: width[k] -> width[k + 1]
+    HIPOK(c, hipSetDevice(c->device));
+    c->dists.ok = false;
+    IrDistsModel m;
+    const char* const who = "ir_dists_configure";
+    const float* src[IR_DISTS_CONVS];
+    for (int k = 0; k < IR_DISTS_CONVS; ++k)   // every tensor is looked up before anything is replaced
+        if (!(src[k] = exact_f32(c, who, "VGG-16's", fmt("dists.c%d.w", k + 1), (size_t)width[k + 1] * width[k] * 9)) ||
+            !(m.b[k] = exact_f32(c, who, "VGG-16's", fmt("dists.c%d.b", k + 1), (size_t)width[k + 1])))
+            return -2;
+    if (!(m.alpha = exact_f32(c, who, "DISTS'", "dists.alpha", IR_DISTS_CHANNELS)) || !(m.beta = exact_f32(c, who, "DISTS'", "dists.beta", IR_DISTS_CHANNELS))) return -2;
+    std::vector<void*>& own = c->own[OWN_DISTS];
+    release_list(own);
+    HIPOK(c, hipDeviceSynchronize());
+    float tab[3 * 256], x01[256];
+    ir_dists_scale_table(tab);
+    for (int v = 0; v < 256; ++v) x01[v] = (float)v / 255.0f;
+    if (int e = own_copy(c, own, tab, sizeof tab, hipMemcpyHostToDevice, &m.tab)) return e;
+    if (int e = own_copy(c, own, x01, sizeof x01, hipMemcpyHostToDevice, &m.x01)) return e;
+    for (int k = 0; k < IR_DISTS_CONVS; ++k) {
+        std::vector<float> t;
+        if (int e = repacked_conv(c, src[k], width[k], width[k + 1], 3, t)) return e;
+        if (int e = own_copy(c, own, t.data(), t.size() * 4, hipMemcpyHostToDevice, &m.w[k])) return e;
+        if (int e = own_copy(c, own, m.b[k], (size_t)width[k + 1] * 4, hipMemcpyDeviceToDevice, &m.b[k])) return e;   // a copy: later uploads do not reach the binding
+    }
+    std::vector<float> ab(2 * IR_DISTS_CHANNELS);
+    HIPOK(c, hipMemcpy(ab.data(), m.alpha, IR_DISTS_CHANNELS * 4, hipMemcpyDeviceToHost));
+    HIPOK(c, hipMemcpy(ab.data() + IR_DISTS_CHANNELS, m.beta, IR_DISTS_CHANNELS * 4, hipMemcpyDeviceToHost));
+    double sa = 0.0, sb = 0.0;
+    for (int i = 0; i < IR_DISTS_CHANNELS; ++i) {
+        sa += (double)ab[i];
+        sb += (double)ab[IR_DISTS_CHANNELS + i];
+    }
+    m.wsum = sa + sb;
+    if (int e = own_copy(c, own, ab.data(), IR_DISTS_CHANNELS * 4, hipMemcpyHostToDevice, &m.alpha)) return e;
+    if (int e = own_copy(c, own, ab.data() + IR_DISTS_CHANNELS, IR_DISTS_CHANNELS * 4, hipMemcpyHostToDevice, &m.beta)) return e;
+    m.ok = true;
+    c->dists = m;
+    ++c->generation;
+    return 0;
+}
+
+int ir_dists(ir_ctx* c, void* stream, const uint8_t* a, int a_rows, long a_pitch, const uint8_t* b, int b_rows, long b_pitch, int n, int h, int w,
+             double* out, double* moments, void* ws, size_t ws_bytes) {
+    if (!c || !a || !b || !out || !ws) return fail(c, -1, "ir_dists: null argument");
+    if (int e = check_rect(c, "ir_dists", "this library scores DISTS from 16 x 16", n, h, w, IR_DISTS_MIN_EDGE, {{a_rows, a_pitch}, {b_rows, b_pitch}})) return e;
+    IrDistsPlan pl;
+    if (ir_dists_plan(n, h, w, &pl)) return fail(c, -1, "ir_dists: n %d of %d x %d is more than one call takes (2^31 pixels, 65535 pairs)", n, h, w);
+    if (int e = check_ws(c, "ir_dists", ws, ws_bytes, pl.total, 256)) return e;
+    if (int e = check_out8(c, "ir_dists", out)) return e;
+    if (int e = check_out8(c, "ir_dists", moments)) return e;
+    if (!c->dists.ok) return fail(c, -14, "ir_dists: DISTS not configured (ir_dists_configure)");
+    use_ctx(c);
+    if (ir_launch_dists(c->dists, a, a_rows, a_pitch, b, b_rows, b_pitch, n, h, w, ws, out, moments, (hipStream_t)stream)) return fail(c, -100, "ir_dists: launch failed");
     return 0;
 }
 
@@ -964,6 +1036,7 @@ bool ir_host::image_workspace(ir_ctx* c, int stage, int n, int h, int w, int fla
     IrMusiqPlan mp;
     IrManiqaPlan qp;
     IrLpipsPlan lp;
+    IrDistsPlan dp;
     IrJpegLayout jl;
     *bytes = 0;
     switch (stage) {
@@ -976,6 +1049,7 @@ bool ir_host::image_workspace(ir_ctx* c, int stage, int n, int h, int w, int fla
             if (c && c->maniqa.ok && !ir_maniqa_plan(c->maniqa, n, flags, std::max(tile_size, 1), &qp)) *bytes = qp.total;
             break;
         case IR_STAGE_LPIPS: if (!ir_lpips_plan(n, h, w, &lp)) *bytes = lp.total; break;
+        case IR_STAGE_DISTS: if (!ir_dists_plan(n, h, w, &dp)) *bytes = dp.total; break;
         case IR_STAGE_METRICS: if (some) *bytes = metrics_workspace(n, h, w); break;
         case IR_STAGE_JPEG: if (ir_jpeg_layout(n, h, w, flags, tile_size, &jl)) *bytes = jl.total; break;   // flags: the subsampling, tile_size: restart_mcus
         case IR_STAGE_JPEG_DECODE: if (n >= 1) *bytes = ir_jpeg_decode_workspace(h, w, (uint32_t)flags, tile_size); break;   // flags: stream_bytes, tile_size: subseq_bits

@@ -308,6 +308,31 @@ int ir_lpips_plan(int n, int h, int w, IrLpipsPlan* plan);
 int ir_launch_lpips(const uint8_t* a, int a_rows, long a_pitch, const uint8_t* b, int b_rows, long b_pitch, int n, int h, int w, const float* tab,
                     const float* const* wgt, const float* const* bias, const float* const* lin, void* ws, double* out, hipStream_t s);
 
+// ---- DISTS of uint8 image pairs (dists.hip)
+#define IR_DISTS_CONVS 13
+#define IR_DISTS_MAPS 6          // the raw image and the five stage outputs
+#define IR_DISTS_CHANNELS 1475   // 3 + 64 + 128 + 256 + 512 + 512
+#define IR_DISTS_MIN_EDGE 16
+// tab: [3][256] fp32 network input of a byte, x01: [256] fp32 (float)v / 255.0f, w[k]: [K padded to 32][cout] fp32 with K in (ky, kx, c) order,
+// b[k]: [cout], alpha / beta: [1475] in map order, wsum: sum(alpha) + sum(beta) in fp64
+struct IrDistsModel {
+    bool ok = false;
+    const float *tab = nullptr, *x01 = nullptr, *w[IR_DISTS_CONVS] = {}, *b[IR_DISTS_CONVS] = {}, *alpha = nullptr, *beta = nullptr;
+    double wsum = 0.0;
+};
+// ir_dists_plan: the map sizes of a call (mh x mw: [0] the image, [k] stage k's output, ceil halves) and its workspace: two ping-pong NHWC fp32
+// maps of 64 x h x w floats for each of the 2n images (every later map is smaller), the moment kernel's partial sums of the largest map
+// ([n][chunks][C][5] doubles, chunks[k] = the 1024-pixel chunks of map k) and the folded moments [n][1475][5] doubles. -1 below 16 x 16 or when a
+// row count leaves an int.
+struct IrDistsPlan {
+    int mh[IR_DISTS_MAPS], mw[IR_DISTS_MAPS], chunks[IR_DISTS_MAPS];
+    size_t map_bytes, part_bytes, mom_bytes, total;
+};
+int ir_dists_plan(int n, int h, int w, IrDistsPlan* plan);
+// out: [n] doubles; moments: [n][1475][5] doubles (mx, my, vx, vy, cxy) or null (they then stay in the workspace)
+int ir_launch_dists(const IrDistsModel& m, const uint8_t* a, int a_rows, long a_pitch, const uint8_t* b, int b_rows, long b_pitch, int n, int h, int w, void* ws,
+                    double* out, double* moments, hipStream_t s);
+
 // ---- NIQE's block statistics of uint8 images (niqe.hip)
 // One workgroup per IR_NIQE_BLOCK x IR_NIQE_BLOCK block of the top-left (h / 96 * 96) x (w / 96 * 96) rectangle. tab: four 256-entry fp64 tables in
 // device memory - coef_c * (double)((float)v / 255.0f) for 0.299 / 0.587 / 0.114, then v / 255.0; half: [n][H / 2][W / 2] doubles (the half-size

@@ -95,25 +95,29 @@ class ScoreSlot(Pooled):
     [count][2] (mse_y, ssim_y) with their page-locked twin. All grow on demand and are reused by the next batch of the slot. A batch filled with
     lpips=True is scored by ir_lpips as well (lpips.py; the context's LPIPS weights must be bound): one more double per row, and scores()
     yields (psnr_y, ssim_y, lpips) in place of pairs. A row is an image of the batch: the predictions first, then - filled with copies=2 - the
-    stage-1 images, scored against the same ground truth."""
+    stage-1 images, scored against the same ground truth. A batch filled with dists=True is scored by ir_dists as well (dists.py; the context's
+    DISTS weights must be bound), queued behind ir_lpips for the same images: one more double per row, which dists_values() yields - DISTS is the
+    last value of a score tuple, behind the no-reference scorers', so DistsColumn hands it over there. A pair below 16 pixels on an edge has no
+    DISTS on the device: its value is NaN."""
 
     def __init__(self, ctx):
         self.ctx = ctx
         self.h_gt = self.d_gt = None
         self.d_scores = self.h_scores = None
         self.d_lpips = self.h_lpips = None
-        self.lpips = False
+        self.d_dists = self.h_dists = None
+        self.lpips = self.dists = False
         self.h2d_done = None
         self.fresh = False
         self.offsets: List[int] = []
         self.shapes: List[Tuple[int, int]] = []
         self.used = self.rows = 0
 
-    def fill(self, gts: Sequence[np.ndarray], lpips: bool = False, copies: int = 1) -> None:
+    def fill(self, gts: Sequence[np.ndarray], lpips: bool = False, copies: int = 1, dists: bool = False) -> None:
         """Copy the ground-truth images into the page-locked buffer (after the previous upload out of it has completed). copies: 2 when the
         stage-1 images are scored as well."""
         from .resample import _grown
-        self.lpips, self.rows = bool(lpips), copies * len(gts)
+        self.lpips, self.dists, self.rows = bool(lpips), bool(dists), copies * len(gts)
         if self.h2d_done is not None:
             self.h2d_done.synchronize()
             self.h2d_done = None
@@ -137,6 +141,10 @@ class ScoreSlot(Pooled):
             cap = max(2 * len(gts), 16)
             self.d_lpips = torch.zeros((cap,), dtype=torch.float64, device=self.ctx.device)
             self.h_lpips = torch.zeros((cap,), dtype=torch.float64).pin_memory()
+        if self.dists and (self.d_dists is None or self.d_dists.shape[0] < 2 * len(gts)):
+            cap = max(2 * len(gts), 16)
+            self.d_dists = torch.zeros((cap,), dtype=torch.float64, device=self.ctx.device)
+            self.h_dists = torch.zeros((cap,), dtype=torch.float64).pin_memory()
 
     def upload(self, stream=None, owner=None):
         """Asynchronous H2D copy of the ground truth on `stream` (default: the current one); stream / owner as in ResizeSlot.upload."""
@@ -157,6 +165,9 @@ class ScoreSlot(Pooled):
         if self.lpips:
             from . import lpips
             lpips.workspace(self.ctx, max(lpips.ws_bytes(n, h, w) for h, w in self.shapes))
+        if self.dists:
+            from . import dists
+            dists.workspace(self.ctx, max(dists.ws_bytes(n, h, w) for h, w in self.shapes))   # 0 for a size below 16 x 16
 
     def queue(self, first: int, images: torch.Tensor, results: Optional[Sequence[Optional[torch.Tensor]]] = None) -> None:
         """Score the images [n][h][w][3] (device uint8: the network's output) against the slot's ground truth into score rows first .. first + n - 1,
@@ -171,12 +182,20 @@ class ScoreSlot(Pooled):
             if self.lpips:
                 from .lpips import queue_lpips
                 queue_lpips(self.ctx, a, a_rows, a_pitch, b, gh, 3 * gw, k - i, gh, gw, self.d_lpips[out])
+            if self.dists:
+                from .dists import MIN_EDGE, queue_dists
+                if min(gh, gw) < MIN_EDGE:
+                    self.d_dists[out].fill_(float("nan"))
+                else:
+                    queue_dists(self.ctx, a, a_rows, a_pitch, b, gh, 3 * gw, k - i, gh, gw, self.d_dists[out])
 
     def download(self) -> None:
         """Asynchronous D2H copy of the batch's score rows on the current stream."""
         self.h_scores[:self.rows].copy_(self.d_scores[:self.rows], non_blocking=True)
         if self.lpips:
             self.h_lpips[:self.rows].copy_(self.d_lpips[:self.rows], non_blocking=True)
+        if self.dists:
+            self.h_dists[:self.rows].copy_(self.d_dists[:self.rows], non_blocking=True)
 
     def scores(self, first: int, count: int) -> List[Tuple[float, ...]]:
         """(psnr_y, ssim_y) of rows first .. first + count - 1 after the download has completed; (psnr_y, ssim_y, lpips) for a batch filled with
@@ -185,6 +204,30 @@ class ScoreSlot(Pooled):
         if not self.lpips:
             return pairs
         return [p + (float(v),) for p, v in zip(pairs, self.h_lpips[first:first + count].tolist())]
+
+    def dists_values(self, first: int, count: int) -> List[float]:
+        """DISTS of rows first .. first + count - 1 of a batch filled with dists=True, after the download has completed."""
+        return [float(v) for v in self.h_dists[first:first + count].tolist()]
+
+
+class DistsColumn:
+    """The place of DISTS in a score tuple: the last one, behind the no-reference scorers'. The values are ScoreSlot's (it queues ir_dists with
+    its own calls and downloads them with its own rows); this object only stands where they are read."""
+
+    def __init__(self, slot: ScoreSlot):
+        self.slot = slot
+
+    def reserve(self) -> None:
+        pass
+
+    def queue(self, first, images, results=None) -> None:
+        pass
+
+    def download(self) -> None:
+        pass
+
+    def scores(self, first: int, count: int) -> List[Tuple[float]]:
+        return [(v,) for v in self.slot.dists_values(first, count)]
 
 
 class GroundTruth:
@@ -238,25 +281,30 @@ class Report:
     key), musiq=True appends MUSIQ (musiq.py) behind that (`musiq: %.5f`), maniqa=True MANIQA (maniqa.py) behind that (`maniqa: %.5f`). The
     full column order is `file,psnr_y,ssim_y,lpips,niqe,clipiqa,musiq,maniqa`; absent metrics are left out. paired=False (a run without ground truth) carries the
     no-reference columns alone: `file,niqe`, `file,clipiqa`, `file,musiq`, `file,maniqa`, `file,niqe,clipiqa` and so on. HEADERS lists
-    the headers without the MANIQA column, HEADERS_MANIQA those with it."""
+    the headers without the MANIQA column, HEADERS_MANIQA those with it. dists=True (a paired report only) appends DISTS (dists.py) as the very
+    last column and average line (`dists: %.5f`): the full order ends `...,musiq,maniqa,dists`; HEADERS_DISTS lists those headers."""
     HEADER = "file,psnr_y,ssim_y"
     HEADER_LPIPS = HEADER + ",lpips"
     HEADER_NIQE = "file,niqe"
     HEADERS = tuple(p + n + c + m for p in (HEADER, HEADER_LPIPS, "file") for n in ("", ",niqe") for c in ("", ",clipiqa") for m in ("", ",musiq")
                     if p != "file" or n or c or m)
     HEADERS_MANIQA = tuple(h + ",maniqa" for h in HEADERS + ("file",))
+    HEADERS_DISTS = tuple(h + ",dists" for h in HEADERS + HEADERS_MANIQA if h.startswith("file,psnr_y,ssim_y"))
 
     def __init__(self, path: Optional[str] = None, lpips: bool = False, niqe: bool = False, paired: bool = True, clipiqa: bool = False,
-                 musiq: bool = False, maniqa: bool = False):
+                 musiq: bool = False, maniqa: bool = False, dists: bool = False):
         self.path, self.rows, self.lpips, self.niqe, self.paired, self.clipiqa = path, [], bool(lpips), bool(niqe), bool(paired), bool(clipiqa)
-        self.musiq, self.maniqa = bool(musiq), bool(maniqa)
+        self.musiq, self.maniqa, self.dists = bool(musiq), bool(maniqa), bool(dists)
+        if self.dists and not self.paired:
+            raise MetricsError("Report: DISTS is a paired score; a report without paired scores cannot carry it")
         if not self.paired and (self.lpips or not (self.niqe or self.clipiqa or self.musiq or self.maniqa)):
             raise MetricsError("Report: a report without paired scores carries NIQE, CLIP-IQA, MUSIQ and / or MANIQA and nothing else")
         self.keys = ((("psnr", "ssim") + (("lpips",) if self.lpips else ()) if self.paired else ()) + (("niqe",) if self.niqe else ())
-                     + (("clipiqa",) if self.clipiqa else ()) + (("musiq",) if self.musiq else ()) + (("maniqa",) if self.maniqa else ()))
+                     + (("clipiqa",) if self.clipiqa else ()) + (("musiq",) if self.musiq else ()) + (("maniqa",) if self.maniqa else ())
+                     + (("dists",) if self.dists else ()))
 
     def add(self, name: str, psnr: Optional[float] = None, ssim: Optional[float] = None, lpips: Optional[float] = None, niqe: Optional[float] = None,
-            clipiqa: Optional[float] = None, musiq: Optional[float] = None, maniqa: Optional[float] = None) -> None:
+            clipiqa: Optional[float] = None, musiq: Optional[float] = None, maniqa: Optional[float] = None, dists: Optional[float] = None) -> None:
         if (lpips is not None) != self.lpips:
             raise MetricsError("Report.add: an LPIPS value is needed by a report made with lpips=True and by no other")
         if (niqe is not None) != self.niqe:
@@ -267,9 +315,11 @@ class Report:
             raise MetricsError("Report.add: a MUSIQ value is needed by a report made with musiq=True and by no other")
         if (maniqa is not None) != self.maniqa:
             raise MetricsError("Report.add: a MANIQA value is needed by a report made with maniqa=True and by no other")
+        if (dists is not None) != self.dists:
+            raise MetricsError("Report.add: a DISTS value is needed by a report made with dists=True and by no other")
         if (psnr is not None) != self.paired or (ssim is not None) != self.paired:
             raise MetricsError("Report.add: PSNR and SSIM are needed by a report with paired scores and by no other")
-        given = dict(psnr=psnr, ssim=ssim, lpips=lpips, niqe=niqe, clipiqa=clipiqa, musiq=musiq, maniqa=maniqa)
+        given = dict(psnr=psnr, ssim=ssim, lpips=lpips, niqe=niqe, clipiqa=clipiqa, musiq=musiq, maniqa=maniqa, dists=dists)
         self.rows.append((str(name),) + tuple(float(given[k]) for k in self.keys))
 
     def add_scores(self, name: str, scores: Sequence[float]) -> None:
@@ -280,8 +330,9 @@ class Report:
 
     def unscored(self, scores: Sequence[float]) -> Optional[str]:
         """For a score tuple in the report's own column order: the no-reference column whose value is NaN - the image has no such score -
-        "niqe" before "clipiqa" before "musiq" before "maniqa"; None when the tuple can be added."""
-        for k in ("niqe", "clipiqa", "musiq", "maniqa"):
+        "niqe" before "clipiqa" before "musiq" before "maniqa" - or "dists" behind them (a pair below 16 pixels on an edge); None when the tuple
+        can be added."""
+        for k in ("niqe", "clipiqa", "musiq", "maniqa", "dists"):
             if k in self.keys and scores[self.keys.index(k)] != scores[self.keys.index(k)]:
                 return k
         return None
@@ -317,10 +368,10 @@ class Report:
 
 def read_report(path: str) -> dict:
     """{file: (psnr_y, ssim_y)} of a CSV that Report wrote; {file: (psnr_y, ssim_y, lpips)} of one with the LPIPS column; with the NIQE column
-    that value follows, with the CLIP-IQA, MUSIQ and MANIQA columns those values come last; a `file,niqe` report gives {file: (niqe,)}."""
+    that value follows, with the CLIP-IQA, MUSIQ and MANIQA columns those values follow, with the DISTS column that value comes last; a `file,niqe` report gives {file: (niqe,)}."""
     import csv
     with open(path, newline="") as f:
         rows = list(csv.reader(f))
-    if not rows or ",".join(rows[0]) not in Report.HEADERS + Report.HEADERS_MANIQA:
+    if not rows or ",".join(rows[0]) not in Report.HEADERS + Report.HEADERS_MANIQA + Report.HEADERS_DISTS:
         raise MetricsError(f"{path}: not a metrics report")
     return {r[0]: tuple(float(v) for v in r[1:len(rows[0])]) for r in rows[1:]}

@@ -229,11 +229,12 @@ class _Batch:
     two streams and keeps the batch's events in `ready` (its uploads) and `done` (its downloads)."""
 
     def __init__(self, ctx, slot, tag, slots, shape, imgs, with_stage1, rects=None, records=None, dparams=None, gts=None, lpips=False, niqe=None,
-                 clipiqa=False, sizes=None, want_lq=False, prompts=(None, None), codec=None, png_runs=False, musiq=False, maniqa=False):
+                 clipiqa=False, sizes=None, want_lq=False, prompts=(None, None), codec=None, png_runs=False, musiq=False, maniqa=False, dists=False):
         """The plan phase, host work only: every size is checked and every ground truth compared with its image's FINAL size, so a batch that
         does not fit raises ValueError before anything is launched for it; then the scorer slots are filled / planned - `scorers` holds them in
         the order of a score tuple: paired (metrics.ScoreSlot; with lpips it scores LPIPS as well, ir_lpips with the weights lpips.configure()
-        bound to the context), NIQE with `niqe` its parameters, CLIP-IQA, MUSIQ, MANIQA (maniqa: True, or the images' names, which key random crops) - and the images copied into page-locked memory: the staging input, or
+        bound to the context), NIQE with `niqe` its parameters, CLIP-IQA, MUSIQ, MANIQA (maniqa: True, or the images' names, which key random crops), and last DISTS (dists: ir_dists with the weights dists.configure() bound to the context; the paired slot queues it, metrics.DistsColumn
+        stands where its value is read) - and the images copied into page-locked memory: the staging input, or
         the decoded files (with their degrade parameters) into the ResizeSlot, whose bicubic chain then makes the staging input on the device.
         sizes: the batch's niqe_rects entry. codec: None - rects are coded as PNG, in the run mode with png_runs - or _jpeg_codec()'s pair."""
         from .slots import final_sizes, record_sizes
@@ -255,7 +256,11 @@ class _Batch:
                 min_edge = MIN_EDGE
             final_sizes("gt", n, h, w, records, rects, gts=gts, min_edge=min_edge)
             self.sc = ScoreSlot.get(ctx, slot, tag)
-            self.sc.fill(gts, lpips, copies)
+            if dists:
+                from .dists import configured as dists_configured
+                if not dists_configured(ctx):
+                    raise ValueError("dists=True: no DISTS weights are bound to the context (instarevive_amd.dists.configure)")
+            self.sc.fill(gts, lpips, copies, dists=bool(dists))
             self.scorers.append(self.sc)
         if niqe is not None or clipiqa or musiq or maniqa:
             finals = final_sizes("niqe" if niqe is not None else "clipiqa" if clipiqa else "musiq" if musiq else "maniqa", n, h, w, records, rects, sizes, gts)
@@ -275,6 +280,9 @@ class _Batch:
                 from .maniqa import ManiqaSlot
                 self.scorers.append(ManiqaSlot.get(ctx, slot, tag))
                 self.scorers[-1].plan(finals, copies, None if maniqa is True else list(maniqa))
+        if gts is not None and dists:
+            from .metrics import DistsColumn
+            self.scorers.append(DistsColumn(self.sc))
         if rects is not None:
             if records is None and len(rects) != n:
                 raise ValueError(f"{'png' if codec is None else 'jpeg'}: {len(rects)} rectangles for a batch of {n} images")
@@ -411,7 +419,7 @@ def process(model, control_imgs: List[np.ndarray], strength: float, color_fix_ty
             tile_size: int, tile_stride: int, preprocess_model=None, vae=None, y=None, y_mask=None, noise_scheduler=None,
             fused: bool = True, graph: bool = False, return_stage1: bool = True, fp8: bool = False, png=None,
             resize=None, gt=None, lpips: bool = False, niqe=None, niqe_rects=None, clipiqa: bool = False, degrade=None,
-            lq_sink=None, jpeg=None, jpeg_quality: int = 95, jpeg_subsampling=2, png_runs: bool = False, musiq: bool = False, maniqa=False) -> Tuple[List[np.ndarray], List[np.ndarray]]:
+            lq_sink=None, jpeg=None, jpeg_quality: int = 95, jpeg_subsampling=2, png_runs: bool = False, musiq: bool = False, maniqa=False, dists: bool = False) -> Tuple[List[np.ndarray], List[np.ndarray]]:
     """test_scripts/inference.py:55-166. control_imgs: list of HWC uint8 RGB arrays of equal size (multiples of 64).
     Returns (preds, stage1_preds) as lists of HWC uint8 arrays (stage1_preds is empty with return_stage1=False, which skips its
     conversion and download).
@@ -462,6 +470,8 @@ def process(model, control_imgs: List[np.ndarray], strength: float, color_fix_ty
     the models' context, queued behind ir_musiq on the same final rectangles. True, or one name per image: with maniqa.configure(mode="random")
     an image's crop origins are drawn from the seed and its name (its row in the batch without names). Its value is the last of every tuple.
     An image whose short side is not above the crop (224) gets NaN.
+    dists (with gt only): score DISTS as well - ir_dists with the weights instarevive_amd.dists.configure() bound to the models' context, queued
+    behind ir_lpips on the same images. Its value is the very last of every tuple, behind maniqa's; a pair below 16 pixels on an edge gets NaN.
     degrade (with resize): one instarevive_amd.degrade.Params (or one degrade.ChainParams - the second-order chain, ir_degrade_chain; a batch
     holds one kind) per image - the decoded files are GROUND TRUTH, and between the upload and the
     bicubic chain ir_degrade makes each one's LQ image on the device (blur, bilinear downsample, noise, JPEG round trip, bilinear resize back;
@@ -470,6 +480,8 @@ def process(model, control_imgs: List[np.ndarray], strength: float, color_fix_ty
     noise_scheduler = noise_scheduler or DDPMScheduler()
     if lpips and gt is None:
         raise ValueError("process(lpips=True) needs gt=: LPIPS is scored against the ground truth")
+    if dists and gt is None:
+        raise ValueError("process(dists=True) needs gt=: DISTS is scored against the ground truth")
     if degrade is not None and resize is None:
         raise ValueError("process(degrade=...) needs resize=: the ground truth is degraded on the device input route")
     n, h, w = _batch_shape(control_imgs, resize)
@@ -486,7 +498,7 @@ def process(model, control_imgs: List[np.ndarray], strength: float, color_fix_ty
             raise RuntimeError("process(fp8=True): call vae.enable_fp8() first - without the fp8 weight forms every layer would silently run in bf16")
         ctx = model.ctx
         batch = _Batch(ctx, 0, "sync", 1, (n, h, w), control_imgs, return_stage1, png if codec is None else jpeg, resize, degrade, gt, lpips, niqe,
-                       clipiqa, niqe_rects, lq_sink is not None, codec=codec, png_runs=png_runs, musiq=musiq, maniqa=maniqa)
+                       clipiqa, niqe_rects, lq_sink is not None, codec=codec, png_runs=png_runs, musiq=musiq, maniqa=maniqa, dists=dists)
         _prepare_fused(model, y, y_mask, h, w, tiled, tile_size, (vae, None if disable_preprocess_model else preprocess_model))
         flags = _pipeline_flags(model, color_fix_type, disable_preprocess_model, tiled) | (L.FLAG_GRAPH if graph else 0) | (L.FLAG_FP8 if fp8 else 0)
         batch.upload()
@@ -554,7 +566,7 @@ def process_stream(model, batches: Iterable[Sequence[np.ndarray]], color_fix_typ
                    return_stage1: bool = True, graph: bool = False, fp8: bool = False, png=None,
                    png_wrap: bool = True, resize=None, gt=None, lpips: bool = False, niqe=None,
                    niqe_rects=None, clipiqa: bool = False, degrade=None, lq_sink=None, jpeg=None, jpeg_quality: int = 95,
-                   jpeg_subsampling=2, png_runs: bool = False, musiq: bool = False, maniqa=False) -> Iterator[Tuple[List[np.ndarray], List[np.ndarray]]]:
+                   jpeg_subsampling=2, png_runs: bool = False, musiq: bool = False, maniqa=False, dists: bool = False) -> Iterator[Tuple[List[np.ndarray], List[np.ndarray]]]:
     """process() over a sequence of image batches with the transfers hidden: while batch i computes on the current stream, batch
     i+1 is uploaded and batch i-1 downloaded on a copy stream (two staging slots per batch shape). Yields process()'s result for
     every batch, in order. Needs the fused form (all models instarevive_amd objects on one context). fp8 as in process() (cfg-5:
@@ -599,10 +611,13 @@ def process_stream(model, batches: Iterable[Sequence[np.ndarray]], color_fix_typ
     musiq (alone or with gt, lpips, niqe and clipiqa): as in process() - ir_musiq is queued behind ir_clipiqa on the same batches and rectangles, and
     its value comes behind clipiqa's.
     maniqa (alone or with the others): as in process() - ir_maniqa is queued behind ir_musiq on the same batches and rectangles, and its value comes
-    last. True, or an iterable in step with the batches that gives each batch's list of names."""
+    last. True, or an iterable in step with the batches that gives each batch's list of names.
+    dists (with gt only): as in process() - the scored batches' tuples end with the DISTS value."""
     noise_scheduler = noise_scheduler or DDPMScheduler()
     if lpips and gt is None:
         raise ValueError("process_stream(lpips=True) needs gt=: LPIPS is scored against the ground truth")
+    if dists and gt is None:
+        raise ValueError("process_stream(dists=True) needs gt=: DISTS is scored against the ground truth")
     if not _fused_ok(model, preprocess_model, vae, disable_preprocess_model):
         raise TypeError("process_stream needs instarevive_amd models sharing one context")
     ctx, device = model.ctx, model.device
@@ -638,7 +653,7 @@ def process_stream(model, batches: Iterable[Sequence[np.ndarray]], color_fix_typ
         imgs, by, bm = _split_batch(batch)
         b = _Batch(ctx, slot, "stream", 2, _batch_shape(imgs, records), imgs, return_stage1, rects, records, dparams, gts, lpips,
                    niqe if with_nq else None, bool(clipiqa) and with_nq, sizes, lq_sink is not None, (by, bm), codec=codec, png_runs=png_runs, musiq=bool(musiq) and with_nq,
-                   maniqa=(names if names is not None else True) if maniqa and with_nq else False)
+                   maniqa=(names if names is not None else True) if maniqa and with_nq else False, dists=dists)
         with torch.cuda.stream(copy):
             b.ready = b.upload(copy, main)
         return b

@@ -1,5 +1,5 @@
 """What the per-slot buffers of a batch in flight share (resample.ResizeSlot, metrics.ScoreSlot, niqe.NiqeSlot, clipiqa.ClipIqaSlot,
-musiq.MusiqSlot, maniqa.ManiqaSlot): the pool
+musiq.MusiqSlot, maniqa.ManiqaSlot; metrics.DistsColumn stands last in a batch's scorers and reads the DISTS values ScoreSlot holds): the pool
 they are kept in, the final size of every image of a batch, and the grouping of a batch's images into device calls. Host code only.
 
 The scorer slots have one life cycle, which pipeline._Batch drives without knowing which is which: fill() / plan() on the host says what

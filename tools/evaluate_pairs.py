@@ -3,6 +3,7 @@
 (/root/reference/evaluate_img.py:30-33 creates them, :40-57 averages them over the sorted file lists).
 
     python tools/evaluate_pairs.py -i results/ -r gt/ [--ntest N] [--lpips_alexnet alexnet-owt-7be5be79.pth --lpips_lin alex.pth]
+                                   [--dists_model DISTS_weights.pt --dists_vgg vgg16-397923af.pth]
 
 The reference takes all three from pyiqa (`create_metric('psnr' | 'ssim', test_y_channel=True, color_space='ycbcr')`, `create_metric('lpips')`);
 its training code wraps the `lpips` package itself (utils/metrics.py:41-66, `LPIPS(net="alex")`). Neither package is in this image or in the
@@ -20,6 +21,8 @@ runs tools/repin_with_diffusers.py-style checks:
     The pretrained weights (torchvision's alexnet-owt-7be5be79.pth, 233 MB, and lpips/weights/v0.1/alex.pth, 6 KB) do not exist offline:
     LPIPS is computed only when the user passes them (--lpips_alexnet / --lpips_lin, or one full `lpips.LPIPS().state_dict()` file through
     --lpips_lin alone); the arithmetic is tested against an independent torch.nn construction on random weights (tests/test_host_cpu.py).
+  * DISTS (not in evaluate_img.py; the column papers print next to LPIPS, pyiqa's `dists` at its defaults): `class DISTS` below states the whole
+    definition; computed only when the user passes the weights (--dists_model [--dists_vgg]).
 Of the no-reference metrics of the same script, MANIQA, MUSIQ and CLIPIQA are pretrained networks: each has its own tool,
 tools/evaluate_clipiqa.py, tools/evaluate_musiq.py and tools/evaluate_maniqa.py (its 20 crops lie on pyiqa's uniform grid, or are drawn from a
 seed and the file's name), which take the user's weights. NIQE
@@ -147,6 +150,113 @@ class LPIPS:
             return total.reshape(-1)
 
 
+# ---------------------------------------------------------------------------------------------------------------- DISTS
+VGG_STAGES = ((0, 2), (5, 7), (10, 12, 14), (17, 19, 21), (24, 26, 28))   # torchvision VGG-16 `features` indices of the convs of each stage
+VGG_WIDTHS = (64, 128, 256, 512, 512)
+DISTS_CHNS = (3,) + VGG_WIDTHS                                             # the six compared maps: the raw image, then each stage's output
+DISTS_MEAN = (0.485, 0.456, 0.406)
+DISTS_STD = (0.229, 0.224, 0.225)
+
+
+class DISTS:
+    """DISTS (Ding, Ma, Wang, Simoncelli: "Image Quality Assessment: Unifying Structure and Texture Similarity") as the published model and
+    pyiqa's `dists` compute it at their defaults - no resize, the image's own size, eval mode - restated; the model of ir_dists.
+      input x = v / 255 in [0, 1]; network input (x - mean) / std, every step rounded to float32 whatever `dtype` is;
+      five stages of torchvision VGG-16 `features` (3x3 convs, stride 1, zero padding 1, bias, ReLU): 3 -> 64 -> 64 | 128, 128 | 256 x 3 | 512 x 3 |
+      512 x 3, with an L2 pool in front of stages 2 .. 5: per channel sqrt(conv2d(x * x, g, stride 2, zero padding 1) + 1e-12) with
+      g = outer(a, a) / sum, a = hanning(5)[1:-1] = (0.5, 1, 0.5), i.e. (1, 2, 1) x (1, 2, 1) / 16, the nine taps added row by row from the
+      top-left; the output is ceil(H / 2) x ceil(W / 2);
+      six maps are compared - the raw x (3 channels, not the normalised input) and the ReLU output that ends each stage, 1475 channels - per
+      channel over the map's own pixels: mx, my the means, vx = mean((fx - mx)^2), vy (biased), cxy = mean(fx fy) - mx my,
+      S1 = (2 mx my + 1e-6) / (mx^2 + my^2 + 1e-6), S2 = (2 cxy + 1e-6) / (vx + vy + 1e-6);
+      score = 1 - sum_c (alpha_c S1_c + beta_c S2_c) / (sum(alpha) + sum(beta)).
+    Weights come from the user's files: `weights` = one state dict in the DISTS module's names (`stage1.0.weight` .. `stage5.28.bias`, `alpha`,
+    `beta` [1, 1475, 1, 1]; the `mean`, `std` and `*.filter` buffers are ignored), or `alpha` / `beta` alone (DISTS_weights.pt) with `vgg` =
+    torchvision's vgg16-397923af.pth (`features.N.*`; the classifier is ignored). dtype: torch.float32 (default) or torch.float64."""
+
+    def __init__(self, weights=None, vgg=None, device="cpu", dtype=None):
+        import torch
+        sd = {}
+        for src in (vgg, weights):
+            if src is None:
+                continue
+            part = torch.load(src, map_location="cpu") if isinstance(src, (str, Path)) else src
+            sd.update(part.get("state_dict", part) if isinstance(part, dict) else part)
+        self.dtype = dtype or torch.float32
+        self.device = device
+        self.stages, cin = [], 3
+        for k, (idxs, cout) in enumerate(zip(VGG_STAGES, VGG_WIDTHS)):
+            convs = []
+            for idx in idxs:
+                for base in (f"stage{k + 1}.{idx}", f"features.{idx}"):
+                    if base + ".weight" in sd:
+                        w, b = sd[base + ".weight"], sd[base + ".bias"]
+                        break
+                else:
+                    raise KeyError(f"VGG-16 conv features.{idx}: neither stage{k + 1}.{idx}.weight nor features.{idx}.weight in the given files")
+                if tuple(w.shape) != (cout, cin, 3, 3) or tuple(b.shape) != (cout,):
+                    raise ValueError(f"features.{idx}: conv {tuple(w.shape)} / bias {tuple(b.shape)} are not VGG-16's")
+                convs.append((w.to(device, self.dtype), b.to(device, self.dtype)))
+                cin = cout
+            self.stages.append(convs)
+        for name in ("alpha", "beta"):
+            if name not in sd:
+                raise KeyError(f"{name} missing: pass the DISTS weights (DISTS_weights.pt)")
+            if sd[name].numel() != sum(DISTS_CHNS):
+                raise ValueError(f"{name} has {sd[name].numel()} entries, DISTS has {sum(DISTS_CHNS)}")
+            setattr(self, name, sd[name].reshape(-1).to(device, self.dtype))
+        self.mean = torch.tensor(DISTS_MEAN, device=device).view(1, 3, 1, 1)
+        self.std = torch.tensor(DISTS_STD, device=device).view(1, 3, 1, 1)
+        a = torch.tensor([0.5, 1.0, 0.5], dtype=self.dtype, device=device)   # hanning(5)[1:-1]
+        self.window = (a[:, None] * a[None, :]) / (a[:, None] * a[None, :]).sum()
+
+    def l2pool(self, x):
+        import torch.nn.functional as F
+        c = x.shape[1]
+        return (F.conv2d(x * x, self.window.expand(c, 1, 3, 3).contiguous(), stride=2, padding=1, groups=c) + 1e-12).sqrt()
+
+    def maps(self, x01):
+        """x01: NCHW float32 in [0, 1] -> the six compared maps in self.dtype."""
+        import torch
+        import torch.nn.functional as F
+        assert x01.dtype == torch.float32
+        outs = [x01.to(self.dtype)]
+        h = ((x01 - self.mean) / self.std).to(self.dtype)   # float32 roundings, then the model's precision
+        for k, convs in enumerate(self.stages):
+            if k:
+                h = self.l2pool(h)
+            for w, b in convs:
+                h = F.relu(F.conv2d(h, w, b, padding=1))
+            outs.append(h)
+        return outs
+
+    def moments(self, fx, fy):
+        """[N][C][5]: mx, my, vx, vy, cxy of one map of either image."""
+        import torch
+        mx, my = fx.mean((2, 3), keepdim=True), fy.mean((2, 3), keepdim=True)
+        vx, vy = ((fx - mx) ** 2).mean((2, 3)), ((fy - my) ** 2).mean((2, 3))
+        cxy = (fx * fy).mean((2, 3)) - mx[..., 0, 0] * my[..., 0, 0]
+        return torch.stack((mx[..., 0, 0], my[..., 0, 0], vx, vy, cxy), -1)
+
+    def all_moments(self, img1, img2):
+        """img1, img2: NCHW RGB tensors in [0, 1] -> [N][1475][5], channels in map order."""
+        import torch
+        with torch.no_grad():
+            a, b = (t.to(self.device, torch.float32) for t in (img1, img2))
+            return torch.cat([self.moments(fx, fy) for fx, fy in zip(self.maps(a), self.maps(b))], 1)
+
+    def score(self, m):
+        """[N][1475][5] moments -> [N] scores."""
+        mx, my, vx, vy, cxy = m.unbind(-1)
+        s1 = (2 * mx * my + 1e-6) / (mx * mx + my * my + 1e-6)
+        s2 = (2 * cxy + 1e-6) / (vx + vy + 1e-6)
+        one = s1.new_ones(s1.shape)   # the weights are summed as the weighted terms are: S1 = S2 = 1 then gives exactly 0
+        return 1 - ((self.alpha * s1).sum(1) + (self.beta * s2).sum(1)) / ((self.alpha * one).sum(1) + (self.beta * one).sum(1))
+
+    def __call__(self, img1, img2):
+        return self.score(self.all_moments(img1, img2))
+
+
 def list_images(folder):
     return sorted(Path(folder).glob("*.[jpJP][pnPN]*[gG]"))
 
@@ -174,8 +284,21 @@ def _gpu_lpips(alexnet, lin):
     return lambda a8, b8: device_lpips.lpips_arrays(ctx, a8, b8)
 
 
-def evaluate(in_path, ref_path, ntest=None, log=print, lpips=None, backend="host", lpips_u8=None):
-    """lpips: the torch model (img1, img2 in [0, 1]); lpips_u8: a scorer of two HWC uint8 arrays in its place (the device's)."""
+def _gpu_dists(model, vgg):
+    """--backend gpu with DISTS weights: the score of a pair from the device kernel (ir_dists, exact fp32 convolutions, fp64 statistics)."""
+    import os
+    sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+    import torch
+    from instarevive_amd import dists as device_dists
+    from instarevive_amd.models import get_context
+    ctx = get_context(torch.device("cuda", 0))
+    device_dists.configure(ctx, model, vgg)
+    return lambda a8, b8: device_dists.dists_arrays(ctx, a8, b8)
+
+
+def evaluate(in_path, ref_path, ntest=None, log=print, lpips=None, backend="host", lpips_u8=None, dists=None, dists_u8=None):
+    """lpips: the torch model (img1, img2 in [0, 1]); lpips_u8: a scorer of two HWC uint8 arrays in its place (the device's). dists / dists_u8:
+    the same two forms of DISTS; its line comes last."""
     from PIL import Image
     ins, refs = list_images(in_path), list_images(ref_path)
     if ntest is not None:
@@ -189,6 +312,9 @@ def evaluate(in_path, ref_path, ntest=None, log=print, lpips=None, backend="host
     elif lpips is not None:
         import torch
         tot["lpips"] = 0.0
+    if dists is not None or dists_u8 is not None:
+        import torch
+        tot["dists"] = 0.0
     score = _gpu_scorer() if backend == "gpu" else None
     for fi, fr in zip(ins, refs):
         a8, b8 = np.asarray(Image.open(fi).convert("RGB")), np.asarray(Image.open(fr).convert("RGB"))
@@ -207,6 +333,10 @@ def evaluate(in_path, ref_path, ntest=None, log=print, lpips=None, backend="host
             tot["lpips"] += float(lpips_u8(a8, b8))
         elif lpips is not None:
             tot["lpips"] += float(lpips(torch.from_numpy(a).permute(2, 0, 1)[None], torch.from_numpy(b).permute(2, 0, 1)[None], normalize=True)[0])
+        if dists_u8 is not None:
+            tot["dists"] += float(dists_u8(a8, b8))
+        elif dists is not None:
+            tot["dists"] += float(dists(torch.from_numpy(a).permute(2, 0, 1)[None], torch.from_numpy(b).permute(2, 0, 1)[None])[0])
     res = {k: v / len(ins) for k, v in tot.items()}
     for k, v in res.items():
         log(f"{k}: {v:.5f}")
@@ -220,18 +350,29 @@ def main():
     ap.add_argument("--ntest", type=int, default=None)
     ap.add_argument("--lpips_alexnet", type=str, default=None, help="torchvision AlexNet state dict (alexnet-owt-7be5be79.pth)")
     ap.add_argument("--lpips_lin", type=str, default=None, help="lpips v0.1 linear heads (lpips/weights/v0.1/alex.pth), or a full lpips.LPIPS() state dict")
+    ap.add_argument("--dists_model", type=str, default=None, help="score DISTS as well (class DISTS; the line `dists:` comes last): one state dict in the DISTS "
+                    "module's names, or alpha / beta alone (DISTS_weights.pt) with --dists_vgg; with --backend gpu also an .npz in ir_dists_configure's names")
+    ap.add_argument("--dists_vgg", type=str, default=None, help="with --dists_model holding alpha / beta alone: torchvision's VGG-16 state dict (vgg16-397923af.pth)")
     ap.add_argument("--device", type=str, default="cpu")
     ap.add_argument("--backend", type=str, default="host", choices=["host", "gpu"], help="who computes PSNR-Y / SSIM-Y: host (default) = the numpy fp64 "
                     "definitions of this file; gpu = ir_metrics_y on the MI355X (the same definitions, fp64 statistics; the printed lines are the same) and, with --lpips_lin, "
-                    "LPIPS from ir_lpips (exact fp32 convolutions, fp64 sums: within 1e-6 relative of the torch model, so a last printed digit may differ)")
+                    "LPIPS from ir_lpips (exact fp32 convolutions, fp64 sums: within 1e-6 relative of the torch model, so a last printed digit may differ) and, with "
+                    "--dists_model, DISTS from ir_dists (within 2e-6 absolute of the torch model)")
     a = ap.parse_args()
+    if a.dists_vgg and not a.dists_model:
+        raise SystemExit("--dists_vgg needs --dists_model (DISTS' alpha / beta)")
+    more = {}
+    if a.dists_model and a.backend == "gpu":
+        more["dists_u8"] = _gpu_dists(a.dists_model, a.dists_vgg)
+    elif a.dists_model:
+        more["dists"] = DISTS(a.dists_model, a.dists_vgg, a.device)
     if a.lpips_lin and a.backend == "gpu":
-        evaluate(a.in_path, a.ref_path, a.ntest, backend=a.backend, lpips_u8=_gpu_lpips(a.lpips_alexnet, a.lpips_lin))
+        evaluate(a.in_path, a.ref_path, a.ntest, backend=a.backend, lpips_u8=_gpu_lpips(a.lpips_alexnet, a.lpips_lin), **more)
         return
     net = LPIPS(a.lpips_alexnet, a.lpips_lin, a.device) if a.lpips_lin else None
     if net is None:
         print("lpips: skipped (no weights given: --lpips_lin [--lpips_alexnet])")
-    evaluate(a.in_path, a.ref_path, a.ntest, lpips=net, backend=a.backend)
+    evaluate(a.in_path, a.ref_path, a.ntest, lpips=net, backend=a.backend, **more)
 
 
 if __name__ == "__main__":

@@ -36,6 +36,9 @@ random-initialised models of reduced width pin it exactly as the 4 GB checkpoint
 12. pyiqa's MANIQA (evaluate_img.py's `create_metric('maniqa')`, the koniq checkpoint) -> tools/evaluate_maniqa.py on pyiqa's own weights, read
     through PYIQA_KEYS, at pyiqa's uniform crop grid: the score of two images to 1e-5 (the score is roughly 0 - 1; pyiqa runs fp32). A mismatch
     points at one of that file's recollections: the key table, uniform_origins(), DEFAULTS (scale, crops, taps), or a step docs/parity.md lists.
+13. pyiqa's DISTS (`create_metric('dists')`, the column papers print next to LPIPS) -> tools/evaluate_pairs.py::DISTS on pyiqa's own weights (its
+    network's state dict, in the DISTS module's names): the score of two pairs to 1e-5 (pyiqa runs fp32). A mismatch points at one of the
+    points docs/parity.md lists: the input range, the L2 pool's window and padding, map 0, the variance, the constants, the weights' sum.
  6. ftfy.fix_text (diffusion/model/t5.py:118-124) -> instarevive_amd.captions.fix_text (deterministic steps + the restricted mojibake repair).
 
 The fixture holds inputs, state-dict checksums and the third party's outputs (data, not source); tests/test_oracle_golden.py picks
@@ -308,6 +311,35 @@ def pin_maniqa(out):
     return ok
 
 
+def pin_dists(out):
+    """pyiqa's `dists` against tools/evaluate_pairs.py::DISTS on the weights pyiqa itself loads."""
+    import pyiqa
+    import importlib.util
+    spec = importlib.util.spec_from_file_location("evaluate_pairs", os.path.join(ROOT, "tools", "evaluate_pairs.py"))
+    ep = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(ep)
+    metric = pyiqa.create_metric("dists", device="cpu")
+    sd = {k: v.detach().float() for k, v in metric.net.state_dict().items()}
+    try:
+        net = ep.DISTS(sd)
+    except (KeyError, ValueError) as ex:
+        print(f"  [13] pyiqa's state dict does not load into evaluate_pairs.DISTS: {ex}; it has e.g. {sorted(sd)[:6]}")
+        return False
+    rng = np.random.default_rng(19)
+    yy, xx = np.mgrid[0:200, 0:264].astype(np.float64)
+    base = np.stack([128 + 80 * np.sin(xx / 23) * np.cos(yy / 31), 128 + 70 * np.sin((xx + yy) / 41), 128 + 90 * np.cos(xx / 17 - yy / 29)], -1)
+    ok = True
+    for name, sigma in (("near", 3.0), ("far", 30.0)):
+        a = np.clip(np.rint(base), 0, 255).astype(np.uint8)
+        b = np.clip(np.rint(base + rng.normal(0, sigma, base.shape)), 0, 255).astype(np.uint8)
+        ta, tb = (torch.from_numpy(x).permute(2, 0, 1)[None].float() / 255.0 for x in (a, b))
+        ref, got = float(metric(ta, tb)), float(net(ta, tb)[0])
+        print(f"  [13] pyiqa DISTS ({name}) {ref:.7f} vs evaluate_pairs.DISTS {got:.7f} (absolute {abs(got - ref):.2e})")
+        out[f"dists_{name}_a"], out[f"dists_{name}_b"], out[f"dists_{name}_ref"] = a, b, np.float64(ref)
+        ok = ok and abs(got - ref) <= 1e-5
+    return ok
+
+
 def pin_musiq(out):
     """pyiqa's `musiq` against tools/evaluate_musiq.py on the koniq10k weights pyiqa itself loads (its network's state dict)."""
     import importlib.util
@@ -399,7 +431,7 @@ def main():
                            ("open_clip (item 4)", pin_clip, ()), ("pyiqa (item 5)", pin_iqa, ()), ("ftfy (item 6)", pin_ftfy, ()), ("lpips (item 7)", pin_lpips, ()),
                            ("pyiqa NIQE (item 8)", pin_niqe, ()), ("pyiqa CLIP-IQA (item 9)", pin_clipiqa, (a.clip_bpe,)),
                            ("OpenCV degradation steps (item 10)", pin_degrade, ()), ("pyiqa MUSIQ (item 11)", pin_musiq, ()),
-                           ("pyiqa MANIQA (item 12)", pin_maniqa, ())):
+                           ("pyiqa MANIQA (item 12)", pin_maniqa, ()), ("pyiqa DISTS (item 13)", pin_dists, ())):
         print(name)
         try:
             verdict[name] = fn(out, *args)
