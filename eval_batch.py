@@ -58,6 +58,12 @@ def parse_args():
     ap.add_argument("--dists_model", default=None, metavar="FILE", help="with --gt (or --degrade): DISTS on the GPU as the last CSV column and a `dists:` average line "
                     "(inference.py --dists_model: a DISTS state dict, alpha / beta with --dists_vgg, or an .npz); --image_size must be at least 16")
     ap.add_argument("--dists_vgg", default=None, metavar="FILE", help="with --dists_model holding alpha / beta alone: torchvision's VGG-16 state dict")
+    ap.add_argument("--fid_model", default=None, metavar="FILE", help="FID of the restored folder on the GPU (inference.py --fid_model: pytorch-fid's pt_inception state "
+                    "dict or an .npz) against the ground truth of the scored files (--gt or --degrade) or against --fid_stats; with neither it is refused. One last "
+                    "line `fid: x.xxxxx` behind the averages; the CSVs do not change")
+    ap.add_argument("--fid_resize", default="clean", choices=["clean", "legacy"], help="with --fid_model: clean (pyiqa / clean-fid: Pillow's float BICUBIC) or legacy (pytorch-fid: torch's bilinear)")
+    ap.add_argument("--fid_stats", default=None, metavar="FILE.npz", help="with --fid_model: the reference set's statistics (pytorch-fid's mu / sigma); needs no --gt")
+    ap.add_argument("--fid_features_out", default=None, metavar="FILE", help="with --fid_model: where the run's features go (default <output>/fid_features.npz; fid_features.rank<k>.npz with several ranks)")
     ap.add_argument("--niqe_params", default=None, help="score NIQE (no reference needed) of both output folders on the GPU (inference.py --niqe_params: "
                     "niqe_modelparameters.mat or an .npz). Works without --gt: the CSVs are then file,niqe; with --gt the column comes last. --image_size must "
                     "be at least 192 for two blocks")
@@ -116,6 +122,7 @@ def main():
     musiq_model = cli.load_musiq_model(args)
     maniqa_model = cli.load_maniqa_model(args)
     dists_weights = cli.load_dists_weights(args)
+    fid_weights, fid_stats = cli.load_fid(args)
     noref = bool(niqe_params) or clipiqa_model is not None or musiq_model is not None or maniqa_model is not None
     recipe = geo = None
     if args.save_lq and not args.degrade:
@@ -130,13 +137,18 @@ def main():
         geo = job_geometry((args.image_size, args.image_size), 1, False, 512)   # the device input route of inference.py --resize gpu
         if geo.chain or geo.net_hw != (args.image_size, args.image_size):
             raise SystemExit("--degrade needs --image_size to be a multiple of 64 of at least 512 (the crop is the network input as it is)")
-        if not args.gt and (args.lpips_lin or noref or dists_weights):
+        if not args.gt and (args.lpips_lin or noref or dists_weights or (fid_weights and fid_stats is None)):
             args.gt = args.input   # the files that are degraded are the ground truth of what is restored from them
     cli.check_device(args.device)
     rank, world, local = parallel.init_distributed()
     torch.cuda.set_device(local)
     m = cli.load_models(args, torch.device("cuda", local))
     cond_dir = args.cond_output or args.output.rstrip("/") + "-cond"
+    fid_run = None
+    if fid_weights:
+        from instarevive_amd import fid
+        fid.configure(m.model.ctx, fid_weights)
+        fid_run = fid.Run(fid.Run.default_path(args.output, args.fid_features_out), fid_stats, rank, world)
     # os.walk order is filesystem-dependent: every rank sorts its listing and takes rank 0's copy, so that ownership of a file follows from
     # ONE list (the same rule as inference.py)
     files = sorted(list_image_files(args.input, follow_links=True))
@@ -240,12 +252,16 @@ def main():
                              **({"jpeg": whole, "jpeg_quality": args.jpeg_quality, "jpeg_subsampling": args.jpeg_subsampling} if gpu_jpg else {}),
                              gt=cli.in_step(truths) if lookup else None, **with_lpips, **({"niqe": niqe_params} if niqe_params else {}),
                              **({"clipiqa": True} if clipiqa_model else {}), **({"musiq": True} if musiq_model else {}), **({"dists": True} if dists_weights else {}),
+                             **({"fid": args.fid_resize} if fid_run else {}),
                              **({"maniqa": [[os.path.basename(out_name(args.output, args.input, f, ext_out)) for f in group] for group in batches]} if maniqa_model else {}),
                              **({"resize": cli.in_step(records)} if recipe or crop_gpu else {}),
                              **({"degrade": cli.in_step(dparams), "lq_sink": lq_images.append if args.save_lq else None} if recipe else {}))
     no_score = {"niqe": 0, "clipiqa": 0, "musiq": 0, "maniqa": 0, "dists": 0}
     for group, out in zip(batches, results):
         preds, stage1 = out[:2]
+        if fid_run:   # every image is a whole crop saved as the device leaves it: every file enters the set
+            fid_run.add([os.path.relpath(out_name(args.output, args.input, f, ext_out), args.output) for f in group], out[-1])
+            out = out[:-1]
         if reports:
             for rep, folder, scores in zip(reports, (args.output, cond_dir), out[2]):
                 for f, score in zip(group, scores):
@@ -287,6 +303,8 @@ def main():
             print(f"[rank {rank}] --niqe_params: {no_score['niqe']} files were not scored (NIQE needs 96 x 96 blocks and two complete feature rows)")
         if no_score["dists"]:
             print(f"[rank {rank}] --dists_model: {no_score['dists']} files were not scored (DISTS is scored from 16 x 16 pixels)")
+    if fid_run:
+        fid_run.finish()
 
 
 if __name__ == "__main__":

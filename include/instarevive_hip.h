@@ -48,7 +48,8 @@ enum { IR_STAGE_SWINIR = 0, IR_STAGE_VAE_ENCODE = 1, IR_STAGE_DIT = 2, IR_STAGE_
        IR_STAGE_MANIQA = 22 /* ir_maniqa: n images, flags = the crops per image, tile_size = the crops one pass takes (0: one - the least
                                ir_maniqa accepts; n * crops: everything at once); depends on these and on the shape bound by
                                ir_maniqa_configure, not on h x w (0 for a context that is not configured) */,
-       IR_STAGE_DISTS = 23 /* ir_dists: n pairs, h, w = the compared rectangle; depends on the sizes alone (ctx may be NULL) */ };
+       IR_STAGE_DISTS = 23 /* ir_dists: n pairs, h, w = the compared rectangle; depends on the sizes alone (ctx may be NULL) */,
+       IR_STAGE_FID = 24 /* ir_fid_features: n images; depends on n alone (ctx may be NULL, h and w do not matter) */ };
 /* ir_pipeline flags */
 enum { IR_FLAG_NO_PREPROCESS = 1, IR_FLAG_TILED = 2, IR_FLAG_FIX_WAVELET = 4, IR_FLAG_FIX_ADAIN = 8,
        /* ir_pipeline only, needs ir_dit_control_configure: run the DiT step with the ControlNet-Half branch, condition latent
@@ -483,6 +484,42 @@ int ir_dists_scale_table(float* tab768);
 int ir_dists_configure(ir_ctx* ctx);
 int ir_dists(ir_ctx* ctx, void* stream, const uint8_t* a, int a_rows, long a_pitch, const uint8_t* b, int b_rows, long b_pitch, int n, int h,
              int w, double* out, double* moments_or_null, void* ws, size_t ws_bytes);
+
+/* The per-image half of FID on the device: the 2048 pooled Inception-v3 features of pytorch-fid's `InceptionV3(output_blocks=[3])`;
+ * tools/evaluate_fid.py::InceptionFID restates the network and the two resizes and is the model of these calls. The set-level half (mean,
+ * covariance, Frechet distance) is fp64 host code (instarevive_amd/fid.py).
+ * ir_fid_resize_plan (host only, no context) fills the tables of the resize of an h x w image to 299 x 299, ir_fid_resize_plan_bytes() bytes
+ * (0 for h or w below 1 or an unknown mode), to be copied to 8-byte aligned device memory. mode IR_FID_RESIZE_CLEAN: Pillow's float32 (mode F)
+ * BICUBIC per colour plane, antialiased - per axis the first tap and tap count of each of the 299 outputs as ints, then Pillow's normalised
+ * coefficients as doubles; the device accumulates ss += (double)pixel * k in Pillow's order, stores float32 after the horizontal and after the
+ * vertical pass, clips to [0, 255]; the network's input is (v - 128) / 128. IR_FID_RESIZE_LEGACY: torch's fp32 bilinear interpolation of v / 255
+ * (align_corners false, no antialiasing, source index fmaf(in / 299, i + 0.5, -0.5) clamped at 0, fmaf(p0, w0, p1 * w1) along x, then along y -
+ * the order of torch's CPU kernels on a processor with fused multiply-adds); the network's input is 2 x - 1.
+ * ir_fid_configure binds tensors uploaded with ir_upload: for each of the 94 convolutions, under torchvision's module name,
+ * `fid.<name>.w` fp32 [cout][cin][kh][kw] and `fid.<name>.bn_w`, `.bn_b`, `.bn_mean`, `.bn_var` fp32 [cout] (Conv2d_1a_3x3 .. Conv2d_4a_3x3,
+ * Mixed_5b .. Mixed_7c with branch1x1, branch5x5_1 .. and so on; shapes in tools/evaluate_fid.py::CONVS). It folds each eval-mode BatchNorm
+ * (eps 1e-3) in fp64 into scale = w / sqrt(var + eps) and shift = b - mean * scale, rounded once, and repacks the weights. Returns -2 for a
+ * missing tensor or one of another size (ir_last_error names it). A size is a byte count: ir_upload carries no shape, so a [192][192][7][1]
+ * tensor uploaded under the name of a [192][192][1][7] kernel is bound as if it were that kernel - the Python loader checks the shapes.
+ * ir_fid_features takes the top-left h x w rectangle of every image of img [n][rows][pitch] (RGB8, addressed as ir_dists does) and writes
+ * features[i][2048] as doubles. Every convolution is conv -> relu(acc * scale + shift) with the accumulation a k-ordered fp32 fmaf chain in
+ * (ky, kx, c) order on the fp32-input MFMA; max pools ignore padding; the average pools of Mixed_5*, Mixed_6b..e and Mixed_7b divide the sum of
+ * the in-bounds taps (row by row from the top-left) by their count; Mixed_7c pools with max; the mean over the 8 x 8 positions is fp64 in a
+ * fixed order. No floating-point atomics: an image gives the same bits on every call and at every position of a batch.
+ * block_means_or_null: [n][10304] doubles - the fp64 per-channel spatial means of the maps after Conv2d_2b_3x3 (64), Conv2d_4a_3x3 (192) and
+ * Mixed_5b, 5c, 5d, 6a .. 6e, 7a, 7b, 7c (256, 288, 288, 5 x 768, 1280, 2048, 2048), in this order. resized_or_null: [n][299][299][3] floats -
+ * the resized image behind the clip and in front of the scaling (0 .. 255 for clean, 0 .. 1 for legacy).
+ * All pointers but the plan's are device pointers; stream-ordered, no allocation, no host synchronisation (capturable).
+ * ws: 256-byte aligned, ir_workspace_bytes(ctx, IR_STAGE_FID, n, 0, 0, 0, 0, 0) bytes (about 24 MB per image, whatever the images' size).
+ * Returns -1 (nothing launched, nothing written) for a null pointer, n < 1 or above 4096, h or w below 2 (a limit of this library), h above
+ * rows, a pitch below 3 w, an unknown mode, misaligned tables or outputs, or a short or misaligned workspace; -14 when ir_fid_configure has not
+ * succeeded on this context. */
+enum { IR_FID_RESIZE_CLEAN = 0, IR_FID_RESIZE_LEGACY = 1 };
+size_t ir_fid_resize_plan_bytes(int h, int w, int mode);
+int ir_fid_resize_plan(int h, int w, int mode, void* host_tables, size_t bytes);
+int ir_fid_configure(ir_ctx* ctx);
+int ir_fid_features(ir_ctx* ctx, void* stream, const uint8_t* img, int rows, long pitch, int n, int h, int w, int mode, const void* tables,
+                    double* features, double* block_means_or_null, float* resized_or_null, void* ws, size_t ws_bytes);
 
 /* The pixel work of NIQE (the no-reference metric of the reference's evaluate_img.py that is no pretrained network; pyiqa's `niqe` defaults:
  * Y of YIQ, no border crop, 96 x 96 blocks) on the device; tools/evaluate_niqe.py restates the definition in numpy fp64, down to the order of

@@ -121,6 +121,17 @@ def parse_args() -> Namespace:
                         "the network itself. Not offered with --shard_tiles")
     parser.add_argument("--dists_vgg", type=str, default=None, metavar="FILE", help="with --dists_model holding alpha / beta alone: torchvision's VGG-16 state dict "
                         "(vgg16-397923af.pth)")
+    parser.add_argument("--fid_model", type=str, default=None, metavar="FILE", help="FID of the run's results on the GPU (ir_fid_features: pytorch-fid's Inception-v3 in "
+                        "exact fp32 on every saved result, the Frechet distance in fp64 at the end of the run; the definition of tools/evaluate_fid.py). FILE is "
+                        "pytorch-fid's pt_inception state dict or an .npz in ir_fid_configure's names. The reference set is the ground truth of the scored "
+                        "files (--gt or --degrade) or --fid_stats; with neither the flag is refused. The averages gain one last line `fid: x.xxxxx`; metrics.csv "
+                        "does not change (FID has no per-file value). Which files enter the set follows --gt's rule (the saved image is the device's image); "
+                        "the run prints both counts. Opt-in. Not offered with --shard_tiles")
+    parser.add_argument("--fid_resize", type=str, default="clean", choices=["clean", "legacy"], help="with --fid_model: how an image becomes the 299 x 299 input: clean "
+                        "(pyiqa's fid, clean-fid: Pillow's float BICUBIC, antialiased) or legacy (pytorch-fid: torch's bilinear)")
+    parser.add_argument("--fid_stats", type=str, default=None, metavar="FILE.npz", help="with --fid_model: the reference set's statistics (pytorch-fid's mu / sigma); needs no --gt")
+    parser.add_argument("--fid_features_out", type=str, default=None, metavar="FILE", help="with --fid_model: where the features of the run go (default "
+                        "<output>/fid_features.npz; with several ranks fid_features.rank<k>.npz, which rank 0 merges)")
     parser.add_argument("--niqe_params", type=str, default=None, help="score NIQE, the no-reference metric of the reference's evaluate_img.py that is no "
                         "pretrained network, on the GPU (ir_niqe_stats; the definition of tools/evaluate_niqe.py, i.e. pyiqa's defaults). FILE holds the pristine "
                         "parameters mu_prisparam [36] / cov_prisparam [36][36]: pyiqa's niqe_modelparameters.mat, or an .npz. Works without --gt: the CSV is then "
@@ -402,6 +413,15 @@ def load_dists_weights(args: Namespace):
         raise SystemExit(f"--dists_model {args.dists_model}: {e}")
 
 
+def load_fid(args: Namespace):
+    """--fid_model [--fid_stats]: (the tensors ir_fid_configure binds, the reference statistics or None), read before any other model is touched;
+    (None, None) without the flag. The refusals are fid.check_flags'."""
+    if not any(getattr(args, f, None) for f in ("fid_model", "fid_stats", "fid_features_out")) and getattr(args, "fid_resize", "clean") == "clean":
+        return None, None
+    from instarevive_amd import fid
+    return fid.check_flags(args, bool(getattr(args, "gt", None) or getattr(args, "degrade", None)))
+
+
 def check_device(device: str) -> str:
     if device != "cuda" or not torch.cuda.is_available():
         raise SystemExit(f"device '{device}' requested / no GPU visible: this build runs on MI355X (ROCm) only and has no CPU or MPS path")
@@ -675,6 +695,7 @@ def main() -> None:
     musiq_model = load_musiq_model(args)
     maniqa_model = load_maniqa_model(args)
     dists_weights = load_dists_weights(args)
+    fid_weights, fid_stats = load_fid(args)
     noref = bool(niqe_params) or clipiqa_model is not None or musiq_model is not None or maniqa_model is not None
     if args.save_lq and not args.degrade:
         raise SystemExit("--save_lq writes the images --degrade synthesises: give --degrade as well")
@@ -688,7 +709,7 @@ def main() -> None:
         if args.resize != "gpu":
             print(f"--degrade: the LQ images are made on the device, switching --resize gpu on")
             args.resize = "gpu"
-        if not args.gt and (args.metrics_out or args.lpips_lin or noref or dists_weights):
+        if not args.gt and (args.metrics_out or args.lpips_lin or noref or dists_weights or (fid_weights and fid_stats is None)):
             args.gt = args.input   # the files that are degraded are the ground truth of what is restored from them
     torch.manual_seed(args.seed)  # the path is deterministic; kept for surface compatibility (pl.seed_everything)
     args.device = check_device(args.device)
@@ -743,6 +764,11 @@ def main() -> None:
         if maniqa_model:
             from instarevive_amd import maniqa
             maniqa.configure(m.model.ctx, maniqa_model, args.maniqa_crops, args.maniqa_seed)
+    fid_run = None
+    if fid_weights:
+        from instarevive_amd import fid
+        fid.configure(m.model.ctx, fid_weights)
+        fid_run = fid.Run(fid.Run.default_path(args.output, args.fid_features_out), fid_stats, rank, world)
     local_world = int(os.environ.get("LOCAL_WORLD_SIZE", world))
     if os.environ.get("IR_SWITCH_INTERVAL"):   # experiment knob: how long a worker thread may keep the GIL while the thread that feeds the GPU waits for it
         import sys
@@ -810,10 +836,11 @@ def main() -> None:
     names = deque()    # --maniqa_model, per batch: the saved files' names, which key random crops
     sizes = deque()    # --niqe_params / --clipiqa_model / --musiq_model / --maniqa_model, per batch: the saved sizes, or None for a batch that is not scored
     dparams = deque()  # --degrade, per batch: the files' degrade.Params
+    fid_sizes = deque()   # --fid_model, per batch: the saved sizes, or None for a batch that does not enter the set
     lq_images = deque()   # --save_lq, per batch: the LQ images process_stream hands over right before the batch's results
 
     def feed():
-        for group in batches_of(jobs, max(args.batch_size, 1), (lambda j: png_rect(j, args) is not None) if on_gpu or report else None):
+        for group in batches_of(jobs, max(args.batch_size, 1), (lambda j: png_rect(j, args) is not None) if on_gpu or report or fid_run else None):
             todo.append(group)
             if args.gt:
                 truths.append([j.gt for j in group] if all(j.gt is not None for j in group) else None)
@@ -825,6 +852,9 @@ def main() -> None:
             if on_gpu:
                 rr = [png_rect(j, args) for j in group]
                 rects.append(rr if all(rr) else None)
+            if fid_run:   # with the ground truth as the reference set, a file enters only together with its ground truth
+                rr = [png_rect(j, args) for j in group]
+                fid_sizes.append(rr if all(rr) and (fid_stats is not None or all(j.gt is not None for j in group)) else None)
             imgs = [j.net_in for j in group]
             if args.resize_on_gpu:
                 from instarevive_amd.resample import ResizeJob
@@ -845,10 +875,16 @@ def main() -> None:
                               **({"niqe": niqe_params} if niqe_params else {}), **({"clipiqa": True} if clipiqa_model else {}),
                               **({"musiq": True} if musiq_model else {}), **({"maniqa": in_step(names)} if maniqa_model else {}),
                               **({"dists": True} if dists_weights else {}),
+                              **({"fid": args.fid_resize, "fid_rects": in_step(fid_sizes)} if fid_run else {}),
                               **({"niqe_rects": in_step(sizes)} if noref else {}),
                               **({"degrade": in_step(dparams), "lq_sink": lq_images.append if args.save_lq else None} if args.degrade else {}), **common):
         preds, stage1 = out[:2]
         group = todo.pop(0)
+        if fid_run:
+            extra = out[-1] if isinstance(out[-1], dict) else None
+            if extra is not None:
+                out = out[:-1]
+            fid_run.add([os.path.relpath(job.save_path, args.output) for job in group], extra)
         if args.save_lq:
             for job, lq in zip(group, lq_images.popleft()):
                 pools.write_behind(write_lq, job, lq, args)
@@ -900,6 +936,8 @@ def main() -> None:
         if unscored:
             print(f"[rank {rank}] {what}: {unscored} of {pools.written} files were not scored (their saved image is not the device's image: an input the host "
                   f"enlarged, or --show_lq) - use --resize gpu")
+    if fid_run:
+        fid_run.finish()
     if pools.written:
         # first read submitted -> last PNG closed, model loading excluded (bench.py --cli_files parses this line)
         rest, dt_rest = pools.written - first[1], t1 - first[0]

@@ -26,7 +26,7 @@ SYMBOLS = [
     "ir_dit_set_prompts", "ir_op_attention_kv_groups", "ir_graph_records", "ir_op_vae_segment", "ir_op_vae_segment_ws", "ir_op_vae_segment_info",
     "ir_op_swin_shell", "ir_op_swin_shell_ws", "ir_op_dit_shell", "ir_op_dit_shell_ws", "ir_op_unet_block", "ir_op_unet_block_ws", "ir_op_text_block", "ir_op_text_block_ws",
     "ir_png_bound", "ir_png_encode", "ir_png_encode_runs", "ir_jpeg_bound", "ir_jpeg_encode", "ir_jpeg_decode", "ir_resample_plan_bytes", "ir_resample_plan", "ir_resample_u8", "ir_resample_u8_window", "ir_metrics_y",
-    "ir_lpips_scale_table", "ir_lpips_configure", "ir_lpips", "ir_dists_scale_table", "ir_dists_configure", "ir_dists", "ir_niqe_window", "ir_niqe_stats",
+    "ir_lpips_scale_table", "ir_lpips_configure", "ir_lpips", "ir_dists_scale_table", "ir_dists_configure", "ir_dists", "ir_fid_resize_plan_bytes", "ir_fid_resize_plan", "ir_fid_configure", "ir_fid_features", "ir_niqe_window", "ir_niqe_stats",
     "ir_clipiqa_scale_table", "ir_clipiqa_configure", "ir_clipiqa", "ir_musiq_layout", "ir_musiq_input_table", "ir_musiq_configure", "ir_musiq",
     "ir_maniqa_input_table", "ir_maniqa_crops", "ir_maniqa_configure", "ir_maniqa",
     "ir_degrade_qtables", "ir_degrade", "ir_degrade_chain",
@@ -45,6 +45,9 @@ STAGE_DEGRADE = 16
 STAGE_MUSIQ = 21
 STAGE_MANIQA = 22
 STAGE_DISTS = 23
+STAGE_FID = 24
+FID_RESIZE_CLEAN, FID_RESIZE_LEGACY = 0, 1
+FID_SIZE, FID_DIM, FID_BLOCK_CHANNELS = 299, 2048, 10304
 DEGRADE_NORM_NONE, DEGRADE_NORM_MAX = 0, 1
 DEGRADE_MAX_KSIZE, DEGRADE_MIN_LOW = 41, 8
 STAGE_DEGRADE_CHAIN = 17
@@ -60,6 +63,7 @@ CLIPIQA_NOT_CONFIGURED = -13   # ir_clipiqa before ir_clipiqa_configure
 MUSIQ_NOT_CONFIGURED = -13     # ir_musiq before ir_musiq_configure
 MANIQA_NOT_CONFIGURED = -13    # ir_maniqa before ir_maniqa_configure
 DISTS_NOT_CONFIGURED = -14     # ir_dists before ir_dists_configure
+FID_NOT_CONFIGURED = -14       # ir_fid_features before ir_fid_configure
 DISTS_CHANNELS = 1475          # 3 + 64 + 128 + 256 + 512 + 512: the channels of the six compared maps
 MUSIQ_LONGER = (224, 384, 0)   # the longer side of each scale; 0: the image at its own size
 FLAG_NO_PREPROCESS, FLAG_TILED, FLAG_FIX_WAVELET, FLAG_FIX_ADAIN, FLAG_CONTROL_LQ, FLAG_GRAPH, FLAG_FP8 = 1, 2, 4, 8, 16, 32, 64
@@ -258,6 +262,11 @@ def load_library():
     lib.ir_dists_scale_table.argtypes = [vp]
     lib.ir_dists_configure.argtypes = [vp]
     lib.ir_dists.argtypes = [vp, vp, vp, i, C.c_long, vp, i, C.c_long, i, i, i, vp, vp, vp, sz]
+    lib.ir_fid_resize_plan_bytes.argtypes = [i, i, i]
+    lib.ir_fid_resize_plan_bytes.restype = sz
+    lib.ir_fid_resize_plan.argtypes = [i, i, i, vp, sz]
+    lib.ir_fid_configure.argtypes = [vp]
+    lib.ir_fid_features.argtypes = [vp, vp, vp, i, C.c_long, i, i, i, i, vp, vp, vp, vp, vp, sz]
     lib.ir_niqe_window.argtypes = [vp]
     lib.ir_niqe_stats.argtypes = [vp, vp, vp, i, C.c_long, i, i, i, vp, vp, sz]
     lib.ir_clipiqa_scale_table.argtypes = [vp]

@@ -1,4 +1,4 @@
-// The image tools of the C ABI: PNG and JPEG encoding, Pillow's resampling, PSNR-Y / SSIM-Y, LPIPS, DISTS, CLIP-IQA, MUSIQ, MANIQA, NIQE and the two degradation paths. Each entry
+// The image tools of the C ABI: PNG and JPEG encoding, Pillow's resampling, PSNR-Y / SSIM-Y, LPIPS, DISTS, FID's features, CLIP-IQA, MUSIQ, MANIQA, NIQE and the two degradation paths. Each entry
 // point checks its arguments and launches the kernels of its own .hip file; none of them runs a model stage, takes the workspace arena or is
 // profiled, so nothing here knows api.cpp's Run. Host code only, except for the tables the kernels read, which are computed here once.
 #include <math.h>
@@ -492,6 +492,151 @@ int ir_dists(ir_ctx* c, void* stream, const uint8_t* a, int a_rows, long a_pitch
     if (!c->dists.ok) return fail(c, -14, "ir_dists: DISTS not configured (ir_dists_configure)");
     use_ctx(c);
     if (ir_launch_dists(c->dists, a, a_rows, a_pitch, b, b_rows, b_pitch, n, h, w, ws, out, moments, (hipStream_t)stream)) return fail(c, -100, "ir_dists: launch failed");
+    return 0;
+}
+
+// ---------------------------------------------------------------- FID's Inception-v3 features (fid.hip)
+// The tables of the two resizes to 299 x 299. clean: Resample.c's precompute_coeffs for BICUBIC as doubles (Pillow's mode-F path keeps them as they
+// are), in Pillow's order of operations. legacy: torch's bilinear indices and weights in fp32, src = fmaf(scale, i + 0.5, -0.5) as its CPU kernels
+// compute it where the processor fuses; the two weights are stored as doubles (exactly).
+extern "C++" int ir_fid_tables_layout(int h, int w, int mode, IrFidTables* t) {
+    if (h < 1 || w < 1 || (mode != IR_FID_RESIZE_CLEAN && mode != IR_FID_RESIZE_LEGACY)) return -1;
+    t->kx = mode == IR_FID_RESIZE_CLEAN ? rs_axis(w, IR_FID_SIZE, IR_RESAMPLE_BICUBIC).ksize : 2;
+    t->ky = mode == IR_FID_RESIZE_CLEAN ? rs_axis(h, IR_FID_SIZE, IR_RESAMPLE_BICUBIC).ksize : 2;
+    t->xb = 0;
+    t->yb = 2 * IR_FID_SIZE * sizeof(int);
+    t->xk = 4 * IR_FID_SIZE * sizeof(int) + 8;   // 4792 + 8: a multiple of 8
+    t->yk = t->xk + (size_t)IR_FID_SIZE * t->kx * sizeof(double);
+    t->total = t->yk + (size_t)IR_FID_SIZE * t->ky * sizeof(double);
+    return 0;
+}
+#pragma clang fp contract(off)
+static void fid_clean_axis(int in, int ksize, int* bounds, double* kk) {
+    const RsAxis a = rs_axis(in, IR_FID_SIZE, IR_RESAMPLE_BICUBIC);
+    const double ss = 1.0 / a.filterscale;
+    for (int xx = 0; xx < IR_FID_SIZE; ++xx) {
+        const double center = (xx + 0.5) * a.scale;
+        double ww = 0.0;
+        int xmin = (int)(center - a.support + 0.5);
+        if (xmin < 0) xmin = 0;
+        int xmax = (int)(center + a.support + 0.5);
+        if (xmax > in) xmax = in;
+        xmax -= xmin;
+        double* k = kk + (size_t)xx * ksize;
+        for (int x = 0; x < ksize; ++x) k[x] = 0.0;
+        for (int x = 0; x < xmax; ++x) {
+            k[x] = rs_bicubic((x + xmin - center + 0.5) * ss);
+            ww += k[x];
+        }
+        for (int x = 0; x < xmax; ++x)
+            if (ww != 0.0) k[x] /= ww;
+        bounds[2 * xx] = xmin;
+        bounds[2 * xx + 1] = xmax;
+    }
+}
+static void fid_legacy_axis(int in, int* idx, double* lam) {
+    const float scale = (float)in / (float)IR_FID_SIZE;
+    for (int i = 0; i < IR_FID_SIZE; ++i) {
+        float real = fmaf(scale, (float)i + 0.5f, -0.5f);
+        if (real < 0.f) real = 0.f;
+        const int i0 = std::min((int)floorf(real), in - 1);
+        const float l1 = std::min(std::max(real - (float)i0, 0.f), 1.f);
+        idx[2 * i] = i0;
+        idx[2 * i + 1] = std::min(i0 + 1, in - 1);
+        lam[2 * i] = (double)(1.f - l1);
+        lam[2 * i + 1] = (double)l1;
+    }
+}
+#pragma clang fp contract(fast)
+size_t ir_fid_resize_plan_bytes(int h, int w, int mode) {
+    IrFidTables t;
+    return ir_fid_tables_layout(h, w, mode, &t) ? 0 : t.total;
+}
+int ir_fid_resize_plan(int h, int w, int mode, void* host_tables, size_t bytes) {
+    IrFidTables t;
+    if (!host_tables || ir_fid_tables_layout(h, w, mode, &t) || bytes < t.total || (reinterpret_cast<uintptr_t>(host_tables) & 7)) return -1;
+    char* b = static_cast<char*>(host_tables);
+    memset(b, 0, t.total);
+    int *xb = reinterpret_cast<int*>(b + t.xb), *yb = reinterpret_cast<int*>(b + t.yb);
+    double *xk = reinterpret_cast<double*>(b + t.xk), *yk = reinterpret_cast<double*>(b + t.yk);
+    if (mode == IR_FID_RESIZE_CLEAN) {
+        fid_clean_axis(w, t.kx, xb, xk);
+        fid_clean_axis(h, t.ky, yb, yk);
+    } else {
+        fid_legacy_axis(w, xb, xk);
+        fid_legacy_axis(h, yb, yk);
+    }
+    return 0;
+}
+
+int ir_fid_configure(ir_ctx* c) {
+    if (!c) return -1;
+    HIPOK(c, hipSetDevice(c->device));
+    c->fid.ok = false;
+    IrFidModel m;
+    const char* const who = "ir_fid_configure";
+    const IrFidConv* convs = ir_fid_convs();
+    static const char* const parts[4] = {"bn_w", "bn_b", "bn_mean", "bn_var"};
+    std::vector<const float*> src(IR_FID_CONVS * 5);
+    for (int k = 0; k < IR_FID_CONVS; ++k) {   // every tensor is looked up before anything is replaced
+        const IrFidConv& v = convs[k];
+        if (!(src[5 * k] = exact_f32(c, who, "Inception-v3's", fmt("fid.%s.w", v.name), (size_t)v.cout * v.cin * v.kh * v.kw))) return -2;
+        for (int j = 0; j < 4; ++j)
+            if (!(src[5 * k + 1 + j] = exact_f32(c, who, "Inception-v3's", fmt("fid.%s.%s", v.name, parts[j]), (size_t)v.cout))) return -2;
+    }
+    std::vector<void*>& own = c->own[OWN_FID];
+    release_list(own);
+    HIPOK(c, hipDeviceSynchronize());
+    float x01[256];
+    for (int v = 0; v < 256; ++v) x01[v] = (float)v / 255.0f;
+    if (int e = own_copy(c, own, x01, sizeof x01, hipMemcpyHostToDevice, &m.x01)) return e;
+    for (int k = 0; k < IR_FID_CONVS; ++k) {
+        const IrFidConv& v = convs[k];
+        const int cin = v.cin == 3 ? 4 : v.cin, K = v.kh * v.kw * cin, npad = (v.cout + 63) / 64 * 64;
+        std::vector<float> w((size_t)v.cout * v.cin * v.kh * v.kw), t((size_t)pad32(K) * npad, 0.f), bn[4];
+        HIPOK(c, hipMemcpy(w.data(), src[5 * k], w.size() * 4, hipMemcpyDeviceToHost));
+        for (int j = 0; j < 4; ++j) {
+            bn[j].resize(v.cout);
+            HIPOK(c, hipMemcpy(bn[j].data(), src[5 * k + 1 + j], (size_t)v.cout * 4, hipMemcpyDeviceToHost));
+        }
+        for (int o = 0; o < v.cout; ++o)
+            for (int ci = 0; ci < v.cin; ++ci)
+                for (int ky = 0; ky < v.kh; ++ky)
+                    for (int kx = 0; kx < v.kw; ++kx)
+                        t[(size_t)((ky * v.kw + kx) * cin + ci) * npad + o] = w[(((size_t)o * v.cin + ci) * v.kh + ky) * v.kw + kx];
+        std::vector<float> scale(v.cout), shift(v.cout);
+        for (int o = 0; o < v.cout; ++o) {   // eval-mode BatchNorm, eps 1e-3: y = (x - mean) / sqrt(var + eps) * w + b, folded in fp64
+            const double sc = (double)bn[0][o] / sqrt((double)bn[3][o] + 1e-3);
+            scale[o] = (float)sc;
+            shift[o] = (float)((double)bn[1][o] - (double)bn[2][o] * sc);
+        }
+        if (int e = own_copy(c, own, t.data(), t.size() * 4, hipMemcpyHostToDevice, &m.w[k])) return e;
+        if (int e = own_copy(c, own, scale.data(), scale.size() * 4, hipMemcpyHostToDevice, &m.scale[k])) return e;
+        if (int e = own_copy(c, own, shift.data(), shift.size() * 4, hipMemcpyHostToDevice, &m.shift[k])) return e;
+    }
+    m.ok = true;
+    c->fid = m;
+    ++c->generation;
+    return 0;
+}
+
+int ir_fid_features(ir_ctx* c, void* stream, const uint8_t* img, int rows, long pitch, int n, int h, int w, int mode, const void* tables, double* features,
+                    double* block_means, float* resized, void* ws, size_t ws_bytes) {
+    if (!c || !img || !tables || !features || !ws) return fail(c, -1, "ir_fid_features: null argument");
+    if (int e = check_rect(c, "ir_fid_features", "this library takes FID's features from 2 x 2", n, h, w, IR_FID_MIN_EDGE, {{rows, pitch}},
+                           mode != IR_FID_RESIZE_CLEAN && mode != IR_FID_RESIZE_LEGACY))
+        return e;
+    IrFidPlan pl;
+    if (ir_fid_plan(n, &pl)) return fail(c, -1, "ir_fid_features: n %d is more than one call takes (%d)", n, IR_FID_MAX_N);
+    if (int e = check_ws(c, "ir_fid_features", ws, ws_bytes, pl.total, 256)) return e;
+    if (int e = check_out8(c, "ir_fid_features", features)) return e;
+    if (int e = check_out8(c, "ir_fid_features", block_means)) return e;
+    if (int e = check_out8(c, "ir_fid_features", tables)) return e;
+    if (reinterpret_cast<uintptr_t>(resized) & 3) return fail(c, -1, "ir_fid_features: resized not aligned to 4 bytes");
+    if (!c->fid.ok) return fail(c, -14, "ir_fid_features: FID not configured (ir_fid_configure)");
+    use_ctx(c);
+    if (ir_launch_fid(c->fid, img, rows, pitch, n, h, w, mode, tables, features, block_means, resized, ws, (hipStream_t)stream))
+        return fail(c, -100, "ir_fid_features: launch failed");
     return 0;
 }
 
@@ -1037,6 +1182,7 @@ bool ir_host::image_workspace(ir_ctx* c, int stage, int n, int h, int w, int fla
     IrManiqaPlan qp;
     IrLpipsPlan lp;
     IrDistsPlan dp;
+    IrFidPlan fp;
     IrJpegLayout jl;
     *bytes = 0;
     switch (stage) {
@@ -1050,6 +1196,7 @@ bool ir_host::image_workspace(ir_ctx* c, int stage, int n, int h, int w, int fla
             break;
         case IR_STAGE_LPIPS: if (!ir_lpips_plan(n, h, w, &lp)) *bytes = lp.total; break;
         case IR_STAGE_DISTS: if (!ir_dists_plan(n, h, w, &dp)) *bytes = dp.total; break;
+        case IR_STAGE_FID: if (!ir_fid_plan(n, &fp)) *bytes = fp.total; break;
         case IR_STAGE_METRICS: if (some) *bytes = metrics_workspace(n, h, w); break;
         case IR_STAGE_JPEG: if (ir_jpeg_layout(n, h, w, flags, tile_size, &jl)) *bytes = jl.total; break;   // flags: the subsampling, tile_size: restart_mcus
         case IR_STAGE_JPEG_DECODE: if (n >= 1) *bytes = ir_jpeg_decode_workspace(h, w, (uint32_t)flags, tile_size); break;   // flags: stream_bytes, tile_size: subseq_bits

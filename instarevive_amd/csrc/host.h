@@ -226,7 +226,7 @@ struct Profiler {
 };
 
 // the owner of each list of ir_ctx::own: the context itself, or the binding that a *_configure / set_* call replaces
-enum Own { OWN_CTX = 0, OWN_DIT_TABS, OWN_DIT_CTRL_TABS, OWN_DIT_PROMPT, OWN_T5, OWN_CLIP, OWN_LPIPS, OWN_CLIPIQA, OWN_MUSIQ, OWN_MANIQA, OWN_DISTS,
+enum Own { OWN_CTX = 0, OWN_DIT_TABS, OWN_DIT_CTRL_TABS, OWN_DIT_PROMPT, OWN_T5, OWN_CLIP, OWN_LPIPS, OWN_CLIPIQA, OWN_MUSIQ, OWN_MANIQA, OWN_DISTS, OWN_FID,
            OWN_UNET_TABS, OWN_UNET_CTX = OWN_UNET_TABS + 2, OWN_COUNT = OWN_UNET_CTX + 2 };   // + which: the two UNets' timestep tables / context K-V caches
 
 }  // namespace ir_host
@@ -284,6 +284,8 @@ struct ir_ctx {
     IrManiqaModel maniqa;
     // ir_dists: the two input tables, the repacked conv weights and copies of the biases, alpha and beta (in OWN_DISTS)
     IrDistsModel dists;
+    // ir_fid_features: the repacked conv weights, the folded BatchNorm vectors and the byte table (in OWN_FID)
+    IrFidModel fid;
 };
 
 namespace ir_host {

@@ -333,6 +333,43 @@ int ir_dists_plan(int n, int h, int w, IrDistsPlan* plan);
 int ir_launch_dists(const IrDistsModel& m, const uint8_t* a, int a_rows, long a_pitch, const uint8_t* b, int b_rows, long b_pitch, int n, int h, int w, void* ws,
                     double* out, double* moments, hipStream_t s);
 
+// ---- FID's Inception-v3 features of uint8 images (fid.hip)
+#define IR_FID_SIZE 299
+#define IR_FID_DIM 2048
+#define IR_FID_CONVS 94
+#define IR_FID_BLOCKS 13               // the maps of block_means: Conv2d_2b, Conv2d_4a and the eleven Mixed_* blocks
+#define IR_FID_BLOCK_CHANNELS 10304    // 64 + 192 + 256 + 288 + 288 + 5 x 768 + 1280 + 2048 + 2048
+#define IR_FID_MIN_EDGE 2
+#define IR_FID_MAX_N 4096
+#define IR_FID_MAP_FLOATS 1382976      // the largest map of an image: Conv2d_2b's 147 x 147 x 64
+// a convolution of the network, in the order the launches take them (and ir_fid_configure binds them); name: torchvision's
+struct IrFidConv {
+    char name[40];
+    int cin, cout, kh, kw, stride, ph, pw;
+};
+const IrFidConv* ir_fid_convs();   // [IR_FID_CONVS]
+// w[k]: [kh kw cin (cin 3 -> 4) padded to 32][cout padded to 64] fp32 with K in (ky, kx, c) order, scale / shift[k]: [cout] the BatchNorm folded in
+// fp64 and rounded once; x01: [256] (float)v / 255.0f
+struct IrFidModel {
+    bool ok = false;
+    const float *w[IR_FID_CONVS] = {}, *scale[IR_FID_CONVS] = {}, *shift[IR_FID_CONVS] = {}, *x01 = nullptr;
+};
+// the workspace of n images: the four-channel input map and four maps of IR_FID_MAP_FLOATS floats per image (two for the trunk, two for the
+// branches); it does not depend on the images' size. -1 for n outside 1 .. IR_FID_MAX_N.
+struct IrFidPlan {
+    size_t x4_bytes, map_bytes, total;
+};
+int ir_fid_plan(int n, IrFidPlan* plan);
+// byte offsets of the parts of ir_fid_resize_plan's tables for h x w images: bounds int[299][2] per axis, coefficients double[299][kx | ky]
+struct IrFidTables {
+    size_t xb, yb, xk, yk, total;
+    int kx, ky;
+};
+int ir_fid_tables_layout(int h, int w, int mode, IrFidTables* t);   // host (api_image.cpp); mode: IR_FID_RESIZE_*; -1 for a bad size or mode
+// features: [n][2048] doubles; block_means: [n][10304] doubles or null; resized: [n][299][299][3] floats or null
+int ir_launch_fid(const IrFidModel& m, const uint8_t* img, int rows, long pitch, int n, int h, int w, int mode, const void* tables, double* features,
+                  double* block_means, float* resized, void* ws, hipStream_t s);
+
 // ---- NIQE's block statistics of uint8 images (niqe.hip)
 // One workgroup per IR_NIQE_BLOCK x IR_NIQE_BLOCK block of the top-left (h / 96 * 96) x (w / 96 * 96) rectangle. tab: four 256-entry fp64 tables in
 // device memory - coef_c * (double)((float)v / 255.0f) for 0.299 / 0.587 / 0.114, then v / 255.0; half: [n][H / 2][W / 2] doubles (the half-size

@@ -229,13 +229,16 @@ class _Batch:
     two streams and keeps the batch's events in `ready` (its uploads) and `done` (its downloads)."""
 
     def __init__(self, ctx, slot, tag, slots, shape, imgs, with_stage1, rects=None, records=None, dparams=None, gts=None, lpips=False, niqe=None,
-                 clipiqa=False, sizes=None, want_lq=False, prompts=(None, None), codec=None, png_runs=False, musiq=False, maniqa=False, dists=False):
+                 clipiqa=False, sizes=None, want_lq=False, prompts=(None, None), codec=None, png_runs=False, musiq=False, maniqa=False, dists=False, fid=None, fid_sizes=None):
         """The plan phase, host work only: every size is checked and every ground truth compared with its image's FINAL size, so a batch that
         does not fit raises ValueError before anything is launched for it; then the scorer slots are filled / planned - `scorers` holds them in
         the order of a score tuple: paired (metrics.ScoreSlot; with lpips it scores LPIPS as well, ir_lpips with the weights lpips.configure()
         bound to the context), NIQE with `niqe` its parameters, CLIP-IQA, MUSIQ, MANIQA (maniqa: True, or the images' names, which key random crops), and last DISTS (dists: ir_dists with the weights dists.configure() bound to the context; the paired slot queues it, metrics.DistsColumn
         stands where its value is read) - and the images copied into page-locked memory: the staging input, or
         the decoded files (with their degrade parameters) into the ResizeSlot, whose bicubic chain then makes the staging input on the device.
+        fid: None, or FID's resize mode - the batch's predictions (and its ground truth, when it has one) go through ir_fid_features into a
+        fid.FidSlot, which is no scorer: FID has no per-file value, so collect() hands the features over beside the scores; fid_sizes: the
+        batch's fid_rects entry.
         sizes: the batch's niqe_rects entry. codec: None - rects are coded as PNG, in the run mode with png_runs - or _jpeg_codec()'s pair."""
         from .slots import final_sizes, record_sizes
         self.ctx, self.slot, self.tag, self.shape, self.with_stage1 = ctx, slot, tag, shape, with_stage1
@@ -283,6 +286,11 @@ class _Batch:
         if gts is not None and dists:
             from .metrics import DistsColumn
             self.scorers.append(DistsColumn(self.sc))
+        self.fid = None
+        if fid:
+            from .fid import FidSlot
+            self.fid = FidSlot.get(ctx, slot, tag)
+            self.fid.plan(final_sizes("fid", n, h, w, records, rects, fid_sizes, gts), fid, self.sc)
         if rects is not None:
             if records is None and len(rects) != n:
                 raise ValueError(f"{'png' if codec is None else 'jpeg'}: {len(rects)} rectangles for a batch of {n} images")
@@ -317,7 +325,7 @@ class _Batch:
         if self.records is not None:
             from .resample import chain_ws_bytes, decode_ws_bytes
             self.ctx.workspace(max(chain_ws_bytes(self.records), decode_ws_bytes(self.records)))
-        for s in self.scorers:
+        for s in self.scorers + ([self.fid] if self.fid is not None else []):
             s.reserve()
 
     def launch(self, flags, tile_size, tile_stride, acp, sf):
@@ -349,7 +357,7 @@ class _Batch:
                 else:   # the resized result, or the valid rectangle of the network's output
                     for i, (r, final) in enumerate(zip(res, record_sizes(self.records))):
                         self.enc.queue(first + i, out[i:i + 1] if r is None else r, [final])
-        for s in self.scorers:
+        for s in self.scorers + ([self.fid] if self.fid is not None else []):
             for first, out, res in self.outs:
                 s.queue(first, out, res)
 
@@ -371,7 +379,7 @@ class _Batch:
             self.rs.download_lq()
         if self.rs is not None:
             self.rs.download_info()
-        for s in self.scorers:
+        for s in self.scorers + ([self.fid] if self.fid is not None else []):
             s.download()
 
     def host_lq(self):
@@ -400,10 +408,11 @@ class _Batch:
                     lists.append([self.rs.host_result(r) if r is not None else host[i, :rec.geo.valid_hw[0], :rec.geo.valid_hw[1]].copy()
                                   for i, (rec, r) in enumerate(zip(self.records, res))])
             lists.append([])
+        fid = () if self.fid is None else (self.fid.features(),)   # the last element of a batch with fid: {"fid": [n][2048], "fid_gt": ... or None}
         if not self.scorers:
-            return lists[0], lists[1]
+            return (lists[0], lists[1]) + fid
         scores = [[sum(row, ()) for row in zip(*(s.scores(first, n) for s in self.scorers))] for first, _, _ in self.outs] + [[]]
-        return lists[0], lists[1], (scores[0], scores[1])
+        return (lists[0], lists[1], (scores[0], scores[1])) + fid
 
 
 def _batch_shape(imgs, records):
@@ -419,7 +428,8 @@ def process(model, control_imgs: List[np.ndarray], strength: float, color_fix_ty
             tile_size: int, tile_stride: int, preprocess_model=None, vae=None, y=None, y_mask=None, noise_scheduler=None,
             fused: bool = True, graph: bool = False, return_stage1: bool = True, fp8: bool = False, png=None,
             resize=None, gt=None, lpips: bool = False, niqe=None, niqe_rects=None, clipiqa: bool = False, degrade=None,
-            lq_sink=None, jpeg=None, jpeg_quality: int = 95, jpeg_subsampling=2, png_runs: bool = False, musiq: bool = False, maniqa=False, dists: bool = False) -> Tuple[List[np.ndarray], List[np.ndarray]]:
+            lq_sink=None, jpeg=None, jpeg_quality: int = 95, jpeg_subsampling=2, png_runs: bool = False, musiq: bool = False, maniqa=False, dists: bool = False, fid=None,
+            fid_rects=None) -> Tuple[List[np.ndarray], List[np.ndarray]]:
     """test_scripts/inference.py:55-166. control_imgs: list of HWC uint8 RGB arrays of equal size (multiples of 64).
     Returns (preds, stage1_preds) as lists of HWC uint8 arrays (stage1_preds is empty with return_stage1=False, which skips its
     conversion and download).
@@ -472,6 +482,11 @@ def process(model, control_imgs: List[np.ndarray], strength: float, color_fix_ty
     An image whose short side is not above the crop (224) gets NaN.
     dists (with gt only): score DISTS as well - ir_dists with the weights instarevive_amd.dists.configure() bound to the models' context, queued
     behind ir_lpips on the same images. Its value is the very last of every tuple, behind maniqa's; a pair below 16 pixels on an edge gets NaN.
+    fid (with or without gt): True / "clean" / "legacy" - the Inception-v3 features of FID (ir_fid_features with the weights
+    instarevive_amd.fid.configure() bound to the models' context) of every prediction at its final size, queued behind the other scorers, and of
+    the ground truth when gt= is given. FID is a statistic of a whole set, so there is no score column: the result gains a LAST element, the dict
+    {"fid": [n][2048] float64, "fid_gt": [n][2048] or None}, which the caller collects (fid.FeatureSet) and scores at the end of the run
+    (fid.frechet_distance). fid_rects: one (h, w) per image where the final size is neither a resize record's, a png rectangle nor the ground truth's.
     degrade (with resize): one instarevive_amd.degrade.Params (or one degrade.ChainParams - the second-order chain, ir_degrade_chain; a batch
     holds one kind) per image - the decoded files are GROUND TRUTH, and between the upload and the
     bicubic chain ir_degrade makes each one's LQ image on the device (blur, bilinear downsample, noise, JPEG round trip, bilinear resize back;
@@ -498,7 +513,8 @@ def process(model, control_imgs: List[np.ndarray], strength: float, color_fix_ty
             raise RuntimeError("process(fp8=True): call vae.enable_fp8() first - without the fp8 weight forms every layer would silently run in bf16")
         ctx = model.ctx
         batch = _Batch(ctx, 0, "sync", 1, (n, h, w), control_imgs, return_stage1, png if codec is None else jpeg, resize, degrade, gt, lpips, niqe,
-                       clipiqa, niqe_rects, lq_sink is not None, codec=codec, png_runs=png_runs, musiq=musiq, maniqa=maniqa, dists=dists)
+                       clipiqa, niqe_rects, lq_sink is not None, codec=codec, png_runs=png_runs, musiq=musiq, maniqa=maniqa, dists=dists,
+                       fid=("clean" if fid is True else fid) or None, fid_sizes=fid_rects)
         _prepare_fused(model, y, y_mask, h, w, tiled, tile_size, (vae, None if disable_preprocess_model else preprocess_model))
         flags = _pipeline_flags(model, color_fix_type, disable_preprocess_model, tiled) | (L.FLAG_GRAPH if graph else 0) | (L.FLAG_FP8 if fp8 else 0)
         batch.upload()
@@ -566,7 +582,8 @@ def process_stream(model, batches: Iterable[Sequence[np.ndarray]], color_fix_typ
                    return_stage1: bool = True, graph: bool = False, fp8: bool = False, png=None,
                    png_wrap: bool = True, resize=None, gt=None, lpips: bool = False, niqe=None,
                    niqe_rects=None, clipiqa: bool = False, degrade=None, lq_sink=None, jpeg=None, jpeg_quality: int = 95,
-                   jpeg_subsampling=2, png_runs: bool = False, musiq: bool = False, maniqa=False, dists: bool = False) -> Iterator[Tuple[List[np.ndarray], List[np.ndarray]]]:
+                   jpeg_subsampling=2, png_runs: bool = False, musiq: bool = False, maniqa=False, dists: bool = False, fid=None,
+                   fid_rects=None) -> Iterator[Tuple[List[np.ndarray], List[np.ndarray]]]:
     """process() over a sequence of image batches with the transfers hidden: while batch i computes on the current stream, batch
     i+1 is uploaded and batch i-1 downloaded on a copy stream (two staging slots per batch shape). Yields process()'s result for
     every batch, in order. Needs the fused form (all models instarevive_amd objects on one context). fp8 as in process() (cfg-5:
@@ -612,7 +629,10 @@ def process_stream(model, batches: Iterable[Sequence[np.ndarray]], color_fix_typ
     its value comes behind clipiqa's.
     maniqa (alone or with the others): as in process() - ir_maniqa is queued behind ir_musiq on the same batches and rectangles, and its value comes
     last. True, or an iterable in step with the batches that gives each batch's list of names.
-    dists (with gt only): as in process() - the scored batches' tuples end with the DISTS value."""
+    dists (with gt only): as in process() - the scored batches' tuples end with the DISTS value.
+    fid: as in process() - a batch that enters the set yields the features dict as its last element. fid_rects: an iterable in step with the
+    batches: per batch one (h, w) per image, or None for a batch that does not enter the set (its saved image is not the device's image);
+    without it every batch enters, a batch with gt= only when it has ground truth."""
     noise_scheduler = noise_scheduler or DDPMScheduler()
     if lpips and gt is None:
         raise ValueError("process_stream(lpips=True) needs gt=: LPIPS is scored against the ground truth")
@@ -637,6 +657,8 @@ def process_stream(model, batches: Iterable[Sequence[np.ndarray]], color_fix_typ
     noref = niqe is not None or bool(clipiqa) or bool(musiq) or bool(maniqa)
     mq_it = iter(maniqa) if maniqa and maniqa is not True else None
     nq_it = iter(niqe_rects) if noref and niqe_rects is not None else None
+    fid = ("clean" if fid is True else fid) or None
+    fid_it = iter(fid_rects) if fid and fid_rects is not None else None
 
     def staged(batch, slot):
         """The next batch, planned and with its uploads queued on the copy stream. Every per-batch iterable is advanced right after the batch
@@ -650,10 +672,13 @@ def process_stream(model, batches: Iterable[Sequence[np.ndarray]], color_fix_typ
         sizes = next(nq_it) if nq_it is not None else None
         with_nq = noref and (sizes is not None if nq_it is not None else (gts is not None or gt_it is None))
         names = next(mq_it) if mq_it is not None else None
+        fsizes = next(fid_it) if fid_it is not None else None
+        with_fid = fid and (fsizes is not None if fid_it is not None else (gts is not None or gt_it is None))
         imgs, by, bm = _split_batch(batch)
         b = _Batch(ctx, slot, "stream", 2, _batch_shape(imgs, records), imgs, return_stage1, rects, records, dparams, gts, lpips,
                    niqe if with_nq else None, bool(clipiqa) and with_nq, sizes, lq_sink is not None, (by, bm), codec=codec, png_runs=png_runs, musiq=bool(musiq) and with_nq,
-                   maniqa=(names if names is not None else True) if maniqa and with_nq else False, dists=dists)
+                   maniqa=(names if names is not None else True) if maniqa and with_nq else False, dists=dists,
+                   fid=fid if with_fid else None, fid_sizes=fsizes)
         with torch.cuda.stream(copy):
             b.ready = b.upload(copy, main)
         return b

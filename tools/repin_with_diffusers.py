@@ -39,6 +39,10 @@ random-initialised models of reduced width pin it exactly as the 4 GB checkpoint
 13. pyiqa's DISTS (`create_metric('dists')`, the column papers print next to LPIPS) -> tools/evaluate_pairs.py::DISTS on pyiqa's own weights (its
     network's state dict, in the DISTS module's names): the score of two pairs to 1e-5 (pyiqa runs fp32). A mismatch points at one of the
     points docs/parity.md lists: the input range, the L2 pool's window and padding, map 0, the variance, the constants, the weights' sum.
+14. pytorch-fid's InceptionV3(output_blocks=[3]) and pyiqa's `fid` input -> tools/evaluate_fid.py::InceptionFID on pytorch-fid's own weights: the
+    2048 features of two images to 1e-5 of their largest (both run fp32) with the `legacy` input, pyiqa's / clean-fid's resized input against
+    resize_clean() bit for bit, and calculate_frechet_distance against frechet_distance() on 4096 random features to 1e-6 relative. A mismatch
+    points at one of the points docs/parity.md lists: eps, count_include_pad, the max pool of Mixed_7c, the branch order, the resize.
  6. ftfy.fix_text (diffusion/model/t5.py:118-124) -> instarevive_amd.captions.fix_text (deterministic steps + the restricted mojibake repair).
 
 The fixture holds inputs, state-dict checksums and the third party's outputs (data, not source); tests/test_oracle_golden.py picks
@@ -340,6 +344,49 @@ def pin_dists(out):
     return ok
 
 
+def pin_fid(out):
+    """pytorch-fid's network, pyiqa's resize and pytorch-fid's distance against tools/evaluate_fid.py on the weights pytorch-fid itself loads."""
+    import importlib.util
+    from pytorch_fid.fid_score import calculate_frechet_distance
+    from pytorch_fid.inception import InceptionV3
+    spec = importlib.util.spec_from_file_location("evaluate_fid", os.path.join(ROOT, "tools", "evaluate_fid.py"))
+    ef = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(ef)
+    theirs = InceptionV3([3], resize_input=True, normalize_input=True).eval()
+    try:   # fid_inception_v3() is the torchvision-named network whose blocks InceptionV3 re-groups: its state dict has the names the loader reads
+        from pytorch_fid.inception import fid_inception_v3
+        net = ef.InceptionFID({k: v.detach().float() for k, v in fid_inception_v3().state_dict().items()}, "fp32")
+    except (KeyError, ValueError) as ex:
+        print(f"  [14] pytorch-fid's state dict does not load into evaluate_fid.InceptionFID: {ex}")
+        return False
+    rng = np.random.default_rng(23)
+    yy, xx = np.mgrid[0:200, 0:264].astype(np.float64)
+    base = np.stack([128 + 80 * np.sin(xx / 23) * np.cos(yy / 31), 128 + 70 * np.sin((xx + yy) / 41), 128 + 90 * np.cos(xx / 17 - yy / 29)], -1)
+    ok = True
+    for name, sigma in (("smooth", 3.0), ("noisy", 30.0)):
+        a = np.clip(np.rint(base + rng.normal(0, sigma, base.shape)), 0, 255).astype(np.uint8)
+        with torch.no_grad():
+            ref = theirs(torch.from_numpy(a).permute(2, 0, 1)[None].float() / 255.0)[0][0, :, 0, 0].numpy().astype(np.float64)
+        got = net.features_of_images([a], "legacy")[0]
+        rel = float(np.abs(got - ref).max() / np.abs(ref).max())
+        print(f"  [14] pytorch-fid features ({name}) vs evaluate_fid.InceptionFID, legacy input: {rel:.2e} of the largest")
+        out[f"fid_{name}_img"], out[f"fid_{name}_ref"] = a, ref
+        ok = ok and rel <= 1e-5
+    try:
+        from pyiqa.archs.fid_arch import clean_resize   # pyiqa's name for clean-fid's resize; absent in some versions
+        r = np.asarray(clean_resize(a))
+        same = np.array_equal(np.asarray(r, np.float32), ef.resize_clean(a))
+        print(f"  [14] pyiqa's clean resize vs evaluate_fid.resize_clean: {'bit-equal' if same else 'DIFFERENT'}")
+        ok = ok and same
+    except ImportError as ex:
+        print(f"  [14] pyiqa's clean resize not compared: {ex}")
+    fa, fb = rng.normal(0, 1, (4096, 2048)), rng.normal(0.05, 1.1, (4096, 2048))
+    (m1, s1), (m2, s2) = ef.statistics(fa), ef.statistics(fb)
+    ref, got = float(calculate_frechet_distance(m1, s1, m2, s2)), ef.frechet_distance(m1, s1, m2, s2)
+    print(f"  [14] pytorch-fid distance {ref:.6f} vs evaluate_fid.frechet_distance {got:.6f}")
+    return ok and abs(got - ref) <= 1e-6 * abs(ref)
+
+
 def pin_musiq(out):
     """pyiqa's `musiq` against tools/evaluate_musiq.py on the koniq10k weights pyiqa itself loads (its network's state dict)."""
     import importlib.util
@@ -431,7 +478,7 @@ def main():
                            ("open_clip (item 4)", pin_clip, ()), ("pyiqa (item 5)", pin_iqa, ()), ("ftfy (item 6)", pin_ftfy, ()), ("lpips (item 7)", pin_lpips, ()),
                            ("pyiqa NIQE (item 8)", pin_niqe, ()), ("pyiqa CLIP-IQA (item 9)", pin_clipiqa, (a.clip_bpe,)),
                            ("OpenCV degradation steps (item 10)", pin_degrade, ()), ("pyiqa MUSIQ (item 11)", pin_musiq, ()),
-                           ("pyiqa MANIQA (item 12)", pin_maniqa, ()), ("pyiqa DISTS (item 13)", pin_dists, ())):
+                           ("pyiqa MANIQA (item 12)", pin_maniqa, ()), ("pyiqa DISTS (item 13)", pin_dists, ()), ("pytorch-fid / pyiqa FID (item 14)", pin_fid, ())):
         print(name)
         try:
             verdict[name] = fn(out, *args)
