@@ -86,6 +86,8 @@ def parse_args():
     ap.add_argument("--save_lq", default=None, metavar="DIR", help="with --degrade: write the synthesised LQ crops to DIR")
     ap.add_argument("--jpeg_decoder", default="host", choices=["host", "gpu"], help="inference.py's flag; `gpu` only together with --center_crop gpu: without it "
                     "every input is centre-cropped on the host (a BOX filter halves large files), which inference.py --jpeg_decoder gpu refuses as --use_center_crop")
+    ap.add_argument("--png_decoder", default="host", choices=["host", "gpu"], help="inference.py's flag, under --jpeg_decoder's condition: `gpu` only together "
+                    "with --center_crop gpu. Both decoder flags may be given")
     ap.add_argument("--center_crop", default="host", choices=["host", "gpu"], help="who centre-crops the inputs to --image_size. host (default): PIL on the reader "
                     "threads (center_crop_arr). gpu: the decoded file - with --jpeg_decoder gpu the compressed bytes of a baseline JPEG - is uploaded and the "
                     "device makes the same pixels (inference.py --center_crop gpu: BOX halvings, the bicubic resize, the central window); with --degrade the crop "
@@ -115,6 +117,11 @@ def main():
         args.jpeg_decode_log = []   # per file None (decoded on the device) or the reason it took the host decoder
     elif args.jpeg_decoder == "gpu":
         raise SystemExit("--jpeg_decoder gpu decodes into the device's resize route, and this tool centre-crops every input on the host (as inference.py "
+                         "--use_center_crop, where the flag is refused too): not offered (or give --center_crop gpu)")
+    if args.png_decoder == "gpu" and crop_gpu:
+        args.png_decode_log = []
+    elif args.png_decoder == "gpu":
+        raise SystemExit("--png_decoder gpu decodes into the device's resize route, and this tool centre-crops every input on the host (as inference.py "
                          "--use_center_crop, where the flag is refused too): not offered (or give --center_crop gpu)")
     ext_out = cli.save_ext(args)
     niqe_params = cli.load_niqe_params(args)
@@ -193,14 +200,7 @@ def main():
     def read(f):
         gt = np.ascontiguousarray(center_crop_arr(lookup.load(f), args.image_size)) if lookup else None
         if crop_gpu:   # decode only (--jpeg_decoder gpu: the headers and one byte pass); the device crops, and degrades the crop
-            source = None
-            if args.jpeg_decoder == "gpu":
-                from instarevive_amd.jpeg_decode import JpegSource
-                with open(f, "rb") as fh:
-                    source, why = JpegSource.open(fh.read())
-                args.jpeg_decode_log.append(why)
-                if source is not None:
-                    source.name = f
+            source = cli.device_source(f, args)   # --jpeg_decoder gpu / --png_decoder gpu
             raw = np.array(Image.open(f).convert("RGB")) if source is None else source
             job = ResizeJob(raw, crop_geometry((raw.shape[1], raw.shape[0]), 1, args.image_size))
             if recipe is None:
@@ -282,6 +282,8 @@ def main():
     print(f"[rank {rank}] saved {pools.written} files")
     if cli.jpeg_decoder_note(args):
         print(f"[rank {rank}] {cli.jpeg_decoder_note(args)}")
+    if cli.png_decoder_note(args):
+        print(f"[rank {rank}] {cli.png_decoder_note(args)}")
     if gpu_png:
         print(f"[rank {rank}] --png_encoder gpu: 0 of {pools.written} files took the host encoder")
     if gpu_jpg:

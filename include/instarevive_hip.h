@@ -49,7 +49,10 @@ enum { IR_STAGE_SWINIR = 0, IR_STAGE_VAE_ENCODE = 1, IR_STAGE_DIT = 2, IR_STAGE_
                                ir_maniqa accepts; n * crops: everything at once); depends on these and on the shape bound by
                                ir_maniqa_configure, not on h x w (0 for a context that is not configured) */,
        IR_STAGE_DISTS = 23 /* ir_dists: n pairs, h, w = the compared rectangle; depends on the sizes alone (ctx may be NULL) */,
-       IR_STAGE_FID = 24 /* ir_fid_features: n images; depends on n alone (ctx may be NULL, h and w do not matter) */ };
+       IR_STAGE_FID = 24 /* ir_fid_features: n images; depends on n alone (ctx may be NULL, h and w do not matter) */,
+       IR_STAGE_PNG_DECODE = 25 /* ir_png_decode: h, w = the largest height and width among the files, flags = the largest stream_bytes,
+                                   tile_size = span_bits; holds for any colour type; the files of a batch share one workspace, so n only has
+                                   to be >= 1; depends on these numbers alone (ctx may be NULL) */ };
 /* ir_pipeline flags */
 enum { IR_FLAG_NO_PREPROCESS = 1, IR_FLAG_TILED = 2, IR_FLAG_FIX_WAVELET = 4, IR_FLAG_FIX_ADAIN = 8,
        /* ir_pipeline only, needs ir_dit_control_configure: run the DiT step with the ControlNet-Half branch, condition latent
@@ -377,6 +380,47 @@ typedef struct ir_jpeg_file {
 } ir_jpeg_file;
 int ir_jpeg_decode(ir_ctx* ctx, void* stream, const ir_jpeg_file* files, int n, int subseq_bits, uint32_t* info, int16_t* coef_or_null, void* ws,
                    size_t ws_bytes);
+
+/* PNG decoding on the device (the reference reads its inputs through PIL: Image.open(path).convert("RGB")). Decodes n files of differing sizes
+ * and colour types into HWC RGB8 images; the pixels are Pillow's (inflate of RFC 1950 / 1951, the PNG unfilter, grey replicated, alpha dropped;
+ * definition: tools/png_decode_model.py). The host reads the chunks, checks their CRCs and joins the IDAT payloads
+ * (instarevive_amd.png_decode.PngSource); it inflates nothing. `files` is a HOST array of n records, read before the call returns:
+ *   stream, stream_bytes  the zlib stream (2 header bytes, deflate blocks, Adler-32 trailer) as a device pointer, 4-byte aligned, zero-padded to
+ *                         stream_bytes, a multiple of 4 in 8 .. 2^28
+ *   adler                 the trailer's value
+ *   h, w                  1 .. 65535 each, with h (1 + 4 w) below 2^31
+ *   color_type            0 grey, 2 RGB, 4 grey + alpha, 6 RGBA: 1, 3, 2, 4 bytes a pixel (bpp), 8 bits a sample, not interlaced
+ *   out, pitch            the image [h][pitch] bytes, pitch >= 3 w; only the first 3 w bytes of each of the h rows are written
+ * Phases, each a kernel boundary (no workgroup ever waits for another): (1) every bit offset is tested as the start of a dynamic-Huffman block
+ * and the first such candidate of every span of span_bits bits (a multiple of 32 in 256 .. 2^20) is recorded; (2) from bit 16 and from every
+ * candidate one decoder walks blocks of any type, counting output bytes, until a block ends on the candidate recorded for the span it ends in,
+ * until BFINAL or an error; (3) one lane follows these entries from bit 16 - candidates it does not reach are ignored, so a false candidate
+ * costs time only - and gives every entry on the chain its output offset; (4) the chain's entries are decoded again: a literal byte i gets
+ * src[i] = i, a copied byte src[i] = i - distance; (5) ceil(log2(inflated bytes)) rounds of src[i] = src[src[i]], each returning at once when
+ * the round before changed nothing, then byte[i] = literal[src[i]]; (6) Adler-32 in parallel; (7) the unfilter (one workgroup, lane = row,
+ * skewed) and the conversion to RGB. A stream without a dynamic block is one lane's serial walk. info[i] = 0, or the first error of file i: 1 bad
+ * block type or block header, 2 invalid code, 3 read past the end, 4 distance before the start, 5 stored-length mismatch, 6 wrong inflated size,
+ * 7 Adler mismatch, 8 filter type above 4; the pixels of such a file are unspecified (inside its image). Every read of the stream is guarded by
+ * stream_bytes and every write by the sizes above, whatever the bytes say. Stream-ordered, no allocation, no host synchronisation; the number
+ * of launches depends on n and on the sizes alone. ws: 256-byte aligned, ir_workspace_bytes(ctx, IR_STAGE_PNG_DECODE, n, max h, max w,
+ * max stream_bytes, span_bits, 0) bytes; sections of 256-byte multiples, in this order, sized for the call's largest h, w (at 4 bytes a
+ * pixel: cap = h (1 + 4 w)) and stream_bytes (spans = ceil(8 stream_bytes / span_bits), entries = spans + 1: entry 0 is bit 16, entry k + 1 span
+ * k's candidate): 64 uint32 (0 the error, 1 the chain's length, 2 its inflated size, 3 the Adler-32 found, 16.. the rounds' flags);
+ * candidates [spans] uint32 (bit offset or 0xffffffff); [entries] uint32 each: end bit, next entry (0xffffffff: none), output length, status,
+ * output offset, the chain's entries in order; Adler partial sums [2 ceil(cap / 16384)] uint32; src [cap] uint32; literals [cap]; the
+ * inflated bytes [cap + 32]; the unfiltered rows, h (4 w + 32) bytes (a file's rows lie (w bpp rounded up to 16) + 16 bytes apart). After the
+ * call they hold the last file's values.
+ * Returns -1 (nothing launched) for a null pointer, n < 1, span_bits outside the above, a record with a size, colour type, alignment or pitch
+ * outside the above, or a short or misaligned workspace. */
+typedef struct ir_png_file {
+    const uint8_t* stream;
+    uint8_t* out;
+    uint32_t stream_bytes;
+    uint32_t adler;
+    int h, w, color_type;
+    long pitch;
+} ir_png_file;
+int ir_png_decode(ir_ctx* ctx, void* stream, const ir_png_file* files, int n, int span_bits, uint32_t* info, void* ws, size_t ws_bytes);
 
 /* Pillow's resampling of 8-bit RGB images on the device (PIL.Image.resize with BICUBIC / LANCZOS, Resample.c): what the command line does to
  * every input (--sr_scale, auto_resize: inference.py:263-291) and to the results of enlarged inputs (LANCZOS back to the LQ size, :323-346).

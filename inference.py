@@ -176,6 +176,11 @@ def parse_args() -> Namespace:
                         "a reader thread parses the headers and removes the byte stuffing, the compressed bytes are uploaded and ir_jpeg_decode makes PIL's "
                         "pixels on the device (baseline files, grey or YCbCr 4:4:4 / 4:2:2 / 4:2:0; every other file, JPEG or not, takes PIL as today and the "
                         "run says how many). Switches --resize gpu on; not offered with --show_lq, --use_center_crop (unless --center_crop gpu), --shard_tiles")
+    parser.add_argument("--png_decoder", type=str, default="host", choices=["host", "gpu"], help="who decodes PNG inputs. host (default): PIL, as the reference. gpu: "
+                        "a reader thread walks the chunks and checks their CRCs, the compressed bytes are uploaded and ir_png_decode inflates, unfilters and "
+                        "converts on the device to PIL's pixels (8 bits a sample, grey / RGB with or without alpha, not interlaced; every other file, PNG or "
+                        "not, takes PIL as today and the run says how many). May be given together with --jpeg_decoder gpu. Switches --resize gpu on; not "
+                        "offered with --show_lq, --use_center_crop (unless --center_crop gpu), --shard_tiles")
     parser.add_argument("--center_crop", type=str, default="host", choices=["host", "gpu"], help="who makes the centre crop of --use_center_crop. host (default): PIL on a "
                         "reader thread, as the reference does (center_crop_arr: BOX halvings, a bicubic resize of the short edge to 512, the central window). gpu: "
                         "the decoded file - or, with --jpeg_decoder gpu, its compressed bytes - is uploaded and the device runs the same chain with Pillow's own "
@@ -264,6 +269,52 @@ def jpeg_decoder_note(args: Namespace) -> str:
     reasons = ", ".join(f"{r}: {host.count(r)}" for r in sorted(set(host)))
     return (f"--jpeg_decoder gpu: {len(log) - len(host)} of {len(log)} files were decoded on the device, {len(host)} took the host decoder"
             + (f" (reasons: {reasons})" if host else ""))
+
+
+def check_png_decoder(args: Namespace) -> None:
+    """--png_decoder gpu decodes into the device's resize route, as --jpeg_decoder gpu does: it switches --resize gpu on and makes the same refusals."""
+    if getattr(args, "png_decoder", "host") != "gpu":
+        return
+    for flag in ("show_lq", "use_center_crop", "shard_tiles"):
+        if getattr(args, flag, False) and not (flag == "use_center_crop" and crop_on_gpu(args)):
+            raise SystemExit(f"--png_decoder gpu decodes into the device's resize route (--resize gpu), which --{flag} keeps on the host: not offered together"
+                             + (" (or give --center_crop gpu)" if flag == "use_center_crop" else ""))
+    if args.resize != "gpu":
+        print("--png_decoder gpu: the files are decoded on the device, switching --resize gpu on")
+        args.resize = "gpu"
+    args.png_decode_log = []   # per file None (decoded on the device) or the reason it took the host decoder; list.append is atomic
+
+
+def png_decoder_note(args: Namespace) -> str:
+    log = getattr(args, "png_decode_log", None)
+    if log is None:
+        return ""
+    host = [r for r in log if r is not None]
+    reasons = ", ".join(f"{r}: {host.count(r)}" for r in sorted(set(host)))
+    return (f"--png_decoder gpu: {len(log) - len(host)} of {len(log)} files were decoded on the device, {len(host)} took the host decoder"
+            + (f" (reasons: {reasons})" if host else ""))
+
+
+def device_source(file_path: str, args: Namespace):
+    """--jpeg_decoder gpu / --png_decoder gpu: the file as a JpegSource or PngSource (the headers and one pass over the bytes, on a reader thread), or
+    None for a file that takes PIL; the reason goes to the flag's log. With both flags a file with PNG's signature is the PNG decoder's, every
+    other one the JPEG decoder's."""
+    jlog, plog = getattr(args, "jpeg_decode_log", None), getattr(args, "png_decode_log", None)
+    if jlog is None and plog is None:
+        return None
+    with open(file_path, "rb") as f:
+        data = f.read()
+    if plog is not None and (jlog is None or data[:8] == b"\x89PNG\r\n\x1a\n"):
+        from instarevive_amd.png_decode import PngSource
+        source, why = PngSource.open(data)
+        plog.append(why)
+    else:
+        from instarevive_amd.jpeg_decode import JpegSource
+        source, why = JpegSource.open(data)
+        jlog.append(why)
+    if source is not None:
+        source.name = file_path
+    return source
 
 
 def save_ext(args: Namespace) -> str:
@@ -484,14 +535,7 @@ def read_job(file_path: str, repeat: int, args: Namespace) -> Job:
 
 def decode_job(file_path: str, repeat: int, args: Namespace) -> Job:
     from instarevive_amd.utils import auto_resize, center_crop_arr, get_file_name_parts, pad
-    source = None
-    if getattr(args, "resize_on_gpu", False) and getattr(args, "jpeg_decode_log", None) is not None:   # --jpeg_decoder gpu: the headers and one byte pass
-        from instarevive_amd.jpeg_decode import JpegSource
-        with open(file_path, "rb") as f:
-            source, why = JpegSource.open(f.read())
-        args.jpeg_decode_log.append(why)
-        if source is not None:
-            source.name = file_path
+    source = device_source(file_path, args) if getattr(args, "resize_on_gpu", False) else None   # --jpeg_decoder gpu / --png_decoder gpu
     lq = Image.open(file_path).convert("RGB") if source is None else None
     if getattr(args, "resize_on_gpu", False):   # decode only: the sizes are worked out here, the pixels are resampled on the device
         from instarevive_amd.resample import crop_geometry, job_geometry
@@ -690,6 +734,7 @@ def main() -> None:
     check_save_format(args)
     check_center_crop(args)
     check_jpeg_decoder(args)
+    check_png_decoder(args)
     niqe_params = load_niqe_params(args)
     clipiqa_model = load_clipiqa_model(args)
     musiq_model = load_musiq_model(args)
@@ -912,6 +957,8 @@ def main() -> None:
     t1 = time.perf_counter()
     if jpeg_decoder_note(args):
         print(f"[rank {rank}] {jpeg_decoder_note(args)}")
+    if png_decoder_note(args):
+        print(f"[rank {rank}] {png_decoder_note(args)}")
     if gpu_png:
         print(f"[rank {rank}] --png_encoder gpu: {host_files} of {pools.written} files took the host encoder (not a plain crop of the prediction)")
     if gpu_jpg:

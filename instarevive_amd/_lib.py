@@ -25,7 +25,7 @@ SYMBOLS = [
     "ir_unet_configure", "ir_unet_set_context", "ir_cldm_sample", "ir_cldm_pipeline", "ir_clip_text_configure", "ir_clip_text_encode", "ir_op_groupnorm_any", "ir_op_geglu",
     "ir_dit_set_prompts", "ir_op_attention_kv_groups", "ir_graph_records", "ir_op_vae_segment", "ir_op_vae_segment_ws", "ir_op_vae_segment_info",
     "ir_op_swin_shell", "ir_op_swin_shell_ws", "ir_op_dit_shell", "ir_op_dit_shell_ws", "ir_op_unet_block", "ir_op_unet_block_ws", "ir_op_text_block", "ir_op_text_block_ws",
-    "ir_png_bound", "ir_png_encode", "ir_png_encode_runs", "ir_jpeg_bound", "ir_jpeg_encode", "ir_jpeg_decode", "ir_resample_plan_bytes", "ir_resample_plan", "ir_resample_u8", "ir_resample_u8_window", "ir_metrics_y",
+    "ir_png_bound", "ir_png_encode", "ir_png_encode_runs", "ir_jpeg_bound", "ir_jpeg_encode", "ir_jpeg_decode", "ir_png_decode", "ir_resample_plan_bytes", "ir_resample_plan", "ir_resample_u8", "ir_resample_u8_window", "ir_metrics_y",
     "ir_lpips_scale_table", "ir_lpips_configure", "ir_lpips", "ir_dists_scale_table", "ir_dists_configure", "ir_dists", "ir_fid_resize_plan_bytes", "ir_fid_resize_plan", "ir_fid_configure", "ir_fid_features", "ir_niqe_window", "ir_niqe_stats",
     "ir_clipiqa_scale_table", "ir_clipiqa_configure", "ir_clipiqa", "ir_musiq_layout", "ir_musiq_input_table", "ir_musiq_configure", "ir_musiq",
     "ir_maniqa_input_table", "ir_maniqa_crops", "ir_maniqa_configure", "ir_maniqa",
@@ -46,6 +46,7 @@ STAGE_MUSIQ = 21
 STAGE_MANIQA = 22
 STAGE_DISTS = 23
 STAGE_FID = 24
+STAGE_PNG_DECODE = 25   # h, w = the largest sides, flags = the largest stream_bytes, tile_size = span_bits
 FID_RESIZE_CLEAN, FID_RESIZE_LEGACY = 0, 1
 FID_SIZE, FID_DIM, FID_BLOCK_CHANNELS = 299, 2048, 10304
 DEGRADE_NORM_NONE, DEGRADE_NORM_MAX = 0, 1
@@ -117,6 +118,12 @@ class JpegFile(C.Structure):
     _fields_ = [("stream", C.c_void_p), ("intervals", C.c_void_p), ("tables", C.c_void_p), ("out", C.c_void_p), ("pitch", C.c_long),
                 ("stream_bytes", C.c_uint32), ("n_intervals", C.c_int), ("h", C.c_int), ("w", C.c_int), ("comps", C.c_int), ("hs", C.c_int),
                 ("vs", C.c_int), ("restart_mcus", C.c_int), ("tq", C.c_uint8 * 4), ("td", C.c_uint8 * 4), ("ta", C.c_uint8 * 4)]
+
+
+class PngFile(C.Structure):
+    """ir_png_file (include/instarevive_hip.h): one file's record; stream and out are device addresses."""
+    _fields_ = [("stream", C.c_void_p), ("out", C.c_void_p), ("stream_bytes", C.c_uint32), ("adler", C.c_uint32), ("h", C.c_int), ("w", C.c_int),
+                ("color_type", C.c_int), ("pitch", C.c_long)]
 
 
 class NativeLibraryError(RuntimeError):
@@ -250,6 +257,7 @@ def load_library():
     lib.ir_jpeg_bound.restype = sz
     lib.ir_jpeg_encode.argtypes = [vp, vp, vp, i, i, i, C.c_long, i, i, i, i, i, vp, sz, vp, vp, sz]
     lib.ir_jpeg_decode.argtypes = [vp, vp, C.POINTER(JpegFile), i, i, vp, vp, vp, sz]
+    lib.ir_png_decode.argtypes = [vp, vp, C.POINTER(PngFile), i, i, vp, vp, sz]
     lib.ir_resample_plan_bytes.argtypes = [i, i, i, i, i]
     lib.ir_resample_plan_bytes.restype = sz
     lib.ir_resample_plan.argtypes = [i, i, i, i, i, vp, sz]

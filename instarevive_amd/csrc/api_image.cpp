@@ -206,6 +206,28 @@ int ir_jpeg_decode(ir_ctx* c, void* stream, const ir_jpeg_file* files, int n, in
     return 0;
 }
 
+// ---------------------------------------------------------------- PNG decoding (png_decode.hip)
+int ir_png_decode(ir_ctx* c, void* stream, const ir_png_file* files, int n, int span_bits, uint32_t* info, void* ws, size_t ws_bytes) {
+    if (!c || !files || !info || !ws) return fail(c, -1, "ir_png_decode: null argument");
+    if (n < 1) return fail(c, -1, "ir_png_decode: n %d", n);
+    if (span_bits < 256 || span_bits > (1 << 20) || span_bits % 32) return fail(c, -1, "ir_png_decode: span_bits %d is no multiple of 32 in 256 .. 2^20", span_bits);
+    if (reinterpret_cast<uintptr_t>(info) & 3) return fail(c, -1, "ir_png_decode: misaligned info pointer");
+    int mh = 0, mw = 0;
+    uint32_t ms = 0;
+    for (int i = 0; i < n; ++i) {   // every file is checked before the first launch
+        const char* why;
+        if (ir_png_decode_check(&files[i], &why)) return fail(c, -1, "ir_png_decode: file %d (%d x %d): %s", i, files[i].h, files[i].w, why);
+        mh = std::max(mh, files[i].h), mw = std::max(mw, files[i].w), ms = std::max(ms, files[i].stream_bytes);
+    }
+    IrPngLayout L;   // one layout for the batch: the sections lie where ir_workspace_bytes's arguments put them
+    if (!ir_png_decode_layout(mh, mw, ms, span_bits, &L)) return fail(c, -1, "ir_png_decode: %d x %d with %u stream bytes is outside the contract", mh, mw, ms);
+    if (int e = check_ws(c, "ir_png_decode", ws, ws_bytes, L.total, 256)) return e;
+    use_ctx(c);
+    for (int i = 0; i < n; ++i)
+        if (ir_launch_png_decode(&files[i], span_bits, info + i, ws, L, (hipStream_t)stream)) return fail(c, -100, "ir_png_decode: launch failed (file %d)", i);
+    return 0;
+}
+
 // ---------------------------------------------------------------- Pillow's 8-bit resampling (resample.hip)
 // The tables of Resample.c's precompute_coeffs + normalize_coeffs_8bpc. Plain double arithmetic in Pillow's order of operations (no contraction
 // into fused multiply-adds): the quantised coefficients have to be Pillow's to the last bit.
@@ -1200,6 +1222,7 @@ bool ir_host::image_workspace(ir_ctx* c, int stage, int n, int h, int w, int fla
         case IR_STAGE_METRICS: if (some) *bytes = metrics_workspace(n, h, w); break;
         case IR_STAGE_JPEG: if (ir_jpeg_layout(n, h, w, flags, tile_size, &jl)) *bytes = jl.total; break;   // flags: the subsampling, tile_size: restart_mcus
         case IR_STAGE_JPEG_DECODE: if (n >= 1) *bytes = ir_jpeg_decode_workspace(h, w, (uint32_t)flags, tile_size); break;   // flags: stream_bytes, tile_size: subseq_bits
+        case IR_STAGE_PNG_DECODE: if (n >= 1) *bytes = ir_png_decode_workspace(h, w, (uint32_t)flags, tile_size); break;   // flags: stream_bytes, tile_size: span_bits
         case IR_STAGE_PNG: if (some) *bytes = png_layout(n, h, w).total; break;
         case IR_STAGE_PNG_RUNS: if (some) *bytes = png_runs_layout(n, h, w).total; break;
         case IR_STAGE_RESAMPLE: if (some) *bytes = rs_workspace(n, h, w); break;   // n images, h = in_h, w = out_w: the uint8 image between the passes

@@ -274,6 +274,21 @@ size_t ir_jpeg_decode_workspace(int h, int w, uint32_t stream_bytes, int subseq_
 long ir_jpeg_decode_blocks(const ir_jpeg_file* f);
 int ir_launch_jpeg_decode(const ir_jpeg_file* f, int subseq_bits, uint32_t* info, int16_t* coef, void* ws, hipStream_t s);
 
+// ---- PNG decoding into uint8 images (png_decode.hip); ir_png_file and the workspace's sections: include/instarevive_hip.h
+// ir_png_decode_check: 0, or -1 with *why for a record the kernels do not take. ir_png_decode_layout: the byte offsets of the workspace's sections
+// for files of at most h x w pixels and stream_bytes at span_bits (false for sizes outside the contract); ir_png_decode_workspace: its total, or 0.
+// ir_launch_png_decode: one file's chain of launches; ws: that many bytes, 256-byte aligned.
+#define IR_PNG_ADLER_CHUNK 16384
+#define IR_PNG_UNFILTER_LANES 1024
+struct ir_png_file;
+struct IrPngLayout {
+    size_t spans, entries, cap, chunks, hdr, cand, e_end, e_next, e_len, e_status, e_off, chain, adler, src, lit, bytes, pix, total;
+};
+int ir_png_decode_check(const ir_png_file* f, const char** why);
+bool ir_png_decode_layout(int h, int w, uint32_t stream_bytes, int span_bits, IrPngLayout* L);
+size_t ir_png_decode_workspace(int h, int w, uint32_t stream_bytes, int span_bits);
+int ir_launch_png_decode(const ir_png_file* f, int span_bits, uint32_t* info, void* ws, const IrPngLayout& L, hipStream_t s);
+
 // ---- Pillow's 8-bit resampling of uint8 images (resample.hip)
 // The plan (ir_resample_plan) is an int32 array: a header of IR_RESAMPLE_HEADER ints - [0] IR_RESAMPLE_MAGIC, [1..4] in_h, in_w, out_h, out_w, [5] the
 // filter, [6] ksize_h, [7] ksize_v, [8] / [9] the offsets (in ints, from the plan's start) of the horizontal bounds [out_w][2] and coefficients

@@ -337,7 +337,7 @@ class _Batch:
         from .slots import record_sizes
         ctx, st, slot, rs, (n, h, w) = self.ctx, self.st, self.slot, self.rs, self.shape
         if rs is not None:
-            rs.decode(self.records)   # the batch's JPEG files (jpeg_decode.JpegSource records), into the places of their pixels
+            rs.decode(self.records)   # the batch's JPEG and PNG files (JpegSource / PngSource records), into the places of their pixels
             if self.dparams is not None:
                 rs.degrade(self.records)
             rs.to_network(self.records, st.d_in[slot])
@@ -448,9 +448,9 @@ def process(model, control_imgs: List[np.ndarray], strength: float, color_fix_ty
     jpeg_quality (1 .. 100) and jpeg_subsampling (2 or 420: 4:2:0, 0 or 444: 4:4:4), byte for byte PIL's Image.save(format="JPEG", quality,
     subsampling, restart_marker_blocks=jpeg.RESTART_MCUS) of the raw result. It combines with resize, degrade, gt, niqe and clipiqa as png does;
     the scores are those of the device's image, the result BEFORE the JPEG loss.
-    resize (fused form only): a list of one resample.ResizeJob per image - the DECODED file (or a jpeg_decode.JpegSource: the file's compressed bytes
-    are uploaded and ir_jpeg_decode makes the pixels on the device, Pillow's bytes; a stream the device cannot decode raises RuntimeError when the
-    batch is collected) and its job_geometry(). control_imgs is then not read:
+    resize (fused form only): a list of one resample.ResizeJob per image - the DECODED file (or a jpeg_decode.JpegSource / png_decode.PngSource: the file's
+    compressed bytes are uploaded and ir_jpeg_decode / ir_png_decode makes the pixels on the device, Pillow's bytes; a stream the device cannot
+    decode raises RuntimeError when the batch is collected) and its job_geometry(). control_imgs is then not read:
     the decoded bytes are uploaded, ir_resample_u8 makes the network input on the device (the bicubic chain of --sr_scale / auto_resize, the
     zero pad), and behind ir_pipeline the valid rectangle of every image that auto_resize enlarged is resampled (LANCZOS) back to its LQ size.
     Both lists then hold the FINAL images - what the command line saves: the resized result, else the valid rectangle - bit for bit what

@@ -78,8 +78,8 @@ def job_geometry(size: Tuple[int, int], sr_scale: float, tiled: bool, tile_size:
 
 
 class ResizeJob(NamedTuple):
-    """One image of a process(resize=...) batch: the decoded file (HWC uint8 RGB) - or a jpeg_decode.JpegSource, a JPEG file the device decodes
-    into the place the pixels would have been copied to - and its job_geometry()."""
+    """One image of a process(resize=...) batch: the decoded file (HWC uint8 RGB) - or a jpeg_decode.JpegSource / png_decode.PngSource, a JPEG or
+    PNG file the device decodes into the place the pixels would have been copied to - and its job_geometry()."""
     raw: np.ndarray
     geo: Geometry
 
@@ -201,11 +201,23 @@ def _is_jpeg(raw) -> bool:
     return isinstance(raw, JpegSource)
 
 
+def _is_png(raw) -> bool:
+    from .png_decode import PngSource
+    return isinstance(raw, PngSource)
+
+
+def _is_source(raw) -> bool:
+    """A file the device decodes: its compressed bytes travel, and its image's place in d_raw is filled by decode()."""
+    return _is_jpeg(raw) or _is_png(raw)
+
+
 def decode_ws_bytes(records: Sequence[ResizeJob]) -> int:
-    """Workspace of the batch's ir_jpeg_decode call (0 without JPEG files)."""
+    """Workspace of the batch's ir_jpeg_decode and ir_png_decode calls (the larger; 0 without such files)."""
     from . import jpeg_decode as J
-    sources = [rec.raw for rec in records if _is_jpeg(rec.raw)]
-    return J.ws_bytes(sources) if sources else 0
+    from . import png_decode as P
+    jpegs = [rec.raw for rec in records if _is_jpeg(rec.raw)]
+    pngs = [rec.raw for rec in records if _is_png(rec.raw)]
+    return max(J.ws_bytes(jpegs) if jpegs else 0, P.ws_bytes(pngs) if pngs else 0)
 
 
 def check_records(records: Sequence[ResizeJob]) -> Tuple[int, int, int]:
@@ -213,8 +225,8 @@ def check_records(records: Sequence[ResizeJob]) -> Tuple[int, int, int]:
         raise ValueError("resize: empty batch")
     for rec in records:
         a = rec.raw
-        if not _is_jpeg(a) and (not isinstance(a, np.ndarray) or a.dtype != np.uint8 or a.ndim != 3 or a.shape[-1] != 3):
-            raise ValueError("resize: the decoded files must be HWC uint8 RGB arrays (or jpeg_decode.JpegSource files)")
+        if not _is_source(a) and (not isinstance(a, np.ndarray) or a.dtype != np.uint8 or a.ndim != 3 or a.shape[-1] != 3):
+            raise ValueError("resize: the decoded files must be HWC uint8 RGB arrays (or jpeg_decode.JpegSource / png_decode.PngSource files)")
         if rec.geo.net_hw != records[0].geo.net_hw:
             raise ValueError("resize: the images of a batch must reach one network input size")
         last = rec.geo.chain[-1] if rec.geo.chain else (a.shape[1], a.shape[0])
@@ -262,12 +274,14 @@ class ResizeSlot(Pooled):
         self.lq_offsets: List[int] = []   # where every image's LQ image (and the centre crop it is made from) lies in d_lq / d_crop
         self.lq_bytes = 0
         self.jpeg: List[tuple] = []     # per JPEG file of the batch (a JpegSource record): its index and the offset of its compressed bytes
-        self.d_info = self.h_info = None   # ir_jpeg_decode's info words of the batch, device and page-locked
+        self.png: List[tuple] = []      # the same per PNG file (a PngSource record)
+        self.d_info = self.h_info = None   # ir_jpeg_decode's, then ir_png_decode's info words of the batch, device and page-locked
 
     def fill(self, records: Sequence[ResizeJob], degrade=None) -> None:
         """Copy the decoded files into the page-locked buffer (after the previous upload out of it has completed). degrade: one degrade.Params
         (or one degrade.ChainParams: a batch holds one kind) per image, or None - their blur kernels and noise fields travel behind the images.
-        A JpegSource keeps its image's place free and travels as compressed bytes behind all of that; decode() fills the place on the device."""
+        A JpegSource or PngSource keeps its image's place free and travels as compressed bytes behind all of that; decode() fills the place on
+        the device."""
         if degrade is not None:
             from . import degrade as D
             if len(degrade) != len(records):
@@ -290,11 +304,11 @@ class ResizeSlot(Pooled):
             self.lq_bytes += (int(np.prod(_lq_shape(rec))) + 255) & ~255
         if degrade is not None:
             at += sum(D.extra_bytes(p) for p in degrade)
-        self.jpeg = []
+        self.jpeg, self.png = [], []
         for i, rec in enumerate(records):
-            if _is_jpeg(rec.raw):
+            if _is_source(rec.raw):
                 at = (at + 255) & ~255
-                self.jpeg.append((i, at))
+                (self.jpeg if _is_jpeg(rec.raw) else self.png).append((i, at))
                 at += rec.raw.blob_bytes
         self.h_raw = _grown(self.h_raw, at, pinned=True)
         if self.d_raw is None or self.d_raw.numel() < self.h_raw.numel():
@@ -302,13 +316,13 @@ class ResizeSlot(Pooled):
         self.used = at
         host = self.h_raw.numpy()
         for rec, o in zip(records, self.offsets):
-            if not _is_jpeg(rec.raw):
+            if not _is_source(rec.raw):
                 np.copyto(host[o:o + rec.raw.size].reshape(rec.raw.shape), rec.raw)
         at = self.img_bytes
         for p in degrade or ():
             k_at, n_at, at = D.pack_extras(p, host, at)
             self.extras.append((k_at, n_at))
-        for i, b_at in self.jpeg:
+        for i, b_at in self.jpeg + self.png:
             records[i].raw.pack(host, b_at)
 
     def upload(self, stream=None, owner=None):
@@ -318,7 +332,7 @@ class ResizeSlot(Pooled):
         if self.fresh and owner is not None and stream is not None:
             stream.wait_stream(owner)
         self.fresh = False
-        first = self.img_bytes if self.jpeg and len(self.jpeg) == len(self.offsets) else 0   # a batch of JPEG files alone uploads no pixels
+        first = self.img_bytes if len(self.jpeg) + len(self.png) == len(self.offsets) else 0   # a batch of compressed files alone uploads no pixels
         self.d_raw[first:self.used].copy_(self.h_raw[first:self.used], non_blocking=True)
         ev = torch.cuda.Event()
         ev.record(stream if stream is not None else torch.cuda.current_stream(self.ctx.device))
@@ -327,20 +341,26 @@ class ResizeSlot(Pooled):
 
     def decode(self, records: Sequence[ResizeJob]) -> None:
         """Between upload() and degrade() / to_network(), on the current stream: every JPEG file of the batch is decoded (ir_jpeg_decode, one call)
-        into its image's place in d_raw. The info words follow with download_info() and are read by check_info()."""
+        and every PNG file (ir_png_decode, one call) into its image's place in d_raw. The info words - the JPEG files', then the PNG files' -
+        follow with download_info() and are read by check_info()."""
         from . import jpeg_decode as J
-        if not self.jpeg:
+        from . import png_decode as P
+        n = len(self.jpeg) + len(self.png)
+        if not n:
             return
-        n = len(self.jpeg)
         if self.d_info is None or self.d_info.numel() < n:
             self.d_info = torch.zeros(max(n, 16), dtype=torch.int32, device=self.ctx.device)
             self.h_info = torch.zeros(max(n, 16), dtype=torch.int32).pin_memory()
         base = self.d_raw.data_ptr()
-        J.launch(self.ctx, [records[i].raw.record(base + b_at, base + self.offsets[i]) for i, b_at in self.jpeg], self.d_info.data_ptr())
+        if self.jpeg:
+            J.launch(self.ctx, [records[i].raw.record(base + b_at, base + self.offsets[i]) for i, b_at in self.jpeg], self.d_info.data_ptr())
+        if self.png:
+            P.launch(self.ctx, [records[i].raw.record(base + b_at, base + self.offsets[i]) for i, b_at in self.png],
+                     self.d_info.data_ptr() + 4 * len(self.jpeg))
 
     def download_info(self) -> None:
         """Asynchronous D2H copy of decode()'s info words, on the current stream."""
-        if self.jpeg:
+        if self.jpeg or self.png:
             self.h_info.copy_(self.d_info, non_blocking=True)
 
     def check_info(self, records: Sequence[ResizeJob]) -> None:
@@ -351,6 +371,12 @@ class ResizeSlot(Pooled):
             if cls:
                 name = getattr(records[i].raw, "name", None) or f"image {i} of the batch"
                 raise RuntimeError(f"ir_jpeg_decode: {name} is not a valid baseline JPEG stream ({J.ERRORS.get(cls, cls)})")
+        from . import png_decode as P
+        for k, (i, _) in enumerate(self.png):
+            cls = int(self.h_info[len(self.jpeg) + k])
+            if cls:
+                name = getattr(records[i].raw, "name", None) or f"image {i} of the batch"
+                raise RuntimeError(f"ir_png_decode: {name} is not a valid PNG stream ({P.ERRORS.get(cls, cls)})")
 
     def degrade(self, records: Sequence[ResizeJob]) -> None:
         """Between upload() and to_network(), on the current stream: every decoded file (ground truth) becomes its LQ image in d_lq, at the
