@@ -67,6 +67,8 @@ def parse_args():
     ap.add_argument("--niqe_params", default=None, help="score NIQE (no reference needed) of both output folders on the GPU (inference.py --niqe_params: "
                     "niqe_modelparameters.mat or an .npz). Works without --gt: the CSVs are then file,niqe; with --gt the column comes last. --image_size must "
                     "be at least 192 for two blocks")
+    ap.add_argument("--ilniqe_params", default=None, help="score IL-NIQE (no reference needed) of both output folders on the GPU (inference.py --ilniqe_params: "
+                    "ILNIQE_templateModel.mat or an .npz). Works with or without --gt and the other metric flags; its column stands right behind niqe's place")
     ap.add_argument("--clipiqa_model", default=None, help="score CLIP-IQA (no reference needed) of both output folders on the GPU (inference.py --clipiqa_model: "
                     "OpenAI's RN50.pt or an .npz). Works with or without --gt and --niqe_params; its column comes last. --image_size must be at least 32")
     ap.add_argument("--musiq_model", default=None, help="score MUSIQ (no reference needed) of both output folders on the GPU (inference.py --musiq_model: an .npz "
@@ -125,12 +127,13 @@ def main():
                          "--use_center_crop, where the flag is refused too): not offered (or give --center_crop gpu)")
     ext_out = cli.save_ext(args)
     niqe_params = cli.load_niqe_params(args)
+    ilniqe_params = cli.load_ilniqe_params(args)
     clipiqa_model = cli.load_clipiqa_model(args)
     musiq_model = cli.load_musiq_model(args)
     maniqa_model = cli.load_maniqa_model(args)
     dists_weights = cli.load_dists_weights(args)
     fid_weights, fid_stats = cli.load_fid(args)
-    noref = bool(niqe_params) or clipiqa_model is not None or musiq_model is not None or maniqa_model is not None
+    noref = bool(niqe_params) or ilniqe_params is not None or clipiqa_model is not None or musiq_model is not None or maniqa_model is not None
     recipe = geo = None
     if args.save_lq and not args.degrade:
         raise SystemExit("--save_lq writes the images --degrade synthesises: give --degrade as well")
@@ -173,7 +176,7 @@ def main():
     if args.lpips_alexnet and not args.lpips_lin:
         raise SystemExit("--lpips_alexnet needs --lpips_lin (the lpips linear heads)")
     with_lpips = {"lpips": True} if args.lpips_lin else {}
-    with_niqe = {**({"niqe": True} if niqe_params else {}), **({"clipiqa": True} if clipiqa_model else {}), **({"musiq": True} if musiq_model else {}),
+    with_niqe = {**({"niqe": True} if niqe_params else {}), **({"ilniqe": True} if ilniqe_params else {}), **({"clipiqa": True} if clipiqa_model else {}), **({"musiq": True} if musiq_model else {}),
                  **({"maniqa": True} if maniqa_model else {}), **({"paired": bool(args.gt)} if noref else {}), **({"dists": True} if dists_weights else {})}
     lookup = None
     if args.gt or noref:
@@ -187,6 +190,9 @@ def main():
         if dists_weights:
             from instarevive_amd import dists
             dists.configure(m.model.ctx, dists_weights)
+        if ilniqe_params:
+            from instarevive_amd import ilniqe
+            ilniqe.configure(m.model.ctx)
         if clipiqa_model:
             from instarevive_amd import clipiqa
             clipiqa.configure(m.model.ctx, clipiqa_model)
@@ -250,13 +256,13 @@ def main():
                              y=m.y, y_mask=m.y_mask, noise_scheduler=m.noise_scheduler, return_stage1=True,
                              png=whole if gpu_png else None, png_wrap=False, png_runs=args.png_runs,
                              **({"jpeg": whole, "jpeg_quality": args.jpeg_quality, "jpeg_subsampling": args.jpeg_subsampling} if gpu_jpg else {}),
-                             gt=cli.in_step(truths) if lookup else None, **with_lpips, **({"niqe": niqe_params} if niqe_params else {}),
+                             gt=cli.in_step(truths) if lookup else None, **with_lpips, **({"niqe": niqe_params} if niqe_params else {}), **({"ilniqe": ilniqe_params} if ilniqe_params else {}),
                              **({"clipiqa": True} if clipiqa_model else {}), **({"musiq": True} if musiq_model else {}), **({"dists": True} if dists_weights else {}),
                              **({"fid": args.fid_resize} if fid_run else {}),
                              **({"maniqa": [[os.path.basename(out_name(args.output, args.input, f, ext_out)) for f in group] for group in batches]} if maniqa_model else {}),
                              **({"resize": cli.in_step(records)} if recipe or crop_gpu else {}),
                              **({"degrade": cli.in_step(dparams), "lq_sink": lq_images.append if args.save_lq else None} if recipe else {}))
-    no_score = {"niqe": 0, "clipiqa": 0, "musiq": 0, "maniqa": 0, "dists": 0}
+    no_score = {"niqe": 0, "ilniqe": 0, "clipiqa": 0, "musiq": 0, "maniqa": 0, "dists": 0}
     for group, out in zip(batches, results):
         preds, stage1 = out[:2]
         if fid_run:   # every image is a whole crop saved as the device leaves it: every file enters the set
@@ -291,7 +297,7 @@ def main():
     if reports:
         for rep, folder in zip(reports, (args.output, cond_dir)):
             lines = rep.write()
-            print(f"[rank {rank}] {' / '.join(f for f, on in (('--gt', args.gt), ('--niqe_params', niqe_params), ('--clipiqa_model', clipiqa_model), ('--musiq_model', musiq_model), ('--maniqa_model', maniqa_model)) if on)}: scored {len(rep.rows)} files of {folder}"
+            print(f"[rank {rank}] {' / '.join(f for f, on in (('--gt', args.gt), ('--niqe_params', niqe_params), ('--ilniqe_params', ilniqe_params), ('--clipiqa_model', clipiqa_model), ('--musiq_model', musiq_model), ('--maniqa_model', maniqa_model)) if on)}: scored {len(rep.rows)} files of {folder}"
                   + (f" against {args.gt}" if args.gt else "") + f" -> {rep.path}")
             for ln in lines:
                 print(ln)
@@ -303,6 +309,8 @@ def main():
             print(f"[rank {rank}] --maniqa_model: {no_score['maniqa']} files were not scored (MANIQA needs a short side above 224 pixels)")
         if no_score["niqe"]:
             print(f"[rank {rank}] --niqe_params: {no_score['niqe']} files were not scored (NIQE needs 96 x 96 blocks and two complete feature rows)")
+        if no_score["ilniqe"]:
+            print(f"[rank {rank}] --ilniqe_params: {no_score['ilniqe']} files were not scored (IL-NIQE needs two complete feature rows)")
         if no_score["dists"]:
             print(f"[rank {rank}] --dists_model: {no_score['dists']} files were not scored (DISTS is scored from 16 x 16 pixels)")
     if fid_run:

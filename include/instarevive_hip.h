@@ -52,7 +52,11 @@ enum { IR_STAGE_SWINIR = 0, IR_STAGE_VAE_ENCODE = 1, IR_STAGE_DIT = 2, IR_STAGE_
        IR_STAGE_FID = 24 /* ir_fid_features: n images; depends on n alone (ctx may be NULL, h and w do not matter) */,
        IR_STAGE_PNG_DECODE = 25 /* ir_png_decode: h, w = the largest height and width among the files, flags = the largest stream_bytes,
                                    tile_size = span_bits; holds for any colour type; the files of a batch share one workspace, so n only has
-                                   to be >= 1; depends on these numbers alone (ctx may be NULL) */ };
+                                   to be >= 1; depends on these numbers alone (ctx may be NULL) */,
+       IR_STAGE_ILNIQE = 27 /* ir_ilniqe_stats: h, w = the image size; the images of a batch share one workspace, so n only has to be >= 1;
+                               depends on w alone (ctx may be NULL) */,
+       IR_STAGE_ILNIQE_DFT = 26 /* ir_op_dft2_f64: h = w = size (252 or 504, 0 bytes for anything else); n only has to be >= 1; depends on the
+                                   size alone (ctx may be NULL) */ };
 /* ir_pipeline flags */
 enum { IR_FLAG_NO_PREPROCESS = 1, IR_FLAG_TILED = 2, IR_FLAG_FIX_WAVELET = 4, IR_FLAG_FIX_ADAIN = 8,
        /* ir_pipeline only, needs ir_dit_control_configure: run the DiT step with the ControlNet-Half branch, condition latent
@@ -585,6 +589,62 @@ int ir_fid_features(ir_ctx* ctx, void* stream, const uint8_t* img, int rows, lon
 int ir_niqe_window(double* k49);
 int ir_niqe_stats(ir_ctx* ctx, void* stream, const uint8_t* img, int rows, long pitch, int n, int h, int w, double* out, void* ws,
                   size_t ws_bytes);
+
+/* The pixel work of IL-NIQE (Zhang, Zhang and Bovik 2015; the no-reference metric `ilniqe` that the reference's evaluate_img.py keeps commented
+ * out next to `niqe`, and like it classical statistics against a small pristine model) on the device. tools/evaluate_ilniqe.py restates the
+ * definition in numpy fp64 and is the model of these calls; parity with pyiqa is unpinned (docs/parity.md). All arithmetic is fp64 with
+ * separate multiplies and adds, every sum has a fixed order and nothing uses floating-point atomics: an image gives the same bits on every
+ * call and at every position of a batch.
+ * The definition: (1) x = (double)v on 0 .. 255 is resized to 524 x 524 by MATLAB's antialiased bicubic imresize (a = -0.5; scale = 524 / in,
+ * the kernel widened by 1 / scale when scale < 1, ceil(width) + 2 taps, weights divided by their sum, symmetric padding; down the columns
+ * first, then along the rows, each output summed from 0.0 in tap order; clamped to [0, 255]) and the top-left 504 x 504 is used;
+ * (2) O1 = (0.3 R + 0.04 G) - 0.35 B, O2 = (0.34 R - 0.6 G) + 0.17 B, O3 = (0.06 R + 0.63 G) + 0.27 B; (3) per scale s = 1, 2 (scale 2:
+ * O1 .. O3, R, G, B through the 6 x 6 fspecial('gaussian', 6, 0.9), correlation with replicate padding and taps -2 .. +3, rows and columns
+ * 0, 2, 4, ... kept) 109 planes: 0 the MSCN values of O3 (5 x 5 window fspecial('gaussian', 5, 5/6), replicate padding, mu and m2 as 25-tap
+ * sums from 0.0 in row-major order, (O3 - mu) / (sqrt(|m2 - mu mu|) + 1)); 1-3 sqrt(Ix^2 + Iy^2 + 1e-8) of O1 .. O3 with Ix, Iy =
+ * conv2(., 'same') by x g(x) g(y) and y g(y) g(x) on -5 .. 5, sigma 1.66 / s^0.28, as two 11-tap passes (rows first, zero padding); 4-6 the
+ * log colour planes (l_c = log(c + 1e-5) minus its plane mean; (r + g + b) / sqrt 3, (r + g - 2 b) / sqrt 6, (r - g) / sqrt 2); 7-12 Ix, Iy
+ * of O1, O2, O3; 13-36 Re, Im of ifft2(F_f .* fft2(O3)) for the twelve log-Gabor filters f in (scale, orientation) order; 37-84 per filter
+ * dx Re, dy Re, dx Im, dy Im; 85-108 per filter sqrt(dx^2 + dy^2) + 1e-8 of Re and of Im; (4) per block of (84 / s)^2 pixels (36 per scale,
+ * row-major) IR_ILNIQE_STATS = 558 doubles: [0, 30) of plane 0's five fields (the value and its products with the copy shifted circularly
+ * inside the block by (0,1), (1,0), (1,1), (1,-1)) the six numbers count(p < 0), count(p > 0), sum p^2 over the negatives, over the
+ * positives, sum |p|, sum p^2; [30, 498) the same six numbers of planes 7-84; [498, 504) mean and unbiased variance of planes 4-6;
+ * [504, 558) the Weibull (k, lambda) of planes 1-3 and 85-108. A block is summed by one workgroup: thread t of 256 adds elements t, t + 256,
+ * ... (row-major) from 0.0, a wave folds by xor 32 .. 1, the four waves are added in turn. out is [n][2][36][558]. The asymmetric generalised
+ * Gaussian fits, the projection on the principal vectors and the score are host work (instarevive_amd/ilniqe.py).
+ * ir_ilniqe_plan_bytes / ir_ilniqe_plan (host only, no context): the resize tables of one input size h x w - idx0 [524][P0] and idx1 [524][P1]
+ * as int (0-based source rows / columns), padded to 8 bytes, then w0 [524][P0] and w1 [524][P1] as doubles; ir_ilniqe_stats takes a DEVICE
+ * copy of them as `plan`. -1 for h or w below 2, a null or misaligned pointer or too few bytes.
+ * ir_ilniqe_configure binds the fixed tables: the twiddle matrices cos / sin(2 pi (jk mod N) / N) of N = 252 and 504, computed here with jk
+ * reduced mod N in integers first, and copies of the uploaded double tensors ilniqe.win5 [25], ilniqe.win6 [36], ilniqe.taps [2][2][11]
+ * (scale, x g | g), ilniqe.bank252 and ilniqe.bank504 [12][N][N] (instarevive_amd/ilniqe.py: tables()); -2 when one is missing or of another
+ * size. It may be called again.
+ * ir_ilniqe_stats: img is [n][rows][pitch] bytes (RGB8, addressed as ir_metrics_y addresses a), every image h x w. ws: 8-byte aligned,
+ * ir_workspace_bytes(ctx, IR_STAGE_ILNIQE, n, h, w, 0, 0, 0) bytes (241 MB + 12 KB per column of w; the images of a batch take turns).
+ * Returns -1 (nothing launched, out untouched) for a null pointer, n < 1, h or w below 2, h above rows, a pitch below 3 w, a short or
+ * misaligned workspace, or a call before ir_ilniqe_configure.
+ * ir_op_dft2_f64: the 2-D DFT of a size x size plane (size 252 or 504, row-major doubles; im may be NULL for a real input):
+ * out[j][k] = sum_r sum_c x[r][c] exp(-/+ 2 pi i (j r + k c) / size), forward (inverse = 0, unscaled) or inverse (inverse != 0, times
+ * 1 / size^2), as two dense complex matrix products with the twiddle matrix on v_mfma_f64_16x16x4_f64: first down the columns (W x), then along
+ * the rows (. W). K is never padded (252 and 504 are multiples of 4); the tiles past the last row and column are computed on zeros and not
+ * stored. out_re and out_im must not overlap re, im or each other. ws: 8-byte aligned, ir_workspace_bytes(ctx, IR_STAGE_ILNIQE_DFT, 1, size,
+ * size, 0, 0, 0) bytes (the column transform, 4.1 MB at 504).
+ * ir_op_weibull_fit: the maximum-likelihood Weibull fit of each of `rows` rows of `count` positive doubles (x is [rows][count], count 2 ..
+ * 7056, one 84 x 84 block), one workgroup per row with ln x held in LDS: k0 = 1.2 / std(ln x) (unbiased), Newton on
+ * f(k) = sum(x^k ln x) / sum(x^k) - mean(ln x) - 1 / k with x^k = exp(k ln x), at most 50 steps, stopped when |k - k_prev| < 1e-2;
+ * lambda = mean(x^k)^(1 / k). k_lambda is [rows][2]: (k, lambda), which IL-NIQE stores as (scale, shape) = (lambda, k). A row with a value
+ * <= 0 or NaN gives NaN.
+ * All pointers of the three calls are device pointers; stream-ordered, no allocation, no host synchronisation (capturable). The two ops return
+ * -1 (nothing launched, the outputs untouched) for a null pointer (im excepted), a size other than 252 / 504, rows < 1, a count outside 2 ..
+ * 7056, a pointer not aligned to 8 bytes, a short workspace, or - ir_op_dft2_f64 - a call before ir_ilniqe_configure. */
+int ir_ilniqe_plan_bytes(int h, int w);
+int ir_ilniqe_plan(int h, int w, void* host_tables, size_t bytes);
+int ir_ilniqe_stats(ir_ctx* ctx, void* stream, const uint8_t* img, int rows, long pitch, int n, int h, int w, const void* plan, double* out,
+                    void* ws, size_t ws_bytes);
+int ir_ilniqe_configure(ir_ctx* ctx);
+int ir_op_dft2_f64(ir_ctx* ctx, void* stream, const double* re, const double* im_or_null, int size, int inverse, double* out_re, double* out_im,
+                   void* ws, size_t ws_bytes);
+int ir_op_weibull_fit(ir_ctx* ctx, void* stream, const double* x, int rows, int count, double* k_lambda);
 
 /* CLIP-IQA (the no-reference metric `clipiqa` of the reference's evaluate_img.py; pyiqa's default: OpenAI CLIP RN50, no positional embedding in
  * the attention pool, five antonym prompt pairs) on the device; tools/evaluate_clipiqa.py states the definition as a torch model and is the

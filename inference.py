@@ -137,6 +137,10 @@ def parse_args() -> Namespace:
                         "parameters mu_prisparam [36] / cov_prisparam [36][36]: pyiqa's niqe_modelparameters.mat, or an .npz. Works without --gt: the CSV is then "
                         "file,niqe and the average prints as `niqe: x.xxxxx`; with --gt the column and the line come last. Which files are scored follows --gt's "
                         "rule (the saved image is the device's image); files below 96 pixels on an edge or without two complete feature rows are counted as not scored")
+    parser.add_argument("--ilniqe_params", type=str, default=None, help="score IL-NIQE, the no-reference metric the reference's evaluate_img.py keeps commented out "
+                        "next to niqe, on the GPU (ir_ilniqe_stats; the definition of tools/evaluate_ilniqe.py). FILE is the user's ILNIQE_templateModel.mat, or an "
+                        ".npz with mu_prisparam / cov_prisparam / meanOfSampleData / principleVectors. Works with or without --gt and the other metric flags: the "
+                        "column `ilniqe` stands right behind niqe's place and the average prints as `ilniqe: x.xxxxx`. Which files are scored follows --gt's rule")
     parser.add_argument("--clipiqa_model", type=str, default=None, help="score CLIP-IQA, the no-reference metric `clipiqa` of the reference's evaluate_img.py, on "
                         "the GPU (ir_clipiqa; the definition of tools/evaluate_clipiqa.py, i.e. pyiqa's default over OpenAI CLIP RN50 at the image's own size). "
                         "FILE is OpenAI's RN50.pt (TorchScript archive or state dict), or an .npz with the same names - which may carry the ten text rows as "
@@ -379,6 +383,19 @@ def host_keeps_up(workers: int, out_pixels: int, compress_level, encoder: str = 
     return (f"host-bound: {workers} encoder threads write ~{host_rate:.1f} files/s of {out_pixels / 1e6:.1f} Mpixel against ~{gpu_rate:.1f} from the GPU - give the rank more "
             f"cores (--workers / $IR_WORKERS), or trade file size for speed with --png_compress_level 1 (same pixels, lossless)"
             + ("" if encoder == "gpu" else ", or encode photographs on the GPU with --png_encoder gpu"))
+
+
+def load_ilniqe_params(args: Namespace):
+    """--ilniqe_params: the template, read before any model is touched; a file that is missing or holds anything else ends the run."""
+    if not getattr(args, "ilniqe_params", None):
+        return None
+    from instarevive_amd.ilniqe import IlniqeError, load_params
+    if not os.path.isfile(args.ilniqe_params):
+        raise SystemExit(f"--ilniqe_params {args.ilniqe_params}: no such file")
+    try:
+        return load_params(args.ilniqe_params)
+    except IlniqeError as e:
+        raise SystemExit(str(e))
 
 
 def load_niqe_params(args: Namespace):
@@ -736,12 +753,15 @@ def main() -> None:
     check_jpeg_decoder(args)
     check_png_decoder(args)
     niqe_params = load_niqe_params(args)
+    ilniqe_params = load_ilniqe_params(args)
+    if ilniqe_params is not None and args.shard_tiles:
+        raise SystemExit("--ilniqe_params is not offered together with --shard_tiles (the assembled frame of the tile-sharded path is not scored on the device)")
     clipiqa_model = load_clipiqa_model(args)
     musiq_model = load_musiq_model(args)
     maniqa_model = load_maniqa_model(args)
     dists_weights = load_dists_weights(args)
     fid_weights, fid_stats = load_fid(args)
-    noref = bool(niqe_params) or clipiqa_model is not None or musiq_model is not None or maniqa_model is not None
+    noref = bool(niqe_params) or ilniqe_params is not None or clipiqa_model is not None or musiq_model is not None or maniqa_model is not None
     if args.save_lq and not args.degrade:
         raise SystemExit("--save_lq writes the images --degrade synthesises: give --degrade as well")
     if args.degrade:
@@ -791,9 +811,12 @@ def main() -> None:
         if args.gt:
             args.gt_lookup = GroundTruth(args.gt, args.input)
         report = Report(args.metrics_out or os.path.join(args.output, "metrics.csv" if world == 1 else f"metrics.rank{rank}.csv"),
-                        **({"lpips": True} if args.lpips_lin else {}), **({"niqe": True} if niqe_params else {}), **({"clipiqa": True} if clipiqa_model else {}),
+                        **({"lpips": True} if args.lpips_lin else {}), **({"niqe": True} if niqe_params else {}), **({"ilniqe": True} if ilniqe_params else {}), **({"clipiqa": True} if clipiqa_model else {}),
                         **({"musiq": True} if musiq_model else {}), **({"maniqa": True} if maniqa_model else {}), **({"paired": bool(args.gt)} if noref else {}),
                         **({"dists": True} if dists_weights else {}))
+        if ilniqe_params:
+            from instarevive_amd import ilniqe
+            ilniqe.configure(m.model.ctx)
         if dists_weights:
             from instarevive_amd import dists
             dists.configure(m.model.ctx, dists_weights)
@@ -911,13 +934,14 @@ def main() -> None:
     first = None    # (time, files) when the first result left the GPU: what follows is the steady state (no library / workspace warm-up in it)
     unscored = 0    # --gt / --niqe_params / --clipiqa_model / --musiq_model / --maniqa_model: files whose saved image is not the device's image
     # files below 96 pixels on an edge or without two complete feature rows; files below 32 pixels on an edge; files of which a resized side rounds to 0
-    no_score = {"niqe": 0, "clipiqa": 0, "musiq": 0, "maniqa": 0, "dists": 0}   # maniqa: files with a short side of 224 or less; dists: files below 16 x 16
+    no_score = {"niqe": 0, "ilniqe": 0, "clipiqa": 0, "musiq": 0, "maniqa": 0, "dists": 0}   # maniqa: files with a short side of 224 or less; dists: files below 16 x 16
     for out in process_stream(m.model, feed(), tiled=args.tiled, return_stage1=args.show_lq and not args.disable_preprocess_model,
                               fp8=args.fp8 != "off", png=in_step(rects) if gpu_png else None, png_wrap=False, png_runs=args.png_runs,
                               **({"jpeg": in_step(rects), "jpeg_quality": args.jpeg_quality, "jpeg_subsampling": args.jpeg_subsampling} if gpu_jpg else {}),
                               resize=in_step(records) if args.resize_on_gpu else None, gt=in_step(truths) if args.gt else None,
                               **({"lpips": True} if report and report.lpips else {}),
-                              **({"niqe": niqe_params} if niqe_params else {}), **({"clipiqa": True} if clipiqa_model else {}),
+                              **({"niqe": niqe_params} if niqe_params else {}), **({"ilniqe": ilniqe_params} if ilniqe_params else {}),
+                              **({"clipiqa": True} if clipiqa_model else {}),
                               **({"musiq": True} if musiq_model else {}), **({"maniqa": in_step(names)} if maniqa_model else {}),
                               **({"dists": True} if dists_weights else {}),
                               **({"fid": args.fid_resize, "fid_rects": in_step(fid_sizes)} if fid_run else {}),
@@ -966,12 +990,14 @@ def main() -> None:
               f"encoder (their saved image is not the device's image; the same bytes)")
     if report:
         lines = report.write()
-        what = " / ".join(f for f, on in (("--gt", args.gt), ("--niqe_params", niqe_params), ("--clipiqa_model", clipiqa_model), ("--musiq_model", musiq_model), ("--maniqa_model", maniqa_model)) if on)
+        what = " / ".join(f for f, on in (("--gt", args.gt), ("--niqe_params", niqe_params), ("--ilniqe_params", ilniqe_params), ("--clipiqa_model", clipiqa_model), ("--musiq_model", musiq_model), ("--maniqa_model", maniqa_model)) if on)
         print(f"[rank {rank}] {what}: scored {len(report.rows)} files" + (f" against {args.gt}" if args.gt else "") + f" -> {report.path}")
         for ln in lines:
             print(ln)
         if no_score["niqe"]:
             print(f"[rank {rank}] --niqe_params: {no_score['niqe']} of {pools.written} files were not scored (NIQE needs 96 x 96 blocks and two complete feature rows)")
+        if no_score["ilniqe"]:
+            print(f"[rank {rank}] --ilniqe_params: {no_score['ilniqe']} of {pools.written} files were not scored (IL-NIQE needs two complete feature rows)")
         if no_score["clipiqa"]:
             print(f"[rank {rank}] --clipiqa_model: {no_score['clipiqa']} of {pools.written} files were not scored (CLIP-IQA needs 32 x 32 pixels)")
         if no_score["musiq"]:

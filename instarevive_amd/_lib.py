@@ -26,7 +26,7 @@ SYMBOLS = [
     "ir_dit_set_prompts", "ir_op_attention_kv_groups", "ir_graph_records", "ir_op_vae_segment", "ir_op_vae_segment_ws", "ir_op_vae_segment_info",
     "ir_op_swin_shell", "ir_op_swin_shell_ws", "ir_op_dit_shell", "ir_op_dit_shell_ws", "ir_op_unet_block", "ir_op_unet_block_ws", "ir_op_text_block", "ir_op_text_block_ws",
     "ir_png_bound", "ir_png_encode", "ir_png_encode_runs", "ir_jpeg_bound", "ir_jpeg_encode", "ir_jpeg_decode", "ir_png_decode", "ir_resample_plan_bytes", "ir_resample_plan", "ir_resample_u8", "ir_resample_u8_window", "ir_metrics_y",
-    "ir_lpips_scale_table", "ir_lpips_configure", "ir_lpips", "ir_dists_scale_table", "ir_dists_configure", "ir_dists", "ir_fid_resize_plan_bytes", "ir_fid_resize_plan", "ir_fid_configure", "ir_fid_features", "ir_niqe_window", "ir_niqe_stats",
+    "ir_lpips_scale_table", "ir_lpips_configure", "ir_lpips", "ir_dists_scale_table", "ir_dists_configure", "ir_dists", "ir_fid_resize_plan_bytes", "ir_fid_resize_plan", "ir_fid_configure", "ir_fid_features", "ir_niqe_window", "ir_niqe_stats", "ir_ilniqe_plan_bytes", "ir_ilniqe_plan", "ir_ilniqe_configure", "ir_ilniqe_stats", "ir_op_dft2_f64", "ir_op_weibull_fit",
     "ir_clipiqa_scale_table", "ir_clipiqa_configure", "ir_clipiqa", "ir_musiq_layout", "ir_musiq_input_table", "ir_musiq_configure", "ir_musiq",
     "ir_maniqa_input_table", "ir_maniqa_crops", "ir_maniqa_configure", "ir_maniqa",
     "ir_degrade_qtables", "ir_degrade", "ir_degrade_chain",
@@ -46,6 +46,8 @@ STAGE_MUSIQ = 21
 STAGE_MANIQA = 22
 STAGE_DISTS = 23
 STAGE_FID = 24
+STAGE_ILNIQE = 27   # ir_ilniqe_stats: h, w = the image size
+STAGE_ILNIQE_DFT = 26   # h = w = size (252 | 504)
 STAGE_PNG_DECODE = 25   # h, w = the largest sides, flags = the largest stream_bytes, tile_size = span_bits
 FID_RESIZE_CLEAN, FID_RESIZE_LEGACY = 0, 1
 FID_SIZE, FID_DIM, FID_BLOCK_CHANNELS = 299, 2048, 10304
@@ -277,6 +279,12 @@ def load_library():
     lib.ir_fid_features.argtypes = [vp, vp, vp, i, C.c_long, i, i, i, i, vp, vp, vp, vp, vp, sz]
     lib.ir_niqe_window.argtypes = [vp]
     lib.ir_niqe_stats.argtypes = [vp, vp, vp, i, C.c_long, i, i, i, vp, vp, sz]
+    lib.ir_ilniqe_plan_bytes.argtypes = [i, i]
+    lib.ir_ilniqe_plan.argtypes = [i, i, vp, sz]
+    lib.ir_ilniqe_configure.argtypes = [vp]
+    lib.ir_ilniqe_stats.argtypes = [vp, vp, vp, i, C.c_long, i, i, i, vp, vp, vp, sz]
+    lib.ir_op_dft2_f64.argtypes = [vp, vp, vp, vp, i, i, vp, vp, vp, sz]
+    lib.ir_op_weibull_fit.argtypes = [vp, vp, vp, i, i, vp]
     lib.ir_clipiqa_scale_table.argtypes = [vp]
     lib.ir_clipiqa_configure.argtypes = [vp, C.POINTER(C.c_int), i, i, i, i, C.c_float]
     lib.ir_clipiqa.argtypes = [vp, vp, vp, i, C.c_long, i, i, i, vp, vp, vp, sz]

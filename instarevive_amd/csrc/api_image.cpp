@@ -1,4 +1,4 @@
-// The image tools of the C ABI: PNG and JPEG encoding, Pillow's resampling, PSNR-Y / SSIM-Y, LPIPS, DISTS, FID's features, CLIP-IQA, MUSIQ, MANIQA, NIQE and the two degradation paths. Each entry
+// The image tools of the C ABI: PNG and JPEG encoding, Pillow's resampling, PSNR-Y / SSIM-Y, LPIPS, DISTS, FID's features, CLIP-IQA, MUSIQ, MANIQA, NIQE, IL-NIQE's DFT and Weibull fit and the two degradation paths. Each entry
 // point checks its arguments and launches the kernels of its own .hip file; none of them runs a model stage, takes the workspace arena or is
 // profiled, so nothing here knows api.cpp's Run. Host code only, except for the tables the kernels read, which are computed here once.
 #include <math.h>
@@ -1104,6 +1104,101 @@ int ir_niqe_stats(ir_ctx* c, void* stream, const uint8_t* img, int rows, long pi
     return 0;
 }
 
+// ---------------------------------------------------------------- IL-NIQE's DFT and Weibull fit (ilniqe.hip)
+// the column transform, real and imaginary
+static size_t dft2_workspace(int size) { return size == 252 || size == 504 ? (size_t)2 * size * size * sizeof(double) : 0; }
+// the double tensor `name` of the context with exactly `count` values, or null with ir_last_error naming it
+static const double* exact_f64(ir_ctx* c, const char* who, const char* name, size_t count) {
+    auto it = c->t.find(name);
+    if (it == c->t.end() || it->second.bytes != count * 8) {
+        fail(c, -2, "%s: tensor %s (%s; %zu doubles are needed)", who, name, it == c->t.end() ? "missing" : "another size", count);
+        return nullptr;
+    }
+    return static_cast<const double*>(it->second.p);
+}
+int ir_ilniqe_plan_bytes(int h, int w) {
+    if (h < 2 || w < 2) return -1;
+    size_t a, b, d;
+    const size_t bytes = ir_ilniqe_plan_layout(h, w, &a, &b, &d);
+    return bytes > 0x7fffffff ? -1 : (int)bytes;
+}
+int ir_ilniqe_plan(int h, int w, void* host_tables, size_t bytes) {
+    const int need = ir_ilniqe_plan_bytes(h, w);
+    if (need < 0 || !host_tables || bytes < (size_t)need || (reinterpret_cast<uintptr_t>(host_tables) & 7)) return -1;
+    ir_ilniqe_plan_host(h, w, host_tables);
+    return 0;
+}
+int ir_ilniqe_configure(ir_ctx* c) {
+    if (!c) return -1;
+    HIPOK(c, hipSetDevice(c->device));
+    c->ilniqe.ok = false;
+    const char* const who = "ir_ilniqe_configure";
+    static const int sizes[2] = {252, 504};
+    const double *win5, *win6, *taps, *bank[2];   // every tensor is looked up before anything is replaced
+    if (!(win5 = exact_f64(c, who, "ilniqe.win5", 25)) || !(win6 = exact_f64(c, who, "ilniqe.win6", 36)) || !(taps = exact_f64(c, who, "ilniqe.taps", 44)) ||
+        !(bank[0] = exact_f64(c, who, "ilniqe.bank252", (size_t)12 * 252 * 252)) || !(bank[1] = exact_f64(c, who, "ilniqe.bank504", (size_t)12 * 504 * 504)))
+        return -2;
+    IrIlniqeTables m;
+    std::vector<void*>& own = c->own[OWN_ILNIQE];
+    release_list(own);
+    HIPOK(c, hipDeviceSynchronize());
+    HIPOK(c, hipMemcpy(m.win5, win5, sizeof m.win5, hipMemcpyDeviceToHost));
+    HIPOK(c, hipMemcpy(m.win6, win6, sizeof m.win6, hipMemcpyDeviceToHost));
+    HIPOK(c, hipMemcpy(m.taps, taps, sizeof m.taps, hipMemcpyDeviceToHost));
+    for (int k = 0; k < 2; ++k) {
+        const size_t nn = (size_t)sizes[k] * sizes[k];
+        std::vector<double> t(2 * nn);
+        ir_ilniqe_twiddles_host(sizes[k], t.data(), t.data() + nn);
+        void* d = nullptr;
+        if (dev_alloc(c, own, &d, t.size() * sizeof(double))) return -100;
+        HIPOK(c, hipMemcpy(d, t.data(), t.size() * sizeof(double), hipMemcpyHostToDevice));
+        m.tw[k] = static_cast<const double*>(d);
+        if (dev_alloc(c, own, &d, 12 * nn * sizeof(double))) return -100;
+        HIPOK(c, hipMemcpy(d, bank[k], 12 * nn * sizeof(double), hipMemcpyDeviceToDevice));
+        m.bank[k] = static_cast<const double*>(d);
+    }
+    m.ok = true;
+    c->ilniqe = m;
+    ++c->generation;
+    return 0;
+}
+int ir_ilniqe_stats(ir_ctx* c, void* stream, const uint8_t* img, int rows, long pitch, int n, int h, int w, const void* plan, double* out, void* ws,
+                    size_t ws_bytes) {
+    if (!c || !img || !plan || !out || !ws) return fail(c, -1, "ir_ilniqe_stats: null argument");
+    if (int e = check_rect(c, "ir_ilniqe_stats", "an image is at least 2 x 2", n, h, w, 2, {{rows, pitch}})) return e;
+    if (int e = check_ws(c, "ir_ilniqe_stats", ws, ws_bytes, ir_ilniqe_workspace(w), 8)) return e;
+    if (int e = check_out8(c, "ir_ilniqe_stats", out)) return e;
+    if (int e = check_out8(c, "ir_ilniqe_stats", plan)) return e;
+    if (!c->ilniqe.ok) return fail(c, -1, "ir_ilniqe_stats: IL-NIQE's tables are not bound (ir_ilniqe_configure)");
+    use_ctx(c);
+    if (ir_launch_ilniqe_stats(c->ilniqe, img, rows, pitch, n, h, w, plan, out, static_cast<double*>(ws), (hipStream_t)stream))
+        return fail(c, -100, "ir_ilniqe_stats: launch failed");
+    return 0;
+}
+int ir_op_dft2_f64(ir_ctx* c, void* stream, const double* re, const double* im, int size, int inverse, double* out_re, double* out_im, void* ws,
+                   size_t ws_bytes) {
+    if (!c || !re || !out_re || !out_im || !ws) return fail(c, -1, "ir_op_dft2_f64: null argument");
+    if (size != 252 && size != 504) return fail(c, -1, "ir_op_dft2_f64: bad size (%d; 252 or 504)", size);
+    if (int e = check_ws(c, "ir_op_dft2_f64", ws, ws_bytes, dft2_workspace(size), 8)) return e;
+    for (const void* p : {(const void*)re, (const void*)im, (const void*)out_re, (const void*)out_im})
+        if (int e = check_out8(c, "ir_op_dft2_f64", p)) return e;
+    const double* tw = c->ilniqe.ok ? c->ilniqe.tw[size == 504] : nullptr;
+    if (!tw) return fail(c, -1, "ir_op_dft2_f64: IL-NIQE's tables are not bound (ir_ilniqe_configure)");
+    use_ctx(c);
+    if (ir_launch_dft2_f64(tw, tw + (size_t)size * size, re, im, size, inverse, out_re, out_im, static_cast<double*>(ws), (hipStream_t)stream))
+        return fail(c, -100, "ir_op_dft2_f64: launch failed");
+    return 0;
+}
+int ir_op_weibull_fit(ir_ctx* c, void* stream, const double* x, int rows, int count, double* k_lambda) {
+    if (!c || !x || !k_lambda) return fail(c, -1, "ir_op_weibull_fit: null argument");
+    if (rows < 1 || count < 2 || count > IR_WEIBULL_MAX) return fail(c, -1, "ir_op_weibull_fit: bad size (%d rows of %d; 2 .. %d values)", rows, count, IR_WEIBULL_MAX);
+    if (int e = check_out8(c, "ir_op_weibull_fit", x)) return e;
+    if (int e = check_out8(c, "ir_op_weibull_fit", k_lambda)) return e;
+    use_ctx(c);
+    if (ir_launch_weibull_fit(x, rows, count, k_lambda, (hipStream_t)stream)) return fail(c, -100, "ir_op_weibull_fit: launch failed");
+    return 0;
+}
+
 // ---------------------------------------------------------------- low-quality inputs from ground truth (degrade.hip)
 int ir_degrade_qtables(int q, uint16_t* luma64, uint16_t* chroma64) {
     if (!luma64 || !chroma64 || q < 1 || q > 100) return -1;
@@ -1211,6 +1306,8 @@ bool ir_host::image_workspace(ir_ctx* c, int stage, int n, int h, int w, int fla
         case IR_STAGE_DEGRADE_CHAIN: if (n >= 1) *bytes = ir_degrade_chain_workspace(h, w, flags, tile_size); break;   // flags, tile_size: the largest intermediate image
         case IR_STAGE_DEGRADE: if (n >= 1) *bytes = ir_degrade_workspace(h, w); break;   // the images of a batch share it
         case IR_STAGE_NIQE: if (n >= 1 && h >= IR_NIQE_BLOCK && w >= IR_NIQE_BLOCK) *bytes = niqe_workspace(n, h, w); break;
+        case IR_STAGE_ILNIQE: if (n >= 1 && h >= 2 && w >= 2) *bytes = ir_ilniqe_workspace(w); break;   // the images of a batch share it
+        case IR_STAGE_ILNIQE_DFT: if (n >= 1 && h == w) *bytes = dft2_workspace(h); break;
         case IR_STAGE_CLIPIQA: if (c && c->clipiqa.ok && !ir_clipiqa_plan(c->clipiqa, n, h, w, &cp)) *bytes = cp.total; break;
         case IR_STAGE_MUSIQ: if (c && c->musiq.ok && !ir_musiq_plan(c->musiq, n, h, w, &mp)) *bytes = mp.total; break;
         case IR_STAGE_MANIQA:   // flags: the crops per image, tile_size: the crops per pass (0: one, the least a call takes); h and w do not matter

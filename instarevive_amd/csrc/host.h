@@ -226,7 +226,7 @@ struct Profiler {
 };
 
 // the owner of each list of ir_ctx::own: the context itself, or the binding that a *_configure / set_* call replaces
-enum Own { OWN_CTX = 0, OWN_DIT_TABS, OWN_DIT_CTRL_TABS, OWN_DIT_PROMPT, OWN_T5, OWN_CLIP, OWN_LPIPS, OWN_CLIPIQA, OWN_MUSIQ, OWN_MANIQA, OWN_DISTS, OWN_FID,
+enum Own { OWN_CTX = 0, OWN_DIT_TABS, OWN_DIT_CTRL_TABS, OWN_DIT_PROMPT, OWN_T5, OWN_CLIP, OWN_LPIPS, OWN_CLIPIQA, OWN_MUSIQ, OWN_MANIQA, OWN_DISTS, OWN_FID, OWN_ILNIQE,
            OWN_UNET_TABS, OWN_UNET_CTX = OWN_UNET_TABS + 2, OWN_COUNT = OWN_UNET_CTX + 2 };   // + which: the two UNets' timestep tables / context K-V caches
 
 }  // namespace ir_host
@@ -286,6 +286,8 @@ struct ir_ctx {
     IrDistsModel dists;
     // ir_fid_features: the repacked conv weights, the folded BatchNorm vectors and the byte table (in OWN_FID)
     IrFidModel fid;
+    // ir_ilniqe_stats / ir_op_dft2_f64: the twiddle tables and copies of the uploaded filter banks, windows and taps (in OWN_ILNIQE)
+    IrIlniqeTables ilniqe;
 };
 
 namespace ir_host {

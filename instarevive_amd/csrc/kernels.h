@@ -393,6 +393,38 @@ int ir_launch_fid(const IrFidModel& m, const uint8_t* img, int rows, long pitch,
 void ir_niqe_window_host(double* k49);
 int ir_launch_niqe_stats(const uint8_t* img, int rows, long pitch, int n, int h, int w, const double* tab, double* half, double* out, hipStream_t s);
 
+// ---- IL-NIQE's dense fp64 2-D DFT and Weibull fit (ilniqe.hip)
+// ir_ilniqe_twiddles_host: cos and sin of 2 pi (jk mod N) / N as [N][N] doubles each. ir_launch_dft2_f64: the 2-D DFT of an N x N plane (N = 252 or
+// 504; im may be null for a real input), forward (exp(-i ..), unscaled) or inverse (exp(+i ..), times 1 / N^2), as two complex matrix products on
+// the fp64 MFMA; tw_cos / tw_sin: the device copies of the twiddles of that N; ws: 2 N N doubles. The outputs must not overlap the inputs.
+// ir_launch_weibull_fit: (k, lambda) of each of `rows` rows of `count` positive doubles (2 .. IR_WEIBULL_MAX), out [rows][2].
+#define IR_WEIBULL_MAX 7056
+void ir_ilniqe_twiddles_host(int N, double* cos_nn, double* sin_nn);
+int ir_launch_dft2_f64(const double* tw_cos, const double* tw_sin, const double* re, const double* im, int N, int inverse, double* out_re, double* out_im,
+                       double* ws, hipStream_t s);
+int ir_launch_weibull_fit(const double* x, int rows, int count, double* k_lambda, hipStream_t s);
+// ir_ilniqe_stats. IrIlniqeTables: the device tables ir_ilniqe_configure binds - tw[0], tw[1]: cos | sin of 252 and 504; bank[0], bank[1]: the twelve
+// log-Gabor filters [12][N][N] of 252 and 504; host copies of the 5 x 5 and 6 x 6 windows and of the derivative taps [scale][x g | g][11].
+// ir_ilniqe_plan_host fills the resize tables of one input size (ir_ilniqe_plan_layout bytes: idx0 [524][P0] and idx1 [524][P1] as int, padded to
+// 8 bytes, then w0 and w1 as doubles; P = ir_ilniqe_taps(n_in)). out: [n][2][36][IR_ILNIQE_STATS] doubles per scale and block: 5 x 6 AGGD
+// numbers of plane 0's fields, 78 x 6 of planes 7-84, 3 x (mean, variance) of planes 4-6, 27 x (k, lambda) of planes 1-3 and 85-108.
+#define IR_ILNIQE_SIZE 524
+#define IR_ILNIQE_USED 504
+#define IR_ILNIQE_BLOCK 84
+#define IR_ILNIQE_STATS 558
+struct IrIlniqeTables {
+    bool ok = false;
+    const double* tw[2] = {nullptr, nullptr};
+    const double* bank[2] = {nullptr, nullptr};
+    double win5[25], win6[36], taps[2][22];
+};
+int ir_ilniqe_taps(int n_in);
+size_t ir_ilniqe_plan_layout(int h, int w, size_t* idx1, size_t* w0, size_t* w1);
+void ir_ilniqe_plan_host(int h, int w, void* tables);
+size_t ir_ilniqe_workspace(int w);
+int ir_launch_ilniqe_stats(const IrIlniqeTables& tb, const uint8_t* img, int rows, long pitch, int n, int h, int w, const void* plan, double* out,
+                           double* ws, hipStream_t s);
+
 // ---- CLIP-IQA of uint8 images (clipiqa.hip)
 // The bound model: every convolution as w [K padded to 32][cout] fp32 with K in (ky, kx, c) order and the folded BatchNorm as scale / shift [cout];
 // the stem's three, then the bottleneck blocks in order (down: the identity branch's 1 x 1, present when the stride is 2 or the counts differ);

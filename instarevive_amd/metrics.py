@@ -282,7 +282,8 @@ class Report:
     full column order is `file,psnr_y,ssim_y,lpips,niqe,clipiqa,musiq,maniqa`; absent metrics are left out. paired=False (a run without ground truth) carries the
     no-reference columns alone: `file,niqe`, `file,clipiqa`, `file,musiq`, `file,maniqa`, `file,niqe,clipiqa` and so on. HEADERS lists
     the headers without the MANIQA column, HEADERS_MANIQA those with it. dists=True (a paired report only) appends DISTS (dists.py) as the very
-    last column and average line (`dists: %.5f`): the full order ends `...,musiq,maniqa,dists`; HEADERS_DISTS lists those headers."""
+    last column and average line (`dists: %.5f`): the full order ends `...,musiq,maniqa,dists`; HEADERS_DISTS lists those headers. ilniqe=True puts
+    IL-NIQE (ilniqe.py) right behind NIQE's place (`...,niqe,ilniqe,clipiqa,...`, `ilniqe: %.5f`); a report without it is what it was."""
     HEADER = "file,psnr_y,ssim_y"
     HEADER_LPIPS = HEADER + ",lpips"
     HEADER_NIQE = "file,niqe"
@@ -292,19 +293,22 @@ class Report:
     HEADERS_DISTS = tuple(h + ",dists" for h in HEADERS + HEADERS_MANIQA if h.startswith("file,psnr_y,ssim_y"))
 
     def __init__(self, path: Optional[str] = None, lpips: bool = False, niqe: bool = False, paired: bool = True, clipiqa: bool = False,
-                 musiq: bool = False, maniqa: bool = False, dists: bool = False):
+                 musiq: bool = False, maniqa: bool = False, dists: bool = False, ilniqe: bool = False):
+        self.ilniqe = bool(ilniqe)
         self.path, self.rows, self.lpips, self.niqe, self.paired, self.clipiqa = path, [], bool(lpips), bool(niqe), bool(paired), bool(clipiqa)
         self.musiq, self.maniqa, self.dists = bool(musiq), bool(maniqa), bool(dists)
         if self.dists and not self.paired:
             raise MetricsError("Report: DISTS is a paired score; a report without paired scores cannot carry it")
-        if not self.paired and (self.lpips or not (self.niqe or self.clipiqa or self.musiq or self.maniqa)):
+        if not self.paired and (self.lpips or not (self.niqe or self.ilniqe or self.clipiqa or self.musiq or self.maniqa)):
             raise MetricsError("Report: a report without paired scores carries NIQE, CLIP-IQA, MUSIQ and / or MANIQA and nothing else")
-        self.keys = ((("psnr", "ssim") + (("lpips",) if self.lpips else ()) if self.paired else ()) + (("niqe",) if self.niqe else ())
+        self.keys = ((("psnr", "ssim") + (("lpips",) if self.lpips else ()) if self.paired else ()) + (("niqe",) if self.niqe else ()) + (("ilniqe",) if self.ilniqe else ())
                      + (("clipiqa",) if self.clipiqa else ()) + (("musiq",) if self.musiq else ()) + (("maniqa",) if self.maniqa else ())
                      + (("dists",) if self.dists else ()))
 
     def add(self, name: str, psnr: Optional[float] = None, ssim: Optional[float] = None, lpips: Optional[float] = None, niqe: Optional[float] = None,
-            clipiqa: Optional[float] = None, musiq: Optional[float] = None, maniqa: Optional[float] = None, dists: Optional[float] = None) -> None:
+            clipiqa: Optional[float] = None, musiq: Optional[float] = None, maniqa: Optional[float] = None, dists: Optional[float] = None, ilniqe: Optional[float] = None) -> None:
+        if (ilniqe is not None) != self.ilniqe:
+            raise MetricsError("Report.add: an IL-NIQE value is needed by a report made with ilniqe=True and by no other")
         if (lpips is not None) != self.lpips:
             raise MetricsError("Report.add: an LPIPS value is needed by a report made with lpips=True and by no other")
         if (niqe is not None) != self.niqe:
@@ -319,7 +323,7 @@ class Report:
             raise MetricsError("Report.add: a DISTS value is needed by a report made with dists=True and by no other")
         if (psnr is not None) != self.paired or (ssim is not None) != self.paired:
             raise MetricsError("Report.add: PSNR and SSIM are needed by a report with paired scores and by no other")
-        given = dict(psnr=psnr, ssim=ssim, lpips=lpips, niqe=niqe, clipiqa=clipiqa, musiq=musiq, maniqa=maniqa, dists=dists)
+        given = dict(psnr=psnr, ssim=ssim, lpips=lpips, niqe=niqe, ilniqe=ilniqe, clipiqa=clipiqa, musiq=musiq, maniqa=maniqa, dists=dists)
         self.rows.append((str(name),) + tuple(float(given[k]) for k in self.keys))
 
     def add_scores(self, name: str, scores: Sequence[float]) -> None:
@@ -332,7 +336,7 @@ class Report:
         """For a score tuple in the report's own column order: the no-reference column whose value is NaN - the image has no such score -
         "niqe" before "clipiqa" before "musiq" before "maniqa" - or "dists" behind them (a pair below 16 pixels on an edge); None when the tuple
         can be added."""
-        for k in ("niqe", "clipiqa", "musiq", "maniqa", "dists"):
+        for k in ("niqe", "ilniqe", "clipiqa", "musiq", "maniqa", "dists"):
             if k in self.keys and scores[self.keys.index(k)] != scores[self.keys.index(k)]:
                 return k
         return None
@@ -372,6 +376,7 @@ def read_report(path: str) -> dict:
     import csv
     with open(path, newline="") as f:
         rows = list(csv.reader(f))
-    if not rows or ",".join(rows[0]) not in Report.HEADERS + Report.HEADERS_MANIQA + Report.HEADERS_DISTS:
+    head = [c for c in rows[0] if c != "ilniqe"] if rows else []   # the IL-NIQE column may stand in any report
+    if not rows or (",".join(head) not in Report.HEADERS + Report.HEADERS_MANIQA + Report.HEADERS_DISTS and rows[0] != ["file", "ilniqe"]):
         raise MetricsError(f"{path}: not a metrics report")
     return {r[0]: tuple(float(v) for v in r[1:len(rows[0])]) for r in rows[1:]}

@@ -229,11 +229,11 @@ class _Batch:
     two streams and keeps the batch's events in `ready` (its uploads) and `done` (its downloads)."""
 
     def __init__(self, ctx, slot, tag, slots, shape, imgs, with_stage1, rects=None, records=None, dparams=None, gts=None, lpips=False, niqe=None,
-                 clipiqa=False, sizes=None, want_lq=False, prompts=(None, None), codec=None, png_runs=False, musiq=False, maniqa=False, dists=False, fid=None, fid_sizes=None):
+                 clipiqa=False, sizes=None, want_lq=False, prompts=(None, None), codec=None, png_runs=False, musiq=False, maniqa=False, dists=False, fid=None, fid_sizes=None, ilniqe=None):
         """The plan phase, host work only: every size is checked and every ground truth compared with its image's FINAL size, so a batch that
         does not fit raises ValueError before anything is launched for it; then the scorer slots are filled / planned - `scorers` holds them in
         the order of a score tuple: paired (metrics.ScoreSlot; with lpips it scores LPIPS as well, ir_lpips with the weights lpips.configure()
-        bound to the context), NIQE with `niqe` its parameters, CLIP-IQA, MUSIQ, MANIQA (maniqa: True, or the images' names, which key random crops), and last DISTS (dists: ir_dists with the weights dists.configure() bound to the context; the paired slot queues it, metrics.DistsColumn
+        bound to the context), NIQE with `niqe` its parameters, IL-NIQE with `ilniqe` its template (ilniqe.configure() bound to the context), CLIP-IQA, MUSIQ, MANIQA (maniqa: True, or the images' names, which key random crops), and last DISTS (dists: ir_dists with the weights dists.configure() bound to the context; the paired slot queues it, metrics.DistsColumn
         stands where its value is read) - and the images copied into page-locked memory: the staging input, or
         the decoded files (with their degrade parameters) into the ResizeSlot, whose bicubic chain then makes the staging input on the device.
         fid: None, or FID's resize mode - the batch's predictions (and its ground truth, when it has one) go through ir_fid_features into a
@@ -265,12 +265,18 @@ class _Batch:
                     raise ValueError("dists=True: no DISTS weights are bound to the context (instarevive_amd.dists.configure)")
             self.sc.fill(gts, lpips, copies, dists=bool(dists))
             self.scorers.append(self.sc)
-        if niqe is not None or clipiqa or musiq or maniqa:
-            finals = final_sizes("niqe" if niqe is not None else "clipiqa" if clipiqa else "musiq" if musiq else "maniqa", n, h, w, records, rects, sizes, gts)
+        if niqe is not None or ilniqe is not None or clipiqa or musiq or maniqa:
+            finals = final_sizes("niqe" if niqe is not None else "ilniqe" if ilniqe is not None else "clipiqa" if clipiqa else "musiq" if musiq else "maniqa", n, h, w, records, rects, sizes, gts)
             if niqe is not None:
                 from .niqe import NiqeSlot
                 self.scorers.append(NiqeSlot.get(ctx, slot, tag))
                 self.scorers[-1].plan(finals, niqe, copies)
+            if ilniqe is not None:
+                from .ilniqe import IlniqeSlot, configured
+                if not configured(ctx):
+                    raise ValueError("ilniqe=...: IL-NIQE's tables are not bound to the context (instarevive_amd.ilniqe.configure)")
+                self.scorers.append(IlniqeSlot.get(ctx, slot, tag))
+                self.scorers[-1].plan(finals, ilniqe, copies)
             if clipiqa:
                 from .clipiqa import ClipIqaSlot
                 self.scorers.append(ClipIqaSlot.get(ctx, slot, tag))
@@ -429,7 +435,7 @@ def process(model, control_imgs: List[np.ndarray], strength: float, color_fix_ty
             fused: bool = True, graph: bool = False, return_stage1: bool = True, fp8: bool = False, png=None,
             resize=None, gt=None, lpips: bool = False, niqe=None, niqe_rects=None, clipiqa: bool = False, degrade=None,
             lq_sink=None, jpeg=None, jpeg_quality: int = 95, jpeg_subsampling=2, png_runs: bool = False, musiq: bool = False, maniqa=False, dists: bool = False, fid=None,
-            fid_rects=None) -> Tuple[List[np.ndarray], List[np.ndarray]]:
+            fid_rects=None, ilniqe=None) -> Tuple[List[np.ndarray], List[np.ndarray]]:
     """test_scripts/inference.py:55-166. control_imgs: list of HWC uint8 RGB arrays of equal size (multiples of 64).
     Returns (preds, stage1_preds) as lists of HWC uint8 arrays (stage1_preds is empty with return_stage1=False, which skips its
     conversion and download).
@@ -470,6 +476,9 @@ def process(model, control_imgs: List[np.ndarray], strength: float, color_fix_ty
     job, niqe_rects (one (h, w) per image), the ground truth's size, else the whole output - and the fits and the score are computed on the host
     when the scores are read. Alone, the call returns the triple with scores a pair of lists of (niqe,); with gt the value is appended to each
     tuple. An image without a score (an edge below 96 pixels, fewer than two complete feature rows) gets NaN.
+    ilniqe (fused form only; with or without gt and the other scores): the template of instarevive_amd.ilniqe.load_params(), with
+    instarevive_amd.ilniqe.configure() bound to the models' context. ir_ilniqe_stats is queued behind ir_niqe_stats on the same final forms
+    (niqe_rects serves it too); its value stands right behind NIQE's in every tuple: (ilniqe,), (niqe, ilniqe), (psnr_y, ssim_y[, lpips][, niqe], ilniqe, ...).
     clipiqa (fused form only; with or without gt and niqe): score CLIP-IQA as well - ir_clipiqa with the model instarevive_amd.clipiqa.configure()
     bound to the models' context, queued behind ir_niqe_stats on the same final rectangles (niqe_rects serves both). Its value is the last of
     every tuple: (clipiqa,), (niqe, clipiqa), (psnr_y, ssim_y[, lpips][, niqe], clipiqa). An image below 32 pixels on an edge gets NaN.
@@ -501,7 +510,7 @@ def process(model, control_imgs: List[np.ndarray], strength: float, color_fix_ty
         raise ValueError("process(degrade=...) needs resize=: the ground truth is degraded on the device input route")
     n, h, w = _batch_shape(control_imgs, resize)
     codec = _jpeg_codec(png, jpeg, jpeg_quality, jpeg_subsampling)
-    if (png is not None or jpeg is not None or resize is not None or gt is not None or niqe is not None or clipiqa or musiq or maniqa) and not (fused and _fused_ok(model, preprocess_model, vae, disable_preprocess_model)):
+    if (png is not None or jpeg is not None or resize is not None or gt is not None or niqe is not None or ilniqe is not None or clipiqa or musiq or maniqa) and not (fused and _fused_ok(model, preprocess_model, vae, disable_preprocess_model)):
         raise ValueError("process(png=... / resize=... / gt=... / niqe=...) needs the fused form (instarevive_amd models sharing one context)")
     device = model.device
     acp = float(noise_scheduler.alphas_cumprod[400])
@@ -514,7 +523,7 @@ def process(model, control_imgs: List[np.ndarray], strength: float, color_fix_ty
         ctx = model.ctx
         batch = _Batch(ctx, 0, "sync", 1, (n, h, w), control_imgs, return_stage1, png if codec is None else jpeg, resize, degrade, gt, lpips, niqe,
                        clipiqa, niqe_rects, lq_sink is not None, codec=codec, png_runs=png_runs, musiq=musiq, maniqa=maniqa, dists=dists,
-                       fid=("clean" if fid is True else fid) or None, fid_sizes=fid_rects)
+                       fid=("clean" if fid is True else fid) or None, fid_sizes=fid_rects, ilniqe=ilniqe)
         _prepare_fused(model, y, y_mask, h, w, tiled, tile_size, (vae, None if disable_preprocess_model else preprocess_model))
         flags = _pipeline_flags(model, color_fix_type, disable_preprocess_model, tiled) | (L.FLAG_GRAPH if graph else 0) | (L.FLAG_FP8 if fp8 else 0)
         batch.upload()
@@ -583,7 +592,7 @@ def process_stream(model, batches: Iterable[Sequence[np.ndarray]], color_fix_typ
                    png_wrap: bool = True, resize=None, gt=None, lpips: bool = False, niqe=None,
                    niqe_rects=None, clipiqa: bool = False, degrade=None, lq_sink=None, jpeg=None, jpeg_quality: int = 95,
                    jpeg_subsampling=2, png_runs: bool = False, musiq: bool = False, maniqa=False, dists: bool = False, fid=None,
-                   fid_rects=None) -> Iterator[Tuple[List[np.ndarray], List[np.ndarray]]]:
+                   fid_rects=None, ilniqe=None) -> Iterator[Tuple[List[np.ndarray], List[np.ndarray]]]:
     """process() over a sequence of image batches with the transfers hidden: while batch i computes on the current stream, batch
     i+1 is uploaded and batch i-1 downloaded on a copy stream (two staging slots per batch shape). Yields process()'s result for
     every batch, in order. Needs the fused form (all models instarevive_amd objects on one context). fp8 as in process() (cfg-5:
@@ -623,6 +632,8 @@ def process_stream(model, batches: Iterable[Sequence[np.ndarray]], color_fix_typ
     ground truth) at its png rectangle / resize target / ground truth's size / whole output. ir_niqe_stats is queued behind the paired scores on
     the compute stream, the statistics come back with the batch's download, and the fits and the score run when the batch is yielded. A scored
     batch yields the triple; alone its tuples are (niqe,), with gt the value is appended.
+    ilniqe (with or without gt and the other scores): the template, as in process() - ir_ilniqe_stats is queued behind ir_niqe_stats on the batches
+    NIQE scores or would score (niqe_rects serves it too), and its value stands right behind NIQE's.
     clipiqa (with or without gt and niqe): as in process() - ir_clipiqa is queued behind ir_niqe_stats on the batches NIQE scores or would score
     (niqe_rects serves both), and its value comes last in every tuple.
     musiq (alone or with gt, lpips, niqe and clipiqa): as in process() - ir_musiq is queued behind ir_clipiqa on the same batches and rectangles, and
@@ -654,7 +665,7 @@ def process_stream(model, batches: Iterable[Sequence[np.ndarray]], color_fix_typ
     if degrade_it is not None and resize_it is None:
         raise ValueError("process_stream(degrade=...) needs resize=: the ground truth is degraded on the device input route")
     gt_it = iter(gt) if gt is not None else None
-    noref = niqe is not None or bool(clipiqa) or bool(musiq) or bool(maniqa)
+    noref = niqe is not None or ilniqe is not None or bool(clipiqa) or bool(musiq) or bool(maniqa)
     mq_it = iter(maniqa) if maniqa and maniqa is not True else None
     nq_it = iter(niqe_rects) if noref and niqe_rects is not None else None
     fid = ("clean" if fid is True else fid) or None
@@ -678,7 +689,7 @@ def process_stream(model, batches: Iterable[Sequence[np.ndarray]], color_fix_typ
         b = _Batch(ctx, slot, "stream", 2, _batch_shape(imgs, records), imgs, return_stage1, rects, records, dparams, gts, lpips,
                    niqe if with_nq else None, bool(clipiqa) and with_nq, sizes, lq_sink is not None, (by, bm), codec=codec, png_runs=png_runs, musiq=bool(musiq) and with_nq,
                    maniqa=(names if names is not None else True) if maniqa and with_nq else False, dists=dists,
-                   fid=fid if with_fid else None, fid_sizes=fsizes)
+                   fid=fid if with_fid else None, fid_sizes=fsizes, ilniqe=ilniqe if with_nq else None)
         with torch.cuda.stream(copy):
             b.ready = b.upload(copy, main)
         return b

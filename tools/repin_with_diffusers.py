@@ -43,6 +43,10 @@ random-initialised models of reduced width pin it exactly as the 4 GB checkpoint
     2048 features of two images to 1e-5 of their largest (both run fp32) with the `legacy` input, pyiqa's / clean-fid's resized input against
     resize_clean() bit for bit, and calculate_frechet_distance against frechet_distance() on 4096 random features to 1e-6 relative. A mismatch
     points at one of the points docs/parity.md lists: eps, count_include_pad, the max pool of Mixed_7c, the branch order, the resize.
+15. pyiqa's IL-NIQE (the `create_metric('ilniqe')` that evaluate_img.py keeps commented out) -> tools/evaluate_ilniqe.py on pyiqa's own
+    ILNIQE_templateModel.mat: the score of two images without flat areas to 1e-3 relative (pyiqa scales its input in fp32). A mismatch points
+    at one of the choices docs/parity.md lists as unpinned: the fp32 input scaling, the padding of the derivative convolutions, the resize
+    order, the plane order, the unbiased std of the Weibull start.
  6. ftfy.fix_text (diffusion/model/t5.py:118-124) -> instarevive_amd.captions.fix_text (deterministic steps + the restricted mojibake repair).
 
 The fixture holds inputs, state-dict checksums and the third party's outputs (data, not source); tests/test_oracle_golden.py picks
@@ -251,6 +255,35 @@ def pin_niqe(out):
         out[f"niqe_{name}"], out[f"niqe_{name}_ref"] = img, np.float64(ref)
         if name == "plain":
             ok = abs(got - ref) <= 1e-6 * ref
+    return ok
+
+
+def pin_ilniqe(out):
+    """pyiqa's `ilniqe` against tools/evaluate_ilniqe.py on pyiqa's own template. The model takes MATLAB's side wherever the two may differ
+    (docs/parity.md), so a mismatch here names a choice to revisit, not a bug of the device code, which is tested against the model."""
+    import importlib.util
+    import pyiqa
+    spec = importlib.util.spec_from_file_location("evaluate_ilniqe", os.path.join(ROOT, "tools", "evaluate_ilniqe.py"))
+    ei = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(ei)
+    metric = pyiqa.create_metric("ilniqe", device="cpu")
+    path = None
+    for root, _, names in os.walk(os.path.expanduser(os.environ.get("PYIQA_CACHE", "~/.cache/pyiqa"))):
+        path = os.path.join(root, "ILNIQE_templateModel.mat") if "ILNIQE_templateModel.mat" in names else path
+    if path is None:
+        raise ImportError("pyiqa has not downloaded ILNIQE_templateModel.mat")
+    par = ei.load_params(path)
+    rng = np.random.default_rng(15)
+    ok = True
+    for name, (h, w) in (("small", (288, 384)), ("large", (600, 1100))):
+        yy, xx = np.mgrid[0:h, 0:w].astype(np.float64)
+        base = np.stack([128 + 80 * np.sin(xx / 23) * np.cos(yy / 31), 128 + 70 * np.sin((xx + yy) / 41), 128 + 90 * np.cos(xx / 17 - yy / 29)], -1)
+        img = np.clip(np.rint(base + rng.normal(0, 6.0, base.shape)), 1, 254).astype(np.uint8)
+        ref = float(metric(torch.from_numpy(img).permute(2, 0, 1)[None].float() / 255.0))
+        got = ei.ilniqe(img, par)
+        print(f"  [15] pyiqa IL-NIQE ({name}) {ref:.6f} vs evaluate_ilniqe {got:.6f} (relative {abs(got - ref) / ref:.2e})")
+        out[f"ilniqe_{name}"], out[f"ilniqe_{name}_ref"] = img, np.float64(ref)
+        ok = ok and abs(got - ref) <= 1e-3 * ref
     return ok
 
 
@@ -478,7 +511,8 @@ def main():
                            ("open_clip (item 4)", pin_clip, ()), ("pyiqa (item 5)", pin_iqa, ()), ("ftfy (item 6)", pin_ftfy, ()), ("lpips (item 7)", pin_lpips, ()),
                            ("pyiqa NIQE (item 8)", pin_niqe, ()), ("pyiqa CLIP-IQA (item 9)", pin_clipiqa, (a.clip_bpe,)),
                            ("OpenCV degradation steps (item 10)", pin_degrade, ()), ("pyiqa MUSIQ (item 11)", pin_musiq, ()),
-                           ("pyiqa MANIQA (item 12)", pin_maniqa, ()), ("pyiqa DISTS (item 13)", pin_dists, ()), ("pytorch-fid / pyiqa FID (item 14)", pin_fid, ())):
+                           ("pyiqa MANIQA (item 12)", pin_maniqa, ()), ("pyiqa DISTS (item 13)", pin_dists, ()), ("pytorch-fid / pyiqa FID (item 14)", pin_fid, ()),
+                           ("pyiqa IL-NIQE (item 15)", pin_ilniqe, ())):
         print(name)
         try:
             verdict[name] = fn(out, *args)
