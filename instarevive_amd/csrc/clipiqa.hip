@@ -1,10 +1,9 @@
 // CLIP-IQA of uint8 HWC RGB device images (ir_clipiqa): the model of tools/evaluate_clipiqa.py - CLIP's ModifiedResNet image tower at the image's
 // own size, its attention pool without positional embedding, and the pair softmax against the fixed text rows - in exact fp32 with an fp64 tail.
-//   Convolutions: implicit GEMMs on the fp32-input MFMA (v_mfma_f32_32x32x2_f32: bit for bit a k-ordered fmaf chain, so an output element
-//   depends neither on the tile it falls in nor on its place in a batch), NHWC fp32 maps, M = output pixels of the n images, N = cout,
+//   Convolutions: implicit GEMMs on the exact-fp32 tile loop of exact_f32_tile.h, NHWC fp32 maps, M = output pixels of the n images, N = cout,
 //   K = k * k * cin in (ky, kx, c) order with the weights repacked to [K padded to 32][cout] by ir_clipiqa_configure. One kernel serves 1 x 1 and
-//   3 x 3 at stride 1 (cin and cout multiples of 32: a 32-deep k-tile never crosses a tap); a workgroup of four waves owns a 128 x BN tile
-//   (BN = 128 / 64 / 32 by cout's largest such divisor), or a 64 x 64 tile where the larger one would leave fewer than 512 workgroups.
+//   3 x 3 at stride 1 (cin and cout multiples of 32: a 32-deep k-tile never crosses a tap); the tile is 128 x BN (BN = 128 / 64 / 32 by cout's
+//   largest such divisor), or 64 x 64 where the larger one would leave fewer than 512 workgroups.
 //   Epilogue: acc * scale[c] + shift[c] (the BatchNorm folded in fp64 and rounded once), an optional residual add, an optional ReLU -
 //   separate roundings, the file is built with -ffp-contract=off. The 3-channel stride-2 stem conv
 //   gathers from the bytes through the 3 x 256 table (the host's fp32 (v / 255 - mean) / std), K = 27 padded to 32; padding is 0 in that domain.
@@ -13,18 +12,18 @@
 //   exists, its scores are u_h . x_t + q_h . bk_h with u_h = Wk_h^T q_h, and the attention output is Wv_h (sum_t p_th x_t) + bv_h (the p sum
 //   to 1) - algebraically the three projections, at T C heads instead of T C C multiplies; softmax over the T = HW + 1 tokens; c_proj; the
 //   feature norm, the logits against the text rows, the softmax of each pair, the mean of the first entries. Every sum is a per-thread or
-//   per-lane sequential chain followed by a fixed butterfly / a fixed fold: no floating-point atomics, the same bits on every call and at every
+//   per-lane sequential chain followed by a fixed butterfly / a fixed fold: the same bits on every call and at every
 //   place in a batch. One double per image.
 // Reads are clipped to the scored rectangle h x w; every store is guarded by the row count of its launch.
 #include <algorithm>
 
 #include "common.h"
+#include "exact_f32_tile.h"
 #include "kernels.h"
 
 namespace {
 
-constexpr int TPB = 256;
-constexpr int BK = 32;
+using namespace exact_tile;
 constexpr int SMALL_GRID = 512;   // below this many 128-row workgroups a launch takes the 64 x 64 tile: two or more workgroups per CU hide the k-tile's latency
 
 struct ConvArgs {
@@ -44,162 +43,37 @@ struct ConvArgs {
     float* out;                 // [M][N]
 };
 
+// folded BatchNorm, residual, ReLU
+struct BnResRelu {
+    const ConvArgs& p;
+    int col;
+    float sc, sh;
+    IR_DEVINL bool column(int c) {
+        col = c;
+        sc = p.scale[c];
+        sh = p.shift[c];
+        return true;   // N is a multiple of BN
+    }
+    IR_DEVINL void store(int m, float acc) const {
+        float v = acc * sc + sh;
+        if (p.res) v = v + p.res[(long)m * p.N + col];
+        if (p.relu) v = fmaxf(v, 0.f);
+        p.out[(long)m * p.N + col] = v;
+    }
+};
+
 // STEM: 3 x 3 / stride 2 / pad 1 from the bytes through the table; else stride 1 from an fp32 map whose cin is a multiple of BK
 template <int BM, int BN, bool STEM>
-__global__ __launch_bounds__(TPB) void clipiqa_conv_kernel(ConvArgs p) {
-    constexpr int LDA = BM + 4;
-    constexpr int WN = BN >= 64 ? 2 : 1, WM = 4 / WN;   // waves across the tile
-    constexpr int TM = BM / (32 * WM), TN = BN / (32 * WN);   // 32 x 32 blocks per wave
-    static_assert(TM >= 1 && TN >= 1 && BK * BN / 4 >= TPB, "tile too small for four waves");
-    constexpr int LDB = BN + 4;
-    constexpr int BV = BK * BN / 4 / TPB;   // float4 of the weight tile per thread
-    __shared__ float s_a[BK][LDA];
-    __shared__ float s_b[BK][LDB];
-    __shared__ float s_tab[STEM ? 3 * 256 : 1];
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int wm = wave / WN, wn = wave % WN;
-    const int m0 = blockIdx.x * BM, n0 = blockIdx.y * BN;
-    const int HWo = p.Ho * p.Wo;
-    const int nk = (p.K + BK - 1) / BK;
-
-    constexpr int AR = STEM ? BM * BK / TPB : BM * BK / 4 / TPB;   // 16 scalars of one k / 4 float4
-    const uint8_t* rb[STEM ? AR : 1];
-    long ro[STEM ? 1 : AR];
-    int riy[AR], rix[AR];
+__global__ __launch_bounds__(TPB, STEM ? (BN == 64 ? 3 : 4) : BM == 64 ? 7 : BN == 128 ? 3 : BN == 64 ? 4 : 6) void clipiqa_conv_kernel(ConvArgs p) {
+    const KnB<BN, false> b{.b = p.wgt, .ldb = p.N};
     if constexpr (STEM) {
-        for (int i = tid; i < 3 * 256; i += TPB) s_tab[i] = p.tab[i];
-#pragma unroll
-        for (int i = 0; i < AR; ++i) {
-            const int m = m0 + (tid >> 5) + 8 * i;
-            if (m < p.M) {
-                const int img = m / HWo, r = m - img * HWo, oy = r / p.Wo, ox = r - oy * p.Wo;
-                riy[i] = oy * 2 - p.pad;
-                rix[i] = ox * 2 - p.pad;
-                rb[i] = p.img + (long)img * p.img_stride + (long)riy[i] * p.pitch + 3L * rix[i];
-            } else {
-                riy[i] = -(1 << 20);   // every tap out of bounds
-                rix[i] = 0;
-                rb[i] = p.img;
-            }
-        }
+        __shared__ float s_tab[3 * 256];
+        const ByteTableA<BM, false> a{.a = p.img, .a_pitch = p.pitch, .a_img = p.img_stride, .tab = p.tab, .s_tab = s_tab, .H = p.H, .W = p.W, .Ho = p.Ho, .Wo = p.Wo,
+                                      .row_k = 9, .stride = 2, .pad = p.pad, .M = p.M, .K = p.K};   // 9 = 3 taps x 3 channels of one image row
+        tile_loop<BM, BN>(a, b, p.M, p.K, BnResRelu{p});
     } else {
-#pragma unroll
-        for (int i = 0; i < AR; ++i) {
-            const int m = m0 + (tid >> 3) + 32 * i;
-            if (m < p.M) {
-                const int img = m / HWo, r = m - img * HWo, oy = r / p.Wo, ox = r - oy * p.Wo;
-                riy[i] = oy - p.pad;
-                rix[i] = ox - p.pad;
-                ro[i] = (((long)img * p.H + riy[i]) * p.W + rix[i]) * p.cin;
-            } else {
-                riy[i] = -(1 << 20);
-                rix[i] = 0;
-                ro[i] = 0;
-            }
-        }
-    }
-
-    float ga[STEM ? AR : 1];
-    float4 gv[STEM ? 1 : AR];
-    float4 gb[BV];
-    auto load_tile = [&](int kt) {
-        const int k0 = kt * BK;
-        if constexpr (STEM) {
-            const int k = k0 + (tid & 31);
-            const int ky = k / 9, r = k - ky * 9, kx = r / 3, c = r - kx * 3;   // 9 = 3 taps x 3 channels of one image row
-#pragma unroll
-            for (int i = 0; i < AR; ++i) {
-                const int iy = riy[i] + ky, ix = rix[i] + kx;
-                float v = 0.f;
-                if (k < p.K && iy >= 0 && iy < p.H && ix >= 0 && ix < p.W) v = s_tab[256 * c + rb[i][(long)ky * p.pitch + r]];
-                ga[i] = v;
-            }
-        } else {
-            const int tap = k0 / p.cin, c0 = k0 - tap * p.cin + 4 * (tid & 7);
-            const int ky = tap / p.ks, kx = tap - ky * p.ks;
-#pragma unroll
-            for (int i = 0; i < AR; ++i) {
-                const int iy = riy[i] + ky, ix = rix[i] + kx;
-                float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
-                if (iy >= 0 && iy < p.H && ix >= 0 && ix < p.W)
-                    v = *reinterpret_cast<const float4*>(p.in + ro[i] + ((long)ky * p.W + kx) * p.cin + c0);
-                gv[i] = v;
-            }
-        }
-#pragma unroll
-        for (int i = 0; i < BV; ++i) {
-            const int idx = tid + i * TPB, kr = idx / (BN / 4), nc = idx - kr * (BN / 4);
-            gb[i] = *reinterpret_cast<const float4*>(p.wgt + (long)(k0 + kr) * p.N + n0 + 4 * nc);   // rows up to Kpad exist, N is a multiple of BN
-        }
-    };
-    auto store_tile = [&]() {
-        if constexpr (STEM) {
-#pragma unroll
-            for (int i = 0; i < AR; ++i) s_a[tid & 31][(tid >> 5) + 8 * i] = ga[i];
-        } else {
-#pragma unroll
-            for (int i = 0; i < AR; ++i) {
-                const int row = (tid >> 3) + 32 * i, kq = 4 * (tid & 7);
-                s_a[kq][row] = gv[i].x;
-                s_a[kq + 1][row] = gv[i].y;
-                s_a[kq + 2][row] = gv[i].z;
-                s_a[kq + 3][row] = gv[i].w;
-            }
-        }
-#pragma unroll
-        for (int i = 0; i < BV; ++i) {
-            const int idx = tid + i * TPB, kr = idx / (BN / 4), nc = idx - kr * (BN / 4);
-            *reinterpret_cast<float4*>(&s_b[kr][4 * nc]) = gb[i];
-        }
-    };
-
-    f32x16 acc[TM][TN];
-#pragma unroll
-    for (int i = 0; i < TM; ++i)
-#pragma unroll
-        for (int j = 0; j < TN; ++j)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
-
-    if constexpr (STEM) __syncthreads();   // the table
-    load_tile(0);
-    const int kh = lane >> 5, l31 = lane & 31;
-    for (int kt = 0; kt < nk; ++kt) {
-        store_tile();
-        __syncthreads();
-        if (kt + 1 < nk) load_tile(kt + 1);
-#pragma unroll
-        for (int kk = 0; kk < BK; kk += 2) {
-            float fa[TM], fb[TN];
-#pragma unroll
-            for (int i = 0; i < TM; ++i) fa[i] = s_a[kk + kh][wm * (32 * TM) + i * 32 + l31];
-#pragma unroll
-            for (int j = 0; j < TN; ++j) fb[j] = s_b[kk + kh][wn * (32 * TN) + j * 32 + l31];
-#pragma unroll
-            for (int i = 0; i < TM; ++i)
-#pragma unroll
-                for (int j = 0; j < TN; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(fa[i], fb[j], acc[i][j], 0, 0, 0);
-        }
-        __syncthreads();
-    }
-
-    // folded BatchNorm, residual, ReLU; the column is on the lane, so a row of the tile is one 128-byte store per wave
-#pragma unroll
-    for (int j = 0; j < TN; ++j) {
-        const int col = n0 + wn * (32 * TN) + j * 32 + l31;
-        const float sc = p.scale[col], sh = p.shift[col];
-#pragma unroll
-        for (int i = 0; i < TM; ++i)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                const int m = m0 + wm * (32 * TM) + i * 32 + mfma_row(r, lane);
-                if (m < p.M) {
-                    float v = acc[i][j][r] * sc + sh;
-                    if (p.res) v = v + p.res[(long)m * p.N + col];
-                    if (p.relu) v = fmaxf(v, 0.f);
-                    p.out[(long)m * p.N + col] = v;
-                }
-            }
+        const NhwcA<BM, true> a{.in = p.in, .H = p.H, .W = p.W, .cin = p.cin, .pitch = p.cin, .kw = p.ks, .stride = 1, .ph = p.pad, .pw = p.pad, .Ho = p.Ho, .Wo = p.Wo, .M = p.M, .K = p.K};
+        tile_loop<BM, BN>(a, b, p.M, p.K, BnResRelu{p});
     }
 }
 

@@ -1,30 +1,27 @@
 // DISTS of uint8 HWC RGB device images (ir_dists): the model of tools/evaluate_pairs.py::DISTS, exact fp32 convolutions and fp64 statistics.
 // The 2n images of a call (a's n, then b's n) go through one set of launches:
-//   the thirteen 3x3 convolutions of VGG-16 as implicit GEMMs on the fp32-input MFMA (v_mfma_f32_32x32x2_f32: bit for bit a k-ordered fmaf
-//   chain, so an output element does not depend on the tile it falls in), bias + ReLU in the epilogue, feature maps NHWC fp32. M = pixels of
-//   2n images, N = cout, K = 9 cin in (ky, kx, c) order - the weights are repacked to [K padded to 32][cout] by ir_dists_configure, zero rows
-//   behind K (27 -> 32 for the first conv; the A tile is zero there as well). A workgroup of four waves owns a 128 x BN tile (BN = 128 where
-//   cout is a multiple of 128, else 64), a wave 64 x BN / 2 as 32 x 32 blocks; the 32-deep k-tile goes global -> registers -> LDS with the
-//   next tile's loads in flight during the MFMAs. The first conv gathers straight from the bytes through the 3 x 256 table (the host's fp32
-//   (v / 255 - mean) / std, so the network's input is the host model's to the bit); padding is 0 in that normalised domain.
+//   the thirteen 3x3 convolutions of VGG-16 as implicit GEMMs on the exact-fp32 tile loop of exact_f32_tile.h, bias + ReLU in the epilogue,
+//   feature maps NHWC fp32. M = pixels of 2n images, N = cout, K = 9 cin in (ky, kx, c) order - the weights are repacked to
+//   [K padded to 32][cout] by ir_dists_configure, zero rows behind K (27 -> 32 for the first conv; the A tile is zero there as well). The tile
+//   is 128 x BN, BN = 128 where cout is a multiple of 128, else 64. The first conv gathers straight from the bytes through the 3 x 256 table
+//   (the host's fp32 (v / 255 - mean) / std, so the network's input is the host model's to the bit); padding is 0 in that normalised domain.
 //   The L2 pool in front of stages 2 .. 5 is one kernel: sqrt(sum_taps g x^2 + 1e-12), g = (1, 2, 1) x (1, 2, 1) / 16, stride 2, padding 1,
 //   the taps added row by row from the top-left in fp32 (the file is built with -ffp-contract=off); taps outside the map add nothing.
 //   One moment kernel per compared map: a lane per channel, 1024 pixels per workgroup, the five sums of a pair in fp64 about the channel's
 //   first pixel (sum dx, sum dy, sum dx^2, sum dy^2, sum dx dy with dx = x - x[0]: a constant map sums to exactly 0), the workgroup's sums to
 //   the workspace; a fold kernel adds the partials of a (pair, channel) in a fixed order and writes mx, my, vx, vy, cxy; the last launch makes
-//   S1, S2 and the weighted sum of a pair in fp64. No floating-point atomics: a pair gives the same bits on every call and at every place in a
-//   batch.
+//   S1, S2 and the weighted sum of a pair in fp64: a pair gives the same bits on every call and at every place in a batch.
 // Reads are clipped to the compared rectangle h x w of either image; every store is guarded by the row count M of its launch.
 #include <algorithm>
 
 #include "common.h"
+#include "exact_f32_tile.h"
 #include "kernels.h"
 
 namespace {
 
-constexpr int TPB = 256;
-constexpr int BM = 128, BK = 32;
-constexpr int LDA = BM + 4;
+using namespace exact_tile;
+constexpr int BM = 128;
 constexpr int MOM_PIX = 1024;   // pixels per workgroup of the moment kernels: the unit of the partial sums
 
 struct ConvArgs {
@@ -41,162 +38,32 @@ struct ConvArgs {
     float* out;                 // [M][N]
 };
 
-// FIRST: the first conv (bytes through the table, K = 27); else from an fp32 map whose cin is a multiple of BK
+struct BiasRelu {
+    const ConvArgs& p;
+    int col;
+    float bias;
+    IR_DEVINL bool column(int c) {
+        col = c;
+        bias = p.bias[c];
+        return true;   // N is a multiple of BN
+    }
+    IR_DEVINL void store(int m, float acc) const { p.out[(long)m * p.N + col] = fmaxf(acc + bias, 0.f); }
+};
+
+// FIRST: the first conv (bytes through the table, K = 27); else from an fp32 map whose cin is a multiple of BK. Waves per SIMD: the 128 x 128
+// tile asks for one, which leaves its accumulators in AGPRs at two waves - DISTS's large maps run it at the MFMA rate, where that measured faster
+// than VGPR accumulators at three (docs/kernels.md)
 template <int BN, bool FIRST>
-__global__ __launch_bounds__(TPB) void dists_conv_kernel(ConvArgs p) {
-    constexpr int TN = BN / 64;           // 32-column blocks per wave
-    constexpr int LDB = BN + 4;
-    constexpr int BV = BK * BN / 4 / TPB; // float4 of the weight tile per thread
-    __shared__ float s_a[BK][LDA];
-    __shared__ float s_b[BK][LDB];
-    __shared__ float s_tab[FIRST ? 3 * 256 : 1];
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int wm = wave >> 1, wn = wave & 1;
-    const int m0 = blockIdx.x * BM, n0 = blockIdx.y * BN;
-    const int HW = p.H * p.W;
-    const int nk = (p.K + BK - 1) / BK;
-
-    // the rows this thread gathers
-    constexpr int AR = FIRST ? BM * BK / TPB : BM * BK / 4 / TPB;   // 16 scalars of one k / 4 float4
-    const uint8_t* rb[FIRST ? AR : 1];
-    long ro[FIRST ? 1 : AR];
-    int riy[AR], rix[AR];
-    bool rsec[FIRST ? AR : 1];   // first conv: the row belongs to an image of b (its pitch)
+__global__ __launch_bounds__(TPB, FIRST ? 2 : BN == 128 ? 1 : 4) void dists_conv_kernel(ConvArgs p) {
+    const KnB<BN, false> b{.b = p.wgt, .ldb = p.N};
     if constexpr (FIRST) {
-        for (int i = tid; i < 3 * 256; i += TPB) s_tab[i] = p.tab[i];
-#pragma unroll
-        for (int i = 0; i < AR; ++i) {
-            const int m = m0 + (tid >> 5) + 8 * i;
-            if (m < p.M) {
-                const int img = m / HW, r = m - img * HW, oy = r / p.W, ox = r - oy * p.W;
-                riy[i] = oy - 1;
-                rix[i] = ox - 1;
-                rb[i] = img < p.n ? p.a + (long)img * p.a_img : p.b + (long)(img - p.n) * p.b_img;
-                rb[i] += (long)riy[i] * (img < p.n ? p.a_pitch : p.b_pitch) + 3L * rix[i];
-                rsec[i] = img >= p.n;
-            } else {
-                riy[i] = -(1 << 20);   // every tap out of bounds
-                rix[i] = 0;
-                rb[i] = p.a;
-                rsec[i] = false;
-            }
-        }
+        __shared__ float s_tab[3 * 256];
+        const ByteTableA<BM, true> a{.a = p.a, .b = p.b, .a_pitch = p.a_pitch, .a_img = p.a_img, .b_pitch = p.b_pitch, .b_img = p.b_img, .n = p.n, .tab = p.tab, .s_tab = s_tab,
+                                     .H = p.H, .W = p.W, .Ho = p.H, .Wo = p.W, .row_k = 9, .stride = 1, .pad = 1, .M = p.M, .K = p.K};   // 9 = 3 taps x 3 channels of one image row
+        tile_loop<BM, BN>(a, b, p.M, p.K, BiasRelu{p});
     } else {
-#pragma unroll
-        for (int i = 0; i < AR; ++i) {
-            const int m = m0 + (tid >> 3) + 32 * i;
-            if (m < p.M) {
-                const int img = m / HW, r = m - img * HW, oy = r / p.W, ox = r - oy * p.W;
-                riy[i] = oy - 1;
-                rix[i] = ox - 1;
-                ro[i] = (((long)img * p.H + riy[i]) * p.W + rix[i]) * p.cin;
-            } else {
-                riy[i] = -(1 << 20);
-                rix[i] = 0;
-                ro[i] = 0;
-            }
-        }
-    }
-
-    float ga[FIRST ? AR : 1];
-    float4 gv[FIRST ? 1 : AR];
-    float4 gb[BV];
-    auto load_tile = [&](int kt) {
-        const int k0 = kt * BK;
-        if constexpr (FIRST) {
-            const int k = k0 + (tid & 31);
-            const int ky = k / 9, r = k - ky * 9, kx = r / 3, c = r - kx * 3;   // 9 = 3 taps x 3 channels of one image row
-#pragma unroll
-            for (int i = 0; i < AR; ++i) {
-                const int iy = riy[i] + ky, ix = rix[i] + kx;
-                float v = 0.f;
-                if (k < p.K && iy >= 0 && iy < p.H && ix >= 0 && ix < p.W) {
-                    const uint8_t byte = rb[i][(long)ky * (rsec[i] ? p.b_pitch : p.a_pitch) + r];
-                    v = s_tab[256 * c + byte];
-                }
-                ga[i] = v;
-            }
-        } else {
-            const int tap = k0 / p.cin, c0 = k0 - tap * p.cin + 4 * (tid & 7);
-            const int ky = tap / 3, kx = tap - ky * 3;
-#pragma unroll
-            for (int i = 0; i < AR; ++i) {
-                const int iy = riy[i] + ky, ix = rix[i] + kx;
-                float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
-                if (iy >= 0 && iy < p.H && ix >= 0 && ix < p.W)
-                    v = *reinterpret_cast<const float4*>(p.in + ro[i] + ((long)ky * p.W + kx) * p.cin + c0);
-                gv[i] = v;
-            }
-        }
-#pragma unroll
-        for (int i = 0; i < BV; ++i) {
-            const int idx = tid + i * TPB, kr = idx / (BN / 4), nc = idx - kr * (BN / 4);
-            gb[i] = *reinterpret_cast<const float4*>(p.wgt + (long)(k0 + kr) * p.N + n0 + 4 * nc);   // rows up to Kpad exist, N is a multiple of BN
-        }
-    };
-    auto store_tile = [&]() {
-        if constexpr (FIRST) {
-#pragma unroll
-            for (int i = 0; i < AR; ++i) s_a[tid & 31][(tid >> 5) + 8 * i] = ga[i];
-        } else {
-#pragma unroll
-            for (int i = 0; i < AR; ++i) {
-                const int row = (tid >> 3) + 32 * i, kq = 4 * (tid & 7);
-                s_a[kq][row] = gv[i].x;
-                s_a[kq + 1][row] = gv[i].y;
-                s_a[kq + 2][row] = gv[i].z;
-                s_a[kq + 3][row] = gv[i].w;
-            }
-        }
-#pragma unroll
-        for (int i = 0; i < BV; ++i) {
-            const int idx = tid + i * TPB, kr = idx / (BN / 4), nc = idx - kr * (BN / 4);
-            *reinterpret_cast<float4*>(&s_b[kr][4 * nc]) = gb[i];
-        }
-    };
-
-    f32x16 acc[2][TN];
-#pragma unroll
-    for (int i = 0; i < 2; ++i)
-#pragma unroll
-        for (int j = 0; j < TN; ++j)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
-
-    if constexpr (FIRST) __syncthreads();   // the table
-    load_tile(0);
-    const int kh = lane >> 5, l31 = lane & 31;
-    for (int kt = 0; kt < nk; ++kt) {
-        store_tile();
-        __syncthreads();
-        if (kt + 1 < nk) load_tile(kt + 1);
-#pragma unroll
-        for (int kk = 0; kk < BK; kk += 2) {
-            float fa[2], fb[TN];
-#pragma unroll
-            for (int i = 0; i < 2; ++i) fa[i] = s_a[kk + kh][wm * 64 + i * 32 + l31];
-#pragma unroll
-            for (int j = 0; j < TN; ++j) fb[j] = s_b[kk + kh][wn * (BN / 2) + j * 32 + l31];
-#pragma unroll
-            for (int i = 0; i < 2; ++i)
-#pragma unroll
-                for (int j = 0; j < TN; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(fa[i], fb[j], acc[i][j], 0, 0, 0);
-        }
-        __syncthreads();
-    }
-
-    // bias + ReLU; the column is on the lane, so a row of the tile is one 128-byte store per wave
-#pragma unroll
-    for (int j = 0; j < TN; ++j) {
-        const int col = n0 + wn * (BN / 2) + j * 32 + l31;
-        const float bias = p.bias[col];
-#pragma unroll
-        for (int i = 0; i < 2; ++i)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                const int m = m0 + wm * 64 + i * 32 + mfma_row(r, lane);
-                if (m < p.M) p.out[(long)m * p.N + col] = fmaxf(acc[i][j][r] + bias, 0.f);
-            }
+        const NhwcA<BM, true> a{.in = p.in, .H = p.H, .W = p.W, .cin = p.cin, .pitch = p.cin, .kw = 3, .stride = 1, .ph = 1, .pw = 1, .Ho = p.H, .Wo = p.W, .M = p.M, .K = p.K};
+        tile_loop<BM, BN>(a, b, p.M, p.K, BiasRelu{p});
     }
 }
 

@@ -5,32 +5,31 @@
 //   order, rounds it to float32 as Pillow stores the image between its passes, and adds the rows in double in the same way; clip to [0, 255],
 //   (v - 128) / 128. Nothing is kept between the passes, so the workspace does not depend on the image's size. `legacy`: torch's fp32 bilinear,
 //   fmaf(p0, w0, p1 * w1) along x and then along y. The network's input map has four channels, the fourth zero.
-//   The 94 convolutions as implicit GEMMs on the fp32-input MFMA (v_mfma_f32_32x32x2_f32: bit for bit a k-ordered fmaf chain, so an output
-//   element depends neither on its tile nor on its place in a batch), the structure of dists.hip's conv with what Inception needs: kh x kw
+//   The 94 convolutions as implicit GEMMs on the exact-fp32 tile loop of exact_f32_tile.h, with what Inception needs: kh x kw
 //   kernels with their own paddings, stride 1 or 2, a k-tile that may cross a tap (K = kh kw cin in (ky, kx, c) order, cin a multiple of 4: a
 //   thread's float4 of the A tile has its own tap, so cin = 48 and 80 need no padded maps; zero rows behind K and a zero fourth input channel
 //   are exact, fmaf(0, 0, acc) = acc), cout padded to the 64-column tile in the weights alone, and an epilogue relu(acc * scale + shift) - the
 //   BatchNorm folded in fp64 by ir_fid_configure, product and sum rounded separately (the file is built with -ffp-contract=off) - that writes
-//   into a channel slice of a wider NHWC map (pitch + offset), so a block's concatenation costs nothing. A workgroup of four waves owns a
-//   128 x 64 tile, or 64 x 64 where 128-row tiles would leave most of the chip idle (the 8 x 8 and 17 x 17 maps of few images).
+//   into a channel slice of a wider NHWC map (pitch + offset), so a block's concatenation costs nothing. The tile is 128 x 64, or 64 x 64
+//   where 128-row tiles would leave most of the chip idle (the 8 x 8 and 17 x 17 maps of few images).
 //   Pools: 3 x 3, stride 1 (padding 1) or 2 (no padding); max, where padding never wins, or the average over the in-bounds taps, added row by row
 //   from the top-left and divided once by their count.
 //   Means: a lane per channel, the pixels dealt to the waves of a workgroup, the waves' fp64 sums added in wave order, one division: the 2048
 //   features, and on request the per-channel means of thirteen maps.
-// No floating-point atomics. Reads are clipped to the scored rectangle h x w; every store is guarded by the row / element count of its launch.
+// Reads are clipped to the scored rectangle h x w; every store is guarded by the row / element count of its launch.
 #include <algorithm>
 #include <cstdio>
 #include <string>
 #include <vector>
 
 #include "common.h"
+#include "exact_f32_tile.h"
 #include "kernels.h"
 
 namespace {
 
-constexpr int TPB = 256;
-constexpr int BN = 64, BK = 32;
-constexpr int LDB = BN + 4;
+using namespace exact_tile;
+constexpr int BN = 64;
 constexpr int S = IR_FID_SIZE;
 constexpr int MEAN_TPB = 1024;
 constexpr int RESIZE_CLEAN = 0;   // IR_FID_RESIZE_CLEAN of the public header
@@ -118,108 +117,26 @@ struct ConvArgs {
     int out_pitch, out_off;
 };
 
+// BatchNorm (scale, shift) and ReLU into the channel slice
+struct BnRelu {
+    const ConvArgs& p;
+    int col;
+    float sc, sh;
+    IR_DEVINL bool column(int c) {
+        if (c >= p.N) return false;   // cout is padded to the tile in the weights alone
+        col = c;
+        sc = p.scale[c];
+        sh = p.shift[c];
+        return true;
+    }
+    IR_DEVINL void store(int m, float acc) const { p.out[(long)m * p.out_pitch + p.out_off + col] = fmaxf(acc * sc + sh, 0.f); }
+};
+
 template <int BM>
-__global__ __launch_bounds__(TPB) void fid_conv_kernel(ConvArgs p) {
-    constexpr int TM = BM / 64;           // 32-row blocks per wave
-    constexpr int LDA = BM + 4;
-    constexpr int AR = BM * BK / 4 / TPB; // float4 of the A tile per thread
-    constexpr int BV = BK * BN / 4 / TPB; // float4 of the weight tile per thread
-    __shared__ float s_a[BK][LDA];
-    __shared__ float s_b[BK][LDB];
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int wm = wave >> 1, wn = wave & 1;
-    const int m0 = blockIdx.x * BM, n0 = blockIdx.y * BN;
-    const int HoWo = p.Ho * p.Wo;
-    const int nk = (p.K + BK - 1) / BK;
-
-    // the rows this thread gathers: the input position of tap (0, 0) and the offset of its pixel
-    long ro[AR];
-    int riy[AR], rix[AR];
-#pragma unroll
-    for (int i = 0; i < AR; ++i) {
-        const int m = m0 + (tid >> 3) + 32 * i;
-        if (m < p.M) {
-            const int img = m / HoWo, r = m - img * HoWo, oy = r / p.Wo, ox = r - oy * p.Wo;
-            riy[i] = oy * p.stride - p.ph;
-            rix[i] = ox * p.stride - p.pw;
-            ro[i] = (((long)img * p.H + riy[i]) * p.W + rix[i]) * p.in_pitch;
-        } else {
-            riy[i] = -(1 << 20);   // every tap out of bounds
-            rix[i] = 0;
-            ro[i] = 0;
-        }
-    }
-
-    float4 gv[AR];
-    float4 gb[BV];
-    auto load_tile = [&](int kt) {
-        const int k0 = kt * BK;
-        const int k = k0 + 4 * (tid & 7);   // this thread's four k of the tile: one tap, cin is a multiple of 4
-        const int tap = k / p.cin, c0 = k - tap * p.cin;
-        const int ky = tap / p.kw, kx = tap - ky * p.kw;
-        const long toff = ((long)ky * p.W + kx) * p.in_pitch + c0;
-#pragma unroll
-        for (int i = 0; i < AR; ++i) {
-            const int iy = riy[i] + ky, ix = rix[i] + kx;
-            float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
-            if (k < p.K && iy >= 0 && iy < p.H && ix >= 0 && ix < p.W) v = *reinterpret_cast<const float4*>(p.in + ro[i] + toff);
-            gv[i] = v;
-        }
-#pragma unroll
-        for (int i = 0; i < BV; ++i) {
-            const int idx = tid + i * TPB, kr = idx / (BN / 4), nc = idx - kr * (BN / 4);
-            gb[i] = *reinterpret_cast<const float4*>(p.wgt + (long)(k0 + kr) * p.Npad + n0 + 4 * nc);   // rows up to Kpad exist, Npad is a multiple of BN
-        }
-    };
-    auto store_tile = [&]() {
-#pragma unroll
-        for (int i = 0; i < AR; ++i) {
-            const int row = (tid >> 3) + 32 * i, kq = 4 * (tid & 7);
-            s_a[kq][row] = gv[i].x;
-            s_a[kq + 1][row] = gv[i].y;
-            s_a[kq + 2][row] = gv[i].z;
-            s_a[kq + 3][row] = gv[i].w;
-        }
-#pragma unroll
-        for (int i = 0; i < BV; ++i) {
-            const int idx = tid + i * TPB, kr = idx / (BN / 4), nc = idx - kr * (BN / 4);
-            *reinterpret_cast<float4*>(&s_b[kr][4 * nc]) = gb[i];
-        }
-    };
-
-    f32x16 acc[TM];
-#pragma unroll
-    for (int i = 0; i < TM; ++i)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) acc[i][r] = 0.f;
-
-    load_tile(0);
-    const int kh = lane >> 5, l31 = lane & 31;
-    for (int kt = 0; kt < nk; ++kt) {
-        store_tile();
-        __syncthreads();
-        if (kt + 1 < nk) load_tile(kt + 1);
-#pragma unroll
-        for (int kk = 0; kk < BK; kk += 2) {
-            const float fb = s_b[kk + kh][wn * 32 + l31];
-#pragma unroll
-            for (int i = 0; i < TM; ++i) acc[i] = __builtin_amdgcn_mfma_f32_32x32x2f32(s_a[kk + kh][wm * (BM / 2) + i * 32 + l31], fb, acc[i], 0, 0, 0);
-        }
-        __syncthreads();
-    }
-
-    // BatchNorm (scale, shift) and ReLU; the column is on the lane, so a row of the tile is one 128-byte store per wave
-    const int col = n0 + wn * 32 + l31;
-    if (col < p.N) {
-        const float sc = p.scale[col], sh = p.shift[col];
-#pragma unroll
-        for (int i = 0; i < TM; ++i)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                const int m = m0 + wm * (BM / 2) + i * 32 + mfma_row(r, lane);
-                if (m < p.M) p.out[(long)m * p.out_pitch + p.out_off + col] = fmaxf(acc[i][r] * sc + sh, 0.f);
-            }
-    }
+__global__ __launch_bounds__(TPB, BM == 64 ? 7 : 4) void fid_conv_kernel(ConvArgs p) {
+    const NhwcA<BM, false> a{.in = p.in, .H = p.H, .W = p.W, .cin = p.cin, .pitch = p.in_pitch, .kw = p.kw, .stride = p.stride, .ph = p.ph, .pw = p.pw, .Ho = p.Ho, .Wo = p.Wo, .M = p.M, .K = p.K};
+    const KnB<BN, false> b{.b = p.wgt, .ldb = p.Npad};
+    tile_loop<BM, BN>(a, b, p.M, p.K, BnRelu{p});
 }
 
 struct PoolArgs {

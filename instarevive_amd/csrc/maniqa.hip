@@ -1,9 +1,8 @@
 // MANIQA of uint8 HWC RGB device images (ir_maniqa): the model of tools/evaluate_maniqa.py - `crops` windows of crop x crop pixels per image at
 // given origins, a ViT trunk of which four block outputs are tapped, two transposed-attention blocks (TAB) and a Swin stage, twice, two small
 // heads per patch token and one weighted mean over the patches of all crops of an image - in exact fp32 with fp64 statistics.
-//   Contractions: ONE GEMM kernel on the fp32-input MFMA (v_mfma_f32_32x32x2_f32: bit for bit a k-ordered fmaf chain from 0, so an output element
-//   depends neither on the tile it falls in, nor on the crop's place in a launch, nor on the image's place in a batch). A workgroup of four waves
-//   owns a 128 x 64 tile, the k-tile is 32. The A operand is row-major rows, k-major columns (A[k][m]: the 1 x 1 convs read the [C][N] maps as they
+//   Contractions: ONE GEMM kernel on the exact-fp32 tile loop of exact_f32_tile.h (an output element depends neither on the tile it falls in, nor
+//   on the crop's place in a launch, nor on the image's place in a batch), 128 x 64 tiles. The A operand is row-major rows, k-major columns (A[k][m]: the 1 x 1 convs read the [C][N] maps as they
 //   lie), or the implicit im2col of the patch conv straight from the byte image through the 256-entry table at a crop's origin - no crop is ever
 //   materialised as pixels; the origin is clamped into the scored rectangle, so every read stays inside it. The B operand is [K][N] or [N][K].
 //   K need not be a multiple of the k-tile (N = 784 tokens): operands at or behind K read as exact zeros, as do the padded key columns of the
@@ -14,8 +13,8 @@
 //   rows 0 .. 15 of one 32 x 32 MFMA tile (the other rows and columns are fed zeros), gathered by index arithmetic from the cyclically shifted
 //   grid; q is scaled before the chain as the published code does; the relative-position bias and the -100 mask of the shifted windows' region
 //   labels are added in the softmax, which runs per row in fp64 in key order.
-//   LayerNorm, softmax rows, the heads' last linear and the pooled sum: fp64, each a per-lane sequential chain followed by a fixed fold; the exact
-//   GELU through fp64 erf. No floating-point atomics. The crops of a call are processed in passes of as many crops as the workspace holds; the
+//   The heads' last linear and the pooled sum: fp64, each a per-lane sequential chain followed by a fixed fold; LayerNorm, softmax rows and the
+//   exact GELU are the kernels of exact_rows.h. The crops of a call are processed in passes of as many crops as the workspace holds; the
 //   per-patch (s, w) of every crop are kept, and ONE reduction per image makes the score, whose bits thus do not depend on the passes.
 // Every store is guarded by the element count of its launch.
 #include <math.h>
@@ -23,12 +22,14 @@
 #include <algorithm>
 
 #include "common.h"
+#include "exact_f32_tile.h"
+#include "exact_rows.h"
 #include "kernels.h"
 
 namespace {
 
-constexpr int TPB = 256;
-constexpr int BK = 32, BM = 128, BN = 64;
+using namespace exact_tile;
+constexpr int BM = 128, BN = 64;
 constexpr size_t SCORE_BYTES = (size_t)1 << 26;   // the ViT score matrices of one attention launch: as many (crop, head) pairs as fit, at least one
 
 enum { A_ROWS = 0, A_KM = 1, A_PATCH = 2 };
@@ -57,27 +58,45 @@ struct GemmArgs {
     int g0, crops, h, w, crop, patch, G;
 };
 
-template <int AMODE, int BMODE>
-__global__ __launch_bounds__(TPB) void maniqa_gemm_kernel(GemmArgs p) {
-    constexpr int LDA = BM + 4, LDB = BN + 4;
-    constexpr int TM = 2;   // 2 x 2 waves, each 64 x 32 of the tile
-    __shared__ __attribute__((aligned(16))) float s_a[BK][LDA];
-    __shared__ __attribute__((aligned(16))) float s_b[BK][LDB];
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int wm = wave >> 1, wn = wave & 1;
-    const int m0 = blockIdx.x * BM, n0 = blockIdx.y * BN;
-    const int pair = p.z0 + (int)blockIdx.z, zi = pair / p.zdiv, zj = pair - zi * p.zdiv;
-    const float* A = AMODE == A_PATCH ? nullptr : p.a + zi * p.a_s0 + zj * p.a_s1 + (long)blockIdx.z * p.a_sl;
-    const float* B = p.b + zi * p.b_s0 + zj * p.b_s1 + (long)blockIdx.z * p.b_sl;
-    const long coff = zi * p.c_s0 + zj * p.c_s1 + (long)blockIdx.z * p.c_sl;
-    const int nk = (p.K + BK - 1) / BK;
+// A_KM: k-major columns A[k][m] (the 1 x 1 convs read the [C][N] maps as they lie): the tile is copied as it lies, zeros at or behind K and M
+struct KmA {
+    static constexpr int AR = BM * BK / 4 / TPB;
+    const float* a;
+    long lda;
+    int M, K;
+    int m0;
+    float4 gv[AR];
 
-    constexpr int AR = AMODE == A_PATCH ? BM * BK / TPB : BM * BK / 4 / TPB;   // 16 scalars of one k / 4 float4
-    long ro[AR];
+    IR_DEVINL void rows(int m) { m0 = m; }
+    IR_DEVINL void load(int k0) {
 #pragma unroll
-    for (int i = 0; i < AR; ++i) {
-        if constexpr (AMODE == A_PATCH) {
-            const int m = m0 + (tid >> 5) + 8 * i;
+        for (int i = 0; i < AR; ++i) {
+            const int idx = (int)threadIdx.x + i * TPB, kr = idx / (BM / 4), mc = idx - kr * (BM / 4);
+            gv[i] = (k0 + kr < K && m0 + 4 * mc < M) ? *reinterpret_cast<const float4*>(a + (long)(k0 + kr) * lda + m0 + 4 * mc) : make_float4(0.f, 0.f, 0.f, 0.f);
+        }
+    }
+    template <int LDA>
+    IR_DEVINL void store(float (&s_a)[BK][LDA]) const {
+#pragma unroll
+        for (int i = 0; i < AR; ++i) {
+            const int idx = (int)threadIdx.x + i * TPB, kr = idx / (BM / 4), mc = idx - kr * (BM / 4);
+            *reinterpret_cast<float4*>(&s_a[kr][4 * mc]) = gv[i];
+        }
+    }
+};
+
+// A_PATCH: the implicit im2col of the patch conv from the byte image through the 256-entry table; row m is patch token m % tokens of crop
+// g0 + m / tokens at its origin (clamped into the scored rectangle), k is (channel, ky, kx)
+struct PatchA {
+    static constexpr int AR = BM * BK / TPB;
+    const GemmArgs& p;
+    long ro[AR];
+    float ga[AR];
+
+    IR_DEVINL void rows(int m0) {
+#pragma unroll
+        for (int i = 0; i < AR; ++i) {
+            const int m = m0 + ((int)threadIdx.x >> 5) + 8 * i;
             ro[i] = -1;
             if (m < p.M) {
                 const int tokens = p.G * p.G, lc = m / tokens, t = m - lc * tokens, gy = t / p.G, gx = t - gy * p.G;
@@ -85,131 +104,59 @@ __global__ __launch_bounds__(TPB) void maniqa_gemm_kernel(GemmArgs p) {
                 const int oy = min(max(p.origins[2 * g], 0), p.h - p.crop), ox = min(max(p.origins[2 * g + 1], 0), p.w - p.crop);
                 ro[i] = (g / p.crops) * p.img_stride + (long)(oy + gy * p.patch) * p.pitch + 3L * (ox + gx * p.patch);
             }
-        } else if constexpr (AMODE == A_ROWS) {
-            const int m = m0 + (tid >> 3) + 32 * i;
-            ro[i] = m < p.M ? (long)m * p.lda : -1;
-        } else {
-            ro[i] = 0;
         }
     }
+    IR_DEVINL void load(int k0) {
+        const int k = k0 + ((int)threadIdx.x & 31), pp = p.patch * p.patch;
+        const int ch = k / pp, r = k - ch * pp, ky = r / p.patch, kx = r - ky * p.patch;
+        const long ko = (long)ky * p.pitch + 3L * kx + ch;
+#pragma unroll
+        for (int i = 0; i < AR; ++i) ga[i] = (k < p.K && ro[i] >= 0) ? p.tab[p.img[ro[i] + ko]] : 0.f;
+    }
+    template <int LDA>
+    IR_DEVINL void store(float (&s_a)[BK][LDA]) const { store_a_k1(s_a, ga); }
+};
 
-    float ga[AMODE == A_PATCH ? AR : 1];
-    float4 gv[AMODE == A_PATCH ? 1 : AR];
-    float4 gb[2];
-    const float4 zero4 = make_float4(0.f, 0.f, 0.f, 0.f);
-    auto load_tile = [&](int kt) {
-        const int k0 = kt * BK;
-        if constexpr (AMODE == A_PATCH) {
-            const int k = k0 + (tid & 31), pp = p.patch * p.patch;
-            const int ch = k / pp, r = k - ch * pp, ky = r / p.patch, kx = r - ky * p.patch;
-            const long ko = (long)ky * p.pitch + 3L * kx + ch;
-#pragma unroll
-            for (int i = 0; i < AR; ++i) ga[i] = (k < p.K && ro[i] >= 0) ? p.tab[p.img[ro[i] + ko]] : 0.f;
-        } else if constexpr (AMODE == A_ROWS) {
-            const int k = k0 + 4 * (tid & 7);
-#pragma unroll
-            for (int i = 0; i < AR; ++i) gv[i] = (ro[i] >= 0 && k < p.K) ? *reinterpret_cast<const float4*>(A + ro[i] + k) : zero4;
-        } else {
-#pragma unroll
-            for (int i = 0; i < AR; ++i) {
-                const int idx = tid + i * TPB, kr = idx / (BM / 4), mc = idx - kr * (BM / 4);
-                gv[i] = (k0 + kr < p.K && m0 + 4 * mc < p.M) ? *reinterpret_cast<const float4*>(A + (long)(k0 + kr) * p.lda + m0 + 4 * mc) : zero4;
-            }
-        }
-#pragma unroll
-        for (int i = 0; i < 2; ++i) {
-            const int idx = tid + i * TPB;
-            if constexpr (BMODE == B_KN) {
-                const int kr = idx / (BN / 4), nc = idx - kr * (BN / 4);
-                gb[i] = (k0 + kr < p.Kb && n0 + 4 * nc < p.N) ? *reinterpret_cast<const float4*>(B + (long)(k0 + kr) * p.ldb + n0 + 4 * nc) : zero4;
-            } else {
-                const int row = idx >> 3, kq = 4 * (idx & 7);
-                gb[i] = (n0 + row < p.N && k0 + kq < p.K) ? *reinterpret_cast<const float4*>(B + (long)(n0 + row) * p.ldb + k0 + kq) : zero4;
-            }
-        }
+// acc * alpha + bias[col] + residual, separate roundings; tstore: element (m, col) lies at col * ldc + m (c and the residual)
+struct AlphaBiasRes {
+    const GemmArgs& p;
+    float* c;
+    const float* res;
+    int col;
+    float bs;
+    IR_DEVINL bool column(int n) {
+        if (n >= p.N) return false;
+        col = n;
+        bs = p.bias ? p.bias[n] : 0.f;
+        return true;
+    }
+    IR_DEVINL void store(int m, float acc) const {
+        const long at = p.tstore ? (long)col * p.ldc + m : (long)m * p.ldc + col;
+        float v = acc * p.alpha;
+        v = v + bs;
+        if (res) v = v + res[at];
+        c[at] = v;
+    }
+};
+
+template <int AMODE, int BMODE>
+__global__ __launch_bounds__(TPB, AMODE == A_PATCH ? 3 : AMODE == A_KM ? 5 : 4) void maniqa_gemm_kernel(GemmArgs p) {
+    const int pair = p.z0 + (int)blockIdx.z, zi = pair / p.zdiv, zj = pair - zi * p.zdiv;
+    const float* A = AMODE == A_PATCH ? nullptr : p.a + zi * p.a_s0 + zj * p.a_s1 + (long)blockIdx.z * p.a_sl;
+    const float* B = p.b + zi * p.b_s0 + zj * p.b_s1 + (long)blockIdx.z * p.b_sl;
+    const AlphaBiasRes epi{p, p.c + zi * p.c_s0 + zj * p.c_s1 + (long)blockIdx.z * p.c_sl, p.res ? p.res + zi * p.r_s0 : nullptr};
+    const auto run = [&](auto a) {
+        if constexpr (BMODE == B_KN)
+            tile_loop<BM, BN>(a, KnB<BN, true>{.b = B, .ldb = p.ldb, .Kb = p.Kb, .N = p.N}, p.M, p.K, epi);
+        else
+            tile_loop<BM, BN>(a, NkB<BN, true>{.b = B, .ldb = p.ldb, .N = p.N, .K = p.K}, p.M, p.K, epi);
     };
-    auto store_tile = [&]() {
-        if constexpr (AMODE == A_PATCH) {
-#pragma unroll
-            for (int i = 0; i < AR; ++i) s_a[tid & 31][(tid >> 5) + 8 * i] = ga[i];
-        } else if constexpr (AMODE == A_ROWS) {
-#pragma unroll
-            for (int i = 0; i < AR; ++i) {
-                const int row = (tid >> 3) + 32 * i, kq = 4 * (tid & 7);
-                s_a[kq][row] = gv[i].x;
-                s_a[kq + 1][row] = gv[i].y;
-                s_a[kq + 2][row] = gv[i].z;
-                s_a[kq + 3][row] = gv[i].w;
-            }
-        } else {
-#pragma unroll
-            for (int i = 0; i < AR; ++i) {
-                const int idx = tid + i * TPB, kr = idx / (BM / 4), mc = idx - kr * (BM / 4);
-                *reinterpret_cast<float4*>(&s_a[kr][4 * mc]) = gv[i];
-            }
-        }
-#pragma unroll
-        for (int i = 0; i < 2; ++i) {
-            const int idx = tid + i * TPB;
-            if constexpr (BMODE == B_KN) {
-                const int kr = idx / (BN / 4), nc = idx - kr * (BN / 4);
-                *reinterpret_cast<float4*>(&s_b[kr][4 * nc]) = gb[i];
-            } else {
-                const int row = idx >> 3, kq = 4 * (idx & 7);
-                s_b[kq][row] = gb[i].x;
-                s_b[kq + 1][row] = gb[i].y;
-                s_b[kq + 2][row] = gb[i].z;
-                s_b[kq + 3][row] = gb[i].w;
-            }
-        }
-    };
-
-    f32x16 acc[TM];
-#pragma unroll
-    for (int i = 0; i < TM; ++i)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) acc[i][r] = 0.f;
-
-    load_tile(0);
-    const int kh = lane >> 5, l31 = lane & 31;
-    for (int kt = 0; kt < nk; ++kt) {
-        store_tile();
-        __syncthreads();
-        if (kt + 1 < nk) load_tile(kt + 1);
-#pragma unroll
-        for (int kk = 0; kk < BK; kk += 2) {
-            const float fb = s_b[kk + kh][wn * 32 + l31];
-#pragma unroll
-            for (int i = 0; i < TM; ++i) acc[i] = __builtin_amdgcn_mfma_f32_32x32x2f32(s_a[kk + kh][wm * 64 + i * 32 + l31], fb, acc[i], 0, 0, 0);
-        }
-        __syncthreads();
-    }
-
-    const int col = n0 + wn * 32 + l31;
-    if (col < p.N) {
-        const float bs = p.bias ? p.bias[col] : 0.f;
-        const float* R = p.res ? p.res + zi * p.r_s0 : nullptr;
-        float* Cc = p.c + coff;
-#pragma unroll
-        for (int i = 0; i < TM; ++i)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                const int m = m0 + wm * 64 + i * 32 + mfma_row(r, lane);
-                if (m < p.M) {
-                    const long at = p.tstore ? (long)col * p.ldc + m : (long)m * p.ldc + col;
-                    float v = acc[i][r] * p.alpha;
-                    v = v + bs;
-                    if (R) v = v + R[at];
-                    Cc[at] = v;
-                }
-            }
-    }
-}
-
-IR_DEVINL double wave_sum_d(double v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-    return v;
+    if constexpr (AMODE == A_PATCH)
+        run(PatchA{p});
+    else if constexpr (AMODE == A_KM)
+        run(KmA{.a = A, .lda = p.lda, .M = p.M, .K = p.K});
+    else
+        run(RowsA<BM, true>{.a = A, .lda = p.lda, .M = p.M, .K = p.K});
 }
 
 // x[crop][0] = cls + pos[0], x[crop][1 + t] = emb[crop][t] + pos[1 + t]
@@ -223,48 +170,6 @@ __global__ __launch_bounds__(TPB) void maniqa_tokens_kernel(const float* __restr
     const long b = row / T;
     const float v = t == 0 ? cls[c] : emb[(b * (T - 1) + t - 1) * C + c];
     x[i] = v + pos[(long)t * C + c];
-}
-
-// LayerNorm of row blockIdx.x * 4 + wave: lane l sums columns l, l + 64, ... in order, the lanes fold in a fixed butterfly
-__global__ __launch_bounds__(TPB) void maniqa_ln_kernel(const float* __restrict__ x, long rows, int C, const float* __restrict__ gamma, const float* __restrict__ beta,
-                                                        double eps, float* __restrict__ out) {
-    const int lane = threadIdx.x & 63;
-    const long row = (long)blockIdx.x * (TPB / 64) + (threadIdx.x >> 6);
-    if (row >= rows) return;   // uniform over the wave
-    const float* q = x + row * C;
-    double s = 0.0;
-    for (int c = lane; c < C; c += 64) s += (double)q[c];
-    const double mean = wave_sum_d(s) / (double)C;
-    double v = 0.0;
-    for (int c = lane; c < C; c += 64) {
-        const double d = (double)q[c] - mean;
-        v += d * d;
-    }
-    const double rstd = 1.0 / sqrt(wave_sum_d(v) / (double)C + eps);
-    for (int c = lane; c < C; c += 64) out[row * C + c] = (float)(((double)q[c] - mean) * rstd * (double)gamma[c] + (double)beta[c]);
-}
-
-// softmax of row blockIdx.x * 4 + wave of [rows][Tpad], in place over its first T columns; the columns behind them become 0
-__global__ __launch_bounds__(TPB) void maniqa_softmax_kernel(float* __restrict__ s, long rows, int T, int Tpad) {
-    const int lane = threadIdx.x & 63;
-    const long row = (long)blockIdx.x * (TPB / 64) + (threadIdx.x >> 6);
-    if (row >= rows) return;   // uniform over the wave
-    float* q = s + row * Tpad;
-    float mx = -INFINITY;
-    for (int t = lane; t < T; t += 64) mx = fmaxf(mx, q[t]);
-    mx = wave_max(mx);
-    double sum = 0.0;
-    for (int t = lane; t < T; t += 64) sum += exp((double)q[t] - (double)mx);
-    sum = wave_sum_d(sum);
-    for (int t = lane; t < Tpad; t += 64) q[t] = t < T ? (float)(exp((double)q[t] - (double)mx) / sum) : 0.f;
-}
-
-// the exact GELU, in place
-__global__ __launch_bounds__(TPB) void maniqa_gelu_kernel(float* __restrict__ x, long total) {
-    const long i = (long)blockIdx.x * TPB + threadIdx.x;
-    if (i >= total) return;
-    const double v = (double)x[i];
-    x[i] = (float)(0.5 * v * (1.0 + erf(v * 0.70710678118654752440)));
 }
 
 // out[b][c][r] = in[b][r][c] for r < R, c < C: rows of ld_in floats, a batch moves by in_stride / out_stride; 32 x 32 tiles through LDS
@@ -417,8 +322,6 @@ __global__ __launch_bounds__(TPB) void maniqa_pool_kernel(const double* __restri
 }
 
 size_t up256(size_t b) { return (b + 255) & ~(size_t)255; }
-unsigned blocks_of(long total, int per) { return (unsigned)((total + per - 1) / per); }
-
 GemmArgs gemm_args(const float* a, long lda, const float* b, long ldb, int M, int N, int K, const float* bias, const float* res, float* c, long ldc) {
     GemmArgs p{};
     p.a = a; p.lda = lda; p.b = b; p.ldb = ldb; p.Kb = K; p.M = M; p.N = N; p.K = K;
@@ -428,9 +331,6 @@ GemmArgs gemm_args(const float* a, long lda, const float* b, long ldb, int M, in
 template <int AMODE, int BMODE>
 void launch_gemm(const GemmArgs& p, int z, hipStream_t s) {
     hipLaunchKernelGGL((maniqa_gemm_kernel<AMODE, BMODE>), dim3((unsigned)((p.M + BM - 1) / BM), (unsigned)((p.N + BN - 1) / BN), (unsigned)z), dim3(TPB), 0, s, p);
-}
-void launch_ln(const float* x, long rows, int C, const float* g, const float* b, double eps, float* out, hipStream_t s) {
-    hipLaunchKernelGGL(maniqa_ln_kernel, dim3(blocks_of(rows, TPB / 64)), dim3(TPB), 0, s, x, rows, C, g, b, eps, out);
 }
 
 }  // namespace
@@ -541,7 +441,7 @@ int ir_launch_maniqa(const IrManiqaModel& m, const uint8_t* img, int rows, long 
                 p.z0 = z0; p.zdiv = m.vit_heads;
                 p.a_s0 = p.b_s0 = (long)T * 3 * E; p.a_s1 = p.b_s1 = hd; p.c_sl = (long)T * pl.Tpad;
                 launch_gemm<A_ROWS, B_NK>(p, z, s);
-                hipLaunchKernelGGL(maniqa_softmax_kernel, dim3(blocks_of((long)z * T, TPB / 64)), dim3(TPB), 0, s, S, (long)z * T, T, pl.Tpad);
+                launch_softmax(S, (long)z * T, T, pl.Tpad, s);
                 p = gemm_args(S, pl.Tpad, QKV + 2 * E, 3 * E, T, hd, pl.Tpad, nullptr, nullptr, O, E);   // p v; the padded columns of p are 0
                 p.Kb = T;
                 p.z0 = z0; p.zdiv = m.vit_heads;
@@ -553,7 +453,7 @@ int ir_launch_maniqa(const IrManiqaModel& m, const uint8_t* img, int rows, long 
             launch_ln(X, R, E, b.ln2g, b.ln2b, 1e-6, HN, s);
             p = gemm_args(HN, E, b.f1w, m.vit_mlp, (int)R, m.vit_mlp, E, b.f1b, nullptr, F, m.vit_mlp);
             launch_gemm<A_ROWS, B_KN>(p, 1, s);
-            hipLaunchKernelGGL(maniqa_gelu_kernel, dim3(blocks_of(R * m.vit_mlp, TPB)), dim3(TPB), 0, s, F, R * m.vit_mlp);
+            launch_gelu(F, R * m.vit_mlp, s);
             p = gemm_args(F, m.vit_mlp, b.f2w, E, (int)R, E, m.vit_mlp, b.f2b, X, X, E);
             launch_gemm<A_ROWS, B_KN>(p, 1, s);
             if (tap < 4 && m.taps[tap] == l) {   // the patch tokens [N][E] of every crop -> rows tap * E .. of its map [4 E][N]
@@ -573,7 +473,7 @@ int ir_launch_maniqa(const IrManiqaModel& m, const uint8_t* img, int rows, long 
                     p = gemm_args(q, 3 * N, q + N, 3 * N, C, C, N, nullptr, nullptr, TS, C);   // (q k^T) * N^-0.5
                     p.alpha = 1.0f / sqrtf((float)N);
                     launch_gemm<A_ROWS, B_NK>(p, 1, s);
-                    hipLaunchKernelGGL(maniqa_softmax_kernel, dim3(blocks_of(C, TPB / 64)), dim3(TPB), 0, s, TS, (long)C, C, C);
+                    launch_softmax(TS, (long)C, C, C, s);
                     p = gemm_args(TS, C, q + 2 * N, 3 * N, C, N, C, nullptr, cur + (long)j * C * N, oth + (long)j * C * N, C);
                     p.tstore = 1;   // element [c][n] at n * C + c, the residual from the same address of the input map
                     launch_gemm<A_ROWS, B_KN>(p, 1, s);
@@ -601,7 +501,7 @@ int ir_launch_maniqa(const IrManiqaModel& m, const uint8_t* img, int rows, long 
                     launch_ln(Y, RS, D, b.ln2g, b.ln2b, 1e-5, YN, s);
                     p = gemm_args(YN, D, b.f1w, mlp, (int)RS, mlp, D, b.f1b, nullptr, SF, mlp);
                     launch_gemm<A_ROWS, B_KN>(p, 1, s);
-                    hipLaunchKernelGGL(maniqa_gelu_kernel, dim3(blocks_of(RS * mlp, TPB)), dim3(TPB), 0, s, SF, RS * mlp);
+                    launch_gelu(SF, RS * mlp, s);
                     p = gemm_args(SF, mlp, b.f2w, D, (int)RS, D, mlp, b.f2b, Y, Y, D);
                     launch_gemm<A_ROWS, B_KN>(p, 1, s);
                 }

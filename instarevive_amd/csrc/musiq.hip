@@ -1,9 +1,8 @@
 // MUSIQ of uint8 HWC RGB device images (ir_musiq): the model of tools/evaluate_musiq.py - the image at three scales, 32 x 32 patches with 'SAME'
 // padding, a small ResNet stem per patch, the hashed spatial and the scale embedding, 14 pre-LN transformer blocks over all T tokens of the image,
 // the final LayerNorm of the class token and a linear head - in exact fp32 with fp64 statistics.
-//   Contractions: ONE GEMM kernel on the fp32-input MFMA (v_mfma_f32_32x32x2_f32: bit for bit a k-ordered fmaf chain from 0, so an output element
-//   depends neither on the tile it falls in, nor on T, nor on its place in a batch). A workgroup of four waves owns a 128 x 64 tile, the k-tile is
-//   32. The A operand is row-major rows (the 1 x 1 convs on NHWC maps, the embedding, the linears, Q and the probabilities), the implicit im2col of
+//   Contractions: ONE GEMM kernel on the exact-fp32 tile loop of exact_f32_tile.h (an output element depends neither on the tile it falls in, nor
+//   on T, nor on its place in a batch), 128 x 64 tiles. The A operand is row-major rows (the 1 x 1 convs on NHWC maps, the embedding, the linears, Q and the probabilities), the implicit im2col of
 //   a 3 x 3 'SAME' conv over each patch's 8 x 8 map, or that of the 7 x 7 stride-2 stem conv over the patch's 32 x 32 x 3 input (K = 147, zero
 //   behind it); the B operand is [K][N] (the repacked weights, V) or [N][K] (K of Q K^T). Rows of B at or behind Kb read as zero, as do the
 //   padded columns of the probabilities: the PV product's K = T is padded with exact zeros. Epilogue: acc * alpha + bias[col] + residual, separate
@@ -12,20 +11,22 @@
 //   The patch kernel makes every patch's input: the byte through the 256-entry table ((v / 255 - 0.5) * 2 in fp32) at the image's own size, or
 //   torch's bicubic (A = -0.75, align_corners = False, taps clamped, no antialias) of the table values for a resized scale - coordinates, weights and
 //   the 16-tap sum in fp64, rounded once; 0 outside the scale's image ('SAME' padding in that domain). Reads are clipped to the scored rectangle.
-//   GroupNorm (per patch), LayerNorm, the softmax rows and the head: fp64 sums, each a per-lane sequential chain followed by a fixed butterfly; the
-//   exact GELU through fp64 erf. No floating-point atomics: an image gives the same bits on every call and at every place in a batch.
+//   GroupNorm (per patch) and the head: fp64 sums, each a per-lane sequential chain followed by a fixed butterfly; LayerNorm, the softmax rows
+//   and the exact GELU are the kernels of exact_rows.h. An image gives the same bits on every call and at every place in a batch.
 // Every store is guarded by the element count of its launch.
 #include <math.h>
 
 #include <algorithm>
 
 #include "common.h"
+#include "exact_f32_tile.h"
+#include "exact_rows.h"
 #include "kernels.h"
 
 namespace {
 
-constexpr int TPB = 256;
-constexpr int BK = 32, BM = 128, BN = 64;
+using namespace exact_tile;
+constexpr int BM = 128, BN = 64;
 constexpr int PATCH = 32, PIN = PATCH * PATCH * 3;   // a patch's input values
 constexpr int STEM_K = 147, STEM_O = 16, POOL_O = 8, STEM_C = 64, OUT_C = 256;   // 7 * 7 * 3; 32 -> 16 -> 8; channel counts of the stem
 // The score matrices of one attention launch: as many (image, head) pairs as fit SCORE_BYTES, but the heads of one image together while they fit
@@ -53,29 +54,20 @@ struct GemmArgs {
     long a_s0, a_s1, a_sl, b_s0, b_s1, b_sl, c_s0, c_s1, c_sl;
 };
 
-template <int AMODE, int BMODE>
-__global__ __launch_bounds__(TPB) void musiq_gemm_kernel(GemmArgs p) {
-    constexpr int LDA = BM + 4, LDB = BN + 4;
-    constexpr int TM = 2;   // 2 x 2 waves, each 64 x 32 of the tile
-    __shared__ float s_a[BK][LDA];
-    __shared__ float s_b[BK][LDB];
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int wm = wave >> 1, wn = wave & 1;
-    const int m0 = blockIdx.x * BM, n0 = blockIdx.y * BN;
-    const int pair = p.z0 + (int)blockIdx.z, zi = pair / p.zdiv, zj = pair - zi * p.zdiv;
-    const float* A = p.a + zi * p.a_s0 + zj * p.a_s1 + (long)blockIdx.z * p.a_sl;
-    const float* B = p.b + zi * p.b_s0 + zj * p.b_s1 + (long)blockIdx.z * p.b_sl;
-    float* Cc = p.c + zi * p.c_s0 + zj * p.c_s1 + (long)blockIdx.z * p.c_sl;
-    const int nk = (p.K + BK - 1) / BK;
-
-    constexpr int AR = AMODE == A_STEM ? BM * BK / TPB : BM * BK / 4 / TPB;   // 16 scalars of one k / 4 float4
+// A_STEM: the implicit im2col of the 7 x 7 stride-2 'SAME' stem conv over fp32 patches [M / 256][32][32][3], K = 147 in (ky, kx, c) order
+struct StemA {
+    static constexpr int AR = BM * BK / TPB;
+    const float* a;
+    int M;
     long ro[AR];
     int riy[AR], rix[AR];
+    float ga[AR];
+
+    IR_DEVINL void rows(int m0) {
 #pragma unroll
-    for (int i = 0; i < AR; ++i) {
-        if constexpr (AMODE == A_STEM) {
-            const int m = m0 + (tid >> 5) + 8 * i;
-            if (m < p.M) {
+        for (int i = 0; i < AR; ++i) {
+            const int m = m0 + ((int)threadIdx.x >> 5) + 8 * i;
+            if (m < M) {
                 const int pt = m / (STEM_O * STEM_O), r = m - pt * (STEM_O * STEM_O), oy = r / STEM_O, ox = r - oy * STEM_O;
                 riy[i] = oy * 2 - 2;   // 'SAME' at stride 2: 2 in front, 3 behind
                 rix[i] = ox * 2 - 2;
@@ -85,141 +77,61 @@ __global__ __launch_bounds__(TPB) void musiq_gemm_kernel(GemmArgs p) {
                 rix[i] = 0;
                 ro[i] = 0;
             }
-        } else if constexpr (AMODE == A_CONV3) {
-            const int m = m0 + (tid >> 3) + 32 * i;
-            if (m < p.M) {
-                const int HW = p.H * p.W, im = m / HW, r = m - im * HW, oy = r / p.W, ox = r - oy * p.W;
-                riy[i] = oy - 1;
-                rix[i] = ox - 1;
-                ro[i] = (((long)im * p.H + riy[i]) * p.W + rix[i]) * p.cin;
-            } else {
-                riy[i] = -(1 << 20);
-                rix[i] = 0;
-                ro[i] = 0;
-            }
-        } else {
-            const int m = m0 + (tid >> 3) + 32 * i;
-            ro[i] = m < p.M ? (long)m * p.lda : -1;
-            riy[i] = rix[i] = 0;
         }
     }
+    IR_DEVINL void load(int k0) {
+        const int k = k0 + ((int)threadIdx.x & 31);
+        const int ky = k / 21, r = k - ky * 21, kx = r / 3, ch = r - kx * 3;   // 21 = 7 taps x 3 channels of one row
+#pragma unroll
+        for (int i = 0; i < AR; ++i) {
+            const int iy = riy[i] + ky, ix = rix[i] + kx;
+            float v = 0.f;
+            if (k < STEM_K && iy >= 0 && iy < PATCH && ix >= 0 && ix < PATCH) v = a[ro[i] + (iy * PATCH + ix) * 3 + ch];
+            ga[i] = v;
+        }
+    }
+    template <int LDA>
+    IR_DEVINL void store(float (&s_a)[BK][LDA]) const { store_a_k1(s_a, ga); }
+};
 
-    float ga[AMODE == A_STEM ? AR : 1];
-    float4 gv[AMODE == A_STEM ? 1 : AR];
-    float4 gb[2];
-    const float4 zero4 = make_float4(0.f, 0.f, 0.f, 0.f);
-    auto load_tile = [&](int kt) {
-        const int k0 = kt * BK;
-        if constexpr (AMODE == A_STEM) {
-            const int k = k0 + (tid & 31);
-            const int ky = k / 21, r = k - ky * 21, kx = r / 3, ch = r - kx * 3;   // 21 = 7 taps x 3 channels of one row
-#pragma unroll
-            for (int i = 0; i < AR; ++i) {
-                const int iy = riy[i] + ky, ix = rix[i] + kx;
-                float v = 0.f;
-                if (k < STEM_K && iy >= 0 && iy < PATCH && ix >= 0 && ix < PATCH) v = A[ro[i] + (iy * PATCH + ix) * 3 + ch];
-                ga[i] = v;
-            }
-        } else if constexpr (AMODE == A_CONV3) {
-            const int tap = k0 / p.cin, c0 = k0 - tap * p.cin + 4 * (tid & 7);   // cin is a multiple of BK: a k-tile never crosses a tap
-            const int ky = tap / 3, kx = tap - ky * 3;
-#pragma unroll
-            for (int i = 0; i < AR; ++i) {
-                const int iy = riy[i] + ky, ix = rix[i] + kx;
-                float4 v = zero4;
-                if (iy >= 0 && iy < p.H && ix >= 0 && ix < p.W) v = *reinterpret_cast<const float4*>(A + ro[i] + ((long)ky * p.W + kx) * p.cin + c0);
-                gv[i] = v;
-            }
-        } else {
-#pragma unroll
-            for (int i = 0; i < AR; ++i) gv[i] = ro[i] >= 0 ? *reinterpret_cast<const float4*>(A + ro[i] + k0 + 4 * (tid & 7)) : zero4;
-        }
-#pragma unroll
-        for (int i = 0; i < 2; ++i) {
-            const int idx = tid + i * TPB;
-            if constexpr (BMODE == B_KN) {
-                const int kr = idx / (BN / 4), nc = idx - kr * (BN / 4);
-                gb[i] = (k0 + kr < p.Kb && n0 + 4 * nc < p.N) ? *reinterpret_cast<const float4*>(B + (long)(k0 + kr) * p.ldb + n0 + 4 * nc) : zero4;
-            } else {
-                const int row = idx >> 3, kq = 4 * (idx & 7);
-                gb[i] = n0 + row < p.N ? *reinterpret_cast<const float4*>(B + (long)(n0 + row) * p.ldb + k0 + kq) : zero4;
-            }
-        }
+// acc * alpha + bias[col] + residual, separate roundings
+struct AlphaBiasRes {
+    const GemmArgs& p;
+    float* c;
+    int col;
+    float bs;
+    IR_DEVINL bool column(int n) {
+        if (n >= p.N) return false;
+        col = n;
+        bs = p.bias ? p.bias[n] : 0.f;
+        return true;
+    }
+    IR_DEVINL void store(int m, float acc) const {
+        float v = acc * p.alpha;   // 1 or a power of two: exact
+        v = v + bs;
+        if (p.res) v = v + p.res[(long)m * p.ldc + col];
+        c[(long)m * p.ldc + col] = v;
+    }
+};
+
+template <int AMODE, int BMODE>
+__global__ __launch_bounds__(TPB, AMODE == A_STEM ? 3 : 4) void musiq_gemm_kernel(GemmArgs p) {
+    const int pair = p.z0 + (int)blockIdx.z, zi = pair / p.zdiv, zj = pair - zi * p.zdiv;
+    const float* A = p.a + zi * p.a_s0 + zj * p.a_s1 + (long)blockIdx.z * p.a_sl;
+    const float* B = p.b + zi * p.b_s0 + zj * p.b_s1 + (long)blockIdx.z * p.b_sl;
+    const AlphaBiasRes epi{p, p.c + zi * p.c_s0 + zj * p.c_s1 + (long)blockIdx.z * p.c_sl};
+    const auto run = [&](auto a) {
+        if constexpr (BMODE == B_KN)
+            tile_loop<BM, BN>(a, KnB<BN, true>{.b = B, .ldb = p.ldb, .Kb = p.Kb, .N = p.N}, p.M, p.K, epi);
+        else
+            tile_loop<BM, BN>(a, NkB<BN, false>{.b = B, .ldb = p.ldb, .N = p.N, .K = p.K}, p.M, p.K, epi);
     };
-    auto store_tile = [&]() {
-        if constexpr (AMODE == A_STEM) {
-#pragma unroll
-            for (int i = 0; i < AR; ++i) s_a[tid & 31][(tid >> 5) + 8 * i] = ga[i];
-        } else {
-#pragma unroll
-            for (int i = 0; i < AR; ++i) {
-                const int row = (tid >> 3) + 32 * i, kq = 4 * (tid & 7);
-                s_a[kq][row] = gv[i].x;
-                s_a[kq + 1][row] = gv[i].y;
-                s_a[kq + 2][row] = gv[i].z;
-                s_a[kq + 3][row] = gv[i].w;
-            }
-        }
-#pragma unroll
-        for (int i = 0; i < 2; ++i) {
-            const int idx = tid + i * TPB;
-            if constexpr (BMODE == B_KN) {
-                const int kr = idx / (BN / 4), nc = idx - kr * (BN / 4);
-                *reinterpret_cast<float4*>(&s_b[kr][4 * nc]) = gb[i];
-            } else {
-                const int row = idx >> 3, kq = 4 * (idx & 7);
-                s_b[kq][row] = gb[i].x;
-                s_b[kq + 1][row] = gb[i].y;
-                s_b[kq + 2][row] = gb[i].z;
-                s_b[kq + 3][row] = gb[i].w;
-            }
-        }
-    };
-
-    f32x16 acc[TM];
-#pragma unroll
-    for (int i = 0; i < TM; ++i)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) acc[i][r] = 0.f;
-
-    load_tile(0);
-    const int kh = lane >> 5, l31 = lane & 31;
-    for (int kt = 0; kt < nk; ++kt) {
-        store_tile();
-        __syncthreads();
-        if (kt + 1 < nk) load_tile(kt + 1);
-#pragma unroll
-        for (int kk = 0; kk < BK; kk += 2) {
-            const float fb = s_b[kk + kh][wn * 32 + l31];
-#pragma unroll
-            for (int i = 0; i < TM; ++i) acc[i] = __builtin_amdgcn_mfma_f32_32x32x2f32(s_a[kk + kh][wm * 64 + i * 32 + l31], fb, acc[i], 0, 0, 0);
-        }
-        __syncthreads();
-    }
-
-    // the column is on the lane, so a row of the tile is one 128-byte store per wave
-    const int col = n0 + wn * 32 + l31;
-    if (col < p.N) {
-        const float bs = p.bias ? p.bias[col] : 0.f;
-#pragma unroll
-        for (int i = 0; i < TM; ++i)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                const int m = m0 + wm * 64 + i * 32 + mfma_row(r, lane);
-                if (m < p.M) {
-                    float v = acc[i][r] * p.alpha;   // 1 or a power of two: exact
-                    v = v + bs;
-                    if (p.res) v = v + p.res[(long)m * p.ldc + col];
-                    Cc[(long)m * p.ldc + col] = v;
-                }
-            }
-    }
-}
-
-IR_DEVINL double wave_sum_d(double v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-    return v;
+    if constexpr (AMODE == A_STEM)
+        run(StemA{.a = A, .M = p.M});
+    else if constexpr (AMODE == A_CONV3)   // cin is a multiple of BK: a k-tile never crosses a tap
+        run(NhwcA<BM, true>{.in = A, .H = p.H, .W = p.W, .cin = p.cin, .pitch = p.cin, .kw = 3, .stride = 1, .ph = 1, .pw = 1, .Ho = p.H, .Wo = p.W, .M = p.M, .K = p.K});
+    else
+        run(RowsA<BM, false>{.a = A, .lda = p.lda, .M = p.M, .K = p.K});
 }
 
 struct PatchArgs {
@@ -366,48 +278,6 @@ __global__ __launch_bounds__(TPB) void musiq_tokens_kernel(const float* __restri
     x[i] = e + semb[(long)s * C + c];
 }
 
-// LayerNorm of row blockIdx.x * 4 + wave: lane l sums columns l, l + 64, ... in order, the lanes fold in a fixed butterfly
-__global__ __launch_bounds__(TPB) void musiq_ln_kernel(const float* __restrict__ x, long rows, int C, const float* __restrict__ gamma, const float* __restrict__ beta,
-                                                       double eps, float* __restrict__ out) {
-    const int lane = threadIdx.x & 63;
-    const long row = (long)blockIdx.x * (TPB / 64) + (threadIdx.x >> 6);
-    if (row >= rows) return;   // uniform over the wave
-    const float* q = x + row * C;
-    double s = 0.0;
-    for (int c = lane; c < C; c += 64) s += (double)q[c];
-    const double mean = wave_sum_d(s) / (double)C;
-    double v = 0.0;
-    for (int c = lane; c < C; c += 64) {
-        const double d = (double)q[c] - mean;
-        v += d * d;
-    }
-    const double rstd = 1.0 / sqrt(wave_sum_d(v) / (double)C + eps);
-    for (int c = lane; c < C; c += 64) out[row * C + c] = (float)(((double)q[c] - mean) * rstd * (double)gamma[c] + (double)beta[c]);
-}
-
-// softmax of row blockIdx.x * 4 + wave of [rows][Tpad], in place over its first T columns; the columns behind them become 0
-__global__ __launch_bounds__(TPB) void musiq_softmax_kernel(float* __restrict__ s, long rows, int T, int Tpad) {
-    const int lane = threadIdx.x & 63;
-    const long row = (long)blockIdx.x * (TPB / 64) + (threadIdx.x >> 6);
-    if (row >= rows) return;   // uniform over the wave
-    float* q = s + row * Tpad;
-    float mx = -INFINITY;
-    for (int t = lane; t < T; t += 64) mx = fmaxf(mx, q[t]);
-    mx = wave_max(mx);
-    double sum = 0.0;
-    for (int t = lane; t < T; t += 64) sum += exp((double)q[t] - (double)mx);
-    sum = wave_sum_d(sum);
-    for (int t = lane; t < Tpad; t += 64) q[t] = t < T ? (float)(exp((double)q[t] - (double)mx) / sum) : 0.f;
-}
-
-// the exact GELU, in place
-__global__ __launch_bounds__(TPB) void musiq_gelu_kernel(float* __restrict__ x, long total) {
-    const long i = (long)blockIdx.x * TPB + threadIdx.x;
-    if (i >= total) return;
-    const double v = (double)x[i];
-    x[i] = (float)(0.5 * v * (1.0 + erf(v * 0.70710678118654752440)));
-}
-
 // one wave per image: the final LayerNorm of the class token (feat: the fp64 value rounded once), then head_w . it + head_b
 __global__ __launch_bounds__(64) void musiq_head_kernel(const float* __restrict__ x, long img_stride, int C, const float* __restrict__ gamma,
                                                         const float* __restrict__ beta, double eps, const float* __restrict__ hw, const float* __restrict__ hb, int n,
@@ -435,8 +305,6 @@ __global__ __launch_bounds__(64) void musiq_head_kernel(const float* __restrict_
 }
 
 size_t up256(size_t b) { return (b + 255) & ~(size_t)255; }
-unsigned blocks_of(long total, int per) { return (unsigned)((total + per - 1) / per); }
-
 GemmArgs gemm_args(const float* a, long lda, const float* b, long ldb, int M, int N, int K, const float* bias, const float* res, float* c, long ldc) {
     GemmArgs p{};
     p.a = a; p.lda = lda; p.b = b; p.ldb = ldb; p.Kb = K; p.M = M; p.N = N; p.K = K;
@@ -573,7 +441,7 @@ int ir_launch_musiq(const IrMusiqModel& m, const uint8_t* img, int rows, long pi
     const int pairs = n * m.heads, hd = C / m.heads;
     for (int l = 0; l < m.layers; ++l) {
         const IrMusiqBlock& b = m.blk[l];
-        hipLaunchKernelGGL(musiq_ln_kernel, dim3(blocks_of(R, TPB / 64)), dim3(TPB), 0, s, X, R, C, b.ln1g, b.ln1b, 1e-6, HN);
+        launch_ln(X, R, C, b.ln1g, b.ln1b, 1e-6, HN, s);
         GemmArgs p = gemm_args(HN, C, b.qkvw, 3 * C, (int)R, 3 * C, C, b.qkvb, nullptr, QKV, 3 * C);
         launch_gemm<A_ROWS, B_KN>(p, 1, s);
         for (int z0 = 0; z0 < pairs; z0 += pl.zc) {
@@ -583,7 +451,7 @@ int ir_launch_musiq(const IrMusiqModel& m, const uint8_t* img, int rows, long pi
             p.z0 = z0; p.zdiv = m.heads;
             p.a_s0 = p.b_s0 = (long)T * 3 * C; p.a_s1 = p.b_s1 = hd; p.c_sl = (long)T * pl.Tpad;
             launch_gemm<A_ROWS, B_NK>(p, z, s);
-            hipLaunchKernelGGL(musiq_softmax_kernel, dim3(blocks_of((long)z * T, TPB / 64)), dim3(TPB), 0, s, S, (long)z * T, T, pl.Tpad);
+            launch_softmax(S, (long)z * T, T, pl.Tpad, s);
             p = gemm_args(S, pl.Tpad, QKV + 2 * C, 3 * C, T, hd, pl.Tpad, nullptr, nullptr, O, C);   // p v; the padded columns of p are 0
             p.Kb = T;
             p.z0 = z0; p.zdiv = m.heads;
@@ -592,10 +460,10 @@ int ir_launch_musiq(const IrMusiqModel& m, const uint8_t* img, int rows, long pi
         }
         p = gemm_args(O, C, b.ow, C, (int)R, C, C, b.ob, X, X, C);
         launch_gemm<A_ROWS, B_KN>(p, 1, s);
-        hipLaunchKernelGGL(musiq_ln_kernel, dim3(blocks_of(R, TPB / 64)), dim3(TPB), 0, s, X, R, C, b.ln2g, b.ln2b, 1e-6, HN);
+        launch_ln(X, R, C, b.ln2g, b.ln2b, 1e-6, HN, s);
         p = gemm_args(HN, C, b.f1w, m.mlp, (int)R, m.mlp, C, b.f1b, nullptr, F, m.mlp);
         launch_gemm<A_ROWS, B_KN>(p, 1, s);
-        hipLaunchKernelGGL(musiq_gelu_kernel, dim3(blocks_of(R * m.mlp, TPB)), dim3(TPB), 0, s, F, R * m.mlp);
+        launch_gelu(F, R * m.mlp, s);
         p = gemm_args(F, m.mlp, b.f2w, C, (int)R, C, m.mlp, b.f2b, X, X, C);
         launch_gemm<A_ROWS, B_KN>(p, 1, s);
     }
