@@ -76,6 +76,9 @@ def parse_args():
     ap.add_argument("--maniqa_model", default=None, help="score MANIQA (no reference needed) of both output folders on the GPU (inference.py --maniqa_model: an .npz "
                     "in tools/evaluate_maniqa.py's names or pyiqa's .pth). Works with or without --gt and the other scorers; its column comes last. --image_size "
                     "must be above 224")
+    ap.add_argument("--topiq_model", default=None, help="score TOPIQ-NR (no reference needed) of both output folders on the GPU (inference.py --topiq_model: an .npz "
+                    "in tools/evaluate_topiq.py's names or pyiqa's .pth). Works with or without --gt and the other scorers; its column comes behind maniqa's "
+                    "and before dists's. --image_size below 16 leaves every file unscored")
     ap.add_argument("--maniqa_crops", default="uniform", choices=["uniform", "random"], help="inference.py's flag: pyiqa's grid, or draws from --maniqa_seed and the saved file's name")
     ap.add_argument("--maniqa_seed", type=int, default=None, help="with --maniqa_crops random: the seed (default 231)")
     ap.add_argument("--clip_bpe", default=None, help="with --clipiqa_model: the folder that holds CLIP's BPE table (inference.py --clip_bpe)")
@@ -126,6 +129,7 @@ def main():
         raise SystemExit("--png_decoder gpu decodes into the device's resize route, and this tool centre-crops every input on the host (as inference.py "
                          "--use_center_crop, where the flag is refused too): not offered (or give --center_crop gpu)")
     ext_out = cli.save_ext(args)
+    topiq_model = cli.load_topiq_model(args)
     niqe_params = cli.load_niqe_params(args)
     ilniqe_params = cli.load_ilniqe_params(args)
     clipiqa_model = cli.load_clipiqa_model(args)
@@ -133,7 +137,7 @@ def main():
     maniqa_model = cli.load_maniqa_model(args)
     dists_weights = cli.load_dists_weights(args)
     fid_weights, fid_stats = cli.load_fid(args)
-    noref = bool(niqe_params) or ilniqe_params is not None or clipiqa_model is not None or musiq_model is not None or maniqa_model is not None
+    noref = bool(niqe_params) or ilniqe_params is not None or clipiqa_model is not None or musiq_model is not None or maniqa_model is not None or topiq_model is not None
     recipe = geo = None
     if args.save_lq and not args.degrade:
         raise SystemExit("--save_lq writes the images --degrade synthesises: give --degrade as well")
@@ -177,7 +181,7 @@ def main():
         raise SystemExit("--lpips_alexnet needs --lpips_lin (the lpips linear heads)")
     with_lpips = {"lpips": True} if args.lpips_lin else {}
     with_niqe = {**({"niqe": True} if niqe_params else {}), **({"ilniqe": True} if ilniqe_params else {}), **({"clipiqa": True} if clipiqa_model else {}), **({"musiq": True} if musiq_model else {}),
-                 **({"maniqa": True} if maniqa_model else {}), **({"paired": bool(args.gt)} if noref else {}), **({"dists": True} if dists_weights else {})}
+                 **({"maniqa": True} if maniqa_model else {}), **({"paired": bool(args.gt)} if noref else {}), **({"dists": True} if dists_weights else {}), **({"topiq_nr": True} if topiq_model else {})}
     lookup = None
     if args.gt or noref:
         from instarevive_amd.metrics import GroundTruth, Report
@@ -202,6 +206,9 @@ def main():
         if maniqa_model:
             from instarevive_amd import maniqa
             maniqa.configure(m.model.ctx, maniqa_model, args.maniqa_crops, args.maniqa_seed)
+        if topiq_model:
+            from instarevive_amd import topiq
+            topiq.configure(m.model.ctx, topiq_model)
 
     def read(f):
         gt = np.ascontiguousarray(center_crop_arr(lookup.load(f), args.image_size)) if lookup else None
@@ -258,11 +265,12 @@ def main():
                              **({"jpeg": whole, "jpeg_quality": args.jpeg_quality, "jpeg_subsampling": args.jpeg_subsampling} if gpu_jpg else {}),
                              gt=cli.in_step(truths) if lookup else None, **with_lpips, **({"niqe": niqe_params} if niqe_params else {}), **({"ilniqe": ilniqe_params} if ilniqe_params else {}),
                              **({"clipiqa": True} if clipiqa_model else {}), **({"musiq": True} if musiq_model else {}), **({"dists": True} if dists_weights else {}),
+                             **({"topiq": True} if topiq_model else {}),
                              **({"fid": args.fid_resize} if fid_run else {}),
                              **({"maniqa": [[os.path.basename(out_name(args.output, args.input, f, ext_out)) for f in group] for group in batches]} if maniqa_model else {}),
                              **({"resize": cli.in_step(records)} if recipe or crop_gpu else {}),
                              **({"degrade": cli.in_step(dparams), "lq_sink": lq_images.append if args.save_lq else None} if recipe else {}))
-    no_score = {"niqe": 0, "ilniqe": 0, "clipiqa": 0, "musiq": 0, "maniqa": 0, "dists": 0}
+    no_score = {"niqe": 0, "ilniqe": 0, "clipiqa": 0, "musiq": 0, "maniqa": 0, "topiq_nr": 0, "dists": 0}
     for group, out in zip(batches, results):
         preds, stage1 = out[:2]
         if fid_run:   # every image is a whole crop saved as the device leaves it: every file enters the set
@@ -297,7 +305,7 @@ def main():
     if reports:
         for rep, folder in zip(reports, (args.output, cond_dir)):
             lines = rep.write()
-            print(f"[rank {rank}] {' / '.join(f for f, on in (('--gt', args.gt), ('--niqe_params', niqe_params), ('--ilniqe_params', ilniqe_params), ('--clipiqa_model', clipiqa_model), ('--musiq_model', musiq_model), ('--maniqa_model', maniqa_model)) if on)}: scored {len(rep.rows)} files of {folder}"
+            print(f"[rank {rank}] {' / '.join(f for f, on in (('--gt', args.gt), ('--niqe_params', niqe_params), ('--ilniqe_params', ilniqe_params), ('--clipiqa_model', clipiqa_model), ('--musiq_model', musiq_model), ('--maniqa_model', maniqa_model), ('--topiq_model', topiq_model)) if on)}: scored {len(rep.rows)} files of {folder}"
                   + (f" against {args.gt}" if args.gt else "") + f" -> {rep.path}")
             for ln in lines:
                 print(ln)
@@ -307,6 +315,8 @@ def main():
             print(f"[rank {rank}] --musiq_model: {no_score['musiq']} files were not scored (a resized side rounds to 0)")
         if no_score["maniqa"]:
             print(f"[rank {rank}] --maniqa_model: {no_score['maniqa']} files were not scored (MANIQA needs a short side above 224 pixels)")
+        if no_score["topiq_nr"]:
+            print(f"[rank {rank}] --topiq_model: {no_score['topiq_nr']} files were not scored (TOPIQ-NR needs 16 x 16 pixels)")
         if no_score["niqe"]:
             print(f"[rank {rank}] --niqe_params: {no_score['niqe']} files were not scored (NIQE needs 96 x 96 blocks and two complete feature rows)")
         if no_score["ilniqe"]:

@@ -56,7 +56,9 @@ enum { IR_STAGE_SWINIR = 0, IR_STAGE_VAE_ENCODE = 1, IR_STAGE_DIT = 2, IR_STAGE_
        IR_STAGE_ILNIQE = 27 /* ir_ilniqe_stats: h, w = the image size; the images of a batch share one workspace, so n only has to be >= 1;
                                depends on w alone (ctx may be NULL) */,
        IR_STAGE_ILNIQE_DFT = 26 /* ir_op_dft2_f64: h = w = size (252 or 504, 0 bytes for anything else); n only has to be >= 1; depends on the
-                                   size alone (ctx may be NULL) */ };
+                                   size alone (ctx may be NULL) */,
+       IR_STAGE_TOPIQ = 28 /* ir_topiq: n images, h, w = the scored rectangle; depends on the sizes and on the shape bound by ir_topiq_configure
+                              (0 for a context that is not configured and for a size ir_topiq refuses) */ };
 /* ir_pipeline flags */
 enum { IR_FLAG_NO_PREPROCESS = 1, IR_FLAG_TILED = 2, IR_FLAG_FIX_WAVELET = 4, IR_FLAG_FIX_ADAIN = 8,
        /* ir_pipeline only, needs ir_dit_control_configure: run the DiT step with the ControlNet-Half branch, condition latent
@@ -762,6 +764,36 @@ int ir_maniqa(ir_ctx* ctx, void* stream, const uint8_t* img, int rows, long pitc
               const int* origins_yx /* device, [n][crops][2] */, int crops,
               double* scores /* [n] */, float* feat_or_null /* [n][crops][tokens][embed / 2], the tokens the two heads read */,
               void* ws, size_t ws_bytes);
+
+/* TOPIQ-NR (the no-reference metric `topiq_nr` that the reference's evaluate_img.py names; pyiqa's CFANet in the topiq_nr configuration: a
+ * ResNet-50 trunk at the image's own size, no test-time resize) on the device; tools/evaluate_topiq.py states the definition as a torch model,
+ * and its float64 run is the model of this call. The input is x = (v / 255 - mean) / std per channel in fp32 through a 3 x 256 table
+ * (ir_topiq_input_table, host only, no context), padding 0 in that domain. Exact fp32 on the fp32-input MFMA with fp64 LayerNorm / softmax
+ * sums, fp64 pooling and position table, and an fp64 tail from the token mean on; no floating-point atomics: a call gives the same bits twice
+ * and at every place in a batch.
+ * ir_topiq_configure binds fp32 tensors uploaded with ir_upload under these names (L = 1 .. 4, B = 0 .. depths[L - 1] - 1, I = 0 .. 4,
+ * K = 0 .. 3; C = width, 4, 8, 16, 32 x width for I = 0 .. 4; D = dim):
+ *   topiq.trunk.conv1.weight [width][3][7][7], topiq.trunk.bn1.{weight,bias,running_mean,running_var};
+ *   topiq.trunk.layerL.B.conv{1,2,3}.weight, topiq.trunk.layerL.B.bn{1,2,3}.*, topiq.trunk.layerL.0.downsample.{0.weight,1.*};
+ *   topiq.gate.I.split.{weight [2 C][C][1][1], bias}, topiq.gate.I.conv1.* [64][C][1][1], topiq.gate.I.conv2.* [64][64][3][3],
+ *   topiq.gate.I.conv3.* [1][64][3][3]; topiq.reduce.I.{weight [D][C][1][1], bias};
+ *   topiq.sa.I.*, topiq.ca.K.*, topiq.pool.*: attn.in_proj_weight [3 D][D], attn.in_proj_bias, attn.out_proj.{weight,bias},
+ *   linear1.{weight [ffn][D], bias}, linear2.*, norm1.*, norm2.* (and norm3.* for ca);
+ *   topiq.score.{0,3}.{weight,bias} [D], topiq.score.{1,4}.{weight [D][D], bias}, topiq.score.6.{weight [1][D], bias [1]};
+ *   topiq.h_emb [1][D / 2][32][1], topiq.w_emb [1][D / 2][1][32].
+ * width (64 in the product) is a multiple of 4, dim a multiple of 8 up to 2048, dim / heads and ffn multiples of 4. A missing tensor or another
+ * size is refused with -2 and ir_last_error naming it; the earlier binding stays released. The binding holds copies: later uploads under
+ * these names do not change it.
+ * ir_topiq scores the top-left h x w of each of the n images of [n][rows][pitch] bytes (RGB8, addressed as ir_clipiqa addresses them):
+ * scores[n] (device doubles), and when given feat [n][dim] (the token mean the score head reads) and level_means [n][5][dim] (the token mean
+ * of each level after its encoder layer). Asynchronous on `stream`, no allocation, no synchronisation (capturable). ws: 256-byte aligned, at
+ * least ir_workspace_bytes(ctx, IR_STAGE_TOPIQ, n, h, w, 0, 0, 0) bytes. Returns -1 (nothing launched, nothing written) for a null pointer,
+ * n < 1, h or w below 16, h > rows, pitch < 3 w, misaligned outputs, a short or misaligned workspace or more than one call takes, and -13
+ * for a context without ir_topiq_configure. */
+int ir_topiq_input_table(float* tab768);
+int ir_topiq_configure(ir_ctx* ctx, const int depths[4], int width, int dim, int heads, int ffn);
+int ir_topiq(ir_ctx* ctx, void* stream, const uint8_t* img, int rows, long pitch, int n, int h, int w, double* scores /* [n] */,
+             float* feat_or_null /* [n][dim] */, float* level_means_or_null /* [n][5][dim] */, void* ws, size_t ws_bytes);
 
 /* Low-quality inputs from ground truth on the device: the first-order degradation of the reference's dataset/codeformer.py:140-163 and
  * tools/lq.py - a K x K blur, a bilinear downsample, Gaussian noise, a JPEG round trip, a bilinear resize back - without OpenCV and without

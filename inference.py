@@ -156,6 +156,11 @@ def parse_args() -> Namespace:
                         ".npz in that file's names, or pyiqa's .pth state dict. Works with or without --gt and the other scorers: the column "
                         "`maniqa` and the line `maniqa: x.xxxxx` come last. Which files are scored follows --gt's rule; files with a short side of "
                         "224 or less are counted as not scored. Costs about as much as the network's own step (20 crops through a ViT-B/8)")
+    parser.add_argument("--topiq_model", type=str, default=None, help="score TOPIQ-NR, the no-reference metric `topiq_nr` that the reference's evaluate_img.py names, on the "
+                        "GPU (ir_topiq; the definition of tools/evaluate_topiq.py, i.e. pyiqa's CFANet with a ResNet-50 trunk at the image's own size, in exact "
+                        "fp32). FILE is an .npz in that file's names, or pyiqa's .pth state dict. Works with or without --gt and the other scorers: the column "
+                        "`topiq_nr` and the line `topiq_nr: x.xxxxx` come behind maniqa's and before dists's. Which files are scored follows --gt's rule; "
+                        "files with a side below 16 are counted as not scored. Not offered with --shard_tiles")
     parser.add_argument("--maniqa_crops", type=str, default="uniform", choices=["uniform", "random"], help="with --maniqa_model: where the 20 crops lie. uniform "
                         "(default): pyiqa's grid. random: drawn from --maniqa_seed and the saved file's name (as tools/evaluate_maniqa.py draws them for that file), whatever the batch size, worker "
                         "count or rank")
@@ -460,6 +465,22 @@ def load_maniqa_model(args: Namespace):
         raise SystemExit(f"--maniqa_model {args.maniqa_model}: {e}")
 
 
+def load_topiq_model(args: Namespace):
+    """--topiq_model: the TOPIQ-NR model, read before any other model is touched; a file that is missing or holds anything else ends the run with the
+    loader's message. Not offered with --shard_tiles."""
+    if not getattr(args, "topiq_model", None):
+        return None
+    if getattr(args, "shard_tiles", False):
+        raise SystemExit("--topiq_model is not offered together with --shard_tiles (the assembled frame of the tile-sharded path is not scored on the device)")
+    from instarevive_amd import topiq
+    if not os.path.isfile(args.topiq_model):
+        raise SystemExit(f"--topiq_model {args.topiq_model}: no such file")
+    try:
+        return topiq.load_model(args.topiq_model)
+    except Exception as e:   # TopiqError is a ValueError; a file torch cannot unpickle raises its own kinds
+        raise SystemExit(f"--topiq_model {args.topiq_model}: {e}")
+
+
 def load_dists_weights(args: Namespace):
     """--dists_model [--dists_vgg]: the tensors ir_dists_configure binds, read before any other model is touched. The flag alone (no --gt, no
     --degrade), with --shard_tiles, or with a file that is missing or holds anything else ends the run in one line."""
@@ -752,6 +773,7 @@ def main() -> None:
     check_center_crop(args)
     check_jpeg_decoder(args)
     check_png_decoder(args)
+    topiq_model = load_topiq_model(args)
     niqe_params = load_niqe_params(args)
     ilniqe_params = load_ilniqe_params(args)
     if ilniqe_params is not None and args.shard_tiles:
@@ -761,7 +783,7 @@ def main() -> None:
     maniqa_model = load_maniqa_model(args)
     dists_weights = load_dists_weights(args)
     fid_weights, fid_stats = load_fid(args)
-    noref = bool(niqe_params) or ilniqe_params is not None or clipiqa_model is not None or musiq_model is not None or maniqa_model is not None
+    noref = bool(niqe_params) or ilniqe_params is not None or clipiqa_model is not None or musiq_model is not None or maniqa_model is not None or topiq_model is not None
     if args.save_lq and not args.degrade:
         raise SystemExit("--save_lq writes the images --degrade synthesises: give --degrade as well")
     if args.degrade:
@@ -813,7 +835,7 @@ def main() -> None:
         report = Report(args.metrics_out or os.path.join(args.output, "metrics.csv" if world == 1 else f"metrics.rank{rank}.csv"),
                         **({"lpips": True} if args.lpips_lin else {}), **({"niqe": True} if niqe_params else {}), **({"ilniqe": True} if ilniqe_params else {}), **({"clipiqa": True} if clipiqa_model else {}),
                         **({"musiq": True} if musiq_model else {}), **({"maniqa": True} if maniqa_model else {}), **({"paired": bool(args.gt)} if noref else {}),
-                        **({"dists": True} if dists_weights else {}))
+                        **({"dists": True} if dists_weights else {}), **({"topiq_nr": True} if topiq_model else {}))
         if ilniqe_params:
             from instarevive_amd import ilniqe
             ilniqe.configure(m.model.ctx)
@@ -832,6 +854,9 @@ def main() -> None:
         if maniqa_model:
             from instarevive_amd import maniqa
             maniqa.configure(m.model.ctx, maniqa_model, args.maniqa_crops, args.maniqa_seed)
+        if topiq_model:
+            from instarevive_amd import topiq
+            topiq.configure(m.model.ctx, topiq_model)
     fid_run = None
     if fid_weights:
         from instarevive_amd import fid
@@ -934,7 +959,7 @@ def main() -> None:
     first = None    # (time, files) when the first result left the GPU: what follows is the steady state (no library / workspace warm-up in it)
     unscored = 0    # --gt / --niqe_params / --clipiqa_model / --musiq_model / --maniqa_model: files whose saved image is not the device's image
     # files below 96 pixels on an edge or without two complete feature rows; files below 32 pixels on an edge; files of which a resized side rounds to 0
-    no_score = {"niqe": 0, "ilniqe": 0, "clipiqa": 0, "musiq": 0, "maniqa": 0, "dists": 0}   # maniqa: files with a short side of 224 or less; dists: files below 16 x 16
+    no_score = {"niqe": 0, "ilniqe": 0, "clipiqa": 0, "musiq": 0, "maniqa": 0, "topiq_nr": 0, "dists": 0}   # topiq_nr: files with a side below 16; maniqa: files with a short side of 224 or less; dists: files below 16 x 16
     for out in process_stream(m.model, feed(), tiled=args.tiled, return_stage1=args.show_lq and not args.disable_preprocess_model,
                               fp8=args.fp8 != "off", png=in_step(rects) if gpu_png else None, png_wrap=False, png_runs=args.png_runs,
                               **({"jpeg": in_step(rects), "jpeg_quality": args.jpeg_quality, "jpeg_subsampling": args.jpeg_subsampling} if gpu_jpg else {}),
@@ -943,6 +968,7 @@ def main() -> None:
                               **({"niqe": niqe_params} if niqe_params else {}), **({"ilniqe": ilniqe_params} if ilniqe_params else {}),
                               **({"clipiqa": True} if clipiqa_model else {}),
                               **({"musiq": True} if musiq_model else {}), **({"maniqa": in_step(names)} if maniqa_model else {}),
+                              **({"topiq": True} if topiq_model else {}),
                               **({"dists": True} if dists_weights else {}),
                               **({"fid": args.fid_resize, "fid_rects": in_step(fid_sizes)} if fid_run else {}),
                               **({"niqe_rects": in_step(sizes)} if noref else {}),
@@ -990,7 +1016,7 @@ def main() -> None:
               f"encoder (their saved image is not the device's image; the same bytes)")
     if report:
         lines = report.write()
-        what = " / ".join(f for f, on in (("--gt", args.gt), ("--niqe_params", niqe_params), ("--ilniqe_params", ilniqe_params), ("--clipiqa_model", clipiqa_model), ("--musiq_model", musiq_model), ("--maniqa_model", maniqa_model)) if on)
+        what = " / ".join(f for f, on in (("--gt", args.gt), ("--niqe_params", niqe_params), ("--ilniqe_params", ilniqe_params), ("--clipiqa_model", clipiqa_model), ("--musiq_model", musiq_model), ("--maniqa_model", maniqa_model), ("--topiq_model", topiq_model)) if on)
         print(f"[rank {rank}] {what}: scored {len(report.rows)} files" + (f" against {args.gt}" if args.gt else "") + f" -> {report.path}")
         for ln in lines:
             print(ln)
@@ -1004,6 +1030,8 @@ def main() -> None:
             print(f"[rank {rank}] --musiq_model: {no_score['musiq']} of {pools.written} files were not scored (a resized side rounds to 0)")
         if no_score["maniqa"]:
             print(f"[rank {rank}] --maniqa_model: {no_score['maniqa']} of {pools.written} files were not scored (MANIQA needs a short side above 224 pixels)")
+        if no_score["topiq_nr"]:
+            print(f"[rank {rank}] --topiq_model: {no_score['topiq_nr']} of {pools.written} files were not scored (TOPIQ-NR needs 16 x 16 pixels)")
         if no_score["dists"]:
             print(f"[rank {rank}] --dists_model: {no_score['dists']} of {pools.written} files were not scored (DISTS is scored from 16 x 16 pixels)")
         if unscored:

@@ -29,6 +29,7 @@ SYMBOLS = [
     "ir_lpips_scale_table", "ir_lpips_configure", "ir_lpips", "ir_dists_scale_table", "ir_dists_configure", "ir_dists", "ir_fid_resize_plan_bytes", "ir_fid_resize_plan", "ir_fid_configure", "ir_fid_features", "ir_niqe_window", "ir_niqe_stats", "ir_ilniqe_plan_bytes", "ir_ilniqe_plan", "ir_ilniqe_configure", "ir_ilniqe_stats", "ir_op_dft2_f64", "ir_op_weibull_fit",
     "ir_clipiqa_scale_table", "ir_clipiqa_configure", "ir_clipiqa", "ir_musiq_layout", "ir_musiq_input_table", "ir_musiq_configure", "ir_musiq",
     "ir_maniqa_input_table", "ir_maniqa_crops", "ir_maniqa_configure", "ir_maniqa",
+    "ir_topiq_input_table", "ir_topiq_configure", "ir_topiq",
     "ir_degrade_qtables", "ir_degrade", "ir_degrade_chain",
     "ir_op_linear_ex", "ir_op_conv_ex", "ir_op_igemm_route", "ir_op_igemm_route_range",
 ]
@@ -46,6 +47,7 @@ STAGE_MUSIQ = 21
 STAGE_MANIQA = 22
 STAGE_DISTS = 23
 STAGE_FID = 24
+STAGE_TOPIQ = 28    # ir_topiq: h, w = the scored rectangle; 0 for a context that is not configured
 STAGE_ILNIQE = 27   # ir_ilniqe_stats: h, w = the image size
 STAGE_ILNIQE_DFT = 26   # h = w = size (252 | 504)
 STAGE_PNG_DECODE = 25   # h, w = the largest sides, flags = the largest stream_bytes, tile_size = span_bits
@@ -65,6 +67,7 @@ LPIPS_NOT_CONFIGURED = -12   # ir_lpips before ir_lpips_configure
 CLIPIQA_NOT_CONFIGURED = -13   # ir_clipiqa before ir_clipiqa_configure
 MUSIQ_NOT_CONFIGURED = -13     # ir_musiq before ir_musiq_configure
 MANIQA_NOT_CONFIGURED = -13    # ir_maniqa before ir_maniqa_configure
+TOPIQ_NOT_CONFIGURED = -13     # ir_topiq before ir_topiq_configure
 DISTS_NOT_CONFIGURED = -14     # ir_dists before ir_dists_configure
 FID_NOT_CONFIGURED = -14       # ir_fid_features before ir_fid_configure
 DISTS_CHANNELS = 1475          # 3 + 64 + 128 + 256 + 512 + 512: the channels of the six compared maps
@@ -296,6 +299,9 @@ def load_library():
     lib.ir_maniqa_crops.argtypes = [i, i, i, i, vp]
     lib.ir_maniqa_configure.argtypes = [vp, i, i, i, i, i, i, C.POINTER(C.c_int), i, i, i, i, C.c_float]
     lib.ir_maniqa.argtypes = [vp, vp, vp, i, C.c_long, i, i, i, vp, i, vp, vp, vp, sz]
+    lib.ir_topiq_input_table.argtypes = [vp]
+    lib.ir_topiq_configure.argtypes = [vp, C.POINTER(C.c_int), i, i, i, i]
+    lib.ir_topiq.argtypes = [vp, vp, vp, i, C.c_long, i, i, i, vp, vp, vp, vp, sz]
     lib.ir_degrade_qtables.argtypes = [i, vp, vp]
     lib.ir_degrade.argtypes = [vp, vp, vp, i, C.c_long, i, i, i, C.POINTER(DegradeParams), vp, vp, vp, sz]
     lib.ir_degrade_chain.argtypes = [vp, vp, vp, i, C.c_long, i, i, i, C.POINTER(Chain), vp, vp, vp, sz]

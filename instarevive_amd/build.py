@@ -11,16 +11,16 @@ from concurrent.futures import ThreadPoolExecutor
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(CSRC, "libinstarevive_hip.so")
-SOURCES = ["igemm.hip", "conv_s1.hip", "conv_s1_fp8.hip", "norm.hip", "attention.hip", "attn_d512.hip", "attn_fp8.hip", "attn_d512_fp8.hip", "swin_fused.hip", "elementwise.hip", "vae_io.hip", "t5.hip", "unet.hip", "png_encode.hip", "jpeg_encode.hip", "jpeg_decode.hip", "png_decode.hip", "resample.hip", "metrics.hip", "lpips.hip", "dists.hip", "fid.hip", "niqe.hip", "ilniqe.hip", "clipiqa.hip", "musiq.hip", "maniqa.hip", "degrade.hip", "degrade_chain.hip", "api.cpp", "api_image.cpp"]
+SOURCES = ["igemm.hip", "conv_s1.hip", "conv_s1_fp8.hip", "norm.hip", "attention.hip", "attn_d512.hip", "attn_fp8.hip", "attn_d512_fp8.hip", "swin_fused.hip", "elementwise.hip", "vae_io.hip", "t5.hip", "unet.hip", "png_encode.hip", "jpeg_encode.hip", "jpeg_decode.hip", "png_decode.hip", "resample.hip", "metrics.hip", "lpips.hip", "dists.hip", "fid.hip", "niqe.hip", "ilniqe.hip", "clipiqa.hip", "musiq.hip", "maniqa.hip", "topiq.hip", "degrade.hip", "degrade_chain.hip", "api.cpp", "api_image.cpp"]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++20", "-fPIC", "-ffp-contract=fast"] + os.environ.get("IR_EXTRA_HIPCC_FLAGS", "").split()
 # Flags of single files, behind FLAGS. niqe.hip: its order of operations is part of NIQE's definition (the sign of rounding noise decides counts),
 # and -ffp-contract=fast fuses multiplies and adds in the backend whatever `#pragma clang fp contract(off)` says - only the flag keeps them apart.
 # ilniqe.hip: as niqe.hip - its resize, windows and MSCN values have to equal the model's bits. clipiqa.hip: its fp64 tail and its fp32 epilogue (scale, shift, residual) are what the file says, separate multiplies and adds, for the same reason.
-# musiq.hip: as clipiqa.hip - its epilogue (alpha, bias, residual) and its fp64 sums are separate operations. maniqa.hip: likewise.
+# musiq.hip: as clipiqa.hip - its epilogue (alpha, bias, residual) and its fp64 sums are separate operations. maniqa.hip: likewise. topiq.hip: likewise, and its position table's fp64 bicubic has to equal the model's, operation for operation.
 # dists.hip: the L2 pool's squares and its 9-tap sum are separate fp32 operations in the order the model states.
 # fid.hip: Pillow's float resampling multiplies and adds in double separately, and the BatchNorm epilogue and the pools round every operation.
 # degrade.hip, degrade_chain.hip: their bytes are truncations and roundings of float results that have to equal the numpy model's, operation for operation.
-FILE_FLAGS = {"niqe.hip": ["-ffp-contract=off"], "ilniqe.hip": ["-ffp-contract=off"], "clipiqa.hip": ["-ffp-contract=off"], "musiq.hip": ["-ffp-contract=off"], "maniqa.hip": ["-ffp-contract=off"], "dists.hip": ["-ffp-contract=off"], "fid.hip": ["-ffp-contract=off"], "degrade.hip": ["-ffp-contract=off"],
+FILE_FLAGS = {"niqe.hip": ["-ffp-contract=off"], "ilniqe.hip": ["-ffp-contract=off"], "clipiqa.hip": ["-ffp-contract=off"], "musiq.hip": ["-ffp-contract=off"], "maniqa.hip": ["-ffp-contract=off"], "topiq.hip": ["-ffp-contract=off"], "dists.hip": ["-ffp-contract=off"], "fid.hip": ["-ffp-contract=off"], "degrade.hip": ["-ffp-contract=off"],
               "degrade_chain.hip": ["-ffp-contract=off"]}
 
 

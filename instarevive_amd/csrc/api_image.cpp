@@ -1,4 +1,4 @@
-// The image tools of the C ABI: PNG and JPEG encoding, Pillow's resampling, PSNR-Y / SSIM-Y, LPIPS, DISTS, FID's features, CLIP-IQA, MUSIQ, MANIQA, NIQE, IL-NIQE's DFT and Weibull fit and the two degradation paths. Each entry
+// The image tools of the C ABI: PNG and JPEG encoding, Pillow's resampling, PSNR-Y / SSIM-Y, LPIPS, DISTS, FID's features, CLIP-IQA, MUSIQ, MANIQA, TOPIQ-NR, NIQE, IL-NIQE's DFT and Weibull fit and the two degradation paths. Each entry
 // point checks its arguments and launches the kernels of its own .hip file; none of them runs a model stage, takes the workspace arena or is
 // profiled, so nothing here knows api.cpp's Run. Host code only, except for the tables the kernels read, which are computed here once.
 #include <math.h>
@@ -1081,6 +1081,173 @@ int ir_maniqa(ir_ctx* c, void* stream, const uint8_t* img, int rows, long pitch,
     return 0;
 }
 
+// ---------------------------------------------------------------- TOPIQ-NR (topiq.hip)
+int ir_topiq_input_table(float* tab) {
+    if (!tab) return -1;
+    ir_topiq_input_table_host(tab);
+    return 0;
+}
+
+int ir_topiq_configure(ir_ctx* c, const int* depths, int width, int dim, int heads, int ffn) {
+    if (!c || !depths) return fail(c, -1, "ir_topiq_configure: null argument");
+    int n_blocks = 0;
+    for (int l = 0; l < 4; ++l) {
+        if (depths[l] < 1) return fail(c, -1, "ir_topiq_configure: stage %d has %d blocks", l + 1, depths[l]);
+        n_blocks += depths[l];
+    }
+    if (n_blocks > IR_TOPIQ_MAX_BLOCKS) return fail(c, -1, "ir_topiq_configure: %d blocks, at most %d", n_blocks, IR_TOPIQ_MAX_BLOCKS);
+    if (width < 4 || width % 4 || width > 1024 || dim < 8 || dim % 8 || dim > IR_TOPIQ_MAX_DIM || heads < 1 || dim % heads || (dim / heads) % 4 || ffn < 4 || ffn % 4 ||
+        ffn > 65536)
+        return fail(c, -1, "ir_topiq_configure: unsupported model (width %d of 4, dim %d of 8 up to %d, %d heads of a multiple of 4, ffn %d of 4)", width, dim,
+                    IR_TOPIQ_MAX_DIM, heads, ffn);
+    HIPOK(c, hipSetDevice(c->device));
+    c->topiq.ok = false;
+    auto m = std::make_unique<IrTopiqModel>();
+    for (int l = 0; l < 4; ++l) m->depths[l] = depths[l];
+    m->width = width; m->dim = dim; m->heads = heads; m->ffn = ffn; m->n_blocks = n_blocks;
+    const int D = dim, GHID = IR_TOPIQ_GATE_HIDDEN;
+    struct Conv { std::string conv, bn; int cin, cout, ks, stride; IrTopiqConv* dst; };   // bn empty: conv + ".bias" is the shift
+    struct Vec { std::string name; size_t floats; const float** dst; };                  // copied as it is
+    struct Lin { std::string name; int rows, cols; const float** dst; };                 // [rows][cols] -> [cols][rows]
+    std::vector<Conv> convs;
+    std::vector<Vec> vecs;
+    std::vector<Lin> lins;
+    convs.push_back({"topiq.trunk.conv1", "topiq.trunk.bn1", 3, width, 7, 2, &m->stem});
+    int inplanes = width, bi = 0;
+    for (int l = 0; l < 4; ++l) {
+        const int planes = width << l;
+        for (int i = 0; i < depths[l]; ++i, ++bi) {
+            IrTopiqBlock& b = m->blocks[bi];
+            const int stride = (i == 0 && l > 0) ? 2 : 1;
+            b.has_down = i == 0;
+            const std::string base = fmt("topiq.trunk.layer%d.%d.", l + 1, i);
+            convs.push_back({base + "conv1", base + "bn1", inplanes, planes, 1, 1, &b.c1});
+            convs.push_back({base + "conv2", base + "bn2", planes, planes, 3, stride, &b.c2});
+            convs.push_back({base + "conv3", base + "bn3", planes, planes * 4, 1, 1, &b.c3});
+            if (b.has_down) convs.push_back({base + "downsample.0", base + "downsample.1", inplanes, planes * 4, 1, stride, &b.down});
+            inplanes = planes * 4;
+        }
+    }
+    auto attn = [&](const std::string& p, IrTopiqAttn& a, int norms) {
+        const float** ng[3] = {&a.n1g, &a.n2g, &a.n3g};
+        const float** nb[3] = {&a.n1b, &a.n2b, &a.n3b};
+        for (int j = 0; j < norms; ++j) {
+            vecs.push_back({fmt("%snorm%d.weight", p.c_str(), j + 1), (size_t)D, ng[j]});
+            vecs.push_back({fmt("%snorm%d.bias", p.c_str(), j + 1), (size_t)D, nb[j]});
+        }
+        vecs.push_back({p + "attn.in_proj_bias", (size_t)3 * D, &a.inb});
+        vecs.push_back({p + "attn.out_proj.bias", (size_t)D, &a.ob});
+        vecs.push_back({p + "linear1.bias", (size_t)ffn, &a.f1b});
+        vecs.push_back({p + "linear2.bias", (size_t)D, &a.f2b});
+        lins.push_back({p + "attn.in_proj_weight", 3 * D, D, &a.inw});
+        lins.push_back({p + "attn.out_proj.weight", D, D, &a.ow});
+        lins.push_back({p + "linear1.weight", ffn, D, &a.f1w});
+        lins.push_back({p + "linear2.weight", D, ffn, &a.f2w});
+    };
+    for (int i = 0; i < 5; ++i) {
+        IrTopiqGate& g = m->gate[i];
+        const int C = width << (i == 0 ? 0 : i + 1);
+        const std::string p = fmt("topiq.gate.%d.", i);
+        lins.push_back({p + "split.weight", 2 * C, C, &g.sw});
+        vecs.push_back({p + "split.bias", (size_t)2 * C, &g.sb});
+        lins.push_back({p + "conv1.weight", GHID, C, &g.w1});
+        vecs.push_back({p + "conv1.bias", (size_t)GHID, &g.b1});
+        convs.push_back({p + "conv2", "", GHID, GHID, 3, 1, &g.c2});
+        vecs.push_back({p + "conv3.bias", 1, &g.b3});
+        lins.push_back({fmt("topiq.reduce.%d.weight", i), D, C, &g.rw});
+        vecs.push_back({fmt("topiq.reduce.%d.bias", i), (size_t)D, &g.rb});
+        attn(fmt("topiq.sa.%d.", i), m->sa[i], 2);
+    }
+    for (int k = 0; k < 4; ++k) attn(fmt("topiq.ca.%d.", k), m->ca[k], 3);
+    attn("topiq.pool.", m->pool, 2);
+    static const int sidx[5] = {0, 1, 3, 4, 6};
+    for (int j = 0; j < 5; ++j) {
+        const size_t rows = sidx[j] == 6 ? 1 : D, cols = (sidx[j] == 0 || sidx[j] == 3) ? 1 : D;
+        vecs.push_back({fmt("topiq.score.%d.weight", sidx[j]), rows * cols, &m->sc[2 * j]});
+        vecs.push_back({fmt("topiq.score.%d.bias", sidx[j]), rows, &m->sc[2 * j + 1]});
+    }
+    vecs.push_back({"topiq.h_emb", (size_t)(D / 2) * IR_TOPIQ_EMB, &m->h_emb});
+    vecs.push_back({"topiq.w_emb", (size_t)(D / 2) * IR_TOPIQ_EMB, &m->w_emb});
+
+    auto tensor = [&](const std::string& name, size_t floats) { return exact_f32(c, "ir_topiq_configure", "the configured model's", name, floats); };
+    static const char* const bnv[4] = {".weight", ".bias", ".running_mean", ".running_var"};
+    // every tensor is looked up before anything is replaced
+    for (const Conv& s : convs) {
+        if (!tensor(s.conv + ".weight", (size_t)s.cout * s.cin * s.ks * s.ks)) return -2;
+        if (s.bn.empty()) {
+            if (!tensor(s.conv + ".bias", (size_t)s.cout)) return -2;
+        } else {
+            for (const char* v : bnv)
+                if (!tensor(s.bn + v, (size_t)s.cout)) return -2;
+        }
+    }
+    for (const Vec& v : vecs)
+        if (!tensor(v.name, v.floats)) return -2;
+    for (const Lin& l : lins)
+        if (!tensor(l.name, (size_t)l.rows * l.cols)) return -2;
+    for (int i = 0; i < 5; ++i)
+        if (!tensor(fmt("topiq.gate.%d.conv3.weight", i), (size_t)9 * GHID)) return -2;
+
+    std::vector<void*>& own = c->own[OWN_TOPIQ];
+    release_list(own);
+    HIPOK(c, hipDeviceSynchronize());
+    float tab[3 * 256];
+    ir_topiq_input_table_host(tab);
+    if (int e = own_copy(c, own, tab, sizeof tab, hipMemcpyHostToDevice, &m->tab)) return e;
+    std::vector<float> t;
+    for (const Conv& s : convs) {   // the repacked weights, and BatchNorm folded in fp64
+        if (int e = repacked_conv(c, tensor(s.conv + ".weight", (size_t)s.cout * s.cin * s.ks * s.ks), s.cin, s.cout, s.ks, t)) return e;
+        s.dst->cin = s.cin; s.dst->cout = s.cout; s.dst->ks = s.ks; s.dst->stride = s.stride;
+        if (int e = own_copy(c, own, t.data(), t.size() * 4, hipMemcpyHostToDevice, &s.dst->w)) return e;
+        if (s.bn.empty()) {
+            if (int e = own_copy(c, own, tensor(s.conv + ".bias", (size_t)s.cout), (size_t)s.cout * 4, hipMemcpyDeviceToDevice, &s.dst->shift)) return e;
+            continue;
+        }
+        std::vector<float> bn[4], sc(s.cout), sh(s.cout);
+        for (int k = 0; k < 4; ++k) {
+            bn[k].resize(s.cout);
+            HIPOK(c, hipMemcpy(bn[k].data(), tensor(s.bn + bnv[k], (size_t)s.cout), (size_t)s.cout * 4, hipMemcpyDeviceToHost));
+        }
+        for (int o = 0; o < s.cout; ++o) {   // scale = g / sqrt(var + eps), shift = b - mean scale, each rounded to fp32 once
+            const double scale = (double)bn[0][o] / sqrt((double)bn[3][o] + 1e-5);
+            sc[o] = (float)scale;
+            sh[o] = (float)((double)bn[1][o] - (double)bn[2][o] * scale);
+        }
+        if (int e = own_copy(c, own, sc.data(), sc.size() * 4, hipMemcpyHostToDevice, &s.dst->scale)) return e;
+        if (int e = own_copy(c, own, sh.data(), sh.size() * 4, hipMemcpyHostToDevice, &s.dst->shift)) return e;
+    }
+    for (const Vec& v : vecs)
+        if (int e = own_copy(c, own, tensor(v.name, v.floats), v.floats * 4, hipMemcpyDeviceToDevice, v.dst)) return e;
+    for (const Lin& l : lins) {
+        t.assign((size_t)l.rows * l.cols, 0.f);
+        if (int e = transposed_into(c, tensor(l.name, (size_t)l.rows * l.cols), l.rows, l.cols, t, l.rows, 0)) return e;
+        if (int e = own_copy(c, own, t.data(), t.size() * 4, hipMemcpyHostToDevice, l.dst)) return e;
+    }
+    for (int i = 0; i < 5; ++i) {   // [1][64][3][3] -> [(ky, kx, c)]
+        if (int e = repacked_conv(c, tensor(fmt("topiq.gate.%d.conv3.weight", i), (size_t)9 * GHID), GHID, 1, 3, t)) return e;
+        if (int e = own_copy(c, own, t.data(), (size_t)9 * GHID * 4, hipMemcpyHostToDevice, &m->gate[i].w3)) return e;
+    }
+    m->ok = true;
+    c->topiq = *m;
+    ++c->generation;
+    return 0;
+}
+
+int ir_topiq(ir_ctx* c, void* stream, const uint8_t* img, int rows, long pitch, int n, int h, int w, double* scores, float* feat, float* level_means, void* ws,
+             size_t ws_bytes) {
+    if (!c || !img || !scores || !ws) return fail(c, -1, "ir_topiq: null argument");
+    if (int e = check_rect(c, "ir_topiq", "the coarsest grid needs 16 x 16", n, h, w, IR_TOPIQ_MIN_EDGE, {{rows, pitch}})) return e;
+    if (!c->topiq.ok) return fail(c, -13, "ir_topiq: TOPIQ not configured (ir_topiq_configure)");
+    IrTopiqPlan pl;
+    if (ir_topiq_plan(c->topiq, n, h, w, &pl)) return fail(c, -1, "ir_topiq: n %d of %d x %d is more than one call takes (2^31 output pixels, 65535 images)", n, h, w);
+    if (int e = check_ws(c, "ir_topiq", ws, ws_bytes, pl.total, 256)) return e;
+    if ((reinterpret_cast<uintptr_t>(scores) & 7) || (reinterpret_cast<uintptr_t>(feat) & 3) || (reinterpret_cast<uintptr_t>(level_means) & 3))
+        return fail(c, -1, "ir_topiq: scores / feat / level_means not aligned");
+    use_ctx(c);
+    if (ir_launch_topiq(c->topiq, img, rows, pitch, n, h, w, scores, feat, level_means, ws, (hipStream_t)stream)) return fail(c, -100, "ir_topiq: launch failed");
+    return 0;
+}
+
 // ---------------------------------------------------------------- NIQE's block statistics (niqe.hip)
 // the half-size fp64 luma plane of every image's scored rectangle
 static size_t niqe_workspace(int n, int h, int w) {
@@ -1291,12 +1458,13 @@ int ir_host::image_init(ir_ctx* c) {
     return upload(tab, sizeof tab, &c->niqe_tab);
 }
 
-// Sizes alone decide every answer except CLIP-IQA's, MUSIQ's and MANIQA's, which also take the configured model's shape: no context is needed for the others.
+// Sizes alone decide every answer except CLIP-IQA's, MUSIQ's, MANIQA's and TOPIQ's, which also take the configured model's shape: no context is needed for the others.
 bool ir_host::image_workspace(ir_ctx* c, int stage, int n, int h, int w, int flags, int tile_size, size_t* bytes) {
     const bool some = n >= 1 && h >= 1 && w >= 1;
     IrClipiqaPlan cp;
     IrMusiqPlan mp;
     IrManiqaPlan qp;
+    IrTopiqPlan tp;
     IrLpipsPlan lp;
     IrDistsPlan dp;
     IrFidPlan fp;
@@ -1313,6 +1481,7 @@ bool ir_host::image_workspace(ir_ctx* c, int stage, int n, int h, int w, int fla
         case IR_STAGE_MANIQA:   // flags: the crops per image, tile_size: the crops per pass (0: one, the least a call takes); h and w do not matter
             if (c && c->maniqa.ok && !ir_maniqa_plan(c->maniqa, n, flags, std::max(tile_size, 1), &qp)) *bytes = qp.total;
             break;
+        case IR_STAGE_TOPIQ: if (c && c->topiq.ok && !ir_topiq_plan(c->topiq, n, h, w, &tp)) *bytes = tp.total; break;
         case IR_STAGE_LPIPS: if (!ir_lpips_plan(n, h, w, &lp)) *bytes = lp.total; break;
         case IR_STAGE_DISTS: if (!ir_dists_plan(n, h, w, &dp)) *bytes = dp.total; break;
         case IR_STAGE_FID: if (!ir_fid_plan(n, &fp)) *bytes = fp.total; break;

@@ -226,7 +226,7 @@ struct Profiler {
 };
 
 // the owner of each list of ir_ctx::own: the context itself, or the binding that a *_configure / set_* call replaces
-enum Own { OWN_CTX = 0, OWN_DIT_TABS, OWN_DIT_CTRL_TABS, OWN_DIT_PROMPT, OWN_T5, OWN_CLIP, OWN_LPIPS, OWN_CLIPIQA, OWN_MUSIQ, OWN_MANIQA, OWN_DISTS, OWN_FID, OWN_ILNIQE,
+enum Own { OWN_CTX = 0, OWN_DIT_TABS, OWN_DIT_CTRL_TABS, OWN_DIT_PROMPT, OWN_T5, OWN_CLIP, OWN_LPIPS, OWN_CLIPIQA, OWN_MUSIQ, OWN_MANIQA, OWN_DISTS, OWN_FID, OWN_ILNIQE, OWN_TOPIQ,
            OWN_UNET_TABS, OWN_UNET_CTX = OWN_UNET_TABS + 2, OWN_COUNT = OWN_UNET_CTX + 2 };   // + which: the two UNets' timestep tables / context K-V caches
 
 }  // namespace ir_host
@@ -282,6 +282,8 @@ struct ir_ctx {
     IrMusiqModel musiq;
     // ir_maniqa: the input table, the transposed linears, copies of the norm vectors, embeddings and relative-position tables (in OWN_MANIQA)
     IrManiqaModel maniqa;
+    // ir_topiq: the input table, the repacked convs with their folded BatchNorm, the transposed linears and copies of the norm vectors and embeddings (in OWN_TOPIQ)
+    IrTopiqModel topiq;
     // ir_dists: the two input tables, the repacked conv weights and copies of the biases, alpha and beta (in OWN_DISTS)
     IrDistsModel dists;
     // ir_fid_features: the repacked conv weights, the folded BatchNorm vectors and the byte table (in OWN_FID)

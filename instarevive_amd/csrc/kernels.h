@@ -542,6 +542,54 @@ int ir_maniqa_plan(const IrManiqaModel& m, int n, int crops, int per_pass, IrMan
 int ir_launch_maniqa(const IrManiqaModel& m, const uint8_t* img, int rows, long pitch, int n, int h, int w, const int* origins, int crops, double* scores,
                      float* feat, void* ws, const IrManiqaPlan& plan, hipStream_t s);
 
+// ---- TOPIQ-NR of uint8 images (topiq.hip)
+#define IR_TOPIQ_MAX_BLOCKS 64
+#define IR_TOPIQ_GATE_HIDDEN 64
+#define IR_TOPIQ_EMB 32
+#define IR_TOPIQ_MIN_EDGE 16
+#define IR_TOPIQ_MAX_DIM 2048
+void ir_topiq_input_table_host(float* tab768);
+// The bound model: every conv as [K padded to 32][cout] with K in (ky, kx, c) order and its folded BatchNorm (scale null: shift is the bias), every
+// linear and 1 x 1 conv of the head as [in][out] (q | k | v side by side as in_proj packs them), the gate's last conv as [(ky, kx, c)], the
+// score head's linears as they were uploaded ([out][in]: the fp64 tail reads rows).
+struct IrTopiqConv {
+    const float *w = nullptr, *scale = nullptr, *shift = nullptr;
+    int cin = 0, cout = 0, ks = 0, stride = 1;
+};
+struct IrTopiqBlock {
+    IrTopiqConv c1, c2, c3, down;
+    int has_down = 0;
+};
+struct IrTopiqAttn {
+    const float *n1g, *n1b, *n2g, *n2b, *n3g, *n3b, *inw, *inb, *ow, *ob, *f1w, *f1b, *f2w, *f2b;
+};
+struct IrTopiqGate {
+    const float *sw, *sb, *w1, *b1, *w3, *b3, *rw, *rb;   // splitconv [C][2 C], the gate's 1 x 1 [C][64], its last conv [576], dim_reduce [C][D]
+    IrTopiqConv c2;                                        // the gate's 3 x 3, 64 -> 64
+};
+struct IrTopiqModel {
+    bool ok = false;
+    int depths[4] = {}, width = 0, dim = 0, heads = 0, ffn = 0, n_blocks = 0;
+    const float* tab = nullptr;   // [3][256] input table
+    IrTopiqConv stem;
+    IrTopiqBlock blocks[IR_TOPIQ_MAX_BLOCKS];
+    IrTopiqGate gate[5] = {};
+    IrTopiqAttn sa[5] = {}, ca[4] = {}, pool = {};
+    const float *h_emb = nullptr, *w_emb = nullptr;
+    const float* sc[10] = {};   // score.0.{weight,bias}, score.1.*, score.3.*, score.4.*, score.6.*
+};
+// ir_topiq_plan: the workspace of a call, byte offsets - the trunk's five NHWC map slots as ir_clipiqa_plan has them, the gate's maps (x2, then x1
+// over it; the two hidden maps), the pooled map, the tokens of the five levels, and the transformer's arrays (two LayerNorm outputs, q | k | v,
+// the attention output, the FFN's hidden rows, the score matrices of as many (image, head) pairs as one launch takes). H x W: the feature maps,
+// TH x TW: the token grids. -1 below 16 x 16, for more than 65535 images or when a row count leaves an int.
+struct IrTopiqPlan {
+    int H[5], W[5], TH[5], TW[5];
+    size_t slot[5], ga, gh1, gh2, pooled, tok[5], hn, hm, qkv, o, f, s, total;
+};
+int ir_topiq_plan(const IrTopiqModel& m, int n, int h, int w, IrTopiqPlan* plan);
+int ir_launch_topiq(const IrTopiqModel& m, const uint8_t* img, int rows, long pitch, int n, int h, int w, double* scores, float* feat, float* level_means,
+                    void* ws, hipStream_t s);
+
 // ---- low-quality inputs from ground truth (degrade.hip)
 // One image: blur (K x K fp64 taps in device memory, K odd, at most IR_DEGRADE_MAX_KSIZE: the float halo tile of a 32 x 32 patch must fit in 64 KB
 // of LDS), bilinear to lh x lw, noise (or NULL), the JPEG round trip at q (0: none), bilinear back, bytes (norm: include/instarevive_hip.h's IR_DEGRADE_NORM_*). jpeg: NULL or lh x lw x 3 bytes behind

@@ -283,7 +283,9 @@ class Report:
     no-reference columns alone: `file,niqe`, `file,clipiqa`, `file,musiq`, `file,maniqa`, `file,niqe,clipiqa` and so on. HEADERS lists
     the headers without the MANIQA column, HEADERS_MANIQA those with it. dists=True (a paired report only) appends DISTS (dists.py) as the very
     last column and average line (`dists: %.5f`): the full order ends `...,musiq,maniqa,dists`; HEADERS_DISTS lists those headers. ilniqe=True puts
-    IL-NIQE (ilniqe.py) right behind NIQE's place (`...,niqe,ilniqe,clipiqa,...`, `ilniqe: %.5f`); a report without it is what it was."""
+    IL-NIQE (ilniqe.py) right behind NIQE's place (`...,niqe,ilniqe,clipiqa,...`, `ilniqe: %.5f`); a report without it is what it was.
+    topiq_nr=True puts TOPIQ-NR (topiq.py) behind MANIQA's place and before DISTS's (`...,musiq,maniqa,topiq_nr,dists`, `topiq_nr: %.5f`);
+    HEADERS_TOPIQ lists those headers, and a report without the column is what it was."""
     HEADER = "file,psnr_y,ssim_y"
     HEADER_LPIPS = HEADER + ",lpips"
     HEADER_NIQE = "file,niqe"
@@ -291,22 +293,25 @@ class Report:
                     if p != "file" or n or c or m)
     HEADERS_MANIQA = tuple(h + ",maniqa" for h in HEADERS + ("file",))
     HEADERS_DISTS = tuple(h + ",dists" for h in HEADERS + HEADERS_MANIQA if h.startswith("file,psnr_y,ssim_y"))
+    HEADERS_TOPIQ = tuple(h[:-len(",dists")] + ",topiq_nr,dists" if h.endswith(",dists") else h + ",topiq_nr" for h in HEADERS + HEADERS_MANIQA + HEADERS_DISTS + ("file",))
 
     def __init__(self, path: Optional[str] = None, lpips: bool = False, niqe: bool = False, paired: bool = True, clipiqa: bool = False,
-                 musiq: bool = False, maniqa: bool = False, dists: bool = False, ilniqe: bool = False):
-        self.ilniqe = bool(ilniqe)
+                 musiq: bool = False, maniqa: bool = False, dists: bool = False, ilniqe: bool = False, topiq_nr: bool = False):
+        self.ilniqe, self.topiq_nr = bool(ilniqe), bool(topiq_nr)
         self.path, self.rows, self.lpips, self.niqe, self.paired, self.clipiqa = path, [], bool(lpips), bool(niqe), bool(paired), bool(clipiqa)
         self.musiq, self.maniqa, self.dists = bool(musiq), bool(maniqa), bool(dists)
         if self.dists and not self.paired:
             raise MetricsError("Report: DISTS is a paired score; a report without paired scores cannot carry it")
-        if not self.paired and (self.lpips or not (self.niqe or self.ilniqe or self.clipiqa or self.musiq or self.maniqa)):
-            raise MetricsError("Report: a report without paired scores carries NIQE, CLIP-IQA, MUSIQ and / or MANIQA and nothing else")
+        if not self.paired and (self.lpips or not (self.niqe or self.ilniqe or self.clipiqa or self.musiq or self.maniqa or self.topiq_nr)):
+            raise MetricsError("Report: a report without paired scores carries NIQE, CLIP-IQA, MUSIQ, MANIQA and / or TOPIQ-NR and nothing else")
         self.keys = ((("psnr", "ssim") + (("lpips",) if self.lpips else ()) if self.paired else ()) + (("niqe",) if self.niqe else ()) + (("ilniqe",) if self.ilniqe else ())
-                     + (("clipiqa",) if self.clipiqa else ()) + (("musiq",) if self.musiq else ()) + (("maniqa",) if self.maniqa else ())
+                     + (("clipiqa",) if self.clipiqa else ()) + (("musiq",) if self.musiq else ()) + (("maniqa",) if self.maniqa else ()) + (("topiq_nr",) if self.topiq_nr else ())
                      + (("dists",) if self.dists else ()))
 
     def add(self, name: str, psnr: Optional[float] = None, ssim: Optional[float] = None, lpips: Optional[float] = None, niqe: Optional[float] = None,
-            clipiqa: Optional[float] = None, musiq: Optional[float] = None, maniqa: Optional[float] = None, dists: Optional[float] = None, ilniqe: Optional[float] = None) -> None:
+            clipiqa: Optional[float] = None, musiq: Optional[float] = None, maniqa: Optional[float] = None, dists: Optional[float] = None, ilniqe: Optional[float] = None, topiq_nr: Optional[float] = None) -> None:
+        if (topiq_nr is not None) != self.topiq_nr:
+            raise MetricsError("Report.add: a TOPIQ-NR value is needed by a report made with topiq_nr=True and by no other")
         if (ilniqe is not None) != self.ilniqe:
             raise MetricsError("Report.add: an IL-NIQE value is needed by a report made with ilniqe=True and by no other")
         if (lpips is not None) != self.lpips:
@@ -323,7 +328,7 @@ class Report:
             raise MetricsError("Report.add: a DISTS value is needed by a report made with dists=True and by no other")
         if (psnr is not None) != self.paired or (ssim is not None) != self.paired:
             raise MetricsError("Report.add: PSNR and SSIM are needed by a report with paired scores and by no other")
-        given = dict(psnr=psnr, ssim=ssim, lpips=lpips, niqe=niqe, ilniqe=ilniqe, clipiqa=clipiqa, musiq=musiq, maniqa=maniqa, dists=dists)
+        given = dict(psnr=psnr, ssim=ssim, lpips=lpips, niqe=niqe, ilniqe=ilniqe, clipiqa=clipiqa, musiq=musiq, maniqa=maniqa, topiq_nr=topiq_nr, dists=dists)
         self.rows.append((str(name),) + tuple(float(given[k]) for k in self.keys))
 
     def add_scores(self, name: str, scores: Sequence[float]) -> None:
@@ -334,9 +339,9 @@ class Report:
 
     def unscored(self, scores: Sequence[float]) -> Optional[str]:
         """For a score tuple in the report's own column order: the no-reference column whose value is NaN - the image has no such score -
-        "niqe" before "clipiqa" before "musiq" before "maniqa" - or "dists" behind them (a pair below 16 pixels on an edge); None when the tuple
+        "niqe" before "clipiqa" before "musiq" before "maniqa" before "topiq_nr" - or "dists" behind them (a pair below 16 pixels on an edge); None when the tuple
         can be added."""
-        for k in ("niqe", "ilniqe", "clipiqa", "musiq", "maniqa", "dists"):
+        for k in ("niqe", "ilniqe", "clipiqa", "musiq", "maniqa", "topiq_nr", "dists"):
             if k in self.keys and scores[self.keys.index(k)] != scores[self.keys.index(k)]:
                 return k
         return None
@@ -372,11 +377,11 @@ class Report:
 
 def read_report(path: str) -> dict:
     """{file: (psnr_y, ssim_y)} of a CSV that Report wrote; {file: (psnr_y, ssim_y, lpips)} of one with the LPIPS column; with the NIQE column
-    that value follows, with the CLIP-IQA, MUSIQ and MANIQA columns those values follow, with the DISTS column that value comes last; a `file,niqe` report gives {file: (niqe,)}."""
+    that value follows, with the CLIP-IQA, MUSIQ, MANIQA and TOPIQ-NR columns those values follow, with the DISTS column that value comes last; a `file,niqe` report gives {file: (niqe,)}."""
     import csv
     with open(path, newline="") as f:
         rows = list(csv.reader(f))
     head = [c for c in rows[0] if c != "ilniqe"] if rows else []   # the IL-NIQE column may stand in any report
-    if not rows or (",".join(head) not in Report.HEADERS + Report.HEADERS_MANIQA + Report.HEADERS_DISTS and rows[0] != ["file", "ilniqe"]):
+    if not rows or (",".join(head) not in Report.HEADERS + Report.HEADERS_MANIQA + Report.HEADERS_DISTS + Report.HEADERS_TOPIQ and rows[0] not in (["file", "ilniqe"], ["file", "ilniqe", "topiq_nr"])):
         raise MetricsError(f"{path}: not a metrics report")
     return {r[0]: tuple(float(v) for v in r[1:len(rows[0])]) for r in rows[1:]}

@@ -229,11 +229,11 @@ class _Batch:
     two streams and keeps the batch's events in `ready` (its uploads) and `done` (its downloads)."""
 
     def __init__(self, ctx, slot, tag, slots, shape, imgs, with_stage1, rects=None, records=None, dparams=None, gts=None, lpips=False, niqe=None,
-                 clipiqa=False, sizes=None, want_lq=False, prompts=(None, None), codec=None, png_runs=False, musiq=False, maniqa=False, dists=False, fid=None, fid_sizes=None, ilniqe=None):
+                 clipiqa=False, sizes=None, want_lq=False, prompts=(None, None), codec=None, png_runs=False, musiq=False, maniqa=False, dists=False, fid=None, fid_sizes=None, ilniqe=None, topiq=False):
         """The plan phase, host work only: every size is checked and every ground truth compared with its image's FINAL size, so a batch that
         does not fit raises ValueError before anything is launched for it; then the scorer slots are filled / planned - `scorers` holds them in
         the order of a score tuple: paired (metrics.ScoreSlot; with lpips it scores LPIPS as well, ir_lpips with the weights lpips.configure()
-        bound to the context), NIQE with `niqe` its parameters, IL-NIQE with `ilniqe` its template (ilniqe.configure() bound to the context), CLIP-IQA, MUSIQ, MANIQA (maniqa: True, or the images' names, which key random crops), and last DISTS (dists: ir_dists with the weights dists.configure() bound to the context; the paired slot queues it, metrics.DistsColumn
+        bound to the context), NIQE with `niqe` its parameters, IL-NIQE with `ilniqe` its template (ilniqe.configure() bound to the context), CLIP-IQA, MUSIQ, MANIQA (maniqa: True, or the images' names, which key random crops), TOPIQ-NR (topiq.configure() bound to the context), and last DISTS (dists: ir_dists with the weights dists.configure() bound to the context; the paired slot queues it, metrics.DistsColumn
         stands where its value is read) - and the images copied into page-locked memory: the staging input, or
         the decoded files (with their degrade parameters) into the ResizeSlot, whose bicubic chain then makes the staging input on the device.
         fid: None, or FID's resize mode - the batch's predictions (and its ground truth, when it has one) go through ir_fid_features into a
@@ -265,8 +265,8 @@ class _Batch:
                     raise ValueError("dists=True: no DISTS weights are bound to the context (instarevive_amd.dists.configure)")
             self.sc.fill(gts, lpips, copies, dists=bool(dists))
             self.scorers.append(self.sc)
-        if niqe is not None or ilniqe is not None or clipiqa or musiq or maniqa:
-            finals = final_sizes("niqe" if niqe is not None else "ilniqe" if ilniqe is not None else "clipiqa" if clipiqa else "musiq" if musiq else "maniqa", n, h, w, records, rects, sizes, gts)
+        if niqe is not None or ilniqe is not None or clipiqa or musiq or maniqa or topiq:
+            finals = final_sizes("niqe" if niqe is not None else "ilniqe" if ilniqe is not None else "clipiqa" if clipiqa else "musiq" if musiq else "maniqa" if maniqa else "topiq", n, h, w, records, rects, sizes, gts)
             if niqe is not None:
                 from .niqe import NiqeSlot
                 self.scorers.append(NiqeSlot.get(ctx, slot, tag))
@@ -289,6 +289,10 @@ class _Batch:
                 from .maniqa import ManiqaSlot
                 self.scorers.append(ManiqaSlot.get(ctx, slot, tag))
                 self.scorers[-1].plan(finals, copies, None if maniqa is True else list(maniqa))
+            if topiq:
+                from .topiq import TopiqSlot
+                self.scorers.append(TopiqSlot.get(ctx, slot, tag))
+                self.scorers[-1].plan(finals, copies)
         if gts is not None and dists:
             from .metrics import DistsColumn
             self.scorers.append(DistsColumn(self.sc))
@@ -435,7 +439,7 @@ def process(model, control_imgs: List[np.ndarray], strength: float, color_fix_ty
             fused: bool = True, graph: bool = False, return_stage1: bool = True, fp8: bool = False, png=None,
             resize=None, gt=None, lpips: bool = False, niqe=None, niqe_rects=None, clipiqa: bool = False, degrade=None,
             lq_sink=None, jpeg=None, jpeg_quality: int = 95, jpeg_subsampling=2, png_runs: bool = False, musiq: bool = False, maniqa=False, dists: bool = False, fid=None,
-            fid_rects=None, ilniqe=None) -> Tuple[List[np.ndarray], List[np.ndarray]]:
+            fid_rects=None, ilniqe=None, topiq: bool = False) -> Tuple[List[np.ndarray], List[np.ndarray]]:
     """test_scripts/inference.py:55-166. control_imgs: list of HWC uint8 RGB arrays of equal size (multiples of 64).
     Returns (preds, stage1_preds) as lists of HWC uint8 arrays (stage1_preds is empty with return_stage1=False, which skips its
     conversion and download).
@@ -489,6 +493,9 @@ def process(model, control_imgs: List[np.ndarray], strength: float, color_fix_ty
     the models' context, queued behind ir_musiq on the same final rectangles. True, or one name per image: with maniqa.configure(mode="random")
     an image's crop origins are drawn from the seed and its name (its row in the batch without names). Its value is the last of every tuple.
     An image whose short side is not above the crop (224) gets NaN.
+    topiq (fused form only; alone or with the others): score TOPIQ-NR as well - ir_topiq with the model instarevive_amd.topiq.configure() bound to
+    the models' context, queued behind ir_maniqa on the same final rectangles. Its value comes behind maniqa's and before dists's in every
+    tuple. An image with a side below 16 gets NaN.
     dists (with gt only): score DISTS as well - ir_dists with the weights instarevive_amd.dists.configure() bound to the models' context, queued
     behind ir_lpips on the same images. Its value is the very last of every tuple, behind maniqa's; a pair below 16 pixels on an edge gets NaN.
     fid (with or without gt): True / "clean" / "legacy" - the Inception-v3 features of FID (ir_fid_features with the weights
@@ -510,7 +517,7 @@ def process(model, control_imgs: List[np.ndarray], strength: float, color_fix_ty
         raise ValueError("process(degrade=...) needs resize=: the ground truth is degraded on the device input route")
     n, h, w = _batch_shape(control_imgs, resize)
     codec = _jpeg_codec(png, jpeg, jpeg_quality, jpeg_subsampling)
-    if (png is not None or jpeg is not None or resize is not None or gt is not None or niqe is not None or ilniqe is not None or clipiqa or musiq or maniqa) and not (fused and _fused_ok(model, preprocess_model, vae, disable_preprocess_model)):
+    if (png is not None or jpeg is not None or resize is not None or gt is not None or niqe is not None or ilniqe is not None or clipiqa or musiq or maniqa or topiq) and not (fused and _fused_ok(model, preprocess_model, vae, disable_preprocess_model)):
         raise ValueError("process(png=... / resize=... / gt=... / niqe=...) needs the fused form (instarevive_amd models sharing one context)")
     device = model.device
     acp = float(noise_scheduler.alphas_cumprod[400])
@@ -523,7 +530,7 @@ def process(model, control_imgs: List[np.ndarray], strength: float, color_fix_ty
         ctx = model.ctx
         batch = _Batch(ctx, 0, "sync", 1, (n, h, w), control_imgs, return_stage1, png if codec is None else jpeg, resize, degrade, gt, lpips, niqe,
                        clipiqa, niqe_rects, lq_sink is not None, codec=codec, png_runs=png_runs, musiq=musiq, maniqa=maniqa, dists=dists,
-                       fid=("clean" if fid is True else fid) or None, fid_sizes=fid_rects, ilniqe=ilniqe)
+                       fid=("clean" if fid is True else fid) or None, fid_sizes=fid_rects, ilniqe=ilniqe, topiq=bool(topiq))
         _prepare_fused(model, y, y_mask, h, w, tiled, tile_size, (vae, None if disable_preprocess_model else preprocess_model))
         flags = _pipeline_flags(model, color_fix_type, disable_preprocess_model, tiled) | (L.FLAG_GRAPH if graph else 0) | (L.FLAG_FP8 if fp8 else 0)
         batch.upload()
@@ -592,7 +599,7 @@ def process_stream(model, batches: Iterable[Sequence[np.ndarray]], color_fix_typ
                    png_wrap: bool = True, resize=None, gt=None, lpips: bool = False, niqe=None,
                    niqe_rects=None, clipiqa: bool = False, degrade=None, lq_sink=None, jpeg=None, jpeg_quality: int = 95,
                    jpeg_subsampling=2, png_runs: bool = False, musiq: bool = False, maniqa=False, dists: bool = False, fid=None,
-                   fid_rects=None, ilniqe=None) -> Iterator[Tuple[List[np.ndarray], List[np.ndarray]]]:
+                   fid_rects=None, ilniqe=None, topiq: bool = False) -> Iterator[Tuple[List[np.ndarray], List[np.ndarray]]]:
     """process() over a sequence of image batches with the transfers hidden: while batch i computes on the current stream, batch
     i+1 is uploaded and batch i-1 downloaded on a copy stream (two staging slots per batch shape). Yields process()'s result for
     every batch, in order. Needs the fused form (all models instarevive_amd objects on one context). fp8 as in process() (cfg-5:
@@ -640,6 +647,8 @@ def process_stream(model, batches: Iterable[Sequence[np.ndarray]], color_fix_typ
     its value comes behind clipiqa's.
     maniqa (alone or with the others): as in process() - ir_maniqa is queued behind ir_musiq on the same batches and rectangles, and its value comes
     last. True, or an iterable in step with the batches that gives each batch's list of names.
+    topiq (alone or with the others): as in process() - ir_topiq is queued behind ir_maniqa on the same batches and rectangles, and its value
+    comes behind maniqa's and before dists's.
     dists (with gt only): as in process() - the scored batches' tuples end with the DISTS value.
     fid: as in process() - a batch that enters the set yields the features dict as its last element. fid_rects: an iterable in step with the
     batches: per batch one (h, w) per image, or None for a batch that does not enter the set (its saved image is not the device's image);
@@ -665,7 +674,7 @@ def process_stream(model, batches: Iterable[Sequence[np.ndarray]], color_fix_typ
     if degrade_it is not None and resize_it is None:
         raise ValueError("process_stream(degrade=...) needs resize=: the ground truth is degraded on the device input route")
     gt_it = iter(gt) if gt is not None else None
-    noref = niqe is not None or ilniqe is not None or bool(clipiqa) or bool(musiq) or bool(maniqa)
+    noref = niqe is not None or ilniqe is not None or bool(clipiqa) or bool(musiq) or bool(maniqa) or bool(topiq)
     mq_it = iter(maniqa) if maniqa and maniqa is not True else None
     nq_it = iter(niqe_rects) if noref and niqe_rects is not None else None
     fid = ("clean" if fid is True else fid) or None
@@ -689,7 +698,7 @@ def process_stream(model, batches: Iterable[Sequence[np.ndarray]], color_fix_typ
         b = _Batch(ctx, slot, "stream", 2, _batch_shape(imgs, records), imgs, return_stage1, rects, records, dparams, gts, lpips,
                    niqe if with_nq else None, bool(clipiqa) and with_nq, sizes, lq_sink is not None, (by, bm), codec=codec, png_runs=png_runs, musiq=bool(musiq) and with_nq,
                    maniqa=(names if names is not None else True) if maniqa and with_nq else False, dists=dists,
-                   fid=fid if with_fid else None, fid_sizes=fsizes, ilniqe=ilniqe if with_nq else None)
+                   fid=fid if with_fid else None, fid_sizes=fsizes, ilniqe=ilniqe if with_nq else None, topiq=bool(topiq) and with_nq)
         with torch.cuda.stream(copy):
             b.ready = b.upload(copy, main)
         return b

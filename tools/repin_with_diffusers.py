@@ -47,6 +47,9 @@ random-initialised models of reduced width pin it exactly as the 4 GB checkpoint
     ILNIQE_templateModel.mat: the score of two images without flat areas to 1e-3 relative (pyiqa scales its input in fp32). A mismatch points
     at one of the choices docs/parity.md lists as unpinned: the fp32 input scaling, the padding of the derivative convolutions, the resize
     order, the plane order, the unbiased std of the Weibull start.
+16. pyiqa's TOPIQ-NR (the `create_metric('topiq_nr')` that evaluate_img.py keeps commented out) -> tools/evaluate_topiq.py on pyiqa's own weights,
+    read through PYIQA_KEYS: the score of two images to 1e-5 (the score is roughly 0 - 1; pyiqa runs fp32). A mismatch points at one of that
+    file's recollections: the key table, decoder_layer() (no self-attention), DEFAULT_HEADS, or a step docs/parity.md lists.
  6. ftfy.fix_text (diffusion/model/t5.py:118-124) -> instarevive_amd.captions.fix_text (deterministic steps + the restricted mojibake repair).
 
 The fixture holds inputs, state-dict checksums and the third party's outputs (data, not source); tests/test_oracle_golden.py picks
@@ -348,6 +351,41 @@ def pin_maniqa(out):
     return ok
 
 
+def pin_topiq(out):
+    """pyiqa's `topiq_nr` against tools/evaluate_topiq.py on the weights pyiqa itself loads (its network's state dict)."""
+    import importlib.util
+    import pyiqa
+    spec = importlib.util.spec_from_file_location("evaluate_topiq", os.path.join(ROOT, "tools", "evaluate_topiq.py"))
+    et = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(et)
+    metric = pyiqa.create_metric("topiq_nr", device="cpu")
+    net = metric.net
+    sd = {k: v.detach().float() for k, v in net.state_dict().items()}
+    heads = getattr(getattr(net, "attn_pool", None), "self_attn", None)
+    heads = getattr(heads, "num_heads", None)
+    import tempfile
+    try:
+        with tempfile.TemporaryDirectory() as tmp:   # through the .pth reader, as a user's file goes
+            torch.save(sd, os.path.join(tmp, "topiq.pth"))
+            model = et.load_model(os.path.join(tmp, "topiq.pth"), heads)
+    except et.TopiqError as ex:
+        print(f"  [16] evaluate_topiq refuses pyiqa's state dict: {ex}; it has e.g. {sorted(sd)[:5]}")
+        return False
+    print(f"  [16] pyiqa: heads {heads}; evaluate_topiq: {model['cfg']}")
+    rng = np.random.default_rng(19)
+    yy, xx = np.mgrid[0:288, 0:352].astype(np.float64)
+    base = np.stack([128 + 80 * np.sin(xx / 23) * np.cos(yy / 31), 128 + 70 * np.sin((xx + yy) / 41), 128 + 90 * np.cos(xx / 17 - yy / 29)], -1)
+    ok = True
+    for name, sigma in (("smooth", 2.0), ("noisy", 25.0)):
+        img = np.clip(np.rint(base + rng.normal(0, sigma, base.shape)), 0, 255).astype(np.uint8)
+        ref = float(metric(torch.from_numpy(img).permute(2, 0, 1)[None].float() / 255.0))
+        got = et.topiq(img, model)
+        print(f"  [16] pyiqa TOPIQ-NR ({name}) {ref:.6f} vs evaluate_topiq {got:.6f} (absolute {abs(got - ref):.2e})")
+        out[f"topiq_{name}"], out[f"topiq_{name}_ref"] = img, np.float64(ref)
+        ok = ok and abs(got - ref) <= 1e-5
+    return ok
+
+
 def pin_dists(out):
     """pyiqa's `dists` against tools/evaluate_pairs.py::DISTS on the weights pyiqa itself loads."""
     import pyiqa
@@ -512,7 +550,7 @@ def main():
                            ("pyiqa NIQE (item 8)", pin_niqe, ()), ("pyiqa CLIP-IQA (item 9)", pin_clipiqa, (a.clip_bpe,)),
                            ("OpenCV degradation steps (item 10)", pin_degrade, ()), ("pyiqa MUSIQ (item 11)", pin_musiq, ()),
                            ("pyiqa MANIQA (item 12)", pin_maniqa, ()), ("pyiqa DISTS (item 13)", pin_dists, ()), ("pytorch-fid / pyiqa FID (item 14)", pin_fid, ()),
-                           ("pyiqa IL-NIQE (item 15)", pin_ilniqe, ())):
+                           ("pyiqa IL-NIQE (item 15)", pin_ilniqe, ()), ("pyiqa TOPIQ-NR (item 16)", pin_topiq, ())):
         print(name)
         try:
             verdict[name] = fn(out, *args)
