@@ -42,6 +42,7 @@ def parse_args():
     ap.add_argument("--prompt_embeds", default=cli.DEFAULT_PROMPT)
     ap.add_argument("--caption_dir", default=None, help="per-image prompts: DIR/<input-relative path without extension>.npz, else DIR/<file stem>.npz "
                     "(caption_feature [1, T, 4096], optional attention_mask; the reference's caption files). Images without one get --prompt_embeds")
+    cli.add_text_prompt_flags(ap)   # --prompt, --captions, --t5 / --t5_pipeline, --prompt_max_length, --clean_captions, --save_captions: as in inference.py
     ap.add_argument("--device", default="cuda")
     ap.add_argument("--png_encoder", default="host", choices=["host", "gpu"], help="who compresses the PNGs of both output folders: the host (PIL, default) or "
                     "the GPU behind the network (inference.py --png_encoder: lossless, meant for photographs; flat content comes out larger than PIL's unless "
@@ -116,6 +117,7 @@ def main():
     from instarevive_amd.resample import ResizeJob, crop_geometry
     from instarevive_amd.utils import center_crop_arr, list_image_files
     args = parse_args()
+    cli.check_text_prompts(args)
     cli.check_save_format(args)
     crop_gpu = args.center_crop == "gpu"
     if args.jpeg_decoder == "gpu" and crop_gpu:
@@ -157,6 +159,8 @@ def main():
     rank, world, local = parallel.init_distributed()
     torch.cuda.set_device(local)
     m = cli.load_models(args, torch.device("cuda", local))
+    from instarevive_amd import text_prompts
+    text_caps = text_prompts.setup(args, m, torch.device("cuda", local), log=lambda t: print(f"[rank {rank}] {t}"), max_batch=max(args.batch_size, 1))
     cond_dir = args.cond_output or args.output.rstrip("/") + "-cond"
     fid_run = None
     if fid_weights:
@@ -172,7 +176,7 @@ def main():
     batches = [files[i:i + args.batch_size] for i in range(0, len(files), args.batch_size)]
     pools = cli.HostPools(cli.default_workers(int(os.environ.get("LOCAL_WORLD_SIZE", world))) if args.workers < 0 else args.workers)
 
-    caps = Captions(args.caption_dir, m.y, m.y_mask, args.input) if args.caption_dir else None
+    caps = Captions(args.caption_dir, m.y, m.y_mask, args.input) if args.caption_dir else text_caps   # --captions: the same per-batch path, prompts on the device
 
     reports, truths, records, dparams, lq_images = None, deque(), deque(), deque(), []
     if (args.lpips_lin or args.lpips_alexnet) and not args.gt:
@@ -293,6 +297,9 @@ def main():
                 pools.written -= 1   # a file counts by its results
         print(f"[rank {rank}] queued {len(group)} images ({group[0]} ...)")
     pools.drain()
+    if text_caps:
+        text_caps.finish()   # the device's status word: nothing outside the vocabulary or the cache reached it
+        print(f"[rank {rank}] --captions: {text_caps.encoded} captions were T5-encoded in the run" + (f", {len(text_caps.saved)} caption files written to {args.save_captions}" if args.save_captions else ""))
     print(f"[rank {rank}] saved {pools.written} files")
     if cli.jpeg_decoder_note(args):
         print(f"[rank {rank}] {cli.jpeg_decoder_note(args)}")

@@ -169,6 +169,37 @@ int ir_t5_configure(ir_ctx* ctx, int n_layers, int d_model, int heads, int d_kv,
  * reference's embedding lookup does (the producer runs once per prompt, off the image path). */
 int ir_t5_encode(ir_ctx* ctx, void* stream, const int32_t* ids, const float* key_mask, float* out, int b, int tokens, void* ws, size_t ws_bytes);
 
+/* ---- Prompts as text inside a run (no reference counterpart: the reference encodes captions offline, tools/extract_caption.py).
+ * ir_t5_encode_prompts is ir_t5_encode behind the network: the same arguments and the same launches in the same order, so `out` holds
+ * ir_t5_encode's bits. It is STREAM-ORDERED: it never waits on the host, copies nothing to the host and allocates nothing - the position-bias
+ * table `t5.bias.{tokens}` has to be uploaded beforehand (the call fails with -11 if it is not; it never uploads on first use). The caller
+ * validates the ids against the vocabulary before it uploads them. On the device the embedding lookup never reads outside the table whatever
+ * the ids are: an id outside [0, vocab) reads row 0 and sets bit IR_T5_STATUS_BAD_ID of the context's sticky status word, and the call still
+ * returns 0. ir_t5_status reads that word at the end of the run. */
+enum { IR_T5_STATUS_BAD_ID = 1 /* an id outside the vocabulary reached ir_t5_encode_prompts */,
+       IR_T5_STATUS_BAD_SLOT = 2 /* a slot >= n_slots reached ir_prompt_gather (it took the fixed prompt) */ };
+int ir_t5_encode_prompts(ir_ctx* ctx, void* stream, const int32_t* ids, const float* key_mask, float* out, int b, int tokens, void* ws, size_t ws_bytes);
+/* The sticky status word of ir_t5_encode_prompts / ir_prompt_gather: waits for `stream`, writes the word to *status (host) and, with clear != 0,
+ * resets it. Needs a configured T5 encoder. */
+int ir_t5_status(ir_ctx* ctx, void* stream, int* status, int clear);
+/* Bytes of device memory the encoder's tensors (`t5.*`, the position-bias tables included) hold in this context. */
+size_t ir_t5_resident_bytes(ir_ctx* ctx);
+/* Free every `t5.*` tensor of the context (waits for the device first); the encoder is "not configured" afterwards. Returns 0. */
+int ir_t5_release(ir_ctx* ctx);
+/* Store encoder output in a device-resident cache of encoded captions: src fp32 [b][tokens][dim] -> slots slot0 .. slot0 + b - 1 of
+ * cache [n_slots][tokens][dim], as fp16 (cache_fp16 != 0: rounded to nearest even, overflow to infinity, subnormals kept - the bits of torch's
+ * tensor.to(torch.float16), what the reference's npz producer saves) or as fp32 (a copy). mask_src fp32 [b][tokens] (NULL: ones) goes to
+ * cache_mask fp32 [n_slots][tokens] as it is. Stream-ordered; needs no context state (ctx only carries the error text). */
+int ir_prompt_cache_store(ir_ctx* ctx, void* stream, const float* src, const float* mask_src, void* cache, float* cache_mask, int cache_fp16,
+                          int n_slots, int slot0, int b, int tokens, int dim);
+/* Assemble the block ir_dit_set_prompts takes for a batch of n images in ONE launch: embeds_out fp32 [n][tokens][dim] = cache slot
+ * slots[i] widened (exact), bias_out fp32 [n][tokens] = that slot's mask row with its values as they are (the reference adds its 3-D mask to
+ * the scores; instarevive_amd/prompts.py); a negative slot takes fixed_embeds fp32 [tokens][dim] / fixed_mask fp32 [tokens]. slots: device
+ * int32 [n]. A slot >= n_slots reads nothing from the cache: it takes the fixed prompt and, when `status` (the device word of a configured T5
+ * context, taken from ctx; ignored when the encoder is not configured) exists, sets IR_T5_STATUS_BAD_SLOT. Stream-ordered. */
+int ir_prompt_gather(ir_ctx* ctx, void* stream, const void* cache, const float* cache_mask, int cache_fp16, int n_slots, const int32_t* slots,
+                     const float* fixed_embeds, const float* fixed_mask, float* embeds_out, float* bias_out, int n, int tokens, int dim);
+
 size_t ir_workspace_bytes(ir_ctx* ctx, int stage, int n, int h, int w, int flags, int tile_size, int tile_stride);
 
 /* preprocess_model(control)  — SwinIR.forward, diffusion/model/swinir.py:867-905 (inference.py:97). in/out [n,3,h,w], h,w % 64 == 0. */

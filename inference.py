@@ -69,6 +69,7 @@ def parse_args() -> Namespace:
     parser.add_argument("--caption_dir", type=str, default=None, help="per-image prompts (no reference flag: the evaluation loop's captions, "
                         "test_dmd_general.py:173-174): DIR/<input-relative path without extension>.npz, else DIR/<file stem>.npz (caption_feature "
                         "[1, T, 4096], optional attention_mask). Images without one get --prompt_embeds; every prompt needs the same T")
+    add_text_prompt_flags(parser)
     # extensions (defaults reproduce the reference's behaviour)
     parser.add_argument("--batch_size", type=int, default=1, help="consecutive files of equal network-input size per process() call")
     parser.add_argument("--shard_tiles", action="store_true", help="with --tiled under torchrun: spread the TILES of each image over the "
@@ -199,6 +200,20 @@ def parse_args() -> Namespace:
     parser.add_argument("--workers", type=int, default=-1, help="host threads that decode / resize the inputs and resize / PNG-encode the results "
                         "around the GPU (PIL releases the GIL there); -1 = this process's CPU share, 0 = everything on the main thread like the reference")
     return parser.parse_args()
+
+
+def add_text_prompt_flags(parser) -> None:
+    """--prompt, --captions and what goes with them (eval_batch.py takes the same ones): prompts as text, T5-encoded inside the run."""
+    from instarevive_amd.text_prompts import add_flags
+    add_flags(parser)
+
+
+def check_text_prompts(args: Namespace) -> None:
+    """The refusals around --prompt / --captions, one line each; before anything is loaded."""
+    from instarevive_amd.text_prompts import check_flags
+    msg = check_flags(args, DEFAULT_PROMPT)
+    if msg:
+        raise SystemExit(msg)
 
 
 def add_jpeg_flags(parser) -> None:
@@ -756,6 +771,9 @@ def load_models(args: Namespace, device: torch.device) -> SimpleNamespace:
     load_state_dict(m.preprocess_model, torch.load(args.swinir_ckpt, map_location="cpu"), strict=True)
     m.model.to(device)
     m.preprocess_model.to(device)
+    if getattr(args, "prompt", None) is not None:   # --prompt TEXT: text_prompts.setup() encodes the fixed prompt, no file is read
+        m.y = m.y_mask = None
+        return m
     prompt = torch.load(args.prompt_embeds, map_location="cpu")
     embeds = prompt["caption_embeds"]
     m.y = embeds.to(device, torch.float32).reshape(1, -1, embeds.shape[-1])
@@ -769,6 +787,7 @@ def main() -> None:
     from instarevive_amd.pipeline import HipTileEngine, process_stream
     from instarevive_amd.utils import list_image_files
     args = parse_args()
+    check_text_prompts(args)
     check_save_format(args)
     check_center_crop(args)
     check_jpeg_decoder(args)
@@ -804,6 +823,8 @@ def main() -> None:
     torch.cuda.set_device(local)
     device = torch.device("cuda", local)
     m = load_models(args, device)
+    from instarevive_amd import text_prompts
+    text_caps = text_prompts.setup(args, m, device, log=lambda t: print(f"[rank {rank}] {t}"), max_batch=max(args.batch_size, 1))
     if args.fp8 != "off":
         from instarevive_amd import _lib as L
         if args.shard_tiles:
@@ -893,7 +914,7 @@ def main() -> None:
     common = dict(color_fix_type=args.color_fix_type, disable_preprocess_model=args.disable_preprocess_model, tile_size=args.tile_size,
                   tile_stride=args.tile_stride, preprocess_model=m.preprocess_model, vae=m.vae, y=m.y, y_mask=m.y_mask,
                   noise_scheduler=m.noise_scheduler)
-    caps = None
+    caps = text_caps   # --captions: the same per-batch path as --caption_dir, with the prompts already on the device
     if args.caption_dir:
         from instarevive_amd.prompts import Captions
         caps = Captions(args.caption_dir, m.y, m.y_mask, args.input)
@@ -914,6 +935,8 @@ def main() -> None:
                 else:
                     pools.write_behind(write_job, job, preds[0], stage1[0], args)
         pools.drain()
+        if text_caps:
+            text_caps.finish()
         if gpu_png and rank == 0:
             print(f"[rank {rank}] --png_encoder gpu: {host_files} of {pools.written} files took the host encoder (not a plain crop of the prediction)")
         if gpu_jpg and rank == 0:
@@ -1005,6 +1028,9 @@ def main() -> None:
                 pools.write_behind(write_job, job, preds[k], stage1[k] if stage1 else None, args)
     pools.drain()
     t1 = time.perf_counter()
+    if text_caps:
+        text_caps.finish()   # the device's status word: nothing outside the vocabulary or the cache reached it
+        print(f"[rank {rank}] --captions: {text_caps.encoded} captions were T5-encoded in the run" + (f", {len(text_caps.saved)} caption files written to {args.save_captions}" if args.save_captions else ""))
     if jpeg_decoder_note(args):
         print(f"[rank {rank}] {jpeg_decoder_note(args)}")
     if png_decoder_note(args):

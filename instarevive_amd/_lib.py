@@ -32,11 +32,13 @@ SYMBOLS = [
     "ir_topiq_input_table", "ir_topiq_configure", "ir_topiq",
     "ir_degrade_qtables", "ir_degrade", "ir_degrade_chain",
     "ir_op_linear_ex", "ir_op_conv_ex", "ir_op_igemm_route", "ir_op_igemm_route_range",
+    "ir_t5_encode_prompts", "ir_t5_status", "ir_t5_resident_bytes", "ir_t5_release", "ir_prompt_cache_store", "ir_prompt_gather",
 ]
 
 SWIN_SHELL_HEAD, SWIN_SHELL_RSTB_TAIL, SWIN_SHELL_RECON = range(3)   # ir_op_swin_shell parts
 DIT_SHELL_TABLES, DIT_SHELL_EMBED, DIT_SHELL_CONTROL, DIT_SHELL_FINAL = range(4)   # ir_op_dit_shell parts
 TEXT_T5, TEXT_CLIP = range(2)   # ir_op_text_block encoders
+T5_STATUS_BAD_ID, T5_STATUS_BAD_SLOT = 1, 2   # bits of ir_t5_status
 TEXT_EMBED, TEXT_ATTN, TEXT_FFN, TEXT_FINAL = range(4)   # ir_op_text_block parts
 STAGE_SWINIR, STAGE_VAE_ENCODE, STAGE_DIT, STAGE_VAE_DECODE, STAGE_PIPELINE, STAGE_COLORFIX, STAGE_T5, STAGE_CLDM, STAGE_CLDM_PIPELINE, STAGE_CLIP_TEXT, STAGE_PNG, STAGE_RESAMPLE, STAGE_METRICS = range(13)
 STAGE_LPIPS = 13
@@ -162,6 +164,13 @@ def load_library():
     lib.ir_dit_set_prompt.argtypes = [vp, vp, vp, vp, i]
     lib.ir_t5_configure.argtypes = [vp, i, i, i, i, i, i]
     lib.ir_t5_encode.argtypes = [vp, vp, vp, vp, vp, i, i, vp, sz]
+    lib.ir_t5_encode_prompts.argtypes = [vp, vp, vp, vp, vp, i, i, vp, sz]
+    lib.ir_t5_status.argtypes = [vp, vp, C.POINTER(C.c_int), i]
+    lib.ir_t5_resident_bytes.argtypes = [vp]
+    lib.ir_t5_resident_bytes.restype = sz
+    lib.ir_t5_release.argtypes = [vp]
+    lib.ir_prompt_cache_store.argtypes = [vp, vp, vp, vp, vp, vp, i, i, i, i, i, i]
+    lib.ir_prompt_gather.argtypes = [vp, vp, vp, vp, i, i, vp, vp, vp, vp, vp, i, i, i]
     lib.ir_workspace_bytes.argtypes = [vp, i, i, i, i, i, i, i]
     lib.ir_workspace_bytes.restype = sz
     lib.ir_swinir_forward.argtypes = [vp, vp, vp, vp, i, i, i, vp, sz]
@@ -379,6 +388,11 @@ class Context:
                 self.check(-1, f"ir_drop_optional({fam})")
         for k, v in tensors.items():
             self.upload(k, v)
+
+    def forget_family(self, family):
+        """The host's bookkeeping after the library has freed a family's tensors (ir_t5_release): its names, and which model was bound."""
+        self._names = {n for n in self._names if not n.startswith(family + ".")}
+        self.__dict__.get("_bound", {}).pop(family, None)
 
     def has(self, name):
         return bool(self.lib.ir_has_tensor(self.h, name.encode()))

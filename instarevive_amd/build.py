@@ -11,7 +11,7 @@ from concurrent.futures import ThreadPoolExecutor
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(CSRC, "libinstarevive_hip.so")
-SOURCES = ["igemm.hip", "conv_s1.hip", "conv_s1_fp8.hip", "norm.hip", "attention.hip", "attn_d512.hip", "attn_fp8.hip", "attn_d512_fp8.hip", "swin_fused.hip", "elementwise.hip", "vae_io.hip", "t5.hip", "unet.hip", "png_encode.hip", "jpeg_encode.hip", "jpeg_decode.hip", "png_decode.hip", "resample.hip", "metrics.hip", "lpips.hip", "dists.hip", "fid.hip", "niqe.hip", "ilniqe.hip", "clipiqa.hip", "musiq.hip", "maniqa.hip", "topiq.hip", "degrade.hip", "degrade_chain.hip", "api.cpp", "api_image.cpp"]
+SOURCES = ["igemm.hip", "conv_s1.hip", "conv_s1_fp8.hip", "norm.hip", "attention.hip", "attn_d512.hip", "attn_fp8.hip", "attn_d512_fp8.hip", "swin_fused.hip", "elementwise.hip", "vae_io.hip", "t5.hip", "prompt_cache.hip", "unet.hip", "png_encode.hip", "jpeg_encode.hip", "jpeg_decode.hip", "png_decode.hip", "resample.hip", "metrics.hip", "lpips.hip", "dists.hip", "fid.hip", "niqe.hip", "ilniqe.hip", "clipiqa.hip", "musiq.hip", "maniqa.hip", "topiq.hip", "degrade.hip", "degrade_chain.hip", "api.cpp", "api_image.cpp"]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++20", "-fPIC", "-ffp-contract=fast"] + os.environ.get("IR_EXTRA_HIPCC_FLAGS", "").split()
 # Flags of single files, behind FLAGS. niqe.hip: its order of operations is part of NIQE's definition (the sign of rounding noise decides counts),
 # and -ffp-contract=fast fuses multiplies and adds in the backend whatever `#pragma clang fp contract(off)` says - only the flag keeps them apart.

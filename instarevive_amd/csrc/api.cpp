@@ -2262,7 +2262,7 @@ static int dit_entry_check(ir_ctx* c, const char* who, int n, int h, int w, bool
     return 0;
 }
 
-static void t5_run(Run& r, const int* ids, const float* key_mask, const float* bias, float* out, int B, int T);
+static void t5_run(Run& r, const int* ids, const float* key_mask, const float* bias, float* out, int B, int T, int* flag = nullptr);
 static void clip_text_run(Run& r, const int* ids, float* out, int B);
 static int stage_dispatch(ir_ctx* c, Run& r, int stage, int n, int h, int w, int flags, int tile_size, int tile_stride) {
     // dry-run bodies used by ir_workspace_bytes; pointers are fake and never dereferenced
@@ -2887,9 +2887,10 @@ static TextBufs text_bufs(Run& r, long BT, int D, int HD, int F, int gated, int 
     return b;
 }
 // The encoder in parts; t5_run() chains them, ir_op_text_block runs one at a time.
-static void t5_embed(Run& r, const int* ids, float* x, long BT) {
+// flag: the device word an id outside the vocabulary sets (null: the one ir_t5_encode checks and clears; ir_t5_encode_prompts has its own, sticky)
+static void t5_embed(Run& r, const int* ids, float* x, long BT, int* flag = nullptr) {
     T5Model& m = r.c->t5;
-    LAUNCH(r, PC_OTHER, 0.0, 0.0, ir_launch_t5_embed(ids, m.embed, x, BT, m.D, m.vocab, m.bad, r.s), "t5_embed");
+    LAUNCH(r, PC_OTHER, 0.0, 0.0, ir_launch_t5_embed(ids, m.embed, x, BT, m.D, m.vocab, flag ? flag : m.bad, r.s), "t5_embed");
 }
 static void t5_attn(Run& r, const T5Layer& Lw, float* x, const float* bias, const float* key_mask, const TextBufs& b, int B, int T) {
     T5Model& m = r.c->t5;
@@ -2911,13 +2912,13 @@ static void t5_final(Run& r, const float* x, float* out, long BT) {
     T5Model& m = r.c->t5;
     LAUNCH(r, PC_LAYERNORM, 0.0, 8.0 * BT * m.D, ir_launch_t5_rmsnorm(x, m.final_ln, nullptr, out, BT, m.D, 1e-6f, r.s), "t5_final_norm");
 }
-static void t5_run(Run& r, const int* ids, const float* key_mask, const float* bias, float* out, int B, int T) {
+static void t5_run(Run& r, const int* ids, const float* key_mask, const float* bias, float* out, int B, int T, int* flag) {
     T5Model& m = r.c->t5;
     const long BT = (long)B * T;
     const size_t mk = r.a.mark();
     float* x = r.a.alloc<float>(BT * m.D);
     const TextBufs b = text_bufs(r, BT, m.D, m.H * m.dk, m.F, 1, TEXT_BUFS_ATTN | TEXT_BUFS_FFN);
-    t5_embed(r, ids, x, BT);
+    t5_embed(r, ids, x, BT, flag);
     for (const T5Layer& Lw : m.layers) {
         t5_attn(r, Lw, x, bias, key_mask, b, B, T);
         t5_ffn(r, Lw, x, b, BT);
@@ -2951,7 +2952,7 @@ int ir_t5_configure(ir_ctx* c, int n_layers, int d_model, int heads, int d_kv, i
     if (!b.ok) return fail(c, -2, "ir_t5_configure: tensor %s", b.missing.c_str());
     release_list(c->own[OWN_T5]);
     if (dev_alloc(c, c->own[OWN_T5], (void**)&m.bad, 256)) return -100;
-    HIPOK(c, hipMemset(m.bad, 0, 4));
+    HIPOK(c, hipMemset(m.bad, 0, 256));   // [0]: ir_t5_encode's flag; [1], [2]: the sticky words of ir_t5_encode_prompts / ir_prompt_gather
     m.ok = true;
     c->t5 = m;
     ++c->generation;
@@ -2980,6 +2981,88 @@ int ir_t5_encode(ir_ctx* c, void* stream, const int32_t* ids, const float* key_m
     t5_run(r, ids, key_mask, (const float*)it->second.p, out, b, t);
     if (int rc = finish(r, c, ws_bytes)) return rc;
     return check_bad_ids(c, stream, c->t5.bad, "ir_t5_encode", c->t5.vocab);
+}
+
+// ---------------------------------------------------------------- prompts as text inside a run
+// ir_t5_encode's launches with the host wait taken out: the bad-id flag is a sticky device word of its own (m.bad[1]) that ir_t5_status reads.
+int ir_t5_encode_prompts(ir_ctx* c, void* stream, const int32_t* ids, const float* key_mask, float* out, int b, int t, void* ws, size_t ws_bytes) {
+    REQUIRE(c && c->t5.ok, "T5 encoder not configured");
+    REQUIRE(ids && out && b > 0 && t > 0 && t <= 512, "ir_t5_encode_prompts: bad argument (1 <= tokens <= 512)");
+    auto it = c->t.find(fmt("t5.bias.%d", t));
+    REQUIRE(it != c->t.end() && it->second.bytes >= (size_t)c->t5.H * t * t * 4, "ir_t5_encode_prompts: t5.bias table for this length not uploaded (upload it when the prompt source is set up)");
+    Run r = make_run(c, stream, ws, ws_bytes, false);
+    t5_run(r, ids, key_mask, (const float*)it->second.p, out, b, t, c->t5.bad + 1);
+    return finish(r, c, ws_bytes);
+}
+
+int ir_t5_status(ir_ctx* c, void* stream, int* status, int clear) {
+    REQUIRE(c && c->t5.ok, "T5 encoder not configured");
+    if (!status) return fail(c, -1, "ir_t5_status: bad argument");
+    HIPOK(c, hipSetDevice(c->device));
+    int w[2] = {0, 0};
+    HIPOK(c, hipMemcpyAsync(w, c->t5.bad + 1, sizeof w, hipMemcpyDeviceToHost, (hipStream_t)stream));
+    HIPOK(c, hipStreamSynchronize((hipStream_t)stream));
+    *status = (w[0] ? IR_T5_STATUS_BAD_ID : 0) | (w[1] ? IR_T5_STATUS_BAD_SLOT : 0);
+    if (clear && *status) {
+        HIPOK(c, hipMemsetAsync(c->t5.bad + 1, 0, sizeof w, (hipStream_t)stream));
+        HIPOK(c, hipStreamSynchronize((hipStream_t)stream));
+    }
+    return 0;
+}
+
+size_t ir_t5_resident_bytes(ir_ctx* c) {
+    size_t n = 0;
+    if (c)
+        for (const auto& kv : c->t)
+            if (kv.first.compare(0, 3, "t5.") == 0) n += (kv.second.bytes + 255) & ~(size_t)255;
+    return n;
+}
+
+int ir_t5_release(ir_ctx* c) {
+    if (!c) return fail(c, -1, "ir_t5_release: bad argument");
+    HIPOK(c, hipSetDevice(c->device));
+    HIPOK(c, hipDeviceSynchronize());   // nothing queued may still read them
+    c->t5.ok = false;
+    c->t5.layers.clear();
+    c->t5.bad = nullptr;
+    for (auto it = c->t.begin(); it != c->t.end();) {
+        if (it->first.compare(0, 3, "t5.") == 0) {
+            if (it->second.p) (void)hipFree(it->second.p);
+            it = c->t.erase(it);
+        } else {
+            ++it;
+        }
+    }
+    release_list(c->own[OWN_T5]);
+    ++c->generation;
+    return 0;
+}
+
+int ir_prompt_cache_store(ir_ctx* c, void* stream, const float* src, const float* mask_src, void* cache, float* cache_mask, int cache_fp16, int n_slots,
+                          int slot0, int b, int t, int dim) {
+    if (!c) return fail(c, -11, "null context");
+    if (!src || !cache || !cache_mask || b <= 0 || t <= 0 || dim <= 0 || (dim & 3))
+        return fail(c, -1, "ir_prompt_cache_store: bad argument (dim a multiple of 4)");
+    if (slot0 < 0 || n_slots <= 0 || (long)slot0 + b > n_slots)
+        return fail(c, -10, "ir_prompt_cache_store: slots %d .. %ld of a cache of %d", slot0, (long)slot0 + b - 1, n_slots);
+    HIPOK(c, hipSetDevice(c->device));
+    if (int e = ir_launch_prompt_cache_store(src, mask_src, cache, cache_mask, cache_fp16 != 0, slot0, b, t, dim, (hipStream_t)stream))
+        return fail(c, e, "prompt_cache_store failed (code %d)", e);
+    return 0;
+}
+
+int ir_prompt_gather(ir_ctx* c, void* stream, const void* cache, const float* cache_mask, int cache_fp16, int n_slots, const int32_t* slots,
+                     const float* fixed_embeds, const float* fixed_mask, float* embeds_out, float* bias_out, int n, int t, int dim) {
+    if (!c) return fail(c, -11, "null context");
+    if (!slots || !fixed_embeds || !fixed_mask || !embeds_out || !bias_out || n <= 0 || n > 65535 || t <= 0 || dim <= 0 || (dim & 3) || n_slots < 0 ||
+        (n_slots > 0 && (!cache || !cache_mask)))
+        return fail(c, -1, "ir_prompt_gather: bad argument (dim a multiple of 4, a fixed prompt, a cache for n_slots > 0)");
+    HIPOK(c, hipSetDevice(c->device));
+    int* bad_slot = c->t5.ok && c->t5.bad ? c->t5.bad + 2 : nullptr;
+    if (int e = ir_launch_prompt_gather(cache, cache_mask, cache_fp16 != 0, n_slots, slots, fixed_embeds, fixed_mask, embeds_out, bias_out, n, t, dim,
+                                        bad_slot, (hipStream_t)stream))
+        return fail(c, e, "prompt_gather failed (code %d)", e);
+    return 0;
 }
 
 // ---------------------------------------------------------------- OpenCLIP text tower (ControlLDM's cond_stage_model)

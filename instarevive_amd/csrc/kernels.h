@@ -224,6 +224,15 @@ int ir_launch_t5_rmsnorm(const float* x, const float* w, bf16_t* yb, float* yf, 
 int ir_launch_t5_attn(const bf16_t* qkv, const float* bias, const float* key_mask, bf16_t* out, int B, int T, int H, int dk, hipStream_t s);
 int ir_launch_t5_gated_gelu(const bf16_t* ab, bf16_t* out, long rows, int F, hipStream_t s);
 
+// ---- the cache of encoded captions behind ir_t5_encode_prompts (prompt_cache.hip)
+// src fp32 [b][T][D] -> cache slots slot0 .. slot0 + b - 1 (fp16, round to nearest even, or fp32); mask_src [b][T] (null: ones) -> cache_mask
+int ir_launch_prompt_cache_store(const float* src, const float* mask_src, void* cache, float* cache_mask, int fp16, int slot0, int b, int T, int D,
+                                 hipStream_t s);
+// image i of n: embeds_out [i][T][D] / bias_out [i][T] from cache slot slots[i], or from the fixed prompt for a slot outside [0, n_slots)
+// (a slot >= n_slots also sets *bad_slot when that is not null)
+int ir_launch_prompt_gather(const void* cache, const float* cache_mask, int fp16, int n_slots, const int* slots, const float* fixed_embeds,
+                            const float* fixed_mask, float* embeds_out, float* bias_out, int n, int T, int D, int* bad_slot, hipStream_t s);
+
 // ---- PNG encoding of uint8 results (png_encode.hip)
 // png_encode.hip: zlib streams of Paeth-filtered rows, one dynamic-Huffman block of literals per chunk of IR_PNG_ROWS rows (in the run mode, where shorter,
 // one block of literals and distance-1 matches). IR_PNG_ROWS is a build

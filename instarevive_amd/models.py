@@ -493,6 +493,17 @@ class Transformer2DModel(_DeviceModule):
         self._prompt_dev = (yd, bd)   # read by the queued projection: released (stream-ordered) when the next prompt replaces it
         self._prompt_key = None
 
+    def set_prompts_device(self, y, bias):
+        """Prompts that are on the device already (a text prompt source's gather): y fp32 [P, T, caption_dim] and additive bias fp32 [P, T], both
+        contiguous device tensors, straight into ir_dit_set_prompts - stream-ordered, no trip through the host. The tensors are kept until the
+        next prompt replaces them."""
+        self._ready()
+        if y.dtype != torch.float32 or bias.dtype != torch.float32 or y.ndim != 3 or tuple(bias.shape) != tuple(y.shape[:2]) or y.device != self.device:
+            raise ValueError("set_prompts_device: y fp32 [P, T, C] and bias fp32 [P, T] on the model's device")
+        self.ctx.check(self.ctx.lib.ir_dit_set_prompts(self.ctx.h, self.ctx.stream(), L.ptr(y), L.ptr(bias), y.shape[0], y.shape[1]), "ir_dit_set_prompts")
+        self._prompt_dev = (y, bias)
+        self._prompt_key = None
+
     def invalidate_prompt(self):
         """Forget the cached prompt: the next call projects encoder_hidden_states again even if it is the same tensor object."""
         self._prompt_key = None
@@ -719,6 +730,53 @@ class T5EncoderModel(_DeviceModule):
         self._bias_lengths = set()  # position-bias tables depend on the weights: rebuilt per sequence length after every upload
         self._mark_bound()
 
+    def ensure_bias(self, t):
+        """Upload the position-bias table of sequence length t (once per length and upload of the weights)."""
+        self._ready()
+        if t not in self._bias_lengths:
+            self._bias_lengths.add(t)
+            self.ctx.upload(f"t5.bias.{t}", W.t5_position_bias(self._sd["encoder.block.0.layer.0.SelfAttention.relative_attention_bias.weight"], t,
+                                                               self.cfg["buckets"], self.cfg["max_distance"]))
+
+    def prepare(self, batch, tokens):
+        """What a run needs before its first encode_prompts(batch, tokens) so that the call itself allocates nothing: the position-bias table and
+        the workspace."""
+        if not 1 <= tokens <= 512:
+            raise ValueError(f"the T5 encoder takes 1 .. 512 tokens, got {tokens}")
+        self.ensure_bias(tokens)
+        self.ctx.workspace(self.ctx.ws_bytes(L.STAGE_T5, batch, tokens, 0))
+
+    @torch.no_grad()
+    def encode_prompts(self, ids, mask, out):
+        """ir_t5_encode_prompts: ids int32 [b, T] / mask fp32 [b, T] / out fp32 [b, T, d_model], all on the device and contiguous. Stream-ordered:
+        no host wait, no check of the ids on the way (validate them on the host first; status() tells at the end of the run)."""
+        self._ready()
+        b, t = ids.shape
+        if ids.dtype != torch.int32 or mask.dtype != torch.float32 or out.dtype != torch.float32 or tuple(mask.shape) != (b, t) or \
+                tuple(out.shape) != (b, t, self.cfg["d_model"]):
+            raise ValueError("encode_prompts: ids int32 [b, T], mask fp32 [b, T], out fp32 [b, T, d_model]")
+        ws = self.ctx.workspace(self.ctx.ws_bytes(L.STAGE_T5, b, t, 0))
+        self.ctx.check(self.ctx.lib.ir_t5_encode_prompts(self.ctx.h, self.ctx.stream(), L.ptr(ids), L.ptr(mask), L.ptr(out), b, t, L.ptr(ws), ws.numel()),
+                       "ir_t5_encode_prompts")
+        return out
+
+    def status(self, clear=True):
+        """The sticky status word of encode_prompts / the prompt gather (bits L.T5_STATUS_*); waits for the stream."""
+        self._ready()
+        word = C.c_int(0)
+        self.ctx.check(self.ctx.lib.ir_t5_status(self.ctx.h, self.ctx.stream(), C.byref(word), int(clear)), "ir_t5_status")
+        return word.value
+
+    def resident_bytes(self):
+        return int(self.ctx.lib.ir_t5_resident_bytes(self.ctx.h)) if self.ctx is not None else 0
+
+    def release(self):
+        """Free the encoder's device memory (the state dict on the host goes too); the object cannot encode afterwards."""
+        if self.ctx is not None and self._is_bound():
+            self.ctx.check(self.ctx.lib.ir_t5_release(self.ctx.h), "ir_t5_release")
+            self.ctx.forget_family(self.FAMILY)
+        self._sd = None
+
     @torch.no_grad()
     def __call__(self, input_ids=None, attention_mask=None, **unused):
         self._ready()
@@ -726,11 +784,7 @@ class T5EncoderModel(_DeviceModule):
         if ids.ndim != 2 or ids.shape[1] > 512:
             raise ValueError(f"input_ids must be [B, T] with T <= 512, got {tuple(ids.shape)}")
         b, t = ids.shape
-        name = f"t5.bias.{t}"
-        if t not in self._bias_lengths:
-            self._bias_lengths.add(t)
-            self.ctx.upload(name, W.t5_position_bias(self._sd["encoder.block.0.layer.0.SelfAttention.relative_attention_bias.weight"], t,
-                                                     self.cfg["buckets"], self.cfg["max_distance"]))
+        self.ensure_bias(t)
         mask = None if attention_mask is None else attention_mask.to(self.device, torch.float32).contiguous()
         if mask is not None and tuple(mask.shape) != (b, t):
             raise ValueError("attention_mask must have the shape of input_ids")

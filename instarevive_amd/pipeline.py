@@ -719,12 +719,24 @@ def process_stream(model, batches: Iterable[Sequence[np.ndarray]], color_fix_typ
                 last_prompt = None
             model.set_prompt(y, y_mask)
             return
+        key = getattr(by, "text_prompt_key", None)
+        if key is not None:   # a batch that text_prompts.PromptSource.batch() marked: its prompts stay on the device. The key names their contents, so
+            # the two things the host route does by comparing tensors are done on the key: equal prompts as one slot, an unchanged batch sets nothing
+            if len(key) not in (1, n):
+                raise ValueError(f"process_stream: a batch of {n} images came with {len(key)} prompts (one, or one per image)")
+            if last_prompt is not None and last_prompt[0] is None and last_prompt[1] == key:
+                return
+            rows = 1 if len(set(key)) == 1 else len(key)
+            yd = by.detach().reshape(len(key), by.shape[-2], by.shape[-1])[:rows].contiguous()
+            model.set_prompts_device(yd, bm.detach().reshape(len(key), by.shape[-2])[:rows].contiguous())
+            last_prompt = (None, key)
+            return
         hy = by.detach().to("cpu", torch.float32)
         hy = hy.reshape(-1, hy.shape[-2], hy.shape[-1])
         hb = prompt_bias(bm, hy.shape[0], hy.shape[1])
         if hy.shape[0] not in (1, n):
             raise ValueError(f"process_stream: a batch of {n} images came with {hy.shape[0]} prompts (one, or one per image)")
-        if last_prompt is not None and torch.equal(last_prompt[0], hy) and torch.equal(last_prompt[1], hb):
+        if last_prompt is not None and last_prompt[0] is not None and torch.equal(last_prompt[0], hy) and torch.equal(last_prompt[1], hb):
             return
         model._set_prompt_rows(hy, hb, stream_ordered=True)
         last_prompt = (hy, hb)
